@@ -6,11 +6,16 @@ synthetic windows that is already resident in HBM: BASELINE.json configs[1]/[2] 
 (4 854 windows x 50 000 sites), 465 haplotypes, populations A = rows 0-139, B = rows 140-239 —
 computing pi, pi_A, pi_B, Dxy, Fst, S and Tajima's D for every window in the same pass.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 is launched by torch.distributed.run, one rank per GPU; every rank holds its own
 chromosome shard (weak scaling, no data-path collective) and the per-window records are
 all-gathered once per step over RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything
+else the benchmark measures or checks: the parity gate against the CPU oracle, `cpu_baseline`
+and the all-pairs point under `secondary` (--secondary: more of those).  --dump-outputs DIR
+writes the records of the last timed step as DIR/<field>.npy (float64, one value per window).
 """
 from __future__ import annotations
 
@@ -64,6 +69,26 @@ def host_cores():
     except (OSError, ValueError):
         pass
     return max(min(n, 16), 1)
+
+
+DUMP_MAX_BYTES = 64_000_000  # all files of --dump-outputs together, .npy headers included
+
+
+def dump_outputs(out_dir, records):
+    """--dump-outputs: the per-window records a caller of the timed path receives, one float64 array per field
+    (integer fields are exact in float64), plus `window_index` (which windows the arrays hold).  Above DUMP_MAX_BYTES a
+    fixed, seeded sample of windows is written instead of all of them."""
+    import numpy as np
+    names = records.dtype.names
+    idx = np.arange(len(records))
+    cap = (DUMP_MAX_BYTES - 256 * (len(names) + 1)) // (8 * (len(names) + 1))
+    if len(idx) > cap:
+        idx = np.sort(np.random.default_rng(20251031).choice(len(idx), cap, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "window_index.npy"), idx.astype(np.float64))
+    for name in names:
+        np.save(os.path.join(out_dir, f"{name}.npy"), records[name][idx].astype(np.float64))
+    log(f"[bench] wrote {len(names) + 1} arrays of {len(idx)} windows to {out_dir}")
 
 
 FP4_DENSE_PEAK_TFLOPS = 10000.0  # MI355X FP4 / FP6 dense MFMA peak (MI355X_MICROARCH.md: ~10 PF dense); 1 MAC = 2 FLOP
@@ -418,6 +443,8 @@ def run_config4(args, ctx, stream, dev, rank, world, backend, use_dist):
     for b in (0, 1):
         if args.steps > b:
             assert all_records(b).tobytes() == ref_all.tobytes(), f"rank {rank}: records of a timed step differ from the checked first step"
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        dump_outputs(args.dump_outputs, all_records((counter[0] - 1) & 1))
     per = [elapsed, kern_ms / max(launches, 1), float(bm.device_bytes), float(cnt)]
     if use_dist:
         t = torch.tensor(per, dtype=torch.float64, device=gdev)
@@ -473,16 +500,23 @@ def main():
     ap.add_argument("--genome-sites", type=int, default=3_100_000_000, help="--config4: sites of the whole genome (3.1 Gb = 186 GB at 465 haplotypes)")
     ap.add_argument("--c4-window", type=int, default=10000)
     ap.add_argument("--c4-step", type=int, default=5000)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gate against the CPU oracle before timing, `cpu_baseline` and the "
+                         "all-pairs point under `secondary` (each can be left out with --no-cpu-baseline / --no-secondary)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records of the last timed step as DIR/<field>.npy (float64, one value per window)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--secondary", action="store_true",
-                    help="also measure the variable-sites-only scan and the all-pairs mode on the compacted matrix (under "
+                    help="with --full: also measure the variable-sites-only scan and the all-pairs mode on the compacted matrix (under "
                          "`secondary`, never in `value`).  Off by default: the compacted scan launches the headline kernel's own "
                          "instantiation on another workload, which would pollute a rocprofv3 --stats average of the default command")
     ap.add_argument("--all-pairs-windows", type=int, default=4096, help="windows of the all-pairs point (one impop_pairwise_scan call)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the all-pairs point (run_tajd.sh's default chain on the MFMA path) the default command measures "
-                         "after the timed region")
+                    help="skip the all-pairs point (run_tajd.sh's default chain on the MFMA path) --full measures after the "
+                         "timed region")
     args = ap.parse_args()
+    if args.secondary and not args.full:
+        ap.error("--secondary adds to the measurements of --full; pass both")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -620,14 +654,17 @@ def main():
         assert allrec[rank * NW * 128: (rank + 1) * NW * 128] == mine, f"rank {rank}: gathered records differ from local ({what})"
         return mine
 
-    # ---- parity gate before timing (rank 0): GPU records vs the CPU oracle on sampled windows
-    step()
-    drain()
-    recs = np.frombuffer(bufs[0].cpu().numpy().tobytes(), dtype=impop_amd.STATS_DTYPE)
+    # ---- first step, checked before timing: its records are what every gathered buffer must hold (use_dist) and, with
+    # --full, rank 0's records vs the CPU oracle on sampled windows (parity gate)
+    recs = None
+    if use_dist or args.full:
+        step()
+        drain()
+        recs = np.frombuffer(bufs[0].cpu().numpy().tobytes(), dtype=impop_amd.STATS_DTYPE)
     if use_dist:
         check_gathered(0, "first step")
     cpu, first = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         from oracle import oracle as orc
         orc.build()
         ones = orc.pack_mask(np.ones(n, np.uint8))
@@ -691,10 +728,15 @@ def main():
                 "gather_exposed_ms_per_step_max": 0.0, "gather_issue_host_ms_per_step_max": 0.0,
                 "gather_bytes_per_rank": 0, "gathered_records_checked": False}
 
+    if rank == 0 and args.dump_outputs and args.steps > 0:
+        last = (counter[0] - 1) & 1
+        raw = gathered[last].cpu().numpy().tobytes() if use_dist else bufs[last].cpu().numpy().tobytes()
+        dump_outputs(args.dump_outputs, np.frombuffer(raw, dtype=impop_amd.STATS_DTYPE))
+
     secondary = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu, first = cpu_baseline(bm, windows, in_a, in_b)
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         secondary = secondary_points(ctx, bm, windows, in_a, in_b, recs, args.secondary, args.all_pairs_windows)
 
     if rank == 0:

@@ -1,5 +1,5 @@
 """GPU: bench.py keeps the driver's contract — one JSON line with the required keys, `roofline` and
-(when not disabled) `cpu_baseline` — at N = 1, and the N > 1 code path (process group, sharded windows,
+(with --full, when not disabled) `cpu_baseline` — at N = 1, and the N > 1 code path (process group, sharded windows,
 all-gather of records, MAX over ranks) runs with two ranks sharing the one GPU over gloo (rehearsal mode;
 the measured configuration is one rank per GPU over RCCL)."""
 import json
@@ -27,7 +27,7 @@ def _last_json(text):
 
 def test_bench_single_gpu_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--n-windows", "96",
-                        "--no-cpu-baseline", "--all-pairs-windows", "96"], capture_output=True, text=True, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--all-pairs-windows", "96"], capture_output=True, text=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr
     d = _last_json(r.stdout)
     for k in REQUIRED:
@@ -41,7 +41,7 @@ def test_bench_single_gpu_line():
     for k in RANK_KEYS:  # the fields a bad N-GPU number is diagnosed from are present at N = 1 too
         assert k in d["ranks"], k
     assert len(d["ranks"]["kernel_ms_avg_per_rank"]) == 1
-    # the default command also measures the reference's DEFAULT chain (run_tajd.sh: pica2 -t 0.999 -r 5 -> %.8f -> tj_d) on
+    # --full also measures the reference's DEFAULT chain (run_tajd.sh: pica2 -t 0.999 -r 5 -> %.8f -> tj_d) on
     # the all-pairs path, parity-gated against the oracle inside bench.py, with its own roofline block
     ap = d["secondary"]["all_pairs_mode"]
     assert "error" not in ap, ap
@@ -50,6 +50,36 @@ def test_bench_single_gpu_line():
     # ... and the dominant kernel alone from HIP events on its stream: shorter than the call, hence a higher fraction
     assert ap["roofline"]["gram_kernel_launches"] == 5 and 0 < ap["roofline"]["gram_kernel_ms_avg"] < ap["s_per_call"] * 1e3
     assert ap["roofline"]["gram_kernel_frac"] > ap["roofline"]["frac"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run times exactly --steps steps, measures nothing else (no oracle, no CPU baseline, no secondary points) and
+    with --dump-outputs writes the records of its last timed step, one float64 array per field; a second run on the same
+    arguments writes the same arrays (seeded inputs, deterministic kernels)."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        out = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2",
+                            "--n-windows", "96", "--dump-outputs", str(out)], capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = _last_json(r.stdout)
+        for key in REQUIRED:
+            assert key in d, key
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["ms_per_step"] > 0 and d["value"] > 0
+        assert abs(d["value"] - 96 / (d["ms_per_step"] / 1e3)) <= 1e-6 * d["value"]
+        assert d["cpu_baseline"] is None and d["secondary"] is None
+        assert "parity gate" not in r.stderr
+        names = sorted(p.name for p in out.iterdir())
+        assert "window_index.npy" in names and "pi.npy" in names and "fst.npy" in names and "tajima_d.npy" in names
+        arrs = {nm[:-4]: np.load(out / nm) for nm in names}
+        for nm, a in arrs.items():
+            assert a.dtype == np.float64 and a.shape == (96,), (nm, a.dtype, a.shape)
+        assert (arrs["n_sites"] == 50000).all() and (arrs["pi"] > 0).all()
+        dumps.append(arrs)
+    for nm in dumps[0]:
+        assert dumps[0][nm].tobytes() == dumps[1][nm].tobytes(), nm
 
 
 def test_bench_one_rank_rccl_gather():

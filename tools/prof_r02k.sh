@@ -7,8 +7,8 @@ python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "config5 or pairwise o
 tail -2 $O/pytest_subset.log
 python3 tools/bench_config5.py --out $O/config5.json > $O/config5.log 2>&1
 grep what $O/config5.log | cut -c1-120
-# the exact default bench command under the profiler (kernel stats), then the two PMC traffic passes
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -o p -- python3 bench.py > $O/bench_n1.json 2> $O/bench_stats.err
+# the full bench command under the profiler (kernel stats), then the two PMC traffic passes
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/bench_stats -o p -- python3 bench.py --full > $O/bench_n1.json 2> $O/bench_stats.err
 cat $O/bench_n1.json | cut -c1-400
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/bench_fetch -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_fetch.out 2> $O/bench_fetch.err
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/bench_write -o p -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_write.out 2> $O/bench_write.err
