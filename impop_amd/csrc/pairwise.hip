@@ -2,9 +2,7 @@
 // window, then the full pica2 / h-fst semantics (thresholds, rounding,
 // greedy grouping) on identities formed on the fly from the integer Gram matrix.
 //
-// This path is MFMA-bound, not HBM-bound.  Shipped Gram kernel: gram_fp4_kernel
-// (FP4 bit planes, further down); gram_mfma_kernel (int8 + look-up table) is its predecessor,
-// selectable with IMPOP_GRAM_MFMA=i8 for A/B measurements.
+// This path is MFMA-bound, not HBM-bound.  Gram kernel: gram_fp4_kernel (FP4 bit planes, below).
 #include <stdlib.h>
 #include <string.h>
 
@@ -17,232 +15,30 @@
 
 namespace impop {
 
-// ---- Gram kernel: int8 MFMA, register-only (no LDS, no barriers) ---------------------------
-// G[i][j] = sum_s x_i[s] x_j[s] as a dense contraction on the matrix cores: each lane expands the
-// bits of ITS rows to 0/1 bytes in registers and feeds v_mfma_i32_32x32x32_i8 (exact: int32
-// accumulation).  Design history, all measured on MI355X:
-//   * VALU AND + v_bcnt (128x128 tile, 8x8 register tile): v_bcnt_u32_b32 is a HALF-rate
-//     instruction on gfx950 (tools/micro/valu_rate.hip: 4.8 vs 2.55 cycles per wave-instruction),
-//     ceiling ~1e5 windows/s at n = 465, W = 50 000; reached 23 us/window.
-//   * int8 MFMA with bits expanded into LDS byte tiles: ds_write_b128 + one barrier per 64 sites
-//     dominate (LDS write path ~79 B/clk/CU); 9 us/window.
-//   * int8 MFMA, register-only, rows 1.6 MB apart (plain hap-major): every wave-load touched 32
-//     cache lines for 512 useful bytes and the address path, not the ALUs, set the pace; 9-11 us.
-//   * 64 x 128 per wave on a ROW-GROUP-BLOCKED operand (RB32, internal.h: one wave-load of a cell
-//     for 32 rows is contiguous): 6.4 us/window, MfmaUtil 59 %, VALU ~85 % busy (PMC).
-//   * this kernel: 96 x 96 per wave, diagonal tiles reuse A as B, no register copies.
-// One WAVE owns one 96 x 96 tile (3 x 3 MFMA tiles of 32 x 32 = 144 accumulator registers), which
-// still leaves room for TWO waves per SIMD (a lone wave issues one VALU instruction per ~8
-// cycles, two or more reach one per 2.6 / 4.8 cycles).  Lane l supplies row
-// (l & 31) of each 32-row group and the 16 sites [16 (l>>5), +16) of a 32-site k-step.  Expansion:
-// y = x & 0x0F0F and z = (x >> 4) & 0x0F0F hold the four nibbles as clean bytes, v_mul_u32_u24
-// with an SDWA byte select spreads one nibble per instruction (nibble * 0x204081: copies at bits
-// 0-3, 7-10, 14-17, 21-24, no carries) and one AND keeps bits 0, 8, 16, 24: 12 VALU ops per
-// fragment; 6 fragments per 9 MFMAs (off-diagonal), 3 per 6 (diagonal).  MFMA and VALU runs of one wave do not overlap unless finely
-// interleaved (tools/micro/mfma_rate.hip: 257 + 368 -> 589 cycles), hence the software pipeline
-// (expand step t+1 under the MFMAs of step t) and the sched_group_barrier issue pattern.
-// Both MFMA operands use the same (lane>>5, byte) -> site mapping, so the result does not depend
-// on the instruction's internal k order; C/D map: col = lane&31, row = (reg&3)+8(reg>>2)+4(lane>>5).
+// ---- Gram kernel on the FP4 matrix cores, straight from the raw bit planes (no table, no LDS) ------
+// G[i][j] = sum_s x_i[s] x_j[s] as a dense, exact contraction.  One task = one 96 x 96 tile pair (ti <= tj) of one window
+// (x one K-slice), owned by one WAVE: 3 x 3 MFMA tiles of 32 x 32 = 144 accumulator registers, which still leaves room for
+// TWO waves per SIMD (a lone wave issues one VALU instruction per ~8 cycles, two or more reach one per 2.6 / 4.8 cycles).
+// Diagonal tiles reuse A as B and compute only the 6 blocks on and above the block diagonal.
+// C/D map of a 32 x 32 block: col = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
 #ifndef IMPOP_GRAM_ABLATE
-#define IMPOP_GRAM_ABLATE 0  // timing-only ablation builds (tools/): bit 0 no lookups, bit 1 no global loads, bit 2 no MFMA
+#define IMPOP_GRAM_ABLATE 0  // timing-only ablation builds (tools/ablate_gram_fp4.sh): bit 0 no expansion VALU, bit 1 no global loads, bit 3 no result stores
 #endif
-constexpr int GT = 96;  // tile edge (haplotypes): 3 row groups of 32
+constexpr int GT = 96;  // tile edge (haplotypes): 3 row groups of 32 (pads 465 haplotypes to 480 instead of 512)
 
 struct GramWindow {
     uint64_t site_begin, site_end;
 };
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ uint32_t spread_byte0(uint32_t v, uint32_t k) {
-    uint32_t r;
-    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD"
-        : "=v"(r) : "v"(v), "v"(k));
-    return r;
-}
-__device__ __forceinline__ uint32_t spread_byte1(uint32_t v, uint32_t k) {
-    uint32_t r;
-    asm("v_mul_u32_u24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_1 src1_sel:DWORD"
-        : "=v"(r) : "v"(v), "v"(k));
-    return r;
-}
-__device__ __forceinline__ i32x4 expand16(uint32_t xs /* the lane's 16 bits in the low half */, uint32_t kmul) {
-    const uint32_t y = xs & 0x0F0Fu;         // nibbles 0, 2 as bytes 0, 1
-    const uint32_t z = (xs >> 4) & 0x0F0Fu;  // nibbles 1, 3 as bytes 0, 1
-    i32x4 r;
-    r.x = (int)(spread_byte0(y, kmul) & 0x01010101u);
-    r.y = (int)(spread_byte0(z, kmul) & 0x01010101u);
-    r.z = (int)(spread_byte1(y, kmul) & 0x01010101u);
-    r.w = (int)(spread_byte1(z, kmul) & 0x01010101u);
-    return r;
-}
-
-// One task = one 96 x 96 tile pair (ti <= tj) of one window (x one K-slice).  3 x 3 MFMA tiles of
-// 32 x 32 per wave (144 accumulators, two waves per SIMD).  Off-diagonal tiles: 6 fragment
-// expansions feed 9 MFMAs per 32-site step; diagonal tiles: B == A, so 3 expansions feed the 6
-// MFMAs on and above the block diagonal.  Measured motivation (rocprofv3 PMC on the 64 x 128
-// predecessor): MfmaUtil 59 %, VALU ~85 % busy, every issue pattern within 1 % => fewer
-// expansions per MFMA is the lever (96 also pads 465 haplotypes to 480 instead of 512).
-// Pipeline (no register copies): the two 64-site cells PA / PB alternate, fragments F / G alternate;
-// a cell is reloaded right after its last use, three steps before its next use.
-// Expansion by table: the 8 sites of one byte become 8 int8 through ONE conflict-free ds_read_b64.
-// The table is laid out [entry 0..255][lane slot 0..31] x 8 bytes (64 KB per workgroup): a lane only
-// ever reads its own slot column, so the 32 lanes of a half-wave always hit 32 different bank
-// pairs whatever their entries are.  The LDS address (entry << 8 | slot << 3) is formed by one
-// v_perm_b32 of the data dword with a per-lane constant: 1 VALU + 1 LDS read per 8 sites instead of
-// 6 VALU, which is what lifts the kernel off the VALU issue limit.
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
-template <bool DIAG>
-__device__ __forceinline__ void gram_task(const uint32_t *__restrict__ rb, uint64_t nb_row, uint32_t ti, uint32_t tj,
-                                          const GramWindow w, uint32_t ks, uint32_t ksplit, int32_t *__restrict__ o,
-                                          uint32_t ld, const unsigned char *__restrict__ lut) {
-    constexpr int NB = DIAG ? 0 : 3;  // B row groups to load (diagonal: reuse A)
-    const uint32_t lane = threadIdx.x & 63, r32 = lane & 31, hi_half = lane >> 5;
-    const uint32_t slot = r32 << 3;   // byte 0 of the v_perm source: this lane's 8-byte column in every table row
-    i32x16 acc[3][3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[a][b][e] = 0;
-    if (w.site_end > w.site_begin) {
-        // 32-bit, window-relative indices: cell c = 64 sites = dwords 2c, 2c+1 (relative to the cell of site_begin)
-        const uint64_t cell0 = w.site_begin >> 6;
-        const uint32_t ncell = (uint32_t)(((w.site_end + 63) >> 6) - cell0);
-        const uint32_t cbeg = (uint32_t)((uint64_t)ncell * ks / ksplit);
-        const uint32_t cend = (uint32_t)((uint64_t)ncell * (ks + 1) / ksplit);  // this K-slice: cells [cbeg, cend)
-        const uint32_t f = (uint32_t)((w.site_begin >> 5) - 2 * cell0);         // first window dword (0 or 1)
-        const uint32_t l = (uint32_t)(((w.site_end + 31) >> 5) - 1 - 2 * cell0);  // last window dword
-        const uint32_t first_mask = 0xFFFFFFFFu << (w.site_begin & 31);
-        const uint32_t last_mask = (w.site_end & 31) ? (0xFFFFFFFFu >> (32 - (w.site_end & 31))) : 0xFFFFFFFFu;
-        auto mask_of = [&](uint32_t d) -> uint32_t {  // wave-uniform; zero outside the window AND outside this slice
-            uint32_t m = (d >= f && d <= l && d >= 2 * cbeg && d < 2 * cend) ? 0xFFFFFFFFu : 0u;
-            if (d == f) m &= first_mask;
-            if (d == l) m &= last_mask;
-            return m;
-        };
-        // RB32: dword (row, d) @ (((row>>5) * nb_row + (d>>1)) * 32 + (row&31)) * 2 + (d&1)
-        const uint32_t *gA = rb + (((uint64_t)(ti * 3) * nb_row + cell0) * 32 + r32) * 2;
-        const uint32_t *gB = rb + (((uint64_t)(tj * 3) * nb_row + cell0) * 32 + r32) * 2;
-        const uint64_t g32 = nb_row * 64;  // dwords between consecutive 32-row groups
-        // A 64-site cell is two dwords; lane half 0 works on dword 0, lane half 1 on dword 1, and the
-        // cell's two 32-site MFMA steps take bytes {0,1} then {2,3} of that dword: every site of the
-        // cell is used exactly once, identically for the A and the B operand (the order of sites
-        // inside a sum is irrelevant), and no per-lane shift is needed.
-        // The window mask of a cell is kept in its own register and applied when the cell is EXPANDED:
-        // masking at load time (`load & m`) makes the load's first use immediate and the compiler
-        // then waits vmcnt(0) right behind the prefetch (seen in the ISA), which serialises it.
-        uint32_t PA_a[3], PB_a[3], PA_b[3], PB_b[3], PA_m, PB_m;
-        const uint32_t hsel = hi_half ? 0xFFFFFFFFu : 0u;
-        auto load_cell = [&](uint32_t (&ca)[3], uint32_t (&cb)[3], uint32_t &cm, uint32_t c) {  // slack cells keep this in bounds
-            const uint32_t m0 = mask_of(2 * c), m1 = mask_of(2 * c + 1);
-            cm = (hsel & m1) | (~hsel & m0);  // v_bfi: lane half 1 works on dword 1 (masking A suffices)
-#if IMPOP_GRAM_ABLATE & 2  // timing-only build: no global loads
-#pragma unroll
-            for (int g = 0; g < 3; ++g) ca[g] = c * 2654435761u + g + lane;
-#pragma unroll
-            for (int g = 0; g < NB; ++g) cb[g] = c * 40503u + g + lane;
-            return;
-#endif
-#pragma unroll
-            for (int g = 0; g < 3; ++g) ca[g] = gA[g * g32 + (uint64_t)c * 64 + hi_half];
-#pragma unroll
-            for (int g = 0; g < NB; ++g) cb[g] = gB[g * g32 + (uint64_t)c * 64 + hi_half];
-        };
-        i32x4 Fa[3], Fb[3], Ga[3], Gb[3];
-        auto lookup16 = [&](uint32_t x, int half) -> i32x4 {  // bytes {2*half, 2*half+1} of x -> 16 int8
-#if IMPOP_GRAM_ABLATE & 1  // timing-only build: no v_perm / LDS reads (results are wrong)
-            i32x4 q = {(int)x, (int)(x + half), (int)x, (int)x};
-            return q;
-#endif
-            const uint32_t a0 = __builtin_amdgcn_perm(x, slot, half ? 0x0C0C0600u : 0x0C0C0400u);
-            const uint32_t a1 = __builtin_amdgcn_perm(x, slot, half ? 0x0C0C0700u : 0x0C0C0500u);
-            const u32x2 lo = *reinterpret_cast<const u32x2 *>(lut + a0);
-            const u32x2 hi = *reinterpret_cast<const u32x2 *>(lut + a1);
-            i32x4 r = {(int)lo.x, (int)lo.y, (int)hi.x, (int)hi.y};
-            return r;
-        };
-        auto expand_step = [&](i32x4 (&fa)[3], i32x4 (&fb)[3], const uint32_t (&ca)[3], const uint32_t (&cb)[3], uint32_t cm,
-                               int half) {
-#pragma unroll
-            for (int g = 0; g < 3; ++g) fa[g] = lookup16(ca[g] & cm, half);
-#pragma unroll
-            for (int g = 0; g < NB; ++g) fb[g] = lookup16(cb[g], half);
-        };
-        auto mfma_step = [&](const i32x4 (&fa)[3], const i32x4 (&fb)[3]) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = 0; b < 3; ++b) {
-                    if (DIAG && b < a) continue;  // strictly below the block diagonal: by symmetry
-#if IMPOP_GRAM_ABLATE & 4  // timing-only build: no MFMA (operands kept alive)
-                    asm volatile("" ::"v"(fa[a]), "v"(DIAG ? fa[b] : fb[b]));
-                    continue;
-#endif
-                    acc[a][b] = __builtin_amdgcn_mfma_i32_32x32x32_i8(fa[a], DIAG ? fa[b] : fb[b], acc[a][b], 0, 0, 0);
-                }
-        };
-        load_cell(PA_a, PA_b, PA_m, cbeg);
-        load_cell(PB_a, PB_b, PB_m, cbeg + 1);
-        expand_step(Fa, Fb, PA_a, PA_b, PA_m, 0);
-        // Inside a phase: first the address perms and the LDS look-ups of the NEXT step (their latency
-        // then hides under this phase's MFMAs, whose own operands were read one phase ago), then the
-        // MFMAs; the closing sched_barrier stops any motion across phases.
-#define PHASE_ORDER()                                                                      \
-    do {                                                                                   \
-        __builtin_amdgcn_sched_group_barrier(0x002, DIAG ? 9 : 15, 0);  /* VALU: and + perm */ \
-        __builtin_amdgcn_sched_group_barrier(0x100, DIAG ? 6 : 12, 0);  /* DS reads */     \
-        __builtin_amdgcn_sched_group_barrier(0x008, DIAG ? 6 : 9, 0);   /* MFMA */         \
-        __builtin_amdgcn_sched_barrier(0);                                                 \
-    } while (0)
-        // Four phases per iteration; sched_barrier keeps the compiler from pulling a later phase's
-        // expansion (and with it the vmcnt wait on the cell just prefetched) forward: without it the
-        // ISA showed vmcnt(0) a few instructions behind the loads.  Inside a phase the 12 LDS look-ups
-        // of the NEXT step and the 9 MFMAs of the CURRENT step are free to interleave.
-        for (uint32_t c = cbeg; c < cend; c += 2) {
-            expand_step(Ga, Gb, PA_a, PA_b, PA_m, 1);   // cell c, second half: last use of PA
-            load_cell(PA_a, PA_b, PA_m, c + 2);         // reloaded 3 phases before its next use
-            mfma_step(Fa, Fb);
-            PHASE_ORDER();
-            expand_step(Fa, Fb, PB_a, PB_b, PB_m, 0);   // cell c+1 (all-zero A if past the slice)
-            mfma_step(Ga, Gb);
-            PHASE_ORDER();
-            expand_step(Ga, Gb, PB_a, PB_b, PB_m, 1);   // last use of PB
-            load_cell(PB_a, PB_b, PB_m, c + 3);
-            mfma_step(Fa, Fb);
-            PHASE_ORDER();
-            expand_step(Fa, Fb, PA_a, PA_b, PA_m, 0);   // cell c+2 for the next iteration
-            mfma_step(Ga, Gb);
-            PHASE_ORDER();
-        }
-#undef PHASE_ORDER
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-            if (DIAG && b < a) continue;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t row = ti * GT + 32 * a + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                const uint32_t col = tj * GT + 32 * b + r32;
-                if (ksplit == 1) o[(uint64_t)row * ld + col] = acc[a][b][e];
-                else atomicAdd(&o[(uint64_t)row * ld + col], acc[a][b][e]);
-            }
-        }
-}
-
-// ---- Gram task on the FP4 matrix cores, straight from the raw bit planes (no table, no LDS) ------
 // v_mfma_f32_32x32x64_f8f6f4 with E2M1 operands runs K = 64 in the 32 cycles the int8 form needs for
 // K = 32 (tools/micro/fp4_probe.hip: 8.45 PFLOP/s over the chip), and a 0/1 matrix needs NO table
 // for it: the E2M1 nibble 0010 is 1.0, so the four vectors
 //     (x << 1) & 0x22222222,  x & 0x22222222,  (x >> 1) & 0x22222222,  (x >> 2) & 0x22222222
 // are valid FP4 operands that together hold every bit of the raw dword x exactly once: 7 VALU per 32
-// sites of a row instead of a v_perm + a 64 KB-table look-up per 8 sites.  The four planes of ONE raw
+// sites of a row.  The four planes of ONE raw
 // dword are the four operand dwords of one MFMA (K = 64: lane half 0 supplies 32 sites of cell c,
 // lane half 1 the same dword of cell c+1; A and B use the same mapping, so the order of sites inside
 // the sum is irrelevant).  fp32 accumulation of 0/1 products is exact below 2^24 (K-slices are
@@ -259,21 +55,6 @@ struct GramPlanes {          // bit planes of the site weights (weight_planes_ke
     uint32_t bits;           // planes with any set bit
 };
 constexpr uint32_t FP4_MAX_SLICE_PAIRS = (1u << 24) / 128;  // fp32 accumulators stay exact integers
-#ifndef IMPOP_GRAM_PACK16
-#define IMPOP_GRAM_PACK16 1  // uint16 counts stored two to a dword (0: A/B build with one 2-byte store per count)
-#endif
-#ifndef IMPOP_GRAM_ORDER
-#define IMPOP_GRAM_ORDER 0  // order of a window's tile-pair tasks in its queue (A/B builds: 1, 2; measured equal, profiles/r03_gram_experiments.txt §12)
-#endif
-#ifndef IMPOP_GRAM_RING
-#define IMPOP_GRAM_RING 0  // 0: operands straight into three rotating register cell buffers (shipped); 1: prefetched through a
-                          // per-wave LDS ring, 2-3 quads ahead (A/B builds: tools/build_variants.py pairwise.hip ring1:-DIMPOP_GRAM_RING=1).
-                          // Measured equal (7.07 vs 6.99 ms per 4096 windows, profiles/r03_gram_experiments.txt): the kernel is not
-                          // waiting for its loads, so the simpler form without LDS ships.
-#endif
-constexpr uint32_t RING_SLOT = 6 * 1024;  // one quad: 6 row groups x (4 cells x 32 rows x 8 B)
-constexpr uint32_t RING_SLOTS = 3;
-constexpr uint32_t RING_BYTES = RING_SLOT * RING_SLOTS;  // per wave: 18 KB; 4 waves x 2 workgroups = 144 of a CU's 160 KB
 
 __device__ __forceinline__ i32x4 fp4_planes(uint32_t x) {
     i32x4 f;
@@ -301,11 +82,9 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
                                               const GramWindow *__restrict__ wins, uint32_t win0, uint32_t wstep, uint32_t nchain,
                                               uint32_t ks, uint32_t ksplit, int32_t *__restrict__ out, uint64_t out_stride,
                                               uint32_t ld, uint32_t shift, bool add, const GramPlanes wp,
-                                              uint32_t ring /* LDS byte address of this wave's operand ring (wave-uniform) */,
                                               bool out16 /* counts stored as uint16 (host: every window's W < 65536, no atomics) */) {
     constexpr int NB = DIAG ? 0 : 3;
     constexpr int NM = DIAG ? 6 : 9;  // MFMAs per phase
-    constexpr int NL = DIAG ? 3 : 6;  // row groups = global loads per quad
     const uint32_t lane = threadIdx.x & 63, r32 = lane & 31, hi_half = lane >> 5;
     struct Cell {
         u32x2 a[3], b[3];
@@ -342,7 +121,8 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
     // is a UNIFORM pointer per (a, b, e) (scalar arithmetic) plus ONE per-lane 32-bit offset: 144 per-lane 64-bit addresses would be
     // hoisted out of the chain loop and spilled
     const uint32_t lane_elem = (ti * GT + 4 * (lane >> 5)) * ld + tj * GT + r32;  // < ld^2 <= 2^32 (ld <= 65535 + padding)
-    // uint16 counts go out two to a dword: registers e and e + 1 (e even) of a block are the rows r and r + 1 of this lane's
+    // uint16 counts (half the result bytes: a third of a short-window launch was writing 553 KB of counts per window) go out two
+    // to a dword: registers e and e + 1 (e even) of a block are the rows r and r + 1 of this lane's
     // column; a lane swaps both with its neighbour column (DPP quad_perm [1,0,3,2]), even lanes then hold (col, col + 1) of row r,
     // odd lanes (col - 1, col) of row r + 1 — one 4-byte store per lane instead of two 2-byte ones (half the store instructions;
     // on short windows a quarter of the launch was its stores, profiles/r03_gram_experiments.txt §10, §13)
@@ -354,7 +134,7 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
 #pragma unroll
             for (int b = 0; b < 3; ++b) {
                 if (a < a_from || a >= a_to || (DIAG && b < a)) continue;
-                if (out16 && IMPOP_GRAM_PACK16) {
+                if (out16) {
 #pragma unroll
                     for (int e = 0; e < 16; e += 2) {
                         const uint64_t eo = (uint64_t)(32 * a + (e & 3) + 8 * (e >> 2)) * ld + 32 * b;  // uniform element offset of (a, b, e)
@@ -374,10 +154,6 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
                     int32_t *ob = o + eo;
                     // weighted matrices: this launch is bit plane `shift` of the site weights, added into the other planes' sum
                     const int32_t v = (int32_t)((uint32_t)(int32_t)acc[a][b][e] << sh);
-                    if (out16) {  // half the result bytes: a third of a short-window launch is writing 553 KB of counts per window
-                        (reinterpret_cast<uint16_t *>(o) + eo)[lane_elem] = (uint16_t)v;
-                        continue;
-                    }
 #if IMPOP_GRAM_ABLATE & 8  // timing-only build: results are not written (only one lane's worth, to keep the work alive)
                     if (lane_elem == 0xFFFFFFFFu) ob[0] = v;
                     continue;
@@ -460,36 +236,6 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
             if (wrap) return (j < n_pairs ? j : n_pairs - 1) * 512u;
             return (n_pairs - 1) * 512u;
         };
-        // ---- operand ring in LDS (IMPOP_GRAM_RING = 1, an A/B build; see the macro) -----------------------------------
-        // The hypothesis it tested: three cell buffers in registers are a prefetch distance of ~2.5 pairs (1.4 us), less than a
-        // loaded HBM / L2-miss latency, and there is no register left for a fourth (2 waves per SIMD x 144 accumulators) — so
-        // let the prefetch buffer live in LDS: `buffer_load_dwordx4 ... lds` writes 1 KB per wave instruction — cells c..c+3 of a
-        // 32-row group = two pairs, a "quad" — straight into this wave's private ring of RING_SLOTS quads (no VGPR, no barrier:
-        // nobody else reads the ring), 2-3 quads = 8-12 phases ahead of use, and a lane fetches its dword pair of the NEXT pair
-        // with one ds_read_b64 per row group one phase before the expansion needs it.  The ds_reads are volatile asm (the compiler
-        // must not put `vmcnt(0)` in front of LDS reads it would see aliasing the DMA); the waits are explicit:
-        //   vmcnt(NL)  before the first ds_read of a quad: everything but the newest quad's NL loads has landed (loads return in
-        //              order; the queue pop's atomic drained the previous task's stores),
-        //   lgkmcnt(0) before the first expansion that reads a ds_read's destination.
-        const uint32_t nquad = (uend - ubeg + 1) >> 1;  // quad j = pairs ubeg + 2j, ubeg + 2j + 1
-        auto quad_soff = [&](uint32_t j) -> uint32_t { return (j < nquad ? j : nquad - 1) * 1024u; };  // clamped like pair_soff
-        const uint32_t dma_voff = lane * 16;
-        typedef __attribute__((address_space(3))) void *lds_ptr_t;
-        auto dma_one = [&](int i, uint32_t slot_lds, uint32_t soff) {  // i = 0..2: A groups, 3..5: B groups; slot_lds wave-uniform
-            if (i < 3) __builtin_amdgcn_raw_ptr_buffer_load_lds(rA[i], (lds_ptr_t)(uintptr_t)(slot_lds + i * 1024), 16, dma_voff, soff, 0, 0);
-            else __builtin_amdgcn_raw_ptr_buffer_load_lds(rB[i - 3], (lds_ptr_t)(uintptr_t)(slot_lds + i * 1024), 16, dma_voff, soff, 0, 0);
-        };
-        const uint32_t lds_lane = ring + r32 * 8 + hi_half * 256;  // this lane's dword pair inside a 512-byte pair of a group
-#define DS_CELL(DST, VA, IMM) asm volatile("ds_read_b64 %0, %1 offset:" #IMM : "=v"(DST) : "v"(VA) : "memory")
-#define DS_ONE(C, I, VA)                          \
-    do {                                          \
-        if ((I) == 0) DS_CELL(C.a[0], VA, 0);     \
-        if ((I) == 1) DS_CELL(C.a[1], VA, 1024);  \
-        if ((I) == 2) DS_CELL(C.a[2], VA, 2048);  \
-        if ((I) == 3) DS_CELL(C.b[0], VA, 3072);  \
-        if ((I) == 4) DS_CELL(C.b[1], VA, 4096);  \
-        if ((I) == 5) DS_CELL(C.b[2], VA, 5120);  \
-    } while (0)
         // The phase is scheduled BY HAND in volatile inline asm: builtins let the compiler float the
         // expansion arithmetic across sched_barriers (it is not chained to them) and the MFMAs ended up
         // in runs of 3-9 with the VALU work in one lump behind them.  Volatile asm statements keep their
@@ -563,80 +309,9 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
         FP4_PHASE(F, G, CUR, 1, mA, CUR, soff, false);                              \
         FP4_PHASE(G, F, NXT, 0, mB, CUR, soff, true);                               \
     } while (0)
-        // The ring version of a phase: MFMA i, then (first-half phases) nothing more than the expansion, (second-half phases)
-        // the ds_read of row group i of the pair after next into the cell the previous phase finished with; DMA_MODE 1 / 2
-        // issues the A / B row groups of the quad three ahead into the slot whose last ds_read has been waited for.
-#define FP4_PHASE_R(CURF, NXTF, SRC, D, M, DSC, VA, DO_DS, WAITS, DMA_MODE, SLOT_LDS, SOFF)                  \
-    do {                                                                                                  \
-        uint32_t xa0 = 0, xa1 = 0, xa2 = 0;                                                               \
-        _Pragma("unroll") for (int i = 0; i < NM; ++i) {                                                  \
-            const int a = DIAG ? (i < 3 ? 0 : i < 5 ? 1 : 2) : i / 3;                                     \
-            const int b = DIAG ? (i < 3 ? i : i < 5 ? i - 2 : 2) : i % 3;                                 \
-            if (DIAG) mfma_asm(acc[a][b], CURF.a[a], CURF.a[b]);                                          \
-            else mfma_asm(acc[a][b], CURF.a[a], CURF.b[b]);                                               \
-            if (i == 0 && (WAITS) == 1) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                \
-            if (i == 0 && (WAITS) == 2 && DIAG) asm volatile("s_waitcnt vmcnt(3) lgkmcnt(0)" ::: "memory");  \
-            if (i == 0 && (WAITS) == 2 && !DIAG) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory"); \
-            if (DO_DS && i < NL) DS_ONE(DSC, i, VA);                                                      \
-            if (!(IMPOP_GRAM_ABLATE & 2) && (DMA_MODE) == 1 && i < 3) dma_one(i, SLOT_LDS, SOFF);         \
-            if (!(IMPOP_GRAM_ABLATE & 2) && (DMA_MODE) == 2 && i < NB) dma_one(3 + i, SLOT_LDS, SOFF);    \
-            if (IMPOP_GRAM_ABLATE & 1) continue; /* timing-only build: no expansion VALU */               \
-            if (DIAG) {                                                                                   \
-                if (i == 0) lo_masked(NXTF.a[0], xa0, D ? SRC.a[0].y : SRC.a[0].x, M);                    \
-                if (i == 1) hi_planes(NXTF.a[0], xa0);                                                    \
-                if (i == 2) lo_masked(NXTF.a[1], xa1, D ? SRC.a[1].y : SRC.a[1].x, M);                    \
-                if (i == 3) hi_planes(NXTF.a[1], xa1);                                                    \
-                if (i == 4) lo_masked(NXTF.a[2], xa2, D ? SRC.a[2].y : SRC.a[2].x, M);                    \
-                if (i == 5) hi_planes(NXTF.a[2], xa2);                                                    \
-            } else {                                                                                      \
-                if (i == 0) lo_masked(NXTF.a[0], xa0, D ? SRC.a[0].y : SRC.a[0].x, M);                    \
-                if (i == 1) { hi_planes(NXTF.a[0], xa0); lo_plain(NXTF.b[0], D ? SRC.b[0].y : SRC.b[0].x); } \
-                if (i == 2) hi_planes(NXTF.b[0], D ? SRC.b[0].y : SRC.b[0].x);                            \
-                if (i == 3) lo_masked(NXTF.a[1], xa1, D ? SRC.a[1].y : SRC.a[1].x, M);                    \
-                if (i == 4) { hi_planes(NXTF.a[1], xa1); lo_plain(NXTF.b[1], D ? SRC.b[1].y : SRC.b[1].x); } \
-                if (i == 5) hi_planes(NXTF.b[1], D ? SRC.b[1].y : SRC.b[1].x);                            \
-                if (i == 6) lo_masked(NXTF.a[2], xa2, D ? SRC.a[2].y : SRC.a[2].x, M);                    \
-                if (i == 7) { hi_planes(NXTF.a[2], xa2); lo_plain(NXTF.b[2], D ? SRC.b[2].y : SRC.b[2].x); } \
-                if (i == 8) hi_planes(NXTF.b[2], D ? SRC.b[2].y : SRC.b[2].x);                            \
-            }                                                                                             \
-        }                                                                                                 \
-    } while (0)
-        // pair U lives in CUR (dword 0 already expanded in F), pair U+1 in NXT; the second phase refills CUR with pair U+2 from
-        // the ring (address VA).  WAITS 2 on the first pair of a quad (the quad it reads from must have landed), 1 on the second.
-#define FP4_PAIR_R(CUR, NXT, U, VA, WAITS, DMA1, DMA2, SLOT_LDS, SOFF)                \
-    do {                                                                            \
-        uint32_t mA = 0xFFFFFFFFu, mB = 0xFFFFFFFFu;                                \
-        if (!(4 * (U) + 1 > f && 4 * (U) + 6 < l && (U) + 1 < uend)) {              \
-            asm volatile("");                                                       \
-            mA = lane_mask((U), 1);                                                 \
-            mB = lane_mask((U) + 1, 0);                                             \
-        }                                                                           \
-        if (P) {                                                                    \
-            mA &= plane_mask((U), 1);                                               \
-            mB &= plane_mask((U) + 1, 0);                                           \
-        }                                                                           \
-        FP4_PHASE_R(F, G, CUR, 1, mA, CUR, VA, false, 0, DMA1, SLOT_LDS, SOFF);     \
-        FP4_PHASE_R(G, F, NXT, 0, mB, CUR, VA, true, WAITS, DMA2, SLOT_LDS, SOFF);  \
-    } while (0)
         do {  // once, or once per used weight plane (a plain bottom-tested loop: more exits make the compiler shuffle the accumulators)
         if (wp.planes) P = wp.planes + (uint64_t)kcur * wp.stride + 2 * cell0;
         if (ubeg < uend) {
-#if IMPOP_GRAM_RING
-            Frag F, G;
-#pragma unroll
-            for (int j = 0; j < (int)RING_SLOTS; ++j)  // quads 0 .. RING_SLOTS-1 on their way
-#pragma unroll
-                for (int i = 0; i < NL; ++i) dma_one(i < 3 ? i : i, ring + j * RING_SLOT, quad_soff(j));
-            if (DIAG) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");  // quad 0 has landed (RING_SLOTS - 1 quads may still fly)
-            else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-            static_assert(RING_SLOTS == 3, "the vmcnt immediates above assume three slots");
-            {
-                const uint32_t va0 = lds_lane, va1 = lds_lane + 512;
-#pragma unroll
-                for (int i = 0; i < NL; ++i) { DS_ONE(C0, i, va0); DS_ONE(C1, i, va1); }
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-#else
             Frag F, G;
             wrap = (plane_left & ~(1u << kcur)) != 0;
             if (!have_cells) {  // first link of a chain (or nothing could be prefetched): wait for the first three pairs here
@@ -648,7 +323,6 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
                 }
             }
             have_cells = wrap;  // what the loop below leaves in C0..C2 (pair_soff)
-#endif
             {
                 const uint32_t m0 = lane_mask(ubeg, 0) & (P ? plane_mask(ubeg, 0) : 0xFFFFFFFFu);
                 uint32_t xm;
@@ -678,27 +352,11 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
             }
             // no early exit (extra loop exits make the compiler merge 144 accumulators and spill): a slice
             // whose length is not a multiple of 3 pairs runs up to two fully masked pairs
-#if IMPOP_GRAM_RING
-            // one quad per iteration: its two pairs sit in C0 / C1; quad q + 1 is read out of slot (q + 1) % 3 into the cells
-            // as they fall free, quad q + 3 is sent after into slot q % 3 (fully read and waited for one iteration ago)
-            uint32_t slot = 0, qj = 0;  // slot of quad q (uniform), quad index relative to the slice
-            for (uint32_t u = ubeg; u < uend; u += 2) {
-                const uint32_t nslot = slot == RING_SLOTS - 1 ? 0 : slot + 1;
-                const uint32_t va = lds_lane + nslot * RING_SLOT;
-                const uint32_t slot_lds = ring + slot * RING_SLOT, soff = quad_soff(qj + RING_SLOTS);
-                FP4_PAIR_R(C0, C1, u, va, 2, 0, 0, slot_lds, soff);
-                FP4_PAIR_R(C1, C0, u + 1, va + 512, 1, 1, 2, slot_lds, soff);
-                slot = nslot;
-                ++qj;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the cells' last (unused) refills, before the registers are reused
-#else
             for (uint32_t u = ubeg; u < uend; u += 3) {
                 FP4_PAIR(C0, C1, u);
                 FP4_PAIR(C1, C2, u + 1);
                 FP4_PAIR(C2, C0, u + 2);
             }
-#endif
         }
         asm volatile("s_nop 15\n\ts_nop 15");  // last MFMA results -> the VALU conversions / doublings below
         plane_left &= ~(1u << kcur);
@@ -719,7 +377,7 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
         if (wp.planes) sh += kcur;  // Horner stopped at the lowest used plane
         store_blocks(0, 1);
         __builtin_amdgcn_sched_barrier(0);  // the loads stay HERE: hoisted above the stores they would not fit the registers
-        if (nx_ok && !(IMPOP_GRAM_RING)) {
+        if (nx_ok) {
 #pragma unroll
             for (int i = 0; i < (DIAG ? 3 : 6); ++i) {
                 load_one(C0, i, nx_off);
@@ -733,27 +391,29 @@ __device__ __forceinline__ void gram_task_fp4(const uint32_t *__restrict__ rb, u
         stored = true;
 #undef FP4_PAIR
 #undef FP4_PHASE
-#undef FP4_PAIR_R
-#undef FP4_PHASE_R
-#undef DS_ONE
-#undef DS_CELL
     }
     if (!stored) store_blocks(0, 3);  // an empty window never started: zeros
     w = wn;
     }  // chain links
 }
 
-// Persistent FP4 Gram kernel: same task queues as gram_mfma_kernel below; LDS only as each wave's private operand ring.
+// Persistent workgroups (2 per CU, 4 waves each, no LDS); every WAVE pulls (window, tile pair, K-slice) tasks from one of 8
+// queues until all are drained, so a wave whose task was short (diagonal tiles do 2/3 of the MFMAs) immediately starts another
+// one and both SIMD slots stay occupied (PMC before queues: 1.45-1.6 resident waves per SIMD, after: ~2).
+// Queue q holds the tasks of windows with win % 8 == q and is served first by workgroups with blockIdx % 8 == q, i.e. (under
+// the observed round-robin placement) by one XCD, whose L2 then holds that window's rows for all of its 15 tile pairs; a
+// workgroup whose queue is empty steals from the others, so the result and termination never depend on placement: every wave
+// leaves once all eight counters have passed their queue length.
+// ksplit > 1: the site range of a window is cut into ksplit slices handled by different tasks that atomicAdd into a
+// zero-initialised output (integer adds commute: still bit-reproducible); used when there are too few (window, tile) tasks to
+// keep two waves on every SIMD.
 __global__ __launch_bounds__(256, 2) void gram_fp4_kernel(const uint32_t *__restrict__ rb, uint64_t nb_row, uint32_t n_tiles,
                                                           uint32_t tasks_per_win, uint32_t n_win, uint32_t ksplit,
                                                           const GramWindow *__restrict__ wins, int32_t *__restrict__ out,
                                                           uint32_t ld, uint64_t out_stride, uint32_t *__restrict__ queue_heads,
                                                           uint32_t shift, bool add, GramPlanes wp, uint32_t chain, uint32_t out16) {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char gram_ring[];  // 4 waves x RING_BYTES (dynamic: > 64 KB)
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t ring = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)gram_ring + wave * RING_BYTES;
-    const uint32_t slots = tasks_per_win * ksplit;
-    const bool by_window = n_win >= 8;
+    const uint32_t slots = tasks_per_win * ksplit;  // (tile pair, K-slice) slots of one window
+    const bool by_window = n_win >= 8;              // few windows: deal single tasks round-robin instead
     const uint64_t total = (uint64_t)n_win * slots;
     const uint32_t nc = (by_window && ksplit == 1 && chain > 1) ? chain : 1u;  // windows per ticket (gram_task_fp4: chains)
     for (uint32_t dq = 0; dq < 8; ++dq) {
@@ -764,7 +424,7 @@ __global__ __launch_bounds__(256, 2) void gram_fp4_kernel(const uint32_t *__rest
             uint32_t k = 0;
             if ((threadIdx.x & 63) == 0) k = atomicAdd(&queue_heads[q], 1u);
             k = __builtin_amdgcn_readfirstlane(k);
-            if (k >= q_len) break;
+            if (k >= q_len) break;  // queue drained (the head keeps counting, harmlessly)
             uint32_t win, t2, links = 1, wstep = 0;
             if (by_window) {
                 const uint32_t wb = k / slots;  // ticket = (block of nc windows of this queue, tile pair)
@@ -775,76 +435,10 @@ __global__ __launch_bounds__(256, 2) void gram_fp4_kernel(const uint32_t *__rest
             } else { const uint64_t i = q + 8ull * k; win = (uint32_t)(i / slots); t2 = (uint32_t)(i % slots); }
             const uint32_t ks = t2 % ksplit;
             uint32_t rem = t2 / ksplit, ti = 0, tj;
-#if IMPOP_GRAM_ORDER == 1  // A/B build (tools/build_variants.py): a window's off-diagonal tile pairs first, its diagonal ones last
-            const uint32_t n_off = n_tiles * (n_tiles - 1) / 2;
-            if (rem < n_off) {
-                while (rem >= n_tiles - 1 - ti) { rem -= n_tiles - 1 - ti; ++ti; }
-                tj = ti + 1 + rem;
-            } else { ti = tj = rem - n_off; }
-#elif IMPOP_GRAM_ORDER == 2  // ... diagonal ones first
-            if (rem < n_tiles) { ti = tj = rem; }
-            else {
-                rem -= n_tiles;
-                while (rem >= n_tiles - 1 - ti) { rem -= n_tiles - 1 - ti; ++ti; }
-                tj = ti + 1 + rem;
-            }
-#else
             while (rem >= n_tiles - ti) { rem -= n_tiles - ti; ++ti; }
             tj = ti + rem;
-#endif
-            if (ti == tj) gram_task_fp4<true>(rb, nb_row, ti, tj, wins, win, wstep, links, ks, ksplit, out, out_stride, ld, shift, add, wp, ring, out16 != 0);
-            else gram_task_fp4<false>(rb, nb_row, ti, tj, wins, win, wstep, links, ks, ksplit, out, out_stride, ld, shift, add, wp, ring, out16 != 0);
-        }
-    }
-}
-
-// Persistent workgroups (2 per CU, 4 waves each) that share only the lookup table; every WAVE pulls
-// (window, tile pair, K-slice) tasks from one of 8 queues until all are drained, so a wave whose task
-// was short (diagonal tiles do 2/3 of the MFMAs) immediately starts another one and both SIMD slots
-// stay occupied (PMC before this change: 1.45-1.6 resident waves per SIMD, after: ~2).
-// Queue q holds the tasks of windows with win % 8 == q and is served first by workgroups with
-// blockIdx % 8 == q, i.e. (under the observed round-robin placement) by one XCD, whose L2 then holds
-// that window's rows for all of its 15 tile pairs; a workgroup whose queue is empty steals from the
-// others, so the result and termination never depend on placement: every wave leaves once all eight
-// counters have passed their queue length.
-// ksplit > 1: the site range of a window is cut into ksplit slices handled by different tasks that
-// atomicAdd into a zero-initialised output (integer adds commute: still bit-reproducible); used
-// when there are too few (window, tile) tasks to keep two waves on every SIMD.
-__global__ __launch_bounds__(256, 2) void gram_mfma_kernel(const uint32_t *__restrict__ rb, uint64_t nb_row,
-                                                           uint32_t n_tiles, uint32_t tasks_per_win, uint32_t n_win,
-                                                           uint32_t ksplit, const GramWindow *__restrict__ wins,
-                                                           int32_t *__restrict__ out, uint32_t ld, uint64_t out_stride,
-                                                           uint32_t *__restrict__ queue_heads /* 8, zeroed per launch */) {
-    __shared__ __attribute__((aligned(16))) unsigned char lut[256 * 32 * 8];  // 64 KB: [entry][lane slot] x 8 bytes
-    for (uint32_t i = threadIdx.x; i < 256 * 32; i += 256) {
-        const uint32_t e = i >> 5;  // entry: bit j of e -> byte j
-        u32x2 v;
-        v.x = __umul24(e & 0xFu, 0x204081u) & 0x01010101u;
-        v.y = __umul24((e >> 4) & 0xFu, 0x204081u) & 0x01010101u;
-        *reinterpret_cast<u32x2 *>(lut + (size_t)i * 8) = v;
-    }
-    __syncthreads();  // the only barrier; everything below is per wave
-    const uint32_t slots = tasks_per_win * ksplit;  // (tile pair, K-slice) slots of one window
-    const bool by_window = n_win >= 8;              // few windows: deal single tasks round-robin instead
-    const uint64_t total = (uint64_t)n_win * slots;
-    for (uint32_t dq = 0; dq < 8; ++dq) {
-        const uint32_t q = (blockIdx.x + dq) & 7;
-        const uint64_t q_len = by_window ? (uint64_t)((n_win + 7 - q) / 8) * slots : (total + 7 - q) / 8;
-        for (;;) {
-            uint32_t k = 0;
-            if ((threadIdx.x & 63) == 0) k = atomicAdd(&queue_heads[q], 1u);
-            k = __builtin_amdgcn_readfirstlane(k);
-            if (k >= q_len) break;  // queue drained (the head keeps counting, harmlessly)
-            uint32_t win, t2;
-            if (by_window) { win = q + 8 * (k / slots); t2 = k % slots; }
-            else { const uint64_t i = q + 8ull * k; win = (uint32_t)(i / slots); t2 = (uint32_t)(i % slots); }
-            const uint32_t ks = t2 % ksplit;
-            uint32_t rem = t2 / ksplit, ti = 0;
-            while (rem >= n_tiles - ti) { rem -= n_tiles - ti; ++ti; }
-            const uint32_t tj = ti + rem;
-            int32_t *o = out + (uint64_t)win * out_stride;
-            if (ti == tj) gram_task<true>(rb, nb_row, ti, tj, wins[win], ks, ksplit, o, ld, lut);
-            else gram_task<false>(rb, nb_row, ti, tj, wins[win], ks, ksplit, o, ld, lut);
+            if (ti == tj) gram_task_fp4<true>(rb, nb_row, ti, tj, wins, win, wstep, links, ks, ksplit, out, out_stride, ld, shift, add, wp, out16 != 0);
+            else gram_task_fp4<false>(rb, nb_row, ti, tj, wins, win, wstep, links, ks, ksplit, out, out_stride, ld, shift, add, wp, out16 != 0);
         }
     }
 }
@@ -926,20 +520,10 @@ __global__ void pairwise_finalize_kernel(PairFinalIn in, uint64_t n_windows, uin
     out[i] = r;
 }
 
-// IMPOP_GRAM_MFMA=i8 selects the int8 kernel (kept for A/B measurements); default: FP4 bit planes
-static bool gram_use_fp4() {
-    static const bool v = [] {
-        const char *e = getenv("IMPOP_GRAM_MFMA");
-        return !(e && e[0] == 'i');
-    }();
-    return v;
-}
-
-// add_shift < 0: d_out = Gram; >= 0 (FP4 kernel only): d_out += Gram << add_shift (d_out holds the other planes' sum).
-// fused_planes (FP4 kernel only): the weighted Gram matrix of m in one launch (gram_task_fp4), every window's summed
-// weight below 2^24.
+// add_shift < 0: d_out = Gram; >= 0: d_out += Gram << add_shift (d_out holds the other planes' sum).
+// fused_planes: the weighted Gram matrix of m in one launch (gram_task_fp4), every window's summed weight below 2^24.
 // out16 (in / out, nullable): the caller would take uint16 counts (every window's W < 65536); set to whether the launch wrote them
-// (only the FP4 kernel, only without K-split atomics and plane accumulation)
+// (only without K-split atomics and plane accumulation)
 static int launch_gram(impop_ctx *ctx, const impop_matrix *m, const uint32_t *d_rb, const GramWindow *d_wins, uint32_t n_win,
                        int32_t *d_out, uint64_t max_window_sites, int add_shift = -1, bool fused_planes = false, bool *out16 = nullptr) {
     const uint32_t T = m->n_hap_pad / GT;
@@ -949,22 +533,19 @@ static int launch_gram(impop_ctx *ctx, const impop_matrix *m, const uint32_t *d_
     const uint64_t want = 32ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
     uint32_t ksplit = 1;
     while ((uint64_t)n_win * tasks_per_win * ksplit < want && ksplit < 64) ksplit *= 2;
-    // FP4: fp32 accumulators must stay below 2^24 per K-slice
-    while (gram_use_fp4() && (max_window_sites / 128 + 2) / ksplit + 1 > FP4_MAX_SLICE_PAIRS) ksplit *= 2;
-    const bool w16 = out16 && *out16 && gram_use_fp4() && ksplit == 1 && add_shift < 0;
+    // fp32 accumulators must stay below 2^24 per K-slice
+    while ((max_window_sites / 128 + 2) / ksplit + 1 > FP4_MAX_SLICE_PAIRS) ksplit *= 2;
+    const bool w16 = out16 && *out16 && ksplit == 1 && add_shift < 0;
     if (out16) *out16 = w16;
     if (ksplit > 1 && add_shift < 0)
         HIP_TRY(hipMemsetAsync(d_out, 0, (size_t)n_win * m->n_hap_pad * m->n_hap_pad * sizeof(int32_t), ctx->stream));
     REQUIRE((uint64_t)n_win * tasks_per_win * ksplit < 0xFFFFFFF0ull, "gram: too many tasks for one launch");
     if (!ctx->d_queue) HIP_TRY(hipMalloc((void **)&ctx->d_queue, 8 * sizeof(uint32_t)));
     HIP_TRY(hipMemsetAsync(ctx->d_queue, 0, 8 * sizeof(uint32_t), ctx->stream));
-    // persistent grid: two 256-thread workgroups per CU (64 KB of LDS each), never fewer than 8
+    // persistent grid: two 256-thread workgroups per CU, never fewer than 8
     const uint32_t n_cu = (uint32_t)(ctx->n_cu > 0 ? ctx->n_cu : 256);
     const uint64_t need_wg = ((uint64_t)n_win * tasks_per_win * ksplit + 3) / 4;
-    // IMPOP_GRAM_WG_PER_CU=1 (A/B runs): one workgroup = one wave per SIMD on every CU (the LDS request keeps a second one out)
-    static const uint32_t wg_per_cu = [] { const char *e = getenv("IMPOP_GRAM_WG_PER_CU"); return (e && e[0] == '1') ? 1u : 2u; }();
-    const uint32_t grid = (uint32_t)std::max<uint64_t>(8, std::min<uint64_t>((uint64_t)wg_per_cu * n_cu, need_wg));
-    const uint32_t ring_lds = wg_per_cu == 1 ? 100u * 1024u : (IMPOP_GRAM_RING ? 4 * RING_BYTES : 0u);
+    const uint32_t grid = (uint32_t)std::max<uint64_t>(8, std::min<uint64_t>(2ull * n_cu, need_wg));
     GramPlanes wp{nullptr, 0, 0};
     if (fused_planes) wp = GramPlanes{m->d_wplanes, m->wplane_stride, m->wplane_bits};
     // chains of windows per ticket (gram_task_fp4) where a task is short — at most 8192 columns = 64 pairs, 20 us of MFMAs — and
@@ -979,29 +560,15 @@ static int launch_gram(impop_ctx *ctx, const impop_matrix *m, const uint32_t *d_
         static const int forced = [] { const char *e = getenv("IMPOP_GRAM_CHAIN"); return e ? atoi(e) : 0; }();
         if (forced > 0 && ksplit == 1) chain = (uint32_t)forced;
     }
-    {
-        static const hipError_t ring_attr = hipFuncSetAttribute((const void *)gram_fp4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                                (int)(100 * 1024));  // 72 KB per workgroup: above the 64 KB default
-        HIP_TRY(ring_attr);
-    }
-    if (gram_use_fp4())
-        hipLaunchKernelGGL(gram_fp4_kernel, dim3(grid), dim3(256), ring_lds, ctx->stream, d_rb, m->rb_nb, T, tasks_per_win, n_win,
-                           ksplit, d_wins, d_out, m->n_hap_pad, (uint64_t)m->n_hap_pad * m->n_hap_pad, ctx->d_queue,
-                           add_shift < 0 ? 0u : (uint32_t)add_shift, add_shift >= 0, wp, chain, w16 ? 1u : 0u);
-    else
-        hipLaunchKernelGGL(gram_mfma_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_rb, m->rb_nb, T, tasks_per_win, n_win,
-                           ksplit, d_wins, d_out, m->n_hap_pad, (uint64_t)m->n_hap_pad * m->n_hap_pad, ctx->d_queue);
+    hipLaunchKernelGGL(gram_fp4_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_rb, m->rb_nb, T, tasks_per_win, n_win, ksplit,
+                       d_wins, d_out, m->n_hap_pad, (uint64_t)m->n_hap_pad * m->n_hap_pad, ctx->d_queue,
+                       add_shift < 0 ? 0u : (uint32_t)add_shift, add_shift >= 0, wp, chain, w16 ? 1u : 0u);
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }
 
-// every window lighter than 2^24 (fp32-exact sums): all weight planes inside one launch (Horner in gram_task_fp4);
-// IMPOP_GRAM_PLANES=split keeps the launch-per-plane form for A/B measurements
+// every window lighter than 2^24 (fp32-exact sums): all weight planes inside one launch (Horner in gram_task_fp4)
 constexpr uint64_t GRAM_FUSED_WEIGHT_LIMIT = 1ull << 24;
-static bool gram_planes_in_task() {
-    static const bool split_planes = [] { const char *e = getenv("IMPOP_GRAM_PLANES"); return e && e[0] == 's'; }();
-    return gram_use_fp4() && !split_planes;
-}
 
 // ---- weighted sites on the all-pairs path ------------------------------------------------------------------
 // Column s stands for w_s base pairs (one column per graph node, impop_matrix_set_site_weights): what `impg
@@ -1054,11 +621,6 @@ __global__ void rb_mask_kernel(const uint32_t *__restrict__ rb, uint32_t *__rest
     *reinterpret_cast<u32x2 *>(out + at) = o;
 }
 
-__global__ void gram_accumulate_kernel(int32_t *__restrict__ acc, const int32_t *__restrict__ part, uint32_t shift, uint64_t count) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) acc[i] += (int32_t)((uint32_t)part[i] << shift);
-}
-
 static int ensure_weight_planes(impop_ctx *ctx, const impop_matrix *m) {
     if (m->d_wplanes) return IMPOP_OK;
     const uint64_t n_dword = 2 * m->g.n_block;
@@ -1083,10 +645,9 @@ static int ensure_weight_planes(impop_ctx *ctx, const impop_matrix *m) {
     return IMPOP_OK;
 }
 
-// Gram matrices of `n_win` cells (host copy h_wins of d_wins for the cell range) into d_out; d_tmp: a second buffer
-// of the same size, used by weighted matrices only
+// Gram matrices of `n_win` cells (host copy h_wins of d_wins for the cell range) into d_out
 static int launch_gram_any(impop_ctx *ctx, const impop_matrix *m, const GramWindow *d_wins, const GramWindow *h_wins,
-                           uint32_t n_win, int32_t *d_out, int32_t *d_tmp, uint64_t max_window_sites, bool *out16 = nullptr) {
+                           uint32_t n_win, int32_t *d_out, uint64_t max_window_sites, bool *out16 = nullptr) {
     if (m->wt_prefix.empty()) return launch_gram(ctx, m, m->d_rb, d_wins, n_win, d_out, max_window_sites, -1, false, out16);
     int rc = ensure_weight_planes(ctx, m);
     if (rc) return rc;
@@ -1102,32 +663,25 @@ static int launch_gram_any(impop_ctx *ctx, const impop_matrix *m, const GramWind
     for (uint32_t i = 0; i < n_win; ++i)
         if (h_wins[i].site_end > h_wins[i].site_begin)
             heaviest = std::max(heaviest, pre[h_wins[i].site_end] - pre[h_wins[i].site_begin]);
-    if (gram_planes_in_task() && m->wplane_bits && heaviest < GRAM_FUSED_WEIGHT_LIMIT) {
+    if (m->wplane_bits && heaviest < GRAM_FUSED_WEIGHT_LIMIT) {
         if (out16 && heaviest >= 65536) *out16 = false;
         return launch_gram(ctx, m, m->d_rb, d_wins, n_win, d_out, max_window_sites, -1, true, out16);
     }
     if (out16) *out16 = false;  // one launch per plane, accumulated with atomics: 32-bit counts
-    REQUIRE(d_tmp || !m->wplane_bits, "weighted Gram: no buffer for the plane partials");
     HIP_TRY(hipMemsetAsync(d_out, 0, count * 4, ctx->stream));
     if (c_lo >= c_hi) return IMPOP_OK;
     c_hi = std::min<uint64_t>(c_hi + 8, m->rb_nb);  // the Gram pipeline prefetches a few cells past a window's end
     const uint32_t n_group = m->n_hap_pad / 32;
     const uint64_t threads = (c_hi - c_lo) * 32 * n_group;
-    REQUIRE((threads + 255) / 256 < 0x7FFFFFFFull && (count + 255) / 256 < 0x7FFFFFFFull, "weighted Gram: batch too large");
+    REQUIRE((threads + 255) / 256 < 0x7FFFFFFFull, "weighted Gram: batch too large");
     for (uint32_t k = 0; k < 32; ++k) {
         if (!((m->wplane_bits >> k) & 1u)) continue;
         hipLaunchKernelGGL(rb_mask_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, ctx->stream, m->d_rb, m->d_rb_masked,
                            m->rb_nb, n_group, c_lo, c_hi, m->d_wplanes + (uint64_t)k * m->wplane_stride, m->wplane_stride);
         HIP_TRY(hipGetLastError());
-        if (gram_use_fp4()) {  // the plane's shift and the sum over planes happen in the Gram kernel's own stores
-            rc = launch_gram(ctx, m, m->d_rb_masked, d_wins, n_win, d_out, max_window_sites, (int)k);
-            if (rc) return rc;
-            continue;
-        }
-        rc = launch_gram(ctx, m, m->d_rb_masked, d_wins, n_win, d_tmp, max_window_sites);
+        // the plane's shift and the sum over planes happen in the Gram kernel's own stores
+        rc = launch_gram(ctx, m, m->d_rb_masked, d_wins, n_win, d_out, max_window_sites, (int)k);
         if (rc) return rc;
-        hipLaunchKernelGGL(gram_accumulate_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_out, d_tmp, k, count);
-        HIP_TRY(hipGetLastError());
     }
     return IMPOP_OK;
 }
@@ -1250,18 +804,17 @@ IMPOP_API int impop_pairwise_counts(impop_ctx *ctx, const impop_matrix *m, uint6
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
     void *d = nullptr;
-    rc = ctx_scratch(ctx, 2048 + (size_t)ld * ld * 8, &d);
+    rc = ctx_scratch(ctx, 2048 + (size_t)ld * ld * 4, &d);
     if (rc) return rc;
     Carve2 cv(d);
     GramWindow *d_w = cv.take<GramWindow>(1);
     int32_t *d_g = cv.take<int32_t>((size_t)ld * ld);
-    int32_t *d_t = cv.take<int32_t>((size_t)ld * ld);
     GramWindow *d_ow = cv.take<GramWindow>(1);
     uint32_t *d_add = cv.take<uint32_t>(1);
     GramWindow w;
     map_range(m, site_begin, site_end, &w.site_begin, &w.site_end);  // compacted: the kept sites of the range
     HIP_TRY(hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_gram_any(ctx, m, d_w, &w, 1, d_g, d_t, w.site_end - w.site_begin);
+    rc = launch_gram_any(ctx, m, d_w, &w, 1, d_g, w.site_end - w.site_begin);
     if (rc) return rc;
     rc = launch_gram_unflip(ctx, m, d_g, 1);  // exported counts / identities: the original polarity
     if (rc) return rc;
@@ -1295,13 +848,12 @@ IMPOP_API int impop_pairwise_identity(impop_ctx *ctx, const impop_matrix *m, uin
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
     void *d = nullptr;
-    rc = ctx_scratch(ctx, 4096 + (size_t)ld * ld * 8 + (size_t)n * n * 8, &d);
+    rc = ctx_scratch(ctx, 4096 + (size_t)ld * ld * 4 + (size_t)n * n * 8, &d);
     if (rc) return rc;
     Carve2 cv(d);
     GramWindow *d_w = cv.take<GramWindow>(1);
     uint64_t *d_W = cv.take<uint64_t>(1);
     int32_t *d_g = cv.take<int32_t>((size_t)ld * ld);
-    int32_t *d_t = cv.take<int32_t>((size_t)ld * ld);
     double *d_id = cv.take<double>((size_t)n * n);
     GramWindow *d_ow = cv.take<GramWindow>(1);
     uint32_t *d_add = cv.take<uint32_t>(1);
@@ -1310,7 +862,7 @@ IMPOP_API int impop_pairwise_identity(impop_ctx *ctx, const impop_matrix *m, uin
     const uint64_t W = window_W(m, site_begin, site_end);  // the window's ORIGINAL length
     HIP_TRY(hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_W, &W, 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_gram_any(ctx, m, d_w, &w, 1, d_g, d_t, w.site_end - w.site_begin);
+    rc = launch_gram_any(ctx, m, d_w, &w, 1, d_g, w.site_end - w.site_begin);
     if (rc) return rc;
     rc = launch_gram_unflip(ctx, m, d_g, 1);  // exported counts / identities: the original polarity
     if (rc) return rc;
@@ -1481,29 +1033,20 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
     }
     // Chunks of consecutive (in `ord`) windows whose cells fit the Gram scratch (<= ~8 GiB of 288): large
     // chunks keep the persistent Gram grid's last, partially filled round of tasks small next to the launch
-    // weighted matrices need a second Gram buffer (the plane partials) only where the planes are NOT walked inside the
-    // Gram task: the int8 kernel, or a window as heavy as 2^24 (launch_gram_any)
-    bool plane_buffer = !m->wt_prefix.empty();
-    if (plane_buffer && gram_planes_in_task()) {
-        uint64_t heaviest = 0;  // a Gram cell is a window or a piece of one: never heavier
-        for (uint64_t i = 0; i < n_windows; ++i) heaviest = std::max(heaviest, window_W(m, windows[i].site_begin, windows[i].site_end));
-        if (heaviest < GRAM_FUSED_WEIGHT_LIMIT) plane_buffer = false;
-    }
     lap("cells");
     const size_t gram_bytes = (size_t)ld * ld * 4;
-    uint64_t cap = ((plane_buffer ? 4ull : 8ull) << 30) / gram_bytes;  // (a chromosome of 50 kb windows — 4854 on chr2 — is one chunk)
+    uint64_t cap = (8ull << 30) / gram_bytes;  // (a chromosome of 50 kb windows — 4854 on chr2 — is one chunk)
     if (cap > 8192) cap = 8192;
     cap = std::min<uint64_t>(cap, std::max<uint64_t>(cells.size(), n_windows));  // a short call stages (and copies) short tables
     if (cap < 1) cap = 1;
     void *d = nullptr;
-    const size_t need = 4096 + cap * ((plane_buffer ? 2 : 1) * gram_bytes + sizeof(GramWindow) + 24 + sizeof(Pica2Out) + sizeof(HfstOut) +
+    const size_t need = 4096 + cap * (gram_bytes + sizeof(GramWindow) + 24 + sizeof(Pica2Out) + sizeof(HfstOut) +
                                       sizeof(impop_window_stats) + sizeof(impop_pairwise_stats) + 2 * sizeof(GramWindow) + 4 + 3584) + 16 * 256 +
                         (size_t)n * 16 + 8192;
     rc = ctx_scratch(ctx, need, &d);
     if (rc) return fail(rc);
     Carve2 cv(d);
     int32_t *d_g = cv.take<int32_t>(cap * (size_t)ld * ld);
-    int32_t *d_gt = plane_buffer ? cv.take<int32_t>(cap * (size_t)ld * ld) : nullptr;
     // per-chunk metadata: ONE contiguous region mirrored on the host, so that a chunk costs one host-to-device copy
     // (eight small pageable copies were ~0.3 ms of host time between two Gram launches)
     auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
@@ -1619,7 +1162,7 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
             // counts as uint16 where every count of the call fits (a count is at most its window's W): half the result bytes
             static const bool u16_off = [] { const char *e = getenv("IMPOP_GRAM_U16"); return e && e[0] == '0'; }();
             g16 = !u16_off && call_max_W < 65536;
-            rc = launch_gram_any(ctx, m, d_w, gw, n_cells, d_g, d_gt, max_sites, &g16);
+            rc = launch_gram_any(ctx, m, d_w, gw, n_cells, d_g, max_sites, &g16);
             if (rc) return fail(rc);
             if (ev1) PW_TRY(hipEventRecord(ev1, ctx->stream));
             if (params->identity_kind != IMPOP_IDENTITY_MATCH) {  // `match` sees Hamming distances only: polarity-invariant
@@ -1667,32 +1210,26 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
         }
         // pica2 grouping and the Fst sums are independent, latency-bound one-workgroup-per-window kernels: pica2 goes
         // to the side stream (fork behind the Gram launch, join before the finalize) so the two overlap
-        static const bool use_side = [] { const char *e = getenv("IMPOP_PW_SIDE_STREAM"); return !(e && e[0] == '0'); }();
-        if (!use_side) {  // A/B switch (tools/): the two kernels one after the other on the main stream
-            rc = launch_pica2(ctx, b, cnt, mask_p ? d_idx : nullptr, nP, nullptr, params->threshold, d_L, d_p, nullptr);
-            if (rc) return fail(rc);
-        } else {
-            if (!ctx->side) {
-                PW_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-                PW_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-                PW_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-            }
-            PW_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-            PW_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-            hipStream_t main_stream = ctx->stream;
-            ctx->stream = ctx->side;
-            rc = launch_pica2(ctx, b, cnt, mask_p ? d_idx : nullptr, nP, nullptr, params->threshold, d_L, d_p, nullptr);
-            ctx->stream = main_stream;
-            if (rc) return fail(rc);
-            PW_TRY(hipEventRecord(ctx->ev_join, ctx->side));
+        if (!ctx->side) {
+            PW_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+            PW_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+            PW_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
         }
+        PW_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
+        PW_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        hipStream_t main_stream = ctx->stream;
+        ctx->stream = ctx->side;
+        rc = launch_pica2(ctx, b, cnt, mask_p ? d_idx : nullptr, nP, nullptr, params->threshold, d_L, d_p, nullptr);
+        ctx->stream = main_stream;
+        if (rc) return fail(rc);
+        PW_TRY(hipEventRecord(ctx->ev_join, ctx->side));
         if (params->fst_method == 1)
             rc = launch_hud_grouped(ctx, b, cnt, d_ia, (uint32_t)ia.size(), d_ib, (uint32_t)ib.size(), nullptr, nullptr, params->threshold,
                                         d_L, d_h);
         else
             rc = launch_hfst(ctx, b, cnt, d_fa, d_fb, d_L, d_h);
         if (rc) return fail(rc);
-        if (use_side) PW_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        PW_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
         PairFinalIn in{d_p, d_h, d_s};
         rc = ensure_tajima_consts(ctx, nP >= 2 ? (int64_t)nP : 2);  // the cache may have been retargeted by another plan
         if (rc) return fail(rc);

@@ -341,7 +341,7 @@ def test_full_size_window_properties(ctx):
 
 def test_config5_shape_4096_haplotypes(ctx, oracle):
     """BASELINE config 5 shape (4096 haplotypes) at a size the oracle finishes in seconds: the
-    generic (wps = 128) scan kernel and the K-split int8-MFMA Gram kernel, integers bit-exact."""
+    generic (wps = 128) scan kernel and the K-split Gram kernel, integers bit-exact."""
     import impop_amd
     n, W = 4096, 6000
     bm = ctx.synthetic(n, W, seed=5, n_founder=16, p_founder=0.05, p_private_word=0.05, keep_hap_major=True)
@@ -702,27 +702,17 @@ def test_compacted_matrix_gives_identical_records(ctx, oracle):
         full_m.free()
 
 
-def test_int8_gram_kernel_still_exact():
-    """The int8 + look-up-table Gram kernel is kept for A/B measurements (IMPOP_GRAM_MFMA=i8; the FP4
-    bit-plane kernel is the default).  The switch is read once per process, hence the subprocess."""
-    import os
-    import subprocess
-    import sys
-    from conftest import ROOT
-    code = (
-        "import numpy as np, impop_amd\n"
-        "ctx = impop_amd.Context(0)\n"
-        "rng = np.random.default_rng(3)\n"
-        "m = (rng.random((131, 3000)) < 0.3).astype(np.uint8)\n"
-        "bm = ctx.upload_dense(m, keep_hap_major=True)\n"
-        "for s0, s1 in ((0, 3000), (17, 2049), (64, 128), (5, 6)):\n"
-        "    I = bm.pairwise_counts(s0, s1).astype(np.int64)\n"
-        "    w = m[:, s0:s1].astype(np.int64)\n"
-        "    assert (I == w @ w.T).all(), (s0, s1)\n"
-        "print('ok')\n")
-    env = dict(os.environ, IMPOP_GRAM_MFMA="i8", PYTHONPATH=ROOT)
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env, cwd=ROOT)
-    assert r.returncode == 0 and r.stdout.strip().endswith("ok"), r.stderr
+def test_pairwise_counts_exact_on_unaligned_ranges(ctx):
+    """pairwise_counts of a 131-haplotype matrix (a padded last tile) equals w @ w.T on the whole matrix, on a range
+    unaligned at both ends, on one 64-site cell and on a single site."""
+    rng = np.random.default_rng(3)
+    m = (rng.random((131, 3000)) < 0.3).astype(np.uint8)
+    bm = ctx.upload_dense(m, keep_hap_major=True)
+    for s0, s1 in ((0, 3000), (17, 2049), (64, 128), (5, 6)):
+        I = bm.pairwise_counts(s0, s1).astype(np.int64)
+        w = m[:, s0:s1].astype(np.int64)
+        assert (I == w @ w.T).all(), (s0, s1)
+    bm.free()
 
 
 def test_minor_allele_polarity_of_the_operand_is_invisible():

@@ -58,8 +58,7 @@ def main():
     out["pairwise_scan_465x50kb"] = {"windows": NW, "s_per_batch": dt, "windows_per_s": NW / dt, "groups_window0": G,
                                      "first_call_with_S_s": dt_first, "first_call_windows_per_s": NW / dt_first,
                                      "algorithmic_macs_per_window": macs, "algorithmic_macs_per_s": macs * NW / dt,
-                                     "frac_of_fp4_dense_peak_end_to_end": macs * NW / dt / FP4_DENSE_PEAK_MACS,
-                                     "gram_kernel": os.environ.get("IMPOP_GRAM_MFMA", "fp4")}
+                                     "frac_of_fp4_dense_peak_end_to_end": macs * NW / dt / FP4_DENSE_PEAK_MACS}
     # the same windows from the matrix compacted to its variable sites (impop_matrix_compact): identical records,
     # the contraction runs over the kept sites only (+ the per-window count of dropped all-ones sites)
     t0 = time.perf_counter()
