@@ -560,6 +560,12 @@ static int launch_gram(impop_ctx *ctx, const impop_matrix *m, const uint32_t *d_
         static const int forced = [] { const char *e = getenv("IMPOP_GRAM_CHAIN"); return e ? atoi(e) : 0; }();
         if (forced > 0 && ksplit == 1) chain = (uint32_t)forced;
     }
+    {  // IMPOP_TRACE=1: the launch configuration (the chain as gram_fp4_kernel applies it: only with >= 8 cells and no K-split)
+        static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
+        if (trace)
+            fprintf(stderr, "[impop_gram] cells=%u tiles=%u ksplit=%u chain=%u u16=%d fused_planes=%d\n", n_win, T, ksplit,
+                    (n_win >= 8 && ksplit == 1) ? chain : 1u, w16 ? 1 : 0, fused_planes ? 1 : 0);
+    }
     hipLaunchKernelGGL(gram_fp4_kernel, dim3(grid), dim3(256), 0, ctx->stream, d_rb, m->rb_nb, T, tasks_per_win, n_win, ksplit,
                        d_wins, d_out, m->n_hap_pad, (uint64_t)m->n_hap_pad * m->n_hap_pad, ctx->d_queue,
                        add_shift < 0 ? 0u : (uint32_t)add_shift, add_shift >= 0, wp, chain, w16 ? 1u : 0u);

@@ -755,6 +755,15 @@ for n, W in ((61, 1500), (96, 700), (200, 2100)):
     bm.set_site_weights(rng.integers(1, 40, size=W).astype(np.uint32))
     h.update(bm.pairwise_counts(0, W).tobytes())
     h.update(bm.pairwise_scan(wins[:2], None, inA, inB, kind="dice", threshold=0.98, round_digits=None).tobytes())
+# a production-size batch: enough (window, tile pair) tasks for one launch without K-split (uint16 counts, chained tickets)
+big = ctx.synthetic(200, 3000 * 300 + 64, seed=12, keep_hap_major=True)
+bw = [(k * 300 + k % 7, k * 300 + 300 - (k % 5) * 37, (0, 300, 50000)[k % 3]) for k in range(3000)]
+inA = (np.arange(200) % 3 == 0).astype(np.uint8); inB = (np.arange(200) % 3 == 1).astype(np.uint8)
+sys.stderr.write("@@batch\n"); sys.stderr.flush()
+for kind, fm in (("match", "direct"), ("dice", "grouped")):
+    r = big.pairwise_scan(bw, None, inA, inB, kind=kind, threshold=0.999, round_digits=4, fst_method=fm)
+    h.update(r.tobytes()); recs.append(r)
+sys.stderr.write("@@end\n"); sys.stderr.flush()
 np.save(sys.argv[1], np.concatenate(recs))
 print(h.hexdigest())
 """
@@ -765,18 +774,27 @@ print(h.hexdigest())
     # inside a family, equal across the two within the tolerance policy (their sums run in another order).
     import tempfile
     from conftest import stat_close
-    outs, recs = {}, {}
+    outs, recs, grams = {}, {}, {}
     with tempfile.TemporaryDirectory() as td:
         for tag, extra in (("default", {}), ("no polarity", {"IMPOP_NO_POLARITY": "1"}), ("no chains", {"IMPOP_GRAM_CHAIN": "1"}),
                            ("long chains", {"IMPOP_GRAM_CHAIN": "8"}), ("int32 counts", {"IMPOP_GRAM_U16": "0"}),
                            ("general", {"IMPOP_EPILOGUE_SMALL": "0"}), ("general, int32 counts", {"IMPOP_EPILOGUE_SMALL": "0", "IMPOP_GRAM_U16": "0"}),
                            ("general, runtime variants", {"IMPOP_EPILOGUE_SMALL": "0", "IMPOP_EPILOGUE_FAST": "0"})):
-            env = dict(os.environ, PYTHONPATH=ROOT, **extra)
+            env = dict(os.environ, PYTHONPATH=ROOT, IMPOP_TRACE="1", **extra)
             path = os.path.join(td, tag.replace(" ", "_").replace(",", "") + ".npy")
             r = subprocess.run([sys.executable, "-c", code, path], capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
             assert r.returncode == 0, (tag, r.stderr[-2000:])
             outs[tag] = r.stdout.strip()
             recs[tag] = np.load(path)
+            batch = r.stderr.split("@@batch\n", 1)[1].split("@@end\n", 1)[0]
+            grams[tag] = [dict(kv.split("=") for kv in ln.split("] ", 1)[1].split()) for ln in batch.splitlines()
+                          if ln.startswith("[impop_gram]")]
+    # the production-size batch really ran the configurations these variants are named after (read from the launch trace)
+    for tag, ks, u16, chain in (("default", "1", "1", None), ("no chains", "1", "1", "1"), ("long chains", "1", "1", "8"),
+                                ("int32 counts", "1", "0", None)):
+        g = grams[tag]
+        assert len(g) == 2 and all(x["ksplit"] == ks and x["u16"] == u16 for x in g), (tag, g)
+        assert all((x["chain"] == chain) if chain else int(x["chain"]) > 1 for x in g), (tag, g)
     small = {outs[t] for t in ("default", "no polarity", "no chains", "long chains", "int32 counts")}
     general = {outs[t] for t in outs if t.startswith("general")}
     assert len(outs["default"]) == 64 and len(small) == 1 and len(general) == 1, outs
@@ -1705,7 +1723,8 @@ def test_bit_matrix_grouping_beyond_4096_elements(ctx, oracle):
 
 
 def test_window_statistics_kernels_edge_shapes(ctx, oracle):
-    """csrc/stats_small.hip (pica2 / h-fst on disjoint and sliding windows of <= 512 haplotypes, `match`, uint16 counts): sizes around the
+    """csrc/stats_small.hip (pica2 / h-fst on disjoint and sliding windows of <= 512 haplotypes, `match`; at most 9 windows, so the
+    Gram launches are K-split and the counts int32 — uint16 counts: tests/test_gpu_batch_regimes.py): sizes around the
     64-position words and the 256-member switch of the h-fst rows, element lists (subset P), overlapping / empty / one-member
     populations, thresholds from "one group" (-1) to "nobody joins" (1.5), roundings 0..6 — every field against the oracle
     (tools/soak_small.py is the long-running form)."""
