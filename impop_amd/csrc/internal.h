@@ -154,6 +154,17 @@ struct impop_matrix {
     // the weights of the dropped sites every haplotype carries (a window's constant `add`), and of the kept columns' weights
     std::vector<uint64_t> ones_wt_prefix, kept_wt_prefix;
     std::vector<uint64_t> wt_prefix;  // weighted: prefix sums of the (ORIGINAL, if compacted) site weights, n + 1 entries
+    // variable-site scan index (layout.hip index_begin / index_finish), built with every full matrix unless the caller opts out
+    // (IMPOP_KEEP_DENSE_SCAN): the sites that vary among ALL haplotypes (0 < c < n) as an SB64 copy of their own (geometry vg:
+    // the matrix's wps / G / r, n_site = the number kept, the same slack block), plus per 64-site block of the matrix the mask
+    // of its kept sites and the number kept before it (n_block + 1 entries each; the last is {0, n_kept}), so a window edge s
+    // maps in O(1) to kept(s) = vbase[s >> 6] + popc(vmask[s >> 6] & ((1 << (s & 63)) - 1)).  Scan plans of an unweighted
+    // matrix stream d_vsb instead of d_sb (scan.hip); what the index holds depends on the matrix alone.
+    uint32_t *d_vsb = nullptr;                         // null: no index (vskip says why)
+    uint64_t *d_vmask = nullptr, *d_vbase = nullptr;   // one allocation, d_vmask first
+    impop::SbGeom vg;
+    uint64_t vsb_bytes = 0, vidx_bytes = 0;            // kept-site SB64 without slack; everything the index allocated
+    std::string vskip = "not built";
     int device = 0;
     mutable int users = 0;      // live scan plans referencing this matrix (impop_matrix_free refuses while > 0)
 };
@@ -180,8 +191,15 @@ int map_windows_device(impop_ctx *ctx, const impop_matrix *m, const impop_window
 uint64_t pos_lower_bound(const impop_matrix *m, uint64_t s);
 constexpr unsigned POS_COARSE_SHIFT = 12;
 
+// variable-site scan index: window edges in matrix coordinates -> kept-site index ranges of d_vsb (one thread per edge, no search)
+int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped);
+// the index a kept fraction above 1/IMPOP_INDEX_MAX_KEPT_INV of the sites is not built for (the dense stream is then nearly as short)
+constexpr uint64_t IMPOP_INDEX_MAX_KEPT_INV = 4;
+
 // layout.hip
-int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb);
+// d_mask / d_cnt (nullable): also write the variable-site mask of every block and its popcount (scan index)
+int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb,
+                    uint64_t *d_mask = nullptr, uint32_t *d_cnt = nullptr);
 // rb_nb == 0: plain hap-major rows of hm_stride dwords; else RB32 addressing with rb_nb cells per row group
 int launch_sb_to_hm(impop_ctx *ctx, const uint32_t *d_sb, const SbGeom &g, uint64_t blk_begin, uint64_t blk_end,
                     uint32_t *d_hm, uint64_t hm_stride, uint32_t n_rows, uint64_t rb_nb = 0, uint32_t phi_row = 0xFFFFFFFFu);

@@ -28,12 +28,15 @@ static SbGeom make_geom(uint32_t n_hap, uint64_t n_site) {
 // One wave per 64-site block.  For each 32-haplotype dword k, lanes 0..31 fetch the
 // 64-site word of haplotype 32k+lane; v_readlane broadcasts each of them and every lane
 // (= site) picks its own bit: a 32x64 bit transpose in 32 readlane+bfe+lshl_or steps.
+// mask / cnt (nullable): the variable-site mask of every block and its popcount (scan index), one ballot per block.
 __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restrict__ hm, uint64_t hm_stride,
                                                        uint32_t n_rows, uint32_t wps, uint32_t G, uint32_t r,
-                                                       uint64_t n_block, uint32_t *__restrict__ sb) {
+                                                       uint64_t n_block, uint32_t *__restrict__ sb, uint64_t n_site,
+                                                       uint32_t n_hap, uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;  // wave-uniform
+    uint32_t c = 0;
     for (uint32_t k = 0; k < wps; ++k) {
         uint64_t w = 0;
         const uint32_t row = 32 * k + lane;
@@ -48,6 +51,11 @@ __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restric
             out |= (uint32_t)((wj >> lane) & 1ull) << j;
         }
         sb[sb_index(wps, G, r, b, lane, k)] = out;
+        c += __popc(out);
+    }
+    if (mask) {
+        const uint64_t v = __ballot(b * 64 + lane < n_site && c > 0 && c < n_hap);
+        if (lane == 0) { mask[b] = v; cnt[b] = (uint32_t)__popcll(v); }
     }
 }
 
@@ -133,13 +141,14 @@ __global__ void hm_clear_tail_kernel(uint32_t *hm, uint64_t hm_stride, uint32_t 
     }
 }
 
-int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb) {
+int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb, uint64_t *d_mask,
+                    uint32_t *d_cnt) {
     if (g.n_block == 0) return IMPOP_OK;
     const uint64_t grid = (g.n_block + 3) / 4;
     REQUIRE(grid < 0x7FFFFFFFull, "matrix too long for one launch (%llu blocks)", (unsigned long long)g.n_block);
     const uint32_t n_rows = (g.n_hap + 95) / 96 * 96;
     hipLaunchKernelGGL(hm_to_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, d_hm, hm_stride, n_rows, g.wps,
-                       g.G, g.r, g.n_block, d_sb);
+                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, d_mask, d_cnt);
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }
@@ -167,7 +176,8 @@ struct SynthDev {
 // tables: fmask[f*wps + k] (haplotypes of founder f in dword k), then valid[k]
 __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_t *__restrict__ tables, uint32_t wps,
                                                        uint32_t G, uint32_t r, uint64_t n_block, uint64_t n_site,
-                                                       uint64_t site0, uint32_t *__restrict__ sb) {
+                                                       uint64_t site0, uint32_t *__restrict__ sb, uint32_t n_hap,
+                                                       uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;
@@ -182,6 +192,7 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
     for (uint32_t f = 0; f < p.n_founder; ++f)
         if ((uint32_t)(synth_hash(p.seed, 2 + f, s) >> 32) < p.thr_founder) fl |= 1u << f;
     const uint32_t *valid = tables + (uint64_t)p.n_founder * wps;
+    uint32_t c = 0;  // carriers of this lane's site: the scan index's mask comes from a ballot, not from a second pass
     for (uint32_t k = 0; k < wps; ++k) {
         uint32_t w = anc;
         uint32_t m = fl;
@@ -192,8 +203,13 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
         }
         const uint64_t h = synth_hash(p.seed, 64 + k, s);
         if ((uint32_t)(h >> 32) < p.thr_private) w ^= 1u << (uint32_t)(h & 31);
-        w &= valid[k];
-        sb[sb_index(wps, G, r, b, lane, k)] = live ? w : 0u;
+        w = live ? w & valid[k] : 0u;
+        c += __popc(w);
+        sb[sb_index(wps, G, r, b, lane, k)] = w;
+    }
+    if (mask) {
+        const uint64_t v = __ballot(live && c > 0 && c < n_hap);
+        if (lane == 0) { mask[b] = v; cnt[b] = (uint32_t)__popcll(v); }
     }
 }
 
@@ -240,6 +256,24 @@ static int alloc_matrix(impop_ctx *ctx, uint32_t n_hap, uint64_t n_site, bool wa
     return IMPOP_OK;
 }
 
+// variable-site scan index (built below, next to the compaction kernels it shares): index_begin allocates the per-block mask
+// and prefix (or records why there is none), the kernel that writes SB64 fills the mask by ballot, index_finish does the rest
+struct IndexBuild {
+    uint64_t *d_mask = nullptr;  // == m->d_vmask while the build goes on
+    uint32_t *d_cnt = nullptr;   // kept sites per block, n_block + 1 entries (inside d_tmp)
+    void *d_tmp = nullptr;       // transient: counts, chunk sums, total
+    uint64_t *d_pos = nullptr;   // transient: source site of every kept site
+    uint64_t n_chunks = 0;
+    IndexBuild() = default;
+    IndexBuild(const IndexBuild &) = delete;
+    ~IndexBuild() {
+        if (d_tmp) hipFree(d_tmp);
+        if (d_pos) hipFree(d_pos);
+    }
+};
+static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, IndexBuild &ib);
+static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib);
+
 }  // namespace impop
 
 using namespace impop;
@@ -280,7 +314,12 @@ IMPOP_API int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits, uint32_t
                            m->n_hap_pad, n_site, words * 2);
         if ((e = hipGetLastError()) != hipSuccess) return fail(hip_fail(e, "hm_clear_tail_kernel", __FILE__, __LINE__));
     }
-    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb);
+    IndexBuild ib;
+    rc = index_begin(ctx, m, keep_flags, ib);
+    if (rc) return fail(rc);
+    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.d_mask, ib.d_cnt);
+    if (rc) return fail(rc);
+    rc = index_finish(ctx, m, ib);
     if (rc) return fail(rc);
     if (want_rb) {
         rc = launch_sb_to_hm(ctx, m->d_sb, m->g, 0, m->g.n_block, m->d_rb, 0, m->n_hap_pad, m->rb_nb, m->phi_row);
@@ -335,6 +374,9 @@ IMPOP_API int impop_matrix_synthetic_slab(impop_ctx *ctx, uint32_t n_hap, uint64
     sp.n_founder = p->n_founder;
     sp.thr_founder = (uint32_t)(p->p_founder * 4294967296.0);
     sp.thr_private = (uint32_t)(p->p_private_word * 4294967296.0);
+    IndexBuild ib;
+    rc = index_begin(ctx, m, keep_flags, ib);
+    if (rc) return fail(rc);
     if (m->g.n_block) {
         const uint64_t grid = (m->g.n_block + 3) / 4;
         if (grid >= 0x7FFFFFFFull) {
@@ -342,7 +384,7 @@ IMPOP_API int impop_matrix_synthetic_slab(impop_ctx *ctx, uint32_t n_hap, uint64
             return fail(IMPOP_E_INVALID);
         }
         hipLaunchKernelGGL(synth_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, sp, (const uint32_t *)d_tab,
-                           wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb);
+                           wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb, n_hap, ib.d_mask, ib.d_cnt);
         if ((e = hipGetLastError()) != hipSuccess) return fail(hip_fail(e, "synth_sb_kernel", __FILE__, __LINE__));
         if (want_hm) {
             rc = launch_sb_to_hm(ctx, m->d_sb, m->g, 0, m->g.n_block, m->d_rb, 0, m->n_hap_pad, m->rb_nb, m->phi_row);
@@ -351,6 +393,8 @@ IMPOP_API int impop_matrix_synthetic_slab(impop_ctx *ctx, uint32_t n_hap, uint64
             if (rc) return fail(rc);
         }
     }
+    rc = index_finish(ctx, m, ib);
+    if (rc) return fail(rc);
     e = hipStreamSynchronize(ctx->stream);  // `tables` (pageable) must stay alive until the copy is done
     if (e != hipSuccess) return fail(hip_fail(e, "hipStreamSynchronize", __FILE__, __LINE__));
     *out = m;
@@ -582,6 +626,160 @@ void map_windows(const impop_matrix *m, const impop_window *windows, uint64_t n,
     }
 }
 
+// ---- variable-site scan index -------------------------------------------------------------------
+// The same sites impop_matrix_compact keeps, but as a second layout of the SAME matrix: windows stay in matrix coordinates,
+// an edge s maps to kept(s) = base[s >> 6] + popc(mask[s >> 6] & ((1 << (s & 63)) - 1)) with no search, and every scan plan
+// of an unweighted matrix streams the kept sites only (scan.hip).  A monomorphic site adds 0 to every sum c (n - c) of
+// every subset and segregates in none, so the records are those of the dense stream.
+
+// source site of every kept site (thread per source block; a block holds few kept sites, most hold none)
+__global__ __launch_bounds__(256) void kept_pos_kernel(const uint64_t *__restrict__ mask, const uint64_t *__restrict__ base,
+                                                       uint64_t n_block, uint64_t *__restrict__ pos) {
+    const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= n_block) return;
+    uint64_t v = mask[b], d = base[b];
+    while (v) {
+        pos[d++] = b * 64 + (uint64_t)__builtin_ctzll(v);
+        v &= v - 1;
+    }
+}
+
+// Destination-ordered gather: one wave per kept-site block, lane l = kept site 64j + l reads its source site's 16-byte
+// granules and the wave writes each granule of the compacted block as one coalesced 1 KiB store (the last, shorter granule
+// as r contiguous dwords per lane).  Lanes past n_kept write zeros: the last block is padded like any SB64 block.
+__global__ __launch_bounds__(256) void gather_kept_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
+                                                          const uint64_t *__restrict__ pos, uint64_t n_kept, uint64_t n_vblock,
+                                                          uint32_t *__restrict__ out) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t j = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (j >= n_vblock) return;  // wave-uniform
+    const uint64_t d = j * 64 + lane;
+    const bool live = d < n_kept;
+    const uint64_t s = live ? pos[d] : 0;
+    const uint32_t *src = sb + (s >> 6) * 64ull * wps;
+    const uint32_t sl = (uint32_t)(s & 63);
+    uint32_t *dst = out + j * 64ull * wps;
+    const uint32_t Gf = r == 4 ? G : G - 1;  // full 16-byte granules
+#pragma unroll 4
+    for (uint32_t g = 0; g < Gf; ++g) {
+        uint4 v = {0u, 0u, 0u, 0u};
+        if (live) v = *reinterpret_cast<const uint4 *>(src + (uint64_t)g * 256 + sl * 4);
+        *reinterpret_cast<uint4 *>(dst + (uint64_t)g * 256 + lane * 4) = v;
+    }
+    if (Gf < G)
+        for (uint32_t e = 0; e < r; ++e) dst[(uint64_t)Gf * 256 + lane * r + e] = live ? src[(uint64_t)Gf * 256 + sl * r + e] : 0u;
+}
+
+__global__ void map_edges_index_kernel(const uint64_t *__restrict__ mask, const uint64_t *__restrict__ base,
+                                       const impop_window *__restrict__ win, uint64_t n_win, impop_window *__restrict__ out) {
+    const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= 2 * n_win) return;
+    const uint64_t key = (e & 1) ? win[e >> 1].site_end : win[e >> 1].site_begin;  // <= n_site: entry n_block exists
+    const uint64_t kept = base[key >> 6] + (uint64_t)__popcll(mask[key >> 6] & ((1ull << (key & 63)) - 1ull));
+    if (e & 1) out[e >> 1].site_end = kept;
+    else { out[e >> 1].site_begin = kept; out[e >> 1].seq_len = win[e >> 1].seq_len; }
+}
+
+int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped) {
+    mapped.resize(n);
+    if (!n) return IMPOP_OK;
+    REQUIRE(m->d_vsb, "map_windows_index: the matrix has no scan index");
+    REQUIRE((2 * n + 255) / 256 < 0x7FFFFFFFull, "map_windows_index: too many windows");
+    void *d = nullptr;
+    const int rc = ctx_aux(ctx, 0, 2 * n * sizeof(impop_window), &d);  // as map_windows_device: idle outside the all-pairs path
+    if (rc) return rc;
+    impop_window *d_in = reinterpret_cast<impop_window *>(d), *d_out = d_in + n;
+    HIP_TRY(hipMemcpyAsync(d_in, windows, n * sizeof(impop_window), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(map_edges_index_kernel, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream, m->d_vmask,
+                       m->d_vbase, d_in, n, d_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(mapped.data(), d_out, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return IMPOP_OK;
+}
+
+static void index_drop(impop_matrix *m, std::string why) {
+    if (m->d_vmask) hipFree(m->d_vmask);
+    if (m->d_vsb) hipFree(m->d_vsb);
+    m->d_vmask = m->d_vbase = nullptr;
+    m->d_vsb = nullptr;
+    m->vg = SbGeom();
+    m->vsb_bytes = m->vidx_bytes = 0;
+    m->vskip = std::move(why);
+}
+
+// An allocation of the index that fails leaves the matrix without one: the error is cleared, the matrix is still made.
+static bool index_alloc(impop_matrix *m, void **p, size_t bytes, const char *what) {
+    if (hipMalloc(p, bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    *p = nullptr;
+    index_drop(m, std::string("hipMalloc of the ") + what + " failed");
+    return false;
+}
+
+static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, IndexBuild &ib) {
+    if (keep_flags & IMPOP_KEEP_DENSE_SCAN) {
+        m->vskip = "opted out (IMPOP_KEEP_DENSE_SCAN)";
+        return IMPOP_OK;
+    }
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const uint64_t ne = m->g.n_block + 1;  // one entry past the last block: an edge at n_site maps there when 64 | n_site
+    ib.n_chunks = (ne + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    void *meta = nullptr;
+    if (!index_alloc(m, &meta, 2 * ne * 8, "index mask")) return IMPOP_OK;
+    m->d_vmask = reinterpret_cast<uint64_t *>(meta);
+    m->d_vbase = m->d_vmask + ne;
+    if (!index_alloc(m, &ib.d_tmp, up(ne * 4) + up(ib.n_chunks * 8) + 256, "index counts")) return IMPOP_OK;
+    ib.d_mask = m->d_vmask;
+    ib.d_cnt = reinterpret_cast<uint32_t *>(ib.d_tmp);
+    HIP_TRY(hipMemsetAsync(m->d_vmask + m->g.n_block, 0, 8, ctx->stream));  // the entry past the last block keeps nothing
+    HIP_TRY(hipMemsetAsync(ib.d_cnt + m->g.n_block, 0, 4, ctx->stream));
+    return IMPOP_OK;
+}
+
+static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
+    if (!ib.d_mask) return IMPOP_OK;
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const SbGeom &g = m->g;
+    const uint64_t nb = g.n_block, ne = nb + 1;
+    uint64_t *d_chunk = reinterpret_cast<uint64_t *>((char *)ib.d_tmp + up(ne * 4));
+    uint64_t *d_total = reinterpret_cast<uint64_t *>((char *)d_chunk + up(ib.n_chunks * 8));
+    REQUIRE(ib.n_chunks < 0x7FFFFFFFull && (nb + 255) / 256 < 0x7FFFFFFFull, "scan index: matrix too long for one launch");
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)ib.n_chunks), dim3(256), 0, ctx->stream, ib.d_cnt, ne, d_chunk);
+    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, d_chunk, ib.n_chunks, d_total);
+    hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)ib.n_chunks), dim3(64), 0, ctx->stream, ib.d_cnt, ne, d_chunk, m->d_vbase);
+    HIP_TRY(hipGetLastError());
+    uint64_t n_kept = 0;
+    HIP_TRY(hipMemcpyAsync(&n_kept, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (n_kept * IMPOP_INDEX_MAX_KEPT_INV > g.n_site) {
+        char why[160];
+        snprintf(why, sizeof why, "%llu of %llu sites vary: above 1/%llu", (unsigned long long)n_kept, (unsigned long long)g.n_site,
+                 (unsigned long long)IMPOP_INDEX_MAX_KEPT_INV);
+        index_drop(m, why);
+        return IMPOP_OK;
+    }
+    m->vg = make_geom(g.n_hap, n_kept);
+    m->vsb_bytes = m->vg.n_block * 64ull * g.wps * 4ull;
+    const uint64_t slack = 64ull * g.wps * 4ull + 256;  // as alloc_matrix: one block past the end may be prefetched
+    void *vsb = nullptr;
+    if (!index_alloc(m, &vsb, m->vsb_bytes + slack, "kept-site layout")) return IMPOP_OK;
+    m->d_vsb = reinterpret_cast<uint32_t *>(vsb);
+    HIP_TRY(hipMemsetAsync((char *)vsb + m->vsb_bytes, 0, slack, ctx->stream));
+    if (n_kept) {
+        if (!index_alloc(m, (void **)&ib.d_pos, n_kept * 8, "kept-site positions")) return IMPOP_OK;
+        REQUIRE((m->vg.n_block + 3) / 4 < 0x7FFFFFFFull, "scan index: too many kept sites for one launch");
+        hipLaunchKernelGGL(kept_pos_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, m->d_vmask, m->d_vbase, nb,
+                           ib.d_pos);
+        hipLaunchKernelGGL(gather_kept_kernel, dim3((uint32_t)((m->vg.n_block + 3) / 4)), dim3(256), 0, ctx->stream, m->d_sb, g.wps,
+                           g.G, g.r, ib.d_pos, n_kept, m->vg.n_block, m->d_vsb);
+        HIP_TRY(hipGetLastError());
+    }
+    m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack;
+    m->vskip.clear();
+    return IMPOP_OK;
+}
+
 }  // namespace impop
 
 IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop_matrix **out) {
@@ -631,6 +829,7 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
         return code;
     };
     m->compact = true;
+    m->vskip = "compacted matrix (every site is kept)";
     m->n_site_orig = g.n_site;
     m->pos.resize(n_kept);
     if (n_kept) {
@@ -747,6 +946,14 @@ IMPOP_API int impop_matrix_info(const impop_matrix *m, uint32_t *n_hap, uint64_t
     return IMPOP_OK;
 }
 
+IMPOP_API int impop_matrix_scan_index_info(const impop_matrix *m, uint64_t *n_kept, uint64_t *index_bytes, char *why, size_t why_len) {
+    REQUIRE(m, "impop_matrix_scan_index_info: matrix is NULL");
+    if (n_kept) *n_kept = m->d_vsb ? m->vg.n_site : 0;
+    if (index_bytes) *index_bytes = m->d_vsb ? m->vidx_bytes : 0;
+    if (why && why_len) snprintf(why, why_len, "%s", m->d_vsb ? "" : m->vskip.c_str());
+    return IMPOP_OK;
+}
+
 IMPOP_API int impop_matrix_free(impop_ctx *ctx, impop_matrix *m) {
     if (!m) return IMPOP_OK;
     REQUIRE(m->users == 0, "impop_matrix_free: %d scan plan(s) still reference this matrix; destroy them first", m->users);
@@ -759,6 +966,8 @@ IMPOP_API int impop_matrix_free(impop_ctx *ctx, impop_matrix *m) {
     if (m->d_wt) hipFree(m->d_wt);
     if (m->d_onesmap) hipFree(m->d_onesmap);
     if (m->d_pos) hipFree(m->d_pos);
+    if (m->d_vmask) hipFree(m->d_vmask);
+    if (m->d_vsb) hipFree(m->d_vsb);
     matrix_drop_derived(m);
     delete m;
     return IMPOP_OK;

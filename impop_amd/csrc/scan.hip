@@ -751,6 +751,7 @@ using namespace impop;
 struct impop_scan_plan {
     impop_ctx *ctx = nullptr;
     const impop_matrix *m = nullptr;
+    const uint32_t *sb = nullptr;  // the layout launches stream: m->d_vsb (route "indexed", tiles in kept-site coordinates) or m->d_sb
     uint64_t n_windows = 0, n_tiles = 0, bytes_streamed = 0;
     PopSizes ps{};
     bool subset_p = false;
@@ -767,8 +768,9 @@ struct impop_scan_plan {
     size_t events_used = 0;
 };
 
-// W of every window in ORIGINAL coordinates: its length, or the sum of its columns' weights
-static int window_weights(const impop_matrix *m, const impop_window *windows, uint64_t n_windows, std::vector<WinDesc> &wd) {
+// W of every window in ORIGINAL coordinates: its length, or the sum of its columns' weights (tiles of compacted matrices and
+// of indexed plans are in kept-site coordinates, so build_tiles' lengths are not the windows')
+static int window_weights(const impop_matrix *m, bool indexed, const impop_window *windows, uint64_t n_windows, std::vector<WinDesc> &wd) {
     for (uint64_t i = 0; i < n_windows; ++i) {
         if (!m->wt_prefix.empty()) {
             wd[i].n_sites = m->wt_prefix[windows[i].site_end] - m->wt_prefix[windows[i].site_begin];
@@ -776,7 +778,7 @@ static int window_weights(const impop_matrix *m, const impop_window *windows, ui
             // checked against the same limit by their length)
             REQUIRE(wd[i].n_sites <= 0xFFFFFFFFull, "window %llu: the weights of its columns add up to %llu >= 2^32; split the window",
                     (unsigned long long)i, (unsigned long long)wd[i].n_sites);
-        } else if (m->compact) {
+        } else if (m->compact || indexed) {
             wd[i].n_sites = windows[i].site_end - windows[i].site_begin;
         }
     }
@@ -785,12 +787,16 @@ static int window_weights(const impop_matrix *m, const impop_window *windows, ui
 
 // Default tile: ~256 KB of matrix per workgroup, but never so large that a small job leaves CUs without
 // work (>= 16 tiles per CU wanted), and never below the 32 blocks the kernel was tuned with.
-static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
+// `windows` are in the coordinates of the layout streamed (kept-site coordinates for an indexed plan); the blocks they
+// cover are capped at that layout's length when windows of a compacted matrix or an index overlap.
+static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                    bool indexed) {
     // ~256 KB per tile; wide sites (the any-n kernel, wps > 16) go down to 4 blocks = one per wave
     const uint32_t by_bytes = m->g.wps > 16 ? std::max<uint32_t>(4, 1024 / m->g.wps) : std::max<uint32_t>(32, 1024 / m->g.wps);
     uint64_t blocks = 0;
     for (uint64_t i = 0; i < n_windows; ++i) blocks += (windows[i].site_end - windows[i].site_begin + 63) / 64;
     if (m->compact && blocks > m->g.n_block) blocks = m->g.n_block;
+    if (indexed && blocks > m->vg.n_block) blocks = m->vg.n_block;
     const uint64_t by_parallelism = blocks / (16ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
     return (uint32_t)std::max<uint64_t>(std::min<uint32_t>(32, by_bytes), std::min<uint64_t>(by_bytes, by_parallelism));
 }
@@ -815,6 +821,28 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
     p->masks.insert(p->masks.end(), mb.begin(), mb.end());
 }
 
+// the route of a scan of m: the variable-site index when the matrix has one and no site weights (d_wt is indexed by matrix site)
+static bool scan_indexed(const impop_matrix *m) { return m->d_vsb != nullptr && m->wt_prefix.empty(); }
+
+// windows (validated, matrix coordinates) -> the ranges of the layout the route streams
+static int map_for_route(impop_ctx *ctx, const impop_matrix *m, bool indexed, const impop_window *windows, uint64_t n_windows,
+                         std::vector<impop_window> &mapped) {
+    if (indexed) return map_windows_index(ctx, m, windows, n_windows, mapped);
+    map_windows(m, windows, n_windows, mapped);  // compacted matrix: original coordinates -> kept-site index ranges
+    return IMPOP_OK;
+}
+
+// IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it
+static void trace_route(const impop_matrix *m, bool indexed, uint64_t n_tiles, uint64_t bytes_streamed, uint64_t n_windows) {
+    static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
+    if (!trace) return;
+    const char *why = indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
+    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu%s%s\n",
+            indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(indexed ? m->vg.n_site : m->g.n_site),
+            (unsigned long long)n_tiles, (unsigned long long)bytes_streamed, (unsigned long long)n_windows, *why ? " why=" : "", why);
+    fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
+}
+
 template <int WPS>
 static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
     MaskArgs<WPS> mk;
@@ -824,10 +852,10 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
         mk.b[k] = p->masks[2 * WPS + k];
     }
     if (p->subset_p)
-        hipLaunchKernelGGL((scan_tiles_kernel<WPS, true>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->m->d_sb,
+        hipLaunchKernelGGL((scan_tiles_kernel<WPS, true>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb,
                            p->d_tiles, mk, p->ps, p->d_parts);
     else
-        hipLaunchKernelGGL((scan_tiles_kernel<WPS, false>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->m->d_sb,
+        hipLaunchKernelGGL((scan_tiles_kernel<WPS, false>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb,
                            p->d_tiles, mk, p->ps, p->d_parts);
 }
 
@@ -849,11 +877,7 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     }
     REQUIRE(prm.d_pi_mode >= 0 && prm.d_pi_mode <= 2, "impop_scan_params.d_pi_mode must be 0..2");
     REQUIRE(prm.s_scope == 0 || prm.s_scope == 1, "impop_scan_params.s_scope must be 0 or 1");
-    // default tile: ~160 KB of matrix per workgroup.  With few haplotypes a 32-block tile is only a few KB and
-    // the per-workgroup costs (launch, LDS reduction, partial store) bound the kernel instead of HBM:
-    // n = 32 ran at 2.6 TB/s with 32-block tiles and 5.0 TB/s with whole-window tiles (DESIGN.md 4.1)
-    uint32_t tile_blocks = prm.tile_blocks ? prm.tile_blocks : default_tile_blocks(ctx, m, windows, n_windows);
-    REQUIRE(tile_blocks <= 4096, "impop_scan_params.tile_blocks too large");
+    REQUIRE(prm.tile_blocks <= 4096, "impop_scan_params.tile_blocks too large");
     for (uint64_t i = 0; i < n_windows; ++i) {
         REQUIRE(windows[i].site_begin <= windows[i].site_end && windows[i].site_end <= matrix_span(m),
                 "window %llu: bad site range [%llu,%llu) for %llu sites", (unsigned long long)i,
@@ -863,8 +887,20 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
                 (unsigned long long)i);
     }
     HIP_TRY(hipSetDevice(ctx->device));
+    const bool indexed = scan_indexed(m);
+    std::vector<impop_window> mapped;
+    {
+        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped);
+        if (mrc) return mrc;
+    }
+    // default tile: ~160 KB of matrix per workgroup.  With few haplotypes a 32-block tile is only a few KB and
+    // the per-workgroup costs (launch, LDS reduction, partial store) bound the kernel instead of HBM:
+    // n = 32 ran at 2.6 TB/s with 32-block tiles and 5.0 TB/s with whole-window tiles (DESIGN.md 4.1)
+    const uint32_t tile_blocks = prm.tile_blocks ? prm.tile_blocks
+                                                 : default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, n_windows, indexed);
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
+    p->sb = indexed ? m->d_vsb : m->d_sb;
     m->users++;
     p->d_pi_mode = prm.d_pi_mode; p->s_scope = prm.s_scope;
     const uint32_t wps = m->g.wps;
@@ -872,20 +908,17 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
 
     std::vector<ScanTile> tiles;
     std::vector<WinDesc> wd;
-    {
-        std::vector<impop_window> mapped;  // compacted matrix: original coordinates -> kept-site index ranges
-        map_windows(m, windows, n_windows, mapped);
-        build_tiles(mapped.data(), n_windows, tile_blocks, wps, tiles, wd, p->bytes_streamed);
-    }
+    build_tiles(mapped.data(), n_windows, tile_blocks, wps, tiles, wd, p->bytes_streamed);
     p->n_tiles = tiles.size();
     auto fail = [&](int code) {
         impop_scan_plan_destroy(p);
         return code;
     };
     {
-        const int wrc = window_weights(m, windows, n_windows, wd);
+        const int wrc = window_weights(m, indexed, windows, n_windows, wd);
         if (wrc) return fail(wrc);
     }
+    trace_route(m, indexed, p->n_tiles, p->bytes_streamed, n_windows);
     uint64_t longest_range = 0;
     for (const WinDesc &w : wd) longest_range = std::max(longest_range, w.t1 - w.t0);
     p->finalize_tpw = longest_range > 2048 ? 256 : longest_range > 48 ? 64 : 1;
@@ -950,7 +983,7 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
     if (p->n_tiles && (weighted || wps > 16)) {
         const size_t lds = (size_t)3 * ((wps + 3) & ~3u) * 4;
 #define ANYN(SP, WT)                                                                                                     \
-    hipLaunchKernelGGL((scan_tiles_anyn_kernel<SP, WT>), dim3((uint32_t)p->n_tiles), dim3(256), lds, st, p->m->d_sb,     \
+    hipLaunchKernelGGL((scan_tiles_anyn_kernel<SP, WT>), dim3((uint32_t)p->n_tiles), dim3(256), lds, st, p->sb,          \
                        p->d_tiles, p->d_masks, wps, p->m->g.G, p->m->g.r, p->ps, p->m->d_wt, p->d_parts)
         if (weighted) { if (p->subset_p) ANYN(true, true); else ANYN(false, true); }
         else          { if (p->subset_p) ANYN(true, false); else ANYN(false, false); }
@@ -1088,16 +1121,16 @@ IMPOP_API int impop_site_counts(impop_ctx *ctx, const impop_matrix *m, const uin
 }
 
 template <int K>
-static int launch_multi(hipStream_t st, const impop_matrix *m, uint64_t n_tiles, const ScanTile *d_tiles, const uint32_t *d_masks,
-                        const uint32_t *d_n, uint64_t *d_parts, bool small) {
+static int launch_multi(hipStream_t st, const impop_matrix *m, const uint32_t *sb, uint64_t n_tiles, const ScanTile *d_tiles,
+                        const uint32_t *d_masks, const uint32_t *d_n, uint64_t *d_parts, bool small) {
     const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
     if (small) {
-        hipLaunchKernelGGL((scan_multi_kernel<K, true>), dim3((uint32_t)n_tiles), dim3(256), lds, st, m->d_sb, d_tiles, d_masks, d_n,
+        hipLaunchKernelGGL((scan_multi_kernel<K, true>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, d_tiles, d_masks, d_n,
                            m->g.wps, m->g.G, m->g.r, m->d_wt, d_parts);
     } else {
         if (lds > 48 * 1024)
             HIP_TRY(hipFuncSetAttribute((const void *)scan_multi_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((scan_multi_kernel<K, false>), dim3((uint32_t)n_tiles), dim3(256), lds, st, m->d_sb, d_tiles, d_masks, d_n,
+        hipLaunchKernelGGL((scan_multi_kernel<K, false>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, d_tiles, d_masks, d_n,
                            m->g.wps, m->g.G, m->g.r, m->d_wt, d_parts);
     }
     return IMPOP_OK;
@@ -1134,15 +1167,21 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
     std::vector<ScanTile> tiles;
     std::vector<WinDesc> wd;
     uint64_t bytes = 0;
-    const uint32_t tile_blocks_used = default_tile_blocks(ctx, m, windows, n_windows);
+    const bool indexed = scan_indexed(m);
+    std::vector<impop_window> mapped;
     {
-        std::vector<impop_window> mapped;
-        map_windows(m, windows, n_windows, mapped);
+        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped);
+        if (mrc) return mrc;
+    }
+    const uint32_t tile_blocks_used = default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, n_windows, indexed);
+    {
         build_tiles(mapped.data(), n_windows, tile_blocks_used, wps, tiles, wd, bytes);
-        const int wrc = window_weights(m, windows, n_windows, wd);
+        const int wrc = window_weights(m, indexed, windows, n_windows, wd);
         if (wrc) return wrc;
     }
+    const uint32_t *sb = indexed ? m->d_vsb : m->d_sb;
     REQUIRE(tiles.size() < 0x7FFFFFFFull, "impop_scan_multi: too many tiles");
+    trace_route(m, indexed, tiles.size(), bytes, n_windows);
     const size_t nt = tiles.size();
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t o_tiles = 0, o_wins = o_tiles + up(std::max<size_t>(nt, 1) * sizeof(ScanTile)),
@@ -1164,13 +1203,13 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
         // 32-bit per-lane partial sums: unweighted, <= 512 haplotypes, <= 1024 sites per lane and tile
         const bool small = m->wt_prefix.empty() && n <= 512 && tile_blocks_used <= 4096;
         switch (K) {
-            case 2: rc = launch_multi<2>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
-            case 3: rc = launch_multi<3>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
-            case 4: rc = launch_multi<4>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
-            case 5: rc = launch_multi<5>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
-            case 6: rc = launch_multi<6>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
-            case 7: rc = launch_multi<7>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
-            default: rc = launch_multi<8>(ctx->stream, m, nt, dt, dm, dn, dp, small); break;
+            case 2: rc = launch_multi<2>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            case 3: rc = launch_multi<3>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            case 4: rc = launch_multi<4>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            case 5: rc = launch_multi<5>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            case 6: rc = launch_multi<6>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            case 7: rc = launch_multi<7>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            default: rc = launch_multi<8>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
         }
         if (rc) return rc;
         HIP_TRY(hipGetLastError());

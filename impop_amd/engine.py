@@ -11,7 +11,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_HAP_MAJOR, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
+from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
                    PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
@@ -170,27 +170,30 @@ class Context:
             pass
 
     # ---- matrices -----------------------------------------------------------------
-    def upload(self, bits_hap_major: np.ndarray, n_site: int, keep_hap_major: bool = True) -> "BitMatrix":
+    def upload(self, bits_hap_major: np.ndarray, n_site: int, keep_hap_major: bool = True, dense_scan: bool = False) -> "BitMatrix":
+        """dense_scan=True: no variable-site scan index (IMPOP_KEEP_DENSE_SCAN); scans then stream every site."""
         b = np.ascontiguousarray(bits_hap_major, dtype=np.uint64)
         if b.ndim != 2:
             raise ValueError("bits must be [n_hap, words]")
         h = C.c_void_p()
-        keep = KEEP_SITE_BLOCKED | (KEEP_HAP_MAJOR if keep_hap_major else 0)
+        keep = KEEP_SITE_BLOCKED | (KEEP_HAP_MAJOR if keep_hap_major else 0) | (KEEP_DENSE_SCAN if dense_scan else 0)
         check(self._lib.impop_matrix_upload(self.handle, b.ctypes.data_as(C.POINTER(C.c_uint64)), b.shape[0], int(n_site),
                                             b.shape[1], keep, C.byref(h)))
         return BitMatrix(self, h)
 
-    def upload_dense(self, mat01, keep_hap_major: bool = True) -> "BitMatrix":
+    def upload_dense(self, mat01, keep_hap_major: bool = True, dense_scan: bool = False) -> "BitMatrix":
         m = np.asarray(mat01)
-        return self.upload(pack_hap_major(m), m.shape[1], keep_hap_major)
+        return self.upload(pack_hap_major(m), m.shape[1], keep_hap_major, dense_scan)
 
     def synthetic(self, n_hap: int, n_site: int, seed: int = 20251031, n_founder: int = 8, p_founder: float = 1e-3,
-                  p_private_word: float = 3.2e-3, keep_hap_major: bool = False, site_begin: int = 0) -> "BitMatrix":
+                  p_private_word: float = 3.2e-3, keep_hap_major: bool = False, site_begin: int = 0,
+                  dense_scan: bool = False) -> "BitMatrix":
         """Sites [site_begin, site_begin + n_site) of the synthetic chromosome of `seed` (counter-based generator: a slab is
-        a cut of the whole, impop_matrix_synthetic_slab); site 0 of the result is global site `site_begin`."""
+        a cut of the whole, impop_matrix_synthetic_slab); site 0 of the result is global site `site_begin`.
+        dense_scan=True: no variable-site scan index (IMPOP_KEEP_DENSE_SCAN)."""
         p = SynthParams(int(seed), int(n_founder), float(p_founder), float(p_private_word))
         h = C.c_void_p()
-        keep = KEEP_SITE_BLOCKED | (KEEP_HAP_MAJOR if keep_hap_major else 0)
+        keep = KEEP_SITE_BLOCKED | (KEEP_HAP_MAJOR if keep_hap_major else 0) | (KEEP_DENSE_SCAN if dense_scan else 0)
         check(self._lib.impop_matrix_synthetic_slab(self.handle, int(n_hap), int(site_begin), int(n_site), C.byref(p), keep, C.byref(h)))
         return BitMatrix(self, h)
 
@@ -343,6 +346,13 @@ class BitMatrix:
         bm = BitMatrix(self.ctx, out)
         bm.compacted_from_sites = self.n_site
         return bm
+
+    def scan_index_info(self) -> dict:
+        """The variable-site scan index: {"n_kept", "index_bytes" (0 = none), "why" (reason there is none, else "")}."""
+        k, b = C.c_uint64(), C.c_uint64()
+        why = C.create_string_buffer(256)
+        check(self.ctx._lib.impop_matrix_scan_index_info(self.handle, C.byref(k), C.byref(b), why, len(why)))
+        return {"n_kept": k.value, "index_bytes": b.value, "why": why.value.decode()}
 
     def positions(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """Original site index of the kept sites of a compacted matrix."""

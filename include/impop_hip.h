@@ -74,6 +74,18 @@ int impop_ctx_device_name(impop_ctx *ctx, char *buf, size_t buflen);
  * keep flags: which device layouts to materialise. */
 #define IMPOP_KEEP_SITE_BLOCKED 1u /* SB64 layout used by impop_scan (always kept) */
 #define IMPOP_KEEP_HAP_MAJOR 2u    /* haplotype-major (row-group-blocked) copy needed by impop_pairwise_* */
+/* Opt out of the variable-site scan index.  Without this flag every matrix made by impop_matrix_upload /
+ * impop_matrix_synthetic[_slab] also gets, built on the device when it is made, a second SB64 layout of the sites
+ * that vary among ALL haplotypes (0 < c_s < n) plus, per 64-site block, the mask of those sites and the number
+ * kept before it.  A monomorphic site adds 0 to every sum_s c(n-c) of every subset and segregates in none, so
+ * impop_scan / impop_scan_plan_* / impop_scan_multi / impop_scan_sharded on an unweighted matrix stream the kept
+ * sites only and return the records of the dense stream, byte for byte (window edges map in O(1); n_sites stays the
+ * window's length).  The index depends on the matrix alone, not on windows or masks.  It is not built when more
+ * than 1/4 of the sites vary (the dense stream is then barely longer) or when its device memory cannot be had (the
+ * matrix is made all the same); impop_matrix_scan_index_info says which.  Weighted matrices (site weights are
+ * indexed by matrix site) always stream the dense layout; impop_afs, impop_site_counts, impop_ehh, download and the
+ * all-pairs path never use the index.  impop_matrix_info's device_bytes does not count it. */
+#define IMPOP_KEEP_DENSE_SCAN 4u
 
 int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits_hap_major, uint32_t n_hap, uint64_t n_site,
                         uint64_t row_stride_words, uint32_t keep_flags, impop_matrix **out);
@@ -133,6 +145,10 @@ int impop_matrix_positions(const impop_matrix *m, uint64_t first, uint64_t count
                            uint64_t *n_site_orig);
 int impop_matrix_info(const impop_matrix *m, uint32_t *n_hap, uint64_t *n_site, uint64_t *device_bytes,
                       uint32_t *bytes_per_site);
+/* The variable-site scan index (see IMPOP_KEEP_DENSE_SCAN): n_kept = sites it holds, index_bytes = device memory it
+ * takes (0 = the matrix has none; compacted matrices never have one, all their sites are kept); why (nullable, why_len
+ * bytes) receives the reason there is none, or "" when there is one.  All outputs nullable. */
+int impop_matrix_scan_index_info(const impop_matrix *m, uint64_t *n_kept, uint64_t *index_bytes, char *why, size_t why_len);
 int impop_matrix_free(impop_ctx *ctx, impop_matrix *m);
 
 /* ---- windowed scan: pi + Hudson Fst + Tajima's D + S in one pass ------------
@@ -195,6 +211,9 @@ int impop_scan_plan_set_masks(impop_scan_plan *plan, const uint64_t *mask_p, con
 int impop_scan_plan_launch(impop_scan_plan *plan, void *d_out);
 /* Synchronise and copy the plan's internal result buffer to the host. */
 int impop_scan_plan_fetch(impop_scan_plan *plan, impop_window_stats *out_host);
+/* bytes_streamed: layout bytes one launch reads (of the kept-site layout when the plan streams the scan index).
+ * Under IMPOP_TRACE=1 impop_scan_plan_create prints one line per plan on stderr:
+ *   [impop_scan] route=<indexed|dense|compact> kept_sites=<n> tiles=<n> bytes_streamed=<n> windows=<n> [why=<reason>] */
 int impop_scan_plan_info(const impop_scan_plan *plan, uint64_t *n_tiles, uint64_t *bytes_streamed);
 /* Measurement aid: with timing enabled every launch brackets the streaming kernel
  * (not the tiny epilogue) with hipEvents on the context's stream; elapsed() synchronises
