@@ -164,7 +164,19 @@ struct impop_matrix {
     uint64_t *d_vmask = nullptr, *d_vbase = nullptr;   // one allocation, d_vmask first
     impop::SbGeom vg;
     uint64_t vsb_bytes = 0, vidx_bytes = 0;            // kept-site SB64 without slack; everything the index allocated
+    uint64_t n_vkept = 0;                              // variable sites (rare + common when split)
     std::string vskip = "not built";
+    // rare/common split of the index (layout.hip rare_entries_kernel): a kept site is RARE when min(c, n - c) <= IMPOP_RARE_MAX.
+    // Then d_vsb (geometry vg) holds the COMMON kept sites only, and d_vrare one 8-byte entry per rare site in site order:
+    //     bits 0..1 = m (1..3 listed haplotypes), bit 15 = the listed haplotypes carry 0 (else 1), bits 16k+16..16k+31 = index k
+    //     (unused slots 0xFFFF); listed = carriers of the allele with count <= n/2, ties to the 1-allele.
+    // Per 64-site block of the matrix: d_cmask = mask of its common sites, d_cbase = common sites before it (n_block + 1
+    // entries each, one allocation); rare(s) = kept(s) - common(s).  d_vrare null: no split (rskip says why), d_vsb holds every
+    // kept site as before.
+    uint64_t *d_vrare = nullptr;
+    uint64_t *d_cmask = nullptr, *d_cbase = nullptr;
+    uint64_t n_vrare = 0;
+    std::string rskip = "not built";
     int device = 0;
     mutable int users = 0;      // live scan plans referencing this matrix (impop_matrix_free refuses while > 0)
 };
@@ -192,14 +204,19 @@ uint64_t pos_lower_bound(const impop_matrix *m, uint64_t s);
 constexpr unsigned POS_COARSE_SHIFT = 12;
 
 // variable-site scan index: window edges in matrix coordinates -> kept-site index ranges of d_vsb (one thread per edge, no search)
-int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped);
 // the index a kept fraction above 1/IMPOP_INDEX_MAX_KEPT_INV of the sites is not built for (the dense stream is then nearly as short)
 constexpr uint64_t IMPOP_INDEX_MAX_KEPT_INV = 4;
+// rare kept sites: min(c, n - c) <= IMPOP_RARE_MAX (one 8-byte entry lists their minor-allele carriers)
+constexpr uint32_t IMPOP_RARE_MAX = 3;
+// split index: the same edges also as common-site (`mapped`) and rare-entry (`rare`) ranges; rare == nullptr: kept-site ranges
+int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
+                      std::vector<impop_window> *rare);
 
 // layout.hip
-// d_mask / d_cnt (nullable): also write the variable-site mask of every block and its popcount (scan index)
+// d_mask / d_cnt (nullable): also write the variable-site mask of every block and its popcount (scan index);
+// d_cmask / d_ccnt (nullable): the same for the common sites, min(c, n - c) > IMPOP_RARE_MAX (split index)
 int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb,
-                    uint64_t *d_mask = nullptr, uint32_t *d_cnt = nullptr);
+                    uint64_t *d_mask = nullptr, uint32_t *d_cnt = nullptr, uint64_t *d_cmask = nullptr, uint32_t *d_ccnt = nullptr);
 // rb_nb == 0: plain hap-major rows of hm_stride dwords; else RB32 addressing with rb_nb cells per row group
 int launch_sb_to_hm(impop_ctx *ctx, const uint32_t *d_sb, const SbGeom &g, uint64_t blk_begin, uint64_t blk_end,
                     uint32_t *d_hm, uint64_t hm_stride, uint32_t n_rows, uint64_t rb_nb = 0, uint32_t phi_row = 0xFFFFFFFFu);

@@ -32,7 +32,8 @@ static SbGeom make_geom(uint32_t n_hap, uint64_t n_site) {
 __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restrict__ hm, uint64_t hm_stride,
                                                        uint32_t n_rows, uint32_t wps, uint32_t G, uint32_t r,
                                                        uint64_t n_block, uint32_t *__restrict__ sb, uint64_t n_site,
-                                                       uint32_t n_hap, uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt) {
+                                                       uint32_t n_hap, uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt,
+                                                       uint64_t *__restrict__ cmask, uint32_t *__restrict__ ccnt) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;  // wave-uniform
@@ -56,6 +57,10 @@ __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restric
     if (mask) {
         const uint64_t v = __ballot(b * 64 + lane < n_site && c > 0 && c < n_hap);
         if (lane == 0) { mask[b] = v; cnt[b] = (uint32_t)__popcll(v); }
+    }
+    if (cmask) {
+        const uint64_t v = __ballot(b * 64 + lane < n_site && c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX);
+        if (lane == 0) { cmask[b] = v; ccnt[b] = (uint32_t)__popcll(v); }
     }
 }
 
@@ -142,13 +147,13 @@ __global__ void hm_clear_tail_kernel(uint32_t *hm, uint64_t hm_stride, uint32_t 
 }
 
 int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb, uint64_t *d_mask,
-                    uint32_t *d_cnt) {
+                    uint32_t *d_cnt, uint64_t *d_cmask, uint32_t *d_ccnt) {
     if (g.n_block == 0) return IMPOP_OK;
     const uint64_t grid = (g.n_block + 3) / 4;
     REQUIRE(grid < 0x7FFFFFFFull, "matrix too long for one launch (%llu blocks)", (unsigned long long)g.n_block);
     const uint32_t n_rows = (g.n_hap + 95) / 96 * 96;
     hipLaunchKernelGGL(hm_to_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, d_hm, hm_stride, n_rows, g.wps,
-                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, d_mask, d_cnt);
+                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, d_mask, d_cnt, d_cmask, d_ccnt);
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }
@@ -177,7 +182,8 @@ struct SynthDev {
 __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_t *__restrict__ tables, uint32_t wps,
                                                        uint32_t G, uint32_t r, uint64_t n_block, uint64_t n_site,
                                                        uint64_t site0, uint32_t *__restrict__ sb, uint32_t n_hap,
-                                                       uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt) {
+                                                       uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt, uint64_t *__restrict__ cmask,
+                                                       uint32_t *__restrict__ ccnt) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;
@@ -210,6 +216,10 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
     if (mask) {
         const uint64_t v = __ballot(live && c > 0 && c < n_hap);
         if (lane == 0) { mask[b] = v; cnt[b] = (uint32_t)__popcll(v); }
+    }
+    if (cmask) {  // split index: the common kept sites, min(c, n - c) > IMPOP_RARE_MAX
+        const uint64_t v = __ballot(live && c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX);
+        if (lane == 0) { cmask[b] = v; ccnt[b] = (uint32_t)__popcll(v); }
     }
 }
 
@@ -261,7 +271,9 @@ static int alloc_matrix(impop_ctx *ctx, uint32_t n_hap, uint64_t n_site, bool wa
 struct IndexBuild {
     uint64_t *d_mask = nullptr;  // == m->d_vmask while the build goes on
     uint32_t *d_cnt = nullptr;   // kept sites per block, n_block + 1 entries (inside d_tmp)
-    void *d_tmp = nullptr;       // transient: counts, chunk sums, total
+    uint64_t *d_cmask = nullptr; // == m->d_cmask: split index wanted (else null)
+    uint32_t *d_ccnt = nullptr;  // common sites per block (inside d_tmp)
+    void *d_tmp = nullptr;       // transient: counts, chunk sums, totals
     uint64_t *d_pos = nullptr;   // transient: source site of every kept site
     uint64_t n_chunks = 0;
     IndexBuild() = default;
@@ -317,7 +329,7 @@ IMPOP_API int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits, uint32_t
     IndexBuild ib;
     rc = index_begin(ctx, m, keep_flags, ib);
     if (rc) return fail(rc);
-    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.d_mask, ib.d_cnt);
+    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.d_mask, ib.d_cnt, ib.d_cmask, ib.d_ccnt);
     if (rc) return fail(rc);
     rc = index_finish(ctx, m, ib);
     if (rc) return fail(rc);
@@ -384,7 +396,8 @@ IMPOP_API int impop_matrix_synthetic_slab(impop_ctx *ctx, uint32_t n_hap, uint64
             return fail(IMPOP_E_INVALID);
         }
         hipLaunchKernelGGL(synth_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, sp, (const uint32_t *)d_tab,
-                           wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb, n_hap, ib.d_mask, ib.d_cnt);
+                           wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb, n_hap, ib.d_mask, ib.d_cnt,
+                           ib.d_cmask, ib.d_ccnt);
         if ((e = hipGetLastError()) != hipSuccess) return fail(hip_fail(e, "synth_sb_kernel", __FILE__, __LINE__));
         if (want_hm) {
             rc = launch_sb_to_hm(ctx, m->d_sb, m->g, 0, m->g.n_block, m->d_rb, 0, m->n_hap_pad, m->rb_nb, m->phi_row);
@@ -670,32 +683,87 @@ __global__ __launch_bounds__(256) void gather_kept_kernel(const uint32_t *__rest
         for (uint32_t e = 0; e < r; ++e) dst[(uint64_t)Gf * 256 + lane * r + e] = live ? src[(uint64_t)Gf * 256 + sl * r + e] : 0u;
 }
 
+// Rare kept sites -> 8-byte entries (layout: internal.h, d_vrare).  One thread per source block walks its rare sites (a few per
+// block) and reads each one's wps dwords twice: the count picks the allele to list, then the first (at most three) carriers of it.
+__global__ __launch_bounds__(256) void rare_entries_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
+                                                           uint32_t n_hap, const uint64_t *__restrict__ vmask,
+                                                           const uint64_t *__restrict__ vbase, const uint64_t *__restrict__ cmask,
+                                                           const uint64_t *__restrict__ cbase, uint64_t n_block,
+                                                           uint64_t *__restrict__ out) {
+    const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= n_block) return;
+    uint64_t v = vmask[b] & ~cmask[b], d = vbase[b] - cbase[b];
+    while (v) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(v);
+        v &= v - 1;
+        uint32_t c = 0;
+        for (uint32_t k = 0; k < wps; ++k) c += __popc(sb[sb_index(wps, G, r, b, l, k)]);
+        const bool zeros = 2 * c > n_hap;  // list the carriers of 0 (padding haplotypes excluded below)
+        uint64_t slots = 0xFFFFFFFFFFFF0000ull;
+        uint32_t m = 0;
+        for (uint32_t k = 0; k < wps && m < IMPOP_RARE_MAX; ++k) {
+            uint32_t w = sb[sb_index(wps, G, r, b, l, k)];
+            if (zeros) w = ~w & (32 * k + 32 <= n_hap ? 0xFFFFFFFFu : (1u << (n_hap - 32 * k)) - 1u);
+            while (w && m < IMPOP_RARE_MAX) {
+                const uint64_t h = 32 * k + (uint32_t)__builtin_ctz(w);
+                w &= w - 1;
+                slots = (slots & ~(0xFFFFull << (16 * m + 16))) | (h << (16 * m + 16));
+                ++m;
+            }
+        }
+        out[d++] = slots | m | (zeros ? 0x8000u : 0u);
+    }
+}
+
+// edge s -> kept(s); split index: -> common(s) into `out` and kept(s) - common(s) into `out_rare`
 __global__ void map_edges_index_kernel(const uint64_t *__restrict__ mask, const uint64_t *__restrict__ base,
-                                       const impop_window *__restrict__ win, uint64_t n_win, impop_window *__restrict__ out) {
+                                       const uint64_t *__restrict__ cmask, const uint64_t *__restrict__ cbase,
+                                       const impop_window *__restrict__ win, uint64_t n_win, impop_window *__restrict__ out,
+                                       impop_window *__restrict__ out_rare) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= 2 * n_win) return;
     const uint64_t key = (e & 1) ? win[e >> 1].site_end : win[e >> 1].site_begin;  // <= n_site: entry n_block exists
-    const uint64_t kept = base[key >> 6] + (uint64_t)__popcll(mask[key >> 6] & ((1ull << (key & 63)) - 1ull));
-    if (e & 1) out[e >> 1].site_end = kept;
-    else { out[e >> 1].site_begin = kept; out[e >> 1].seq_len = win[e >> 1].seq_len; }
+    const uint64_t below = (1ull << (key & 63)) - 1ull;
+    const uint64_t kept = base[key >> 6] + (uint64_t)__popcll(mask[key >> 6] & below);
+    uint64_t v = kept;
+    if (cmask) {
+        v = cbase[key >> 6] + (uint64_t)__popcll(cmask[key >> 6] & below);
+        if (e & 1) out_rare[e >> 1].site_end = kept - v;
+        else { out_rare[e >> 1].site_begin = kept - v; out_rare[e >> 1].seq_len = win[e >> 1].seq_len; }
+    }
+    if (e & 1) out[e >> 1].site_end = v;
+    else { out[e >> 1].site_begin = v; out[e >> 1].seq_len = win[e >> 1].seq_len; }
 }
 
-int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped) {
+int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
+                      std::vector<impop_window> *rare) {
     mapped.resize(n);
+    const bool split = rare && m->d_vrare;
+    if (split) rare->resize(n);
     if (!n) return IMPOP_OK;
     REQUIRE(m->d_vsb, "map_windows_index: the matrix has no scan index");
     REQUIRE((2 * n + 255) / 256 < 0x7FFFFFFFull, "map_windows_index: too many windows");
     void *d = nullptr;
-    const int rc = ctx_aux(ctx, 0, 2 * n * sizeof(impop_window), &d);  // as map_windows_device: idle outside the all-pairs path
+    const int rc = ctx_aux(ctx, 0, 3 * n * sizeof(impop_window), &d);  // as map_windows_device: idle outside the all-pairs path
     if (rc) return rc;
-    impop_window *d_in = reinterpret_cast<impop_window *>(d), *d_out = d_in + n;
+    impop_window *d_in = reinterpret_cast<impop_window *>(d), *d_out = d_in + n, *d_rare = d_out + n;
     HIP_TRY(hipMemcpyAsync(d_in, windows, n * sizeof(impop_window), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(map_edges_index_kernel, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream, m->d_vmask,
-                       m->d_vbase, d_in, n, d_out);
+                       m->d_vbase, split ? m->d_cmask : nullptr, split ? m->d_cbase : nullptr, d_in, n, d_out, d_rare);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(mapped.data(), d_out, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
+    if (split) HIP_TRY(hipMemcpyAsync(rare->data(), d_rare, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return IMPOP_OK;
+}
+
+static void split_drop(impop_matrix *m, std::string why) {
+    if (m->d_cmask) hipFree(m->d_cmask);
+    if (m->d_vrare) hipFree(m->d_vrare);
+    m->d_cmask = m->d_cbase = nullptr;
+    m->d_vrare = nullptr;
+    m->n_vrare = 0;
+    m->rskip = std::move(why);
 }
 
 static void index_drop(impop_matrix *m, std::string why) {
@@ -705,6 +773,8 @@ static void index_drop(impop_matrix *m, std::string why) {
     m->d_vsb = nullptr;
     m->vg = SbGeom();
     m->vsb_bytes = m->vidx_bytes = 0;
+    m->n_vkept = 0;
+    split_drop(m, "no scan index");
     m->vskip = std::move(why);
 }
 
@@ -717,41 +787,82 @@ static bool index_alloc(impop_matrix *m, void **p, size_t bytes, const char *wha
     return false;
 }
 
+// d_tmp: kept counts | common counts | chunk sums (kept) | chunk sums (common) | the two totals
+struct IndexTmp {
+    size_t o_ccnt, o_chunk, o_cchunk, o_total, bytes;
+    IndexTmp(uint64_t ne, uint64_t n_chunks) {
+        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        o_ccnt = up(ne * 4); o_chunk = o_ccnt + up(ne * 4); o_cchunk = o_chunk + up(n_chunks * 8); o_total = o_cchunk + up(n_chunks * 8);
+        bytes = o_total + 256;
+    }
+};
+
 static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, IndexBuild &ib) {
     if (keep_flags & IMPOP_KEEP_DENSE_SCAN) {
         m->vskip = "opted out (IMPOP_KEEP_DENSE_SCAN)";
+        m->rskip = "no scan index";
         return IMPOP_OK;
     }
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const uint64_t ne = m->g.n_block + 1;  // one entry past the last block: an edge at n_site maps there when 64 | n_site
     ib.n_chunks = (ne + SCAN_CHUNK - 1) / SCAN_CHUNK;
     void *meta = nullptr;
     if (!index_alloc(m, &meta, 2 * ne * 8, "index mask")) return IMPOP_OK;
     m->d_vmask = reinterpret_cast<uint64_t *>(meta);
     m->d_vbase = m->d_vmask + ne;
-    if (!index_alloc(m, &ib.d_tmp, up(ne * 4) + up(ib.n_chunks * 8) + 256, "index counts")) return IMPOP_OK;
+    const IndexTmp lay(ne, ib.n_chunks);
+    if (!index_alloc(m, &ib.d_tmp, lay.bytes, "index counts")) return IMPOP_OK;
     ib.d_mask = m->d_vmask;
     ib.d_cnt = reinterpret_cast<uint32_t *>(ib.d_tmp);
     HIP_TRY(hipMemsetAsync(m->d_vmask + m->g.n_block, 0, 8, ctx->stream));  // the entry past the last block keeps nothing
     HIP_TRY(hipMemsetAsync(ib.d_cnt + m->g.n_block, 0, 4, ctx->stream));
+    // the rare/common split: an entry (8 B) must be narrower than a row, and its haplotype indices fit 16 bits
+    if (keep_flags & IMPOP_KEEP_NO_RARE_SPLIT) {
+        m->rskip = "opted out (IMPOP_KEEP_NO_RARE_SPLIT)";
+    } else if (m->g.wps <= 2) {
+        m->rskip = "n_hap <= 64: a row is no wider than an 8-byte rare entry";
+    } else if (m->g.n_hap > 65535) {
+        m->rskip = "n_hap > 65535: haplotype indices do not fit 16 bits";
+    } else {
+        void *cm = nullptr;
+        if (hipMalloc(&cm, 2 * ne * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            m->rskip = "hipMalloc of the common-site mask failed";
+        } else {
+            m->d_cmask = reinterpret_cast<uint64_t *>(cm);
+            m->d_cbase = m->d_cmask + ne;
+            ib.d_cmask = m->d_cmask;
+            ib.d_ccnt = reinterpret_cast<uint32_t *>((char *)ib.d_tmp + lay.o_ccnt);
+            HIP_TRY(hipMemsetAsync(m->d_cmask + m->g.n_block, 0, 8, ctx->stream));
+            HIP_TRY(hipMemsetAsync(ib.d_ccnt + m->g.n_block, 0, 4, ctx->stream));
+        }
+    }
     return IMPOP_OK;
+}
+
+// exclusive prefix over the n_block + 1 per-block counts: base[b] = sum of cnt[< b]; the total goes to *d_total
+static void block_prefix(impop_ctx *ctx, const uint32_t *cnt, uint64_t ne, uint64_t n_chunks, uint64_t *d_chunk, uint64_t *d_total,
+                         uint64_t *base) {
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)n_chunks), dim3(256), 0, ctx->stream, cnt, ne, d_chunk);
+    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, d_chunk, n_chunks, d_total);
+    hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)n_chunks), dim3(64), 0, ctx->stream, cnt, ne, d_chunk, base);
 }
 
 static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
     if (!ib.d_mask) return IMPOP_OK;
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const SbGeom &g = m->g;
     const uint64_t nb = g.n_block, ne = nb + 1;
-    uint64_t *d_chunk = reinterpret_cast<uint64_t *>((char *)ib.d_tmp + up(ne * 4));
-    uint64_t *d_total = reinterpret_cast<uint64_t *>((char *)d_chunk + up(ib.n_chunks * 8));
+    const IndexTmp lay(ne, ib.n_chunks);
+    char *tmp = (char *)ib.d_tmp;
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(tmp + lay.o_total);  // [0] kept, [1] common
     REQUIRE(ib.n_chunks < 0x7FFFFFFFull && (nb + 255) / 256 < 0x7FFFFFFFull, "scan index: matrix too long for one launch");
-    hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)ib.n_chunks), dim3(256), 0, ctx->stream, ib.d_cnt, ne, d_chunk);
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, d_chunk, ib.n_chunks, d_total);
-    hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)ib.n_chunks), dim3(64), 0, ctx->stream, ib.d_cnt, ne, d_chunk, m->d_vbase);
+    block_prefix(ctx, ib.d_cnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_chunk), d_total, m->d_vbase);
+    if (ib.d_cmask)
+        block_prefix(ctx, ib.d_ccnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_cchunk), d_total + 1, m->d_cbase);
     HIP_TRY(hipGetLastError());
-    uint64_t n_kept = 0;
-    HIP_TRY(hipMemcpyAsync(&n_kept, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t totals[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, d_total, ib.d_cmask ? 16 : 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const uint64_t n_kept = totals[0];
     if (n_kept * IMPOP_INDEX_MAX_KEPT_INV > g.n_site) {
         char why[160];
         snprintf(why, sizeof why, "%llu of %llu sites vary: above 1/%llu", (unsigned long long)n_kept, (unsigned long long)g.n_site,
@@ -759,23 +870,43 @@ static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
         index_drop(m, why);
         return IMPOP_OK;
     }
-    m->vg = make_geom(g.n_hap, n_kept);
+    // the rare entries first: when they cannot be had, d_vsb holds every kept site (the unsplit index)
+    if (ib.d_cmask) {
+        m->n_vrare = n_kept - totals[1];
+        void *rare = nullptr;
+        if (hipMalloc(&rare, std::max<uint64_t>(m->n_vrare, 1) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            split_drop(m, "hipMalloc of the rare entries failed");
+        } else {
+            m->d_vrare = reinterpret_cast<uint64_t *>(rare);
+            m->rskip.clear();
+        }
+    }
+    const bool split = m->d_vrare != nullptr;
+    const uint64_t *smask = split ? m->d_cmask : m->d_vmask, *sbase = split ? m->d_cbase : m->d_vbase;
+    const uint64_t n_stream = split ? totals[1] : n_kept;  // sites of the SB64 copy
+    m->n_vkept = n_kept;
+    m->vg = make_geom(g.n_hap, n_stream);
     m->vsb_bytes = m->vg.n_block * 64ull * g.wps * 4ull;
     const uint64_t slack = 64ull * g.wps * 4ull + 256;  // as alloc_matrix: one block past the end may be prefetched
     void *vsb = nullptr;
     if (!index_alloc(m, &vsb, m->vsb_bytes + slack, "kept-site layout")) return IMPOP_OK;
     m->d_vsb = reinterpret_cast<uint32_t *>(vsb);
     HIP_TRY(hipMemsetAsync((char *)vsb + m->vsb_bytes, 0, slack, ctx->stream));
-    if (n_kept) {
-        if (!index_alloc(m, (void **)&ib.d_pos, n_kept * 8, "kept-site positions")) return IMPOP_OK;
+    if (n_stream) {
+        if (!index_alloc(m, (void **)&ib.d_pos, n_stream * 8, "kept-site positions")) return IMPOP_OK;
         REQUIRE((m->vg.n_block + 3) / 4 < 0x7FFFFFFFull, "scan index: too many kept sites for one launch");
-        hipLaunchKernelGGL(kept_pos_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, m->d_vmask, m->d_vbase, nb,
-                           ib.d_pos);
+        hipLaunchKernelGGL(kept_pos_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, smask, sbase, nb, ib.d_pos);
         hipLaunchKernelGGL(gather_kept_kernel, dim3((uint32_t)((m->vg.n_block + 3) / 4)), dim3(256), 0, ctx->stream, m->d_sb, g.wps,
-                           g.G, g.r, ib.d_pos, n_kept, m->vg.n_block, m->d_vsb);
+                           g.G, g.r, ib.d_pos, n_stream, m->vg.n_block, m->d_vsb);
         HIP_TRY(hipGetLastError());
     }
-    m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack;
+    if (split && m->n_vrare) {
+        hipLaunchKernelGGL(rare_entries_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, m->d_sb, g.wps, g.G, g.r,
+                           g.n_hap, m->d_vmask, m->d_vbase, m->d_cmask, m->d_cbase, nb, m->d_vrare);
+        HIP_TRY(hipGetLastError());
+    }
+    m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack + (split ? 2 * ne * 8 + std::max<uint64_t>(m->n_vrare, 1) * 8 : 0);
     m->vskip.clear();
     return IMPOP_OK;
 }
@@ -830,6 +961,7 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     };
     m->compact = true;
     m->vskip = "compacted matrix (every site is kept)";
+    m->rskip = "no scan index";
     m->n_site_orig = g.n_site;
     m->pos.resize(n_kept);
     if (n_kept) {
@@ -948,9 +1080,20 @@ IMPOP_API int impop_matrix_info(const impop_matrix *m, uint32_t *n_hap, uint64_t
 
 IMPOP_API int impop_matrix_scan_index_info(const impop_matrix *m, uint64_t *n_kept, uint64_t *index_bytes, char *why, size_t why_len) {
     REQUIRE(m, "impop_matrix_scan_index_info: matrix is NULL");
-    if (n_kept) *n_kept = m->d_vsb ? m->vg.n_site : 0;
+    if (n_kept) *n_kept = m->d_vsb ? m->n_vkept : 0;
     if (index_bytes) *index_bytes = m->d_vsb ? m->vidx_bytes : 0;
     if (why && why_len) snprintf(why, why_len, "%s", m->d_vsb ? "" : m->vskip.c_str());
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_matrix_scan_split_info(const impop_matrix *m, uint64_t *n_rare, uint64_t *n_common, uint64_t *rare_bytes,
+                                           char *why, size_t why_len) {
+    REQUIRE(m, "impop_matrix_scan_split_info: matrix is NULL");
+    const bool split = m->d_vsb && m->d_vrare;
+    if (n_rare) *n_rare = split ? m->n_vrare : 0;
+    if (n_common) *n_common = split ? m->vg.n_site : 0;
+    if (rare_bytes) *rare_bytes = split ? m->n_vrare * 8 : 0;
+    if (why && why_len) snprintf(why, why_len, "%s", split ? "" : m->rskip.c_str());
     return IMPOP_OK;
 }
 
@@ -968,6 +1111,8 @@ IMPOP_API int impop_matrix_free(impop_ctx *ctx, impop_matrix *m) {
     if (m->d_pos) hipFree(m->d_pos);
     if (m->d_vmask) hipFree(m->d_vmask);
     if (m->d_vsb) hipFree(m->d_vsb);
+    if (m->d_cmask) hipFree(m->d_cmask);
+    if (m->d_vrare) hipFree(m->d_vrare);
     matrix_drop_derived(m);
     delete m;
     return IMPOP_OK;

@@ -18,8 +18,11 @@
 
 namespace impop {
 
+// site_begin..site_end: sites of the SB64 layout streamed; rare_begin..rare_end: entries of the split index's rare stream
+// (internal.h, d_vrare).  Either range may be empty.
 struct ScanTile {
     uint64_t site_begin, site_end;
+    uint64_t rare_begin, rare_end;
 };
 struct TilePartial {  // 48 B
     uint32_t s_all, s_p, s_a, s_b;
@@ -51,6 +54,9 @@ struct MaskArgs {
 #endif
 #ifndef IMPOP_SCAN_MIN_WAVES
 #define IMPOP_SCAN_MIN_WAVES 6 // __launch_bounds__ 2nd argument (waves per SIMD)
+#endif
+#ifndef IMPOP_SCAN_SEPARATE_STREAMS
+#define IMPOP_SCAN_SEPARATE_STREAMS 0  // 1: a segment's rare entries and common rows go to separate tiles (A/B builds only)
 #endif
 
 template <typename T>
@@ -108,6 +114,34 @@ struct LaneAcc32 {
 // One site per lane.  No validity test here: lanes outside the tile had their words zeroed by the caller
 // (only the first / last block of a tile can be partial), and all-zero words add nothing to any counter.
 // Segregating test 0 < c < n as ONE unsigned compare: (c - 1) < (n - 1)  (false for n = 0 or 1 as well).
+template <bool SUBSET_P>
+__device__ __forceinline__ void counts_accumulate(uint32_t c, uint32_t cP, uint32_t cA, uint32_t cB, const PopSizes &ps,
+                                                  LaneAcc32 &acc) {
+    if (!SUBSET_P) cP = c;
+    acc.s_all += (c - 1u) < (ps.n - 1u);
+    acc.s_p += (cP - 1u) < (ps.nP - 1u);
+    acc.s_a += (cA - 1u) < (ps.nA - 1u);
+    acc.s_b += (cB - 1u) < (ps.nB - 1u);
+    const uint32_t rA = ps.nA - cA, rB = ps.nB - cB;
+    acc.q_p += __umul24(cP, ps.nP - cP);
+    acc.q_a += __umul24(cA, rA);
+    acc.q_b += __umul24(cB, rB);
+    acc.q_ab += __umul24(cA, rB) + __umul24(cB, rA);
+}
+
+// the same for the 64-bit accumulators of the any-n kernel (n <= 65535: every product is below 2^32)
+template <bool SUBSET_P>
+__device__ __forceinline__ void counts_accumulate(uint32_t c, uint32_t cP, uint32_t cA, uint32_t cB, const PopSizes &ps,
+                                                  LaneAcc &acc) {
+    if (!SUBSET_P) cP = c;
+    acc.s_all += (c - 1u) < (ps.n - 1u);
+    acc.s_p += (cP - 1u) < (ps.nP - 1u);
+    acc.s_a += (cA - 1u) < (ps.nA - 1u);
+    acc.s_b += (cB - 1u) < (ps.nB - 1u);
+    acc.q_p += cP * (ps.nP - cP); acc.q_a += cA * (ps.nA - cA); acc.q_b += cB * (ps.nB - cB);
+    acc.q_ab += (uint64_t)(cA * (ps.nB - cB)) + (uint64_t)(cB * (ps.nA - cA));
+}
+
 template <int WPS, bool SUBSET_P>
 __device__ __forceinline__ void site_accumulate(const uint32_t (&w)[WPS], const MaskArgs<WPS> &mk, const PopSizes &ps,
                                                 LaneAcc32 &acc) {
@@ -119,16 +153,51 @@ __device__ __forceinline__ void site_accumulate(const uint32_t (&w)[WPS], const 
         cA += __popc(w[k] & mk.a[k]);
         cB += __popc(w[k] & mk.b[k]);
     }
-    if (!SUBSET_P) cP = c;
-    acc.s_all += (c - 1u) < (ps.n - 1u);
-    acc.s_p += (cP - 1u) < (ps.nP - 1u);
-    acc.s_a += (cA - 1u) < (ps.nA - 1u);
-    acc.s_b += (cB - 1u) < (ps.nB - 1u);
-    const uint32_t rA = ps.nA - cA, rB = ps.nB - cB;
-    acc.q_p += __umul24(cP, ps.nP - cP);
-    acc.q_a += __umul24(cA, rA);
-    acc.q_b += __umul24(cB, rB);
-    acc.q_ab += __umul24(cA, rB) + __umul24(cB, rA);
+    counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
+}
+
+// A rare entry (internal.h, d_vrare) lists the m <= 3 carriers of its minor allele: their P / A / B membership comes from bit
+// tests on the masks in LDS (per-lane addresses, a few dwords), and the counts of the 1-allele follow, mirrored through n - m,
+// nP - mP, ... when the listed haplotypes carry 0 (then every 0-carrier is listed).  Exact integers as for a row.
+template <bool SUBSET_P>
+__device__ __forceinline__ void rare_counts(uint64_t v, const uint32_t *lp, const uint32_t *la, const uint32_t *lb, const PopSizes &ps,
+                                            uint32_t &c, uint32_t &cP, uint32_t &cA, uint32_t &cB) {
+    const uint32_t m = (uint32_t)v & 3u;
+    uint32_t mP = 0, mA = 0, mB = 0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+        if ((uint32_t)i < m) {
+            const uint32_t h = (uint32_t)(v >> (16 * i + 16)) & 0xFFFFu, wd = h >> 5, bit = h & 31u;
+            mA += (la[wd] >> bit) & 1u;
+            mB += (lb[wd] >> bit) & 1u;
+            if (SUBSET_P) mP += (lp[wd] >> bit) & 1u;
+        }
+    if (v & 0x8000u) { c = ps.n - m; cP = ps.nP - mP; cA = ps.nA - mA; cB = ps.nB - mB; }
+    else { c = m; cP = mP; cA = mA; cB = mB; }
+}
+
+// entries [e0, e1) of a tile, thread t takes e0 + t, e0 + t + 256, ...: RU coalesced 512-byte wave loads in flight per wave
+template <bool SUBSET_P, typename Acc>
+__device__ __forceinline__ void rare_range(const uint64_t *__restrict__ rare, uint64_t e0, uint64_t e1, const uint32_t *lp,
+                                           const uint32_t *la, const uint32_t *lb, const PopSizes &ps, Acc &acc) {
+    constexpr int RU = 4;
+    uint64_t e = e0 + threadIdx.x;
+    for (; e + 256 * (RU - 1) < e1; e += 256 * RU) {
+        uint64_t v[RU];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) v[u] = stream_load(rare + e + 256 * u);
+#pragma unroll
+        for (int u = 0; u < RU; ++u) {
+            uint32_t c, cP, cA, cB;
+            rare_counts<SUBSET_P>(v[u], lp, la, lb, ps, c, cP, cA, cB);
+            counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
+        }
+    }
+    for (; e < e1; e += 256) {
+        uint32_t c, cP, cA, cB;
+        rare_counts<SUBSET_P>(stream_load(rare + e), lp, la, lb, ps, c, cP, cA, cB);
+        counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
+    }
 }
 
 __device__ __forceinline__ void tile_reduce_store(LaneAcc &acc, TilePartial *out) {
@@ -161,11 +230,12 @@ __device__ __forceinline__ void tile_reduce_store(LaneAcc &acc, TilePartial *out
 
 template <int WPS, bool SUBSET_P>
 __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(const uint32_t *__restrict__ sb,
+                                                                               const uint64_t *__restrict__ rare,
                                                                                const ScanTile *__restrict__ tiles,
                                                                                const MaskArgs<WPS> mk, const PopSizes ps,
                                                                                TilePartial *__restrict__ out) {
     const ScanTile t = tiles[blockIdx.x];
-    const uint64_t b0 = t.site_begin >> 6, b1 = (t.site_end + 63) >> 6;
+    const uint64_t b0 = t.site_begin >> 6, b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
     // wave index through readfirstlane: block addresses and the loop stay scalar (SGPR) state
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     LaneAcc32 acc;
@@ -200,6 +270,15 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         load_site<WPS>(sb + b * (64ull * WPS), lane, w0);
         trim(w0, b);
         site_accumulate<WPS, SUBSET_P>(w0, mk, ps, acc);
+    }
+    if (t.rare_end > t.rare_begin) {  // workgroup-uniform
+        __shared__ uint32_t rmk[3][WPS];
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < WPS; ++k) { rmk[0][k] = mk.p[k]; rmk[1][k] = mk.a[k]; rmk[2][k] = mk.b[k]; }
+        }
+        __syncthreads();
+        rare_range<SUBSET_P>(rare, t.rare_begin, t.rare_end, rmk[0], rmk[1], rmk[2], ps, acc);
     }
     LaneAcc wide;
     wide.s_all = acc.s_all; wide.s_p = acc.s_p; wide.s_a = acc.s_a; wide.s_b = acc.s_b;
@@ -236,7 +315,8 @@ __device__ __forceinline__ void anyn_granule(const u32v4 v, const uint32_t *lp, 
 }
 
 template <bool SUBSET_P, bool WEIGHTED>
-__global__ __launch_bounds__(256, 4) void scan_tiles_anyn_kernel(const uint32_t *__restrict__ sb, const ScanTile *__restrict__ tiles,
+__global__ __launch_bounds__(256, 4) void scan_tiles_anyn_kernel(const uint32_t *__restrict__ sb, const uint64_t *__restrict__ rare,
+                                                                 const ScanTile *__restrict__ tiles,
                                                                  const uint32_t *__restrict__ masks, uint32_t wps, uint32_t G,
                                                                  uint32_t r, const PopSizes ps, const uint32_t *__restrict__ weights,
                                                                  TilePartial *__restrict__ out) {
@@ -249,7 +329,7 @@ __global__ __launch_bounds__(256, 4) void scan_tiles_anyn_kernel(const uint32_t 
     }
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    const uint64_t b0 = t.site_begin >> 6, b1 = (t.site_end + 63) >> 6;
+    const uint64_t b0 = t.site_begin >> 6, b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     // full 16-byte granules: all of them when the last one holds 4 dwords per site (r == 4: its addressing is
     // the full granules'), else all but the last, whose r = 1..3 dwords per site are read one by one
@@ -314,6 +394,9 @@ __global__ __launch_bounds__(256, 4) void scan_tiles_anyn_kernel(const uint32_t 
                 acc.q_p += qp; acc.q_a += qa; acc.q_b += qb; acc.q_ab += qab;
             }
         }
+    }
+    if constexpr (!WEIGHTED) {  // weighted matrices never stream the split index
+        if (t.rare_end > t.rare_begin) rare_range<SUBSET_P>(rare, t.rare_begin, t.rare_end, lp, la, lb, ps, acc);
     }
     tile_reduce_store(acc, out);
 }
@@ -452,7 +535,8 @@ __global__ __launch_bounds__(256) void site_counts_kernel(const uint32_t *__rest
 // follow once per lane and tile (every partial sum stays below 2^32: <= 1024 sites per lane and tile, products < 2^18);
 // the first version did three to four 64-bit multiplies per pair and site, which made K = 8 VALU-bound.
 template <int K, bool SMALL>
-__global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restrict__ sb, const ScanTile *__restrict__ tiles,
+__global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restrict__ sb, const uint64_t *__restrict__ rare,
+                                                         const ScanTile *__restrict__ tiles,
                                                          const uint32_t *__restrict__ masks /* K x wps */,
                                                          const uint32_t *__restrict__ pop_n /* K */, uint32_t wps,
                                                          uint32_t G, uint32_t r, const uint32_t *__restrict__ weights /* nullable */,
@@ -468,7 +552,7 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
     }
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    const uint64_t b0 = t.site_begin >> 6, b1 = (t.site_end + 63) >> 6;
+    const uint64_t b0 = t.site_begin >> 6, b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
     const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     uint32_t nk[K];
 #pragma unroll
@@ -514,29 +598,30 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
                 for (int k = 0; k < K; ++k) c[k] += __popc(tl[j] & mk_lds[k * wps4 + 4 * Gf + j]);
             }
     };
-    auto tally = [&](uint64_t b, const uint32_t (&c)[K]) {
-        const uint64_t s = b * 64 + lane;
-        if (s >= t.site_begin && s < t.site_end) {
-            if (SMALL) {
-                int pi = 0;
+    // wt: the site's weight (unweighted: 1)
+    auto tally_counts = [&](const uint32_t (&c)[K], uint64_t wt) {
+        if (SMALL) {
+            int pi = 0;
 #pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    s1[k] += c[k];
-                    q2[k] += __umul24(c[k], c[k]);
+            for (int k = 0; k < K; ++k) {
+                s1[k] += c[k];
+                q2[k] += __umul24(c[k], c[k]);
 #pragma unroll
-                    for (int l = k + 1; l < K; ++l) px[pi++] += __umul24(c[k], c[l]);
-                }
-            } else {
-                const uint64_t wt = weights ? weights[s] : 1;  // wave-uniform choice
-                int pi = K;
+                for (int l = k + 1; l < K; ++l) px[pi++] += __umul24(c[k], c[l]);
+            }
+        } else {
+            int pi = K;
 #pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    acc[k] += wt * (c[k] * (nk[k] - c[k]));
+            for (int k = 0; k < K; ++k) {
+                acc[k] += wt * (c[k] * (nk[k] - c[k]));
 #pragma unroll
-                    for (int l = k + 1; l < K; ++l) acc[pi++] += wt * (c[k] * (nk[l] - c[l]) + c[l] * (nk[k] - c[k]));
-                }
+                for (int l = k + 1; l < K; ++l) acc[pi++] += wt * (c[k] * (nk[l] - c[l]) + c[l] * (nk[k] - c[k]));
             }
         }
+    };
+    auto tally = [&](uint64_t b, const uint32_t (&c)[K]) {
+        const uint64_t s = b * 64 + lane;
+        if (s >= t.site_begin && s < t.site_end) tally_counts(c, !SMALL && weights ? weights[s] : 1);  // wave-uniform choice
     };
     uint64_t b = b0 + wave;
     if (Gf <= (uint32_t)MU) {
@@ -575,6 +660,25 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
         }
         count_tail(tl, c);
         tally(b, c);
+    }
+    // rare entries of the split index (unweighted matrices only): each population's count from bit tests of the listed
+    // haplotypes, mirrored through n_k - m_k when they carry 0 (rare_counts)
+    for (uint64_t e = t.rare_begin + threadIdx.x; e < t.rare_end; e += 256) {
+        const uint64_t v = stream_load(rare + e);
+        const uint32_t m = (uint32_t)v & 3u;
+        uint32_t c[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            uint32_t mk = 0;
+#pragma unroll
+            for (int i = 0; i < 3; ++i)
+                if ((uint32_t)i < m) {
+                    const uint32_t h = (uint32_t)(v >> (16 * i + 16)) & 0xFFFFu;
+                    mk += (mk_lds[k * wps4 + (h >> 5)] >> (h & 31u)) & 1u;
+                }
+            c[k] = (v & 0x8000u) ? nk[k] - mk : mk;
+        }
+        tally_counts(c, 1);
     }
     if (SMALL) {
         int pi = K;
@@ -690,42 +794,70 @@ static uint32_t popcount_vec(const std::vector<uint32_t> &v) {
 // windows -> elementary segments between sorted window boundaries (a segment is tiled iff some
 // window covers it, and exactly once however many windows overlap it) -> tiles of <= tile_blocks
 // 64-site blocks; every window becomes a contiguous tile range [t0, t1).
-static void build_tiles(const impop_window *windows, uint64_t n_windows, uint32_t tile_blocks, uint32_t wps,
+// rare (nullable, split index): the same windows as rare-entry ranges.  A window edge is then the pair (site, entry); both map
+// monotonically from the matrix coordinate, so the pairs are ordered as the edges are.  A segment's blocks and entries are cut
+// into the same number of tiles by their bytes (an entry is 8 B, tile_blocks blocks the budget): one workgroup reads a share
+// of both streams.  Without rare entries the tiles are those of the unsplit index.
+static void build_tiles(const impop_window *windows, const impop_window *rare, uint64_t n_windows, uint32_t tile_blocks, uint32_t wps,
                         std::vector<ScanTile> &tiles, std::vector<WinDesc> &wd, uint64_t &bytes_streamed) {
-    std::vector<uint64_t> cuts;
+    struct Cut {
+        uint64_t c, r;
+        bool operator<(const Cut &o) const { return c < o.c || (c == o.c && r < o.r); }
+        bool operator==(const Cut &o) const { return c == o.c && r == o.r; }
+    };
+    auto lo = [&](uint64_t i) { return Cut{windows[i].site_begin, rare ? rare[i].site_begin : 0}; };
+    auto hi = [&](uint64_t i) { return Cut{windows[i].site_end, rare ? rare[i].site_end : 0}; };
+    auto nonempty = [&](uint64_t i) {
+        return windows[i].site_end > windows[i].site_begin || (rare && rare[i].site_end > rare[i].site_begin);
+    };
+    std::vector<Cut> cuts;
     cuts.reserve(2 * n_windows);
     for (uint64_t i = 0; i < n_windows; ++i)
-        if (windows[i].site_end > windows[i].site_begin) {
-            cuts.push_back(windows[i].site_begin);
-            cuts.push_back(windows[i].site_end);
+        if (nonempty(i)) {
+            cuts.push_back(lo(i));
+            cuts.push_back(hi(i));
         }
     std::sort(cuts.begin(), cuts.end());
     cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
     std::vector<int64_t> cover(cuts.size() + 1, 0);
-    auto cut_index = [&](uint64_t s) { return (size_t)(std::lower_bound(cuts.begin(), cuts.end(), s) - cuts.begin()); };
+    auto cut_index = [&](const Cut &x) { return (size_t)(std::lower_bound(cuts.begin(), cuts.end(), x) - cuts.begin()); };
     for (uint64_t i = 0; i < n_windows; ++i)
-        if (windows[i].site_end > windows[i].site_begin) {
-            cover[cut_index(windows[i].site_begin)] += 1;
-            cover[cut_index(windows[i].site_end)] -= 1;
+        if (nonempty(i)) {
+            cover[cut_index(lo(i))] += 1;
+            cover[cut_index(hi(i))] -= 1;
         }
+    const uint64_t row_bytes = 64ull * wps * 4ull, budget = (uint64_t)tile_blocks * row_bytes;
     std::vector<uint64_t> seg_tile_start(cuts.size() + 1, 0);
     int64_t depth = 0;
     for (size_t k = 0; k + 1 < cuts.size(); ++k) {
         seg_tile_start[k] = tiles.size();
         depth += cover[k];
         if (depth <= 0) continue;
-        // tiles are cut on 64-site block boundaries of the matrix so interior tiles read whole blocks
-        uint64_t s = cuts[k];
-        const uint64_t e = cuts[k + 1];
-        // equal shares: a 781-block segment under a 512-block limit becomes 391 + 390 blocks, not 512 + 269
-        const uint64_t nblk = (e + 63) / 64 - s / 64, n_parts = (nblk + tile_blocks - 1) / tile_blocks;
-        const uint64_t per = (nblk + n_parts - 1) / n_parts;
-        while (s < e) {
-            uint64_t t_end = ((s / 64) + per) * 64;  // block-aligned end
-            if (t_end > e) t_end = e;
-            tiles.push_back({s, t_end});
-            bytes_streamed += ((t_end + 63) / 64 - s / 64) * 64ull * wps * 4ull;
-            s = t_end;
+        // tiles are cut on 64-site block boundaries of the layout so interior tiles read whole blocks
+        auto cut = [&](const Cut &s, const Cut &e) {
+            // equal shares: a 781-block segment under a 512-block limit becomes 391 + 390 blocks, not 512 + 269
+            const uint64_t nblk = e.c > s.c ? (e.c + 63) / 64 - s.c / 64 : 0, nr = e.r - s.r;
+            const uint64_t n_parts = std::max<uint64_t>(1, (nblk * row_bytes + nr * 8 + budget - 1) / budget);
+            const uint64_t per = (nblk + n_parts - 1) / n_parts, per_r = (nr + n_parts - 1) / n_parts;
+            uint64_t cs = s.c, rs = s.r;
+            for (uint64_t part = 0; part < n_parts; ++part) {
+                uint64_t ce = cs;
+                if (cs < e.c) ce = std::min(e.c, ((cs / 64) + per) * 64);  // block-aligned end
+                const uint64_t re = std::min(e.r, rs + per_r);
+                if (ce > cs || re > rs) {
+                    tiles.push_back({cs, ce, rs, re});
+                    bytes_streamed += (ce > cs ? ((ce + 63) / 64 - cs / 64) * row_bytes : 0) + (re - rs) * 8ull;
+                }
+                cs = ce;
+                rs = re;
+            }
+        };
+        const Cut s = cuts[k], e = cuts[k + 1];
+        if (IMPOP_SCAN_SEPARATE_STREAMS && e.c > s.c && e.r > s.r) {
+            cut(s, Cut{e.c, s.r});
+            cut(Cut{e.c, s.r}, e);
+        } else {
+            cut(s, e);
         }
     }
     if (!cuts.empty()) seg_tile_start[cuts.size() - 1] = tiles.size();
@@ -735,9 +867,9 @@ static void build_tiles(const impop_window *windows, uint64_t n_windows, uint32_
         WinDesc &w = wd[i];
         w.n_sites = windows[i].site_end - windows[i].site_begin;
         w.seq_len = windows[i].seq_len;
-        if (w.n_sites) {
-            w.t0 = seg_tile_start[cut_index(windows[i].site_begin)];
-            w.t1 = seg_tile_start[cut_index(windows[i].site_end)];
+        if (nonempty(i)) {
+            w.t0 = seg_tile_start[cut_index(lo(i))];
+            w.t1 = seg_tile_start[cut_index(hi(i))];
         } else {
             w.t0 = w.t1 = 0;
         }
@@ -752,6 +884,7 @@ struct impop_scan_plan {
     impop_ctx *ctx = nullptr;
     const impop_matrix *m = nullptr;
     const uint32_t *sb = nullptr;  // the layout launches stream: m->d_vsb (route "indexed", tiles in kept-site coordinates) or m->d_sb
+    const uint64_t *rare = nullptr;  // split index: m->d_vrare (tiles' rare ranges), else null
     uint64_t n_windows = 0, n_tiles = 0, bytes_streamed = 0;
     PopSizes ps{};
     bool subset_p = false;
@@ -789,14 +922,19 @@ static int window_weights(const impop_matrix *m, bool indexed, const impop_windo
 // work (>= 16 tiles per CU wanted), and never below the 32 blocks the kernel was tuned with.
 // `windows` are in the coordinates of the layout streamed (kept-site coordinates for an indexed plan); the blocks they
 // cover are capped at that layout's length when windows of a compacted matrix or an index overlap.
-static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                                    bool indexed) {
+// rare (nullable): the windows' rare-entry ranges of a split index, counted as the blocks of rows their bytes would fill.
+static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, const impop_window *rare,
+                                    uint64_t n_windows, bool indexed) {
     // ~256 KB per tile; wide sites (the any-n kernel, wps > 16) go down to 4 blocks = one per wave
     const uint32_t by_bytes = m->g.wps > 16 ? std::max<uint32_t>(4, 1024 / m->g.wps) : std::max<uint32_t>(32, 1024 / m->g.wps);
-    uint64_t blocks = 0;
+    uint64_t blocks = 0, entries = 0;
     for (uint64_t i = 0; i < n_windows; ++i) blocks += (windows[i].site_end - windows[i].site_begin + 63) / 64;
+    if (rare)
+        for (uint64_t i = 0; i < n_windows; ++i) entries += rare[i].site_end - rare[i].site_begin;
     if (m->compact && blocks > m->g.n_block) blocks = m->g.n_block;
     if (indexed && blocks > m->vg.n_block) blocks = m->vg.n_block;
+    if (entries > m->n_vrare) entries = m->n_vrare;
+    blocks += entries * 8 / (64ull * m->g.wps * 4ull);
     const uint64_t by_parallelism = blocks / (16ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
     return (uint32_t)std::max<uint64_t>(std::min<uint32_t>(32, by_bytes), std::min<uint64_t>(by_bytes, by_parallelism));
 }
@@ -823,23 +961,35 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
 
 // the route of a scan of m: the variable-site index when the matrix has one and no site weights (d_wt is indexed by matrix site)
 static bool scan_indexed(const impop_matrix *m) { return m->d_vsb != nullptr && m->wt_prefix.empty(); }
+// ... and, on that route, the rare-entry stream of a split index
+static bool scan_split(const impop_matrix *m) { return scan_indexed(m) && m->d_vrare != nullptr; }
 
-// windows (validated, matrix coordinates) -> the ranges of the layout the route streams
+// windows (validated, matrix coordinates) -> the ranges of the layout the route streams (and, split index, of the rare entries)
 static int map_for_route(impop_ctx *ctx, const impop_matrix *m, bool indexed, const impop_window *windows, uint64_t n_windows,
-                         std::vector<impop_window> &mapped) {
-    if (indexed) return map_windows_index(ctx, m, windows, n_windows, mapped);
+                         std::vector<impop_window> &mapped, std::vector<impop_window> &rare) {
+    rare.clear();
+    if (indexed) return map_windows_index(ctx, m, windows, n_windows, mapped, scan_split(m) ? &rare : nullptr);
     map_windows(m, windows, n_windows, mapped);  // compacted matrix: original coordinates -> kept-site index ranges
     return IMPOP_OK;
 }
 
-// IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it
-static void trace_route(const impop_matrix *m, bool indexed, uint64_t n_tiles, uint64_t bytes_streamed, uint64_t n_windows) {
+// IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it.  kept_sites = every
+// variable site of an indexed route; rare_sites / rare_bytes = the split index's rare entries (all of the matrix / the plan's);
+// split = on, or off:<the reason there is none, blanks as _>
+static void trace_route(const impop_matrix *m, bool indexed, uint64_t n_tiles, uint64_t bytes_streamed, uint64_t n_windows,
+                        const std::vector<ScanTile> &tiles) {
     static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
     if (!trace) return;
     const char *why = indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
-    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu%s%s\n",
-            indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(indexed ? m->vg.n_site : m->g.n_site),
-            (unsigned long long)n_tiles, (unsigned long long)bytes_streamed, (unsigned long long)n_windows, *why ? " why=" : "", why);
+    const bool split = indexed && m->d_vrare;
+    uint64_t rare_bytes = 0;
+    for (const ScanTile &t : tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
+    std::string off = "off:" + (!m->wt_prefix.empty() && m->d_vrare ? std::string("site weights") : m->rskip);
+    for (char &ch : off) ch = ch == ' ' ? '_' : ch;
+    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s%s%s\n",
+            indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(indexed ? m->n_vkept : m->g.n_site),
+            (unsigned long long)n_tiles, (unsigned long long)bytes_streamed, (unsigned long long)n_windows,
+            (unsigned long long)(split ? m->n_vrare : 0), (unsigned long long)rare_bytes, split ? "on" : off.c_str(), *why ? " why=" : "", why);
     fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
 }
 
@@ -852,10 +1002,10 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
         mk.b[k] = p->masks[2 * WPS + k];
     }
     if (p->subset_p)
-        hipLaunchKernelGGL((scan_tiles_kernel<WPS, true>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb,
+        hipLaunchKernelGGL((scan_tiles_kernel<WPS, true>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare,
                            p->d_tiles, mk, p->ps, p->d_parts);
     else
-        hipLaunchKernelGGL((scan_tiles_kernel<WPS, false>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb,
+        hipLaunchKernelGGL((scan_tiles_kernel<WPS, false>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare,
                            p->d_tiles, mk, p->ps, p->d_parts);
 }
 
@@ -888,19 +1038,22 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     }
     HIP_TRY(hipSetDevice(ctx->device));
     const bool indexed = scan_indexed(m);
-    std::vector<impop_window> mapped;
+    std::vector<impop_window> mapped, rare;
     {
-        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped);
+        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped, rare);
         if (mrc) return mrc;
     }
+    const impop_window *rare_w = rare.empty() ? nullptr : rare.data();
     // default tile: ~160 KB of matrix per workgroup.  With few haplotypes a 32-block tile is only a few KB and
     // the per-workgroup costs (launch, LDS reduction, partial store) bound the kernel instead of HBM:
     // n = 32 ran at 2.6 TB/s with 32-block tiles and 5.0 TB/s with whole-window tiles
     const uint32_t tile_blocks = prm.tile_blocks ? prm.tile_blocks
-                                                 : default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, n_windows, indexed);
+                                                 : default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, rare_w, n_windows,
+                                                                       indexed);
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
     p->sb = indexed ? m->d_vsb : m->d_sb;
+    p->rare = rare_w ? m->d_vrare : nullptr;
     m->users++;
     p->d_pi_mode = prm.d_pi_mode; p->s_scope = prm.s_scope;
     const uint32_t wps = m->g.wps;
@@ -908,7 +1061,7 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
 
     std::vector<ScanTile> tiles;
     std::vector<WinDesc> wd;
-    build_tiles(mapped.data(), n_windows, tile_blocks, wps, tiles, wd, p->bytes_streamed);
+    build_tiles(mapped.data(), rare_w, n_windows, tile_blocks, wps, tiles, wd, p->bytes_streamed);
     p->n_tiles = tiles.size();
     auto fail = [&](int code) {
         impop_scan_plan_destroy(p);
@@ -918,7 +1071,7 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
         const int wrc = window_weights(m, indexed, windows, n_windows, wd);
         if (wrc) return fail(wrc);
     }
-    trace_route(m, indexed, p->n_tiles, p->bytes_streamed, n_windows);
+    trace_route(m, indexed, p->n_tiles, p->bytes_streamed, n_windows, tiles);
     uint64_t longest_range = 0;
     for (const WinDesc &w : wd) longest_range = std::max(longest_range, w.t1 - w.t0);
     p->finalize_tpw = longest_range > 2048 ? 256 : longest_range > 48 ? 64 : 1;
@@ -983,7 +1136,7 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
     if (p->n_tiles && (weighted || wps > 16)) {
         const size_t lds = (size_t)3 * ((wps + 3) & ~3u) * 4;
 #define ANYN(SP, WT)                                                                                                     \
-    hipLaunchKernelGGL((scan_tiles_anyn_kernel<SP, WT>), dim3((uint32_t)p->n_tiles), dim3(256), lds, st, p->sb,          \
+    hipLaunchKernelGGL((scan_tiles_anyn_kernel<SP, WT>), dim3((uint32_t)p->n_tiles), dim3(256), lds, st, p->sb, p->rare, \
                        p->d_tiles, p->d_masks, wps, p->m->g.G, p->m->g.r, p->ps, p->m->d_wt, p->d_parts)
         if (weighted) { if (p->subset_p) ANYN(true, true); else ANYN(false, true); }
         else          { if (p->subset_p) ANYN(true, false); else ANYN(false, false); }
@@ -1121,16 +1274,17 @@ IMPOP_API int impop_site_counts(impop_ctx *ctx, const impop_matrix *m, const uin
 }
 
 template <int K>
-static int launch_multi(hipStream_t st, const impop_matrix *m, const uint32_t *sb, uint64_t n_tiles, const ScanTile *d_tiles,
+static int launch_multi(hipStream_t st, const impop_matrix *m, const uint32_t *sb, const uint64_t *rare, uint64_t n_tiles,
+                        const ScanTile *d_tiles,
                         const uint32_t *d_masks, const uint32_t *d_n, uint64_t *d_parts, bool small) {
     const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
     if (small) {
-        hipLaunchKernelGGL((scan_multi_kernel<K, true>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, d_tiles, d_masks, d_n,
+        hipLaunchKernelGGL((scan_multi_kernel<K, true>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, rare, d_tiles, d_masks, d_n,
                            m->g.wps, m->g.G, m->g.r, m->d_wt, d_parts);
     } else {
         if (lds > 48 * 1024)
             HIP_TRY(hipFuncSetAttribute((const void *)scan_multi_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((scan_multi_kernel<K, false>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, d_tiles, d_masks, d_n,
+        hipLaunchKernelGGL((scan_multi_kernel<K, false>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, rare, d_tiles, d_masks, d_n,
                            m->g.wps, m->g.G, m->g.r, m->d_wt, d_parts);
     }
     return IMPOP_OK;
@@ -1168,20 +1322,22 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
     std::vector<WinDesc> wd;
     uint64_t bytes = 0;
     const bool indexed = scan_indexed(m);
-    std::vector<impop_window> mapped;
+    std::vector<impop_window> mapped, rare;
     {
-        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped);
+        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped, rare);
         if (mrc) return mrc;
     }
-    const uint32_t tile_blocks_used = default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, n_windows, indexed);
+    const impop_window *rare_w = rare.empty() ? nullptr : rare.data();
+    const uint32_t tile_blocks_used = default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, rare_w, n_windows, indexed);
     {
-        build_tiles(mapped.data(), n_windows, tile_blocks_used, wps, tiles, wd, bytes);
+        build_tiles(mapped.data(), rare_w, n_windows, tile_blocks_used, wps, tiles, wd, bytes);
         const int wrc = window_weights(m, indexed, windows, n_windows, wd);
         if (wrc) return wrc;
     }
     const uint32_t *sb = indexed ? m->d_vsb : m->d_sb;
+    const uint64_t *rare_sb = rare_w ? m->d_vrare : nullptr;
     REQUIRE(tiles.size() < 0x7FFFFFFFull, "impop_scan_multi: too many tiles");
-    trace_route(m, indexed, tiles.size(), bytes, n_windows);
+    trace_route(m, indexed, tiles.size(), bytes, n_windows, tiles);
     const size_t nt = tiles.size();
     auto up = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t o_tiles = 0, o_wins = o_tiles + up(std::max<size_t>(nt, 1) * sizeof(ScanTile)),
@@ -1203,13 +1359,13 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
         // 32-bit per-lane partial sums: unweighted, <= 512 haplotypes, <= 1024 sites per lane and tile
         const bool small = m->wt_prefix.empty() && n <= 512 && tile_blocks_used <= 4096;
         switch (K) {
-            case 2: rc = launch_multi<2>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
-            case 3: rc = launch_multi<3>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
-            case 4: rc = launch_multi<4>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
-            case 5: rc = launch_multi<5>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
-            case 6: rc = launch_multi<6>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
-            case 7: rc = launch_multi<7>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
-            default: rc = launch_multi<8>(ctx->stream, m, sb, nt, dt, dm, dn, dp, small); break;
+            case 2: rc = launch_multi<2>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            case 3: rc = launch_multi<3>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            case 4: rc = launch_multi<4>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            case 5: rc = launch_multi<5>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            case 6: rc = launch_multi<6>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            case 7: rc = launch_multi<7>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            default: rc = launch_multi<8>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
         }
         if (rc) return rc;
         HIP_TRY(hipGetLastError());

@@ -86,6 +86,11 @@ int impop_ctx_device_name(impop_ctx *ctx, char *buf, size_t buflen);
  * indexed by matrix site) always stream the dense layout; impop_afs, impop_site_counts, impop_ehh, download and the
  * all-pairs path never use the index.  impop_matrix_info's device_bytes does not count it. */
 #define IMPOP_KEEP_DENSE_SCAN 4u
+/* The index is also split, when it is built and n_hap is 65..65535: a kept site with min(c, n - c) <= 3 (a RARE site) is
+ * stored as one 8-byte entry listing its minor-allele carriers, and only the other (COMMON) kept sites as SB64 rows.  Scans
+ * read both streams and return the same records.  IMPOP_KEEP_NO_RARE_SPLIT keeps every kept site as a row (the unsplit
+ * index); impop_matrix_scan_split_info reports the split, or why there is none. */
+#define IMPOP_KEEP_NO_RARE_SPLIT 8u
 
 int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits_hap_major, uint32_t n_hap, uint64_t n_site,
                         uint64_t row_stride_words, uint32_t keep_flags, impop_matrix **out);
@@ -149,6 +154,11 @@ int impop_matrix_info(const impop_matrix *m, uint32_t *n_hap, uint64_t *n_site, 
  * takes (0 = the matrix has none; compacted matrices never have one, all their sites are kept); why (nullable, why_len
  * bytes) receives the reason there is none, or "" when there is one.  All outputs nullable. */
 int impop_matrix_scan_index_info(const impop_matrix *m, uint64_t *n_kept, uint64_t *index_bytes, char *why, size_t why_len);
+/* The rare/common split of that index (see IMPOP_KEEP_NO_RARE_SPLIT): n_rare = rare sites (8-byte entries), n_common = kept
+ * sites stored as rows, rare_bytes = bytes of the entries; all 0 when there is no split, and why (nullable, why_len bytes)
+ * receives the reason, else "".  All outputs nullable. */
+int impop_matrix_scan_split_info(const impop_matrix *m, uint64_t *n_rare, uint64_t *n_common, uint64_t *rare_bytes, char *why,
+                                 size_t why_len);
 int impop_matrix_free(impop_ctx *ctx, impop_matrix *m);
 
 /* ---- windowed scan: pi + Hudson Fst + Tajima's D + S in one pass ------------
