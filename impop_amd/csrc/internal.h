@@ -76,6 +76,23 @@ __host__ __device__ inline uint64_t sb_index(uint32_t wps, uint32_t G, uint32_t 
                        : base + (uint64_t)(G - 1) * 256 + (uint64_t)l * r + (k - 4 * (G - 1));
 }
 
+// sub-buffers of one device allocation start on 256-byte boundaries
+inline size_t round_up_256(size_t x) { return (x + 255) / 256 * 256; }
+
+// rare kept sites: min(c, n - c) <= IMPOP_RARE_MAX (one 8-byte entry lists their minor-allele carriers)
+constexpr uint32_t IMPOP_RARE_MAX = 3;
+// ---- the 8-byte rare entry of the split scan index (impop_matrix::d_vrare) ----
+//     bits 0..1 = m (1..3 listed haplotypes), bit 15 = the listed haplotypes carry 0 (else 1), bits 16i+16..16i+31 = the index
+//     of listed haplotype i (unused slots 0xFFFF); listed = carriers of the allele with count <= n/2, ties to the 1-allele.
+constexpr uint64_t RARE_NO_SLOTS = 0xFFFFFFFFFFFF0000ull;  // every slot unused
+__host__ __device__ inline uint32_t rare_count(uint64_t e) { return (uint32_t)e & 3u; }
+__host__ __device__ inline bool rare_lists_zeros(uint64_t e) { return (e & 0x8000u) != 0; }
+__host__ __device__ inline uint32_t rare_slot(uint64_t e, uint32_t i) { return (uint32_t)(e >> (16 * i + 16)) & 0xFFFFu; }
+__host__ __device__ inline uint64_t rare_set_slot(uint64_t slots, uint32_t i, uint32_t h) {
+    return (slots & ~(0xFFFFull << (16 * i + 16))) | ((uint64_t)h << (16 * i + 16));
+}
+__host__ __device__ inline uint64_t rare_pack(uint64_t slots, uint32_t m, bool zeros) { return slots | m | (zeros ? 0x8000u : 0u); }
+
 }  // namespace impop
 
 struct impop_ctx {
@@ -167,9 +184,8 @@ struct impop_matrix {
     uint64_t n_vkept = 0;                              // variable sites (rare + common when split)
     std::string vskip = "not built";
     // rare/common split of the index (layout.hip rare_entries_kernel): a kept site is RARE when min(c, n - c) <= IMPOP_RARE_MAX.
-    // Then d_vsb (geometry vg) holds the COMMON kept sites only, and d_vrare one 8-byte entry per rare site in site order:
-    //     bits 0..1 = m (1..3 listed haplotypes), bit 15 = the listed haplotypes carry 0 (else 1), bits 16k+16..16k+31 = index k
-    //     (unused slots 0xFFFF); listed = carriers of the allele with count <= n/2, ties to the 1-allele.
+    // Then d_vsb (geometry vg) holds the COMMON kept sites only, and d_vrare one 8-byte entry per rare site in site order
+    // (format: rare_pack and its readers above).
     // Per 64-site block of the matrix: d_cmask = mask of its common sites, d_cbase = common sites before it (n_block + 1
     // entries each, one allocation); rare(s) = kept(s) - common(s).  d_vrare null: no split (rskip says why), d_vsb holds every
     // kept site as before.
@@ -206,8 +222,6 @@ constexpr unsigned POS_COARSE_SHIFT = 12;
 // variable-site scan index: window edges in matrix coordinates -> kept-site index ranges of d_vsb (one thread per edge, no search)
 // the index a kept fraction above 1/IMPOP_INDEX_MAX_KEPT_INV of the sites is not built for (the dense stream is then nearly as short)
 constexpr uint64_t IMPOP_INDEX_MAX_KEPT_INV = 4;
-// rare kept sites: min(c, n - c) <= IMPOP_RARE_MAX (one 8-byte entry lists their minor-allele carriers)
-constexpr uint32_t IMPOP_RARE_MAX = 3;
 // split index: the same edges also as common-site (`mapped`) and rare-entry (`rare`) ranges; rare == nullptr: kept-site ranges
 int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
                       std::vector<impop_window> *rare);

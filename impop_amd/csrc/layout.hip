@@ -10,6 +10,7 @@
 
 #include "device_utils.h"
 #include "internal.h"
+#include "sb64.h"
 
 namespace impop {
 
@@ -466,13 +467,8 @@ __global__ __launch_bounds__(256) void variable_mask_kernel(const uint32_t *__re
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t stride = (uint64_t)gridDim.x * 4;
     for (uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < n_block; b += stride) {
-        const uint32_t *site = sb + b * 64ull * wps;
         uint32_t c = 0;
-        for (uint32_t g = 0; g + 1 < G; ++g) {  // whole 16-byte granules: one coalesced 1 KiB wave load each
-            const uint4 v = *reinterpret_cast<const uint4 *>(site + (uint64_t)g * 256 + lane * 4);
-            c += __popc(v.x) + __popc(v.y) + __popc(v.z) + __popc(v.w);
-        }
-        for (uint32_t j = 0; j < r; ++j) c += __popc(site[(uint64_t)(G - 1) * 256 + lane * r + j]);
+        sb_for_each_dword<false>(sb + b * 64ull * wps, G, r, lane, [&](uint32_t, uint32_t w) { c += __popc(w); });
         const bool var = (b * 64 + lane < n_site) && c > 0 && c < n_hap;
         const uint64_t m = __ballot(var);
         const uint64_t o = ones ? __ballot((b * 64 + lane < n_site) && c == n_hap) : 0ull;
@@ -672,15 +668,17 @@ __global__ __launch_bounds__(256) void gather_kept_kernel(const uint32_t *__rest
     const uint32_t *src = sb + (s >> 6) * 64ull * wps;
     const uint32_t sl = (uint32_t)(s & 63);
     uint32_t *dst = out + j * 64ull * wps;
-    const uint32_t Gf = r == 4 ? G : G - 1;  // full 16-byte granules
+    const uint32_t Gf = sb_full_granules(G, r);
+    uint32_t tl[3] = {0u, 0u, 0u};
+    if (live) sb_load_tail<false>(src, G, r, sl, tl);
 #pragma unroll 4
     for (uint32_t g = 0; g < Gf; ++g) {
-        uint4 v = {0u, 0u, 0u, 0u};
-        if (live) v = *reinterpret_cast<const uint4 *>(src + (uint64_t)g * 256 + sl * 4);
-        *reinterpret_cast<uint4 *>(dst + (uint64_t)g * 256 + lane * 4) = v;
+        u32v4 v = {0u, 0u, 0u, 0u};
+        if (live) v = *sb_granule(src, g, sl);
+        *sb_granule(dst, g, lane) = v;
     }
-    if (Gf < G)
-        for (uint32_t e = 0; e < r; ++e) dst[(uint64_t)Gf * 256 + lane * r + e] = live ? src[(uint64_t)Gf * 256 + sl * r + e] : 0u;
+    uint32_t *last = sb_tail(dst, G, r, lane);
+    sb_use_tail(G, r, tl, [&](uint32_t k, uint32_t w) { last[k & 3] = w; });  // k & 3: the dword's place in its granule
 }
 
 // Rare kept sites -> 8-byte entries (layout: internal.h, d_vrare).  One thread per source block walks its rare sites (a few per
@@ -699,19 +697,18 @@ __global__ __launch_bounds__(256) void rare_entries_kernel(const uint32_t *__res
         uint32_t c = 0;
         for (uint32_t k = 0; k < wps; ++k) c += __popc(sb[sb_index(wps, G, r, b, l, k)]);
         const bool zeros = 2 * c > n_hap;  // list the carriers of 0 (padding haplotypes excluded below)
-        uint64_t slots = 0xFFFFFFFFFFFF0000ull;
+        uint64_t slots = RARE_NO_SLOTS;
         uint32_t m = 0;
         for (uint32_t k = 0; k < wps && m < IMPOP_RARE_MAX; ++k) {
             uint32_t w = sb[sb_index(wps, G, r, b, l, k)];
             if (zeros) w = ~w & (32 * k + 32 <= n_hap ? 0xFFFFFFFFu : (1u << (n_hap - 32 * k)) - 1u);
             while (w && m < IMPOP_RARE_MAX) {
-                const uint64_t h = 32 * k + (uint32_t)__builtin_ctz(w);
+                const uint32_t h = 32 * k + (uint32_t)__builtin_ctz(w);
                 w &= w - 1;
-                slots = (slots & ~(0xFFFFull << (16 * m + 16))) | (h << (16 * m + 16));
-                ++m;
+                slots = rare_set_slot(slots, m++, h);
             }
         }
-        out[d++] = slots | m | (zeros ? 0x8000u : 0u);
+        out[d++] = rare_pack(slots, m, zeros);
     }
 }
 
@@ -791,7 +788,7 @@ static bool index_alloc(impop_matrix *m, void **p, size_t bytes, const char *wha
 struct IndexTmp {
     size_t o_ccnt, o_chunk, o_cchunk, o_total, bytes;
     IndexTmp(uint64_t ne, uint64_t n_chunks) {
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        const auto up = round_up_256;
         o_ccnt = up(ne * 4); o_chunk = o_ccnt + up(ne * 4); o_cchunk = o_chunk + up(n_chunks * 8); o_total = o_cchunk + up(n_chunks * 8);
         bytes = o_total + 256;
     }
@@ -839,7 +836,7 @@ static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, Ind
     return IMPOP_OK;
 }
 
-// exclusive prefix over the n_block + 1 per-block counts: base[b] = sum of cnt[< b]; the total goes to *d_total
+// exclusive prefix over ne per-block counts: base[b] = sum of cnt[< b]; the total goes to *d_total
 static void block_prefix(impop_ctx *ctx, const uint32_t *cnt, uint64_t ne, uint64_t n_chunks, uint64_t *d_chunk, uint64_t *d_total,
                          uint64_t *base) {
     hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)n_chunks), dim3(256), 0, ctx->stream, cnt, ne, d_chunk);
@@ -921,7 +918,7 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     const SbGeom &g = in->g;
     const uint64_t nb = g.n_block, n_chunks = (nb + SCAN_CHUNK - 1) / SCAN_CHUNK;
     REQUIRE((nb + 3) / 4 < 0x7FFFFFFFull, "impop_matrix_compact: matrix too long for one launch");
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const auto up = round_up_256;
     const size_t o_mask = 0, o_cnt = o_mask + up(nb * 8), o_base = o_cnt + up(nb * 4), o_chunk = o_base + up(nb * 8),
                  o_total = o_chunk + up(n_chunks * 8);
     void *d = nullptr;
@@ -941,9 +938,7 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
         const uint32_t wide_grid = (uint32_t)std::min<uint64_t>((nb + 3) / 4, 32ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
         hipLaunchKernelGGL(variable_mask_kernel, dim3(wide_grid), dim3(256), 0, ctx->stream, in->d_sb, g.wps, g.G, g.r, nb, g.n_site,
                            g.n_hap, d_mask, d_cnt, d_ones);
-        hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)n_chunks), dim3(256), 0, ctx->stream, d_cnt, nb, d_chunk);
-        hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, d_chunk, n_chunks, d_total);
-        hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)n_chunks), dim3(64), 0, ctx->stream, d_cnt, nb, d_chunk, d_base);
+        block_prefix(ctx, d_cnt, nb, n_chunks, d_chunk, d_total, d_base);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&n_kept, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -15,6 +15,7 @@
 
 #include "device_utils.h"
 #include "internal.h"
+#include "sb64.h"
 
 namespace impop {
 
@@ -42,62 +43,32 @@ struct MaskArgs {
     uint32_t p[WPS], a[WPS], b[WPS];
 };
 
-// Tuning knobs (defaults chosen by tools/tune_scan.py on MI355X)
-// Measured (tools/tune_scan.py, 465 x 75 M sites, interleaved rounds): nt loads 6.65-6.68 TB/s
-// algorithmic vs 5.9-6.07 TB/s with default-policy loads (+10 %); unroll / occupancy / tile
+// Tuning knobs (defaults chosen by tools/tune_scan.py on MI355X; IMPOP_SCAN_NT: sb64.h)
+// Measured (tools/tune_scan.py, 465 x 75 M sites, interleaved rounds): unroll / occupancy / tile
 // size move the result by < 2 % once nt is on; a 64-VGPR cap (min_waves 8 at unroll 2) spills.
-#ifndef IMPOP_SCAN_NT
-#define IMPOP_SCAN_NT 1        // 1: non-temporal (streaming) loads for the once-read matrix
-#endif
 #ifndef IMPOP_SCAN_UNROLL
 #define IMPOP_SCAN_UNROLL 0    // 64-site blocks in flight per wave; 0 = auto (about 8 wave loads in flight)
 #endif
 #ifndef IMPOP_SCAN_MIN_WAVES
 #define IMPOP_SCAN_MIN_WAVES 6 // __launch_bounds__ 2nd argument (waves per SIMD)
 #endif
-#ifndef IMPOP_SCAN_SEPARATE_STREAMS
-#define IMPOP_SCAN_SEPARATE_STREAMS 0  // 1: a segment's rare entries and common rows go to separate tiles (A/B builds only)
-#endif
 
-template <typename T>
-__device__ __forceinline__ T stream_load(const T *p) {
-#if IMPOP_SCAN_NT
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
+// the blocks [b0, b1) a tile's sites lie in, and this thread's place: wave w takes blocks b0 + w, b0 + w + 4, ...; the wave
+// index goes through readfirstlane so that block addresses and the loops stay scalar (SGPR) state
+struct TileBlocks {
+    uint64_t b0, b1;
+    uint32_t lane, wave;
+};
+__device__ __forceinline__ TileBlocks tile_blocks_of(const ScanTile &t) {
+    const uint64_t b0 = t.site_begin >> 6;
+    return {b0, t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0, threadIdx.x & 63,
+            (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)};
 }
 
-typedef uint32_t u32v4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32v2 __attribute__((ext_vector_type(2)));
-
-template <int WPS>
-__device__ __forceinline__ void load_site(const uint32_t *__restrict__ blk, uint32_t lane, uint32_t (&w)[WPS]) {
-    constexpr int G = (WPS + 3) / 4;
-    constexpr int R = WPS - 4 * (G - 1);
-#pragma unroll
-    for (int g = 0; g < G - 1; ++g) {
-        const u32v4 v = stream_load(reinterpret_cast<const u32v4 *>(blk + g * 256 + lane * 4));
-        w[4 * g + 0] = v.x; w[4 * g + 1] = v.y; w[4 * g + 2] = v.z; w[4 * g + 3] = v.w;
-    }
-    const uint32_t *last = blk + (G - 1) * 256 + lane * R;
-    if constexpr (R == 4) {
-        const u32v4 v = stream_load(reinterpret_cast<const u32v4 *>(last));
-        w[4 * (G - 1) + 0] = v.x; w[4 * (G - 1) + 1] = v.y; w[4 * (G - 1) + 2] = v.z; w[4 * (G - 1) + 3] = v.w;
-    } else if constexpr (R == 3) {
-        // 12-byte, 4-byte-aligned: three dwords (the backend merges them into one dwordx3)
-        w[4 * (G - 1) + 0] = stream_load(last);
-        w[4 * (G - 1) + 1] = stream_load(last + 1);
-        w[4 * (G - 1) + 2] = stream_load(last + 2);
-    } else if constexpr (R == 2) {
-        const u32v2 v = stream_load(reinterpret_cast<const u32v2 *>(last));
-        w[4 * (G - 1) + 0] = v.x; w[4 * (G - 1) + 1] = v.y;
-    } else {
-        w[4 * (G - 1)] = stream_load(last);
-    }
-}
-
+// per-lane sums of one tile, any n <= 65535: every product c (n - c) is below 2^32, the sums are 64 bits wide
 struct LaneAcc {
+    typedef uint64_t sum_t;
+    static __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b) { return a * b; }
     uint32_t s_all = 0, s_p = 0, s_a = 0, s_b = 0;
     uint64_t q_p = 0, q_a = 0, q_b = 0, q_ab = 0;
 };
@@ -107,39 +78,29 @@ struct LaneAcc {
 // (v_mul_lo_u32 is a quarter-rate instruction); they are widened once, at the tile reduction.  This is
 // what lifts the small-n cases, which are VALU-bound rather than HBM-bound (4-16 B per site).
 struct LaneAcc32 {
+    typedef uint32_t sum_t;
+    static __device__ __forceinline__ uint32_t mul(uint32_t a, uint32_t b) { return __umul24(a, b); }
     uint32_t s_all = 0, s_p = 0, s_a = 0, s_b = 0;
     uint32_t q_p = 0, q_a = 0, q_b = 0, q_ab = 0;
 };
 
-// One site per lane.  No validity test here: lanes outside the tile had their words zeroed by the caller
+// One site per lane, wt = its weight.  No validity test here: lanes outside the tile had their words zeroed by the caller
 // (only the first / last block of a tile can be partial), and all-zero words add nothing to any counter.
 // Segregating test 0 < c < n as ONE unsigned compare: (c - 1) < (n - 1)  (false for n = 0 or 1 as well).
-template <bool SUBSET_P>
-__device__ __forceinline__ void counts_accumulate(uint32_t c, uint32_t cP, uint32_t cA, uint32_t cB, const PopSizes &ps,
-                                                  LaneAcc32 &acc) {
+template <bool SUBSET_P, typename Acc>
+__device__ __forceinline__ void counts_accumulate(uint32_t c, uint32_t cP, uint32_t cA, uint32_t cB, const PopSizes &ps, Acc &acc,
+                                                  typename Acc::sum_t wt = 1) {
+    typedef typename Acc::sum_t sum_t;
     if (!SUBSET_P) cP = c;
     acc.s_all += (c - 1u) < (ps.n - 1u);
     acc.s_p += (cP - 1u) < (ps.nP - 1u);
     acc.s_a += (cA - 1u) < (ps.nA - 1u);
     acc.s_b += (cB - 1u) < (ps.nB - 1u);
     const uint32_t rA = ps.nA - cA, rB = ps.nB - cB;
-    acc.q_p += __umul24(cP, ps.nP - cP);
-    acc.q_a += __umul24(cA, rA);
-    acc.q_b += __umul24(cB, rB);
-    acc.q_ab += __umul24(cA, rB) + __umul24(cB, rA);
-}
-
-// the same for the 64-bit accumulators of the any-n kernel (n <= 65535: every product is below 2^32)
-template <bool SUBSET_P>
-__device__ __forceinline__ void counts_accumulate(uint32_t c, uint32_t cP, uint32_t cA, uint32_t cB, const PopSizes &ps,
-                                                  LaneAcc &acc) {
-    if (!SUBSET_P) cP = c;
-    acc.s_all += (c - 1u) < (ps.n - 1u);
-    acc.s_p += (cP - 1u) < (ps.nP - 1u);
-    acc.s_a += (cA - 1u) < (ps.nA - 1u);
-    acc.s_b += (cB - 1u) < (ps.nB - 1u);
-    acc.q_p += cP * (ps.nP - cP); acc.q_a += cA * (ps.nA - cA); acc.q_b += cB * (ps.nB - cB);
-    acc.q_ab += (uint64_t)(cA * (ps.nB - cB)) + (uint64_t)(cB * (ps.nA - cA));
+    acc.q_p += wt * Acc::mul(cP, ps.nP - cP);
+    acc.q_a += wt * Acc::mul(cA, rA);
+    acc.q_b += wt * Acc::mul(cB, rB);
+    acc.q_ab += wt * ((sum_t)Acc::mul(cA, rB) + (sum_t)Acc::mul(cB, rA));
 }
 
 template <int WPS, bool SUBSET_P>
@@ -156,23 +117,36 @@ __device__ __forceinline__ void site_accumulate(const uint32_t (&w)[WPS], const 
     counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
 }
 
-// A rare entry (internal.h, d_vrare) lists the m <= 3 carriers of its minor allele: their P / A / B membership comes from bit
-// tests on the masks in LDS (per-lane addresses, a few dwords), and the counts of the 1-allele follow, mirrored through n - m,
-// nP - mP, ... when the listed haplotypes carry 0 (then every 0-carrier is listed).  Exact integers as for a row.
+// A rare entry (internal.h, rare_pack) lists the m <= 3 carriers of its minor allele: how many of them belong to a population
+// comes from bit tests on its mask in LDS (per-lane addresses, a few dwords)
+__device__ __forceinline__ uint32_t rare_listed_in(const uint32_t *mask_lds, uint64_t e) {
+    const uint32_t m = rare_count(e);
+    uint32_t in = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < IMPOP_RARE_MAX; ++i)
+        if (i < m) {
+            const uint32_t h = rare_slot(e, i);
+            in += (mask_lds[h >> 5] >> (h & 31u)) & 1u;
+        }
+    return in;
+}
+// ... and the counts of the 1-allele follow, mirrored through n - m, nP - mP, ... when the listed haplotypes carry 0 (then
+// every 0-carrier is listed).  Exact integers as for a row.  One loop over the slots tests all three masks (not three calls of
+// rare_listed_in): most sites of the headline workload arrive here, and three separate loops measured 4 % slower there.
 template <bool SUBSET_P>
 __device__ __forceinline__ void rare_counts(uint64_t v, const uint32_t *lp, const uint32_t *la, const uint32_t *lb, const PopSizes &ps,
                                             uint32_t &c, uint32_t &cP, uint32_t &cA, uint32_t &cB) {
-    const uint32_t m = (uint32_t)v & 3u;
+    const uint32_t m = rare_count(v);
     uint32_t mP = 0, mA = 0, mB = 0;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-        if ((uint32_t)i < m) {
-            const uint32_t h = (uint32_t)(v >> (16 * i + 16)) & 0xFFFFu, wd = h >> 5, bit = h & 31u;
+    for (uint32_t i = 0; i < IMPOP_RARE_MAX; ++i)
+        if (i < m) {
+            const uint32_t h = rare_slot(v, i), wd = h >> 5, bit = h & 31u;
             mA += (la[wd] >> bit) & 1u;
             mB += (lb[wd] >> bit) & 1u;
             if (SUBSET_P) mP += (lp[wd] >> bit) & 1u;
         }
-    if (v & 0x8000u) { c = ps.n - m; cP = ps.nP - mP; cA = ps.nA - mA; cB = ps.nB - mB; }
+    if (rare_lists_zeros(v)) { c = ps.n - m; cP = ps.nP - mP; cA = ps.nA - mA; cB = ps.nB - mB; }
     else { c = m; cP = mP; cA = mA; cB = mB; }
 }
 
@@ -235,39 +209,37 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
                                                                                const MaskArgs<WPS> mk, const PopSizes ps,
                                                                                TilePartial *__restrict__ out) {
     const ScanTile t = tiles[blockIdx.x];
-    const uint64_t b0 = t.site_begin >> 6, b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
-    // wave index through readfirstlane: block addresses and the loop stay scalar (SGPR) state
-    const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const TileBlocks tb = tile_blocks_of(t);
     LaneAcc32 acc;
-    uint64_t b = b0 + wave;
+    uint64_t b = tb.b0 + tb.wave;
     constexpr int G = (WPS + 3) / 4;
     constexpr int U = IMPOP_SCAN_UNROLL > 0 ? IMPOP_SCAN_UNROLL : (G >= 3 ? 2 : G == 2 ? 4 : 8);
     // Only the first and the last block of a tile can be partial: lanes before `lo` in block b0 and from `hi`
     // on in block b1-1 get all-zero words (wave-uniform branch, taken for those two blocks only); interior
     // blocks carry no validity arithmetic and no branch, so all U loads of an iteration are in flight together.
-    const uint32_t lo = (uint32_t)(t.site_begin - (b0 << 6));
-    const uint32_t hi = (uint32_t)(t.site_end - ((b1 - 1) << 6));  // 1..64
+    const uint32_t lo = (uint32_t)(t.site_begin - (tb.b0 << 6));
+    const uint32_t hi = (uint32_t)(t.site_end - ((tb.b1 - 1) << 6));  // 1..64
     auto trim = [&](uint32_t (&w)[WPS], uint64_t blk) {
-        if ((blk == b0 && lo != 0) | (blk == b1 - 1 && hi != 64)) {
-            const bool keep = lane >= (blk == b0 ? lo : 0u) && lane < (blk == b1 - 1 ? hi : 64u);
+        if ((blk == tb.b0 && lo != 0) | (blk == tb.b1 - 1 && hi != 64)) {
+            const bool keep = tb.lane >= (blk == tb.b0 ? lo : 0u) && tb.lane < (blk == tb.b1 - 1 ? hi : 64u);
 #pragma unroll
             for (int k = 0; k < WPS; ++k) w[k] = keep ? w[k] : 0u;
         }
     };
     // U blocks per iteration: U*ceil(WPS/4) independent 1 KiB wave loads in flight per wave
-    for (; b + 4 * (U - 1) < b1; b += 4 * U) {
+    for (; b + 4 * (U - 1) < tb.b1; b += 4 * U) {
         uint32_t w[U][WPS];
 #pragma unroll
-        for (int u = 0; u < U; ++u) load_site<WPS>(sb + (b + 4 * u) * (64ull * WPS), lane, w[u]);
+        for (int u = 0; u < U; ++u) load_site<WPS>(sb + (b + 4 * u) * (64ull * WPS), tb.lane, w[u]);
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             trim(w[u], b + 4 * u);
             site_accumulate<WPS, SUBSET_P>(w[u], mk, ps, acc);
         }
     }
-    for (; b < b1; b += 4) {
+    for (; b < tb.b1; b += 4) {
         uint32_t w0[WPS];
-        load_site<WPS>(sb + b * (64ull * WPS), lane, w0);
+        load_site<WPS>(sb + b * (64ull * WPS), tb.lane, w0);
         trim(w0, b);
         site_accumulate<WPS, SUBSET_P>(w0, mk, ps, acc);
     }
@@ -329,30 +301,20 @@ __global__ __launch_bounds__(256, 4) void scan_tiles_anyn_kernel(const uint32_t 
     }
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    const uint64_t b0 = t.site_begin >> 6, b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
-    const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // full 16-byte granules: all of them when the last one holds 4 dwords per site (r == 4: its addressing is
-    // the full granules'), else all but the last, whose r = 1..3 dwords per site are read one by one
-    const uint32_t Gf = r == 4 ? G : G - 1;
+    const auto [b0, b1, lane, wave] = tile_blocks_of(t);
+    const uint32_t Gf = sb_full_granules(G, r);
     LaneAcc acc;
     for (uint64_t b = b0 + wave; b < b1; b += 4) {
-        const uint32_t *blk = sb + b * 64ull * wps + lane * 4;
+        const uint32_t *blk = sb + b * 64ull * wps;
         uint32_t c = 0, cP = 0, cA = 0, cB = 0;
-        // the last granule's r = 1..3 dwords per site go out first, together with the first batch (read behind the
-        // batches they cost one more memory latency per block)
+        // the last granule's r = 1..3 dwords per site go out first, together with the first batch
         uint32_t tail[3] = {0u, 0u, 0u};
-        if (Gf < G) {
-            const uint32_t *last = sb + b * 64ull * wps + (uint64_t)Gf * 256 + lane * r;
-#pragma unroll
-            for (int e = 0; e < 3; ++e)
-                if ((uint32_t)e < r) tail[e] = stream_load(last + e);
-        }
+        sb_load_tail(blk, G, r, lane, tail);
         // full batches of AN_U granules (all loads out first, consumed with staggered waits) ...
         uint32_t g = 0;
         for (; g + AN_U <= Gf; g += AN_U) {
             u32v4 v[AN_U];
-#pragma unroll
-            for (int u = 0; u < AN_U; ++u) v[u] = stream_load(reinterpret_cast<const u32v4 *>(blk + (uint64_t)(g + u) * 256));
+            sb_load_granules(blk, g, AN_U, lane, v);
 #pragma unroll
             for (int u = 0; u < AN_U; ++u) anyn_granule<SUBSET_P>(v[u], lp, la, lb, g + u, c, cP, cA, cB);
         }
@@ -360,40 +322,19 @@ __global__ __launch_bounds__(256, 4) void scan_tiles_anyn_kernel(const uint32_t 
         // one-at-a-time remainder loop paid the full HBM latency per granule
         if (g < Gf) {
             const uint32_t nb = Gf - g;
-            u32v4 v[AN_U];
-#pragma unroll
-            for (int u = 0; u < AN_U - 1; ++u)
-                if ((uint32_t)u < nb) v[u] = stream_load(reinterpret_cast<const u32v4 *>(blk + (uint64_t)(g + u) * 256));
+            u32v4 v[AN_U - 1];
+            sb_load_granules(blk, g, nb, lane, v);
 #pragma unroll
             for (int u = 0; u < AN_U - 1; ++u)
                 if ((uint32_t)u < nb) anyn_granule<SUBSET_P>(v[u], lp, la, lb, g + u, c, cP, cA, cB);
         }
-        if (Gf < G) {
-#pragma unroll
-            for (int e = 0; e < 3; ++e)
-                if ((uint32_t)e < r) {
-                    const uint32_t v = tail[e], k = 4 * Gf + e;
-                    c += __popc(v); cA += __popc(v & la[k]); cB += __popc(v & lb[k]);
-                    if (SUBSET_P) cP += __popc(v & lp[k]);
-                }
-        }
-        if (!SUBSET_P) cP = c;
+        sb_use_tail(G, r, tail, [&](uint32_t k, uint32_t v) {
+            c += __popc(v); cA += __popc(v & la[k]); cB += __popc(v & lb[k]);
+            if (SUBSET_P) cP += __popc(v & lp[k]);
+        });
         const uint64_t s = b * 64 + lane;
-        if (s >= t.site_begin && s < t.site_end) {  // only the first / last block of a tile is partial
-            acc.s_all += (c - 1u) < (ps.n - 1u);
-            acc.s_p += (cP - 1u) < (ps.nP - 1u);
-            acc.s_a += (cA - 1u) < (ps.nA - 1u);
-            acc.s_b += (cB - 1u) < (ps.nB - 1u);
-            // n <= 65535: every product is below 2^32
-            const uint32_t qp = cP * (ps.nP - cP), qa = cA * (ps.nA - cA), qb = cB * (ps.nB - cB);
-            const uint64_t qab = (uint64_t)(cA * (ps.nB - cB)) + (uint64_t)(cB * (ps.nA - cA));
-            if (WEIGHTED) {
-                const uint64_t wt = weights[s];
-                acc.q_p += wt * qp; acc.q_a += wt * qa; acc.q_b += wt * qb; acc.q_ab += wt * qab;
-            } else {
-                acc.q_p += qp; acc.q_a += qa; acc.q_b += qb; acc.q_ab += qab;
-            }
-        }
+        if (s >= t.site_begin && s < t.site_end)  // only the first / last block of a tile is partial
+            counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc, WEIGHTED ? weights[s] : 1);
     }
     if constexpr (!WEIGHTED) {  // weighted matrices never stream the split index
         if (t.rare_end > t.rare_begin) rare_range<SUBSET_P>(rare, t.rare_begin, t.rare_end, lp, la, lb, ps, acc);
@@ -412,6 +353,25 @@ struct WinTotals {
     uint64_t sum_p, sum_a, sum_b, sum_ab;
 };
 
+// Hudson Fst of populations A, B from a window's exact pair sums (h-fst.py:203-240): W = window length or weight.  The order
+// of the fp64 operations is the parity contract with the reference.
+__device__ __forceinline__ impop_pair_stats hudson_fst(uint64_t sum_a, uint64_t sum_b, uint64_t sum_ab, uint32_t n_a, uint32_t n_b,
+                                                       double W, double seq_len) {
+    const double nA = (double)n_a, nB = (double)n_b;
+    const double pairsA = nA * (nA - 1.0) / 2.0, pairsB = nB * (nB - 1.0) / 2.0;
+    impop_pair_stats r;
+    r.pi_a = (n_a >= 2 && W > 0) ? (double)sum_a / (pairsA * W) : 0.0;
+    r.pi_b = (n_b >= 2 && W > 0) ? (double)sum_b / (pairsB * W) : 0.0;
+    r.dxy = (n_a && n_b && W > 0) ? (double)sum_ab / (nA * nB * W) : 0.0;
+    r.pi_xy = 0.5 * (r.pi_a + r.pi_b);
+    r.fst = (r.dxy > 0) ? (r.dxy - r.pi_xy) / r.dxy : 0.0;
+    r.da = r.dxy - r.pi_xy;
+    if (seq_len > 0) {
+        r.pi_a /= seq_len; r.pi_b /= seq_len; r.da = (r.dxy - r.pi_xy) / seq_len; r.pi_xy /= seq_len; r.dxy /= seq_len;
+    }
+    return r;
+}
+
 __device__ inline void window_epilogue(const WinDesc &w, const WinTotals &T, const PopSizes &ps, const double *__restrict__ taj,
                                        int d_pi_mode, int s_scope, impop_window_stats *__restrict__ dst) {
     const uint64_t n_sites = w.n_sites;  // window length, or the sum of its columns' weights (window_weights)
@@ -422,21 +382,12 @@ __device__ inline void window_epilogue(const WinDesc &w, const WinTotals &T, con
     const double nan = __builtin_nan("");
     const double W = (double)n_sites;
     const double seq_len = (double)w.seq_len;
-    const double nP = (double)ps.nP, nA = (double)ps.nA, nB = (double)ps.nB;
+    const double nP = (double)ps.nP;
     const double pairsP = nP * (double)(ps.nP - 1) / 2.0;
     const double pi = (ps.nP >= 2 && W > 0) ? (double)T.sum_p / (pairsP * W) : 0.0;
     const double pi_site = (seq_len != 0.0) ? pi / seq_len : nan;
-    const double pairsA = nA * (nA - 1.0) / 2.0, pairsB = nB * (nB - 1.0) / 2.0;
-    double pi_a = (ps.nA >= 2 && W > 0) ? (double)T.sum_a / (pairsA * W) : 0.0;
-    double pi_b = (ps.nB >= 2 && W > 0) ? (double)T.sum_b / (pairsB * W) : 0.0;
-    double dxy = (ps.nA && ps.nB && W > 0) ? (double)T.sum_ab / (nA * nB * W) : 0.0;
-    double pi_xy = 0.5 * (pi_a + pi_b);
-    const double fst = (dxy > 0) ? (dxy - pi_xy) / dxy : 0.0;
-    double da = dxy - pi_xy;
-    if (seq_len > 0) {
-        pi_a /= seq_len; pi_b /= seq_len; da = (dxy - pi_xy) / seq_len; pi_xy /= seq_len; dxy /= seq_len;
-    }
-    r.pi = pi; r.pi_site = pi_site; r.pi_a = pi_a; r.pi_b = pi_b; r.pi_xy = pi_xy; r.dxy = dxy; r.da = da; r.fst = fst;
+    const impop_pair_stats h = hudson_fst(T.sum_a, T.sum_b, T.sum_ab, ps.nA, ps.nB, W, seq_len);
+    r.pi = pi; r.pi_site = pi_site; r.pi_a = h.pi_a; r.pi_b = h.pi_b; r.pi_xy = h.pi_xy; r.dxy = h.dxy; r.da = h.da; r.fst = h.fst;
     const double S = (double)(s_scope == 0 ? T.s_all : T.s_p);
     const double pin = d_pi_mode == 0 ? py_round(pi_site, 8) : d_pi_mode == 1 ? pi_site : pi * W;
     double D = nan;
@@ -484,33 +435,11 @@ __global__ __launch_bounds__(TPW == 1 ? 128 : 256) void scan_finalize_kernel(con
     if (sub == 0) window_epilogue(w, T, ps, taj, d_pi_mode, s_scope, out + i);
 }
 
-// c = sum_k popc(dword_k & mask_k) of site `lane` of a block: whole 16-byte granules (one coalesced 1 KiB wave load
-// each, all of them and the last granule's dwords issued before the first is consumed when G <= 5), masks wave-uniform
+// c = sum_k popc(dword_k & mask_k) of site `lane` of a block; masks wave-uniform
 __device__ __forceinline__ uint32_t masked_site_count(const uint32_t *__restrict__ blk, const uint32_t *__restrict__ mask, uint32_t G,
                                                       uint32_t r, uint32_t lane) {
     uint32_t c = 0;
-    const uint32_t Gf = r == 4 ? G : G - 1;
-    const uint32_t *last = blk + (uint64_t)Gf * 256 + lane * r;
-    uint32_t tl[3] = {0u, 0u, 0u};
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        if (Gf < G && (uint32_t)j < r) tl[j] = stream_load(last + j);
-    for (uint32_t g = 0; g < Gf; g += 4) {
-        const uint32_t nb = Gf - g < 4u ? Gf - g : 4u;
-        u32v4 v[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if ((uint32_t)u < nb) v[u] = stream_load(reinterpret_cast<const u32v4 *>(blk + (uint64_t)(g + u) * 256 + lane * 4));
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-            if ((uint32_t)u < nb) {
-                const uint32_t *m = mask + 4 * (g + u);
-                c += __popc(v[u].x & m[0]) + __popc(v[u].y & m[1]) + __popc(v[u].z & m[2]) + __popc(v[u].w & m[3]);
-            }
-    }
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-        if (Gf < G && (uint32_t)j < r) c += __popc(tl[j] & mask[4 * Gf + j]);
+    sb_for_each_dword<true>(blk, G, r, lane, [&](uint32_t k, uint32_t w) { c += __popc(w & mask[k]); });
     return c;
 }
 
@@ -552,8 +481,7 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
     }
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    const uint64_t b0 = t.site_begin >> 6, b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
-    const uint32_t lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const TileBlocks tb = tile_blocks_of(t);
     uint32_t nk[K];
 #pragma unroll
     for (int k = 0; k < K; ++k) nk[k] = pop_n[k];
@@ -565,12 +493,7 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
     for (int k = 0; k < K; ++k) { s1[k] = 0; q2[k] = 0; }
 #pragma unroll
     for (int i = 0; i < NP; ++i) px[i] = 0;
-    const uint32_t Gf = r == 4 ? G : G - 1;  // full 16-byte granules (see scan_tiles_anyn_kernel)
-    auto load_batch = [&](const uint32_t *blk, uint32_t g, uint32_t nb, u32v4 (&v)[MU]) {
-#pragma unroll
-        for (int u = 0; u < MU; ++u)
-            if ((uint32_t)u < nb) v[u] = stream_load(reinterpret_cast<const u32v4 *>(blk + (uint64_t)(g + u) * 256 + lane * 4));
-    };
+    const uint32_t Gf = sb_full_granules(G, r);
     auto count_batch = [&](uint32_t g, uint32_t nb, const u32v4 (&v)[MU], uint32_t (&c)[K]) {
 #pragma unroll
         for (int u = 0; u < MU; ++u)
@@ -582,21 +505,12 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
                 }
             }
     };
-    // the last granule's r = 1..3 dwords per site (r == 4 counts as a full granule): loaded TOGETHER with the batch —
-    // read one by one behind it they cost three more memory latencies per block
-    auto load_tail = [&](const uint32_t *blk, uint32_t (&tl)[3]) {
-        const uint32_t *last = blk + (uint64_t)Gf * 256 + lane * r;
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (Gf < G && (uint32_t)j < r) tl[j] = stream_load(last + j);
-    };
+    // the last granule's r = 1..3 dwords per site are loaded TOGETHER with the batch (sb_load_tail)
     auto count_tail = [&](const uint32_t (&tl)[3], uint32_t (&c)[K]) {
+        sb_use_tail(G, r, tl, [&](uint32_t j, uint32_t v) {
 #pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (Gf < G && (uint32_t)j < r) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) c[k] += __popc(tl[j] & mk_lds[k * wps4 + 4 * Gf + j]);
-            }
+            for (int k = 0; k < K; ++k) c[k] += __popc(v & mk_lds[k * wps4 + j]);  // j: the dword's index in the site
+        });
     };
     // wt: the site's weight (unweighted: 1)
     auto tally_counts = [&](const uint32_t (&c)[K], uint64_t wt) {
@@ -620,20 +534,20 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
         }
     };
     auto tally = [&](uint64_t b, const uint32_t (&c)[K]) {
-        const uint64_t s = b * 64 + lane;
+        const uint64_t s = b * 64 + tb.lane;
         if (s >= t.site_begin && s < t.site_end) tally_counts(c, !SMALL && weights ? weights[s] : 1);  // wave-uniform choice
     };
-    uint64_t b = b0 + wave;
+    uint64_t b = tb.b0 + tb.wave;
     if (Gf <= (uint32_t)MU) {
         // <= 512 haplotypes: a block is one batch; two blocks (up to 8 wave loads) in flight per wave
-        for (; b + 4 < b1; b += 8) {
+        for (; b + 4 < tb.b1; b += 8) {
             const uint32_t *blk0 = sb + b * 64ull * wps, *blk1 = sb + (b + 4) * 64ull * wps;
             u32v4 v0[MU], v1[MU];
             uint32_t t0[3], t1[3];
-            load_batch(blk0, 0, Gf, v0);
-            load_tail(blk0, t0);
-            load_batch(blk1, 0, Gf, v1);
-            load_tail(blk1, t1);
+            sb_load_granules(blk0, 0, Gf, tb.lane, v0);
+            sb_load_tail(blk0, G, r, tb.lane, t0);
+            sb_load_granules(blk1, 0, Gf, tb.lane, v1);
+            sb_load_tail(blk1, G, r, tb.lane, t1);
             uint32_t c0[K], c1[K];
 #pragma unroll
             for (int k = 0; k < K; ++k) { c0[k] = 0; c1[k] = 0; }
@@ -645,17 +559,17 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
             tally(b + 4, c1);
         }
     }
-    for (; b < b1; b += 4) {
+    for (; b < tb.b1; b += 4) {
         const uint32_t *blk = sb + b * 64ull * wps;
         uint32_t c[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) c[k] = 0;
         uint32_t tl[3];
-        load_tail(blk, tl);
+        sb_load_tail(blk, G, r, tb.lane, tl);
         for (uint32_t g = 0; g < Gf; g += MU) {
             const uint32_t nb = Gf - g < (uint32_t)MU ? Gf - g : (uint32_t)MU;
             u32v4 v[MU];
-            load_batch(blk, g, nb, v);
+            sb_load_granules(blk, g, nb, tb.lane, v);
             count_batch(g, nb, v, c);
         }
         count_tail(tl, c);
@@ -665,18 +579,11 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
     // haplotypes, mirrored through n_k - m_k when they carry 0 (rare_counts)
     for (uint64_t e = t.rare_begin + threadIdx.x; e < t.rare_end; e += 256) {
         const uint64_t v = stream_load(rare + e);
-        const uint32_t m = (uint32_t)v & 3u;
         uint32_t c[K];
 #pragma unroll
         for (int k = 0; k < K; ++k) {
-            uint32_t mk = 0;
-#pragma unroll
-            for (int i = 0; i < 3; ++i)
-                if ((uint32_t)i < m) {
-                    const uint32_t h = (uint32_t)(v >> (16 * i + 16)) & 0xFFFFu;
-                    mk += (mk_lds[k * wps4 + (h >> 5)] >> (h & 31u)) & 1u;
-                }
-            c[k] = (v & 0x8000u) ? nk[k] - mk : mk;
+            const uint32_t mk = rare_listed_in(mk_lds + k * wps4, v);
+            c[k] = rare_lists_zeros(v) ? nk[k] - mk : mk;
         }
         tally_counts(c, 1);
     }
@@ -692,7 +599,7 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
 #pragma unroll
     for (int i = 0; i < K + NP; ++i) {
         const uint64_t v = wave_sum_u64(acc[i]);
-        if (lane == 0) red[wave][i] = v;
+        if (tb.lane == 0) red[tb.wave][i] = v;
     }
     __syncthreads();
     if (threadIdx.x < K + NP)
@@ -718,19 +625,7 @@ __global__ void scan_multi_finalize_kernel(const uint64_t *__restrict__ parts, c
         sl += parts[t * stride + l];
         skl += parts[t * stride + K + (uint32_t)(i % NP)];
     }
-    const double W = (double)w.n_sites, seq_len = (double)w.seq_len;
-    const double nA = (double)pop_n[k], nB = (double)pop_n[l];
-    const double pairsA = nA * (nA - 1.0) / 2.0, pairsB = nB * (nB - 1.0) / 2.0;
-    double pi_a = (pop_n[k] >= 2 && W > 0) ? (double)sk / (pairsA * W) : 0.0;
-    double pi_b = (pop_n[l] >= 2 && W > 0) ? (double)sl / (pairsB * W) : 0.0;
-    double dxy = (pop_n[k] && pop_n[l] && W > 0) ? (double)skl / (nA * nB * W) : 0.0;
-    double pi_xy = 0.5 * (pi_a + pi_b);
-    const double fst = (dxy > 0) ? (dxy - pi_xy) / dxy : 0.0;
-    double da = dxy - pi_xy;
-    if (seq_len > 0) { pi_a /= seq_len; pi_b /= seq_len; da = (dxy - pi_xy) / seq_len; pi_xy /= seq_len; dxy /= seq_len; }
-    impop_pair_stats r;
-    r.fst = fst; r.pi_a = pi_a; r.pi_b = pi_b; r.pi_xy = pi_xy; r.dxy = dxy; r.da = da;
-    out[i] = r;
+    out[i] = hudson_fst(sk, sl, skl, pop_n[k], pop_n[l], (double)w.n_sites, (double)w.seq_len);
 }
 
 // ---- allele-frequency spectrum (scripts/wip/op-afs.py): per window, how many sites carry c copies ----
@@ -791,15 +686,29 @@ static uint32_t popcount_vec(const std::vector<uint32_t> &v) {
     return c;
 }
 
+// What a scan of `windows` streams, derived once for impop_scan_plan_create and impop_scan_multi (scan_route below).
+struct ScanRoute {
+    bool indexed = false;  // the variable-site index (d_vsb, tiles in kept-site coordinates), else d_sb (dense, or a compacted matrix)
+    bool split = false;    // ... and its rare-entry stream (d_vrare)
+    const uint32_t *sb = nullptr;
+    const uint64_t *rare = nullptr;           // null unless split
+    std::vector<impop_window> mapped, rare_w;  // the windows as ranges of sb's sites and (split) of rare's entries
+    uint32_t tile_blocks = 0;
+    std::vector<ScanTile> tiles;
+    std::vector<WinDesc> wins;
+    uint64_t bytes_streamed = 0;
+};
+
 // windows -> elementary segments between sorted window boundaries (a segment is tiled iff some
 // window covers it, and exactly once however many windows overlap it) -> tiles of <= tile_blocks
 // 64-site blocks; every window becomes a contiguous tile range [t0, t1).
-// rare (nullable, split index): the same windows as rare-entry ranges.  A window edge is then the pair (site, entry); both map
-// monotonically from the matrix coordinate, so the pairs are ordered as the edges are.  A segment's blocks and entries are cut
-// into the same number of tiles by their bytes (an entry is 8 B, tile_blocks blocks the budget): one workgroup reads a share
-// of both streams.  Without rare entries the tiles are those of the unsplit index.
-static void build_tiles(const impop_window *windows, const impop_window *rare, uint64_t n_windows, uint32_t tile_blocks, uint32_t wps,
-                        std::vector<ScanTile> &tiles, std::vector<WinDesc> &wd, uint64_t &bytes_streamed) {
+// Split index: a window edge is the pair (site, entry); both map monotonically from the matrix coordinate, so the pairs are
+// ordered as the edges are.  A segment's blocks and entries are cut into the same number of tiles by their bytes (an entry is
+// 8 B, tile_blocks blocks the budget): one workgroup reads a share of both streams.  Without rare entries the tiles are those
+// of the unsplit index.
+static void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
+    const impop_window *windows = rt.mapped.data(), *rare = rt.split ? rt.rare_w.data() : nullptr;
+    std::vector<ScanTile> &tiles = rt.tiles;
     struct Cut {
         uint64_t c, r;
         bool operator<(const Cut &o) const { return c < o.c || (c == o.c && r < o.r); }
@@ -826,45 +735,37 @@ static void build_tiles(const impop_window *windows, const impop_window *rare, u
             cover[cut_index(lo(i))] += 1;
             cover[cut_index(hi(i))] -= 1;
         }
-    const uint64_t row_bytes = 64ull * wps * 4ull, budget = (uint64_t)tile_blocks * row_bytes;
+    const uint64_t row_bytes = 64ull * wps * 4ull, budget = (uint64_t)rt.tile_blocks * row_bytes;
     std::vector<uint64_t> seg_tile_start(cuts.size() + 1, 0);
     int64_t depth = 0;
     for (size_t k = 0; k + 1 < cuts.size(); ++k) {
         seg_tile_start[k] = tiles.size();
         depth += cover[k];
         if (depth <= 0) continue;
-        // tiles are cut on 64-site block boundaries of the layout so interior tiles read whole blocks
-        auto cut = [&](const Cut &s, const Cut &e) {
-            // equal shares: a 781-block segment under a 512-block limit becomes 391 + 390 blocks, not 512 + 269
-            const uint64_t nblk = e.c > s.c ? (e.c + 63) / 64 - s.c / 64 : 0, nr = e.r - s.r;
-            const uint64_t n_parts = std::max<uint64_t>(1, (nblk * row_bytes + nr * 8 + budget - 1) / budget);
-            const uint64_t per = (nblk + n_parts - 1) / n_parts, per_r = (nr + n_parts - 1) / n_parts;
-            uint64_t cs = s.c, rs = s.r;
-            for (uint64_t part = 0; part < n_parts; ++part) {
-                uint64_t ce = cs;
-                if (cs < e.c) ce = std::min(e.c, ((cs / 64) + per) * 64);  // block-aligned end
-                const uint64_t re = std::min(e.r, rs + per_r);
-                if (ce > cs || re > rs) {
-                    tiles.push_back({cs, ce, rs, re});
-                    bytes_streamed += (ce > cs ? ((ce + 63) / 64 - cs / 64) * row_bytes : 0) + (re - rs) * 8ull;
-                }
-                cs = ce;
-                rs = re;
-            }
-        };
+        // tiles are cut on 64-site block boundaries of the layout so interior tiles read whole blocks, in equal shares:
+        // a 781-block segment under a 512-block limit becomes 391 + 390 blocks, not 512 + 269
         const Cut s = cuts[k], e = cuts[k + 1];
-        if (IMPOP_SCAN_SEPARATE_STREAMS && e.c > s.c && e.r > s.r) {
-            cut(s, Cut{e.c, s.r});
-            cut(Cut{e.c, s.r}, e);
-        } else {
-            cut(s, e);
+        const uint64_t nblk = e.c > s.c ? (e.c + 63) / 64 - s.c / 64 : 0, nr = e.r - s.r;
+        const uint64_t n_parts = std::max<uint64_t>(1, (nblk * row_bytes + nr * 8 + budget - 1) / budget);
+        const uint64_t per = (nblk + n_parts - 1) / n_parts, per_r = (nr + n_parts - 1) / n_parts;
+        uint64_t cs = s.c, rs = s.r;
+        for (uint64_t part = 0; part < n_parts; ++part) {
+            uint64_t ce = cs;
+            if (cs < e.c) ce = std::min(e.c, ((cs / 64) + per) * 64);  // block-aligned end
+            const uint64_t re = std::min(e.r, rs + per_r);
+            if (ce > cs || re > rs) {
+                tiles.push_back({cs, ce, rs, re});
+                rt.bytes_streamed += (ce > cs ? ((ce + 63) / 64 - cs / 64) * row_bytes : 0) + (re - rs) * 8ull;
+            }
+            cs = ce;
+            rs = re;
         }
     }
     if (!cuts.empty()) seg_tile_start[cuts.size() - 1] = tiles.size();
     seg_tile_start[cuts.size()] = tiles.size();
-    wd.resize(n_windows);
+    rt.wins.resize(n_windows);
     for (uint64_t i = 0; i < n_windows; ++i) {
-        WinDesc &w = wd[i];
+        WinDesc &w = rt.wins[i];
         w.n_sites = windows[i].site_end - windows[i].site_begin;
         w.seq_len = windows[i].seq_len;
         if (nonempty(i)) {
@@ -903,36 +804,40 @@ struct impop_scan_plan {
 
 // W of every window in ORIGINAL coordinates: its length, or the sum of its columns' weights (tiles of compacted matrices and
 // of indexed plans are in kept-site coordinates, so build_tiles' lengths are not the windows')
-static int window_weights(const impop_matrix *m, bool indexed, const impop_window *windows, uint64_t n_windows, std::vector<WinDesc> &wd) {
+static int window_weights(const impop_matrix *m, const impop_window *windows, uint64_t n_windows, ScanRoute &rt) {
     for (uint64_t i = 0; i < n_windows; ++i) {
+        uint64_t &W = rt.wins[i].n_sites;
         if (!m->wt_prefix.empty()) {
-            wd[i].n_sites = m->wt_prefix[windows[i].site_end] - m->wt_prefix[windows[i].site_begin];
+            W = m->wt_prefix[windows[i].site_end] - m->wt_prefix[windows[i].site_begin];
             // impop_window_stats.n_sites is 32 bits wide: refuse rather than truncate (unweighted windows are
             // checked against the same limit by their length)
-            REQUIRE(wd[i].n_sites <= 0xFFFFFFFFull, "window %llu: the weights of its columns add up to %llu >= 2^32; split the window",
-                    (unsigned long long)i, (unsigned long long)wd[i].n_sites);
-        } else if (m->compact || indexed) {
-            wd[i].n_sites = windows[i].site_end - windows[i].site_begin;
+            REQUIRE(W <= 0xFFFFFFFFull, "window %llu: the weights of its columns add up to %llu >= 2^32; split the window",
+                    (unsigned long long)i, (unsigned long long)W);
+        } else if (m->compact || rt.indexed) {
+            W = windows[i].site_end - windows[i].site_begin;
         }
     }
     return IMPOP_OK;
 }
 
-// Default tile: ~256 KB of matrix per workgroup, but never so large that a small job leaves CUs without
-// work (>= 16 tiles per CU wanted), and never below the 32 blocks the kernel was tuned with.
-// `windows` are in the coordinates of the layout streamed (kept-site coordinates for an indexed plan); the blocks they
-// cover are capped at that layout's length when windows of a compacted matrix or an index overlap.
-// rare (nullable): the windows' rare-entry ranges of a split index, counted as the blocks of rows their bytes would fill.
-static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, const impop_window *rare,
-                                    uint64_t n_windows, bool indexed) {
-    // ~256 KB per tile; wide sites (the any-n kernel, wps > 16) go down to 4 blocks = one per wave
+// Default tile: ~256 KB of matrix per workgroup (wide sites — the any-n kernel, wps > 16 — go down to 4 blocks = one per
+// wave), but never so large that a small job leaves CUs without work (>= 16 tiles per CU wanted), and never below the 32
+// blocks the kernel was tuned with.  With few haplotypes a 32-block tile is only a few KB and the per-workgroup costs
+// (launch, LDS reduction, partial store) bound the kernel instead of HBM: n = 32 ran at 2.6 TB/s with 32-block tiles and
+// 5.0 TB/s with whole-window tiles.
+// The blocks the windows cover are counted in the coordinates of the layout streamed (a compacted matrix: in the original
+// ones) and capped at that layout's length, which overlapping windows exceed; the rare entries of a split index count as
+// the blocks of rows their bytes would fill.
+static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                    const ScanRoute &rt) {
     const uint32_t by_bytes = m->g.wps > 16 ? std::max<uint32_t>(4, 1024 / m->g.wps) : std::max<uint32_t>(32, 1024 / m->g.wps);
+    const impop_window *w = rt.indexed ? rt.mapped.data() : windows;
     uint64_t blocks = 0, entries = 0;
-    for (uint64_t i = 0; i < n_windows; ++i) blocks += (windows[i].site_end - windows[i].site_begin + 63) / 64;
-    if (rare)
-        for (uint64_t i = 0; i < n_windows; ++i) entries += rare[i].site_end - rare[i].site_begin;
+    for (uint64_t i = 0; i < n_windows; ++i) blocks += (w[i].site_end - w[i].site_begin + 63) / 64;
+    if (rt.split)
+        for (uint64_t i = 0; i < n_windows; ++i) entries += rt.rare_w[i].site_end - rt.rare_w[i].site_begin;
     if (m->compact && blocks > m->g.n_block) blocks = m->g.n_block;
-    if (indexed && blocks > m->vg.n_block) blocks = m->vg.n_block;
+    if (rt.indexed && blocks > m->vg.n_block) blocks = m->vg.n_block;
     if (entries > m->n_vrare) entries = m->n_vrare;
     blocks += entries * 8 / (64ull * m->g.wps * 4ull);
     const uint64_t by_parallelism = blocks / (16ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
@@ -959,38 +864,60 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
     p->masks.insert(p->masks.end(), mb.begin(), mb.end());
 }
 
-// the route of a scan of m: the variable-site index when the matrix has one and no site weights (d_wt is indexed by matrix site)
-static bool scan_indexed(const impop_matrix *m) { return m->d_vsb != nullptr && m->wt_prefix.empty(); }
-// ... and, on that route, the rare-entry stream of a split index
-static bool scan_split(const impop_matrix *m) { return scan_indexed(m) && m->d_vrare != nullptr; }
-
-// windows (validated, matrix coordinates) -> the ranges of the layout the route streams (and, split index, of the rare entries)
-static int map_for_route(impop_ctx *ctx, const impop_matrix *m, bool indexed, const impop_window *windows, uint64_t n_windows,
-                         std::vector<impop_window> &mapped, std::vector<impop_window> &rare) {
-    rare.clear();
-    if (indexed) return map_windows_index(ctx, m, windows, n_windows, mapped, scan_split(m) ? &rare : nullptr);
-    map_windows(m, windows, n_windows, mapped);  // compacted matrix: original coordinates -> kept-site index ranges
-    return IMPOP_OK;
-}
-
 // IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it.  kept_sites = every
 // variable site of an indexed route; rare_sites / rare_bytes = the split index's rare entries (all of the matrix / the plan's);
 // split = on, or off:<the reason there is none, blanks as _>
-static void trace_route(const impop_matrix *m, bool indexed, uint64_t n_tiles, uint64_t bytes_streamed, uint64_t n_windows,
-                        const std::vector<ScanTile> &tiles) {
+static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
     static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
     if (!trace) return;
-    const char *why = indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
-    const bool split = indexed && m->d_vrare;
+    const char *why = rt.indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
     uint64_t rare_bytes = 0;
-    for (const ScanTile &t : tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
+    for (const ScanTile &t : rt.tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
     std::string off = "off:" + (!m->wt_prefix.empty() && m->d_vrare ? std::string("site weights") : m->rskip);
     for (char &ch : off) ch = ch == ' ' ? '_' : ch;
     fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s%s%s\n",
-            indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(indexed ? m->n_vkept : m->g.n_site),
-            (unsigned long long)n_tiles, (unsigned long long)bytes_streamed, (unsigned long long)n_windows,
-            (unsigned long long)(split ? m->n_vrare : 0), (unsigned long long)rare_bytes, split ? "on" : off.c_str(), *why ? " why=" : "", why);
+            rt.indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(rt.indexed ? m->n_vkept : m->g.n_site),
+            (unsigned long long)rt.tiles.size(), (unsigned long long)rt.bytes_streamed, (unsigned long long)n_windows,
+            (unsigned long long)(rt.split ? m->n_vrare : 0), (unsigned long long)rare_bytes, rt.split ? "on" : off.c_str(), *why ? " why=" : "", why);
     fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
+}
+
+// every window lies in the matrix and is at most 2^32 - 1 sites long (impop_window_stats.n_sites is 32 bits wide)
+static int check_windows(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        REQUIRE(windows[i].site_begin <= windows[i].site_end && windows[i].site_end <= matrix_span(m),
+                "%s: window %llu: bad site range [%llu,%llu) for %llu sites", fn, (unsigned long long)i,
+                (unsigned long long)windows[i].site_begin, (unsigned long long)windows[i].site_end,
+                (unsigned long long)matrix_span(m));
+        REQUIRE(windows[i].site_end - windows[i].site_begin <= 0xFFFFFFFFull, "%s: window %llu longer than 2^32 sites", fn,
+                (unsigned long long)i);
+    }
+    return IMPOP_OK;
+}
+
+// windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams: the variable-site
+// index when the matrix has one and no site weights (d_wt is indexed by matrix site), with the rare-entry stream of a split
+// index; else the matrix itself (compacted: original coordinates -> kept-site index ranges).  tile_blocks 0: the default.
+static int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                      uint32_t tile_blocks, ScanRoute &rt) {
+    rt.indexed = m->d_vsb != nullptr && m->wt_prefix.empty();
+    rt.split = rt.indexed && m->d_vrare != nullptr;
+    rt.sb = rt.indexed ? m->d_vsb : m->d_sb;
+    rt.rare = rt.split ? m->d_vrare : nullptr;
+    if (rt.indexed) {
+        const int rc = map_windows_index(ctx, m, windows, n_windows, rt.mapped, rt.split ? &rt.rare_w : nullptr);
+        if (rc) return rc;
+    } else {
+        map_windows(m, windows, n_windows, rt.mapped);
+    }
+    rt.tile_blocks = tile_blocks ? tile_blocks : default_tile_blocks(ctx, m, windows, n_windows, rt);
+    build_tiles(rt, n_windows, m->g.wps);
+    const int rc = window_weights(m, windows, n_windows, rt);
+    if (rc) return rc;
+    REQUIRE(rt.tiles.size() < 0x7FFFFFFFull, "%s: %llu tiles exceed one launch; raise tile_blocks", fn,
+            (unsigned long long)rt.tiles.size());
+    trace_route(m, rt, n_windows);
+    return IMPOP_OK;
 }
 
 template <int WPS>
@@ -1028,71 +955,41 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     REQUIRE(prm.d_pi_mode >= 0 && prm.d_pi_mode <= 2, "impop_scan_params.d_pi_mode must be 0..2");
     REQUIRE(prm.s_scope == 0 || prm.s_scope == 1, "impop_scan_params.s_scope must be 0 or 1");
     REQUIRE(prm.tile_blocks <= 4096, "impop_scan_params.tile_blocks too large");
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        REQUIRE(windows[i].site_begin <= windows[i].site_end && windows[i].site_end <= matrix_span(m),
-                "window %llu: bad site range [%llu,%llu) for %llu sites", (unsigned long long)i,
-                (unsigned long long)windows[i].site_begin, (unsigned long long)windows[i].site_end,
-                (unsigned long long)matrix_span(m));
-        REQUIRE(windows[i].site_end - windows[i].site_begin <= 0xFFFFFFFFull, "window %llu longer than 2^32 sites",
-                (unsigned long long)i);
-    }
+    int rc = check_windows("impop_scan", m, windows, n_windows);
+    if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
-    const bool indexed = scan_indexed(m);
-    std::vector<impop_window> mapped, rare;
-    {
-        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped, rare);
-        if (mrc) return mrc;
-    }
-    const impop_window *rare_w = rare.empty() ? nullptr : rare.data();
-    // default tile: ~160 KB of matrix per workgroup.  With few haplotypes a 32-block tile is only a few KB and
-    // the per-workgroup costs (launch, LDS reduction, partial store) bound the kernel instead of HBM:
-    // n = 32 ran at 2.6 TB/s with 32-block tiles and 5.0 TB/s with whole-window tiles
-    const uint32_t tile_blocks = prm.tile_blocks ? prm.tile_blocks
-                                                 : default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, rare_w, n_windows,
-                                                                       indexed);
+    ScanRoute rt;
+    rc = scan_route("impop_scan", ctx, m, windows, n_windows, prm.tile_blocks, rt);
+    if (rc) return rc;
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
-    p->sb = indexed ? m->d_vsb : m->d_sb;
-    p->rare = rare_w ? m->d_vrare : nullptr;
+    p->sb = rt.sb; p->rare = rt.rare;
+    p->n_tiles = rt.tiles.size(); p->bytes_streamed = rt.bytes_streamed;
     m->users++;
     p->d_pi_mode = prm.d_pi_mode; p->s_scope = prm.s_scope;
     const uint32_t wps = m->g.wps;
     plan_set_masks(p, mask_p, mask_a, mask_b);
-
-    std::vector<ScanTile> tiles;
-    std::vector<WinDesc> wd;
-    build_tiles(mapped.data(), rare_w, n_windows, tile_blocks, wps, tiles, wd, p->bytes_streamed);
-    p->n_tiles = tiles.size();
+    uint64_t longest_range = 0;
+    for (const WinDesc &w : rt.wins) longest_range = std::max(longest_range, w.t1 - w.t0);
+    p->finalize_tpw = longest_range > 2048 ? 256 : longest_range > 48 ? 64 : 1;
     auto fail = [&](int code) {
         impop_scan_plan_destroy(p);
         return code;
     };
-    {
-        const int wrc = window_weights(m, indexed, windows, n_windows, wd);
-        if (wrc) return fail(wrc);
-    }
-    trace_route(m, indexed, p->n_tiles, p->bytes_streamed, n_windows, tiles);
-    uint64_t longest_range = 0;
-    for (const WinDesc &w : wd) longest_range = std::max(longest_range, w.t1 - w.t0);
-    p->finalize_tpw = longest_range > 2048 ? 256 : longest_range > 48 ? 64 : 1;
-    if (p->n_tiles >= 0x7FFFFFFFull) {
-        set_error("impop_scan: %llu tiles exceed one launch; raise tile_blocks", (unsigned long long)p->n_tiles);
-        return fail(IMPOP_E_INVALID);
-    }
     hipError_t e;
 #define PLAN_TRY(expr) \
     if ((e = (expr)) != hipSuccess) return fail(hip_fail(e, #expr, __FILE__, __LINE__))
-    PLAN_TRY(hipMalloc((void **)&p->d_tiles, std::max<size_t>(tiles.size(), 1) * sizeof(ScanTile)));
-    PLAN_TRY(hipMalloc((void **)&p->d_parts, std::max<size_t>(tiles.size(), 1) * sizeof(TilePartial)));
+    PLAN_TRY(hipMalloc((void **)&p->d_tiles, std::max<size_t>(rt.tiles.size(), 1) * sizeof(ScanTile)));
+    PLAN_TRY(hipMalloc((void **)&p->d_parts, std::max<size_t>(rt.tiles.size(), 1) * sizeof(TilePartial)));
     PLAN_TRY(hipMalloc((void **)&p->d_wins, std::max<size_t>(n_windows, 1) * sizeof(WinDesc)));
     PLAN_TRY(hipMalloc((void **)&p->d_out, std::max<size_t>(n_windows, 1) * sizeof(impop_window_stats)));
     PLAN_TRY(hipMalloc((void **)&p->d_masks, (size_t)3 * wps * 4));
-    if (!tiles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_tiles, tiles.data(), tiles.size() * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
-    if (n_windows) PLAN_TRY(hipMemcpyAsync(p->d_wins, wd.data(), wd.size() * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
+    if (!rt.tiles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_tiles, rt.tiles.data(), rt.tiles.size() * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
+    if (n_windows) PLAN_TRY(hipMemcpyAsync(p->d_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
     PLAN_TRY(hipMemcpyAsync(p->d_masks, p->masks.data(), (size_t)3 * wps * 4, hipMemcpyHostToDevice, ctx->stream));
     PLAN_TRY(hipStreamSynchronize(ctx->stream));  // host vectors die at return
 #undef PLAN_TRY
-    int rc = ensure_tajima_consts(ctx, p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2);
+    rc = ensure_tajima_consts(ctx, p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2);
     if (rc) return fail(rc);
     *out = p;
     return IMPOP_OK;
@@ -1298,10 +1195,8 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
     REQUIRE(m->g.n_hap <= 65535, "impop_scan_multi: n_hap > 65535 not supported");
     if (!n_windows) return IMPOP_OK;
     REQUIRE(windows && out_host, "impop_scan_multi: NULL windows/out");
-    for (uint64_t i = 0; i < n_windows; ++i)
-        REQUIRE(windows[i].site_begin <= windows[i].site_end && windows[i].site_end <= matrix_span(m) &&
-                    windows[i].site_end - windows[i].site_begin <= 0xFFFFFFFFull,
-                "impop_scan_multi: window %llu: bad site range", (unsigned long long)i);
+    int rc = check_windows("impop_scan_multi", m, windows, n_windows);
+    if (rc) return rc;
     const uint32_t n = m->g.n_hap, wps = m->g.wps, K = n_pop, NP = K * (K - 1) / 2;
     const uint32_t mwords = (n + 63) / 64;
     std::vector<uint32_t> mk((size_t)K * wps), nk(K);
@@ -1318,38 +1213,21 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
         nk[k] = popcount_vec(one);
     }
     HIP_TRY(hipSetDevice(ctx->device));
-    std::vector<ScanTile> tiles;
-    std::vector<WinDesc> wd;
-    uint64_t bytes = 0;
-    const bool indexed = scan_indexed(m);
-    std::vector<impop_window> mapped, rare;
-    {
-        const int mrc = map_for_route(ctx, m, indexed, windows, n_windows, mapped, rare);
-        if (mrc) return mrc;
-    }
-    const impop_window *rare_w = rare.empty() ? nullptr : rare.data();
-    const uint32_t tile_blocks_used = default_tile_blocks(ctx, m, indexed ? mapped.data() : windows, rare_w, n_windows, indexed);
-    {
-        build_tiles(mapped.data(), rare_w, n_windows, tile_blocks_used, wps, tiles, wd, bytes);
-        const int wrc = window_weights(m, indexed, windows, n_windows, wd);
-        if (wrc) return wrc;
-    }
-    const uint32_t *sb = indexed ? m->d_vsb : m->d_sb;
-    const uint64_t *rare_sb = rare_w ? m->d_vrare : nullptr;
-    REQUIRE(tiles.size() < 0x7FFFFFFFull, "impop_scan_multi: too many tiles");
-    trace_route(m, indexed, tiles.size(), bytes, n_windows, tiles);
-    const size_t nt = tiles.size();
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    ScanRoute rt;
+    rc = scan_route("impop_scan_multi", ctx, m, windows, n_windows, 0, rt);
+    if (rc) return rc;
+    const size_t nt = rt.tiles.size();
+    const auto up = round_up_256;
     const size_t o_tiles = 0, o_wins = o_tiles + up(std::max<size_t>(nt, 1) * sizeof(ScanTile)),
                  o_masks = o_wins + up(n_windows * sizeof(WinDesc)), o_n = o_masks + up(mk.size() * 4),
                  o_parts = o_n + up(K * 4), o_out = o_parts + up(std::max<size_t>(nt, 1) * (K + NP) * 8),
                  total = o_out + up(n_windows * NP * sizeof(impop_pair_stats));
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, total, &d);
+    rc = ctx_scratch(ctx, total, &d);
     if (rc) return rc;
     char *base = (char *)d;
-    if (nt) HIP_TRY(hipMemcpyAsync(base + o_tiles, tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_wins, wd.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
+    if (nt) HIP_TRY(hipMemcpyAsync(base + o_tiles, rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(base + o_masks, mk.data(), mk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(base + o_n, nk.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nt) {
@@ -1357,15 +1235,15 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
         const uint32_t *dm = (const uint32_t *)(base + o_masks), *dn = (const uint32_t *)(base + o_n);
         uint64_t *dp = (uint64_t *)(base + o_parts);
         // 32-bit per-lane partial sums: unweighted, <= 512 haplotypes, <= 1024 sites per lane and tile
-        const bool small = m->wt_prefix.empty() && n <= 512 && tile_blocks_used <= 4096;
+        const bool small = m->wt_prefix.empty() && n <= 512 && rt.tile_blocks <= 4096;
         switch (K) {
-            case 2: rc = launch_multi<2>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
-            case 3: rc = launch_multi<3>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
-            case 4: rc = launch_multi<4>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
-            case 5: rc = launch_multi<5>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
-            case 6: rc = launch_multi<6>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
-            case 7: rc = launch_multi<7>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
-            default: rc = launch_multi<8>(ctx->stream, m, sb, rare_sb, nt, dt, dm, dn, dp, small); break;
+            case 2: rc = launch_multi<2>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
+            case 3: rc = launch_multi<3>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
+            case 4: rc = launch_multi<4>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
+            case 5: rc = launch_multi<5>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
+            case 6: rc = launch_multi<6>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
+            case 7: rc = launch_multi<7>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
+            default: rc = launch_multi<8>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
         }
         if (rc) return rc;
         HIP_TRY(hipGetLastError());
@@ -1397,7 +1275,7 @@ IMPOP_API int impop_afs(impop_ctx *ctx, const impop_matrix *m, const impop_windo
     const uint32_t bins = popcount_vec(mk) + 1;
     REQUIRE((size_t)bins * 4 <= 64 * 1024, "impop_afs: more than 16383 haplotypes in the mask");
     HIP_TRY(hipSetDevice(ctx->device));
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const auto up = round_up_256;
     const size_t o_mask = 0, o_wins = up((size_t)m->g.wps * 4), o_out = o_wins + up(n_windows * sizeof(impop_window)),
                  total = o_out + n_windows * bins * 4;
     void *d = nullptr;

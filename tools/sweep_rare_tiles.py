@@ -6,9 +6,9 @@ setting.  --cold also times single launches each behind a 512 MiB write to anoth
 
     python tools/sweep_rare_tiles.py [--rounds 7] [--launches 50] [--tiles 0,8,16,32,49,64,96,128] [--cold 20]
 
-Built with -DIMPOP_SCAN_SEPARATE_STREAMS=1 (tools/build_variants.py scan.hip sep:-DIMPOP_SCAN_SEPARATE_STREAMS=1, then
-IMPOP_HIP_LIBRARY=impop_amd/_variants/libimpop_sep.so) a segment's entries and rows go to separate tiles instead of one
-workgroup reading a share of both.  Prints one JSON line per setting."""
+The lines of profiles/r05_rare_tile_sweep.jsonl marked "separate" came from a variant build that put a segment's entries and
+rows into separate tiles instead of one workgroup reading a share of both; it was slower (0.0512-0.0520 ms) and was removed
+(commit 7af4fd5 still has its build switch).  Prints one JSON line per setting."""
 import argparse
 import json
 import os
