@@ -21,7 +21,7 @@ class ImpopError(RuntimeError):
         self.message = message
 
 
-ABI_VERSION = 2  # IMPOP_ABI_VERSION of include/impop_hip.h
+ABI_VERSION = 3  # IMPOP_ABI_VERSION of include/impop_hip.h
 E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED, E_INTERNAL = -1, -2, -3, -4, -5, -6
 KEEP_SITE_BLOCKED, KEEP_HAP_MAJOR, KEEP_DENSE_SCAN, KEEP_NO_RARE_SPLIT = 1, 2, 4, 8
 IDENTITY_MATCH, IDENTITY_DICE = 0, 1
@@ -72,6 +72,24 @@ class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
 
+class IdentityProblem(C.Structure):
+    _fields_ = [("ident", C.POINTER(C.c_double)), ("n", C.c_uint32), ("reserved", C.c_uint32), ("seq_len", C.c_uint64),
+                ("seed_rank", C.POINTER(C.c_uint32)), ("in_a", C.POINTER(C.c_uint8)), ("in_b", C.POINTER(C.c_uint8)),
+                ("tajima_n", C.c_int64), ("tajima_S", C.c_double)]
+
+
+class IdentityStats(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_groups", C.c_uint32), ("pi", C.c_double), ("pi_site", C.c_double),
+                ("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64), ("fst", C.c_double * 6),
+                ("fst_counts", C.c_uint64 * 6), ("tajima_d", C.c_double)]
+
+
+class IdentityBatchParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("round_digits", C.c_int32), ("threshold", C.c_double),
+                ("fst_round_digits", C.c_int32), ("reserved", C.c_uint32), ("max_chunk_bytes", C.c_uint64)]
+
+
+assert C.sizeof(IdentityStats) == 144 and C.sizeof(IdentityProblem) == 64 and C.sizeof(IdentityBatchParams) == 32
 assert C.sizeof(WindowStats) == 128 and C.sizeof(Window) == 24 and C.sizeof(PairwiseStats) == 96
 
 _vp = C.c_void_p
@@ -153,6 +171,10 @@ SIGNATURES = {
     "impop_sim_bad_text": (C.c_int, [_vp, C.c_char_p, C.c_size_t]),
     "impop_sim_dense": (C.c_int, [_vp, _f64p]),
     "impop_sim_free": (C.c_int, [_vp]),
+    "impop_sim_parse_many": (C.c_int, [C.POINTER(C.c_char_p), C.c_uint64, C.c_int, C.c_int, C.POINTER(_vp), _i32p]),
+    "impop_tajimas_d_from_pi_site": (C.c_int, [C.c_int64, C.c_double, C.c_double, _f64p]),
+    "impop_stats_from_identity_batch": (C.c_int, [_vp, C.POINTER(IdentityProblem), C.c_uint64, C.POINTER(IdentityBatchParams),
+                                                  C.POINTER(IdentityStats), _u32p]),
     "impop_gfa_parse": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(_vp)]),
     "impop_paths_table_parse": (C.c_int, [C.c_char_p, C.POINTER(_vp)]),
     "impop_gfa_info": (C.c_int, [_vp, _u32p, _u64p, _u64p, _i64p]),

@@ -17,8 +17,10 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <atomic>
 #include <string>
 #include <string_view>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -220,6 +222,38 @@ IMPOP_API int impop_sim_parse(const char *path, int flavor, impop_sim **out) {
     }
     *out = S;
     return done(IMPOP_OK);
+}
+
+// the same over k files on a bounded pool of worker threads: files are dealt out one at a time (tables differ in size)
+IMPOP_API int impop_sim_parse_many(const char *const *paths, uint64_t k, int flavor, int n_threads, impop_sim **out, int *rc_out) {
+    REQUIRE(k == 0 || (paths && out && rc_out), "impop_sim_parse_many: NULL argument");
+    REQUIRE(n_threads >= 0, "impop_sim_parse_many: n_threads must be >= 0");
+    if (n_threads == 0) {  // never the machine's core count: the caller's share of it, or 16
+        const char *e = getenv("OMP_NUM_THREADS");
+        const long v = e ? strtol(e, nullptr, 10) : 0;
+        n_threads = v > 0 && v < 4096 ? (int)v : 16;
+    }
+    const uint64_t workers = std::min<uint64_t>((uint64_t)n_threads, k);
+    std::atomic<uint64_t> next{0};
+    auto work = [&]() {
+        for (uint64_t i; (i = next.fetch_add(1)) < k;) {
+            out[i] = nullptr;
+            try {
+                rc_out[i] = paths[i] ? impop_sim_parse(paths[i], flavor, &out[i]) : IMPOP_E_INVALID;
+            } catch (...) {  // out of memory inside one file's parse: that file's status, the others go on
+                out[i] = nullptr;
+                rc_out[i] = IMPOP_E_NOMEM;
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (uint64_t t = 1; t < workers; ++t) pool.emplace_back(work);
+    } catch (...) {  // no more threads to be had: the ones that started, and this one, share the files
+    }
+    work();
+    for (auto &t : pool) t.join();
+    return IMPOP_OK;
 }
 
 IMPOP_API int impop_sim_info(const impop_sim *s, uint32_t *n_names, uint64_t *n_rows, uint64_t *names_bytes,

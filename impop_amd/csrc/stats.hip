@@ -17,25 +17,9 @@ constexpr int ST = 256;  // threads per problem
 // branch on it for divergent (execution masks, loads parked behind their own waits) unless it is told
 __device__ __forceinline__ uint32_t wave_index() { return (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
 
-// deterministic block sums (wave butterfly, then waves in order)
-__device__ __forceinline__ double block_sum_f64(double v, double *sh /*>= ST/64*/) {
-    v = wave_sum_f64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    double t = 0.0;
-    for (int w = 0; w < ST / 64; ++w) t += sh[w];
-    return t;
-}
-__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t *sh) {
-    v = wave_sum_u64(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint64_t t = 0;
-    for (int w = 0; w < ST / 64; ++w) t += sh[w];
-    return t;
-}
+// deterministic block sums (stats_kernels.h) at this file's workgroup size
+__device__ __forceinline__ double block_sum_f64(double v, double *sh /*>= ST/64*/) { return block_sum_f64_n<ST>(v, sh); }
+__device__ __forceinline__ uint64_t block_sum_u64(uint64_t v, uint64_t *sh) { return block_sum_u64_n<ST>(v, sh); }
 
 // ---------------------------------------------------------------------------------------
 // Greedy grouping shared by pica2 (pica2.py:94-112) and hud.py (hud.py:64-86): repeatedly take a seed from

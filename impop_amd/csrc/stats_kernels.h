@@ -141,6 +141,30 @@ __device__ __forceinline__ double sim_get(const SimView &S, uint32_t i, uint32_t
     return v;
 }
 
+#ifdef __HIPCC__
+// deterministic sums over a workgroup of NT threads (wave butterfly, then the waves in order); sh: NT / 64 entries of LDS
+template <int NT>
+__device__ __forceinline__ double block_sum_f64_n(double v, double *sh) {
+    v = wave_sum_f64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double t = 0.0;
+    for (int w = 0; w < NT / 64; ++w) t += sh[w];
+    return t;
+}
+template <int NT>
+__device__ __forceinline__ uint64_t block_sum_u64_n(uint64_t v, uint64_t *sh) {
+    v = wave_sum_u64(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    uint64_t t = 0;
+    for (int w = 0; w < NT / 64; ++w) t += sh[w];
+    return t;
+}
+#endif
+
 struct Pica2Out {
     double pi, pi_site;
     uint32_t n_groups, pad;

@@ -29,6 +29,11 @@ assert PAIRWISE_DTYPE.itemsize == 96
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 
+IDENTITY_STATS_DTYPE = np.dtype([
+    ("status", "<i4"), ("n_groups", "<u4"), ("pi", "<f8"), ("pi_site", "<f8"), ("sum_2pairs", "<f8"), ("n_pairs_with_data", "<u8"),
+    ("fst", "<f8", (6,)), ("fst_counts", "<u8", (6,)), ("tajima_d", "<f8")])
+assert IDENTITY_STATS_DTYPE.itemsize == 144
+
 WINDOW_DTYPE = np.dtype([("site_begin", "<u8"), ("site_end", "<u8"), ("seq_len", "<u8")])
 
 IDENTITY_KINDS = {"match": IDENTITY_MATCH, "dice": IDENTITY_DICE}
@@ -222,6 +227,65 @@ class Context:
                                                C.byref(G), C.byref(det)))
         out = (pi.value, ps.value, grp[:n].copy(), G.value)
         return out + ((det.sum_2pairs, int(det.n_pairs_with_data)),) if detail else out
+
+    def stats_from_identity_batch(self, problems, threshold: float = 1.0, round_digits: Optional[int] = None,
+                                  fst_round_digits: Optional[int] = None, max_chunk_bytes: int = 0, with_groups: bool = True):
+        """pica2 / h-fst / Tajima's D for many identity tables of different size in one call (impop_stats_from_identity_batch).
+        `problems`: dicts with `ident` ([n, n] doubles, NaN = absent) and optionally `seq_len`, `seed_rank`, `in_a` + `in_b`,
+        `tajima_n` + `tajima_S`.  -> (records [k] of IDENTITY_STATS_DTYPE, list of per-problem group_of arrays or None).
+        A problem of 1024 or more elements comes back with status E_UNSUPPORTED in its own record."""
+        k = len(problems)
+        arr = (_lib.IdentityProblem * max(k, 1))()
+        keep = []  # the arrays the pointers refer to
+        total = 0
+        f64p, u32p, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint8)
+        for q, pr in zip(arr, problems):
+            a = np.ascontiguousarray(pr["ident"], dtype=np.float64)
+            n = a.shape[0] if a.ndim == 2 else 0
+            if n and a.shape != (n, n):
+                raise ValueError("ident must be a square matrix")
+            keep.append(a)
+            q.ident = a.ctypes.data_as(f64p) if n else None
+            q.n = n
+            q.seq_len = int(pr.get("seq_len") or 0) if (pr.get("seq_len") or 0) > 0 else 0
+            sr = pr.get("seed_rank")
+            if sr is not None:
+                sr = np.ascontiguousarray(sr, dtype=np.uint32)
+                if sr.shape != (n,):
+                    raise ValueError("seed_rank must have one entry per element")
+                keep.append(sr)
+                q.seed_rank = sr.ctypes.data_as(u32p) if n else None
+            fa, fb = pr.get("in_a"), pr.get("in_b")
+            if (fa is None) != (fb is None):
+                raise ValueError("in_a and in_b go together")
+            if fa is not None:
+                fa = np.ascontiguousarray(fa, dtype=np.uint8)
+                fb = np.ascontiguousarray(fb, dtype=np.uint8)
+                if fa.shape != (n,) or fb.shape != (n,):
+                    raise ValueError("in_a / in_b must have one flag per element")
+                if n == 0:  # the flags' presence is carried by the pointers
+                    fa, fb = np.zeros(1, np.uint8), np.zeros(1, np.uint8)
+                keep += [fa, fb]
+                q.in_a, q.in_b = fa.ctypes.data_as(u8p), fb.ctypes.data_as(u8p)
+            tn = pr.get("tajima_n")
+            q.tajima_n = int(tn) if tn is not None else 0
+            q.tajima_S = float(pr.get("tajima_S") or 0.0)
+            total += n
+        par = _lib.IdentityBatchParams(C.sizeof(_lib.IdentityBatchParams), -1 if round_digits is None else int(round_digits),
+                                       float(threshold), -1 if fst_round_digits is None else int(fst_round_digits), 0,
+                                       int(max_chunk_bytes))
+        out = np.zeros(k, dtype=IDENTITY_STATS_DTYPE)
+        grp = np.zeros(max(total, 1), dtype=np.uint32) if with_groups else None
+        check(self._lib.impop_stats_from_identity_batch(self.handle, arr, k, C.byref(par),
+                                                        out.ctypes.data_as(C.POINTER(_lib.IdentityStats)),
+                                                        grp.ctypes.data_as(u32p) if with_groups else None))
+        if not with_groups:
+            return out, None
+        groups, o = [], 0
+        for q in arr[:k]:
+            groups.append(grp[o:o + q.n].copy())
+            o += q.n
+        return out, groups
 
     def pica2_pair_terms(self, ident: np.ndarray, round_digits: Optional[int], rep, group_size):
         """Identity of the representatives and (1 - sim) f_g f_h for every group pair g < h, row-major

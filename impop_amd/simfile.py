@@ -117,6 +117,44 @@ def densify(similarity_dict, names: Sequence[str]) -> np.ndarray:
     return out
 
 
+def table_from_handle(lib, h, with_elements: bool = False):
+    """A natively parsed table (impop_sim handle) as (sorted names, dense, row count[, elements]); None where the
+    reference-faithful Python reader has to take over: a bad value was seen, or the file holds no data."""
+    import ctypes as C
+
+    from . import _lib
+    n, rows, nb, bad_line, n_bad = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_int64(), C.c_uint64()
+    _lib.check(lib.impop_sim_info(h, C.byref(n), C.byref(rows), C.byref(nb), C.byref(bad_line), C.byref(n_bad)))
+    if bad_line.value >= 0 or n_bad.value or not (n.value or rows.value):
+        return None
+    buf = C.create_string_buffer(max(nb.value, 1))
+    _lib.check(lib.impop_sim_names(h, buf))
+    names = [x.decode("utf-8", "surrogateescape") for x in buf.raw[: nb.value].split(b"\0")[: n.value]]
+    dense = np.empty((n.value, n.value))
+    _lib.check(lib.impop_sim_dense(h, dense.ctypes.data_as(C.POINTER(C.c_double))))
+    if not with_elements:
+        return names, dense, int(rows.value)
+    seen = np.zeros(max(n.value, 1), dtype=np.uint32)
+    _lib.check(lib.impop_sim_first_seen(h, seen.ctypes.data_as(C.POINTER(C.c_uint32))))
+    elements = set()
+    for k in seen[: n.value]:
+        elements.add(names[int(k)])
+    return names, dense, int(rows.value), elements
+
+
+def python_read_dense(filename, flavor: str = "pica2", stream=None):
+    """read_dense through the reference-faithful Python readers alone -> (names, dense, row count, elements).  `stream`
+    (optional): where the reader's messages go instead of the flavour's own stdout / stderr."""
+    fl = _flavor(flavor)
+    if stream is not None:
+        fl.stream = stream
+    d, elements, pair_count = _read_table(filename, fl)
+    if flavor != "pica2":
+        pair_count = len(d)
+    names = sorted(elements)
+    return names, densify(d, names), pair_count, elements
+
+
 def read_dense(filename, flavor: str = "pica2", with_elements: bool = False):
     """Fast ingest used by the drop-in CLIs: (sorted names, dense [n,n] identity with NaN for absent
     pairs, number of data rows[, elements]).  `elements` (with_elements=True) is the set of names built the
@@ -133,32 +171,13 @@ def read_dense(filename, flavor: str = "pica2", with_elements: bool = False):
     rc = lib.impop_sim_parse(os.fsencode(filename), 0 if flavor == "pica2" else 1, C.byref(h))
     if rc == 0:
         try:
-            n, rows, nb, bad_line, n_bad = C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_int64(), C.c_uint64()
-            _lib.check(lib.impop_sim_info(h, C.byref(n), C.byref(rows), C.byref(nb), C.byref(bad_line), C.byref(n_bad)))
-            if bad_line.value < 0 and n_bad.value == 0:
-                buf = C.create_string_buffer(max(nb.value, 1))
-                _lib.check(lib.impop_sim_names(h, buf))
-                names = [x.decode("utf-8", "surrogateescape") for x in buf.raw[: nb.value].split(b"\0")[: n.value]]
-                dense = np.empty((n.value, n.value))
-                _lib.check(lib.impop_sim_dense(h, dense.ctypes.data_as(C.POINTER(C.c_double))))
-                if n.value or rows.value:
-                    if not with_elements:
-                        return names, dense, int(rows.value)
-                    seen = np.zeros(max(n.value, 1), dtype=np.uint32)
-                    _lib.check(lib.impop_sim_first_seen(h, seen.ctypes.data_as(C.POINTER(C.c_uint32))))
-                    elements = set()
-                    for k in seen[: n.value]:
-                        elements.add(names[int(k)])
-                    return names, dense, int(rows.value), elements
+            got = table_from_handle(lib, h, with_elements)
+            if got is not None:
+                return got
         finally:
             lib.impop_sim_free(h)
     # fall back: exact reference behaviour (including its messages / sys.exit) for everything else
-    if flavor == "pica2":
-        d, elements, pair_count = read_similarity_file_pica2(filename)
-    else:
-        d, elements = read_similarity_file_hfst(filename)
-        pair_count = len(d)
-    names = sorted(elements)
+    names, dense, pair_count, elements = python_read_dense(filename, flavor)
     if with_elements:
-        return names, densify(d, names), pair_count, elements
-    return names, densify(d, names), pair_count
+        return names, dense, pair_count, elements
+    return names, dense, pair_count

@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define IMPOP_ABI_VERSION 2
+#define IMPOP_ABI_VERSION 3
 
 typedef enum impop_status {
     IMPOP_OK = 0,
@@ -423,6 +423,56 @@ int impop_fst_grouped_from_identity(impop_ctx *ctx, const double *ident, uint32_
 int impop_tajimas_d(impop_ctx *ctx, const int64_t *n, const double *S, const double *pi, uint64_t count,
                     double *D, double *comps);
 
+/* ---- a ragged batch of identity tables (one `.sim` table per window) ------------
+ * pica2, h-fst and Tajima's D for k tables of different size, names and seed order in one call: per chunk of tables one
+ * upload of the matrices, one of the side tables, two kernel launches whatever the number of tables, one download.
+ * Chunks are capped by the bytes they upload (max_chunk_bytes; 0 = the size of the context's scratch, at least 128 MiB);
+ * chunking never changes a record.  Staging goes through the context's page-locked buffer.
+ * Per problem: pica2 as impop_pi_from_identity (threshold, round_digits, seq_len, seed_rank); with in_a / in_b also
+ * h-fst as impop_fst_from_identity (fst_round_digits; the same seq_len) — without them fst[] is NaN and fst_counts[] 0;
+ * with tajima_n >= 2 also Tajima's D as impop_tajimas_d(tajima_n, tajima_S, pi) with pi = pi_site through its "%.8f" text
+ * (run_tajd.sh:174-180) — else, or for a negative S or a NaN pi_site, tajima_d is NaN.
+ * Supported n per problem: 0 .. 1023.  A larger problem gets status = IMPOP_E_UNSUPPORTED in its own record (every other
+ * field 0) and does not fail the call: send it through the single-problem entry points.
+ * group_of (nullable): the problems' n group indices back to back, in problem order.
+ * Checks the device error word like impop_pi_from_identity.
+ * Under IMPOP_TRACE=1 every chunk prints one line on stderr:
+ *   [impop_sim_batch] tables=<in the chunk> chunk=<index> bytes_up=<uploaded> launches=<kernel launches> max_n=<largest n>
+ *                     stage_us=<host copy into the staging buffer> up_us= kernels_us= down_us=<GPU time of each phase> */
+typedef struct impop_identity_problem {
+    const double *ident;        /* n x n row-major, NaN = pair absent; NULL allowed when n == 0 */
+    uint32_t n, reserved;
+    uint64_t seq_len;           /* 0 = None */
+    const uint32_t *seed_rank;  /* nullable; n distinct values, as impop_pi_from_identity */
+    const uint8_t *in_a, *in_b; /* n flags each; both or neither */
+    int64_t tajima_n;           /* < 2 = no D */
+    double tajima_S;
+} impop_identity_problem;
+#define IMPOP_IDENTITY_STATS_BYTES 144
+typedef struct impop_identity_stats { /* 144 bytes, fixed layout */
+    int32_t status;             /* IMPOP_OK or IMPOP_E_UNSUPPORTED */
+    uint32_t n_groups;
+    double pi, pi_site, sum_2pairs;
+    uint64_t n_pairs_with_data;
+    double fst[6];              /* fst, pi_a, pi_b, pi_xy, dxy, da */
+    uint64_t fst_counts[6];     /* pairs_a, missing_a, pairs_b, missing_b, pairs_between, missing_between */
+    double tajima_d;
+} impop_identity_stats;
+typedef struct impop_identity_batch_params {
+    uint32_t struct_size;       /* sizeof(impop_identity_batch_params) */
+    int32_t round_digits;       /* pica2 rounding, < 0 = none */
+    double threshold;
+    int32_t fst_round_digits;   /* h-fst rounding, < 0 = none */
+    uint32_t reserved;
+    uint64_t max_chunk_bytes;   /* 0 = default */
+} impop_identity_batch_params;
+int impop_stats_from_identity_batch(impop_ctx *ctx, const impop_identity_problem *problems, uint64_t k,
+                                    const impop_identity_batch_params *params, impop_identity_stats *out,
+                                    uint32_t *group_of);
+/* The tajima_d of a batch record as host arithmetic (no device needed): Tajima's D for (n, S) and pi = pi_site rounded
+ * through its "%.8f" text; NaN for n < 2, S < 0, or a negative or NaN pi_site. */
+int impop_tajimas_d_from_pi_site(int64_t n, double S, double pi_site, double *D);
+
 /* af.cluster (af.py:35-44): connected components of {identity >= threshold}
  * ordered by (-size, members); cluster_of[i] = 0-based cluster rank (c1 = 0),
  * sizes (nullable): n entries, first n_clusters valid. */
@@ -450,6 +500,11 @@ int impop_sim_first_seen(const impop_sim *s, uint32_t *first_seen_out);
 int impop_sim_bad_text(const impop_sim *s, char *buf, size_t buflen);
 int impop_sim_dense(const impop_sim *s, double *out);        /* n x n, sorted-name order, NaN = absent */
 int impop_sim_free(impop_sim *s);
+/* impop_sim_parse on k files with at most n_threads worker threads (0 = OMP_NUM_THREADS if set, else 16; never the
+ * machine's core count).  out[i] / rc_out[i] are what impop_sim_parse(paths[i], flavor, ..) gives (out[i] NULL where
+ * rc_out[i] != 0; IMPOP_E_NOMEM for a file whose parse ran out of memory).  Returns IMPOP_OK unless an argument is bad;
+ * per-file failures are in rc_out. */
+int impop_sim_parse_many(const char *const *paths, uint64_t k, int flavor, int n_threads, impop_sim **out, int *rc_out);
 
 /* ---- native GFA ingest (host code) ---------------------------------------------
  * S / P / W lines of the window graph (`impg query -o gfa`, run_tajd.sh:126; `odgi view -g`, :140) -> the NODE-level

@@ -8,6 +8,13 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr1.npz --bed windows.bed --format hfst -A afr.txt -B eas.txt [-r 5]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format pica2 -t 0.999 -r 5 [-u subset.txt]
     impop_scan.py --matrix chr1.npz chr2.npz ... --bed genome.bed --format all ...            # one matrix per chromosome
+    impop_scan.py --sim-list windows.tsv --format pica2 -t 0.999 -r 5                         # one `.sim` table per window
+
+--sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
+window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
+two kernel launches (impop_stats_from_identity_batch) while the next chunk is parsed on the host threads.  tajd / all need the
+S column (segregating sites, run_tajd.sh:129-150) and -l.  A window whose table fails (missing file, invalid similarity value,
+a population without sequences) is skipped with the reference driver's stderr lines; no per-window log files are written.
 
 What -t / -r mean, per format (the THRESHOLD / R_VALUE columns always print what was computed):
   tajd    pica2's threshold / rounding behind the PI column and Tajima's D.  Defaults 0.999 and 5 — run_tajd.sh:9-10.
@@ -30,14 +37,14 @@ import numpy as np
 
 import _bootstrap  # noqa: F401
 import impop_amd
+from impop_amd.drivers import bed_row_ok
 from impop_amd.matrixio import load_matrix
 from impop_amd.popnames import expand_population, read_subset_file
 
 
 def read_bed(path, fmt="tajd"):
     """BED rows -> [(chrom, start, end)].  Comment / empty rows are skipped silently, unusable rows with the warning the
-    reference driver of that table prints on stderr: run_tajd.sh:104-117 (tajd, all), run_h-fst.sh:159-181 (hfst),
-    run_fst_impg.sh:166-179 (fst3pi), run_pica2_impg.sh:128-136 (pica2; it validates only the length)."""
+    reference driver of that table prints on stderr (impop_amd.drivers.bed_row_ok)."""
     rows = []
     with open(path) as f:
         for line_no, line in enumerate(f, 1):
@@ -46,37 +53,8 @@ def read_bed(path, fmt="tajd"):
                 continue
             chrom = p[0]
             start, end = (p[1] if len(p) > 1 else ""), (p[2] if len(p) > 2 else "")
-            numeric = start.isdigit() and end.isdigit()
-            if fmt == "hfst":
-                if not start or not end:
-                    print(f"Warning: Incomplete BED entry at line {line_no}, skipping", file=sys.stderr)
-                    continue
-                if not numeric:
-                    print(f"Warning: Non-integer coordinates at line {line_no}: {chrom}:{start}-{end}, skipping", file=sys.stderr)
-                    continue
-                if int(start) >= int(end):
-                    print(f"Warning: Invalid interval at line {line_no}: {chrom}:{start}-{end}, skipping", file=sys.stderr)
-                    continue
-            elif fmt == "fst3pi":
-                if not start or not end:
-                    print(f"Warning: Incomplete BED entry for chromosome {chrom}, skipping", file=sys.stderr)
-                    continue
-                if not numeric:  # the driver's plain `echo` prints the backslash-t sequences literally
-                    print(f"Warning: Non-integer coordinates in BED entry {chrom}\\t{start}\\t{end}, skipping", file=sys.stderr)
-                    continue
-                if int(end) - int(start) <= 0:
-                    print(f"Warning: Non-positive interval length for {chrom}:{start}-{end}, skipping", file=sys.stderr)
-                    continue
-            else:
-                if not numeric:
-                    print(f"Warning: Skipping malformed BED entry: {chrom} {start} {end}", file=sys.stderr)  # run_tajd.sh:108-111
-                    continue
-                if int(end) - int(start) <= 0:
-                    if fmt == "pica2":
-                        print(f"Warning: Skipping region with non-positive length: {chrom}:{start}-{end}", file=sys.stderr)
-                    else:
-                        print(f"Warning: Skipping non-positive interval length for {chrom}:{start}-{end}", file=sys.stderr)
-                    continue
+            if not bed_row_ok(chrom, start, end, line_no, fmt):
+                continue
             rows.append((chrom, int(start), int(end)))
     return rows
 
@@ -213,10 +191,181 @@ class Runner:
         self.ctx.close()
 
 
+def write_tables(out, args, fmt, regions, L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables=None, panel_labels=None, fst_skip=()):
+    """the TSV tables of the reference's drivers (headers run_pica2_impg.sh:119,122 / run_h-fst.sh:148 / run_tajd.sh:101 /
+    run_fst_impg.sh:158) from per-row columns; shared by the matrix path and --sim-list"""
+    if args.panel:
+        p = 0
+        K = len(args.panel)
+        for k in range(K):
+            for l in range(k + 1, K):
+                print(f"# {panel_labels[k]}-vs-{panel_labels[l]}", file=out)
+                print("REGION\tLENGTH\tFST\tPI_A\tPI_B\tPI_XY\tDXY\tDA", file=out)
+                for i, reg in enumerate(regions):
+                    r = panel_tables[i, p]
+                    print(f"{reg}\t{L_col[i]}\t{float(r['fst']):.8f}\t{float(r['pi_a']):.8f}\t{float(r['pi_b']):.8f}\t"
+                          f"{float(r['pi_xy']):.8f}\t{float(r['dxy']):.8f}\t{float(r['da']):.8f}", file=out)
+                p += 1
+    if fmt in ("pica2", "all"):
+        if args.subset:
+            print("REGION\tSUBSET\tLENGTH\tTHRESHOLD\tR_VALUE\tPICA_OUTPUT", file=out)
+        else:
+            print("REGION\tLENGTH\tTHRESHOLD\tR_VALUE\tPICA_OUTPUT", file=out)
+        for i, reg in enumerate(regions):
+            cell = f"{col['pi_site'][i]:.8f} (sequence length: {L_col[i]})"  # pica2.py:226
+            if args.subset:
+                print(f"{reg}\t{os.path.basename(args.subset)}\t{L_col[i]}\t{thr_txt}\t{r_txt}\t{cell}", file=out)
+            else:
+                print(f"{reg}\t{L_col[i]}\t{thr_txt}\t{r_txt}\t{cell}", file=out)
+    if fmt in ("hfst", "all") and args.pop_a and args.pop_b and not args.panel:
+        print("REGION\tLENGTH\tFST\tPI_A\tPI_B\tPI_XY\tDXY\tDA", file=out)
+        for i, reg in enumerate(regions):
+            if i in fst_skip:  # --sim-list: a window whose table holds no member of one population
+                continue
+            print(f"{reg}\t{L_col[i]}\t{col['fst'][i]:.8f}\t{col['pi_a'][i]:.8f}\t{col['pi_b'][i]:.8f}\t"
+                  f"{col['pi_xy'][i]:.8f}\t{col['dxy'][i]:.8f}\t{col['da'][i]:.8f}", file=out)
+    if fmt == "fst3pi":
+        from impop_amd.drivers import fst_3pi_fields
+        print("REGION\tLENGTH\tTHRESHOLD\tR_VALUE\tPI_A\tPI_B\tPI_C\tPI_AB_AVG\tFST", file=out)  # run_fst_impg.sh:158
+        for i, reg in enumerate(regions):
+            ta, tb, tc, avg, fst = fst_3pi_fields(float(col["pi3_a"][i]), float(col["pi3_b"][i]), float(col["pi3_c"][i]))
+            print(f"{reg}\t{L_col[i]}\t{thr_txt}\t{r_txt}\t{ta}\t{tb}\t{tc}\t{avg}\t{fst}", file=out)
+    if fmt in ("tajd", "all"):
+        print("REGION\tLENGTH\tSAMPLES\tSEGREGATING_SITES\tPI\tTAJIMAS_D", file=out)
+        for i, reg in enumerate(regions):
+            D = float(col["tajima_d"][i])
+            taj = "NA" if D != D else repr(D)  # run_tajd.sh:192-194
+            print(f"{reg}\t{L_col[i]}\t{samples_col}\t{int(s_all[i])}\t{col['pi_site'][i]:.8f}\t{taj}", file=out)
+
+
+def sim_list_refusal(args):
+    """what --sim-list does not combine with (one line each, exit 2, before any device is opened)"""
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--sim-list is a one-process, one-GPU driver: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--sim-list runs on one GPU: not with --devices N"
+    if args.panel:
+        return "--sim-list has no --panel (the K-population scan streams a presence matrix)"
+    if args.compact:
+        return "--sim-list has no --compact (there is no presence matrix to compact)"
+    if args.fst_method == "grouped":
+        return "--sim-list computes the direct h-fst table: not with --fst-method grouped"
+    if args.format == "fst3pi":
+        return "--sim-list formats are pica2, hfst, tajd and all"
+    if args.format == "hfst" and not (args.pop_a and args.pop_b):
+        return "--format hfst needs -A and -B"
+    if args.format in ("tajd", "all") and not args.sample_list:
+        return "--sim-list --format tajd / all needs -l samples.txt (SAMPLE_COUNT, run_tajd.sh:83)"
+    if args.sequence_length is not None and (args.format != "pica2" or args.sequence_length <= 0):
+        return "--sequence-length (a positive integer) belongs to --format pica2 (run_pica2_impg.sh -l)"
+    return None
+
+
+def scan_sim_list(args, fmt, pica_t, pica_r, fst_r, thr_txt, r_txt):
+    """--sim-list: every window's own `.sim` table through impop_stats_from_identity_batch (impop_amd.simbatch)"""
+    from impop_amd import simbatch
+    rows = simbatch.read_sim_list(args.sim_list, fmt)
+    want_pica, want_fst, want_d = fmt in ("pica2", "tajd", "all"), fmt in ("hfst", "all") and bool(args.pop_a and args.pop_b), \
+        fmt in ("tajd", "all")
+    if want_d:
+        for row in rows:
+            try:
+                ok = row.S is not None and float(row.S) >= 0
+            except ValueError:
+                ok = False
+            if not ok:
+                print(f"Error: --format {fmt} with --sim-list needs a non-negative S column (row {row.chrom}:{row.start}-{row.end})",
+                      file=sys.stderr)
+                sys.exit(2)
+    sample_count = None
+    if args.sample_list:
+        sample_count = awk_line_count(args.sample_list)  # run_tajd.sh:83
+        if want_d and sample_count < 2:
+            print(f"Error: Need at least two samples to compute Tajima's D (found {sample_count})", file=sys.stderr)  # :84-87
+            sys.exit(1)
+    pops, no_fst = None, set()
+    NO_POP = "Error: No valid sequences found in one or both populations"
+    if want_fst:
+        pops = [simbatch.PopulationFlags(read_subset_file(f)) for f in (args.pop_a, args.pop_b)]
+
+    def full_name(chrom):
+        return chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
+
+    def length_of(row):
+        return args.sequence_length if args.sequence_length is not None else row.end - row.start
+
+    def make_problem(row, tab):
+        pr = {"ident": tab.dense, "seq_len": length_of(row)}
+        if want_pica:
+            pr["seed_rank"] = simbatch.seed_rank(tab)
+        if want_fst:
+            (fa, miss_a), (fb, miss_b) = pops[0](tab.names), pops[1](tab.names)
+            for tag, miss in (("A", miss_a), ("B", miss_b)):  # per window, as the per-window script prints them
+                if miss:
+                    print(f"Warning: {miss} identifiers from population {tag} did not match any sequences", file=sys.stderr)
+            both = int((fa & fb).sum())
+            if both:
+                print(f"Warning: {both} sequences appear in both populations", file=sys.stderr)  # h-fst.py:181-185
+            if not fa.any() or not fb.any():  # h-fst.py:319-321
+                if fmt == "hfst":
+                    return simbatch.SimFailure(NO_POP)
+                no_fst.add((row.chrom, row.start, row.end))  # --format all: only the h-fst table loses the window
+            else:
+                pr["in_a"], pr["in_b"] = fa, fb
+        if want_d:
+            pr["tajima_n"], pr["tajima_S"] = sample_count, float(row.S)
+        return pr
+
+    ctx = impop_amd.Context(args.device)
+    flavor = "hfst" if fmt == "hfst" else "pica2"
+    results = simbatch.run_pipeline(ctx, rows, flavor, make_problem, pica_t, pica_r, fst_r, n_threads=args.sim_threads)
+    ctx.close()
+    kept = []
+    for row, res in zip(rows, results):
+        region = f"{full_name(row.chrom)}:{row.start}-{row.end}"
+        if res[0] == "ok":
+            kept.append((region, row, res[1]))
+            continue
+        # the reference drivers' stderr lines: run_pica2_impg.sh:174-176, run_h-fst.sh:83-84, run_tajd.sh:166-167
+        if fmt == "hfst":
+            print(res[1], file=sys.stderr)
+            print(f"Error: FST calculation failed for region {region}", file=sys.stderr)
+        elif fmt == "pica2":
+            print(f"Error: pica2.py failed for region {region}", file=sys.stderr)
+            print(res[1], file=sys.stderr)
+        else:
+            print(f"Warning: pica2.py failed for region {region}", file=sys.stderr)
+    n_rows = len(kept)
+    col = {k: np.full(n_rows, np.nan) for k in ("pi_site", "tajima_d", "fst", "pi_a", "pi_b", "pi_xy", "dxy", "da")}
+    s_all = np.zeros(n_rows, dtype=np.int64)
+    L_col = np.array([length_of(row) for _, row, _ in kept], dtype=np.int64)
+    for i, (_, row, rec) in enumerate(kept):
+        col["pi_site"][i], col["tajima_d"][i] = rec["pi_site"], rec["tajima_d"]
+        for j, k in enumerate(("fst", "pi_a", "pi_b", "pi_xy", "dxy", "da")):
+            col[k][i] = rec["fst"][j]
+        if want_d:
+            s_all[i] = int(float(row.S))
+    out = open(args.output, "w") if args.output else sys.stdout
+    fst_skip = set()
+    for i, (region, row, _) in enumerate(kept):
+        if (row.chrom, row.start, row.end) in no_fst:  # run_h-fst.sh:83-84, behind h-fst.py's own line
+            print(NO_POP, file=sys.stderr)
+            print(f"Error: FST calculation failed for region {region}", file=sys.stderr)
+            fst_skip.add(i)
+    write_tables(out, args, fmt, [k[0] for k in kept], L_col, col, s_all, sample_count if sample_count is not None else 0, thr_txt, r_txt,
+                 fst_skip=fst_skip)
+    if args.output:
+        out.close()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--matrix", required=True, nargs="+", help=".npz presence matrices (impop_amd.matrixio), one per chromosome")
-    ap.add_argument("--bed", "-b", required=True)
+    ap.add_argument("--matrix", nargs="+", help=".npz presence matrices (impop_amd.matrixio), one per chromosome")
+    ap.add_argument("--bed", "-b")
+    ap.add_argument("--sim-list", metavar="FILE", help="instead of --matrix / --bed: TSV `chrom start end sim_path [S]`, one .sim "
+                    "identity table per window (formats pica2, hfst, tajd, all)")
+    ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
+                    "(default: OMP_NUM_THREADS, else 16)")
     ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
@@ -245,6 +394,15 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend when launched with WORLD_SIZE > 1 "
                     "(nccl = RCCL over xGMI; gloo for rehearsals)")
     args = ap.parse_args()
+    if args.sim_list and (args.matrix or args.bed):
+        ap.error("--sim-list replaces --matrix / --bed: give one or the other")
+    if not args.sim_list and not (args.matrix and args.bed):
+        ap.error("give --matrix and --bed, or --sim-list")
+    if args.sim_list:
+        refusal = sim_list_refusal(args)
+        if refusal:
+            print(f"Error: {refusal}", file=sys.stderr)
+            sys.exit(2)
     threshold_text = None
     if args.threshold is not None:
         args.threshold, threshold_text = args.threshold
@@ -297,6 +455,11 @@ def main():
     if args.panel and (fmt != "hfst" or fst_pairs):
         print("Error: --panel is the streaming K-population scan of --format hfst (direct method, match identity, no rounding)", file=sys.stderr)
         sys.exit(2)
+
+    thr_txt = threshold_text if threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
+    r_txt = "" if pica_r is None else str(pica_r)
+    if args.sim_list:
+        return scan_sim_list(args, fmt, pica_t, pica_r, fst_r, thr_txt, r_txt)
 
     # ---- matrices by chromosome, BED rows to their matrix
     mats = [load_matrix(p) for p in args.matrix]
@@ -424,49 +587,7 @@ def main():
                 col[k][idx] = fst_rec[k]
         run.close()
 
-    regions = [r[0] for r in rows]
-    thr_txt = threshold_text if threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
-    r_txt = "" if pica_r is None else str(pica_r)
-    if args.panel:
-        p = 0
-        K = len(args.panel)
-        for k in range(K):
-            for l in range(k + 1, K):
-                print(f"# {panel_labels[k]}-vs-{panel_labels[l]}", file=out)
-                print("REGION\tLENGTH\tFST\tPI_A\tPI_B\tPI_XY\tDXY\tDA", file=out)
-                for i, reg in enumerate(regions):
-                    r = panel_tables[i, p]
-                    print(f"{reg}\t{L_col[i]}\t{float(r['fst']):.8f}\t{float(r['pi_a']):.8f}\t{float(r['pi_b']):.8f}\t"
-                          f"{float(r['pi_xy']):.8f}\t{float(r['dxy']):.8f}\t{float(r['da']):.8f}", file=out)
-                p += 1
-    if fmt in ("pica2", "all"):
-        if args.subset:
-            print("REGION\tSUBSET\tLENGTH\tTHRESHOLD\tR_VALUE\tPICA_OUTPUT", file=out)
-        else:
-            print("REGION\tLENGTH\tTHRESHOLD\tR_VALUE\tPICA_OUTPUT", file=out)
-        for i, reg in enumerate(regions):
-            cell = f"{col['pi_site'][i]:.8f} (sequence length: {L_col[i]})"  # pica2.py:226
-            if args.subset:
-                print(f"{reg}\t{os.path.basename(args.subset)}\t{L_col[i]}\t{thr_txt}\t{r_txt}\t{cell}", file=out)
-            else:
-                print(f"{reg}\t{L_col[i]}\t{thr_txt}\t{r_txt}\t{cell}", file=out)
-    if fmt in ("hfst", "all") and args.pop_a and args.pop_b and not args.panel:
-        print("REGION\tLENGTH\tFST\tPI_A\tPI_B\tPI_XY\tDXY\tDA", file=out)
-        for i, reg in enumerate(regions):
-            print(f"{reg}\t{L_col[i]}\t{col['fst'][i]:.8f}\t{col['pi_a'][i]:.8f}\t{col['pi_b'][i]:.8f}\t"
-                  f"{col['pi_xy'][i]:.8f}\t{col['dxy'][i]:.8f}\t{col['da'][i]:.8f}", file=out)
-    if fmt == "fst3pi":
-        from impop_amd.drivers import fst_3pi_fields
-        print("REGION\tLENGTH\tTHRESHOLD\tR_VALUE\tPI_A\tPI_B\tPI_C\tPI_AB_AVG\tFST", file=out)  # run_fst_impg.sh:158
-        for i, reg in enumerate(regions):
-            ta, tb, tc, avg, fst = fst_3pi_fields(float(col["pi3_a"][i]), float(col["pi3_b"][i]), float(col["pi3_c"][i]))
-            print(f"{reg}\t{L_col[i]}\t{thr_txt}\t{r_txt}\t{ta}\t{tb}\t{tc}\t{avg}\t{fst}", file=out)
-    if fmt in ("tajd", "all"):
-        print("REGION\tLENGTH\tSAMPLES\tSEGREGATING_SITES\tPI\tTAJIMAS_D", file=out)
-        for i, reg in enumerate(regions):
-            D = float(col["tajima_d"][i])
-            taj = "NA" if D != D else repr(D)  # run_tajd.sh:192-194
-            print(f"{reg}\t{L_col[i]}\t{samples_col}\t{int(s_all[i])}\t{col['pi_site'][i]:.8f}\t{taj}", file=out)
+    write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels)
     if args.output or rank != 0:
         out.close()
     if world > 1:
