@@ -1293,6 +1293,8 @@ IMPOP_API int impop_afs(impop_ctx *ctx, const impop_matrix *m, const impop_windo
     if (chunks) chunks = (longest + chunk_sites - 1) / chunk_sites;
     if (chunks) {
         REQUIRE(chunks < 0x7FFFFFFFull, "impop_afs: window too long");
+        if ((size_t)bins * 4 > 48 * 1024)  // 12288 .. 16383 haplotypes in the mask: opt in like launch_af / launch_multi
+            HIP_TRY(hipFuncSetAttribute((const void *)afs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)bins * 4)));
         // windows ride on gridDim.y (<= 65535): any number of windows goes out in batches of that many
         for (uint64_t w0 = 0; w0 < n_windows; w0 += 65535) {
             const uint32_t nw = (uint32_t)std::min<uint64_t>(65535, n_windows - w0);

@@ -1169,13 +1169,26 @@ __global__ void af_adjacency_kernel(SimBatch batch, double threshold, uint32_t w
     for (uint32_t b = 0; b < 32; ++b) {
         const uint32_t j = 32 * w + b;
         if (j >= n) break;
-        const double v = sim_get(S, i, j);
-        if (v == v && v >= threshold) bits |= 1u << b;  // non-strict (af.py:38)
+        const double v = sim_get(S, i, j);  // the orientation above the diagonal
+        bool link = v == v && v >= threshold;  // non-strict (af.py:38)
+        if (!link && S.dense && i != j) {
+            // af.py:37 unions every ROW of the file, whichever way round it names the pair: a dense table that holds a
+            // pair only below the diagonal (NaN above) links it all the same
+            const double u = sim_get_raw(S, i > j ? i : j, i > j ? j : i);
+            link = u == u && u >= threshold;
+        }
+        if (link) bits |= 1u << b;
     }
     adj[t] = bits;
 }
 
-// dynamic LDS: label[n] | size[n] | rank[n]
+// dynamic LDS: label[n] | size[n] | rank[n] (+ 16 bytes of padding); static LDS: the two words `changed` and `K`.
+// The workgroup is given AF_LDS_BUDGET of the 160 KB a CDNA4 workgroup has; AF_MAX_N is the largest n that fits
+// (12798; include/impop_hip.h states the same number as IMPOP_CLUSTER_MAX_N).
+constexpr size_t AF_LDS_BUDGET = 150 * 1024, AF_STATIC_LDS = 2 * sizeof(uint32_t), AF_DYN_PAD = 16;
+constexpr uint32_t AF_MAX_N = (uint32_t)((AF_LDS_BUDGET - AF_STATIC_LDS - AF_DYN_PAD) / 12);
+static_assert(AF_MAX_N == IMPOP_CLUSTER_MAX_N, "the header documents the clustering limit");
+#define REQUIRE_AF_N(n) REQUIRE((n) <= AF_MAX_N, "af: %u samples exceed the LDS-resident clustering limit (%u)", (n), AF_MAX_N)
 __global__ __launch_bounds__(ST) void af_components_kernel(uint32_t n, uint32_t words, const uint32_t *__restrict__ adj,
                                                            uint32_t *__restrict__ cluster_of, uint32_t *__restrict__ sizes,
                                                            uint32_t *__restrict__ n_clusters) {
@@ -1199,8 +1212,8 @@ __global__ __launch_bounds__(ST) void af_components_kernel(uint32_t n, uint32_t 
                     bits &= bits - 1;
                     const uint32_t lj = label[j];
                     if (lj < m) m = lj;
-                    // symmetric relation: pull i's label into j as well (rows may be one-sided
-                    // when only one orientation of a pair is present in the table)
+                    // af_adjacency_kernel writes a symmetric relation (bit (i, j) == bit (j, i)), so j's own row would
+                    // pull this label too; pushing it from here as well only saves iterations
                     if (label[i] < lj) { atomicMin(&label[j], label[i]); changed = 1; }
                 }
             }
@@ -1399,8 +1412,8 @@ int launch_hud_grouped(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, c
 int launch_af(impop_ctx *ctx, const SimBatch &b, double threshold, uint32_t *d_adj, uint32_t *d_cluster_of,
               uint32_t *d_sizes, uint32_t *d_nclusters) {
     const uint32_t n = b.n, words = (n + 31) / 32;
-    const size_t lds = (size_t)n * 12 + 16;
-    REQUIRE(lds <= 150 * 1024, "af: %u samples exceed the LDS-resident clustering limit (12700)", n);
+    REQUIRE_AF_N(n);
+    const size_t lds = (size_t)n * 12 + AF_DYN_PAD;
     if (n) {
         const uint64_t total = (uint64_t)n * words;
         hipLaunchKernelGGL(af_adjacency_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, b,
@@ -1606,6 +1619,8 @@ IMPOP_API int impop_cluster_from_identity(impop_ctx *ctx, const double *ident, u
         if (n_clusters) *n_clusters = 0;
         return IMPOP_OK;
     }
+    // refused before anything is allocated, uploaded or launched (launch_af checks the same constant)
+    REQUIRE_AF_N(n);
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n * n;
     const uint32_t words = (n + 31) / 32;

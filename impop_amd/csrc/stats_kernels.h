@@ -132,13 +132,18 @@ __device__ __forceinline__ double sim_from_gram(const SimView &S, int64_t I, int
 }
 
 // identity of the unordered pair {i, j}; NaN = pair absent (pica2.py:85-87 keying)
+// entry (row, col) of a DENSE table as stored, rounded like the analysis (the one place the rounding rule of a dense view lives)
+__device__ __forceinline__ double sim_get_raw(const SimView &S, uint32_t row, uint32_t col) {
+    double v = S.dense[(uint64_t)row * S.ld + col];
+    if (S.round_digits >= 0 && v == v) v = py_round(v, S.round_digits);
+    return v;
+}
+// the pair {i, j} as the reference keys it, (smaller, larger) (pica2.py:86): of a dense table the entry above the diagonal
 __device__ __forceinline__ double sim_get(const SimView &S, uint32_t i, uint32_t j) {
     if (i > j) { const uint32_t t = i; i = j; j = t; }
     if (!S.dense)
         return sim_from_gram(S, gram_at(S, i, j), S.diag ? S.diag[i] : gram_at(S, i, i), S.diag ? S.diag[j] : gram_at(S, j, j));
-    double v = S.dense[(uint64_t)i * S.ld + j];
-    if (S.round_digits >= 0 && v == v) v = py_round(v, S.round_digits);
-    return v;
+    return sim_get_raw(S, i, j);
 }
 
 #ifdef __HIPCC__

@@ -169,7 +169,9 @@ int impop_matrix_free(impop_ctx *ctx, impop_matrix *m);
  * sim_ij = (W - H_ij)/W of the window's W sites, using the exact identities
  *   sum_{i<j in P} H_ij = sum_s c_P,s (n_P - c_P,s)
  *   sum_{i in A, j in B} H_ij = sum_s [c_A,s (n_B - c_B,s) + c_B,s (n_A - c_A,s)]
- * (SURVEY.md Appendix A.1), so one streaming pass over the bit matrix suffices. */
+ * (SURVEY.md Appendix A.1), so one streaming pass over the bit matrix suffices.
+ * n_hap <= 65535 for impop_scan_plan_create / impop_scan / impop_scan_multi / impop_scan_sharded (the per-site
+ * products c (n - c) stay below 2^32); a matrix of more haplotypes is refused with IMPOP_E_INVALID. */
 typedef struct impop_window {
     uint64_t site_begin;  /* first site of the window */
     uint64_t site_end;    /* one past the last site */
@@ -249,7 +251,8 @@ int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impop_window *
 
 /* Allele-frequency spectrum per window (scripts/wip/op-afs.py): out[w*(nP+1) + c] = number of
  * sites of window w at which exactly c haplotypes of `mask` (NULL = all; nP = its size) carry the
- * allele. */
+ * allele.  nP <= 16383 (the nP + 1 bins of a window are one workgroup's 64 KiB LDS histogram); a larger
+ * mask returns IMPOP_E_INVALID.  Any number of windows. */
 int impop_afs(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
               const uint64_t *mask, uint32_t *out_host);
 
@@ -394,7 +397,8 @@ int impop_pi_from_identity(impop_ctx *ctx, const double *ident, uint32_t n, doub
 /* The "Step 2" table of pica2's log (pica2.py:125-145) for given groups: rep[g] = index of group g's first
  * member, group_size[g]; for the pairs g < h in row-major order sims_out = identity of the two
  * representatives (rounded like the analysis; NaN = pair absent) and values_out = (1 - sim) * f_g * f_h.
- * Both arrays hold n_groups*(n_groups-1)/2 doubles. */
+ * Both arrays hold n_groups*(n_groups-1)/2 doubles.  n_groups < 2: there is no pair, nothing is written and the call
+ * returns IMPOP_OK.  A rep[g] >= n, or group sizes that sum to 0, return IMPOP_E_INVALID before anything is launched. */
 int impop_pica2_pair_terms(impop_ctx *ctx, const double *ident, uint32_t n, int round_digits, const uint32_t *rep,
                            const uint32_t *group_size, uint32_t n_groups, double *sims_out, double *values_out);
 
@@ -475,7 +479,12 @@ int impop_tajimas_d_from_pi_site(int64_t n, double S, double pi_site, double *D)
 
 /* af.cluster (af.py:35-44): connected components of {identity >= threshold}
  * ordered by (-size, members); cluster_of[i] = 0-based cluster rank (c1 = 0),
- * sizes (nullable): n entries, first n_clusters valid. */
+ * sizes (nullable): n entries, first n_clusters valid.
+ * i and j are linked when EITHER ident[i*n+j] or ident[j*n+i] is a number >= threshold: a table that holds only
+ * one orientation of a pair (NaN in the other) clusters like the symmetric one.
+ * n <= IMPOP_CLUSTER_MAX_N (the labels of all samples stay in the LDS of one workgroup); a larger n returns
+ * IMPOP_E_INVALID before anything is uploaded or launched. */
+#define IMPOP_CLUSTER_MAX_N 12798u
 int impop_cluster_from_identity(impop_ctx *ctx, const double *ident, uint32_t n, double threshold,
                                 uint32_t *cluster_of, uint32_t *n_clusters, uint32_t *sizes);
 

@@ -267,7 +267,7 @@ ORACLE_API int oracle_af_cluster(const double *sim, uint32_t n, double threshold
     uint32_t *p = (uint32_t *)malloc((size_t)(n ? n : 1) * sizeof(uint32_t));
     for (uint32_t i = 0; i < n; ++i) p[i] = i;
     for (uint32_t i = 0; i < n; ++i)
-        for (uint32_t j = i; j < n; ++j) {
+        for (uint32_t j = 0; j < n; ++j) { /* both triangles: either orientation of a pair links it */
             double v = sim[(size_t)i * n + j];
             if (!isnan(v) && v >= threshold) { /* af.py:38 non-strict */
                 uint32_t ra = uf_find(p, i), rb = uf_find(p, j);
