@@ -21,7 +21,7 @@ class ImpopError(RuntimeError):
         self.message = message
 
 
-ABI_VERSION = 3  # IMPOP_ABI_VERSION of include/impop_hip.h
+ABI_VERSION = 4  # IMPOP_ABI_VERSION of include/impop_hip.h
 E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED, E_INTERNAL = -1, -2, -3, -4, -5, -6
 KEEP_SITE_BLOCKED, KEEP_HAP_MAJOR, KEEP_DENSE_SCAN, KEEP_NO_RARE_SPLIT = 1, 2, 4, 8
 IDENTITY_MATCH, IDENTITY_DICE = 0, 1
@@ -68,6 +68,16 @@ class PairwiseStats(C.Structure):
                 ("n_sites", C.c_uint32), ("reserved", C.c_uint64)]
 
 
+class ClusterParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("identity_kind", C.c_int32), ("threshold", C.c_double),
+                ("round_digits", C.c_int32), ("reserved", C.c_uint32)]
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_clusters", C.c_uint32), ("largest", C.c_uint32), ("n_singletons", C.c_uint32),
+                ("sum_sq", C.c_uint64), ("n_sites", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -91,6 +101,7 @@ class IdentityBatchParams(C.Structure):
 
 assert C.sizeof(IdentityStats) == 144 and C.sizeof(IdentityProblem) == 64 and C.sizeof(IdentityBatchParams) == 32
 assert C.sizeof(WindowStats) == 128 and C.sizeof(Window) == 24 and C.sizeof(PairwiseStats) == 96
+assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -114,6 +125,7 @@ SIGNATURES = {
     "impop_debug_raise_device_error": (C.c_int, [_vp, C.c_uint32]),
     "impop_ctx_gram_timing": (C.c_int, [_vp, C.c_int]),
     "impop_ctx_gram_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "impop_ctx_cluster_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_matrix_synthetic_slab": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams), C.c_uint32, C.POINTER(_vp)]),
     "impop_matrix_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),
     "impop_matrix_info": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u32p]),
@@ -151,6 +163,8 @@ SIGNATURES = {
     "impop_pairwise_identity": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_int, _f64p]),
     "impop_pairwise_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, _u64p, _u64p,
                                       C.POINTER(PairwiseParams), C.POINTER(PairwiseStats)]),
+    "impop_cluster_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(ClusterParams),
+                                     C.POINTER(ClusterStats), _u32p, _u32p]),
     "impop_pi_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, C.c_double, C.c_int, C.c_uint64, _u32p, _f64p, _f64p, _u32p, _u32p,
                                          C.POINTER(Pica2Detail)]),
     "impop_pica2_pair_terms": (C.c_int, [_vp, _f64p, C.c_uint32, C.c_int, _u32p, _u32p, C.c_uint32, _f64p, _f64p]),

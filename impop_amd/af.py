@@ -47,6 +47,40 @@ def cluster(rows, samples, threshold, ctx=None):
     return comps
 
 
+def clusters_from_ranks(cluster_of, samples):
+    """One window's `cluster_of` row (BitMatrix.cluster_scan: 0-based cluster rank per member, clusters ranked by
+    (-size, smallest member index)) and the members' sample names -> what af.cluster returns: member lists ordered
+    by (-len, sorted members).  Names sort as strings while the kernel breaks ties by index, so clusters of equal
+    size are re-ordered by their sorted name lists here; members that share a sample name (names cut at ':') are one
+    sample, and their clusters one cluster (af.py:11-12 names the union-find's nodes by the cut name)."""
+    by_rank = {}
+    for s, r in zip(samples, cluster_of):
+        by_rank.setdefault(int(r), []).append(s)
+    comps = [sorted(set(members)) for _, members in sorted(by_rank.items())]
+    if len({s for c in comps for s in c}) != sum(len(c) for c in comps):  # a sample in two clusters: merge them
+        merged = []
+        for c in comps:
+            hit = [k for k in merged if not k.isdisjoint(c)]
+            for k in hit:
+                merged.remove(k)
+            merged.append(set(c).union(*hit))
+        comps = [sorted(k) for k in merged]
+    return sorted(comps, key=lambda c: (-len(c), c))
+
+
+def cluster_windows(matrix, windows, names, threshold=1.0, mask_p=None, kind="match", round_digits=None):
+    """af.cluster for every window straight from the resident bit matrix (impop_cluster_scan; no identity table
+    leaves the GPU).  names: one per haplotype of the matrix, in row order; mask_p (flags, optional) selects the
+    members.  -> per window the list af.cluster returns."""
+    names = [_sample_of(x) for x in names]
+    if len(names) != matrix.n_hap:
+        raise ValueError(f"{len(names)} names for a matrix of {matrix.n_hap} haplotypes")
+    _, cluster_of, _ = matrix.cluster_scan(windows, mask_p=mask_p, kind=kind, threshold=threshold, round_digits=round_digits)
+    keep = range(len(names)) if mask_p is None else np.flatnonzero(np.asarray(mask_p))
+    members = [names[i] for i in keep]
+    return [clusters_from_ranks(row, members) for row in cluster_of]
+
+
 def build_summary(clusters):
     """-> [(cluster id c1.., size, frequency, sorted members)] in the given order (af.py:46-54)"""
     sizes = [len(c) for c in clusters]

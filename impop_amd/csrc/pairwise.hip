@@ -893,67 +893,48 @@ IMPOP_API int impop_pairwise_identity(impop_ctx *ctx, const impop_matrix *m, uin
     return IMPOP_OK;
 }
 
-IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                                  const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
-                                  const impop_pairwise_params *params, impop_pairwise_stats *out_host) {
-    REQUIRE(ctx && m && params, "impop_pairwise_scan: NULL argument");
-    REQUIRE(params->struct_size == sizeof(impop_pairwise_params), "impop_pairwise_params.struct_size mismatch");
-    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE,
-            "impop_pairwise_scan: unknown identity kind");
-    REQUIRE(params->round_digits <= 19, "impop_pairwise_scan: round_digits > 19 unsupported");
-    REQUIRE(params->d_pi_mode >= 0 && params->d_pi_mode <= 2 && params->s_scope >= 0 && params->s_scope <= 2,
-            "impop_pairwise_scan: bad d_pi_mode / s_scope");
-    REQUIRE(params->fst_method <= 1, "impop_pairwise_scan: fst_method must be 0 (direct) or 1 (grouped)");
-    if (!n_windows) return IMPOP_OK;
-    REQUIRE(windows && out_host, "impop_pairwise_scan: NULL windows/out");
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, "impop_pairwise_scan");
-        if (rc) return rc;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
-    // integer S / W of the same windows from the streaming scan
-    impop_scan_params sp;
-    sp.struct_size = sizeof sp; sp.d_pi_mode = params->d_pi_mode; sp.s_scope = params->s_scope; sp.tile_blocks = 0;
+// ---- the shared front end of the windowed all-pairs calls (impop_pairwise_scan, impop_cluster_scan) -------------------
+// windows -> Gram cells (elementary segments where windows overlap) -> chunks that fit the scratch -> per chunk the Gram
+// launch (uint16 counts where they fit), the per-window tables and the filled SimBatch.  What a call does with the
+// identities — its epilogue kernels, its records — is the PairEpilogue it hands in.
+struct PairChunk {
+    SimBatch b;               // the chunk's problems: Gram counts, W, segments, the constant of a compacted matrix
+    uint64_t cnt;             // windows (= problems) of the chunk
+    const uint64_t *ord;      // problem k is window ord[k] of the caller's list
+    uint64_t *d_L;            // seq_len per problem
+    impop_window_stats *d_s;  // per problem: n_sites, and S / the scan's sums when the call asked for them
+    void *h_out;              // page-locked staging for the chunk's results (out_per_window bytes per problem)
+};
+struct PairEpilogue {
+    virtual ~PairEpilogue() {}
+    // once, before the first chunk: d_epi = the epilogue's own device region, sized for chunks of up to cap windows
+    virtual int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) = 0;
+    // enqueue the chunk's kernels and the copies of its results into c.h_out (the front end then checks the device error
+    // word and synchronises)
+    virtual int launch(impop_ctx *ctx, const PairChunk &c) = 0;
+    virtual void collect(const PairChunk &c) = 0;  // after the synchronisation: c.h_out -> the caller's arrays
+};
+struct PairFront {
+    const char *fn;
+    int identity_kind, round_digits;
+    const impop_window_stats *scan_host;  // nullable: the streaming scan's records of the same windows
+    bool use_segmap;                      // S of every window from the matrix's site bitmap (into d_s)
+    size_t epi_fixed, epi_per_window;     // device bytes of the epilogue: per call, per window of a chunk
+    size_t out_per_window;                // staged result bytes per window
+    uint64_t max_chunk_windows;           // 0 = no limit of the epilogue's own
+};
+static inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+static int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const PairFront &in,
+                          PairEpilogue &epi) {
+    const uint32_t ld = m->n_hap_pad, n = m->g.n_hap;
     // IMPOP_TRACE=1: host-side phase times of this call on stderr (where a call's time goes when the kernels are short)
     static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
     const auto t_enter = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
-        if (trace) fprintf(stderr, "[impop_pairwise_scan] %-22s +%.1f us\n", what,
+        if (trace) fprintf(stderr, "[%s] %-22s +%.1f us\n", in.fn, what,
                            std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enter).count());
     };
-    // s_scope 2: the caller does not need S / Tajima's D (pica2- or Fst-only output): skip the site scan
-    const bool want_s = params->s_scope != 2;
-    if (!want_s) sp.s_scope = 0;
-    // without a subset mask S comes from the matrix's cached site bitmap (s_p = s_all); with one, s_p needs the
-    // subset's own counts: the streaming scan of the same windows
-    const bool use_segmap = want_s && !mask_p;
-    impop_scan_plan *plan = nullptr;
-    int rc = (want_s && !use_segmap) ? impop_scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, &sp, &plan) : IMPOP_OK;
-    if (rc) return rc;
-    if (use_segmap) {
-        rc = ensure_segmap(ctx, m);
-        if (rc) return rc;
-    }
-    auto fail = [&](int code) {
-        if (plan) impop_scan_plan_destroy(plan);
-        return code;
-    };
-    // subset P index list and A/B flags
-    std::vector<uint32_t> idx;
-    std::vector<uint8_t> fa(n, 0), fb(n, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        const bool inP = mask_p ? ((mask_p[i >> 6] >> (i & 63)) & 1ull) : true;
-        if (inP) idx.push_back(i);
-        fa[i] = mask_a ? (uint8_t)((mask_a[i >> 6] >> (i & 63)) & 1ull) : 0;
-        fb[i] = mask_b ? (uint8_t)((mask_b[i >> 6] >> (i & 63)) & 1ull) : 0;
-    }
-    const uint32_t nP = (uint32_t)idx.size();
-    std::vector<uint32_t> ia, ib;  // hud.py grouped: members of A / B with the overlap removed from both
-    for (uint32_t i = 0; i < n && params->fst_method == 1; ++i) {
-        if (fa[i] && !fb[i]) ia.push_back(i);
-        if (fb[i] && !fa[i]) ib.push_back(i);
-    }
     // ---- Gram cells.  I_ij is additive over disjoint site ranges, so overlapping (sliding) windows share the
     // Gram matrices of the elementary segments between the sorted window boundaries: every site is
     // contracted once however many windows cover it, and a window is the sum of its consecutive segments
@@ -961,10 +942,9 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
     // windows themselves.
     // compacted matrix: the contraction runs over the KEPT (variable) sites of each window; the dropped all-ones
     // sites come back as a per-window constant (SimBatch.add), the dropped all-zero sites contribute nothing
-    lap("masks");
     std::vector<impop_window> mw;
-    rc = map_windows_device(ctx, m, windows, n_windows, mw);
-    if (rc) return fail(rc);
+    int rc = map_windows_device(ctx, m, windows, n_windows, mw);
+    if (rc) return rc;
     lap("map_windows");
     struct Cell { uint64_t b, e; };
     std::vector<Cell> cells;                                // all Gram cells, in site order when segmented
@@ -973,6 +953,7 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
     for (uint64_t i = 0; i < n_windows; ++i) ord[i] = i;
     // the usual window list — a BED tiling: sorted, no two windows overlapping — has nothing to share: its cells are the windows
     // (one O(n) check instead of the sort + searches below, 0.15 ms of host time per 4096 windows while the GPU waits)
+    bool segmented = false;  // cells are elementary segments shared by windows (else: cell k is window k)
     bool tiling = n_windows < 0xFFFFFFF0ull;
     for (uint64_t i = 1; i < n_windows && tiling; ++i) tiling = mw[i].site_begin >= mw[i - 1].site_end && mw[i].site_end >= mw[i].site_begin;
     if (tiling) {
@@ -1015,6 +996,7 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
         if (!cuts.empty()) seg_before[cuts.size() - 1] = (uint32_t)segs.size();
         if (seg_sites * 20 < win_sites * 19 && segs.size() < 0xFFFFFFF0ull) {  // >= 5 % of the contraction is shared
             cells.swap(segs);
+            segmented = true;
             for (uint64_t i = 0; i < n_windows; ++i)
                 if (mw[i].site_end > mw[i].site_begin) {
                     first[i] = seg_before[at(mw[i].site_begin)];
@@ -1025,10 +1007,7 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
                 return ea != eb ? eb : (!ea && first[a] < first[b]);
             });
         } else {
-            if (n_windows >= 0xFFFFFFF0ull) {
-                set_error("impop_pairwise_scan: too many windows");
-                return fail(IMPOP_E_INVALID);
-            }
+            REQUIRE(n_windows < 0xFFFFFFF0ull, "%s: too many windows", in.fn);
             cells.resize(n_windows);
             for (uint64_t i = 0; i < n_windows; ++i) {
                 cells[i] = {mw[i].site_begin, mw[i].site_end};
@@ -1045,54 +1024,39 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
     if (cap > 8192) cap = 8192;
     cap = std::min<uint64_t>(cap, std::max<uint64_t>(cells.size(), n_windows));  // a short call stages (and copies) short tables
     if (cap < 1) cap = 1;
-    void *d = nullptr;
-    const size_t need = 4096 + cap * (gram_bytes + sizeof(GramWindow) + 24 + sizeof(Pica2Out) + sizeof(HfstOut) +
-                                      sizeof(impop_window_stats) + sizeof(impop_pairwise_stats) + 2 * sizeof(GramWindow) + 4 + 3584) + 16 * 256 +
-                        (size_t)n * 16 + 8192;
-    rc = ctx_scratch(ctx, need, &d);
-    if (rc) return fail(rc);
-    Carve2 cv(d);
-    int32_t *d_g = cv.take<int32_t>(cap * (size_t)ld * ld);
+    // windows per chunk: the Gram capacity, what the epilogue's own buffers allow, and the test switch IMPOP_PAIRWISE_CHUNK
+    // (windows per chunk: forces several chunks on lists far too short to need them; records must not change)
+    uint64_t win_cap = cap;
+    if (in.max_chunk_windows) win_cap = std::min<uint64_t>(win_cap, std::max<uint64_t>(in.max_chunk_windows, 1));
+    static const uint64_t chunk_env = [] { const char *e = getenv("IMPOP_PAIRWISE_CHUNK"); return e ? strtoull(e, nullptr, 10) : 0ull; }();
+    if (chunk_env) win_cap = std::min<uint64_t>(win_cap, chunk_env);
+    // one cell per window: a chunk never holds more Gram matrices than windows, so the Gram and table scratch is sized for that
+    // (an epilogue that allows ~100 windows per chunk would otherwise reserve room for 8192 matrices it can never fill)
+    if (!segmented) cap = std::min<uint64_t>(cap, win_cap);
     // per-chunk metadata: ONE contiguous region mirrored on the host, so that a chunk costs one host-to-device copy
     // (eight small pageable copies were ~0.3 ms of host time between two Gram launches)
-    auto up256 = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t o_w = 0, o_W = o_w + up256(cap * sizeof(GramWindow)), o_L = o_W + up256(cap * 8), o_first = o_L + up256(cap * 8),
                  o_count = o_first + up256(cap * 4), o_s = o_count + up256(cap * 4), o_sw = o_s + up256(cap * sizeof(impop_window_stats)),
                  o_ow = o_sw + up256(cap * sizeof(GramWindow)), meta_bytes = o_ow + up256(cap * sizeof(GramWindow));
+    const size_t epi_bytes = in.epi_fixed + win_cap * in.epi_per_window;
+    void *d = nullptr;
+    rc = ctx_scratch(ctx, 4096 + up256(cap * gram_bytes) + up256(meta_bytes) + up256(cap * 4) + up256(epi_bytes) + 1024, &d);
+    if (rc) return rc;
+    Carve2 cv(d);
+    int32_t *d_g = cv.take<int32_t>(cap * (size_t)ld * ld);
     char *d_meta = cv.take<char>(meta_bytes);
     GramWindow *d_w = reinterpret_cast<GramWindow *>(d_meta + o_w);
     uint64_t *d_W = reinterpret_cast<uint64_t *>(d_meta + o_W);
     uint64_t *d_L = reinterpret_cast<uint64_t *>(d_meta + o_L);
     uint32_t *d_first = reinterpret_cast<uint32_t *>(d_meta + o_first);
     uint32_t *d_count = reinterpret_cast<uint32_t *>(d_meta + o_count);
-    Pica2Out *d_p = cv.take<Pica2Out>(cap);
-    HfstOut *d_h = cv.take<HfstOut>(cap);
     impop_window_stats *d_s = reinterpret_cast<impop_window_stats *>(d_meta + o_s);
-    impop_pairwise_stats *d_o = cv.take<impop_pairwise_stats>(cap);
     GramWindow *d_sw = reinterpret_cast<GramWindow *>(d_meta + o_sw);  // the chunk's WINDOWS (d_w holds its Gram cells), matrix coordinates
     GramWindow *d_ow = reinterpret_cast<GramWindow *>(d_meta + o_ow);  // the same windows in ORIGINAL coordinates (compacted matrices)
     uint32_t *d_add = cv.take<uint32_t>(cap);     // compacted: dropped all-ones sites per window
-    uint32_t *d_idx = cv.take<uint32_t>(n ? n : 1);
-    uint8_t *d_fa = cv.take<uint8_t>(n ? n : 1);
-    uint8_t *d_fb = cv.take<uint8_t>(n ? n : 1);
-    uint32_t *d_ia = cv.take<uint32_t>(n ? n : 1);
-    uint32_t *d_ib = cv.take<uint32_t>(n ? n : 1);
-    hipError_t e;
-#define PW_TRY(expr) \
-    if ((e = (expr)) != hipSuccess) return fail(hip_fail(e, #expr, __FILE__, __LINE__))
-    if (nP) PW_TRY(hipMemcpyAsync(d_idx, idx.data(), (size_t)nP * 4, hipMemcpyHostToDevice, ctx->stream));
-    PW_TRY(hipMemcpyAsync(d_fa, fa.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    PW_TRY(hipMemcpyAsync(d_fb, fb.data(), n, hipMemcpyHostToDevice, ctx->stream));
-    if (!ia.empty()) PW_TRY(hipMemcpyAsync(d_ia, ia.data(), ia.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (!ib.empty()) PW_TRY(hipMemcpyAsync(d_ib, ib.data(), ib.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    std::vector<impop_window_stats> scan_host;  // only with a scan plan; else the records are n_sites and zeros (S: the device fills it in)
-    if (plan) {
-        scan_host.resize(n_windows);
-        rc = impop_scan_plan_launch(plan, nullptr);
-        if (rc) return fail(rc);
-        rc = impop_scan_plan_fetch(plan, scan_host.data());
-        if (rc) return fail(rc);
-    }
+    void *d_epi = cv.take<char>(epi_bytes ? epi_bytes : 1);
+    rc = epi.prepare(ctx, d_epi, win_cap);
+    if (rc) return rc;
     // even out the chunks: a total slightly above the capacity would otherwise leave a last chunk of a few
     // windows whose single-workgroup epilogue kernels cost their full latency
     uint64_t cell_limit = cap;
@@ -1103,12 +1067,12 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
         if ((cells.size() + n_chunks - 1) / n_chunks + widest > cap) ++n_chunks;  // neighbours re-contract up to `widest` cells
         cell_limit = std::min<uint64_t>(cap, (cells.size() + n_chunks - 1) / n_chunks + widest);
     }
-    lap("scratch + scan_host");
-    // page-locked staging for the metadata going up and the records coming down (ctx_pinned)
+    lap("scratch");
+    // page-locked staging for the metadata going up and the results coming down (ctx_pinned)
     const size_t out_off = up256(meta_bytes);
     void *pin = nullptr;
-    rc = ctx_pinned(ctx, out_off + cap * sizeof(impop_pairwise_stats), &pin);
-    if (rc) return fail(rc);
+    rc = ctx_pinned(ctx, out_off + win_cap * in.out_per_window, &pin);
+    if (rc) return rc;
     char *hmeta = reinterpret_cast<char *>(pin);
     memset(hmeta, 0, meta_bytes);
     GramWindow *gw = reinterpret_cast<GramWindow *>(hmeta + o_w), *swv = reinterpret_cast<GramWindow *>(hmeta + o_sw),
@@ -1116,7 +1080,6 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
     uint64_t *Wv = reinterpret_cast<uint64_t *>(hmeta + o_W), *Lv = reinterpret_cast<uint64_t *>(hmeta + o_L);
     uint32_t *fv = reinterpret_cast<uint32_t *>(hmeta + o_first), *cvv = reinterpret_cast<uint32_t *>(hmeta + o_count);
     impop_window_stats *sv = reinterpret_cast<impop_window_stats *>(hmeta + o_s);
-    impop_pairwise_stats *ov = reinterpret_cast<impop_pairwise_stats *>(hmeta + out_off);
     std::vector<uint32_t> add_h;
     uint64_t call_max_W = 0;  // bounds every Gram count of the call (a cell is a window or a piece of one; compacted: + its constant)
     for (uint64_t i = 0; i < n_windows; ++i) call_max_W = std::max(call_max_W, window_W(m, windows[i].site_begin, windows[i].site_end));
@@ -1126,17 +1089,14 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
         uint64_t cnt = 0;
         uint32_t c_lo = 0, c_hi = 0;
         bool have = false;
-        while (base + cnt < n_windows && cnt < cell_limit) {
+        while (base + cnt < n_windows && cnt < cell_limit && cnt < win_cap) {
             const uint64_t wdx = ord[base + cnt];
             if (count[wdx]) {
                 const uint32_t lo = have ? std::min(c_lo, first[wdx]) : first[wdx];
                 const uint32_t hi = have ? std::max(c_hi, first[wdx] + count[wdx]) : first[wdx] + count[wdx];
                 if ((uint64_t)(hi - lo) > (cnt == 0 ? cap : cell_limit)) {
-                    if (cnt == 0) {
-                        set_error("impop_pairwise_scan: window %llu spans %u segments, more than the %llu Gram matrices that fit "
-                                  "the scratch", (unsigned long long)wdx, count[wdx], (unsigned long long)cap);
-                        return fail(IMPOP_E_INVALID);
-                    }
+                    REQUIRE(cnt != 0, "%s: window %llu spans %u segments, more than the %llu Gram matrices that fit the scratch", in.fn,
+                            (unsigned long long)wdx, count[wdx], (unsigned long long)cap);
                     break;
                 }
                 c_lo = lo; c_hi = hi; have = true;
@@ -1151,17 +1111,17 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
         }
         // the Gram launch needs the cells alone: they go up first and the kernel starts, the per-window tables are filled in (and
         // copied) while it runs
-        if (n_cells) PW_TRY(hipMemcpyAsync(d_meta + o_w, hmeta + o_w, (size_t)n_cells * sizeof(GramWindow), hipMemcpyHostToDevice, ctx->stream));
+        if (n_cells) HIP_TRY(hipMemcpyAsync(d_meta + o_w, hmeta + o_w, (size_t)n_cells * sizeof(GramWindow), hipMemcpyHostToDevice, ctx->stream));
         if (n_cells) {
             hipEvent_t ev1 = nullptr;
             if (ctx->gram_timing) {  // impop_ctx_gram_timing: the Gram launch(es) of this chunk between two events
                 if (ctx->gram_events_used == ctx->gram_events.size()) {
                     hipEvent_t a, b;
-                    PW_TRY(hipEventCreate(&a));
-                    PW_TRY(hipEventCreate(&b));
+                    HIP_TRY(hipEventCreate(&a));
+                    HIP_TRY(hipEventCreate(&b));
                     ctx->gram_events.push_back({a, b});
                 }
-                PW_TRY(hipEventRecord(ctx->gram_events[ctx->gram_events_used].first, ctx->stream));
+                HIP_TRY(hipEventRecord(ctx->gram_events[ctx->gram_events_used].first, ctx->stream));
                 ev1 = ctx->gram_events[ctx->gram_events_used].second;
                 ctx->gram_events_used++;
             }
@@ -1169,11 +1129,11 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
             static const bool u16_off = [] { const char *e = getenv("IMPOP_GRAM_U16"); return e && e[0] == '0'; }();
             g16 = !u16_off && call_max_W < 65536;
             rc = launch_gram_any(ctx, m, d_w, gw, n_cells, d_g, max_sites, &g16);
-            if (rc) return fail(rc);
-            if (ev1) PW_TRY(hipEventRecord(ev1, ctx->stream));
-            if (params->identity_kind != IMPOP_IDENTITY_MATCH) {  // `match` sees Hamming distances only: polarity-invariant
+            if (rc) return rc;
+            if (ev1) HIP_TRY(hipEventRecord(ev1, ctx->stream));
+            if (in.identity_kind != IMPOP_IDENTITY_MATCH) {  // `match` sees Hamming distances only: polarity-invariant
                 rc = launch_gram_unflip(ctx, m, d_g, n_cells, g16);
-                if (rc) return fail(rc);
+                if (rc) return rc;
             }
         }
         for (uint64_t k = 0; k < cnt; ++k) {
@@ -1182,7 +1142,7 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
             Lv[k] = windows[wdx].seq_len;
             fv[k] = count[wdx] ? first[wdx] - c_lo : 0;
             cvv[k] = count[wdx];
-            if (plan) sv[k] = scan_host[wdx];
+            if (in.scan_host) sv[k] = in.scan_host[wdx];
             else { memset(&sv[k], 0, sizeof(sv[k])); sv[k].n_sites = (uint32_t)Wv[k]; }
             swv[k] = {mw[wdx].site_begin, mw[wdx].site_end};
             owv[k] = {windows[wdx].site_begin, windows[wdx].site_end};
@@ -1191,69 +1151,301 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
         bool one_to_one = true;
         for (uint64_t k = 0; k < cnt && one_to_one; ++k) one_to_one = cvv[k] == 1 && fv[k] == k;
         lap("chunk metadata");
-        PW_TRY(hipMemcpyAsync(d_meta + o_W, hmeta + o_W, meta_bytes - o_W, hipMemcpyHostToDevice, ctx->stream));
-        if (use_segmap) {
+        HIP_TRY(hipMemcpyAsync(d_meta + o_W, hmeta + o_W, meta_bytes - o_W, hipMemcpyHostToDevice, ctx->stream));
+        if (in.use_segmap) {
             hipLaunchKernelGGL(seg_count_kernel, dim3((uint32_t)((cnt + 3) / 4)), dim3(256), 0, ctx->stream, m->d_segmap, d_sw, cnt, d_s,
                                (uint32_t *)nullptr);
-            PW_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
-        SimBatch b{};
-        b.gram = d_g; b.stride = (uint64_t)ld * ld; b.ld = ld; b.n = n; b.W = d_W; b.kind = params->identity_kind;
+        PairChunk ch{};
+        SimBatch &b = ch.b;
+        b.gram = d_g; b.stride = (uint64_t)ld * ld; b.ld = ld; b.n = n; b.W = d_W; b.kind = in.identity_kind;
         b.g16 = g16 ? 1u : 0u;
         b.max_W = call_max_W;
-        b.round_digits = params->round_digits < 0 ? -1 : params->round_digits;
+        b.round_digits = in.round_digits < 0 ? -1 : in.round_digits;
         b.seg_first = one_to_one ? nullptr : d_first; b.seg_count = one_to_one ? nullptr : d_count;
         if (compact_weighted(m)) {  // the dropped all-ones sites' summed weights, from the host prefix sums
             add_h.resize(cnt);
             for (uint64_t k = 0; k < cnt; ++k) add_h[k] = ones_weight(m, windows[ord[base + k]].site_begin, windows[ord[base + k]].site_end);
-            PW_TRY(hipMemcpyAsync(d_add, add_h.data(), cnt * 4, hipMemcpyHostToDevice, ctx->stream));
+            HIP_TRY(hipMemcpyAsync(d_add, add_h.data(), cnt * 4, hipMemcpyHostToDevice, ctx->stream));
             b.add = d_add;
         } else if (m->compact) {    // ... their count, from the bitmap on the device
             hipLaunchKernelGGL(seg_count_kernel, dim3((uint32_t)((cnt + 3) / 4)), dim3(256), 0, ctx->stream, m->d_onesmap, d_ow, cnt,
                                (impop_window_stats *)nullptr, d_add);
-            PW_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
             b.add = d_add;
         }
-        // pica2 grouping and the Fst sums are independent, latency-bound one-workgroup-per-window kernels: pica2 goes
-        // to the side stream (fork behind the Gram launch, join before the finalize) so the two overlap
-        if (!ctx->side) {
-            PW_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-            PW_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            PW_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        PW_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-        PW_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->side;
-        rc = launch_pica2(ctx, b, cnt, mask_p ? d_idx : nullptr, nP, nullptr, params->threshold, d_L, d_p, nullptr);
-        ctx->stream = main_stream;
-        if (rc) return fail(rc);
-        PW_TRY(hipEventRecord(ctx->ev_join, ctx->side));
-        if (params->fst_method == 1)
-            rc = launch_hud_grouped(ctx, b, cnt, d_ia, (uint32_t)ia.size(), d_ib, (uint32_t)ib.size(), nullptr, nullptr, params->threshold,
-                                        d_L, d_h);
-        else
-            rc = launch_hfst(ctx, b, cnt, d_fa, d_fb, d_L, d_h);
-        if (rc) return fail(rc);
-        PW_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        PairFinalIn in{d_p, d_h, d_s};
-        rc = ensure_tajima_consts(ctx, nP >= 2 ? (int64_t)nP : 2);  // the cache may have been retargeted by another plan
-        if (rc) return fail(rc);
-        hipLaunchKernelGGL(pairwise_finalize_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, ctx->stream, in, cnt,
-                           want_s ? nP : 0u, params->d_pi_mode, want_s ? params->s_scope : 0, ctx->d_taj, d_o);
-        PW_TRY(hipGetLastError());
+        ch.cnt = cnt; ch.ord = ord.data() + base; ch.d_L = d_L; ch.d_s = d_s; ch.h_out = hmeta + out_off;
+        rc = epi.launch(ctx, ch);
+        if (rc) return rc;
         lap("chunk launched");
-        PW_TRY(hipMemcpyAsync(ov, d_o, cnt * sizeof(impop_pairwise_stats), hipMemcpyDeviceToHost, ctx->stream));
         rc = ctx_err_fetch(ctx);
-        if (rc) return fail(rc);
-        PW_TRY(hipStreamSynchronize(ctx->stream));  // the staging vectors are reused by the next chunk
-        rc = ctx_err_result(ctx, "impop_pairwise_scan");  // a device-side consistency check tripped: no partial results
-        if (rc) return fail(rc);
-        for (uint64_t k = 0; k < cnt; ++k) out_host[ord[base + k]] = ov[k];
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging vectors are reused by the next chunk
+        rc = ctx_err_result(ctx, in.fn);  // a device-side consistency check tripped: no partial results
+        if (rc) return rc;
+        epi.collect(ch);
         base += cnt;
         lap("chunk done");
     }
-#undef PW_TRY
-    if (plan) impop_scan_plan_destroy(plan);
     return IMPOP_OK;
+}
+
+namespace {
+// impop_pairwise_scan's epilogue: pica2 grouping next to the Fst sums, then the fixed records
+struct PairwiseStatsEpilogue final : PairEpilogue {
+    const impop_pairwise_params *params;
+    const uint64_t *mask_p;
+    uint32_t n, nP;
+    bool want_s;
+    const std::vector<uint32_t> *idx, *ia, *ib;
+    const std::vector<uint8_t> *fa, *fb;
+    impop_pairwise_stats *out_host;
+    Pica2Out *d_p = nullptr;
+    HfstOut *d_h = nullptr;
+    impop_pairwise_stats *d_o = nullptr;
+    uint32_t *d_idx = nullptr, *d_ia = nullptr, *d_ib = nullptr;
+    uint8_t *d_fa = nullptr, *d_fb = nullptr;
+    static size_t fixed_bytes(uint32_t n) { return 3 * up256((size_t)(n ? n : 1) * 4) + 2 * up256(n ? n : 1) + 256; }
+    static size_t window_bytes() { return sizeof(Pica2Out) + sizeof(HfstOut) + sizeof(impop_pairwise_stats); }
+    int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) override {
+        Carve2 cv(d_epi);
+        d_idx = cv.take<uint32_t>(n ? n : 1);
+        d_ia = cv.take<uint32_t>(n ? n : 1);
+        d_ib = cv.take<uint32_t>(n ? n : 1);
+        d_fa = cv.take<uint8_t>(n ? n : 1);
+        d_fb = cv.take<uint8_t>(n ? n : 1);
+        char *w = cv.take<char>(cap * window_bytes());
+        d_h = reinterpret_cast<HfstOut *>(w);
+        d_o = reinterpret_cast<impop_pairwise_stats *>(w + cap * sizeof(HfstOut));
+        d_p = reinterpret_cast<Pica2Out *>(w + cap * (sizeof(HfstOut) + sizeof(impop_pairwise_stats)));
+        if (nP) HIP_TRY(hipMemcpyAsync(d_idx, idx->data(), (size_t)nP * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_fa, fa->data(), n, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_fb, fb->data(), n, hipMemcpyHostToDevice, ctx->stream));
+        if (!ia->empty()) HIP_TRY(hipMemcpyAsync(d_ia, ia->data(), ia->size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!ib->empty()) HIP_TRY(hipMemcpyAsync(d_ib, ib->data(), ib->size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const SimBatch &b = c.b;
+        const uint64_t cnt = c.cnt;
+        // pica2 grouping and the Fst sums are independent, latency-bound one-workgroup-per-window kernels: pica2 goes
+        // to the side stream (fork behind the Gram launch, join before the finalize) so the two overlap
+        if (!ctx->side) {
+            HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        hipStream_t main_stream = ctx->stream;
+        ctx->stream = ctx->side;
+        int rc = launch_pica2(ctx, b, cnt, mask_p ? d_idx : nullptr, nP, nullptr, params->threshold, c.d_L, d_p, nullptr);
+        ctx->stream = main_stream;
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->side));
+        if (params->fst_method == 1)
+            rc = launch_hud_grouped(ctx, b, cnt, d_ia, (uint32_t)ia->size(), d_ib, (uint32_t)ib->size(), nullptr, nullptr, params->threshold,
+                                    c.d_L, d_h);
+        else
+            rc = launch_hfst(ctx, b, cnt, d_fa, d_fb, c.d_L, d_h);
+        if (rc) return rc;
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        PairFinalIn in{d_p, d_h, c.d_s};
+        rc = ensure_tajima_consts(ctx, nP >= 2 ? (int64_t)nP : 2);  // the cache may have been retargeted by another plan
+        if (rc) return rc;
+        hipLaunchKernelGGL(pairwise_finalize_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, ctx->stream, in, cnt,
+                           want_s ? nP : 0u, params->d_pi_mode, want_s ? params->s_scope : 0, ctx->d_taj, d_o);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(c.h_out, d_o, cnt * sizeof(impop_pairwise_stats), hipMemcpyDeviceToHost, ctx->stream));
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        const impop_pairwise_stats *ov = reinterpret_cast<const impop_pairwise_stats *>(c.h_out);
+        for (uint64_t k = 0; k < c.cnt; ++k) out_host[c.ord[k]] = ov[k];
+    }
+};
+
+// impop_cluster_scan's epilogue: one clustering launch (stats_kernels.h launch_af_batch), records and member tables
+struct ClusterEpilogue final : PairEpilogue {
+    const impop_cluster_params *params;
+    const uint64_t *mask_p;
+    uint32_t nP;
+    const std::vector<uint32_t> *idx;
+    impop_cluster_stats *out_host;
+    uint32_t *cluster_of, *sizes;
+    size_t adj_bytes = 0;  // per window: the general form's adjacency rows (0 when the call is sure to take the window-shape kernel)
+    impop_cluster_stats *d_rec = nullptr;
+    uint32_t *d_idx = nullptr, *d_cl = nullptr, *d_sz = nullptr, *d_adj = nullptr;
+    size_t members_bytes() const { return (size_t)nP * 4; }
+    bool want_members() const { return cluster_of || sizes; }
+    static size_t fixed_bytes(uint32_t nP) { return up256((size_t)(nP ? nP : 1) * 4) + 4 * 256; }
+    // the window-shape kernel writes tables only when asked; the general form always writes both (sizes is its ranking's output)
+    size_t tables_bytes() const { return (adj_bytes == 0 && !want_members()) ? 0 : 2 * members_bytes(); }
+    size_t window_bytes() const { return sizeof(impop_cluster_stats) + tables_bytes() + adj_bytes; }
+    int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) override {
+        Carve2 cv(d_epi);
+        d_idx = cv.take<uint32_t>(nP ? nP : 1);
+        d_rec = cv.take<impop_cluster_stats>(cap);
+        // (together with the three alignment gaps below: fixed_bytes' 4 x 256)
+        char *w = cv.take<char>(cap * (tables_bytes() + adj_bytes) + 1);
+        d_cl = reinterpret_cast<uint32_t *>(w);
+        d_sz = reinterpret_cast<uint32_t *>(w + cap * (tables_bytes() / 2));
+        d_adj = reinterpret_cast<uint32_t *>(w + cap * tables_bytes());
+        if (nP) HIP_TRY(hipMemcpyAsync(d_idx, idx->data(), (size_t)nP * 4, hipMemcpyHostToDevice, ctx->stream));
+        return IMPOP_OK;
+    }
+    // staged per chunk: cnt records | cnt x nP cluster_of | cnt x nP sizes (the tables only when asked for)
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const uint64_t cnt = c.cnt;
+        hipEvent_t ev1 = nullptr;
+        if (ctx->gram_timing) {  // the clustering kernel(s) between two events of their own: impop_ctx_cluster_elapsed
+            if (ctx->cluster_events_used == ctx->cluster_events.size()) {
+                hipEvent_t a, b;
+                HIP_TRY(hipEventCreate(&a));
+                HIP_TRY(hipEventCreate(&b));
+                ctx->cluster_events.push_back({a, b});
+            }
+            HIP_TRY(hipEventRecord(ctx->cluster_events[ctx->cluster_events_used].first, ctx->stream));
+            ev1 = ctx->cluster_events[ctx->cluster_events_used].second;
+        }
+        int rc = launch_af_batch(ctx, c.b, cnt, mask_p ? d_idx : nullptr, nP, params->threshold, d_adj, adj_bytes, d_rec, d_cl, d_sz, want_members());
+        if (rc) return rc;
+        if (ev1) {
+            HIP_TRY(hipEventRecord(ev1, ctx->stream));
+            ctx->cluster_events_used++;
+        }
+        char *h = reinterpret_cast<char *>(c.h_out);
+        HIP_TRY(hipMemcpyAsync(h, d_rec, cnt * sizeof(impop_cluster_stats), hipMemcpyDeviceToHost, ctx->stream));
+        if (want_members() && nP) {
+            h += cnt * sizeof(impop_cluster_stats);
+            if (cluster_of) HIP_TRY(hipMemcpyAsync(h, d_cl, cnt * members_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+            if (sizes) HIP_TRY(hipMemcpyAsync(h + cnt * members_bytes(), d_sz, cnt * members_bytes(), hipMemcpyDeviceToHost, ctx->stream));
+        }
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        const char *h = reinterpret_cast<const char *>(c.h_out);
+        const impop_cluster_stats *rv = reinterpret_cast<const impop_cluster_stats *>(h);
+        const char *hc = h + c.cnt * sizeof(impop_cluster_stats), *hs = hc + c.cnt * members_bytes();
+        for (uint64_t k = 0; k < c.cnt; ++k) {
+            out_host[c.ord[k]] = rv[k];
+            if (cluster_of && nP) memcpy(cluster_of + c.ord[k] * nP, hc + k * members_bytes(), members_bytes());
+            if (sizes && nP) memcpy(sizes + c.ord[k] * nP, hs + k * members_bytes(), members_bytes());
+        }
+    }
+};
+}  // namespace
+
+IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                  const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
+                                  const impop_pairwise_params *params, impop_pairwise_stats *out_host) {
+    REQUIRE(ctx && m && params, "impop_pairwise_scan: NULL argument");
+    REQUIRE(params->struct_size == sizeof(impop_pairwise_params), "impop_pairwise_params.struct_size mismatch");
+    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE,
+            "impop_pairwise_scan: unknown identity kind");
+    REQUIRE(params->round_digits <= 19, "impop_pairwise_scan: round_digits > 19 unsupported");
+    REQUIRE(params->d_pi_mode >= 0 && params->d_pi_mode <= 2 && params->s_scope >= 0 && params->s_scope <= 2,
+            "impop_pairwise_scan: bad d_pi_mode / s_scope");
+    REQUIRE(params->fst_method <= 1, "impop_pairwise_scan: fst_method must be 0 (direct) or 1 (grouped)");
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_host, "impop_pairwise_scan: NULL windows/out");
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, "impop_pairwise_scan");
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint32_t n = m->g.n_hap;
+    // integer S / W of the same windows from the streaming scan
+    impop_scan_params sp;
+    sp.struct_size = sizeof sp; sp.d_pi_mode = params->d_pi_mode; sp.s_scope = params->s_scope; sp.tile_blocks = 0;
+    // s_scope 2: the caller does not need S / Tajima's D (pica2- or Fst-only output): skip the site scan
+    const bool want_s = params->s_scope != 2;
+    if (!want_s) sp.s_scope = 0;
+    // without a subset mask S comes from the matrix's cached site bitmap (s_p = s_all); with one, s_p needs the
+    // subset's own counts: the streaming scan of the same windows
+    const bool use_segmap = want_s && !mask_p;
+    impop_scan_plan *plan = nullptr;
+    int rc = (want_s && !use_segmap) ? impop_scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, &sp, &plan) : IMPOP_OK;
+    if (rc) return rc;
+    auto fail = [&](int code) {
+        if (plan) impop_scan_plan_destroy(plan);
+        return code;
+    };
+    if (use_segmap) {
+        rc = ensure_segmap(ctx, m);
+        if (rc) return fail(rc);
+    }
+    // subset P index list and A/B flags
+    std::vector<uint32_t> idx;
+    std::vector<uint8_t> fa(n, 0), fb(n, 0);
+    for (uint32_t i = 0; i < n; ++i) {
+        const bool inP = mask_p ? ((mask_p[i >> 6] >> (i & 63)) & 1ull) : true;
+        if (inP) idx.push_back(i);
+        fa[i] = mask_a ? (uint8_t)((mask_a[i >> 6] >> (i & 63)) & 1ull) : 0;
+        fb[i] = mask_b ? (uint8_t)((mask_b[i >> 6] >> (i & 63)) & 1ull) : 0;
+    }
+    const uint32_t nP = (uint32_t)idx.size();
+    std::vector<uint32_t> ia, ib;  // hud.py grouped: members of A / B with the overlap removed from both
+    for (uint32_t i = 0; i < n && params->fst_method == 1; ++i) {
+        if (fa[i] && !fb[i]) ia.push_back(i);
+        if (fb[i] && !fa[i]) ib.push_back(i);
+    }
+    std::vector<impop_window_stats> scan_host;  // only with a scan plan; else the records are n_sites and zeros (S: the device fills it in)
+    if (plan) {
+        scan_host.resize(n_windows);
+        rc = impop_scan_plan_launch(plan, nullptr);
+        if (rc) return fail(rc);
+        rc = impop_scan_plan_fetch(plan, scan_host.data());
+        if (rc) return fail(rc);
+    }
+    PairwiseStatsEpilogue epi;
+    epi.params = params; epi.mask_p = mask_p; epi.n = n; epi.nP = nP; epi.want_s = want_s;
+    epi.idx = &idx; epi.ia = &ia; epi.ib = &ib; epi.fa = &fa; epi.fb = &fb; epi.out_host = out_host;
+    PairFront in{};
+    in.fn = "impop_pairwise_scan"; in.identity_kind = params->identity_kind; in.round_digits = params->round_digits;
+    in.scan_host = plan ? scan_host.data() : nullptr; in.use_segmap = use_segmap;
+    in.epi_fixed = PairwiseStatsEpilogue::fixed_bytes(n); in.epi_per_window = PairwiseStatsEpilogue::window_bytes();
+    in.out_per_window = sizeof(impop_pairwise_stats);
+    return fail(pairwise_front(ctx, m, windows, n_windows, in, epi));
+}
+
+IMPOP_API int impop_cluster_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                 const uint64_t *mask_p, const impop_cluster_params *params, impop_cluster_stats *out_host,
+                                 uint32_t *cluster_of, uint32_t *sizes) {
+    REQUIRE(ctx && m && params, "impop_cluster_scan: NULL argument");
+    REQUIRE(params->struct_size == sizeof(impop_cluster_params), "impop_cluster_params.struct_size mismatch");
+    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE,
+            "impop_cluster_scan: unknown identity kind");
+    REQUIRE(params->round_digits <= 19, "impop_cluster_scan: round_digits > 19 unsupported");
+    // subset P index list
+    const uint32_t n = m->g.n_hap;
+    std::vector<uint32_t> idx;
+    for (uint32_t i = 0; i < n; ++i)
+        if (mask_p ? ((mask_p[i >> 6] >> (i & 63)) & 1ull) : true) idx.push_back(i);
+    const uint32_t nP = (uint32_t)idx.size();
+    // refused before anything is uploaded or launched
+    REQUIRE(nP <= IMPOP_CLUSTER_MAX_N, "impop_cluster_scan: %u members exceed the LDS-resident clustering limit (%u)", nP,
+            (uint32_t)IMPOP_CLUSTER_MAX_N);
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_host, "impop_cluster_scan: NULL windows/out");
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, "impop_cluster_scan");
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    ClusterEpilogue epi;
+    epi.params = params; epi.mask_p = mask_p; epi.nP = nP; epi.idx = &idx; epi.out_host = out_host;
+    epi.cluster_of = cluster_of; epi.sizes = sizes;
+    uint64_t call_max_W = 0;
+    for (uint64_t i = 0; i < n_windows; ++i) call_max_W = std::max(call_max_W, window_W(m, windows[i].site_begin, windows[i].site_end));
+    epi.adj_bytes = af_small_certain(params->identity_kind, nP, m->n_hap_pad, call_max_W) ? 0 : af_adjacency_bytes(nP);
+    PairFront in{};
+    in.fn = "impop_cluster_scan"; in.identity_kind = params->identity_kind; in.round_digits = params->round_digits;
+    in.scan_host = nullptr; in.use_segmap = false;  // the site scan for S / D is not needed (impop_pairwise_scan's s_scope 2)
+    in.epi_fixed = ClusterEpilogue::fixed_bytes(nP); in.epi_per_window = epi.window_bytes();
+    in.out_per_window = sizeof(impop_cluster_stats) + (epi.want_members() ? 2 * (size_t)nP * 4 : 0);
+    // the general form keeps a window's adjacency rows in memory (20 MB at the limit): chunks of at most 2 GiB of them
+    in.max_chunk_windows = std::min<uint64_t>(65535, std::max<uint64_t>(1, (2ull << 30) / std::max<size_t>(in.epi_per_window, 1)));
+    return pairwise_front(ctx, m, windows, n_windows, in, epi);
 }

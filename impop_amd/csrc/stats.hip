@@ -1158,17 +1158,22 @@ __global__ __launch_bounds__(ST, 5) void hud_grouped_kernel(SimBatch batch, cons
 }
 
 // ---------------------------------------------------------------------------------------
-// af.cluster (af.py:35-44): adjacency bits, then min-label propagation with pointer jumping
-__global__ void af_adjacency_kernel(SimBatch batch, double threshold, uint32_t words, uint32_t *__restrict__ adj) {
-    const uint32_t n = batch.n;
+// af.cluster (af.py:35-44): adjacency bits, then min-label propagation with pointer jumping.
+// A grid over problems (blockIdx.y): positions 0..m of a problem are the elements idx[0..m) (nullptr: the sequences
+// themselves); problem p's rows at adj + p * m * words.
+__global__ void af_adjacency_kernel(SimBatch batch, const uint32_t *__restrict__ idx, uint32_t m, double threshold, uint32_t words,
+                                    uint32_t *__restrict__ adj) {
+    const uint64_t prob = blockIdx.y;
     const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (uint64_t)n * words) return;
-    const uint32_t i = (uint32_t)(t / words), w = (uint32_t)(t % words);
-    const SimView S = sim_view(batch, 0);
+    if (t >= (uint64_t)m * words) return;
+    const uint32_t o = (uint32_t)(t / words), w = (uint32_t)(t % words);
+    const SimView S = sim_view(batch, prob);
+    const uint32_t i = idx ? idx[o] : o;
     uint32_t bits = 0;
     for (uint32_t b = 0; b < 32; ++b) {
-        const uint32_t j = 32 * w + b;
-        if (j >= n) break;
+        const uint32_t q = 32 * w + b;
+        if (q >= m) break;
+        const uint32_t j = idx ? idx[q] : q;
         const double v = sim_get(S, i, j);  // the orientation above the diagonal
         bool link = v == v && v >= threshold;  // non-strict (af.py:38)
         if (!link && S.dense && i != j) {
@@ -1179,28 +1184,39 @@ __global__ void af_adjacency_kernel(SimBatch batch, double threshold, uint32_t w
         }
         if (link) bits |= 1u << b;
     }
-    adj[t] = bits;
+    adj[prob * (uint64_t)m * words + t] = bits;
 }
 
-// dynamic LDS: label[n] | size[n] | rank[n] (+ 16 bytes of padding); static LDS: the two words `changed` and `K`.
+// dynamic LDS: label[n] | size[n] | rank[n] | the record's three sums (largest, singletons, sum of squares: 12 of the 16 bytes of
+// padding; n <= 12798 keeps the sum of squares below 2^32); static LDS: the two words `changed` and `K`.
 // The workgroup is given AF_LDS_BUDGET of the 160 KB a CDNA4 workgroup has; AF_MAX_N is the largest n that fits
 // (12798; include/impop_hip.h states the same number as IMPOP_CLUSTER_MAX_N).
 constexpr size_t AF_LDS_BUDGET = 150 * 1024, AF_STATIC_LDS = 2 * sizeof(uint32_t), AF_DYN_PAD = 16;
 constexpr uint32_t AF_MAX_N = (uint32_t)((AF_LDS_BUDGET - AF_STATIC_LDS - AF_DYN_PAD) / 12);
 static_assert(AF_MAX_N == IMPOP_CLUSTER_MAX_N, "the header documents the clustering limit");
+static_assert((uint64_t)AF_MAX_N * AF_MAX_N < (1ull << 32) && AF_DYN_PAD >= 3 * sizeof(uint32_t), "the record's sums are 32-bit words in the padding");
 #define REQUIRE_AF_N(n) REQUIRE((n) <= AF_MAX_N, "af: %u samples exceed the LDS-resident clustering limit (%u)", (n), AF_MAX_N)
+// One workgroup per problem (blockIdx.x); problem p's outputs at cluster_of + p * n, sizes + p * n (zeroed by the caller),
+// n_clusters + p (nullable) and rec + p (nullable; W: the problems' site counts for the record, nullable).
 __global__ __launch_bounds__(ST) void af_components_kernel(uint32_t n, uint32_t words, const uint32_t *__restrict__ adj,
                                                            uint32_t *__restrict__ cluster_of, uint32_t *__restrict__ sizes,
-                                                           uint32_t *__restrict__ n_clusters) {
+                                                           uint32_t *__restrict__ n_clusters, impop_cluster_stats *__restrict__ rec,
+                                                           const uint64_t *__restrict__ W, uint32_t *__restrict__ err) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     uint32_t *label = reinterpret_cast<uint32_t *>(lds_raw);
     uint32_t *size = label + n;
     uint32_t *rank = size + n;
+    uint32_t *sums = rank + n;  // [0] largest, [1] singletons, [2] sum of squared sizes
     __shared__ uint32_t changed, K;
     const uint32_t tid = threadIdx.x;
+    const uint64_t prob = blockIdx.x;
+    adj += prob * (uint64_t)n * words;
+    cluster_of += prob * n;
+    sizes += prob * n;
     for (uint32_t i = tid; i < n; i += ST) { label[i] = i; size[i] = 0; }
     __syncthreads();
-    for (uint32_t iter = 0; iter <= n; ++iter) {  // bounded: labels only decrease
+    bool done = false;
+    for (uint32_t iter = 0; iter <= n; ++iter) {  // bounded: the smallest label of a component reaches a member d edges away in d rounds
         if (tid == 0) changed = 0;
         __syncthreads();
         for (uint32_t i = tid; i < n; i += ST) {
@@ -1227,12 +1243,14 @@ __global__ __launch_bounds__(ST) void af_components_kernel(uint32_t n, uint32_t 
         __syncthreads();
         const uint32_t c = changed;
         __syncthreads();
-        if (!c) break;
+        if (!c) { done = true; break; }
     }
+    if (!done && tid == 0 && err) atomicOr(err, DEV_ERR_CLUSTER);  // out of rounds: the call fails (IMPOP_E_INTERNAL), nothing spins
     for (uint32_t i = tid; i < n; i += ST) atomicAdd(&size[label[i]], 1u);
-    if (tid == 0) K = 0;
+    if (tid == 0) { K = 0; sums[0] = 0; sums[1] = 0; sums[2] = 0; }
     __syncthreads();
     // order roots by (-size, smallest member) (af.py:43); the root label IS the smallest member
+    uint32_t my_k = 0, my_max = 0, my_single = 0, my_sq = 0;
     for (uint32_t r = tid; r < n; r += ST) {
         if (!size[r]) continue;
         uint32_t rk = 0;
@@ -1242,11 +1260,28 @@ __global__ __launch_bounds__(ST) void af_components_kernel(uint32_t n, uint32_t 
         }
         rank[r] = rk;
         sizes[rk] = size[r];
-        atomicAdd(&K, 1u);
+        ++my_k;
+        my_max = size[r] > my_max ? size[r] : my_max;
+        my_single += size[r] == 1 ? 1u : 0u;
+        my_sq += size[r] * size[r];
+    }
+    if (my_k) {  // integer sums: the order of the additions does not show
+        atomicAdd(&K, my_k);
+        atomicMax(&sums[0], my_max);
+        atomicAdd(&sums[1], my_single);
+        atomicAdd(&sums[2], my_sq);
     }
     __syncthreads();
     for (uint32_t i = tid; i < n; i += ST) cluster_of[i] = rank[label[i]];
-    if (tid == 0) *n_clusters = K;
+    if (tid == 0) {
+        if (n_clusters) n_clusters[prob] = K;
+        if (rec) {
+            impop_cluster_stats o;
+            o.n_members = n; o.n_clusters = K; o.largest = sums[0]; o.n_singletons = sums[1]; o.sum_sq = sums[2];
+            o.n_sites = W ? (uint32_t)W[prob] : 0u; o.reserved = 0;
+            rec[prob] = o;
+        }
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1409,24 +1444,49 @@ int launch_hud_grouped(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, c
     return IMPOP_OK;
 }
 
-int launch_af(impop_ctx *ctx, const SimBatch &b, double threshold, uint32_t *d_adj, uint32_t *d_cluster_of,
-              uint32_t *d_sizes, uint32_t *d_nclusters) {
-    const uint32_t n = b.n, words = (n + 31) / 32;
-    REQUIRE_AF_N(n);
-    const size_t lds = (size_t)n * 12 + AF_DYN_PAD;
-    if (n) {
-        const uint64_t total = (uint64_t)n * words;
-        hipLaunchKernelGGL(af_adjacency_kernel, dim3((uint32_t)((total + 255) / 256)), dim3(256), 0, ctx->stream, b,
-                           threshold, words, d_adj);
+// general form of the clustering: any identity, any counts, m <= AF_MAX_N positions per problem.  d_adj: n_problems x m x
+// ceil(m / 32) words; d_sizes (n_problems x m) must be zero; d_nclusters / d_rec nullable.
+int launch_af_general(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t m, double threshold,
+                      uint32_t *d_adj, uint32_t *d_cluster_of, uint32_t *d_sizes, uint32_t *d_nclusters, impop_cluster_stats *d_rec) {
+    const uint32_t words = (m + 31) / 32;
+    REQUIRE_AF_N(m);
+    if (!n_problems) return IMPOP_OK;
+    REQUIRE(n_problems <= 65535, "af: too many problems in one launch");
+    const size_t lds = (size_t)m * 12 + AF_DYN_PAD;
+    if (m) {
+        const uint64_t total = (uint64_t)m * words;
+        hipLaunchKernelGGL(af_adjacency_kernel, dim3((uint32_t)((total + 255) / 256), (uint32_t)n_problems), dim3(256), 0, ctx->stream, b,
+                           d_idx, m, threshold, words, d_adj);
         HIP_TRY(hipGetLastError());
     }
+    // above 48 KiB the kernel's limit is raised for this launch, on the device the caller made current (a process-wide
+    // "done once" flag would leave every other device at the default)
     if (lds > 48 * 1024)
         HIP_TRY(hipFuncSetAttribute((const void *)af_components_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                     (int)lds));
-    hipLaunchKernelGGL(af_components_kernel, dim3(1), dim3(ST), lds, ctx->stream, n, words, d_adj, d_cluster_of, d_sizes,
-                       d_nclusters);
+    hipLaunchKernelGGL(af_components_kernel, dim3((uint32_t)n_problems), dim3(ST), lds, ctx->stream, m, words, d_adj, d_cluster_of, d_sizes,
+                       d_nclusters, d_rec, b.W, ctx->d_err);
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
+}
+
+int launch_af(impop_ctx *ctx, const SimBatch &b, double threshold, uint32_t *d_adj, uint32_t *d_cluster_of,
+              uint32_t *d_sizes, uint32_t *d_nclusters) {
+    return launch_af_general(ctx, b, 1, nullptr, b.n, threshold, d_adj, d_cluster_of, d_sizes, d_nclusters, nullptr);
+}
+
+size_t af_adjacency_bytes(uint32_t m) { return (size_t)m * ((m + 31) / 32) * 4; }
+
+int launch_af_batch(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t m, double threshold,
+                    uint32_t *d_adj, size_t adj_bytes_per_problem, impop_cluster_stats *d_rec, uint32_t *d_cluster_of, uint32_t *d_sizes,
+                    bool want_members) {
+    if (!n_problems) return IMPOP_OK;
+    if (af_small_applies(b, m))  // the window-statistics shape: stats_small.hip
+        return launch_af_small(ctx, b, n_problems, d_idx, m, threshold, d_rec, want_members ? d_cluster_of : nullptr,
+                               want_members ? d_sizes : nullptr);
+    REQUIRE(adj_bytes_per_problem >= af_adjacency_bytes(m), "af: the general form was given no room for its adjacency rows");
+    if (m) HIP_TRY(hipMemsetAsync(d_sizes, 0, n_problems * (size_t)m * 4, ctx->stream));
+    return launch_af_general(ctx, b, n_problems, d_idx, m, threshold, d_adj, d_cluster_of, d_sizes, nullptr, d_rec);
 }
 
 // scratch carve helper

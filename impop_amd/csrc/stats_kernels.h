@@ -222,5 +222,19 @@ int launch_hud_grouped(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, c
                        double threshold, const uint64_t *d_seq_len, HfstOut *d_out);
 int launch_af(impop_ctx *ctx, const SimBatch &b, double threshold, uint32_t *d_adj, uint32_t *d_cluster_of,
               uint32_t *d_sizes, uint32_t *d_nclusters);
+// af.cluster for a batch of Gram problems (impop_cluster_scan): positions 0..m of every problem are the elements d_idx[0..m)
+// (nullptr: the sequences themselves).  Two forms, chosen like the pica2 kernels: the window-statistics shape (m <= 512,
+// `match`; stats_small.hip: adjacency bits in LDS, needs no d_adj) and the general one (stats.hip: d_adj holds
+// n_problems x adj_bytes_per_problem >= af_adjacency_bytes(m), d_cluster_of and d_sizes n_problems x m words whatever want_members says).
+// want_members false: the small form writes the records only.
+bool af_small_applies(const SimBatch &b, uint32_t m);
+// known before any chunk exists: every chunk of a call with these parameters (max_W = its largest window) takes the small form
+bool af_small_certain(int kind, uint32_t m, uint32_t ld, uint64_t max_W);
+size_t af_adjacency_bytes(uint32_t m);
+int launch_af_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t m, double threshold,
+                    impop_cluster_stats *d_rec, uint32_t *d_cluster_of, uint32_t *d_sizes);
+int launch_af_batch(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t m, double threshold,
+                    uint32_t *d_adj, size_t adj_bytes_per_problem, impop_cluster_stats *d_rec, uint32_t *d_cluster_of, uint32_t *d_sizes,
+                    bool want_members);
 
 }  // namespace impop

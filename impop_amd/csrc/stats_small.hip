@@ -106,9 +106,11 @@ __device__ __forceinline__ int32_t one_count(const CT *__restrict__ g, uint32_t 
 // "identity > threshold" is "H <= H*" (stats.hip match_cutoff: the largest H whose identity — the very function the pairs
 // would be tested with — exceeds the threshold; -1: none).  One wave searches 64 distances at a time: three rounds for a
 // 50 kb window instead of seventeen bisection steps every thread repeats.
+// GE: the non-strict compare of af.py:38 — the largest H whose identity is >= the threshold.
+template <bool GE = false>
 __device__ __forceinline__ int32_t match_cutoff_wave(const SimView &S, double thr) {
     const uint32_t lane = threadIdx.x & 63;
-    auto above = [&](int64_t H) { const double v = match_identity(S.W, H, S.round_digits); return v == v && v > thr; };
+    auto above = [&](int64_t H) { const double v = match_identity(S.W, H, S.round_digits); return v == v && (GE ? v >= thr : v > thr); };
     const int64_t W = (int64_t)S.W;
     const bool a0 = above(0), aW = above(W);
     if (!a0) return -1;
@@ -528,12 +530,175 @@ __global__ __launch_bounds__(SM_T, SEG ? 4 : 5) void pica2_small_kernel(SimBatch
     }
 }
 
-bool small_shape(const SimBatch &b) {
+// ---------------------------------------------------------------------------------------
+// af.py:35-54 cluster: connected components of {identity >= threshold} over the positions 0..m (elements idx[0..m), ascending),
+// ordered by (-size, smallest member).  The link test is H <= H* (match_cutoff_wave<true>: the non-strict compare, decided
+// through the very identity function).  A wave takes rows c and the words of the positions right of them (the upper triangle,
+// the part the Gram kernel writes; two rows' loads in flight): ballot(H <= H*) is a 64-bit word of row c's adjacency, and the
+// lane whose position j linked sets bit c of row j — the relation is symmetric in LDS, so label propagation only PULLS and a
+// label has one writer.  Rows are AF_ROW = 17 words apart (16 hold 512 bits): the lanes' transposed bits fall into different
+// banks.  LDS per workgroup: 34 KB of bits + 5 KB (diagonal counts, later the cluster sizes; elements; labels; ranks) = under
+// 40 KB, four workgroups per CU.
+constexpr uint32_t AF_ROW = SM_N / 32 + 1;
+template <bool SEG, typename CT>
+__global__ __launch_bounds__(SM_T, 4) void af_small_kernel(SimBatch batch, const uint32_t *__restrict__ idx, uint32_t m, double thr,
+                                                           impop_cluster_stats *__restrict__ rec, uint32_t *__restrict__ cluster_of,
+                                                           uint32_t *__restrict__ sizes) {
+    __shared__ uint32_t adj[SM_N * AF_ROW];
+    __shared__ uint32_t dg_or_size[SM_N];  // Gram diagonal by position while the bits are formed, then the size of the cluster rooted there
+    __shared__ uint16_t epos[SM_N], label[SM_N], crank[SM_N];
+    __shared__ uint32_t sh_changed, sh_K, sh_largest, sh_single;
+    __shared__ unsigned long long sh_sq;
+    __shared__ int32_t sh_hcut;
+    const uint64_t prob = blockIdx.x;
+    SimView S = sim_view(batch, prob);
+    S.dense = nullptr; S.g16 = sizeof(CT) == 2 ? 1u : 0u;  // (sim_view took the problem's base from batch.g16: the launch matches CT to it)
+    if (!SEG) S.nseg = 1;
+    const uint32_t nseg = S.nseg, sstride = (uint32_t)S.seg_stride;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = uni(tid >> 6), ld = S.ld;
+    const CT *__restrict__ g = reinterpret_cast<const CT *>(S.gram);
+    const int32_t junk = (int32_t)lane;  // see skipped_load
+    const uint32_t nw = (m + 63) >> 6;
+    int32_t *dg_l = reinterpret_cast<int32_t *>(dg_or_size);
+    uint32_t *csize = dg_or_size;
+    for (uint32_t o = tid; o < SM_N; o += SM_T) {
+        const uint32_t e = o < m ? (idx ? idx[o] : o) : 0u;
+        epos[o] = (uint16_t)e;
+        dg_l[o] = o < m ? one_count<SEG, CT>(g, nseg, sstride, e * (ld + 1)) : 0;
+        label[o] = (uint16_t)o;
+    }
+    for (uint32_t t = tid; t < m * AF_ROW; t += SM_T) adj[t] = 0;
+    if (wave == 0) {
+        const int32_t hc = match_cutoff_wave<true>(S, thr);
+        if (lane == 0) { sh_hcut = hc; sh_K = 0; sh_largest = 0; sh_single = 0; sh_sq = 0; }
+    }
+    __syncthreads();
+    const int32_t hcut = (int32_t)uni((uint32_t)sh_hcut);
+    uint32_t ek[SM_W];  // element and diagonal of this lane's positions
+    int32_t dgk[SM_W];
+#pragma unroll
+    for (uint32_t k = 0; k < SM_W; ++k) { ek[k] = epos[64 * k + lane]; dgk[k] = dg_l[64 * k + lane]; }
+    for (uint32_t b0 = wave; b0 < m; b0 += 2 * (SM_T / 64)) {
+        uint32_t c[2], k0[2], row[2];
+        int32_t ac[2];
+        bool lv[2];
+        int32_t I[2][SM_W];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const uint32_t b = b0 + (SM_T / 64) * u;
+            lv[u] = b < m;
+            c[u] = lv[u] ? b : b0;
+            k0[u] = c[u] >> 6;
+            ac[u] = (int32_t)uni((uint32_t)dg_l[c[u]]);
+            row[u] = uni((uint32_t)epos[c[u]]) * ld;
+        }
+        // positions ascend, so do the elements: (row, column) is in the upper triangle
+        row_counts<SM_W, 2, SEG, CT>(g, nseg, sstride, lv, k0, nw, junk, [&](int u, uint32_t k) { return row[u] + ek[k]; }, I);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (!lv[u]) continue;
+#pragma unroll
+            for (uint32_t k = 0; k < SM_W; ++k) {
+                if (k >= k0[u] && k < nw) {
+                    const uint32_t j = 64 * k + lane;
+                    const int32_t H = ac[u] + dgk[k] - 2 * I[u][k];  // (the constant of a compacted matrix cancels)
+                    const bool link = j > c[u] && j < m && H <= hcut;  // non-strict >= threshold (af.py:38)
+                    const uint64_t bits = __ballot(link);
+                    if (lane == 0 && (uint32_t)bits) atomicOr(&adj[c[u] * AF_ROW + 2 * k], (uint32_t)bits);
+                    if (lane == 1 && (uint32_t)(bits >> 32)) atomicOr(&adj[c[u] * AF_ROW + 2 * k + 1], (uint32_t)(bits >> 32));
+                    if (link) atomicOr(&adj[j * AF_ROW + (c[u] >> 5)], 1u << (c[u] & 31));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    // min-label propagation with pointer jumping.  label[o] is written by the thread that owns o alone; what it reads of the
+    // others may be a round old, never wrong (labels only fall, and only to labels of the same component).  The smallest label of
+    // a component reaches a member d edges away after d rounds at the latest: m + 1 rounds bound the loop whatever happens; running
+    // out of them means an invariant broke — the device error word then fails the call (IMPOP_E_INTERNAL).
+    const uint32_t nw32 = (m + 31) >> 5;
+    bool done = false;
+    for (uint32_t round = 0; round <= m; ++round) {
+        if (tid == 0) sh_changed = 0;
+        __syncthreads();
+        bool ch = false;
+        for (uint32_t o = tid; o < m; o += SM_T) {
+            uint32_t mn = label[o];
+            for (uint32_t w = 0; w < nw32; ++w) {
+                uint32_t bits = adj[o * AF_ROW + w];
+                while (bits) {
+                    const uint32_t j = 32 * w + (uint32_t)(__ffs(bits) - 1);
+                    bits &= bits - 1;
+                    const uint32_t lj = label[j];
+                    mn = lj < mn ? lj : mn;
+                }
+            }
+            if (mn < label[o]) { label[o] = (uint16_t)mn; ch = true; }
+        }
+        __syncthreads();
+        for (uint32_t o = tid; o < m; o += SM_T) {
+            const uint32_t l = label[o], ll = label[l];
+            if (ll < l) { label[o] = (uint16_t)ll; ch = true; }
+        }
+        if (ch) sh_changed = 1;
+        __syncthreads();
+        const uint32_t any = uni(sh_changed);
+        __syncthreads();
+        if (!any) { done = true; break; }
+    }
+    if (!done && tid == 0 && batch.err) atomicOr(batch.err, DEV_ERR_CLUSTER);
+    // sizes by root (the root's label IS the component's smallest position); the diagonal counts are no longer needed
+    for (uint32_t o = tid; o < SM_N; o += SM_T) csize[o] = 0;
+    __syncthreads();
+    for (uint32_t o = tid; o < m; o += SM_T) atomicAdd(&csize[label[o]], 1u);
+    __syncthreads();
+    // rank of a root among the roots by (-size, root) (af.py:43) and the record's integer sums (order-independent)
+    uint32_t my_k = 0, my_max = 0, my_single = 0, my_sq = 0;
+    for (uint32_t r = tid; r < m; r += SM_T) {
+        const uint32_t sr = csize[r];
+        if (!sr) continue;
+        uint32_t rk = 0;
+        for (uint32_t q = 0; q < m; ++q) {
+            const uint32_t sq = csize[q];
+            rk += (sq > sr || (sq == sr && q < r)) ? 1u : 0u;  // (sr > 0: an empty position never counts)
+        }
+        crank[r] = (uint16_t)rk;
+        if (sizes) sizes[prob * m + rk] = sr;
+        ++my_k;
+        my_max = sr > my_max ? sr : my_max;
+        my_single += sr == 1 ? 1u : 0u;
+        my_sq += sr * sr;
+    }
+    if (my_k) {
+        atomicAdd(&sh_K, my_k);
+        atomicMax(&sh_largest, my_max);
+        atomicAdd(&sh_single, my_single);
+        atomicAdd(&sh_sq, (unsigned long long)my_sq);
+    }
+    __syncthreads();
+    const uint32_t K = uni(sh_K);
+    for (uint32_t o = tid; o < m; o += SM_T) {
+        if (cluster_of) cluster_of[prob * m + o] = crank[label[o]];
+        if (sizes && o >= K) sizes[prob * m + o] = 0;
+    }
+    if (tid == 0) {
+        impop_cluster_stats r;
+        r.n_members = m; r.n_clusters = K; r.largest = sh_largest; r.n_singletons = sh_single; r.sum_sq = sh_sq;
+        r.n_sites = (uint32_t)S.W; r.reserved = 0;
+        rec[prob] = r;
+    }
+}
+
+// what the window-statistics kernels ask of a batch's PARAMETERS (known before any Gram matrix exists): `match` identity, counts of
+// 16 bits (g16; they imply W < 2^16) or of 32 bits with a stated largest W below 2^30 (Hamming distances are formed in 32-bit
+// arithmetic), element offsets inside a matrix in 32 bits (elements and positions in 16)
+bool small_params(int kind, uint32_t ld, bool g16, uint64_t max_W) {
     static const bool off = [] { const char *e = getenv("IMPOP_EPILOGUE_SMALL"); return e && e[0] == '0'; }();  // A/B and test switch
-    // counts of 16 or 32 bits; Hamming distances are formed in 32-bit arithmetic: W < 2^30 (uint16 counts imply W < 2^16)
-    const bool w_ok = b.g16 || (b.max_W != 0 && b.max_W < (1ull << 30));
-    return !off && b.gram && !b.dense && w_ok && (b.seg_first != nullptr) == (b.seg_count != nullptr) && b.kind == IMPOP_IDENTITY_MATCH &&
-           b.ld <= 4096;  // (element offsets inside a matrix are 32-bit, elements and positions 16-bit)
+    const bool w_ok = g16 || (max_W != 0 && max_W < (1ull << 30));
+    return !off && w_ok && kind == IMPOP_IDENTITY_MATCH && ld <= 4096;
+}
+bool small_shape(const SimBatch &b) {
+    return b.gram && !b.dense && (b.seg_first != nullptr) == (b.seg_count != nullptr) && small_params(b.kind, b.ld, b.g16 != 0, b.max_W);
 }
 
 }  // namespace
@@ -542,6 +707,9 @@ bool pica2_small_applies(const SimBatch &b, uint32_t n_el, const uint32_t *d_ord
     return small_shape(b) && n_el <= SM_N && !d_order && !d_group_of;
 }
 bool hfst_small_applies(const SimBatch &b) { return small_shape(b) && b.n <= SM_N; }
+bool af_small_applies(const SimBatch &b, uint32_t m) { return small_shape(b) && m <= SM_N; }
+// (a chunk's counts may still come out as uint16, which only widens what small_params accepts)
+bool af_small_certain(int kind, uint32_t m, uint32_t ld, uint64_t max_W) { return small_params(kind, ld, false, max_W) && m <= SM_N; }
 
 int launch_pica2_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t n_el, double threshold,
                        const uint64_t *d_seq_len, Pica2Out *d_out) {
@@ -553,6 +721,20 @@ int launch_pica2_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, c
     if (b.seg_first) { if (b.g16) LAUNCH_P2(true, uint16_t); else LAUNCH_P2(true, int32_t); }
     else { if (b.g16) LAUNCH_P2(false, uint16_t); else LAUNCH_P2(false, int32_t); }
 #undef LAUNCH_P2
+    HIP_TRY(hipGetLastError());
+    return IMPOP_OK;
+}
+
+int launch_af_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t m, double threshold,
+                    impop_cluster_stats *d_rec, uint32_t *d_cluster_of, uint32_t *d_sizes) {
+    SimBatch be = b;
+    be.err = ctx->d_err;  // the propagation's round bound reports here
+#define LAUNCH_AF(SEG, CT)                                                                                                          \
+    hipLaunchKernelGGL((af_small_kernel<SEG, CT>), dim3((uint32_t)n_problems), dim3(SM_T), 0, ctx->stream, be, d_idx, m, threshold, d_rec, \
+                       d_cluster_of, d_sizes)
+    if (b.seg_first) { if (b.g16) LAUNCH_AF(true, uint16_t); else LAUNCH_AF(true, int32_t); }
+    else { if (b.g16) LAUNCH_AF(false, uint16_t); else LAUNCH_AF(false, int32_t); }
+#undef LAUNCH_AF
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }

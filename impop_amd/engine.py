@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -26,6 +26,10 @@ PAIRWISE_DTYPE = np.dtype([
     ("dxy", "<f8"), ("da", "<f8"), ("tajima_d", "<f8"), ("n_groups", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"),
     ("n_sites", "<u4"), ("reserved", "<u8")])
 assert PAIRWISE_DTYPE.itemsize == 96
+
+CLUSTER_DTYPE = np.dtype([("n_members", "<u4"), ("n_clusters", "<u4"), ("largest", "<u4"), ("n_singletons", "<u4"), ("sum_sq", "<u8"),
+                          ("n_sites", "<u4"), ("reserved", "<u4")])
+assert CLUSTER_DTYPE.itemsize == 32
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 
@@ -155,6 +159,12 @@ class Context:
         """-> (summed Gram-kernel ms, launches) since gram_timing(True)"""
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_gram_elapsed(self.handle, C.byref(t), C.byref(k)))
+        return t.value, k.value
+
+    def cluster_elapsed(self):
+        """-> (summed clustering-kernel ms of cluster_scan, chunks) since gram_timing(True)"""
+        t, k = C.c_double(), C.c_uint64()
+        check(self._lib.impop_ctx_cluster_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
 
     def close(self) -> None:
@@ -525,6 +535,27 @@ class BitMatrix:
         check(self.ctx._lib.impop_pairwise_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
                                                 pp, pa, pb, C.byref(prm), out.ctypes.data_as(C.POINTER(PairwiseStats))))
         return out
+
+    def cluster_scan(self, windows, mask_p=None, kind: str = "match", threshold: float = 1.0, round_digits: Optional[int] = None,
+                     want_members: bool = True):
+        """af.cluster (af.py:35-54) per window from the bit matrix (impop_cluster_scan): components of
+        {identity >= threshold} over the members of mask_p, ordered by (-size, smallest member index).
+        -> records (CLUSTER_DTYPE), and with want_members also cluster_of and sizes, both [n_windows, |P|]
+        (members in ascending haplotype index; sizes: first n_clusters valid, the rest 0)."""
+        w = make_windows(windows)
+        out = np.zeros(len(w), dtype=CLUSTER_DTYPE)
+        prm = ClusterParams(C.sizeof(ClusterParams), IDENTITY_KINDS[kind], float(threshold),
+                            -1 if round_digits is None else int(round_digits), 0)
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        n_p = self.n_hap if mask_p is None else int(np.unpackbits(kp.view(np.uint8), bitorder="little")[: self.n_hap].sum())
+        cl = np.zeros((len(w), n_p), dtype=np.uint32) if want_members else None
+        sz = np.zeros((len(w), n_p), dtype=np.uint32) if want_members else None
+        u32p = C.POINTER(C.c_uint32)
+        check(self.ctx._lib.impop_cluster_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, C.byref(prm),
+                                               out.ctypes.data_as(C.POINTER(ClusterStats)),
+                                               cl.ctypes.data_as(u32p) if want_members else None,
+                                               sz.ctypes.data_as(u32p) if want_members else None))
+        return (out, cl, sz) if want_members else out
 
 
 class ScanPlan:

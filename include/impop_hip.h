@@ -34,7 +34,7 @@
 extern "C" {
 #endif
 
-#define IMPOP_ABI_VERSION 3
+#define IMPOP_ABI_VERSION 4
 
 typedef enum impop_status {
     IMPOP_OK = 0,
@@ -328,8 +328,8 @@ int impop_pairwise_counts(impop_ctx *ctx, const impop_matrix *m, uint64_t site_b
 int impop_pairwise_identity(impop_ctx *ctx, const impop_matrix *m, uint64_t site_begin, uint64_t site_end,
                             int identity_kind, double *out_host);
 
-/* Full pica2 / h-fst / af semantics (thresholds, rounding, grouping) for a
- * batch of windows straight from the bit matrix; identity never leaves the GPU. */
+/* Full pica2 / h-fst semantics (thresholds, rounding, grouping) for a batch of windows straight from the bit
+ * matrix; identity never leaves the GPU.  af.py's clustering of the same windows is impop_cluster_scan below. */
 typedef struct impop_pairwise_params {
     uint32_t struct_size;
     int32_t identity_kind;   /* IMPOP_IDENTITY_* */
@@ -350,6 +350,36 @@ typedef struct impop_pairwise_stats { /* 96 bytes */
 int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                         const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
                         const impop_pairwise_params *params, impop_pairwise_stats *out_host);
+#define IMPOP_CLUSTER_MAX_N 12798u /* see impop_cluster_from_identity */
+/* af.cluster (af.py:35-54) for a batch of windows straight from the bit matrix: per window the connected components of
+ * {identity(i, j) >= threshold} over the members of P, the identity being exactly the double impop_pairwise_identity
+ * yields for that window (weights and compacted matrices included; rounded like pica2 -r when round_digits >= 0).
+ * Clusters are ordered by (-size, smallest member index), as impop_cluster_from_identity orders them.  At threshold
+ * 1.0 (af.py:73) the clusters are the window's distinct haplotypes: sizes is the haplotype frequency spectrum and
+ * sum_sq / n_members^2 the haplotype homozygosity.
+ * |P| <= IMPOP_CLUSTER_MAX_N; a larger |P| returns IMPOP_E_INVALID before anything is uploaded or launched.  A window
+ * without sites has identity 1.0 for every pair (one cluster).  Checks the device error word like impop_pairwise_scan;
+ * chunking never changes a record. */
+typedef struct impop_cluster_params {
+    uint32_t struct_size;
+    int32_t identity_kind;   /* IMPOP_IDENTITY_MATCH / _DICE */
+    double threshold;        /* af.py --threshold; linked when identity >= threshold (af.py:38) */
+    int32_t round_digits;    /* < 0 = none (af.py does not round); >= 0: the identity pica2 -r would see */
+    uint32_t reserved;
+} impop_cluster_params;
+typedef struct impop_cluster_stats { /* 32 bytes, fixed layout */
+    uint32_t n_members;      /* |P| */
+    uint32_t n_clusters;
+    uint32_t largest;        /* size of c1 */
+    uint32_t n_singletons;
+    uint64_t sum_sq;         /* sum of size_k^2; haplotype homozygosity = sum_sq / n_members^2 */
+    uint32_t n_sites, reserved;
+} impop_cluster_stats;
+/* cluster_of (nullable): n_windows x |P|, the 0-based cluster rank of each member of P in ascending haplotype index;
+ * sizes (nullable): n_windows x |P|, first n_clusters valid, the rest 0. */
+int impop_cluster_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                       const uint64_t *mask_p, const impop_cluster_params *params, impop_cluster_stats *out_host,
+                       uint32_t *cluster_of, uint32_t *sizes);
 /* Measurement aid (like impop_scan_plan_timing): with timing enabled every Gram launch of impop_pairwise_scan on this context
  * is bracketed with hipEvents on the context's stream; elapsed() synchronises and returns the summed Gram-kernel time and the
  * number of launches since enable / reset. */
@@ -359,6 +389,9 @@ int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_windo
 int impop_debug_raise_device_error(impop_ctx *ctx, uint32_t bits);
 int impop_ctx_gram_timing(impop_ctx *ctx, int enable);
 int impop_ctx_gram_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
+/* With the same switch on, impop_cluster_scan also brackets its clustering kernel(s): their summed time and number of
+ * chunks since enable / reset, next to the Gram time above. */
+int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
 
 /* impop_pairwise_scan over several devices, sharded like impop_scan_sharded (declared with the multi-GPU entry points
  * above; run_pica2_impg.sh:125-236 / run_h-fst.sh:155-190 with thresholds):
@@ -484,7 +517,6 @@ int impop_tajimas_d_from_pi_site(int64_t n, double S, double pi_site, double *D)
  * one orientation of a pair (NaN in the other) clusters like the symmetric one.
  * n <= IMPOP_CLUSTER_MAX_N (the labels of all samples stay in the LDS of one workgroup); a larger n returns
  * IMPOP_E_INVALID before anything is uploaded or launched. */
-#define IMPOP_CLUSTER_MAX_N 12798u
 int impop_cluster_from_identity(impop_ctx *ctx, const double *ident, uint32_t n, double threshold,
                                 uint32_t *cluster_of, uint32_t *n_clusters, uint32_t *sizes);
 

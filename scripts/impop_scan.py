@@ -9,6 +9,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format pica2 -t 0.999 -r 5 [-u subset.txt]
     impop_scan.py --matrix chr1.npz chr2.npz ... --bed genome.bed --format all ...            # one matrix per chromosome
     impop_scan.py --sim-list windows.tsv --format pica2 -t 0.999 -r 5                         # one `.sim` table per window
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format af [-t 1.0] [-u subset.txt] [--af-clusters c.tsv] [--af-details d.tsv]
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
 window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
@@ -22,7 +23,14 @@ What -t / -r mean, per format (the THRESHOLD / R_VALUE columns always print what
   fst3pi  the three pica2 runs of run_fst_impg.sh:73 (same defaults as pica2).
   hfst    -r is h-fst.py -r (run_h-fst.sh:76-78); -t only with --fst-method grouped (hud.py -t, default 0.999).
   all     -t / -r as for tajd (same defaults) for the pica2 and tajd tables; the h-fst table rounds with --fst-round-digits.
+  af      af.py --threshold (default 1.0, af.py:73); -r rounds the identity like pica2 -r first (af.py itself does not round).
   `-r none` switches rounding off where a default would apply.
+
+--format af (scripts/af.py per window, impop_cluster_scan): haplotype clusters = connected components of {identity >= -t} among
+the sequences of -u (default: all).  Main table REGION LENGTH THRESHOLD HAPLOTYPES CLUSTERS LARGEST SINGLETONS HOMOZYGOSITY
+(homozygosity = sum of squared cluster frequencies, "%.6f" like af.py:60); --af-clusters FILE gets af.py's summary rows and
+--af-details FILE its per-sample rows, each behind a REGION column.  One process, one GPU; not with --sim-list.  Sequence names
+are cut at the first ':' as af.py cuts them and must then be distinct (af.py would merge two rows of one name into one sample).
 
 A threshold >= 1 without rounding on the `match` identity is the streaming site-count scan (every haplotype its own
 group: exact integer identities); anything else runs the all-pairs path (impop_pairwise_scan).
@@ -238,6 +246,59 @@ def write_tables(out, args, fmt, regions, L_col, col, s_all, samples_col, thr_tx
             print(f"{reg}\t{L_col[i]}\t{samples_col}\t{int(s_all[i])}\t{col['pi_site'][i]:.8f}\t{taj}", file=out)
 
 
+AF_HEADER = "REGION\tLENGTH\tTHRESHOLD\tHAPLOTYPES\tCLUSTERS\tLARGEST\tSINGLETONS\tHOMOZYGOSITY"
+
+
+def af_refusal(args):
+    """what --format af does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "af":
+        if args.af_clusters or args.af_details:
+            return "--af-clusters / --af-details belong to --format af"
+        return None
+    if args.sim_list:
+        return "--format af scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format af is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format af runs on one GPU: not with --devices N"
+    if args.panel or args.pop_a or args.pop_b or args.sample_list:
+        return "--format af clusters the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    return None
+
+
+def write_af_table(out, regions, L_col, thr_txt, recs):
+    """the main table of --format af from impop_cluster_stats records (one per region)"""
+    print(AF_HEADER, file=out)
+    for reg, L, r in zip(regions, L_col, recs):
+        n, sq = int(r["n_members"]), int(r["sum_sq"])
+        hom = sq / (n * n) if n else 0.0
+        print(f"{reg}\t{L}\t{thr_txt}\t{n}\t{int(r['n_clusters'])}\t{int(r['largest'])}\t{int(r['n_singletons'])}\t{hom:.6f}", file=out)
+
+
+def write_af_clusters(handle, regions, clusters_per_region, header=True):
+    """REGION + the rows of af.write_summary (af.py:56-60: cluster_id, count, "%.6f" frequency; csv-module line endings)"""
+    import csv
+    from impop_amd.af import build_summary
+    w = csv.writer(handle, delimiter="\t")
+    if header:
+        w.writerow(("REGION", "cluster_id", "count", "frequency"))
+    for reg, clusters in zip(regions, clusters_per_region):
+        w.writerows([(reg, cid, size, f"{freq:.6f}") for cid, size, freq, _ in build_summary(clusters)])
+
+
+def write_af_details(handle, regions, clusters_per_region, threshold, header=True):
+    """REGION + the rows of af.write_details (af.py:62-68: sample_id, cluster_id, threshold)"""
+    import csv
+    from impop_amd.af import build_summary
+    w = csv.writer(handle, delimiter="\t")
+    if header:
+        w.writerow(("REGION", "sample_id", "cluster_id", "threshold"))
+    for reg, clusters in zip(regions, clusters_per_region):
+        w.writerows([(reg, sample, cid, threshold) for cid, _, _, members in build_summary(clusters) for sample in members])
+
+
 def sim_list_refusal(args):
     """what --sim-list does not combine with (one line each, exit 2, before any device is opened)"""
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -366,8 +427,11 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "all"], default="all",
-                    help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint)")
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "all"], default="all",
+                    help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
+                         "(scripts/af.py; not part of `all`)")
+    ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
+    ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="hfst: K >= 2 disjoint population lists; every pair "
                     "in ONE pass (replaces run_h_fst_panels.sh); one table per pair, labelled POP_A-vs-POP_B")
@@ -398,6 +462,10 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
+    refusal = af_refusal(args)
+    if refusal:
+        print(f"Error: {refusal}", file=sys.stderr)
+        sys.exit(2)
     if args.sim_list:
         refusal = sim_list_refusal(args)
         if refusal:
@@ -451,7 +519,7 @@ def main():
     fst_pairs = grouped_fst or fst_r is not None or args.identity != "match"
     want_pica = fmt in ("pica2", "tajd", "all", "fst3pi")
     want_fst = fmt in ("hfst", "all") and not args.panel
-    need_pairs = (want_pica and pica_pairs) or (want_fst and fst_pairs)
+    need_pairs = (want_pica and pica_pairs) or (want_fst and fst_pairs) or fmt == "af"
     if args.panel and (fmt != "hfst" or fst_pairs):
         print("Error: --panel is the streaming K-population scan of --format hfst (direct method, match identity, no rounding)", file=sys.stderr)
         sys.exit(2)
@@ -506,6 +574,8 @@ def main():
     s_all = np.zeros(n_rows, dtype=np.int64)
     panel_tables, panel_labels = None, None
     samples_col = 0
+    af_recs = np.zeros(n_rows, dtype=impop_amd.CLUSTER_DTYPE)
+    af_clusters = [None] * n_rows
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -535,6 +605,28 @@ def main():
             if panel_tables is None:
                 panel_tables = np.zeros((n_rows, pr.shape[1]), dtype=pr.dtype)
             panel_tables[idx] = pr
+            run.close()
+            continue
+        if fmt == "af":
+            from impop_amd.af import _sample_of, clusters_from_ranks
+            want_members = bool(args.af_clusters or args.af_details)
+            members = [_sample_of(names[i]) for i in (range(mf.n_hap) if mask_p is None else np.flatnonzero(mask_p))]
+            if len(set(members)) != len(members):
+                # af.py names its nodes by the cut name, so two sequences of one name would be ONE sample there, while the
+                # records count sequences: the main table and the side tables of one run would disagree
+                dup = sorted({m for m in members if members.count(m) > 1})[0]
+                print(f"Error: --format af needs distinct sequence names before the first ':' ('{dup}' names several rows of the matrix)",
+                      file=sys.stderr)
+                run.close()
+                sys.exit(2)
+            res = run.bm.cluster_scan(run.local_wins, mask_p=mask_p, kind=args.identity, threshold=pica_t, round_digits=pica_r,
+                                      want_members=want_members)
+            if want_members:
+                af_recs[idx] = res[0]
+                for i, row in zip(idx, res[1]):
+                    af_clusters[i] = clusters_from_ranks(row, members)
+            else:
+                af_recs[idx] = res
             run.close()
             continue
         if fmt == "fst3pi":
@@ -587,7 +679,17 @@ def main():
                 col[k][idx] = fst_rec[k]
         run.close()
 
-    write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels)
+    if fmt == "af":
+        regions = [r[0] for r in rows]
+        write_af_table(out, regions, L_col, thr_txt, af_recs)
+        if args.af_clusters:
+            with open(args.af_clusters, "w", newline="") as fh:
+                write_af_clusters(fh, regions, af_clusters)
+        if args.af_details:
+            with open(args.af_details, "w", newline="") as fh:
+                write_af_details(fh, regions, af_clusters, float(pica_t))
+    else:
+        write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels)
     if args.output or rank != 0:
         out.close()
     if world > 1:
