@@ -25,6 +25,8 @@ ABI_VERSION = 4  # IMPOP_ABI_VERSION of include/impop_hip.h
 E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED, E_INTERNAL = -1, -2, -3, -4, -5, -6
 KEEP_SITE_BLOCKED, KEEP_HAP_MAJOR, KEEP_DENSE_SCAN, KEEP_NO_RARE_SPLIT = 1, 2, 4, 8
 IDENTITY_MATCH, IDENTITY_DICE = 0, 1
+EHH_FLANKS_REFERENCE, EHH_FLANKS_TWO_SIDED = 0, 1
+EHH_SCAN_MAX_N = 4096  # IMPOP_EHH_SCAN_MAX_N
 
 
 class Window(C.Structure):
@@ -78,6 +80,20 @@ class ClusterStats(C.Structure):
                 ("sum_sq", C.c_uint64), ("n_sites", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class EhhWindow(C.Structure):
+    _fields_ = [("site_begin", C.c_uint64), ("site_end", C.c_uint64), ("core_site", C.c_uint64)]
+
+
+class EhhParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("flanks", C.c_int32), ("ref_hap", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class EhhStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32 * 2), ("ref_allele", C.c_uint32), ("reserved", C.c_uint32),
+                ("area_milli", (C.c_int64 * 2) * 2), ("area", C.c_double * 2)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -102,6 +118,7 @@ class IdentityBatchParams(C.Structure):
 assert C.sizeof(IdentityStats) == 144 and C.sizeof(IdentityProblem) == 64 and C.sizeof(IdentityBatchParams) == 32
 assert C.sizeof(WindowStats) == 128 and C.sizeof(Window) == 24 and C.sizeof(PairwiseStats) == 96
 assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
+assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -126,6 +143,7 @@ SIGNATURES = {
     "impop_ctx_gram_timing": (C.c_int, [_vp, C.c_int]),
     "impop_ctx_gram_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_cluster_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "impop_ctx_ehh_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_matrix_synthetic_slab": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams), C.c_uint32, C.POINTER(_vp)]),
     "impop_matrix_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),
     "impop_matrix_info": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u32p]),
@@ -173,6 +191,7 @@ SIGNATURES = {
     "impop_matrix_compact": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "impop_matrix_positions": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u64p, _u64p]),
     "impop_ehh": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_int, _f64p, _u32p]),
+    "impop_ehh_scan": (C.c_int, [_vp, _vp, C.POINTER(EhhWindow), C.c_uint64, _u64p, C.POINTER(EhhParams), C.POINTER(EhhStats)]),
     "impop_fst_grouped_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, _u8p, _u8p, C.c_double, C.c_uint64, C.c_int, _u32p, _f64p,
                                                   _u64p]),
     "impop_tajimas_d": (C.c_int, [_vp, _i64p, _f64p, _f64p, C.c_uint64, _f64p, _f64p]),

@@ -160,6 +160,7 @@ IMPOP_API int impop_ctx_destroy(impop_ctx *ctx) {
     if (ctx->d_err) hipFree(ctx->d_err);
     for (auto &e : ctx->gram_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &e : ctx->cluster_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
+    for (auto &e : ctx->ehh_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     for (void *a : ctx->d_aux)
@@ -183,9 +184,10 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
     const uint32_t w = ctx->h_err;
     ctx->h_err = 0;
     HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-    set_error("%s: internal device check failed (code 0x%x%s%s); the results of this call are invalid", fn, w,
+    set_error("%s: internal device check failed (code 0x%x%s%s%s); the results of this call are invalid", fn, w,
               (w & DEV_ERR_GROUPING) ? ": greedy grouping made no progress" : "",
-              (w & DEV_ERR_CLUSTER) ? ": clustering ran out of rounds" : "");
+              (w & DEV_ERR_CLUSTER) ? ": clustering ran out of rounds" : "",
+              (w & DEV_ERR_EHH) ? ": EHH partition refinement is inconsistent" : "");
     return IMPOP_E_INTERNAL;
 }
 }  // namespace impop
@@ -207,6 +209,7 @@ IMPOP_API int impop_ctx_gram_timing(impop_ctx *ctx, int enable) {
     ctx->gram_timing = enable != 0;
     ctx->gram_events_used = 0;
     ctx->cluster_events_used = 0;
+    ctx->ehh_events_used = 0;
     return IMPOP_OK;
 }
 
@@ -237,6 +240,21 @@ IMPOP_API int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64
     }
     if (total_ms) *total_ms = t;
     if (launches) *launches = ctx->cluster_events_used;
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
+    REQUIRE(ctx, "impop_ctx_ehh_elapsed: ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    double t = 0.0;
+    for (size_t i = 0; i < ctx->ehh_events_used; ++i) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ehh_events[i].first, ctx->ehh_events[i].second));
+        t += (double)ms;
+    }
+    if (total_ms) *total_ms = t;
+    if (launches) *launches = ctx->ehh_events_used;
     return IMPOP_OK;
 }
 

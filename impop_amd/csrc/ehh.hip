@@ -12,6 +12,16 @@
 //                             non-zero word; integer atomic into hist[f]
 //   3. ehh_finalize_kernel    one workgroup: scan of hist, then the reference's division and
 //                             CPython round(, 3) in fp64
+//
+// impop_ehh_scan keeps only the integral of each curve, for a batch of (window, core allele, half) problems:
+//   1. ehh_scan_transpose_kernel  the ballot transpose with a window dimension (blockIdx.y), rows compacted to the
+//                                 members of P, every window at its own base of the chunk scratch
+//   2. ehh_refine_kernel          one workgroup per problem: partition refinement of the members (class label,
+//                                 representative and size in LDS) along the walking direction; the curve only steps
+//                                 where a class splits, so one lane integrates it as a run-length sum of thousandths
+#include <string.h>
+
+#include <algorithm>
 #include <vector>
 
 #include "device_utils.h"
@@ -104,6 +114,261 @@ __global__ void ehh_fill_kernel(double *out, uint64_t W, double v) {
     if (i < W) out[i] = v;
 }
 
+
+// ---- impop_ehh_scan ------------------------------------------------------------------------------------------------
+// one window of a chunk: its sites, and where its transposed words live (absolute 64-site blocks tblk0 .. tblk0 + n_blk)
+struct EhhWin {
+    uint64_t begin, end, core;
+    uint64_t woff;   // first word of the window in the chunk scratch
+    uint64_t tblk0;
+    uint32_t n_blk, pad;
+};
+
+// grid = (ceil(max n_blk / 4), windows): wave = one 64-site block of window blockIdx.y; ppos[h] = position of haplotype h
+// in P or -1 (padding rows included); row stride = |P|.  No edge masks: a problem masks its own range.
+__global__ __launch_bounds__(256) void ehh_scan_transpose_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
+                                                                 const EhhWin *__restrict__ win, const int32_t *__restrict__ ppos,
+                                                                 uint32_t stride, uint64_t *__restrict__ wm) {
+    const EhhWin w = win[blockIdx.y];
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t bi = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (bi >= w.n_blk) return;  // wave-uniform
+    const uint64_t b = w.tblk0 + bi;
+    uint64_t *dst = wm + w.woff + bi * stride;
+    for (uint32_t k = 0; k < wps; ++k) {
+        const uint32_t v = sb[sb_index(wps, G, r, b, lane, k)];
+        uint64_t keep = 0;
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            const uint64_t m = __ballot((v >> j) & 1u);
+            if (lane == (uint32_t)j) keep = m;
+        }
+        if (lane < 32) {
+            const int32_t pp = ppos[32 * k + lane];
+            if (pp >= 0) dst[pp] = keep;
+        }
+    }
+}
+
+constexpr int EHH_ST = 256;          // threads of a refinement workgroup
+constexpr int EHH_GRP = 4;           // 64-site blocks tested per barrier while nothing differs
+constexpr uint32_t EHH_NONE = 0xFFFFFFFFu;
+constexpr uint32_t EHH_NEWID = 0x80000000u;  // tmp[c] holds the id of the class split off c
+constexpr uint16_t EHH_MOVER = 0x8000u, EHH_LEADER = 0x4000u, EHH_LABEL = 0x0FFFu;  // label bits (ids < 4096)
+static_assert(IMPOP_EHH_SCAN_MAX_N <= EHH_LABEL + 1u, "class ids must fit the label bits");
+
+__device__ inline long long ehh_milli(unsigned long long total, unsigned long long broken, double denom) {
+    return llrint(1000.0 * py_round((double)(total - broken) / denom, 3));  // the double ehh_finalize_kernel writes, in thousandths
+}
+
+// workgroup minimum; slots alternate so that one barrier per call suffices
+__device__ inline uint32_t ehh_block_min(uint32_t v, uint32_t (*slots)[EHH_ST / 64], uint32_t &par) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, off, 64));
+    if ((threadIdx.x & 63) == 0) slots[par][threadIdx.x >> 6] = v;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < EHH_ST / 64; ++k) v = min(v, slots[par][k]);
+    par ^= 1u;
+    return v;
+}
+
+// grid = 4 problems per window: blockIdx.x = 4 * window + 2 * allele + half.  Dynamic LDS: 12 bytes x mcap (|P| rounded up
+// to even): tmp u32 | size u16 | row u16 | label u16 | rep u16.
+//   row[i]    position in P of member i (ascending)          label[i]  class of member i (+ the two step flags)
+//   rep[c]    member that represents class c (never moves)   size[c]   members of class c (u16 halves of u32 atomics)
+//   tmp[c]    during a step: smallest mover of c, then the id split off c; tmp[new id] = c; EHH_NONE between steps
+__global__ __launch_bounds__(EHH_ST) void ehh_refine_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
+                                                            const EhhWin *__restrict__ win, const uint32_t *__restrict__ idx, uint32_t nP,
+                                                            uint32_t mcap, int flanks, uint32_t ref_hap, const uint64_t *__restrict__ wm,
+                                                            uint32_t stride, impop_ehh_stats *__restrict__ rec, uint32_t *__restrict__ err) {
+    extern __shared__ uint32_t ehh_lds[];
+    uint32_t *tmp = ehh_lds;
+    uint32_t *size32 = tmp + mcap;
+    uint16_t *size = reinterpret_cast<uint16_t *>(size32);
+    uint16_t *row = size + mcap, *label = row + mcap, *rep = label + mcap;
+    __shared__ uint32_t s_slots[2][EHH_ST / 64];
+    __shared__ uint32_t s_ncls;
+    __shared__ unsigned long long s_broken, s_chk;
+    const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t wi = blockIdx.x >> 2, a = (blockIdx.x >> 1) & 1u, half = blockIdx.x & 1u;
+    const EhhWin w = win[wi];
+    const uint64_t cb = w.core >> 6;
+    const uint32_t cl = (uint32_t)(w.core & 63);
+
+    // members of P carrying allele a at the core, in ascending order
+    uint32_t m = 0;
+    for (uint32_t base = 0; base < nP; base += EHH_ST) {
+        const uint32_t j = base + tid;
+        bool f = false;
+        if (j < nP) {
+            const uint32_t hp = idx[j];
+            f = ((sb[sb_index(wps, G, r, cb, cl, hp >> 5)] >> (hp & 31)) & 1u) == a;
+        }
+        const uint64_t bal = __ballot(f);
+        if (lane == 0) s_slots[0][wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t off = m, tot = 0;
+#pragma unroll
+        for (int k = 0; k < EHH_ST / 64; ++k) {
+            if ((uint32_t)k < wave) off += s_slots[0][k];
+            tot += s_slots[0][k];
+        }
+        if (f) row[off + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull))] = (uint16_t)j;
+        m += tot;
+        __syncthreads();
+    }
+
+    // the half's sites [rb, re) and direction
+    const bool reverse = half == 0;
+    const bool right = half == 1 || flanks == IMPOP_EHH_FLANKS_REFERENCE;
+    const uint64_t rb = right ? w.core + 1 : w.begin, re = right ? w.end : w.core;
+    const uint64_t W = re - rb;
+    if (tid == 0) {
+        if (half == 0) {
+            rec[wi].n_members[a] = m;
+            rec[wi].area[a] = 0.0;  // the host fills it in from both halves
+        }
+        if ((blockIdx.x & 3u) == 0) {
+            rec[wi].ref_allele = (sb[sb_index(wps, G, r, cb, cl, ref_hap >> 5)] >> (ref_hap & 31)) & 1u;
+            rec[wi].reserved = 0;
+        }
+    }
+    if (m < 2 || W == 0) {  // ehhgfa.py:17-18: one member -> 500 at every site; nobody, or no site -> 0
+        if (tid == 0) rec[wi].area_milli[a][half] = (m == 1) ? (long long)(500000ull * W) : 0ll;
+        return;
+    }
+
+    for (uint32_t i = tid; i < m; i += EHH_ST) {
+        tmp[i] = EHH_NONE;
+        size[i] = 0;
+        label[i] = 0;
+        rep[i] = 0;
+    }
+    if (tid == 0) {
+        s_ncls = 1;
+        s_broken = 0;
+        s_chk = 0;
+    }
+    __syncthreads();
+    if (tid == 0) size32[0] = m;  // size[0] = m (<= 4096), size[1] = 0
+    __syncthreads();
+
+    const unsigned long long total = (unsigned long long)m * (m - 1) / 2;
+    const double denom = (double)((unsigned long long)m * (m - 1)) / 2.0;  // as ehh_finalize_kernel
+    long long area = 0, k = ehh_milli(total, 0, denom);                    // thread 0's run-length sum
+    uint64_t last = 0;                                                     // walking index up to which `area` is summed
+    const uint64_t b_lo = rb >> 6, b_hi = (re - 1) >> 6, nb = b_hi - b_lo + 1;
+    const uint64_t *wbase = wm + w.woff;
+    uint32_t par = 1;
+    bool done = false;
+    for (uint64_t u = 0; u < nb && !done; u += EHH_GRP) {
+        const uint32_t g = nb - u < (uint64_t)EHH_GRP ? (uint32_t)(nb - u) : (uint32_t)EHH_GRP;
+        // the common case: no member differs from its representative anywhere in these blocks
+        uint64_t acc = 0;
+        for (uint32_t i = tid; i < m; i += EHH_ST) {
+            const uint32_t ri = row[i], rr = row[rep[label[i]]];
+            if (ri == rr) continue;
+            for (uint32_t j = 0; j < g; ++j) {
+                const uint64_t B = reverse ? b_hi - (u + j) : b_lo + (u + j);
+                const uint64_t *p = wbase + (B - w.tblk0) * stride;
+                uint64_t x = p[ri] ^ p[rr];
+                if (B == b_lo) x &= ~0ull << (rb & 63);
+                if (B == b_hi && (re & 63)) x &= (1ull << (re & 63)) - 1ull;
+                acc |= x;
+            }
+        }
+        if (!__syncthreads_or(acc != 0)) continue;
+        for (uint32_t j = 0; j < g && !done; ++j) {
+            const uint64_t B = reverse ? b_hi - (u + j) : b_lo + (u + j);
+            const uint64_t *p = wbase + (B - w.tblk0) * stride;
+            uint64_t mask = ~0ull;  // sites of the block inside the range and not yet walked
+            if (B == b_lo) mask &= ~0ull << (rb & 63);
+            if (B == b_hi && (re & 63)) mask &= (1ull << (re & 63)) - 1ull;
+            while (mask) {
+                // nearest differing site in walking direction
+                uint32_t q = 64;
+                for (uint32_t i = tid; i < m; i += EHH_ST) {
+                    const uint32_t ri = row[i], rr = row[rep[label[i]]];
+                    const uint64_t x = (p[ri] ^ p[rr]) & mask;
+                    if (x) q = min(q, (uint32_t)(reverse ? __builtin_clzll(x) : __builtin_ctzll(x)));
+                }
+                q = ehh_block_min(q, s_slots, par);
+                if (q == 64) break;
+                const uint32_t sbit = reverse ? 63 - q : q;
+                // movers: members that differ from their representative at this site; the smallest leads the new class
+                for (uint32_t i = tid; i < m; i += EHH_ST) {
+                    const uint32_t c = label[i];
+                    const uint32_t ri = row[i], rr = row[rep[c]];
+                    if (((p[ri] ^ p[rr]) >> sbit) & 1ull) {
+                        label[i] = (uint16_t)(c | EHH_MOVER);
+                        atomicMin(&tmp[c], i);
+                    }
+                }
+                __syncthreads();
+                for (uint32_t i = tid; i < m; i += EHH_ST) {
+                    const uint32_t l = label[i];
+                    if (!(l & EHH_MOVER)) continue;
+                    const uint32_t c = l & EHH_LABEL;
+                    if (tmp[c] == i) {  // other movers of c see the smallest mover or the flagged id, never their own index
+                        const uint32_t id = atomicAdd(&s_ncls, 1u);
+                        rep[id] = (uint16_t)i;
+                        tmp[id] = c;
+                        tmp[c] = EHH_NEWID | id;
+                        label[i] = (uint16_t)(l | EHH_LEADER);
+                    }
+                }
+                __syncthreads();
+                for (uint32_t i = tid; i < m; i += EHH_ST) {
+                    const uint32_t l = label[i];
+                    if (!(l & EHH_MOVER)) continue;
+                    const uint32_t c = l & EHH_LABEL, id = tmp[c] & ~EHH_NEWID;
+                    atomicSub(&size32[c >> 1], (c & 1u) ? 0x10000u : 1u);
+                    atomicAdd(&size32[id >> 1], (id & 1u) ? 0x10000u : 1u);
+                    label[i] = (uint16_t)(id | (l & EHH_LEADER));
+                }
+                __syncthreads();
+                unsigned long long br = 0;
+                for (uint32_t i = tid; i < m; i += EHH_ST) {
+                    const uint32_t l = label[i];
+                    if (!(l & EHH_LEADER)) continue;
+                    const uint32_t id = l & EHH_LABEL, c = tmp[id];
+                    br += (unsigned long long)size[id] * size[c];  // pairs between the movers and those that stay
+                    tmp[id] = EHH_NONE;
+                    tmp[c] = EHH_NONE;
+                    label[i] = (uint16_t)id;
+                }
+                if (br) atomicAdd(&s_broken, br);
+                __syncthreads();
+                const unsigned long long broken = s_broken;
+                if (tid == 0) {
+                    const uint64_t site = B * 64 + sbit, pos = reverse ? re - 1 - site : site - rb;
+                    area += (long long)(pos - last) * k;
+                    last = pos;
+                    k = ehh_milli(total, broken, denom);
+                }
+                if (broken == total) {  // every class is a single member: the curve stays at its last value
+                    done = true;
+                    break;
+                }
+                mask &= reverse ? ((1ull << sbit) - 1ull) : (sbit == 63 ? 0ull : ~0ull << (sbit + 1));
+            }
+        }
+    }
+    // consistency: the classes that are left account for exactly the pairs that never broke
+    unsigned long long chk = 0;
+    const uint32_t ncls = s_ncls;
+    for (uint32_t c = tid; c < ncls && c < m; c += EHH_ST) chk += (unsigned long long)size[c] * (size[c] - 1u) / 2;
+    chk = wave_sum_u64(chk);
+    if (lane == 0 && chk) atomicAdd(&s_chk, chk);
+    __syncthreads();
+    if (tid == 0) {
+        area += (long long)(W - last) * k;
+        rec[wi].area_milli[a][half] = area;
+        if (s_chk != total - s_broken || ncls > m) atomicOr(err, DEV_ERR_EHH);
+    }
+}
+
 }  // namespace impop
 
 using namespace impop;
@@ -153,5 +418,138 @@ IMPOP_API int impop_ehh(impop_ctx *ctx, const impop_matrix *m, uint64_t site_beg
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(ehh_out_host, d_out, W * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_ehh_window *windows, uint64_t n_windows,
+                             const uint64_t *mask_p, const impop_ehh_params *params, impop_ehh_stats *out_host) {
+    static_assert(sizeof(impop_ehh_stats) == 64 && sizeof(impop_ehh_window) == 24 && sizeof(impop_ehh_params) == 24, "ABI layout");
+    REQUIRE(ctx && m && params, "impop_ehh_scan: NULL argument");
+    REQUIRE(params->struct_size == sizeof(impop_ehh_params), "impop_ehh_params.struct_size mismatch");
+    NOT_COMPACT(m, "impop_ehh_scan");
+    REQUIRE(params->flanks == IMPOP_EHH_FLANKS_REFERENCE || params->flanks == IMPOP_EHH_FLANKS_TWO_SIDED,
+            "impop_ehh_scan: unknown flanks mode %d", params->flanks);
+    const uint32_t n = m->g.n_hap, n_pad = m->g.wps * 32;
+    REQUIRE(params->ref_hap < n, "impop_ehh_scan: ref_hap %u is not one of the %u haplotypes", params->ref_hap, n);
+    std::vector<uint32_t> idx;
+    std::vector<int32_t> ppos(n_pad, -1);
+    for (uint32_t i = 0; i < n; ++i)
+        if (!mask_p || ((mask_p[i >> 6] >> (i & 63)) & 1ull)) {
+            ppos[i] = (int32_t)idx.size();
+            idx.push_back(i);
+        }
+    const uint32_t nP = (uint32_t)idx.size();
+    if (nP > IMPOP_EHH_SCAN_MAX_N) {
+        set_error("impop_ehh_scan: %u members exceed the LDS-resident refinement limit (%u); impop_ehh takes one window of up to 65535",
+                  nP, (uint32_t)IMPOP_EHH_SCAN_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_host, "impop_ehh_scan: NULL windows/out");
+    for (uint64_t i = 0; i < n_windows; ++i)
+        REQUIRE(windows[i].site_begin <= windows[i].core_site && windows[i].core_site < windows[i].site_end &&
+                    windows[i].site_end <= m->g.n_site,
+                "impop_ehh_scan: window %llu: bad range [%llu,%llu) or core %llu for %llu sites", (unsigned long long)i,
+                (unsigned long long)windows[i].site_begin, (unsigned long long)windows[i].site_end,
+                (unsigned long long)windows[i].core_site, (unsigned long long)m->g.n_site);
+    HIP_TRY(hipSetDevice(ctx->device));
+    static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
+
+    // the windows' transposed blocks and the chunks they fall into (by scratch bytes; blockIdx.y holds 65535 windows)
+    const uint32_t stride = nP ? nP : 1;
+    const uint64_t budget = params->max_chunk_bytes ? params->max_chunk_bytes : (1ull << 30);
+    std::vector<EhhWin> meta(n_windows);
+    std::vector<uint64_t> chunk_begin{0};
+    uint64_t used = 0, max_words = 0, max_cnt = 0;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        const impop_ehh_window &wv = windows[i];
+        const uint64_t tb = params->flanks == IMPOP_EHH_FLANKS_REFERENCE ? wv.core_site + 1 : wv.site_begin, te = wv.site_end;
+        const uint64_t nblk = (nP && te > tb) ? ((te + 63) >> 6) - (tb >> 6) : 0;
+        REQUIRE(nblk < 0x7FFFFFFFull, "impop_ehh_scan: window %llu too long", (unsigned long long)i);
+        const uint64_t words = nblk * stride;
+        if (i > chunk_begin.back() && ((used + words) * 8 > budget || i - chunk_begin.back() == 65535)) {
+            chunk_begin.push_back(i);
+            used = 0;
+        }
+        meta[i] = EhhWin{wv.site_begin, wv.site_end, wv.core_site, used, tb >> 6, (uint32_t)nblk, 0};
+        used += words;
+        max_words = std::max(max_words, used);
+        max_cnt = std::max(max_cnt, i + 1 - chunk_begin.back());
+    }
+    chunk_begin.push_back(n_windows);
+    REQUIRE(max_words * 8 <= (64ull << 30), "impop_ehh_scan: a window needs %llu MiB of transposed scratch",
+            (unsigned long long)(max_words >> 17));
+
+    // device: idx | ppos | chunk windows | chunk records | transposed words; the first four mirrored in page-locked staging
+    const size_t o_idx = 0, o_ppos = o_idx + round_up_256((size_t)stride * 4), o_win = o_ppos + round_up_256((size_t)n_pad * 4),
+                 o_rec = o_win + round_up_256(max_cnt * sizeof(EhhWin)), o_wm = o_rec + round_up_256(max_cnt * sizeof(impop_ehh_stats));
+    const size_t scratch_bytes = o_wm + (size_t)max_words * 8 + 256;
+    void *d = nullptr, *pin = nullptr;
+    int rc = ctx_scratch(ctx, scratch_bytes, &d);
+    if (rc) return rc;
+    rc = ctx_pinned(ctx, o_wm, &pin);
+    if (rc) return rc;
+    char *dc = (char *)d, *hc = (char *)pin;
+    if (nP) memcpy(hc + o_idx, idx.data(), (size_t)nP * 4);
+    memcpy(hc + o_ppos, ppos.data(), (size_t)n_pad * 4);
+    HIP_TRY(hipMemcpyAsync(dc, hc, o_win, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t mcap = (nP + 1) & ~1u;
+    const size_t lds = (size_t)(mcap ? mcap : 2) * 12;
+
+    for (size_t c = 0; c + 1 < chunk_begin.size(); ++c) {
+        const uint64_t base = chunk_begin[c], cnt = chunk_begin[c + 1] - base;
+        uint32_t max_blk = 0;
+        uint64_t words = 0;
+        for (uint64_t k = 0; k < cnt; ++k) {
+            max_blk = std::max(max_blk, meta[base + k].n_blk);
+            words += (uint64_t)meta[base + k].n_blk * stride;
+        }
+        memcpy(hc + o_win, &meta[base], cnt * sizeof(EhhWin));
+        HIP_TRY(hipMemcpyAsync(dc + o_win, hc + o_win, cnt * sizeof(EhhWin), hipMemcpyHostToDevice, ctx->stream));
+        hipEvent_t ev1 = nullptr;
+        if (ctx->gram_timing) {  // the chunk's kernels between two events of their own: impop_ctx_ehh_elapsed
+            if (ctx->ehh_events_used == ctx->ehh_events.size()) {
+                hipEvent_t a, b;
+                HIP_TRY(hipEventCreate(&a));
+                HIP_TRY(hipEventCreate(&b));
+                ctx->ehh_events.push_back({a, b});
+            }
+            HIP_TRY(hipEventRecord(ctx->ehh_events[ctx->ehh_events_used].first, ctx->stream));
+            ev1 = ctx->ehh_events[ctx->ehh_events_used].second;
+        }
+        uint32_t launches = 0;
+        if (max_blk) {
+            hipLaunchKernelGGL(ehh_scan_transpose_kernel, dim3((max_blk + 3) / 4, (uint32_t)cnt), dim3(256), 0, ctx->stream, m->d_sb,
+                               m->g.wps, m->g.G, m->g.r, (const EhhWin *)(dc + o_win), (const int32_t *)(dc + o_ppos), stride,
+                               (uint64_t *)(dc + o_wm));
+            ++launches;
+        }
+        hipLaunchKernelGGL(ehh_refine_kernel, dim3((uint32_t)(cnt * 4)), dim3(EHH_ST), lds, ctx->stream, m->d_sb, m->g.wps, m->g.G,
+                           m->g.r, (const EhhWin *)(dc + o_win), (const uint32_t *)(dc + o_idx), nP, mcap, params->flanks,
+                           params->ref_hap, (const uint64_t *)(dc + o_wm), stride, (impop_ehh_stats *)(dc + o_rec), ctx->d_err);
+        ++launches;
+        HIP_TRY(hipGetLastError());
+        if (ev1) {
+            HIP_TRY(hipEventRecord(ev1, ctx->stream));
+            ctx->ehh_events_used++;
+        }
+        if (trace) {
+            fprintf(stderr, "[impop_ehh_scan] windows=%llu problems=%llu chunk=%llu launches=%u scratch_bytes=%llu\n",
+                    (unsigned long long)cnt, (unsigned long long)(cnt * 4), (unsigned long long)c, launches, (unsigned long long)(words * 8));
+            fflush(stderr);
+        }
+        HIP_TRY(hipMemcpyAsync(hc + o_rec, dc + o_rec, cnt * sizeof(impop_ehh_stats), hipMemcpyDeviceToHost, ctx->stream));
+        rc = ctx_err_fetch(ctx);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging is reused by the next chunk
+        rc = ctx_err_result(ctx, "impop_ehh_scan");
+        if (rc) return rc;
+        const impop_ehh_stats *rv = (const impop_ehh_stats *)(hc + o_rec);
+        for (uint64_t k = 0; k < cnt; ++k) {
+            impop_ehh_stats o = rv[k];
+            for (int a = 0; a < 2; ++a) o.area[a] = (double)(o.area_milli[a][0] + o.area_milli[a][1]) / 1000.0;
+            out_host[base + k] = o;
+        }
+    }
     return IMPOP_OK;
 }

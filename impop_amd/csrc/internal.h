@@ -116,6 +116,9 @@ struct impop_ctx {
     // the same switch also brackets the clustering kernel(s) of impop_cluster_scan (impop_ctx_cluster_elapsed)
     std::vector<std::pair<hipEvent_t, hipEvent_t>> cluster_events;
     size_t cluster_events_used = 0;
+    // ... and the kernels of every chunk of impop_ehh_scan (impop_ctx_ehh_elapsed)
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> ehh_events;
+    size_t ehh_events_used = 0;
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
     // all-pairs path run next to each other instead of one after the other
     hipStream_t side = nullptr;
@@ -207,6 +210,7 @@ int ctx_err_fetch(impop_ctx *ctx);                 // enqueue its copy to the ho
 int ctx_err_result(impop_ctx *ctx, const char *fn);  // after that sync: IMPOP_OK, or IMPOP_E_INTERNAL (word cleared, message set)
 constexpr uint32_t DEV_ERR_GROUPING = 1u;            // greedy_groups_bits ran out of its progress bound
 constexpr uint32_t DEV_ERR_CLUSTER = 2u;             // af label propagation ran out of its rounds
+constexpr uint32_t DEV_ERR_EHH = 4u;                 // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // pairwise.hip: build (once) the bitmap of the sites that segregate among all haplotypes, m->d_segmap
 int ensure_segmap(impop_ctx *ctx, const impop_matrix *m);

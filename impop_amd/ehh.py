@@ -1,5 +1,6 @@
 """GPU-backed mirror of the reference's EHH scripts (scripts/wip/ehhgfa.py, ehh2.py): calc_EHH and
-the fixed-width window loop of ehhgfa.main.  The pair work runs in libimpop_hip.so (impop_ehh)."""
+the fixed-width window loop of ehhgfa.main.  The pair work runs in libimpop_hip.so (impop_ehh); scan_matrix runs the
+same loop as one batch (impop_ehh_scan) and returns the integrals in exact thousandths."""
 from __future__ import annotations
 
 import numpy as np
@@ -85,3 +86,47 @@ def scan_windows(whole, test_snp: int, window_size: int, refpos: int, ctx=None):
             name += 1
     finally:
         bm.free()
+
+
+def window_list(n_col: int, window_size: int, test_snp: int):
+    """The windows ehhgfa.main walks over `n_col` columns (ehhgfa.py:44-70), without touching any data:
+    -> [(window_name, colstart, colend, site_end, core_site)], colend = colstart + window_size as the reference prints it,
+    site_end = colend cut at n_col, core_site = colstart + test_snp - 1.  Raises what the reference raises, for the first
+    window that does: IndexError 'index t is out of bounds for axis 1 with size k' for a (last, cut) window without the
+    test column (ehhgfa.py:53), and 'index -1 is out of bounds for axis 0 with size 0' for a test column that is the
+    window's last, whose empty right flank has no integral (ehhgfa.py:64)."""
+    if test_snp < 1:
+        raise ValueError("-p is the 1-based position of the test SNP in the window (>= 1)")
+    if window_size < 1:
+        raise ValueError("-w must be a positive number of columns")
+    t = test_snp - 1
+    out, name, colstart = [], 1, 0
+    while colstart < n_col:
+        colend = colstart + window_size
+        hi = min(colend, n_col)
+        if t >= hi - colstart:
+            raise IndexError(f"index {t} is out of bounds for axis 1 with size {hi - colstart}")
+        if colstart + t + 1 == hi:
+            raise IndexError("index -1 is out of bounds for axis 0 with size 0")
+        out.append((name, colstart, colend, hi, colstart + t))
+        colstart = colend
+        name += 1
+    return out
+
+
+def scan_matrix(bm, window_size: int, test_snp: int, refpos: int, n_col=None):
+    """ehhgfa.main's loop (ehhgfa.py:40-69) on a resident matrix as ONE impop_ehh_scan call: -> rows (window_name, colstart,
+    colend, allele, 'REF'|'ALT', area_milli, area) for the alleles present at each window's test SNP, allele 0 first as
+    np.unique orders them.  area_milli is the reference's area in exact thousandths (the reference's own fp64 cumsum
+    differs from area = area_milli / 1000 by rounding only); the drop-in CLI and scan_windows, which print the cumsum's
+    repr, stay on the per-window path."""
+    n_col = bm.n_site if n_col is None else int(n_col)
+    wl = window_list(n_col, window_size, test_snp)
+    rec = bm.ehh_scan([(w[1], w[3]) for w in wl], [w[4] for w in wl], ref_hap=(refpos - 1) % bm.n_hap, flanks="reference")
+    rows = []
+    for (name, colstart, colend, _, _), r in zip(wl, rec):
+        for al in (0, 1):
+            if r["n_members"][al]:
+                milli = int(r["area_milli"][al].sum())
+                rows.append((name, colstart, colend, al, "REF" if al == int(r["ref_allele"]) else "ALT", milli, float(r["area"][al])))
+    return rows

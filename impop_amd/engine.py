@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -30,6 +30,12 @@ assert PAIRWISE_DTYPE.itemsize == 96
 CLUSTER_DTYPE = np.dtype([("n_members", "<u4"), ("n_clusters", "<u4"), ("largest", "<u4"), ("n_singletons", "<u4"), ("sum_sq", "<u8"),
                           ("n_sites", "<u4"), ("reserved", "<u4")])
 assert CLUSTER_DTYPE.itemsize == 32
+
+EHH_DTYPE = np.dtype([("n_members", "<u4", (2,)), ("ref_allele", "<u4"), ("reserved", "<u4"), ("area_milli", "<i8", (2, 2)),
+                      ("area", "<f8", (2,))])
+assert EHH_DTYPE.itemsize == 64
+EHH_WINDOW_DTYPE = np.dtype([("site_begin", "<u8"), ("site_end", "<u8"), ("core_site", "<u8")])
+EHH_FLANKS = {"reference": _lib.EHH_FLANKS_REFERENCE, "two-sided": _lib.EHH_FLANKS_TWO_SIDED}
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 
@@ -165,6 +171,12 @@ class Context:
         """-> (summed clustering-kernel ms of cluster_scan, chunks) since gram_timing(True)"""
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_cluster_elapsed(self.handle, C.byref(t), C.byref(k)))
+        return t.value, k.value
+
+    def ehh_elapsed(self):
+        """-> (summed kernel ms of ehh_scan, chunks) since gram_timing(True)"""
+        t, k = C.c_double(), C.c_uint64()
+        check(self._lib.impop_ctx_ehh_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
 
     def close(self) -> None:
@@ -556,6 +568,31 @@ class BitMatrix:
                                                cl.ctypes.data_as(u32p) if want_members else None,
                                                sz.ctypes.data_as(u32p) if want_members else None))
         return (out, cl, sz) if want_members else out
+
+    def ehh_scan(self, windows, cores, mask=None, ref_hap: int = 0, flanks: str = "reference", max_chunk_bytes: int = 0) -> np.ndarray:
+        """Integrated EHH per core site (impop_ehh_scan; the area of scripts/wip/ehhgfa.py:63) for a batch of windows:
+        windows = (site_begin, site_end) rows, cores = one site per window inside it.  For the members of `mask` carrying
+        allele a at the core, area_milli[a][h] = sum over the half's sites of 1000 * EHH, exact; flanks 'reference' takes both
+        halves from (core, end) like ehhgfa.py:56-61, 'two-sided' half 0 from [begin, core) walking away from the core.
+        -> records (EHH_DTYPE)."""
+        wv = np.asarray(windows)
+        cv = np.asarray(cores, dtype=np.int64).ravel()
+        if wv.dtype.names:
+            be = np.stack([wv["site_begin"], wv["site_end"]], axis=1)
+        else:
+            be = wv.reshape(-1, wv.shape[-1] if wv.ndim > 1 else 2)[:, :2] if wv.size else np.zeros((0, 2), np.int64)
+        if len(be) != len(cv):
+            raise ValueError(f"{len(be)} windows but {len(cv)} cores")
+        if len(be) and (np.asarray(be).astype(np.int64).min() < 0 or cv.min() < 0):
+            raise ValueError("negative site index")
+        w = np.zeros(len(be), dtype=EHH_WINDOW_DTYPE)
+        w["site_begin"], w["site_end"], w["core_site"] = be[:, 0], be[:, 1], cv
+        out = np.zeros(len(w), dtype=EHH_DTYPE)
+        prm = EhhParams(C.sizeof(EhhParams), EHH_FLANKS[flanks], int(ref_hap), 0, int(max_chunk_bytes))
+        keep, ptr = _mask_ptr(mask, self.n_hap)
+        check(self.ctx._lib.impop_ehh_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(EhhWindow)), len(w), ptr,
+                                           C.byref(prm), out.ctypes.data_as(C.POINTER(EhhStats))))
+        return out
 
 
 class ScanPlan:

@@ -269,6 +269,47 @@ int impop_site_counts(impop_ctx *ctx, const impop_matrix *m, const uint64_t *mas
 int impop_ehh(impop_ctx *ctx, const impop_matrix *m, uint64_t site_begin, uint64_t site_end, const uint64_t *mask,
               int reverse, double *ehh_out_host, uint32_t *n_members);
 
+/* Integrated EHH per core site for a batch of windows (the scan of scripts/wip/ehhgfa.py:40-69, which keeps only the
+ * integral of each curve, :63).  Every (window, allele a, half h) is one calc_EHH problem: its members are the haplotypes
+ * of P (mask_p, NULL = all) whose bit at core_site equals a, its sites and direction are
+ *     flanks REFERENCE: half 0 = (core, end) walked backwards from end - 1, half 1 = (core, end) walked forwards
+ *     flanks TWO_SIDED: half 0 = [begin, core) walked backwards from core - 1, half 1 = (core, end) walked forwards
+ * and EHH[i] is exactly the double impop_ehh returns for that range, members and direction: k / 1000 for an integer k.
+ * area_milli is the sum of those k over the half's sites - an integer, so no summation order enters and chunking never
+ * changes a record - and area[a] = (area_milli[a][0] + area_milli[a][1]) / 1000.0.  A problem with one member counts
+ * 500 000 per site (ehhgfa.py:17-18), one without members 0 (n_members 0), an empty flank 0.
+ * |P| <= IMPOP_EHH_SCAN_MAX_N: a problem's class labels, representatives and sizes (12 bytes per member) stay in the LDS
+ * of its workgroup; a larger |P| returns IMPOP_E_UNSUPPORTED (impop_ehh takes up to 65535 members).  A compacted matrix
+ * returns IMPOP_E_UNSUPPORTED; a core outside its window, a window outside the matrix or ref_hap >= n_hap return
+ * IMPOP_E_INVALID; all of these before anything is uploaded or launched.  Windows may overlap or repeat with other cores.
+ * Two kernel launches per chunk of windows whatever their number (a chunk holds up to max_chunk_bytes of transposed
+ * window words, at most 65535 windows); checks the device error word like impop_pairwise_scan. */
+#define IMPOP_EHH_SCAN_MAX_N 4096u
+typedef struct impop_ehh_window {
+    uint64_t site_begin, site_end, core_site;  /* core in [begin, end) */
+} impop_ehh_window;
+#define IMPOP_EHH_FLANKS_REFERENCE 0 /* both halves from the right flank (core, end): ehhgfa.py:56-61 */
+#define IMPOP_EHH_FLANKS_TWO_SIDED 1 /* half 0 = [begin, core) walking away from the core, half 1 = (core, end) */
+typedef struct impop_ehh_params {
+    uint32_t struct_size;
+    int32_t flanks;           /* IMPOP_EHH_FLANKS_* */
+    uint32_t ref_hap;         /* haplotype whose core allele is reported as ref_allele (ehhgfa.py:52) */
+    uint32_t reserved;
+    uint64_t max_chunk_bytes; /* 0 = default (1 GiB); tests use it to force several chunks */
+} impop_ehh_params;
+typedef struct impop_ehh_stats { /* 64 bytes, fixed layout */
+    uint32_t n_members[2];       /* members of P carrying allele 0 / 1 at the core site */
+    uint32_t ref_allele;         /* allele of haplotype ref_hap at the core; REF / ALT is the caller's label */
+    uint32_t reserved;
+    int64_t area_milli[2][2];    /* [allele][half]: sum over the half's sites of 1000 * EHH[i], exact */
+    double area[2];              /* (area_milli[a][0] + area_milli[a][1]) / 1000.0 */
+} impop_ehh_stats;
+int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_ehh_window *windows, uint64_t n_windows,
+                   const uint64_t *mask_p, const impop_ehh_params *params, impop_ehh_stats *out_host);
+/* With impop_ctx_gram_timing on, impop_ehh_scan brackets the kernels of every chunk: their summed time and the number
+ * of chunks since enable / reset. */
+int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
+
 /* Device address of the plan's internal record buffer (n_windows x impop_window_stats, written by launches
  * with d_out == NULL): what a caller hands to impop_gather_records without owning any device memory itself. */
 int impop_scan_plan_device_records(impop_scan_plan *plan, void **d_records);

@@ -10,6 +10,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr1.npz chr2.npz ... --bed genome.bed --format all ...            # one matrix per chromosome
     impop_scan.py --sim-list windows.tsv --format pica2 -t 0.999 -r 5                         # one `.sim` table per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format af [-t 1.0] [-u subset.txt] [--af-clusters c.tsv] [--af-details d.tsv]
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format ehh [--ehh-core-offset N | --ehh-cores pos.txt] [--ehh-flanks two-sided]
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
 window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
@@ -31,6 +32,15 @@ the sequences of -u (default: all).  Main table REGION LENGTH THRESHOLD HAPLOTYP
 (homozygosity = sum of squared cluster frequencies, "%.6f" like af.py:60); --af-clusters FILE gets af.py's summary rows and
 --af-details FILE its per-sample rows, each behind a REGION column.  One process, one GPU; not with --sim-list.  Sequence names
 are cut at the first ':' as af.py cuts them and must then be distinct (af.py would merge two rows of one name into one sample).
+
+--format ehh (scripts/wip/ehhgfa.py's scan, impop_ehh_scan): every BED row is a window with one core site, --ehh-core-offset N
+(0-based site offset into the window; default its midpoint (end - begin) // 2) or --ehh-cores FILE (one bp position per BED row,
+blank / # lines skipped; the first site at or right of it is the core).  One row per allele present at the core among the sequences
+of -u (default: all): REGION LENGTH CORE ALLELE REF_ALT N_HAPLOTYPES AREA IHH_LEFT IHH_RIGHT.  CORE is the core site's bp position,
+REF_ALT compares the allele with that of --ehh-ref NAME (default: the matrix's first sequence), IHH_LEFT / IHH_RIGHT are the integrals
+of the two halves' EHH curves in sites and AREA their sum, all three exact thousandths printed as integer.milli ("12.276").
+--ehh-flanks reference (default) takes both halves from the sites right of the core like ehhgfa.py:56-61, two-sided the left half
+from the sites left of it.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --compact, --devices N, -t / -r.
 
 A threshold >= 1 without rounding on the `match` identity is the streaming site-count scan (every haplotype its own
 group: exact integer identities); anything else runs the all-pairs path (impop_pairwise_scan).
@@ -268,6 +278,57 @@ def af_refusal(args):
     return None
 
 
+EHH_HEADER = "REGION\tLENGTH\tCORE\tALLELE\tREF_ALT\tN_HAPLOTYPES\tAREA\tIHH_LEFT\tIHH_RIGHT"
+
+
+def ehh_refusal(args):
+    """what --format ehh does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "ehh":
+        if args.ehh_core_offset is not None or args.ehh_cores or args.ehh_flanks is not None or args.ehh_ref is not None:
+            return "--ehh-core-offset / --ehh-cores / --ehh-flanks / --ehh-ref belong to --format ehh"
+        return None
+    if args.sim_list:
+        return "--format ehh scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format ehh is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format ehh runs on one GPU: not with --devices N"
+    if args.panel or args.pop_a or args.pop_b or args.sample_list or args.compact:
+        return "--format ehh scans the sequences of -u (default: all) on the full matrix: not with -A / -B / --panel / -l / --compact"
+    if args.ehh_core_offset is not None and args.ehh_cores:
+        return "give --ehh-core-offset or --ehh-cores, not both"
+    if args.ehh_core_offset is not None and args.ehh_core_offset < 0:
+        return "--ehh-core-offset is a 0-based offset into the window (>= 0)"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    return None
+
+
+def milli_text(k):
+    """exact thousandths as text: 12276 -> '12.276'"""
+    k = int(k)
+    return f"{k // 1000}.{k % 1000:03d}"
+
+
+def ehh_rows(region, length, core_bp, rec):
+    """the rows of --format ehh for one impop_ehh_stats record: one per allele present"""
+    out = []
+    for al in (0, 1):
+        n = int(rec["n_members"][al])
+        if n:
+            left, right = int(rec["area_milli"][al][0]), int(rec["area_milli"][al][1])
+            out.append(f"{region}\t{length}\t{core_bp}\t{al}\t{'REF' if al == int(rec['ref_allele']) else 'ALT'}\t{n}\t"
+                       f"{milli_text(left + right)}\t{milli_text(left)}\t{milli_text(right)}")
+    return out
+
+
+def read_core_positions(path):
+    with open(path) as f:
+        return [int(line.split()[0]) for line in f if line.strip() and not line.lstrip().startswith("#")]
+
+
 def write_af_table(out, regions, L_col, thr_txt, recs):
     """the main table of --format af from impop_cluster_stats records (one per region)"""
     print(AF_HEADER, file=out)
@@ -427,11 +488,17 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
-                         "(scripts/af.py; not part of `all`)")
+                         "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
+    ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
+                    "(default: the window's midpoint)")
+    ap.add_argument("--ehh-cores", metavar="FILE", help="ehh: one core position (bp) per BED row instead of an offset")
+    ap.add_argument("--ehh-flanks", choices=["reference", "two-sided"], default=None, help="ehh: reference (default) = both halves from "
+                    "the sites right of the core (ehhgfa.py:56-61); two-sided = the left half from the sites left of it")
+    ap.add_argument("--ehh-ref", metavar="NAME", default=None, help="ehh: the sequence whose core allele is REF (default: the first)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="hfst: K >= 2 disjoint population lists; every pair "
                     "in ONE pass (replaces run_h_fst_panels.sh); one table per pair, labelled POP_A-vs-POP_B")
@@ -462,7 +529,7 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = af_refusal(args)
+    refusal = af_refusal(args) or ehh_refusal(args)
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
@@ -544,8 +611,12 @@ def main():
         print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
         sys.exit(2)
     bed = read_bed(args.bed, fmt)
-    rows, per_mat = [], {}
-    for chrom, s, e in bed:
+    rows, per_mat, row_bed = [], {}, []  # row_bed[i] = index of row i among the usable BED rows (--ehh-cores is per BED row)
+    ehh_cores = read_core_positions(args.ehh_cores) if args.ehh_cores else None
+    if ehh_cores is not None and len(ehh_cores) != len(bed):
+        print(f"Error: --ehh-cores holds {len(ehh_cores)} positions for {len(bed)} BED rows", file=sys.stderr)
+        sys.exit(2)
+    for bed_no, (chrom, s, e) in enumerate(bed):
         region = f"{full_name(chrom)}:{s}-{e}"
         key = "" if "" in by_contig else full_name(chrom)
         if key not in by_contig:
@@ -553,6 +624,7 @@ def main():
             continue
         per_mat.setdefault(key, []).append(len(rows))
         rows.append((region, key, s, e))
+        row_bed.append(bed_no)
     n_rows = len(rows)
     L_col = np.array([e - s for _, _, s, e in rows], dtype=np.int64)  # LENGTH = end - start (run_pica2_impg.sh:133)
     if args.sequence_length is not None:
@@ -576,6 +648,7 @@ def main():
     samples_col = 0
     af_recs = np.zeros(n_rows, dtype=impop_amd.CLUSTER_DTYPE)
     af_clusters = [None] * n_rows
+    ehh_lines = [None] * n_rows
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -585,6 +658,23 @@ def main():
             _, _, s, e = rows[i]
             b, en = mf.site_range(s, e)
             wins.append((b, en, int(L_col[i])))
+        if fmt == "ehh":  # cores and the reference sequence are checked before the matrix goes up
+            cores = []
+            for i, (b, en, _) in zip(idx, wins):
+                if ehh_cores is not None:
+                    c = mf.site_range(ehh_cores[row_bed[i]], ehh_cores[row_bed[i]])[0]
+                else:
+                    c = b + ((en - b) // 2 if args.ehh_core_offset is None else args.ehh_core_offset)
+                if not b <= c < en:
+                    print(f"Error: --format ehh: the core of {rows[i][0]} (site {c}) is outside the window's sites [{b}, {en})", file=sys.stderr)
+                    sys.exit(2)
+                cores.append(c)
+            ref_hap = 0
+            if args.ehh_ref is not None:
+                if args.ehh_ref not in names:
+                    print(f"Error: --ehh-ref {args.ehh_ref} is not a sequence of the matrix", file=sys.stderr)
+                    sys.exit(2)
+                ref_hap = list(names).index(args.ehh_ref)
         run = Runner(args, mf, wins, need_pairs, rank, world, local_rank)
         mask_p = mask_a = mask_b = None
         n_matched = mf.n_hap
@@ -627,6 +717,13 @@ def main():
                     af_clusters[i] = clusters_from_ranks(row, members)
             else:
                 af_recs[idx] = res
+            run.close()
+            continue
+        if fmt == "ehh":
+            recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=mask_p, ref_hap=ref_hap, flanks=args.ehh_flanks or "reference")
+            for i, c, r in zip(idx, cores, recs):
+                core_bp = int(mf.site_pos[c]) if mf.site_pos is not None else int(mf.origin + c)
+                ehh_lines[i] = ehh_rows(rows[i][0], int(L_col[i]), core_bp, r)
             run.close()
             continue
         if fmt == "fst3pi":
@@ -688,6 +785,11 @@ def main():
         if args.af_details:
             with open(args.af_details, "w", newline="") as fh:
                 write_af_details(fh, regions, af_clusters, float(pica_t))
+    elif fmt == "ehh":
+        print(EHH_HEADER, file=out)
+        for lines in ehh_lines:
+            for line in lines:
+                print(line, file=out)
     else:
         write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels)
     if args.output or rank != 0:
