@@ -144,6 +144,7 @@ SIGNATURES = {
     "impop_ctx_gram_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_cluster_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_ehh_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "impop_debug_timer_pool_sizes": (C.c_int, [_vp, _vp, _u64p]),
     "impop_matrix_synthetic_slab": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams), C.c_uint32, C.POINTER(_vp)]),
     "impop_matrix_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),
     "impop_matrix_info": (C.c_int, [_vp, _u32p, _u64p, _u64p, _u32p]),

@@ -62,7 +62,9 @@ def build(force: bool = False, verbose: bool = False) -> str:
         raise RuntimeError("hipcc not found: cannot build libimpop_hip.so")
     if jobs:
         from concurrent.futures import ThreadPoolExecutor
-        with ThreadPoolExecutor(max_workers=min(len(jobs), max((os.cpu_count() or 2) - 1, 1))) as ex:
+        # at most 16 compilers at once, fewer where MAX_JOBS says so: a shared machine reports far more CPUs than a job may use
+        cap = int(os.environ.get("MAX_JOBS") or 0) or max((os.cpu_count() or 2) - 1, 1)
+        with ThreadPoolExecutor(max_workers=max(min(len(jobs), 16, cap), 1)) as ex:
             for src, err in ex.map(_compile_one, jobs):
                 if err is not None:
                     raise RuntimeError(f"hipcc failed on {src}:\n{err}")

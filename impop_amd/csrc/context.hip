@@ -76,6 +76,45 @@ __global__ void tajima_consts_kernel(int64_t n, double *out) {
     }
 }
 
+int EventPairs::begin(hipStream_t stream, size_t *slot) {
+    if (done == pool.size()) {
+        hipEvent_t a, b;
+        HIP_TRY(hipEventCreate(&a));
+        HIP_TRY(hipEventCreate(&b));
+        pool.push_back({a, b});
+    }
+    *slot = done;
+    HIP_TRY(hipEventRecord(pool[done].first, stream));
+    return IMPOP_OK;
+}
+
+int EventPairs::end(hipStream_t stream, size_t slot) {
+    HIP_TRY(hipEventRecord(pool[slot].second, stream));
+    done = slot + 1;
+    return IMPOP_OK;
+}
+
+int EventPairs::elapsed(double *total_ms, uint64_t *launches) const {
+    double t = 0.0;
+    for (size_t i = 0; i < done; ++i) {
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, pool[i].first, pool[i].second));
+        t += (double)ms;
+    }
+    if (total_ms) *total_ms = t;
+    if (launches) *launches = done;
+    return IMPOP_OK;
+}
+
+void EventPairs::destroy() {
+    for (auto &e : pool) {
+        hipEventDestroy(e.first);
+        hipEventDestroy(e.second);
+    }
+    pool.clear();
+    done = 0;
+}
+
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n) {
     if (!ctx->d_taj) HIP_TRY(hipMalloc(&ctx->d_taj, 8 * sizeof(double)));
     if (ctx->taj_n != n) {
@@ -158,9 +197,9 @@ IMPOP_API int impop_ctx_destroy(impop_ctx *ctx) {
     if (ctx->d_taj) hipFree(ctx->d_taj);
     if (ctx->d_queue) hipFree(ctx->d_queue);
     if (ctx->d_err) hipFree(ctx->d_err);
-    for (auto &e : ctx->gram_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    for (auto &e : ctx->cluster_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
-    for (auto &e : ctx->ehh_events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
+    ctx->gram_timer.destroy();
+    ctx->cluster_timer.destroy();
+    ctx->ehh_timer.destroy();
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     for (void *a : ctx->d_aux)
@@ -207,9 +246,9 @@ IMPOP_API int impop_ctx_gram_timing(impop_ctx *ctx, int enable) {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->gram_timing = enable != 0;
-    ctx->gram_events_used = 0;
-    ctx->cluster_events_used = 0;
-    ctx->ehh_events_used = 0;
+    ctx->gram_timer.reset();
+    ctx->cluster_timer.reset();
+    ctx->ehh_timer.reset();
     return IMPOP_OK;
 }
 
@@ -217,45 +256,21 @@ IMPOP_API int impop_ctx_gram_elapsed(impop_ctx *ctx, double *total_ms, uint64_t 
     REQUIRE(ctx, "impop_ctx_gram_elapsed: ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    double t = 0.0;
-    for (size_t i = 0; i < ctx->gram_events_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->gram_events[i].first, ctx->gram_events[i].second));
-        t += (double)ms;
-    }
-    if (total_ms) *total_ms = t;
-    if (launches) *launches = ctx->gram_events_used;
-    return IMPOP_OK;
+    return ctx->gram_timer.elapsed(total_ms, launches);
 }
 
 IMPOP_API int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_cluster_elapsed: ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    double t = 0.0;
-    for (size_t i = 0; i < ctx->cluster_events_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->cluster_events[i].first, ctx->cluster_events[i].second));
-        t += (double)ms;
-    }
-    if (total_ms) *total_ms = t;
-    if (launches) *launches = ctx->cluster_events_used;
-    return IMPOP_OK;
+    return ctx->cluster_timer.elapsed(total_ms, launches);
 }
 
 IMPOP_API int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_ehh_elapsed: ctx is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    double t = 0.0;
-    for (size_t i = 0; i < ctx->ehh_events_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ctx->ehh_events[i].first, ctx->ehh_events[i].second));
-        t += (double)ms;
-    }
-    if (total_ms) *total_ms = t;
-    if (launches) *launches = ctx->ehh_events_used;
-    return IMPOP_OK;
+    return ctx->ehh_timer.elapsed(total_ms, launches);
 }
 
 IMPOP_API int impop_ctx_synchronize(impop_ctx *ctx) {

@@ -123,4 +123,16 @@ __device__ inline double wave_sum_f64(double v) {  // fixed butterfly order: det
 }
 #endif
 
+// 32 x 64 bit transpose across a wave: every lane hands in one dword; lane j < 32 gets the 64-bit ballot of bit j
+// (bit l = bit j of lane l's dword), lanes 32..63 get 0
+__device__ inline uint64_t ballot_transpose32(uint32_t w, uint32_t lane) {
+    uint64_t keep = 0;
+#pragma unroll
+    for (int j = 0; j < 32; ++j) {
+        const uint64_t m = __ballot((w >> j) & 1u);
+        if (lane == (uint32_t)j) keep = m;
+    }
+    return keep;
+}
+
 }  // namespace impop

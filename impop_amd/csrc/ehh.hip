@@ -41,13 +41,7 @@ __global__ __launch_bounds__(256) void ehh_transpose_kernel(const uint32_t *__re
     if (b * 64 < site_begin) edge &= ~0ull << (site_begin - b * 64);
     if (site_end - b * 64 < 64) edge &= (1ull << (site_end - b * 64)) - 1ull;
     for (uint32_t k = 0; k < wps; ++k) {
-        const uint32_t w = sb[sb_index(wps, G, r, b, lane, k)];
-        uint64_t keep = 0;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const uint64_t m = __ballot((w >> j) & 1u);
-            if (lane == (uint32_t)j) keep = m;
-        }
+        const uint64_t keep = ballot_transpose32(sb[sb_index(wps, G, r, b, lane, k)], lane);
         if (lane < 32) wm[bi * n_pad + 32 * k + lane] = keep & edge;
     }
 }
@@ -136,13 +130,7 @@ __global__ __launch_bounds__(256) void ehh_scan_transpose_kernel(const uint32_t 
     const uint64_t b = w.tblk0 + bi;
     uint64_t *dst = wm + w.woff + bi * stride;
     for (uint32_t k = 0; k < wps; ++k) {
-        const uint32_t v = sb[sb_index(wps, G, r, b, lane, k)];
-        uint64_t keep = 0;
-#pragma unroll
-        for (int j = 0; j < 32; ++j) {
-            const uint64_t m = __ballot((v >> j) & 1u);
-            if (lane == (uint32_t)j) keep = m;
-        }
+        const uint64_t keep = ballot_transpose32(sb[sb_index(wps, G, r, b, lane, k)], lane);
         if (lane < 32) {
             const int32_t pp = ppos[32 * k + lane];
             if (pp >= 0) dst[pp] = keep;
@@ -394,15 +382,16 @@ IMPOP_API int impop_ehh(impop_ctx *ctx, const impop_matrix *m, uint64_t site_beg
     const size_t wm_bytes = (size_t)n_blk * n_pad * 8;
     REQUIRE(wm_bytes <= (64ull << 30), "impop_ehh: window too large (%llu MiB of transposed scratch)",
             (unsigned long long)(wm_bytes >> 20));
-    const size_t o_hist = (wm_bytes + 255) / 256 * 256, o_out = o_hist + (W * 8 + 255) / 256 * 256,
-                 o_idx = o_out + (W * 8 + 255) / 256 * 256;
+    Carve L;
+    const size_t o_wm = L.take_bytes(wm_bytes), o_hist = L.take<unsigned long long>(W), o_out = L.take<double>(W),
+                 o_idx = L.take<uint32_t>(mm ? mm : 1);
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, o_idx + (size_t)(mm ? mm : 1) * 4, &d);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    uint64_t *d_wm = (uint64_t *)d;
-    unsigned long long *d_hist = (unsigned long long *)((char *)d + o_hist);
-    double *d_out = (double *)((char *)d + o_out);
-    uint32_t *d_idx = (uint32_t *)((char *)d + o_idx);
+    uint64_t *d_wm = L.at<uint64_t>(d, o_wm);
+    unsigned long long *d_hist = L.at<unsigned long long>(d, o_hist);
+    double *d_out = L.at<double>(d, o_out);
+    uint32_t *d_idx = L.at<uint32_t>(d, o_idx);
     if (mm < 2) {  // ehhgfa.py:17-18: fewer than two haplotypes -> every entry 500
         hipLaunchKernelGGL(ehh_fill_kernel, dim3((uint32_t)((W + 255) / 256)), dim3(256), 0, ctx->stream, d_out, W, 500.0);
     } else {
@@ -453,7 +442,6 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
                 (unsigned long long)windows[i].site_begin, (unsigned long long)windows[i].site_end,
                 (unsigned long long)windows[i].core_site, (unsigned long long)m->g.n_site);
     HIP_TRY(hipSetDevice(ctx->device));
-    static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
 
     // the windows' transposed blocks and the chunks they fall into (by scratch bytes; blockIdx.y holds 65535 windows)
     const uint32_t stride = nP ? nP : 1;
@@ -481,13 +469,13 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
             (unsigned long long)(max_words >> 17));
 
     // device: idx | ppos | chunk windows | chunk records | transposed words; the first four mirrored in page-locked staging
-    const size_t o_idx = 0, o_ppos = o_idx + round_up_256((size_t)stride * 4), o_win = o_ppos + round_up_256((size_t)n_pad * 4),
-                 o_rec = o_win + round_up_256(max_cnt * sizeof(EhhWin)), o_wm = o_rec + round_up_256(max_cnt * sizeof(impop_ehh_stats));
-    const size_t scratch_bytes = o_wm + (size_t)max_words * 8 + 256;
+    Carve L;
+    const size_t o_idx = L.take<uint32_t>(stride), o_ppos = L.take<int32_t>(n_pad), o_win = L.take<EhhWin>(max_cnt),
+                 o_rec = L.take<impop_ehh_stats>(max_cnt), staged = L.total(), o_wm = L.take<uint64_t>(max_words);
     void *d = nullptr, *pin = nullptr;
-    int rc = ctx_scratch(ctx, scratch_bytes, &d);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    rc = ctx_pinned(ctx, o_wm, &pin);
+    rc = ctx_pinned(ctx, staged, &pin);
     if (rc) return rc;
     char *dc = (char *)d, *hc = (char *)pin;
     if (nP) memcpy(hc + o_idx, idx.data(), (size_t)nP * 4);
@@ -506,17 +494,8 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
         }
         memcpy(hc + o_win, &meta[base], cnt * sizeof(EhhWin));
         HIP_TRY(hipMemcpyAsync(dc + o_win, hc + o_win, cnt * sizeof(EhhWin), hipMemcpyHostToDevice, ctx->stream));
-        hipEvent_t ev1 = nullptr;
-        if (ctx->gram_timing) {  // the chunk's kernels between two events of their own: impop_ctx_ehh_elapsed
-            if (ctx->ehh_events_used == ctx->ehh_events.size()) {
-                hipEvent_t a, b;
-                HIP_TRY(hipEventCreate(&a));
-                HIP_TRY(hipEventCreate(&b));
-                ctx->ehh_events.push_back({a, b});
-            }
-            HIP_TRY(hipEventRecord(ctx->ehh_events[ctx->ehh_events_used].first, ctx->stream));
-            ev1 = ctx->ehh_events[ctx->ehh_events_used].second;
-        }
+        size_t slot = 0;  // the chunk's kernels between two events of their own: impop_ctx_ehh_elapsed
+        if (ctx->gram_timing && (rc = ctx->ehh_timer.begin(ctx->stream, &slot))) return rc;
         uint32_t launches = 0;
         if (max_blk) {
             hipLaunchKernelGGL(ehh_scan_transpose_kernel, dim3((max_blk + 3) / 4, (uint32_t)cnt), dim3(256), 0, ctx->stream, m->d_sb,
@@ -529,11 +508,8 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
                            params->ref_hap, (const uint64_t *)(dc + o_wm), stride, (impop_ehh_stats *)(dc + o_rec), ctx->d_err);
         ++launches;
         HIP_TRY(hipGetLastError());
-        if (ev1) {
-            HIP_TRY(hipEventRecord(ev1, ctx->stream));
-            ctx->ehh_events_used++;
-        }
-        if (trace) {
+        if (ctx->gram_timing && (rc = ctx->ehh_timer.end(ctx->stream, slot))) return rc;
+        if (trace_on()) {
             fprintf(stderr, "[impop_ehh_scan] windows=%llu problems=%llu chunk=%llu launches=%u scratch_bytes=%llu\n",
                     (unsigned long long)cnt, (unsigned long long)(cnt * 4), (unsigned long long)c, launches, (unsigned long long)(words * 8));
             fflush(stderr);

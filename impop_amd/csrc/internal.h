@@ -3,10 +3,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <vector>
 
 #include "../../include/impop_hip.h"
+#include "carve.h"
 
 #define IMPOP_API extern "C" __attribute__((visibility("default")))
 
@@ -76,8 +78,29 @@ __host__ __device__ inline uint64_t sb_index(uint32_t wps, uint32_t G, uint32_t 
                        : base + (uint64_t)(G - 1) * 256 + (uint64_t)l * r + (k - 4 * (G - 1));
 }
 
-// sub-buffers of one device allocation start on 256-byte boundaries
-inline size_t round_up_256(size_t x) { return (x + 255) / 256 * 256; }
+// one-character environment switches (IMPOP_EPILOGUE_FAST=0, IMPOP_NO_POLARITY=1, ...): is the variable set and does it start with ch
+inline bool env_is(const char *name, char ch) {
+    const char *e = getenv(name);
+    return e && e[0] == ch;
+}
+// IMPOP_TRACE=1: the calls' trace lines on stderr (read once per process)
+inline bool trace_on() {
+    static const bool on = env_is("IMPOP_TRACE", '1');
+    return on;
+}
+
+// The timer of the batched calls: a pool of (start, stop) event pairs and the number of pairs COMPLETED since the last reset.
+// A pair counts only once its stop event is recorded, so elapsed() never asks for an event that a failed launch left out.
+// Bodies in context.hip.
+struct EventPairs {
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pool;
+    size_t done = 0;
+    int begin(hipStream_t stream, size_t *slot);  // grows the pool if needed, records the start event of pair *slot
+    int end(hipStream_t stream, size_t slot);     // records its stop event, then counts the pair
+    void reset() { done = 0; }
+    int elapsed(double *total_ms, uint64_t *launches) const;  // the stream must be synchronised; either pointer may be null
+    void destroy();
+};
 
 // rare kept sites: min(c, n - c) <= IMPOP_RARE_MAX (one 8-byte entry lists their minor-allele carriers)
 constexpr uint32_t IMPOP_RARE_MAX = 3;
@@ -109,16 +132,11 @@ struct impop_ctx {
     // invariant fails (stats.hip: the grouping's progress bound), the call that launched them returns IMPOP_E_INTERNAL
     uint32_t *d_err = nullptr;
     uint32_t h_err = 0;
-    // impop_ctx_gram_timing: event pairs around the Gram launches of impop_pairwise_scan
+    // impop_ctx_gram_timing: one switch, three timers (impop::EventPairs) — around the Gram launch(es) of every chunk of
+    // impop_pairwise_scan / impop_cluster_scan (impop_ctx_gram_elapsed), the clustering kernel(s) of impop_cluster_scan
+    // (impop_ctx_cluster_elapsed) and the kernels of every chunk of impop_ehh_scan (impop_ctx_ehh_elapsed)
     bool gram_timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> gram_events;
-    size_t gram_events_used = 0;
-    // the same switch also brackets the clustering kernel(s) of impop_cluster_scan (impop_ctx_cluster_elapsed)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> cluster_events;
-    size_t cluster_events_used = 0;
-    // ... and the kernels of every chunk of impop_ehh_scan (impop_ctx_ehh_elapsed)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ehh_events;
-    size_t ehh_events_used = 0;
+    impop::EventPairs gram_timer, cluster_timer, ehh_timer;
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
     // all-pairs path run next to each other instead of one after the other
     hipStream_t side = nullptr;
@@ -212,6 +230,9 @@ constexpr uint32_t DEV_ERR_GROUPING = 1u;            // greedy_groups_bits ran o
 constexpr uint32_t DEV_ERR_CLUSTER = 2u;             // af label propagation ran out of its rounds
 constexpr uint32_t DEV_ERR_EHH = 4u;                 // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
+// stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need
+// to be distinct among the members, else IMPOP_E_INVALID with *dup = a rank that occurs twice (the caller words the message)
+int seed_order_of(const uint32_t *seed_rank, const uint32_t *members, uint32_t m, std::vector<uint32_t> &order, uint32_t *dup);
 // pairwise.hip: build (once) the bitmap of the sites that segregate among all haplotypes, m->d_segmap
 int ensure_segmap(impop_ctx *ctx, const impop_matrix *m);
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n);  // fills ctx->d_taj for n (device kernel)

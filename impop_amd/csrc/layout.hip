@@ -230,7 +230,7 @@ static int alloc_matrix(impop_ctx *ctx, uint32_t n_hap, uint64_t n_site, bool wa
     m->device = ctx->device;
     m->n_hap_pad = (n_hap + 95) / 96 * 96;  // Gram tiles are 96 haplotypes wide (3 row groups of 32)
     {   // minor-allele polarity of the all-pairs operand (sb_to_hm_kernel) needs one padding row for the set of complemented sites
-        static const bool off = [] { const char *e = getenv("IMPOP_NO_POLARITY"); return e && e[0] == '1'; }();
+        static const bool off = env_is("IMPOP_NO_POLARITY", '1');
         m->phi_row = (want_hm && !off && n_hap % 96 != 0 && n_hap <= 16384 /* gram_unflip_kernel's LDS */) ? n_hap : 0xFFFFFFFFu;
     }
     m->sb_bytes = m->g.n_block * 64ull * m->g.wps * 4ull;
@@ -788,9 +788,10 @@ static bool index_alloc(impop_matrix *m, void **p, size_t bytes, const char *wha
 struct IndexTmp {
     size_t o_ccnt, o_chunk, o_cchunk, o_total, bytes;
     IndexTmp(uint64_t ne, uint64_t n_chunks) {
-        const auto up = round_up_256;
-        o_ccnt = up(ne * 4); o_chunk = o_ccnt + up(ne * 4); o_cchunk = o_chunk + up(n_chunks * 8); o_total = o_cchunk + up(n_chunks * 8);
-        bytes = o_total + 256;
+        Carve L;
+        L.take<uint32_t>(ne);  // the kept counts, at offset 0
+        o_ccnt = L.take<uint32_t>(ne); o_chunk = L.take<uint64_t>(n_chunks); o_cchunk = L.take<uint64_t>(n_chunks); o_total = L.take<uint64_t>(2);
+        bytes = L.total();
     }
 };
 
@@ -918,15 +919,15 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     const SbGeom &g = in->g;
     const uint64_t nb = g.n_block, n_chunks = (nb + SCAN_CHUNK - 1) / SCAN_CHUNK;
     REQUIRE((nb + 3) / 4 < 0x7FFFFFFFull, "impop_matrix_compact: matrix too long for one launch");
-    const auto up = round_up_256;
-    const size_t o_mask = 0, o_cnt = o_mask + up(nb * 8), o_base = o_cnt + up(nb * 4), o_chunk = o_base + up(nb * 8),
-                 o_total = o_chunk + up(n_chunks * 8);
+    Carve L;
+    const size_t o_mask = L.take<uint64_t>(nb), o_cnt = L.take<uint32_t>(nb), o_base = L.take<uint64_t>(nb), o_chunk = L.take<uint64_t>(n_chunks),
+                 o_total = L.take<uint64_t>(1);
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, o_total + 256, &d);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    uint64_t *d_mask = (uint64_t *)((char *)d + o_mask), *d_base = (uint64_t *)((char *)d + o_base),
-             *d_chunk = (uint64_t *)((char *)d + o_chunk), *d_total = (uint64_t *)((char *)d + o_total);
-    uint32_t *d_cnt = (uint32_t *)((char *)d + o_cnt);
+    uint64_t *d_mask = L.at<uint64_t>(d, o_mask), *d_base = L.at<uint64_t>(d, o_base), *d_chunk = L.at<uint64_t>(d, o_chunk),
+             *d_total = L.at<uint64_t>(d, o_total);
+    uint32_t *d_cnt = L.at<uint32_t>(d, o_cnt);
     uint64_t n_kept = 0;
     // a source that kept its hap-major copy hands the all-pairs path on: the compacted matrix gets its own RB32
     // operand and the bitmap of the dropped all-ones sites (their count — for a weighted source the sum of their

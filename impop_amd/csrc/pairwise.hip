@@ -561,8 +561,7 @@ static int launch_gram(impop_ctx *ctx, const impop_matrix *m, const uint32_t *d_
         if (forced > 0 && ksplit == 1) chain = (uint32_t)forced;
     }
     {  // IMPOP_TRACE=1: the launch configuration (the chain as gram_fp4_kernel applies it: only with >= 8 cells and no K-split)
-        static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
-        if (trace)
+        if (trace_on())
             fprintf(stderr, "[impop_gram] cells=%u tiles=%u ksplit=%u chain=%u u16=%d fused_planes=%d\n", n_win, T, ksplit,
                     (n_win >= 8 && ksplit == 1) ? chain : 1u, w16 ? 1 : 0, fused_planes ? 1 : 0);
     }
@@ -772,19 +771,6 @@ static inline uint32_t ones_weight(const impop_matrix *m, uint64_t s0, uint64_t 
 }
 static inline bool compact_weighted(const impop_matrix *m) { return m->compact && !m->ones_wt_prefix.empty(); }
 
-struct Carve2 {
-    char *base;
-    size_t off = 0;
-    explicit Carve2(void *p) : base((char *)p) {}
-    template <typename T>
-    T *take(size_t count) {
-        off = (off + 255) / 256 * 256;
-        T *p = reinterpret_cast<T *>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-
 }  // namespace impop
 
 using namespace impop;
@@ -810,13 +796,13 @@ IMPOP_API int impop_pairwise_counts(impop_ctx *ctx, const impop_matrix *m, uint6
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
     void *d = nullptr;
-    rc = ctx_scratch(ctx, 2048 + (size_t)ld * ld * 4, &d);
+    Carve L;
+    const size_t o_w = L.take<GramWindow>(1), o_g = L.take<int32_t>((size_t)ld * ld), o_ow = L.take<GramWindow>(1), o_add = L.take<uint32_t>(1);
+    rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve2 cv(d);
-    GramWindow *d_w = cv.take<GramWindow>(1);
-    int32_t *d_g = cv.take<int32_t>((size_t)ld * ld);
-    GramWindow *d_ow = cv.take<GramWindow>(1);
-    uint32_t *d_add = cv.take<uint32_t>(1);
+    GramWindow *d_w = L.at<GramWindow>(d, o_w), *d_ow = L.at<GramWindow>(d, o_ow);
+    int32_t *d_g = L.at<int32_t>(d, o_g);
+    uint32_t *d_add = L.at<uint32_t>(d, o_add);
     GramWindow w;
     map_range(m, site_begin, site_end, &w.site_begin, &w.site_end);  // compacted: the kept sites of the range
     HIP_TRY(hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
@@ -854,15 +840,16 @@ IMPOP_API int impop_pairwise_identity(impop_ctx *ctx, const impop_matrix *m, uin
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
     void *d = nullptr;
-    rc = ctx_scratch(ctx, 4096 + (size_t)ld * ld * 4 + (size_t)n * n * 8, &d);
+    Carve L;
+    const size_t o_w = L.take<GramWindow>(1), o_W = L.take<uint64_t>(1), o_g = L.take<int32_t>((size_t)ld * ld),
+                 o_id = L.take<double>((size_t)n * n), o_ow = L.take<GramWindow>(1), o_add = L.take<uint32_t>(1);
+    rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve2 cv(d);
-    GramWindow *d_w = cv.take<GramWindow>(1);
-    uint64_t *d_W = cv.take<uint64_t>(1);
-    int32_t *d_g = cv.take<int32_t>((size_t)ld * ld);
-    double *d_id = cv.take<double>((size_t)n * n);
-    GramWindow *d_ow = cv.take<GramWindow>(1);
-    uint32_t *d_add = cv.take<uint32_t>(1);
+    GramWindow *d_w = L.at<GramWindow>(d, o_w), *d_ow = L.at<GramWindow>(d, o_ow);
+    uint64_t *d_W = L.at<uint64_t>(d, o_W);
+    int32_t *d_g = L.at<int32_t>(d, o_g);
+    double *d_id = L.at<double>(d, o_id);
+    uint32_t *d_add = L.at<uint32_t>(d, o_add);
     GramWindow w;
     map_range(m, site_begin, site_end, &w.site_begin, &w.site_end);
     const uint64_t W = window_W(m, site_begin, site_end);  // the window's ORIGINAL length
@@ -923,13 +910,11 @@ struct PairFront {
     size_t out_per_window;                // staged result bytes per window
     uint64_t max_chunk_windows;           // 0 = no limit of the epilogue's own
 };
-static inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
 static int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const PairFront &in,
                           PairEpilogue &epi) {
     const uint32_t ld = m->n_hap_pad, n = m->g.n_hap;
     // IMPOP_TRACE=1: host-side phase times of this call on stderr (where a call's time goes when the kernels are short)
-    static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
+    const bool trace = trace_on();
     const auto t_enter = std::chrono::steady_clock::now();
     auto lap = [&](const char *what) {
         if (trace) fprintf(stderr, "[%s] %-22s +%.1f us\n", in.fn, what,
@@ -1035,26 +1020,27 @@ static int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_win
     if (!segmented) cap = std::min<uint64_t>(cap, win_cap);
     // per-chunk metadata: ONE contiguous region mirrored on the host, so that a chunk costs one host-to-device copy
     // (eight small pageable copies were ~0.3 ms of host time between two Gram launches)
-    const size_t o_w = 0, o_W = o_w + up256(cap * sizeof(GramWindow)), o_L = o_W + up256(cap * 8), o_first = o_L + up256(cap * 8),
-                 o_count = o_first + up256(cap * 4), o_s = o_count + up256(cap * 4), o_sw = o_s + up256(cap * sizeof(impop_window_stats)),
-                 o_ow = o_sw + up256(cap * sizeof(GramWindow)), meta_bytes = o_ow + up256(cap * sizeof(GramWindow));
+    Carve M;  // cells first: they go up on their own, everything from o_W on in a second copy
+    const size_t o_w = M.take<GramWindow>(cap), o_W = M.take<uint64_t>(cap), o_L = M.take<uint64_t>(cap), o_first = M.take<uint32_t>(cap),
+                 o_count = M.take<uint32_t>(cap), o_s = M.take<impop_window_stats>(cap), o_sw = M.take<GramWindow>(cap),
+                 o_ow = M.take<GramWindow>(cap), meta_bytes = M.total();
     const size_t epi_bytes = in.epi_fixed + win_cap * in.epi_per_window;
+    Carve D;  // device: Gram matrices | metadata | compacted: dropped all-ones sites per window | the epilogue's own region
+    const size_t o_g = D.take_bytes(cap * gram_bytes), o_meta = D.take_bytes(meta_bytes), o_add = D.take<uint32_t>(cap),
+                 o_epi = D.take_bytes(epi_bytes);
     void *d = nullptr;
-    rc = ctx_scratch(ctx, 4096 + up256(cap * gram_bytes) + up256(meta_bytes) + up256(cap * 4) + up256(epi_bytes) + 1024, &d);
+    rc = ctx_scratch(ctx, D.total(), &d);
     if (rc) return rc;
-    Carve2 cv(d);
-    int32_t *d_g = cv.take<int32_t>(cap * (size_t)ld * ld);
-    char *d_meta = cv.take<char>(meta_bytes);
-    GramWindow *d_w = reinterpret_cast<GramWindow *>(d_meta + o_w);
-    uint64_t *d_W = reinterpret_cast<uint64_t *>(d_meta + o_W);
-    uint64_t *d_L = reinterpret_cast<uint64_t *>(d_meta + o_L);
-    uint32_t *d_first = reinterpret_cast<uint32_t *>(d_meta + o_first);
-    uint32_t *d_count = reinterpret_cast<uint32_t *>(d_meta + o_count);
-    impop_window_stats *d_s = reinterpret_cast<impop_window_stats *>(d_meta + o_s);
-    GramWindow *d_sw = reinterpret_cast<GramWindow *>(d_meta + o_sw);  // the chunk's WINDOWS (d_w holds its Gram cells), matrix coordinates
-    GramWindow *d_ow = reinterpret_cast<GramWindow *>(d_meta + o_ow);  // the same windows in ORIGINAL coordinates (compacted matrices)
-    uint32_t *d_add = cv.take<uint32_t>(cap);     // compacted: dropped all-ones sites per window
-    void *d_epi = cv.take<char>(epi_bytes ? epi_bytes : 1);
+    int32_t *d_g = D.at<int32_t>(d, o_g);
+    char *d_meta = D.at<char>(d, o_meta);
+    GramWindow *d_w = M.at<GramWindow>(d_meta, o_w);
+    uint64_t *d_W = M.at<uint64_t>(d_meta, o_W), *d_L = M.at<uint64_t>(d_meta, o_L);
+    uint32_t *d_first = M.at<uint32_t>(d_meta, o_first), *d_count = M.at<uint32_t>(d_meta, o_count);
+    impop_window_stats *d_s = M.at<impop_window_stats>(d_meta, o_s);
+    GramWindow *d_sw = M.at<GramWindow>(d_meta, o_sw);  // the chunk's WINDOWS (d_w holds its Gram cells), matrix coordinates
+    GramWindow *d_ow = M.at<GramWindow>(d_meta, o_ow);  // the same windows in ORIGINAL coordinates (compacted matrices)
+    uint32_t *d_add = D.at<uint32_t>(d, o_add);
+    void *d_epi = D.at<char>(d, o_epi);
     rc = epi.prepare(ctx, d_epi, win_cap);
     if (rc) return rc;
     // even out the chunks: a total slightly above the capacity would otherwise leave a last chunk of a few
@@ -1069,17 +1055,16 @@ static int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_win
     }
     lap("scratch");
     // page-locked staging for the metadata going up and the results coming down (ctx_pinned)
-    const size_t out_off = up256(meta_bytes);
+    const size_t out_off = meta_bytes;
     void *pin = nullptr;
     rc = ctx_pinned(ctx, out_off + win_cap * in.out_per_window, &pin);
     if (rc) return rc;
     char *hmeta = reinterpret_cast<char *>(pin);
     memset(hmeta, 0, meta_bytes);
-    GramWindow *gw = reinterpret_cast<GramWindow *>(hmeta + o_w), *swv = reinterpret_cast<GramWindow *>(hmeta + o_sw),
-               *owv = reinterpret_cast<GramWindow *>(hmeta + o_ow);
-    uint64_t *Wv = reinterpret_cast<uint64_t *>(hmeta + o_W), *Lv = reinterpret_cast<uint64_t *>(hmeta + o_L);
-    uint32_t *fv = reinterpret_cast<uint32_t *>(hmeta + o_first), *cvv = reinterpret_cast<uint32_t *>(hmeta + o_count);
-    impop_window_stats *sv = reinterpret_cast<impop_window_stats *>(hmeta + o_s);
+    GramWindow *gw = M.at<GramWindow>(hmeta, o_w), *swv = M.at<GramWindow>(hmeta, o_sw), *owv = M.at<GramWindow>(hmeta, o_ow);
+    uint64_t *Wv = M.at<uint64_t>(hmeta, o_W), *Lv = M.at<uint64_t>(hmeta, o_L);
+    uint32_t *fv = M.at<uint32_t>(hmeta, o_first), *cvv = M.at<uint32_t>(hmeta, o_count);
+    impop_window_stats *sv = M.at<impop_window_stats>(hmeta, o_s);
     std::vector<uint32_t> add_h;
     uint64_t call_max_W = 0;  // bounds every Gram count of the call (a cell is a window or a piece of one; compacted: + its constant)
     for (uint64_t i = 0; i < n_windows; ++i) call_max_W = std::max(call_max_W, window_W(m, windows[i].site_begin, windows[i].site_end));
@@ -1113,24 +1098,14 @@ static int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_win
         // copied) while it runs
         if (n_cells) HIP_TRY(hipMemcpyAsync(d_meta + o_w, hmeta + o_w, (size_t)n_cells * sizeof(GramWindow), hipMemcpyHostToDevice, ctx->stream));
         if (n_cells) {
-            hipEvent_t ev1 = nullptr;
-            if (ctx->gram_timing) {  // impop_ctx_gram_timing: the Gram launch(es) of this chunk between two events
-                if (ctx->gram_events_used == ctx->gram_events.size()) {
-                    hipEvent_t a, b;
-                    HIP_TRY(hipEventCreate(&a));
-                    HIP_TRY(hipEventCreate(&b));
-                    ctx->gram_events.push_back({a, b});
-                }
-                HIP_TRY(hipEventRecord(ctx->gram_events[ctx->gram_events_used].first, ctx->stream));
-                ev1 = ctx->gram_events[ctx->gram_events_used].second;
-                ctx->gram_events_used++;
-            }
+            size_t slot = 0;  // impop_ctx_gram_timing: the Gram launch(es) of this chunk between two events
+            if (ctx->gram_timing && (rc = ctx->gram_timer.begin(ctx->stream, &slot))) return rc;
             // counts as uint16 where every count of the call fits (a count is at most its window's W): half the result bytes
-            static const bool u16_off = [] { const char *e = getenv("IMPOP_GRAM_U16"); return e && e[0] == '0'; }();
+            static const bool u16_off = env_is("IMPOP_GRAM_U16", '0');
             g16 = !u16_off && call_max_W < 65536;
             rc = launch_gram_any(ctx, m, d_w, gw, n_cells, d_g, max_sites, &g16);
             if (rc) return rc;
-            if (ev1) HIP_TRY(hipEventRecord(ev1, ctx->stream));
+            if (ctx->gram_timing && (rc = ctx->gram_timer.end(ctx->stream, slot))) return rc;
             if (in.identity_kind != IMPOP_IDENTITY_MATCH) {  // `match` sees Hamming distances only: polarity-invariant
                 rc = launch_gram_unflip(ctx, m, d_g, n_cells, g16);
                 if (rc) return rc;
@@ -1206,16 +1181,17 @@ struct PairwiseStatsEpilogue final : PairEpilogue {
     impop_pairwise_stats *d_o = nullptr;
     uint32_t *d_idx = nullptr, *d_ia = nullptr, *d_ib = nullptr;
     uint8_t *d_fa = nullptr, *d_fb = nullptr;
-    static size_t fixed_bytes(uint32_t n) { return 3 * up256((size_t)(n ? n : 1) * 4) + 2 * up256(n ? n : 1) + 256; }
+    // prepare()'s member lists and flags; + 256: the total of its layout is rounded up
+    static size_t fixed_bytes(uint32_t n) { return 3 * round_up_256((size_t)(n ? n : 1) * 4) + 2 * round_up_256(n ? n : 1) + 256; }
     static size_t window_bytes() { return sizeof(Pica2Out) + sizeof(HfstOut) + sizeof(impop_pairwise_stats); }
     int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) override {
-        Carve2 cv(d_epi);
-        d_idx = cv.take<uint32_t>(n ? n : 1);
-        d_ia = cv.take<uint32_t>(n ? n : 1);
-        d_ib = cv.take<uint32_t>(n ? n : 1);
-        d_fa = cv.take<uint8_t>(n ? n : 1);
-        d_fb = cv.take<uint8_t>(n ? n : 1);
-        char *w = cv.take<char>(cap * window_bytes());
+        Carve L;
+        d_idx = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
+        d_ia = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
+        d_ib = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
+        d_fa = L.at<uint8_t>(d_epi, L.take<uint8_t>(n ? n : 1));
+        d_fb = L.at<uint8_t>(d_epi, L.take<uint8_t>(n ? n : 1));
+        char *w = L.at<char>(d_epi, L.take_bytes(cap * window_bytes()));
         d_h = reinterpret_cast<HfstOut *>(w);
         d_o = reinterpret_cast<impop_pairwise_stats *>(w + cap * sizeof(HfstOut));
         d_p = reinterpret_cast<Pica2Out *>(w + cap * (sizeof(HfstOut) + sizeof(impop_pairwise_stats)));
@@ -1279,16 +1255,16 @@ struct ClusterEpilogue final : PairEpilogue {
     uint32_t *d_idx = nullptr, *d_cl = nullptr, *d_sz = nullptr, *d_adj = nullptr;
     size_t members_bytes() const { return (size_t)nP * 4; }
     bool want_members() const { return cluster_of || sizes; }
-    static size_t fixed_bytes(uint32_t nP) { return up256((size_t)(nP ? nP : 1) * 4) + 4 * 256; }
+    static size_t fixed_bytes(uint32_t nP) { return round_up_256((size_t)(nP ? nP : 1) * 4) + 4 * 256; }
     // the window-shape kernel writes tables only when asked; the general form always writes both (sizes is its ranking's output)
     size_t tables_bytes() const { return (adj_bytes == 0 && !want_members()) ? 0 : 2 * members_bytes(); }
     size_t window_bytes() const { return sizeof(impop_cluster_stats) + tables_bytes() + adj_bytes; }
     int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) override {
-        Carve2 cv(d_epi);
-        d_idx = cv.take<uint32_t>(nP ? nP : 1);
-        d_rec = cv.take<impop_cluster_stats>(cap);
-        // (together with the three alignment gaps below: fixed_bytes' 4 x 256)
-        char *w = cv.take<char>(cap * (tables_bytes() + adj_bytes) + 1);
+        Carve L;
+        d_idx = L.at<uint32_t>(d_epi, L.take<uint32_t>(nP ? nP : 1));
+        d_rec = L.at<impop_cluster_stats>(d_epi, L.take<impop_cluster_stats>(cap));
+        // (the layout's alignment gaps and rounded total: fixed_bytes' 4 x 256)
+        char *w = L.at<char>(d_epi, L.take_bytes(cap * (tables_bytes() + adj_bytes)));
         d_cl = reinterpret_cast<uint32_t *>(w);
         d_sz = reinterpret_cast<uint32_t *>(w + cap * (tables_bytes() / 2));
         d_adj = reinterpret_cast<uint32_t *>(w + cap * tables_bytes());
@@ -1298,23 +1274,12 @@ struct ClusterEpilogue final : PairEpilogue {
     // staged per chunk: cnt records | cnt x nP cluster_of | cnt x nP sizes (the tables only when asked for)
     int launch(impop_ctx *ctx, const PairChunk &c) override {
         const uint64_t cnt = c.cnt;
-        hipEvent_t ev1 = nullptr;
-        if (ctx->gram_timing) {  // the clustering kernel(s) between two events of their own: impop_ctx_cluster_elapsed
-            if (ctx->cluster_events_used == ctx->cluster_events.size()) {
-                hipEvent_t a, b;
-                HIP_TRY(hipEventCreate(&a));
-                HIP_TRY(hipEventCreate(&b));
-                ctx->cluster_events.push_back({a, b});
-            }
-            HIP_TRY(hipEventRecord(ctx->cluster_events[ctx->cluster_events_used].first, ctx->stream));
-            ev1 = ctx->cluster_events[ctx->cluster_events_used].second;
-        }
-        int rc = launch_af_batch(ctx, c.b, cnt, mask_p ? d_idx : nullptr, nP, params->threshold, d_adj, adj_bytes, d_rec, d_cl, d_sz, want_members());
+        size_t slot = 0;  // the clustering kernel(s) between two events of their own: impop_ctx_cluster_elapsed
+        int rc = ctx->gram_timing ? ctx->cluster_timer.begin(ctx->stream, &slot) : IMPOP_OK;
         if (rc) return rc;
-        if (ev1) {
-            HIP_TRY(hipEventRecord(ev1, ctx->stream));
-            ctx->cluster_events_used++;
-        }
+        rc = launch_af_batch(ctx, c.b, cnt, mask_p ? d_idx : nullptr, nP, params->threshold, d_adj, adj_bytes, d_rec, d_cl, d_sz, want_members());
+        if (rc) return rc;
+        if (ctx->gram_timing && (rc = ctx->cluster_timer.end(ctx->stream, slot))) return rc;
         char *h = reinterpret_cast<char *>(c.h_out);
         HIP_TRY(hipMemcpyAsync(h, d_rec, cnt * sizeof(impop_cluster_stats), hipMemcpyDeviceToHost, ctx->stream));
         if (want_members() && nP) {

@@ -798,8 +798,7 @@ struct impop_scan_plan {
     uint32_t *d_masks = nullptr;
     impop_window_stats *d_out = nullptr;
     bool timing = false;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> events;  // pool, one pair per timed launch
-    size_t events_used = 0;
+    EventPairs timer;  // one pair per timed launch of the streaming kernel
 };
 
 // W of every window in ORIGINAL coordinates: its length, or the sum of its columns' weights (tiles of compacted matrices and
@@ -868,8 +867,7 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
 // variable site of an indexed route; rare_sites / rare_bytes = the split index's rare entries (all of the matrix / the plan's);
 // split = on, or off:<the reason there is none, blanks as _>
 static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
-    static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
-    if (!trace) return;
+    if (!trace_on()) return;
     const char *why = rt.indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
     uint64_t rare_bytes = 0;
     for (const ScanTile &t : rt.tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
@@ -1015,19 +1013,9 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
     // the cached Tajima constants belong to the context; another plan may have changed n since
     int rc = ensure_tajima_consts(ctx, p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2);
     if (rc) return rc;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (p->timing && p->n_tiles) {
-        if (p->events_used == p->events.size()) {
-            hipEvent_t a, b;
-            HIP_TRY(hipEventCreate(&a));
-            HIP_TRY(hipEventCreate(&b));
-            p->events.push_back({a, b});
-        }
-        ev0 = p->events[p->events_used].first;
-        ev1 = p->events[p->events_used].second;
-        p->events_used++;
-        HIP_TRY(hipEventRecord(ev0, st));
-    }
+    const bool timed = p->timing && p->n_tiles;
+    size_t slot = 0;
+    if (timed && (rc = p->timer.begin(st, &slot))) return rc;
     const bool weighted = !p->m->wt_prefix.empty();  // W of each window came from the host prefix sums at plan time
     const uint32_t wps = p->m->g.wps;
     if (p->n_tiles && (weighted || wps > 16)) {
@@ -1039,7 +1027,6 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
         else          { if (p->subset_p) ANYN(true, false); else ANYN(false, false); }
 #undef ANYN
         HIP_TRY(hipGetLastError());
-        if (ev1) HIP_TRY(hipEventRecord(ev1, st));
     } else if (p->n_tiles) {
         switch (wps) {
 #define CASE(W) case W: launch_scan_fixed<W>(p, st); break;
@@ -1048,8 +1035,8 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
 #undef CASE
         }
         HIP_TRY(hipGetLastError());
-        if (ev1) HIP_TRY(hipEventRecord(ev1, st));
     }
+    if (timed && (rc = p->timer.end(st, slot))) return rc;
     if (p->n_windows) {
         impop_window_stats *dst = d_out ? (impop_window_stats *)d_out : p->d_out;
         if (p->finalize_tpw == 1)
@@ -1094,7 +1081,7 @@ IMPOP_API int impop_scan_plan_timing(impop_scan_plan *p, int enable) {
     HIP_TRY(hipSetDevice(p->ctx->device));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
     p->timing = enable != 0;
-    p->events_used = 0;
+    p->timer.reset();
     return IMPOP_OK;
 }
 
@@ -1102,14 +1089,15 @@ IMPOP_API int impop_scan_plan_elapsed(impop_scan_plan *p, double *total_ms, uint
     REQUIRE(p, "impop_scan_plan_elapsed: plan is NULL");
     HIP_TRY(hipSetDevice(p->ctx->device));
     HIP_TRY(hipStreamSynchronize(p->ctx->stream));
-    double t = 0.0;
-    for (size_t i = 0; i < p->events_used; ++i) {
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, p->events[i].first, p->events[i].second));
-        t += (double)ms;
-    }
-    if (total_ms) *total_ms = t;
-    if (launches) *launches = p->events_used;
+    return p->timer.elapsed(total_ms, launches);
+}
+
+IMPOP_API int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]) {
+    REQUIRE(ctx && sizes, "impop_debug_timer_pool_sizes: NULL argument");
+    sizes[0] = ctx->gram_timer.pool.size();
+    sizes[1] = ctx->cluster_timer.pool.size();
+    sizes[2] = ctx->ehh_timer.pool.size();
+    sizes[3] = plan ? plan->timer.pool.size() : 0;
     return IMPOP_OK;
 }
 
@@ -1117,10 +1105,7 @@ IMPOP_API int impop_scan_plan_destroy(impop_scan_plan *p) {
     if (!p) return IMPOP_OK;
     hipSetDevice(p->ctx->device);
     hipStreamSynchronize(p->ctx->stream);
-    for (auto &e : p->events) {
-        hipEventDestroy(e.first);
-        hipEventDestroy(e.second);
-    }
+    p->timer.destroy();
     if (p->d_tiles) hipFree(p->d_tiles);
     if (p->d_parts) hipFree(p->d_parts);
     if (p->d_wins) hipFree(p->d_wins);
@@ -1155,10 +1140,11 @@ IMPOP_API int impop_site_counts(impop_ctx *ctx, const impop_matrix *m, const uin
     std::vector<uint32_t> mk;
     mask_to_dwords(mask, m->g.n_hap, m->g.wps, true, mk);
     void *d = nullptr;
-    const size_t mask_bytes = ((size_t)m->g.wps * 4 + 255) / 256 * 256;
-    int rc = ctx_scratch(ctx, mask_bytes + W * 4, &d);
+    Carve L;
+    const size_t o_mask = L.take<uint32_t>(m->g.wps), o_cnt = L.take<uint32_t>(W);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    uint32_t *d_mask = (uint32_t *)d, *d_cnt = (uint32_t *)((char *)d + mask_bytes);
+    uint32_t *d_mask = L.at<uint32_t>(d, o_mask), *d_cnt = L.at<uint32_t>(d, o_cnt);
     HIP_TRY(hipMemcpyAsync(d_mask, mk.data(), (size_t)m->g.wps * 4, hipMemcpyHostToDevice, ctx->stream));
     const uint64_t nb = (site_end + 63) / 64 - site_begin / 64;
     REQUIRE((nb + 3) / 4 < 0x7FFFFFFFull, "impop_site_counts: range too long");
@@ -1217,13 +1203,12 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
     rc = scan_route("impop_scan_multi", ctx, m, windows, n_windows, 0, rt);
     if (rc) return rc;
     const size_t nt = rt.tiles.size();
-    const auto up = round_up_256;
-    const size_t o_tiles = 0, o_wins = o_tiles + up(std::max<size_t>(nt, 1) * sizeof(ScanTile)),
-                 o_masks = o_wins + up(n_windows * sizeof(WinDesc)), o_n = o_masks + up(mk.size() * 4),
-                 o_parts = o_n + up(K * 4), o_out = o_parts + up(std::max<size_t>(nt, 1) * (K + NP) * 8),
-                 total = o_out + up(n_windows * NP * sizeof(impop_pair_stats));
+    Carve L;
+    const size_t o_tiles = L.take<ScanTile>(std::max<size_t>(nt, 1)), o_wins = L.take<WinDesc>(n_windows),
+                 o_masks = L.take<uint32_t>(mk.size()), o_n = L.take<uint32_t>(K),
+                 o_parts = L.take<uint64_t>(std::max<size_t>(nt, 1) * (K + NP)), o_out = L.take<impop_pair_stats>(n_windows * NP);
     void *d = nullptr;
-    rc = ctx_scratch(ctx, total, &d);
+    rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
     char *base = (char *)d;
     if (nt) HIP_TRY(hipMemcpyAsync(base + o_tiles, rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
@@ -1275,11 +1260,11 @@ IMPOP_API int impop_afs(impop_ctx *ctx, const impop_matrix *m, const impop_windo
     const uint32_t bins = popcount_vec(mk) + 1;
     REQUIRE((size_t)bins * 4 <= 64 * 1024, "impop_afs: more than 16383 haplotypes in the mask");
     HIP_TRY(hipSetDevice(ctx->device));
-    const auto up = round_up_256;
-    const size_t o_mask = 0, o_wins = up((size_t)m->g.wps * 4), o_out = o_wins + up(n_windows * sizeof(impop_window)),
-                 total = o_out + n_windows * bins * 4;
+    Carve L;
+    const size_t o_mask = L.take<uint32_t>(m->g.wps), o_wins = L.take<impop_window>(n_windows),
+                 o_out = L.take<uint32_t>(n_windows * bins);
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, total, &d);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
     char *base = (char *)d;
     HIP_TRY(hipMemcpyAsync(base + o_mask, mk.data(), (size_t)m->g.wps * 4, hipMemcpyHostToDevice, ctx->stream));

@@ -1314,7 +1314,7 @@ static size_t dynamic_lds_room(const void *kernel) {
 
 // which kernel variant a batch may take (pica2_kernel / hfst_kernel FAST): Gram problems, one matrix per problem at index p
 static int sim_batch_fast(const SimBatch &b) {
-    static const bool off = [] { const char *e = getenv("IMPOP_EPILOGUE_FAST"); return e && e[0] == '0'; }();  // A/B and test switch
+    static const bool off = env_is("IMPOP_EPILOGUE_FAST", '0');  // A/B and test switch
     if (off || !b.gram || b.dense || b.seg_first || b.seg_count) return 0;
     return b.g16 ? 1 : 2;
 }
@@ -1341,8 +1341,8 @@ int launch_pica2(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const u
     }
     Pica2Split split{nullptr, nullptr, nullptr};
     if (chunks > 1) {
-        const size_t tab_bytes = ((size_t)n_problems * (2ull * n_el + 4) * 4 + 255) / 256 * 256;
-        const size_t sum_bytes = ((size_t)n_problems * n_el * 8 + 255) / 256 * 256;
+        const size_t tab_bytes = round_up_256((size_t)n_problems * (2ull * n_el + 4) * 4);
+        const size_t sum_bytes = round_up_256((size_t)n_problems * n_el * 8);
         // seeds in position order (no set order handed in): the join tests of Step 1 go to pica2_adj_kernel, one bit each
         const size_t adj_bytes = (size_t)n_problems * n_el * bit_words(n_el) * 8;
         const bool bits = !d_order && n_el <= 8192 && adj_bytes <= ((size_t)2 << 30);
@@ -1489,43 +1489,29 @@ int launch_af_batch(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, cons
     return launch_af_general(ctx, b, n_problems, d_idx, m, threshold, d_adj, d_cluster_of, d_sizes, nullptr, d_rec);
 }
 
-// scratch carve helper
-struct Carve {
-    char *base;
-    size_t off = 0;
-    explicit Carve(void *p) : base((char *)p) {}
-    template <typename T>
-    T *take(size_t count) {
-        off = (off + 255) / 256 * 256;
-        T *p = reinterpret_cast<T *>(base + off);
-        off += count * sizeof(T);
-        return p;
-    }
-};
-static size_t carve_size(std::initializer_list<size_t> sizes) {
-    size_t t = 0;
-    for (size_t s : sizes) t = (t + 255) / 256 * 256 + s;
-    return t + 256;
+int seed_order_of(const uint32_t *seed_rank, const uint32_t *members, uint32_t m, std::vector<uint32_t> &order, uint32_t *dup) {
+    auto rank = [&](uint32_t k) { return seed_rank[members ? members[k] : k]; };  // members null: the elements 0..m themselves
+    order.resize(m);
+    for (uint32_t k = 0; k < m; ++k) order[k] = k;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return rank(x) < rank(y); });
+    for (uint32_t k = 1; k < m; ++k)
+        if (rank(order[k - 1]) == rank(order[k])) {
+            *dup = rank(order[k]);
+            return IMPOP_E_INVALID;
+        }
+    return IMPOP_OK;
 }
 
 }  // namespace impop
 
 using namespace impop;
 
-// seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list);
-// ranks only need to be distinct among the members
-static int seed_order_of(const uint32_t *seed_rank, const std::vector<uint32_t> &members, std::vector<uint32_t> &order,
-                         const char *fn) {
-    const uint32_t m = (uint32_t)members.size();
-    order.resize(m);
-    for (uint32_t k = 0; k < m; ++k) order[k] = k;
-    std::stable_sort(order.begin(), order.end(),
-                     [&](uint32_t x, uint32_t y) { return seed_rank[members[x]] < seed_rank[members[y]]; });
-    for (uint32_t k = 1; k < m; ++k)
-        REQUIRE(seed_rank[members[order[k - 1]]] != seed_rank[members[order[k]]],
-                "%s: seed_rank must be distinct among the elements it orders (rank %u occurs twice)", fn,
-                seed_rank[members[order[k]]]);
-    return IMPOP_OK;
+// seed_order_of for the single-problem entry points: their wording of a repeated rank
+static int seed_order_or_error(const uint32_t *seed_rank, const uint32_t *members, uint32_t m, std::vector<uint32_t> &order, const char *fn) {
+    uint32_t dup = 0;
+    const int rc = seed_order_of(seed_rank, members, m, order, &dup);
+    if (rc) set_error("%s: seed_rank must be distinct among the elements it orders (rank %u occurs twice)", fn, dup);
+    return rc;
 }
 
 IMPOP_API int impop_pi_from_identity(impop_ctx *ctx, const double *ident, uint32_t n, double threshold, int round_digits,
@@ -1537,21 +1523,20 @@ IMPOP_API int impop_pi_from_identity(impop_ctx *ctx, const double *ident, uint32
     HIP_TRY(hipSetDevice(ctx->device));
     std::vector<uint32_t> order;
     if (seed_rank && n) {
-        std::vector<uint32_t> all(n);
-        for (uint32_t i = 0; i < n; ++i) all[i] = i;
-        int rc0 = seed_order_of(seed_rank, all, order, "impop_pi_from_identity");
+        int rc0 = seed_order_or_error(seed_rank, nullptr, n, order, "impop_pi_from_identity");
         if (rc0) return rc0;
     }
     const size_t nn = (size_t)n * n;
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, carve_size({nn * 8, 8, sizeof(Pica2Out), (size_t)n * 4, (size_t)n * 4}), &d);
+    Carve L;
+    const size_t o_id = L.take<double>(nn ? nn : 1), o_L = L.take<uint64_t>(1), o_out = L.take<Pica2Out>(1),
+                 o_grp = L.take<uint32_t>(n ? n : 1), o_order = L.take<uint32_t>(n ? n : 1);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    double *d_id = cv.take<double>(nn ? nn : 1);
-    uint64_t *d_L = cv.take<uint64_t>(1);
-    Pica2Out *d_out = cv.take<Pica2Out>(1);
-    uint32_t *d_grp = cv.take<uint32_t>(n ? n : 1);
-    uint32_t *d_order = cv.take<uint32_t>(n ? n : 1);
+    double *d_id = L.at<double>(d, o_id);
+    uint64_t *d_L = L.at<uint64_t>(d, o_L);
+    Pica2Out *d_out = L.at<Pica2Out>(d, o_out);
+    uint32_t *d_grp = L.at<uint32_t>(d, o_grp), *d_order = L.at<uint32_t>(d, o_order);
     if (nn) HIP_TRY(hipMemcpyAsync(d_id, ident, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_L, &seq_len, 8, hipMemcpyHostToDevice, ctx->stream));
     if (!order.empty()) HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1615,12 +1600,14 @@ IMPOP_API int impop_pica2_pair_terms(impop_ctx *ctx, const double *ident, uint32
     const uint64_t np = (uint64_t)n_groups * (n_groups - 1) / 2;
     REQUIRE((np + 255) / 256 < 0x7FFFFFFFull, "impop_pica2_pair_terms: too many group pairs");
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, carve_size({nn * 8, (size_t)n_groups * 4, (size_t)n_groups * 4, np * 8, np * 8}), &d);
+    Carve L;
+    const size_t o_id = L.take<double>(nn), o_rep = L.take<uint32_t>(n_groups), o_sz = L.take<uint32_t>(n_groups),
+                 o_s = L.take<double>(np), o_v = L.take<double>(np);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    double *d_id = cv.take<double>(nn);
-    uint32_t *d_rep = cv.take<uint32_t>(n_groups), *d_sz = cv.take<uint32_t>(n_groups);
-    double *d_s = cv.take<double>(np), *d_v = cv.take<double>(np);
+    double *d_id = L.at<double>(d, o_id);
+    uint32_t *d_rep = L.at<uint32_t>(d, o_rep), *d_sz = L.at<uint32_t>(d, o_sz);
+    double *d_s = L.at<double>(d, o_s), *d_v = L.at<double>(d, o_v);
     HIP_TRY(hipMemcpyAsync(d_id, ident, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_rep, rep, (size_t)n_groups * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_sz, group_size, (size_t)n_groups * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1644,14 +1631,15 @@ IMPOP_API int impop_fst_from_identity(impop_ctx *ctx, const double *ident, uint3
     HIP_TRY(hipSetDevice(ctx->device));
     const size_t nn = (size_t)n * n;
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, carve_size({nn * 8, 8, sizeof(HfstOut), (size_t)n, (size_t)n}), &d);
+    Carve L;
+    const size_t o_id = L.take<double>(nn ? nn : 1), o_L = L.take<uint64_t>(1), o_out = L.take<HfstOut>(1),
+                 o_a = L.take<uint8_t>(n ? n : 1), o_b = L.take<uint8_t>(n ? n : 1);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    double *d_id = cv.take<double>(nn ? nn : 1);
-    uint64_t *d_L = cv.take<uint64_t>(1);
-    HfstOut *d_out = cv.take<HfstOut>(1);
-    uint8_t *d_a = cv.take<uint8_t>(n ? n : 1);
-    uint8_t *d_b = cv.take<uint8_t>(n ? n : 1);
+    double *d_id = L.at<double>(d, o_id);
+    uint64_t *d_L = L.at<uint64_t>(d, o_L);
+    HfstOut *d_out = L.at<HfstOut>(d, o_out);
+    uint8_t *d_a = L.at<uint8_t>(d, o_a), *d_b = L.at<uint8_t>(d, o_b);
     if (nn) HIP_TRY(hipMemcpyAsync(d_id, ident, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     if (n) {
         HIP_TRY(hipMemcpyAsync(d_a, in_a, n, hipMemcpyHostToDevice, ctx->stream));
@@ -1685,14 +1673,14 @@ IMPOP_API int impop_cluster_from_identity(impop_ctx *ctx, const double *ident, u
     const size_t nn = (size_t)n * n;
     const uint32_t words = (n + 31) / 32;
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, carve_size({nn * 8, (size_t)n * words * 4, (size_t)n * 4, (size_t)n * 4, 4}), &d);
+    Carve L;
+    const size_t o_id = L.take<double>(nn), o_adj = L.take<uint32_t>((size_t)n * words), o_cl = L.take<uint32_t>(n),
+                 o_sz = L.take<uint32_t>(n), o_k = L.take<uint32_t>(1);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    double *d_id = cv.take<double>(nn);
-    uint32_t *d_adj = cv.take<uint32_t>((size_t)n * words);
-    uint32_t *d_cl = cv.take<uint32_t>(n);
-    uint32_t *d_sz = cv.take<uint32_t>(n);
-    uint32_t *d_k = cv.take<uint32_t>(1);
+    double *d_id = L.at<double>(d, o_id);
+    uint32_t *d_adj = L.at<uint32_t>(d, o_adj), *d_cl = L.at<uint32_t>(d, o_cl), *d_sz = L.at<uint32_t>(d, o_sz),
+             *d_k = L.at<uint32_t>(d, o_k);
     HIP_TRY(hipMemcpyAsync(d_id, ident, nn * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(d_sz, 0, (size_t)n * 4, ctx->stream));
     SimBatch b{};
@@ -1721,12 +1709,13 @@ IMPOP_API int impop_tajimas_d(impop_ctx *ctx, const int64_t *n, const double *S,
     }
     HIP_TRY(hipSetDevice(ctx->device));
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, carve_size({count * 8, count * 8, count * 8, count * 8, count * 80}), &d);
+    Carve L;
+    const size_t o_n = L.take<int64_t>(count), o_S = L.take<double>(count), o_pi = L.take<double>(count), o_D = L.take<double>(count),
+                 o_c = L.take<double>(count * 10);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    int64_t *d_n = cv.take<int64_t>(count);
-    double *d_S = cv.take<double>(count), *d_pi = cv.take<double>(count), *d_D = cv.take<double>(count);
-    double *d_c = cv.take<double>(count * 10);
+    int64_t *d_n = L.at<int64_t>(d, o_n);
+    double *d_S = L.at<double>(d, o_S), *d_pi = L.at<double>(d, o_pi), *d_D = L.at<double>(d, o_D), *d_c = L.at<double>(d, o_c);
     HIP_TRY(hipMemcpyAsync(d_n, n, count * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_S, S, count * 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_pi, pi, count * 8, hipMemcpyHostToDevice, ctx->stream));
@@ -1747,10 +1736,11 @@ IMPOP_API int impop_py_round(impop_ctx *ctx, const double *x, uint64_t count, in
     REQUIRE(ndigits >= 0 && ndigits <= 19, "impop_py_round: ndigits must be 0..19");
     HIP_TRY(hipSetDevice(ctx->device));
     void *d = nullptr;
-    int rc = ctx_scratch(ctx, carve_size({count * 8, count * 8}), &d);
+    Carve L;
+    const size_t o_x = L.take<double>(count), o_o = L.take<double>(count);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    double *d_x = cv.take<double>(count), *d_o = cv.take<double>(count);
+    double *d_x = L.at<double>(d, o_x), *d_o = L.at<double>(d, o_o);
     HIP_TRY(hipMemcpyAsync(d_x, x, count * 8, hipMemcpyHostToDevice, ctx->stream));
     REQUIRE((count + 255) / 256 < 0x7FFFFFFFull, "impop_py_round: too many values");
     hipLaunchKernelGGL(py_round_kernel, dim3((uint32_t)((count + 255) / 256)), dim3(256), 0, ctx->stream, d_x, count,
@@ -1781,19 +1771,20 @@ IMPOP_API int impop_fst_grouped_from_identity(impop_ctx *ctx, const double *iden
     void *d = nullptr;
     std::vector<uint32_t> oa, ob;
     if (seed_rank) {
-        int rc0 = seed_order_of(seed_rank, ia, oa, "impop_fst_grouped_from_identity");
-        if (!rc0) rc0 = seed_order_of(seed_rank, ib, ob, "impop_fst_grouped_from_identity");
+        int rc0 = seed_order_or_error(seed_rank, ia.data(), ma, oa, "impop_fst_grouped_from_identity");
+        if (!rc0) rc0 = seed_order_or_error(seed_rank, ib.data(), mb, ob, "impop_fst_grouped_from_identity");
         if (rc0) return rc0;
     }
-    int rc = ctx_scratch(ctx, carve_size({nn * 8, 8, sizeof(HfstOut), (size_t)ma * 4, (size_t)mb * 4, (size_t)ma * 4,
-                                          (size_t)mb * 4}), &d);
+    Carve L;
+    const size_t o_id = L.take<double>(nn ? nn : 1), o_L = L.take<uint64_t>(1), o_out = L.take<HfstOut>(1),
+                 o_ia = L.take<uint32_t>(ma ? ma : 1), o_ib = L.take<uint32_t>(mb ? mb : 1), o_oa = L.take<uint32_t>(ma ? ma : 1),
+                 o_ob = L.take<uint32_t>(mb ? mb : 1);
+    int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
-    Carve cv(d);
-    double *d_id = cv.take<double>(nn ? nn : 1);
-    uint64_t *d_L = cv.take<uint64_t>(1);
-    HfstOut *d_out = cv.take<HfstOut>(1);
-    uint32_t *d_ia = cv.take<uint32_t>(ma ? ma : 1), *d_ib = cv.take<uint32_t>(mb ? mb : 1);
-    uint32_t *d_oa = cv.take<uint32_t>(ma ? ma : 1), *d_ob = cv.take<uint32_t>(mb ? mb : 1);
+    double *d_id = L.at<double>(d, o_id);
+    uint64_t *d_L = L.at<uint64_t>(d, o_L);
+    HfstOut *d_out = L.at<HfstOut>(d, o_out);
+    uint32_t *d_ia = L.at<uint32_t>(d, o_ia), *d_ib = L.at<uint32_t>(d, o_ib), *d_oa = L.at<uint32_t>(d, o_oa), *d_ob = L.at<uint32_t>(d, o_ob);
     if (!oa.empty()) HIP_TRY(hipMemcpyAsync(d_oa, oa.data(), (size_t)ma * 4, hipMemcpyHostToDevice, ctx->stream));
     if (!ob.empty()) HIP_TRY(hipMemcpyAsync(d_ob, ob.data(), (size_t)mb * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nn) HIP_TRY(hipMemcpyAsync(d_id, ident, nn * 8, hipMemcpyHostToDevice, ctx->stream));

@@ -270,14 +270,15 @@ struct ChunkLayout {  // one device (and one pinned host) allocation per chunk, 
     size_t down_bytes() const { return total - recs; }  // records + group indices: the download
 };
 ChunkLayout chunk_layout(size_t mat_el, size_t k, size_t n_order, size_t n_flag, size_t n_grp) {
+    Carve cv;
     ChunkLayout L;
-    L.mats = 0;
-    L.descs = round_up_256(mat_el * 8);
-    L.u32tab = L.descs + round_up_256(k * sizeof(BatchDesc));
-    L.flags = L.u32tab + round_up_256(n_order * 4);
-    L.recs = L.flags + round_up_256(n_flag);
-    L.groups = L.recs + round_up_256(k * sizeof(impop_identity_stats));
-    L.total = L.groups + round_up_256(n_grp * 4);
+    L.mats = cv.take<double>(mat_el);
+    L.descs = cv.take<BatchDesc>(k);
+    L.u32tab = cv.take<uint32_t>(n_order);
+    L.flags = cv.take<uint8_t>(n_flag);
+    L.recs = cv.take<impop_identity_stats>(k);
+    L.groups = cv.take<uint32_t>(n_grp);
+    L.total = cv.total();
     return L;
 }
 
@@ -316,7 +317,7 @@ IMPOP_API int impop_stats_from_identity_batch(impop_ctx *ctx, const impop_identi
     HIP_TRY(hipSetDevice(ctx->device));
     // chunks are capped by the bytes they upload; default: what the context's scratch already holds, at least 128 MiB
     const size_t cap = P.max_chunk_bytes ? (size_t)P.max_chunk_bytes : std::max<size_t>(ctx->scratch_bytes, (size_t)128 << 20);
-    static const bool trace = [] { const char *e = getenv("IMPOP_TRACE"); return e && e[0] == '1'; }();
+    const bool trace = trace_on();
     std::vector<uint64_t> grp_base(k + 1, 0);  // where each problem's group indices start in the caller's array
     for (uint64_t p = 0; p < k; ++p) grp_base[p + 1] = grp_base[p] + problems[p].n;
     std::vector<uint32_t> order;
@@ -373,13 +374,10 @@ IMPOP_API int impop_stats_from_identity_batch(impop_ctx *ctx, const impop_identi
             const size_t nn = (size_t)q.n * q.n;
             if (nn) memcpy(h_mats + mo, q.ident, nn * 8);
             if (q.seed_rank && q.n) {  // seed_rank -> order (inverse permutation); ranks must be distinct
-                order.resize(q.n);
-                for (uint32_t i = 0; i < q.n; ++i) order[i] = i;
-                std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return q.seed_rank[x] < q.seed_rank[y]; });
-                for (uint32_t i = 1; i < q.n; ++i)
-                    REQUIRE(q.seed_rank[order[i - 1]] != q.seed_rank[order[i]],
-                            "impop_stats_from_identity_batch: problem %llu: seed_rank must be distinct (rank %u occurs twice)",
-                            (unsigned long long)p, q.seed_rank[order[i]]);
+                uint32_t dup = 0;
+                REQUIRE(seed_order_of(q.seed_rank, nullptr, q.n, order, &dup) == IMPOP_OK,
+                        "impop_stats_from_identity_batch: problem %llu: seed_rank must be distinct (rank %u occurs twice)",
+                        (unsigned long long)p, dup);
                 memcpy(h_u32 + oo, order.data(), (size_t)q.n * 4);
                 d.order_off = (uint32_t)oo;
                 oo += q.n;

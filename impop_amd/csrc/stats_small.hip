@@ -693,7 +693,7 @@ __global__ __launch_bounds__(SM_T, 4) void af_small_kernel(SimBatch batch, const
 // 16 bits (g16; they imply W < 2^16) or of 32 bits with a stated largest W below 2^30 (Hamming distances are formed in 32-bit
 // arithmetic), element offsets inside a matrix in 32 bits (elements and positions in 16)
 bool small_params(int kind, uint32_t ld, bool g16, uint64_t max_W) {
-    static const bool off = [] { const char *e = getenv("IMPOP_EPILOGUE_SMALL"); return e && e[0] == '0'; }();  // A/B and test switch
+    static const bool off = env_is("IMPOP_EPILOGUE_SMALL", '0');  // A/B and test switch
     const bool w_ok = g16 || (max_W != 0 && max_W < (1ull << 30));
     return !off && w_ok && kind == IMPOP_IDENTITY_MATCH && ld <= 4096;
 }

@@ -433,6 +433,9 @@ int impop_ctx_gram_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches)
 /* With the same switch on, impop_cluster_scan also brackets its clustering kernel(s): their summed time and number of
  * chunks since enable / reset, next to the Gram time above. */
 int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
+/* Test aid: how many event pairs the four timers hold (created on first timed use, kept for reuse): sizes[0..2] = the
+ * context's Gram / clustering / EHH timers, sizes[3] = the plan's (plan nullable: 0).  Nothing is created while timing is off. */
+int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]);
 
 /* impop_pairwise_scan over several devices, sharded like impop_scan_sharded (declared with the multi-GPU entry points
  * above; run_pica2_impg.sh:125-236 / run_h-fst.sh:155-190 with thresholds):

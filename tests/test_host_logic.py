@@ -2,6 +2,7 @@
 library loads and exports every declared symbol (no compute without a GPU)."""
 import os
 import re
+import shutil
 import subprocess
 
 import numpy as np
@@ -220,3 +221,35 @@ def test_batch_driver_bed_warnings_are_the_reference_drivers(tmp_path, capsys):
         err = capsys.readouterr().err.strip().split("\n")
         assert err == lines, (fmt, err)
     assert mod.threshold_arg("0.9990") == (0.999, "0.9990") and mod.round_arg("none") == "none" and mod.round_arg("5") == 5
+
+
+# ---- csrc/carve.h: the one scratch carver (plain C++, no HIP, no GPU) ---------------------------------------------------
+
+@pytest.fixture(scope="module")
+def carve_exe(tmp_path_factory):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path_factory.mktemp("carve") / "carve_layout")
+    r = subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-I" + os.path.join(ROOT, "impop_amd", "csrc"), "-x", "c++", os.path.join(ROOT, "tests", "fuzz", "carve_layout.cc"),
+                        "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return exe
+
+
+@pytest.mark.parametrize("sizes", [[1, 255, 256, 257, 4096, 3], [0, 0, 8, 0, 1000, 0], [0], [], [768, 0, 0]])
+def test_carve_layout(carve_exe, sizes):
+    """Offsets are multiples of 256, in order and non-overlapping; total() covers the last region; a zero-sized region gets a valid
+    offset (that of whatever follows it) inside total(); the same sizes give the same layout (the driver builds it twice and, under
+    ASan + UBSan, fills every region to its last byte)."""
+    r = subprocess.run([carve_exe] + [str(s) for s in sizes], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-4000:])
+    *off, total = [int(x) for x in r.stdout.split()]
+    assert len(off) == len(sizes) and total % 256 == 0
+    end = 0
+    for o, s in zip(off, sizes):
+        assert o % 256 == 0 and o >= end and o - end < 256  # aligned, behind the region before it, no gap of a whole unit
+        end = o + s
+        assert end <= total
+    assert total - end < 256
