@@ -70,6 +70,15 @@ class PairwiseStats(C.Structure):
                 ("n_sites", C.c_uint32), ("reserved", C.c_uint64)]
 
 
+class PanelStats(C.Structure):
+    _fields_ = [("pi", C.c_double), ("pi_site", C.c_double), ("tajima_d", C.c_double), ("n_members", C.c_uint32),
+                ("n_groups", C.c_uint32), ("s_p", C.c_uint32), ("reserved", C.c_uint32), ("reserved2", C.c_uint64)]
+
+
+class PanelWindow(C.Structure):
+    _fields_ = [("n_sites", C.c_uint32), ("s_all", C.c_uint32)]
+
+
 class ClusterParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("identity_kind", C.c_int32), ("threshold", C.c_double),
                 ("round_digits", C.c_int32), ("reserved", C.c_uint32)]
@@ -118,6 +127,7 @@ class IdentityBatchParams(C.Structure):
 assert C.sizeof(IdentityStats) == 144 and C.sizeof(IdentityProblem) == 64 and C.sizeof(IdentityBatchParams) == 32
 assert C.sizeof(WindowStats) == 128 and C.sizeof(Window) == 24 and C.sizeof(PairwiseStats) == 96
 assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
+assert C.sizeof(PanelStats) == 48 and C.sizeof(PanelWindow) == 8
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
 
 _vp = C.c_void_p
@@ -182,6 +192,8 @@ SIGNATURES = {
     "impop_pairwise_identity": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_int, _f64p]),
     "impop_pairwise_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, _u64p, _u64p,
                                       C.POINTER(PairwiseParams), C.POINTER(PairwiseStats)]),
+    "impop_pairwise_scan_panel": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairwiseParams),
+                                            C.POINTER(PanelStats), C.POINTER(PairStats), C.POINTER(PanelWindow)]),
     "impop_cluster_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(ClusterParams),
                                      C.POINTER(ClusterStats), _u32p, _u32p]),
     "impop_pi_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, C.c_double, C.c_int, C.c_uint64, _u32p, _f64p, _f64p, _u32p, _u32p,

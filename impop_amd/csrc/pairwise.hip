@@ -1300,7 +1300,261 @@ struct ClusterEpilogue final : PairEpilogue {
         }
     }
 };
+// impop_pairwise_scan_panel's records from the per-panel pica2 results, the per-pair Fst results and the window's S / W: one thread
+// per (window, panel or pair); the arithmetic of a panel record is pairwise_finalize_kernel's with nP = the panel's size
+struct PanelFinalIn {
+    const Pica2Out *pica;            // panel k of problem w at k * stride + w
+    const HfstOut *hfst;             // pair p of problem w at p * stride + w; nullptr: no pair records asked for
+    const impop_window_stats *scan;  // n_sites, and s_all from the site bitmap (s_scope 0, 1)
+    const uint32_t *s_p;             // s_scope 1: panel k of problem w at k * stride + w
+    const double *taj;               // a1,a2,b1,b2,c1,c2,e1,e2 per panel
+    const uint32_t *n_members;       // per panel
+    uint64_t stride;
+};
+__global__ void panel_finalize_kernel(PanelFinalIn in, uint64_t n_windows, uint32_t K, int d_pi_mode, int s_scope,
+                                      impop_panel_stats *__restrict__ out_panels, impop_pair_stats *__restrict__ out_pairs,
+                                      impop_panel_window *__restrict__ out_windows) {
+    const uint32_t NP = in.hfst ? K * (K - 1) / 2 : 0u, items = K + NP;
+    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_windows * items) return;
+    const uint64_t w = t / items;
+    const uint32_t j = (uint32_t)(t % items);
+    if (j >= K) {
+        const HfstOut h = in.hfst[(uint64_t)(j - K) * in.stride + w];
+        impop_pair_stats r;
+        r.fst = h.v[0]; r.pi_a = h.v[1]; r.pi_b = h.v[2]; r.pi_xy = h.v[3]; r.dxy = h.v[4]; r.da = h.v[5];
+        out_pairs[w * NP + (j - K)] = r;
+        return;
+    }
+    const impop_window_stats s = in.scan[w];
+    if (j == 0) out_windows[w] = impop_panel_window{s.n_sites, s.s_all};
+    const Pica2Out p = in.pica[(uint64_t)j * in.stride + w];
+    const uint32_t nP = in.n_members[j], sp = s_scope == 1 ? in.s_p[(uint64_t)j * in.stride + w] : 0u;
+    impop_panel_stats r;
+    r.pi = p.pi; r.pi_site = p.pi_site;
+    r.n_members = nP; r.n_groups = p.n_groups; r.s_p = sp; r.reserved = 0; r.reserved2 = 0;
+    const double S = (double)(s_scope == 1 ? sp : s.s_all);
+    const double pin = d_pi_mode == 0 ? py_round(p.pi_site, 8) : d_pi_mode == 1 ? p.pi_site : p.pi * (double)s.n_sites;
+    double D = __builtin_nan("");
+    if (s_scope != 2 && nP >= 2 && pin == pin && pin >= 0) {
+        const double *tj = in.taj + 8 * j;
+        TajConsts c;
+        c.a1 = tj[0]; c.a2 = tj[1]; c.b1 = tj[2]; c.b2 = tj[3]; c.c1 = tj[4]; c.c2 = tj[5]; c.e1 = tj[6]; c.e2 = tj[7];
+        D = tajima_d_from(c, S, pin, nullptr, nullptr);
+    }
+    r.tajima_d = D;
+    out_panels[w * K + j] = r;
+}
+
+// impop_pairwise_scan_panel's epilogue: K panels and their K (K - 1) / 2 pairs on the chunk's ONE set of Gram matrices — pica2 per
+// panel on the side stream, next to it the Fst sums of all pairs (one launch of hfst_panel_small_kernel on the window-statistics
+// shape; launch_hfst per pair on every other), then the records
+struct PanelEpilogue final : PairEpilogue {
+    const impop_pairwise_params *params;
+    uint32_t n, K, NP;                      // NP = 0: no pair records asked for
+    const std::vector<uint32_t> *idx;       // the panels' members back to back, each ascending
+    const std::vector<uint32_t> *sizes;     // members per panel
+    const std::vector<uint8_t> *cls;        // class of haplotype i, 0xFF: none
+    const std::vector<uint32_t> *sp_host;   // s_scope 1: K x n_windows, panel-major; else nullptr
+    uint64_t n_windows;
+    impop_panel_stats *out_panels;
+    impop_pair_stats *out_pairs;
+    impop_panel_window *out_windows;
+    bool traced = false;
+    uint64_t cap = 0;
+    Pica2Out *d_p = nullptr;
+    HfstOut *d_h = nullptr;
+    impop_panel_stats *d_opan = nullptr;
+    impop_pair_stats *d_opair = nullptr;
+    impop_panel_window *d_owin = nullptr;
+    uint32_t *d_idx = nullptr, *d_sizes = nullptr, *d_sp = nullptr;
+    uint8_t *d_cls = nullptr, *d_flags = nullptr;  // d_flags: K x n membership flags (the general route's in_a / in_b)
+    double *d_taj = nullptr;
+    std::vector<uint32_t> sp_chunk;
+    // the member list, sizes, Tajima constants, classes and flags, plus the layout's alignment gaps (fifteen sub-buffers)
+    static size_t fixed_bytes(uint32_t n, uint32_t K) {
+        return round_up_256((size_t)(n ? n : 1) * 4) + 2 * round_up_256((size_t)K * 8 * 8) + round_up_256(n ? n : 1) +
+               round_up_256((size_t)K * (n ? n : 1)) + 16 * 256;
+    }
+    static size_t window_bytes(uint32_t K, uint32_t NP) {
+        return (size_t)K * (sizeof(Pica2Out) + sizeof(impop_panel_stats) + 4) + (size_t)NP * (sizeof(HfstOut) + sizeof(impop_pair_stats)) +
+               sizeof(impop_panel_window);
+    }
+    static size_t staged_bytes(uint32_t K, uint32_t NP) {
+        return (size_t)K * sizeof(impop_panel_stats) + (size_t)NP * sizeof(impop_pair_stats) + sizeof(impop_panel_window);
+    }
+    int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap_) override {
+        cap = cap_;
+        Carve L;
+        d_idx = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
+        d_sizes = L.at<uint32_t>(d_epi, L.take<uint32_t>(K));
+        d_taj = L.at<double>(d_epi, L.take<double>((size_t)K * 8));
+        d_cls = L.at<uint8_t>(d_epi, L.take<uint8_t>(n ? n : 1));
+        d_flags = L.at<uint8_t>(d_epi, L.take<uint8_t>((size_t)K * (n ? n : 1)));
+        d_p = L.at<Pica2Out>(d_epi, L.take<Pica2Out>(cap * K));
+        d_h = L.at<HfstOut>(d_epi, L.take<HfstOut>(cap * NP));
+        d_opan = L.at<impop_panel_stats>(d_epi, L.take<impop_panel_stats>(cap * K));
+        d_opair = L.at<impop_pair_stats>(d_epi, L.take<impop_pair_stats>(cap * NP));
+        d_owin = L.at<impop_panel_window>(d_epi, L.take<impop_panel_window>(cap));
+        d_sp = L.at<uint32_t>(d_epi, L.take<uint32_t>(cap * K));
+        if (!idx->empty()) HIP_TRY(hipMemcpyAsync(d_idx, idx->data(), idx->size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_sizes, sizes->data(), (size_t)K * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_cls, cls->data(), n, hipMemcpyHostToDevice, ctx->stream));
+        flags_host.assign((size_t)K * n, 0);
+        for (uint32_t i = 0; i < n; ++i)
+            if ((*cls)[i] < K) flags_host[(size_t)(*cls)[i] * n + i] = 1;
+        HIP_TRY(hipMemcpyAsync(d_flags, flags_host.data(), flags_host.size(), hipMemcpyHostToDevice, ctx->stream));
+        for (uint32_t k = 0; k < K; ++k) {  // the context caches the constants of ONE n: each panel's are copied out behind their kernel
+            const int rc = ensure_tajima_consts(ctx, (*sizes)[k] >= 2 ? (int64_t)(*sizes)[k] : 2);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(d_taj + 8 * k, ctx->d_taj, 8 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        return IMPOP_OK;
+    }
+    std::vector<uint8_t> flags_host;
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const SimBatch &b = c.b;
+        const uint64_t cnt = c.cnt;
+        const bool small = hfst_panel_small_applies(b);
+        if (!traced && trace_on())
+            fprintf(stderr, "[impop_pairwise_scan_panel] pops=%u pairs=%u route=%s\n", K, K * (K - 1) / 2, small ? "small" : "general");
+        traced = true;
+        if (!ctx->side) {
+            HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+        }
+        if (sp_host) {  // s_scope 1: the chunk's rows of the streaming scan's s_p, in the chunk's problem order
+            sp_chunk.resize((size_t)K * cap);
+            for (uint32_t k = 0; k < K; ++k)
+                for (uint64_t i = 0; i < cnt; ++i) sp_chunk[(size_t)k * cap + i] = (*sp_host)[(size_t)k * n_windows + c.ord[i]];
+            HIP_TRY(hipMemcpyAsync(d_sp, sp_chunk.data(), (size_t)K * cap * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
+        HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+        hipStream_t main_stream = ctx->stream;
+        ctx->stream = ctx->side;
+        int rc = IMPOP_OK;
+        for (uint32_t k = 0, at = 0; k < K && !rc; at += (*sizes)[k], ++k)
+            rc = launch_pica2(ctx, b, cnt, d_idx + at, (*sizes)[k], nullptr, params->threshold, c.d_L, d_p + (uint64_t)k * cap, nullptr);
+        ctx->stream = main_stream;
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->side));
+        if (NP) {
+            size_t slot = 0;  // impop_ctx_gram_timing: the Fst kernel(s) of the chunk between two events (impop_ctx_cluster_elapsed)
+            if (ctx->gram_timing && (rc = ctx->cluster_timer.begin(ctx->stream, &slot))) return rc;
+            if (small) {
+                rc = launch_hfst_panel_small(ctx, b, cnt, d_cls, K, c.d_L, d_h, cap);
+            } else {
+                uint32_t p = 0;
+                for (uint32_t a = 0; a < K && !rc; ++a)
+                    for (uint32_t bb = a + 1; bb < K && !rc; ++bb, ++p)
+                        rc = launch_hfst(ctx, b, cnt, d_flags + (size_t)a * n, d_flags + (size_t)bb * n, c.d_L, d_h + (uint64_t)p * cap);
+            }
+            if (rc) return rc;
+            if (ctx->gram_timing && (rc = ctx->cluster_timer.end(ctx->stream, slot))) return rc;
+        }
+        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+        PanelFinalIn in{d_p, NP ? d_h : nullptr, c.d_s, sp_host ? d_sp : nullptr, d_taj, d_sizes, cap};
+        const uint64_t items = cnt * (K + NP);
+        hipLaunchKernelGGL(panel_finalize_kernel, dim3((uint32_t)((items + 127) / 128)), dim3(128), 0, ctx->stream, in, cnt, K,
+                           params->d_pi_mode, params->s_scope, d_opan, d_opair, d_owin);
+        HIP_TRY(hipGetLastError());
+        char *h = reinterpret_cast<char *>(c.h_out);
+        HIP_TRY(hipMemcpyAsync(h, d_opan, cnt * K * sizeof(impop_panel_stats), hipMemcpyDeviceToHost, ctx->stream));
+        h += cnt * K * sizeof(impop_panel_stats);
+        if (NP) HIP_TRY(hipMemcpyAsync(h, d_opair, cnt * NP * sizeof(impop_pair_stats), hipMemcpyDeviceToHost, ctx->stream));
+        h += cnt * NP * sizeof(impop_pair_stats);
+        HIP_TRY(hipMemcpyAsync(h, d_owin, cnt * sizeof(impop_panel_window), hipMemcpyDeviceToHost, ctx->stream));
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        const char *h = reinterpret_cast<const char *>(c.h_out);
+        const impop_panel_stats *pv = reinterpret_cast<const impop_panel_stats *>(h);
+        const impop_pair_stats *qv = reinterpret_cast<const impop_pair_stats *>(h + c.cnt * K * sizeof(impop_panel_stats));
+        const impop_panel_window *wv =
+            reinterpret_cast<const impop_panel_window *>(h + c.cnt * (K * sizeof(impop_panel_stats) + NP * sizeof(impop_pair_stats)));
+        for (uint64_t k = 0; k < c.cnt; ++k) {
+            memcpy(out_panels + c.ord[k] * K, pv + k * K, (size_t)K * sizeof(impop_panel_stats));
+            if (NP) memcpy(out_pairs + c.ord[k] * NP, qv + k * NP, (size_t)NP * sizeof(impop_pair_stats));
+            if (out_windows) out_windows[c.ord[k]] = wv[k];
+        }
+    }
+};
 }  // namespace
+static_assert(sizeof(impop_panel_stats) == 48 && sizeof(impop_panel_window) == 8 && sizeof(impop_pair_stats) == 48, "fixed record layouts");
+
+IMPOP_API int impop_pairwise_scan_panel(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                        const uint64_t *masks, uint32_t n_pop, const impop_pairwise_params *params,
+                                        impop_panel_stats *out_panels, impop_pair_stats *out_pairs, impop_panel_window *out_windows) {
+    const char *fn = "impop_pairwise_scan_panel";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_pairwise_params), "impop_pairwise_params.struct_size mismatch");
+    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE, "%s: unknown identity kind", fn);
+    REQUIRE(params->round_digits <= 19, "%s: round_digits > 19 unsupported", fn);
+    REQUIRE(params->d_pi_mode >= 0 && params->d_pi_mode <= 2 && params->s_scope >= 0 && params->s_scope <= 2, "%s: bad d_pi_mode / s_scope", fn);
+    REQUIRE(params->fst_method <= 1, "%s: fst_method must be 0 (direct)", fn);
+    if (params->fst_method == 1) {
+        set_error("%s: fst_method 1 (hud.py grouped) is not available for panels; use impop_pairwise_scan per pair", fn);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    REQUIRE(n_pop >= 2 && n_pop <= 8, "%s: n_pop must be 2..8", fn);
+    REQUIRE(masks, "%s: masks is NULL", fn);
+    const uint32_t n = m->g.n_hap, K = n_pop, mwords = (n + 63) / 64;
+    std::vector<uint8_t> cls(n, 0xFF);
+    std::vector<uint32_t> idx, sizes(K, 0);
+    for (uint32_t k = 0; k < K; ++k) {
+        const uint64_t *mk = masks + (size_t)k * mwords;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (!((mk[i >> 6] >> (i & 63)) & 1ull)) continue;
+            // h-fst.py:181-185 removes shared members per pair, which would make a panel's size depend on the pair
+            REQUIRE(cls[i] == 0xFF, "%s: populations must be disjoint (population %u overlaps population %u)", fn, k, (uint32_t)cls[i]);
+            cls[i] = (uint8_t)k;
+            idx.push_back(i);
+            ++sizes[k];
+        }
+        REQUIRE(sizes[k] > 0, "%s: population %u is empty", fn, k);
+    }
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_panels, "%s: NULL windows/out", fn);
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, fn);
+        if (rc) return rc;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = IMPOP_OK;
+    // s_scope 1: s_p of every panel from the streaming scan of the same windows — one plan, its subset mask swapped per panel
+    std::vector<uint32_t> sp_host;
+    if (params->s_scope == 1) {
+        impop_scan_params sp;
+        sp.struct_size = sizeof sp; sp.d_pi_mode = params->d_pi_mode; sp.s_scope = 1; sp.tile_blocks = 0;
+        impop_scan_plan *plan = nullptr;
+        rc = impop_scan_plan_create(ctx, m, windows, n_windows, masks, nullptr, nullptr, &sp, &plan);
+        if (rc) return rc;
+        std::vector<impop_window_stats> rec(n_windows);
+        sp_host.resize((size_t)K * n_windows);
+        for (uint32_t k = 0; k < K && !rc; ++k) {
+            rc = impop_scan_plan_set_masks(plan, masks + (size_t)k * mwords, nullptr, nullptr);
+            if (!rc) rc = impop_scan_plan_launch(plan, nullptr);
+            if (!rc) rc = impop_scan_plan_fetch(plan, rec.data());
+            for (uint64_t i = 0; i < n_windows && !rc; ++i) sp_host[(size_t)k * n_windows + i] = rec[i].s_p;
+        }
+        impop_scan_plan_destroy(plan);
+        if (rc) return rc;
+    }
+    const bool use_segmap = params->s_scope != 2;  // s_all of every window from the matrix's cached site bitmap
+    if (use_segmap && (rc = ensure_segmap(ctx, m))) return rc;
+    PanelEpilogue epi;
+    epi.params = params; epi.n = n; epi.K = K; epi.NP = out_pairs ? K * (K - 1) / 2 : 0u;
+    epi.idx = &idx; epi.sizes = &sizes; epi.cls = &cls; epi.sp_host = params->s_scope == 1 ? &sp_host : nullptr;
+    epi.n_windows = n_windows; epi.out_panels = out_panels; epi.out_pairs = out_pairs; epi.out_windows = out_windows;
+    PairFront in{};
+    in.fn = fn; in.identity_kind = params->identity_kind; in.round_digits = params->round_digits;
+    in.scan_host = nullptr; in.use_segmap = use_segmap;
+    in.epi_fixed = PanelEpilogue::fixed_bytes(n, K); in.epi_per_window = PanelEpilogue::window_bytes(K, epi.NP);
+    in.out_per_window = PanelEpilogue::staged_bytes(K, epi.NP);
+    return pairwise_front(ctx, m, windows, n_windows, in, epi);
+}
 
 IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                                   const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,

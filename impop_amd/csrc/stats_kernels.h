@@ -210,6 +210,14 @@ int launch_pica2_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, c
 int launch_hfst_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint8_t *d_in_a, const uint8_t *d_in_b,
                       const uint64_t *d_seq_len, HfstOut *d_out);
 
+// h-fst for K disjoint classes from ONE read of the union's upper triangle (impop_pairwise_scan_panel), on the same shape as
+// launch_hfst_small: d_cls[i] = class of sequence i (0 .. n_pop - 1; anything larger: in no class), n_pop 2..8.  Pair p = (a, b),
+// a < b, in the order (0,1),(0,2),..,(1,2),.. of problem w goes to d_out[p * pair_stride + w] (pair_stride >= n_problems): the
+// layout n_pop (n_pop - 1) / 2 calls of launch_hfst with d_out + p * pair_stride produce on every other shape.
+bool hfst_panel_small_applies(const SimBatch &b);
+int launch_hfst_panel_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint8_t *d_cls, uint32_t n_pop,
+                            const uint64_t *d_seq_len, HfstOut *d_out, uint64_t pair_stride);
+
 // d_order (nullable): seed order of the greedy grouping as positions into the element list (stats.hip greedy_groups)
 int launch_pica2(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t n_el,
                  const uint32_t *d_order, double threshold, const uint64_t *d_seq_len, Pica2Out *d_out,

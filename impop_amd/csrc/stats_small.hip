@@ -262,6 +262,172 @@ __global__ __launch_bounds__(SM_T, SEG ? 4 : 5) void hfst_small_kernel(SimBatch 
 }
 
 // ---------------------------------------------------------------------------------------
+// h-fst for K disjoint classes at once (impop_pairwise_scan_panel): the union's upper triangle is read ONCE and yields the K
+// within-class and the K (K - 1) / 2 between-class sums of 1 - identity that hfst_small_kernel would form in one pass per pair.
+// The member list is class-major (class 0 ascending, class 1 ascending, ...), so a pair (list index q, list index p > q) has
+// class(q) <= class(p): its sum is T[class(q)][class(p)].  Rows and loads as hfst_small_rows; what is new is the bookkeeping:
+//  - a 64-wide word of the list may straddle class boundaries: the class of this lane's position in word k is nibble k of `cpk`
+//    (15: past the list);
+//  - a wave's rows q = wave + 4 r ascend, so they pass through the classes in order: accR[k] sums the CURRENT row class by
+//    word, and at each (wave-uniform) change of row class the lanes' sums are split by column class — words in order 0, 1, .. —
+//    reduced with the wave butterfly and written to tab[wave][row class][column class], an entry only this wave writes, once.
+// The four waves' tables are added in wave order at the end: no floating-point atomics, one fixed order of additions whatever
+// the chunk, the count width or the number of segments.
+constexpr uint32_t PANEL_MAX_K = 8;
+template <uint32_t NWK, int U, bool SEG, typename CT>
+__device__ __forceinline__ void hfst_panel_rows(const SimView &S, const double *tbl, const CT *__restrict__ g, uint32_t ld, uint32_t wave,
+                                                uint32_t lane, uint32_t K, uint32_t nmem, uint32_t nw, const uint16_t *mpos,
+                                                const int32_t *dg_l, const uint32_t *cbeg /*K + 1 list offsets*/, double *tab) {
+    const int32_t junk = (int32_t)lane;  // see skipped_load
+    auto class_of = [&](uint32_t p) -> uint32_t {  // list index -> class (p < nmem)
+        uint32_t c = 0;
+        for (uint32_t j = 1; j < K; ++j) c += p >= cbeg[j] ? 1u : 0u;
+        return c;
+    };
+    uint32_t pos[NWK], cpk = 0;
+    int32_t dgk[NWK];
+#pragma unroll
+    for (uint32_t k = 0; k < NWK; ++k) {
+        const uint32_t p = 64 * k + lane;
+        pos[k] = p < nmem ? (uint32_t)mpos[p] : 0u;
+        dgk[k] = p < nmem ? dg_l[p] : 0;
+        cpk |= (p < nmem ? class_of(p) : 15u) << (4 * k);
+    }
+    double accR[NWK];
+#pragma unroll
+    for (uint32_t k = 0; k < NWK; ++k) accR[k] = 0.0;
+    constexpr uint32_t NT = NWK / 4;  // staging sets: 64 rows per wave and set (hfst_small_rows)
+    uint32_t prow[NT], crow[NT];
+    int32_t arow[NT];
+#pragma unroll
+    for (uint32_t t = 0; t < NT; ++t) {
+        const uint32_t q = wave + (SM_T / 64) * (lane + 64 * t);
+        prow[t] = q < nmem ? (uint32_t)mpos[q] : 0u;
+        arow[t] = q < nmem ? dg_l[q] : 0;
+        crow[t] = q < nmem ? class_of(q) : 0u;
+    }
+    uint32_t cur = 0;  // the row class accR belongs to (wave-uniform)
+    auto flush = [&](uint32_t rc) {
+        for (uint32_t c = rc; c < K; ++c) {
+            double v = 0.0;
+#pragma unroll
+            for (uint32_t k = 0; k < NWK; ++k) v += ((cpk >> (4 * k)) & 15u) == c ? accR[k] : 0.0;
+            v = wave_sum_f64(v);
+            if (lane == 0) tab[(wave * PANEL_MAX_K + rc) * PANEL_MAX_K + c] = v;
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < NWK; ++k) accR[k] = 0.0;
+    };
+    const uint32_t nrows = nmem > wave ? (nmem - wave + SM_T / 64 - 1) / (SM_T / 64) : 0;
+    for (uint32_t r0 = 0; r0 < nrows; r0 += U) {
+        uint32_t q[U], k0[U], pr[U], rc[U];
+        int32_t ar[U];
+        bool lv[U];
+        int32_t I[U][NWK];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            lv[u] = r0 + u < nrows;
+            const uint32_t r = lv[u] ? r0 + u : r0;
+            q[u] = wave + (SM_T / 64) * r;
+            k0[u] = q[u] >> 6;
+            if (NT == 1 || r < 64) {
+                pr[u] = (uint32_t)__builtin_amdgcn_readlane((int)prow[0], (int)(r & 63));
+                ar[u] = __builtin_amdgcn_readlane(arow[0], (int)(r & 63));
+                rc[u] = (uint32_t)__builtin_amdgcn_readlane((int)crow[0], (int)(r & 63));
+            } else {
+                pr[u] = (uint32_t)__builtin_amdgcn_readlane((int)prow[NT - 1], (int)(r & 63));
+                ar[u] = __builtin_amdgcn_readlane(arow[NT - 1], (int)(r & 63));
+                rc[u] = (uint32_t)__builtin_amdgcn_readlane((int)crow[NT - 1], (int)(r & 63));
+            }
+        }
+        // the pair's entry in the upper triangle (the part the Gram kernel writes)
+        row_counts<NWK, U, SEG, CT>(g, S.nseg, (uint32_t)S.seg_stride, lv, k0, nw, junk,
+                                    [&](int u, uint32_t k) { return (pr[u] < pos[k] ? pr[u] : pos[k]) * ld + (pr[u] < pos[k] ? pos[k] : pr[u]); }, I);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            if (!lv[u]) continue;
+            if (rc[u] != cur) {  // wave-uniform: the rows have left class `cur`
+                flush(cur);
+                cur = rc[u];
+            }
+#pragma unroll
+            for (uint32_t k = 0; k < NWK; ++k) {
+                if (k >= k0[u] && k < nw) {
+                    const uint32_t p = 64 * k + lane;
+                    // a lane without a pair here (left of q, or past the list) looks up distance 0: identity 1, the term 0
+                    const int32_t H = (p > q[u] && p < nmem) ? ar[u] + dgk[k] - 2 * I[u][k] : 0;
+                    accR[k] += 1 - ident_of(S, tbl, H);
+                }
+            }
+        }
+    }
+    if (nrows) flush(cur);
+}
+
+template <bool SEG, typename CT>
+__global__ __launch_bounds__(SM_T, SEG ? 4 : 5) void hfst_panel_small_kernel(SimBatch batch, const uint8_t *__restrict__ cls /* class of sequence i, >= K: none */,
+                                                                   uint32_t K, const uint64_t *__restrict__ seq_len,
+                                                                   HfstOut *__restrict__ out /* pair p of problem w at p * pair_stride + w */,
+                                                                   uint64_t pair_stride) {
+    __shared__ double tbl[SIM_TBL_N];
+    __shared__ int32_t dg_l[SM_N];    // Gram diagonal of list member p
+    __shared__ uint16_t mpos[SM_N];   // its position (= sequence index)
+    __shared__ uint8_t cls_l[SM_N];   // class of sequence i (PANEL_MAX_K: none)
+    __shared__ uint32_t cbeg[PANEL_MAX_K + 1];  // list offset of class c; cbeg[K] = members
+    __shared__ double tab[(SM_T / 64) * PANEL_MAX_K * PANEL_MAX_K], tsum[PANEL_MAX_K * PANEL_MAX_K];
+    const uint64_t prob = blockIdx.x;
+    SimView S = sim_view(batch, prob);
+    S.dense = nullptr; S.g16 = sizeof(CT) == 2 ? 1u : 0u;  // (sim_view took the problem's base from batch.g16: the launch matches CT to it)
+    if (!SEG) S.nseg = 1;
+    const uint32_t n = batch.n, tid = threadIdx.x, lane = tid & 63, wave = uni(tid >> 6), ld = S.ld;
+    const CT *__restrict__ g = reinterpret_cast<const CT *>(S.gram);
+    for (uint32_t i = tid; i < SM_N; i += SM_T) {
+        uint32_t cc = PANEL_MAX_K;
+        if (i < n && cls[i] < K) cc = cls[i];
+        cls_l[i] = (uint8_t)cc;
+    }
+    for (uint32_t h = tid; h < SIM_TBL_N; h += SM_T) tbl[h] = match_identity(S.W, (int64_t)h, S.round_digits);
+    for (uint32_t t = tid; t < (SM_T / 64) * PANEL_MAX_K * PANEL_MAX_K; t += SM_T) tab[t] = 0.0;
+    __syncthreads();
+    if (wave == 0) {  // the member list, class-major: ballots + prefix popcounts, one class after the other
+        const uint64_t below = (1ull << lane) - 1ull;
+        uint32_t at = 0;
+        for (uint32_t c = 0; c < K; ++c) {
+            if (lane == 0) cbeg[c] = at;
+            for (uint32_t i0 = 0; i0 < n; i0 += 64) {
+                const bool mine = cls_l[i0 + lane] == c;
+                const uint64_t bal = __ballot(mine);
+                if (mine) mpos[at + (uint32_t)__popcll(bal & below)] = (uint16_t)(i0 + lane);
+                at += (uint32_t)__popcll(bal);
+            }
+        }
+        if (lane == 0) cbeg[K] = at;
+    }
+    __syncthreads();
+    const uint32_t nmem = uni(cbeg[K]), nw = (nmem + 63) >> 6;
+    for (uint32_t p = tid; p < nmem; p += SM_T) dg_l[p] = one_count<SEG, CT>(g, S.nseg, (uint32_t)S.seg_stride, (uint32_t)mpos[p] * (ld + 1));
+    __syncthreads();
+    if (nw <= 4) hfst_panel_rows<4, 4, SEG, CT>(S, tbl, g, ld, wave, lane, K, nmem, nw, mpos, dg_l, cbeg, tab);
+    else hfst_panel_rows<8, 2, SEG, CT>(S, tbl, g, ld, wave, lane, K, nmem, nw, mpos, dg_l, cbeg, tab);
+    __syncthreads();
+    if (tid < PANEL_MAX_K * PANEL_MAX_K) {
+        double t = 0.0;
+        for (uint32_t w = 0; w < SM_T / 64; ++w) t += tab[w * PANEL_MAX_K * PANEL_MAX_K + tid];  // the waves in order
+        tsum[tid] = t;
+    }
+    __syncthreads();
+    const uint32_t NP = K * (K - 1) / 2;
+    if (tid < NP) {  // pair tid = (a, b), a < b, in the order (0,1),(0,2),..,(1,2),..
+        uint32_t a = 0, rem = tid;
+        while (rem >= K - 1 - a) { rem -= K - 1 - a; ++a; }
+        const uint32_t b = a + 1 + rem;
+        const uint64_t a_ = cbeg[a + 1] - cbeg[a], b_ = cbeg[b + 1] - cbeg[b];  // every pair is present on a Gram problem
+        hfst_outputs(tsum[a * PANEL_MAX_K + a], tsum[b * PANEL_MAX_K + b], tsum[a * PANEL_MAX_K + b], a_ * (a_ - (a_ ? 1 : 0)) / 2, 0,
+                     b_ * (b_ - (b_ ? 1 : 0)) / 2, 0, a_ * b_, 0, seq_len ? seq_len[prob] : 0, out + (uint64_t)tid * pair_stride + prob);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // pica2.py:60-169 analyze_similarity_matrix, seeds in position order (the smallest remaining name: stats.hip greedy_groups).
 // Positions 0..m are the elements idx[0..m) (nullptr: the sequences themselves), ascending.
 //  Step 1 in blocks: wave 0 lists the next <= 64 free positions (the candidates, ascending); the four waves test each
@@ -746,6 +912,22 @@ int launch_hfst_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, co
     if (b.seg_first) { if (b.g16) LAUNCH_HF(true, uint16_t); else LAUNCH_HF(true, int32_t); }
     else { if (b.g16) LAUNCH_HF(false, uint16_t); else LAUNCH_HF(false, int32_t); }
 #undef LAUNCH_HF
+    HIP_TRY(hipGetLastError());
+    return IMPOP_OK;
+}
+
+bool hfst_panel_small_applies(const SimBatch &b) { return hfst_small_applies(b); }
+int launch_hfst_panel_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint8_t *d_cls, uint32_t n_pop,
+                            const uint64_t *d_seq_len, HfstOut *d_out, uint64_t pair_stride) {
+    if (!n_problems) return IMPOP_OK;
+    REQUIRE(n_problems < 0x7FFFFFFFull, "hfst panel: too many problems");
+    REQUIRE(n_pop >= 2 && n_pop <= PANEL_MAX_K && n_problems <= pair_stride, "hfst panel: bad class count / pair stride");
+#define LAUNCH_HP(SEG, CT)                                                                                                            \
+    hipLaunchKernelGGL((hfst_panel_small_kernel<SEG, CT>), dim3((uint32_t)n_problems), dim3(SM_T), 0, ctx->stream, b, d_cls, n_pop, d_seq_len, \
+                       d_out, pair_stride)
+    if (b.seg_first) { if (b.g16) LAUNCH_HP(true, uint16_t); else LAUNCH_HP(true, int32_t); }
+    else { if (b.g16) LAUNCH_HP(false, uint16_t); else LAUNCH_HP(false, int32_t); }
+#undef LAUNCH_HP
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }

@@ -38,6 +38,10 @@ EHH_WINDOW_DTYPE = np.dtype([("site_begin", "<u8"), ("site_end", "<u8"), ("core_
 EHH_FLANKS = {"reference": _lib.EHH_FLANKS_REFERENCE, "two-sided": _lib.EHH_FLANKS_TWO_SIDED}
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
+PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), ("n_members", "<u4"), ("n_groups", "<u4"), ("s_p", "<u4"),
+                        ("reserved", "<u4"), ("reserved2", "<u8")])
+PANEL_WINDOW_DTYPE = np.dtype([("n_sites", "<u4"), ("s_all", "<u4")])
+assert PANEL_DTYPE.itemsize == 48 and PANEL_WINDOW_DTYPE.itemsize == 8
 
 IDENTITY_STATS_DTYPE = np.dtype([
     ("status", "<i4"), ("n_groups", "<u4"), ("pi", "<f8"), ("pi_site", "<f8"), ("sum_2pairs", "<f8"), ("n_pairs_with_data", "<u8"),
@@ -168,7 +172,7 @@ class Context:
         return t.value, k.value
 
     def cluster_elapsed(self):
-        """-> (summed clustering-kernel ms of cluster_scan, chunks) since gram_timing(True)"""
+        """-> (summed clustering-kernel ms of cluster_scan — and Fst-kernel ms of pairwise_scan_panel —, chunks) since gram_timing(True)"""
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_cluster_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
@@ -547,6 +551,28 @@ class BitMatrix:
         check(self.ctx._lib.impop_pairwise_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
                                                 pp, pa, pb, C.byref(prm), out.ctypes.data_as(C.POINTER(PairwiseStats))))
         return out
+
+    def pairwise_scan_panel(self, windows, pops, kind: str = "match", threshold: float = 0.99, round_digits: Optional[int] = None,
+                            d_pi_mode: int = 0, s_scope: int = 0, want_pairs: bool = True):
+        """K disjoint panels and all their pairs from ONE Gram pass per window (impop_pairwise_scan_panel): per panel what
+        pairwise_scan(mask_p=panel) returns of pica2 / Tajima's D, per pair what pairwise_scan(mask_a, mask_b) returns of h-fst,
+        at any threshold, rounding and identity.
+        -> (panels [n_windows, K] PANEL_DTYPE, pairs [n_windows, K(K-1)/2] PAIR_DTYPE in the pair order of scan_multi,
+            windows [n_windows] PANEL_WINDOW_DTYPE); want_pairs False skips the Fst work (pairs has no column then)."""
+        w = make_windows(windows)
+        K = len(pops)
+        packed = np.concatenate([_mask_ptr(p, self.n_hap)[0] for p in pops]).astype(np.uint64) if K else np.zeros(1, np.uint64)
+        panels = np.zeros((len(w), K), dtype=PANEL_DTYPE)
+        pairs = np.zeros((len(w), K * (K - 1) // 2 if want_pairs else 0), dtype=PAIR_DTYPE)
+        wins = np.zeros(len(w), dtype=PANEL_WINDOW_DTYPE)
+        prm = PairwiseParams(C.sizeof(PairwiseParams), IDENTITY_KINDS[kind], float(threshold),
+                             -1 if round_digits is None else int(round_digits), int(d_pi_mode), int(s_scope), 0)
+        check(self.ctx._lib.impop_pairwise_scan_panel(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
+                                                      packed.ctypes.data_as(C.POINTER(C.c_uint64)), K, C.byref(prm),
+                                                      panels.ctypes.data_as(C.POINTER(_lib.PanelStats)),
+                                                      pairs.ctypes.data_as(C.POINTER(_lib.PairStats)) if want_pairs else None,
+                                                      wins.ctypes.data_as(C.POINTER(_lib.PanelWindow))))
+        return panels, pairs, wins
 
     def cluster_scan(self, windows, mask_p=None, kind: str = "match", threshold: float = 1.0, round_digits: Optional[int] = None,
                      want_members: bool = True):

@@ -391,6 +391,37 @@ typedef struct impop_pairwise_stats { /* 96 bytes */
 int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                         const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
                         const impop_pairwise_params *params, impop_pairwise_stats *out_host);
+/* K disjoint panels and all their K(K-1)/2 pairs from ONE Gram pass per window: replaces the panel loops of
+ * run_tajd_panels.sh:60-84 (run_tajd.sh per panel: pica2 -t 0.999 -r 5 on the panel's subset, then tj_d) and
+ * run_h_fst_panels.sh:60-95 (run_h-fst.sh per pair) at ANY threshold, rounding and identity — where impop_scan_multi is exact
+ * only for the direct method on unrounded `match`.  The Gram matrix of a window does not depend on the masks, so the K
+ * impop_pairwise_scan(mask_p = panel k) and K(K-1)/2 impop_pairwise_scan(mask_a, mask_b) calls this replaces contract it
+ * K + K(K-1)/2 times; here it is contracted once and the masks only select what the statistics kernels read.
+ * masks: as impop_scan_multi — n_pop (2..8) bitsets of ceil(n_hap/64) uint64 words each, pairwise disjoint, none empty (anything
+ * else: IMPOP_E_INVALID); haplotypes in no panel contribute nothing.
+ * params: identity_kind, threshold, round_digits, d_pi_mode as impop_pairwise_scan; s_scope 0: S = s_all of the window from the
+ * matrix's site bitmap; 1: S = s_p of the panel, from the streaming scan of the same windows with mask_p = the panel (one more
+ * streaming pass per panel); 2: no S, tajima_d = NaN.  fst_method 1 returns IMPOP_E_UNSUPPORTED.
+ * out_panels: n_windows x n_pop, a panel record equal byte for byte to the fields of the same name impop_pairwise_scan(mask_p =
+ * the panel) returns (s_p: s_scope 1 only, else 0).  out_pairs (nullable: no Fst work is done): n_windows x K(K-1)/2 in the pair
+ * order of impop_scan_multi, population k as A and l as B.  out_windows (nullable): n_sites, and s_all unless s_scope is 2.
+ * Compacted and weighted matrices, overlapping windows and chunking as impop_pairwise_scan; records do not depend on any of
+ * them, and two calls return identical bytes (the sums have one fixed order; no floating-point atomics).  Checks the device
+ * error word like impop_pairwise_scan.  With impop_ctx_gram_timing on, impop_ctx_cluster_elapsed returns the summed time of the
+ * chunks' Fst kernel(s) next to the Gram time.  Under IMPOP_TRACE=1 one line per call on stderr, next to the [impop_gram] lines:
+ *   [impop_pairwise_scan_panel] pops=<K> pairs=<K(K-1)/2> route=<small|general>
+ * small = one kernel reads the panels' union once for all pairs (n_hap <= 512, `match`, windows lighter than 2^30); general =
+ * one h-fst launch per pair on the one Gram pass. */
+typedef struct impop_panel_stats {      /* 48 bytes, fixed layout: one per (window, panel) */
+    double pi, pi_site;                 /* pica2.py:154,164 on the panel's members, grouped at `threshold` */
+    double tajima_d;                    /* tj_d.py:47 wired per d_pi_mode / s_scope, n = panel size */
+    uint32_t n_members, n_groups, s_p, reserved;
+    uint64_t reserved2;                 /* 0; pads the record to the 48 bytes of impop_pair_stats */
+} impop_panel_stats;
+typedef struct impop_panel_window { uint32_t n_sites, s_all; } impop_panel_window;   /* one per window */
+int impop_pairwise_scan_panel(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                              const uint64_t *masks, uint32_t n_pop, const impop_pairwise_params *params,
+                              impop_panel_stats *out_panels, impop_pair_stats *out_pairs, impop_panel_window *out_windows);
 #define IMPOP_CLUSTER_MAX_N 12798u /* see impop_cluster_from_identity */
 /* af.cluster (af.py:35-54) for a batch of windows straight from the bit matrix: per window the connected components of
  * {identity(i, j) >= threshold} over the members of P, the identity being exactly the double impop_pairwise_identity

@@ -8,6 +8,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr1.npz --bed windows.bed --format hfst -A afr.txt -B eas.txt [-r 5]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format pica2 -t 0.999 -r 5 [-u subset.txt]
     impop_scan.py --matrix chr1.npz chr2.npz ... --bed genome.bed --format all ...            # one matrix per chromosome
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format all --panel afr.txt amr.txt eas.txt eur.txt sas.txt   # both panel drivers
     impop_scan.py --sim-list windows.tsv --format pica2 -t 0.999 -r 5                         # one `.sim` table per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format af [-t 1.0] [-u subset.txt] [--af-clusters c.tsv] [--af-details d.tsv]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ehh [--ehh-core-offset N | --ehh-cores pos.txt] [--ehh-flanks two-sided]
@@ -41,6 +42,12 @@ REF_ALT compares the allele with that of --ehh-ref NAME (default: the matrix's f
 of the two halves' EHH curves in sites and AREA their sum, all three exact thousandths printed as integer.milli ("12.276").
 --ehh-flanks reference (default) takes both halves from the sites right of the core like ehhgfa.py:56-61, two-sided the left half
 from the sites left of it.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --compact, --devices N, -t / -r.
+
+--panel A.txt B.txt ... (2..8 disjoint lists; run_tajd_panels.sh / run_h_fst_panels.sh).  --format hfst: one h-fst table per pair,
+headed `# A-vs-B`; --format tajd: one tajd table per panel, headed `# A`, SAMPLES = the list's line count, -t 0.999 -r 5 and S
+over all rows like run_tajd.sh; --format all: the pair tables, then the panel tables (h-fst rounds with --fst-round-digits).  The
+panels and pairs of a window share ONE Gram pass (impop_pairwise_scan_panel); only unrounded `match` h-fst tables alone keep the
+streaming K-population scan (impop_scan_multi).  One process, one GPU; not with --fst-method grouped, -l, --devices N, --sim-list.
 
 A threshold >= 1 without rounding on the `match` identity is the streaming site-count scan (every haplotype its own
 group: exact integer identities); anything else runs the all-pairs path (impop_pairwise_scan).
@@ -201,6 +208,12 @@ class Runner:
             pr = full.view(pr.dtype).reshape(self.n_total, n_pairs)
         return pr
 
+    def panel_allpairs(self, pops, threshold, round_digits, want_s, want_pairs):
+        """K panels and their pairs from one Gram pass per window (impop_pairwise_scan_panel): thresholded / rounded pica2 and
+        Tajima's D per panel, rounded or `dice` h-fst per pair -> (panels, pairs, windows).  One process, one GPU."""
+        return self.bm.pairwise_scan_panel(self.local_wins, pops, kind=self.args.identity, threshold=threshold, round_digits=round_digits,
+                                           s_scope=0 if want_s else 2, want_pairs=want_pairs)
+
     def close(self):
         for sk, ck in zip(self.slabs, self.ctxs):
             sk.free(); ck.close()
@@ -209,13 +222,14 @@ class Runner:
         self.ctx.close()
 
 
-def write_tables(out, args, fmt, regions, L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables=None, panel_labels=None, fst_skip=()):
+def write_tables(out, args, fmt, regions, L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables=None, panel_labels=None, fst_skip=(),
+                 panel_taj=None):
     """the TSV tables of the reference's drivers (headers run_pica2_impg.sh:119,122 / run_h-fst.sh:148 / run_tajd.sh:101 /
     run_fst_impg.sh:158) from per-row columns; shared by the matrix path and --sim-list"""
-    if args.panel:
+    if args.panel:  # one table per pair (run_h_fst_panels.sh), then one per panel (run_tajd_panels.sh); nothing else
         p = 0
         K = len(args.panel)
-        for k in range(K):
+        for k in range(K if panel_tables is not None else 0):
             for l in range(k + 1, K):
                 print(f"# {panel_labels[k]}-vs-{panel_labels[l]}", file=out)
                 print("REGION\tLENGTH\tFST\tPI_A\tPI_B\tPI_XY\tDXY\tDA", file=out)
@@ -224,6 +238,14 @@ def write_tables(out, args, fmt, regions, L_col, col, s_all, samples_col, thr_tx
                     print(f"{reg}\t{L_col[i]}\t{float(r['fst']):.8f}\t{float(r['pi_a']):.8f}\t{float(r['pi_b']):.8f}\t"
                           f"{float(r['pi_xy']):.8f}\t{float(r['dxy']):.8f}\t{float(r['da']):.8f}", file=out)
                 p += 1
+        for k in range(K if panel_taj is not None else 0):
+            print(f"# {panel_labels[k]}", file=out)
+            print("REGION\tLENGTH\tSAMPLES\tSEGREGATING_SITES\tPI\tTAJIMAS_D", file=out)  # run_tajd.sh:101
+            for i, reg in enumerate(regions):
+                D = float(panel_taj["tajima_d"][i, k])
+                taj = "NA" if D != D else repr(D)  # run_tajd.sh:192-194
+                print(f"{reg}\t{L_col[i]}\t{panel_taj['samples'][k]}\t{int(panel_taj['s_all'][i])}\t{panel_taj['pi_site'][i, k]:.8f}\t{taj}", file=out)
+        return
     if fmt in ("pica2", "all"):
         if args.subset:
             print("REGION\tSUBSET\tLENGTH\tTHRESHOLD\tR_VALUE\tPICA_OUTPUT", file=out)
@@ -500,8 +522,11 @@ def main():
                     "the sites right of the core (ehhgfa.py:56-61); two-sided = the left half from the sites left of it")
     ap.add_argument("--ehh-ref", metavar="NAME", default=None, help="ehh: the sequence whose core allele is REF (default: the first)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
-    ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="hfst: K >= 2 disjoint population lists; every pair "
-                    "in ONE pass (replaces run_h_fst_panels.sh); one table per pair, labelled POP_A-vs-POP_B")
+    ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
+                    "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
+                    "-r N or --identity dice from one Gram pass per window (impop_pairwise_scan_panel).  tajd: every panel (replaces "
+                    "run_tajd_panels.sh: -t 0.999 -r 5, S over all rows), one table per panel headed `# POP`, SAMPLES = the list's "
+                    "line count.  all: both.  One process, one GPU; not with --fst-method grouped, -l, --devices N, --sim-list")
     ap.add_argument("-l", "--sample-list", help="tajd: sample list (run_tajd.sh -l); n = its line count")
     ap.add_argument("-u", "--subset", help="pica2: --subset-sequence-list")
     ap.add_argument("--sequence-length", type=int, default=None, metavar="L",
@@ -546,6 +571,21 @@ def main():
     # all-gather of the fixed-size records per scan brings everything to rank 0, which prints.
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    # --panel on the all-pairs path (impop_pairwise_scan_panel) is the one-process form: refused before any rank waits for another
+    panel_allpairs = bool(args.panel) and (args.format in ("tajd", "all") or args.round_digits not in (None, "none") or args.identity != "match")
+    if panel_allpairs and world > 1:
+        print("Error: --panel with --format tajd / all, -r N or --identity dice runs on one GPU (impop_pairwise_scan_panel has no sharded "
+              "form): not under torch.distributed.run", file=sys.stderr)
+        sys.exit(2)
+    if args.panel and args.fst_method == "grouped":
+        print("Error: --panel has no --fst-method grouped (the panel calls are the direct method; use -A / -B per pair)", file=sys.stderr)
+        sys.exit(2)
+    if args.panel and args.format in ("tajd", "all") and args.sample_list:
+        print("Error: --panel with --format tajd / all takes every panel's list as its sample list: not with -l", file=sys.stderr)
+        sys.exit(2)
+    if args.panel and not 2 <= len(args.panel) <= 8:
+        print("Error: --panel takes 2 to 8 population lists", file=sys.stderr)
+        sys.exit(2)
     if world > 1:
         import torch
         import torch.distributed as dist
@@ -587,9 +627,15 @@ def main():
     want_pica = fmt in ("pica2", "tajd", "all", "fst3pi")
     want_fst = fmt in ("hfst", "all") and not args.panel
     need_pairs = (want_pica and pica_pairs) or (want_fst and fst_pairs) or fmt == "af"
-    if args.panel and (fmt != "hfst" or fst_pairs):
-        print("Error: --panel is the streaming K-population scan of --format hfst (direct method, match identity, no rounding)", file=sys.stderr)
+    if args.panel and fmt not in ("hfst", "tajd", "all"):
+        print("Error: --panel belongs to --format hfst (every pair), tajd (every panel) or all (both)", file=sys.stderr)
         sys.exit(2)
+    # --panel: the pair tables come from the streaming K-population scan (impop_scan_multi) when h-fst is unrounded on `match`,
+    # else - like every per-panel tajd table - from impop_pairwise_scan_panel: one Gram pass per window for all panels and pairs
+    panel_fst = bool(args.panel) and fmt in ("hfst", "all")
+    panel_tajd = bool(args.panel) and fmt in ("tajd", "all")
+    if args.panel:
+        need_pairs = panel_tajd or (panel_fst and fst_pairs)
 
     thr_txt = threshold_text if threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
     r_txt = "" if pica_r is None else str(pica_r)
@@ -644,7 +690,7 @@ def main():
     f64 = lambda: np.full(n_rows, np.nan)  # noqa: E731
     col = {k: f64() for k in ("pi_site", "tajima_d", "fst", "pi_a", "pi_b", "pi_xy", "dxy", "da", "pi3_a", "pi3_b", "pi3_c")}
     s_all = np.zeros(n_rows, dtype=np.int64)
-    panel_tables, panel_labels = None, None
+    panel_tables, panel_labels, panel_taj = None, None, None
     samples_col = 0
     af_recs = np.zeros(n_rows, dtype=impop_amd.CLUSTER_DTYPE)
     af_clusters = [None] * n_rows
@@ -691,10 +737,40 @@ def main():
                 sys.exit(1)
         if args.panel:
             panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
-            pr = run.panel([flags_for(f, names) for f in args.panel])
-            if panel_tables is None:
-                panel_tables = np.zeros((n_rows, pr.shape[1]), dtype=pr.dtype)
-            panel_tables[idx] = pr
+            pops = [flags_for(f, names) for f in args.panel]
+            pr = pan = pw = None
+            if panel_fst and not fst_pairs:
+                pr = run.panel(pops)
+            one_call = panel_fst and fst_pairs and panel_tajd and pica_r == fst_r
+            if panel_tajd:
+                pan, pr2, pw = run.panel_allpairs(pops, pica_t, pica_r, True, one_call)
+                if one_call:
+                    pr = pr2
+            if panel_fst and pr is None:  # (h-fst.py has no threshold: it only groups pica2)
+                _, pr, _ = run.panel_allpairs(pops, pica_t, fst_r, False, True)
+            if pr is not None:
+                if panel_tables is None:
+                    panel_tables = np.zeros((n_rows, pr.shape[1]), dtype=pr.dtype)
+                panel_tables[idx] = pr
+            if pan is not None:
+                K = len(pops)
+                if panel_taj is None:
+                    panel_taj = {"pi_site": np.full((n_rows, K), np.nan), "tajima_d": np.full((n_rows, K), np.nan),
+                                 "s_all": np.zeros(n_rows, dtype=np.int64), "samples": [awk_line_count(f) for f in args.panel]}
+                panel_taj["pi_site"][idx] = pan["pi_site"]
+                panel_taj["s_all"][idx] = pw["s_all"]
+                D = pan["tajima_d"].copy()
+                for k in range(K):
+                    cnt_k, matched = panel_taj["samples"][k], int(pops[k].sum())
+                    if cnt_k < 2:
+                        print(f"Error: Need at least two samples to compute Tajima's D (found {cnt_k})", file=sys.stderr)  # run_tajd.sh:84-87
+                        sys.exit(1)
+                    if cnt_k != matched and len(idx):  # run_tajd.sh:180: n = the list's LINE count (see the -l case below)
+                        print(f"Warning: sample list {panel_labels[k]} has {cnt_k} lines but selects {matched} haplotypes; Tajima's D uses "
+                              f"n = {cnt_k} like run_tajd.sh", file=sys.stderr)
+                        pi_txt = np.array([float(f"{float(x):.8f}") for x in pan["pi_site"][:, k]])
+                        D[:, k] = run.ctx.tajimas_d(np.full(len(idx), cnt_k, dtype=np.int64), pw["s_all"].astype(np.float64), pi_txt)
+                panel_taj["tajima_d"][idx] = D
             run.close()
             continue
         if fmt == "af":
@@ -791,7 +867,8 @@ def main():
             for line in lines:
                 print(line, file=out)
     else:
-        write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels)
+        write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels,
+                     panel_taj=panel_taj)
     if args.output or rank != 0:
         out.close()
     if world > 1:
