@@ -2,6 +2,9 @@
 #pragma once
 #include <stddef.h>
 
+#include <functional>
+#include <vector>
+
 namespace impop {
 
 // sub-buffers of one allocation start on 256-byte boundaries
@@ -22,6 +25,20 @@ struct Carve {
     size_t total() const { return round_up_256(used); }  // a whole number of 256-byte units: the next region of a larger layout can follow
     template <typename T>
     static T *at(void *base, size_t off) { return reinterpret_cast<T *>(static_cast<char *>(base) + off); }
+};
+
+// A Carve that also remembers whose pointer each sub-buffer is: list the sub-buffers once with sub(), allocate total() bytes, then
+// bind(base) points every listed pointer into the allocation.  The size and the pointers cannot disagree: both come from one list.
+struct Layout : Carve {
+    std::vector<std::function<void(char *)>> binders;
+    template <typename T>
+    void sub(T *&p, size_t count) {
+        const size_t off = take<T>(count);
+        binders.push_back([&p, off](char *base) { p = reinterpret_cast<T *>(base + off); });
+    }
+    void bind(void *base) const {
+        for (const auto &b : binders) b(static_cast<char *>(base));
+    }
 };
 
 }  // namespace impop

@@ -115,6 +115,23 @@ void EventPairs::destroy() {
     done = 0;
 }
 
+int on_side_stream(impop_ctx *ctx, const std::function<int()> &body) {
+    if (!ctx->side) {
+        HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    }
+    HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
+    HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
+    hipStream_t main_stream = ctx->stream;
+    ctx->stream = ctx->side;
+    const int rc = body();
+    ctx->stream = main_stream;
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(ctx->ev_join, ctx->side));
+    return IMPOP_OK;
+}
+
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n) {
     if (!ctx->d_taj) HIP_TRY(hipMalloc(&ctx->d_taj, 8 * sizeof(double)));
     if (ctx->taj_n != n) {

@@ -233,8 +233,34 @@ int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need
 // to be distinct among the members, else IMPOP_E_INVALID with *dup = a rank that occurs twice (the caller words the message)
 int seed_order_of(const uint32_t *seed_rank, const uint32_t *members, uint32_t m, std::vector<uint32_t> &order, uint32_t *dup);
+// context.hip: fork the side stream (created with its two events on first use) off ctx->stream, run `body` with ctx->stream
+// pointing at it, record ev_join behind what it enqueued.  ctx->stream is the caller's again on every path, errors included;
+// the caller joins where it needs the results: hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0)
+int on_side_stream(impop_ctx *ctx, const std::function<int()> &body);
 // pairwise.hip: build (once) the bitmap of the sites that segregate among all haplotypes, m->d_segmap
 int ensure_segmap(impop_ctx *ctx, const impop_matrix *m);
+// pairwise.hip, for the windowed calls of pairwise_scan.hip
+struct GramWindow {
+    uint64_t site_begin, site_end;
+};
+// Gram matrices of `n_win` cells (host copy h_wins of d_wins for the cell range) into d_out.  out16 (in / out, nullable): the
+// caller would take uint16 counts (every window's W < 65536); set to whether the launch wrote them
+int launch_gram_any(impop_ctx *ctx, const impop_matrix *m, const GramWindow *d_wins, const GramWindow *h_wins, uint32_t n_win,
+                    int32_t *d_out, uint64_t max_window_sites, bool *out16 = nullptr);
+int launch_gram_unflip(impop_ctx *ctx, const impop_matrix *m, int32_t *d_g, uint64_t n_mats, bool g16 = false);
+// popcount of a site bitmap over each window -> s_all and s_p of d_stats[w] and / or d_plain[w] (either nullable)
+int launch_seg_count(impop_ctx *ctx, const uint32_t *d_map, const GramWindow *d_wins, uint64_t n_win, impop_window_stats *d_stats,
+                     uint32_t *d_plain);
+int check_pairwise_args(impop_ctx *ctx, const impop_matrix *m, uint64_t s0, uint64_t s1, const char *fn);
+// W of a window: its length, or the sum of its columns' weights
+inline uint64_t window_W(const impop_matrix *m, uint64_t s0, uint64_t s1) {
+    return m->wt_prefix.empty() ? s1 - s0 : m->wt_prefix[s1] - m->wt_prefix[s0];
+}
+// compacted from a weighted matrix: the summed weights of the dropped all-ones sites of [s0, s1) (original coordinates)
+inline uint32_t ones_weight(const impop_matrix *m, uint64_t s0, uint64_t s1) {
+    return (uint32_t)(m->ones_wt_prefix[s1] - m->ones_wt_prefix[s0]);  // < 2^31: part of the window's W
+}
+inline bool compact_weighted(const impop_matrix *m) { return m->compact && !m->ones_wt_prefix.empty(); }
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n);  // fills ctx->d_taj for n (device kernel)
 
 // windows are given in ORIGINAL site coordinates; for a compacted matrix map them to kept-site index

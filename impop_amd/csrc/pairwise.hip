@@ -7,7 +7,6 @@
 #include <string.h>
 
 #include <algorithm>
-#include <chrono>
 #include <type_traits>
 #include <vector>
 
@@ -25,10 +24,6 @@ namespace impop {
 #define IMPOP_GRAM_ABLATE 0  // timing-only ablation builds (tools/ablate_gram_fp4.sh): bit 0 no expansion VALU, bit 1 no global loads, bit 3 no result stores
 #endif
 constexpr int GT = 96;  // tile edge (haplotypes): 3 row groups of 32 (pads 465 haplotypes to 480 instead of 512)
-
-struct GramWindow {
-    uint64_t site_begin, site_end;
-};
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
@@ -463,7 +458,7 @@ __global__ __launch_bounds__(256) void gram_unflip_kernel(T *__restrict__ g, uin
         for (uint32_t j = i + threadIdx.x; j < n; j += 256) row[j] = (T)((int32_t)row[j] + ri - unflip_t[j]);  // column phi itself (j = n) stays as written
     }
 }
-static int launch_gram_unflip(impop_ctx *ctx, const impop_matrix *m, int32_t *d_g, uint64_t n_mats, bool g16 = false) {
+int launch_gram_unflip(impop_ctx *ctx, const impop_matrix *m, int32_t *d_g, uint64_t n_mats, bool g16) {
     if (m->phi_row == 0xFFFFFFFFu || n_mats == 0) return IMPOP_OK;
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
     REQUIRE(n_mats < 0x7FFFFFFFull && (size_t)n * 4 <= 64 * 1024, "gram_unflip: too many matrices / haplotypes");
@@ -489,35 +484,6 @@ __global__ void identity_dense_kernel(SimBatch b, uint32_t n, double *__restrict
     if (i >= n || j >= n) return;
     const SimView S = sim_view(b, 0);
     out[(uint64_t)i * n + j] = sim_get(S, i, j);
-}
-
-struct PairFinalIn {
-    const Pica2Out *pica;
-    const HfstOut *hfst;
-    const impop_window_stats *scan;  // integer S / W from the site scan of the same windows
-};
-__global__ void pairwise_finalize_kernel(PairFinalIn in, uint64_t n_windows, uint32_t nP, int d_pi_mode, int s_scope,
-                                         const double *__restrict__ taj /* a1,a2,b1,b2,c1,c2,e1,e2 for n = nP */,
-                                         impop_pairwise_stats *__restrict__ out) {
-    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_windows) return;
-    const Pica2Out p = in.pica[i];
-    const HfstOut h = in.hfst[i];
-    const impop_window_stats s = in.scan[i];
-    impop_pairwise_stats r;
-    r.pi = p.pi; r.pi_site = p.pi_site;
-    r.fst = h.v[0]; r.pi_a = h.v[1]; r.pi_b = h.v[2]; r.pi_xy = h.v[3]; r.dxy = h.v[4]; r.da = h.v[5];
-    r.n_groups = p.n_groups; r.s_all = s.s_all; r.s_p = s.s_p; r.n_sites = s.n_sites; r.reserved = 0;
-    const double S = (double)(s_scope == 0 ? s.s_all : s.s_p);
-    const double pin = d_pi_mode == 0 ? py_round(p.pi_site, 8) : d_pi_mode == 1 ? p.pi_site : p.pi * (double)s.n_sites;
-    double D = __builtin_nan("");
-    if (nP >= 2 && pin == pin && pin >= 0) {
-        TajConsts c;
-        c.a1 = taj[0]; c.a2 = taj[1]; c.b1 = taj[2]; c.b2 = taj[3]; c.c1 = taj[4]; c.c2 = taj[5]; c.e1 = taj[6]; c.e2 = taj[7];
-        D = tajima_d_from(c, S, pin, nullptr, nullptr);
-    }
-    r.tajima_d = D;
-    out[i] = r;
 }
 
 // add_shift < 0: d_out = Gram; >= 0: d_out += Gram << add_shift (d_out holds the other planes' sum).
@@ -651,8 +617,8 @@ static int ensure_weight_planes(impop_ctx *ctx, const impop_matrix *m) {
 }
 
 // Gram matrices of `n_win` cells (host copy h_wins of d_wins for the cell range) into d_out
-static int launch_gram_any(impop_ctx *ctx, const impop_matrix *m, const GramWindow *d_wins, const GramWindow *h_wins,
-                           uint32_t n_win, int32_t *d_out, uint64_t max_window_sites, bool *out16 = nullptr) {
+int launch_gram_any(impop_ctx *ctx, const impop_matrix *m, const GramWindow *d_wins, const GramWindow *h_wins, uint32_t n_win,
+                    int32_t *d_out, uint64_t max_window_sites, bool *out16) {
     if (m->wt_prefix.empty()) return launch_gram(ctx, m, m->d_rb, d_wins, n_win, d_out, max_window_sites, -1, false, out16);
     int rc = ensure_weight_planes(ctx, m);
     if (rc) return rc;
@@ -760,22 +726,14 @@ int ensure_segmap(impop_ctx *ctx, const impop_matrix *m) {
     return IMPOP_OK;
 }
 
-// W of a window: its length, or the sum of its columns' weights
-static inline uint64_t window_W(const impop_matrix *m, uint64_t s0, uint64_t s1) {
-    return m->wt_prefix.empty() ? s1 - s0 : m->wt_prefix[s1] - m->wt_prefix[s0];
+int launch_seg_count(impop_ctx *ctx, const uint32_t *d_map, const GramWindow *d_wins, uint64_t n_win, impop_window_stats *d_stats,
+                     uint32_t *d_plain) {
+    hipLaunchKernelGGL(seg_count_kernel, dim3((uint32_t)((n_win + 3) / 4)), dim3(256), 0, ctx->stream, d_map, d_wins, n_win, d_stats, d_plain);
+    HIP_TRY(hipGetLastError());
+    return IMPOP_OK;
 }
 
-// compacted from a weighted matrix: the summed weights of the dropped all-ones sites of [s0, s1) (original coordinates)
-static inline uint32_t ones_weight(const impop_matrix *m, uint64_t s0, uint64_t s1) {
-    return (uint32_t)(m->ones_wt_prefix[s1] - m->ones_wt_prefix[s0]);  // < 2^31: part of the window's W
-}
-static inline bool compact_weighted(const impop_matrix *m) { return m->compact && !m->ones_wt_prefix.empty(); }
-
-}  // namespace impop
-
-using namespace impop;
-
-static int check_pairwise_args(impop_ctx *ctx, const impop_matrix *m, uint64_t s0, uint64_t s1, const char *fn) {
+int check_pairwise_args(impop_ctx *ctx, const impop_matrix *m, uint64_t s0, uint64_t s1, const char *fn) {
     REQUIRE(ctx && m, "%s: NULL argument", fn);
     if (m->compact && !(m->d_rb && m->d_onesmap)) {
         set_error("%s: this compacted matrix has no all-pairs operand (compact a matrix that kept IMPOP_KEEP_HAP_MAJOR)", fn);
@@ -788,6 +746,42 @@ static int check_pairwise_args(impop_ctx *ctx, const impop_matrix *m, uint64_t s
     return IMPOP_OK;
 }
 
+// The Gram matrix of ONE window [s0, s1) (original coordinates), in the original polarity, for the calls that export counts or
+// identities: scratch for L's sub-buffers (the caller's own, listed before the call) plus the helper's, the window mapped and
+// uploaded, the Gram launch, the unflip; *d_g = the ld x ld counts.  Compacted matrix: *d_add = the constant every I_ij lacks —
+// the dropped sites every haplotype carries (their count, or their summed weights) — else nullptr.
+static int gram_one_window(impop_ctx *ctx, const impop_matrix *m, uint64_t s0, uint64_t s1, Layout &L, int32_t **d_g, uint32_t **d_add) {
+    const uint32_t ld = m->n_hap_pad;
+    GramWindow *d_w, *d_ow;
+    uint32_t *d_a;
+    L.sub(d_w, 1); L.sub(*d_g, (size_t)ld * ld); L.sub(d_ow, 1); L.sub(d_a, 1);
+    void *d = nullptr;
+    int rc = ctx_scratch(ctx, L.total(), &d);
+    if (rc) return rc;
+    L.bind(d);
+    GramWindow w;
+    map_range(m, s0, s1, &w.site_begin, &w.site_end);  // compacted: the kept sites of the range
+    HIP_TRY(hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
+    rc = launch_gram_any(ctx, m, d_w, &w, 1, *d_g, w.site_end - w.site_begin);
+    if (rc) return rc;
+    rc = launch_gram_unflip(ctx, m, *d_g, 1);
+    if (rc) return rc;
+    *d_add = m->compact ? d_a : nullptr;
+    if (compact_weighted(m)) {
+        const uint32_t add_w = ones_weight(m, s0, s1);
+        HIP_TRY(hipMemcpyAsync(d_a, &add_w, 4, hipMemcpyHostToDevice, ctx->stream));
+    } else if (m->compact) {
+        const GramWindow ow{s0, s1};
+        HIP_TRY(hipMemcpyAsync(d_ow, &ow, sizeof ow, hipMemcpyHostToDevice, ctx->stream));
+        rc = launch_seg_count(ctx, m->d_onesmap, d_ow, 1, nullptr, d_a);
+    }
+    return rc;
+}
+
+}  // namespace impop
+
+using namespace impop;
+
 IMPOP_API int impop_pairwise_counts(impop_ctx *ctx, const impop_matrix *m, uint64_t site_begin, uint64_t site_end,
                                     int32_t *out_host) {
     int rc = check_pairwise_args(ctx, m, site_begin, site_end, "impop_pairwise_counts");
@@ -795,30 +789,12 @@ IMPOP_API int impop_pairwise_counts(impop_ctx *ctx, const impop_matrix *m, uint6
     REQUIRE(out_host, "impop_pairwise_counts: out is NULL");
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
-    void *d = nullptr;
-    Carve L;
-    const size_t o_w = L.take<GramWindow>(1), o_g = L.take<int32_t>((size_t)ld * ld), o_ow = L.take<GramWindow>(1), o_add = L.take<uint32_t>(1);
-    rc = ctx_scratch(ctx, L.total(), &d);
+    Layout L;
+    int32_t *d_g;
+    uint32_t *d_add;
+    rc = gram_one_window(ctx, m, site_begin, site_end, L, &d_g, &d_add);
     if (rc) return rc;
-    GramWindow *d_w = L.at<GramWindow>(d, o_w), *d_ow = L.at<GramWindow>(d, o_ow);
-    int32_t *d_g = L.at<int32_t>(d, o_g);
-    uint32_t *d_add = L.at<uint32_t>(d, o_add);
-    GramWindow w;
-    map_range(m, site_begin, site_end, &w.site_begin, &w.site_end);  // compacted: the kept sites of the range
-    HIP_TRY(hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_gram_any(ctx, m, d_w, &w, 1, d_g, w.site_end - w.site_begin);
-    if (rc) return rc;
-    rc = launch_gram_unflip(ctx, m, d_g, 1);  // exported counts / identities: the original polarity
-    if (rc) return rc;
-    const GramWindow ow{site_begin, site_end};
-    const uint32_t add_w = compact_weighted(m) ? ones_weight(m, site_begin, site_end) : 0u;
-    if (m->compact) {  // + the dropped sites every haplotype carries (their count, or their summed weights)
-        if (compact_weighted(m)) {
-            HIP_TRY(hipMemcpyAsync(d_add, &add_w, 4, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_ow, &ow, sizeof ow, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(seg_count_kernel, dim3(1), dim3(256), 0, ctx->stream, m->d_onesmap, d_ow, 1, (impop_window_stats *)nullptr, d_add);
-        }
+    if (d_add) {
         hipLaunchKernelGGL(gram_add_const_kernel, dim3((n + 15) / 16, (n + 15) / 16), dim3(16, 16), 0, ctx->stream, d_g, ld, n, d_add);
         HIP_TRY(hipGetLastError());
     }
@@ -839,832 +815,22 @@ IMPOP_API int impop_pairwise_identity(impop_ctx *ctx, const impop_matrix *m, uin
             "impop_pairwise_identity: unknown identity kind %d", identity_kind);
     HIP_TRY(hipSetDevice(ctx->device));
     const uint32_t n = m->g.n_hap, ld = m->n_hap_pad;
-    void *d = nullptr;
-    Carve L;
-    const size_t o_w = L.take<GramWindow>(1), o_W = L.take<uint64_t>(1), o_g = L.take<int32_t>((size_t)ld * ld),
-                 o_id = L.take<double>((size_t)n * n), o_ow = L.take<GramWindow>(1), o_add = L.take<uint32_t>(1);
-    rc = ctx_scratch(ctx, L.total(), &d);
+    Layout L;
+    uint64_t *d_W;
+    double *d_id;
+    L.sub(d_W, 1); L.sub(d_id, (size_t)n * n);
+    int32_t *d_g;
+    uint32_t *d_add;
+    rc = gram_one_window(ctx, m, site_begin, site_end, L, &d_g, &d_add);
     if (rc) return rc;
-    GramWindow *d_w = L.at<GramWindow>(d, o_w), *d_ow = L.at<GramWindow>(d, o_ow);
-    uint64_t *d_W = L.at<uint64_t>(d, o_W);
-    int32_t *d_g = L.at<int32_t>(d, o_g);
-    double *d_id = L.at<double>(d, o_id);
-    uint32_t *d_add = L.at<uint32_t>(d, o_add);
-    GramWindow w;
-    map_range(m, site_begin, site_end, &w.site_begin, &w.site_end);
     const uint64_t W = window_W(m, site_begin, site_end);  // the window's ORIGINAL length
-    HIP_TRY(hipMemcpyAsync(d_w, &w, sizeof w, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_W, &W, 8, hipMemcpyHostToDevice, ctx->stream));
-    rc = launch_gram_any(ctx, m, d_w, &w, 1, d_g, w.site_end - w.site_begin);
-    if (rc) return rc;
-    rc = launch_gram_unflip(ctx, m, d_g, 1);  // exported counts / identities: the original polarity
-    if (rc) return rc;
     SimBatch b{};
     b.gram = d_g; b.stride = (uint64_t)ld * ld; b.ld = ld; b.n = n; b.W = d_W; b.kind = identity_kind; b.round_digits = -1;
-    const GramWindow ow{site_begin, site_end};
-    const uint32_t add_w = compact_weighted(m) ? ones_weight(m, site_begin, site_end) : 0u;
-    if (m->compact) {
-        if (compact_weighted(m)) {
-            HIP_TRY(hipMemcpyAsync(d_add, &add_w, 4, hipMemcpyHostToDevice, ctx->stream));
-        } else {
-            HIP_TRY(hipMemcpyAsync(d_ow, &ow, sizeof ow, hipMemcpyHostToDevice, ctx->stream));
-            hipLaunchKernelGGL(seg_count_kernel, dim3(1), dim3(256), 0, ctx->stream, m->d_onesmap, d_ow, 1, (impop_window_stats *)nullptr, d_add);
-            HIP_TRY(hipGetLastError());
-        }
-        b.add = d_add;
-    }
+    b.add = d_add;
     hipLaunchKernelGGL(identity_dense_kernel, dim3((n + 15) / 16, (n + 15) / 16), dim3(16, 16), 0, ctx->stream, b, n, d_id);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out_host, d_id, (size_t)n * n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return IMPOP_OK;
-}
-
-// ---- the shared front end of the windowed all-pairs calls (impop_pairwise_scan, impop_cluster_scan) -------------------
-// windows -> Gram cells (elementary segments where windows overlap) -> chunks that fit the scratch -> per chunk the Gram
-// launch (uint16 counts where they fit), the per-window tables and the filled SimBatch.  What a call does with the
-// identities — its epilogue kernels, its records — is the PairEpilogue it hands in.
-struct PairChunk {
-    SimBatch b;               // the chunk's problems: Gram counts, W, segments, the constant of a compacted matrix
-    uint64_t cnt;             // windows (= problems) of the chunk
-    const uint64_t *ord;      // problem k is window ord[k] of the caller's list
-    uint64_t *d_L;            // seq_len per problem
-    impop_window_stats *d_s;  // per problem: n_sites, and S / the scan's sums when the call asked for them
-    void *h_out;              // page-locked staging for the chunk's results (out_per_window bytes per problem)
-};
-struct PairEpilogue {
-    virtual ~PairEpilogue() {}
-    // once, before the first chunk: d_epi = the epilogue's own device region, sized for chunks of up to cap windows
-    virtual int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) = 0;
-    // enqueue the chunk's kernels and the copies of its results into c.h_out (the front end then checks the device error
-    // word and synchronises)
-    virtual int launch(impop_ctx *ctx, const PairChunk &c) = 0;
-    virtual void collect(const PairChunk &c) = 0;  // after the synchronisation: c.h_out -> the caller's arrays
-};
-struct PairFront {
-    const char *fn;
-    int identity_kind, round_digits;
-    const impop_window_stats *scan_host;  // nullable: the streaming scan's records of the same windows
-    bool use_segmap;                      // S of every window from the matrix's site bitmap (into d_s)
-    size_t epi_fixed, epi_per_window;     // device bytes of the epilogue: per call, per window of a chunk
-    size_t out_per_window;                // staged result bytes per window
-    uint64_t max_chunk_windows;           // 0 = no limit of the epilogue's own
-};
-static int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const PairFront &in,
-                          PairEpilogue &epi) {
-    const uint32_t ld = m->n_hap_pad, n = m->g.n_hap;
-    // IMPOP_TRACE=1: host-side phase times of this call on stderr (where a call's time goes when the kernels are short)
-    const bool trace = trace_on();
-    const auto t_enter = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) {
-        if (trace) fprintf(stderr, "[%s] %-22s +%.1f us\n", in.fn, what,
-                           std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t_enter).count());
-    };
-    // ---- Gram cells.  I_ij is additive over disjoint site ranges, so overlapping (sliding) windows share the
-    // Gram matrices of the elementary segments between the sorted window boundaries: every site is
-    // contracted once however many windows cover it, and a window is the sum of its consecutive segments
-    // (formed on the fly by the statistics kernels, SimBatch.seg_*).  Without overlap the cells are the
-    // windows themselves.
-    // compacted matrix: the contraction runs over the KEPT (variable) sites of each window; the dropped all-ones
-    // sites come back as a per-window constant (SimBatch.add), the dropped all-zero sites contribute nothing
-    std::vector<impop_window> mw;
-    int rc = map_windows_device(ctx, m, windows, n_windows, mw);
-    if (rc) return rc;
-    lap("map_windows");
-    struct Cell { uint64_t b, e; };
-    std::vector<Cell> cells;                                // all Gram cells, in site order when segmented
-    std::vector<uint32_t> first(n_windows, 0), count(n_windows, 0);
-    std::vector<uint64_t> ord(n_windows);
-    for (uint64_t i = 0; i < n_windows; ++i) ord[i] = i;
-    // the usual window list — a BED tiling: sorted, no two windows overlapping — has nothing to share: its cells are the windows
-    // (one O(n) check instead of the sort + searches below, 0.15 ms of host time per 4096 windows while the GPU waits)
-    bool segmented = false;  // cells are elementary segments shared by windows (else: cell k is window k)
-    bool tiling = n_windows < 0xFFFFFFF0ull;
-    for (uint64_t i = 1; i < n_windows && tiling; ++i) tiling = mw[i].site_begin >= mw[i - 1].site_end && mw[i].site_end >= mw[i].site_begin;
-    if (tiling) {
-        cells.resize(n_windows);
-        for (uint64_t i = 0; i < n_windows; ++i) {
-            cells[i] = {mw[i].site_begin, mw[i].site_end};
-            first[i] = (uint32_t)i;
-            count[i] = 1;
-        }
-    } else {
-        std::vector<uint64_t> cuts;
-        uint64_t win_sites = 0;
-        for (uint64_t i = 0; i < n_windows; ++i)
-            if (mw[i].site_end > mw[i].site_begin) {
-                cuts.push_back(mw[i].site_begin);
-                cuts.push_back(mw[i].site_end);
-                win_sites += mw[i].site_end - mw[i].site_begin;
-            }
-        std::sort(cuts.begin(), cuts.end());
-        cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-        auto at = [&](uint64_t s) { return (size_t)(std::lower_bound(cuts.begin(), cuts.end(), s) - cuts.begin()); };
-        std::vector<int64_t> cover(cuts.size() + 1, 0);
-        for (uint64_t i = 0; i < n_windows; ++i)
-            if (mw[i].site_end > mw[i].site_begin) {
-                cover[at(mw[i].site_begin)] += 1;
-                cover[at(mw[i].site_end)] -= 1;
-            }
-        std::vector<uint32_t> seg_before(cuts.size() + 1, 0);  // covered intervals left of cut k
-        uint64_t seg_sites = 0;
-        int64_t depth = 0;
-        std::vector<Cell> segs;
-        for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-            seg_before[k] = (uint32_t)segs.size();
-            depth += cover[k];
-            if (depth > 0) {
-                segs.push_back({cuts[k], cuts[k + 1]});
-                seg_sites += cuts[k + 1] - cuts[k];
-            }
-        }
-        if (!cuts.empty()) seg_before[cuts.size() - 1] = (uint32_t)segs.size();
-        if (seg_sites * 20 < win_sites * 19 && segs.size() < 0xFFFFFFF0ull) {  // >= 5 % of the contraction is shared
-            cells.swap(segs);
-            segmented = true;
-            for (uint64_t i = 0; i < n_windows; ++i)
-                if (mw[i].site_end > mw[i].site_begin) {
-                    first[i] = seg_before[at(mw[i].site_begin)];
-                    count[i] = seg_before[at(mw[i].site_end)] - first[i];
-                }
-            std::stable_sort(ord.begin(), ord.end(), [&](uint64_t a, uint64_t b) {
-                const bool ea = count[a] == 0, eb = count[b] == 0;  // empty windows last
-                return ea != eb ? eb : (!ea && first[a] < first[b]);
-            });
-        } else {
-            REQUIRE(n_windows < 0xFFFFFFF0ull, "%s: too many windows", in.fn);
-            cells.resize(n_windows);
-            for (uint64_t i = 0; i < n_windows; ++i) {
-                cells[i] = {mw[i].site_begin, mw[i].site_end};
-                first[i] = (uint32_t)i;
-                count[i] = 1;
-            }
-        }
-    }
-    // Chunks of consecutive (in `ord`) windows whose cells fit the Gram scratch (<= ~8 GiB of 288): large
-    // chunks keep the persistent Gram grid's last, partially filled round of tasks small next to the launch
-    lap("cells");
-    const size_t gram_bytes = (size_t)ld * ld * 4;
-    uint64_t cap = (8ull << 30) / gram_bytes;  // (a chromosome of 50 kb windows — 4854 on chr2 — is one chunk)
-    if (cap > 8192) cap = 8192;
-    cap = std::min<uint64_t>(cap, std::max<uint64_t>(cells.size(), n_windows));  // a short call stages (and copies) short tables
-    if (cap < 1) cap = 1;
-    // windows per chunk: the Gram capacity, what the epilogue's own buffers allow, and the test switch IMPOP_PAIRWISE_CHUNK
-    // (windows per chunk: forces several chunks on lists far too short to need them; records must not change)
-    uint64_t win_cap = cap;
-    if (in.max_chunk_windows) win_cap = std::min<uint64_t>(win_cap, std::max<uint64_t>(in.max_chunk_windows, 1));
-    static const uint64_t chunk_env = [] { const char *e = getenv("IMPOP_PAIRWISE_CHUNK"); return e ? strtoull(e, nullptr, 10) : 0ull; }();
-    if (chunk_env) win_cap = std::min<uint64_t>(win_cap, chunk_env);
-    // one cell per window: a chunk never holds more Gram matrices than windows, so the Gram and table scratch is sized for that
-    // (an epilogue that allows ~100 windows per chunk would otherwise reserve room for 8192 matrices it can never fill)
-    if (!segmented) cap = std::min<uint64_t>(cap, win_cap);
-    // per-chunk metadata: ONE contiguous region mirrored on the host, so that a chunk costs one host-to-device copy
-    // (eight small pageable copies were ~0.3 ms of host time between two Gram launches)
-    Carve M;  // cells first: they go up on their own, everything from o_W on in a second copy
-    const size_t o_w = M.take<GramWindow>(cap), o_W = M.take<uint64_t>(cap), o_L = M.take<uint64_t>(cap), o_first = M.take<uint32_t>(cap),
-                 o_count = M.take<uint32_t>(cap), o_s = M.take<impop_window_stats>(cap), o_sw = M.take<GramWindow>(cap),
-                 o_ow = M.take<GramWindow>(cap), meta_bytes = M.total();
-    const size_t epi_bytes = in.epi_fixed + win_cap * in.epi_per_window;
-    Carve D;  // device: Gram matrices | metadata | compacted: dropped all-ones sites per window | the epilogue's own region
-    const size_t o_g = D.take_bytes(cap * gram_bytes), o_meta = D.take_bytes(meta_bytes), o_add = D.take<uint32_t>(cap),
-                 o_epi = D.take_bytes(epi_bytes);
-    void *d = nullptr;
-    rc = ctx_scratch(ctx, D.total(), &d);
-    if (rc) return rc;
-    int32_t *d_g = D.at<int32_t>(d, o_g);
-    char *d_meta = D.at<char>(d, o_meta);
-    GramWindow *d_w = M.at<GramWindow>(d_meta, o_w);
-    uint64_t *d_W = M.at<uint64_t>(d_meta, o_W), *d_L = M.at<uint64_t>(d_meta, o_L);
-    uint32_t *d_first = M.at<uint32_t>(d_meta, o_first), *d_count = M.at<uint32_t>(d_meta, o_count);
-    impop_window_stats *d_s = M.at<impop_window_stats>(d_meta, o_s);
-    GramWindow *d_sw = M.at<GramWindow>(d_meta, o_sw);  // the chunk's WINDOWS (d_w holds its Gram cells), matrix coordinates
-    GramWindow *d_ow = M.at<GramWindow>(d_meta, o_ow);  // the same windows in ORIGINAL coordinates (compacted matrices)
-    uint32_t *d_add = D.at<uint32_t>(d, o_add);
-    void *d_epi = D.at<char>(d, o_epi);
-    rc = epi.prepare(ctx, d_epi, win_cap);
-    if (rc) return rc;
-    // even out the chunks: a total slightly above the capacity would otherwise leave a last chunk of a few
-    // windows whose single-workgroup epilogue kernels cost their full latency
-    uint64_t cell_limit = cap;
-    if (cells.size() > cap) {
-        uint32_t widest = 1;
-        for (uint64_t i = 0; i < n_windows; ++i) widest = std::max(widest, count[i]);
-        uint64_t n_chunks = (cells.size() + cap - 1) / cap;
-        if ((cells.size() + n_chunks - 1) / n_chunks + widest > cap) ++n_chunks;  // neighbours re-contract up to `widest` cells
-        cell_limit = std::min<uint64_t>(cap, (cells.size() + n_chunks - 1) / n_chunks + widest);
-    }
-    lap("scratch");
-    // page-locked staging for the metadata going up and the results coming down (ctx_pinned)
-    const size_t out_off = meta_bytes;
-    void *pin = nullptr;
-    rc = ctx_pinned(ctx, out_off + win_cap * in.out_per_window, &pin);
-    if (rc) return rc;
-    char *hmeta = reinterpret_cast<char *>(pin);
-    memset(hmeta, 0, meta_bytes);
-    GramWindow *gw = M.at<GramWindow>(hmeta, o_w), *swv = M.at<GramWindow>(hmeta, o_sw), *owv = M.at<GramWindow>(hmeta, o_ow);
-    uint64_t *Wv = M.at<uint64_t>(hmeta, o_W), *Lv = M.at<uint64_t>(hmeta, o_L);
-    uint32_t *fv = M.at<uint32_t>(hmeta, o_first), *cvv = M.at<uint32_t>(hmeta, o_count);
-    impop_window_stats *sv = M.at<impop_window_stats>(hmeta, o_s);
-    std::vector<uint32_t> add_h;
-    uint64_t call_max_W = 0;  // bounds every Gram count of the call (a cell is a window or a piece of one; compacted: + its constant)
-    for (uint64_t i = 0; i < n_windows; ++i) call_max_W = std::max(call_max_W, window_W(m, windows[i].site_begin, windows[i].site_end));
-    bool g16 = false;
-    for (uint64_t base = 0; base < n_windows;) {
-        // windows ord[base .. base+cnt): their cells are [c_lo, c_hi)
-        uint64_t cnt = 0;
-        uint32_t c_lo = 0, c_hi = 0;
-        bool have = false;
-        while (base + cnt < n_windows && cnt < cell_limit && cnt < win_cap) {
-            const uint64_t wdx = ord[base + cnt];
-            if (count[wdx]) {
-                const uint32_t lo = have ? std::min(c_lo, first[wdx]) : first[wdx];
-                const uint32_t hi = have ? std::max(c_hi, first[wdx] + count[wdx]) : first[wdx] + count[wdx];
-                if ((uint64_t)(hi - lo) > (cnt == 0 ? cap : cell_limit)) {
-                    REQUIRE(cnt != 0, "%s: window %llu spans %u segments, more than the %llu Gram matrices that fit the scratch", in.fn,
-                            (unsigned long long)wdx, count[wdx], (unsigned long long)cap);
-                    break;
-                }
-                c_lo = lo; c_hi = hi; have = true;
-            }
-            ++cnt;
-        }
-        const uint32_t n_cells = have ? c_hi - c_lo : 0;
-        uint64_t max_sites = 0;
-        for (uint32_t c = 0; c < n_cells; ++c) {
-            gw[c] = {cells[c_lo + c].b, cells[c_lo + c].e};
-            max_sites = std::max<uint64_t>(max_sites, cells[c_lo + c].e - cells[c_lo + c].b);
-        }
-        // the Gram launch needs the cells alone: they go up first and the kernel starts, the per-window tables are filled in (and
-        // copied) while it runs
-        if (n_cells) HIP_TRY(hipMemcpyAsync(d_meta + o_w, hmeta + o_w, (size_t)n_cells * sizeof(GramWindow), hipMemcpyHostToDevice, ctx->stream));
-        if (n_cells) {
-            size_t slot = 0;  // impop_ctx_gram_timing: the Gram launch(es) of this chunk between two events
-            if (ctx->gram_timing && (rc = ctx->gram_timer.begin(ctx->stream, &slot))) return rc;
-            // counts as uint16 where every count of the call fits (a count is at most its window's W): half the result bytes
-            static const bool u16_off = env_is("IMPOP_GRAM_U16", '0');
-            g16 = !u16_off && call_max_W < 65536;
-            rc = launch_gram_any(ctx, m, d_w, gw, n_cells, d_g, max_sites, &g16);
-            if (rc) return rc;
-            if (ctx->gram_timing && (rc = ctx->gram_timer.end(ctx->stream, slot))) return rc;
-            if (in.identity_kind != IMPOP_IDENTITY_MATCH) {  // `match` sees Hamming distances only: polarity-invariant
-                rc = launch_gram_unflip(ctx, m, d_g, n_cells, g16);
-                if (rc) return rc;
-            }
-        }
-        for (uint64_t k = 0; k < cnt; ++k) {
-            const uint64_t wdx = ord[base + k];
-            Wv[k] = window_W(m, windows[wdx].site_begin, windows[wdx].site_end);
-            Lv[k] = windows[wdx].seq_len;
-            fv[k] = count[wdx] ? first[wdx] - c_lo : 0;
-            cvv[k] = count[wdx];
-            if (in.scan_host) sv[k] = in.scan_host[wdx];
-            else { memset(&sv[k], 0, sizeof(sv[k])); sv[k].n_sites = (uint32_t)Wv[k]; }
-            swv[k] = {mw[wdx].site_begin, mw[wdx].site_end};
-            owv[k] = {windows[wdx].site_begin, windows[wdx].site_end};
-        }
-        // problem k IS Gram matrix k (disjoint windows, none empty): the epilogue kernels then take their one-matrix variants
-        bool one_to_one = true;
-        for (uint64_t k = 0; k < cnt && one_to_one; ++k) one_to_one = cvv[k] == 1 && fv[k] == k;
-        lap("chunk metadata");
-        HIP_TRY(hipMemcpyAsync(d_meta + o_W, hmeta + o_W, meta_bytes - o_W, hipMemcpyHostToDevice, ctx->stream));
-        if (in.use_segmap) {
-            hipLaunchKernelGGL(seg_count_kernel, dim3((uint32_t)((cnt + 3) / 4)), dim3(256), 0, ctx->stream, m->d_segmap, d_sw, cnt, d_s,
-                               (uint32_t *)nullptr);
-            HIP_TRY(hipGetLastError());
-        }
-        PairChunk ch{};
-        SimBatch &b = ch.b;
-        b.gram = d_g; b.stride = (uint64_t)ld * ld; b.ld = ld; b.n = n; b.W = d_W; b.kind = in.identity_kind;
-        b.g16 = g16 ? 1u : 0u;
-        b.max_W = call_max_W;
-        b.round_digits = in.round_digits < 0 ? -1 : in.round_digits;
-        b.seg_first = one_to_one ? nullptr : d_first; b.seg_count = one_to_one ? nullptr : d_count;
-        if (compact_weighted(m)) {  // the dropped all-ones sites' summed weights, from the host prefix sums
-            add_h.resize(cnt);
-            for (uint64_t k = 0; k < cnt; ++k) add_h[k] = ones_weight(m, windows[ord[base + k]].site_begin, windows[ord[base + k]].site_end);
-            HIP_TRY(hipMemcpyAsync(d_add, add_h.data(), cnt * 4, hipMemcpyHostToDevice, ctx->stream));
-            b.add = d_add;
-        } else if (m->compact) {    // ... their count, from the bitmap on the device
-            hipLaunchKernelGGL(seg_count_kernel, dim3((uint32_t)((cnt + 3) / 4)), dim3(256), 0, ctx->stream, m->d_onesmap, d_ow, cnt,
-                               (impop_window_stats *)nullptr, d_add);
-            HIP_TRY(hipGetLastError());
-            b.add = d_add;
-        }
-        ch.cnt = cnt; ch.ord = ord.data() + base; ch.d_L = d_L; ch.d_s = d_s; ch.h_out = hmeta + out_off;
-        rc = epi.launch(ctx, ch);
-        if (rc) return rc;
-        lap("chunk launched");
-        rc = ctx_err_fetch(ctx);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging vectors are reused by the next chunk
-        rc = ctx_err_result(ctx, in.fn);  // a device-side consistency check tripped: no partial results
-        if (rc) return rc;
-        epi.collect(ch);
-        base += cnt;
-        lap("chunk done");
-    }
-    return IMPOP_OK;
-}
-
-namespace {
-// impop_pairwise_scan's epilogue: pica2 grouping next to the Fst sums, then the fixed records
-struct PairwiseStatsEpilogue final : PairEpilogue {
-    const impop_pairwise_params *params;
-    const uint64_t *mask_p;
-    uint32_t n, nP;
-    bool want_s;
-    const std::vector<uint32_t> *idx, *ia, *ib;
-    const std::vector<uint8_t> *fa, *fb;
-    impop_pairwise_stats *out_host;
-    Pica2Out *d_p = nullptr;
-    HfstOut *d_h = nullptr;
-    impop_pairwise_stats *d_o = nullptr;
-    uint32_t *d_idx = nullptr, *d_ia = nullptr, *d_ib = nullptr;
-    uint8_t *d_fa = nullptr, *d_fb = nullptr;
-    // prepare()'s member lists and flags; + 256: the total of its layout is rounded up
-    static size_t fixed_bytes(uint32_t n) { return 3 * round_up_256((size_t)(n ? n : 1) * 4) + 2 * round_up_256(n ? n : 1) + 256; }
-    static size_t window_bytes() { return sizeof(Pica2Out) + sizeof(HfstOut) + sizeof(impop_pairwise_stats); }
-    int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) override {
-        Carve L;
-        d_idx = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
-        d_ia = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
-        d_ib = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
-        d_fa = L.at<uint8_t>(d_epi, L.take<uint8_t>(n ? n : 1));
-        d_fb = L.at<uint8_t>(d_epi, L.take<uint8_t>(n ? n : 1));
-        char *w = L.at<char>(d_epi, L.take_bytes(cap * window_bytes()));
-        d_h = reinterpret_cast<HfstOut *>(w);
-        d_o = reinterpret_cast<impop_pairwise_stats *>(w + cap * sizeof(HfstOut));
-        d_p = reinterpret_cast<Pica2Out *>(w + cap * (sizeof(HfstOut) + sizeof(impop_pairwise_stats)));
-        if (nP) HIP_TRY(hipMemcpyAsync(d_idx, idx->data(), (size_t)nP * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_fa, fa->data(), n, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_fb, fb->data(), n, hipMemcpyHostToDevice, ctx->stream));
-        if (!ia->empty()) HIP_TRY(hipMemcpyAsync(d_ia, ia->data(), ia->size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        if (!ib->empty()) HIP_TRY(hipMemcpyAsync(d_ib, ib->data(), ib->size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        return IMPOP_OK;
-    }
-    int launch(impop_ctx *ctx, const PairChunk &c) override {
-        const SimBatch &b = c.b;
-        const uint64_t cnt = c.cnt;
-        // pica2 grouping and the Fst sums are independent, latency-bound one-workgroup-per-window kernels: pica2 goes
-        // to the side stream (fork behind the Gram launch, join before the finalize) so the two overlap
-        if (!ctx->side) {
-            HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->side;
-        int rc = launch_pica2(ctx, b, cnt, mask_p ? d_idx : nullptr, nP, nullptr, params->threshold, c.d_L, d_p, nullptr);
-        ctx->stream = main_stream;
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->side));
-        if (params->fst_method == 1)
-            rc = launch_hud_grouped(ctx, b, cnt, d_ia, (uint32_t)ia->size(), d_ib, (uint32_t)ib->size(), nullptr, nullptr, params->threshold,
-                                    c.d_L, d_h);
-        else
-            rc = launch_hfst(ctx, b, cnt, d_fa, d_fb, c.d_L, d_h);
-        if (rc) return rc;
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        PairFinalIn in{d_p, d_h, c.d_s};
-        rc = ensure_tajima_consts(ctx, nP >= 2 ? (int64_t)nP : 2);  // the cache may have been retargeted by another plan
-        if (rc) return rc;
-        hipLaunchKernelGGL(pairwise_finalize_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, ctx->stream, in, cnt,
-                           want_s ? nP : 0u, params->d_pi_mode, want_s ? params->s_scope : 0, ctx->d_taj, d_o);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(c.h_out, d_o, cnt * sizeof(impop_pairwise_stats), hipMemcpyDeviceToHost, ctx->stream));
-        return IMPOP_OK;
-    }
-    void collect(const PairChunk &c) override {
-        const impop_pairwise_stats *ov = reinterpret_cast<const impop_pairwise_stats *>(c.h_out);
-        for (uint64_t k = 0; k < c.cnt; ++k) out_host[c.ord[k]] = ov[k];
-    }
-};
-
-// impop_cluster_scan's epilogue: one clustering launch (stats_kernels.h launch_af_batch), records and member tables
-struct ClusterEpilogue final : PairEpilogue {
-    const impop_cluster_params *params;
-    const uint64_t *mask_p;
-    uint32_t nP;
-    const std::vector<uint32_t> *idx;
-    impop_cluster_stats *out_host;
-    uint32_t *cluster_of, *sizes;
-    size_t adj_bytes = 0;  // per window: the general form's adjacency rows (0 when the call is sure to take the window-shape kernel)
-    impop_cluster_stats *d_rec = nullptr;
-    uint32_t *d_idx = nullptr, *d_cl = nullptr, *d_sz = nullptr, *d_adj = nullptr;
-    size_t members_bytes() const { return (size_t)nP * 4; }
-    bool want_members() const { return cluster_of || sizes; }
-    static size_t fixed_bytes(uint32_t nP) { return round_up_256((size_t)(nP ? nP : 1) * 4) + 4 * 256; }
-    // the window-shape kernel writes tables only when asked; the general form always writes both (sizes is its ranking's output)
-    size_t tables_bytes() const { return (adj_bytes == 0 && !want_members()) ? 0 : 2 * members_bytes(); }
-    size_t window_bytes() const { return sizeof(impop_cluster_stats) + tables_bytes() + adj_bytes; }
-    int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap) override {
-        Carve L;
-        d_idx = L.at<uint32_t>(d_epi, L.take<uint32_t>(nP ? nP : 1));
-        d_rec = L.at<impop_cluster_stats>(d_epi, L.take<impop_cluster_stats>(cap));
-        // (the layout's alignment gaps and rounded total: fixed_bytes' 4 x 256)
-        char *w = L.at<char>(d_epi, L.take_bytes(cap * (tables_bytes() + adj_bytes)));
-        d_cl = reinterpret_cast<uint32_t *>(w);
-        d_sz = reinterpret_cast<uint32_t *>(w + cap * (tables_bytes() / 2));
-        d_adj = reinterpret_cast<uint32_t *>(w + cap * tables_bytes());
-        if (nP) HIP_TRY(hipMemcpyAsync(d_idx, idx->data(), (size_t)nP * 4, hipMemcpyHostToDevice, ctx->stream));
-        return IMPOP_OK;
-    }
-    // staged per chunk: cnt records | cnt x nP cluster_of | cnt x nP sizes (the tables only when asked for)
-    int launch(impop_ctx *ctx, const PairChunk &c) override {
-        const uint64_t cnt = c.cnt;
-        size_t slot = 0;  // the clustering kernel(s) between two events of their own: impop_ctx_cluster_elapsed
-        int rc = ctx->gram_timing ? ctx->cluster_timer.begin(ctx->stream, &slot) : IMPOP_OK;
-        if (rc) return rc;
-        rc = launch_af_batch(ctx, c.b, cnt, mask_p ? d_idx : nullptr, nP, params->threshold, d_adj, adj_bytes, d_rec, d_cl, d_sz, want_members());
-        if (rc) return rc;
-        if (ctx->gram_timing && (rc = ctx->cluster_timer.end(ctx->stream, slot))) return rc;
-        char *h = reinterpret_cast<char *>(c.h_out);
-        HIP_TRY(hipMemcpyAsync(h, d_rec, cnt * sizeof(impop_cluster_stats), hipMemcpyDeviceToHost, ctx->stream));
-        if (want_members() && nP) {
-            h += cnt * sizeof(impop_cluster_stats);
-            if (cluster_of) HIP_TRY(hipMemcpyAsync(h, d_cl, cnt * members_bytes(), hipMemcpyDeviceToHost, ctx->stream));
-            if (sizes) HIP_TRY(hipMemcpyAsync(h + cnt * members_bytes(), d_sz, cnt * members_bytes(), hipMemcpyDeviceToHost, ctx->stream));
-        }
-        return IMPOP_OK;
-    }
-    void collect(const PairChunk &c) override {
-        const char *h = reinterpret_cast<const char *>(c.h_out);
-        const impop_cluster_stats *rv = reinterpret_cast<const impop_cluster_stats *>(h);
-        const char *hc = h + c.cnt * sizeof(impop_cluster_stats), *hs = hc + c.cnt * members_bytes();
-        for (uint64_t k = 0; k < c.cnt; ++k) {
-            out_host[c.ord[k]] = rv[k];
-            if (cluster_of && nP) memcpy(cluster_of + c.ord[k] * nP, hc + k * members_bytes(), members_bytes());
-            if (sizes && nP) memcpy(sizes + c.ord[k] * nP, hs + k * members_bytes(), members_bytes());
-        }
-    }
-};
-// impop_pairwise_scan_panel's records from the per-panel pica2 results, the per-pair Fst results and the window's S / W: one thread
-// per (window, panel or pair); the arithmetic of a panel record is pairwise_finalize_kernel's with nP = the panel's size
-struct PanelFinalIn {
-    const Pica2Out *pica;            // panel k of problem w at k * stride + w
-    const HfstOut *hfst;             // pair p of problem w at p * stride + w; nullptr: no pair records asked for
-    const impop_window_stats *scan;  // n_sites, and s_all from the site bitmap (s_scope 0, 1)
-    const uint32_t *s_p;             // s_scope 1: panel k of problem w at k * stride + w
-    const double *taj;               // a1,a2,b1,b2,c1,c2,e1,e2 per panel
-    const uint32_t *n_members;       // per panel
-    uint64_t stride;
-};
-__global__ void panel_finalize_kernel(PanelFinalIn in, uint64_t n_windows, uint32_t K, int d_pi_mode, int s_scope,
-                                      impop_panel_stats *__restrict__ out_panels, impop_pair_stats *__restrict__ out_pairs,
-                                      impop_panel_window *__restrict__ out_windows) {
-    const uint32_t NP = in.hfst ? K * (K - 1) / 2 : 0u, items = K + NP;
-    const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= n_windows * items) return;
-    const uint64_t w = t / items;
-    const uint32_t j = (uint32_t)(t % items);
-    if (j >= K) {
-        const HfstOut h = in.hfst[(uint64_t)(j - K) * in.stride + w];
-        impop_pair_stats r;
-        r.fst = h.v[0]; r.pi_a = h.v[1]; r.pi_b = h.v[2]; r.pi_xy = h.v[3]; r.dxy = h.v[4]; r.da = h.v[5];
-        out_pairs[w * NP + (j - K)] = r;
-        return;
-    }
-    const impop_window_stats s = in.scan[w];
-    if (j == 0) out_windows[w] = impop_panel_window{s.n_sites, s.s_all};
-    const Pica2Out p = in.pica[(uint64_t)j * in.stride + w];
-    const uint32_t nP = in.n_members[j], sp = s_scope == 1 ? in.s_p[(uint64_t)j * in.stride + w] : 0u;
-    impop_panel_stats r;
-    r.pi = p.pi; r.pi_site = p.pi_site;
-    r.n_members = nP; r.n_groups = p.n_groups; r.s_p = sp; r.reserved = 0; r.reserved2 = 0;
-    const double S = (double)(s_scope == 1 ? sp : s.s_all);
-    const double pin = d_pi_mode == 0 ? py_round(p.pi_site, 8) : d_pi_mode == 1 ? p.pi_site : p.pi * (double)s.n_sites;
-    double D = __builtin_nan("");
-    if (s_scope != 2 && nP >= 2 && pin == pin && pin >= 0) {
-        const double *tj = in.taj + 8 * j;
-        TajConsts c;
-        c.a1 = tj[0]; c.a2 = tj[1]; c.b1 = tj[2]; c.b2 = tj[3]; c.c1 = tj[4]; c.c2 = tj[5]; c.e1 = tj[6]; c.e2 = tj[7];
-        D = tajima_d_from(c, S, pin, nullptr, nullptr);
-    }
-    r.tajima_d = D;
-    out_panels[w * K + j] = r;
-}
-
-// impop_pairwise_scan_panel's epilogue: K panels and their K (K - 1) / 2 pairs on the chunk's ONE set of Gram matrices — pica2 per
-// panel on the side stream, next to it the Fst sums of all pairs (one launch of hfst_panel_small_kernel on the window-statistics
-// shape; launch_hfst per pair on every other), then the records
-struct PanelEpilogue final : PairEpilogue {
-    const impop_pairwise_params *params;
-    uint32_t n, K, NP;                      // NP = 0: no pair records asked for
-    const std::vector<uint32_t> *idx;       // the panels' members back to back, each ascending
-    const std::vector<uint32_t> *sizes;     // members per panel
-    const std::vector<uint8_t> *cls;        // class of haplotype i, 0xFF: none
-    const std::vector<uint32_t> *sp_host;   // s_scope 1: K x n_windows, panel-major; else nullptr
-    uint64_t n_windows;
-    impop_panel_stats *out_panels;
-    impop_pair_stats *out_pairs;
-    impop_panel_window *out_windows;
-    bool traced = false;
-    uint64_t cap = 0;
-    Pica2Out *d_p = nullptr;
-    HfstOut *d_h = nullptr;
-    impop_panel_stats *d_opan = nullptr;
-    impop_pair_stats *d_opair = nullptr;
-    impop_panel_window *d_owin = nullptr;
-    uint32_t *d_idx = nullptr, *d_sizes = nullptr, *d_sp = nullptr;
-    uint8_t *d_cls = nullptr, *d_flags = nullptr;  // d_flags: K x n membership flags (the general route's in_a / in_b)
-    double *d_taj = nullptr;
-    std::vector<uint32_t> sp_chunk;
-    // the member list, sizes, Tajima constants, classes and flags, plus the layout's alignment gaps (fifteen sub-buffers)
-    static size_t fixed_bytes(uint32_t n, uint32_t K) {
-        return round_up_256((size_t)(n ? n : 1) * 4) + 2 * round_up_256((size_t)K * 8 * 8) + round_up_256(n ? n : 1) +
-               round_up_256((size_t)K * (n ? n : 1)) + 16 * 256;
-    }
-    static size_t window_bytes(uint32_t K, uint32_t NP) {
-        return (size_t)K * (sizeof(Pica2Out) + sizeof(impop_panel_stats) + 4) + (size_t)NP * (sizeof(HfstOut) + sizeof(impop_pair_stats)) +
-               sizeof(impop_panel_window);
-    }
-    static size_t staged_bytes(uint32_t K, uint32_t NP) {
-        return (size_t)K * sizeof(impop_panel_stats) + (size_t)NP * sizeof(impop_pair_stats) + sizeof(impop_panel_window);
-    }
-    int prepare(impop_ctx *ctx, void *d_epi, uint64_t cap_) override {
-        cap = cap_;
-        Carve L;
-        d_idx = L.at<uint32_t>(d_epi, L.take<uint32_t>(n ? n : 1));
-        d_sizes = L.at<uint32_t>(d_epi, L.take<uint32_t>(K));
-        d_taj = L.at<double>(d_epi, L.take<double>((size_t)K * 8));
-        d_cls = L.at<uint8_t>(d_epi, L.take<uint8_t>(n ? n : 1));
-        d_flags = L.at<uint8_t>(d_epi, L.take<uint8_t>((size_t)K * (n ? n : 1)));
-        d_p = L.at<Pica2Out>(d_epi, L.take<Pica2Out>(cap * K));
-        d_h = L.at<HfstOut>(d_epi, L.take<HfstOut>(cap * NP));
-        d_opan = L.at<impop_panel_stats>(d_epi, L.take<impop_panel_stats>(cap * K));
-        d_opair = L.at<impop_pair_stats>(d_epi, L.take<impop_pair_stats>(cap * NP));
-        d_owin = L.at<impop_panel_window>(d_epi, L.take<impop_panel_window>(cap));
-        d_sp = L.at<uint32_t>(d_epi, L.take<uint32_t>(cap * K));
-        if (!idx->empty()) HIP_TRY(hipMemcpyAsync(d_idx, idx->data(), idx->size() * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_sizes, sizes->data(), (size_t)K * 4, hipMemcpyHostToDevice, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(d_cls, cls->data(), n, hipMemcpyHostToDevice, ctx->stream));
-        flags_host.assign((size_t)K * n, 0);
-        for (uint32_t i = 0; i < n; ++i)
-            if ((*cls)[i] < K) flags_host[(size_t)(*cls)[i] * n + i] = 1;
-        HIP_TRY(hipMemcpyAsync(d_flags, flags_host.data(), flags_host.size(), hipMemcpyHostToDevice, ctx->stream));
-        for (uint32_t k = 0; k < K; ++k) {  // the context caches the constants of ONE n: each panel's are copied out behind their kernel
-            const int rc = ensure_tajima_consts(ctx, (*sizes)[k] >= 2 ? (int64_t)(*sizes)[k] : 2);
-            if (rc) return rc;
-            HIP_TRY(hipMemcpyAsync(d_taj + 8 * k, ctx->d_taj, 8 * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        return IMPOP_OK;
-    }
-    std::vector<uint8_t> flags_host;
-    int launch(impop_ctx *ctx, const PairChunk &c) override {
-        const SimBatch &b = c.b;
-        const uint64_t cnt = c.cnt;
-        const bool small = hfst_panel_small_applies(b);
-        if (!traced && trace_on())
-            fprintf(stderr, "[impop_pairwise_scan_panel] pops=%u pairs=%u route=%s\n", K, K * (K - 1) / 2, small ? "small" : "general");
-        traced = true;
-        if (!ctx->side) {
-            HIP_TRY(hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-        }
-        if (sp_host) {  // s_scope 1: the chunk's rows of the streaming scan's s_p, in the chunk's problem order
-            sp_chunk.resize((size_t)K * cap);
-            for (uint32_t k = 0; k < K; ++k)
-                for (uint64_t i = 0; i < cnt; ++i) sp_chunk[(size_t)k * cap + i] = (*sp_host)[(size_t)k * n_windows + c.ord[i]];
-            HIP_TRY(hipMemcpyAsync(d_sp, sp_chunk.data(), (size_t)K * cap * 4, hipMemcpyHostToDevice, ctx->stream));
-        }
-        HIP_TRY(hipEventRecord(ctx->ev_fork, ctx->stream));
-        HIP_TRY(hipStreamWaitEvent(ctx->side, ctx->ev_fork, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->side;
-        int rc = IMPOP_OK;
-        for (uint32_t k = 0, at = 0; k < K && !rc; at += (*sizes)[k], ++k)
-            rc = launch_pica2(ctx, b, cnt, d_idx + at, (*sizes)[k], nullptr, params->threshold, c.d_L, d_p + (uint64_t)k * cap, nullptr);
-        ctx->stream = main_stream;
-        if (rc) return rc;
-        HIP_TRY(hipEventRecord(ctx->ev_join, ctx->side));
-        if (NP) {
-            size_t slot = 0;  // impop_ctx_gram_timing: the Fst kernel(s) of the chunk between two events (impop_ctx_cluster_elapsed)
-            if (ctx->gram_timing && (rc = ctx->cluster_timer.begin(ctx->stream, &slot))) return rc;
-            if (small) {
-                rc = launch_hfst_panel_small(ctx, b, cnt, d_cls, K, c.d_L, d_h, cap);
-            } else {
-                uint32_t p = 0;
-                for (uint32_t a = 0; a < K && !rc; ++a)
-                    for (uint32_t bb = a + 1; bb < K && !rc; ++bb, ++p)
-                        rc = launch_hfst(ctx, b, cnt, d_flags + (size_t)a * n, d_flags + (size_t)bb * n, c.d_L, d_h + (uint64_t)p * cap);
-            }
-            if (rc) return rc;
-            if (ctx->gram_timing && (rc = ctx->cluster_timer.end(ctx->stream, slot))) return rc;
-        }
-        HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-        PanelFinalIn in{d_p, NP ? d_h : nullptr, c.d_s, sp_host ? d_sp : nullptr, d_taj, d_sizes, cap};
-        const uint64_t items = cnt * (K + NP);
-        hipLaunchKernelGGL(panel_finalize_kernel, dim3((uint32_t)((items + 127) / 128)), dim3(128), 0, ctx->stream, in, cnt, K,
-                           params->d_pi_mode, params->s_scope, d_opan, d_opair, d_owin);
-        HIP_TRY(hipGetLastError());
-        char *h = reinterpret_cast<char *>(c.h_out);
-        HIP_TRY(hipMemcpyAsync(h, d_opan, cnt * K * sizeof(impop_panel_stats), hipMemcpyDeviceToHost, ctx->stream));
-        h += cnt * K * sizeof(impop_panel_stats);
-        if (NP) HIP_TRY(hipMemcpyAsync(h, d_opair, cnt * NP * sizeof(impop_pair_stats), hipMemcpyDeviceToHost, ctx->stream));
-        h += cnt * NP * sizeof(impop_pair_stats);
-        HIP_TRY(hipMemcpyAsync(h, d_owin, cnt * sizeof(impop_panel_window), hipMemcpyDeviceToHost, ctx->stream));
-        return IMPOP_OK;
-    }
-    void collect(const PairChunk &c) override {
-        const char *h = reinterpret_cast<const char *>(c.h_out);
-        const impop_panel_stats *pv = reinterpret_cast<const impop_panel_stats *>(h);
-        const impop_pair_stats *qv = reinterpret_cast<const impop_pair_stats *>(h + c.cnt * K * sizeof(impop_panel_stats));
-        const impop_panel_window *wv =
-            reinterpret_cast<const impop_panel_window *>(h + c.cnt * (K * sizeof(impop_panel_stats) + NP * sizeof(impop_pair_stats)));
-        for (uint64_t k = 0; k < c.cnt; ++k) {
-            memcpy(out_panels + c.ord[k] * K, pv + k * K, (size_t)K * sizeof(impop_panel_stats));
-            if (NP) memcpy(out_pairs + c.ord[k] * NP, qv + k * NP, (size_t)NP * sizeof(impop_pair_stats));
-            if (out_windows) out_windows[c.ord[k]] = wv[k];
-        }
-    }
-};
-}  // namespace
-static_assert(sizeof(impop_panel_stats) == 48 && sizeof(impop_panel_window) == 8 && sizeof(impop_pair_stats) == 48, "fixed record layouts");
-
-IMPOP_API int impop_pairwise_scan_panel(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                                        const uint64_t *masks, uint32_t n_pop, const impop_pairwise_params *params,
-                                        impop_panel_stats *out_panels, impop_pair_stats *out_pairs, impop_panel_window *out_windows) {
-    const char *fn = "impop_pairwise_scan_panel";
-    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
-    REQUIRE(params->struct_size == sizeof(impop_pairwise_params), "impop_pairwise_params.struct_size mismatch");
-    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE, "%s: unknown identity kind", fn);
-    REQUIRE(params->round_digits <= 19, "%s: round_digits > 19 unsupported", fn);
-    REQUIRE(params->d_pi_mode >= 0 && params->d_pi_mode <= 2 && params->s_scope >= 0 && params->s_scope <= 2, "%s: bad d_pi_mode / s_scope", fn);
-    REQUIRE(params->fst_method <= 1, "%s: fst_method must be 0 (direct)", fn);
-    if (params->fst_method == 1) {
-        set_error("%s: fst_method 1 (hud.py grouped) is not available for panels; use impop_pairwise_scan per pair", fn);
-        return IMPOP_E_UNSUPPORTED;
-    }
-    REQUIRE(n_pop >= 2 && n_pop <= 8, "%s: n_pop must be 2..8", fn);
-    REQUIRE(masks, "%s: masks is NULL", fn);
-    const uint32_t n = m->g.n_hap, K = n_pop, mwords = (n + 63) / 64;
-    std::vector<uint8_t> cls(n, 0xFF);
-    std::vector<uint32_t> idx, sizes(K, 0);
-    for (uint32_t k = 0; k < K; ++k) {
-        const uint64_t *mk = masks + (size_t)k * mwords;
-        for (uint32_t i = 0; i < n; ++i) {
-            if (!((mk[i >> 6] >> (i & 63)) & 1ull)) continue;
-            // h-fst.py:181-185 removes shared members per pair, which would make a panel's size depend on the pair
-            REQUIRE(cls[i] == 0xFF, "%s: populations must be disjoint (population %u overlaps population %u)", fn, k, (uint32_t)cls[i]);
-            cls[i] = (uint8_t)k;
-            idx.push_back(i);
-            ++sizes[k];
-        }
-        REQUIRE(sizes[k] > 0, "%s: population %u is empty", fn, k);
-    }
-    if (!n_windows) return IMPOP_OK;
-    REQUIRE(windows && out_panels, "%s: NULL windows/out", fn);
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, fn);
-        if (rc) return rc;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    int rc = IMPOP_OK;
-    // s_scope 1: s_p of every panel from the streaming scan of the same windows — one plan, its subset mask swapped per panel
-    std::vector<uint32_t> sp_host;
-    if (params->s_scope == 1) {
-        impop_scan_params sp;
-        sp.struct_size = sizeof sp; sp.d_pi_mode = params->d_pi_mode; sp.s_scope = 1; sp.tile_blocks = 0;
-        impop_scan_plan *plan = nullptr;
-        rc = impop_scan_plan_create(ctx, m, windows, n_windows, masks, nullptr, nullptr, &sp, &plan);
-        if (rc) return rc;
-        std::vector<impop_window_stats> rec(n_windows);
-        sp_host.resize((size_t)K * n_windows);
-        for (uint32_t k = 0; k < K && !rc; ++k) {
-            rc = impop_scan_plan_set_masks(plan, masks + (size_t)k * mwords, nullptr, nullptr);
-            if (!rc) rc = impop_scan_plan_launch(plan, nullptr);
-            if (!rc) rc = impop_scan_plan_fetch(plan, rec.data());
-            for (uint64_t i = 0; i < n_windows && !rc; ++i) sp_host[(size_t)k * n_windows + i] = rec[i].s_p;
-        }
-        impop_scan_plan_destroy(plan);
-        if (rc) return rc;
-    }
-    const bool use_segmap = params->s_scope != 2;  // s_all of every window from the matrix's cached site bitmap
-    if (use_segmap && (rc = ensure_segmap(ctx, m))) return rc;
-    PanelEpilogue epi;
-    epi.params = params; epi.n = n; epi.K = K; epi.NP = out_pairs ? K * (K - 1) / 2 : 0u;
-    epi.idx = &idx; epi.sizes = &sizes; epi.cls = &cls; epi.sp_host = params->s_scope == 1 ? &sp_host : nullptr;
-    epi.n_windows = n_windows; epi.out_panels = out_panels; epi.out_pairs = out_pairs; epi.out_windows = out_windows;
-    PairFront in{};
-    in.fn = fn; in.identity_kind = params->identity_kind; in.round_digits = params->round_digits;
-    in.scan_host = nullptr; in.use_segmap = use_segmap;
-    in.epi_fixed = PanelEpilogue::fixed_bytes(n, K); in.epi_per_window = PanelEpilogue::window_bytes(K, epi.NP);
-    in.out_per_window = PanelEpilogue::staged_bytes(K, epi.NP);
-    return pairwise_front(ctx, m, windows, n_windows, in, epi);
-}
-
-IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                                  const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
-                                  const impop_pairwise_params *params, impop_pairwise_stats *out_host) {
-    REQUIRE(ctx && m && params, "impop_pairwise_scan: NULL argument");
-    REQUIRE(params->struct_size == sizeof(impop_pairwise_params), "impop_pairwise_params.struct_size mismatch");
-    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE,
-            "impop_pairwise_scan: unknown identity kind");
-    REQUIRE(params->round_digits <= 19, "impop_pairwise_scan: round_digits > 19 unsupported");
-    REQUIRE(params->d_pi_mode >= 0 && params->d_pi_mode <= 2 && params->s_scope >= 0 && params->s_scope <= 2,
-            "impop_pairwise_scan: bad d_pi_mode / s_scope");
-    REQUIRE(params->fst_method <= 1, "impop_pairwise_scan: fst_method must be 0 (direct) or 1 (grouped)");
-    if (!n_windows) return IMPOP_OK;
-    REQUIRE(windows && out_host, "impop_pairwise_scan: NULL windows/out");
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, "impop_pairwise_scan");
-        if (rc) return rc;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t n = m->g.n_hap;
-    // integer S / W of the same windows from the streaming scan
-    impop_scan_params sp;
-    sp.struct_size = sizeof sp; sp.d_pi_mode = params->d_pi_mode; sp.s_scope = params->s_scope; sp.tile_blocks = 0;
-    // s_scope 2: the caller does not need S / Tajima's D (pica2- or Fst-only output): skip the site scan
-    const bool want_s = params->s_scope != 2;
-    if (!want_s) sp.s_scope = 0;
-    // without a subset mask S comes from the matrix's cached site bitmap (s_p = s_all); with one, s_p needs the
-    // subset's own counts: the streaming scan of the same windows
-    const bool use_segmap = want_s && !mask_p;
-    impop_scan_plan *plan = nullptr;
-    int rc = (want_s && !use_segmap) ? impop_scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, &sp, &plan) : IMPOP_OK;
-    if (rc) return rc;
-    auto fail = [&](int code) {
-        if (plan) impop_scan_plan_destroy(plan);
-        return code;
-    };
-    if (use_segmap) {
-        rc = ensure_segmap(ctx, m);
-        if (rc) return fail(rc);
-    }
-    // subset P index list and A/B flags
-    std::vector<uint32_t> idx;
-    std::vector<uint8_t> fa(n, 0), fb(n, 0);
-    for (uint32_t i = 0; i < n; ++i) {
-        const bool inP = mask_p ? ((mask_p[i >> 6] >> (i & 63)) & 1ull) : true;
-        if (inP) idx.push_back(i);
-        fa[i] = mask_a ? (uint8_t)((mask_a[i >> 6] >> (i & 63)) & 1ull) : 0;
-        fb[i] = mask_b ? (uint8_t)((mask_b[i >> 6] >> (i & 63)) & 1ull) : 0;
-    }
-    const uint32_t nP = (uint32_t)idx.size();
-    std::vector<uint32_t> ia, ib;  // hud.py grouped: members of A / B with the overlap removed from both
-    for (uint32_t i = 0; i < n && params->fst_method == 1; ++i) {
-        if (fa[i] && !fb[i]) ia.push_back(i);
-        if (fb[i] && !fa[i]) ib.push_back(i);
-    }
-    std::vector<impop_window_stats> scan_host;  // only with a scan plan; else the records are n_sites and zeros (S: the device fills it in)
-    if (plan) {
-        scan_host.resize(n_windows);
-        rc = impop_scan_plan_launch(plan, nullptr);
-        if (rc) return fail(rc);
-        rc = impop_scan_plan_fetch(plan, scan_host.data());
-        if (rc) return fail(rc);
-    }
-    PairwiseStatsEpilogue epi;
-    epi.params = params; epi.mask_p = mask_p; epi.n = n; epi.nP = nP; epi.want_s = want_s;
-    epi.idx = &idx; epi.ia = &ia; epi.ib = &ib; epi.fa = &fa; epi.fb = &fb; epi.out_host = out_host;
-    PairFront in{};
-    in.fn = "impop_pairwise_scan"; in.identity_kind = params->identity_kind; in.round_digits = params->round_digits;
-    in.scan_host = plan ? scan_host.data() : nullptr; in.use_segmap = use_segmap;
-    in.epi_fixed = PairwiseStatsEpilogue::fixed_bytes(n); in.epi_per_window = PairwiseStatsEpilogue::window_bytes();
-    in.out_per_window = sizeof(impop_pairwise_stats);
-    return fail(pairwise_front(ctx, m, windows, n_windows, in, epi));
-}
-
-IMPOP_API int impop_cluster_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                                 const uint64_t *mask_p, const impop_cluster_params *params, impop_cluster_stats *out_host,
-                                 uint32_t *cluster_of, uint32_t *sizes) {
-    REQUIRE(ctx && m && params, "impop_cluster_scan: NULL argument");
-    REQUIRE(params->struct_size == sizeof(impop_cluster_params), "impop_cluster_params.struct_size mismatch");
-    REQUIRE(params->identity_kind == IMPOP_IDENTITY_MATCH || params->identity_kind == IMPOP_IDENTITY_DICE,
-            "impop_cluster_scan: unknown identity kind");
-    REQUIRE(params->round_digits <= 19, "impop_cluster_scan: round_digits > 19 unsupported");
-    // subset P index list
-    const uint32_t n = m->g.n_hap;
-    std::vector<uint32_t> idx;
-    for (uint32_t i = 0; i < n; ++i)
-        if (mask_p ? ((mask_p[i >> 6] >> (i & 63)) & 1ull) : true) idx.push_back(i);
-    const uint32_t nP = (uint32_t)idx.size();
-    // refused before anything is uploaded or launched
-    REQUIRE(nP <= IMPOP_CLUSTER_MAX_N, "impop_cluster_scan: %u members exceed the LDS-resident clustering limit (%u)", nP,
-            (uint32_t)IMPOP_CLUSTER_MAX_N);
-    if (!n_windows) return IMPOP_OK;
-    REQUIRE(windows && out_host, "impop_cluster_scan: NULL windows/out");
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        int rc = check_pairwise_args(ctx, m, windows[i].site_begin, windows[i].site_end, "impop_cluster_scan");
-        if (rc) return rc;
-    }
-    HIP_TRY(hipSetDevice(ctx->device));
-    ClusterEpilogue epi;
-    epi.params = params; epi.mask_p = mask_p; epi.nP = nP; epi.idx = &idx; epi.out_host = out_host;
-    epi.cluster_of = cluster_of; epi.sizes = sizes;
-    uint64_t call_max_W = 0;
-    for (uint64_t i = 0; i < n_windows; ++i) call_max_W = std::max(call_max_W, window_W(m, windows[i].site_begin, windows[i].site_end));
-    epi.adj_bytes = af_small_certain(params->identity_kind, nP, m->n_hap_pad, call_max_W) ? 0 : af_adjacency_bytes(nP);
-    PairFront in{};
-    in.fn = "impop_cluster_scan"; in.identity_kind = params->identity_kind; in.round_digits = params->round_digits;
-    in.scan_host = nullptr; in.use_segmap = false;  // the site scan for S / D is not needed (impop_pairwise_scan's s_scope 2)
-    in.epi_fixed = ClusterEpilogue::fixed_bytes(nP); in.epi_per_window = epi.window_bytes();
-    in.out_per_window = sizeof(impop_cluster_stats) + (epi.want_members() ? 2 * (size_t)nP * 4 : 0);
-    // the general form keeps a window's adjacency rows in memory (20 MB at the limit): chunks of at most 2 GiB of them
-    in.max_chunk_windows = std::min<uint64_t>(65535, std::max<uint64_t>(1, (2ull << 30) / std::max<size_t>(in.epi_per_window, 1)));
-    return pairwise_front(ctx, m, windows, n_windows, in, epi);
 }

@@ -591,5 +591,62 @@ def test_compaction_and_window_mapping_at_scale(ctx, oracle):
         _check(oracle, oracle.pairwise_counts(bits, CN, a, b), b - a, recs["compact/all"][k], c, inA, inB, L, ("compact", k))
 
 
+# ---- (e) several chunks of overlapping windows --------------------------------------------------------------------------
+
+SLIDE_N, SLIDE_W = 40, 320
+SLIDE_CALLS = ({"kind": "match", "thr": 0.97, "rd": 4}, {"kind": "dice", "thr": 0.95, "rd": None})
+
+
+def _slide_inputs():
+    """Windows of 64 sites at step 16 (every site but the edges in four windows: shared segments) and an empty window among
+    them; a subset P and disjoint A / B."""
+    wins = _sliding((SLIDE_W - 64) // 16 + 1, 64, 16, start=0)
+    wins.insert(7, (100, 100, 0))
+    rng = np.random.default_rng(41)
+    inP = (rng.random(SLIDE_N) < 0.8).astype(np.uint8)
+    inA, inB = _pops(SLIDE_N, 42)
+    return wins, inP, inA, inB
+
+
+def _sc_slide(ctx, call):
+    wins, inP, inA, inB = _slide_inputs()
+    bm = ctx.synthetic(SLIDE_N, SLIDE_W, seed=43, keep_hap_major=True)
+    for ci, c in enumerate(SLIDE_CALLS):
+        call(f"slide/{ci}", lambda: bm.pairwise_scan(wins, inP, inA, inB, kind=c["kind"], threshold=c["thr"], round_digits=c["rd"], s_scope=1))
+    bm.free()
+
+
+def test_overlapping_windows_in_chunks_of_three(ctx, oracle):
+    """impop_pairwise_scan on sliding windows (elementary segments shared by neighbours, an empty window, subset P, A / B) with
+    IMPOP_PAIRWISE_CHUNK=3: several chunks, neighbouring chunks contract their shared segments again — the records of the one-chunk
+    call byte for byte, and both the oracle's."""
+    recs, trace = _launch("slide")
+    chunked, ctrace = _launch("slide", {"IMPOP_PAIRWISE_CHUNK": "3"})
+    wins, inP, inA, inB = _slide_inputs()
+    assert all(not (a & b) for a, b in zip(inA, inB)) and inA.any() and inB.any() and 1 < inP.sum() < SLIDE_N
+    for tag in recs:
+        assert trace[tag]["chunks"] == 1 and ctrace[tag]["chunks"] == (len(wins) + 2) // 3, (tag, trace[tag], ctrace[tag])
+    _same_records(recs, chunked, "one chunk vs chunks of three windows")
+    bm = ctx.synthetic(SLIDE_N, SLIDE_W, seed=43, keep_hap_major=False)
+    sel = np.nonzero(inP)[0]
+    try:
+        for ci, c in enumerate(SLIDE_CALLS):
+            for got in (recs, chunked):
+                for k, (a, b, L) in enumerate(wins):
+                    I = oracle.pairwise_counts(bm.download(a, b), SLIDE_N, 0, b - a) if b > a else np.zeros((SLIDE_N, SLIDE_N), np.int64)
+                    sim = oracle.identity(I, b - a, {"match": 0, "dice": 1}[c["kind"]])
+                    rec, what = got[f"slide/{ci}"][k], (ci, k, (a, b, L))
+                    pi, ps, _, G = oracle.pica2(sim[np.ix_(sel, sel)], c["thr"], L if L else None, c["rd"])
+                    assert int(rec["n_groups"]) == G, what + (int(rec["n_groups"]), G)
+                    for f, v in (("pi", pi), ("pi_site", ps)):
+                        x = float(rec[f])
+                        assert (x != x and v != v) or rel_close(x, v, REL, 0.0), what + (f, x, v)
+                    h, _ = oracle.hfst(sim, inA, inB, L if L else None, c["rd"])
+                    for f, v in h.items():
+                        assert stat_close(f, float(rec[f]), v, h["dxy"], REL), what + (f, float(rec[f]), v)
+    finally:
+        bm.free()
+
+
 SCENARIOS = {"chains": _sc_chains, "forced_chain": _sc_forced_chain, "high_u16": _sc_high_u16, "big_ld": _sc_big_ld,
-             "compact": _sc_compact}
+             "compact": _sc_compact, "slide": _sc_slide}

@@ -253,3 +253,47 @@ def test_carve_layout(carve_exe, sizes):
         end = o + s
         assert end <= total
     assert total - end < 256
+
+
+# ---- csrc/pair_plan.h: Gram cells and chunks of the windowed all-pairs calls (plain C++, no HIP, no GPU) ------------------
+
+@pytest.fixture(scope="module")
+def pair_plan_exe(tmp_path_factory):
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("g++ not available")
+    exe = str(tmp_path_factory.mktemp("pair_plan") / "pair_plan")
+    r = subprocess.run([gxx, "-std=c++17", "-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                        "-I" + os.path.join(ROOT, "impop_amd", "csrc"), "-x", "c++", os.path.join(ROOT, "tests", "fuzz", "pair_plan.cc"),
+                        "-o", exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+    return exe
+
+
+_TILED = [(0, 10), (10, 20), (20, 30), (30, 40), (40, 50)]
+_SLIDING = [(s, s + 4) for s in range(0, 12, 2)]  # 6 windows of 4 sites at step 2: 7 elementary segments
+_BIG = 8192
+PAIR_PLAN_CASES = {  # name: (windows, cap, win_cap, the driver's line)
+    "tiled": (_TILED, _BIG, _BIG, "plan segmented=0 cells=5 chunks=1"),
+    "tiled_with_empty": (_TILED[:2] + [(20, 20)] + _TILED[2:4], _BIG, _BIG, "plan segmented=0 cells=5 chunks=1"),
+    "sliding": (_SLIDING, _BIG, _BIG, "plan segmented=1 cells=7 chunks=1"),
+    "sliding_reversed": (_SLIDING[::-1], _BIG, _BIG, "plan segmented=1 cells=7 chunks=1"),
+    "identical_and_nested": ([(0, 10), (0, 10), (3, 6)], _BIG, _BIG, "plan segmented=1 cells=3 chunks=1"),
+    "overlap_below_5_percent": ([(0, 20), (19, 39)], _BIG, _BIG, "plan segmented=0 cells=2 chunks=1"),
+    "only_empty": ([(5, 5), (5, 5), (3, 3)], _BIG, _BIG, "plan segmented=0 cells=3 chunks=1"),
+    "one_window": ([(7, 19)], _BIG, _BIG, "plan segmented=0 cells=1 chunks=1"),
+    "sliding_cap_3": (_SLIDING, 3, _BIG, "plan segmented=1 cells=7 chunks=3"),  # neighbouring chunks re-contract a segment
+    "sliding_win_cap_2": (_SLIDING, _BIG, 2, "plan segmented=1 cells=7 chunks=3"),
+    "window_wider_than_cap": ([(0, 10), (2, 4), (6, 8)], 4, _BIG, "too_wide window=0 cells=5"),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PAIR_PLAN_CASES))
+def test_pair_plan(pair_plan_exe, case):
+    """The driver checks the plan and every chunk against its own site-by-site model (tests/fuzz/pair_plan.cc lists the properties)
+    and exits non-zero on any breach; here: it ran clean under ASan + UBSan and took the branch the case is there for."""
+    windows, cap, win_cap, line = PAIR_PLAN_CASES[case]
+    args = [pair_plan_exe, str(cap), str(win_cap)] + [str(x) for w in windows for x in w]
+    r = subprocess.run(args, capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "ERROR" not in r.stderr and "runtime error" not in r.stderr, (r.returncode, r.stderr[-4000:])
+    assert r.stdout.strip() == line
