@@ -101,11 +101,12 @@ def _regime(launches, what, ksplit=1, u16=1, chain_min=2, chain=None):
 
 # ---- the oracle ---------------------------------------------------------------------------------------------------
 
-def _check(oracle, I, W, rec, call, inA, inB, L, what):
-    """One window's record against oracle identity -> pica2 / h-fst (or hud.py's grouped Fst) from its exact counts I."""
-    kind, thr, rd, fm = call["kind"], call["thr"], call["rd"], call["fm"]
+def _check(oracle, I, W, rec, call, inA, inB, L, what, sel=None):
+    """One window's record against oracle identity -> pica2 (of the members `sel`, indices; None: of everybody) / h-fst (or
+    hud.py's grouped Fst) from its exact counts I.  (tests/test_gpu_irregular_overlap.py uses it too.)"""
+    kind, thr, rd, fm = call["kind"], call["thr"], call["rd"], call.get("fm", "direct")
     sim = oracle.identity(I, W, {"match": 0, "dice": 1}[kind])
-    pi, ps, _, G = oracle.pica2(sim, thr, L if L else None, rd)
+    pi, ps, _, G = oracle.pica2(sim if sel is None else sim[np.ix_(sel, sel)], thr, L if L else None, rd)
     assert int(rec["n_groups"]) == G, what + (int(rec["n_groups"]), G)
     for k, v in (("pi", pi), ("pi_site", ps)):
         got = float(rec[k])
@@ -634,16 +635,7 @@ def test_overlapping_windows_in_chunks_of_three(ctx, oracle):
             for got in (recs, chunked):
                 for k, (a, b, L) in enumerate(wins):
                     I = oracle.pairwise_counts(bm.download(a, b), SLIDE_N, 0, b - a) if b > a else np.zeros((SLIDE_N, SLIDE_N), np.int64)
-                    sim = oracle.identity(I, b - a, {"match": 0, "dice": 1}[c["kind"]])
-                    rec, what = got[f"slide/{ci}"][k], (ci, k, (a, b, L))
-                    pi, ps, _, G = oracle.pica2(sim[np.ix_(sel, sel)], c["thr"], L if L else None, c["rd"])
-                    assert int(rec["n_groups"]) == G, what + (int(rec["n_groups"]), G)
-                    for f, v in (("pi", pi), ("pi_site", ps)):
-                        x = float(rec[f])
-                        assert (x != x and v != v) or rel_close(x, v, REL, 0.0), what + (f, x, v)
-                    h, _ = oracle.hfst(sim, inA, inB, L if L else None, c["rd"])
-                    for f, v in h.items():
-                        assert stat_close(f, float(rec[f]), v, h["dxy"], REL), what + (f, float(rec[f]), v)
+                    _check(oracle, I, b - a, got[f"slide/{ci}"][k], c, inA, inB, L, (ci, k, (a, b, L)), sel=sel)
     finally:
         bm.free()
 

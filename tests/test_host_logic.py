@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import overlap_cases
 from conftest import ROOT, load_golden
 
 
@@ -273,6 +274,7 @@ def pair_plan_exe(tmp_path_factory):
 _TILED = [(0, 10), (10, 20), (20, 30), (30, 40), (40, 50)]
 _SLIDING = [(s, s + 4) for s in range(0, 12, 2)]  # 6 windows of 4 sites at step 2: 7 elementary segments
 _BIG = 8192
+_IRREGULAR = [(a, b) for a, b, _ in overlap_cases.WINDOWS]  # unsorted; duplicate, nested, empty and one-site windows, one behind a gap
 PAIR_PLAN_CASES = {  # name: (windows, cap, win_cap, the driver's line)
     "tiled": (_TILED, _BIG, _BIG, "plan segmented=0 cells=5 chunks=1"),
     "tiled_with_empty": (_TILED[:2] + [(20, 20)] + _TILED[2:4], _BIG, _BIG, "plan segmented=0 cells=5 chunks=1"),
@@ -285,6 +287,11 @@ PAIR_PLAN_CASES = {  # name: (windows, cap, win_cap, the driver's line)
     "sliding_cap_3": (_SLIDING, 3, _BIG, "plan segmented=1 cells=7 chunks=3"),  # neighbouring chunks re-contract a segment
     "sliding_win_cap_2": (_SLIDING, _BIG, 2, "plan segmented=1 cells=7 chunks=3"),
     "window_wider_than_cap": ([(0, 10), (2, 4), (6, 8)], 4, _BIG, "too_wide window=0 cells=5"),
+    # the irregular list of tests/test_gpu_irregular_overlap.py: what that test assumes of the plan, from the planner itself
+    "irregular": (_IRREGULAR, _BIG, _BIG, "plan segmented=1 cells=18 chunks=1"),
+    "irregular_win_cap_3": (_IRREGULAR, _BIG, 3, "plan segmented=1 cells=18 chunks=4"),
+    "irregular_win_cap_2": (_IRREGULAR, _BIG, 2, "plan segmented=1 cells=18 chunks=6"),
+    "irregular_cap_12": (_IRREGULAR, 12, _BIG, "too_wide window=2 cells=14"),
 }
 
 
