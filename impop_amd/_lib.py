@@ -27,6 +27,7 @@ KEEP_SITE_BLOCKED, KEEP_HAP_MAJOR, KEEP_DENSE_SCAN, KEEP_NO_RARE_SPLIT = 1, 2, 4
 IDENTITY_MATCH, IDENTITY_DICE = 0, 1
 EHH_FLANKS_REFERENCE, EHH_FLANKS_TWO_SIDED = 0, 1
 EHH_SCAN_MAX_N = 4096  # IMPOP_EHH_SCAN_MAX_N
+HAPLOTYPE_MAX_N = 4096  # IMPOP_HAPLOTYPE_MAX_N
 
 
 class Window(C.Structure):
@@ -103,6 +104,16 @@ class EhhStats(C.Structure):
                 ("area_milli", (C.c_int64 * 2) * 2), ("area", C.c_double * 2)]
 
 
+class HaplotypeParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_uint32), ("max_chunk_bytes", C.c_uint64)]
+
+
+class HaplotypeStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_distinct", C.c_uint32), ("largest", C.c_uint32), ("second", C.c_uint32),
+                ("n_singletons", C.c_uint32), ("n_sites", C.c_uint32), ("sum_sq", C.c_uint64),
+                ("h1", C.c_double), ("h12", C.c_double), ("h2_h1", C.c_double), ("hap_diversity", C.c_double)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -129,6 +140,7 @@ assert C.sizeof(WindowStats) == 128 and C.sizeof(Window) == 24 and C.sizeof(Pair
 assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
 assert C.sizeof(PanelStats) == 48 and C.sizeof(PanelWindow) == 8
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
+assert C.sizeof(HaplotypeStats) == 64 and C.sizeof(HaplotypeParams) == 16
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -205,6 +217,9 @@ SIGNATURES = {
     "impop_matrix_positions": (C.c_int, [_vp, C.c_uint64, C.c_uint64, _u64p, _u64p]),
     "impop_ehh": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_int, _f64p, _u32p]),
     "impop_ehh_scan": (C.c_int, [_vp, _vp, C.POINTER(EhhWindow), C.c_uint64, _u64p, C.POINTER(EhhParams), C.POINTER(EhhStats)]),
+    "impop_haplotype_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(HaplotypeParams),
+                                       C.POINTER(HaplotypeStats), _u32p, _u32p]),
+    "impop_ctx_haplotype_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_fst_grouped_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, _u8p, _u8p, C.c_double, C.c_uint64, C.c_int, _u32p, _f64p,
                                                   _u64p]),
     "impop_tajimas_d": (C.c_int, [_vp, _i64p, _f64p, _f64p, C.c_uint64, _f64p, _f64p]),

@@ -16,23 +16,13 @@
 #include "device_utils.h"
 #include "internal.h"
 #include "sb64.h"
+#include "scan_route.h"
 
 namespace impop {
 
-// site_begin..site_end: sites of the SB64 layout streamed; rare_begin..rare_end: entries of the split index's rare stream
-// (internal.h, d_vrare).  Either range may be empty.
-struct ScanTile {
-    uint64_t site_begin, site_end;
-    uint64_t rare_begin, rare_end;
-};
 struct TilePartial {  // 48 B
     uint32_t s_all, s_p, s_a, s_b;
     uint64_t sum_p, sum_a, sum_b, sum_ab;
-};
-struct WinDesc {
-    uint64_t t0, t1;  // tile range
-    uint64_t n_sites;
-    uint64_t seq_len;
 };
 struct PopSizes {
     uint32_t n, nP, nA, nB;
@@ -686,19 +676,6 @@ static uint32_t popcount_vec(const std::vector<uint32_t> &v) {
     return c;
 }
 
-// What a scan of `windows` streams, derived once for impop_scan_plan_create and impop_scan_multi (scan_route below).
-struct ScanRoute {
-    bool indexed = false;  // the variable-site index (d_vsb, tiles in kept-site coordinates), else d_sb (dense, or a compacted matrix)
-    bool split = false;    // ... and its rare-entry stream (d_vrare)
-    const uint32_t *sb = nullptr;
-    const uint64_t *rare = nullptr;           // null unless split
-    std::vector<impop_window> mapped, rare_w;  // the windows as ranges of sb's sites and (split) of rare's entries
-    uint32_t tile_blocks = 0;
-    std::vector<ScanTile> tiles;
-    std::vector<WinDesc> wins;
-    uint64_t bytes_streamed = 0;
-};
-
 // windows -> elementary segments between sorted window boundaries (a segment is tiled iff some
 // window covers it, and exactly once however many windows overlap it) -> tiles of <= tile_blocks
 // 64-site blocks; every window becomes a contiguous tile range [t0, t1).
@@ -706,7 +683,7 @@ struct ScanRoute {
 // ordered as the edges are.  A segment's blocks and entries are cut into the same number of tiles by their bytes (an entry is
 // 8 B, tile_blocks blocks the budget): one workgroup reads a share of both streams.  Without rare entries the tiles are those
 // of the unsplit index.
-static void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
+void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
     const impop_window *windows = rt.mapped.data(), *rare = rt.split ? rt.rare_w.data() : nullptr;
     std::vector<ScanTile> &tiles = rt.tiles;
     struct Cut {
@@ -881,7 +858,7 @@ static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_w
 }
 
 // every window lies in the matrix and is at most 2^32 - 1 sites long (impop_window_stats.n_sites is 32 bits wide)
-static int check_windows(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
+int impop::check_windows(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
     for (uint64_t i = 0; i < n_windows; ++i) {
         REQUIRE(windows[i].site_begin <= windows[i].site_end && windows[i].site_end <= matrix_span(m),
                 "%s: window %llu: bad site range [%llu,%llu) for %llu sites", fn, (unsigned long long)i,
@@ -896,7 +873,7 @@ static int check_windows(const char *fn, const impop_matrix *m, const impop_wind
 // windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams: the variable-site
 // index when the matrix has one and no site weights (d_wt is indexed by matrix site), with the rare-entry stream of a split
 // index; else the matrix itself (compacted: original coordinates -> kept-site index ranges).  tile_blocks 0: the default.
-static int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                       uint32_t tile_blocks, ScanRoute &rt) {
     rt.indexed = m->d_vsb != nullptr && m->wt_prefix.empty();
     rt.split = rt.indexed && m->d_vrare != nullptr;

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -36,6 +36,10 @@ EHH_DTYPE = np.dtype([("n_members", "<u4", (2,)), ("ref_allele", "<u4"), ("reser
 assert EHH_DTYPE.itemsize == 64
 EHH_WINDOW_DTYPE = np.dtype([("site_begin", "<u8"), ("site_end", "<u8"), ("core_site", "<u8")])
 EHH_FLANKS = {"reference": _lib.EHH_FLANKS_REFERENCE, "two-sided": _lib.EHH_FLANKS_TWO_SIDED}
+
+HAPLOTYPE_DTYPE = np.dtype([("n_members", "<u4"), ("n_distinct", "<u4"), ("largest", "<u4"), ("second", "<u4"), ("n_singletons", "<u4"),
+                            ("n_sites", "<u4"), ("sum_sq", "<u8"), ("h1", "<f8"), ("h12", "<f8"), ("h2_h1", "<f8"), ("hap_diversity", "<f8")])
+assert HAPLOTYPE_DTYPE.itemsize == 64
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), ("n_members", "<u4"), ("n_groups", "<u4"), ("s_p", "<u4"),
@@ -182,6 +186,12 @@ class Context:
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_ehh_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
+
+    def haplotype_elapsed(self):
+        """-> ([fingerprint, grouping, verification] kernel ms of haplotype_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 3)(), C.c_uint64()
+        check(self._lib.impop_ctx_haplotype_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
 
     def close(self) -> None:
         if self._h:
@@ -593,6 +603,25 @@ class BitMatrix:
                                                out.ctypes.data_as(C.POINTER(ClusterStats)),
                                                cl.ctypes.data_as(u32p) if want_members else None,
                                                sz.ctypes.data_as(u32p) if want_members else None))
+        return (out, cl, sz) if want_members else out
+
+    def haplotype_scan(self, windows, mask_p=None, want_members: bool = False, max_chunk_bytes: int = 0):
+        """Haplotype-frequency statistics per window (impop_haplotype_scan): the classes of members of mask_p whose bits agree at
+        every column of the window, from the scan's own stream (no hap-major operand).  -> records (HAPLOTYPE_DTYPE: K = n_distinct,
+        H1, H12, H2/H1, haplotype diversity), and with want_members also class_of and sizes, both [n_windows, |P|], laid out and
+        ordered like cluster_scan's tables."""
+        w = make_windows(windows)
+        out = np.zeros(len(w), dtype=HAPLOTYPE_DTYPE)
+        prm = HaplotypeParams(C.sizeof(HaplotypeParams), 0, int(max_chunk_bytes))
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        n_p = self.n_hap if mask_p is None else int(np.unpackbits(kp.view(np.uint8), bitorder="little")[: self.n_hap].sum())
+        cl = np.zeros((len(w), n_p), dtype=np.uint32) if want_members else None
+        sz = np.zeros((len(w), n_p), dtype=np.uint32) if want_members else None
+        u32p = C.POINTER(C.c_uint32)
+        check(self.ctx._lib.impop_haplotype_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, C.byref(prm),
+                                                 out.ctypes.data_as(C.POINTER(HaplotypeStats)),
+                                                 cl.ctypes.data_as(u32p) if want_members else None,
+                                                 sz.ctypes.data_as(u32p) if want_members else None))
         return (out, cl, sz) if want_members else out
 
     def ehh_scan(self, windows, cores, mask=None, ref_hap: int = 0, flanks: str = "reference", max_chunk_bytes: int = 0) -> np.ndarray:

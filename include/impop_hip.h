@@ -452,6 +452,37 @@ typedef struct impop_cluster_stats { /* 32 bytes, fixed layout */
 int impop_cluster_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                        const uint64_t *mask_p, const impop_cluster_params *params, impop_cluster_stats *out_host,
                        uint32_t *cluster_of, uint32_t *sizes);
+#define IMPOP_HAPLOTYPE_MAX_N 4096u
+/* Haplotype-frequency statistics per window from the stream impop_scan reads (no hap-major operand, no Gram; works on matrices
+ * uploaded without IMPOP_KEEP_HAP_MAJOR, on compacted and on weighted ones).  Two members of P are the same haplotype in a window
+ * iff their bits agree at every column of the window; site weights play no part in that, n_sites is the window's W as every other
+ * record reports it (sum of weights, or the length).  Classes are ordered by (-size, smallest member index); class_of and sizes
+ * have the layout and order of impop_cluster_scan's cluster_of and sizes, and at threshold 1.0 on the `match` identity that call
+ * returns the same integers.  largest and second are the two largest sizes (second = 0 when there is one class).  The doubles
+ * follow from the integers, with n = n_members, in this operation order:
+ *     h1 = (double)sum_sq / ((double)n * (double)n)              h12 = h1 + 2.0 * ((double)largest / n) * ((double)second / n)
+ *     h2_h1 = (h1 - ((double)largest / n) * ((double)largest / n)) / h1      hap_diversity = n < 2 ? 0.0 : (1.0 - h1) * n / (n - 1)
+ * The result is exact: members are grouped by a 128-bit fingerprint of their bits, every group is then compared bit by bit with
+ * its representative, and a window in which that comparison fails is regrouped by comparison alone.  A window without sites has
+ * one class.  |P| = 0 returns IMPOP_E_INVALID, |P| > IMPOP_HAPLOTYPE_MAX_N IMPOP_E_UNSUPPORTED before anything is uploaded or
+ * launched; n_windows == 0 returns IMPOP_OK.  Windows may overlap.  max_chunk_bytes (0 = 1 GiB) bounds the device memory of one
+ * chunk of windows; chunking, the route (index, rows only, dense) and compaction never change a record. */
+typedef struct impop_haplotype_params {
+    uint32_t struct_size;
+    uint32_t reserved;
+    uint64_t max_chunk_bytes; /* 0 = default */
+} impop_haplotype_params;
+typedef struct impop_haplotype_stats { /* 64 bytes, fixed layout */
+    uint32_t n_members, n_distinct, largest, second, n_singletons, n_sites;
+    uint64_t sum_sq;          /* sum of size_k^2 */
+    double h1, h12, h2_h1, hap_diversity;
+} impop_haplotype_stats;
+int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                         const uint64_t *mask_p, const impop_haplotype_params *params, impop_haplotype_stats *out_host,
+                         uint32_t *class_of /* nullable, n_windows x |P| */, uint32_t *sizes /* nullable, n_windows x |P| */);
+/* With impop_ctx_gram_timing on, impop_haplotype_scan brackets its kernels per chunk: kernel_ms[0] = fingerprints, [1] = grouping,
+ * [2] = bitwise verification (and regrouping of flagged windows), summed since enable / reset; chunks = chunks timed. */
+int impop_ctx_haplotype_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
 /* Measurement aid (like impop_scan_plan_timing): with timing enabled every Gram launch of impop_pairwise_scan on this context
  * is bracketed with hipEvents on the context's stream; elapsed() synchronises and returns the summed Gram-kernel time and the
  * number of launches since enable / reset. */

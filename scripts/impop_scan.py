@@ -12,6 +12,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --sim-list windows.tsv --format pica2 -t 0.999 -r 5                         # one `.sim` table per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format af [-t 1.0] [-u subset.txt] [--af-clusters c.tsv] [--af-details d.tsv]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ehh [--ehh-core-offset N | --ehh-cores pos.txt] [--ehh-flanks two-sided]
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
 window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
@@ -42,6 +43,12 @@ REF_ALT compares the allele with that of --ehh-ref NAME (default: the matrix's f
 of the two halves' EHH curves in sites and AREA their sum, all three exact thousandths printed as integer.milli ("12.276").
 --ehh-flanks reference (default) takes both halves from the sites right of the core like ehhgfa.py:56-61, two-sided the left half
 from the sites left of it.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --compact, --devices N, -t / -r.
+
+--format hapstats (impop_haplotype_scan): the haplotype-frequency statistics of every BED row among the sequences of -u (default:
+all) - two sequences are the same haplotype when they agree at every site of the window.  One table REGION LENGTH SAMPLES SITES
+HAPLOTYPES H1 H12 H2_H1 HAP_DIVERSITY (SAMPLES = sequences compared, SITES = the window's sites or summed weights, HAPLOTYPES = distinct
+ones, H1 = haplotype homozygosity, H12 / H2_H1 after Garud et al., the doubles "%.8f").  Streams the scan index, needs no all-pairs
+operand; --compact allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
 
 --panel A.txt B.txt ... (2..8 disjoint lists; run_tajd_panels.sh / run_h_fst_panels.sh).  --format hfst: one h-fst table per pair,
 headed `# A-vs-B`; --format tajd: one tajd table per panel, headed `# A`, SAMPLES = the list's line count, -t 0.999 -r 5 and S
@@ -214,6 +221,10 @@ class Runner:
         return self.bm.pairwise_scan_panel(self.local_wins, pops, kind=self.args.identity, threshold=threshold, round_digits=round_digits,
                                            s_scope=0 if want_s else 2, want_pairs=want_pairs)
 
+    def hapstats(self, mask_p):
+        """haplotype-frequency statistics per window (impop_haplotype_scan; HAPLOTYPE records).  One process, one GPU."""
+        return self.bm.haplotype_scan(self.local_wins, mask_p=mask_p)
+
     def close(self):
         for sk, ck in zip(self.slabs, self.ctxs):
             sk.free(); ck.close()
@@ -326,6 +337,36 @@ def ehh_refusal(args):
     if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
         return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
     return None
+
+
+HAP_HEADER = "REGION\tLENGTH\tSAMPLES\tSITES\tHAPLOTYPES\tH1\tH12\tH2_H1\tHAP_DIVERSITY"
+
+
+def hap_refusal(args):
+    """what --format hapstats does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "hapstats":
+        return None
+    if args.sim_list:
+        return "--format hapstats scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format hapstats is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format hapstats runs on one GPU: not with --devices N"
+    if args.panel or args.pop_a or args.pop_b or args.sample_list:
+        return "--format hapstats compares the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    return None
+
+
+def write_hap_table(out, regions, L_col, recs):
+    """the table of --format hapstats from impop_haplotype_stats records (one per region)"""
+    print(HAP_HEADER, file=out)
+    for reg, L, r in zip(regions, L_col, recs):
+        print(f"{reg}\t{L}\t{int(r['n_members'])}\t{int(r['n_sites'])}\t{int(r['n_distinct'])}\t{float(r['h1']):.8f}\t{float(r['h12']):.8f}\t"
+              f"{float(r['h2_h1']):.8f}\t{float(r['hap_diversity']):.8f}", file=out)
 
 
 def milli_text(k):
@@ -510,9 +551,10 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
-                         "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`)")
+                         "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
+                         "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
@@ -554,7 +596,7 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = af_refusal(args) or ehh_refusal(args)
+    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args)
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
@@ -695,6 +737,7 @@ def main():
     af_recs = np.zeros(n_rows, dtype=impop_amd.CLUSTER_DTYPE)
     af_clusters = [None] * n_rows
     ehh_lines = [None] * n_rows
+    hap_recs = np.zeros(n_rows, dtype=impop_amd.HAPLOTYPE_DTYPE)
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -795,6 +838,14 @@ def main():
                 af_recs[idx] = res
             run.close()
             continue
+        if fmt == "hapstats":
+            if mask_p is not None and not mask_p.any():
+                print("Error: --format hapstats: -u selects no sequence of the matrix", file=sys.stderr)
+                run.close()
+                sys.exit(2)
+            hap_recs[idx] = run.hapstats(mask_p)
+            run.close()
+            continue
         if fmt == "ehh":
             recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=mask_p, ref_hap=ref_hap, flanks=args.ehh_flanks or "reference")
             for i, c, r in zip(idx, cores, recs):
@@ -861,6 +912,8 @@ def main():
         if args.af_details:
             with open(args.af_details, "w", newline="") as fh:
                 write_af_details(fh, regions, af_clusters, float(pica_t))
+    elif fmt == "hapstats":
+        write_hap_table(out, [r[0] for r in rows], L_col, hap_recs)
     elif fmt == "ehh":
         print(EHH_HEADER, file=out)
         for lines in ehh_lines:
