@@ -114,6 +114,18 @@ class HaplotypeStats(C.Structure):
                 ("h1", C.c_double), ("h12", C.c_double), ("h2_h1", C.c_double), ("hap_diversity", C.c_double)]
 
 
+class LdParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_mac", C.c_uint32), ("max_sites", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class LdStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("n_qualifying", C.c_uint32), ("n_used", C.c_uint32),
+                ("n_perfect", C.c_uint32), ("n_complete", C.c_uint32), ("omega_split", C.c_uint32), ("reserved", C.c_uint32),
+                ("sum_r2", C.c_double), ("sum_dprime", C.c_double), ("zns", C.c_double), ("mean_dprime", C.c_double),
+                ("omega_max", C.c_double)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -141,6 +153,8 @@ assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
 assert C.sizeof(PanelStats) == 48 and C.sizeof(PanelWindow) == 8
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
 assert C.sizeof(HaplotypeStats) == 64 and C.sizeof(HaplotypeParams) == 16
+assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
+LD_MAX_N, LD_MAX_SITES = 4096, 1024
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -220,6 +234,8 @@ SIGNATURES = {
     "impop_haplotype_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(HaplotypeParams),
                                        C.POINTER(HaplotypeStats), _u32p, _u32p]),
     "impop_ctx_haplotype_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_ld_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(LdParams), C.POINTER(LdStats), _u64p]),
+    "impop_ctx_ld_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_fst_grouped_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, _u8p, _u8p, C.c_double, C.c_uint64, C.c_int, _u32p, _f64p,
                                                   _u64p]),
     "impop_tajimas_d": (C.c_int, [_vp, _i64p, _f64p, _f64p, C.c_uint64, _f64p, _f64p]),

@@ -138,6 +138,7 @@ struct impop_ctx {
     bool gram_timing = false;
     impop::EventPairs gram_timer, cluster_timer, ehh_timer;
     impop::EventPairs hap_timer[3];  // impop_haplotype_scan: fingerprint / classify / verify + exact kernels (impop_ctx_haplotype_elapsed)
+    impop::EventPairs ld_timer[3];   // impop_ld_scan: select / gather / pairs kernels (impop_ctx_ld_elapsed)
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
     // all-pairs path run next to each other instead of one after the other
     hipStream_t side = nullptr;
@@ -230,6 +231,7 @@ int ctx_err_result(impop_ctx *ctx, const char *fn);  // after that sync: IMPOP_O
 constexpr uint32_t DEV_ERR_GROUPING = 1u;            // greedy_groups_bits ran out of its progress bound
 constexpr uint32_t DEV_ERR_CLUSTER = 2u;             // af label propagation ran out of its rounds
 constexpr uint32_t DEV_ERR_HAPSCAN = 8u;             // haplotype scan: the classes of a window do not partition its members
+constexpr uint32_t DEV_ERR_LDSCAN = 16u;             // LD scan: the rows gathered for a window are not its n_used
 constexpr uint32_t DEV_ERR_EHH = 4u;                 // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need

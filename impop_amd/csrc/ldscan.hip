@@ -1,0 +1,400 @@
+// ldscan.hip — impop_ld_scan: linkage disequilibrium between the sites of every window (Kelly's ZnS, mean |D'|, the Kim-Nielsen
+// omega) from the site-major rows alone.  A site's row holds the haplotypes as bits, so a site pair costs wps ANDs and popcounts.
+//
+// Windows are mapped straight onto d_sb, which holds every row of the matrix whatever index was built beside it (a compacted
+// matrix: onto its kept sites; the dropped ones are monomorphic and never qualify), so a record cannot depend on the upload's
+// keep flags.  Per chunk of windows, three launches:
+//   1. ld_select_kernel  one wave per 64-site block of a window: c = carriers among P of the lane's site, the ballot of
+//                        min(c, |P| - c) >= min_mac over the window's sites -> one 64-bit qualifying mask per block.
+//   2. ld_gather_kernel  one workgroup per window: q = the masks' popcount, a running prefix over the blocks ranks every
+//                        qualifying site, the sites of rank floor(k q / m) are kept; their rows ANDed with P, their c and their
+//                        original coordinate go to the chunk's scratch at [window][k].
+//   3. ld_pairs_kernel   one workgroup per window: the lane that owns site t runs k = 0..m-1 over broadcast rows and adds r2 into
+//                        a_t while k < t and into b_t while k > t, |D'| into dp_t while k < t — every pair is evaluated twice and
+//                        nothing is accumulated across lanes, so the doubles do not depend on scheduling.  One lane then runs the
+//                        sequential prefix L, suffix R and the omega search, and stores the record.
+// Operation order of every double: include/impop_hip.h, impop_ld_scan.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "device_utils.h"
+#include "internal.h"
+#include "sb64.h"
+#include "scan_route.h"
+
+namespace impop {
+
+constexpr int LD_T = 256;  // threads of every workgroup here
+// the used rows of a window are staged in LDS up to this many bytes (465 haplotypes x 512 sites: 32 KB); else read from scratch
+constexpr size_t LD_LDS_ROW_BYTES = 64 * 1024;
+static_assert(IMPOP_LD_MAX_N <= 4096u, "num^2 and den stay below 2^53 only for n <= 4096");
+
+struct LdWin {          // a window of a chunk
+    uint64_t s0, s1;    // its sites in d_sb
+    uint64_t blk_off;   // its first qualifying mask in the chunk's mask array
+    uint32_t n_sites, pad;  // W
+};
+
+// grid = (windows of the chunk, slices of a window's blocks)
+__global__ __launch_bounds__(LD_T) void ld_select_kernel(const uint32_t *__restrict__ sb, const LdWin *__restrict__ wins, uint32_t wps,
+                                                         uint32_t G, uint32_t r, const uint32_t *__restrict__ pbits, uint32_t nP,
+                                                         uint32_t min_mac, uint64_t *__restrict__ qmask) {
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const LdWin w = wins[blockIdx.x];
+    if (w.s1 <= w.s0) return;
+    const uint64_t b0 = w.s0 >> 6, b1 = (w.s1 + 63) >> 6;
+    for (uint64_t b = b0 + (uint64_t)blockIdx.y * 4 + wave; b < b1; b += 4ull * gridDim.y) {
+        uint32_t c = 0;
+        sb_for_each_dword<true>(sb + b * 64ull * wps, G, r, lane, [&](uint32_t k, uint32_t d) { c += __popc(d & pbits[k]); });
+        const uint64_t site = b * 64 + lane;
+        const uint32_t mac = c < nP - c ? c : nP - c;
+        const uint64_t mask = __ballot(site >= w.s0 && site < w.s1 && mac >= min_mac);
+        if (lane == 0) qmask[w.blk_off + (b - b0)] = mask;
+    }
+}
+
+// grid = windows of the chunk.  qm[2 w] = q, qm[2 w + 1] = m.
+__global__ __launch_bounds__(LD_T) void ld_gather_kernel(const uint32_t *__restrict__ sb, const LdWin *__restrict__ wins, uint32_t wps,
+                                                         uint32_t G, uint32_t r, const uint32_t *__restrict__ pbits,
+                                                         const uint64_t *__restrict__ pos, uint32_t max_sites,
+                                                         const uint64_t *__restrict__ qmask, uint32_t *__restrict__ rows,
+                                                         uint32_t *__restrict__ cs, uint64_t *__restrict__ coords, uint32_t *__restrict__ qm,
+                                                         uint32_t *__restrict__ err) {
+    __shared__ uint64_t s_site[IMPOP_LD_MAX_SITES];
+    __shared__ uint32_t s_scan[LD_T];
+    __shared__ uint32_t s_q, s_base, s_placed;
+    const uint32_t tid = threadIdx.x;
+    const LdWin w = wins[blockIdx.x];
+    const uint64_t b0 = w.s0 >> 6, nb = w.s1 > w.s0 ? ((w.s1 + 63) >> 6) - b0 : 0;
+    const uint64_t *qw = qmask + w.blk_off;
+    if (tid == 0) {
+        s_q = 0;
+        s_base = 0;
+        s_placed = 0;
+    }
+    for (uint32_t k = tid; k < max_sites; k += LD_T) s_site[k] = w.s0;  // a site that can be read, whatever goes wrong below
+    __syncthreads();
+    uint32_t mine = 0;
+    for (uint64_t i = tid; i < nb; i += LD_T) mine += (uint32_t)__popcll(qw[i]);
+    if (mine) atomicAdd(&s_q, mine);
+    __syncthreads();
+    const uint64_t q = s_q, m = q < max_sites ? q : max_sites;
+    // ranks: blocks LD_T at a time, an exclusive scan of their counts on top of the running base
+    for (uint64_t i0 = 0; i0 < nb && m; i0 += LD_T) {
+        const uint64_t i = i0 + tid;
+        uint64_t mask = i < nb ? qw[i] : 0ull;
+        const uint32_t c = (uint32_t)__popcll(mask);
+        s_scan[tid] = c;
+        __syncthreads();
+        for (uint32_t off = 1; off < LD_T; off <<= 1) {
+            const uint32_t v = tid >= off ? s_scan[tid - off] : 0u;
+            __syncthreads();
+            s_scan[tid] += v;
+            __syncthreads();
+        }
+        uint64_t rank = (uint64_t)s_base + s_scan[tid] - c;
+        uint32_t placed = 0;
+        for (; mask; mask &= mask - 1, ++rank) {
+            // rank is used iff some k < m has floor(k q / m) == rank; q >= m: at most one, the smallest k >= rank m / q
+            const uint64_t k = (rank * m + q - 1) / q;
+            if (k < m && k * q / m == rank) {
+                s_site[k] = (b0 + i) * 64 + (uint64_t)__builtin_ctzll(mask);
+                ++placed;
+            }
+        }
+        if (placed) atomicAdd(&s_placed, placed);
+        __syncthreads();
+        if (tid == LD_T - 1) s_base += s_scan[tid];
+        __syncthreads();
+    }
+    __syncthreads();
+    const uint64_t o = (uint64_t)blockIdx.x * max_sites;
+    for (uint32_t k = tid; k < max_sites; k += LD_T) coords[o + k] = k < m ? (pos ? pos[s_site[k]] : s_site[k]) : 0ull;
+    uint32_t *dst = rows + o * wps;
+    for (uint64_t idx = tid; idx < m * wps; idx += LD_T) {
+        const uint32_t k = (uint32_t)(idx / wps), j = (uint32_t)(idx % wps);
+        const uint64_t s = s_site[k];
+        dst[idx] = sb[sb_index(wps, G, r, s >> 6, (uint32_t)(s & 63), j)] & pbits[j];
+    }
+    __syncthreads();  // the rows this workgroup wrote are read back below
+    for (uint32_t k = tid; k < m; k += LD_T) {
+        uint32_t c = 0;
+        for (uint32_t j = 0; j < wps; ++j) c += __popc(dst[(uint64_t)k * wps + j]);
+        cs[o + k] = c;
+    }
+    if (tid == 0) {
+        qm[2 * blockIdx.x] = (uint32_t)q;
+        qm[2 * blockIdx.x + 1] = (uint32_t)m;
+        if (s_placed != m) atomicOr(err, DEV_ERR_LDSCAN);
+    }
+}
+
+// grid = windows of the chunk.  Dynamic LDS: a, b, dp (8 max_sites each) | c (4 max_sites) | 4 counters | LDS_ROWS: the rows,
+// one every wps | 1 dwords (an odd stride: the lanes' own rows fall on different banks).
+template <bool LDS_ROWS>
+__global__ __launch_bounds__(LD_T) void ld_pairs_kernel(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ cs,
+                                                        const uint32_t *__restrict__ qm, const LdWin *__restrict__ wins, uint32_t wps,
+                                                        uint32_t max_sites, uint32_t nP, impop_ld_stats *__restrict__ rec) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char ld_lds[];
+    double *a = reinterpret_cast<double *>(ld_lds), *b = a + max_sites, *dp = b + max_sites;
+    uint32_t *cl = reinterpret_cast<uint32_t *>(dp + max_sites), *cnt = cl + max_sites, *lrows = cnt + 4;
+    const uint32_t tid = threadIdx.x, win = blockIdx.x;
+    const uint32_t q = qm[2 * win], m = qm[2 * win + 1];
+    const uint64_t o = (uint64_t)win * max_sites;
+    const uint32_t *grow = rows + o * wps;
+    const uint32_t stride = LDS_ROWS ? (wps | 1u) : wps;
+    if (LDS_ROWS)
+        for (uint32_t idx = tid; idx < m * wps; idx += LD_T) lrows[(idx / wps) * stride + idx % wps] = grow[idx];
+    for (uint32_t k = tid; k < m; k += LD_T) cl[k] = cs[o + k];
+    if (tid == 0) cnt[0] = cnt[1] = 0u;
+    __syncthreads();
+    const int64_t n = nP;
+    uint32_t perfect = 0, complete = 0;
+    for (uint32_t t = tid; t < m; t += LD_T) {
+        const int64_t ct = cl[t];
+        double at = 0.0, bt = 0.0, dt = 0.0;
+        for (uint32_t k = 0; k < m; ++k) {
+            uint32_t n11 = 0;
+            if (LDS_ROWS) {
+                for (uint32_t j = 0; j < wps; ++j) n11 += __popc(lrows[t * stride + j] & lrows[k * stride + j]);
+            } else {
+                for (uint32_t j = 0; j < wps; ++j) n11 += __popc(grow[(uint64_t)t * wps + j] & grow[(uint64_t)k * wps + j]);
+            }
+            const int64_t ck = cl[k];
+            const int64_t num = n * (int64_t)n11 - ct * ck;
+            const int64_t den = ct * (n - ct) * (ck * (n - ck));
+            const double r2 = (double)(num * num) / (double)den;
+            if (k < t) {
+                at += r2;
+                double d = 0.0;
+                if (num != 0) {
+                    const int64_t x = num > 0 ? ct * (n - ck) : ct * ck, y = num > 0 ? (n - ct) * ck : (n - ct) * (n - ck);
+                    const int64_t dmax = x < y ? x : y, an = num < 0 ? -num : num;
+                    d = (double)an / (double)dmax;
+                    complete += an == dmax;
+                }
+                dt += d;
+                perfect += num * num == den;
+            } else if (k > t) {
+                bt += r2;
+            }
+        }
+        a[t] = at;
+        b[t] = bt;
+        dp[t] = dt;
+    }
+    if (perfect) atomicAdd(&cnt[0], perfect);
+    if (complete) atomicAdd(&cnt[1], complete);
+    __syncthreads();
+    if (tid != 0) return;
+    // a[l] <- L(l), b[l] <- R(l); L(m) = sum_r2 and R(m) = 0 are not stored: no split uses them
+    double run = 0.0;
+    for (uint32_t j = 0; j < m; ++j) {
+        const double aj = a[j];
+        a[j] = run;
+        run += aj;
+    }
+    const double sum_r2 = run;
+    run = 0.0;
+    for (uint32_t j = m; j-- > 0;) {
+        run += b[j];
+        b[j] = run;
+    }
+    double sum_dp = 0.0;
+    for (uint32_t j = 0; j < m; ++j) sum_dp += dp[j];
+    double best = 0.0;
+    uint32_t split = 0;
+    for (uint32_t l = 2; l + 2 <= m; ++l) {
+        const double cross = (sum_r2 - a[l]) - b[l];
+        if (!(cross > 0.0)) continue;
+        const uint64_t within = (uint64_t)l * (l - 1) / 2 + (uint64_t)(m - l) * (m - l - 1) / 2, between = (uint64_t)l * (m - l);
+        const double om = ((a[l] + b[l]) / (double)within) / (cross / (double)between);
+        if (split == 0 || om > best) {
+            best = om;
+            split = l;
+        }
+    }
+    impop_ld_stats out;
+    out.n_members = nP;
+    out.n_sites = wins[win].n_sites;
+    out.n_qualifying = q;
+    out.n_used = m;
+    out.n_perfect = cnt[0];
+    out.n_complete = cnt[1];
+    out.omega_split = split;
+    out.reserved = 0;
+    out.sum_r2 = sum_r2;
+    out.sum_dprime = sum_dp;
+    const uint64_t pairs = (uint64_t)m * (m > 0 ? m - 1 : 0) / 2;
+    out.zns = m < 2 ? 0.0 : sum_r2 / (double)pairs;
+    out.mean_dprime = m < 2 ? 0.0 : sum_dp / (double)pairs;
+    out.omega_max = best;
+    rec[win] = out;
+}
+
+struct LdChunk {
+    uint64_t w_begin = 0, w_end = 0, n_blocks = 0, longest = 0;  // blocks of all its windows / of its longest one
+    std::vector<LdWin> wins;
+};
+
+}  // namespace impop
+
+using namespace impop;
+
+IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,
+                            const impop_ld_params *params, impop_ld_stats *out_host, uint64_t *used_sites) {
+    static_assert(sizeof(impop_ld_stats) == 72 && sizeof(impop_ld_params) == 24 && sizeof(LdWin) == 32, "ABI layout");
+    const char *fn = "impop_ld_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_ld_params), "impop_ld_params.struct_size mismatch");
+    REQUIRE(m->device == ctx->device, "%s: matrix lives on device %d, context on %d", fn, m->device, ctx->device);
+    const uint32_t n = m->g.n_hap, wps = m->g.wps;
+    std::vector<uint32_t> pbits(wps, 0u);
+    uint32_t nP = 0;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!mask_p || ((mask_p[i >> 6] >> (i & 63)) & 1ull)) {
+            pbits[i >> 5] |= 1u << (i & 31);
+            ++nP;
+        }
+    REQUIRE(nP > 0, "%s: the mask selects no haplotype", fn);
+    REQUIRE(params->min_mac >= 1, "%s: min_mac must be at least 1", fn);
+    const uint32_t max_sites = params->max_sites ? params->max_sites : 512u;
+    REQUIRE(max_sites >= 4 && max_sites <= IMPOP_LD_MAX_SITES, "%s: max_sites %u outside 4..%u", fn, max_sites, (uint32_t)IMPOP_LD_MAX_SITES);
+    int rc = check_windows(fn, m, windows, windows ? n_windows : 0);
+    if (rc) return rc;
+    if (nP > IMPOP_LD_MAX_N) {
+        set_error("%s: %u members exceed the exact-arithmetic limit (%u)", fn, nP, (uint32_t)IMPOP_LD_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_host, "%s: NULL windows/out", fn);
+    std::vector<impop_window> mapped;
+    map_windows(m, windows, n_windows, mapped);
+    for (uint64_t i = 0; i < n_windows; ++i)
+        REQUIRE(window_W(m, windows[i].site_begin, windows[i].site_end) <= 0xFFFFFFFFull,
+                "%s: window %llu: the weights of its columns add up to 2^32 or more; split the window", fn, (unsigned long long)i);
+
+    // windows in order, cut where the chunk's device bytes would pass the budget; a window alone may exceed it
+    const uint64_t budget = params->max_chunk_bytes ? params->max_chunk_bytes : (1ull << 30);
+    const uint64_t per_win = (uint64_t)max_sites * (4ull * wps + 12) + sizeof(impop_ld_stats) + sizeof(LdWin) + 8;
+    std::vector<LdChunk> chunks;
+    uint64_t bytes_streamed = 0;
+    for (uint64_t i = 0; i < n_windows;) {
+        LdChunk c;
+        c.w_begin = i;
+        uint64_t bytes = 0;
+        for (; i < n_windows; ++i) {
+            const uint64_t s0 = mapped[i].site_begin, s1 = mapped[i].site_end;
+            const uint64_t nb = s1 > s0 ? ((s1 + 63) >> 6) - (s0 >> 6) : 0;
+            const uint64_t add = per_win + nb * 8;
+            if (i > c.w_begin && bytes + add > budget) break;
+            bytes += add;
+            c.wins.push_back(LdWin{s0, s1, c.n_blocks, (uint32_t)window_W(m, windows[i].site_begin, windows[i].site_end), 0u});
+            c.n_blocks += nb;
+            c.longest = std::max(c.longest, nb);
+            bytes_streamed += nb * 256ull * wps;
+        }
+        c.w_end = i;
+        chunks.push_back(std::move(c));
+    }
+    size_t max_wins = 1, max_blocks = 1;
+    for (const LdChunk &c : chunks) {
+        max_wins = std::max(max_wins, c.wins.size());
+        max_blocks = std::max<size_t>(max_blocks, c.n_blocks);
+    }
+    REQUIRE(max_wins < 0x7FFFFFFFull, "%s: a chunk of %zu windows exceeds one launch", fn, max_wins);
+
+    // device: P as dwords | windows (up, through the page-locked staging with the same offsets) | records (down, staged) |
+    // (q, m) per window | qualifying masks | gathered rows, their c, their coordinates
+    Carve L;
+    const size_t o_pbits = L.take<uint32_t>(wps), o_wins = L.take<LdWin>(max_wins), o_rec = L.take<impop_ld_stats>(max_wins),
+                 staged = L.total(), o_qm = L.take<uint32_t>(2 * max_wins), o_qmask = L.take<uint64_t>(max_blocks),
+                 o_rows = L.take<uint32_t>(max_wins * max_sites * wps), o_cs = L.take<uint32_t>(max_wins * max_sites),
+                 o_coords = L.take<uint64_t>(max_wins * max_sites);
+    HIP_TRY(hipSetDevice(ctx->device));
+    void *d = nullptr, *pin = nullptr;
+    rc = ctx_scratch(ctx, L.total(), &d);
+    if (rc) return rc;
+    rc = ctx_pinned(ctx, staged, &pin);
+    if (rc) return rc;
+    char *dc = (char *)d, *hc = (char *)pin;
+    memcpy(hc + o_pbits, pbits.data(), (size_t)wps * 4);
+    HIP_TRY(hipMemcpyAsync(dc + o_pbits, hc + o_pbits, (size_t)wps * 4, hipMemcpyHostToDevice, ctx->stream));
+
+    const size_t lds_rows = (size_t)max_sites * (wps | 1u) * 4;
+    const bool rows_in_lds = lds_rows <= LD_LDS_ROW_BYTES;
+    const size_t lds_pairs = (size_t)max_sites * 28 + 16 + (rows_in_lds ? lds_rows : 0);
+    if (lds_pairs > 48 * 1024)
+        HIP_TRY(hipFuncSetAttribute(rows_in_lds ? (const void *)ld_pairs_kernel<true> : (const void *)ld_pairs_kernel<false>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pairs));
+
+    const uint32_t *d_pbits = (const uint32_t *)(dc + o_pbits);
+    const LdWin *d_wins = (const LdWin *)(dc + o_wins);
+    impop_ld_stats *d_rec = (impop_ld_stats *)(dc + o_rec);
+    uint32_t *d_qm = (uint32_t *)(dc + o_qm), *d_rows = (uint32_t *)(dc + o_rows), *d_cs = (uint32_t *)(dc + o_cs);
+    uint64_t *d_qmask = (uint64_t *)(dc + o_qmask), *d_coords = (uint64_t *)(dc + o_coords);
+    uint64_t launches = 0, qualifying = 0, used = 0;
+    const bool timed = ctx->gram_timing;
+    for (const LdChunk &c : chunks) {
+        const size_t cnt = c.wins.size();
+        memcpy(hc + o_wins, c.wins.data(), cnt * sizeof(LdWin));
+        HIP_TRY(hipMemcpyAsync(dc + o_wins, hc + o_wins, cnt * sizeof(LdWin), hipMemcpyHostToDevice, ctx->stream));
+        size_t slot = 0;
+        const uint32_t slices = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((c.longest + 63) / 64, 1), 1024);
+        if (timed && (rc = ctx->ld_timer[0].begin(ctx->stream, &slot))) return rc;
+        hipLaunchKernelGGL(ld_select_kernel, dim3((uint32_t)cnt, slices), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r,
+                           d_pbits, nP, params->min_mac, d_qmask);
+        HIP_TRY(hipGetLastError());
+        if (timed && (rc = ctx->ld_timer[0].end(ctx->stream, slot))) return rc;
+        if (timed && (rc = ctx->ld_timer[1].begin(ctx->stream, &slot))) return rc;
+        hipLaunchKernelGGL(ld_gather_kernel, dim3((uint32_t)cnt), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r, d_pbits,
+                           m->compact ? m->d_pos : nullptr, max_sites, d_qmask, d_rows, d_cs, d_coords, d_qm, ctx->d_err);
+        HIP_TRY(hipGetLastError());
+        if (timed && (rc = ctx->ld_timer[1].end(ctx->stream, slot))) return rc;
+        if (timed && (rc = ctx->ld_timer[2].begin(ctx->stream, &slot))) return rc;
+        if (rows_in_lds)
+            hipLaunchKernelGGL(ld_pairs_kernel<true>, dim3((uint32_t)cnt), dim3(LD_T), lds_pairs, ctx->stream, d_rows, d_cs, d_qm, d_wins, wps,
+                               max_sites, nP, d_rec);
+        else
+            hipLaunchKernelGGL(ld_pairs_kernel<false>, dim3((uint32_t)cnt), dim3(LD_T), lds_pairs, ctx->stream, d_rows, d_cs, d_qm, d_wins, wps,
+                               max_sites, nP, d_rec);
+        HIP_TRY(hipGetLastError());
+        if (timed && (rc = ctx->ld_timer[2].end(ctx->stream, slot))) return rc;
+        launches += 3;
+        HIP_TRY(hipMemcpyAsync(hc + o_rec, d_rec, cnt * sizeof(impop_ld_stats), hipMemcpyDeviceToHost, ctx->stream));
+        if (used_sites)
+            HIP_TRY(hipMemcpyAsync(used_sites + c.w_begin * max_sites, d_coords, cnt * max_sites * 8, hipMemcpyDeviceToHost, ctx->stream));
+        rc = ctx_err_fetch(ctx);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging is reused by the next chunk
+        rc = ctx_err_result(ctx, fn);
+        if (rc) return rc;
+        const impop_ld_stats *rv = (const impop_ld_stats *)(hc + o_rec);
+        for (size_t k = 0; k < cnt; ++k) {
+            out_host[c.w_begin + k] = rv[k];
+            qualifying += rv[k].n_qualifying;
+            used += rv[k].n_used;
+        }
+    }
+    if (trace_on()) {
+        fprintf(stderr, "[impop_ld_scan] route=%s windows=%llu chunks=%llu launches=%llu qualifying=%llu used=%llu bytes_streamed=%llu\n",
+                m->compact ? "compact" : "dense", (unsigned long long)n_windows, (unsigned long long)chunks.size(),
+                (unsigned long long)launches, (unsigned long long)qualifying, (unsigned long long)used,
+                (unsigned long long)(bytes_streamed + used * 4ull * wps));
+        fflush(stderr);
+    }
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_ctx_ld_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks) {
+    REQUIRE(ctx && kernel_ms, "impop_ctx_ld_elapsed: NULL argument");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < 3; ++k) {
+        const int rc = ctx->ld_timer[k].elapsed(&kernel_ms[k], k == 2 ? chunks : nullptr);
+        if (rc) return rc;
+    }
+    return IMPOP_OK;
+}

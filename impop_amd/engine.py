@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -40,6 +40,10 @@ EHH_FLANKS = {"reference": _lib.EHH_FLANKS_REFERENCE, "two-sided": _lib.EHH_FLAN
 HAPLOTYPE_DTYPE = np.dtype([("n_members", "<u4"), ("n_distinct", "<u4"), ("largest", "<u4"), ("second", "<u4"), ("n_singletons", "<u4"),
                             ("n_sites", "<u4"), ("sum_sq", "<u8"), ("h1", "<f8"), ("h12", "<f8"), ("h2_h1", "<f8"), ("hap_diversity", "<f8")])
 assert HAPLOTYPE_DTYPE.itemsize == 64
+LD_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_qualifying", "<u4"), ("n_used", "<u4"), ("n_perfect", "<u4"),
+                     ("n_complete", "<u4"), ("omega_split", "<u4"), ("reserved", "<u4"), ("sum_r2", "<f8"), ("sum_dprime", "<f8"),
+                     ("zns", "<f8"), ("mean_dprime", "<f8"), ("omega_max", "<f8")])
+assert LD_DTYPE.itemsize == 72
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), ("n_members", "<u4"), ("n_groups", "<u4"), ("s_p", "<u4"),
@@ -191,6 +195,12 @@ class Context:
         """-> ([fingerprint, grouping, verification] kernel ms of haplotype_scan, chunks) since gram_timing(True)"""
         t, k = (C.c_double * 3)(), C.c_uint64()
         check(self._lib.impop_ctx_haplotype_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def ld_elapsed(self):
+        """-> ([select, gather, pairs] kernel ms of ld_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 3)(), C.c_uint64()
+        check(self._lib.impop_ctx_ld_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def close(self) -> None:
@@ -623,6 +633,21 @@ class BitMatrix:
                                                  cl.ctypes.data_as(u32p) if want_members else None,
                                                  sz.ctypes.data_as(u32p) if want_members else None))
         return (out, cl, sz) if want_members else out
+
+    def ld_scan(self, windows, mask_p=None, min_mac: int = 1, max_sites: int = 512, want_sites: bool = False, max_chunk_bytes: int = 0):
+        """Linkage disequilibrium per window (impop_ld_scan): among the members of mask_p, the sites with minor-allele count >=
+        min_mac, thinned evenly to at most max_sites, all their pairs.  -> records (LD_DTYPE: ZnS, mean |D'|, the perfect and
+        complete pairs, Kim-Nielsen omega_max and its split), and with want_sites also used_sites [n_windows, max_sites] uint64:
+        the original coordinates of a window's used sites, first n_used valid, the rest 0."""
+        w = make_windows(windows)
+        out = np.zeros(len(w), dtype=LD_DTYPE)
+        prm = LdParams(C.sizeof(LdParams), int(min_mac), int(max_sites), 0, int(max_chunk_bytes))
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        sites = np.zeros((len(w), int(max_sites) if max_sites else 512), dtype=np.uint64) if want_sites else None
+        check(self.ctx._lib.impop_ld_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, C.byref(prm),
+                                          out.ctypes.data_as(C.POINTER(LdStats)),
+                                          sites.ctypes.data_as(C.POINTER(C.c_uint64)) if want_sites else None))
+        return (out, sites) if want_sites else out
 
     def ehh_scan(self, windows, cores, mask=None, ref_hap: int = 0, flanks: str = "reference", max_chunk_bytes: int = 0) -> np.ndarray:
         """Integrated EHH per core site (impop_ehh_scan; the area of scripts/wip/ehhgfa.py:63) for a batch of windows:

@@ -483,6 +483,55 @@ int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const impop_wind
 /* With impop_ctx_gram_timing on, impop_haplotype_scan brackets its kernels per chunk: kernel_ms[0] = fingerprints, [1] = grouping,
  * [2] = bitwise verification (and regrouping of flagged windows), summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_haplotype_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
+#define IMPOP_LD_MAX_N     4096u
+#define IMPOP_LD_MAX_SITES 1024u
+/* Linkage disequilibrium per window: Kelly's ZnS, mean |D'| and the Kim-Nielsen omega, from the site-major rows alone (no hap-major
+ * operand, no Gram; works on full, weighted and compacted matrices).  Site weights play no part, a site is a column; n_sites is the
+ * window's W as every other record reports it.
+ * Site selection, per window: a site qualifies iff min(c, |P| - c) >= min_mac, c = its carriers among P.  The qualifying sites
+ * are taken in ascending position and ranked 0..q-1; with m = min(q, max_sites) the site of rank floor(k q / m) (64-bit
+ * integers; the identity when q <= max_sites) is used, k = 0..m-1.  n_qualifying = q, n_used = m.  used_sites (nullable,
+ * n_windows x max_sites with max_sites as resolved, 0 -> 512) receives the ORIGINAL coordinates of the used sites: the first m
+ * entries of a window's row are valid, the rest 0.
+ * Pair arithmetic, used sites indexed 0..m-1 in position order, n = |P|, for sites s and t: c_s, c_t = carriers among P,
+ * n11 = popcount(row_s & row_t & P),
+ *     num = n n11 - c_s c_t (int64)             den = c_s (n - c_s) c_t (n - c_t) (int64)
+ *     r2 = (double)(num num) / (double)den      (both below 2^53 for n <= 4096: one IEEE division of exact values)
+ *     dmax = num > 0 ? min(c_s (n - c_t), (n - c_s) c_t) : min(c_s c_t, (n - c_s)(n - c_t))
+ *     |D'| = (double)|num| / (double)dmax, 0.0 when num = 0
+ * n_perfect counts the pairs with num num == den, n_complete those with num != 0 && |num| == dmax.  Either statistic is unchanged
+ * when a site's alleles are flipped: stored polarity is irrelevant.
+ * Sums, in this fixed order.  For site j: a_j = sum_{i<j} r2(i,j), i ascending from 0.0; b_j = sum_{k>j} r2(j,k), k ascending;
+ * dp_j = sum_{i<j} |D'|(i,j), i ascending.  L(l) = sum_{j<l} a_j, j ascending; R(l) = sum_{j>=l} b_j, accumulated from j = m-1
+ * downwards.  sum_r2 = L(m); sum_dprime = sum_j dp_j, j ascending; zns = sum_r2 / (m (m-1) / 2) and mean_dprime the same way,
+ * both 0.0 when m < 2.
+ * omega: for 2 <= l <= m-2, cross = (sum_r2 - L(l)) - R(l); a split with cross <= 0 is skipped, otherwise
+ *     omega(l) = ((L(l) + R(l)) / (double)(C(l,2) + C(m-l,2))) / (cross / (double)(l (m-l)))
+ * omega_max is the largest omega(l), omega_split its l (ties: the smallest l); both 0 when no split is defined.
+ * Every pair is evaluated twice (once by each of its sites), so that a record needs no atomics and does not depend on scheduling.
+ * |P| = 0, min_mac = 0, max_sites outside 4..IMPOP_LD_MAX_SITES (0 = 512) or a window outside the matrix return IMPOP_E_INVALID,
+ * |P| > IMPOP_LD_MAX_N IMPOP_E_UNSUPPORTED, all before anything is uploaded or launched; n_windows == 0 returns IMPOP_OK.
+ * Windows may overlap.  max_chunk_bytes (0 = 1 GiB) bounds the device memory of one chunk of windows; chunking, the upload's
+ * keep flags and compaction never change a record (dropped sites are monomorphic and never qualify).  Checks the device error
+ * word like impop_haplotype_scan (set when a window's gathered rows are not its n_used).
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_ld_scan] route=<dense|compact> windows= chunks= launches= qualifying= used= bytes_streamed= */
+typedef struct impop_ld_params {
+    uint32_t struct_size;
+    uint32_t min_mac;         /* >= 1 */
+    uint32_t max_sites;       /* 0 = 512; 4 .. IMPOP_LD_MAX_SITES */
+    uint32_t reserved;
+    uint64_t max_chunk_bytes; /* 0 = 1 GiB */
+} impop_ld_params;
+typedef struct impop_ld_stats { /* 72 bytes, fixed layout */
+    uint32_t n_members, n_sites, n_qualifying, n_used, n_perfect, n_complete, omega_split, reserved;
+    double sum_r2, sum_dprime, zns, mean_dprime, omega_max;
+} impop_ld_stats;
+int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,
+                  const impop_ld_params *params, impop_ld_stats *out_host, uint64_t *used_sites /* nullable, n_windows x max_sites */);
+/* With impop_ctx_gram_timing on, impop_ld_scan brackets its kernels per chunk: kernel_ms[0] = select, [1] = gather, [2] = pairs,
+ * summed since enable / reset; chunks = chunks timed. */
+int impop_ctx_ld_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
 /* Measurement aid (like impop_scan_plan_timing): with timing enabled every Gram launch of impop_pairwise_scan on this context
  * is bracketed with hipEvents on the context's stream; elapsed() synchronises and returns the summed Gram-kernel time and the
  * number of launches since enable / reset. */

@@ -13,6 +13,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format af [-t 1.0] [-u subset.txt] [--af-clusters c.tsv] [--af-details d.tsv]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ehh [--ehh-core-offset N | --ehh-cores pos.txt] [--ehh-flanks two-sided]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
 window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
@@ -50,6 +51,14 @@ HAPLOTYPES H1 H12 H2_H1 HAP_DIVERSITY (SAMPLES = sequences compared, SITES = the
 ones, H1 = haplotype homozygosity, H12 / H2_H1 after Garud et al., the doubles "%.8f").  Streams the scan index, needs no all-pairs
 operand; --compact allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
 
+--format ld (impop_ld_scan): linkage disequilibrium between the sites of every BED row among the sequences of -u (default: all).
+A site qualifies when its minor allele is carried by at least max(1, ceil(F * SAMPLES)) of them (--ld-min-maf F, default 0.05); more
+than --ld-max-sites M qualifying sites (default 512, 4..1024) are thinned evenly to M.  One table REGION LENGTH SAMPLES SITES
+QUALIFYING USED ZNS MEAN_DPRIME PERFECT COMPLETE OMEGA_MAX OMEGA_POS (ZNS = Kelly's mean r2 over the used pairs, PERFECT / COMPLETE =
+pairs with r2 = 1 / |D'| = 1, OMEGA_MAX = the Kim-Nielsen omega at its best split and OMEGA_POS the position of the first used site
+right of that split, NA when fewer than 4 sites are used; the doubles "%.8f").  Needs no all-pairs operand; --compact allowed.  One
+process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
+
 --panel A.txt B.txt ... (2..8 disjoint lists; run_tajd_panels.sh / run_h_fst_panels.sh).  --format hfst: one h-fst table per pair,
 headed `# A-vs-B`; --format tajd: one tajd table per panel, headed `# A`, SAMPLES = the list's line count, -t 0.999 -r 5 and S
 over all rows like run_tajd.sh; --format all: the pair tables, then the panel tables (h-fst rounds with --fst-round-digits).  The
@@ -62,6 +71,7 @@ BED rows are matched to matrices by chromosome (run_pica2_impg.sh:139-151 builds
 a row whose chromosome no matrix holds is skipped with a warning.
 """
 import argparse
+import math
 import os
 import sys
 
@@ -225,6 +235,10 @@ class Runner:
         """haplotype-frequency statistics per window (impop_haplotype_scan; HAPLOTYPE records).  One process, one GPU."""
         return self.bm.haplotype_scan(self.local_wins, mask_p=mask_p)
 
+    def ld(self, mask_p, min_mac, max_sites):
+        """linkage disequilibrium per window (impop_ld_scan) -> (LD records, used_sites).  One process, one GPU."""
+        return self.bm.ld_scan(self.local_wins, mask_p=mask_p, min_mac=min_mac, max_sites=max_sites, want_sites=True)
+
     def close(self):
         for sk, ck in zip(self.slabs, self.ctxs):
             sk.free(); ck.close()
@@ -359,6 +373,48 @@ def hap_refusal(args):
     if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
         return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
     return None
+
+
+LD_HEADER = "REGION\tLENGTH\tSAMPLES\tSITES\tQUALIFYING\tUSED\tZNS\tMEAN_DPRIME\tPERFECT\tCOMPLETE\tOMEGA_MAX\tOMEGA_POS"
+
+
+def ld_refusal(args):
+    """what --format ld does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "ld":
+        if args.ld_min_maf is not None or args.ld_max_sites is not None:
+            return "--ld-min-maf / --ld-max-sites belong to --format ld"
+        return None
+    if args.sim_list:
+        return "--format ld scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format ld is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format ld runs on one GPU: not with --devices N"
+    if args.panel or args.pop_a or args.pop_b or args.sample_list:
+        return "--format ld compares the sites among the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    if args.ld_min_maf is not None and not 0.0 <= args.ld_min_maf <= 0.5:
+        return "--ld-min-maf is a minor-allele frequency (0 .. 0.5)"
+    if args.ld_max_sites is not None and not 4 <= args.ld_max_sites <= 1024:
+        return "--ld-max-sites takes 4 .. 1024"
+    return None
+
+
+def ld_min_mac(min_maf, n_members):
+    """--ld-min-maf F among n_members sequences as the min_mac of impop_ld_scan"""
+    return max(1, int(math.ceil(min_maf * n_members)))
+
+
+def write_ld_table(out, regions, L_col, recs, omega_pos):
+    """the table of --format ld from impop_ld_stats records (one per region); omega_pos: the position of used site omega_split, or None"""
+    print(LD_HEADER, file=out)
+    for reg, L, r, pos in zip(regions, L_col, recs, omega_pos):
+        print(f"{reg}\t{L}\t{int(r['n_members'])}\t{int(r['n_sites'])}\t{int(r['n_qualifying'])}\t{int(r['n_used'])}\t{float(r['zns']):.8f}\t"
+              f"{float(r['mean_dprime']):.8f}\t{int(r['n_perfect'])}\t{int(r['n_complete'])}\t{float(r['omega_max']):.8f}\t"
+              f"{'NA' if pos is None else pos}", file=out)
 
 
 def write_hap_table(out, regions, L_col, recs):
@@ -551,10 +607,11 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
-                         "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`)")
+                         "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
+                         "ld = linkage disequilibrium per window (ZnS, mean |D'|, Kim-Nielsen omega; not part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
@@ -563,6 +620,10 @@ def main():
     ap.add_argument("--ehh-flanks", choices=["reference", "two-sided"], default=None, help="ehh: reference (default) = both halves from "
                     "the sites right of the core (ehhgfa.py:56-61); two-sided = the left half from the sites left of it")
     ap.add_argument("--ehh-ref", metavar="NAME", default=None, help="ehh: the sequence whose core allele is REF (default: the first)")
+    ap.add_argument("--ld-min-maf", type=float, default=None, metavar="F", help="ld: a site takes part when its minor allele is carried by "
+                    "at least max(1, ceil(F * SAMPLES)) sequences (default 0.05)")
+    ap.add_argument("--ld-max-sites", type=int, default=None, metavar="M", help="ld: more qualifying sites than M are thinned evenly to M "
+                    "(default 512; 4..1024)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
                     "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
@@ -596,7 +657,7 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args)
+    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args)
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
@@ -738,6 +799,8 @@ def main():
     af_clusters = [None] * n_rows
     ehh_lines = [None] * n_rows
     hap_recs = np.zeros(n_rows, dtype=impop_amd.HAPLOTYPE_DTYPE)
+    ld_recs = np.zeros(n_rows, dtype=impop_amd.LD_DTYPE)
+    ld_pos = [None] * n_rows
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -846,6 +909,19 @@ def main():
             hap_recs[idx] = run.hapstats(mask_p)
             run.close()
             continue
+        if fmt == "ld":
+            if mask_p is not None and not mask_p.any():
+                print("Error: --format ld: -u selects no sequence of the matrix", file=sys.stderr)
+                run.close()
+                sys.exit(2)
+            recs, used = run.ld(mask_p, ld_min_mac(0.05 if args.ld_min_maf is None else args.ld_min_maf, n_matched), args.ld_max_sites or 512)
+            ld_recs[idx] = recs
+            for i, r, u in zip(idx, recs, used):
+                if r["omega_split"]:
+                    c = int(u[int(r["omega_split"])])
+                    ld_pos[i] = int(mf.site_pos[c]) if mf.site_pos is not None else int(mf.origin + c)
+            run.close()
+            continue
         if fmt == "ehh":
             recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=mask_p, ref_hap=ref_hap, flanks=args.ehh_flanks or "reference")
             for i, c, r in zip(idx, cores, recs):
@@ -914,6 +990,8 @@ def main():
                 write_af_details(fh, regions, af_clusters, float(pica_t))
     elif fmt == "hapstats":
         write_hap_table(out, [r[0] for r in rows], L_col, hap_recs)
+    elif fmt == "ld":
+        write_ld_table(out, [r[0] for r in rows], L_col, ld_recs, ld_pos)
     elif fmt == "ehh":
         print(EHH_HEADER, file=out)
         for lines in ehh_lines:
