@@ -126,6 +126,21 @@ class LdStats(C.Structure):
                 ("omega_max", C.c_double)]
 
 
+class DiploidParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_run", C.c_uint32), ("max_chunk_bytes", C.c_uint64)]
+
+
+class DiploidStats(C.Structure):
+    _fields_ = [("n_ind", C.c_uint32), ("n_sites", C.c_uint32), ("s_p", C.c_uint32), ("het_sites", C.c_uint32),
+                ("het_total", C.c_uint64), ("sum_p", C.c_uint64), ("roh_sites_total", C.c_uint64), ("roh_runs_total", C.c_uint32),
+                ("longest_run", C.c_uint32), ("ho", C.c_double), ("he", C.c_double), ("f_is", C.c_double), ("f_roh", C.c_double)]
+
+
+class DiploidInd(C.Structure):
+    _fields_ = [("het", C.c_uint32), ("hom_alt", C.c_uint32), ("longest_run", C.c_uint32), ("roh_runs", C.c_uint32),
+                ("roh_sites", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -155,6 +170,8 @@ assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWi
 assert C.sizeof(HaplotypeStats) == 64 and C.sizeof(HaplotypeParams) == 16
 assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
 LD_MAX_N, LD_MAX_SITES = 4096, 1024
+assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(DiploidParams) == 16
+DIPLOID_MAX_N = 2048
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -236,6 +253,9 @@ SIGNATURES = {
     "impop_ctx_haplotype_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_ld_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(LdParams), C.POINTER(LdStats), _u64p]),
     "impop_ctx_ld_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_diploid_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u32p, C.c_uint32, C.POINTER(DiploidParams),
+                                     C.POINTER(DiploidStats), C.POINTER(DiploidInd)]),
+    "impop_ctx_diploid_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_fst_grouped_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, _u8p, _u8p, C.c_double, C.c_uint64, C.c_int, _u32p, _f64p,
                                                   _u64p]),
     "impop_tajimas_d": (C.c_int, [_vp, _i64p, _f64p, _f64p, C.c_uint64, _f64p, _f64p]),

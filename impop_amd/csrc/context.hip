@@ -219,6 +219,7 @@ IMPOP_API int impop_ctx_destroy(impop_ctx *ctx) {
     ctx->ehh_timer.destroy();
     for (impop::EventPairs &t : ctx->hap_timer) t.destroy();
     for (impop::EventPairs &t : ctx->ld_timer) t.destroy();
+    for (impop::EventPairs &t : ctx->dip_timer) t.destroy();
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     for (void *a : ctx->d_aux)
@@ -242,12 +243,13 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
     const uint32_t w = ctx->h_err;
     ctx->h_err = 0;
     HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s); the results of this call are invalid", fn, w,
+    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s); the results of this call are invalid", fn, w,
               (w & DEV_ERR_GROUPING) ? ": greedy grouping made no progress" : "",
               (w & DEV_ERR_CLUSTER) ? ": clustering ran out of rounds" : "",
               (w & DEV_ERR_EHH) ? ": EHH partition refinement is inconsistent" : "",
               (w & DEV_ERR_HAPSCAN) ? ": haplotype classes do not partition the members" : "",
-              (w & DEV_ERR_LDSCAN) ? ": LD scan gathered a different number of sites than it selected" : "");
+              (w & DEV_ERR_LDSCAN) ? ": LD scan gathered a different number of sites than it selected" : "",
+              (w & DEV_ERR_DIPLOID) ? ": diploid scan rows do not add up to their window" : "");
     return IMPOP_E_INTERNAL;
 }
 }  // namespace impop
@@ -272,6 +274,7 @@ IMPOP_API int impop_ctx_gram_timing(impop_ctx *ctx, int enable) {
     ctx->ehh_timer.reset();
     for (impop::EventPairs &t : ctx->hap_timer) t.reset();
     for (impop::EventPairs &t : ctx->ld_timer) t.reset();
+    for (impop::EventPairs &t : ctx->dip_timer) t.reset();
     return IMPOP_OK;
 }
 

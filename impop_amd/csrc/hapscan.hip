@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "hap_words.h"
 #include "internal.h"
 #include "sb64.h"
 #include "scan_route.h"
@@ -39,43 +40,6 @@ struct HapWin {  // a window of a chunk: its tiles (chunk-local) and its W
 struct HapItem {  // one workgroup of the verify kernel
     uint32_t win, tile;
 };
-
-// the blocks a tile's sites lie in, and the sites of block b inside the tile
-__device__ __forceinline__ void hap_tile_blocks(const ScanTile &t, uint64_t &b0, uint64_t &b1) {
-    b0 = t.site_begin >> 6;
-    b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
-}
-__device__ __forceinline__ uint64_t hap_edge(const ScanTile &t, uint64_t b) {
-    uint64_t edge = ~0ull;
-    if (b * 64 < t.site_begin) edge &= ~0ull << (t.site_begin - b * 64);
-    if (t.site_end - b * 64 < 64) edge &= (1ull << (t.site_end - b * 64)) - 1ull;
-    return edge;
-}
-
-// f(pp, word) for every member of P (pp = its position in P) with its 64-site word of block blk, sites outside `edge` cleared.
-// Dword columns without a member are skipped (pmask[k], wave-uniform).  Called by whole waves; lanes 0..31 run f.
-template <typename F>
-__device__ __forceinline__ void hap_block_words(const uint32_t *blk, uint32_t G, uint32_t r, uint32_t lane, uint64_t edge,
-                                                const int32_t *__restrict__ ppos, const uint32_t *__restrict__ pmask, F f) {
-    sb_for_each_dword<true>(blk, G, r, lane, [&](uint32_t k, uint32_t w) {
-        if (__builtin_amdgcn_readfirstlane(pmask[k]) == 0u) return;
-        const uint64_t word = ballot_transpose32(w, lane) & edge;
-        if (lane < 32) {
-            const int32_t pp = ppos[32 * k + lane];
-            if (pp >= 0) f((uint32_t)pp, word);
-        }
-    });
-}
-
-// P positions of the haplotypes a rare entry lists (-1: not in P, or an unused slot)
-__device__ __forceinline__ void hap_rare_members(uint64_t v, const int32_t *__restrict__ ppos, uint32_t n_pad, int32_t (&pp)[IMPOP_RARE_MAX]) {
-    const uint32_t m = rare_count(v);
-#pragma unroll
-    for (uint32_t i = 0; i < IMPOP_RARE_MAX; ++i) {
-        const uint32_t h = rare_slot(v, i);
-        pp[i] = (i < m && h < n_pad) ? ppos[h] : -1;
-    }
-}
 
 // grid = tiles of the chunk; dynamic LDS: 16 bytes x nP
 __global__ __launch_bounds__(HAP_T) void hap_fingerprint_kernel(const uint32_t *__restrict__ sb, const uint64_t *__restrict__ rare,

@@ -139,6 +139,7 @@ struct impop_ctx {
     impop::EventPairs gram_timer, cluster_timer, ehh_timer;
     impop::EventPairs hap_timer[3];  // impop_haplotype_scan: fingerprint / classify / verify + exact kernels (impop_ctx_haplotype_elapsed)
     impop::EventPairs ld_timer[3];   // impop_ld_scan: select / gather / pairs kernels (impop_ctx_ld_elapsed)
+    impop::EventPairs dip_timer[2];  // impop_diploid_scan: tile / window kernels (impop_ctx_diploid_elapsed)
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
     // all-pairs path run next to each other instead of one after the other
     hipStream_t side = nullptr;
@@ -184,9 +185,9 @@ struct impop_matrix {
     // lazily built bitmap of the sites that segregate among ALL haplotypes (bit s of dword s>>5), cached for the
     // all-pairs path's S (pairwise.hip); dropped with the matrix
     mutable uint32_t *d_segmap = nullptr;
-    // compacted matrix built from one that kept its hap-major copy: bitmap, in ORIGINAL site coordinates, of the
-    // dropped sites that EVERY haplotype carries (c_s = n): each adds 1 to every I_ij, so the all-pairs path on the
-    // variable sites alone plus this per-window count is exact (pairwise.hip)
+    // compacted matrix: bitmap, in ORIGINAL site coordinates, of the dropped sites that EVERY haplotype carries (c_s = n):
+    // each adds 1 to every I_ij, so the all-pairs path on the variable sites alone plus this per-window count is exact
+    // (pairwise.hip, which also needs d_rb: a source that kept its hap-major copy); likewise every individual's hom_alt (diploid.hip)
     uint32_t *d_onesmap = nullptr;
     uint64_t *d_pos = nullptr;  // compacted: device copy of `pos` (map_windows_device: window edges -> kept-site indices on the GPU)
     bool compact = false;
@@ -232,6 +233,7 @@ constexpr uint32_t DEV_ERR_GROUPING = 1u;            // greedy_groups_bits ran o
 constexpr uint32_t DEV_ERR_CLUSTER = 2u;             // af label propagation ran out of its rounds
 constexpr uint32_t DEV_ERR_HAPSCAN = 8u;             // haplotype scan: the classes of a window do not partition its members
 constexpr uint32_t DEV_ERR_LDSCAN = 16u;             // LD scan: the rows gathered for a window are not its n_used
+constexpr uint32_t DEV_ERR_DIPLOID = 32u;           // diploid scan: a window's rows do not add up to its het_total or its length
 constexpr uint32_t DEV_ERR_EHH = 4u;                 // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need

@@ -930,11 +930,12 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     uint32_t *d_cnt = L.at<uint32_t>(d, o_cnt);
     uint64_t n_kept = 0;
     // a source that kept its hap-major copy hands the all-pairs path on: the compacted matrix gets its own RB32
-    // operand and the bitmap of the dropped all-ones sites (their count — for a weighted source the sum of their
-    // weights, from host prefix sums built below — comes back as a per-window constant)
+    // operand; the bitmap of the dropped all-ones sites is built for every compacted matrix (their count — for a weighted
+    // source the sum of their weights, from host prefix sums built below — comes back as a per-window constant of the
+    // all-pairs path; impop_diploid_scan adds it to every individual's hom_alt)
     const bool want_pairs = in->d_rb != nullptr;
     uint64_t *d_ones = nullptr;
-    if (want_pairs && nb) HIP_TRY(hipMalloc((void **)&d_ones, nb * 8 + 256));
+    if (nb) HIP_TRY(hipMalloc((void **)&d_ones, nb * 8 + 256));
     if (nb) {
         const uint32_t wide_grid = (uint32_t)std::min<uint64_t>((nb + 3) / 4, 32ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
         hipLaunchKernelGGL(variable_mask_kernel, dim3(wide_grid), dim3(256), 0, ctx->stream, in->d_sb, g.wps, g.G, g.r, nb, g.n_site,

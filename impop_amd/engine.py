@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -44,6 +44,12 @@ LD_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_qualifying", 
                      ("n_complete", "<u4"), ("omega_split", "<u4"), ("reserved", "<u4"), ("sum_r2", "<f8"), ("sum_dprime", "<f8"),
                      ("zns", "<f8"), ("mean_dprime", "<f8"), ("omega_max", "<f8")])
 assert LD_DTYPE.itemsize == 72
+DIPLOID_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("s_p", "<u4"), ("het_sites", "<u4"), ("het_total", "<u8"), ("sum_p", "<u8"),
+                          ("roh_sites_total", "<u8"), ("roh_runs_total", "<u4"), ("longest_run", "<u4"), ("ho", "<f8"), ("he", "<f8"),
+                          ("f_is", "<f8"), ("f_roh", "<f8")])
+DIPLOID_IND_DTYPE = np.dtype([("het", "<u4"), ("hom_alt", "<u4"), ("longest_run", "<u4"), ("roh_runs", "<u4"), ("roh_sites", "<u4"),
+                              ("reserved", "<u4")])
+assert DIPLOID_DTYPE.itemsize == 80 and DIPLOID_IND_DTYPE.itemsize == 24
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), ("n_members", "<u4"), ("n_groups", "<u4"), ("s_p", "<u4"),
@@ -201,6 +207,12 @@ class Context:
         """-> ([select, gather, pairs] kernel ms of ld_scan, chunks) since gram_timing(True)"""
         t, k = (C.c_double * 3)(), C.c_uint64()
         check(self._lib.impop_ctx_ld_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def diploid_elapsed(self):
+        """-> ([tile, window] kernel ms of diploid_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 2)(), C.c_uint64()
+        check(self._lib.impop_ctx_diploid_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def close(self) -> None:
@@ -648,6 +660,28 @@ class BitMatrix:
                                           out.ctypes.data_as(C.POINTER(LdStats)),
                                           sites.ctypes.data_as(C.POINTER(C.c_uint64)) if want_sites else None))
         return (out, sites) if want_sites else out
+
+    def diploid_scan(self, windows, pairs, min_run: int, want_individuals: bool = False, max_chunk_bytes: int = 0):
+        """The individual level of a windowed scan (impop_diploid_scan): pairs = [N, 2] haplotype indices, the two copies of each
+        diploid individual.  -> records (DIPLOID_DTYPE: heterozygous sites, observed / expected heterozygosity, F_IS, runs of
+        homozygosity of at least min_run sites, F_ROH), and with want_individuals also the rows [n_windows, N]
+        (DIPLOID_IND_DTYPE: het, hom_alt, longest_run, roh_runs, roh_sites per individual)."""
+        w = make_windows(windows)
+        pr = np.asarray(pairs)
+        if pr.size and (pr.ndim != 2 or pr.shape[1] != 2):
+            raise ValueError("pairs must be [N, 2] haplotype indices")
+        if pr.size and (pr.min() < 0 or pr.max() > 0xFFFFFFFF):
+            raise ValueError("haplotype index outside 0 .. 2^32 - 1")
+        pr = np.ascontiguousarray(pr.reshape(-1, 2), dtype=np.uint32)
+        n_ind = len(pr)
+        out = np.zeros(len(w), dtype=DIPLOID_DTYPE)
+        prm = DiploidParams(C.sizeof(DiploidParams), int(min_run), int(max_chunk_bytes))
+        ind = np.zeros((len(w), n_ind), dtype=DIPLOID_IND_DTYPE) if want_individuals else None
+        check(self.ctx._lib.impop_diploid_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
+                                               pr.ctypes.data_as(C.POINTER(C.c_uint32)), n_ind, C.byref(prm),
+                                               out.ctypes.data_as(C.POINTER(DiploidStats)),
+                                               ind.ctypes.data_as(C.POINTER(DiploidInd)) if want_individuals else None))
+        return (out, ind) if want_individuals else out
 
     def ehh_scan(self, windows, cores, mask=None, ref_hap: int = 0, flanks: str = "reference", max_chunk_bytes: int = 0) -> np.ndarray:
         """Integrated EHH per core site (impop_ehh_scan; the area of scripts/wip/ehhgfa.py:63) for a batch of windows:

@@ -48,3 +48,29 @@ def read_subset_file(filename):
         sys.exit(1)
     with handle:
         return {ln.strip() for ln in handle if ln.strip() and ln[0] != "#"}
+
+
+def pair_haplotypes(names, subset=None):
+    """The diploid individuals among PanSN sequence names: `sample#1#...` and `sample#2#...` are the two copies of one person.
+    names: the sequences in matrix order (anything behind the first ':' is cut first, as af.py cuts it); subset: the names that take
+    part (default: all).  -> (pairs, sample_names, unpaired): pairs[i] = (index of sample i's haplotype 1, index of its haplotype 2),
+    samples in order of first appearance; unpaired = the taking-part names of samples that are not exactly one `#1#` and one `#2#`
+    sequence (a haploid assembly such as CHM13#0#chr1, half a person, a sample with more than two haplotypes, a name without a
+    haplotype field), in matrix order."""
+    chosen = None if subset is None else set(subset)
+    by_sample = {}
+    for idx, name in enumerate(names):
+        if chosen is not None and name not in chosen:
+            continue
+        fields = name.partition(":")[0].split("#")
+        sample = fields[0] if len(fields) >= 2 else name
+        by_sample.setdefault(sample, []).append((idx, fields[1] if len(fields) >= 2 else None))
+    pairs, sample_names, unpaired = [], [], []
+    for sample, members in by_sample.items():
+        if sorted(str(h) for _, h in members) == ["1", "2"]:
+            first, second = sorted(members, key=lambda m: m[1])
+            pairs.append((first[0], second[0]))
+            sample_names.append(sample)
+        else:
+            unpaired.extend(idx for idx, _ in members)
+    return pairs, sample_names, [names[i] for i in sorted(unpaired)]

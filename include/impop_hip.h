@@ -532,6 +532,69 @@ int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *win
 /* With impop_ctx_gram_timing on, impop_ld_scan brackets its kernels per chunk: kernel_ms[0] = select, [1] = gather, [2] = pairs,
  * summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_ld_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
+#define IMPOP_DIPLOID_MAX_N 2048u
+/* The individual level of a windowed scan: observed heterozygosity, Wright's F_IS and runs of homozygosity per window and per
+ * diploid individual, from the site-major rows alone (no hap-major operand, no Gram; works on full, weighted and compacted
+ * matrices).  pairs lists 2 n_ind haplotype indices, (h1, h2) per individual; P = the 2N haplotypes of the pairs.  Haplotypes in
+ * no pair play no part.  Site weights play no part either, a site is a column; n_sites is the window's W as every other record
+ * reports it (sum of weights, or the length).
+ * Per individual i of window [b, e): het = sites where bit(h1) != bit(h2), hom_alt = sites where both carry the allele.
+ * Runs: let i be heterozygous at sites p_1 < ... < p_k of the window, in ORIGINAL site coordinates.  Its runs are p_1 - b, then
+ * p_{j+1} - p_j - 1 for each j, then e - 1 - p_k; with k = 0 there is one run of length e - b.  Runs of length 0 are not runs.
+ * longest_run = the longest run, roh_runs = the runs of at least min_run sites, roh_sites = the sites inside those.  On a
+ * compacted matrix the coordinates are the kept sites' original positions, so the dropped monomorphic sites lie inside runs, as
+ * they should.
+ * Per window: s_p and sum_p are impop_window_stats' for P = the pairs (c_s = carriers among the 2N), het_sites = sites at which at
+ * least one individual is heterozygous, the other integers sum (longest_run: maximise) the individuals' rows.  The doubles are
+ * computed on the host from the integers, with L = seq_len if it is greater than 0, else W, and n = 2N, in exactly this order:
+ *     ho    = (double)het_total / ((double)N * L)
+ *     he    = 2.0 * (double)sum_p / ((double)n * (n - 1) * L)
+ *     f_is  = 1.0 - (double)(het_total * (n - 1)) / (double)sum_p          NaN when sum_p == 0
+ *     f_roh = (double)roh_sites_total / ((double)N * W)                    NaN when W == 0
+ * All device output is integers: a plain host restatement of the definitions agrees bit for bit.
+ * Known answer: haplotype rows over 6 sites h0 = 100010, h1 = 000010, h2 = 110000, h3 = 100001 (site 0 first), pairs (0,1) and
+ * (2,3), one window [0, 6), min_run = 3, seq_len = 0.  Individual 0: het 1, hom_alt 1, longest_run 5, roh_runs 1, roh_sites 5;
+ * individual 1: het 2, hom_alt 1, longest_run 3, roh_runs 1, roh_sites 3.  Window: s_p 4, het_sites 3, het_total 3, sum_p 13,
+ * roh_sites_total 8, roh_runs_total 2, longest_run 5, ho 0.25, he 26/72, f_is 1 - 9/13, f_roh 8/12.
+ * n_ind == 0, min_run == 0, a wrong struct_size, an index >= n_hap, h1 == h2, a haplotype in two pairs or a window outside the
+ * matrix return IMPOP_E_INVALID, n_ind > IMPOP_DIPLOID_MAX_N IMPOP_E_UNSUPPORTED, all before anything is uploaded or launched;
+ * n_windows == 0 returns IMPOP_OK.  Windows may overlap and may hold one site.  max_chunk_bytes (0 = 1 GiB) bounds the device
+ * memory of one chunk of windows; chunking, the upload's keep flags and compaction never change a record.  Checks the device
+ * error word like impop_haplotype_scan (set when a window's het_total is not the sum of its rows' het, or a row's run lengths
+ * and het do not add up to the window's length).
+ * ind_out (nullable): n_windows x n_ind rows, individual-minor, in the order of `pairs`.
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_diploid_scan] route=<dense|compact> windows= tiles= chunks= launches= individuals= bytes_streamed= */
+typedef struct impop_diploid_params {
+    uint32_t struct_size;
+    uint32_t min_run;          /* >= 1: a homozygous run counts as ROH when it is at least this many sites long */
+    uint64_t max_chunk_bytes;  /* 0 = 1 GiB */
+} impop_diploid_params;
+typedef struct impop_diploid_stats {   /* 80 bytes, fixed layout, one per window */
+    uint32_t n_ind, n_sites;           /* N, W */
+    uint32_t s_p;                      /* sites with 0 < c < 2N among the 2N haplotypes of the pairs */
+    uint32_t het_sites;                /* sites at which at least one individual is heterozygous */
+    uint64_t het_total;                /* sum over individuals of het_i */
+    uint64_t sum_p;                    /* sum_s c_s (2N - c_s): same quantity as impop_window_stats.sum_p for P = the pairs */
+    uint64_t roh_sites_total;          /* sum over individuals of roh_sites_i */
+    uint32_t roh_runs_total;           /* sum over individuals of roh_runs_i */
+    uint32_t longest_run;              /* max over individuals of longest_run_i */
+    double ho, he, f_is, f_roh;        /* host, from the integers, see above */
+} impop_diploid_stats;
+typedef struct impop_diploid_ind {     /* 24 bytes, optional table, n_windows x N, individual-minor */
+    uint32_t het;          /* sites where bit(h1) != bit(h2) */
+    uint32_t hom_alt;      /* sites where both carry the allele */
+    uint32_t longest_run;  /* longest stretch of window sites with no heterozygous site */
+    uint32_t roh_runs;     /* number of such stretches >= min_run */
+    uint32_t roh_sites;    /* sites inside them */
+    uint32_t reserved;     /* 0 */
+} impop_diploid_ind;
+int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                       const uint32_t *pairs /* 2N haplotype indices: h1,h2 per individual */, uint32_t n_ind,
+                       const impop_diploid_params *params, impop_diploid_stats *out, impop_diploid_ind *ind_out /* nullable */);
+/* With impop_ctx_gram_timing on, impop_diploid_scan brackets its kernels per chunk: kernel_ms[0] = tile summaries, [1] = window
+ * records, summed since enable / reset; chunks = chunks timed. */
+int impop_ctx_diploid_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks);
 /* Measurement aid (like impop_scan_plan_timing): with timing enabled every Gram launch of impop_pairwise_scan on this context
  * is bracketed with hipEvents on the context's stream; elapsed() synchronises and returns the summed Gram-kernel time and the
  * number of launches since enable / reset. */

@@ -14,6 +14,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ehh [--ehh-core-offset N | --ehh-cores pos.txt] [--ehh-flanks two-sided]
     impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format diploid [-u subset.txt] [--roh-min-sites N] [--ind-table PATH]   # Ho, He, F_IS, ROH
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
 window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
@@ -58,6 +59,14 @@ QUALIFYING USED ZNS MEAN_DPRIME PERFECT COMPLETE OMEGA_MAX OMEGA_POS (ZNS = Kell
 pairs with r2 = 1 / |D'| = 1, OMEGA_MAX = the Kim-Nielsen omega at its best split and OMEGA_POS the position of the first used site
 right of that split, NA when fewer than 4 sites are used; the doubles "%.8f").  Needs no all-pairs operand; --compact allowed.  One
 process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
+
+--format diploid (impop_diploid_scan): the individual level.  The sequences of -u (default: all) are paired by their PanSN fields,
+`sample#1#...` with `sample#2#...`; sequences of samples that are not exactly one of each are named in one warning and left out.
+One table CHROM START END N_IND SITES HET_SITES HO HE FIS ROH_RUNS F_ROH LONGEST_RUN (HO = heterozygous sites per individual and
+site, HE = 2 sum p q n / (n - 1) per site among the 2 N_IND copies, FIS = 1 - HO / HE, runs of homozygosity = stretches of at least
+--roh-min-sites N sites (default 50) without a heterozygous site, F_ROH = the share of sites inside them; NA where undefined);
+--ind-table PATH adds one row per window and sample: CHROM START END SAMPLE HET HOM_ALT LONGEST_RUN ROH_RUNS ROH_SITES.  --compact
+allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
 
 --panel A.txt B.txt ... (2..8 disjoint lists; run_tajd_panels.sh / run_h_fst_panels.sh).  --format hfst: one h-fst table per pair,
 headed `# A-vs-B`; --format tajd: one tajd table per panel, headed `# A`, SAMPLES = the list's line count, -t 0.999 -r 5 and S
@@ -239,6 +248,10 @@ class Runner:
         """linkage disequilibrium per window (impop_ld_scan) -> (LD records, used_sites).  One process, one GPU."""
         return self.bm.ld_scan(self.local_wins, mask_p=mask_p, min_mac=min_mac, max_sites=max_sites, want_sites=True)
 
+    def diploid(self, pairs, min_run, want_individuals):
+        """the individual level per window (impop_diploid_scan) -> DIPLOID records, or (records, rows).  One process, one GPU."""
+        return self.bm.diploid_scan(self.local_wins, pairs, min_run, want_individuals=want_individuals)
+
     def close(self):
         for sk, ck in zip(self.slabs, self.ctxs):
             sk.free(); ck.close()
@@ -401,6 +414,65 @@ def ld_refusal(args):
     if args.ld_max_sites is not None and not 4 <= args.ld_max_sites <= 1024:
         return "--ld-max-sites takes 4 .. 1024"
     return None
+
+
+DIPLOID_HEADER = "CHROM\tSTART\tEND\tN_IND\tSITES\tHET_SITES\tHO\tHE\tFIS\tROH_RUNS\tF_ROH\tLONGEST_RUN"
+DIPLOID_IND_HEADER = "CHROM\tSTART\tEND\tSAMPLE\tHET\tHOM_ALT\tLONGEST_RUN\tROH_RUNS\tROH_SITES"
+
+
+def diploid_refusal(args):
+    """what --format diploid does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "diploid":
+        if args.roh_min_sites is not None or args.ind_table is not None:
+            return "--roh-min-sites / --ind-table belong to --format diploid"
+        return None
+    if args.sim_list:
+        return "--format diploid scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format diploid is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format diploid runs on one GPU: not with --devices N"
+    if args.panel or args.pop_a or args.pop_b or args.sample_list:
+        return "--format diploid pairs the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    if args.roh_min_sites is not None and args.roh_min_sites < 1:
+        return "--roh-min-sites takes 1 or more"
+    return None
+
+
+def _na(x, digits=8):
+    x = float(x)
+    return "NA" if x != x else f"{x:.{digits}f}"
+
+
+def split_region(region):
+    """'CHM13#0#chr2:100-200' -> ('CHM13#0#chr2', '100', '200')"""
+    chrom, _, span = region.rpartition(":")
+    start, _, end = span.partition("-")
+    return chrom, start, end
+
+
+def write_diploid_table(out, regions, recs):
+    """the table of --format diploid from impop_diploid_stats records (one per region)"""
+    print(DIPLOID_HEADER, file=out)
+    for reg, r in zip(regions, recs):
+        chrom, start, end = split_region(reg)
+        print(f"{chrom}\t{start}\t{end}\t{int(r['n_ind'])}\t{int(r['n_sites'])}\t{int(r['het_sites'])}\t{_na(r['ho'])}\t{_na(r['he'])}\t"
+              f"{_na(r['f_is'])}\t{int(r['roh_runs_total'])}\t{_na(r['f_roh'])}\t{int(r['longest_run'])}", file=out)
+
+
+def write_diploid_ind_table(out, regions, samples, rows, header=True):
+    """--ind-table: one row per region and sample from impop_diploid_ind rows ([regions, samples])"""
+    if header:
+        print(DIPLOID_IND_HEADER, file=out)
+    for reg, per_sample in zip(regions, rows):
+        chrom, start, end = split_region(reg)
+        for name, q in zip(samples, per_sample):
+            print(f"{chrom}\t{start}\t{end}\t{name}\t{int(q['het'])}\t{int(q['hom_alt'])}\t{int(q['longest_run'])}\t{int(q['roh_runs'])}\t"
+                  f"{int(q['roh_sites'])}", file=out)
 
 
 def ld_min_mac(min_maf, n_members):
@@ -607,11 +679,12 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
-                         "ld = linkage disequilibrium per window (ZnS, mean |D'|, Kim-Nielsen omega; not part of `all`)")
+                         "ld = linkage disequilibrium per window (ZnS, mean |D'|, Kim-Nielsen omega; not part of `all`); "
+                         "diploid = heterozygosity, F_IS and runs of homozygosity per window and individual (not part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
@@ -624,6 +697,9 @@ def main():
                     "at least max(1, ceil(F * SAMPLES)) sequences (default 0.05)")
     ap.add_argument("--ld-max-sites", type=int, default=None, metavar="M", help="ld: more qualifying sites than M are thinned evenly to M "
                     "(default 512; 4..1024)")
+    ap.add_argument("--roh-min-sites", type=int, default=None, metavar="N", help="diploid: a stretch without a heterozygous site counts as a "
+                    "run of homozygosity when it is at least N sites long (default 50)")
+    ap.add_argument("--ind-table", metavar="PATH", help="diploid: also write one row per window and sample to PATH")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
                     "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
@@ -657,7 +733,7 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args)
+    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args)
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
@@ -801,6 +877,8 @@ def main():
     hap_recs = np.zeros(n_rows, dtype=impop_amd.HAPLOTYPE_DTYPE)
     ld_recs = np.zeros(n_rows, dtype=impop_amd.LD_DTYPE)
     ld_pos = [None] * n_rows
+    dip_recs = np.zeros(n_rows, dtype=impop_amd.DIPLOID_DTYPE)
+    dip_ind = [None] * n_rows  # per row: (sample names, impop_diploid_ind rows)
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -922,6 +1000,28 @@ def main():
                     ld_pos[i] = int(mf.site_pos[c]) if mf.site_pos is not None else int(mf.origin + c)
             run.close()
             continue
+        if fmt == "diploid":
+            from impop_amd.popnames import pair_haplotypes
+            chosen = None if mask_p is None else [nm for nm, f in zip(names, mask_p) if f]
+            dip_pairs, dip_samples, unpaired = pair_haplotypes(list(names), chosen)
+            if unpaired:
+                print(f"Warning: --format diploid: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
+                      + " ".join(unpaired), file=sys.stderr)
+            if len(dip_pairs) < 1:
+                print("Error: --format diploid: no sample with both of its haplotypes (sample#1#..., sample#2#...) among the sequences",
+                      file=sys.stderr)
+                run.close()
+                sys.exit(2)
+            min_run = 50 if args.roh_min_sites is None else args.roh_min_sites
+            if args.ind_table:
+                recs, ind_rows = run.diploid(dip_pairs, min_run, True)
+                for i, q in zip(idx, ind_rows):
+                    dip_ind[i] = (dip_samples, q)
+            else:
+                recs = run.diploid(dip_pairs, min_run, False)
+            dip_recs[idx] = recs
+            run.close()
+            continue
         if fmt == "ehh":
             recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=mask_p, ref_hap=ref_hap, flanks=args.ehh_flanks or "reference")
             for i, c, r in zip(idx, cores, recs):
@@ -992,6 +1092,13 @@ def main():
         write_hap_table(out, [r[0] for r in rows], L_col, hap_recs)
     elif fmt == "ld":
         write_ld_table(out, [r[0] for r in rows], L_col, ld_recs, ld_pos)
+    elif fmt == "diploid":
+        write_diploid_table(out, [r[0] for r in rows], dip_recs)
+        if args.ind_table:
+            with open(args.ind_table, "w") as fh:
+                print(DIPLOID_IND_HEADER, file=fh)
+                for (reg, _, _, _), entry in zip(rows, dip_ind):
+                    write_diploid_ind_table(fh, [reg], entry[0], [entry[1]], header=False)
     elif fmt == "ehh":
         print(EHH_HEADER, file=out)
         for lines in ehh_lines:
