@@ -140,6 +140,52 @@ __device__ __forceinline__ void rare_counts(uint64_t v, const uint32_t *lp, cons
     else { c = m; cP = mP; cA = mA; cB = mB; }
 }
 
+// The fixed-WPS kernel (n <= 512) decodes an entry through a table in LDS instead: hcode[h] holds, in three 5-bit fields, whether
+// haplotype h belongs to A, B and P, and entry RARE_CODE_NONE is 0, where the unused slots of an entry (0xFFFF) land.  The sum of
+// an entry's three table values is (mA, mB, mP), its listed haplotypes per population, in three bit-field reads, three LDS reads
+// and one add — no per-slot predicate, no 64-bit shifts.
+// Which allele the listed haplotypes carry does not matter here: with c = m or n - m alike, c (n - c) = m (n - m), the cross
+// term cA (nB - cB) + cB (nA - cA) = mA (nB - mB) + mB (nA - mA), and 0 < c < n iff 0 < m < n.  So the tile's sums follow from
+// the moments sum m, sum m^2 and sum mA mB, folded once per lane and tile (RareMoments::fold): exact integers, the same totals.
+constexpr uint32_t RARE_CODE_SIZE = 1024, RARE_CODE_NONE = RARE_CODE_SIZE - 1;  // > 512 haplotypes; 0xFFFF & 1023 = 1023
+struct RareMoments {
+    uint32_t a1 = 0, b1 = 0, p1 = 0, a2 = 0, b2 = 0, p2 = 0, ab = 0;
+    __device__ __forceinline__ void add(uint64_t e, const uint16_t *hcode, const PopSizes &ps, LaneAcc32 &acc) {
+        const uint32_t lo = (uint32_t)e, hi = (uint32_t)(e >> 32);
+        const uint32_t code = (uint32_t)hcode[(lo >> 16) & RARE_CODE_NONE] + (uint32_t)hcode[hi & RARE_CODE_NONE] +
+                              (uint32_t)hcode[(hi >> 16) & RARE_CODE_NONE];
+        const uint32_t m = rare_count(e), mA = code & 31u, mB = (code >> 5) & 31u, mP = (code >> 10) & 31u;
+        acc.s_all += (m - 1u) < (ps.n - 1u);
+        acc.s_p += (mP - 1u) < (ps.nP - 1u);
+        acc.s_a += (mA - 1u) < (ps.nA - 1u);
+        acc.s_b += (mB - 1u) < (ps.nB - 1u);
+        a1 += mA; b1 += mB; p1 += mP;
+        a2 += __umul24(mA, mA); b2 += __umul24(mB, mB); p2 += __umul24(mP, mP); ab += __umul24(mA, mB);
+    }
+    // sum m (n - m) = n sum m - sum m^2;  sum [mA (nB - mB) + mB (nA - mA)] = nB sum mA + nA sum mB - 2 sum mA mB
+    __device__ __forceinline__ void fold(const PopSizes &ps, LaneAcc32 &acc) const {
+        acc.q_p += ps.nP * p1 - p2;
+        acc.q_a += ps.nA * a1 - a2;
+        acc.q_b += ps.nB * b1 - b2;
+        acc.q_ab += ps.nB * a1 + ps.nA * b1 - 2u * ab;
+    }
+};
+__device__ __forceinline__ void rare_range_coded(const uint64_t *__restrict__ rare, uint64_t e0, uint64_t e1, const uint16_t *hcode,
+                                                 const PopSizes &ps, LaneAcc32 &acc) {
+    constexpr int RU = 4;
+    RareMoments mo;
+    uint64_t e = e0 + threadIdx.x;
+    for (; e + 256 * (RU - 1) < e1; e += 256 * RU) {
+        uint64_t v[RU];
+#pragma unroll
+        for (int u = 0; u < RU; ++u) v[u] = stream_load(rare + e + 256 * u);
+#pragma unroll
+        for (int u = 0; u < RU; ++u) mo.add(v[u], hcode, ps, acc);
+    }
+    for (; e < e1; e += 256) mo.add(stream_load(rare + e), hcode, ps, acc);
+    mo.fold(ps, acc);
+}
+
 // entries [e0, e1) of a tile, thread t takes e0 + t, e0 + t + 256, ...: RU coalesced 512-byte wave loads in flight per wave
 template <bool SUBSET_P, typename Acc>
 __device__ __forceinline__ void rare_range(const uint64_t *__restrict__ rare, uint64_t e0, uint64_t e1, const uint32_t *lp,
@@ -200,6 +246,19 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
                                                                                TilePartial *__restrict__ out) {
     const ScanTile t = tiles[blockIdx.x];
     const TileBlocks tb = tile_blocks_of(t);
+    // split index: this thread's share of the haplotype code table (RareMoments) — the mask words of haplotypes threadIdx.x and
+    // threadIdx.x + 256, read from the kernel arguments (MaskArgs is p | a | b) BEFORE the rows so that they arrive behind them
+    constexpr int CODE_PER_THREAD = (32 * WPS + 255) / 256;
+    const bool has_rare = t.rare_end > t.rare_begin;  // workgroup-uniform
+    uint32_t mw[CODE_PER_THREAD][3] = {};
+    if (has_rare) {
+        const uint32_t *mkw = reinterpret_cast<const uint32_t *>(&mk);
+#pragma unroll
+        for (int j = 0; j < CODE_PER_THREAD; ++j) {
+            const uint32_t h = threadIdx.x + 256u * j;
+            if (h < 32u * WPS) { mw[j][0] = mkw[h >> 5]; mw[j][1] = mkw[WPS + (h >> 5)]; mw[j][2] = mkw[2 * WPS + (h >> 5)]; }
+        }
+    }
     LaneAcc32 acc;
     uint64_t b = tb.b0 + tb.wave;
     constexpr int G = (WPS + 3) / 4;
@@ -233,14 +292,17 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         trim(w0, b);
         site_accumulate<WPS, SUBSET_P>(w0, mk, ps, acc);
     }
-    if (t.rare_end > t.rare_begin) {  // workgroup-uniform
-        __shared__ uint32_t rmk[3][WPS];
-        if (threadIdx.x == 0) {
+    if (has_rare) {
+        __shared__ uint16_t hcode[RARE_CODE_SIZE];
 #pragma unroll
-            for (int k = 0; k < WPS; ++k) { rmk[0][k] = mk.p[k]; rmk[1][k] = mk.a[k]; rmk[2][k] = mk.b[k]; }
+        for (int j = 0; j < CODE_PER_THREAD; ++j) {
+            const uint32_t h = threadIdx.x + 256u * j, bit = h & 31u;
+            if (h < 32u * WPS)
+                hcode[h] = (uint16_t)(((mw[j][1] >> bit) & 1u) | (((mw[j][2] >> bit) & 1u) << 5) | (((mw[j][0] >> bit) & 1u) << 10));
         }
+        if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
         __syncthreads();
-        rare_range<SUBSET_P>(rare, t.rare_begin, t.rare_end, rmk[0], rmk[1], rmk[2], ps, acc);
+        rare_range_coded(rare, t.rare_begin, t.rare_end, hcode, ps, acc);
     }
     LaneAcc wide;
     wide.s_all = acc.s_all; wide.s_p = acc.s_p; wide.s_a = acc.s_a; wide.s_b = acc.s_b;
