@@ -141,6 +141,16 @@ class DiploidInd(C.Structure):
                 ("roh_sites", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class DstatParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("polarize", C.c_int32), ("tile_blocks", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DstatStats(C.Structure):
+    _fields_ = [("n_sites", C.c_uint32), ("n_informative", C.c_uint32), ("n_skipped", C.c_uint32), ("flags", C.c_uint32),
+                ("abba", C.c_int64), ("baba", C.c_int64), ("f4_num", C.c_int64), ("fd_den_p2", C.c_int64), ("fd_den_p3", C.c_int64),
+                ("d", C.c_double), ("f4", C.c_double), ("fd", C.c_double)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -172,6 +182,8 @@ assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
 LD_MAX_N, LD_MAX_SITES = 4096, 1024
 assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(DiploidParams) == 16
 DIPLOID_MAX_N = 2048
+assert C.sizeof(DstatStats) == 80 and C.sizeof(DstatParams) == 16
+DSTAT_GROUP, DSTAT_MAX_QUARTETS = 3, 64
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -256,6 +268,9 @@ SIGNATURES = {
     "impop_diploid_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u32p, C.c_uint32, C.POINTER(DiploidParams),
                                      C.POINTER(DiploidStats), C.POINTER(DiploidInd)]),
     "impop_ctx_diploid_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_dstat_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, _u32p, C.c_uint32, C.POINTER(DstatParams),
+                                   C.POINTER(DstatStats)]),
+    "impop_ctx_dstat_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_fst_grouped_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, _u8p, _u8p, C.c_double, C.c_uint64, C.c_int, _u32p, _f64p,
                                                   _u64p]),
     "impop_tajimas_d": (C.c_int, [_vp, _i64p, _f64p, _f64p, C.c_uint64, _f64p, _f64p]),

@@ -220,6 +220,7 @@ IMPOP_API int impop_ctx_destroy(impop_ctx *ctx) {
     for (impop::EventPairs &t : ctx->hap_timer) t.destroy();
     for (impop::EventPairs &t : ctx->ld_timer) t.destroy();
     for (impop::EventPairs &t : ctx->dip_timer) t.destroy();
+    ctx->dstat_timer.destroy();
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     for (void *a : ctx->d_aux)
@@ -275,6 +276,7 @@ IMPOP_API int impop_ctx_gram_timing(impop_ctx *ctx, int enable) {
     for (impop::EventPairs &t : ctx->hap_timer) t.reset();
     for (impop::EventPairs &t : ctx->ld_timer) t.reset();
     for (impop::EventPairs &t : ctx->dip_timer) t.reset();
+    ctx->dstat_timer.reset();
     return IMPOP_OK;
 }
 

@@ -1,0 +1,420 @@
+// dstat.hip — impop_dstat_scan: Patterson's D (ABBA-BABA), f4 and Martin's f_d per window and quartet of populations
+// (include/impop_hip.h).  One streaming pass over what scan_route picks — the variable-site index with its rare entries, the
+// rows of a weighted matrix, the kept sites of a compacted one — modelled on scan_multi_kernel (scan.hip): masks of all K
+// populations in LDS, a lane per site, several granules in flight, per-tile integer partials, a finalize kernel that adds each
+// window's tile range.  Every term is zero where the site is monomorphic among all haplotypes, so the sites the index and a
+// compaction drop add nothing, with or without polarisation (an outgroup count of 0 or nO is never a tie).
+//
+// New is the per-site work: from the K counts of a site, per quartet five 64-bit sums and two counters.  The four populations of
+// a quartet are disjoint and n <= 65535, so every product of two counts / sizes of different populations is below 2^30: each
+// term is ONE 32 x 32 -> 64 multiply-add of two such products (v_mad_u64_u32 / v_mad_i64_i32), plus the weight multiply on
+// weighted matrices only.  The accumulators cost 12 VGPRs per quartet, so the quartet list is handled IMPOP_DSTAT_GROUP at a
+// time: the same tiles for every group, one streaming and one finalize launch per group (DESIGN.md has the register report the
+// group size was chosen from).  The doubles of a record are computed on the host from its integers, in one place.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "device_utils.h"
+#include "hap_words.h"
+#include "internal.h"
+#include "sb64.h"
+#include "scan_route.h"
+
+namespace impop {
+
+constexpr int DSTAT_QG = (int)IMPOP_DSTAT_GROUP;  // quartets per launch
+constexpr int DSTAT_NV = 7;                       // per quartet and tile: abba, baba, f4_num, fd_den_p2, fd_den_p3, n_informative, n_skipped
+
+struct DstatQuartet {  // P1, P2, P3, O
+    uint32_t p[4];     // indices into the K populations
+    uint32_t n[4];     // their sizes
+};
+struct DstatGroup {  // a kernel argument: wave-uniform (SGPR) state
+    DstatQuartet q[DSTAT_QG];
+};
+
+struct DstatAcc {
+    uint64_t abba = 0, baba = 0;
+    int64_t f4 = 0, fd2 = 0, fd3 = 0;
+    uint32_t inf = 0, skip = 0;
+};
+
+// c[i] for a wave-uniform i: a chain of K selects (a register array has no run-time index).  The chain starts from a constant,
+// not from c[0]: a select between two elements of c is folded into a load through a selected ADDRESS, which keeps c in scratch.
+template <int K>
+__device__ __forceinline__ uint32_t dstat_pick(const uint32_t (&c)[K], uint32_t i) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v = i == (uint32_t)k ? c[k] : v;
+    return v;
+}
+
+// One site of one quartet.  All products below are of counts / sizes of two different populations of the quartet: < 2^30.
+template <bool WEIGHTED>
+__device__ __forceinline__ void dstat_site(uint32_t c1, uint32_t c2, uint32_t c3, uint32_t cO, const DstatQuartet &q, bool polarize,
+                                           uint32_t wt, DstatAcc &a) {
+    const uint32_t n1 = q.n[0], n2 = q.n[1], n3 = q.n[2], nO = q.n[3];
+    if (polarize) {  // wave-uniform
+        const bool flip = 2u * cO > nO, tie = 2u * cO == nO;
+        c1 = flip ? n1 - c1 : c1;
+        c2 = flip ? n2 - c2 : c2;
+        c3 = flip ? n3 - c3 : c3;
+        cO = flip ? nO - cO : cO;
+        a.skip += tie;
+        if (tie) c1 = c2 = c3 = cO = 0;  // all-zero counts add nothing below
+    }
+    const uint32_t rO = nO - cO, b = c3 * rO;
+    const uint32_t ta = (n1 - c1) * c2, tb = c1 * (n2 - c2);
+    const int32_t x = (int32_t)(c1 * n2) - (int32_t)(c2 * n1), y = (int32_t)(c3 * nO) - (int32_t)(cO * n3);
+    const bool p2 = c2 * n3 >= c3 * n2;  // the donor of Martin's denominator: P2, else P3
+    const int32_t dx = p2 ? -x : (int32_t)(c3 * n1) - (int32_t)(c1 * n3), dy = (int32_t)(p2 ? c2 * rO : b);
+    a.inf += ((ta | tb) != 0u) & (b != 0u);
+    if (WEIGHTED) {
+        const uint64_t w = wt;
+        a.abba += w * ((uint64_t)ta * b);
+        a.baba += w * ((uint64_t)tb * b);
+        a.f4 += (int64_t)w * ((int64_t)x * y);
+        const int64_t fd = (int64_t)w * ((int64_t)dx * dy);
+        a.fd2 += p2 ? fd : 0;
+        a.fd3 += p2 ? 0 : fd;
+    } else {
+        a.abba += (uint64_t)ta * b;
+        a.baba += (uint64_t)tb * b;
+        a.f4 += (int64_t)x * y;
+        a.fd2 += (int64_t)(p2 ? dx : 0) * dy;
+        a.fd3 += (int64_t)(p2 ? 0 : dx) * dy;
+    }
+}
+
+// grid = tiles, block = 256.  Dynamic LDS: the K masks, wps4 dwords each.  grp: the group's nq <= DSTAT_QG quartets.
+// out: tile-major, DSTAT_QG x DSTAT_NV int64 per tile (the first nq are meaningful).
+template <int K, bool WEIGHTED>
+__global__ __launch_bounds__(256, 4) void dstat_tiles_kernel(const uint32_t *__restrict__ sb, const uint64_t *__restrict__ rare,
+                                                             const ScanTile *__restrict__ tiles,
+                                                             const uint32_t *__restrict__ masks /* K x wps */,
+                                                             const uint32_t *__restrict__ pop_n /* K */, uint32_t wps, uint32_t G,
+                                                             uint32_t r, const uint32_t *__restrict__ weights /* WEIGHTED */,
+                                                             DstatGroup grp, uint32_t nq, int polarize, int64_t *__restrict__ out) {
+    constexpr int MU = 4;  // granules in flight per wave
+    constexpr int NV = DSTAT_QG * DSTAT_NV;
+    extern __shared__ __attribute__((aligned(16))) uint32_t mk_lds[];  // K x wps4
+    __shared__ uint64_t red[4][NV];
+    const uint32_t wps4 = (wps + 3) & ~3u;
+    for (uint32_t i = threadIdx.x; i < K * wps4; i += 256) {
+        const uint32_t k = i / wps4, j = i % wps4;
+        mk_lds[i] = j < wps ? masks[(uint64_t)k * wps + j] : 0u;
+    }
+    __syncthreads();
+    const ScanTile t = tiles[blockIdx.x];
+    uint64_t tb0, tb1;
+    hap_tile_blocks(t, tb0, tb1);
+    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const bool pol = polarize != 0;
+    DstatAcc acc[DSTAT_QG];
+    const uint32_t Gf = sb_full_granules(G, r);
+    auto count_batch = [&](uint32_t g, uint32_t nb, const u32v4 (&v)[MU], uint32_t (&c)[K]) {
+#pragma unroll
+        for (int u = 0; u < MU; ++u)
+            if ((uint32_t)u < nb) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const u32v4 m4 = *reinterpret_cast<const u32v4 *>(mk_lds + k * wps4 + 4 * (g + u));
+                    c[k] += __popc(v[u].x & m4.x) + __popc(v[u].y & m4.y) + __popc(v[u].z & m4.z) + __popc(v[u].w & m4.w);
+                }
+            }
+    };
+    auto count_tail = [&](const uint32_t (&tl)[3], uint32_t (&c)[K]) {
+        sb_use_tail(G, r, tl, [&](uint32_t j, uint32_t v) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) c[k] += __popc(v & mk_lds[k * wps4 + j]);  // j: the dword's index in the site
+        });
+    };
+    auto tally_counts = [&](const uint32_t (&c)[K], uint32_t wt) {
+#pragma unroll
+        for (int j = 0; j < DSTAT_QG; ++j) {
+            if ((uint32_t)j >= nq) continue;  // wave-uniform: a short group
+            const DstatQuartet &q = grp.q[j];
+            dstat_site<WEIGHTED>(dstat_pick(c, q.p[0]), dstat_pick(c, q.p[1]), dstat_pick(c, q.p[2]), dstat_pick(c, q.p[3]), q, pol, wt,
+                                 acc[j]);
+        }
+    };
+    auto tally = [&](uint64_t b, const uint32_t (&c)[K]) {
+        const uint64_t s = b * 64 + lane;
+        if (s >= t.site_begin && s < t.site_end) tally_counts(c, WEIGHTED ? weights[s] : 1u);
+    };
+    uint64_t b = tb0 + wave;
+    if (Gf <= (uint32_t)MU) {
+        // <= 512 haplotypes: a block is one batch; two blocks (up to 8 wave loads) in flight per wave
+        for (; b + 4 < tb1; b += 8) {
+            const uint32_t *blk0 = sb + b * 64ull * wps, *blk1 = sb + (b + 4) * 64ull * wps;
+            u32v4 v0[MU], v1[MU];
+            uint32_t t0[3], t1[3];
+            sb_load_granules(blk0, 0, Gf, lane, v0);
+            sb_load_tail(blk0, G, r, lane, t0);
+            sb_load_granules(blk1, 0, Gf, lane, v1);
+            sb_load_tail(blk1, G, r, lane, t1);
+            uint32_t c0[K], c1[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) { c0[k] = 0; c1[k] = 0; }
+            count_batch(0, Gf, v0, c0);
+            count_tail(t0, c0);
+            tally(b, c0);
+            count_batch(0, Gf, v1, c1);
+            count_tail(t1, c1);
+            tally(b + 4, c1);
+        }
+    }
+    for (; b < tb1; b += 4) {
+        const uint32_t *blk = sb + b * 64ull * wps;
+        uint32_t c[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) c[k] = 0;
+        uint32_t tl[3];
+        sb_load_tail(blk, G, r, lane, tl);
+        for (uint32_t g = 0; g < Gf; g += MU) {
+            const uint32_t nb = Gf - g < (uint32_t)MU ? Gf - g : (uint32_t)MU;
+            u32v4 v[MU];
+            sb_load_granules(blk, g, nb, lane, v);
+            count_batch(g, nb, v, c);
+        }
+        count_tail(tl, c);
+        tally(b, c);
+    }
+    // rare entries of the split index (unweighted matrices only): each population's count from bit tests of the listed
+    // haplotypes, mirrored through n_k - m_k when they carry 0
+    if (!WEIGHTED) {
+        uint32_t nk[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) nk[k] = pop_n[k];
+        for (uint64_t e = t.rare_begin + threadIdx.x; e < t.rare_end; e += 256) {
+            const uint64_t v = stream_load(rare + e);
+            uint32_t c[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                const uint32_t mk = rare_listed_in(mk_lds + k * wps4, v);
+                c[k] = rare_lists_zeros(v) ? nk[k] - mk : mk;
+            }
+            tally_counts(c, 1u);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < DSTAT_QG; ++j) {
+        const uint64_t v[DSTAT_NV] = {wave_sum_u64(acc[j].abba), wave_sum_u64(acc[j].baba), wave_sum_u64((uint64_t)acc[j].f4),
+                                      wave_sum_u64((uint64_t)acc[j].fd2), wave_sum_u64((uint64_t)acc[j].fd3),
+                                      (uint64_t)wave_sum_u32(acc[j].inf), (uint64_t)wave_sum_u32(acc[j].skip)};
+        if (lane == 0) {
+#pragma unroll
+            for (int f = 0; f < DSTAT_NV; ++f) red[wave][j * DSTAT_NV + f] = v[f];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < NV)
+        out[(uint64_t)blockIdx.x * NV + threadIdx.x] =
+            (int64_t)(red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+}
+
+// one thread per (window, quartet of the group): the window's tile range added up, the record's integers written
+__global__ __launch_bounds__(128) void dstat_finalize_kernel(const int64_t *__restrict__ parts, const WinDesc *__restrict__ wins,
+                                                             uint64_t n_windows, uint32_t nq, uint32_t q0, uint32_t n_quartets,
+                                                             impop_dstat_stats *__restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_windows * nq) return;
+    const uint64_t win = i / nq;
+    const uint32_t j = (uint32_t)(i % nq);
+    const WinDesc w = wins[win];
+    int64_t s[DSTAT_NV] = {0, 0, 0, 0, 0, 0, 0};
+    for (uint64_t t = w.t0; t < w.t1; ++t) {
+        const int64_t *p = parts + (t * DSTAT_QG + j) * DSTAT_NV;
+#pragma unroll
+        for (int f = 0; f < DSTAT_NV; ++f) s[f] += p[f];
+    }
+    impop_dstat_stats o;
+    o.n_sites = (uint32_t)w.n_sites;
+    o.n_informative = (uint32_t)s[5];
+    o.n_skipped = (uint32_t)s[6];
+    o.flags = 0;
+    o.abba = s[0];
+    o.baba = s[1];
+    o.f4_num = s[2];
+    o.fd_den_p2 = s[3];
+    o.fd_den_p3 = s[4];
+    o.d = o.f4 = o.fd = 0.0;  // the host fills them in from the integers
+    out[win * n_quartets + q0 + j] = o;
+}
+
+// IMPOP_DSTAT_TILE_BLOCKS=n (1..4096) overrides the tile size, so that tests reach many-tile windows on small matrices
+static uint32_t dstat_tile_blocks(const impop_dstat_params *params) {
+    long v = params->tile_blocks;
+    const char *e = getenv("IMPOP_DSTAT_TILE_BLOCKS");
+    if (e && *e) v = strtol(e, nullptr, 10);
+    else if (!v) return 0;
+    return v < 1 ? 1u : v > 4096 ? 4096u : (uint32_t)v;
+}
+
+template <int K>
+static int dstat_launch(hipStream_t st, const impop_matrix *m, const ScanRoute &rt, const ScanTile *d_tiles, const uint32_t *d_masks,
+                        const uint32_t *d_n, const DstatGroup &grp, uint32_t nq, int polarize, int64_t *d_parts) {
+    const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
+    const dim3 grid((uint32_t)rt.tiles.size()), block(256);
+    if (m->d_wt && !rt.indexed) {
+        if (lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)dstat_tiles_kernel<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((dstat_tiles_kernel<K, true>), grid, block, lds, st, rt.sb, rt.rare, d_tiles, d_masks, d_n, m->g.wps, m->g.G,
+                           m->g.r, m->d_wt, grp, nq, polarize, d_parts);
+    } else {
+        if (lds > 48 * 1024)
+            HIP_TRY(hipFuncSetAttribute((const void *)dstat_tiles_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL((dstat_tiles_kernel<K, false>), grid, block, lds, st, rt.sb, rt.rare, d_tiles, d_masks, d_n, m->g.wps, m->g.G,
+                           m->g.r, (const uint32_t *)nullptr, grp, nq, polarize, d_parts);
+    }
+    HIP_TRY(hipGetLastError());
+    return IMPOP_OK;
+}
+
+}  // namespace impop
+
+using namespace impop;
+
+IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                               const uint64_t *masks, uint32_t n_pop, const uint32_t *quartets, uint32_t n_quartets,
+                               const impop_dstat_params *params, impop_dstat_stats *out_host) {
+    static_assert(sizeof(impop_dstat_stats) == 80 && sizeof(impop_dstat_params) == 16 && sizeof(DstatQuartet) == 32, "ABI layout");
+    const char *fn = "impop_dstat_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_dstat_params), "impop_dstat_params.struct_size mismatch");
+    REQUIRE(m->device == ctx->device, "%s: matrix lives on device %d, context on %d", fn, m->device, ctx->device);
+    REQUIRE(n_pop >= 4 && n_pop <= 8, "%s: n_pop must be 4..8 (got %u)", fn, n_pop);
+    REQUIRE(masks, "%s: masks is NULL", fn);
+    REQUIRE(n_quartets >= 1 && n_quartets <= IMPOP_DSTAT_MAX_QUARTETS && quartets, "%s: n_quartets must be 1..%u (got %u)", fn,
+            IMPOP_DSTAT_MAX_QUARTETS, n_quartets);
+    REQUIRE(m->g.n_hap <= 65535, "%s: n_hap > 65535 not supported", fn);
+    const uint32_t n = m->g.n_hap, wps = m->g.wps, K = n_pop, Q = n_quartets, mwords = (n + 63) / 64;
+    std::vector<uint32_t> mk((size_t)K * wps, 0u), nk(K, 0u);
+    for (uint32_t k = 0; k < K; ++k) {
+        const uint64_t *mw = masks + (size_t)k * mwords;
+        for (uint32_t h = 0; h < n; ++h)
+            if ((mw[h >> 6] >> (h & 63)) & 1ull) {
+                mk[(size_t)k * wps + (h >> 5)] |= 1u << (h & 31);
+                ++nk[k];
+            }
+        REQUIRE(nk[k] > 0, "%s: population %u is empty", fn, k);
+    }
+    std::vector<DstatQuartet> qs(Q);
+    for (uint32_t q = 0; q < Q; ++q) {
+        for (int a = 0; a < 4; ++a) {
+            const uint32_t p = quartets[4 * q + a];
+            REQUIRE(p < K, "%s: quartet %u: population index %u outside the %u populations", fn, q, p, K);
+            qs[q].p[a] = p;
+            qs[q].n[a] = nk[p];
+        }
+        for (int a = 0; a < 4; ++a)
+            for (int b = a + 1; b < 4; ++b)
+                for (uint32_t j = 0; j < wps; ++j)
+                    REQUIRE((mk[(size_t)qs[q].p[a] * wps + j] & mk[(size_t)qs[q].p[b] * wps + j]) == 0u,
+                            "%s: quartet %u: populations %u and %u share a haplotype (the four populations of a quartet must be disjoint)",
+                            fn, q, qs[q].p[a], qs[q].p[b]);
+    }
+    int rc = check_windows(fn, m, windows, windows ? n_windows : 0);
+    if (rc) return rc;
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_host, "%s: NULL windows/out", fn);
+    // no sum can wrap: every term is at most n1 nO max(n2, n3)^2 in magnitude, a window adds at most its weight sum of them
+    uint64_t w_max = 0, w_arg = 0;
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        const uint64_t W = window_W(m, windows[i].site_begin, windows[i].site_end);
+        if (W > w_max) { w_max = W; w_arg = i; }
+    }
+    for (uint32_t q = 0; q < Q; ++q) {
+        const uint64_t mx = std::max(qs[q].n[1], qs[q].n[2]);
+        const unsigned __int128 bound = (unsigned __int128)((uint64_t)qs[q].n[0] * qs[q].n[3]) * (mx * mx) * w_max;
+        if (bound >= ((unsigned __int128)1 << 62)) {
+            set_error("%s: quartet %u (population sizes %u, %u, %u, %u) over window %llu (weight sum %llu): n1 nO max(n2, n3)^2 W is not "
+                      "below 2^62, the sums could wrap; split the window",
+                      fn, q, qs[q].n[0], qs[q].n[1], qs[q].n[2], qs[q].n[3], (unsigned long long)w_arg, (unsigned long long)w_max);
+            return IMPOP_E_UNSUPPORTED;
+        }
+    }
+
+    HIP_TRY(hipSetDevice(ctx->device));
+    ScanRoute rt;
+    rc = scan_route(fn, ctx, m, windows, n_windows, dstat_tile_blocks(params), rt);
+    if (rc) return rc;
+    const size_t nt = rt.tiles.size();
+    Carve L;
+    const size_t o_tiles = L.take<ScanTile>(std::max<size_t>(nt, 1)), o_wins = L.take<WinDesc>(n_windows), o_masks = L.take<uint32_t>(mk.size()),
+                 o_n = L.take<uint32_t>(K), o_parts = L.take<int64_t>(std::max<size_t>(nt, 1) * DSTAT_QG * DSTAT_NV),
+                 o_out = L.take<impop_dstat_stats>(n_windows * Q);
+    void *d = nullptr;
+    rc = ctx_scratch(ctx, L.total(), &d);
+    if (rc) return rc;
+    char *base = (char *)d;
+    if (nt) HIP_TRY(hipMemcpyAsync(base + o_tiles, rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_masks, mk.data(), mk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(base + o_n, nk.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
+    const ScanTile *dt = (const ScanTile *)(base + o_tiles);
+    const uint32_t *dm = (const uint32_t *)(base + o_masks), *dn = (const uint32_t *)(base + o_n);
+    int64_t *dp = (int64_t *)(base + o_parts);
+    impop_dstat_stats *d_out = (impop_dstat_stats *)(base + o_out);
+    const int polarize = params->polarize != 0;
+    const bool timed = ctx->gram_timing;
+    uint64_t launches = 0;
+    // the quartet list in groups of DSTAT_QG: the same tiles, the partials reused (the launches of a stream run in order)
+    for (uint32_t q0 = 0; q0 < Q; q0 += DSTAT_QG) {
+        const uint32_t nq = std::min<uint32_t>(DSTAT_QG, Q - q0);
+        DstatGroup grp;
+        for (uint32_t j = 0; j < (uint32_t)DSTAT_QG; ++j) grp.q[j] = qs[q0 + (j < nq ? j : 0)];  // a short group repeats its first quartet
+        if (nt) {
+            size_t slot = 0;
+            if (timed && (rc = ctx->dstat_timer.begin(ctx->stream, &slot))) return rc;
+            switch (K) {
+                case 4: rc = dstat_launch<4>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
+                case 5: rc = dstat_launch<5>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
+                case 6: rc = dstat_launch<6>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
+                case 7: rc = dstat_launch<7>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
+                default: rc = dstat_launch<8>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
+            }
+            if (rc) return rc;
+            if (timed && (rc = ctx->dstat_timer.end(ctx->stream, slot))) return rc;
+            ++launches;
+        }
+        const uint64_t items = n_windows * nq;
+        hipLaunchKernelGGL(dstat_finalize_kernel, dim3((uint32_t)((items + 127) / 128)), dim3(128), 0, ctx->stream, dp,
+                           (const WinDesc *)(base + o_wins), n_windows, nq, q0, Q, d_out);
+        HIP_TRY(hipGetLastError());
+        ++launches;
+    }
+    HIP_TRY(hipMemcpyAsync(out_host, d_out, n_windows * Q * sizeof(impop_dstat_stats), hipMemcpyDeviceToHost, ctx->stream));
+    rc = ctx_err_fetch(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    rc = ctx_err_result(ctx, fn);
+    if (rc) return rc;
+    const double nan = __builtin_nan("");
+    for (uint64_t i = 0; i < n_windows; ++i)
+        for (uint32_t q = 0; q < Q; ++q) {
+            impop_dstat_stats &o = out_host[i * Q + q];
+            const uint64_t n1 = qs[q].n[0], n2 = qs[q].n[1], n3 = qs[q].n[2], nO = qs[q].n[3];
+            const int64_t num = o.abba - o.baba, den = o.abba + o.baba;
+            o.d = den == 0 ? nan : (double)num / (double)den;
+            o.f4 = (double)o.f4_num / (double)(n1 * n2 * n3 * nO);
+            const double fd_den = (double)o.fd_den_p2 / (double)(n1 * n2 * n2 * nO) + (double)o.fd_den_p3 / (double)(n1 * n3 * n3 * nO);
+            o.fd = fd_den == 0.0 ? nan : ((double)num / (double)(n1 * n2 * n3 * nO)) / fd_den;
+        }
+    if (trace_on()) {
+        fprintf(stderr, "[impop_dstat_scan] route=%s windows=%llu tiles=%llu quartets=%u launches=%llu bytes_streamed=%llu\n",
+                rt.split ? "indexed+rare" : rt.indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)n_windows,
+                (unsigned long long)nt, Q, (unsigned long long)launches, (unsigned long long)rt.bytes_streamed);
+        fflush(stderr);
+    }
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_ctx_dstat_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
+    REQUIRE(ctx, "impop_ctx_dstat_elapsed: ctx is NULL");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return ctx->dstat_timer.elapsed(total_ms, launches);
+}

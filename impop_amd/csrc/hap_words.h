@@ -1,5 +1,6 @@
-// hap_words.h — what the streaming kernels over scan_route's tiles share (hapscan.hip, diploid.hip): a tile's 64-site blocks with
-// its edges masked, the ballot transpose of a block into per-haplotype 64-site words, the members a rare entry lists.
+// hap_words.h — what the streaming kernels over scan_route's tiles share (scan.hip, hapscan.hip, diploid.hip, dstat.hip): a tile's
+// 64-site blocks with its edges masked, the ballot transpose of a block into per-haplotype 64-site words, the members a rare entry
+// lists and how many of them a population mask holds.
 #pragma once
 #include "device_utils.h"
 #include "internal.h"
@@ -33,6 +34,20 @@ __device__ __forceinline__ void hap_block_words(const uint32_t *blk, uint32_t G,
             if (pp >= 0) f((uint32_t)pp, word);
         }
     });
+}
+
+// A rare entry (internal.h, rare_pack) lists the m <= 3 carriers of its minor allele: how many of them belong to a population
+// comes from bit tests on its mask in LDS (per-lane addresses, a few dwords)
+__device__ __forceinline__ uint32_t rare_listed_in(const uint32_t *mask_lds, uint64_t e) {
+    const uint32_t m = rare_count(e);
+    uint32_t in = 0;
+#pragma unroll
+    for (uint32_t i = 0; i < IMPOP_RARE_MAX; ++i)
+        if (i < m) {
+            const uint32_t h = rare_slot(e, i);
+            in += (mask_lds[h >> 5] >> (h & 31u)) & 1u;
+        }
+    return in;
 }
 
 // P positions of the haplotypes a rare entry lists (-1: not in P, or an unused slot)

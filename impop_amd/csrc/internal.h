@@ -140,6 +140,7 @@ struct impop_ctx {
     impop::EventPairs hap_timer[3];  // impop_haplotype_scan: fingerprint / classify / verify + exact kernels (impop_ctx_haplotype_elapsed)
     impop::EventPairs ld_timer[3];   // impop_ld_scan: select / gather / pairs kernels (impop_ctx_ld_elapsed)
     impop::EventPairs dip_timer[2];  // impop_diploid_scan: tile / window kernels (impop_ctx_diploid_elapsed)
+    impop::EventPairs dstat_timer;   // impop_dstat_scan: the streaming launches (impop_ctx_dstat_elapsed)
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
     // all-pairs path run next to each other instead of one after the other
     hipStream_t side = nullptr;

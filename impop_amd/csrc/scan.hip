@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "device_utils.h"
+#include "hap_words.h"
 #include "internal.h"
 #include "sb64.h"
 #include "scan_route.h"
@@ -107,19 +108,7 @@ __device__ __forceinline__ void site_accumulate(const uint32_t (&w)[WPS], const 
     counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
 }
 
-// A rare entry (internal.h, rare_pack) lists the m <= 3 carriers of its minor allele: how many of them belong to a population
-// comes from bit tests on its mask in LDS (per-lane addresses, a few dwords)
-__device__ __forceinline__ uint32_t rare_listed_in(const uint32_t *mask_lds, uint64_t e) {
-    const uint32_t m = rare_count(e);
-    uint32_t in = 0;
-#pragma unroll
-    for (uint32_t i = 0; i < IMPOP_RARE_MAX; ++i)
-        if (i < m) {
-            const uint32_t h = rare_slot(e, i);
-            in += (mask_lds[h >> 5] >> (h & 31u)) & 1u;
-        }
-    return in;
-}
+// rare_listed_in (hap_words.h): how many of the haplotypes a rare entry lists belong to a population
 // ... and the counts of the 1-allele follow, mirrored through n - m, nP - mP, ... when the listed haplotypes carry 0 (then
 // every 0-carrier is listed).  Exact integers as for a row.  One loop over the slots tests all three masks (not three calls of
 // rare_listed_in): most sites of the headline workload arrive here, and three separate loops measured 4 % slower there.

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, DstatParams, DstatStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -50,6 +50,9 @@ DIPLOID_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("s_p", "<u4"), 
 DIPLOID_IND_DTYPE = np.dtype([("het", "<u4"), ("hom_alt", "<u4"), ("longest_run", "<u4"), ("roh_runs", "<u4"), ("roh_sites", "<u4"),
                               ("reserved", "<u4")])
 assert DIPLOID_DTYPE.itemsize == 80 and DIPLOID_IND_DTYPE.itemsize == 24
+DSTAT_DTYPE = np.dtype([("n_sites", "<u4"), ("n_informative", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4"), ("abba", "<i8"), ("baba", "<i8"),
+                        ("f4_num", "<i8"), ("fd_den_p2", "<i8"), ("fd_den_p3", "<i8"), ("d", "<f8"), ("f4", "<f8"), ("fd", "<f8")])
+assert DSTAT_DTYPE.itemsize == 80
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), ("n_members", "<u4"), ("n_groups", "<u4"), ("s_p", "<u4"),
@@ -214,6 +217,12 @@ class Context:
         t, k = (C.c_double * 2)(), C.c_uint64()
         check(self._lib.impop_ctx_diploid_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
+
+    def dstat_elapsed(self):
+        """-> (summed ms of dstat_scan's streaming launches, launches) since gram_timing(True)"""
+        t, k = C.c_double(), C.c_uint64()
+        check(self._lib.impop_ctx_dstat_elapsed(self.handle, C.byref(t), C.byref(k)))
+        return t.value, k.value
 
     def close(self) -> None:
         if self._h:
@@ -682,6 +691,27 @@ class BitMatrix:
                                                out.ctypes.data_as(C.POINTER(DiploidStats)),
                                                ind.ctypes.data_as(C.POINTER(DiploidInd)) if want_individuals else None))
         return (out, ind) if want_individuals else out
+
+    def dstat_scan(self, windows, pops, quartets, polarize: bool = False, tile_blocks: int = 0) -> np.ndarray:
+        """Patterson's D (ABBA-BABA), f4 and Martin's f_d per window and quartet (impop_dstat_scan): pops = 4..8 masks, quartets =
+        rows (P1, P2, P3, O) of indices into pops, the four populations of a row pairwise disjoint.  polarize: the outgroup's major
+        allele is ancestral, per site and quartet.  -> records [n_windows, n_quartets] (DSTAT_DTYPE: the exact integers abba, baba,
+        f4_num, fd_den_p2, fd_den_p3 and the doubles d, f4, fd formed from them)."""
+        w = make_windows(windows)
+        K = len(pops)
+        packed = np.concatenate([_mask_ptr(p, self.n_hap)[0] for p in pops]).astype(np.uint64) if K else np.zeros(1, np.uint64)
+        qa = np.asarray(quartets, dtype=np.int64)
+        if qa.size and (qa.ndim != 2 or qa.shape[1] != 4):
+            raise ValueError("quartets must be rows (P1, P2, P3, O) of population indices")
+        if qa.size and (qa.min() < 0 or qa.max() > 0xFFFFFFFF):
+            raise ValueError("population index outside 0 .. 2^32 - 1")
+        qa = np.ascontiguousarray(qa.reshape(-1, 4), dtype=np.uint32)
+        out = np.zeros((len(w), len(qa)), dtype=DSTAT_DTYPE)
+        prm = DstatParams(C.sizeof(DstatParams), 1 if polarize else 0, int(tile_blocks), 0)
+        check(self.ctx._lib.impop_dstat_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
+                                             packed.ctypes.data_as(C.POINTER(C.c_uint64)), K, qa.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                             len(qa), C.byref(prm), out.ctypes.data_as(C.POINTER(DstatStats))))
+        return out
 
     def ehh_scan(self, windows, cores, mask=None, ref_hap: int = 0, flanks: str = "reference", max_chunk_bytes: int = 0) -> np.ndarray:
         """Integrated EHH per core site (impop_ehh_scan; the area of scripts/wip/ehhgfa.py:63) for a batch of windows:

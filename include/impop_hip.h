@@ -595,6 +595,68 @@ int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window
 /* With impop_ctx_gram_timing on, impop_diploid_scan brackets its kernels per chunk: kernel_ms[0] = tile summaries, [1] = window
  * records, summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_diploid_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks);
+#define IMPOP_DSTAT_GROUP 3u   /* quartets whose sums one streaming launch of impop_dstat_scan keeps in registers */
+#define IMPOP_DSTAT_MAX_QUARTETS 64u
+/* Introgression statistics per window and quartet of populations (P1, P2, P3, O): Patterson's D (ABBA-BABA), f4 and Martin's f_d,
+ * from one streaming pass over the scan's own stream (the variable-site index with its rare entries where the matrix has one:
+ * every term is zero at a site that is monomorphic among all haplotypes, so that route is exact; weighted matrices stream the
+ * rows, compacted ones their kept sites).  masks holds n_pop (4..8) bitsets of ceil(n_hap / 64) words, quartets n_quartets
+ * (1..IMPOP_DSTAT_MAX_QUARTETS) x {P1, P2, P3, O} indices into masks.  The four populations of a quartet are pairwise disjoint;
+ * populations that never share a quartet may overlap.  A quartet may be listed twice.
+ * Per site s and quartet, c_k = carriers of allele 1 among population k (n_k members), w_s = the site's weight (1 without
+ * weights).  polarize = 1 takes the outgroup's major allele as ancestral, per site and quartet: 2 cO > nO turns every c_k into
+ * n_k - c_k, 2 cO == nO leaves the site out of that quartet's sums and counts it in n_skipped.  Then
+ *     abba      = sum_s w_s (n1 - c1) c2 c3 (nO - cO)            baba = sum_s w_s c1 (n2 - c2) c3 (nO - cO)
+ *     f4_num    = sum_s w_s (c1 n2 - c2 n1) (c3 nO - cO n3)
+ *     fd_den_p2 = sum over the sites with c2 n3 >= c3 n2 of w_s (c2 n1 - c1 n2) c2 (nO - cO)
+ *     fd_den_p3 = sum over the other sites              of w_s (c3 n1 - c1 n3) c3 (nO - cO)
+ * (fd_den_*: Martin's S(P1, P_D, P_D, O) with the donor P_D the one of P2 / P3 with the higher frequency, a tie to P2), and
+ * n_informative = the sites (columns, not weights) whose abba + baba term is positive.  Every integer is exact: neither the
+ * route, the tiling nor the order of summation enters a record.  The doubles are computed on the host from the integers, in
+ * exactly this order:
+ *     d  = (double)(abba - baba) / (double)(abba + baba)                                   NaN when abba + baba == 0
+ *     f4 = (double)f4_num / (double)(n1 n2 n3 nO)
+ *     fd = ((double)(abba - baba) / (double)(n1 n2 n3 nO)) /
+ *          ((double)fd_den_p2 / (double)(n1 n2 n2 nO) + (double)fd_den_p3 / (double)(n1 n3 n3 nO))    NaN when that sum is 0
+ * Known answer: eight haplotypes, P1 = {0,1}, P2 = {2,3}, P3 = {4,5}, O = {6,7}; six sites with the counts (c1, c2, c3, cO) =
+ * (0,2,2,0) (2,0,2,0) (1,2,1,0) (0,1,2,0) (1,1,0,0) (2,2,2,2), the carriers of a population its lowest-numbered haplotypes; one
+ * window [0, 6).  Quartet (P1,P2,P3,O): abba 28, baba 16, f4_num -12, fd_den_p2 24, fd_den_p3 16, n_informative 4, n_skipped 0,
+ * d = 12/44 = 3/11, f4 = -0.75, fd = 0.3.  Quartet (P2,P1,P3,O): abba 16, baba 28, f4_num 12, fd_den_p2 12, fd_den_p3 8,
+ * d = -3/11, fd = -0.6.  polarize = 1 gives the same records (the last site turns into all zeros, no outgroup count is a tie).
+ * n_pop outside 4..8, n_quartets outside 1..IMPOP_DSTAT_MAX_QUARTETS, a wrong struct_size, an empty population, a quartet index
+ * >= n_pop, a quartet whose populations are not pairwise disjoint, a window outside the matrix and n_hap > 65535 return
+ * IMPOP_E_INVALID; IMPOP_E_UNSUPPORTED when n1 nO max(n2, n3)^2 times the largest window's weight sum is not below 2^62 (the
+ * message names the quartet and the window: no sum can wrap); all before anything is uploaded or launched.  n_windows == 0
+ * returns IMPOP_OK.  Windows may overlap and may hold one site.
+ * The quartets are handled IMPOP_DSTAT_GROUP at a time: one streaming launch and one finalize launch per group, on the same
+ * tiles.  tile_blocks (0 = default; the environment's IMPOP_DSTAT_TILE_BLOCKS=1..4096 overrides it) bounds a tile's 64-site
+ * blocks.  Checks the device error word like impop_haplotype_scan.  out_host: n_windows x n_quartets records, window-major.
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_dstat_scan] route=<indexed+rare|indexed|dense|compact> windows= tiles= quartets= launches= bytes_streamed= */
+typedef struct impop_dstat_params {
+    uint32_t struct_size;
+    int32_t  polarize;     /* 0: allele 1 is the derived allele as stored; 1: the outgroup's major allele is ancestral */
+    uint32_t tile_blocks;  /* 0 = default */
+    uint32_t reserved;
+} impop_dstat_params;
+typedef struct impop_dstat_stats {   /* 80 bytes, fixed layout */
+    uint32_t n_sites;        /* as impop_window_stats.n_sites */
+    uint32_t n_informative;  /* sites (not weights) with abba + baba term > 0 */
+    uint32_t n_skipped;      /* polarize ties */
+    uint32_t flags;          /* 0 */
+    int64_t  abba;           /* sum_s w_s (n1-c1) c2 c3 (nO-cO) */
+    int64_t  baba;           /* sum_s w_s c1 (n2-c2) c3 (nO-cO) */
+    int64_t  f4_num;         /* sum_s w_s (c1 n2 - c2 n1)(c3 nO - cO n3) */
+    int64_t  fd_den_p2;      /* sites with c2 n3 >= c3 n2: sum w_s (c2 n1 - c1 n2) c2 (nO-cO) */
+    int64_t  fd_den_p3;      /* the other sites:           sum w_s (c3 n1 - c1 n3) c3 (nO-cO) */
+    double   d, f4, fd;      /* host, from the integers, see above */
+} impop_dstat_stats;
+int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                     const uint64_t *masks, uint32_t n_pop, const uint32_t *quartets /* n_quartets x {P1,P2,P3,O} */,
+                     uint32_t n_quartets, const impop_dstat_params *params, impop_dstat_stats *out_host /* [window][quartet] */);
+/* With impop_ctx_gram_timing on, impop_dstat_scan brackets its streaming launches: their summed time and number since enable /
+ * reset. */
+int impop_ctx_dstat_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
 /* Measurement aid (like impop_scan_plan_timing): with timing enabled every Gram launch of impop_pairwise_scan on this context
  * is bracketed with hipEvents on the context's stream; elapsed() synchronises and returns the summed Gram-kernel time and the
  * number of launches since enable / reset. */

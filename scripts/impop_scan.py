@@ -15,6 +15,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
     impop_scan.py --matrix chr2.npz --bed windows.bed --format diploid [-u subset.txt] [--roh-min-sites N] [--ind-table PATH]   # Ho, He, F_IS, ROH
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format dstat --panel P1.txt P2.txt P3.txt O.txt [more.txt] [--quartet 1,2,3,4]...   # ABBA-BABA D, f4, f_d
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
 window (a relative sim_path is taken from the list's directory).  Formats pica2, hfst, tajd, all; the tables of a chunk share
@@ -67,6 +68,16 @@ site, HE = 2 sum p q n / (n - 1) per site among the 2 N_IND copies, FIS = 1 - HO
 --roh-min-sites N sites (default 50) without a heterozygous site, F_ROH = the share of sites inside them; NA where undefined);
 --ind-table PATH adds one row per window and sample: CHROM START END SAMPLE HET HOM_ALT LONGEST_RUN ROH_RUNS ROH_SITES.  --compact
 allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
+
+--format dstat (impop_dstat_scan): introgression statistics per BED row and quartet (P1, P2, P3, O) of the --panel lists (4..8 of
+them).  --quartet i,j,k,o names a quartet by 1-based positions in --panel and may be repeated; with exactly four lists the default is
+1,2,3,4.  The four populations of a quartet must not share a sequence.  One table CHROM START END P1 P2 P3 O N_SITES N_INFORMATIVE
+N_SKIPPED ABBA BABA D F4 F_D, one row per window and quartet (P1..O = the lists' base names; ABBA / BABA = the summed site patterns in
+frequencies; D = (ABBA - BABA) / (ABBA + BABA); F4 = mean (p1 - p2)(p3 - pO) summed over sites; F_D after Martin et al. 2015; the
+doubles "%.8f", nan where undefined).  --dstat-polarize takes the outgroup's major allele as ancestral per site (N_SKIPPED = sites where
+the outgroup is split evenly).  --dstat-blocks N with --dstat-summary PATH writes per quartet the value over all rows with its
+block-jackknife error: P1 P2 P3 O D D_SE D_Z F_D F_D_SE BLOCKS ABBA BABA.  Streams the scan index; --compact allowed.  One process, one
+GPU; not with --sim-list, -A / -B / -l / -u, --devices N, -t / -r.
 
 --panel A.txt B.txt ... (2..8 disjoint lists; run_tajd_panels.sh / run_h_fst_panels.sh).  --format hfst: one h-fst table per pair,
 headed `# A-vs-B`; --format tajd: one tajd table per panel, headed `# A`, SAMPLES = the list's line count, -t 0.999 -r 5 and S
@@ -251,6 +262,10 @@ class Runner:
     def diploid(self, pairs, min_run, want_individuals):
         """the individual level per window (impop_diploid_scan) -> DIPLOID records, or (records, rows).  One process, one GPU."""
         return self.bm.diploid_scan(self.local_wins, pairs, min_run, want_individuals=want_individuals)
+
+    def dstat(self, pops, quartets, polarize):
+        """ABBA-BABA D, f4 and f_d per window and quartet (impop_dstat_scan; DSTAT records [windows, quartets]).  One process, one GPU."""
+        return self.bm.dstat_scan(self.local_wins, pops, quartets, polarize=polarize)
 
     def close(self):
         for sk, ck in zip(self.slabs, self.ctxs):
@@ -441,6 +456,107 @@ def diploid_refusal(args):
     if args.roh_min_sites is not None and args.roh_min_sites < 1:
         return "--roh-min-sites takes 1 or more"
     return None
+
+
+DSTAT_HEADER = "CHROM\tSTART\tEND\tP1\tP2\tP3\tO\tN_SITES\tN_INFORMATIVE\tN_SKIPPED\tABBA\tBABA\tD\tF4\tF_D"
+DSTAT_SUMMARY_HEADER = "P1\tP2\tP3\tO\tD\tD_SE\tD_Z\tF_D\tF_D_SE\tBLOCKS\tABBA\tBABA"
+
+
+def parse_quartets(specs, n_panel):
+    """--quartet i,j,k,o (1-based positions in --panel, repeatable) -> [(P1, P2, P3, O)] 0-based; none given: 1,2,3,4 when the
+    panel has exactly four lists.  ValueError with the message otherwise."""
+    if not specs:
+        if n_panel != 4:
+            raise ValueError(f"--panel holds {n_panel} lists: say which four make a quartet with --quartet i,j,k,o (repeatable)")
+        return [(0, 1, 2, 3)]
+    out = []
+    for spec in specs:
+        parts = spec.split(",")
+        if len(parts) != 4 or not all(x.strip().isdigit() for x in parts):
+            raise ValueError(f"--quartet {spec}: four 1-based positions in --panel, as in 1,2,3,4")
+        q = tuple(int(x) - 1 for x in parts)
+        for k in q:
+            if not 0 <= k < n_panel:
+                raise ValueError(f"--quartet {spec}: position {k + 1} is outside the {n_panel} lists of --panel")
+        if len(set(q)) != 4:
+            raise ValueError(f"--quartet {spec}: a population is named twice")
+        out.append(q)
+    if len(out) > 64:
+        raise ValueError("--quartet: at most 64 quartets per run")
+    return out
+
+
+def dstat_refusal(args):
+    """what --format dstat does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "dstat":
+        if args.quartet or args.dstat_polarize or args.dstat_blocks is not None or args.dstat_summary is not None:
+            return "--quartet / --dstat-polarize / --dstat-blocks / --dstat-summary belong to --format dstat"
+        return None
+    if args.sim_list:
+        return "--format dstat scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format dstat is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format dstat runs on one GPU: not with --devices N"
+    if not args.panel or not 4 <= len(args.panel) <= 8:
+        return "--format dstat takes --panel P1.txt P2.txt P3.txt O.txt [more lists]: 4 to 8 population lists"
+    if args.pop_a or args.pop_b or args.sample_list or args.subset:
+        return "--format dstat compares the populations of --panel: not with -A / -B / -l / -u"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    if (args.dstat_blocks is None) != (args.dstat_summary is None):
+        return "--dstat-blocks N and --dstat-summary PATH go together"
+    if args.dstat_blocks is not None and args.dstat_blocks < 1:
+        return "--dstat-blocks takes 1 or more"
+    try:
+        parse_quartets(args.quartet, len(args.panel))
+    except ValueError as e:
+        return str(e)
+    return None
+
+
+def dstat_row(region, labels, quartet, sizes, r):
+    """one row of the --format dstat table: region, the quartet's list names, the record; ABBA / BABA as frequencies"""
+    chrom, start, end = split_region(region)
+    n1, n2, n3, nO = (int(sizes[k]) for k in quartet)
+    norm = float(n1 * n2 * n3 * nO)
+    return (f"{chrom}\t{start}\t{end}\t" + "\t".join(labels[k] for k in quartet) + f"\t{int(r['n_sites'])}\t{int(r['n_informative'])}\t"
+            f"{int(r['n_skipped'])}\t{float(int(r['abba'])) / norm:.8f}\t{float(int(r['baba'])) / norm:.8f}\t{float(r['d']):.8f}\t"
+            f"{float(r['f4']):.8f}\t{float(r['fd']):.8f}")
+
+
+def write_dstat_table(out, regions, labels, quartets, sizes_rows, recs):
+    """the table of --format dstat: one row per region and quartet from impop_dstat_stats records [regions, quartets];
+    sizes_rows[i] = the populations' sizes in the matrix of region i"""
+    print(DSTAT_HEADER, file=out)
+    for reg, sizes, per_q in zip(regions, sizes_rows, recs):
+        for q, r in zip(quartets, per_q):
+            print(dstat_row(reg, labels, q, sizes, r), file=out)
+
+
+def write_dstat_summary(out, labels, quartets, sizes_rows, recs, n_blocks):
+    """--dstat-summary: per quartet the genome-wide D and f_d over all regions with their block-jackknife errors
+    (impop_amd.dstat.block_jackknife over n_blocks consecutive groups of regions)"""
+    from impop_amd.dstat import block_jackknife
+    print(DSTAT_SUMMARY_HEADER, file=out)
+    for qi, q in enumerate(quartets):
+        norms = [[int(sz[k]) for k in q] for sz in sizes_rows]
+        abba = np.array([int(x) for x in recs["abba"][:, qi]], dtype=object)
+        baba = np.array([int(x) for x in recs["baba"][:, qi]], dtype=object)
+        prod = np.array([float(a * b * c * d) for a, b, c, d in norms])
+        if len({tuple(x) for x in norms}) > 1:  # matrices with different population sizes: frequencies, not counts
+            abba, baba = abba.astype(np.float64) / prod, baba.astype(np.float64) / prod
+        d, d_se, d_z, B = block_jackknife(abba - baba, abba + baba, n_blocks)
+        fd_num = (recs["abba"][:, qi] - recs["baba"][:, qi]).astype(np.float64) / prod
+        fd_den = recs["fd_den_p2"][:, qi].astype(np.float64) / np.array([float(a * b * b * d) for a, b, c, d in norms]) \
+            + recs["fd_den_p3"][:, qi].astype(np.float64) / np.array([float(a * c * c * d) for a, b, c, d in norms])
+        fd, fd_se, _, _ = block_jackknife(fd_num, fd_den, n_blocks)
+        s_abba = float(np.sum(recs["abba"][:, qi].astype(np.float64) / prod)) if len(prod) else 0.0
+        s_baba = float(np.sum(recs["baba"][:, qi].astype(np.float64) / prod)) if len(prod) else 0.0
+        print("\t".join(labels[k] for k in q) + f"\t{float(d):.8f}\t{float(d_se):.8f}\t{float(d_z):.8f}\t{float(fd):.8f}\t{float(fd_se):.8f}\t{B}\t"
+              f"{s_abba:.8f}\t{s_baba:.8f}", file=out)
 
 
 def _na(x, digits=8):
@@ -679,12 +795,13 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "dstat", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
                          "ld = linkage disequilibrium per window (ZnS, mean |D'|, Kim-Nielsen omega; not part of `all`); "
-                         "diploid = heterozygosity, F_IS and runs of homozygosity per window and individual (not part of `all`)")
+                         "diploid = heterozygosity, F_IS and runs of homozygosity per window and individual (not part of `all`); "
+                         "dstat = Patterson's D (ABBA-BABA), f4 and f_d per window and quartet of --panel populations (not part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
@@ -700,6 +817,14 @@ def main():
     ap.add_argument("--roh-min-sites", type=int, default=None, metavar="N", help="diploid: a stretch without a heterozygous site counts as a "
                     "run of homozygosity when it is at least N sites long (default 50)")
     ap.add_argument("--ind-table", metavar="PATH", help="diploid: also write one row per window and sample to PATH")
+    ap.add_argument("--quartet", action="append", default=None, metavar="i,j,k,o", help="dstat: the populations P1,P2,P3,O of a quartet as "
+                    "1-based positions in --panel; repeatable (default with exactly four lists: 1,2,3,4)")
+    ap.add_argument("--dstat-polarize", action="store_true", help="dstat: per site and quartet the outgroup's major allele is ancestral "
+                    "(a site where the outgroup is split evenly is skipped)")
+    ap.add_argument("--dstat-blocks", type=int, default=None, metavar="N", help="dstat: with --dstat-summary, the number of consecutive "
+                    "groups of BED rows of the block jackknife")
+    ap.add_argument("--dstat-summary", metavar="PATH", help="dstat: one row per quartet to PATH: D, its jackknife SE and Z, f_d and its "
+                    "SE, the block count, the summed ABBA / BABA")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
                     "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
@@ -733,7 +858,7 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args)
+    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or dstat_refusal(args)
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
@@ -806,8 +931,8 @@ def main():
     want_pica = fmt in ("pica2", "tajd", "all", "fst3pi")
     want_fst = fmt in ("hfst", "all") and not args.panel
     need_pairs = (want_pica and pica_pairs) or (want_fst and fst_pairs) or fmt == "af"
-    if args.panel and fmt not in ("hfst", "tajd", "all"):
-        print("Error: --panel belongs to --format hfst (every pair), tajd (every panel) or all (both)", file=sys.stderr)
+    if args.panel and fmt not in ("hfst", "tajd", "all", "dstat"):
+        print("Error: --panel belongs to --format hfst (every pair), tajd (every panel), all (both) or dstat (quartets)", file=sys.stderr)
         sys.exit(2)
     # --panel: the pair tables come from the streaming K-population scan (impop_scan_multi) when h-fst is unrounded on `match`,
     # else - like every per-panel tajd table - from impop_pairwise_scan_panel: one Gram pass per window for all panels and pairs
@@ -815,6 +940,7 @@ def main():
     panel_tajd = bool(args.panel) and fmt in ("tajd", "all")
     if args.panel:
         need_pairs = panel_tajd or (panel_fst and fst_pairs)
+    dstat_quartets = parse_quartets(args.quartet, len(args.panel)) if fmt == "dstat" else None
 
     thr_txt = threshold_text if threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
     r_txt = "" if pica_r is None else str(pica_r)
@@ -879,6 +1005,8 @@ def main():
     ld_pos = [None] * n_rows
     dip_recs = np.zeros(n_rows, dtype=impop_amd.DIPLOID_DTYPE)
     dip_ind = [None] * n_rows  # per row: (sample names, impop_diploid_ind rows)
+    dstat_recs = np.zeros((n_rows, len(dstat_quartets or [])), dtype=impop_amd.DSTAT_DTYPE)
+    dstat_sizes = [None] * n_rows  # per row: the populations' sizes in its matrix
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -919,6 +1047,27 @@ def main():
             if not mask_a.any() or not mask_b.any():
                 print("Error: No valid sequences found in one or both populations", file=sys.stderr)  # h-fst.py:319-321
                 sys.exit(1)
+        if fmt == "dstat":
+            panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
+            pops = [flags_for(f, names) for f in args.panel]
+            sizes = [int(p.sum()) for p in pops]
+            for q in dstat_quartets:  # what impop_dstat_scan would refuse, with the lists' names
+                for a in q:
+                    if sizes[a] == 0:
+                        print(f"Error: --format dstat: {panel_labels[a]} selects no sequence of the matrix", file=sys.stderr)
+                        run.close()
+                        sys.exit(2)
+                for a, b in ((a, b) for i, a in enumerate(q) for b in q[i + 1:]):
+                    if (pops[a] & pops[b]).any():
+                        print(f"Error: --format dstat: {panel_labels[a]} and {panel_labels[b]} share a sequence; the four populations of a "
+                              "quartet must be disjoint", file=sys.stderr)
+                        run.close()
+                        sys.exit(2)
+            dstat_recs[idx] = run.dstat(pops, dstat_quartets, bool(args.dstat_polarize))
+            for i in idx:
+                dstat_sizes[i] = sizes
+            run.close()
+            continue
         if args.panel:
             panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
             pops = [flags_for(f, names) for f in args.panel]
@@ -1099,6 +1248,11 @@ def main():
                 print(DIPLOID_IND_HEADER, file=fh)
                 for (reg, _, _, _), entry in zip(rows, dip_ind):
                     write_diploid_ind_table(fh, [reg], entry[0], [entry[1]], header=False)
+    elif fmt == "dstat":
+        write_dstat_table(out, [r[0] for r in rows], panel_labels or [], dstat_quartets, dstat_sizes, dstat_recs)
+        if args.dstat_summary:
+            with open(args.dstat_summary, "w") as fh:
+                write_dstat_summary(fh, panel_labels or [], dstat_quartets, dstat_sizes, dstat_recs, args.dstat_blocks)
     elif fmt == "ehh":
         print(EHH_HEADER, file=out)
         for lines in ehh_lines:
