@@ -78,8 +78,8 @@ __global__ __launch_bounds__(DIP_T) void dip_tile_kernel(const uint32_t *__restr
     }
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    uint64_t b0, b1;
-    hap_tile_blocks(t, b0, b1);
+    const TileBlocks tb = tile_blocks_of(t);
+    const uint64_t b0 = tb.b0, b1 = tb.b1;
     const uint64_t per = (b1 - b0 + n_waves - 1) / n_waves;  // blocks per wave: wave w takes [b0 + w per, b0 + (w + 1) per)
     const uint32_t n2 = 2 * N;
     uint64_t sum_p = 0, het_total = 0;
@@ -285,11 +285,7 @@ static void dip_plan_chunks(const impop_matrix *m, const ScanRoute &rt, const im
 // blocks (wide sites: 4).  IMPOP_DIPLOID_TILE_BLOCKS=n (1..4096) overrides it, so that tests reach many-tile windows on small
 // matrices.
 static uint32_t dip_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const std::vector<impop_window> &mapped) {
-    const char *e = getenv("IMPOP_DIPLOID_TILE_BLOCKS");
-    if (e && *e) {
-        const long v = strtol(e, nullptr, 10);
-        return v < 1 ? 1u : v > 4096 ? 4096u : (uint32_t)v;
-    }
+    if (const uint32_t e = env_tile_blocks("IMPOP_DIPLOID_TILE_BLOCKS")) return e;
     const uint32_t wps = m->g.wps, by_bytes = wps > 16 ? std::max<uint32_t>(4, 1024 / wps) : std::max<uint32_t>(32, 1024 / wps);
     uint64_t blocks = 0;
     for (const impop_window &w : mapped) blocks += (w.site_end - w.site_begin + 63) / 64;

@@ -1,8 +1,9 @@
 // dstat.hip — impop_dstat_scan: Patterson's D (ABBA-BABA), f4 and Martin's f_d per window and quartet of populations
 // (include/impop_hip.h).  One streaming pass over what scan_route picks — the variable-site index with its rare entries, the
-// rows of a weighted matrix, the kept sites of a compacted one — modelled on scan_multi_kernel (scan.hip): masks of all K
-// populations in LDS, a lane per site, several granules in flight, per-tile integer partials, a finalize kernel that adds each
-// window's tile range.  Every term is zero where the site is monomorphic among all haplotypes, so the sites the index and a
+// rows of a weighted matrix, the kept sites of a compacted one.  The pass itself is pop_stream.h, shared with scan_multi_kernel
+// (scan.hip): masks of all K populations in LDS, a lane per site, several granules in flight, per-tile integer partials; here a
+// finalize kernel adds each window's tile range.  The host half (masks, upload, launch) is shared as well: scan_route.h.
+// Every term is zero where the site is monomorphic among all haplotypes, so the sites the index and a
 // compaction drop add nothing, with or without polarisation (an outgroup count of 0 or nO is never a tie).
 //
 // New is the per-site work: from the K counts of a site, per quartet five 64-bit sums and two counters.  The four populations of
@@ -17,9 +18,8 @@
 #include <vector>
 
 #include "device_utils.h"
-#include "hap_words.h"
 #include "internal.h"
-#include "sb64.h"
+#include "pop_stream.h"
 #include "scan_route.h"
 
 namespace impop {
@@ -97,40 +97,14 @@ __global__ __launch_bounds__(256, 4) void dstat_tiles_kernel(const uint32_t *__r
                                                              const uint32_t *__restrict__ pop_n /* K */, uint32_t wps, uint32_t G,
                                                              uint32_t r, const uint32_t *__restrict__ weights /* WEIGHTED */,
                                                              DstatGroup grp, uint32_t nq, int polarize, int64_t *__restrict__ out) {
-    constexpr int MU = 4;  // granules in flight per wave
     constexpr int NV = DSTAT_QG * DSTAT_NV;
     extern __shared__ __attribute__((aligned(16))) uint32_t mk_lds[];  // K x wps4
-    __shared__ uint64_t red[4][NV];
-    const uint32_t wps4 = (wps + 3) & ~3u;
-    for (uint32_t i = threadIdx.x; i < K * wps4; i += 256) {
-        const uint32_t k = i / wps4, j = i % wps4;
-        mk_lds[i] = j < wps ? masks[(uint64_t)k * wps + j] : 0u;
-    }
+    pop_masks_to_lds<K>(mk_lds, masks, wps);
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    uint64_t tb0, tb1;
-    hap_tile_blocks(t, tb0, tb1);
-    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const TileBlocks tb = tile_blocks_of(t);
     const bool pol = polarize != 0;
     DstatAcc acc[DSTAT_QG];
-    const uint32_t Gf = sb_full_granules(G, r);
-    auto count_batch = [&](uint32_t g, uint32_t nb, const u32v4 (&v)[MU], uint32_t (&c)[K]) {
-#pragma unroll
-        for (int u = 0; u < MU; ++u)
-            if ((uint32_t)u < nb) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const u32v4 m4 = *reinterpret_cast<const u32v4 *>(mk_lds + k * wps4 + 4 * (g + u));
-                    c[k] += __popc(v[u].x & m4.x) + __popc(v[u].y & m4.y) + __popc(v[u].z & m4.z) + __popc(v[u].w & m4.w);
-                }
-            }
-    };
-    auto count_tail = [&](const uint32_t (&tl)[3], uint32_t (&c)[K]) {
-        sb_use_tail(G, r, tl, [&](uint32_t j, uint32_t v) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) c[k] += __popc(v & mk_lds[k * wps4 + j]);  // j: the dword's index in the site
-        });
-    };
     auto tally_counts = [&](const uint32_t (&c)[K], uint32_t wt) {
 #pragma unroll
         for (int j = 0; j < DSTAT_QG; ++j) {
@@ -140,79 +114,22 @@ __global__ __launch_bounds__(256, 4) void dstat_tiles_kernel(const uint32_t *__r
                                  acc[j]);
         }
     };
-    auto tally = [&](uint64_t b, const uint32_t (&c)[K]) {
-        const uint64_t s = b * 64 + lane;
-        if (s >= t.site_begin && s < t.site_end) tally_counts(c, WEIGHTED ? weights[s] : 1u);
-    };
-    uint64_t b = tb0 + wave;
-    if (Gf <= (uint32_t)MU) {
-        // <= 512 haplotypes: a block is one batch; two blocks (up to 8 wave loads) in flight per wave
-        for (; b + 4 < tb1; b += 8) {
-            const uint32_t *blk0 = sb + b * 64ull * wps, *blk1 = sb + (b + 4) * 64ull * wps;
-            u32v4 v0[MU], v1[MU];
-            uint32_t t0[3], t1[3];
-            sb_load_granules(blk0, 0, Gf, lane, v0);
-            sb_load_tail(blk0, G, r, lane, t0);
-            sb_load_granules(blk1, 0, Gf, lane, v1);
-            sb_load_tail(blk1, G, r, lane, t1);
-            uint32_t c0[K], c1[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) { c0[k] = 0; c1[k] = 0; }
-            count_batch(0, Gf, v0, c0);
-            count_tail(t0, c0);
-            tally(b, c0);
-            count_batch(0, Gf, v1, c1);
-            count_tail(t1, c1);
-            tally(b + 4, c1);
+    // the rare entries of the split index belong to unweighted matrices only: compiled out under WEIGHTED
+    pop_stream_tile<K, !WEIGHTED>(
+        sb, rare, t, tb, mk_lds, pop_n, wps, G, r, [&](const uint32_t (&c)[K], uint64_t s) { tally_counts(c, WEIGHTED ? weights[s] : 1u); },
+        [&](const uint32_t (&c)[K]) { tally_counts(c, 1u); });
+    tile_partials_store<NV>(tb, reinterpret_cast<uint64_t *>(out), [&](int i) -> uint64_t {
+        const DstatAcc &a = acc[i / DSTAT_NV];
+        switch (i % DSTAT_NV) {  // i is a constant once the caller's loop is unrolled
+            case 0: return wave_sum_u64(a.abba);
+            case 1: return wave_sum_u64(a.baba);
+            case 2: return wave_sum_u64((uint64_t)a.f4);
+            case 3: return wave_sum_u64((uint64_t)a.fd2);
+            case 4: return wave_sum_u64((uint64_t)a.fd3);
+            case 5: return wave_sum_u32(a.inf);
+            default: return wave_sum_u32(a.skip);
         }
-    }
-    for (; b < tb1; b += 4) {
-        const uint32_t *blk = sb + b * 64ull * wps;
-        uint32_t c[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) c[k] = 0;
-        uint32_t tl[3];
-        sb_load_tail(blk, G, r, lane, tl);
-        for (uint32_t g = 0; g < Gf; g += MU) {
-            const uint32_t nb = Gf - g < (uint32_t)MU ? Gf - g : (uint32_t)MU;
-            u32v4 v[MU];
-            sb_load_granules(blk, g, nb, lane, v);
-            count_batch(g, nb, v, c);
-        }
-        count_tail(tl, c);
-        tally(b, c);
-    }
-    // rare entries of the split index (unweighted matrices only): each population's count from bit tests of the listed
-    // haplotypes, mirrored through n_k - m_k when they carry 0
-    if (!WEIGHTED) {
-        uint32_t nk[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) nk[k] = pop_n[k];
-        for (uint64_t e = t.rare_begin + threadIdx.x; e < t.rare_end; e += 256) {
-            const uint64_t v = stream_load(rare + e);
-            uint32_t c[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                const uint32_t mk = rare_listed_in(mk_lds + k * wps4, v);
-                c[k] = rare_lists_zeros(v) ? nk[k] - mk : mk;
-            }
-            tally_counts(c, 1u);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < DSTAT_QG; ++j) {
-        const uint64_t v[DSTAT_NV] = {wave_sum_u64(acc[j].abba), wave_sum_u64(acc[j].baba), wave_sum_u64((uint64_t)acc[j].f4),
-                                      wave_sum_u64((uint64_t)acc[j].fd2), wave_sum_u64((uint64_t)acc[j].fd3),
-                                      (uint64_t)wave_sum_u32(acc[j].inf), (uint64_t)wave_sum_u32(acc[j].skip)};
-        if (lane == 0) {
-#pragma unroll
-            for (int f = 0; f < DSTAT_NV; ++f) red[wave][j * DSTAT_NV + f] = v[f];
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < NV)
-        out[(uint64_t)blockIdx.x * NV + threadIdx.x] =
-            (int64_t)(red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+    });
 }
 
 // one thread per (window, quartet of the group): the window's tile range added up, the record's integers written
@@ -244,33 +161,11 @@ __global__ __launch_bounds__(128) void dstat_finalize_kernel(const int64_t *__re
     out[win * n_quartets + q0 + j] = o;
 }
 
-// IMPOP_DSTAT_TILE_BLOCKS=n (1..4096) overrides the tile size, so that tests reach many-tile windows on small matrices
+// IMPOP_DSTAT_TILE_BLOCKS=n (1..4096) overrides the tile size, so that tests reach many-tile windows on small matrices; it
+// beats params->tile_blocks (0: the default)
 static uint32_t dstat_tile_blocks(const impop_dstat_params *params) {
-    long v = params->tile_blocks;
-    const char *e = getenv("IMPOP_DSTAT_TILE_BLOCKS");
-    if (e && *e) v = strtol(e, nullptr, 10);
-    else if (!v) return 0;
-    return v < 1 ? 1u : v > 4096 ? 4096u : (uint32_t)v;
-}
-
-template <int K>
-static int dstat_launch(hipStream_t st, const impop_matrix *m, const ScanRoute &rt, const ScanTile *d_tiles, const uint32_t *d_masks,
-                        const uint32_t *d_n, const DstatGroup &grp, uint32_t nq, int polarize, int64_t *d_parts) {
-    const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
-    const dim3 grid((uint32_t)rt.tiles.size()), block(256);
-    if (m->d_wt && !rt.indexed) {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)dstat_tiles_kernel<K, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((dstat_tiles_kernel<K, true>), grid, block, lds, st, rt.sb, rt.rare, d_tiles, d_masks, d_n, m->g.wps, m->g.G,
-                           m->g.r, m->d_wt, grp, nq, polarize, d_parts);
-    } else {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)dstat_tiles_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((dstat_tiles_kernel<K, false>), grid, block, lds, st, rt.sb, rt.rare, d_tiles, d_masks, d_n, m->g.wps, m->g.G,
-                           m->g.r, (const uint32_t *)nullptr, grp, nq, polarize, d_parts);
-    }
-    HIP_TRY(hipGetLastError());
-    return IMPOP_OK;
+    const uint32_t e = env_tile_blocks("IMPOP_DSTAT_TILE_BLOCKS");
+    return e ? e : std::min<uint32_t>(params->tile_blocks, 4096u);
 }
 
 }  // namespace impop
@@ -290,17 +185,11 @@ IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impo
     REQUIRE(n_quartets >= 1 && n_quartets <= IMPOP_DSTAT_MAX_QUARTETS && quartets, "%s: n_quartets must be 1..%u (got %u)", fn,
             IMPOP_DSTAT_MAX_QUARTETS, n_quartets);
     REQUIRE(m->g.n_hap <= 65535, "%s: n_hap > 65535 not supported", fn);
-    const uint32_t n = m->g.n_hap, wps = m->g.wps, K = n_pop, Q = n_quartets, mwords = (n + 63) / 64;
-    std::vector<uint32_t> mk((size_t)K * wps, 0u), nk(K, 0u);
-    for (uint32_t k = 0; k < K; ++k) {
-        const uint64_t *mw = masks + (size_t)k * mwords;
-        for (uint32_t h = 0; h < n; ++h)
-            if ((mw[h >> 6] >> (h & 63)) & 1ull) {
-                mk[(size_t)k * wps + (h >> 5)] |= 1u << (h & 31);
-                ++nk[k];
-            }
-        REQUIRE(nk[k] > 0, "%s: population %u is empty", fn, k);
-    }
+    const uint32_t wps = m->g.wps, K = n_pop, Q = n_quartets;
+    PopPanel panel;
+    pop_panel_pack(m, masks, K, panel);
+    const std::vector<uint32_t> &mk = panel.mk, &nk = panel.nk;
+    for (uint32_t k = 0; k < K; ++k) REQUIRE(nk[k] > 0, "%s: population %u is empty", fn, k);
     std::vector<DstatQuartet> qs(Q);
     for (uint32_t q = 0; q < Q; ++q) {
         for (int a = 0; a < 4; ++a) {
@@ -342,22 +231,15 @@ IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impo
     rc = scan_route(fn, ctx, m, windows, n_windows, dstat_tile_blocks(params), rt);
     if (rc) return rc;
     const size_t nt = rt.tiles.size();
-    Carve L;
-    const size_t o_tiles = L.take<ScanTile>(std::max<size_t>(nt, 1)), o_wins = L.take<WinDesc>(n_windows), o_masks = L.take<uint32_t>(mk.size()),
-                 o_n = L.take<uint32_t>(K), o_parts = L.take<int64_t>(std::max<size_t>(nt, 1) * DSTAT_QG * DSTAT_NV),
-                 o_out = L.take<impop_dstat_stats>(n_windows * Q);
-    void *d = nullptr;
-    rc = ctx_scratch(ctx, L.total(), &d);
+    PopPanelDev dev;
+    int64_t *dp = nullptr;
+    impop_dstat_stats *d_out = nullptr;
+    rc = pop_panel_upload(ctx, rt, panel, dev, [&](Layout &L) {
+        L.sub(dp, std::max<size_t>(nt, 1) * DSTAT_QG * DSTAT_NV);
+        L.sub(d_out, n_windows * Q);
+    });
     if (rc) return rc;
-    char *base = (char *)d;
-    if (nt) HIP_TRY(hipMemcpyAsync(base + o_tiles, rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_masks, mk.data(), mk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_n, nk.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
-    const ScanTile *dt = (const ScanTile *)(base + o_tiles);
-    const uint32_t *dm = (const uint32_t *)(base + o_masks), *dn = (const uint32_t *)(base + o_n);
-    int64_t *dp = (int64_t *)(base + o_parts);
-    impop_dstat_stats *d_out = (impop_dstat_stats *)(base + o_out);
+    const uint32_t *weights = m->d_wt && !rt.indexed ? m->d_wt : nullptr;  // weighted matrices stream their rows
     const int polarize = params->polarize != 0;
     const bool timed = ctx->gram_timing;
     uint64_t launches = 0;
@@ -369,20 +251,17 @@ IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impo
         if (nt) {
             size_t slot = 0;
             if (timed && (rc = ctx->dstat_timer.begin(ctx->stream, &slot))) return rc;
-            switch (K) {
-                case 4: rc = dstat_launch<4>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
-                case 5: rc = dstat_launch<5>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
-                case 6: rc = dstat_launch<6>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
-                case 7: rc = dstat_launch<7>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
-                default: rc = dstat_launch<8>(ctx->stream, m, rt, dt, dm, dn, grp, nq, polarize, dp); break;
-            }
+            rc = pop_dispatch_k<4>(K, [&](auto k) {
+                return weights ? pop_launch(dstat_tiles_kernel<k.value, true>, K, ctx->stream, m, rt, dev, weights, grp, nq, polarize, dp)
+                               : pop_launch(dstat_tiles_kernel<k.value, false>, K, ctx->stream, m, rt, dev, weights, grp, nq, polarize, dp);
+            });
             if (rc) return rc;
             if (timed && (rc = ctx->dstat_timer.end(ctx->stream, slot))) return rc;
             ++launches;
         }
         const uint64_t items = n_windows * nq;
         hipLaunchKernelGGL(dstat_finalize_kernel, dim3((uint32_t)((items + 127) / 128)), dim3(128), 0, ctx->stream, dp,
-                           (const WinDesc *)(base + o_wins), n_windows, nq, q0, Q, d_out);
+                           (const WinDesc *)dev.wins, n_windows, nq, q0, Q, d_out);
         HIP_TRY(hipGetLastError());
         ++launches;
     }

@@ -1,6 +1,6 @@
-// hap_words.h — what the streaming kernels over scan_route's tiles share (scan.hip, hapscan.hip, diploid.hip, dstat.hip): a tile's
-// 64-site blocks with its edges masked, the ballot transpose of a block into per-haplotype 64-site words, the members a rare entry
-// lists and how many of them a population mask holds.
+// hap_words.h — what the streaming kernels over scan_route's tiles share (scan.hip, hapscan.hip, diploid.hip, and through
+// pop_stream.h dstat.hip): a tile's 64-site blocks (tile_blocks_of, the one block-range helper) with its edges masked, the ballot
+// transpose of a block into per-haplotype 64-site words, the members a rare entry lists and how many of them a population mask holds.
 #pragma once
 #include "device_utils.h"
 #include "internal.h"
@@ -9,11 +9,19 @@
 
 namespace impop {
 
-// the blocks a tile's sites lie in, and the sites of block b inside the tile
-__device__ __forceinline__ void hap_tile_blocks(const ScanTile &t, uint64_t &b0, uint64_t &b1) {
-    b0 = t.site_begin >> 6;
-    b1 = t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0;
+// the blocks [b0, b1) a tile's sites lie in, and this thread's lane and wave; the wave index goes through readfirstlane so that
+// block addresses and loops formed from it stay scalar (SGPR) state.  The 256-thread kernels of scan.hip and pop_stream.h give
+// wave w the blocks b0 + w, b0 + w + 4, ...; hapscan.hip and diploid.hip split a tile their own way and take b0, b1 alone.
+struct TileBlocks {
+    uint64_t b0, b1;
+    uint32_t lane, wave;
+};
+__device__ __forceinline__ TileBlocks tile_blocks_of(const ScanTile &t) {
+    const uint64_t b0 = t.site_begin >> 6;
+    return {b0, t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0, threadIdx.x & 63,
+            (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)};
 }
+// the sites of block b inside the tile
 __device__ __forceinline__ uint64_t hap_edge(const ScanTile &t, uint64_t b) {
     uint64_t edge = ~0ull;
     if (b * 64 < t.site_begin) edge &= ~0ull << (t.site_begin - b * 64);

@@ -51,8 +51,8 @@ __global__ __launch_bounds__(HAP_T) void hap_fingerprint_kernel(const uint32_t *
     for (uint32_t i = tid; i < 2 * nP; i += HAP_T) hap_acc[i] = 0ull;
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
-    uint64_t b0, b1;
-    hap_tile_blocks(t, b0, b1);
+    const TileBlocks tb = tile_blocks_of(t);
+    const uint64_t b0 = tb.b0, b1 = tb.b1;
     for (uint64_t b = b0 + wave; b < b1; b += 4) {
         const uint64_t ka = mix64(2 * b + 1), kb = mix64(~b);  // the block's keys: equal words of different blocks differ
         hap_block_words(sb + b * 64ull * wps, G, r, lane, hap_edge(t, b), ppos, pmask, [&](uint32_t pp, uint64_t word) {
@@ -221,8 +221,8 @@ __global__ __launch_bounds__(HAP_T) void hap_verify_kernel(const uint32_t *__res
     for (uint32_t i = tid; i < nP; i += HAP_T) rs[i] = repsz[(uint64_t)it.win * nP + i];
     __syncthreads();
     const ScanTile t = tiles[it.tile];
-    uint64_t b0, b1;
-    hap_tile_blocks(t, b0, b1);
+    const TileBlocks tb = tile_blocks_of(t);
+    const uint64_t b0 = tb.b0, b1 = tb.b1;
     bool bad = false;
     for (uint64_t bb = b0; bb < b1; bb += 4) {  // the same trip count for every wave: the barriers are workgroup-wide
         const uint64_t b = bb + wave;
@@ -295,8 +295,8 @@ __global__ __launch_bounds__(HAP_T) void hap_exact_kernel(const uint32_t *__rest
         const uint32_t ch = idx[cur];  // its row of the matrix
         for (uint32_t tt = w.t0; tt < w.t1; ++tt) {
             const ScanTile t = tiles[tt];
-            uint64_t b0, b1;
-            hap_tile_blocks(t, b0, b1);
+            const TileBlocks tb = tile_blocks_of(t);
+            const uint64_t b0 = tb.b0, b1 = tb.b1;
             for (uint64_t b = b0 + wave; b < b1; b += 4) {
                 const uint64_t edge = hap_edge(t, b);
                 const uint32_t d = sb[sb_index(wps, G, r, b, lane, ch >> 5)];

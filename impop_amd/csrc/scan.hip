@@ -16,6 +16,7 @@
 #include "device_utils.h"
 #include "hap_words.h"
 #include "internal.h"
+#include "pop_stream.h"
 #include "sb64.h"
 #include "scan_route.h"
 
@@ -43,18 +44,6 @@ struct MaskArgs {
 #ifndef IMPOP_SCAN_MIN_WAVES
 #define IMPOP_SCAN_MIN_WAVES 6 // __launch_bounds__ 2nd argument (waves per SIMD)
 #endif
-
-// the blocks [b0, b1) a tile's sites lie in, and this thread's place: wave w takes blocks b0 + w, b0 + w + 4, ...; the wave
-// index goes through readfirstlane so that block addresses and the loops stay scalar (SGPR) state
-struct TileBlocks {
-    uint64_t b0, b1;
-    uint32_t lane, wave;
-};
-__device__ __forceinline__ TileBlocks tile_blocks_of(const ScanTile &t) {
-    const uint64_t b0 = t.site_begin >> 6;
-    return {b0, t.site_end > t.site_begin ? (t.site_end + 63) >> 6 : b0, threadIdx.x & 63,
-            (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)};
-}
 
 // per-lane sums of one tile, any n <= 65535: every product c (n - c) is below 2^32, the sums are 64 bits wide
 struct LaneAcc {
@@ -512,14 +501,8 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
                                                          uint32_t G, uint32_t r, const uint32_t *__restrict__ weights /* nullable */,
                                                          uint64_t *__restrict__ out) {
     constexpr int NP = K * (K - 1) / 2;
-    constexpr int MU = 4;  // granules in flight per wave
     extern __shared__ __attribute__((aligned(16))) uint32_t mk_lds[];  // K x wps4
-    __shared__ uint64_t red[4][K + NP];
-    const uint32_t wps4 = (wps + 3) & ~3u;
-    for (uint32_t i = threadIdx.x; i < K * wps4; i += 256) {
-        const uint32_t k = i / wps4, j = i % wps4;
-        mk_lds[i] = j < wps ? masks[(uint64_t)k * wps + j] : 0u;
-    }
+    pop_masks_to_lds<K>(mk_lds, masks, wps);
     __syncthreads();
     const ScanTile t = tiles[blockIdx.x];
     const TileBlocks tb = tile_blocks_of(t);
@@ -534,25 +517,6 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
     for (int k = 0; k < K; ++k) { s1[k] = 0; q2[k] = 0; }
 #pragma unroll
     for (int i = 0; i < NP; ++i) px[i] = 0;
-    const uint32_t Gf = sb_full_granules(G, r);
-    auto count_batch = [&](uint32_t g, uint32_t nb, const u32v4 (&v)[MU], uint32_t (&c)[K]) {
-#pragma unroll
-        for (int u = 0; u < MU; ++u)
-            if ((uint32_t)u < nb) {
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const u32v4 m4 = *reinterpret_cast<const u32v4 *>(mk_lds + k * wps4 + 4 * (g + u));
-                    c[k] += __popc(v[u].x & m4.x) + __popc(v[u].y & m4.y) + __popc(v[u].z & m4.z) + __popc(v[u].w & m4.w);
-                }
-            }
-    };
-    // the last granule's r = 1..3 dwords per site are loaded TOGETHER with the batch (sb_load_tail)
-    auto count_tail = [&](const uint32_t (&tl)[3], uint32_t (&c)[K]) {
-        sb_use_tail(G, r, tl, [&](uint32_t j, uint32_t v) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) c[k] += __popc(v & mk_lds[k * wps4 + j]);  // j: the dword's index in the site
-        });
-    };
     // wt: the site's weight (unweighted: 1)
     auto tally_counts = [&](const uint32_t (&c)[K], uint64_t wt) {
         if (SMALL) {
@@ -574,60 +538,10 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
             }
         }
     };
-    auto tally = [&](uint64_t b, const uint32_t (&c)[K]) {
-        const uint64_t s = b * 64 + tb.lane;
-        if (s >= t.site_begin && s < t.site_end) tally_counts(c, !SMALL && weights ? weights[s] : 1);  // wave-uniform choice
-    };
-    uint64_t b = tb.b0 + tb.wave;
-    if (Gf <= (uint32_t)MU) {
-        // <= 512 haplotypes: a block is one batch; two blocks (up to 8 wave loads) in flight per wave
-        for (; b + 4 < tb.b1; b += 8) {
-            const uint32_t *blk0 = sb + b * 64ull * wps, *blk1 = sb + (b + 4) * 64ull * wps;
-            u32v4 v0[MU], v1[MU];
-            uint32_t t0[3], t1[3];
-            sb_load_granules(blk0, 0, Gf, tb.lane, v0);
-            sb_load_tail(blk0, G, r, tb.lane, t0);
-            sb_load_granules(blk1, 0, Gf, tb.lane, v1);
-            sb_load_tail(blk1, G, r, tb.lane, t1);
-            uint32_t c0[K], c1[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) { c0[k] = 0; c1[k] = 0; }
-            count_batch(0, Gf, v0, c0);
-            count_tail(t0, c0);
-            tally(b, c0);
-            count_batch(0, Gf, v1, c1);
-            count_tail(t1, c1);
-            tally(b + 4, c1);
-        }
-    }
-    for (; b < tb.b1; b += 4) {
-        const uint32_t *blk = sb + b * 64ull * wps;
-        uint32_t c[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) c[k] = 0;
-        uint32_t tl[3];
-        sb_load_tail(blk, G, r, tb.lane, tl);
-        for (uint32_t g = 0; g < Gf; g += MU) {
-            const uint32_t nb = Gf - g < (uint32_t)MU ? Gf - g : (uint32_t)MU;
-            u32v4 v[MU];
-            sb_load_granules(blk, g, nb, tb.lane, v);
-            count_batch(g, nb, v, c);
-        }
-        count_tail(tl, c);
-        tally(b, c);
-    }
-    // rare entries of the split index (unweighted matrices only): each population's count from bit tests of the listed
-    // haplotypes, mirrored through n_k - m_k when they carry 0 (rare_counts)
-    for (uint64_t e = t.rare_begin + threadIdx.x; e < t.rare_end; e += 256) {
-        const uint64_t v = stream_load(rare + e);
-        uint32_t c[K];
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-            const uint32_t mk = rare_listed_in(mk_lds + k * wps4, v);
-            c[k] = rare_lists_zeros(v) ? nk[k] - mk : mk;
-        }
-        tally_counts(c, 1);
-    }
+    pop_stream_tile<K, true>(
+        sb, rare, t, tb, mk_lds, pop_n, wps, G, r,
+        [&](const uint32_t (&c)[K], uint64_t s) { tally_counts(c, !SMALL && weights ? weights[s] : 1); },  // wave-uniform choice
+        [&](const uint32_t (&c)[K]) { tally_counts(c, 1); });
     if (SMALL) {
         int pi = K;
 #pragma unroll
@@ -637,15 +551,7 @@ __global__ __launch_bounds__(256) void scan_multi_kernel(const uint32_t *__restr
             for (int l = k + 1; l < K; ++l) { acc[pi] = (uint64_t)nk[l] * s1[k] + (uint64_t)nk[k] * s1[l] - 2ull * px[pi - K]; ++pi; }
         }
     }
-#pragma unroll
-    for (int i = 0; i < K + NP; ++i) {
-        const uint64_t v = wave_sum_u64(acc[i]);
-        if (tb.lane == 0) red[tb.wave][i] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K + NP)
-        out[(uint64_t)blockIdx.x * (K + NP) + threadIdx.x] =
-            red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    tile_partials_store<K + NP>(tb, out, [&](int i) { return wave_sum_u64(acc[i]); });
 }
 
 // one thread per (window, pair): h-fst.py:203-240 on the exact pair sums
@@ -946,6 +852,45 @@ int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, con
     return IMPOP_OK;
 }
 
+uint32_t impop::env_tile_blocks(const char *name) {
+    const char *e = getenv(name);
+    if (!e || !*e) return 0;
+    const long v = strtol(e, nullptr, 10);
+    return v < 1 ? 1u : v > 4096 ? 4096u : (uint32_t)v;
+}
+
+void impop::pop_panel_pack(const impop_matrix *m, const uint64_t *masks, uint32_t K, PopPanel &p) {
+    const uint32_t n = m->g.n_hap, wps = m->g.wps, mwords = (n + 63) / 64;
+    p.mk.clear();
+    p.nk.resize(K);
+    std::vector<uint32_t> one;
+    for (uint32_t k = 0; k < K; ++k) {
+        mask_to_dwords(masks + (size_t)k * mwords, n, wps, false, one);
+        p.mk.insert(p.mk.end(), one.begin(), one.end());
+        p.nk[k] = popcount_vec(one);
+    }
+}
+
+int impop::pop_panel_upload(impop_ctx *ctx, const ScanRoute &rt, const PopPanel &p, PopPanelDev &dev,
+                            const std::function<void(Layout &)> &own) {
+    const size_t nt = rt.tiles.size(), nw = rt.wins.size();
+    Layout L;
+    L.sub(dev.tiles, std::max<size_t>(nt, 1));
+    L.sub(dev.wins, nw);
+    L.sub(dev.masks, p.mk.size());
+    L.sub(dev.n, p.nk.size());
+    own(L);
+    void *d = nullptr;
+    const int rc = ctx_scratch(ctx, L.total(), &d);
+    if (rc) return rc;
+    L.bind(d);
+    if (nt) HIP_TRY(hipMemcpyAsync(dev.tiles, rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dev.wins, rt.wins.data(), nw * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dev.masks, p.mk.data(), p.mk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(dev.n, p.nk.data(), p.nk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    return IMPOP_OK;
+}
+
 template <int WPS>
 static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
     MaskArgs<WPS> mk;
@@ -1184,23 +1129,6 @@ IMPOP_API int impop_site_counts(impop_ctx *ctx, const impop_matrix *m, const uin
     return IMPOP_OK;
 }
 
-template <int K>
-static int launch_multi(hipStream_t st, const impop_matrix *m, const uint32_t *sb, const uint64_t *rare, uint64_t n_tiles,
-                        const ScanTile *d_tiles,
-                        const uint32_t *d_masks, const uint32_t *d_n, uint64_t *d_parts, bool small) {
-    const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
-    if (small) {
-        hipLaunchKernelGGL((scan_multi_kernel<K, true>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, rare, d_tiles, d_masks, d_n,
-                           m->g.wps, m->g.G, m->g.r, m->d_wt, d_parts);
-    } else {
-        if (lds > 48 * 1024)
-            HIP_TRY(hipFuncSetAttribute((const void *)scan_multi_kernel<K, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL((scan_multi_kernel<K, false>), dim3((uint32_t)n_tiles), dim3(256), lds, st, sb, rare, d_tiles, d_masks, d_n,
-                           m->g.wps, m->g.G, m->g.r, m->d_wt, d_parts);
-    }
-    return IMPOP_OK;
-}
-
 IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                                const uint64_t *masks, uint32_t n_pop, impop_pair_stats *out_host) {
     REQUIRE(ctx && m, "impop_scan_multi: NULL argument");
@@ -1212,61 +1140,44 @@ IMPOP_API int impop_scan_multi(impop_ctx *ctx, const impop_matrix *m, const impo
     int rc = check_windows("impop_scan_multi", m, windows, n_windows);
     if (rc) return rc;
     const uint32_t n = m->g.n_hap, wps = m->g.wps, K = n_pop, NP = K * (K - 1) / 2;
-    const uint32_t mwords = (n + 63) / 64;
-    std::vector<uint32_t> mk((size_t)K * wps), nk(K);
-    std::vector<uint32_t> seen(wps, 0u), one;
-    for (uint32_t k = 0; k < K; ++k) {
-        mask_to_dwords(masks + (size_t)k * mwords, n, wps, false, one);
+    PopPanel panel;
+    pop_panel_pack(m, masks, K, panel);
+    std::vector<uint32_t> seen(wps, 0u);
+    for (uint32_t k = 0; k < K; ++k)
         for (uint32_t j = 0; j < wps; ++j) {
             // h-fst.py:181-185 removes shared members per pair; with K populations that would make
             // n_k pair-dependent, so the one-pass form requires disjoint populations
-            REQUIRE((seen[j] & one[j]) == 0, "impop_scan_multi: populations must be disjoint (population %u overlaps an earlier one)", k);
-            seen[j] |= one[j];
-            mk[(size_t)k * wps + j] = one[j];
+            REQUIRE((seen[j] & panel.mk[(size_t)k * wps + j]) == 0,
+                    "impop_scan_multi: populations must be disjoint (population %u overlaps an earlier one)", k);
+            seen[j] |= panel.mk[(size_t)k * wps + j];
         }
-        nk[k] = popcount_vec(one);
-    }
     HIP_TRY(hipSetDevice(ctx->device));
     ScanRoute rt;
     rc = scan_route("impop_scan_multi", ctx, m, windows, n_windows, 0, rt);
     if (rc) return rc;
     const size_t nt = rt.tiles.size();
-    Carve L;
-    const size_t o_tiles = L.take<ScanTile>(std::max<size_t>(nt, 1)), o_wins = L.take<WinDesc>(n_windows),
-                 o_masks = L.take<uint32_t>(mk.size()), o_n = L.take<uint32_t>(K),
-                 o_parts = L.take<uint64_t>(std::max<size_t>(nt, 1) * (K + NP)), o_out = L.take<impop_pair_stats>(n_windows * NP);
-    void *d = nullptr;
-    rc = ctx_scratch(ctx, L.total(), &d);
+    const uint64_t items = n_windows * NP;
+    PopPanelDev dev;
+    uint64_t *d_parts = nullptr;
+    impop_pair_stats *d_out = nullptr;
+    rc = pop_panel_upload(ctx, rt, panel, dev, [&](Layout &L) {
+        L.sub(d_parts, std::max<size_t>(nt, 1) * (K + NP));
+        L.sub(d_out, items);
+    });
     if (rc) return rc;
-    char *base = (char *)d;
-    if (nt) HIP_TRY(hipMemcpyAsync(base + o_tiles, rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_masks, mk.data(), mk.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(base + o_n, nk.data(), K * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nt) {
-        const ScanTile *dt = (const ScanTile *)(base + o_tiles);
-        const uint32_t *dm = (const uint32_t *)(base + o_masks), *dn = (const uint32_t *)(base + o_n);
-        uint64_t *dp = (uint64_t *)(base + o_parts);
         // 32-bit per-lane partial sums: unweighted, <= 512 haplotypes, <= 1024 sites per lane and tile
         const bool small = m->wt_prefix.empty() && n <= 512 && rt.tile_blocks <= 4096;
-        switch (K) {
-            case 2: rc = launch_multi<2>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-            case 3: rc = launch_multi<3>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-            case 4: rc = launch_multi<4>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-            case 5: rc = launch_multi<5>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-            case 6: rc = launch_multi<6>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-            case 7: rc = launch_multi<7>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-            default: rc = launch_multi<8>(ctx->stream, m, rt.sb, rt.rare, nt, dt, dm, dn, dp, small); break;
-        }
+        rc = pop_dispatch_k<2>(K, [&](auto k) {
+            return small ? pop_launch(scan_multi_kernel<k.value, true>, K, ctx->stream, m, rt, dev, m->d_wt, d_parts)
+                         : pop_launch(scan_multi_kernel<k.value, false>, K, ctx->stream, m, rt, dev, m->d_wt, d_parts);
+        });
         if (rc) return rc;
-        HIP_TRY(hipGetLastError());
     }
-    const uint64_t items = n_windows * NP;
     hipLaunchKernelGGL(scan_multi_finalize_kernel, dim3((uint32_t)((items + 127) / 128)), dim3(128), 0, ctx->stream,
-                       (const uint64_t *)(base + o_parts), (const WinDesc *)(base + o_wins), n_windows, K,
-                       (const uint32_t *)(base + o_n), (impop_pair_stats *)(base + o_out));
+                       (const uint64_t *)d_parts, (const WinDesc *)dev.wins, n_windows, K, (const uint32_t *)dev.n, d_out);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out_host, base + o_out, items * sizeof(impop_pair_stats), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, d_out, items * sizeof(impop_pair_stats), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return IMPOP_OK;
 }

@@ -1,6 +1,9 @@
 // scan_route.h — the front end the streaming calls share (bodies in scan.hip): which layout a scan of a window list streams
-// and how the windows are cut into tiles.  impop_scan_plan_create, impop_scan_multi and impop_haplotype_scan all go through it.
+// and how the windows are cut into tiles.  impop_scan_plan_create, impop_scan_multi, impop_haplotype_scan, impop_ld_scan,
+// impop_diploid_scan and impop_dstat_scan all go through it.  Below it, the host half of the K-population calls
+// (impop_scan_multi, impop_dstat_scan; their device half is pop_stream.h): the panel's masks, its upload, its launch.
 #pragma once
+#include <type_traits>
 #include <vector>
 
 #include "internal.h"
@@ -39,5 +42,46 @@ int check_windows(const char *fn, const impop_matrix *m, const impop_window *win
 // windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams.  tile_blocks 0: the default.
 int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                uint32_t tile_blocks, ScanRoute &rt);
+// a tile-size override for tests, <name>=n in the environment: n clamped to 1..4096, 0 where the variable is unset or empty
+uint32_t env_tile_blocks(const char *name);
+
+// K populations as the kernels of pop_stream.h read them
+struct PopPanel {
+    std::vector<uint32_t> mk;  // K x wps dwords, clipped to n_hap
+    std::vector<uint32_t> nk;  // K sizes
+};
+// masks: K bitsets of ceil(n_hap / 64) words.  Refuses nothing: which populations must be disjoint or non-empty is each call's own rule.
+void pop_panel_pack(const impop_matrix *m, const uint64_t *masks, uint32_t K, PopPanel &p);
+
+struct PopPanelDev {
+    ScanTile *tiles = nullptr;
+    WinDesc *wins = nullptr;
+    uint32_t *masks = nullptr, *n = nullptr;
+};
+// Lists the route's tiles and windows and the panel's masks and sizes in L, then what own(L) adds (the call's partials and
+// records), gets L.total() bytes of the context's scratch, binds every listed pointer and queues the four uploads on the
+// context's stream.
+int pop_panel_upload(impop_ctx *ctx, const ScanRoute &rt, const PopPanel &p, PopPanelDev &dev, const std::function<void(Layout &)> &own);
+
+// One streaming launch of a kernel of pop_stream.h: a workgroup per tile, the K masks in dynamic LDS (above 48 KiB by opt-in).
+// Every such kernel starts with (sb, rare, tiles, masks, pop_n, wps, G, r, weights); own... is what follows.
+template <typename Kernel, typename... Own>
+int pop_launch(Kernel kernel, uint32_t K, hipStream_t st, const impop_matrix *m, const ScanRoute &rt, const PopPanelDev &dev,
+               const uint32_t *weights, Own... own) {
+    const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
+    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(kernel, dim3((uint32_t)rt.tiles.size()), dim3(256), lds, st, rt.sb, rt.rare, (const ScanTile *)dev.tiles,
+                       (const uint32_t *)dev.masks, (const uint32_t *)dev.n, m->g.wps, m->g.G, m->g.r, weights, own...);
+    HIP_TRY(hipGetLastError());
+    return IMPOP_OK;
+}
+// f(std::integral_constant<int, k>()) for the run-time k in KMIN..8 (validated by the caller)
+template <int KMIN, typename F>
+int pop_dispatch_k(uint32_t k, F f) {
+    if constexpr (KMIN < 8) {
+        if (k > (uint32_t)KMIN) return pop_dispatch_k<KMIN + 1>(k, f);
+    }
+    return f(std::integral_constant<int, KMIN>());
+}
 
 }  // namespace impop

@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
-"""K-population scan (impop_scan_multi) on the chr2-scale workload: wall time per call, K = 2..8."""
+"""K-population scan (impop_scan_multi) on the chr2-scale workload: wall time per call, K = 2, 5, 8.
+
+    python tools/bench_multi.py [n_windows [n_hap [dense]]]
+
+Defaults: 4854 windows of 50 kb, 465 haplotypes (scan_multi_kernel<K, true>), the matrix's own scan index.  More than 512 haplotypes
+(641: a remainder loop of four granules and one) run scan_multi_kernel<K, false>; "dense" uploads without the index, so the
+rows are streamed."""
 import json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import impop_amd
-n, W, NW = 465, 50000, int(sys.argv[1]) if len(sys.argv) > 1 else 4854
+n, W, NW = int(sys.argv[2]) if len(sys.argv) > 2 else 465, 50000, int(sys.argv[1]) if len(sys.argv) > 1 else 4854
 ctx = impop_amd.Context(0)
-bm = ctx.synthetic(n, W * NW, seed=20251031)
+bm = ctx.synthetic(n, W * NW, seed=20251031, dense_scan="dense" in sys.argv[3:])
 wins = impop_amd.fixed_windows(W * NW, W)
 out = {}
 for K in (2, 5, 8):
