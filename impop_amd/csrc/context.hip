@@ -214,13 +214,7 @@ IMPOP_API int impop_ctx_destroy(impop_ctx *ctx) {
     if (ctx->d_taj) hipFree(ctx->d_taj);
     if (ctx->d_queue) hipFree(ctx->d_queue);
     if (ctx->d_err) hipFree(ctx->d_err);
-    ctx->gram_timer.destroy();
-    ctx->cluster_timer.destroy();
-    ctx->ehh_timer.destroy();
-    for (impop::EventPairs &t : ctx->hap_timer) t.destroy();
-    for (impop::EventPairs &t : ctx->ld_timer) t.destroy();
-    for (impop::EventPairs &t : ctx->dip_timer) t.destroy();
-    ctx->dstat_timer.destroy();
+    for (impop::EventPairs &t : ctx->timers) t.destroy();
     if (ctx->scratch) hipFree(ctx->scratch);
     if (ctx->pinned) hipHostFree(ctx->pinned);
     for (void *a : ctx->d_aux)
@@ -237,6 +231,15 @@ namespace impop {
 int ctx_err_fetch(impop_ctx *ctx) {
     ctx->h_err = 0;
     if (ctx->d_err) HIP_TRY(hipMemcpyAsync(&ctx->h_err, ctx->d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return IMPOP_OK;
+}
+int ctx_timers_elapsed(impop_ctx *ctx, int first, int n, int which, double *kernel_ms, uint64_t *count) {
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < n; ++k) {
+        const int rc = ctx->timers[first + k].elapsed(kernel_ms ? &kernel_ms[k] : nullptr, k == which ? count : nullptr);
+        if (rc) return rc;
+    }
     return IMPOP_OK;
 }
 int ctx_err_result(impop_ctx *ctx, const char *fn) {
@@ -270,35 +273,23 @@ IMPOP_API int impop_ctx_gram_timing(impop_ctx *ctx, int enable) {
     HIP_TRY(hipSetDevice(ctx->device));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     ctx->gram_timing = enable != 0;
-    ctx->gram_timer.reset();
-    ctx->cluster_timer.reset();
-    ctx->ehh_timer.reset();
-    for (impop::EventPairs &t : ctx->hap_timer) t.reset();
-    for (impop::EventPairs &t : ctx->ld_timer) t.reset();
-    for (impop::EventPairs &t : ctx->dip_timer) t.reset();
-    ctx->dstat_timer.reset();
+    for (impop::EventPairs &t : ctx->timers) t.reset();
     return IMPOP_OK;
 }
 
 IMPOP_API int impop_ctx_gram_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_gram_elapsed: ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ctx->gram_timer.elapsed(total_ms, launches);
+    return ctx_timers_elapsed(ctx, impop_ctx::T_GRAM, 1, 0, total_ms, launches);
 }
 
 IMPOP_API int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_cluster_elapsed: ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ctx->cluster_timer.elapsed(total_ms, launches);
+    return ctx_timers_elapsed(ctx, impop_ctx::T_CLUSTER, 1, 0, total_ms, launches);
 }
 
 IMPOP_API int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_ehh_elapsed: ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ctx->ehh_timer.elapsed(total_ms, launches);
+    return ctx_timers_elapsed(ctx, impop_ctx::T_EHH, 1, 0, total_ms, launches);
 }
 
 IMPOP_API int impop_ctx_synchronize(impop_ctx *ctx) {

@@ -18,7 +18,7 @@
 //                         closes the leading and trailing run against the window's edges, writes the individual's row and adds
 //                         it to the window's integers in LDS.  het_total is taken from the tiles' own count and compared with
 //                         the rows' sum; every row's run lengths + het must give the window's length: else the device error word.
-// The doubles of a record are computed on the host from its integers, in one place.
+// The doubles of a record are computed on the host from its integers, in one place.  Chunks: win_chunks.h / chunk_run.h.
 #include <string.h>
 
 #include <algorithm>
@@ -30,6 +30,7 @@
 #include "internal.h"
 #include "sb64.h"
 #include "scan_route.h"
+#include "win_chunks.h"
 
 namespace impop {
 
@@ -224,63 +225,6 @@ __global__ __launch_bounds__(DIP_T) void dip_window_kernel(const DipSummary *__r
     if (s_bad || s_tile_het != s_het) atomicOr(err, DEV_ERR_DIPLOID);
 }
 
-// one chunk of windows: its tiles (each once, ascending) and its windows over them
-struct DipChunk {
-    uint64_t w_begin = 0, w_end = 0;
-    std::vector<ScanTile> tiles;
-    std::vector<DipWin> wins;
-    uint64_t bytes_streamed = 0;
-};
-
-// Windows in order, cut where the chunk's device bytes — per tile N summaries and the totals, per window the record, the
-// descriptor and (if wanted) N rows — would pass the budget.  A window alone may exceed it.
-static void dip_plan_chunks(const impop_matrix *m, const ScanRoute &rt, const impop_window *windows, uint64_t n_windows, uint32_t N,
-                            bool want_ind, uint64_t budget, std::vector<DipChunk> &out) {
-    const uint32_t wps = m->g.wps;
-    const uint64_t per_tile = (uint64_t)N * sizeof(DipSummary) + sizeof(DipTileTotals) + sizeof(ScanTile);
-    const uint64_t per_win = sizeof(impop_diploid_stats) + sizeof(DipWin) + (want_ind ? (uint64_t)N * sizeof(impop_diploid_ind) : 0);
-    std::vector<uint32_t> seen(rt.tiles.size(), 0u), local(rt.tiles.size(), 0u);
-    std::vector<uint64_t> used;
-    uint64_t i = 0;
-    while (i < n_windows) {
-        DipChunk c;
-        c.w_begin = i;
-        const uint32_t stamp = (uint32_t)out.size() + 1;
-        used.clear();
-        uint64_t bytes = 0;
-        for (; i < n_windows; ++i) {
-            const WinDesc &w = rt.wins[i];
-            uint64_t fresh = 0;
-            for (uint64_t t = w.t0; t < w.t1; ++t) fresh += seen[t] != stamp;
-            const uint64_t add = fresh * per_tile + per_win;
-            if (i > c.w_begin && bytes + add > budget) break;
-            for (uint64_t t = w.t0; t < w.t1; ++t)
-                if (seen[t] != stamp) {
-                    seen[t] = stamp;
-                    used.push_back(t);
-                }
-            bytes += add;
-        }
-        c.w_end = i;
-        std::sort(used.begin(), used.end());  // ascending: every window's tile range stays contiguous
-        c.tiles.reserve(used.size());
-        for (size_t k = 0; k < used.size(); ++k) {
-            const ScanTile &t = rt.tiles[used[k]];
-            local[used[k]] = (uint32_t)k;
-            c.tiles.push_back(t);
-            c.bytes_streamed += ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps;
-        }
-        c.wins.reserve(c.w_end - c.w_begin);
-        for (uint64_t k = c.w_begin; k < c.w_end; ++k) {
-            const WinDesc &w = rt.wins[k];
-            const uint32_t l0 = w.t1 > w.t0 ? local[w.t0] : 0u, cnt = (uint32_t)(w.t1 - w.t0);
-            c.wins.push_back(DipWin{windows[k].site_begin, windows[k].site_end, l0, l0 + cnt,
-                                    (uint32_t)window_W(m, windows[k].site_begin, windows[k].site_end), 0u});
-        }
-        out.push_back(std::move(c));
-    }
-}
-
 // The tile of scan.hip's streaming kernels: ~256 KB of matrix per workgroup, at least 16 tiles per CU wanted, never below 32
 // blocks (wide sites: 4).  IMPOP_DIPLOID_TILE_BLOCKS=n (1..4096) overrides it, so that tests reach many-tile windows on small
 // matrices.
@@ -331,9 +275,7 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
     if (rc) return rc;
     if (!n_windows) return IMPOP_OK;
     REQUIRE(windows && out_host, "%s: NULL windows/out", fn);
-    for (uint64_t i = 0; i < n_windows; ++i)
-        REQUIRE(window_W(m, windows[i].site_begin, windows[i].site_end) <= 0xFFFFFFFFull,
-                "%s: window %llu: the weights of its columns add up to 2^32 or more; split the window", fn, (unsigned long long)i);
+    if ((rc = check_window_weights(fn, m, windows, n_windows))) return rc;
 
     // the rows of the matrix itself, whatever index was built beside them
     ScanRoute rt;
@@ -342,14 +284,14 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
     rt.tile_blocks = dip_tile_blocks(ctx, m, rt.mapped);
     build_tiles(rt, n_windows, wps);
 
-    const uint64_t budget = params->max_chunk_bytes ? params->max_chunk_bytes : (1ull << 30);
-    std::vector<DipChunk> chunks;
-    dip_plan_chunks(m, rt, windows, n_windows, N, ind_out != nullptr, budget, chunks);
-    size_t max_tiles = 1, max_wins = 1;
-    for (const DipChunk &c : chunks) {
-        max_tiles = std::max(max_tiles, c.tiles.size());
-        max_wins = std::max(max_wins, c.wins.size());
-    }
+    // device bytes of a chunk: per tile N summaries, the totals and the tile; per window the record, the descriptor and (if
+    // wanted) N rows
+    const TileCosts costs{(uint64_t)N * sizeof(DipSummary) + sizeof(DipTileTotals) + sizeof(ScanTile),
+                          sizeof(impop_diploid_stats) + sizeof(DipWin) + (ind_out ? (uint64_t)N * sizeof(impop_diploid_ind) : 0), 0};
+    const std::vector<TiledChunk> chunks =
+        plan_tiled_chunks(rt.wins.data(), n_windows, rt.tiles.size(), chunk_budget(params->max_chunk_bytes), 0, costs);
+    const size_t max_tiles = max_over(chunks, [](const TiledChunk &c) { return c.tiles.size(); }),
+                 max_wins = max_over(chunks, [](const TiledChunk &c) { return c.w_end - c.w_begin; });
     REQUIRE(max_tiles < 0x7FFFFFFFull && max_wins < 0x7FFFFFFFull, "%s: a chunk of %zu tiles / %zu windows exceeds one launch", fn, max_tiles,
             max_wins);
     REQUIRE((uint64_t)max_tiles * N * sizeof(DipSummary) <= (64ull << 30), "%s: a window needs %llu MiB of tile summaries", fn,
@@ -368,17 +310,17 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
     if (rc) return rc;
     rc = ctx_pinned(ctx, staged, &pin);
     if (rc) return rc;
-    char *dc = (char *)d, *hc = (char *)pin;
+    const ChunkRun run{ctx, fn, (char *)d, (char *)pin};
+    char *dc = run.dc, *hc = run.hc;
     memcpy(hc + o_ppos, ppos.data(), (size_t)n_pad * 4);
     memcpy(hc + o_pmask, pmask.data(), (size_t)wps * 4);
-    HIP_TRY(hipMemcpyAsync(dc, hc, o_fixed, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = run.up(0, o_fixed))) return rc;
 
     // waves of a tile workgroup: as many of 4 as the LDS holds summaries and words for (N <= 658: 4, N = 2048: 1)
     const size_t lds_wave = (size_t)N * (sizeof(DipSummary) + 16);
     const uint32_t n_waves = (uint32_t)std::max<size_t>(1, std::min<size_t>(DIP_T / 64, DIP_LDS_BUDGET / lds_wave));
     const size_t lds_tile = lds_wave * n_waves;
-    if (lds_tile > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)dip_tile_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile));
+    if ((rc = lds_opt_in(dip_tile_kernel, lds_tile))) return rc;
 
     const int32_t *d_ppos = (const int32_t *)(dc + o_ppos);
     const uint32_t *d_pmask = (const uint32_t *)(dc + o_pmask);
@@ -388,37 +330,37 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
     DipSummary *d_sum = (DipSummary *)(dc + o_sum);
     DipTileTotals *d_tot = (DipTileTotals *)(dc + o_tot);
     impop_diploid_ind *d_ind = ind_out ? (impop_diploid_ind *)(dc + o_ind) : nullptr;
+    ScanTile *h_tiles = (ScanTile *)(hc + o_tiles);
+    DipWin *h_wins = (DipWin *)(hc + o_wins);
+    EventPairs *timer = ctx->timers + impop_ctx::T_DIP;
     uint64_t launches = 0, bytes_streamed = 0, tiles_run = 0;
-    const bool timed = ctx->gram_timing;
-    for (const DipChunk &c : chunks) {
-        const size_t nt = c.tiles.size(), cnt = c.wins.size();
-        if (nt) memcpy(hc + o_tiles, c.tiles.data(), nt * sizeof(ScanTile));
-        memcpy(hc + o_wins, c.wins.data(), cnt * sizeof(DipWin));
-        // one copy from the tiles to the end of the windows (the staging mirrors the device offsets)
-        HIP_TRY(hipMemcpyAsync(dc + o_tiles, hc + o_tiles, o_rec - o_tiles, hipMemcpyHostToDevice, ctx->stream));
-        size_t slot = 0;
+    for (const TiledChunk &c : chunks) {
+        const size_t nt = c.tiles.size(), cnt = c.w_end - c.w_begin;
+        for (size_t k = 0; k < nt; ++k) {
+            h_tiles[k] = rt.tiles[c.tiles[k]];
+            bytes_streamed += tile_bytes_streamed(h_tiles[k], wps);  // tiles of build_tiles without an index: never empty, no rare entries
+        }
+        for (size_t k = 0; k < cnt; ++k) {
+            const impop_window &w = windows[c.w_begin + k];
+            const uint32_t l0 = c.l0[k], tiles_k = (uint32_t)(rt.wins[c.w_begin + k].t1 - rt.wins[c.w_begin + k].t0);
+            h_wins[k] = DipWin{w.site_begin, w.site_end, l0, l0 + tiles_k, (uint32_t)window_W(m, w.site_begin, w.site_end), 0u};
+        }
+        if ((rc = run.up(o_tiles, o_rec))) return rc;  // from the tiles to the end of the windows
         if (nt) {
-            if (timed && (rc = ctx->dip_timer[0].begin(ctx->stream, &slot))) return rc;
-            hipLaunchKernelGGL(dip_tile_kernel, dim3((uint32_t)nt), dim3(64 * n_waves), lds_tile, ctx->stream, m->d_sb,
-                               m->compact ? m->d_pos : nullptr, d_tiles, wps, m->g.G, m->g.r, d_ppos, d_pmask, N, min_run, d_sum, d_tot);
-            HIP_TRY(hipGetLastError());
-            if (timed && (rc = ctx->dip_timer[0].end(ctx->stream, slot))) return rc;
+            if ((rc = run.timed(timer[0], [&] {
+                hipLaunchKernelGGL(dip_tile_kernel, dim3((uint32_t)nt), dim3(64 * n_waves), lds_tile, ctx->stream, m->d_sb,
+                                   m->compact ? m->d_pos : nullptr, d_tiles, wps, m->g.G, m->g.r, d_ppos, d_pmask, N, min_run, d_sum, d_tot);
+            }))) return rc;
             ++launches;
         }
-        if (timed && (rc = ctx->dip_timer[1].begin(ctx->stream, &slot))) return rc;
-        hipLaunchKernelGGL(dip_window_kernel, dim3((uint32_t)cnt), dim3(DIP_T), 0, ctx->stream, d_sum, d_tot, d_wins,
-                           m->compact ? m->d_onesmap : nullptr, N, min_run, d_rec, d_ind, ctx->d_err);
-        HIP_TRY(hipGetLastError());
-        if (timed && (rc = ctx->dip_timer[1].end(ctx->stream, slot))) return rc;
+        if ((rc = run.timed(timer[1], [&] {
+            hipLaunchKernelGGL(dip_window_kernel, dim3((uint32_t)cnt), dim3(DIP_T), 0, ctx->stream, d_sum, d_tot, d_wins,
+                               m->compact ? m->d_onesmap : nullptr, N, min_run, d_rec, d_ind, ctx->d_err);
+        }))) return rc;
         ++launches;
-        HIP_TRY(hipMemcpyAsync(hc + o_rec, d_rec, cnt * sizeof(impop_diploid_stats), hipMemcpyDeviceToHost, ctx->stream));
         if (ind_out)
             HIP_TRY(hipMemcpyAsync(ind_out + c.w_begin * N, d_ind, cnt * N * sizeof(impop_diploid_ind), hipMemcpyDeviceToHost, ctx->stream));
-        rc = ctx_err_fetch(ctx);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging is reused by the next chunk
-        rc = ctx_err_result(ctx, fn);
-        if (rc) return rc;
+        if ((rc = run.finish(o_rec, o_rec + cnt * sizeof(impop_diploid_stats)))) return rc;
         const impop_diploid_stats *rv = (const impop_diploid_stats *)(hc + o_rec);
         const double nan = __builtin_nan("");
         for (size_t k = 0; k < cnt; ++k) {
@@ -431,7 +373,6 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
             o.f_roh = W == 0 ? nan : (double)o.roh_sites_total / ((double)N * (double)W);
             out_host[c.w_begin + k] = o;
         }
-        bytes_streamed += c.bytes_streamed;
         tiles_run += nt;
     }
     if (trace_on()) {
@@ -445,11 +386,5 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
 
 IMPOP_API int impop_ctx_diploid_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks) {
     REQUIRE(ctx && kernel_ms, "impop_ctx_diploid_elapsed: NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 2; ++k) {
-        const int rc = ctx->dip_timer[k].elapsed(&kernel_ms[k], k == 1 ? chunks : nullptr);
-        if (rc) return rc;
-    }
-    return IMPOP_OK;
+    return ctx_timers_elapsed(ctx, impop_ctx::T_DIP, 2, 1, kernel_ms, chunks);
 }

@@ -241,7 +241,6 @@ IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impo
     if (rc) return rc;
     const uint32_t *weights = m->d_wt && !rt.indexed ? m->d_wt : nullptr;  // weighted matrices stream their rows
     const int polarize = params->polarize != 0;
-    const bool timed = ctx->gram_timing;
     uint64_t launches = 0;
     // the quartet list in groups of DSTAT_QG: the same tiles, the partials reused (the launches of a stream run in order)
     for (uint32_t q0 = 0; q0 < Q; q0 += DSTAT_QG) {
@@ -249,14 +248,13 @@ IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impo
         DstatGroup grp;
         for (uint32_t j = 0; j < (uint32_t)DSTAT_QG; ++j) grp.q[j] = qs[q0 + (j < nq ? j : 0)];  // a short group repeats its first quartet
         if (nt) {
-            size_t slot = 0;
-            if (timed && (rc = ctx->dstat_timer.begin(ctx->stream, &slot))) return rc;
-            rc = pop_dispatch_k<4>(K, [&](auto k) {
-                return weights ? pop_launch(dstat_tiles_kernel<k.value, true>, K, ctx->stream, m, rt, dev, weights, grp, nq, polarize, dp)
-                               : pop_launch(dstat_tiles_kernel<k.value, false>, K, ctx->stream, m, rt, dev, weights, grp, nq, polarize, dp);
+            rc = timed(ctx, ctx->timers[impop_ctx::T_DSTAT], [&] {
+                return pop_dispatch_k<4>(K, [&](auto k) {
+                    return weights ? pop_launch(dstat_tiles_kernel<k.value, true>, K, ctx->stream, m, rt, dev, weights, grp, nq, polarize, dp)
+                                   : pop_launch(dstat_tiles_kernel<k.value, false>, K, ctx->stream, m, rt, dev, weights, grp, nq, polarize, dp);
+                });
             });
             if (rc) return rc;
-            if (timed && (rc = ctx->dstat_timer.end(ctx->stream, slot))) return rc;
             ++launches;
         }
         const uint64_t items = n_windows * nq;
@@ -293,7 +291,5 @@ IMPOP_API int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impo
 
 IMPOP_API int impop_ctx_dstat_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_dstat_elapsed: ctx is NULL");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    return ctx->dstat_timer.elapsed(total_ms, launches);
+    return ctx_timers_elapsed(ctx, impop_ctx::T_DSTAT, 1, 0, total_ms, launches);
 }

@@ -24,8 +24,10 @@
 #include <algorithm>
 #include <vector>
 
+#include "chunk_run.h"
 #include "device_utils.h"
 #include "internal.h"
+#include "win_chunks.h"
 
 namespace impop {
 
@@ -367,10 +369,7 @@ IMPOP_API int impop_ehh(impop_ctx *ctx, const impop_matrix *m, uint64_t site_beg
     NOT_COMPACT(m, "impop_ehh");
     REQUIRE(site_begin <= site_end && site_end <= m->g.n_site, "impop_ehh: bad site range");
     HIP_TRY(hipSetDevice(ctx->device));
-    const uint32_t n = m->g.n_hap;
-    std::vector<uint32_t> idx;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!mask || ((mask[i >> 6] >> (i & 63)) & 1ull)) idx.push_back(i);
+    const std::vector<uint32_t> idx = member_set(mask, m->g.n_hap, m->g.wps).idx;
     const uint32_t mm = (uint32_t)idx.size();
     if (n_members) *n_members = mm;
     const uint64_t W = site_end - site_begin;
@@ -420,14 +419,8 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
             "impop_ehh_scan: unknown flanks mode %d", params->flanks);
     const uint32_t n = m->g.n_hap, n_pad = m->g.wps * 32;
     REQUIRE(params->ref_hap < n, "impop_ehh_scan: ref_hap %u is not one of the %u haplotypes", params->ref_hap, n);
-    std::vector<uint32_t> idx;
-    std::vector<int32_t> ppos(n_pad, -1);
-    for (uint32_t i = 0; i < n; ++i)
-        if (!mask_p || ((mask_p[i >> 6] >> (i & 63)) & 1ull)) {
-            ppos[i] = (int32_t)idx.size();
-            idx.push_back(i);
-        }
-    const uint32_t nP = (uint32_t)idx.size();
+    const MemberSet P = member_set(mask_p, n, m->g.wps);
+    const uint32_t nP = P.size();
     if (nP > IMPOP_EHH_SCAN_MAX_N) {
         set_error("impop_ehh_scan: %u members exceed the LDS-resident refinement limit (%u); impop_ehh takes one window of up to 65535",
                   nP, (uint32_t)IMPOP_EHH_SCAN_MAX_N);
@@ -445,26 +438,22 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
 
     // the windows' transposed blocks and the chunks they fall into (by scratch bytes; blockIdx.y holds 65535 windows)
     const uint32_t stride = nP ? nP : 1;
-    const uint64_t budget = params->max_chunk_bytes ? params->max_chunk_bytes : (1ull << 30);
-    std::vector<EhhWin> meta(n_windows);
-    std::vector<uint64_t> chunk_begin{0};
-    uint64_t used = 0, max_words = 0, max_cnt = 0;
+    const bool after_core = params->flanks == IMPOP_EHH_FLANKS_REFERENCE;  // the transposed range starts behind the core
+    std::vector<uint32_t> nblk(n_windows);
     for (uint64_t i = 0; i < n_windows; ++i) {
-        const impop_ehh_window &wv = windows[i];
-        const uint64_t tb = params->flanks == IMPOP_EHH_FLANKS_REFERENCE ? wv.core_site + 1 : wv.site_begin, te = wv.site_end;
-        const uint64_t nblk = (nP && te > tb) ? ((te + 63) >> 6) - (tb >> 6) : 0;
-        REQUIRE(nblk < 0x7FFFFFFFull, "impop_ehh_scan: window %llu too long", (unsigned long long)i);
-        const uint64_t words = nblk * stride;
-        if (i > chunk_begin.back() && ((used + words) * 8 > budget || i - chunk_begin.back() == 65535)) {
-            chunk_begin.push_back(i);
-            used = 0;
-        }
-        meta[i] = EhhWin{wv.site_begin, wv.site_end, wv.core_site, used, tb >> 6, (uint32_t)nblk, 0};
-        used += words;
-        max_words = std::max(max_words, used);
-        max_cnt = std::max(max_cnt, i + 1 - chunk_begin.back());
+        const uint64_t tb = after_core ? windows[i].core_site + 1 : windows[i].site_begin, te = windows[i].site_end;
+        const uint64_t nb = (nP && te > tb) ? ((te + 63) >> 6) - (tb >> 6) : 0;
+        REQUIRE(nb < 0x7FFFFFFFull, "impop_ehh_scan: window %llu too long", (unsigned long long)i);
+        nblk[i] = (uint32_t)nb;
     }
-    chunk_begin.push_back(n_windows);
+    const std::vector<WinChunk> chunks = cut_windows(n_windows, chunk_budget(params->max_chunk_bytes), 65535,
+                                                     [&](size_t, uint64_t i) { return (uint64_t)nblk[i] * stride * 8; });
+    const size_t max_cnt = max_over(chunks, [](const WinChunk &c) { return c.w_end - c.w_begin; }),
+                 max_words = max_over(chunks, [&](const WinChunk &c) {
+                     uint64_t words = 0;
+                     for (uint64_t i = c.w_begin; i < c.w_end; ++i) words += (uint64_t)nblk[i] * stride;
+                     return words;
+                 }, 0);
     REQUIRE(max_words * 8 <= (64ull << 30), "impop_ehh_scan: a window needs %llu MiB of transposed scratch",
             (unsigned long long)(max_words >> 17));
 
@@ -477,49 +466,45 @@ IMPOP_API int impop_ehh_scan(impop_ctx *ctx, const impop_matrix *m, const impop_
     if (rc) return rc;
     rc = ctx_pinned(ctx, staged, &pin);
     if (rc) return rc;
-    char *dc = (char *)d, *hc = (char *)pin;
-    if (nP) memcpy(hc + o_idx, idx.data(), (size_t)nP * 4);
-    memcpy(hc + o_ppos, ppos.data(), (size_t)n_pad * 4);
-    HIP_TRY(hipMemcpyAsync(dc, hc, o_win, hipMemcpyHostToDevice, ctx->stream));
+    const ChunkRun run{ctx, "impop_ehh_scan", (char *)d, (char *)pin};
+    char *dc = run.dc, *hc = run.hc;
+    if (nP) memcpy(hc + o_idx, P.idx.data(), (size_t)nP * 4);
+    memcpy(hc + o_ppos, P.ppos.data(), (size_t)n_pad * 4);
+    if ((rc = run.up(0, o_win))) return rc;
     const uint32_t mcap = (nP + 1) & ~1u;
     const size_t lds = (size_t)(mcap ? mcap : 2) * 12;
 
-    for (size_t c = 0; c + 1 < chunk_begin.size(); ++c) {
-        const uint64_t base = chunk_begin[c], cnt = chunk_begin[c + 1] - base;
-        uint32_t max_blk = 0;
-        uint64_t words = 0;
+    EhhWin *h_wins = (EhhWin *)(hc + o_win);
+    for (size_t c = 0; c < chunks.size(); ++c) {
+        const uint64_t base = chunks[c].w_begin, cnt = chunks[c].w_end - base;
+        uint32_t max_blk = 0, launches = 0;
+        uint64_t words = 0;  // so far: every window's word offset inside its chunk
         for (uint64_t k = 0; k < cnt; ++k) {
-            max_blk = std::max(max_blk, meta[base + k].n_blk);
-            words += (uint64_t)meta[base + k].n_blk * stride;
+            const impop_ehh_window &wv = windows[base + k];
+            const uint32_t nb = nblk[base + k];
+            h_wins[k] = EhhWin{wv.site_begin, wv.site_end, wv.core_site, words, (after_core ? wv.core_site + 1 : wv.site_begin) >> 6, nb, 0};
+            max_blk = std::max(max_blk, nb);
+            words += (uint64_t)nb * stride;
         }
-        memcpy(hc + o_win, &meta[base], cnt * sizeof(EhhWin));
-        HIP_TRY(hipMemcpyAsync(dc + o_win, hc + o_win, cnt * sizeof(EhhWin), hipMemcpyHostToDevice, ctx->stream));
-        size_t slot = 0;  // the chunk's kernels between two events of their own: impop_ctx_ehh_elapsed
-        if (ctx->gram_timing && (rc = ctx->ehh_timer.begin(ctx->stream, &slot))) return rc;
-        uint32_t launches = 0;
-        if (max_blk) {
-            hipLaunchKernelGGL(ehh_scan_transpose_kernel, dim3((max_blk + 3) / 4, (uint32_t)cnt), dim3(256), 0, ctx->stream, m->d_sb,
-                               m->g.wps, m->g.G, m->g.r, (const EhhWin *)(dc + o_win), (const int32_t *)(dc + o_ppos), stride,
-                               (uint64_t *)(dc + o_wm));
+        if ((rc = run.up(o_win, o_win + cnt * sizeof(EhhWin)))) return rc;
+        if ((rc = run.timed(ctx->timers[impop_ctx::T_EHH], [&] {  // the chunk's kernels between two events of their own: impop_ctx_ehh_elapsed
+            if (max_blk) {
+                hipLaunchKernelGGL(ehh_scan_transpose_kernel, dim3((max_blk + 3) / 4, (uint32_t)cnt), dim3(256), 0, ctx->stream, m->d_sb,
+                                   m->g.wps, m->g.G, m->g.r, (const EhhWin *)(dc + o_win), (const int32_t *)(dc + o_ppos), stride,
+                                   (uint64_t *)(dc + o_wm));
+                ++launches;
+            }
+            hipLaunchKernelGGL(ehh_refine_kernel, dim3((uint32_t)(cnt * 4)), dim3(EHH_ST), lds, ctx->stream, m->d_sb, m->g.wps, m->g.G,
+                               m->g.r, (const EhhWin *)(dc + o_win), (const uint32_t *)(dc + o_idx), nP, mcap, params->flanks,
+                               params->ref_hap, (const uint64_t *)(dc + o_wm), stride, (impop_ehh_stats *)(dc + o_rec), ctx->d_err);
             ++launches;
-        }
-        hipLaunchKernelGGL(ehh_refine_kernel, dim3((uint32_t)(cnt * 4)), dim3(EHH_ST), lds, ctx->stream, m->d_sb, m->g.wps, m->g.G,
-                           m->g.r, (const EhhWin *)(dc + o_win), (const uint32_t *)(dc + o_idx), nP, mcap, params->flanks,
-                           params->ref_hap, (const uint64_t *)(dc + o_wm), stride, (impop_ehh_stats *)(dc + o_rec), ctx->d_err);
-        ++launches;
-        HIP_TRY(hipGetLastError());
-        if (ctx->gram_timing && (rc = ctx->ehh_timer.end(ctx->stream, slot))) return rc;
+        }))) return rc;
         if (trace_on()) {
             fprintf(stderr, "[impop_ehh_scan] windows=%llu problems=%llu chunk=%llu launches=%u scratch_bytes=%llu\n",
                     (unsigned long long)cnt, (unsigned long long)(cnt * 4), (unsigned long long)c, launches, (unsigned long long)(words * 8));
             fflush(stderr);
         }
-        HIP_TRY(hipMemcpyAsync(hc + o_rec, dc + o_rec, cnt * sizeof(impop_ehh_stats), hipMemcpyDeviceToHost, ctx->stream));
-        rc = ctx_err_fetch(ctx);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging is reused by the next chunk
-        rc = ctx_err_result(ctx, "impop_ehh_scan");
-        if (rc) return rc;
+        if ((rc = run.finish(o_rec, o_rec + cnt * sizeof(impop_ehh_stats)))) return rc;
         const impop_ehh_stats *rv = (const impop_ehh_stats *)(hc + o_rec);
         for (uint64_t k = 0; k < cnt; ++k) {
             impop_ehh_stats o = rv[k];

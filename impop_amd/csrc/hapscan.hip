@@ -14,7 +14,7 @@
 //                              every member at every site.  A fingerprint is never trusted: a mismatch flags the window.
 //   4. hap_exact_kernel        flagged windows only (a fingerprint collision: in practice never): greedy equality grouping
 //                              against the smallest unassigned member, one streaming pass per class, then the same record.
-// The doubles of a record are computed on the host from its integers, in one place.
+// The doubles of a record are computed on the host from its integers, in one place.  Chunks: win_chunks.h / chunk_run.h.
 #include <string.h>
 
 #include <algorithm>
@@ -26,6 +26,7 @@
 #include "internal.h"
 #include "sb64.h"
 #include "scan_route.h"
+#include "win_chunks.h"
 
 namespace impop {
 
@@ -352,68 +353,6 @@ static uint32_t hapscan_key_bits() {
     return v < 1 ? 1u : v > 128 ? 128u : (uint32_t)v;
 }
 
-template <typename K>
-static int hap_lds_opt_in(K kernel, size_t lds) {
-    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    return IMPOP_OK;
-}
-
-// one chunk of windows: its tiles (each once, ascending), its windows over them, the verify kernel's work list
-struct HapChunk {
-    uint64_t w_begin = 0, w_end = 0;
-    std::vector<ScanTile> tiles;
-    std::vector<HapWin> wins;
-    std::vector<HapItem> items;
-    uint64_t bytes_streamed = 0;
-};
-
-// Windows in order, cut where the chunk's device bytes — 16 nP per tile of fingerprints, 12 nP per window of tables, 8 per item —
-// would pass the budget.  A window alone may exceed it.
-static void hap_plan_chunks(const ScanRoute &rt, uint64_t n_windows, uint32_t nP, uint32_t wps, uint64_t budget, std::vector<HapChunk> &out) {
-    const uint64_t per_tile = 16ull * nP, per_win = 12ull * nP + sizeof(impop_haplotype_stats) + sizeof(HapWin) + 4;
-    std::vector<uint32_t> seen(rt.tiles.size(), 0u), local(rt.tiles.size(), 0u);
-    std::vector<uint64_t> used;
-    uint64_t i = 0;
-    while (i < n_windows) {
-        HapChunk c;
-        c.w_begin = i;
-        const uint32_t stamp = (uint32_t)out.size() + 1;
-        used.clear();
-        uint64_t bytes = 0;
-        for (; i < n_windows; ++i) {
-            const WinDesc &w = rt.wins[i];
-            uint64_t fresh = 0;
-            for (uint64_t t = w.t0; t < w.t1; ++t) fresh += seen[t] != stamp;
-            const uint64_t add = fresh * per_tile + per_win + (w.t1 - w.t0) * sizeof(HapItem);
-            if (i > c.w_begin && bytes + add > budget) break;
-            for (uint64_t t = w.t0; t < w.t1; ++t)
-                if (seen[t] != stamp) {
-                    seen[t] = stamp;
-                    used.push_back(t);
-                }
-            bytes += add;
-        }
-        c.w_end = i;
-        std::sort(used.begin(), used.end());  // ascending: every window's tile range stays contiguous
-        c.tiles.reserve(used.size());
-        for (size_t k = 0; k < used.size(); ++k) {
-            const ScanTile &t = rt.tiles[used[k]];
-            local[used[k]] = (uint32_t)k;
-            c.tiles.push_back(t);
-            c.bytes_streamed += (t.site_end > t.site_begin ? ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps : 0) +
-                                (t.rare_end - t.rare_begin) * 8ull;
-        }
-        c.wins.reserve(c.w_end - c.w_begin);
-        for (uint64_t k = c.w_begin; k < c.w_end; ++k) {
-            const WinDesc &w = rt.wins[k];
-            const uint32_t l0 = w.t1 > w.t0 ? local[w.t0] : 0u, cnt = (uint32_t)(w.t1 - w.t0);
-            c.wins.push_back(HapWin{l0, l0 + cnt, (uint32_t)w.n_sites, 0u});
-            for (uint32_t t = 0; t < cnt; ++t) c.items.push_back(HapItem{(uint32_t)(k - c.w_begin), l0 + t});
-        }
-        out.push_back(std::move(c));
-    }
-}
-
 }  // namespace impop
 
 using namespace impop;
@@ -425,16 +364,9 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
     REQUIRE(ctx && m && params, "impop_haplotype_scan: NULL argument");
     REQUIRE(params->struct_size == sizeof(impop_haplotype_params), "impop_haplotype_params.struct_size mismatch");
     REQUIRE(m->device == ctx->device, "impop_haplotype_scan: matrix lives on device %d, context on %d", m->device, ctx->device);
-    const uint32_t n = m->g.n_hap, wps = m->g.wps, n_pad = wps * 32;
-    std::vector<uint32_t> idx, pmask(wps, 0u);
-    std::vector<int32_t> ppos(n_pad, -1);
-    for (uint32_t i = 0; i < n; ++i)
-        if (!mask_p || ((mask_p[i >> 6] >> (i & 63)) & 1ull)) {
-            ppos[i] = (int32_t)idx.size();
-            pmask[i >> 5] |= 1u << (i & 31);
-            idx.push_back(i);
-        }
-    const uint32_t nP = (uint32_t)idx.size();
+    const uint32_t wps = m->g.wps, n_pad = wps * 32;
+    const MemberSet P = member_set(mask_p, m->g.n_hap, wps);
+    const uint32_t nP = P.size();
     REQUIRE(nP > 0, "impop_haplotype_scan: the mask selects no haplotype");
     if (nP > IMPOP_HAPLOTYPE_MAX_N) {
         set_error("impop_haplotype_scan: %u members exceed the LDS-resident grouping limit (%u)", nP, (uint32_t)IMPOP_HAPLOTYPE_MAX_N);
@@ -449,15 +381,13 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
     rc = scan_route("impop_haplotype_scan", ctx, m, windows, n_windows, 0, rt);
     if (rc) return rc;
 
-    const uint64_t budget = params->max_chunk_bytes ? params->max_chunk_bytes : (1ull << 30);
-    std::vector<HapChunk> chunks;
-    hap_plan_chunks(rt, n_windows, nP, wps, budget, chunks);
-    size_t max_tiles = 1, max_wins = 1, max_items = 1;
-    for (const HapChunk &c : chunks) {
-        max_tiles = std::max(max_tiles, c.tiles.size());
-        max_wins = std::max(max_wins, c.wins.size());
-        max_items = std::max(max_items, c.items.size());
-    }
+    // device bytes of a chunk: 16 nP per tile of fingerprints, 12 nP per window of tables, 8 per item of the verify kernel
+    const TileCosts costs{16ull * nP, 12ull * nP + sizeof(impop_haplotype_stats) + sizeof(HapWin) + 4, sizeof(HapItem)};
+    const std::vector<TiledChunk> chunks =
+        plan_tiled_chunks(rt.wins.data(), n_windows, rt.tiles.size(), chunk_budget(params->max_chunk_bytes), 0, costs);
+    const size_t max_tiles = max_over(chunks, [](const TiledChunk &c) { return c.tiles.size(); }),
+                 max_wins = max_over(chunks, [](const TiledChunk &c) { return c.w_end - c.w_begin; }),
+                 max_items = max_over(chunks, [](const TiledChunk &c) { return c.items; });
     REQUIRE(max_tiles < 0x7FFFFFFFull && max_items < 0x7FFFFFFFull && max_wins < 0x7FFFFFFFull,
             "impop_haplotype_scan: a chunk of %zu tiles / %zu window tiles exceeds one launch", max_tiles, max_items);
     REQUIRE((uint64_t)max_tiles * 16ull * nP <= (64ull << 30), "impop_haplotype_scan: a window needs %llu MiB of tile fingerprints",
@@ -465,7 +395,6 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
 
     // device: idx | ppos | pmask | tiles | windows | items (up, through the page-locked staging with the same offsets) |
     // records | flags (down, staged) | fingerprints | rep-and-size, class_of, sizes tables
-    const bool want_tables = class_of || sizes;
     Carve L;
     const size_t o_idx = L.take<uint32_t>(nP), o_ppos = L.take<int32_t>(n_pad), o_pmask = L.take<uint32_t>(wps), o_fixed = L.total(),
                  o_tiles = L.take<ScanTile>(max_tiles), o_wins = L.take<HapWin>(max_wins), o_items = L.take<HapItem>(max_items),
@@ -477,17 +406,18 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
     if (rc) return rc;
     rc = ctx_pinned(ctx, staged, &pin);
     if (rc) return rc;
-    char *dc = (char *)d, *hc = (char *)pin;
-    memcpy(hc + o_idx, idx.data(), (size_t)nP * 4);
-    memcpy(hc + o_ppos, ppos.data(), (size_t)n_pad * 4);
-    memcpy(hc + o_pmask, pmask.data(), (size_t)wps * 4);
-    HIP_TRY(hipMemcpyAsync(dc, hc, o_fixed, hipMemcpyHostToDevice, ctx->stream));
+    const ChunkRun run{ctx, "impop_haplotype_scan", (char *)d, (char *)pin};
+    char *dc = run.dc, *hc = run.hc;
+    memcpy(hc + o_idx, P.idx.data(), (size_t)nP * 4);
+    memcpy(hc + o_ppos, P.ppos.data(), (size_t)n_pad * 4);
+    memcpy(hc + o_pmask, P.bits.data(), (size_t)wps * 4);
+    if ((rc = run.up(0, o_fixed))) return rc;
 
     const uint32_t T = std::max<uint32_t>(64, pow2_at_least(2 * nP));
     const size_t lds_fp = (size_t)nP * 16, lds_cls = (size_t)nP * 20 + (size_t)T * 8, lds_ver = (size_t)nP * 36,
                  lds_exact = (size_t)nP * 16 + (size_t)pow2_at_least(nP) * 4;
-    if ((rc = hap_lds_opt_in(hap_fingerprint_kernel, lds_fp)) || (rc = hap_lds_opt_in(hap_classify_kernel, lds_cls)) ||
-        (rc = hap_lds_opt_in(hap_verify_kernel, lds_ver)) || (rc = hap_lds_opt_in(hap_exact_kernel, lds_exact)))
+    if ((rc = lds_opt_in(hap_fingerprint_kernel, lds_fp)) || (rc = lds_opt_in(hap_classify_kernel, lds_cls)) ||
+        (rc = lds_opt_in(hap_verify_kernel, lds_ver)) || (rc = lds_opt_in(hap_exact_kernel, lds_exact)))
         return rc;
     const uint32_t bits = hapscan_key_bits();
     const uint64_t mask_lo = bits >= 64 ? ~0ull : (1ull << bits) - 1ull;
@@ -500,49 +430,49 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
     impop_haplotype_stats *d_rec = (impop_haplotype_stats *)(dc + o_rec);
     uint32_t *d_flags = (uint32_t *)(dc + o_flags), *d_repsz = (uint32_t *)(dc + o_repsz);
     uint32_t *d_cls = class_of ? (uint32_t *)(dc + o_cls) : nullptr, *d_sz = sizes ? (uint32_t *)(dc + o_sz) : nullptr;
+    ScanTile *h_tiles = (ScanTile *)(hc + o_tiles);
+    HapWin *h_wins = (HapWin *)(hc + o_wins);
+    HapItem *h_items = (HapItem *)(hc + o_items);
+    EventPairs *timer = ctx->timers + impop_ctx::T_HAP;
     uint64_t launches = 0, collided = 0, bytes_streamed = 0, tiles_run = 0;
-    const bool timed = ctx->gram_timing;
-    for (const HapChunk &c : chunks) {
-        const size_t nt = c.tiles.size(), cnt = c.wins.size(), ni = c.items.size();
-        if (nt) memcpy(hc + o_tiles, c.tiles.data(), nt * sizeof(ScanTile));
-        memcpy(hc + o_wins, c.wins.data(), cnt * sizeof(HapWin));
-        if (ni) memcpy(hc + o_items, c.items.data(), ni * sizeof(HapItem));
-        // one copy from tiles to the end of the items (the staging mirrors the device offsets)
-        HIP_TRY(hipMemcpyAsync(dc + o_tiles, hc + o_tiles, o_rec - o_tiles, hipMemcpyHostToDevice, ctx->stream));
+    for (const TiledChunk &c : chunks) {
+        const size_t nt = c.tiles.size(), cnt = c.w_end - c.w_begin, ni = c.items;
+        for (size_t k = 0; k < nt; ++k) {
+            h_tiles[k] = rt.tiles[c.tiles[k]];
+            bytes_streamed += tile_bytes_streamed(h_tiles[k], wps);
+        }
+        for (size_t k = 0, item = 0; k < cnt; ++k) {
+            const WinDesc &w = rt.wins[c.w_begin + k];
+            const uint32_t l0 = c.l0[k], tiles_k = (uint32_t)(w.t1 - w.t0);
+            h_wins[k] = HapWin{l0, l0 + tiles_k, (uint32_t)w.n_sites, 0u};
+            for (uint32_t t = 0; t < tiles_k; ++t) h_items[item++] = HapItem{(uint32_t)k, l0 + t};
+        }
+        if ((rc = run.up(o_tiles, o_rec))) return rc;  // from the tiles to the end of the items
         HIP_TRY(hipMemsetAsync(d_flags, 0, cnt * 4, ctx->stream));
-        size_t slot = 0;
         if (nt) {
-            if (timed && (rc = ctx->hap_timer[0].begin(ctx->stream, &slot))) return rc;
-            hipLaunchKernelGGL(hap_fingerprint_kernel, dim3((uint32_t)nt), dim3(HAP_T), lds_fp, ctx->stream, rt.sb, rt.rare, d_tiles, wps,
-                               m->g.G, m->g.r, d_ppos, d_pmask, n_pad, nP, (uint64_t *)(dc + o_fp));
-            HIP_TRY(hipGetLastError());
-            if (timed && (rc = ctx->hap_timer[0].end(ctx->stream, slot))) return rc;
+            if ((rc = run.timed(timer[0], [&] {
+                hipLaunchKernelGGL(hap_fingerprint_kernel, dim3((uint32_t)nt), dim3(HAP_T), lds_fp, ctx->stream, rt.sb, rt.rare, d_tiles, wps,
+                                   m->g.G, m->g.r, d_ppos, d_pmask, n_pad, nP, (uint64_t *)(dc + o_fp));
+            }))) return rc;
             ++launches;
         }
-        if (timed && (rc = ctx->hap_timer[1].begin(ctx->stream, &slot))) return rc;
-        hipLaunchKernelGGL(hap_classify_kernel, dim3((uint32_t)cnt), dim3(HAP_T), lds_cls, ctx->stream, (const uint64_t *)(dc + o_fp), d_wins,
-                           nP, T, mask_lo, mask_hi, d_rec, d_repsz, d_cls, d_sz, ctx->d_err);
-        HIP_TRY(hipGetLastError());
-        if (timed && (rc = ctx->hap_timer[1].end(ctx->stream, slot))) return rc;
+        if ((rc = run.timed(timer[1], [&] {
+            hipLaunchKernelGGL(hap_classify_kernel, dim3((uint32_t)cnt), dim3(HAP_T), lds_cls, ctx->stream, (const uint64_t *)(dc + o_fp),
+                               d_wins, nP, T, mask_lo, mask_hi, d_rec, d_repsz, d_cls, d_sz, ctx->d_err);
+        }))) return rc;
         ++launches;
         if (ni) {
-            if (timed && (rc = ctx->hap_timer[2].begin(ctx->stream, &slot))) return rc;
-            hipLaunchKernelGGL(hap_verify_kernel, dim3((uint32_t)ni), dim3(HAP_T), lds_ver, ctx->stream, rt.sb, rt.rare, d_tiles,
-                               (const HapItem *)(dc + o_items), wps, m->g.G, m->g.r, d_ppos, d_pmask, n_pad, nP, d_rec, d_repsz, d_flags);
-            hipLaunchKernelGGL(hap_exact_kernel, dim3((uint32_t)cnt), dim3(HAP_T), lds_exact, ctx->stream, rt.sb, rt.rare, d_tiles, d_wins, wps,
-                               m->g.G, m->g.r, d_ppos, d_pmask, d_idx, n_pad, nP, d_flags, d_rec, d_repsz, d_cls, d_sz, ctx->d_err);
-            HIP_TRY(hipGetLastError());
-            if (timed && (rc = ctx->hap_timer[2].end(ctx->stream, slot))) return rc;
+            if ((rc = run.timed(timer[2], [&] {
+                hipLaunchKernelGGL(hap_verify_kernel, dim3((uint32_t)ni), dim3(HAP_T), lds_ver, ctx->stream, rt.sb, rt.rare, d_tiles,
+                                   (const HapItem *)(dc + o_items), wps, m->g.G, m->g.r, d_ppos, d_pmask, n_pad, nP, d_rec, d_repsz, d_flags);
+                hipLaunchKernelGGL(hap_exact_kernel, dim3((uint32_t)cnt), dim3(HAP_T), lds_exact, ctx->stream, rt.sb, rt.rare, d_tiles, d_wins,
+                                   wps, m->g.G, m->g.r, d_ppos, d_pmask, d_idx, n_pad, nP, d_flags, d_rec, d_repsz, d_cls, d_sz, ctx->d_err);
+            }))) return rc;
             launches += 2;
         }
-        HIP_TRY(hipMemcpyAsync(hc + o_rec, dc + o_rec, staged - o_rec, hipMemcpyDeviceToHost, ctx->stream));  // records and flags
         if (class_of) HIP_TRY(hipMemcpyAsync(class_of + c.w_begin * nP, d_cls, cnt * nP * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (sizes) HIP_TRY(hipMemcpyAsync(sizes + c.w_begin * nP, d_sz, cnt * nP * 4, hipMemcpyDeviceToHost, ctx->stream));
-        rc = ctx_err_fetch(ctx);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging is reused by the next chunk
-        rc = ctx_err_result(ctx, "impop_haplotype_scan");
-        if (rc) return rc;
+        if ((rc = run.finish(o_rec, staged))) return rc;  // records and flags
         const impop_haplotype_stats *rv = (const impop_haplotype_stats *)(hc + o_rec);
         const uint32_t *fv = (const uint32_t *)(hc + o_flags);
         for (size_t k = 0; k < cnt; ++k) {
@@ -555,10 +485,8 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
             out_host[c.w_begin + k] = o;
             collided += fv[k] != 0;
         }
-        bytes_streamed += c.bytes_streamed;
         tiles_run += nt;
     }
-    (void)want_tables;
     if (trace_on()) {
         fprintf(stderr, "[impop_haplotype_scan] route=%s windows=%llu tiles=%llu chunks=%llu launches=%llu collided_windows=%llu bytes_streamed=%llu\n",
                 rt.indexed ? (rt.split ? "indexed+rare" : "indexed") : m->compact ? "compact" : "dense", (unsigned long long)n_windows,
@@ -571,11 +499,5 @@ IMPOP_API int impop_haplotype_scan(impop_ctx *ctx, const impop_matrix *m, const 
 
 IMPOP_API int impop_ctx_haplotype_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks) {
     REQUIRE(ctx && kernel_ms, "impop_ctx_haplotype_elapsed: NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) {
-        const int rc = ctx->hap_timer[k].elapsed(&kernel_ms[k], k == 1 ? chunks : nullptr);
-        if (rc) return rc;
-    }
-    return IMPOP_OK;
+    return ctx_timers_elapsed(ctx, impop_ctx::T_HAP, 3, 1, kernel_ms, chunks);
 }

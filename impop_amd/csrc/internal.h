@@ -132,15 +132,19 @@ struct impop_ctx {
     // invariant fails (stats.hip: the grouping's progress bound), the call that launched them returns IMPOP_E_INTERNAL
     uint32_t *d_err = nullptr;
     uint32_t h_err = 0;
-    // impop_ctx_gram_timing: one switch, three timers (impop::EventPairs) — around the Gram launch(es) of every chunk of
-    // impop_pairwise_scan / impop_cluster_scan (impop_ctx_gram_elapsed), the clustering kernel(s) of impop_cluster_scan
-    // (impop_ctx_cluster_elapsed) and the kernels of every chunk of impop_ehh_scan (impop_ctx_ehh_elapsed)
+    // impop_ctx_gram_timing: one switch, every timer (impop::EventPairs) in one array that reset and destroy walk
     bool gram_timing = false;
-    impop::EventPairs gram_timer, cluster_timer, ehh_timer;
-    impop::EventPairs hap_timer[3];  // impop_haplotype_scan: fingerprint / classify / verify + exact kernels (impop_ctx_haplotype_elapsed)
-    impop::EventPairs ld_timer[3];   // impop_ld_scan: select / gather / pairs kernels (impop_ctx_ld_elapsed)
-    impop::EventPairs dip_timer[2];  // impop_diploid_scan: tile / window kernels (impop_ctx_diploid_elapsed)
-    impop::EventPairs dstat_timer;   // impop_dstat_scan: the streaming launches (impop_ctx_dstat_elapsed)
+    enum Timer {
+        T_GRAM,              // the Gram launch(es) of every chunk of impop_pairwise_scan / impop_cluster_scan (impop_ctx_gram_elapsed)
+        T_CLUSTER,           // the clustering kernel(s) of impop_cluster_scan (impop_ctx_cluster_elapsed)
+        T_EHH,               // the kernels of every chunk of impop_ehh_scan (impop_ctx_ehh_elapsed)
+        T_HAP,               // impop_haplotype_scan: fingerprint / classify / verify + exact kernels (impop_ctx_haplotype_elapsed)
+        T_LD = T_HAP + 3,    // impop_ld_scan: select / gather / pairs kernels (impop_ctx_ld_elapsed)
+        T_DIP = T_LD + 3,    // impop_diploid_scan: tile / window kernels (impop_ctx_diploid_elapsed)
+        T_DSTAT = T_DIP + 2, // impop_dstat_scan: the streaming launches (impop_ctx_dstat_elapsed)
+        T_COUNT
+    };
+    impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
     // all-pairs path run next to each other instead of one after the other
     hipStream_t side = nullptr;
@@ -230,6 +234,9 @@ int ctx_scratch(impop_ctx *ctx, size_t bytes, void **out);
 int ctx_pinned(impop_ctx *ctx, size_t bytes, void **out);  // host, page-locked, grow-only; valid until the next larger request
 int ctx_err_fetch(impop_ctx *ctx);                 // enqueue its copy to the host (before the call's own stream sync)
 int ctx_err_result(impop_ctx *ctx, const char *fn);  // after that sync: IMPOP_OK, or IMPOP_E_INTERNAL (word cleared, message set)
+// the impop_ctx_*_elapsed readers: syncs the stream, then timers[first + k] -> kernel_ms[k] for k < n (kernel_ms nullable);
+// *count (nullable) = the completed pairs of timers[first + which]
+int ctx_timers_elapsed(impop_ctx *ctx, int first, int n, int which, double *kernel_ms, uint64_t *count);
 constexpr uint32_t DEV_ERR_GROUPING = 1u;            // greedy_groups_bits ran out of its progress bound
 constexpr uint32_t DEV_ERR_CLUSTER = 2u;             // af label propagation ran out of its rounds
 constexpr uint32_t DEV_ERR_HAPSCAN = 8u;             // haplotype scan: the classes of a window do not partition its members

@@ -23,6 +23,7 @@
 #include "internal.h"
 #include "sb64.h"
 #include "scan_route.h"
+#include "win_chunks.h"
 
 namespace impop {
 
@@ -234,11 +235,6 @@ __global__ __launch_bounds__(LD_T) void ld_pairs_kernel(const uint32_t *__restri
     rec[win] = out;
 }
 
-struct LdChunk {
-    uint64_t w_begin = 0, w_end = 0, n_blocks = 0, longest = 0;  // blocks of all its windows / of its longest one
-    std::vector<LdWin> wins;
-};
-
 }  // namespace impop
 
 using namespace impop;
@@ -251,13 +247,8 @@ IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_w
     REQUIRE(params->struct_size == sizeof(impop_ld_params), "impop_ld_params.struct_size mismatch");
     REQUIRE(m->device == ctx->device, "%s: matrix lives on device %d, context on %d", fn, m->device, ctx->device);
     const uint32_t n = m->g.n_hap, wps = m->g.wps;
-    std::vector<uint32_t> pbits(wps, 0u);
-    uint32_t nP = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!mask_p || ((mask_p[i >> 6] >> (i & 63)) & 1ull)) {
-            pbits[i >> 5] |= 1u << (i & 31);
-            ++nP;
-        }
+    const MemberSet P = member_set(mask_p, n, wps);
+    const uint32_t nP = P.size();
     REQUIRE(nP > 0, "%s: the mask selects no haplotype", fn);
     REQUIRE(params->min_mac >= 1, "%s: min_mac must be at least 1", fn);
     const uint32_t max_sites = params->max_sites ? params->max_sites : 512u;
@@ -272,38 +263,25 @@ IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_w
     REQUIRE(windows && out_host, "%s: NULL windows/out", fn);
     std::vector<impop_window> mapped;
     map_windows(m, windows, n_windows, mapped);
-    for (uint64_t i = 0; i < n_windows; ++i)
-        REQUIRE(window_W(m, windows[i].site_begin, windows[i].site_end) <= 0xFFFFFFFFull,
-                "%s: window %llu: the weights of its columns add up to 2^32 or more; split the window", fn, (unsigned long long)i);
+    if ((rc = check_window_weights(fn, m, windows, n_windows))) return rc;
 
-    // windows in order, cut where the chunk's device bytes would pass the budget; a window alone may exceed it
-    const uint64_t budget = params->max_chunk_bytes ? params->max_chunk_bytes : (1ull << 30);
+    // a window's device bytes: its gathered rows, their c and coordinates, the record, the descriptor, (q, m), a mask per block
     const uint64_t per_win = (uint64_t)max_sites * (4ull * wps + 12) + sizeof(impop_ld_stats) + sizeof(LdWin) + 8;
-    std::vector<LdChunk> chunks;
+    std::vector<uint64_t> nb(n_windows);  // the 64-site blocks a window touches
     uint64_t bytes_streamed = 0;
-    for (uint64_t i = 0; i < n_windows;) {
-        LdChunk c;
-        c.w_begin = i;
-        uint64_t bytes = 0;
-        for (; i < n_windows; ++i) {
-            const uint64_t s0 = mapped[i].site_begin, s1 = mapped[i].site_end;
-            const uint64_t nb = s1 > s0 ? ((s1 + 63) >> 6) - (s0 >> 6) : 0;
-            const uint64_t add = per_win + nb * 8;
-            if (i > c.w_begin && bytes + add > budget) break;
-            bytes += add;
-            c.wins.push_back(LdWin{s0, s1, c.n_blocks, (uint32_t)window_W(m, windows[i].site_begin, windows[i].site_end), 0u});
-            c.n_blocks += nb;
-            c.longest = std::max(c.longest, nb);
-            bytes_streamed += nb * 256ull * wps;
-        }
-        c.w_end = i;
-        chunks.push_back(std::move(c));
+    for (uint64_t i = 0; i < n_windows; ++i) {
+        const uint64_t s0 = mapped[i].site_begin, s1 = mapped[i].site_end;
+        nb[i] = s1 > s0 ? ((s1 + 63) >> 6) - (s0 >> 6) : 0;
+        bytes_streamed += nb[i] * 256ull * wps;
     }
-    size_t max_wins = 1, max_blocks = 1;
-    for (const LdChunk &c : chunks) {
-        max_wins = std::max(max_wins, c.wins.size());
-        max_blocks = std::max<size_t>(max_blocks, c.n_blocks);
-    }
+    const std::vector<WinChunk> chunks =
+        cut_windows(n_windows, chunk_budget(params->max_chunk_bytes), 0, [&](size_t, uint64_t i) { return per_win + nb[i] * 8; });
+    const size_t max_wins = max_over(chunks, [](const WinChunk &c) { return c.w_end - c.w_begin; }),
+                 max_blocks = max_over(chunks, [&](const WinChunk &c) {
+                     uint64_t sum = 0;
+                     for (uint64_t i = c.w_begin; i < c.w_end; ++i) sum += nb[i];
+                     return sum;
+                 });
     REQUIRE(max_wins < 0x7FFFFFFFull, "%s: a chunk of %zu windows exceeds one launch", fn, max_wins);
 
     // device: P as dwords | windows (up, through the page-locked staging with the same offsets) | records (down, staged) |
@@ -319,58 +297,55 @@ IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_w
     if (rc) return rc;
     rc = ctx_pinned(ctx, staged, &pin);
     if (rc) return rc;
-    char *dc = (char *)d, *hc = (char *)pin;
-    memcpy(hc + o_pbits, pbits.data(), (size_t)wps * 4);
-    HIP_TRY(hipMemcpyAsync(dc + o_pbits, hc + o_pbits, (size_t)wps * 4, hipMemcpyHostToDevice, ctx->stream));
+    const ChunkRun run{ctx, fn, (char *)d, (char *)pin};
+    char *dc = run.dc, *hc = run.hc;
+    memcpy(hc + o_pbits, P.bits.data(), (size_t)wps * 4);
+    if ((rc = run.up(o_pbits, o_pbits + (size_t)wps * 4))) return rc;
 
     const size_t lds_rows = (size_t)max_sites * (wps | 1u) * 4;
     const bool rows_in_lds = lds_rows <= LD_LDS_ROW_BYTES;
     const size_t lds_pairs = (size_t)max_sites * 28 + 16 + (rows_in_lds ? lds_rows : 0);
-    if (lds_pairs > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute(rows_in_lds ? (const void *)ld_pairs_kernel<true> : (const void *)ld_pairs_kernel<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_pairs));
+    if ((rc = rows_in_lds ? lds_opt_in(ld_pairs_kernel<true>, lds_pairs) : lds_opt_in(ld_pairs_kernel<false>, lds_pairs))) return rc;
 
     const uint32_t *d_pbits = (const uint32_t *)(dc + o_pbits);
     const LdWin *d_wins = (const LdWin *)(dc + o_wins);
     impop_ld_stats *d_rec = (impop_ld_stats *)(dc + o_rec);
     uint32_t *d_qm = (uint32_t *)(dc + o_qm), *d_rows = (uint32_t *)(dc + o_rows), *d_cs = (uint32_t *)(dc + o_cs);
     uint64_t *d_qmask = (uint64_t *)(dc + o_qmask), *d_coords = (uint64_t *)(dc + o_coords);
+    LdWin *h_wins = (LdWin *)(hc + o_wins);
+    EventPairs *timer = ctx->timers + impop_ctx::T_LD;
     uint64_t launches = 0, qualifying = 0, used = 0;
-    const bool timed = ctx->gram_timing;
-    for (const LdChunk &c : chunks) {
-        const size_t cnt = c.wins.size();
-        memcpy(hc + o_wins, c.wins.data(), cnt * sizeof(LdWin));
-        HIP_TRY(hipMemcpyAsync(dc + o_wins, hc + o_wins, cnt * sizeof(LdWin), hipMemcpyHostToDevice, ctx->stream));
-        size_t slot = 0;
-        const uint32_t slices = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((c.longest + 63) / 64, 1), 1024);
-        if (timed && (rc = ctx->ld_timer[0].begin(ctx->stream, &slot))) return rc;
-        hipLaunchKernelGGL(ld_select_kernel, dim3((uint32_t)cnt, slices), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r,
-                           d_pbits, nP, params->min_mac, d_qmask);
-        HIP_TRY(hipGetLastError());
-        if (timed && (rc = ctx->ld_timer[0].end(ctx->stream, slot))) return rc;
-        if (timed && (rc = ctx->ld_timer[1].begin(ctx->stream, &slot))) return rc;
-        hipLaunchKernelGGL(ld_gather_kernel, dim3((uint32_t)cnt), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r, d_pbits,
-                           m->compact ? m->d_pos : nullptr, max_sites, d_qmask, d_rows, d_cs, d_coords, d_qm, ctx->d_err);
-        HIP_TRY(hipGetLastError());
-        if (timed && (rc = ctx->ld_timer[1].end(ctx->stream, slot))) return rc;
-        if (timed && (rc = ctx->ld_timer[2].begin(ctx->stream, &slot))) return rc;
-        if (rows_in_lds)
-            hipLaunchKernelGGL(ld_pairs_kernel<true>, dim3((uint32_t)cnt), dim3(LD_T), lds_pairs, ctx->stream, d_rows, d_cs, d_qm, d_wins, wps,
-                               max_sites, nP, d_rec);
-        else
-            hipLaunchKernelGGL(ld_pairs_kernel<false>, dim3((uint32_t)cnt), dim3(LD_T), lds_pairs, ctx->stream, d_rows, d_cs, d_qm, d_wins, wps,
-                               max_sites, nP, d_rec);
-        HIP_TRY(hipGetLastError());
-        if (timed && (rc = ctx->ld_timer[2].end(ctx->stream, slot))) return rc;
+    for (const WinChunk &c : chunks) {
+        const size_t cnt = c.w_end - c.w_begin;
+        uint64_t n_blocks = 0, longest = 0;  // blocks of all the chunk's windows / of its longest one
+        for (size_t k = 0; k < cnt; ++k) {
+            const uint64_t i = c.w_begin + k;
+            h_wins[k] = LdWin{mapped[i].site_begin, mapped[i].site_end, n_blocks, (uint32_t)window_W(m, windows[i].site_begin, windows[i].site_end), 0u};
+            n_blocks += nb[i];
+            longest = std::max(longest, nb[i]);
+        }
+        if ((rc = run.up(o_wins, o_wins + cnt * sizeof(LdWin)))) return rc;
+        const uint32_t slices = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((longest + 63) / 64, 1), 1024);
+        if ((rc = run.timed(timer[0], [&] {
+            hipLaunchKernelGGL(ld_select_kernel, dim3((uint32_t)cnt, slices), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r,
+                               d_pbits, nP, params->min_mac, d_qmask);
+        }))) return rc;
+        if ((rc = run.timed(timer[1], [&] {
+            hipLaunchKernelGGL(ld_gather_kernel, dim3((uint32_t)cnt), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r, d_pbits,
+                               m->compact ? m->d_pos : nullptr, max_sites, d_qmask, d_rows, d_cs, d_coords, d_qm, ctx->d_err);
+        }))) return rc;
+        if ((rc = run.timed(timer[2], [&] {
+            if (rows_in_lds)
+                hipLaunchKernelGGL(ld_pairs_kernel<true>, dim3((uint32_t)cnt), dim3(LD_T), lds_pairs, ctx->stream, d_rows, d_cs, d_qm, d_wins,
+                                   wps, max_sites, nP, d_rec);
+            else
+                hipLaunchKernelGGL(ld_pairs_kernel<false>, dim3((uint32_t)cnt), dim3(LD_T), lds_pairs, ctx->stream, d_rows, d_cs, d_qm, d_wins,
+                                   wps, max_sites, nP, d_rec);
+        }))) return rc;
         launches += 3;
-        HIP_TRY(hipMemcpyAsync(hc + o_rec, d_rec, cnt * sizeof(impop_ld_stats), hipMemcpyDeviceToHost, ctx->stream));
         if (used_sites)
             HIP_TRY(hipMemcpyAsync(used_sites + c.w_begin * max_sites, d_coords, cnt * max_sites * 8, hipMemcpyDeviceToHost, ctx->stream));
-        rc = ctx_err_fetch(ctx);
-        if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging is reused by the next chunk
-        rc = ctx_err_result(ctx, fn);
-        if (rc) return rc;
+        if ((rc = run.finish(o_rec, o_rec + cnt * sizeof(impop_ld_stats)))) return rc;
         const impop_ld_stats *rv = (const impop_ld_stats *)(hc + o_rec);
         for (size_t k = 0; k < cnt; ++k) {
             out_host[c.w_begin + k] = rv[k];
@@ -390,11 +365,5 @@ IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_w
 
 IMPOP_API int impop_ctx_ld_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks) {
     REQUIRE(ctx && kernel_ms, "impop_ctx_ld_elapsed: NULL argument");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int k = 0; k < 3; ++k) {
-        const int rc = ctx->ld_timer[k].elapsed(&kernel_ms[k], k == 2 ? chunks : nullptr);
-        if (rc) return rc;
-    }
-    return IMPOP_OK;
+    return ctx_timers_elapsed(ctx, impop_ctx::T_LD, 3, 2, kernel_ms, chunks);
 }

@@ -10,6 +10,7 @@
 
 #include "pair_plan.h"
 #include "stats_kernels.h"
+#include "win_chunks.h"
 
 namespace impop {
 
@@ -226,13 +227,13 @@ int pairwise_front(impop_ctx *ctx, const impop_matrix *m, const impop_window *wi
         if (s.n_cells) {
             HIP_TRY(hipMemcpyAsync(dm.w, hm.w, (size_t)s.n_cells * sizeof(GramWindow), hipMemcpyHostToDevice, ctx->stream));
             size_t slot = 0;  // impop_ctx_gram_timing: the Gram launch(es) of this chunk between two events
-            if (ctx->gram_timing && (rc = ctx->gram_timer.begin(ctx->stream, &slot))) return rc;
+            if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_GRAM].begin(ctx->stream, &slot))) return rc;
             // counts as uint16 where every count of the call fits (a count is at most its window's W): half the result bytes
             static const bool u16_off = env_is("IMPOP_GRAM_U16", '0');
             g16 = !u16_off && in.max_W < 65536;
             rc = launch_gram_any(ctx, m, dm.w, hm.w, s.n_cells, d_g, max_sites, &g16);
             if (rc) return rc;
-            if (ctx->gram_timing && (rc = ctx->gram_timer.end(ctx->stream, slot))) return rc;
+            if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_GRAM].end(ctx->stream, slot))) return rc;
             if (in.identity_kind != IMPOP_IDENTITY_MATCH) {  // `match` sees Hamming distances only: polarity-invariant
                 rc = launch_gram_unflip(ctx, m, d_g, s.n_cells, g16);
                 if (rc) return rc;
@@ -369,12 +370,12 @@ struct ClusterEpilogue final : PairEpilogue {
     int launch(impop_ctx *ctx, const PairChunk &c) override {
         const uint64_t cnt = c.cnt;
         size_t slot = 0;  // the clustering kernel(s) between two events of their own: impop_ctx_cluster_elapsed
-        int rc = ctx->gram_timing ? ctx->cluster_timer.begin(ctx->stream, &slot) : IMPOP_OK;
+        int rc = ctx->gram_timing ? ctx->timers[impop_ctx::T_CLUSTER].begin(ctx->stream, &slot) : IMPOP_OK;
         if (rc) return rc;
         rc = launch_af_batch(ctx, c.b, cnt, mask_p ? d_idx : nullptr, nP, params->threshold, reinterpret_cast<uint32_t *>(d_adj), adj_bytes,
                              d_rec, d_cl, d_sz, want_members());
         if (rc) return rc;
-        if (ctx->gram_timing && (rc = ctx->cluster_timer.end(ctx->stream, slot))) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_CLUSTER].end(ctx->stream, slot))) return rc;
         HIP_TRY(hipMemcpyAsync(h_rec, d_rec, cnt * sizeof(impop_cluster_stats), hipMemcpyDeviceToHost, ctx->stream));
         if (cluster_of && nP) HIP_TRY(hipMemcpyAsync(h_cl, d_cl, cnt * nP * 4, hipMemcpyDeviceToHost, ctx->stream));
         if (sizes && nP) HIP_TRY(hipMemcpyAsync(h_sz, d_sz, cnt * nP * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -459,7 +460,7 @@ struct PanelEpilogue final : PairEpilogue {
         if (rc) return rc;
         if (NP) {
             size_t slot = 0;  // impop_ctx_gram_timing: the Fst kernel(s) of the chunk between two events (impop_ctx_cluster_elapsed)
-            if (ctx->gram_timing && (rc = ctx->cluster_timer.begin(ctx->stream, &slot))) return rc;
+            if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_CLUSTER].begin(ctx->stream, &slot))) return rc;
             if (small) {
                 rc = launch_hfst_panel_small(ctx, b, cnt, d_cls, K, c.d_L, d_h, cap);
             } else {
@@ -469,7 +470,7 @@ struct PanelEpilogue final : PairEpilogue {
                         rc = launch_hfst(ctx, b, cnt, d_flags + (size_t)a * n, d_flags + (size_t)bb * n, c.d_L, d_h + (uint64_t)p * cap);
             }
             if (rc) return rc;
-            if (ctx->gram_timing && (rc = ctx->cluster_timer.end(ctx->stream, slot))) return rc;
+            if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_CLUSTER].end(ctx->stream, slot))) return rc;
         }
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
         PanelFinalIn in{d_p, NP ? d_h : nullptr, c.d_s, sp_host ? d_sp : nullptr, d_taj, d_sizes, cap};
@@ -507,13 +508,8 @@ int check_windows(impop_ctx *ctx, const impop_matrix *m, const impop_window *win
     }
     return IMPOP_OK;
 }
-// the haplotypes a mask selects, ascending (no mask: all n)
-std::vector<uint32_t> mask_members(const uint64_t *mask, uint32_t n) {
-    std::vector<uint32_t> idx;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!mask || ((mask[i >> 6] >> (i & 63)) & 1ull)) idx.push_back(i);
-    return idx;
-}
+// the haplotypes a mask selects, ascending (no mask: all n): a view of member_set, whose other two tables are not needed here
+std::vector<uint32_t> mask_members(const uint64_t *mask, uint32_t n) { return member_set(mask, n, (n + 31) / 32).idx; }
 
 }  // namespace
 static_assert(sizeof(impop_panel_stats) == 48 && sizeof(impop_panel_window) == 8 && sizeof(impop_pair_stats) == 48, "fixed record layouts");

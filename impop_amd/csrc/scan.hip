@@ -689,7 +689,7 @@ void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
             const uint64_t re = std::min(e.r, rs + per_r);
             if (ce > cs || re > rs) {
                 tiles.push_back({cs, ce, rs, re});
-                rt.bytes_streamed += (ce > cs ? ((ce + 63) / 64 - cs / 64) * row_bytes : 0) + (re - rs) * 8ull;
+                rt.bytes_streamed += tile_bytes_streamed(tiles.back(), wps);
             }
             cs = ce;
             rs = re;
@@ -824,6 +824,13 @@ int impop::check_windows(const char *fn, const impop_matrix *m, const impop_wind
         REQUIRE(windows[i].site_end - windows[i].site_begin <= 0xFFFFFFFFull, "%s: window %llu longer than 2^32 sites", fn,
                 (unsigned long long)i);
     }
+    return IMPOP_OK;
+}
+
+int impop::check_window_weights(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
+    for (uint64_t i = 0; i < n_windows; ++i)
+        REQUIRE(window_W(m, windows[i].site_begin, windows[i].site_end) <= 0xFFFFFFFFull,
+                "%s: window %llu: the weights of its columns add up to 2^32 or more; split the window", fn, (unsigned long long)i);
     return IMPOP_OK;
 }
 
@@ -1067,9 +1074,9 @@ IMPOP_API int impop_scan_plan_elapsed(impop_scan_plan *p, double *total_ms, uint
 
 IMPOP_API int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]) {
     REQUIRE(ctx && sizes, "impop_debug_timer_pool_sizes: NULL argument");
-    sizes[0] = ctx->gram_timer.pool.size();
-    sizes[1] = ctx->cluster_timer.pool.size();
-    sizes[2] = ctx->ehh_timer.pool.size();
+    sizes[0] = ctx->timers[impop_ctx::T_GRAM].pool.size();
+    sizes[1] = ctx->timers[impop_ctx::T_CLUSTER].pool.size();
+    sizes[2] = ctx->timers[impop_ctx::T_EHH].pool.size();
     sizes[3] = plan ? plan->timer.pool.size() : 0;
     return IMPOP_OK;
 }
@@ -1217,8 +1224,7 @@ IMPOP_API int impop_afs(impop_ctx *ctx, const impop_matrix *m, const impop_windo
     if (chunks) chunks = (longest + chunk_sites - 1) / chunk_sites;
     if (chunks) {
         REQUIRE(chunks < 0x7FFFFFFFull, "impop_afs: window too long");
-        if ((size_t)bins * 4 > 48 * 1024)  // 12288 .. 16383 haplotypes in the mask: opt in like launch_af / launch_multi
-            HIP_TRY(hipFuncSetAttribute((const void *)afs_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)((size_t)bins * 4)));
+        if ((rc = lds_opt_in(afs_kernel, (size_t)bins * 4))) return rc;  // 12288 .. 16383 haplotypes in the mask
         // windows ride on gridDim.y (<= 65535): any number of windows goes out in batches of that many
         for (uint64_t w0 = 0; w0 < n_windows; w0 += 65535) {
             const uint32_t nw = (uint32_t)std::min<uint64_t>(65535, n_windows - w0);

@@ -1,11 +1,14 @@
 // scan_route.h — the front end the streaming calls share (bodies in scan.hip): which layout a scan of a window list streams
-// and how the windows are cut into tiles.  impop_scan_plan_create, impop_scan_multi, impop_haplotype_scan, impop_ld_scan,
-// impop_diploid_scan and impop_dstat_scan all go through it.  Below it, the host half of the K-population calls
-// (impop_scan_multi, impop_dstat_scan; their device half is pop_stream.h): the panel's masks, its upload, its launch.
+// and how the windows are cut into tiles.  impop_scan_plan_create, impop_scan_multi, impop_haplotype_scan and impop_dstat_scan
+// take their route from scan_route; impop_diploid_scan builds its tiles on the matrix's own rows with build_tiles; they and
+// impop_ld_scan share the window checks.  The chunked calls among them go on through win_chunks.h (member set, chunk cutter)
+// and chunk_run.h (the stream protocol of a chunk).  Below it, the host half of the K-population calls (impop_scan_multi,
+// impop_dstat_scan; their device half is pop_stream.h): the panel's masks, its upload, its launch.
 #pragma once
 #include <type_traits>
 #include <vector>
 
+#include "chunk_run.h"
 #include "internal.h"
 
 namespace impop {
@@ -16,6 +19,10 @@ struct ScanTile {
     uint64_t site_begin, site_end;
     uint64_t rare_begin, rare_end;
 };
+// what a workgroup reads of a tile: its 64-site blocks of 4 wps bytes per site, whole, and its 8-byte rare entries
+inline uint64_t tile_bytes_streamed(const ScanTile &t, uint32_t wps) {
+    return (t.site_end > t.site_begin ? ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps : 0) + (t.rare_end - t.rare_begin) * 8ull;
+}
 struct WinDesc {
     uint64_t t0, t1;  // tile range
     uint64_t n_sites;
@@ -39,6 +46,8 @@ struct ScanRoute {
 void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps);
 // every window lies in the matrix and is at most 2^32 - 1 sites long
 int check_windows(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
+// every window's W (window_W: its length, or the sum of its columns' weights) fits the 32 bits a record gives it
+int check_window_weights(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
 // windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams.  tile_blocks 0: the default.
 int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                uint32_t tile_blocks, ScanRoute &rt);
@@ -69,7 +78,8 @@ template <typename Kernel, typename... Own>
 int pop_launch(Kernel kernel, uint32_t K, hipStream_t st, const impop_matrix *m, const ScanRoute &rt, const PopPanelDev &dev,
                const uint32_t *weights, Own... own) {
     const size_t lds = (size_t)K * ((m->g.wps + 3) & ~3u) * 4;
-    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int rc = lds_opt_in(kernel, lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(kernel, dim3((uint32_t)rt.tiles.size()), dim3(256), lds, st, rt.sb, rt.rare, (const ScanTile *)dev.tiles,
                        (const uint32_t *)dev.masks, (const uint32_t *)dev.n, m->g.wps, m->g.G, m->g.r, weights, own...);
     HIP_TRY(hipGetLastError());

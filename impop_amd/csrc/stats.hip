@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "chunk_run.h"
 #include "stats_kernels.h"
 
 namespace impop {
@@ -1362,7 +1363,8 @@ int launch_pica2(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const u
     be.err = ctx->d_err;  // the grouping's progress bound reports here (ctx_err_fetch / ctx_err_result in the caller)
     const int fast = sim_batch_fast(b);
     const void *kfn = fast == 1 ? (const void *)pica2_kernel<1> : fast == 2 ? (const void *)pica2_kernel<2> : (const void *)pica2_kernel<0>;
-    if (lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int lrc = lds_opt_in(kfn, lds);
+    if (lrc) return lrc;
     if (fast == 1)
         hipLaunchKernelGGL(pica2_kernel<1>, dim3((uint32_t)n_problems), dim3(ST), lds, ctx->stream, be, d_idx, n_el, d_order, threshold,
                            d_seq_len, d_out, d_group_of, split);
@@ -1434,8 +1436,8 @@ int launch_hud_grouped(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, c
     const size_t lds = (size_t)std::max(ma, mb) * 8 + ((size_t)ma + mb) * 12 + 16;
     static const size_t lds_room = dynamic_lds_room((const void *)hud_grouped_kernel);
     REQUIRE(lds <= lds_room, "grouped Fst: populations too large for the LDS-resident grouping");
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)hud_grouped_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const int rc = lds_opt_in(hud_grouped_kernel, lds);
+    if (rc) return rc;
     SimBatch be = b;
     be.err = ctx->d_err;
     hipLaunchKernelGGL(hud_grouped_kernel, dim3((uint32_t)n_problems), dim3(ST), lds, ctx->stream, be, d_ia, ma, d_ib, mb,
@@ -1461,9 +1463,8 @@ int launch_af_general(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, co
     }
     // above 48 KiB the kernel's limit is raised for this launch, on the device the caller made current (a process-wide
     // "done once" flag would leave every other device at the default)
-    if (lds > 48 * 1024)
-        HIP_TRY(hipFuncSetAttribute((const void *)af_components_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)lds));
+    const int rc = lds_opt_in(af_components_kernel, lds);
+    if (rc) return rc;
     hipLaunchKernelGGL(af_components_kernel, dim3((uint32_t)n_problems), dim3(ST), lds, ctx->stream, m, words, d_adj, d_cluster_of, d_sizes,
                        d_nclusters, d_rec, b.W, ctx->d_err);
     HIP_TRY(hipGetLastError());

@@ -259,7 +259,19 @@ def _batch_inputs():
     return m01, wins, cores, flags
 
 
+CAP_N, CAP_S, CAP_PERIOD, CAP_WINDOWS = 8, 512, 200, 65536  # one window more than a launch's blockIdx.y holds
+
+
+def _cap_inputs():
+    """65536 three-site windows, the core in the middle, the list repeating with period 200"""
+    m01 = _bernoulli(np.random.default_rng(4650), CAP_N, CAP_S)
+    begins = (np.arange(CAP_WINDOWS) % CAP_PERIOD) * 5 % (CAP_S - 3)
+    return m01, np.stack([begins, begins + 3], axis=1), begins + 1
+
+
 def _child(out_path):
+    import signal
+
     import impop_amd
     from impop_amd import ImpopError
     m01, wins, cores, flags = _batch_inputs()
@@ -277,6 +289,12 @@ def _child(out_path):
     per_window = 3 * int(flags.sum()) * 8  # a 130-site window touches 3 or 4 blocks of 64 sites
     out["chunked"] = call("chunked", lambda: bm.ehh_scan(wins, cores, mask=flags, flanks="two-sided", max_chunk_bytes=90 * per_window))
     bm.free()
+    cap_m01, cap_wins, cap_cores = _cap_inputs()
+    small = ctx.upload_dense(cap_m01, keep_hap_major=False)
+    signal.alarm(120)  # this step's own limit (some 260000 tiny workgroups: seconds); the default action ends the process
+    out["cap"] = call("cap", lambda: small.ehh_scan(cap_wins, cap_cores, flanks="two-sided"))
+    signal.alarm(0)
+    small.free()
     big = ctx.upload_dense(np.zeros((4097, 200), np.uint8), keep_hap_major=False)
     try:
         call("over", lambda: big.ehh_scan([(0, 200)], [100]))
@@ -300,6 +318,7 @@ def child():
         env = dict(os.environ, IMPOP_TRACE="1", PYTHONPATH=os.pathsep.join([ROOT, HERE]))
         r = subprocess.run([sys.executable, "-c", "import sys, test_gpu_ehh_scan as t; t._child(sys.argv[1])", path],
                            capture_output=True, text=True, cwd=ROOT, env=env, timeout=300)
+        assert r.returncode != -14, "the child's 65536-window step (cap) ran into its own 120 s limit (SIGALRM): a hang\n" + r.stderr[-2000:]
         assert r.returncode == 0, r.stderr[-4000:]
         z = np.load(path)
         recs = {k: z[k] for k in z.files}
@@ -338,6 +357,16 @@ def test_launches_do_not_depend_on_the_number_of_windows(child):
     assert b["scratch_bytes"] > a["scratch_bytes"] > 0
     for t in trace["chunked"]:
         assert t["launches"] == a["launches"]
+
+
+def test_window_cap_of_one_launch_cuts_a_second_chunk(child):
+    """65536 windows, far below the byte budget: the 65535 windows that blockIdx.y holds, then one; the records do not notice"""
+    recs, trace = child
+    assert [(t["chunk"], t["windows"]) for t in trace["cap"]] == [(0, 65535), (1, 1)]
+    rec = recs["cap"]
+    m01, wins, cores = _cap_inputs()
+    check_records(rec[:CAP_PERIOD], m01, None, wins[:CAP_PERIOD].tolist(), cores[:CAP_PERIOD].tolist(), "two-sided", 0, {}, "cap")
+    assert len(rec) == CAP_WINDOWS and rec[np.arange(CAP_WINDOWS) % CAP_PERIOD].tobytes() == rec.tobytes()
 
 
 def test_limit_plus_one_is_refused_before_any_launch(child):

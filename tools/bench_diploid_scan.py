@@ -4,6 +4,8 @@ one run:
 
   tiling_50kb        4096 x 50 kb windows of one synthetic founder matrix
   sliding_10kb_5kb   10239 x 10 kb windows every 5 kb from the start of the same matrix
+  one_window_chunks  the first --chunk-windows (256; 0: skip) windows of tiling_50kb with max_chunk_bytes=1: a chunk per window,
+                     so the host's per-chunk path (metadata up, launches, records down, one synchronisation) is what is timed
 
 Per point: the median of 5 timed calls after one warm-up call of BitMatrix.diploid_scan (min_run 50, the command line's default,
 records only); from HIP events (impop_ctx_gram_timing) the time of its two kernels (tile / window) in one call; the mean
@@ -93,6 +95,17 @@ def gram_loop(ctx, nw, dip_ms_per_window):
             "ratio_to_diploid_scan": round(ms_per_window / dip_ms_per_window, 1) if dip_ms_per_window > 0 else None}
 
 
+def chunk_point(ctx, bm, nw, k):
+    """a chunk per window: the median of 5 calls after one warm-up, and the chunks the timers counted in one call"""
+    wins = impop_amd.make_windows(windows_of("tiling_50kb", min(k, nw)))
+    t = passes(lambda: bm.diploid_scan(wins, PAIRS, MIN_RUN, max_chunk_bytes=1))
+    ctx.gram_timing(True)
+    bm.diploid_scan(wins, PAIRS, MIN_RUN, max_chunk_bytes=1)
+    _, chunks = ctx.diploid_elapsed()
+    ctx.gram_timing(False)
+    return {"windows": min(k, nw), "max_chunk_bytes": 1, "ms": round(t * 1e3, 3), "chunks": int(chunks)}
+
+
 def trace_child(nw):
     ctx = impop_amd.Context(0)
     bm = ctx.synthetic(N_HAP, 50000 * nw, seed=SEED, keep_hap_major=False)
@@ -109,6 +122,7 @@ def trace_child(nw):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=4096)
+    ap.add_argument("--chunk-windows", type=int, default=256)
     ap.add_argument("--out")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -120,6 +134,8 @@ def main():
     bm = ctx.synthetic(N_HAP, 50000 * a.windows, seed=SEED, keep_hap_major=False)
     for name in POINTS:
         res[name] = point(ctx, bm, name, a.windows)
+    if a.chunk_windows > 0:
+        res["one_window_chunks"] = chunk_point(ctx, bm, a.windows, a.chunk_windows)
     bm.free()
     res["gram_loop_50kb"] = gram_loop(ctx, a.windows, res["tiling_50kb"]["diploid_scan_ms"] / res["tiling_50kb"]["windows"])
     ctx.close()

@@ -3,6 +3,8 @@
 
   tiling_50kb        256 x 50 kb windows of one synthetic founder matrix of 465 haplotypes, the core in the middle of each
   sliding_10kb_5kb   as many 10 kb windows every 5 kb from the start of the same matrix (overlapping windows), central cores
+  one_window_chunks  the first --chunk-windows (256; 0: skip) windows of tiling_50kb with max_chunk_bytes=1: a chunk per window,
+                     so the host's per-chunk path (metadata up, launches, records down, one synchronisation) is what is timed
 
 Per point, on the same windows and cores (flanks = reference, ehhgfa.py:56-61):
   scan   one BitMatrix.ehh_scan call
@@ -83,6 +85,17 @@ def point(ctx, bm, name, nw):
             "windows_with_both_alleles": int((minor > 0).sum()), "minor_allele_members_mean": round(float(minor.mean()), 1)}
 
 
+def chunk_point(ctx, bm, nw, k):
+    """a chunk per window: the median of 5 calls after one warm-up, and the chunks the timers counted in one call"""
+    wins, cores = windows_of("tiling_50kb", min(k, nw))
+    t = passes(lambda: bm.ehh_scan(wins, cores, max_chunk_bytes=1))
+    ctx.gram_timing(True)
+    bm.ehh_scan(wins, cores, max_chunk_bytes=1)
+    _, chunks = ctx.ehh_elapsed()
+    ctx.gram_timing(False)
+    return {"windows": min(k, nw), "max_chunk_bytes": 1, "ms": round(t * 1e3, 3), "chunks": int(chunks)}
+
+
 def trace_child(nw):
     ctx = impop_amd.Context(0)
     bm = matrix(ctx, nw)
@@ -97,6 +110,7 @@ def trace_child(nw):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=256)
+    ap.add_argument("--chunk-windows", type=int, default=256)
     ap.add_argument("--out")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -107,6 +121,8 @@ def main():
     bm = matrix(ctx, a.windows)
     for name in ("tiling_50kb", "sliding_10kb_5kb"):
         res[name] = point(ctx, bm, name, a.windows)
+    if a.chunk_windows > 0:
+        res["one_window_chunks"] = chunk_point(ctx, bm, a.windows, a.chunk_windows)
     bm.free()
     ctx.close()
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--trace-child", "--windows", str(a.windows)],

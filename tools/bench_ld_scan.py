@@ -3,6 +3,8 @@
 
   tiling_50kb        4096 x 50 kb windows of one synthetic founder matrix
   sliding_10kb_5kb   10239 x 10 kb windows every 5 kb from the start of the same matrix
+  one_window_chunks  the first --chunk-windows (256; 0: skip) windows of tiling_50kb with max_chunk_bytes=1: a chunk per window,
+                     so the host's per-chunk path (metadata up, launches, records down, one synchronisation) is what is timed
 
 Per point: the median of 5 timed calls after one warm-up call of BitMatrix.ld_scan (min_mac = ceil(0.05 x 465) = 24, max_sites
 512, the command line's defaults); from HIP events (impop_ctx_gram_timing) the time of its three kernel groups (select / gather /
@@ -66,6 +68,17 @@ def point(ctx, bm, name, nw):
             "mean_zns": round(float(rec["zns"].mean()), 6)}
 
 
+def chunk_point(ctx, bm, nw, k):
+    """a chunk per window: the median of 5 calls after one warm-up, and the chunks the timers counted in one call"""
+    wins = impop_amd.make_windows(windows_of("tiling_50kb", min(k, nw)))
+    t = passes(lambda: bm.ld_scan(wins, max_chunk_bytes=1, **LD_KW))
+    ctx.gram_timing(True)
+    bm.ld_scan(wins, max_chunk_bytes=1, **LD_KW)
+    _, chunks = ctx.ld_elapsed()
+    ctx.gram_timing(False)
+    return {"windows": min(k, nw), "max_chunk_bytes": 1, "ms": round(t * 1e3, 3), "chunks": int(chunks)}
+
+
 def trace_child(nw):
     ctx = impop_amd.Context(0)
     bm = ctx.synthetic(N_HAP, 50000 * nw, seed=SEED, keep_hap_major=False)
@@ -82,6 +95,7 @@ def trace_child(nw):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--windows", type=int, default=4096)
+    ap.add_argument("--chunk-windows", type=int, default=256)
     ap.add_argument("--out")
     ap.add_argument("--trace-child", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
@@ -93,6 +107,8 @@ def main():
     bm = ctx.synthetic(N_HAP, 50000 * a.windows, seed=SEED, keep_hap_major=False)
     for name in POINTS:
         res[name] = point(ctx, bm, name, a.windows)
+    if a.chunk_windows > 0:
+        res["one_window_chunks"] = chunk_point(ctx, bm, a.windows, a.chunk_windows)
     bm.free()
     ctx.close()
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "--trace-child", "--windows", str(a.windows)],
