@@ -225,6 +225,19 @@ struct impop_matrix {
     uint64_t *d_cmask = nullptr, *d_cbase = nullptr;
     uint64_t n_vrare = 0;
     std::string rskip = "not built";
+    // singleton stream of the split index (layout.hip rare_entries_kernel; built for wps <= 16, the range of its one consumer,
+    // the fixed-WPS scan kernel): the rare sites once more, as two packed streams in site order.  d_vsingle holds one uint16 per
+    // SINGLETON site, min(c, n - c) = 1: bits 0..14 = the one carrier of the minor allele, bit 15 = that haplotype carries 0 (the
+    // meaning of bit 15 of an 8-byte entry); padded with 0xFFFF to a multiple of 8 bytes plus 8 bytes of slack, so aligned 8-byte
+    // loads of any range stay inside the allocation.  d_vmulti holds the other rare sites (min(c, n - c) = 2 or 3) as 8-byte
+    // entries (rare_pack).  Per 64-site block of the matrix: d_smask = mask of its singleton sites, d_sbase = singletons before
+    // it (n_block + 1 entries each, one allocation); single(s) as common(s), multi(s) = rare(s) - single(s).  d_vrare stays
+    // complete.  d_vsingle null: no stream (sskip says why).
+    uint16_t *d_vsingle = nullptr;
+    uint64_t *d_vmulti = nullptr;
+    uint64_t *d_smask = nullptr, *d_sbase = nullptr;
+    uint64_t n_vsingle = 0, vsingle_bytes = 0;  // singleton sites; everything the stream allocated
+    std::string sskip = "not built";
     int device = 0;
     mutable int users = 0;      // live scan plans referencing this matrix (impop_matrix_free refuses while > 0)
 };
@@ -291,15 +304,19 @@ constexpr unsigned POS_COARSE_SHIFT = 12;
 // variable-site scan index: window edges in matrix coordinates -> kept-site index ranges of d_vsb (one thread per edge, no search)
 // the index a kept fraction above 1/IMPOP_INDEX_MAX_KEPT_INV of the sites is not built for (the dense stream is then nearly as short)
 constexpr uint64_t IMPOP_INDEX_MAX_KEPT_INV = 4;
-// split index: the same edges also as common-site (`mapped`) and rare-entry (`rare`) ranges; rare == nullptr: kept-site ranges
+// split index: the same edges also as common-site (`mapped`) and rare-entry (`rare`) ranges; rare == nullptr: kept-site ranges.
+// single (nullable; needs rare and the matrix's singleton stream): the edges as ranges of d_vsingle, and `rare` then holds the
+// ranges of d_vmulti, rare(s) - single(s)
 int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
-                      std::vector<impop_window> *rare);
+                      std::vector<impop_window> *rare, std::vector<impop_window> *single = nullptr);
 
 // layout.hip
 // d_mask / d_cnt (nullable): also write the variable-site mask of every block and its popcount (scan index);
-// d_cmask / d_ccnt (nullable): the same for the common sites, min(c, n - c) > IMPOP_RARE_MAX (split index)
+// d_cmask / d_ccnt (nullable): the same for the common sites, min(c, n - c) > IMPOP_RARE_MAX (split index);
+// d_smask / d_scnt (nullable): the same for the singleton sites, min(c, n - c) = 1 (singleton stream)
 int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb,
-                    uint64_t *d_mask = nullptr, uint32_t *d_cnt = nullptr, uint64_t *d_cmask = nullptr, uint32_t *d_ccnt = nullptr);
+                    uint64_t *d_mask = nullptr, uint32_t *d_cnt = nullptr, uint64_t *d_cmask = nullptr, uint32_t *d_ccnt = nullptr,
+                    uint64_t *d_smask = nullptr, uint32_t *d_scnt = nullptr);
 // rb_nb == 0: plain hap-major rows of hm_stride dwords; else RB32 addressing with rb_nb cells per row group
 int launch_sb_to_hm(impop_ctx *ctx, const uint32_t *d_sb, const SbGeom &g, uint64_t blk_begin, uint64_t blk_end,
                     uint32_t *d_hm, uint64_t hm_stride, uint32_t n_rows, uint64_t rb_nb = 0, uint32_t phi_row = 0xFFFFFFFFu);

@@ -34,7 +34,8 @@ __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restric
                                                        uint32_t n_rows, uint32_t wps, uint32_t G, uint32_t r,
                                                        uint64_t n_block, uint32_t *__restrict__ sb, uint64_t n_site,
                                                        uint32_t n_hap, uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt,
-                                                       uint64_t *__restrict__ cmask, uint32_t *__restrict__ ccnt) {
+                                                       uint64_t *__restrict__ cmask, uint32_t *__restrict__ ccnt,
+                                                       uint64_t *__restrict__ smask, uint32_t *__restrict__ scnt) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;  // wave-uniform
@@ -62,6 +63,10 @@ __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restric
     if (cmask) {
         const uint64_t v = __ballot(b * 64 + lane < n_site && c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX);
         if (lane == 0) { cmask[b] = v; ccnt[b] = (uint32_t)__popcll(v); }
+    }
+    if (smask) {  // singleton stream: min(c, n - c) = 1 (built for n_hap > 64 only: such a site varies)
+        const uint64_t v = __ballot(b * 64 + lane < n_site && (c == 1 || n_hap - c == 1));
+        if (lane == 0) { smask[b] = v; scnt[b] = (uint32_t)__popcll(v); }
     }
 }
 
@@ -148,13 +153,13 @@ __global__ void hm_clear_tail_kernel(uint32_t *hm, uint64_t hm_stride, uint32_t 
 }
 
 int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb, uint64_t *d_mask,
-                    uint32_t *d_cnt, uint64_t *d_cmask, uint32_t *d_ccnt) {
+                    uint32_t *d_cnt, uint64_t *d_cmask, uint32_t *d_ccnt, uint64_t *d_smask, uint32_t *d_scnt) {
     if (g.n_block == 0) return IMPOP_OK;
     const uint64_t grid = (g.n_block + 3) / 4;
     REQUIRE(grid < 0x7FFFFFFFull, "matrix too long for one launch (%llu blocks)", (unsigned long long)g.n_block);
     const uint32_t n_rows = (g.n_hap + 95) / 96 * 96;
     hipLaunchKernelGGL(hm_to_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, d_hm, hm_stride, n_rows, g.wps,
-                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, d_mask, d_cnt, d_cmask, d_ccnt);
+                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, d_mask, d_cnt, d_cmask, d_ccnt, d_smask, d_scnt);
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }
@@ -184,7 +189,8 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
                                                        uint32_t G, uint32_t r, uint64_t n_block, uint64_t n_site,
                                                        uint64_t site0, uint32_t *__restrict__ sb, uint32_t n_hap,
                                                        uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt, uint64_t *__restrict__ cmask,
-                                                       uint32_t *__restrict__ ccnt) {
+                                                       uint32_t *__restrict__ ccnt, uint64_t *__restrict__ smask,
+                                                       uint32_t *__restrict__ scnt) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;
@@ -221,6 +227,10 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
     if (cmask) {  // split index: the common kept sites, min(c, n - c) > IMPOP_RARE_MAX
         const uint64_t v = __ballot(live && c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX);
         if (lane == 0) { cmask[b] = v; ccnt[b] = (uint32_t)__popcll(v); }
+    }
+    if (smask) {  // singleton stream: the singleton sites, min(c, n - c) = 1
+        const uint64_t v = __ballot(live && (c == 1 || n_hap - c == 1));
+        if (lane == 0) { smask[b] = v; scnt[b] = (uint32_t)__popcll(v); }
     }
 }
 
@@ -274,6 +284,8 @@ struct IndexBuild {
     uint32_t *d_cnt = nullptr;   // kept sites per block, n_block + 1 entries (inside d_tmp)
     uint64_t *d_cmask = nullptr; // == m->d_cmask: split index wanted (else null)
     uint32_t *d_ccnt = nullptr;  // common sites per block (inside d_tmp)
+    uint64_t *d_smask = nullptr; // == m->d_smask: singleton stream wanted (else null)
+    uint32_t *d_scnt = nullptr;  // singleton sites per block (inside d_tmp)
     void *d_tmp = nullptr;       // transient: counts, chunk sums, totals
     uint64_t *d_pos = nullptr;   // transient: source site of every kept site
     uint64_t n_chunks = 0;
@@ -330,7 +342,7 @@ IMPOP_API int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits, uint32_t
     IndexBuild ib;
     rc = index_begin(ctx, m, keep_flags, ib);
     if (rc) return fail(rc);
-    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.d_mask, ib.d_cnt, ib.d_cmask, ib.d_ccnt);
+    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.d_mask, ib.d_cnt, ib.d_cmask, ib.d_ccnt, ib.d_smask, ib.d_scnt);
     if (rc) return fail(rc);
     rc = index_finish(ctx, m, ib);
     if (rc) return fail(rc);
@@ -398,7 +410,7 @@ IMPOP_API int impop_matrix_synthetic_slab(impop_ctx *ctx, uint32_t n_hap, uint64
         }
         hipLaunchKernelGGL(synth_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, sp, (const uint32_t *)d_tab,
                            wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb, n_hap, ib.d_mask, ib.d_cnt,
-                           ib.d_cmask, ib.d_ccnt);
+                           ib.d_cmask, ib.d_ccnt, ib.d_smask, ib.d_scnt);
         if ((e = hipGetLastError()) != hipSuccess) return fail(hip_fail(e, "synth_sb_kernel", __FILE__, __LINE__));
         if (want_hm) {
             rc = launch_sb_to_hm(ctx, m->d_sb, m->g, 0, m->g.n_block, m->d_rb, 0, m->n_hap_pad, m->rb_nb, m->phi_row);
@@ -683,14 +695,20 @@ __global__ __launch_bounds__(256) void gather_kept_kernel(const uint32_t *__rest
 
 // Rare kept sites -> 8-byte entries (layout: internal.h, d_vrare).  One thread per source block walks its rare sites (a few per
 // block) and reads each one's wps dwords twice: the count picks the allele to list, then the first (at most three) carriers of it.
+// Singleton stream (smask non-null): the same pass also writes every rare site to one of the two packed streams, a singleton
+// as its carrier's 16 bits to out_single, any other as its entry to out_multi (internal.h, d_vsingle / d_vmulti).
 __global__ __launch_bounds__(256) void rare_entries_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
                                                            uint32_t n_hap, const uint64_t *__restrict__ vmask,
                                                            const uint64_t *__restrict__ vbase, const uint64_t *__restrict__ cmask,
                                                            const uint64_t *__restrict__ cbase, uint64_t n_block,
-                                                           uint64_t *__restrict__ out) {
+                                                           uint64_t *__restrict__ out, const uint64_t *__restrict__ smask,
+                                                           const uint64_t *__restrict__ sbase, uint16_t *__restrict__ out_single,
+                                                           uint64_t *__restrict__ out_multi) {
     const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (b >= n_block) return;
     uint64_t v = vmask[b] & ~cmask[b], d = vbase[b] - cbase[b];
+    const uint64_t sm = smask ? smask[b] : 0ull;
+    uint64_t ds = smask ? sbase[b] : 0ull, dm = d - ds;
     while (v) {
         const uint32_t l = (uint32_t)__builtin_ctzll(v);
         v &= v - 1;
@@ -708,15 +726,21 @@ __global__ __launch_bounds__(256) void rare_entries_kernel(const uint32_t *__res
                 slots = rare_set_slot(slots, m++, h);
             }
         }
-        out[d++] = rare_pack(slots, m, zeros);
+        const uint64_t e = rare_pack(slots, m, zeros);
+        out[d++] = e;
+        if (smask) {
+            if ((sm >> l) & 1ull) out_single[ds++] = (uint16_t)(rare_slot(e, 0) | (zeros ? 0x8000u : 0u));
+            else out_multi[dm++] = e;
+        }
     }
 }
 
 // edge s -> kept(s); split index: -> common(s) into `out` and kept(s) - common(s) into `out_rare`
 __global__ void map_edges_index_kernel(const uint64_t *__restrict__ mask, const uint64_t *__restrict__ base,
                                        const uint64_t *__restrict__ cmask, const uint64_t *__restrict__ cbase,
+                                       const uint64_t *__restrict__ smask, const uint64_t *__restrict__ sbase,
                                        const impop_window *__restrict__ win, uint64_t n_win, impop_window *__restrict__ out,
-                                       impop_window *__restrict__ out_rare) {
+                                       impop_window *__restrict__ out_rare, impop_window *__restrict__ out_single) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= 2 * n_win) return;
     const uint64_t key = (e & 1) ? win[e >> 1].site_end : win[e >> 1].site_begin;  // <= n_site: entry n_block exists
@@ -725,36 +749,59 @@ __global__ void map_edges_index_kernel(const uint64_t *__restrict__ mask, const 
     uint64_t v = kept;
     if (cmask) {
         v = cbase[key >> 6] + (uint64_t)__popcll(cmask[key >> 6] & below);
-        if (e & 1) out_rare[e >> 1].site_end = kept - v;
-        else { out_rare[e >> 1].site_begin = kept - v; out_rare[e >> 1].seq_len = win[e >> 1].seq_len; }
+        uint64_t rare = kept - v;
+        if (smask) {  // singleton stream: single(s) into out_single, multi(s) = rare(s) - single(s) into out_rare
+            const uint64_t sg = sbase[key >> 6] + (uint64_t)__popcll(smask[key >> 6] & below);
+            rare -= sg;
+            if (e & 1) out_single[e >> 1].site_end = sg;
+            else { out_single[e >> 1].site_begin = sg; out_single[e >> 1].seq_len = win[e >> 1].seq_len; }
+        }
+        if (e & 1) out_rare[e >> 1].site_end = rare;
+        else { out_rare[e >> 1].site_begin = rare; out_rare[e >> 1].seq_len = win[e >> 1].seq_len; }
     }
     if (e & 1) out[e >> 1].site_end = v;
     else { out[e >> 1].site_begin = v; out[e >> 1].seq_len = win[e >> 1].seq_len; }
 }
 
 int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
-                      std::vector<impop_window> *rare) {
+                      std::vector<impop_window> *rare, std::vector<impop_window> *single) {
     mapped.resize(n);
     const bool split = rare && m->d_vrare;
+    const bool packed = split && single && m->d_vsingle;
     if (split) rare->resize(n);
+    if (packed) single->resize(n);
     if (!n) return IMPOP_OK;
     REQUIRE(m->d_vsb, "map_windows_index: the matrix has no scan index");
     REQUIRE((2 * n + 255) / 256 < 0x7FFFFFFFull, "map_windows_index: too many windows");
     void *d = nullptr;
-    const int rc = ctx_aux(ctx, 0, 3 * n * sizeof(impop_window), &d);  // as map_windows_device: idle outside the all-pairs path
+    const int rc = ctx_aux(ctx, 0, 4 * n * sizeof(impop_window), &d);  // as map_windows_device: idle outside the all-pairs path
     if (rc) return rc;
-    impop_window *d_in = reinterpret_cast<impop_window *>(d), *d_out = d_in + n, *d_rare = d_out + n;
+    impop_window *d_in = reinterpret_cast<impop_window *>(d), *d_out = d_in + n, *d_rare = d_out + n, *d_single = d_rare + n;
     HIP_TRY(hipMemcpyAsync(d_in, windows, n * sizeof(impop_window), hipMemcpyHostToDevice, ctx->stream));
     hipLaunchKernelGGL(map_edges_index_kernel, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream, m->d_vmask,
-                       m->d_vbase, split ? m->d_cmask : nullptr, split ? m->d_cbase : nullptr, d_in, n, d_out, d_rare);
+                       m->d_vbase, split ? m->d_cmask : nullptr, split ? m->d_cbase : nullptr, packed ? m->d_smask : nullptr,
+                       packed ? m->d_sbase : nullptr, d_in, n, d_out, d_rare, d_single);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(mapped.data(), d_out, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
     if (split) HIP_TRY(hipMemcpyAsync(rare->data(), d_rare, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
+    if (packed) HIP_TRY(hipMemcpyAsync(single->data(), d_single, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return IMPOP_OK;
 }
 
+static void single_drop(impop_matrix *m, std::string why) {
+    if (m->d_smask) hipFree(m->d_smask);
+    if (m->d_vsingle) hipFree(m->d_vsingle);
+    if (m->d_vmulti) hipFree(m->d_vmulti);
+    m->d_smask = m->d_sbase = nullptr;
+    m->d_vsingle = nullptr;
+    m->d_vmulti = nullptr;
+    m->n_vsingle = m->vsingle_bytes = 0;
+    m->sskip = std::move(why);
+}
+
 static void split_drop(impop_matrix *m, std::string why) {
+    single_drop(m, "no rare/common split");
     if (m->d_cmask) hipFree(m->d_cmask);
     if (m->d_vrare) hipFree(m->d_vrare);
     m->d_cmask = m->d_cbase = nullptr;
@@ -784,13 +831,15 @@ static bool index_alloc(impop_matrix *m, void **p, size_t bytes, const char *wha
     return false;
 }
 
-// d_tmp: kept counts | common counts | chunk sums (kept) | chunk sums (common) | the two totals
+// d_tmp: kept counts | common counts | singleton counts | chunk sums (kept) | (common) | (singleton) | the three totals
 struct IndexTmp {
-    size_t o_ccnt, o_chunk, o_cchunk, o_total, bytes;
+    size_t o_ccnt, o_scnt, o_chunk, o_cchunk, o_schunk, o_total, bytes;
     IndexTmp(uint64_t ne, uint64_t n_chunks) {
         Carve L;
         L.take<uint32_t>(ne);  // the kept counts, at offset 0
-        o_ccnt = L.take<uint32_t>(ne); o_chunk = L.take<uint64_t>(n_chunks); o_cchunk = L.take<uint64_t>(n_chunks); o_total = L.take<uint64_t>(2);
+        o_ccnt = L.take<uint32_t>(ne); o_scnt = L.take<uint32_t>(ne);
+        o_chunk = L.take<uint64_t>(n_chunks); o_cchunk = L.take<uint64_t>(n_chunks); o_schunk = L.take<uint64_t>(n_chunks);
+        o_total = L.take<uint64_t>(3);
         bytes = L.total();
     }
 };
@@ -799,6 +848,7 @@ static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, Ind
     if (keep_flags & IMPOP_KEEP_DENSE_SCAN) {
         m->vskip = "opted out (IMPOP_KEEP_DENSE_SCAN)";
         m->rskip = "no scan index";
+        m->sskip = "no rare/common split";
         return IMPOP_OK;
     }
     const uint64_t ne = m->g.n_block + 1;  // one entry past the last block: an edge at n_site maps there when 64 | n_site
@@ -834,6 +884,27 @@ static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, Ind
             HIP_TRY(hipMemsetAsync(ib.d_ccnt + m->g.n_block, 0, 4, ctx->stream));
         }
     }
+    // the singleton stream: read by the fixed-WPS scan kernel alone, so built for wps <= 16 only
+    if (!ib.d_cmask) {
+        m->sskip = "no rare/common split";
+    } else if (keep_flags & IMPOP_KEEP_NO_SINGLE_STREAM) {
+        m->sskip = "opted out (IMPOP_KEEP_NO_SINGLE_STREAM)";
+    } else if (m->g.wps > 16) {
+        m->sskip = "n_hap > 512: scans run the any-n kernel, which reads the 8-byte entries";
+    } else {
+        void *sm = nullptr;
+        if (hipMalloc(&sm, 2 * ne * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            m->sskip = "hipMalloc of the singleton-site mask failed";
+        } else {
+            m->d_smask = reinterpret_cast<uint64_t *>(sm);
+            m->d_sbase = m->d_smask + ne;
+            ib.d_smask = m->d_smask;
+            ib.d_scnt = reinterpret_cast<uint32_t *>((char *)ib.d_tmp + lay.o_scnt);
+            HIP_TRY(hipMemsetAsync(m->d_smask + m->g.n_block, 0, 8, ctx->stream));
+            HIP_TRY(hipMemsetAsync(ib.d_scnt + m->g.n_block, 0, 4, ctx->stream));
+        }
+    }
     return IMPOP_OK;
 }
 
@@ -851,14 +922,16 @@ static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
     const uint64_t nb = g.n_block, ne = nb + 1;
     const IndexTmp lay(ne, ib.n_chunks);
     char *tmp = (char *)ib.d_tmp;
-    uint64_t *d_total = reinterpret_cast<uint64_t *>(tmp + lay.o_total);  // [0] kept, [1] common
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(tmp + lay.o_total);  // [0] kept, [1] common, [2] singleton
     REQUIRE(ib.n_chunks < 0x7FFFFFFFull && (nb + 255) / 256 < 0x7FFFFFFFull, "scan index: matrix too long for one launch");
     block_prefix(ctx, ib.d_cnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_chunk), d_total, m->d_vbase);
     if (ib.d_cmask)
         block_prefix(ctx, ib.d_ccnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_cchunk), d_total + 1, m->d_cbase);
+    if (ib.d_smask)
+        block_prefix(ctx, ib.d_scnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_schunk), d_total + 2, m->d_sbase);
     HIP_TRY(hipGetLastError());
-    uint64_t totals[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(totals, d_total, ib.d_cmask ? 16 : 8, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t totals[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, d_total, ib.d_smask ? 24 : ib.d_cmask ? 16 : 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const uint64_t n_kept = totals[0];
     if (n_kept * IMPOP_INDEX_MAX_KEPT_INV > g.n_site) {
@@ -878,6 +951,24 @@ static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
         } else {
             m->d_vrare = reinterpret_cast<uint64_t *>(rare);
             m->rskip.clear();
+        }
+    }
+    // ... and their two packed streams; without them the split index is what it was
+    uint64_t single_pad = 0;  // bytes of d_vsingle: whole 8-byte words, then 8 bytes of slack
+    if (ib.d_smask && m->d_vrare) {
+        m->n_vsingle = totals[2];
+        single_pad = (m->n_vsingle * 2 + 7) / 8 * 8 + 8;
+        void *sg = nullptr, *mu = nullptr;
+        if (hipMalloc(&sg, single_pad) != hipSuccess || hipMalloc(&mu, std::max<uint64_t>(m->n_vrare - m->n_vsingle, 1) * 8) != hipSuccess) {
+            (void)hipGetLastError();
+            if (sg) hipFree(sg);
+            single_drop(m, "hipMalloc of the singleton stream failed");
+        } else {
+            m->d_vsingle = reinterpret_cast<uint16_t *>(sg);
+            m->d_vmulti = reinterpret_cast<uint64_t *>(mu);
+            m->vsingle_bytes = 2 * ne * 8 + single_pad + std::max<uint64_t>(m->n_vrare - m->n_vsingle, 1) * 8;
+            m->sskip.clear();
+            HIP_TRY(hipMemsetAsync((char *)sg + m->n_vsingle * 2, 0xFF, single_pad - m->n_vsingle * 2, ctx->stream));
         }
     }
     const bool split = m->d_vrare != nullptr;
@@ -901,10 +992,11 @@ static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
     }
     if (split && m->n_vrare) {
         hipLaunchKernelGGL(rare_entries_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, m->d_sb, g.wps, g.G, g.r,
-                           g.n_hap, m->d_vmask, m->d_vbase, m->d_cmask, m->d_cbase, nb, m->d_vrare);
+                           g.n_hap, m->d_vmask, m->d_vbase, m->d_cmask, m->d_cbase, nb, m->d_vrare, m->d_vsingle ? m->d_smask : nullptr,
+                           m->d_sbase, m->d_vsingle, m->d_vmulti);
         HIP_TRY(hipGetLastError());
     }
-    m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack + (split ? 2 * ne * 8 + std::max<uint64_t>(m->n_vrare, 1) * 8 : 0);
+    m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack + (split ? 2 * ne * 8 + std::max<uint64_t>(m->n_vrare, 1) * 8 : 0) + m->vsingle_bytes;
     m->vskip.clear();
     return IMPOP_OK;
 }
@@ -959,6 +1051,7 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     m->compact = true;
     m->vskip = "compacted matrix (every site is kept)";
     m->rskip = "no scan index";
+    m->sskip = "no rare/common split";
     m->n_site_orig = g.n_site;
     m->pos.resize(n_kept);
     if (n_kept) {
@@ -1094,6 +1187,18 @@ IMPOP_API int impop_matrix_scan_split_info(const impop_matrix *m, uint64_t *n_ra
     return IMPOP_OK;
 }
 
+IMPOP_API int impop_matrix_scan_single_info(const impop_matrix *m, uint64_t *n_single, uint64_t *n_multi, uint64_t *stream_bytes,
+                                            char *why, size_t why_len) {
+    REQUIRE(m, "impop_matrix_scan_single_info: matrix is NULL");
+    const bool built = m->d_vsb && m->d_vrare && m->d_vsingle;
+    const bool has = built && m->wt_prefix.empty();  // no scan of a weighted matrix reads the index
+    if (n_single) *n_single = has ? m->n_vsingle : 0;
+    if (n_multi) *n_multi = has ? m->n_vrare - m->n_vsingle : 0;
+    if (stream_bytes) *stream_bytes = has ? m->vsingle_bytes : 0;
+    if (why && why_len) snprintf(why, why_len, "%s", has ? "" : built ? "site weights: scans stream the dense layout" : m->sskip.c_str());
+    return IMPOP_OK;
+}
+
 IMPOP_API int impop_matrix_free(impop_ctx *ctx, impop_matrix *m) {
     if (!m) return IMPOP_OK;
     REQUIRE(m->users == 0, "impop_matrix_free: %d scan plan(s) still reference this matrix; destroy them first", m->users);
@@ -1110,6 +1215,9 @@ IMPOP_API int impop_matrix_free(impop_ctx *ctx, impop_matrix *m) {
     if (m->d_vsb) hipFree(m->d_vsb);
     if (m->d_cmask) hipFree(m->d_cmask);
     if (m->d_vrare) hipFree(m->d_vrare);
+    if (m->d_smask) hipFree(m->d_smask);
+    if (m->d_vsingle) hipFree(m->d_vsingle);
+    if (m->d_vmulti) hipFree(m->d_vmulti);
     matrix_drop_derived(m);
     delete m;
     return IMPOP_OK;

@@ -119,7 +119,8 @@ __device__ __forceinline__ void rare_counts(uint64_t v, const uint32_t *lp, cons
 }
 
 // The fixed-WPS kernel (n <= 512) decodes an entry through a table in LDS instead: hcode[h] holds, in three 5-bit fields, whether
-// haplotype h belongs to A, B and P, and entry RARE_CODE_NONE is 0, where the unused slots of an entry (0xFFFF) land.  The sum of
+// haplotype h belongs to A, B and P (bit 15: to both A and B, for single_range), and entry RARE_CODE_NONE is 0, where the unused
+// slots of an entry (0xFFFF) land.  The sum of
 // an entry's three table values is (mA, mB, mP), its listed haplotypes per population, in three bit-field reads, three LDS reads
 // and one add — no per-slot predicate, no 64-bit shifts.
 // Which allele the listed haplotypes carry does not matter here: with c = m or n - m alike, c (n - c) = m (n - m), the cross
@@ -162,6 +163,57 @@ __device__ __forceinline__ void rare_range_coded(const uint64_t *__restrict__ ra
     }
     for (; e < e1; e += 256) mo.add(stream_load(rare + e), hcode, ps, acc);
     mo.fold(ps, acc);
+}
+
+// The packed route's singleton stream (internal.h, d_vsingle): singletons [s0, s1) of a tile, 2 bytes each, read as the aligned
+// 8-byte words [s0 / 4, ceil(s1 / 4)) — thread t takes word w0 + t, w0 + t + 256, ..., SU of them in flight (non-temporal,
+// 512 bytes per wave load; the stream's 0xFFFF padding keeps the last word inside the allocation).  Slots outside [s0, s1) —
+// only the first and the last word have any — are set to 0xFFFF, which the table maps to RARE_CODE_NONE like an unused slot of
+// an entry.  A singleton has m = 1, so every per-population count is 0 or 1 and the tile's sums follow from how many of its
+// singletons' carriers lie in A, in B, in P and in both A and B (bit 15 of a table value; the plan removes that overlap, the
+// kernel does not rely on it): per word four table reads and three adds, per batch of SU words one unpack of the four fields
+// (a 5-bit field holds the 4 * SU = 16 a batch can add), and once per lane and tile
+//     S: s_all += k, s_x += kX when nX > 1;   sum m (nX - m) = kX (nX - 1);   cross = nB kA + nA kB - 2 kAB   (RareMoments::fold at m = 1)
+// Exact integers, the same totals as the 8-byte entries give.  The 32-bit lane accumulators still hold: the tile budget counts 8
+// bytes per rare site whichever stream it sits in, so a tile has at most tile_blocks x 64 x 4 WPS / 8 <= 2^21 rare sites at
+// tile_blocks = 4096, 2^13 per lane, each adding at most 2 x 511 to a sum — below 2^24 next to the rows' 2^27.
+__device__ __forceinline__ void single_range(const uint16_t *__restrict__ single, uint64_t s0, uint64_t s1, const uint16_t *hcode,
+                                             const PopSizes &ps, LaneAcc32 &acc) {
+    constexpr int SU = 4;
+    const uint64_t *words = reinterpret_cast<const uint64_t *>(single);
+    const uint64_t w0 = s0 >> 2, w1 = (s1 + 3) >> 2;
+    const uint32_t head = (uint32_t)(s0 & 3), tail = (uint32_t)(s1 & 3);  // slots cut off the first word, slots kept of the last (0: all)
+    uint32_t k = 0, kA = 0, kB = 0, kP = 0, kAB = 0;
+    for (uint64_t w = w0 + threadIdx.x; w < w1; w += 256 * SU) {
+        uint64_t v[SU];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+            const uint64_t i = w + 256 * u;
+            v[u] = stream_load(words + (i < w1 ? i : w1 - 1));  // past the range: a word of it again, dropped below
+        }
+        uint32_t code = 0;
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+            const uint64_t i = w + 256 * u;
+            uint64_t x = i < w1 ? v[u] : ~0ull;
+            uint32_t in = i < w1 ? 4u : 0u;
+            if (i == w0 && head) { x |= (1ull << (16 * head)) - 1ull; in -= head; }
+            if (i == w1 - 1 && tail) { x |= ~0ull << (16 * tail); in -= 4u - tail; }
+            const uint32_t lo = (uint32_t)x, hi = (uint32_t)(x >> 32);
+            code += (uint32_t)hcode[lo & RARE_CODE_NONE] + (uint32_t)hcode[(lo >> 16) & RARE_CODE_NONE] +
+                    (uint32_t)hcode[hi & RARE_CODE_NONE] + (uint32_t)hcode[(hi >> 16) & RARE_CODE_NONE];
+            k += in;
+        }
+        kA += code & 31u; kB += (code >> 5) & 31u; kP += (code >> 10) & 31u; kAB += code >> 15;
+    }
+    acc.s_all += k;
+    acc.s_p += ps.nP > 1u ? kP : 0u;
+    acc.s_a += ps.nA > 1u ? kA : 0u;
+    acc.s_b += ps.nB > 1u ? kB : 0u;
+    acc.q_p += kP * (ps.nP - 1u);
+    acc.q_a += kA * (ps.nA - 1u);
+    acc.q_b += kB * (ps.nB - 1u);
+    acc.q_ab += ps.nB * kA + ps.nA * kB - 2u * kAB;
 }
 
 // entries [e0, e1) of a tile, thread t takes e0 + t, e0 + t + 256, ...: RU coalesced 512-byte wave loads in flight per wave
@@ -221,13 +273,19 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
                                                                                const uint64_t *__restrict__ rare,
                                                                                const ScanTile *__restrict__ tiles,
                                                                                const MaskArgs<WPS> mk, const PopSizes ps,
-                                                                               TilePartial *__restrict__ out) {
+                                                                               TilePartial *__restrict__ out,
+                                                                               const uint16_t *__restrict__ single,
+                                                                               const SingleRange *__restrict__ singles) {
     const ScanTile t = tiles[blockIdx.x];
+    // packed route: the tile's range of the singleton stream (null otherwise), indexed like the tile — no dependent load
+    SingleRange sr = {0, 0};
+    if (singles) sr = singles[blockIdx.x];
     const TileBlocks tb = tile_blocks_of(t);
     // split index: this thread's share of the haplotype code table (RareMoments) — the mask words of haplotypes threadIdx.x and
     // threadIdx.x + 256, read from the kernel arguments (MaskArgs is p | a | b) BEFORE the rows so that they arrive behind them
     constexpr int CODE_PER_THREAD = (32 * WPS + 255) / 256;
-    const bool has_rare = t.rare_end > t.rare_begin;  // workgroup-uniform
+    const bool has_single = sr.end > sr.begin;                            // workgroup-uniform, as the next
+    const bool has_rare = t.rare_end > t.rare_begin || has_single;        // the table is needed
     uint32_t mw[CODE_PER_THREAD][3] = {};
     if (has_rare) {
         const uint32_t *mkw = reinterpret_cast<const uint32_t *>(&mk);
@@ -276,11 +334,13 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         for (int j = 0; j < CODE_PER_THREAD; ++j) {
             const uint32_t h = threadIdx.x + 256u * j, bit = h & 31u;
             if (h < 32u * WPS)
-                hcode[h] = (uint16_t)(((mw[j][1] >> bit) & 1u) | (((mw[j][2] >> bit) & 1u) << 5) | (((mw[j][0] >> bit) & 1u) << 10));
+                hcode[h] = (uint16_t)(((mw[j][1] >> bit) & 1u) | (((mw[j][2] >> bit) & 1u) << 5) | (((mw[j][0] >> bit) & 1u) << 10) |
+                                      (((mw[j][1] & mw[j][2]) >> bit & 1u) << 15));
         }
         if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
         __syncthreads();
         rare_range_coded(rare, t.rare_begin, t.rare_end, hcode, ps, acc);
+        if (has_single) single_range(single, sr.begin, sr.end, hcode, ps, acc);
     }
     LaneAcc wide;
     wide.s_all = acc.s_all; wide.s_p = acc.s_p; wide.s_a = acc.s_a; wide.s_b = acc.s_b;
@@ -640,18 +700,24 @@ static uint32_t popcount_vec(const std::vector<uint32_t> &v) {
 // ordered as the edges are.  A segment's blocks and entries are cut into the same number of tiles by their bytes (an entry is
 // 8 B, tile_blocks blocks the budget): one workgroup reads a share of both streams.  Without rare entries the tiles are those
 // of the unsplit index.
+// Packed route: an edge is the triple (site, multi entry, singleton), ordered as the pairs are (no rare site between two edges
+// means neither a singleton nor a multi between them).  A rare site counts 8 bytes toward the budget whichever stream holds it and
+// a segment's rare sites are cut where the split route cuts them; each part takes the same fraction of the singletons and of the
+// multis as of all the rare sites.  So the tiles, their number and every window's tile range are those of the split route.
 void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
-    const impop_window *windows = rt.mapped.data(), *rare = rt.split ? rt.rare_w.data() : nullptr;
+    const impop_window *windows = rt.mapped.data(), *rare = rt.split ? rt.rare_w.data() : nullptr,
+                       *single = rt.packed ? rt.single_w.data() : nullptr;
     std::vector<ScanTile> &tiles = rt.tiles;
     struct Cut {
-        uint64_t c, r;
-        bool operator<(const Cut &o) const { return c < o.c || (c == o.c && r < o.r); }
-        bool operator==(const Cut &o) const { return c == o.c && r == o.r; }
+        uint64_t c, r, g;
+        bool operator<(const Cut &o) const { return c < o.c || (c == o.c && (r < o.r || (r == o.r && g < o.g))); }
+        bool operator==(const Cut &o) const { return c == o.c && r == o.r && g == o.g; }
     };
-    auto lo = [&](uint64_t i) { return Cut{windows[i].site_begin, rare ? rare[i].site_begin : 0}; };
-    auto hi = [&](uint64_t i) { return Cut{windows[i].site_end, rare ? rare[i].site_end : 0}; };
+    auto lo = [&](uint64_t i) { return Cut{windows[i].site_begin, rare ? rare[i].site_begin : 0, single ? single[i].site_begin : 0}; };
+    auto hi = [&](uint64_t i) { return Cut{windows[i].site_end, rare ? rare[i].site_end : 0, single ? single[i].site_end : 0}; };
     auto nonempty = [&](uint64_t i) {
-        return windows[i].site_end > windows[i].site_begin || (rare && rare[i].site_end > rare[i].site_begin);
+        return windows[i].site_end > windows[i].site_begin || (rare && rare[i].site_end > rare[i].site_begin) ||
+               (single && single[i].site_end > single[i].site_begin);
     };
     std::vector<Cut> cuts;
     cuts.reserve(2 * n_windows);
@@ -679,17 +745,24 @@ void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
         // tiles are cut on 64-site block boundaries of the layout so interior tiles read whole blocks, in equal shares:
         // a 781-block segment under a 512-block limit becomes 391 + 390 blocks, not 512 + 269
         const Cut s = cuts[k], e = cuts[k + 1];
-        const uint64_t nblk = e.c > s.c ? (e.c + 63) / 64 - s.c / 64 : 0, nr = e.r - s.r;
+        const uint64_t nm = e.r - s.r, ng = e.g - s.g, nr = nm + ng;  // entries of rt.rare, singletons, rare sites
+        const uint64_t nblk = e.c > s.c ? (e.c + 63) / 64 - s.c / 64 : 0;
         const uint64_t n_parts = std::max<uint64_t>(1, (nblk * row_bytes + nr * 8 + budget - 1) / budget);
         const uint64_t per = (nblk + n_parts - 1) / n_parts, per_r = (nr + n_parts - 1) / n_parts;
-        uint64_t cs = s.c, rs = s.r;
+        // the first `off` of the segment's nr rare sites hold this many of its x singletons (multis): off itself when x == nr
+        auto share = [&](uint64_t x, uint64_t off) { return nr ? (uint64_t)((unsigned __int128)x * off / nr) : 0; };
+        uint64_t cs = s.c, rs = 0;
         for (uint64_t part = 0; part < n_parts; ++part) {
             uint64_t ce = cs;
             if (cs < e.c) ce = std::min(e.c, ((cs / 64) + per) * 64);  // block-aligned end
-            const uint64_t re = std::min(e.r, rs + per_r);
+            const uint64_t re = std::min(nr, rs + per_r);
             if (ce > cs || re > rs) {
-                tiles.push_back({cs, ce, rs, re});
+                tiles.push_back({cs, ce, s.r + share(nm, rs), s.r + share(nm, re)});
                 rt.bytes_streamed += tile_bytes_streamed(tiles.back(), wps);
+                if (rt.packed) {
+                    rt.singles.push_back({s.g + share(ng, rs), s.g + share(ng, re)});
+                    rt.bytes_streamed += single_bytes_streamed(rt.singles.back());
+                }
             }
             cs = ce;
             rs = re;
@@ -719,7 +792,9 @@ struct impop_scan_plan {
     impop_ctx *ctx = nullptr;
     const impop_matrix *m = nullptr;
     const uint32_t *sb = nullptr;  // the layout launches stream: m->d_vsb (route "indexed", tiles in kept-site coordinates) or m->d_sb
-    const uint64_t *rare = nullptr;  // split index: m->d_vrare (tiles' rare ranges), else null
+    const uint64_t *rare = nullptr;  // split index: m->d_vrare (tiles' rare ranges), packed route: m->d_vmulti, else null
+    const uint16_t *single = nullptr;  // packed route: m->d_vsingle and every tile's range of it, else null
+    SingleRange *d_singles = nullptr;
     uint64_t n_windows = 0, n_tiles = 0, bytes_streamed = 0;
     PopSizes ps{};
     bool subset_p = false;
@@ -769,6 +844,8 @@ static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m,
     for (uint64_t i = 0; i < n_windows; ++i) blocks += (w[i].site_end - w[i].site_begin + 63) / 64;
     if (rt.split)
         for (uint64_t i = 0; i < n_windows; ++i) entries += rt.rare_w[i].site_end - rt.rare_w[i].site_begin;
+    if (rt.packed)  // a rare site of either packed stream counts as its 8-byte entry: the split route's tile size
+        for (uint64_t i = 0; i < n_windows; ++i) entries += rt.single_w[i].site_end - rt.single_w[i].site_begin;
     if (m->compact && blocks > m->g.n_block) blocks = m->g.n_block;
     if (rt.indexed && blocks > m->vg.n_block) blocks = m->vg.n_block;
     if (entries > m->n_vrare) entries = m->n_vrare;
@@ -799,18 +876,22 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
 
 // IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it.  kept_sites = every
 // variable site of an indexed route; rare_sites / rare_bytes = the split index's rare entries (all of the matrix / the plan's);
-// split = on, or off:<the reason there is none, blanks as _>
+// split = on, or off:<the reason there is none, blanks as _>; single_sites = the singleton stream of a packed route (all of the
+// matrix), rare_streamed = the bytes of rare sites the plan really reads (rare_bytes keeps counting 8 per rare site)
 static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
     if (!trace_on()) return;
     const char *why = rt.indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
-    uint64_t rare_bytes = 0;
+    uint64_t rare_bytes = 0, rare_streamed = 0;
     for (const ScanTile &t : rt.tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
+    rare_streamed = rare_bytes;
+    for (const SingleRange &r : rt.singles) { rare_bytes += (r.end - r.begin) * 8ull; rare_streamed += single_bytes_streamed(r); }
     std::string off = "off:" + (!m->wt_prefix.empty() && m->d_vrare ? std::string("site weights") : m->rskip);
     for (char &ch : off) ch = ch == ' ' ? '_' : ch;
-    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s%s%s\n",
+    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu%s%s\n",
             rt.indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(rt.indexed ? m->n_vkept : m->g.n_site),
             (unsigned long long)rt.tiles.size(), (unsigned long long)rt.bytes_streamed, (unsigned long long)n_windows,
-            (unsigned long long)(rt.split ? m->n_vrare : 0), (unsigned long long)rare_bytes, rt.split ? "on" : off.c_str(), *why ? " why=" : "", why);
+            (unsigned long long)(rt.split ? m->n_vrare : 0), (unsigned long long)rare_bytes, rt.split ? "on" : off.c_str(), (unsigned long long)(rt.packed ? m->n_vsingle : 0),
+            (unsigned long long)rare_streamed, *why ? " why=" : "", why);
     fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
 }
 
@@ -838,13 +919,16 @@ int impop::check_window_weights(const char *fn, const impop_matrix *m, const imp
 // index when the matrix has one and no site weights (d_wt is indexed by matrix site), with the rare-entry stream of a split
 // index; else the matrix itself (compacted: original coordinates -> kept-site index ranges).  tile_blocks 0: the default.
 int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                      uint32_t tile_blocks, ScanRoute &rt) {
+                      uint32_t tile_blocks, ScanRoute &rt, bool want_packed) {
     rt.indexed = m->d_vsb != nullptr && m->wt_prefix.empty();
     rt.split = rt.indexed && m->d_vrare != nullptr;
+    rt.packed = want_packed && rt.split && m->d_vsingle != nullptr;
     rt.sb = rt.indexed ? m->d_vsb : m->d_sb;
-    rt.rare = rt.split ? m->d_vrare : nullptr;
+    rt.rare = rt.packed ? m->d_vmulti : rt.split ? m->d_vrare : nullptr;
+    rt.single = rt.packed ? m->d_vsingle : nullptr;
     if (rt.indexed) {
-        const int rc = map_windows_index(ctx, m, windows, n_windows, rt.mapped, rt.split ? &rt.rare_w : nullptr);
+        const int rc = map_windows_index(ctx, m, windows, n_windows, rt.mapped, rt.split ? &rt.rare_w : nullptr,
+                                         rt.packed ? &rt.single_w : nullptr);
         if (rc) return rc;
     } else {
         map_windows(m, windows, n_windows, rt.mapped);
@@ -908,10 +992,10 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
     }
     if (p->subset_p)
         hipLaunchKernelGGL((scan_tiles_kernel<WPS, true>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare,
-                           p->d_tiles, mk, p->ps, p->d_parts);
+                           p->d_tiles, mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles);
     else
         hipLaunchKernelGGL((scan_tiles_kernel<WPS, false>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare,
-                           p->d_tiles, mk, p->ps, p->d_parts);
+                           p->d_tiles, mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles);
 }
 
 IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows,
@@ -937,11 +1021,13 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     ScanRoute rt;
-    rc = scan_route("impop_scan", ctx, m, windows, n_windows, prm.tile_blocks, rt);
+    // the plan will launch the fixed-WPS kernel (impop_scan_plan_launch), the one reader of the singleton stream
+    const bool fixed_wps = m->wt_prefix.empty() && m->g.wps <= 16;
+    rc = scan_route("impop_scan", ctx, m, windows, n_windows, prm.tile_blocks, rt, fixed_wps);
     if (rc) return rc;
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
-    p->sb = rt.sb; p->rare = rt.rare;
+    p->sb = rt.sb; p->rare = rt.rare; p->single = rt.single;
     p->n_tiles = rt.tiles.size(); p->bytes_streamed = rt.bytes_streamed;
     m->users++;
     p->d_pi_mode = prm.d_pi_mode; p->s_scope = prm.s_scope;
@@ -962,6 +1048,10 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     PLAN_TRY(hipMalloc((void **)&p->d_wins, std::max<size_t>(n_windows, 1) * sizeof(WinDesc)));
     PLAN_TRY(hipMalloc((void **)&p->d_out, std::max<size_t>(n_windows, 1) * sizeof(impop_window_stats)));
     PLAN_TRY(hipMalloc((void **)&p->d_masks, (size_t)3 * wps * 4));
+    if (rt.packed) {
+        PLAN_TRY(hipMalloc((void **)&p->d_singles, std::max<size_t>(rt.singles.size(), 1) * sizeof(SingleRange)));
+        if (!rt.singles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_singles, rt.singles.data(), rt.singles.size() * sizeof(SingleRange), hipMemcpyHostToDevice, ctx->stream));
+    }
     if (!rt.tiles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_tiles, rt.tiles.data(), rt.tiles.size() * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
     if (n_windows) PLAN_TRY(hipMemcpyAsync(p->d_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
     PLAN_TRY(hipMemcpyAsync(p->d_masks, p->masks.data(), (size_t)3 * wps * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -1091,6 +1181,7 @@ IMPOP_API int impop_scan_plan_destroy(impop_scan_plan *p) {
     if (p->d_wins) hipFree(p->d_wins);
     if (p->d_out) hipFree(p->d_out);
     if (p->d_masks) hipFree(p->d_masks);
+    if (p->d_singles) hipFree(p->d_singles);
     if (p->m) p->m->users--;
     delete p;
     return IMPOP_OK;

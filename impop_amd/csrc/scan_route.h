@@ -23,6 +23,13 @@ struct ScanTile {
 inline uint64_t tile_bytes_streamed(const ScanTile &t, uint32_t wps) {
     return (t.site_end > t.site_begin ? ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps : 0) + (t.rare_end - t.rare_begin) * 8ull;
 }
+// Packed route: a tile's range of the singleton stream (internal.h, d_vsingle), in uint16 units; the tile's rare range is then
+// one of d_vmulti.  A parallel array to the tiles, so that ScanTile and the kernels that read only it stay what they are.
+struct SingleRange {
+    uint64_t begin, end;
+};
+// what a workgroup reads of it: the aligned 8-byte words (four singletons each) the range touches
+inline uint64_t single_bytes_streamed(const SingleRange &r) { return r.end > r.begin ? ((r.end + 3) / 4 - r.begin / 4) * 8ull : 0; }
 struct WinDesc {
     uint64_t t0, t1;  // tile range
     uint64_t n_sites;
@@ -36,6 +43,13 @@ struct ScanRoute {
     const uint32_t *sb = nullptr;
     const uint64_t *rare = nullptr;           // null unless split
     std::vector<impop_window> mapped, rare_w;  // the windows as ranges of sb's sites and (split) of rare's entries
+    // packed: the rare sites come from the matrix's two packed streams instead of d_vrare.  rare = d_vmulti and rare_w its
+    // ranges, single = d_vsingle and single_w its ranges; singles[k] is tile k's singleton range.  Only scan_route sets it,
+    // and only for a caller that asked (impop_scan_plan_create for the fixed-WPS kernel).
+    bool packed = false;
+    const uint16_t *single = nullptr;
+    std::vector<impop_window> single_w;
+    std::vector<SingleRange> singles;
     uint32_t tile_blocks = 0;
     std::vector<ScanTile> tiles;
     std::vector<WinDesc> wins;
@@ -49,8 +63,9 @@ int check_windows(const char *fn, const impop_matrix *m, const impop_window *win
 // every window's W (window_W: its length, or the sum of its columns' weights) fits the 32 bits a record gives it
 int check_window_weights(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
 // windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams.  tile_blocks 0: the default.
+// want_packed: the caller's kernel reads the singleton stream; the route is packed when the matrix has one (else as without)
 int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-               uint32_t tile_blocks, ScanRoute &rt);
+               uint32_t tile_blocks, ScanRoute &rt, bool want_packed = false);
 // a tile-size override for tests, <name>=n in the environment: n clamped to 1..4096, 0 where the variable is unset or empty
 uint32_t env_tile_blocks(const char *name);
 

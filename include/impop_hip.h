@@ -91,6 +91,12 @@ int impop_ctx_device_name(impop_ctx *ctx, char *buf, size_t buflen);
  * read both streams and return the same records.  IMPOP_KEEP_NO_RARE_SPLIT keeps every kept site as a row (the unsplit
  * index); impop_matrix_scan_split_info reports the split, or why there is none. */
 #define IMPOP_KEEP_NO_RARE_SPLIT 8u
+/* A split index of a matrix of 65..512 haplotypes also keeps its rare sites as two packed streams, which the plans of
+ * impop_scan_plan_create read instead of the 8-byte entries: one uint16 per SINGLETON site (min(c, n - c) = 1: the index of
+ * its one minor-allele carrier) and the 8-byte entries of the other rare sites alone.  Records do not change; a launch
+ * reads 2 bytes per singleton instead of 8.  Every other call keeps reading the 8-byte entries, which stay complete.
+ * IMPOP_KEEP_NO_SINGLE_STREAM leaves the two streams out; impop_matrix_scan_single_info reports them, or why there are none. */
+#define IMPOP_KEEP_NO_SINGLE_STREAM 16u
 
 int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits_hap_major, uint32_t n_hap, uint64_t n_site,
                         uint64_t row_stride_words, uint32_t keep_flags, impop_matrix **out);
@@ -159,6 +165,13 @@ int impop_matrix_scan_index_info(const impop_matrix *m, uint64_t *n_kept, uint64
  * receives the reason, else "".  All outputs nullable. */
 int impop_matrix_scan_split_info(const impop_matrix *m, uint64_t *n_rare, uint64_t *n_common, uint64_t *rare_bytes, char *why,
                                  size_t why_len);
+/* The singleton stream of that split (see IMPOP_KEEP_NO_SINGLE_STREAM): n_single = singleton sites (2 bytes each), n_multi = the
+ * other rare sites (8-byte entries), stream_bytes = device memory the two streams and their per-block mask and prefix take
+ * (counted in impop_matrix_scan_index_info's index_bytes); all 0 when there is none, and why (nullable, why_len bytes) receives
+ * the reason, else "".  impop_matrix_scan_split_info reports what it did before: every rare site, 8 bytes each.  All outputs
+ * nullable. */
+int impop_matrix_scan_single_info(const impop_matrix *m, uint64_t *n_single, uint64_t *n_multi, uint64_t *stream_bytes, char *why,
+                                  size_t why_len);
 int impop_matrix_free(impop_ctx *ctx, impop_matrix *m);
 
 /* ---- windowed scan: pi + Hudson Fst + Tajima's D + S in one pass ------------
