@@ -6,7 +6,7 @@
 // matrix: onto its kept sites, with d_pos for their coordinates — the dropped sites are monomorphic, nobody is heterozygous
 // there, and those that every haplotype carries are counted into hom_alt from the matrix's bitmap of them), so a record cannot
 // depend on the upload's keep flags.  The variable-site index is not used: it keeps no kept-site -> original-coordinate table,
-// and runs need coordinates.  Per chunk of windows, on the tiles of build_tiles (elementary segments: a tile's interior is the
+// and runs need coordinates.  Per chunk of windows, on the tiles of cut_tiles (elementary segments: a tile's interior is the
 // same for every window that contains it, so overlapping windows share tiles), two launches:
 //   1. dip_tile_kernel    one workgroup per tile.  Every wave takes a contiguous share of the tile's 64-site blocks, in block
 //                         order.  Per block, lane = site: c = carriers among the 2N -> sum_p, s_p; the ballot transpose of every
@@ -225,17 +225,13 @@ __global__ __launch_bounds__(DIP_T) void dip_window_kernel(const DipSummary *__r
     if (s_bad || s_tile_het != s_het) atomicOr(err, DEV_ERR_DIPLOID);
 }
 
-// The tile of scan.hip's streaming kernels: ~256 KB of matrix per workgroup, at least 16 tiles per CU wanted, never below 32
-// blocks (wide sites: 4).  IMPOP_DIPLOID_TILE_BLOCKS=n (1..4096) overrides it, so that tests reach many-tile windows on small
-// matrices.
-static uint32_t dip_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const std::vector<impop_window> &mapped) {
+// The tile of scan.hip's streaming kernels (tile_cut.h, default_tile_rule).  IMPOP_DIPLOID_TILE_BLOCKS=n (1..4096) overrides it,
+// so that tests reach many-tile windows on small matrices.
+static uint32_t dip_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const std::vector<LayoutWindow> &lw) {
     if (const uint32_t e = env_tile_blocks("IMPOP_DIPLOID_TILE_BLOCKS")) return e;
-    const uint32_t wps = m->g.wps, by_bytes = wps > 16 ? std::max<uint32_t>(4, 1024 / wps) : std::max<uint32_t>(32, 1024 / wps);
     uint64_t blocks = 0;
-    for (const impop_window &w : mapped) blocks += (w.site_end - w.site_begin + 63) / 64;
-    blocks = std::min<uint64_t>(blocks, m->g.n_block);
-    const uint64_t by_parallelism = blocks / (16ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
-    return (uint32_t)std::max<uint64_t>(std::min<uint32_t>(32, by_bytes), std::min<uint64_t>(by_bytes, by_parallelism));
+    for (const LayoutWindow &w : lw) blocks += (w.hi.c - w.lo.c + 63) / 64;
+    return default_tile_rule(m->g.wps, std::min<uint64_t>(blocks, m->g.n_block), ctx->n_cu);
 }
 
 }  // namespace impop
@@ -280,9 +276,9 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
     // the rows of the matrix itself, whatever index was built beside them
     ScanRoute rt;
     rt.sb = m->d_sb;
-    map_windows(m, windows, n_windows, rt.mapped);
-    rt.tile_blocks = dip_tile_blocks(ctx, m, rt.mapped);
-    build_tiles(rt, n_windows, wps);
+    rt.lw = row_windows(m, windows, n_windows);
+    rt.tile_blocks = dip_tile_blocks(ctx, m, rt.lw);
+    cut_tiles(rt.lw, rt.tile_blocks, wps, false, rt);
 
     // device bytes of a chunk: per tile N summaries, the totals and the tile; per window the record, the descriptor and (if
     // wanted) N rows
@@ -338,7 +334,7 @@ IMPOP_API int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const im
         const size_t nt = c.tiles.size(), cnt = c.w_end - c.w_begin;
         for (size_t k = 0; k < nt; ++k) {
             h_tiles[k] = rt.tiles[c.tiles[k]];
-            bytes_streamed += tile_bytes_streamed(h_tiles[k], wps);  // tiles of build_tiles without an index: never empty, no rare entries
+            bytes_streamed += tile_bytes_streamed(h_tiles[k], wps);  // tiles of cut_tiles without an index: never empty, no rare entries
         }
         for (size_t k = 0; k < cnt; ++k) {
             const impop_window &w = windows[c.w_begin + k];

@@ -9,6 +9,7 @@
 
 #include "../../include/impop_hip.h"
 #include "carve.h"
+#include "tile_cut.h"
 
 #define IMPOP_API extern "C" __attribute__((visibility("default")))
 
@@ -116,6 +117,29 @@ __host__ __device__ inline uint64_t rare_set_slot(uint64_t slots, uint32_t i, ui
 }
 __host__ __device__ inline uint64_t rare_pack(uint64_t slots, uint32_t m, bool zeros) { return slots | m | (zeros ? 0x8000u : 0u); }
 
+
+// ---- the site classes of the scan index (impop_matrix::idx) ----
+// KEPT: the variable sites, 0 < c < n.  COMMON: the kept sites with min(c, n - c) > IMPOP_RARE_MAX (split index).  SINGLE: the
+// singleton sites, min(c, n - c) = 1 (singleton stream).  A class is built only on top of the one before it.
+enum SiteClass { KEPT, COMMON, SINGLE, N_CLASS };
+// Per 64-site block of the matrix, the mask of a class's sites and the number of them before the block: n_block + 1 entries
+// each, one allocation, mask first; the last entry is {0, the total}.  mask null: the class was not built.
+struct BlockRank {
+    const uint64_t *mask = nullptr, *base = nullptr;
+    // the sites of the class left of site s <= n_site, with no search
+    __host__ __device__ uint64_t operator()(uint64_t s) const {
+        return base[s >> 6] + (uint64_t)__builtin_popcountll(mask[s >> 6] & ((1ull << (s & 63)) - 1ull));
+    }
+};
+struct ClassRanks {  // as a kernel argument
+    BlockRank k[N_CLASS];
+};
+// what the kernels that write SB64 add for the index: per block, each wanted class's mask and its popcount (mask null: not wanted)
+struct ClassOut {
+    uint64_t *mask[N_CLASS] = {nullptr, nullptr, nullptr};
+    uint32_t *cnt[N_CLASS] = {nullptr, nullptr, nullptr};
+};
+
 }  // namespace impop
 
 struct impop_ctx {
@@ -205,24 +229,20 @@ struct impop_matrix {
     std::vector<uint64_t> wt_prefix;  // weighted: prefix sums of the (ORIGINAL, if compacted) site weights, n + 1 entries
     // variable-site scan index (layout.hip index_begin / index_finish), built with every full matrix unless the caller opts out
     // (IMPOP_KEEP_DENSE_SCAN): the sites that vary among ALL haplotypes (0 < c < n) as an SB64 copy of their own (geometry vg:
-    // the matrix's wps / G / r, n_site = the number kept, the same slack block), plus per 64-site block of the matrix the mask
-    // of its kept sites and the number kept before it (n_block + 1 entries each; the last is {0, n_kept}), so a window edge s
-    // maps in O(1) to kept(s) = vbase[s >> 6] + popc(vmask[s >> 6] & ((1 << (s & 63)) - 1)).  Scan plans of an unweighted
-    // matrix stream d_vsb instead of d_sb (scan.hip); what the index holds depends on the matrix alone.
+    // the matrix's wps / G / r, n_site = the number kept, the same slack block), plus the per-block rank table of the kept sites,
+    // idx[KEPT], so a window edge s maps in O(1) to kept(s) = idx[KEPT](s).  Scan plans of an unweighted matrix stream d_vsb
+    // instead of d_sb (scan.hip); what the index holds depends on the matrix alone.
     uint32_t *d_vsb = nullptr;                         // null: no index (vskip says why)
-    uint64_t *d_vmask = nullptr, *d_vbase = nullptr;   // one allocation, d_vmask first
+    impop::BlockRank idx[impop::N_CLASS];              // one allocation per class
     impop::SbGeom vg;
     uint64_t vsb_bytes = 0, vidx_bytes = 0;            // kept-site SB64 without slack; everything the index allocated
     uint64_t n_vkept = 0;                              // variable sites (rare + common when split)
     std::string vskip = "not built";
     // rare/common split of the index (layout.hip rare_entries_kernel): a kept site is RARE when min(c, n - c) <= IMPOP_RARE_MAX.
     // Then d_vsb (geometry vg) holds the COMMON kept sites only, and d_vrare one 8-byte entry per rare site in site order
-    // (format: rare_pack and its readers above).
-    // Per 64-site block of the matrix: d_cmask = mask of its common sites, d_cbase = common sites before it (n_block + 1
-    // entries each, one allocation); rare(s) = kept(s) - common(s).  d_vrare null: no split (rskip says why), d_vsb holds every
-    // kept site as before.
+    // (format: rare_pack and its readers above).  idx[COMMON] ranks the common sites; rare(s) = kept(s) - common(s).
+    // d_vrare null: no split (rskip says why), d_vsb holds every kept site as before.
     uint64_t *d_vrare = nullptr;
-    uint64_t *d_cmask = nullptr, *d_cbase = nullptr;
     uint64_t n_vrare = 0;
     std::string rskip = "not built";
     // singleton stream of the split index (layout.hip rare_entries_kernel; built for wps <= 16, the range of its one consumer,
@@ -230,12 +250,10 @@ struct impop_matrix {
     // SINGLETON site, min(c, n - c) = 1: bits 0..14 = the one carrier of the minor allele, bit 15 = that haplotype carries 0 (the
     // meaning of bit 15 of an 8-byte entry); padded with 0xFFFF to a multiple of 8 bytes plus 8 bytes of slack, so aligned 8-byte
     // loads of any range stay inside the allocation.  d_vmulti holds the other rare sites (min(c, n - c) = 2 or 3) as 8-byte
-    // entries (rare_pack).  Per 64-site block of the matrix: d_smask = mask of its singleton sites, d_sbase = singletons before
-    // it (n_block + 1 entries each, one allocation); single(s) as common(s), multi(s) = rare(s) - single(s).  d_vrare stays
-    // complete.  d_vsingle null: no stream (sskip says why).
+    // entries (rare_pack).  idx[SINGLE] ranks the singleton sites; multi(s) = rare(s) - single(s).  d_vrare stays complete.
+    // d_vsingle null: no stream (sskip says why).
     uint16_t *d_vsingle = nullptr;
     uint64_t *d_vmulti = nullptr;
-    uint64_t *d_smask = nullptr, *d_sbase = nullptr;
     uint64_t n_vsingle = 0, vsingle_bytes = 0;  // singleton sites; everything the stream allocated
     std::string sskip = "not built";
     int device = 0;
@@ -304,19 +322,14 @@ constexpr unsigned POS_COARSE_SHIFT = 12;
 // variable-site scan index: window edges in matrix coordinates -> kept-site index ranges of d_vsb (one thread per edge, no search)
 // the index a kept fraction above 1/IMPOP_INDEX_MAX_KEPT_INV of the sites is not built for (the dense stream is then nearly as short)
 constexpr uint64_t IMPOP_INDEX_MAX_KEPT_INV = 4;
-// split index: the same edges also as common-site (`mapped`) and rare-entry (`rare`) ranges; rare == nullptr: kept-site ranges.
-// single (nullable; needs rare and the matrix's singleton stream): the edges as ranges of d_vsingle, and `rare` then holds the
-// ranges of d_vmulti, rare(s) - single(s)
-int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
-                      std::vector<impop_window> *rare, std::vector<impop_window> *single = nullptr);
+// top = the last class wanted: KEPT gives kept-site ranges (r = g = 0), COMMON common-site ranges and the rare entries
+// between them (r = kept(s) - common(s)), SINGLE also the singletons (g = single(s)) and r = multi(s) = rare(s) - single(s)
+int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, SiteClass top,
+                      std::vector<LayoutWindow> &out);
 
 // layout.hip
-// d_mask / d_cnt (nullable): also write the variable-site mask of every block and its popcount (scan index);
-// d_cmask / d_ccnt (nullable): the same for the common sites, min(c, n - c) > IMPOP_RARE_MAX (split index);
-// d_smask / d_scnt (nullable): the same for the singleton sites, min(c, n - c) = 1 (singleton stream)
-int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb,
-                    uint64_t *d_mask = nullptr, uint32_t *d_cnt = nullptr, uint64_t *d_cmask = nullptr, uint32_t *d_ccnt = nullptr,
-                    uint64_t *d_smask = nullptr, uint32_t *d_scnt = nullptr);
+// idx: also write the masks and counts of the classes it names (scan index)
+int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb, const ClassOut &idx = ClassOut());
 // rb_nb == 0: plain hap-major rows of hm_stride dwords; else RB32 addressing with rb_nb cells per row group
 int launch_sb_to_hm(impop_ctx *ctx, const uint32_t *d_sb, const SbGeom &g, uint64_t blk_begin, uint64_t blk_end,
                     uint32_t *d_hm, uint64_t hm_stride, uint32_t n_rows, uint64_t rb_nb = 0, uint32_t phi_row = 0xFFFFFFFFu);

@@ -3,10 +3,7 @@
 #include <string.h>
 
 #include <algorithm>
-
 #include <vector>
-
-#include <algorithm>
 
 #include "device_utils.h"
 #include "internal.h"
@@ -25,17 +22,27 @@ static SbGeom make_geom(uint32_t n_hap, uint64_t n_site) {
     return g;
 }
 
+// The index's share of a kernel that writes SB64, one wave per block and lane = site: c of the lane's n_hap haplotypes carry
+// its site (live: the site exists).  One ballot per wanted class; lane 0 stores the mask and its popcount.
+__device__ inline void class_ballots(const ClassOut &o, bool live, uint32_t c, uint32_t n_hap, uint64_t b, uint32_t lane) {
+    const bool in[N_CLASS] = {c > 0 && c < n_hap, c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX, c == 1 || n_hap - c == 1};
+#pragma unroll
+    for (int k = 0; k < N_CLASS; ++k)
+        if (o.mask[k]) {
+            const uint64_t v = __ballot(live && in[k]);
+            if (lane == 0) { o.mask[k][b] = v; o.cnt[k][b] = (uint32_t)__popcll(v); }
+        }
+}
+
 // ---- hap-major -> SB64 --------------------------------------------------------------
 // One wave per 64-site block.  For each 32-haplotype dword k, lanes 0..31 fetch the
 // 64-site word of haplotype 32k+lane; v_readlane broadcasts each of them and every lane
 // (= site) picks its own bit: a 32x64 bit transpose in 32 readlane+bfe+lshl_or steps.
-// mask / cnt (nullable): the variable-site mask of every block and its popcount (scan index), one ballot per block.
+// idx: the scan index's masks and counts (class_ballots).
 __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restrict__ hm, uint64_t hm_stride,
                                                        uint32_t n_rows, uint32_t wps, uint32_t G, uint32_t r,
                                                        uint64_t n_block, uint32_t *__restrict__ sb, uint64_t n_site,
-                                                       uint32_t n_hap, uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt,
-                                                       uint64_t *__restrict__ cmask, uint32_t *__restrict__ ccnt,
-                                                       uint64_t *__restrict__ smask, uint32_t *__restrict__ scnt) {
+                                                       uint32_t n_hap, ClassOut idx) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;  // wave-uniform
@@ -56,18 +63,7 @@ __global__ __launch_bounds__(256) void hm_to_sb_kernel(const uint32_t *__restric
         sb[sb_index(wps, G, r, b, lane, k)] = out;
         c += __popc(out);
     }
-    if (mask) {
-        const uint64_t v = __ballot(b * 64 + lane < n_site && c > 0 && c < n_hap);
-        if (lane == 0) { mask[b] = v; cnt[b] = (uint32_t)__popcll(v); }
-    }
-    if (cmask) {
-        const uint64_t v = __ballot(b * 64 + lane < n_site && c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX);
-        if (lane == 0) { cmask[b] = v; ccnt[b] = (uint32_t)__popcll(v); }
-    }
-    if (smask) {  // singleton stream: min(c, n - c) = 1 (built for n_hap > 64 only: such a site varies)
-        const uint64_t v = __ballot(b * 64 + lane < n_site && (c == 1 || n_hap - c == 1));
-        if (lane == 0) { smask[b] = v; scnt[b] = (uint32_t)__popcll(v); }
-    }
+    class_ballots(idx, b * 64 + lane < n_site, c, n_hap, b, lane);
 }
 
 // ---- SB64 -> hap-major ---------------------------------------------------------------
@@ -152,14 +148,13 @@ __global__ void hm_clear_tail_kernel(uint32_t *hm, uint64_t hm_stride, uint32_t 
     }
 }
 
-int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb, uint64_t *d_mask,
-                    uint32_t *d_cnt, uint64_t *d_cmask, uint32_t *d_ccnt, uint64_t *d_smask, uint32_t *d_scnt) {
+int launch_hm_to_sb(impop_ctx *ctx, const uint32_t *d_hm, uint64_t hm_stride, const SbGeom &g, uint32_t *d_sb, const ClassOut &idx) {
     if (g.n_block == 0) return IMPOP_OK;
     const uint64_t grid = (g.n_block + 3) / 4;
     REQUIRE(grid < 0x7FFFFFFFull, "matrix too long for one launch (%llu blocks)", (unsigned long long)g.n_block);
     const uint32_t n_rows = (g.n_hap + 95) / 96 * 96;
     hipLaunchKernelGGL(hm_to_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, d_hm, hm_stride, n_rows, g.wps,
-                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, d_mask, d_cnt, d_cmask, d_ccnt, d_smask, d_scnt);
+                       g.G, g.r, g.n_block, d_sb, g.n_site, g.n_hap, idx);
     HIP_TRY(hipGetLastError());
     return IMPOP_OK;
 }
@@ -187,10 +182,7 @@ struct SynthDev {
 // tables: fmask[f*wps + k] (haplotypes of founder f in dword k), then valid[k]
 __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_t *__restrict__ tables, uint32_t wps,
                                                        uint32_t G, uint32_t r, uint64_t n_block, uint64_t n_site,
-                                                       uint64_t site0, uint32_t *__restrict__ sb, uint32_t n_hap,
-                                                       uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt, uint64_t *__restrict__ cmask,
-                                                       uint32_t *__restrict__ ccnt, uint64_t *__restrict__ smask,
-                                                       uint32_t *__restrict__ scnt) {
+                                                       uint64_t site0, uint32_t *__restrict__ sb, uint32_t n_hap, ClassOut idx) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= n_block) return;
@@ -205,7 +197,7 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
     for (uint32_t f = 0; f < p.n_founder; ++f)
         if ((uint32_t)(synth_hash(p.seed, 2 + f, s) >> 32) < p.thr_founder) fl |= 1u << f;
     const uint32_t *valid = tables + (uint64_t)p.n_founder * wps;
-    uint32_t c = 0;  // carriers of this lane's site: the scan index's mask comes from a ballot, not from a second pass
+    uint32_t c = 0;  // carriers of this lane's site: the scan index's masks come from ballots, not from a second pass
     for (uint32_t k = 0; k < wps; ++k) {
         uint32_t w = anc;
         uint32_t m = fl;
@@ -220,18 +212,7 @@ __global__ __launch_bounds__(256) void synth_sb_kernel(SynthDev p, const uint32_
         c += __popc(w);
         sb[sb_index(wps, G, r, b, lane, k)] = w;
     }
-    if (mask) {
-        const uint64_t v = __ballot(live && c > 0 && c < n_hap);
-        if (lane == 0) { mask[b] = v; cnt[b] = (uint32_t)__popcll(v); }
-    }
-    if (cmask) {  // split index: the common kept sites, min(c, n - c) > IMPOP_RARE_MAX
-        const uint64_t v = __ballot(live && c > IMPOP_RARE_MAX && n_hap - c > IMPOP_RARE_MAX);
-        if (lane == 0) { cmask[b] = v; ccnt[b] = (uint32_t)__popcll(v); }
-    }
-    if (smask) {  // singleton stream: the singleton sites, min(c, n - c) = 1
-        const uint64_t v = __ballot(live && (c == 1 || n_hap - c == 1));
-        if (lane == 0) { smask[b] = v; scnt[b] = (uint32_t)__popcll(v); }
-    }
+    class_ballots(idx, live, c, n_hap, b, lane);
 }
 
 static int alloc_matrix(impop_ctx *ctx, uint32_t n_hap, uint64_t n_site, bool want_hm, impop_matrix **out) {
@@ -280,14 +261,10 @@ static int alloc_matrix(impop_ctx *ctx, uint32_t n_hap, uint64_t n_site, bool wa
 // variable-site scan index (built below, next to the compaction kernels it shares): index_begin allocates the per-block mask
 // and prefix (or records why there is none), the kernel that writes SB64 fills the mask by ballot, index_finish does the rest
 struct IndexBuild {
-    uint64_t *d_mask = nullptr;  // == m->d_vmask while the build goes on
-    uint32_t *d_cnt = nullptr;   // kept sites per block, n_block + 1 entries (inside d_tmp)
-    uint64_t *d_cmask = nullptr; // == m->d_cmask: split index wanted (else null)
-    uint32_t *d_ccnt = nullptr;  // common sites per block (inside d_tmp)
-    uint64_t *d_smask = nullptr; // == m->d_smask: singleton stream wanted (else null)
-    uint32_t *d_scnt = nullptr;  // singleton sites per block (inside d_tmp)
-    void *d_tmp = nullptr;       // transient: counts, chunk sums, totals
-    uint64_t *d_pos = nullptr;   // transient: source site of every kept site
+    ClassOut out;               // per class wanted: its mask (== m->idx[k].mask while the build goes on) and its counts (inside d_tmp)
+    uint32_t n_class = 0;       // the classes wanted: KEPT .. n_class - 1
+    void *d_tmp = nullptr;      // transient: counts, chunk sums, totals (IndexTmp)
+    uint64_t *d_pos = nullptr;  // transient: source site of every kept site
     uint64_t n_chunks = 0;
     IndexBuild() = default;
     IndexBuild(const IndexBuild &) = delete;
@@ -342,7 +319,7 @@ IMPOP_API int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits, uint32_t
     IndexBuild ib;
     rc = index_begin(ctx, m, keep_flags, ib);
     if (rc) return fail(rc);
-    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.d_mask, ib.d_cnt, ib.d_cmask, ib.d_ccnt, ib.d_smask, ib.d_scnt);
+    rc = launch_hm_to_sb(ctx, d_hm, hm_stride, m->g, m->d_sb, ib.out);
     if (rc) return fail(rc);
     rc = index_finish(ctx, m, ib);
     if (rc) return fail(rc);
@@ -409,8 +386,7 @@ IMPOP_API int impop_matrix_synthetic_slab(impop_ctx *ctx, uint32_t n_hap, uint64
             return fail(IMPOP_E_INVALID);
         }
         hipLaunchKernelGGL(synth_sb_kernel, dim3((uint32_t)grid), dim3(256), 0, ctx->stream, sp, (const uint32_t *)d_tab,
-                           wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb, n_hap, ib.d_mask, ib.d_cnt,
-                           ib.d_cmask, ib.d_ccnt, ib.d_smask, ib.d_scnt);
+                           wps, m->g.G, m->g.r, m->g.n_block, n_site, site_begin, m->d_sb, n_hap, ib.out);
         if ((e = hipGetLastError()) != hipSuccess) return fail(hip_fail(e, "synth_sb_kernel", __FILE__, __LINE__));
         if (want_hm) {
             rc = launch_sb_to_hm(ctx, m->d_sb, m->g, 0, m->g.n_block, m->d_rb, 0, m->n_hap_pad, m->rb_nb, m->phi_row);
@@ -474,26 +450,28 @@ namespace impop {
 // grid-stride over blocks: a workgroup per 4 blocks cost more in launches than in bytes (37 ms for 14.6 GB)
 __global__ __launch_bounds__(256) void variable_mask_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G,
                                                             uint32_t r, uint64_t n_block, uint64_t n_site, uint32_t n_hap,
-                                                            uint64_t *__restrict__ mask, uint32_t *__restrict__ cnt,
-                                                            uint64_t *__restrict__ ones /* nullable: sites with c = n */) {
+                                                            ClassOut idx /* KEPT */, uint64_t *__restrict__ ones /* nullable: sites with c = n */) {
     const uint32_t lane = threadIdx.x & 63;
     const uint64_t stride = (uint64_t)gridDim.x * 4;
     for (uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); b < n_block; b += stride) {
         uint32_t c = 0;
         sb_for_each_dword<false>(sb + b * 64ull * wps, G, r, lane, [&](uint32_t, uint32_t w) { c += __popc(w); });
-        const bool var = (b * 64 + lane < n_site) && c > 0 && c < n_hap;
-        const uint64_t m = __ballot(var);
+        class_ballots(idx, b * 64 + lane < n_site, c, n_hap, b, lane);
         const uint64_t o = ones ? __ballot((b * 64 + lane < n_site) && c == n_hap) : 0ull;
-        if (lane == 0) {
-            mask[b] = m; cnt[b] = (uint32_t)__popcll(m);
-            if (ones) ones[b] = o;
-        }
+        if (lane == 0 && ones) ones[b] = o;
     }
 }
 
-constexpr uint32_t SCAN_CHUNK = 1024;  // blocks per workgroup in the two-level exclusive scan
-__global__ __launch_bounds__(256) void chunk_sum_kernel(const uint32_t *__restrict__ cnt, uint64_t n, uint64_t *__restrict__ chunk_sum) {
+// Two-level exclusive scan of per-block counts, up to N_CLASS arrays in one launch each (the class on grid dimension y):
+// base[k][b] = the sum of cnt[k][< b], total[k] = the sum of them all.  chunk: n_chunks sums per class, class after class.
+constexpr uint32_t SCAN_CHUNK = 1024;  // blocks per workgroup
+struct PrefixArgs {
+    const uint32_t *cnt[N_CLASS];
+    uint64_t *base[N_CLASS];
+};
+__global__ __launch_bounds__(256) void chunk_sum_kernel(PrefixArgs a, uint64_t n, uint64_t *__restrict__ chunk_sum) {
     __shared__ uint64_t sh[4];
+    const uint32_t *cnt = a.cnt[blockIdx.y];
     const uint64_t base = (uint64_t)blockIdx.x * SCAN_CHUNK;
     uint64_t t = 0;
     for (uint32_t i = threadIdx.x; i < SCAN_CHUNK; i += 256)
@@ -501,23 +479,25 @@ __global__ __launch_bounds__(256) void chunk_sum_kernel(const uint32_t *__restri
     t = wave_sum_u64(t);
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = t;
     __syncthreads();
-    if (threadIdx.x == 0) chunk_sum[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
+    if (threadIdx.x == 0) chunk_sum[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];
 }
-__global__ void chunk_scan_kernel(uint64_t *chunk_sum, uint64_t n_chunks, uint64_t *total) {  // one thread: n_chunks is small
-    if (threadIdx.x || blockIdx.x) return;
+__global__ void chunk_scan_kernel(uint64_t *chunk_sum, uint64_t n_chunks, uint64_t *total) {  // one thread per class: n_chunks is small
+    if (threadIdx.x) return;
+    chunk_sum += blockIdx.x * n_chunks;
     uint64_t run = 0;
     for (uint64_t i = 0; i < n_chunks; ++i) {
         const uint64_t v = chunk_sum[i];
         chunk_sum[i] = run;
         run += v;
     }
-    *total = run;
+    total[blockIdx.x] = run;
 }
-__global__ __launch_bounds__(64) void block_base_kernel(const uint32_t *__restrict__ cnt, uint64_t n, const uint64_t *__restrict__ chunk_off,
-                                                        uint64_t *__restrict__ base) {
+__global__ __launch_bounds__(64) void block_base_kernel(PrefixArgs a, uint64_t n, const uint64_t *__restrict__ chunk_off) {
     // one wave per chunk: 16 rounds of a 64-wide exclusive scan
+    const uint32_t *cnt = a.cnt[blockIdx.y];
+    uint64_t *base = a.base[blockIdx.y];
     const uint64_t b0 = (uint64_t)blockIdx.x * SCAN_CHUNK;
-    uint64_t run = chunk_off[blockIdx.x];
+    uint64_t run = chunk_off[(uint64_t)blockIdx.y * gridDim.x + blockIdx.x];
     for (uint32_t rnd = 0; rnd < SCAN_CHUNK / 64; ++rnd) {
         const uint64_t i = b0 + rnd * 64 + threadIdx.x;
         const uint64_t v = i < n ? cnt[i] : 0;
@@ -695,20 +675,17 @@ __global__ __launch_bounds__(256) void gather_kept_kernel(const uint32_t *__rest
 
 // Rare kept sites -> 8-byte entries (layout: internal.h, d_vrare).  One thread per source block walks its rare sites (a few per
 // block) and reads each one's wps dwords twice: the count picks the allele to list, then the first (at most three) carriers of it.
-// Singleton stream (smask non-null): the same pass also writes every rare site to one of the two packed streams, a singleton
+// Singleton stream (rk has the SINGLE class): the same pass also writes every rare site to one of the two packed streams, a singleton
 // as its carrier's 16 bits to out_single, any other as its entry to out_multi (internal.h, d_vsingle / d_vmulti).
 __global__ __launch_bounds__(256) void rare_entries_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
-                                                           uint32_t n_hap, const uint64_t *__restrict__ vmask,
-                                                           const uint64_t *__restrict__ vbase, const uint64_t *__restrict__ cmask,
-                                                           const uint64_t *__restrict__ cbase, uint64_t n_block,
-                                                           uint64_t *__restrict__ out, const uint64_t *__restrict__ smask,
-                                                           const uint64_t *__restrict__ sbase, uint16_t *__restrict__ out_single,
-                                                           uint64_t *__restrict__ out_multi) {
+                                                           uint32_t n_hap, ClassRanks rk, uint64_t n_block, uint64_t *__restrict__ out,
+                                                           uint16_t *__restrict__ out_single, uint64_t *__restrict__ out_multi) {
     const uint64_t b = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (b >= n_block) return;
-    uint64_t v = vmask[b] & ~cmask[b], d = vbase[b] - cbase[b];
-    const uint64_t sm = smask ? smask[b] : 0ull;
-    uint64_t ds = smask ? sbase[b] : 0ull, dm = d - ds;
+    const bool single = rk.k[SINGLE].mask != nullptr;
+    uint64_t v = rk.k[KEPT].mask[b] & ~rk.k[COMMON].mask[b], d = rk.k[KEPT].base[b] - rk.k[COMMON].base[b];
+    const uint64_t sm = single ? rk.k[SINGLE].mask[b] : 0ull;
+    uint64_t ds = single ? rk.k[SINGLE].base[b] : 0ull, dm = d - ds;
     while (v) {
         const uint32_t l = (uint32_t)__builtin_ctzll(v);
         v &= v - 1;
@@ -728,241 +705,191 @@ __global__ __launch_bounds__(256) void rare_entries_kernel(const uint32_t *__res
         }
         const uint64_t e = rare_pack(slots, m, zeros);
         out[d++] = e;
-        if (smask) {
+        if (single) {
             if ((sm >> l) & 1ull) out_single[ds++] = (uint16_t)(rare_slot(e, 0) | (zeros ? 0x8000u : 0u));
             else out_multi[dm++] = e;
         }
     }
 }
 
-// edge s -> kept(s); split index: -> common(s) into `out` and kept(s) - common(s) into `out_rare`
-__global__ void map_edges_index_kernel(const uint64_t *__restrict__ mask, const uint64_t *__restrict__ base,
-                                       const uint64_t *__restrict__ cmask, const uint64_t *__restrict__ cbase,
-                                       const uint64_t *__restrict__ smask, const uint64_t *__restrict__ sbase,
-                                       const impop_window *__restrict__ win, uint64_t n_win, impop_window *__restrict__ out,
-                                       impop_window *__restrict__ out_rare, impop_window *__restrict__ out_single) {
+// window edge s -> its place in every stream of the route (tile_cut.h, EdgeCut): the ranks of the classes rk names
+__global__ void map_edges_index_kernel(ClassRanks rk, const impop_window *__restrict__ win, uint64_t n_win, LayoutWindow *__restrict__ out) {
     const uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= 2 * n_win) return;
     const uint64_t key = (e & 1) ? win[e >> 1].site_end : win[e >> 1].site_begin;  // <= n_site: entry n_block exists
-    const uint64_t below = (1ull << (key & 63)) - 1ull;
-    const uint64_t kept = base[key >> 6] + (uint64_t)__popcll(mask[key >> 6] & below);
-    uint64_t v = kept;
-    if (cmask) {
-        v = cbase[key >> 6] + (uint64_t)__popcll(cmask[key >> 6] & below);
-        uint64_t rare = kept - v;
-        if (smask) {  // singleton stream: single(s) into out_single, multi(s) = rare(s) - single(s) into out_rare
-            const uint64_t sg = sbase[key >> 6] + (uint64_t)__popcll(smask[key >> 6] & below);
-            rare -= sg;
-            if (e & 1) out_single[e >> 1].site_end = sg;
-            else { out_single[e >> 1].site_begin = sg; out_single[e >> 1].seq_len = win[e >> 1].seq_len; }
-        }
-        if (e & 1) out_rare[e >> 1].site_end = rare;
-        else { out_rare[e >> 1].site_begin = rare; out_rare[e >> 1].seq_len = win[e >> 1].seq_len; }
-    }
-    if (e & 1) out[e >> 1].site_end = v;
-    else { out[e >> 1].site_begin = v; out[e >> 1].seq_len = win[e >> 1].seq_len; }
+    uint64_t n[N_CLASS];
+#pragma unroll
+    for (int k = 0; k < N_CLASS; ++k) n[k] = rk.k[k].mask ? rk.k[k](key) : 0;
+    // unsplit: the kept sites; split: the common sites, rare(s) = kept(s) - common(s) less the singletons, the singletons
+    const EdgeCut c = rk.k[COMMON].mask ? EdgeCut{n[COMMON], n[KEPT] - n[COMMON] - n[SINGLE], n[SINGLE]} : EdgeCut{n[KEPT], 0, 0};
+    if (e & 1) out[e >> 1].hi = c;
+    else { out[e >> 1].lo = c; out[e >> 1].seq_len = win[e >> 1].seq_len; }
 }
 
-int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, std::vector<impop_window> &mapped,
-                      std::vector<impop_window> *rare, std::vector<impop_window> *single) {
-    mapped.resize(n);
-    const bool split = rare && m->d_vrare;
-    const bool packed = split && single && m->d_vsingle;
-    if (split) rare->resize(n);
-    if (packed) single->resize(n);
+int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n, SiteClass top,
+                      std::vector<LayoutWindow> &out) {
+    out.resize(n);
     if (!n) return IMPOP_OK;
     REQUIRE(m->d_vsb, "map_windows_index: the matrix has no scan index");
     REQUIRE((2 * n + 255) / 256 < 0x7FFFFFFFull, "map_windows_index: too many windows");
+    ClassRanks rk;
+    for (int k = KEPT; k <= top; ++k) rk.k[k] = m->idx[k];
+    Carve L;
+    const size_t o_in = L.take<impop_window>(n), o_out = L.take<LayoutWindow>(n);
     void *d = nullptr;
-    const int rc = ctx_aux(ctx, 0, 4 * n * sizeof(impop_window), &d);  // as map_windows_device: idle outside the all-pairs path
+    const int rc = ctx_aux(ctx, 0, L.total(), &d);  // as map_windows_device: idle outside the all-pairs path
     if (rc) return rc;
-    impop_window *d_in = reinterpret_cast<impop_window *>(d), *d_out = d_in + n, *d_rare = d_out + n, *d_single = d_rare + n;
-    HIP_TRY(hipMemcpyAsync(d_in, windows, n * sizeof(impop_window), hipMemcpyHostToDevice, ctx->stream));
-    hipLaunchKernelGGL(map_edges_index_kernel, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream, m->d_vmask,
-                       m->d_vbase, split ? m->d_cmask : nullptr, split ? m->d_cbase : nullptr, packed ? m->d_smask : nullptr,
-                       packed ? m->d_sbase : nullptr, d_in, n, d_out, d_rare, d_single);
+    HIP_TRY(hipMemcpyAsync(L.at<impop_window>(d, o_in), windows, n * sizeof(impop_window), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(map_edges_index_kernel, dim3((uint32_t)((2 * n + 255) / 256)), dim3(256), 0, ctx->stream, rk,
+                       (const impop_window *)L.at<impop_window>(d, o_in), n, L.at<LayoutWindow>(d, o_out));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(mapped.data(), d_out, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
-    if (split) HIP_TRY(hipMemcpyAsync(rare->data(), d_rare, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
-    if (packed) HIP_TRY(hipMemcpyAsync(single->data(), d_single, n * sizeof(impop_window), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out.data(), L.at<LayoutWindow>(d, o_out), n * sizeof(LayoutWindow), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return IMPOP_OK;
 }
 
-static void single_drop(impop_matrix *m, std::string why) {
-    if (m->d_smask) hipFree(m->d_smask);
-    if (m->d_vsingle) hipFree(m->d_vsingle);
-    if (m->d_vmulti) hipFree(m->d_vmulti);
-    m->d_smask = m->d_sbase = nullptr;
-    m->d_vsingle = nullptr;
-    m->d_vmulti = nullptr;
-    m->n_vsingle = m->vsingle_bytes = 0;
-    m->sskip = std::move(why);
+// Drops the index from class k upward: the class's rank table and what was built on it; the classes above it lose theirs for
+// want of the one below.
+static void index_drop(impop_matrix *m, SiteClass k, std::string why) {
+    std::string *const skip[N_CLASS] = {&m->vskip, &m->rskip, &m->sskip};
+    static const char *const no_lower[N_CLASS] = {"", "no scan index", "no rare/common split"};
+    for (int c = k; c < N_CLASS; ++c) {
+        if (m->idx[c].mask) hipFree((void *)m->idx[c].mask);
+        m->idx[c] = BlockRank();
+        *skip[c] = no_lower[c];
+    }
+    *skip[k] = std::move(why);
+    switch (k) {
+    case KEPT:
+        if (m->d_vsb) hipFree(m->d_vsb);
+        m->d_vsb = nullptr;
+        m->vg = SbGeom();
+        m->vsb_bytes = m->vidx_bytes = 0;
+        m->n_vkept = 0;
+        [[fallthrough]];
+    case COMMON:
+        if (m->d_vrare) hipFree(m->d_vrare);
+        m->d_vrare = nullptr;
+        m->n_vrare = 0;
+        [[fallthrough]];
+    default:
+        if (m->d_vsingle) hipFree(m->d_vsingle);
+        if (m->d_vmulti) hipFree(m->d_vmulti);
+        m->d_vsingle = nullptr;
+        m->d_vmulti = nullptr;
+        m->n_vsingle = m->vsingle_bytes = 0;
+    }
 }
 
-static void split_drop(impop_matrix *m, std::string why) {
-    single_drop(m, "no rare/common split");
-    if (m->d_cmask) hipFree(m->d_cmask);
-    if (m->d_vrare) hipFree(m->d_vrare);
-    m->d_cmask = m->d_cbase = nullptr;
-    m->d_vrare = nullptr;
-    m->n_vrare = 0;
-    m->rskip = std::move(why);
-}
-
-static void index_drop(impop_matrix *m, std::string why) {
-    if (m->d_vmask) hipFree(m->d_vmask);
-    if (m->d_vsb) hipFree(m->d_vsb);
-    m->d_vmask = m->d_vbase = nullptr;
-    m->d_vsb = nullptr;
-    m->vg = SbGeom();
-    m->vsb_bytes = m->vidx_bytes = 0;
-    m->n_vkept = 0;
-    split_drop(m, "no scan index");
-    m->vskip = std::move(why);
-}
-
-// An allocation of the index that fails leaves the matrix without one: the error is cleared, the matrix is still made.
-static bool index_alloc(impop_matrix *m, void **p, size_t bytes, const char *what) {
+// An allocation of the index that fails leaves the matrix without class k and the classes above it: the error is cleared, the
+// matrix is still made.
+static bool index_alloc(impop_matrix *m, SiteClass k, void **p, size_t bytes, const char *what) {
     if (hipMalloc(p, bytes) == hipSuccess) return true;
     (void)hipGetLastError();
     *p = nullptr;
-    index_drop(m, std::string("hipMalloc of the ") + what + " failed");
+    index_drop(m, k, std::string("hipMalloc of the ") + what + " failed");
     return false;
 }
 
-// d_tmp: kept counts | common counts | singleton counts | chunk sums (kept) | (common) | (singleton) | the three totals
+// d_tmp: per class its ne counts | per class its chunk sums | the totals
 struct IndexTmp {
-    size_t o_ccnt, o_scnt, o_chunk, o_cchunk, o_schunk, o_total, bytes;
+    size_t o_cnt[N_CLASS], o_chunk, o_total, bytes;
     IndexTmp(uint64_t ne, uint64_t n_chunks) {
         Carve L;
-        L.take<uint32_t>(ne);  // the kept counts, at offset 0
-        o_ccnt = L.take<uint32_t>(ne); o_scnt = L.take<uint32_t>(ne);
-        o_chunk = L.take<uint64_t>(n_chunks); o_cchunk = L.take<uint64_t>(n_chunks); o_schunk = L.take<uint64_t>(n_chunks);
-        o_total = L.take<uint64_t>(3);
+        for (size_t &o : o_cnt) o = L.take<uint32_t>(ne);
+        o_chunk = L.take<uint64_t>(N_CLASS * n_chunks);
+        o_total = L.take<uint64_t>(N_CLASS);
         bytes = L.total();
     }
 };
 
 static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, IndexBuild &ib) {
-    if (keep_flags & IMPOP_KEEP_DENSE_SCAN) {
-        m->vskip = "opted out (IMPOP_KEEP_DENSE_SCAN)";
-        m->rskip = "no scan index";
-        m->sskip = "no rare/common split";
-        return IMPOP_OK;
-    }
-    const uint64_t ne = m->g.n_block + 1;  // one entry past the last block: an edge at n_site maps there when 64 | n_site
+    const SbGeom &g = m->g;
+    // why a class is not wanted (null: it is), and what to call its allocation.  The rare/common split: an entry (8 B) must be
+    // narrower than a row, and its haplotype indices fit 16 bits; the singleton stream: read by the fixed-WPS scan kernel alone
+    const struct {
+        const char *skip, *what;
+    } rule[N_CLASS] = {
+        {keep_flags & IMPOP_KEEP_DENSE_SCAN ? "opted out (IMPOP_KEEP_DENSE_SCAN)" : nullptr, "index mask"},
+        {keep_flags & IMPOP_KEEP_NO_RARE_SPLIT ? "opted out (IMPOP_KEEP_NO_RARE_SPLIT)"
+         : g.wps <= 2                          ? "n_hap <= 64: a row is no wider than an 8-byte rare entry"
+         : g.n_hap > 65535                     ? "n_hap > 65535: haplotype indices do not fit 16 bits"
+                                               : nullptr,
+         "common-site mask"},
+        {keep_flags & IMPOP_KEEP_NO_SINGLE_STREAM ? "opted out (IMPOP_KEEP_NO_SINGLE_STREAM)"
+         : g.wps > 16                             ? "n_hap > 512: scans run the any-n kernel, which reads the 8-byte entries"
+                                                  : nullptr,
+         "singleton-site mask"},
+    };
+    const uint64_t ne = g.n_block + 1;  // one entry past the last block: an edge at n_site maps there when 64 | n_site
     ib.n_chunks = (ne + SCAN_CHUNK - 1) / SCAN_CHUNK;
-    void *meta = nullptr;
-    if (!index_alloc(m, &meta, 2 * ne * 8, "index mask")) return IMPOP_OK;
-    m->d_vmask = reinterpret_cast<uint64_t *>(meta);
-    m->d_vbase = m->d_vmask + ne;
     const IndexTmp lay(ne, ib.n_chunks);
-    if (!index_alloc(m, &ib.d_tmp, lay.bytes, "index counts")) return IMPOP_OK;
-    ib.d_mask = m->d_vmask;
-    ib.d_cnt = reinterpret_cast<uint32_t *>(ib.d_tmp);
-    HIP_TRY(hipMemsetAsync(m->d_vmask + m->g.n_block, 0, 8, ctx->stream));  // the entry past the last block keeps nothing
-    HIP_TRY(hipMemsetAsync(ib.d_cnt + m->g.n_block, 0, 4, ctx->stream));
-    // the rare/common split: an entry (8 B) must be narrower than a row, and its haplotype indices fit 16 bits
-    if (keep_flags & IMPOP_KEEP_NO_RARE_SPLIT) {
-        m->rskip = "opted out (IMPOP_KEEP_NO_RARE_SPLIT)";
-    } else if (m->g.wps <= 2) {
-        m->rskip = "n_hap <= 64: a row is no wider than an 8-byte rare entry";
-    } else if (m->g.n_hap > 65535) {
-        m->rskip = "n_hap > 65535: haplotype indices do not fit 16 bits";
-    } else {
-        void *cm = nullptr;
-        if (hipMalloc(&cm, 2 * ne * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            m->rskip = "hipMalloc of the common-site mask failed";
-        } else {
-            m->d_cmask = reinterpret_cast<uint64_t *>(cm);
-            m->d_cbase = m->d_cmask + ne;
-            ib.d_cmask = m->d_cmask;
-            ib.d_ccnt = reinterpret_cast<uint32_t *>((char *)ib.d_tmp + lay.o_ccnt);
-            HIP_TRY(hipMemsetAsync(m->d_cmask + m->g.n_block, 0, 8, ctx->stream));
-            HIP_TRY(hipMemsetAsync(ib.d_ccnt + m->g.n_block, 0, 4, ctx->stream));
+    for (int k = KEPT; k < N_CLASS; ++k) {
+        void *p = nullptr;
+        if (rule[k].skip) {
+            index_drop(m, (SiteClass)k, rule[k].skip);
+            break;
         }
-    }
-    // the singleton stream: read by the fixed-WPS scan kernel alone, so built for wps <= 16 only
-    if (!ib.d_cmask) {
-        m->sskip = "no rare/common split";
-    } else if (keep_flags & IMPOP_KEEP_NO_SINGLE_STREAM) {
-        m->sskip = "opted out (IMPOP_KEEP_NO_SINGLE_STREAM)";
-    } else if (m->g.wps > 16) {
-        m->sskip = "n_hap > 512: scans run the any-n kernel, which reads the 8-byte entries";
-    } else {
-        void *sm = nullptr;
-        if (hipMalloc(&sm, 2 * ne * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            m->sskip = "hipMalloc of the singleton-site mask failed";
-        } else {
-            m->d_smask = reinterpret_cast<uint64_t *>(sm);
-            m->d_sbase = m->d_smask + ne;
-            ib.d_smask = m->d_smask;
-            ib.d_scnt = reinterpret_cast<uint32_t *>((char *)ib.d_tmp + lay.o_scnt);
-            HIP_TRY(hipMemsetAsync(m->d_smask + m->g.n_block, 0, 8, ctx->stream));
-            HIP_TRY(hipMemsetAsync(ib.d_scnt + m->g.n_block, 0, 4, ctx->stream));
-        }
+        if (k == KEPT && !index_alloc(m, KEPT, &ib.d_tmp, lay.bytes, "index counts")) break;
+        if (!index_alloc(m, (SiteClass)k, &p, 2 * ne * 8, rule[k].what)) break;
+        m->idx[k] = {reinterpret_cast<uint64_t *>(p), reinterpret_cast<uint64_t *>(p) + ne};
+        ib.out.mask[k] = reinterpret_cast<uint64_t *>(p);
+        ib.out.cnt[k] = Carve::at<uint32_t>(ib.d_tmp, lay.o_cnt[k]);
+        ib.n_class = k + 1;
+        HIP_TRY(hipMemsetAsync(ib.out.mask[k] + g.n_block, 0, 8, ctx->stream));  // the entry past the last block holds nothing
+        HIP_TRY(hipMemsetAsync(ib.out.cnt[k] + g.n_block, 0, 4, ctx->stream));
     }
     return IMPOP_OK;
 }
 
-// exclusive prefix over ne per-block counts: base[b] = sum of cnt[< b]; the total goes to *d_total
-static void block_prefix(impop_ctx *ctx, const uint32_t *cnt, uint64_t ne, uint64_t n_chunks, uint64_t *d_chunk, uint64_t *d_total,
-                         uint64_t *base) {
-    hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)n_chunks), dim3(256), 0, ctx->stream, cnt, ne, d_chunk);
-    hipLaunchKernelGGL(chunk_scan_kernel, dim3(1), dim3(64), 0, ctx->stream, d_chunk, n_chunks, d_total);
-    hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)n_chunks), dim3(64), 0, ctx->stream, cnt, ne, d_chunk, base);
+// exclusive prefixes over ne per-block counts for n_class classes at once (chunk_sum_kernel): the totals go to d_total[k]
+static void block_prefix(impop_ctx *ctx, uint32_t n_class, const PrefixArgs &a, uint64_t ne, uint64_t n_chunks, uint64_t *d_chunk,
+                         uint64_t *d_total) {
+    hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)n_chunks, n_class), dim3(256), 0, ctx->stream, a, ne, d_chunk);
+    hipLaunchKernelGGL(chunk_scan_kernel, dim3(n_class), dim3(64), 0, ctx->stream, d_chunk, n_chunks, d_total);
+    hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)n_chunks, n_class), dim3(64), 0, ctx->stream, a, ne, (const uint64_t *)d_chunk);
 }
 
 static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
-    if (!ib.d_mask) return IMPOP_OK;
+    if (!ib.n_class) return IMPOP_OK;
     const SbGeom &g = m->g;
     const uint64_t nb = g.n_block, ne = nb + 1;
     const IndexTmp lay(ne, ib.n_chunks);
-    char *tmp = (char *)ib.d_tmp;
-    uint64_t *d_total = reinterpret_cast<uint64_t *>(tmp + lay.o_total);  // [0] kept, [1] common, [2] singleton
+    uint64_t *d_total = Carve::at<uint64_t>(ib.d_tmp, lay.o_total);
     REQUIRE(ib.n_chunks < 0x7FFFFFFFull && (nb + 255) / 256 < 0x7FFFFFFFull, "scan index: matrix too long for one launch");
-    block_prefix(ctx, ib.d_cnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_chunk), d_total, m->d_vbase);
-    if (ib.d_cmask)
-        block_prefix(ctx, ib.d_ccnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_cchunk), d_total + 1, m->d_cbase);
-    if (ib.d_smask)
-        block_prefix(ctx, ib.d_scnt, ne, ib.n_chunks, reinterpret_cast<uint64_t *>(tmp + lay.o_schunk), d_total + 2, m->d_sbase);
+    PrefixArgs pa{};
+    for (uint32_t k = 0; k < ib.n_class; ++k) {
+        pa.cnt[k] = ib.out.cnt[k];
+        pa.base[k] = ib.out.mask[k] + ne;
+    }
+    block_prefix(ctx, ib.n_class, pa, ne, ib.n_chunks, Carve::at<uint64_t>(ib.d_tmp, lay.o_chunk), d_total);
     HIP_TRY(hipGetLastError());
-    uint64_t totals[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(totals, d_total, ib.d_smask ? 24 : ib.d_cmask ? 16 : 8, hipMemcpyDeviceToHost, ctx->stream));
+    uint64_t totals[N_CLASS] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(totals, d_total, ib.n_class * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const uint64_t n_kept = totals[0];
+    const uint64_t n_kept = totals[KEPT];
     if (n_kept * IMPOP_INDEX_MAX_KEPT_INV > g.n_site) {
         char why[160];
         snprintf(why, sizeof why, "%llu of %llu sites vary: above 1/%llu", (unsigned long long)n_kept, (unsigned long long)g.n_site,
                  (unsigned long long)IMPOP_INDEX_MAX_KEPT_INV);
-        index_drop(m, why);
+        index_drop(m, KEPT, why);
         return IMPOP_OK;
     }
     // the rare entries first: when they cannot be had, d_vsb holds every kept site (the unsplit index)
-    if (ib.d_cmask) {
-        m->n_vrare = n_kept - totals[1];
-        void *rare = nullptr;
-        if (hipMalloc(&rare, std::max<uint64_t>(m->n_vrare, 1) * 8) != hipSuccess) {
-            (void)hipGetLastError();
-            split_drop(m, "hipMalloc of the rare entries failed");
-        } else {
-            m->d_vrare = reinterpret_cast<uint64_t *>(rare);
-            m->rskip.clear();
-        }
+    if (ib.n_class > COMMON) {
+        m->n_vrare = n_kept - totals[COMMON];
+        if (index_alloc(m, COMMON, (void **)&m->d_vrare, std::max<uint64_t>(m->n_vrare, 1) * 8, "rare entries")) m->rskip.clear();
     }
     // ... and their two packed streams; without them the split index is what it was
     uint64_t single_pad = 0;  // bytes of d_vsingle: whole 8-byte words, then 8 bytes of slack
-    if (ib.d_smask && m->d_vrare) {
-        m->n_vsingle = totals[2];
+    if (ib.n_class > SINGLE && m->d_vrare) {
+        m->n_vsingle = totals[SINGLE];
         single_pad = (m->n_vsingle * 2 + 7) / 8 * 8 + 8;
         void *sg = nullptr, *mu = nullptr;
         if (hipMalloc(&sg, single_pad) != hipSuccess || hipMalloc(&mu, std::max<uint64_t>(m->n_vrare - m->n_vsingle, 1) * 8) != hipSuccess) {
             (void)hipGetLastError();
             if (sg) hipFree(sg);
-            single_drop(m, "hipMalloc of the singleton stream failed");
+            index_drop(m, SINGLE, "hipMalloc of the singleton stream failed");
         } else {
             m->d_vsingle = reinterpret_cast<uint16_t *>(sg);
             m->d_vmulti = reinterpret_cast<uint64_t *>(mu);
@@ -972,28 +899,29 @@ static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
         }
     }
     const bool split = m->d_vrare != nullptr;
-    const uint64_t *smask = split ? m->d_cmask : m->d_vmask, *sbase = split ? m->d_cbase : m->d_vbase;
-    const uint64_t n_stream = split ? totals[1] : n_kept;  // sites of the SB64 copy
+    const BlockRank &stream = m->idx[split ? COMMON : KEPT];      // the class of the SB64 copy
+    const uint64_t n_stream = split ? totals[COMMON] : n_kept;  // ... and its sites
     m->n_vkept = n_kept;
     m->vg = make_geom(g.n_hap, n_stream);
     m->vsb_bytes = m->vg.n_block * 64ull * g.wps * 4ull;
     const uint64_t slack = 64ull * g.wps * 4ull + 256;  // as alloc_matrix: one block past the end may be prefetched
     void *vsb = nullptr;
-    if (!index_alloc(m, &vsb, m->vsb_bytes + slack, "kept-site layout")) return IMPOP_OK;
+    if (!index_alloc(m, KEPT, &vsb, m->vsb_bytes + slack, "kept-site layout")) return IMPOP_OK;
     m->d_vsb = reinterpret_cast<uint32_t *>(vsb);
     HIP_TRY(hipMemsetAsync((char *)vsb + m->vsb_bytes, 0, slack, ctx->stream));
     if (n_stream) {
-        if (!index_alloc(m, (void **)&ib.d_pos, n_stream * 8, "kept-site positions")) return IMPOP_OK;
+        if (!index_alloc(m, KEPT, (void **)&ib.d_pos, n_stream * 8, "kept-site positions")) return IMPOP_OK;
         REQUIRE((m->vg.n_block + 3) / 4 < 0x7FFFFFFFull, "scan index: too many kept sites for one launch");
-        hipLaunchKernelGGL(kept_pos_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, smask, sbase, nb, ib.d_pos);
+        hipLaunchKernelGGL(kept_pos_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, stream.mask, stream.base, nb, ib.d_pos);
         hipLaunchKernelGGL(gather_kept_kernel, dim3((uint32_t)((m->vg.n_block + 3) / 4)), dim3(256), 0, ctx->stream, m->d_sb, g.wps,
                            g.G, g.r, ib.d_pos, n_stream, m->vg.n_block, m->d_vsb);
         HIP_TRY(hipGetLastError());
     }
     if (split && m->n_vrare) {
+        ClassRanks rk;
+        for (int k = KEPT; k <= (m->d_vsingle ? SINGLE : COMMON); ++k) rk.k[k] = m->idx[k];
         hipLaunchKernelGGL(rare_entries_kernel, dim3((uint32_t)((nb + 255) / 256)), dim3(256), 0, ctx->stream, m->d_sb, g.wps, g.G, g.r,
-                           g.n_hap, m->d_vmask, m->d_vbase, m->d_cmask, m->d_cbase, nb, m->d_vrare, m->d_vsingle ? m->d_smask : nullptr,
-                           m->d_sbase, m->d_vsingle, m->d_vmulti);
+                           g.n_hap, rk, nb, m->d_vrare, m->d_vsingle, m->d_vmulti);
         HIP_TRY(hipGetLastError());
     }
     m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack + (split ? 2 * ne * 8 + std::max<uint64_t>(m->n_vrare, 1) * 8 : 0) + m->vsingle_bytes;
@@ -1014,12 +942,14 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     Carve L;
     const size_t o_mask = L.take<uint64_t>(nb), o_cnt = L.take<uint32_t>(nb), o_base = L.take<uint64_t>(nb), o_chunk = L.take<uint64_t>(n_chunks),
                  o_total = L.take<uint64_t>(1);
+    ClassOut kept;
     void *d = nullptr;
     int rc = ctx_scratch(ctx, L.total(), &d);
     if (rc) return rc;
     uint64_t *d_mask = L.at<uint64_t>(d, o_mask), *d_base = L.at<uint64_t>(d, o_base), *d_chunk = L.at<uint64_t>(d, o_chunk),
              *d_total = L.at<uint64_t>(d, o_total);
-    uint32_t *d_cnt = L.at<uint32_t>(d, o_cnt);
+    kept.mask[KEPT] = d_mask;
+    kept.cnt[KEPT] = L.at<uint32_t>(d, o_cnt);
     uint64_t n_kept = 0;
     // a source that kept its hap-major copy hands the all-pairs path on: the compacted matrix gets its own RB32
     // operand; the bitmap of the dropped all-ones sites is built for every compacted matrix (their count — for a weighted
@@ -1031,8 +961,8 @@ IMPOP_API int impop_matrix_compact(impop_ctx *ctx, const impop_matrix *in, impop
     if (nb) {
         const uint32_t wide_grid = (uint32_t)std::min<uint64_t>((nb + 3) / 4, 32ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
         hipLaunchKernelGGL(variable_mask_kernel, dim3(wide_grid), dim3(256), 0, ctx->stream, in->d_sb, g.wps, g.G, g.r, nb, g.n_site,
-                           g.n_hap, d_mask, d_cnt, d_ones);
-        block_prefix(ctx, d_cnt, nb, n_chunks, d_chunk, d_total, d_base);
+                           g.n_hap, kept, d_ones);
+        block_prefix(ctx, 1, PrefixArgs{{kept.cnt[KEPT]}, {d_base}}, nb, n_chunks, d_chunk, d_total);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&n_kept, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1211,13 +1141,7 @@ IMPOP_API int impop_matrix_free(impop_ctx *ctx, impop_matrix *m) {
     if (m->d_wt) hipFree(m->d_wt);
     if (m->d_onesmap) hipFree(m->d_onesmap);
     if (m->d_pos) hipFree(m->d_pos);
-    if (m->d_vmask) hipFree(m->d_vmask);
-    if (m->d_vsb) hipFree(m->d_vsb);
-    if (m->d_cmask) hipFree(m->d_cmask);
-    if (m->d_vrare) hipFree(m->d_vrare);
-    if (m->d_smask) hipFree(m->d_smask);
-    if (m->d_vsingle) hipFree(m->d_vsingle);
-    if (m->d_vmulti) hipFree(m->d_vmulti);
+    index_drop(m, KEPT, "");
     matrix_drop_derived(m);
     delete m;
     return IMPOP_OK;

@@ -693,97 +693,6 @@ static uint32_t popcount_vec(const std::vector<uint32_t> &v) {
     return c;
 }
 
-// windows -> elementary segments between sorted window boundaries (a segment is tiled iff some
-// window covers it, and exactly once however many windows overlap it) -> tiles of <= tile_blocks
-// 64-site blocks; every window becomes a contiguous tile range [t0, t1).
-// Split index: a window edge is the pair (site, entry); both map monotonically from the matrix coordinate, so the pairs are
-// ordered as the edges are.  A segment's blocks and entries are cut into the same number of tiles by their bytes (an entry is
-// 8 B, tile_blocks blocks the budget): one workgroup reads a share of both streams.  Without rare entries the tiles are those
-// of the unsplit index.
-// Packed route: an edge is the triple (site, multi entry, singleton), ordered as the pairs are (no rare site between two edges
-// means neither a singleton nor a multi between them).  A rare site counts 8 bytes toward the budget whichever stream holds it and
-// a segment's rare sites are cut where the split route cuts them; each part takes the same fraction of the singletons and of the
-// multis as of all the rare sites.  So the tiles, their number and every window's tile range are those of the split route.
-void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps) {
-    const impop_window *windows = rt.mapped.data(), *rare = rt.split ? rt.rare_w.data() : nullptr,
-                       *single = rt.packed ? rt.single_w.data() : nullptr;
-    std::vector<ScanTile> &tiles = rt.tiles;
-    struct Cut {
-        uint64_t c, r, g;
-        bool operator<(const Cut &o) const { return c < o.c || (c == o.c && (r < o.r || (r == o.r && g < o.g))); }
-        bool operator==(const Cut &o) const { return c == o.c && r == o.r && g == o.g; }
-    };
-    auto lo = [&](uint64_t i) { return Cut{windows[i].site_begin, rare ? rare[i].site_begin : 0, single ? single[i].site_begin : 0}; };
-    auto hi = [&](uint64_t i) { return Cut{windows[i].site_end, rare ? rare[i].site_end : 0, single ? single[i].site_end : 0}; };
-    auto nonempty = [&](uint64_t i) {
-        return windows[i].site_end > windows[i].site_begin || (rare && rare[i].site_end > rare[i].site_begin) ||
-               (single && single[i].site_end > single[i].site_begin);
-    };
-    std::vector<Cut> cuts;
-    cuts.reserve(2 * n_windows);
-    for (uint64_t i = 0; i < n_windows; ++i)
-        if (nonempty(i)) {
-            cuts.push_back(lo(i));
-            cuts.push_back(hi(i));
-        }
-    std::sort(cuts.begin(), cuts.end());
-    cuts.erase(std::unique(cuts.begin(), cuts.end()), cuts.end());
-    std::vector<int64_t> cover(cuts.size() + 1, 0);
-    auto cut_index = [&](const Cut &x) { return (size_t)(std::lower_bound(cuts.begin(), cuts.end(), x) - cuts.begin()); };
-    for (uint64_t i = 0; i < n_windows; ++i)
-        if (nonempty(i)) {
-            cover[cut_index(lo(i))] += 1;
-            cover[cut_index(hi(i))] -= 1;
-        }
-    const uint64_t row_bytes = 64ull * wps * 4ull, budget = (uint64_t)rt.tile_blocks * row_bytes;
-    std::vector<uint64_t> seg_tile_start(cuts.size() + 1, 0);
-    int64_t depth = 0;
-    for (size_t k = 0; k + 1 < cuts.size(); ++k) {
-        seg_tile_start[k] = tiles.size();
-        depth += cover[k];
-        if (depth <= 0) continue;
-        // tiles are cut on 64-site block boundaries of the layout so interior tiles read whole blocks, in equal shares:
-        // a 781-block segment under a 512-block limit becomes 391 + 390 blocks, not 512 + 269
-        const Cut s = cuts[k], e = cuts[k + 1];
-        const uint64_t nm = e.r - s.r, ng = e.g - s.g, nr = nm + ng;  // entries of rt.rare, singletons, rare sites
-        const uint64_t nblk = e.c > s.c ? (e.c + 63) / 64 - s.c / 64 : 0;
-        const uint64_t n_parts = std::max<uint64_t>(1, (nblk * row_bytes + nr * 8 + budget - 1) / budget);
-        const uint64_t per = (nblk + n_parts - 1) / n_parts, per_r = (nr + n_parts - 1) / n_parts;
-        // the first `off` of the segment's nr rare sites hold this many of its x singletons (multis): off itself when x == nr
-        auto share = [&](uint64_t x, uint64_t off) { return nr ? (uint64_t)((unsigned __int128)x * off / nr) : 0; };
-        uint64_t cs = s.c, rs = 0;
-        for (uint64_t part = 0; part < n_parts; ++part) {
-            uint64_t ce = cs;
-            if (cs < e.c) ce = std::min(e.c, ((cs / 64) + per) * 64);  // block-aligned end
-            const uint64_t re = std::min(nr, rs + per_r);
-            if (ce > cs || re > rs) {
-                tiles.push_back({cs, ce, s.r + share(nm, rs), s.r + share(nm, re)});
-                rt.bytes_streamed += tile_bytes_streamed(tiles.back(), wps);
-                if (rt.packed) {
-                    rt.singles.push_back({s.g + share(ng, rs), s.g + share(ng, re)});
-                    rt.bytes_streamed += single_bytes_streamed(rt.singles.back());
-                }
-            }
-            cs = ce;
-            rs = re;
-        }
-    }
-    if (!cuts.empty()) seg_tile_start[cuts.size() - 1] = tiles.size();
-    seg_tile_start[cuts.size()] = tiles.size();
-    rt.wins.resize(n_windows);
-    for (uint64_t i = 0; i < n_windows; ++i) {
-        WinDesc &w = rt.wins[i];
-        w.n_sites = windows[i].site_end - windows[i].site_begin;
-        w.seq_len = windows[i].seq_len;
-        if (nonempty(i)) {
-            w.t0 = seg_tile_start[cut_index(lo(i))];
-            w.t1 = seg_tile_start[cut_index(hi(i))];
-        } else {
-            w.t0 = w.t1 = 0;
-        }
-    }
-}
-
 }  // namespace impop
 
 using namespace impop;
@@ -811,7 +720,7 @@ struct impop_scan_plan {
 };
 
 // W of every window in ORIGINAL coordinates: its length, or the sum of its columns' weights (tiles of compacted matrices and
-// of indexed plans are in kept-site coordinates, so build_tiles' lengths are not the windows')
+// of indexed plans are in kept-site coordinates, so cut_tiles' lengths are not the windows')
 static int window_weights(const impop_matrix *m, const impop_window *windows, uint64_t n_windows, ScanRoute &rt) {
     for (uint64_t i = 0; i < n_windows; ++i) {
         uint64_t &W = rt.wins[i].n_sites;
@@ -828,30 +737,20 @@ static int window_weights(const impop_matrix *m, const impop_window *windows, ui
     return IMPOP_OK;
 }
 
-// Default tile: ~256 KB of matrix per workgroup (wide sites — the any-n kernel, wps > 16 — go down to 4 blocks = one per
-// wave), but never so large that a small job leaves CUs without work (>= 16 tiles per CU wanted), and never below the 32
-// blocks the kernel was tuned with.  With few haplotypes a 32-block tile is only a few KB and the per-workgroup costs
-// (launch, LDS reduction, partial store) bound the kernel instead of HBM: n = 32 ran at 2.6 TB/s with 32-block tiles and
-// 5.0 TB/s with whole-window tiles.
-// The blocks the windows cover are counted in the coordinates of the layout streamed (a compacted matrix: in the original
-// ones) and capped at that layout's length, which overlapping windows exceed; the rare entries of a split index count as
-// the blocks of rows their bytes would fill.
-static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                                    const ScanRoute &rt) {
-    const uint32_t by_bytes = m->g.wps > 16 ? std::max<uint32_t>(4, 1024 / m->g.wps) : std::max<uint32_t>(32, 1024 / m->g.wps);
-    const impop_window *w = rt.indexed ? rt.mapped.data() : windows;
+// The default tile (tile_cut.h, default_tile_rule).  The blocks the windows cover are counted in the coordinates of the layout
+// streamed (a compacted matrix: in the original ones) and capped at that layout's length, which overlapping windows exceed; the
+// rare sites of a split index, whichever stream holds them, count as the blocks of rows their 8-byte entries would fill.
+static uint32_t default_tile_blocks(const impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, const ScanRoute &rt) {
     uint64_t blocks = 0, entries = 0;
-    for (uint64_t i = 0; i < n_windows; ++i) blocks += (w[i].site_end - w[i].site_begin + 63) / 64;
-    if (rt.split)
-        for (uint64_t i = 0; i < n_windows; ++i) entries += rt.rare_w[i].site_end - rt.rare_w[i].site_begin;
-    if (rt.packed)  // a rare site of either packed stream counts as its 8-byte entry: the split route's tile size
-        for (uint64_t i = 0; i < n_windows; ++i) entries += rt.single_w[i].site_end - rt.single_w[i].site_begin;
+    for (size_t i = 0; i < rt.lw.size(); ++i) {
+        const LayoutWindow &w = rt.lw[i];
+        blocks += ((rt.indexed ? w.hi.c - w.lo.c : windows[i].site_end - windows[i].site_begin) + 63) / 64;
+        entries += (w.hi.r - w.lo.r) + (w.hi.g - w.lo.g);
+    }
     if (m->compact && blocks > m->g.n_block) blocks = m->g.n_block;
     if (rt.indexed && blocks > m->vg.n_block) blocks = m->vg.n_block;
     if (entries > m->n_vrare) entries = m->n_vrare;
-    blocks += entries * 8 / (64ull * m->g.wps * 4ull);
-    const uint64_t by_parallelism = blocks / (16ull * (uint64_t)(ctx->n_cu > 0 ? ctx->n_cu : 256));
-    return (uint32_t)std::max<uint64_t>(std::min<uint32_t>(32, by_bytes), std::min<uint64_t>(by_bytes, by_parallelism));
+    return default_tile_rule(m->g.wps, blocks + entries * 8 / (64ull * m->g.wps * 4ull), ctx->n_cu);
 }
 
 // subset masks of a plan; the overlap of A and B is removed from both (h-fst.py:181-185)
@@ -908,6 +807,14 @@ int impop::check_windows(const char *fn, const impop_matrix *m, const impop_wind
     return IMPOP_OK;
 }
 
+std::vector<LayoutWindow> impop::row_windows(const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
+    std::vector<impop_window> mapped;
+    map_windows(m, windows, n_windows, mapped);
+    std::vector<LayoutWindow> lw(n_windows);
+    for (uint64_t i = 0; i < n_windows; ++i) lw[i] = {{mapped[i].site_begin, 0, 0}, {mapped[i].site_end, 0, 0}, mapped[i].seq_len};
+    return lw;
+}
+
 int impop::check_window_weights(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows) {
     for (uint64_t i = 0; i < n_windows; ++i)
         REQUIRE(window_W(m, windows[i].site_begin, windows[i].site_end) <= 0xFFFFFFFFull,
@@ -927,14 +834,13 @@ int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, con
     rt.rare = rt.packed ? m->d_vmulti : rt.split ? m->d_vrare : nullptr;
     rt.single = rt.packed ? m->d_vsingle : nullptr;
     if (rt.indexed) {
-        const int rc = map_windows_index(ctx, m, windows, n_windows, rt.mapped, rt.split ? &rt.rare_w : nullptr,
-                                         rt.packed ? &rt.single_w : nullptr);
+        const int rc = map_windows_index(ctx, m, windows, n_windows, rt.split ? rt.packed ? SINGLE : COMMON : KEPT, rt.lw);
         if (rc) return rc;
     } else {
-        map_windows(m, windows, n_windows, rt.mapped);
+        rt.lw = row_windows(m, windows, n_windows);
     }
-    rt.tile_blocks = tile_blocks ? tile_blocks : default_tile_blocks(ctx, m, windows, n_windows, rt);
-    build_tiles(rt, n_windows, m->g.wps);
+    rt.tile_blocks = tile_blocks ? tile_blocks : default_tile_blocks(ctx, m, windows, rt);
+    cut_tiles(rt.lw, rt.tile_blocks, m->g.wps, rt.packed, rt);
     const int rc = window_weights(m, windows, n_windows, rt);
     if (rc) return rc;
     REQUIRE(rt.tiles.size() < 0x7FFFFFFFull, "%s: %llu tiles exceed one launch; raise tile_blocks", fn,

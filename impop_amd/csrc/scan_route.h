@@ -1,6 +1,6 @@
 // scan_route.h — the front end the streaming calls share (bodies in scan.hip): which layout a scan of a window list streams
 // and how the windows are cut into tiles.  impop_scan_plan_create, impop_scan_multi, impop_haplotype_scan and impop_dstat_scan
-// take their route from scan_route; impop_diploid_scan builds its tiles on the matrix's own rows with build_tiles; they and
+// take their route from scan_route; impop_diploid_scan cuts its tiles on the matrix's own rows (tile_cut.h); they and
 // impop_ld_scan share the window checks.  The chunked calls among them go on through win_chunks.h (member set, chunk cutter)
 // and chunk_run.h (the stream protocol of a chunk).  Below it, the host half of the K-population calls (impop_scan_multi,
 // impop_dstat_scan; their device half is pop_stream.h): the panel's masks, its upload, its launch.
@@ -10,54 +10,26 @@
 
 #include "chunk_run.h"
 #include "internal.h"
+#include "tile_cut.h"
 
 namespace impop {
 
-// site_begin..site_end: sites of the SB64 layout streamed; rare_begin..rare_end: entries of the split index's rare stream
-// (internal.h, d_vrare).  Either range may be empty.
-struct ScanTile {
-    uint64_t site_begin, site_end;
-    uint64_t rare_begin, rare_end;
-};
-// what a workgroup reads of a tile: its 64-site blocks of 4 wps bytes per site, whole, and its 8-byte rare entries
-inline uint64_t tile_bytes_streamed(const ScanTile &t, uint32_t wps) {
-    return (t.site_end > t.site_begin ? ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps : 0) + (t.rare_end - t.rare_begin) * 8ull;
-}
-// Packed route: a tile's range of the singleton stream (internal.h, d_vsingle), in uint16 units; the tile's rare range is then
-// one of d_vmulti.  A parallel array to the tiles, so that ScanTile and the kernels that read only it stay what they are.
-struct SingleRange {
-    uint64_t begin, end;
-};
-// what a workgroup reads of it: the aligned 8-byte words (four singletons each) the range touches
-inline uint64_t single_bytes_streamed(const SingleRange &r) { return r.end > r.begin ? ((r.end + 3) / 4 - r.begin / 4) * 8ull : 0; }
-struct WinDesc {
-    uint64_t t0, t1;  // tile range
-    uint64_t n_sites;
-    uint64_t seq_len;
-};
-
 // What a scan of `windows` streams, derived once per call (scan_route below).
-struct ScanRoute {
+struct ScanRoute : TileCut {  // ... and how cut_tiles cut it: tiles, singles, wins, bytes_streamed
     bool indexed = false;  // the variable-site index (d_vsb, tiles in kept-site coordinates), else d_sb (dense, or a compacted matrix)
     bool split = false;    // ... and its rare-entry stream (d_vrare)
     const uint32_t *sb = nullptr;
-    const uint64_t *rare = nullptr;           // null unless split
-    std::vector<impop_window> mapped, rare_w;  // the windows as ranges of sb's sites and (split) of rare's entries
-    // packed: the rare sites come from the matrix's two packed streams instead of d_vrare.  rare = d_vmulti and rare_w its
-    // ranges, single = d_vsingle and single_w its ranges; singles[k] is tile k's singleton range.  Only scan_route sets it,
-    // and only for a caller that asked (impop_scan_plan_create for the fixed-WPS kernel).
+    const uint64_t *rare = nullptr;  // null unless split
+    // packed: the rare sites come from the matrix's two packed streams instead of d_vrare: rare = d_vmulti, single = d_vsingle.
+    // Only scan_route sets it, and only for a caller that asked (impop_scan_plan_create for the fixed-WPS kernel).
     bool packed = false;
     const uint16_t *single = nullptr;
-    std::vector<impop_window> single_w;
-    std::vector<SingleRange> singles;
+    std::vector<LayoutWindow> lw;  // the windows as ranges of sb's sites, of rare's entries (split) and of single's (packed)
     uint32_t tile_blocks = 0;
-    std::vector<ScanTile> tiles;
-    std::vector<WinDesc> wins;
-    uint64_t bytes_streamed = 0;
 };
 
-// windows -> elementary segments -> tiles of <= rt.tile_blocks 64-site blocks; every window becomes a contiguous tile range
-void build_tiles(ScanRoute &rt, uint64_t n_windows, uint32_t wps);
+// the windows as ranges of the rows of m->d_sb (a compacted matrix: original coordinates -> kept-site index ranges)
+std::vector<LayoutWindow> row_windows(const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
 // every window lies in the matrix and is at most 2^32 - 1 sites long
 int check_windows(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
 // every window's W (window_W: its length, or the sum of its columns' weights) fits the 32 bits a record gives it

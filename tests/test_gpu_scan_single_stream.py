@@ -10,7 +10,9 @@ Shapes: n = 65 and 70 (WPS 3, the smallest split), 257, 465 (WPS 15) and 512 (WP
 for padding).  The crafted matrix has a stretch where every site is a singleton (64 per block; there a site's index is its
 place in the stream, so window edges put the range at every offset mod 4 at both ends), one with MAC 2-3 and common sites but
 no singleton, a monomorphic one, and a mix whose singletons sit at haplotypes 0, n - 1, in no population or anywhere, in both
-polarities.  tile_blocks 1 and 4 cut the singleton run into many tiles (96 rare sites per tile at n = 65)."""
+polarities.  tile_blocks 1 and 4 cut the singleton run into many tiles (96 rare sites per tile at n = 65).  A second crafted
+matrix, 70 haplotypes by 64 * 2048 + 13 sites, puts all three site classes on both sides of the 1024-block chunk boundaries of
+the index's block prefix."""
 import os
 import re
 import subprocess
@@ -211,6 +213,69 @@ def test_other_calls_read_the_entries(mats):
     assert packed.scan_multi(WINDOWS, pops).tobytes() == plain.scan_multi(WINDOWS, pops).tobytes(), n
     quartets = [(0, 1, 2, 3), (1, 0, 3, 2)]
     assert packed.dstat_scan(WINDOWS, pops, quartets).tobytes() == plain.dstat_scan(WINDOWS, pops, quartets).tobytes(), n
+
+
+# ---- all three site classes across the chunks of the index's block prefix (1024 blocks each) ----
+LONG_N, LONG_S = 70, 64 * 2048 + 13           # 2049 blocks + the entry past the last: three chunks, about 1.1 MB
+LONG_B1, LONG_B2 = 64 * 1024, 64 * 2048       # the first sites of the second and of the third chunk
+LONG_WINDOWS = [
+    (LONG_B1 - 5, LONG_B1 + 7, 12), (LONG_B2 - 3, LONG_B2 + 2, 5),              # a few sites either side of a chunk boundary
+    (LONG_B1 - 300, LONG_B1, 300), (LONG_B1, LONG_B1 + 300, 300),               # ending and starting exactly on one
+    (LONG_S - 500, LONG_S, 500), (LONG_B2, LONG_S, 13), (0, LONG_S, LONG_S),    # ending at n_site; the whole matrix
+    (0, LONG_B1, 0), (LONG_B1 - 64, LONG_B2 + 13, 1), (LONG_B2 - 1, LONG_B2, 1),
+]
+
+
+def _crafted_long():
+    """monomorphic but for 4000 singleton, 2000 MAC 2-3 and 2000 common sites anywhere, and 40 sites either side of both chunk
+    boundaries that take the three classes in turn"""
+    n, rng = LONG_N, np.random.default_rng(1717)
+    m = np.repeat((rng.random(LONG_S) < 0.5)[None, :].astype(np.uint8), n, axis=0)
+    near = np.concatenate([np.arange(b - 40, min(b + 40, LONG_S)) for b in (LONG_B1, LONG_B2)])
+    far = rng.choice(np.setdiff1d(np.arange(LONG_S), near), 8000, replace=False)
+    kind = np.concatenate([np.arange(len(near)) % 3, np.repeat([0, 1, 2], [4000, 2000, 2000])])
+    for s, k in zip(np.concatenate([near, far]), kind):
+        col = np.zeros(n, np.uint8)
+        col[rng.choice(n, 1 if k == 0 else rng.integers(2, 4) if k == 1 else rng.integers(4, n - 3), replace=False)] = 1
+        m[:, s] = col ^ (rng.integers(0, 2) if k < 2 else 0)
+    return m
+
+
+@pytest.fixture(scope="module")
+def long_mats(ctx):
+    bits = _crafted_long()
+    ms = [ctx.upload_dense(bits, keep_hap_major=False, **kw) for kw in ({}, dict(single_stream=False), dict(dense_scan=True))]
+    yield bits, ms
+    for m in ms:
+        m.free()
+
+
+def test_classes_across_prefix_chunks(long_mats):
+    """the per-block ranks of the kept, the common and the singleton sites all run over three chunks of the block prefix: the
+    counts are numpy's, and windows on, at and across the chunk boundaries give the records of the dense stream"""
+    bits, (packed, plain, dense) = long_mats
+    n = LONG_N
+    c = bits.sum(axis=0, dtype=np.int64)
+    mac = np.minimum(c, n - c)
+    n_kept, n_single, n_multi = int((mac > 0).sum()), int((mac == 1).sum()), int(((mac == 2) | (mac == 3)).sum())
+    for b in (LONG_B1, LONG_B2):  # every class on both sides of both boundaries
+        for side in (mac[b - 40:b], mac[b:b + 13]):
+            assert (side == 1).any() and ((side == 2) | (side == 3)).any() and (side > 3).any()
+    for m in (packed, plain):
+        idx, split = m.scan_index_info(), m.scan_split_info()
+        assert (idx["n_kept"], idx["why"]) == (n_kept, ""), idx
+        assert (split["n_rare"], split["n_common"], split["why"]) == (n_single + n_multi, n_kept - n_single - n_multi, ""), split
+    single = packed.scan_single_info()
+    assert (single["n_single"], single["n_multi"], single["why"]) == (n_single, n_multi, ""), single
+    assert plain.scan_single_info()["n_single"] == 0 and dense.scan_index_info()["n_kept"] == 0
+    P, A, B = _masks(n, "P")
+    for tb in (0, 4):
+        want = dense.scan(LONG_WINDOWS, P, A, B, tile_blocks=tb)
+        for m in (packed, plain):
+            got = m.scan(LONG_WINDOWS, P, A, B, tile_blocks=tb)
+            for k in INT_KEYS + DBL_KEYS:
+                assert got[k].tobytes() == want[k].tobytes(), (tb, k, got[k], want[k])
+    assert int(want["s_all"][6]) == n_kept  # the whole matrix
 
 
 def _hip_runtime():
