@@ -25,6 +25,7 @@ ABI_VERSION = 4  # IMPOP_ABI_VERSION of include/impop_hip.h
 E_INVALID, E_NODEVICE, E_HIP, E_NOMEM, E_UNSUPPORTED, E_INTERNAL = -1, -2, -3, -4, -5, -6
 KEEP_SITE_BLOCKED, KEEP_HAP_MAJOR, KEEP_DENSE_SCAN, KEEP_NO_RARE_SPLIT = 1, 2, 4, 8
 KEEP_NO_SINGLE_STREAM = 16
+KEEP_NO_UNIQUE_ROWS = 32
 IDENTITY_MATCH, IDENTITY_DICE = 0, 1
 EHH_FLANKS_REFERENCE, EHH_FLANKS_TWO_SIDED = 0, 1
 EHH_SCAN_MAX_N = 4096  # IMPOP_EHH_SCAN_MAX_N
@@ -217,6 +218,7 @@ SIGNATURES = {
     "impop_matrix_scan_index_info": (C.c_int, [_vp, _u64p, _u64p, C.c_char_p, C.c_size_t]),
     "impop_matrix_scan_split_info": (C.c_int, [_vp, _u64p, _u64p, _u64p, C.c_char_p, C.c_size_t]),
     "impop_matrix_scan_single_info": (C.c_int, [_vp, _u64p, _u64p, _u64p, C.c_char_p, C.c_size_t]),
+    "impop_matrix_scan_unique_info": (C.c_int, [_vp, _u64p, _u64p, _u64p, C.c_char_p, C.c_size_t]),
     "impop_matrix_free": (C.c_int, [_vp, _vp]),
     "impop_scan_plan_create": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, _u64p, _u64p,
                                          C.POINTER(ScanParams), C.POINTER(_vp)]),

@@ -256,6 +256,21 @@ struct impop_matrix {
     uint64_t *d_vmulti = nullptr;
     uint64_t n_vsingle = 0, vsingle_bytes = 0;  // singleton sites; everything the stream allocated
     std::string sskip = "not built";
+    // distinct-row stream of the split index (layout.hip unique_rows_build; wps <= 16, the range of its one reader, the fixed-WPS
+    // scan kernel; independent of the singleton stream).  Per 64-row block of d_vsb, rows that are equal or each other's
+    // complement within the n_hap real haplotypes form a class (every scan sum and segregating test is the same for a row and its
+    // complement); the class's first row is its REPRESENTATIVE and its weight the number of rows of the class, 1..64.  d_vuniq is
+    // an SB64 layout (the matrix's wps / G / r, zero rows to the end of the last block, one block of slack) of the representatives'
+    // rows as d_vsb stores them, in order, so a block's representatives are contiguous; d_vuniq_wt holds one weight byte per
+    // representative (zeros to the end of the last block plus 64 bytes of slack: a wave's 64-byte load of any block stays inside).
+    // uidx ranks the representatives in COMMON-ROW coordinates: per block of d_vsb the mask of its representatives and the number
+    // of them before the block, vg.n_block + 1 entries each.  Kept only when it pays: representatives <= 3/4 of the common rows.
+    // d_vuniq null: no stream (uskip says why).  d_vsb stays complete.
+    uint32_t *d_vuniq = nullptr;
+    uint8_t *d_vuniq_wt = nullptr;
+    impop::BlockRank uidx;
+    uint64_t n_vuniq = 0, vuniq_bytes = 0;  // representatives; everything the stream allocated
+    std::string uskip = "not built";
     int device = 0;
     mutable int users = 0;      // live scan plans referencing this matrix (impop_matrix_free refuses while > 0)
 };

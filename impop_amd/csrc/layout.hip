@@ -266,6 +266,7 @@ struct IndexBuild {
     void *d_tmp = nullptr;      // transient: counts, chunk sums, totals (IndexTmp)
     uint64_t *d_pos = nullptr;  // transient: source site of every kept site
     uint64_t n_chunks = 0;
+    uint32_t keep_flags = 0;    // the caller's, for what index_finish builds on top (unique_rows_build)
     IndexBuild() = default;
     IndexBuild(const IndexBuild &) = delete;
     ~IndexBuild() {
@@ -748,6 +749,18 @@ int map_windows_index(impop_ctx *ctx, const impop_matrix *m, const impop_window 
     return IMPOP_OK;
 }
 
+// the distinct-row stream goes (or never came): what it allocated is freed, uskip says why
+static void uniq_drop(impop_matrix *m, std::string why) {
+    if (m->uidx.mask) hipFree((void *)m->uidx.mask);
+    if (m->d_vuniq) hipFree(m->d_vuniq);
+    if (m->d_vuniq_wt) hipFree(m->d_vuniq_wt);
+    m->uidx = BlockRank();
+    m->d_vuniq = nullptr;
+    m->d_vuniq_wt = nullptr;
+    m->n_vuniq = m->vuniq_bytes = 0;
+    m->uskip = std::move(why);
+}
+
 // Drops the index from class k upward: the class's rank table and what was built on it; the classes above it lose theirs for
 // want of the one below.
 static void index_drop(impop_matrix *m, SiteClass k, std::string why) {
@@ -759,6 +772,7 @@ static void index_drop(impop_matrix *m, SiteClass k, std::string why) {
         *skip[c] = no_lower[c];
     }
     *skip[k] = std::move(why);
+    if (k <= COMMON) uniq_drop(m, k == KEPT ? "no scan index" : "no rare/common split");  // built on the common rows
     switch (k) {
     case KEPT:
         if (m->d_vsb) hipFree(m->d_vsb);
@@ -805,6 +819,7 @@ struct IndexTmp {
 
 static int index_begin(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags, IndexBuild &ib) {
     const SbGeom &g = m->g;
+    ib.keep_flags = keep_flags;
     // why a class is not wanted (null: it is), and what to call its allocation.  The rare/common split: an entry (8 B) must be
     // narrower than a row, and its haplotype indices fit 16 bits; the singleton stream: read by the fixed-WPS scan kernel alone
     const struct {
@@ -848,6 +863,139 @@ static void block_prefix(impop_ctx *ctx, uint32_t n_class, const PrefixArgs &a, 
     hipLaunchKernelGGL(chunk_sum_kernel, dim3((uint32_t)n_chunks, n_class), dim3(256), 0, ctx->stream, a, ne, d_chunk);
     hipLaunchKernelGGL(chunk_scan_kernel, dim3(n_class), dim3(64), 0, ctx->stream, d_chunk, n_chunks, d_total);
     hipLaunchKernelGGL(block_base_kernel, dim3((uint32_t)n_chunks, n_class), dim3(64), 0, ctx->stream, a, ne, (const uint64_t *)d_chunk);
+}
+
+// ---- distinct-row stream (internal.h, d_vuniq) ----------------------------------------------------
+// One wave per 64-row block of an SB64 layout of <= 16 dwords per row, lane l holding row l.  The row is canonicalised — complemented
+// within the n_hap real haplotype bits when haplotype 0 carries 1; padding bits stay 0 — and compared with every row of the block
+// (64 broadcasts of a row): same = the live lanes of the block whose canonical row is this lane's.  Lanes that are not live (past
+// the last row of the final block) are in no class.  w: the row as stored.
+constexpr int UNIQ_WPS_MAX = 16;
+__device__ inline uint64_t uniq_block_classes(const uint32_t *__restrict__ blk, uint32_t wps, uint32_t G, uint32_t r, uint32_t n_hap,
+                                              bool live, uint32_t lane, uint32_t (&w)[UNIQ_WPS_MAX]) {
+    uint32_t cw[UNIQ_WPS_MAX];
+#pragma unroll
+    for (int k = 0; k < UNIQ_WPS_MAX; ++k) w[k] = (uint32_t)k < wps ? blk[sb_index(wps, G, r, 0, lane, (uint32_t)k)] : 0u;
+    const bool flip = (w[0] & 1u) != 0;
+#pragma unroll
+    for (int k = 0; k < UNIQ_WPS_MAX; ++k) {
+        const uint32_t real = 32u * k + 32u <= n_hap ? 0xFFFFFFFFu : 32u * k < n_hap ? (1u << (n_hap - 32u * k)) - 1u : 0u;
+        cw[k] = flip ? w[k] ^ real : w[k];
+    }
+    uint64_t same = 0;
+    for (int j = 0; j < 64; ++j) {
+        uint32_t diff = __shfl((int)live, j, 64) ? 0u : 1u;  // every lane takes every broadcast: no lane-dependent branch around one
+#pragma unroll
+        for (int k = 0; k < UNIQ_WPS_MAX; ++k) diff |= (uint32_t)__shfl((int)cw[k], j, 64) ^ cw[k];
+        same |= (uint64_t)(diff == 0u) << j;
+    }
+    return live ? same : 0ull;
+}
+// a lane is its class's representative when no lower lane is in the class
+__device__ inline bool uniq_is_rep(uint64_t same, uint32_t lane) { return same != 0 && (same & ((1ull << lane) - 1ull)) == 0; }
+
+__global__ __launch_bounds__(256) void uniq_mask_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
+                                                        uint32_t n_hap, uint64_t n_row, uint64_t n_block, uint64_t *__restrict__ mask,
+                                                        uint32_t *__restrict__ cnt) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n_block) return;  // wave-uniform
+    uint32_t w[UNIQ_WPS_MAX];
+    const uint64_t same = uniq_block_classes(sb + b * 64ull * wps, wps, G, r, n_hap, b * 64 + lane < n_row, lane, w);
+    const uint64_t reps = __ballot(uniq_is_rep(same, lane));
+    if (lane == 0) { mask[b] = reps; cnt[b] = (uint32_t)__popcll(reps); }
+}
+// the representatives' rows, as stored, to their places in the stream (base: the representatives before each block), and their weights
+__global__ __launch_bounds__(256) void uniq_gather_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
+                                                          uint32_t n_hap, uint64_t n_row, uint64_t n_block,
+                                                          const uint64_t *__restrict__ base, uint64_t n_uniq, uint32_t *__restrict__ out,
+                                                          uint8_t *__restrict__ out_wt) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t b = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= n_block) return;  // wave-uniform
+    uint32_t w[UNIQ_WPS_MAX];
+    const uint64_t same = uniq_block_classes(sb + b * 64ull * wps, wps, G, r, n_hap, b * 64 + lane < n_row, lane, w);
+    const bool rep = uniq_is_rep(same, lane);
+    const uint64_t reps = __ballot(rep);
+    if (!rep) return;
+    const uint64_t dest = base[b] + (uint64_t)__popcll(reps & ((1ull << lane) - 1ull));
+    if (dest >= n_uniq) return;  // cannot happen: base is the prefix of these very counts
+#pragma unroll
+    for (int k = 0; k < UNIQ_WPS_MAX; ++k)
+        if ((uint32_t)k < wps) out[sb_index(wps, G, r, dest >> 6, (uint32_t)(dest & 63), (uint32_t)k)] = w[k];
+    out_wt[dest] = (uint8_t)__popcll(same);  // 1..64
+}
+
+// the stream is kept when its representatives are at most IMPOP_UNIQ_MAX_NUM / IMPOP_UNIQ_MAX_DEN of the common rows
+constexpr uint64_t IMPOP_UNIQ_MAX_NUM = 3, IMPOP_UNIQ_MAX_DEN = 4;
+
+// Builds the distinct-row stream on top of a finished split index (d_vsb holds the common rows), or records why there is none.
+// Like the rest of the index it never fails the matrix: an allocation that cannot be had leaves the matrix without the stream.
+static int unique_rows_build(impop_ctx *ctx, impop_matrix *m, uint32_t keep_flags) {
+    static const bool env_off = env_is("IMPOP_NO_UNIQUE_ROWS", '1');
+    const SbGeom &g = m->g;
+    const uint64_t n_row = m->vg.n_site, nvb = m->vg.n_block, ne = nvb + 1, n_chunks = (ne + SCAN_CHUNK - 1) / SCAN_CHUNK;
+    const char *skip = keep_flags & IMPOP_KEEP_NO_UNIQUE_ROWS ? "opted out (IMPOP_KEEP_NO_UNIQUE_ROWS)"
+                       : env_off                               ? "opted out (IMPOP_NO_UNIQUE_ROWS=1)"
+                       : !m->d_vrare                           ? "no rare/common split"
+                       : g.wps > UNIQ_WPS_MAX                  ? "n_hap > 512: scans run the any-n kernel, which reads the rows"
+                       : n_row == 0                            ? "no common rows"
+                                                               : nullptr;
+    if (skip) {
+        uniq_drop(m, skip);
+        return IMPOP_OK;
+    }
+    REQUIRE((nvb + 3) / 4 < 0x7FFFFFFFull && n_chunks < 0x7FFFFFFFull, "distinct-row stream: too many common rows for one launch");
+    Carve L;
+    const size_t o_cnt = L.take<uint32_t>(ne), o_chunk = L.take<uint64_t>(n_chunks), o_total = L.take<uint64_t>(1);
+    struct Owned {  // freed on every way out unless handed on
+        void *p = nullptr;
+        ~Owned() { if (p) hipFree(p); }
+    } tmp, rank, rows, wts;
+    auto none = [&](std::string why) {
+        (void)hipGetLastError();
+        uniq_drop(m, std::move(why));
+        return IMPOP_OK;
+    };
+    if (hipMalloc(&tmp.p, L.total()) != hipSuccess) { tmp.p = nullptr; return none("hipMalloc of the distinct-row counts failed"); }
+    if (hipMalloc(&rank.p, 2 * ne * 8) != hipSuccess) { rank.p = nullptr; return none("hipMalloc of the distinct-row mask failed"); }
+    uint64_t *mask = reinterpret_cast<uint64_t *>(rank.p), *base = mask + ne, *d_total = L.at<uint64_t>(tmp.p, o_total);
+    uint32_t *cnt = L.at<uint32_t>(tmp.p, o_cnt);
+    HIP_TRY(hipMemsetAsync(mask + nvb, 0, 8, ctx->stream));  // the entry past the last block holds nothing
+    HIP_TRY(hipMemsetAsync(cnt + nvb, 0, 4, ctx->stream));
+    hipLaunchKernelGGL(uniq_mask_kernel, dim3((uint32_t)((nvb + 3) / 4)), dim3(256), 0, ctx->stream, (const uint32_t *)m->d_vsb, g.wps, g.G,
+                       g.r, g.n_hap, n_row, nvb, mask, cnt);
+    block_prefix(ctx, 1, PrefixArgs{{cnt}, {base}}, ne, n_chunks, L.at<uint64_t>(tmp.p, o_chunk), d_total);
+    HIP_TRY(hipGetLastError());
+    uint64_t n_uniq = 0;
+    HIP_TRY(hipMemcpyAsync(&n_uniq, d_total, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (n_uniq * IMPOP_UNIQ_MAX_DEN > n_row * IMPOP_UNIQ_MAX_NUM) {
+        char why[160];
+        snprintf(why, sizeof why, "%llu distinct of %llu common rows: above %llu/%llu", (unsigned long long)n_uniq, (unsigned long long)n_row,
+                 (unsigned long long)IMPOP_UNIQ_MAX_NUM, (unsigned long long)IMPOP_UNIQ_MAX_DEN);
+        return none(why);
+    }
+    // rows: whole blocks and, as for d_vsb, one block of slack; weights: whole blocks and 64 bytes of slack.  All zero first: the
+    // rows past the last representative add nothing to any sum whatever their weight
+    const uint64_t nub = (n_uniq + 63) / 64, row_bytes = (nub + 1) * 64ull * g.wps * 4ull + 256, wt_bytes = nub * 64 + 64;
+    if (hipMalloc(&rows.p, row_bytes) != hipSuccess) { rows.p = nullptr; return none("hipMalloc of the distinct rows failed"); }
+    if (hipMalloc(&wts.p, wt_bytes) != hipSuccess) { wts.p = nullptr; return none("hipMalloc of the distinct rows' weights failed"); }
+    m->uidx = {mask, base};
+    m->d_vuniq = reinterpret_cast<uint32_t *>(rows.p);
+    m->d_vuniq_wt = reinterpret_cast<uint8_t *>(wts.p);
+    rank.p = rows.p = wts.p = nullptr;  // the matrix's from here (uniq_drop frees them)
+    m->n_vuniq = n_uniq;
+    m->vuniq_bytes = 2 * ne * 8 + row_bytes + wt_bytes;
+    m->uskip.clear();
+    HIP_TRY(hipMemsetAsync(m->d_vuniq, 0, row_bytes, ctx->stream));
+    HIP_TRY(hipMemsetAsync(m->d_vuniq_wt, 0, wt_bytes, ctx->stream));
+    hipLaunchKernelGGL(uniq_gather_kernel, dim3((uint32_t)((nvb + 3) / 4)), dim3(256), 0, ctx->stream, (const uint32_t *)m->d_vsb, g.wps,
+                       g.G, g.r, g.n_hap, n_row, nvb, (const uint64_t *)base, n_uniq, m->d_vuniq, m->d_vuniq_wt);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the counts go
+    m->vidx_bytes += m->vuniq_bytes;
+    return IMPOP_OK;
 }
 
 static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
@@ -926,7 +1074,7 @@ static int index_finish(impop_ctx *ctx, impop_matrix *m, IndexBuild &ib) {
     }
     m->vidx_bytes = 2 * ne * 8 + m->vsb_bytes + slack + (split ? 2 * ne * 8 + std::max<uint64_t>(m->n_vrare, 1) * 8 : 0) + m->vsingle_bytes;
     m->vskip.clear();
-    return IMPOP_OK;
+    return unique_rows_build(ctx, m, ib.keep_flags);
 }
 
 }  // namespace impop
@@ -1126,6 +1274,18 @@ IMPOP_API int impop_matrix_scan_single_info(const impop_matrix *m, uint64_t *n_s
     if (n_multi) *n_multi = has ? m->n_vrare - m->n_vsingle : 0;
     if (stream_bytes) *stream_bytes = has ? m->vsingle_bytes : 0;
     if (why && why_len) snprintf(why, why_len, "%s", has ? "" : built ? "site weights: scans stream the dense layout" : m->sskip.c_str());
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_matrix_scan_unique_info(const impop_matrix *m, uint64_t *n_unique, uint64_t *n_common, uint64_t *stream_bytes,
+                                            char *why, size_t why_len) {
+    REQUIRE(m, "impop_matrix_scan_unique_info: matrix is NULL");
+    const bool built = m->d_vsb && m->d_vrare && m->d_vuniq;
+    const bool has = built && m->wt_prefix.empty();  // no scan of a weighted matrix reads the index
+    if (n_unique) *n_unique = has ? m->n_vuniq : 0;
+    if (n_common) *n_common = has ? m->vg.n_site : 0;
+    if (stream_bytes) *stream_bytes = has ? m->vuniq_bytes : 0;
+    if (why && why_len) snprintf(why, why_len, "%s", has ? "" : built ? "site weights: scans stream the dense layout" : m->uskip.c_str());
     return IMPOP_OK;
 }
 

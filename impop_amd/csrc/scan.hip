@@ -83,9 +83,29 @@ __device__ __forceinline__ void counts_accumulate(uint32_t c, uint32_t cP, uint3
     acc.q_ab += wt * ((sum_t)Acc::mul(cA, rB) + (sum_t)Acc::mul(cB, rA));
 }
 
-template <int WPS, bool SUBSET_P>
+// A representative of the distinct-row stream (internal.h, d_vuniq): its counts stand for wt rows, equal or complemented, and
+// every term is linear in wt — s_x += wt [segregating], q_x += wt product — and the same for a row and its complement (c <-> n - c
+// in every population at once: 0 < c < n, c (n - c) and cA (nB - cB) + cB (nA - cA) stay).  wt <= 64 and every product is
+// at most 2^16 (the cross term: nA nB with nA + nB <= 512), so each wt x product is a 24-bit multiply; the lane sums: tile_cut.h, UNIQ_MID_MAX.
+template <bool SUBSET_P>
+__device__ __forceinline__ void counts_accumulate_folded(uint32_t c, uint32_t cP, uint32_t cA, uint32_t cB, const PopSizes &ps,
+                                                         LaneAcc32 &acc, uint32_t wt) {
+    if (!SUBSET_P) cP = c;
+    acc.s_all += (c - 1u) < (ps.n - 1u) ? wt : 0u;
+    acc.s_p += (cP - 1u) < (ps.nP - 1u) ? wt : 0u;
+    acc.s_a += (cA - 1u) < (ps.nA - 1u) ? wt : 0u;
+    acc.s_b += (cB - 1u) < (ps.nB - 1u) ? wt : 0u;
+    const uint32_t rA = ps.nA - cA, rB = ps.nB - cB;
+    acc.q_p += __umul24(wt, __umul24(cP, ps.nP - cP));
+    acc.q_a += __umul24(wt, __umul24(cA, rA));
+    acc.q_b += __umul24(wt, __umul24(cB, rB));
+    acc.q_ab += __umul24(wt, __umul24(cA, rB) + __umul24(cB, rA));
+}
+
+// FOLDED: the row is a representative of weight wt (counts_accumulate_folded), else a row of its own
+template <int WPS, bool SUBSET_P, bool FOLDED = false>
 __device__ __forceinline__ void site_accumulate(const uint32_t (&w)[WPS], const MaskArgs<WPS> &mk, const PopSizes &ps,
-                                                LaneAcc32 &acc) {
+                                                LaneAcc32 &acc, uint32_t wt = 1) {
     uint32_t c = 0, cP = 0, cA = 0, cB = 0;
 #pragma unroll
     for (int k = 0; k < WPS; ++k) {
@@ -94,7 +114,8 @@ __device__ __forceinline__ void site_accumulate(const uint32_t (&w)[WPS], const 
         cA += __popc(w[k] & mk.a[k]);
         cB += __popc(w[k] & mk.b[k]);
     }
-    counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
+    if constexpr (FOLDED) counts_accumulate_folded<SUBSET_P>(c, cP, cA, cB, ps, acc, wt);
+    else counts_accumulate<SUBSET_P>(c, cP, cA, cB, ps, acc);
 }
 
 // rare_listed_in (hap_words.h): how many of the haplotypes a rare entry lists belong to a population
@@ -268,18 +289,77 @@ __device__ __forceinline__ void tile_reduce_store(LaneAcc &acc, TilePartial *out
     }
 }
 
-template <int WPS, bool SUBSET_P>
+// Rows [s0, s1) of an SB64 base, one of the up to three row ranges of a tile: blocks [s0 / 64, ceil(s1 / 64)), U of them per
+// iteration (U*ceil(WPS/4) independent 1 KiB wave loads in flight per wave).  Only the first and the last block of a range can be
+// partial: lanes before s0 in the first and from s1 on in the last get all-zero words (wave-uniform branch, taken for those two
+// blocks only); interior blocks carry no validity arithmetic and no branch, so all U loads of an iteration are in flight together.
+// FOLDED: the base is the distinct-row stream and wts its weight bytes, one per row, loaded with the row.
+// turn: the tile's ranges hand their blocks to the four waves from ONE running block index (a bench tile is a head block, one or
+// two blocks of representatives and a tail block: three loops that each start at wave 0 would give all of them to one wave and
+// serialise the loads).  In: how many blocks of this range go by before this wave's first; out: the same for the next range.
+template <int WPS, bool SUBSET_P, bool FOLDED, int U>
+__device__ __forceinline__ void row_range(const uint32_t *__restrict__ sb, const uint8_t *__restrict__ wts, uint64_t s0, uint64_t s1,
+                                          uint32_t &turn, uint32_t lane, const MaskArgs<WPS> &mk, const PopSizes &ps, LaneAcc32 &acc) {
+    if (s1 <= s0) return;  // workgroup-uniform
+    const uint64_t b0 = s0 >> 6, b1 = (s1 + 63) >> 6;
+    const uint32_t lo = (uint32_t)(s0 - (b0 << 6));
+    const uint32_t hi = (uint32_t)(s1 - ((b1 - 1) << 6));  // 1..64
+    auto trim = [&](uint32_t (&w)[WPS], uint64_t blk) {
+        if ((blk == b0 && lo != 0) | (blk == b1 - 1 && hi != 64)) {
+            const bool keep = lane >= (blk == b0 ? lo : 0u) && lane < (blk == b1 - 1 ? hi : 64u);
+#pragma unroll
+            for (int k = 0; k < WPS; ++k) w[k] = keep ? w[k] : 0u;
+        }
+    };
+    uint64_t b = b0 + turn;
+    turn = (turn + 4u - (uint32_t)((b1 - b0) & 3u)) & 3u;
+    for (; b + 4 * (U - 1) < b1; b += 4 * U) {
+        uint32_t w[U][WPS], wt[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            load_site<WPS>(sb + (b + 4 * u) * (64ull * WPS), lane, w[u]);
+            wt[u] = FOLDED ? (uint32_t)stream_load(wts + (b + 4 * u) * 64 + lane) : 1u;
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            trim(w[u], b + 4 * u);
+            site_accumulate<WPS, SUBSET_P, FOLDED>(w[u], mk, ps, acc, wt[u]);
+        }
+    }
+    if constexpr (U > 1) {
+        for (; b < b1; b += 4) {
+            uint32_t w0[WPS];
+            load_site<WPS>(sb + b * (64ull * WPS), lane, w0);
+            const uint32_t wt0 = FOLDED ? (uint32_t)stream_load(wts + b * 64 + lane) : 1u;
+            trim(w0, b);
+            site_accumulate<WPS, SUBSET_P, FOLDED>(w0, mk, ps, acc, wt0);
+        }
+    }
+}
+
+// uniqs (unique-row route, else null): the tile's range of the distinct-row stream, indexed like the tile.  Not empty: the tile's
+// whole blocks of rows are read as their representatives (uniq, uniq_wt) and only its head and its tail, the partial blocks at
+// window edges (tile_cut.h, mid_blocks), as rows of sb.  Empty: every row of the tile from sb.
+// UNIQ: the plan's route has the stream.  A plan without it launches the instantiation without: one row range and none of the
+// stream's arguments in registers — the kernel it was before the stream (the weighted range and the third range cost
+// <15,false> six SGPRs and with them a wave of occupancy, 8 -> 7, which a route that reads no representative need not pay).
+template <int WPS, bool SUBSET_P, bool UNIQ>
 __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(const uint32_t *__restrict__ sb,
                                                                                const uint64_t *__restrict__ rare,
                                                                                const ScanTile *__restrict__ tiles,
                                                                                const MaskArgs<WPS> mk, const PopSizes ps,
                                                                                TilePartial *__restrict__ out,
                                                                                const uint16_t *__restrict__ single,
-                                                                               const SingleRange *__restrict__ singles) {
+                                                                               const SingleRange *__restrict__ singles,
+                                                                               const uint32_t *__restrict__ uniq,
+                                                                               const uint8_t *__restrict__ uniq_wt,
+                                                                               const UniqRange *__restrict__ uniqs) {
     const ScanTile t = tiles[blockIdx.x];
     // packed route: the tile's range of the singleton stream (null otherwise), indexed like the tile — no dependent load
     SingleRange sr = {0, 0};
     if (singles) sr = singles[blockIdx.x];
+    UniqRange ur = {0, 0};
+    if constexpr (UNIQ) ur = uniqs[blockIdx.x];
     const TileBlocks tb = tile_blocks_of(t);
     // split index: this thread's share of the haplotype code table (RareMoments) — the mask words of haplotypes threadIdx.x and
     // threadIdx.x + 256, read from the kernel arguments (MaskArgs is p | a | b) BEFORE the rows so that they arrive behind them
@@ -296,37 +376,46 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         }
     }
     LaneAcc32 acc;
-    uint64_t b = tb.b0 + tb.wave;
     constexpr int G = (WPS + 3) / 4;
     constexpr int U = IMPOP_SCAN_UNROLL > 0 ? IMPOP_SCAN_UNROLL : (G >= 3 ? 2 : G == 2 ? 4 : 8);
-    // Only the first and the last block of a tile can be partial: lanes before `lo` in block b0 and from `hi`
-    // on in block b1-1 get all-zero words (wave-uniform branch, taken for those two blocks only); interior
-    // blocks carry no validity arithmetic and no branch, so all U loads of an iteration are in flight together.
-    const uint32_t lo = (uint32_t)(t.site_begin - (tb.b0 << 6));
-    const uint32_t hi = (uint32_t)(t.site_end - ((tb.b1 - 1) << 6));  // 1..64
-    auto trim = [&](uint32_t (&w)[WPS], uint64_t blk) {
-        if ((blk == tb.b0 && lo != 0) | (blk == tb.b1 - 1 && hi != 64)) {
-            const bool keep = tb.lane >= (blk == tb.b0 ? lo : 0u) && tb.lane < (blk == tb.b1 - 1 ? hi : 64u);
+    // head | whole blocks as representatives | tail; without a range the head is the whole tile
+    if constexpr (UNIQ) {
+        uint32_t turn = tb.wave;
+        const bool folded = ur.end > ur.begin;  // workgroup-uniform
+        const MidBlocks mid = mid_blocks(t.site_begin, t.site_end);
+        const uint64_t head_end = folded ? mid.g0 << 6 : t.site_end, tail_begin = folded ? mid.g1 << 6 : t.site_end;
+        row_range<WPS, SUBSET_P, false, U>(sb, nullptr, t.site_begin, head_end, turn, tb.lane, mk, ps, acc);
+        row_range<WPS, SUBSET_P, true, U>(uniq, uniq_wt, ur.begin, ur.end, turn, tb.lane, mk, ps, acc);
+        row_range<WPS, SUBSET_P, false, 1>(sb, nullptr, tail_begin, t.site_end, turn, tb.lane, mk, ps, acc);  // one block at most
+    } else {
+        // the tile's blocks tb.b0 .. tb.b1, wave w taking b0 + w, b0 + w + 4, ...: row_range over the whole tile, written out so
+        // that this instantiation stays the kernel it was, register for register
+        uint64_t b = tb.b0 + tb.wave;
+        const uint32_t lo = (uint32_t)(t.site_begin - (tb.b0 << 6));
+        const uint32_t hi = (uint32_t)(t.site_end - ((tb.b1 - 1) << 6));  // 1..64
+        auto trim = [&](uint32_t (&w)[WPS], uint64_t blk) {
+            if ((blk == tb.b0 && lo != 0) | (blk == tb.b1 - 1 && hi != 64)) {
+                const bool keep = tb.lane >= (blk == tb.b0 ? lo : 0u) && tb.lane < (blk == tb.b1 - 1 ? hi : 64u);
 #pragma unroll
-            for (int k = 0; k < WPS; ++k) w[k] = keep ? w[k] : 0u;
+                for (int k = 0; k < WPS; ++k) w[k] = keep ? w[k] : 0u;
+            }
+        };
+        for (; b + 4 * (U - 1) < tb.b1; b += 4 * U) {
+            uint32_t w[U][WPS];
+#pragma unroll
+            for (int u = 0; u < U; ++u) load_site<WPS>(sb + (b + 4 * u) * (64ull * WPS), tb.lane, w[u]);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                trim(w[u], b + 4 * u);
+                site_accumulate<WPS, SUBSET_P>(w[u], mk, ps, acc);
+            }
         }
-    };
-    // U blocks per iteration: U*ceil(WPS/4) independent 1 KiB wave loads in flight per wave
-    for (; b + 4 * (U - 1) < tb.b1; b += 4 * U) {
-        uint32_t w[U][WPS];
-#pragma unroll
-        for (int u = 0; u < U; ++u) load_site<WPS>(sb + (b + 4 * u) * (64ull * WPS), tb.lane, w[u]);
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            trim(w[u], b + 4 * u);
-            site_accumulate<WPS, SUBSET_P>(w[u], mk, ps, acc);
+        for (; b < tb.b1; b += 4) {
+            uint32_t w0[WPS];
+            load_site<WPS>(sb + b * (64ull * WPS), tb.lane, w0);
+            trim(w0, b);
+            site_accumulate<WPS, SUBSET_P>(w0, mk, ps, acc);
         }
-    }
-    for (; b < tb.b1; b += 4) {
-        uint32_t w0[WPS];
-        load_site<WPS>(sb + b * (64ull * WPS), tb.lane, w0);
-        trim(w0, b);
-        site_accumulate<WPS, SUBSET_P>(w0, mk, ps, acc);
     }
     if (has_rare) {
         __shared__ uint16_t hcode[RARE_CODE_SIZE];
@@ -704,6 +793,9 @@ struct impop_scan_plan {
     const uint64_t *rare = nullptr;  // split index: m->d_vrare (tiles' rare ranges), packed route: m->d_vmulti, else null
     const uint16_t *single = nullptr;  // packed route: m->d_vsingle and every tile's range of it, else null
     SingleRange *d_singles = nullptr;
+    const uint32_t *uniq = nullptr;  // unique-row route: m->d_vuniq, m->d_vuniq_wt and every tile's range of them, else null
+    const uint8_t *uniq_wt = nullptr;
+    UniqRange *d_uniqs = nullptr;
     uint64_t n_windows = 0, n_tiles = 0, bytes_streamed = 0;
     PopSizes ps{};
     bool subset_p = false;
@@ -776,7 +868,9 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
 // IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it.  kept_sites = every
 // variable site of an indexed route; rare_sites / rare_bytes = the split index's rare entries (all of the matrix / the plan's);
 // split = on, or off:<the reason there is none, blanks as _>; single_sites = the singleton stream of a packed route (all of the
-// matrix), rare_streamed = the bytes of rare sites the plan really reads (rare_bytes keeps counting 8 per rare site)
+// matrix), rare_streamed = the bytes of rare sites the plan really reads (rare_bytes keeps counting 8 per rare site);
+// unique_rows = the representatives of the distinct-row stream of a unique-row route (all of the matrix), rows_streamed = the
+// bytes of rows the plan really reads (bytes_streamed = rows_streamed + rare_streamed)
 static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
     if (!trace_on()) return;
     const char *why = rt.indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
@@ -784,14 +878,42 @@ static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_w
     for (const ScanTile &t : rt.tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
     rare_streamed = rare_bytes;
     for (const SingleRange &r : rt.singles) { rare_bytes += (r.end - r.begin) * 8ull; rare_streamed += single_bytes_streamed(r); }
+    const uint64_t rows_streamed = rt.bytes_streamed - rare_streamed;
     std::string off = "off:" + (!m->wt_prefix.empty() && m->d_vrare ? std::string("site weights") : m->rskip);
     for (char &ch : off) ch = ch == ' ' ? '_' : ch;
-    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu%s%s\n",
+    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu unique_rows=%llu rows_streamed=%llu%s%s\n",
             rt.indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(rt.indexed ? m->n_vkept : m->g.n_site),
             (unsigned long long)rt.tiles.size(), (unsigned long long)rt.bytes_streamed, (unsigned long long)n_windows,
             (unsigned long long)(rt.split ? m->n_vrare : 0), (unsigned long long)rare_bytes, rt.split ? "on" : off.c_str(), (unsigned long long)(rt.packed ? m->n_vsingle : 0),
-            (unsigned long long)rare_streamed, *why ? " why=" : "", why);
+            (unsigned long long)rare_streamed, (unsigned long long)(rt.uniq ? m->n_vuniq : 0), (unsigned long long)rows_streamed,
+            *why ? " why=" : "", why);
     fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
+}
+
+// unique-row route: every tile's range of the distinct-row stream, from the tiles and the stream's per-block prefix where that
+// lives, on the device (one thread per tile), and back once: bytes_streamed stays the bytes a launch reads
+__global__ void uniq_ranges_kernel(const ScanTile *__restrict__ tiles, uint64_t n_tiles, const uint64_t *__restrict__ ubase,
+                                   uint32_t wps, UniqRange *__restrict__ out) {
+    const uint64_t k = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k < n_tiles) out[k] = uniq_range_of(tiles[k].site_begin, tiles[k].site_end, ubase, wps);
+}
+static int tile_uniq_ranges(impop_ctx *ctx, const impop_matrix *m, ScanRoute &rt) {
+    const size_t nt = rt.tiles.size();
+    rt.uniqs.resize(nt);
+    if (!nt) return IMPOP_OK;
+    REQUIRE((nt + 255) / 256 < 0x7FFFFFFFull, "impop_scan: too many tiles for one launch");
+    Carve L;
+    const size_t o_in = L.take<ScanTile>(nt), o_out = L.take<UniqRange>(nt);
+    void *d = nullptr;
+    const int rc = ctx_aux(ctx, 0, L.total(), &d);  // as map_windows_index: idle outside the all-pairs path
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(L.at<ScanTile>(d, o_in), rt.tiles.data(), nt * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(uniq_ranges_kernel, dim3((uint32_t)((nt + 255) / 256)), dim3(256), 0, ctx->stream,
+                       (const ScanTile *)L.at<ScanTile>(d, o_in), (uint64_t)nt, m->uidx.base, m->g.wps, L.at<UniqRange>(d, o_out));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(rt.uniqs.data(), L.at<UniqRange>(d, o_out), nt * sizeof(UniqRange), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return IMPOP_OK;
 }
 
 // every window lies in the matrix and is at most 2^32 - 1 sites long (impop_window_stats.n_sites is 32 bits wide)
@@ -841,7 +963,15 @@ int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, con
     }
     rt.tile_blocks = tile_blocks ? tile_blocks : default_tile_blocks(ctx, m, windows, rt);
     cut_tiles(rt.lw, rt.tile_blocks, m->g.wps, rt.packed, rt);
-    const int rc = window_weights(m, windows, n_windows, rt);
+    int rc = IMPOP_OK;
+    // unique-row route: the same tiles; each one's range of the distinct-row stream, whichever stream holds its rare sites
+    if (want_packed && rt.split && m->d_vuniq) {
+        rt.uniq = m->d_vuniq;
+        rt.uniq_wt = m->d_vuniq_wt;
+        if ((rc = tile_uniq_ranges(ctx, m, rt))) return rc;
+        rt.apply_uniq_ranges(m->g.wps);
+    }
+    rc = window_weights(m, windows, n_windows, rt);
     if (rc) return rc;
     REQUIRE(rt.tiles.size() < 0x7FFFFFFFull, "%s: %llu tiles exceed one launch; raise tile_blocks", fn,
             (unsigned long long)rt.tiles.size());
@@ -896,12 +1026,13 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
         mk.a[k] = p->masks[WPS + k];
         mk.b[k] = p->masks[2 * WPS + k];
     }
-    if (p->subset_p)
-        hipLaunchKernelGGL((scan_tiles_kernel<WPS, true>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare,
-                           p->d_tiles, mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles);
-    else
-        hipLaunchKernelGGL((scan_tiles_kernel<WPS, false>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare,
-                           p->d_tiles, mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles);
+#define LAUNCH(SP, UQ)                                                                                                        \
+    hipLaunchKernelGGL((scan_tiles_kernel<WPS, SP, UQ>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare, p->d_tiles, \
+                       mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles, p->uniq, p->uniq_wt,                \
+                       (const UniqRange *)p->d_uniqs)
+    if (p->d_uniqs) { if (p->subset_p) LAUNCH(true, true); else LAUNCH(false, true); }
+    else            { if (p->subset_p) LAUNCH(true, false); else LAUNCH(false, false); }
+#undef LAUNCH
 }
 
 IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows,
@@ -927,13 +1058,14 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     if (rc) return rc;
     HIP_TRY(hipSetDevice(ctx->device));
     ScanRoute rt;
-    // the plan will launch the fixed-WPS kernel (impop_scan_plan_launch), the one reader of the singleton stream
+    // the plan will launch the fixed-WPS kernel (impop_scan_plan_launch), the one reader of the singleton and distinct-row streams
     const bool fixed_wps = m->wt_prefix.empty() && m->g.wps <= 16;
     rc = scan_route("impop_scan", ctx, m, windows, n_windows, prm.tile_blocks, rt, fixed_wps);
     if (rc) return rc;
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
     p->sb = rt.sb; p->rare = rt.rare; p->single = rt.single;
+    p->uniq = rt.uniq; p->uniq_wt = rt.uniq_wt;
     p->n_tiles = rt.tiles.size(); p->bytes_streamed = rt.bytes_streamed;
     m->users++;
     p->d_pi_mode = prm.d_pi_mode; p->s_scope = prm.s_scope;
@@ -957,6 +1089,10 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     if (rt.packed) {
         PLAN_TRY(hipMalloc((void **)&p->d_singles, std::max<size_t>(rt.singles.size(), 1) * sizeof(SingleRange)));
         if (!rt.singles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_singles, rt.singles.data(), rt.singles.size() * sizeof(SingleRange), hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (rt.uniq) {
+        PLAN_TRY(hipMalloc((void **)&p->d_uniqs, std::max<size_t>(rt.uniqs.size(), 1) * sizeof(UniqRange)));
+        if (!rt.uniqs.empty()) PLAN_TRY(hipMemcpyAsync(p->d_uniqs, rt.uniqs.data(), rt.uniqs.size() * sizeof(UniqRange), hipMemcpyHostToDevice, ctx->stream));
     }
     if (!rt.tiles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_tiles, rt.tiles.data(), rt.tiles.size() * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
     if (n_windows) PLAN_TRY(hipMemcpyAsync(p->d_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
@@ -1088,6 +1224,7 @@ IMPOP_API int impop_scan_plan_destroy(impop_scan_plan *p) {
     if (p->d_out) hipFree(p->d_out);
     if (p->d_masks) hipFree(p->d_masks);
     if (p->d_singles) hipFree(p->d_singles);
+    if (p->d_uniqs) hipFree(p->d_uniqs);
     if (p->m) p->m->users--;
     delete p;
     return IMPOP_OK;

@@ -24,6 +24,11 @@ struct ScanRoute : TileCut {  // ... and how cut_tiles cut it: tiles, singles, w
     // Only scan_route sets it, and only for a caller that asked (impop_scan_plan_create for the fixed-WPS kernel).
     bool packed = false;
     const uint16_t *single = nullptr;
+    // unique-row route: the whole 64-row blocks of a tile come from the matrix's distinct-row stream (uniq = d_vuniq, uniq_wt =
+    // d_vuniq_wt, uniqs[k] = tile k's range of it) and only the partial blocks at window edges from sb.  Set like packed, for the
+    // same caller, whether or not the route is packed.
+    const uint32_t *uniq = nullptr;
+    const uint8_t *uniq_wt = nullptr;
     std::vector<LayoutWindow> lw;  // the windows as ranges of sb's sites, of rare's entries (split) and of single's (packed)
     uint32_t tile_blocks = 0;
 };
@@ -35,7 +40,8 @@ int check_windows(const char *fn, const impop_matrix *m, const impop_window *win
 // every window's W (window_W: its length, or the sum of its columns' weights) fits the 32 bits a record gives it
 int check_window_weights(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
 // windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams.  tile_blocks 0: the default.
-// want_packed: the caller's kernel reads the singleton stream; the route is packed when the matrix has one (else as without)
+// want_packed: the caller's kernel reads the singleton stream and the distinct-row stream; the route is packed when the matrix
+// has the one and a unique-row route when it has the other (else as without)
 int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                uint32_t tile_blocks, ScanRoute &rt, bool want_packed = false);
 // a tile-size override for tests, <name>=n in the environment: n clamped to 1..4096, 0 where the variable is unset or empty

@@ -25,6 +25,56 @@ struct SingleRange {
 };
 // what a workgroup reads of it: the aligned 8-byte words (four singletons each) the range touches
 inline uint64_t single_bytes_streamed(const SingleRange &r) { return r.end > r.begin ? ((r.end + 3) / 4 - r.begin / 4) * 8ull : 0; }
+// Unique-row route: a tile's range of the distinct-row stream (internal.h, d_vuniq), in rows of that stream.  A tile's common
+// rows [cb, ce) are a head (the part before the first 64-row boundary, if cb % 64 != 0), the whole blocks [g0, g1) between, and a
+// tail (the part after the last boundary, if ce % 64 != 0).  The whole blocks are streamed as their representatives with a
+// weight each, {ubase[g0], ubase[g1]} of the stream (ubase: the representatives before each block of common rows), where that
+// is fewer bytes (uniq_range_of); head and tail as the rows themselves.  A parallel array to the tiles like SingleRange; empty: every row of the tile is streamed as it is.
+struct UniqRange {
+    uint64_t begin, end;
+};
+#ifdef __HIPCC__
+#define IMPOP_TILE_HD __host__ __device__
+#else
+#define IMPOP_TILE_HD
+#endif
+// the whole 64-row blocks [g0, g1) of the rows [cb, ce); g0 >= g1: none
+struct MidBlocks {
+    uint64_t g0, g1;
+    IMPOP_TILE_HD bool any() const { return g1 > g0; }
+};
+IMPOP_TILE_HD inline MidBlocks mid_blocks(uint64_t cb, uint64_t ce) { return {(cb + 63) / 64, ce > cb ? ce / 64 : 0}; }
+// The fixed-WPS kernel's 32-bit lane sums with weights: a representative stands for up to 64 rows, each adding at most 2^16 to a
+// sum (c (n - c) and the A x B cross term at n <= 512), so 2^22 per weighted row.  A tile takes the stream only while its whole
+// blocks number at most UNIQ_MID_MAX: their representatives then touch at most UNIQ_MID_MAX + 1 blocks of the stream, a lane (one
+// wave in four, one row per block) at most ceil(2041 / 4) = 511 of them, 511 x 2^22 < 2^31; the lane's own head or tail row (2^16)
+// and its rare sites (2^24, scan.hip single_range) keep the total below 2^32.  A larger tile streams its rows as they are.
+constexpr uint64_t UNIQ_MID_MAX = 2040;
+constexpr uint64_t UNIQ_ROW_SUM_MAX = 1ull << 16, UNIQ_WEIGHT_MAX = 64, UNIQ_RARE_SUM_MAX = 1ull << 24;
+// the largest sum one lane of a 256-thread workgroup can reach for a tile with `mid` whole blocks that takes the stream
+inline uint64_t uniq_lane_sum_bound(uint64_t mid) {
+    return ((mid + 1 + 3) / 4) * UNIQ_WEIGHT_MAX * UNIQ_ROW_SUM_MAX + UNIQ_ROW_SUM_MAX + UNIQ_RARE_SUM_MAX;
+}
+// bytes of the blocks of the stream the rows [begin, end) of it touch, whole, each with its 64 weight bytes
+IMPOP_TILE_HD inline uint64_t uniq_bytes_streamed(uint64_t begin, uint64_t end, uint32_t wps) {
+    return end > begin ? ((end + 63) / 64 - begin / 64) * (256ull * wps + 64ull) : 0;
+}
+// A tile takes the stream for its whole blocks only where that reads fewer bytes than the blocks themselves (one whole block
+// never does: its representatives fill a block of the stream at least, and their weights come on top).
+IMPOP_TILE_HD inline UniqRange uniq_range_of(uint64_t cb, uint64_t ce, const uint64_t *ubase, uint32_t wps) {
+    const MidBlocks m = mid_blocks(cb, ce);
+    if (!m.any() || m.g1 - m.g0 > UNIQ_MID_MAX) return {0, 0};
+    const UniqRange u{ubase[m.g0], ubase[m.g1]};
+    return uniq_bytes_streamed(u.begin, u.end, wps) < (m.g1 - m.g0) * 256ull * wps ? u : UniqRange{0, 0};
+}
+// what a workgroup reads of a tile's rows on that route.  u empty: its blocks of rows, whole, as tile_bytes_streamed counts them.
+// Else the head's and the tail's block, whole, and the blocks of the stream the range touches, whole, each with its 64 weight bytes.
+inline uint64_t tile_row_bytes_streamed(const ScanTile &t, const UniqRange &u, uint32_t wps) {
+    if (t.site_end <= t.site_begin) return 0;
+    if (u.end <= u.begin) return ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps;
+    const uint64_t edge = (t.site_begin % 64 != 0) + (t.site_end % 64 != 0);
+    return edge * 256ull * wps + uniq_bytes_streamed(u.begin, u.end, wps);
+}
 struct WinDesc {
     uint64_t t0, t1;  // tile range
     uint64_t n_sites;
@@ -49,8 +99,21 @@ struct LayoutWindow {
 struct TileCut {
     std::vector<ScanTile> tiles;
     std::vector<SingleRange> singles;  // packed only: singles[k] is tile k's singleton range
+    std::vector<UniqRange> uniqs;      // unique-row route only: uniqs[k] is tile k's range of the distinct-row stream
     std::vector<WinDesc> wins;
     uint64_t bytes_streamed = 0;
+    // unique-row route: the tiles are cut (cut_tiles) and every tile's range is known (uniqs, one per tile): count the rows as
+    // that route reads them.  Returns the row bytes of the route.
+    uint64_t apply_uniq_ranges(uint32_t wps) {
+        uint64_t rows = 0;
+        for (size_t k = 0; k < tiles.size(); ++k) {
+            const ScanTile row_only{tiles[k].site_begin, tiles[k].site_end, 0, 0};
+            bytes_streamed -= tile_bytes_streamed(row_only, wps);
+            rows += tile_row_bytes_streamed(tiles[k], uniqs[k], wps);
+        }
+        bytes_streamed += rows;
+        return rows;
+    }
 };
 
 // windows -> elementary segments between sorted window boundaries (a segment is tiled iff some window covers it, and exactly
@@ -59,8 +122,11 @@ struct TileCut {
 // whichever stream holds it, tile_blocks blocks the budget): one workgroup reads a share of every stream.  Without rare sites
 // the tiles are those of the unsplit index.  Packed: a segment's rare sites are cut where the split route cuts them, and a
 // part's share of them is multis and singletons in the segment's own proportion; so the tiles, their number, every window's
-// tile range and every tile's count of rare sites are those of the split route.
-inline void cut_tiles(const std::vector<LayoutWindow> &windows, uint32_t tile_blocks, uint32_t wps, bool packed, TileCut &out) {
+// tile range and every tile's count of rare sites are those of the split route.  ubase (unique-row route; the representatives
+// before each 64-row block of the sites' layout, one entry past the last whole block): the same tiles, and every tile's range of
+// the distinct-row stream (uniq_range_of) with its rows counted as that route reads them.
+inline void cut_tiles(const std::vector<LayoutWindow> &windows, uint32_t tile_blocks, uint32_t wps, bool packed, TileCut &out,
+                      const uint64_t *ubase = nullptr) {
     std::vector<ScanTile> &tiles = out.tiles;
     std::vector<EdgeCut> cuts;
     cuts.reserve(2 * windows.size());
@@ -115,6 +181,10 @@ inline void cut_tiles(const std::vector<LayoutWindow> &windows, uint32_t tile_bl
     if (!cuts.empty()) seg_tile_start[cuts.size() - 1] = tiles.size();
     seg_tile_start[cuts.size()] = tiles.size();
     out.wins.resize(windows.size());
+    if (ubase) {
+        for (const ScanTile &t : tiles) out.uniqs.push_back(uniq_range_of(t.site_begin, t.site_end, ubase, wps));
+        out.apply_uniq_ranges(wps);
+    }
     for (size_t i = 0; i < windows.size(); ++i) {
         const LayoutWindow &w = windows[i];
         out.wins[i] = {w.empty() ? 0 : seg_tile_start[cut_index(w.lo)], w.empty() ? 0 : seg_tile_start[cut_index(w.hi)], w.hi.c - w.lo.c,

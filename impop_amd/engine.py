@@ -11,7 +11,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
+from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
                    ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, DstatParams, DstatStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
@@ -243,36 +243,41 @@ class Context:
 
     # ---- matrices -----------------------------------------------------------------
     def upload(self, bits_hap_major: np.ndarray, n_site: int, keep_hap_major: bool = True, dense_scan: bool = False,
-               rare_split: bool = True, single_stream: bool = True) -> "BitMatrix":
+               rare_split: bool = True, single_stream: bool = True, unique_rows: bool = True) -> "BitMatrix":
         """dense_scan=True: no variable-site scan index (IMPOP_KEEP_DENSE_SCAN); scans then stream every site.
         rare_split=False: the index keeps every variable site as a row (IMPOP_KEEP_NO_RARE_SPLIT).
-        single_stream=False: the split keeps no 2-byte singleton stream (IMPOP_KEEP_NO_SINGLE_STREAM)."""
+        single_stream=False: the split keeps no 2-byte singleton stream (IMPOP_KEEP_NO_SINGLE_STREAM).
+        unique_rows=False: the split keeps no distinct-row stream (IMPOP_KEEP_NO_UNIQUE_ROWS)."""
         b = np.ascontiguousarray(bits_hap_major, dtype=np.uint64)
         if b.ndim != 2:
             raise ValueError("bits must be [n_hap, words]")
         h = C.c_void_p()
         keep = KEEP_SITE_BLOCKED | (KEEP_HAP_MAJOR if keep_hap_major else 0) | (KEEP_DENSE_SCAN if dense_scan else 0) \
-            | (0 if rare_split else KEEP_NO_RARE_SPLIT) | (0 if single_stream else KEEP_NO_SINGLE_STREAM)
+            | (0 if rare_split else KEEP_NO_RARE_SPLIT) | (0 if single_stream else KEEP_NO_SINGLE_STREAM) \
+            | (0 if unique_rows else KEEP_NO_UNIQUE_ROWS)
         check(self._lib.impop_matrix_upload(self.handle, b.ctypes.data_as(C.POINTER(C.c_uint64)), b.shape[0], int(n_site),
                                             b.shape[1], keep, C.byref(h)))
         return BitMatrix(self, h)
 
     def upload_dense(self, mat01, keep_hap_major: bool = True, dense_scan: bool = False, rare_split: bool = True,
-                     single_stream: bool = True) -> "BitMatrix":
+                     single_stream: bool = True, unique_rows: bool = True) -> "BitMatrix":
         m = np.asarray(mat01)
-        return self.upload(pack_hap_major(m), m.shape[1], keep_hap_major, dense_scan, rare_split, single_stream)
+        return self.upload(pack_hap_major(m), m.shape[1], keep_hap_major, dense_scan, rare_split, single_stream, unique_rows)
 
     def synthetic(self, n_hap: int, n_site: int, seed: int = 20251031, n_founder: int = 8, p_founder: float = 1e-3,
                   p_private_word: float = 3.2e-3, keep_hap_major: bool = False, site_begin: int = 0,
-                  dense_scan: bool = False, rare_split: bool = True, single_stream: bool = True) -> "BitMatrix":
+                  dense_scan: bool = False, rare_split: bool = True, single_stream: bool = True,
+                  unique_rows: bool = True) -> "BitMatrix":
         """Sites [site_begin, site_begin + n_site) of the synthetic chromosome of `seed` (counter-based generator: a slab is
         a cut of the whole, impop_matrix_synthetic_slab); site 0 of the result is global site `site_begin`.
         dense_scan=True: no variable-site scan index (IMPOP_KEEP_DENSE_SCAN); rare_split=False: an index without the rare/common
-        split (IMPOP_KEEP_NO_RARE_SPLIT); single_stream=False: a split without the singleton stream (IMPOP_KEEP_NO_SINGLE_STREAM)."""
+        split (IMPOP_KEEP_NO_RARE_SPLIT); single_stream=False: a split without the singleton stream (IMPOP_KEEP_NO_SINGLE_STREAM);
+        unique_rows=False: a split without the distinct-row stream (IMPOP_KEEP_NO_UNIQUE_ROWS)."""
         p = SynthParams(int(seed), int(n_founder), float(p_founder), float(p_private_word))
         h = C.c_void_p()
         keep = KEEP_SITE_BLOCKED | (KEEP_HAP_MAJOR if keep_hap_major else 0) | (KEEP_DENSE_SCAN if dense_scan else 0) \
-            | (0 if rare_split else KEEP_NO_RARE_SPLIT) | (0 if single_stream else KEEP_NO_SINGLE_STREAM)
+            | (0 if rare_split else KEEP_NO_RARE_SPLIT) | (0 if single_stream else KEEP_NO_SINGLE_STREAM) \
+            | (0 if unique_rows else KEEP_NO_UNIQUE_ROWS)
         check(self._lib.impop_matrix_synthetic_slab(self.handle, int(n_hap), int(site_begin), int(n_site), C.byref(p), keep, C.byref(h)))
         return BitMatrix(self, h)
 
@@ -507,6 +512,14 @@ class BitMatrix:
         why = C.create_string_buffer(256)
         check(self.ctx._lib.impop_matrix_scan_single_info(self.handle, C.byref(s_), C.byref(m_), C.byref(b), why, len(why)))
         return {"n_single": s_.value, "n_multi": m_.value, "stream_bytes": b.value, "why": why.value.decode()}
+
+    def scan_unique_info(self) -> dict:
+        """The distinct-row stream of the split index: {"n_unique", "n_common", "stream_bytes"} (all 0 = none) and "why" (the
+        reason there is none, else "")."""
+        u, c, b = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        why = C.create_string_buffer(256)
+        check(self.ctx._lib.impop_matrix_scan_unique_info(self.handle, C.byref(u), C.byref(c), C.byref(b), why, len(why)))
+        return {"n_unique": u.value, "n_common": c.value, "stream_bytes": b.value, "why": why.value.decode()}
 
     def positions(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
         """Original site index of the kept sites of a compacted matrix."""

@@ -97,6 +97,14 @@ int impop_ctx_device_name(impop_ctx *ctx, char *buf, size_t buflen);
  * reads 2 bytes per singleton instead of 8.  Every other call keeps reading the 8-byte entries, which stay complete.
  * IMPOP_KEEP_NO_SINGLE_STREAM leaves the two streams out; impop_matrix_scan_single_info reports them, or why there are none. */
 #define IMPOP_KEEP_NO_SINGLE_STREAM 16u
+/* A split index of 65..512 haplotypes also keeps, per 64-row block of its common rows, the DISTINCT rows once with a one-byte
+ * multiplicity: rows that are equal, or each other's complement within the n_hap haplotypes (every sum and segregating test of
+ * a scan is the same for a row and its complement), are one representative of weight 1..64.  Plans of impop_scan_plan_create
+ * read the whole blocks of a tile from this stream and only the partial blocks at window edges as rows; records do not change.
+ * The stream is kept only where it pays (representatives at most 3/4 of the common rows) and costs nothing elsewhere; every
+ * other call keeps reading the rows, which stay complete.  IMPOP_KEEP_NO_UNIQUE_ROWS leaves it out (as does IMPOP_NO_UNIQUE_ROWS=1
+ * in the environment, for every matrix of the process); impop_matrix_scan_unique_info reports it, or why there is none. */
+#define IMPOP_KEEP_NO_UNIQUE_ROWS 32u
 
 int impop_matrix_upload(impop_ctx *ctx, const uint64_t *bits_hap_major, uint32_t n_hap, uint64_t n_site,
                         uint64_t row_stride_words, uint32_t keep_flags, impop_matrix **out);
@@ -172,6 +180,12 @@ int impop_matrix_scan_split_info(const impop_matrix *m, uint64_t *n_rare, uint64
  * nullable. */
 int impop_matrix_scan_single_info(const impop_matrix *m, uint64_t *n_single, uint64_t *n_multi, uint64_t *stream_bytes, char *why,
                                   size_t why_len);
+/* The distinct-row stream of that split (see IMPOP_KEEP_NO_UNIQUE_ROWS): n_unique = representatives over all 64-row blocks of
+ * the common rows, n_common = those rows, stream_bytes = device memory of the representatives' rows, their weight bytes and the
+ * per-block mask and prefix (counted in index_bytes); all 0 when there is none, and why receives the reason, else "".  All
+ * outputs nullable. */
+int impop_matrix_scan_unique_info(const impop_matrix *m, uint64_t *n_unique, uint64_t *n_common, uint64_t *stream_bytes, char *why,
+                                  size_t why_len);
 int impop_matrix_free(impop_ctx *ctx, impop_matrix *m);
 
 /* ---- windowed scan: pi + Hudson Fst + Tajima's D + S in one pass ------------
@@ -236,9 +250,14 @@ int impop_scan_plan_set_masks(impop_scan_plan *plan, const uint64_t *mask_p, con
 int impop_scan_plan_launch(impop_scan_plan *plan, void *d_out);
 /* Synchronise and copy the plan's internal result buffer to the host. */
 int impop_scan_plan_fetch(impop_scan_plan *plan, impop_window_stats *out_host);
-/* bytes_streamed: layout bytes one launch reads (of the kept-site layout when the plan streams the scan index).
+/* bytes_streamed: layout bytes one launch reads (of the kept-site layout when the plan streams the scan index; where a tile
+ * takes the distinct-row stream, the whole blocks of that stream its range touches and their 64 weight bytes each, in place
+ * of the tile's whole blocks of rows).
  * Under IMPOP_TRACE=1 impop_scan_plan_create prints one line per plan on stderr:
- *   [impop_scan] route=<indexed|dense|compact> kept_sites=<n> tiles=<n> bytes_streamed=<n> windows=<n> [why=<reason>] */
+ *   [impop_scan] route=<indexed|dense|compact> kept_sites=<n> tiles=<n> bytes_streamed=<n> windows=<n> rare_sites=<n>
+ *                rare_bytes=<n> split=<on|off:reason> single_sites=<n> rare_streamed=<n> unique_rows=<n> rows_streamed=<n> [why=<reason>]
+ * unique_rows: the representatives of the matrix's distinct-row stream when the plan reads it, else 0; rows_streamed: the bytes
+ * of rows (and representatives) among bytes_streamed, rare_streamed the rest. */
 int impop_scan_plan_info(const impop_scan_plan *plan, uint64_t *n_tiles, uint64_t *bytes_streamed);
 /* Measurement aid: with timing enabled every launch brackets the streaming kernel
  * (not the tiny epilogue) with hipEvents on the context's stream; elapsed() synchronises
