@@ -153,6 +153,23 @@ class DstatStats(C.Structure):
                 ("d", C.c_double), ("f4", C.c_double), ("fd", C.c_double)]
 
 
+class SfsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("outgroup", C.c_int32), ("tile_blocks", C.c_uint32), ("tables", C.c_uint32),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class SfsStats(C.Structure):
+    _fields_ = [("n_sites", C.c_uint32), ("seg", C.c_uint32), ("eta1", C.c_uint32), ("eta_n1", C.c_uint32), ("n_skipped", C.c_uint32),
+                ("flags", C.c_uint32), ("sum_het", C.c_uint64), ("sum_c", C.c_uint64), ("sum_c2", C.c_uint64),
+                ("theta_w", C.c_double), ("theta_pi", C.c_double), ("theta_h", C.c_double), ("theta_l", C.c_double),
+                ("tajima_d", C.c_double), ("faywu_h", C.c_double), ("faywu_h_norm", C.c_double), ("zeng_e", C.c_double)]
+
+
+class SfsPair(C.Structure):
+    _fields_ = [("private_a", C.c_uint32), ("private_b", C.c_uint32), ("shared", C.c_uint32), ("fixed_a", C.c_uint32),
+                ("fixed_b", C.c_uint32), ("n_union", C.c_uint32), ("n_skipped", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class Pica2Detail(C.Structure):
     _fields_ = [("sum_2pairs", C.c_double), ("n_pairs_with_data", C.c_uint64)]
 
@@ -186,6 +203,8 @@ assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(
 DIPLOID_MAX_N = 2048
 assert C.sizeof(DstatStats) == 80 and C.sizeof(DstatParams) == 16
 DSTAT_GROUP, DSTAT_MAX_QUARTETS = 3, 64
+assert C.sizeof(SfsStats) == 112 and C.sizeof(SfsPair) == 32 and C.sizeof(SfsParams) == 24
+SFS_PAIR_GROUP, SFS_MAX_PAIRS, SFS_TABLE_1D, SFS_TABLE_JOINT = 4, 28, 1, 2
 
 _vp = C.c_void_p
 _u64p = C.POINTER(C.c_uint64)
@@ -275,6 +294,10 @@ SIGNATURES = {
     "impop_dstat_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, _u32p, C.c_uint32, C.POINTER(DstatParams),
                                    C.POINTER(DstatStats)]),
     "impop_ctx_dstat_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_sfs_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, _u32p, C.c_uint32, C.POINTER(SfsParams),
+                                 C.POINTER(SfsStats), C.POINTER(SfsPair), _u32p, _u32p]),
+    "impop_sfs_neutrality": (C.c_int, [C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _f64p]),
+    "impop_ctx_sfs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_fst_grouped_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, _u8p, _u8p, C.c_double, C.c_uint64, C.c_int, _u32p, _f64p,
                                                   _u64p]),
     "impop_tajimas_d": (C.c_int, [_vp, _i64p, _f64p, _f64p, C.c_uint64, _f64p, _f64p]),

@@ -41,16 +41,6 @@ struct DstatAcc {
     uint32_t inf = 0, skip = 0;
 };
 
-// c[i] for a wave-uniform i: a chain of K selects (a register array has no run-time index).  The chain starts from a constant,
-// not from c[0]: a select between two elements of c is folded into a load through a selected ADDRESS, which keeps c in scratch.
-template <int K>
-__device__ __forceinline__ uint32_t dstat_pick(const uint32_t (&c)[K], uint32_t i) {
-    uint32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v = i == (uint32_t)k ? c[k] : v;
-    return v;
-}
-
 // One site of one quartet.  All products below are of counts / sizes of two different populations of the quartet: < 2^30.
 template <bool WEIGHTED>
 __device__ __forceinline__ void dstat_site(uint32_t c1, uint32_t c2, uint32_t c3, uint32_t cO, const DstatQuartet &q, bool polarize,

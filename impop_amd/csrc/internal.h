@@ -166,7 +166,8 @@ struct impop_ctx {
         T_LD = T_HAP + 3,    // impop_ld_scan: select / gather / pairs kernels (impop_ctx_ld_elapsed)
         T_DIP = T_LD + 3,    // impop_diploid_scan: tile / window kernels (impop_ctx_diploid_elapsed)
         T_DSTAT = T_DIP + 2, // impop_dstat_scan: the streaming launches (impop_ctx_dstat_elapsed)
-        T_COUNT
+        T_SFS,               // impop_sfs_scan: summary / table launches (impop_ctx_sfs_elapsed)
+        T_COUNT = T_SFS + 2
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the

@@ -112,6 +112,16 @@ __device__ __forceinline__ void pop_stream_tile(const uint32_t *__restrict__ sb,
     }
 }
 
+// c[i] for a wave-uniform i: a chain of K selects (a register array has no run-time index).  The chain starts from a constant,
+// not from c[0]: a select between two elements of c is folded into a load through a selected ADDRESS, which keeps c in scratch.
+template <int K>
+__device__ __forceinline__ uint32_t dstat_pick(const uint32_t (&c)[K], uint32_t i) {
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) v = i == (uint32_t)k ? c[k] : v;
+    return v;
+}
+
 // wave_val(i), i = 0 .. NV - 1: the wave's sum of the tile's value i (wave_sum_u64, or wave_sum_u32 for a 32-bit counter).  The four
 // waves' sums are added and the tile's row is written: out[blockIdx.x * NV + i].  No atomics: the same bits on every run.
 // The sums go SUMS at a time with one lane-0 store block behind them: one value at a time puts a branch and a wait behind every

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, DstatParams, DstatStats, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -53,6 +53,12 @@ assert DIPLOID_DTYPE.itemsize == 80 and DIPLOID_IND_DTYPE.itemsize == 24
 DSTAT_DTYPE = np.dtype([("n_sites", "<u4"), ("n_informative", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4"), ("abba", "<i8"), ("baba", "<i8"),
                         ("f4_num", "<i8"), ("fd_den_p2", "<i8"), ("fd_den_p3", "<i8"), ("d", "<f8"), ("f4", "<f8"), ("fd", "<f8")])
 assert DSTAT_DTYPE.itemsize == 80
+SFS_DTYPE = np.dtype([("n_sites", "<u4"), ("seg", "<u4"), ("eta1", "<u4"), ("eta_n1", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4"),
+                      ("sum_het", "<u8"), ("sum_c", "<u8"), ("sum_c2", "<u8"), ("theta_w", "<f8"), ("theta_pi", "<f8"), ("theta_h", "<f8"),
+                      ("theta_l", "<f8"), ("tajima_d", "<f8"), ("faywu_h", "<f8"), ("faywu_h_norm", "<f8"), ("zeng_e", "<f8")])
+SFS_PAIR_DTYPE = np.dtype([("private_a", "<u4"), ("private_b", "<u4"), ("shared", "<u4"), ("fixed_a", "<u4"), ("fixed_b", "<u4"),
+                           ("n_union", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4")])
+assert SFS_DTYPE.itemsize == 112 and SFS_PAIR_DTYPE.itemsize == 32
 
 PAIR_DTYPE = np.dtype([("fst", "<f8"), ("pi_a", "<f8"), ("pi_b", "<f8"), ("pi_xy", "<f8"), ("dxy", "<f8"), ("da", "<f8")])
 PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), ("n_members", "<u4"), ("n_groups", "<u4"), ("s_p", "<u4"),
@@ -223,6 +229,12 @@ class Context:
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_dstat_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
+
+    def sfs_elapsed(self):
+        """-> ([summary, table] kernel ms of sfs_scan, summary launches) since gram_timing(True)"""
+        t, k = (C.c_double * 2)(), C.c_uint64()
+        check(self._lib.impop_ctx_sfs_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
 
     def close(self) -> None:
         if self._h:
@@ -735,6 +747,58 @@ class BitMatrix:
                                              packed.ctypes.data_as(C.POINTER(C.c_uint64)), K, qa.ctypes.data_as(C.POINTER(C.c_uint32)),
                                              len(qa), C.byref(prm), out.ctypes.data_as(C.POINTER(DstatStats))))
         return out
+
+    def sfs_scan(self, windows, pops, pairs=(), outgroup=None, tables=(), tile_blocks: int = 0, max_chunk_bytes: int = 0):
+        """What is read from the site-frequency spectrum, per window (impop_sfs_scan): pops = 1..8 masks, pairs = rows (a, b) of
+        indices into pops (the two populations of a row disjoint), outgroup = the index of the population whose major allele is
+        ancestral, or None (counts as stored), tables = any of "sfs" (the 1-D spectra) and "jsfs" (the pairs' joint spectra).
+        -> (stats [n_windows, K] (SFS_DTYPE), pair records [n_windows, P] (SFS_PAIR_DTYPE), sfs, jsfs): sfs = None or a list of K
+        uint32 arrays [n_windows, n_k + 1], jsfs = None or a list of P arrays [n_windows, n_a + 1, n_b + 1]."""
+        w = make_windows(windows)
+        K = len(pops)
+        cols = [_mask_ptr(p, self.n_hap)[0] for p in pops]
+        packed = np.concatenate(cols).astype(np.uint64) if K else np.zeros(1, np.uint64)
+        pa = np.asarray(pairs, dtype=np.int64)
+        if pa.size and (pa.ndim != 2 or pa.shape[1] != 2):
+            raise ValueError("pairs must be rows (a, b) of population indices")
+        if pa.size and (pa.min() < 0 or pa.max() > 0xFFFFFFFF):
+            raise ValueError("population index outside 0 .. 2^32 - 1")
+        pa = np.ascontiguousarray(pa.reshape(-1, 2), dtype=np.uint32)
+        tables = (tables,) if isinstance(tables, str) else tuple(tables)
+        for t in tables:
+            if t not in ("sfs", "jsfs"):
+                raise ValueError(f"unknown table {t!r}: 'sfs' or 'jsfs'")
+        bits = (_lib.SFS_TABLE_1D if "sfs" in tables else 0) | (_lib.SFS_TABLE_JOINT if "jsfs" in tables else 0)
+        og = -1 if outgroup is None else int(outgroup)
+        if og < -1 or og > 0x7FFFFFFF:
+            raise ValueError("outgroup must be a population index or None")
+        nk = [int(sum(bin(int(x)).count("1") for x in c)) for c in cols]
+        stats = np.zeros((len(w), K), dtype=SFS_DTYPE)
+        prec = np.zeros((len(w), len(pa)), dtype=SFS_PAIR_DTYPE)
+        ok = all(int(x) < K for x in pa.ravel())  # the library refuses the call otherwise: no table is sized from a bad index
+        sfs_len = sum(n + 1 for n in nk)
+        jsfs_len = sum((nk[a] + 1) * (nk[b] + 1) for a, b in pa.tolist()) if ok else 0
+        sfs = np.zeros((len(w), sfs_len), dtype=np.uint32) if bits & 1 else None
+        jsfs = np.zeros((len(w), jsfs_len), dtype=np.uint32) if bits & 2 else None
+        prm = SfsParams(C.sizeof(SfsParams), og, int(tile_blocks), bits, int(max_chunk_bytes))
+        u32 = C.POINTER(C.c_uint32)
+        check(self.ctx._lib.impop_sfs_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
+                                           packed.ctypes.data_as(C.POINTER(C.c_uint64)), K, pa.ctypes.data_as(u32) if len(pa) else None,
+                                           len(pa), C.byref(prm), stats.ctypes.data_as(C.POINTER(SfsStats)),
+                                           prec.ctypes.data_as(C.POINTER(SfsPair)) if len(pa) else None,
+                                           sfs.ctypes.data_as(u32) if sfs is not None else None,
+                                           jsfs.ctypes.data_as(u32) if jsfs is not None else None))
+        sfs_list = jsfs_list = None
+        if sfs is not None:
+            off = np.concatenate([[0], np.cumsum([n + 1 for n in nk])])
+            sfs_list = [sfs[:, off[k]:off[k + 1]] for k in range(K)]
+        if jsfs is not None:
+            jsfs_list, o = [], 0
+            for a, b in pa.tolist():
+                cells = (nk[a] + 1) * (nk[b] + 1)
+                jsfs_list.append(jsfs[:, o:o + cells].reshape(len(w), nk[a] + 1, nk[b] + 1))
+                o += cells
+        return stats, prec, sfs_list, jsfs_list
 
     def ehh_scan(self, windows, cores, mask=None, ref_hap: int = 0, flanks: str = "reference", max_chunk_bytes: int = 0) -> np.ndarray:
         """Integrated EHH per core site (impop_ehh_scan; the area of scripts/wip/ehhgfa.py:63) for a batch of windows:

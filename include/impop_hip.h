@@ -689,6 +689,106 @@ int impop_dstat_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *
 /* With impop_ctx_gram_timing on, impop_dstat_scan brackets its streaming launches: their summed time and number since enable /
  * reset. */
 int impop_ctx_dstat_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
+#define IMPOP_SFS_PAIR_GROUP 4u   /* pairs whose counters one streaming launch of impop_sfs_scan keeps in registers */
+#define IMPOP_SFS_MAX_PAIRS 28u
+#define IMPOP_SFS_TABLE_1D 1u     /* impop_sfs_params.tables: bit 0 the 1-D spectra, bit 1 the joint spectra */
+#define IMPOP_SFS_TABLE_JOINT 2u
+/* Everything read from the site-frequency spectrum, per window: every population's spectrum summaries and neutrality statistics
+ * (Watterson's theta, theta_pi, theta_H, theta_L, Tajima's D, Fay & Wu's H, its normalised form and Zeng's E), every requested
+ * pair's Wakeley-Hey site classes, and optionally the 1-D and the joint spectra as tables; from the scan's own stream like
+ * impop_dstat_scan (indexed+rare, indexed, dense, compact, weighted).  masks holds n_pop (1..8) bitsets of ceil(n_hap / 64)
+ * words, every population non-empty; pairs holds n_pairs (0..IMPOP_SFS_MAX_PAIRS) x {a, b} indices into masks, a != b, the two
+ * populations of a pair disjoint (populations that share no pair may overlap); outgroup = a population index, or -1 for none.
+ * Per site, c_k = carriers of allele 1 among population k (n_k members).  With an outgroup O: 2 c_O == n_O makes the site a TIE,
+ * which adds 1 to n_skipped and to nothing else; 2 c_O > n_O turns every c_k into n_k - c_k (the outgroup's major allele is
+ * ancestral).  Without an outgroup the counts are taken as stored: the folded quantities (seg, sum_het, theta_w, theta_pi,
+ * tajima_d, the pair classes) do not depend on polarity, while eta1, eta_n1, sum_c, sum_c2, theta_h, theta_l, faywu_h,
+ * faywu_h_norm and zeng_e are meaningful only if allele 1 is the derived allele.  A site that is monomorphic among all haplotypes
+ * adds nothing to any field and is never a tie (its outgroup count is 0 or n_O), so the variable-site index and a compaction
+ * are exact.
+ * Per (window, population k), impop_sfs_stats: seg = #{0 < c_k < n_k}; over those segregating sites eta1 = #{c_k == 1},
+ * eta_n1 = #{c_k == n_k - 1}, sum_het = sum c (n - c), sum_c = sum c, sum_c2 = sum c^2.  On a weighted matrix the three sums
+ * carry the site weight, every counter and every table counts columns, n_sites is the window's weight sum.  The doubles are
+ * computed on the host from the integers, in one place (csrc/sfs_math.h), in exactly this order, with S = seg, n = n_k:
+ *     a1 = sum_{i=1}^{n-1} 1/i, a2 = sum 1/i^2 (ascending); b1, b2, c1, c2, e1, e2 as for impop_window_stats.tajima_d
+ *     P = n (n - 1) / 2
+ *     theta_w  = S / a1              theta_pi = sum_het / P         theta_h = sum_c2 / P         theta_l = sum_c / (n - 1)
+ *     tajima_d = (theta_pi - theta_w) / sqrt(e1 S + e2 S (S - 1))
+ *     T2 = S (S - 1) / (a1^2 + a2)   b = a2 + 1 / n^2
+ *     faywu_h  = theta_pi - theta_h
+ *     var_H = (n - 2) / (6 (n - 1)) theta_w + [18 n^2 (3 n + 2) b - (88 n^3 + 9 n^2 - 13 n + 6)] / (9 n (n - 1)^2) T2
+ *     faywu_h_norm = (theta_pi - theta_l) / sqrt(var_H)
+ *     var_E = (n / (2 (n - 1)) - 1 / a1) theta_w
+ *             + [a2 / a1^2 + 2 (n / (n - 1))^2 a2 - 2 (n a2 - n + 1) / ((n - 1) a1) - (3 n + 1) / (n - 1)] T2
+ *     zeng_e = (theta_l - theta_w) / sqrt(var_E)
+ * (the variances: Zeng et al. 2006, eqs. 14 and 12).  n < 2: all eight doubles are NaN.  A ratio (tajima_d, faywu_h_norm,
+ * zeng_e) is NaN when S == 0 or when its variance is <= 0 or not finite (n = 2 and n = 3 make some of them exactly 0).
+ * Per (window, pair (A, B)), impop_sfs_pair: private_a = A segregates and B does not, private_b the mirror case, shared = both
+ * segregate, fixed_a = c_A == n_A and c_B == 0, fixed_b = c_A == 0 and c_B == n_B, n_union = the sum of the five: exactly the
+ * sites that segregate in A + B.
+ * Tables (uint32, counting columns): sfs_out[w] concatenates the K spectra, n_k + 1 bins each; bin c counts the sites with
+ * c_k == c and 0 < c < n_k, bins 0 and n_k are 0 (so a population's spectrum does not depend on the other populations of the
+ * call).  jsfs_out[w] concatenates, per pair, an (n_A + 1) x (n_B + 1) table, row-major in c_A, over the pair's n_union sites:
+ * [0][0] and [n_A][n_B] are 0.
+ * Every integer is exact: neither the route, the tiling, the chunking nor the order of summation enters a record or a table.
+ * Known answer: 12 haplotypes, A = {0..4}, B = {5..9}, O = {10,11}, the carriers of a population its lowest-numbered members; 11
+ * sites with (c_A, c_B, c_O) = (1,0,0) (2,1,0) (5,0,0) (0,4,0) (1,1,1) (3,5,2) (0,0,0) (5,5,2) (0,0,1) (4,2,0) (0,5,2); one window
+ * [0, 11), pair (A, B).  Without an outgroup (seg, eta1, eta_n1, sum_het, sum_c, sum_c2): A 5 2 1 24 11 31, B 4 2 1 18 8 22,
+ * O 2 2 2 2 2 2; pair: private_a 2, private_b 1, shared 3, fixed_a 1, fixed_b 1, n_union 8; joint cells, one each: (0,4) (0,5)
+ * (1,0) (1,1) (2,1) (3,5) (4,2) (5,0).  A: theta_pi 2.4, theta_h 3.1, theta_l 2.75, faywu_h -0.7.  B: theta_w 1.92, theta_pi 1.8,
+ * tajima_d -0.41017465, faywu_h_norm -0.34892049, zeng_e 0.13767880.  With outgroup O, n_skipped is 2: A 4 1 1 20 9 25,
+ * B 3 1 1 14 7 21, O 0 0 0 0 0 0; pair: private_a 2, private_b 1, shared 2, fixed_a 2, fixed_b 0, n_union 7; joint cells (0,4)
+ * (1,0) (2,0) (2,1) (4,2) and (5,0) twice.  A: tajima_d 0.27344977, faywu_h -0.5, faywu_h_norm -0.43615061, zeng_e 0.56792505.
+ * A wrong struct_size, n_pop outside 1..8, n_pairs above IMPOP_SFS_MAX_PAIRS, an empty population, a pair with a == b or an index
+ * >= n_pop, a pair whose populations share a haplotype, outgroup >= n_pop (or below -1), n_hap > 65535, a window outside the
+ * matrix, tables bit 1 with n_pairs == 0 and a requested table whose pointer is NULL return IMPOP_E_INVALID;
+ * IMPOP_E_UNSUPPORTED unless n_k^2 times the largest window's weight sum is below 2^62 (the message names the population and
+ * the window: no sum can wrap); all before anything is uploaded or launched.  n_windows == 0 returns IMPOP_OK.
+ * The summary pass handles the pair list IMPOP_SFS_PAIR_GROUP at a time, all populations in the first launch: one streaming and
+ * one finalize launch per group, on the same tiles.  The table pass runs one job per requested table (a population's spectrum,
+ * a pair's joint spectrum) over (window, part) items, a part being a run of the window's tiles: a workgroup tallies its item
+ * into a histogram in LDS and adds the non-zero bins to the window's table with integer atomics; a job whose bins do not fit the
+ * LDS (the environment's IMPOP_SFS_LDS_BINS=0..40960 caps what the LDS form takes, a test aid) tallies straight into the table.
+ * Tables come down per chunk of windows; max_chunk_bytes (0 = 1 GiB) bounds the device memory of a chunk's tables.  tile_blocks
+ * (0 = default; the environment's IMPOP_SFS_TILE_BLOCKS=1..4096 overrides it) bounds a tile's 64-site blocks.  Checks the
+ * device error word like impop_haplotype_scan.  Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_sfs_scan] route=<indexed+rare|indexed|dense|compact> windows= tiles= pops= pairs= launches= table_jobs= lds_jobs=
+ *                    table_items= chunks= bytes_streamed= table_bytes_streamed=
+ * (table_bytes_streamed: what the table pass reads, overlapping windows re-reading the tiles they share). */
+typedef struct impop_sfs_params {     /* 24 bytes */
+    uint32_t struct_size;
+    int32_t  outgroup;         /* population index whose major allele is ancestral, -1: none (counts as stored) */
+    uint32_t tile_blocks;      /* 0 = default */
+    uint32_t tables;           /* IMPOP_SFS_TABLE_* bits */
+    uint64_t max_chunk_bytes;  /* 0 = 1 GiB */
+} impop_sfs_params;
+typedef struct impop_sfs_stats {      /* 112 bytes, fixed layout, [window][population] */
+    uint32_t n_sites;          /* as impop_window_stats.n_sites */
+    uint32_t seg;              /* sites with 0 < c < n */
+    uint32_t eta1;             /* of those, c == 1 */
+    uint32_t eta_n1;           /* of those, c == n - 1 */
+    uint32_t n_skipped;        /* outgroup ties of the window */
+    uint32_t flags;            /* 0 */
+    uint64_t sum_het;          /* sum w_s c (n - c) over the segregating sites */
+    uint64_t sum_c;            /* sum w_s c */
+    uint64_t sum_c2;           /* sum w_s c^2 */
+    double theta_w, theta_pi, theta_h, theta_l, tajima_d, faywu_h, faywu_h_norm, zeng_e;   /* host, from the integers, see above */
+} impop_sfs_stats;
+typedef struct impop_sfs_pair {       /* 32 bytes, fixed layout, [window][pair] */
+    uint32_t private_a, private_b, shared, fixed_a, fixed_b, n_union;
+    uint32_t n_skipped;        /* outgroup ties of the window */
+    uint32_t flags;            /* 0 */
+} impop_sfs_pair;
+int impop_sfs_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *masks,
+                   uint32_t n_pop, const uint32_t *pairs /* 2 x n_pairs, nullable */, uint32_t n_pairs, const impop_sfs_params *params,
+                   impop_sfs_stats *stats_out /* n_windows x n_pop */, impop_sfs_pair *pairs_out /* n_windows x n_pairs, nullable */,
+                   uint32_t *sfs_out /* nullable */, uint32_t *jsfs_out /* nullable */);
+/* The eight doubles of an impop_sfs_stats record from its integers (host only, no context), in the record's order: theta_w,
+ * theta_pi, theta_h, theta_l, tajima_d, faywu_h, faywu_h_norm, zeng_e. */
+int impop_sfs_neutrality(uint32_t n, uint64_t seg, uint64_t sum_het, uint64_t sum_c, uint64_t sum_c2, double out[8]);
+/* With impop_ctx_gram_timing on, impop_sfs_scan brackets its streaming launches: kernel_ms[0] = the summary pass, [1] = the table
+ * pass, summed since enable / reset; launches = the summary launches timed. */
+int impop_ctx_sfs_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *launches);
 /* Measurement aid (like impop_scan_plan_timing): with timing enabled every Gram launch of impop_pairwise_scan on this context
  * is bracketed with hipEvents on the context's stream; elapsed() synchronises and returns the summed Gram-kernel time and the
  * number of launches since enable / reset. */

@@ -15,6 +15,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
     impop_scan.py --matrix chr2.npz --bed windows.bed --format diploid [-u subset.txt] [--roh-min-sites N] [--ind-table PATH]   # Ho, He, F_IS, ROH
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format sfs --panel A.txt [B.txt ...] [--sfs-outgroup i] [--sfs-pair i,j]...   # spectra, neutrality tests
     impop_scan.py --matrix chr2.npz --bed windows.bed --format dstat --panel P1.txt P2.txt P3.txt O.txt [more.txt] [--quartet 1,2,3,4]...   # ABBA-BABA D, f4, f_d
 
 --sim-list FILE (instead of --matrix / --bed): TSV rows `chrom  start  end  sim_path  [S]`, one `impg similarity` table per
@@ -78,6 +79,17 @@ doubles "%.8f", nan where undefined).  --dstat-polarize takes the outgroup's maj
 the outgroup is split evenly).  --dstat-blocks N with --dstat-summary PATH writes per quartet the value over all rows with its
 block-jackknife error: P1 P2 P3 O D D_SE D_Z F_D F_D_SE BLOCKS ABBA BABA.  Streams the scan index; --compact allowed.  One process, one
 GPU; not with --sim-list, -A / -B / -l / -u, --devices N, -t / -r.
+
+--format sfs (impop_sfs_scan): what is read from the site-frequency spectrum, per BED row and population of the --panel lists (1..8
+of them).  One table CHROM START END POP N N_SITES S ETA1 ETA_N1 N_SKIPPED THETA_W THETA_PI THETA_H THETA_L TAJIMA_D FAYWU_H
+FAYWU_H_NORM ZENG_E, one row per window and population (POP = the list's base name, N = its sequences in the matrix; the doubles
+"%.8f", nan where undefined).  --sfs-outgroup i takes the major allele of list i (1-based) as ancestral per site; without it allele 1
+counts as derived, which THETA_H, THETA_L, FAYWU_H, FAYWU_H_NORM and ZENG_E rely on.  --sfs-pair i,j (repeatable, lists that share no
+sequence) with --sfs-pairs-out PATH writes per window and pair CHROM START END POP_A POP_B PRIVATE_A PRIVATE_B SHARED FIXED_A FIXED_B
+N_UNION.  --sfs-spectra PATH.npz writes sfs_<label> and (per pair) jsfs_<a>_<b>, summed over the rows of each of --sfs-blocks N
+consecutive groups of BED rows (default 1: the genome-wide spectra); the rows are scanned in batches, so the per-row tables never all
+sit in host memory.  Streams the scan index; --compact allowed.  One process, one GPU; not with --sim-list, -A / -B / -l / -u,
+--devices N, -t / -r.
 
 --panel A.txt B.txt ... (2..8 disjoint lists; run_tajd_panels.sh / run_h_fst_panels.sh).  --format hfst: one h-fst table per pair,
 headed `# A-vs-B`; --format tajd: one tajd table per panel, headed `# A`, SAMPLES = the list's line count, -t 0.999 -r 5 and S
@@ -266,6 +278,11 @@ class Runner:
     def dstat(self, pops, quartets, polarize):
         """ABBA-BABA D, f4 and f_d per window and quartet (impop_dstat_scan; DSTAT records [windows, quartets]).  One process, one GPU."""
         return self.bm.dstat_scan(self.local_wins, pops, quartets, polarize=polarize)
+
+    def sfs(self, pops, pairs, outgroup, tables, w0, w1):
+        """spectrum summaries, pair classes and (tables) spectra of the rows [w0, w1) (impop_sfs_scan) -> (SFS records [rows, pops],
+        SFS_PAIR records [rows, pairs], sfs or None, jsfs or None).  One process, one GPU."""
+        return self.bm.sfs_scan(self.local_wins[w0:w1], pops, pairs, outgroup=outgroup, tables=tables)
 
     def close(self):
         for sk, ck in zip(self.slabs, self.ctxs):
@@ -515,6 +532,101 @@ def dstat_refusal(args):
     except ValueError as e:
         return str(e)
     return None
+
+
+SFS_HEADER = ("CHROM\tSTART\tEND\tPOP\tN\tN_SITES\tS\tETA1\tETA_N1\tN_SKIPPED\tTHETA_W\tTHETA_PI\tTHETA_H\tTHETA_L\tTAJIMA_D\tFAYWU_H\t"
+              "FAYWU_H_NORM\tZENG_E")
+SFS_PAIRS_HEADER = "CHROM\tSTART\tEND\tPOP_A\tPOP_B\tPRIVATE_A\tPRIVATE_B\tSHARED\tFIXED_A\tFIXED_B\tN_UNION"
+SFS_DOUBLES = ("theta_w", "theta_pi", "theta_h", "theta_l", "tajima_d", "faywu_h", "faywu_h_norm", "zeng_e")
+SFS_BATCH_ROWS = 1024  # BED rows per impop_sfs_scan call of --sfs-spectra: their tables are summed into the blocks, then dropped
+
+
+def parse_sfs_pairs(specs, n_panel):
+    """--sfs-pair i,j (1-based positions in --panel, repeatable) -> [(a, b)] 0-based"""
+    out = []
+    for spec in specs or []:
+        try:
+            pair = tuple(int(x) - 1 for x in spec.split(","))
+        except ValueError:
+            pair = ()
+        if len(pair) != 2:
+            raise ValueError(f"--sfs-pair {spec}: two 1-based positions in --panel, as in 1,2")
+        for k in pair:
+            if not 0 <= k < n_panel:
+                raise ValueError(f"--sfs-pair {spec}: position {k + 1} is outside the {n_panel} lists of --panel")
+        if pair[0] == pair[1]:
+            raise ValueError(f"--sfs-pair {spec}: a population is named twice")
+        out.append(pair)
+    if len(out) > 28:
+        raise ValueError("--sfs-pair: at most 28 pairs per run")
+    return out
+
+
+def sfs_refusal(args):
+    """what --format sfs does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "sfs":
+        if (args.sfs_outgroup is not None or args.sfs_pair or args.sfs_pairs_out is not None or args.sfs_spectra is not None
+                or args.sfs_blocks is not None):
+            return "--sfs-outgroup / --sfs-pair / --sfs-pairs-out / --sfs-spectra / --sfs-blocks belong to --format sfs"
+        return None
+    if args.sim_list:
+        return "--format sfs scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format sfs is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format sfs runs on one GPU: not with --devices N"
+    if not args.panel or not 1 <= len(args.panel) <= 8:
+        return "--format sfs takes --panel A.txt [B.txt ...]: 1 to 8 population lists"
+    if args.pop_a or args.pop_b or args.sample_list or args.subset:
+        return "--format sfs reads the spectra of the populations of --panel: not with -A / -B / -l / -u"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    if args.sfs_outgroup is not None and not 1 <= args.sfs_outgroup <= len(args.panel):
+        return f"--sfs-outgroup {args.sfs_outgroup}: position is outside the {len(args.panel)} lists of --panel"
+    if args.sfs_blocks is not None and args.sfs_spectra is None:
+        return "--sfs-blocks N belongs to --sfs-spectra PATH.npz"
+    if args.sfs_blocks is not None and args.sfs_blocks < 1:
+        return "--sfs-blocks takes 1 or more"
+    try:
+        parse_sfs_pairs(args.sfs_pair, len(args.panel))
+    except ValueError as e:
+        return str(e)
+    if args.sfs_pairs_out is not None and not args.sfs_pair:
+        return "--sfs-pairs-out PATH needs at least one --sfs-pair i,j"
+    if args.sfs_pair and args.sfs_pairs_out is None and args.sfs_spectra is None:
+        return "--sfs-pair i,j goes with --sfs-pairs-out PATH or --sfs-spectra PATH.npz"
+    return None
+
+
+def sfs_row(region, label, n, r):
+    """one row of the --format sfs table: region, the population's list name and size, the record"""
+    chrom, start, end = split_region(region)
+    return (f"{chrom}\t{start}\t{end}\t{label}\t{int(n)}\t{int(r['n_sites'])}\t{int(r['seg'])}\t{int(r['eta1'])}\t{int(r['eta_n1'])}\t"
+            f"{int(r['n_skipped'])}\t" + "\t".join(f"{float(r[f]):.8f}" for f in SFS_DOUBLES))
+
+
+def sfs_pair_row(region, label_a, label_b, r):
+    """one row of --sfs-pairs-out: region, the pair's list names, the six counters"""
+    chrom, start, end = split_region(region)
+    return f"{chrom}\t{start}\t{end}\t{label_a}\t{label_b}\t" + "\t".join(
+        str(int(r[f])) for f in ("private_a", "private_b", "shared", "fixed_a", "fixed_b", "n_union"))
+
+
+def write_sfs_table(out, regions, labels, sizes_rows, recs):
+    """the table of --format sfs: one row per region and population from impop_sfs_stats records [regions, populations]"""
+    print(SFS_HEADER, file=out)
+    for reg, sizes, per_k in zip(regions, sizes_rows, recs):
+        for label, n, r in zip(labels, sizes, per_k):
+            print(sfs_row(reg, label, n, r), file=out)
+
+
+def write_sfs_pairs(out, regions, labels, pairs, recs):
+    print(SFS_PAIRS_HEADER, file=out)
+    for reg, per_p in zip(regions, recs):
+        for (a, b), r in zip(pairs, per_p):
+            print(sfs_pair_row(reg, labels[a], labels[b], r), file=out)
 
 
 def dstat_row(region, labels, quartet, sizes, r):
@@ -795,13 +907,15 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "dstat", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "dstat", "sfs", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
                          "ld = linkage disequilibrium per window (ZnS, mean |D'|, Kim-Nielsen omega; not part of `all`); "
                          "diploid = heterozygosity, F_IS and runs of homozygosity per window and individual (not part of `all`); "
-                         "dstat = Patterson's D (ABBA-BABA), f4 and f_d per window and quartet of --panel populations (not part of `all`)")
+                         "dstat = Patterson's D (ABBA-BABA), f4 and f_d per window and quartet of --panel populations (not part of `all`); "
+                         "sfs = spectrum summaries and neutrality tests per window and --panel population, pair classes and spectra "
+                         "(not part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
@@ -825,6 +939,15 @@ def main():
                     "groups of BED rows of the block jackknife")
     ap.add_argument("--dstat-summary", metavar="PATH", help="dstat: one row per quartet to PATH: D, its jackknife SE and Z, f_d and its "
                     "SE, the block count, the summed ABBA / BABA")
+    ap.add_argument("--sfs-outgroup", type=int, default=None, metavar="i", help="sfs: the major allele of --panel list i (1-based) is "
+                    "ancestral per site (a site where it is split evenly is skipped); default: allele 1 counts as derived")
+    ap.add_argument("--sfs-pair", action="append", default=None, metavar="i,j", help="sfs: a pair of --panel lists (1-based, no shared "
+                    "sequence) for --sfs-pairs-out and the joint spectra of --sfs-spectra; repeatable")
+    ap.add_argument("--sfs-pairs-out", metavar="PATH", help="sfs: one row per window and --sfs-pair to PATH: private, shared and fixed sites")
+    ap.add_argument("--sfs-spectra", metavar="PATH.npz", help="sfs: the 1-D spectrum of every list (sfs_<label>) and the joint spectrum of "
+                    "every --sfs-pair (jsfs_<a>_<b>), summed over the BED rows of each of --sfs-blocks groups")
+    ap.add_argument("--sfs-blocks", type=int, default=None, metavar="N", help="sfs: with --sfs-spectra, the number of consecutive groups "
+                    "of BED rows the spectra are summed over (default 1)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
                     "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
@@ -858,7 +981,8 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or dstat_refusal(args)
+    refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or dstat_refusal(args)
+               or sfs_refusal(args))
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
@@ -887,7 +1011,7 @@ def main():
     if args.panel and args.format in ("tajd", "all") and args.sample_list:
         print("Error: --panel with --format tajd / all takes every panel's list as its sample list: not with -l", file=sys.stderr)
         sys.exit(2)
-    if args.panel and not 2 <= len(args.panel) <= 8:
+    if args.panel and args.format != "sfs" and not 2 <= len(args.panel) <= 8:
         print("Error: --panel takes 2 to 8 population lists", file=sys.stderr)
         sys.exit(2)
     if world > 1:
@@ -931,7 +1055,7 @@ def main():
     want_pica = fmt in ("pica2", "tajd", "all", "fst3pi")
     want_fst = fmt in ("hfst", "all") and not args.panel
     need_pairs = (want_pica and pica_pairs) or (want_fst and fst_pairs) or fmt == "af"
-    if args.panel and fmt not in ("hfst", "tajd", "all", "dstat"):
+    if args.panel and fmt not in ("hfst", "tajd", "all", "dstat", "sfs"):
         print("Error: --panel belongs to --format hfst (every pair), tajd (every panel), all (both) or dstat (quartets)", file=sys.stderr)
         sys.exit(2)
     # --panel: the pair tables come from the streaming K-population scan (impop_scan_multi) when h-fst is unrounded on `match`,
@@ -941,6 +1065,7 @@ def main():
     if args.panel:
         need_pairs = panel_tajd or (panel_fst and fst_pairs)
     dstat_quartets = parse_quartets(args.quartet, len(args.panel)) if fmt == "dstat" else None
+    sfs_pairs = parse_sfs_pairs(args.sfs_pair, len(args.panel)) if fmt == "sfs" else []
 
     thr_txt = threshold_text if threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
     r_txt = "" if pica_r is None else str(pica_r)
@@ -1007,6 +1132,17 @@ def main():
     dip_ind = [None] * n_rows  # per row: (sample names, impop_diploid_ind rows)
     dstat_recs = np.zeros((n_rows, len(dstat_quartets or [])), dtype=impop_amd.DSTAT_DTYPE)
     dstat_sizes = [None] * n_rows  # per row: the populations' sizes in its matrix
+    sfs_recs = np.zeros((n_rows, len(args.panel) if fmt == "sfs" else 0), dtype=impop_amd.SFS_DTYPE)
+    sfs_pair_recs = np.zeros((n_rows, len(sfs_pairs)), dtype=impop_amd.SFS_PAIR_DTYPE)
+    sfs_sizes = [None] * n_rows
+    sfs_blocks, sfs_block_of = None, None  # --sfs-spectra: name -> [blocks, bins...] sums; the block of every row
+    if fmt == "sfs" and args.sfs_spectra:
+        from impop_amd.distributed import shard_range
+        n_blocks = args.sfs_blocks or 1
+        sfs_block_of = np.zeros(n_rows, dtype=np.int64)
+        for j in range(n_blocks):
+            lo, hi = shard_range(n_rows, n_blocks, j)
+            sfs_block_of[lo:hi] = j
     for key, idx in per_mat.items():
         mf = by_contig[key]
         names = mf.names
@@ -1047,6 +1183,46 @@ def main():
             if not mask_a.any() or not mask_b.any():
                 print("Error: No valid sequences found in one or both populations", file=sys.stderr)  # h-fst.py:319-321
                 sys.exit(1)
+        if fmt == "sfs":
+            panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
+            pops = [flags_for(f, names) for f in args.panel]
+            sizes = [int(p.sum()) for p in pops]
+            for k, n_k in enumerate(sizes):  # what impop_sfs_scan would refuse, with the lists' names
+                if n_k == 0:
+                    print(f"Error: --format sfs: {panel_labels[k]} selects no sequence of the matrix", file=sys.stderr)
+                    run.close()
+                    sys.exit(2)
+            for a, b in sfs_pairs:
+                if (pops[a] & pops[b]).any():
+                    print(f"Error: --format sfs: {panel_labels[a]} and {panel_labels[b]} share a sequence; the two populations of a pair "
+                          "must be disjoint", file=sys.stderr)
+                    run.close()
+                    sys.exit(2)
+            outgroup = None if args.sfs_outgroup is None else args.sfs_outgroup - 1
+            tables = (("sfs",) + (("jsfs",) if sfs_pairs else ())) if args.sfs_spectra else ()
+            batch = SFS_BATCH_ROWS if tables else max(len(idx), 1)
+            for w0 in range(0, len(idx), batch):
+                part = idx[w0:w0 + batch]
+                st, pr, sfs, jsfs = run.sfs(pops, sfs_pairs, outgroup, tables, w0, w0 + len(part))
+                sfs_recs[part] = st
+                if sfs_pairs:
+                    sfs_pair_recs[part] = pr
+                if tables:
+                    named = [(f"sfs_{panel_labels[k]}", t) for k, t in enumerate(sfs)]
+                    named += [(f"jsfs_{panel_labels[a]}_{panel_labels[b]}", t) for (a, b), t in zip(sfs_pairs, jsfs or [])]
+                    if sfs_blocks is None:
+                        sfs_blocks = {nm: np.zeros((args.sfs_blocks or 1,) + t.shape[1:], dtype=np.uint64) for nm, t in named}
+                    for nm, t in named:
+                        if sfs_blocks[nm].shape[1:] != t.shape[1:]:
+                            print(f"Error: --sfs-spectra: {nm} has another shape in the matrix of {key or 'the run'} (the lists select "
+                                  "another number of its sequences); write the spectra per matrix", file=sys.stderr)
+                            run.close()
+                            sys.exit(2)
+                        np.add.at(sfs_blocks[nm], sfs_block_of[part], t.astype(np.uint64))
+            for i in idx:
+                sfs_sizes[i] = sizes
+            run.close()
+            continue
         if fmt == "dstat":
             panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
             pops = [flags_for(f, names) for f in args.panel]
@@ -1253,6 +1429,13 @@ def main():
         if args.dstat_summary:
             with open(args.dstat_summary, "w") as fh:
                 write_dstat_summary(fh, panel_labels or [], dstat_quartets, dstat_sizes, dstat_recs, args.dstat_blocks)
+    elif fmt == "sfs":
+        write_sfs_table(out, [r[0] for r in rows], panel_labels or [], sfs_sizes, sfs_recs)
+        if args.sfs_pairs_out:
+            with open(args.sfs_pairs_out, "w") as fh:
+                write_sfs_pairs(fh, [r[0] for r in rows], panel_labels or [], sfs_pairs, sfs_pair_recs)
+        if args.sfs_spectra:
+            np.savez(args.sfs_spectra, **(sfs_blocks or {}))
     elif fmt == "ehh":
         print(EHH_HEADER, file=out)
         for lines in ehh_lines:
