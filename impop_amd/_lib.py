@@ -143,6 +143,26 @@ class DiploidInd(C.Structure):
                 ("roh_sites", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class IbsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_sites", C.c_uint32), ("site_begin", C.c_uint64), ("site_end", C.c_uint64),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class IbsPair(C.Structure):
+    _fields_ = [("h1", C.c_uint32), ("h2", C.c_uint32), ("n_diff", C.c_uint32), ("longest", C.c_uint32), ("n_tracts", C.c_uint32),
+                ("reserved", C.c_uint32), ("tract_sites", C.c_uint64)]
+
+
+class IbsSegment(C.Structure):
+    _fields_ = [("h1", C.c_uint32), ("h2", C.c_uint32), ("begin", C.c_uint64), ("end", C.c_uint64), ("pair", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class IbsWindow(C.Structure):
+    _fields_ = [("pair_sites", C.c_uint64), ("tracts", C.c_uint32), ("pairs_spanning", C.c_uint32), ("n_sites", C.c_uint32),
+                ("reserved", C.c_uint32), ("share", C.c_double)]
+
+
 class DstatParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("polarize", C.c_int32), ("tile_blocks", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -201,6 +221,8 @@ assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
 LD_MAX_N, LD_MAX_SITES = 4096, 1024
 assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(DiploidParams) == 16
 DIPLOID_MAX_N = 2048
+assert C.sizeof(IbsParams) == 32 and C.sizeof(IbsPair) == 32 and C.sizeof(IbsSegment) == 32 and C.sizeof(IbsWindow) == 32
+IBS_MAX_N, IBS_MAX_PAIRS, IBS_OPEN_LEFT, IBS_OPEN_RIGHT = 4096, 8388608, 1, 2
 assert C.sizeof(DstatStats) == 80 and C.sizeof(DstatParams) == 16
 DSTAT_GROUP, DSTAT_MAX_QUARTETS = 3, 64
 assert C.sizeof(SfsStats) == 112 and C.sizeof(SfsPair) == 32 and C.sizeof(SfsParams) == 24
@@ -291,6 +313,9 @@ SIGNATURES = {
     "impop_diploid_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u32p, C.c_uint32, C.POINTER(DiploidParams),
                                      C.POINTER(DiploidStats), C.POINTER(DiploidInd)]),
     "impop_ctx_diploid_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_ibs_scan": (C.c_int, [_vp, _vp, _u64p, _u32p, C.c_uint64, C.POINTER(Window), C.c_uint64, C.POINTER(IbsParams),
+                                 C.POINTER(IbsPair), C.POINTER(IbsSegment), C.c_uint64, _u64p, C.POINTER(IbsWindow)]),
+    "impop_ctx_ibs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_dstat_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, _u32p, C.c_uint32, C.POINTER(DstatParams),
                                    C.POINTER(DstatStats)]),
     "impop_ctx_dstat_elapsed": (C.c_int, [_vp, _f64p, _u64p]),

@@ -167,7 +167,8 @@ struct impop_ctx {
         T_DIP = T_LD + 3,    // impop_diploid_scan: tile / window kernels (impop_ctx_diploid_elapsed)
         T_DSTAT = T_DIP + 2, // impop_dstat_scan: the streaming launches (impop_ctx_dstat_elapsed)
         T_SFS,               // impop_sfs_scan: summary / table launches (impop_ctx_sfs_elapsed)
-        T_COUNT = T_SFS + 2
+        T_IBS = T_SFS + 2,   // impop_ibs_scan: transpose / walk / combine + close kernels (impop_ctx_ibs_elapsed)
+        T_COUNT = T_IBS + 3
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
@@ -289,7 +290,8 @@ constexpr uint32_t DEV_ERR_CLUSTER = 2u;             // af label propagation ran
 constexpr uint32_t DEV_ERR_HAPSCAN = 8u;             // haplotype scan: the classes of a window do not partition its members
 constexpr uint32_t DEV_ERR_LDSCAN = 16u;             // LD scan: the rows gathered for a window are not its n_used
 constexpr uint32_t DEV_ERR_DIPLOID = 32u;           // diploid scan: a window's rows do not add up to its het_total or its length
-constexpr uint32_t DEV_ERR_EHH = 4u;                 // ehh partition refinement ended with classes that do not account for the unbroken pairs
+constexpr uint32_t DEV_ERR_IBS = 64u;               // IBS scan: a pair's runs do not add up to the range, or the fill met a tract the count did not announce
+constexpr uint32_t DEV_ERR_EHH = 4u;                // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need
 // to be distinct among the members, else IMPOP_E_INVALID with *dup = a rank that occurs twice (the caller words the message)

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -50,6 +50,12 @@ DIPLOID_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("s_p", "<u4"), 
 DIPLOID_IND_DTYPE = np.dtype([("het", "<u4"), ("hom_alt", "<u4"), ("longest_run", "<u4"), ("roh_runs", "<u4"), ("roh_sites", "<u4"),
                               ("reserved", "<u4")])
 assert DIPLOID_DTYPE.itemsize == 80 and DIPLOID_IND_DTYPE.itemsize == 24
+IBS_PAIR_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("n_diff", "<u4"), ("longest", "<u4"), ("n_tracts", "<u4"), ("reserved", "<u4"),
+                           ("tract_sites", "<u8")])
+IBS_SEGMENT_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("begin", "<u8"), ("end", "<u8"), ("pair", "<u4"), ("flags", "<u4")])
+IBS_WINDOW_DTYPE = np.dtype([("pair_sites", "<u8"), ("tracts", "<u4"), ("pairs_spanning", "<u4"), ("n_sites", "<u4"), ("reserved", "<u4"),
+                             ("share", "<f8")])
+assert IBS_PAIR_DTYPE.itemsize == 32 and IBS_SEGMENT_DTYPE.itemsize == 32 and IBS_WINDOW_DTYPE.itemsize == 32
 DSTAT_DTYPE = np.dtype([("n_sites", "<u4"), ("n_informative", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4"), ("abba", "<i8"), ("baba", "<i8"),
                         ("f4_num", "<i8"), ("fd_den_p2", "<i8"), ("fd_den_p3", "<i8"), ("d", "<f8"), ("f4", "<f8"), ("fd", "<f8")])
 assert DSTAT_DTYPE.itemsize == 80
@@ -222,6 +228,12 @@ class Context:
         """-> ([tile, window] kernel ms of diploid_scan, chunks) since gram_timing(True)"""
         t, k = (C.c_double * 2)(), C.c_uint64()
         check(self._lib.impop_ctx_diploid_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def ibs_elapsed(self):
+        """-> ([transpose, walk, combine + close] kernel ms of ibs_scan, site chunks transposed) since gram_timing(True)"""
+        t, k = (C.c_double * 3)(), C.c_uint64()
+        check(self._lib.impop_ctx_ibs_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def dstat_elapsed(self):
@@ -726,6 +738,61 @@ class BitMatrix:
                                                out.ctypes.data_as(C.POINTER(DiploidStats)),
                                                ind.ctypes.data_as(C.POINTER(DiploidInd)) if want_individuals else None))
         return (out, ind) if want_individuals else out
+
+    def ibs_scan(self, pairs=None, mask_p=None, min_sites: int = 1, site_begin: int = 0, site_end: Optional[int] = None, windows=None,
+                 want_segments: bool = True, max_chunk_bytes: int = 0, seg_capacity: Optional[int] = None):
+        """Pairwise identity-by-state tracts over [site_begin, site_end) (impop_ibs_scan; site_end None = the matrix's end): every
+        pair of the members of mask_p (None = all haplotypes), or pairs = [n, 2] haplotype indices.  -> (pair records
+        (IBS_PAIR_DTYPE), segments (IBS_SEGMENT_DTYPE: the tracts of at least min_sites sites, pair-major) or None, window records
+        (IBS_WINDOW_DTYPE) or None, the total number of segments).  Segments: one counting call, then one filling call; or, with
+        seg_capacity given, one call with room for that many (None when the list is longer)."""
+        pp, n_pairs, pr = None, 0, None
+        if pairs is not None:
+            pr = np.asarray(pairs)
+            if pr.size and (pr.ndim != 2 or pr.shape[1] != 2):
+                raise ValueError("pairs must be [n, 2] haplotype indices")
+            if pr.size and (pr.min() < 0 or pr.max() > 0xFFFFFFFF):
+                raise ValueError("haplotype index outside 0 .. 2^32 - 1")
+            pr = np.ascontiguousarray(pr.reshape(-1, 2), dtype=np.uint32)
+            n_pairs = len(pr)
+            pp = pr.ctypes.data_as(C.POINTER(C.c_uint32))
+            n_rec = n_pairs
+        else:
+            flags = None if mask_p is None else np.asarray(mask_p)
+            if flags is None:
+                k = self.n_hap
+            elif flags.dtype == np.uint64:
+                k = int(sum(bin(int(x)).count("1") for x in flags))
+            else:
+                k = int(np.count_nonzero(flags))
+            n_rec = k * (k - 1) // 2
+        mk, mp = _mask_ptr(mask_p, self.n_hap)
+        w = None if windows is None else make_windows(windows)
+        prm = IbsParams(C.sizeof(IbsParams), int(min_sites), int(site_begin), 0 if site_end is None else int(site_end), int(max_chunk_bytes))
+        rec = np.zeros(max(n_rec, 0), dtype=IBS_PAIR_DTYPE)
+        win = None if w is None else np.zeros(len(w), dtype=IBS_WINDOW_DTYPE)
+        total = C.c_uint64(0)
+
+        def call(seg, cap):
+            check(self.ctx._lib.impop_ibs_scan(self.ctx.handle, self.handle, mp, pp, n_pairs,
+                                               None if w is None else w.ctypes.data_as(C.POINTER(Window)), 0 if w is None else len(w),
+                                               C.byref(prm), rec.ctypes.data_as(C.POINTER(IbsPair)),
+                                               None if seg is None else seg.ctypes.data_as(C.POINTER(IbsSegment)), cap, C.byref(total),
+                                               None if win is None else win.ctypes.data_as(C.POINTER(IbsWindow))))
+
+        seg = None
+        if not want_segments:
+            call(None, 0)
+        elif seg_capacity is not None:
+            seg = np.zeros(int(seg_capacity), dtype=IBS_SEGMENT_DTYPE)
+            call(seg, len(seg))
+            seg = seg[:total.value] if total.value <= len(seg) else None
+        else:
+            call(None, 0)
+            seg = np.zeros(total.value, dtype=IBS_SEGMENT_DTYPE)
+            if total.value:
+                call(seg, len(seg))
+        return rec, seg, win, int(total.value)
 
     def dstat_scan(self, windows, pops, quartets, polarize: bool = False, tile_blocks: int = 0) -> np.ndarray:
         """Patterson's D (ABBA-BABA), f4 and Martin's f_d per window and quartet (impop_dstat_scan): pops = 4..8 masks, quartets =

@@ -627,6 +627,81 @@ int impop_diploid_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window
 /* With impop_ctx_gram_timing on, impop_diploid_scan brackets its kernels per chunk: kernel_ms[0] = tile summaries, [1] = window
  * records, summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_diploid_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks);
+#define IMPOP_IBS_MAX_N     4096u        /* |P| in the all-pairs form */
+#define IMPOP_IBS_MAX_PAIRS 8388608u     /* pairs per call, either form (>= C(4096,2)) */
+#define IMPOP_IBS_OPEN_LEFT  1u          /* tract begins at site_begin: cut by the range, not by a difference */
+#define IMPOP_IBS_OPEN_RIGHT 2u          /* tract ends at site_end */
+/* Pairwise identity-by-state tracts over a whole range of sites in one pass: where two haplotypes are identical, and for how
+ * long.  Between the two copies of one sample these are the runs of homozygosity as segments.  Works on full, weighted and
+ * compacted matrices, from the site-major rows alone (no hap-major operand).
+ * Pairs: either every pair i < j of the members of mask_p (NULL = all haplotypes), i-major in ascending haplotype order, or,
+ * with pairs non-NULL, the n_pairs listed (h1, h2); n_pairs is ignored in the all-pairs form.  A pair may repeat and a
+ * haplotype may be in any number of pairs.  Swapping h1 and h2 changes nothing but the two fields.
+ * Definition: for pair (h1, h2) and range [b, e) = [site_begin, site_end) let p_1 < ... < p_k be the sites of the range where
+ * the two rows differ.  The tracts are [b, p_1), (p_j + 1 .. p_{j+1}) for each j and [p_k + 1, e); with k = 0 there is one tract
+ * [b, e).  Tracts of length 0 are not tracts.  These are impop_diploid_scan's runs for the "individual" (h1, h2) and window
+ * [b, e).  Reported tracts are those with end - begin >= min_sites; n_diff and longest do not depend on min_sites.  The segment
+ * list is pair-major, ascending begin inside a pair.  Site weights play no part (n_sites of a window record is its W as every
+ * other record reports it).  On a compacted matrix the coordinates are the kept sites' original positions, so dropped
+ * monomorphic sites lie inside tracts.  site_end - site_begin must be below 2^32.
+ * Segment capacity: *n_segments always receives the total.  When seg_out is NULL or seg_capacity is smaller than the total, the
+ * call returns IMPOP_OK and writes nothing to seg_out; pair_out and win_out are filled all the same, so the caller can call
+ * again with room.  The device never writes a segment past what the counting sweep announced: a mismatch between the two sweeps
+ * sets the device error word and the call returns IMPOP_E_INTERNAL.
+ * Window records are integer sums over the REPORTED tracts, formed with integer atomics and sums only, whether or not the
+ * segment list is returned; no per-site array over the range is used, and chunking never changes them.  An empty window gets
+ * zeros and share = NaN.
+ * Known answer: rows over 6 sites, site 0 first, h0 = 100010, h1 = 000010, h2 = 110000, h3 = 100001; all pairs, range [0, 6),
+ * min_sites = 2.  (0,1): n_diff 1, longest 5, tract [1,6) OPEN_RIGHT; (0,2): 2, 2, [2,4); (0,3): 2, 4, [0,4) OPEN_LEFT;
+ * (1,2): 3, 2, [2,4); (1,3): 3, 3, [1,4); (2,3): 2, 3, [2,5).  Six segments, 19 tract sites.  Windows (pair_sites, tracts,
+ * pairs_spanning): [0,6) -> (19, 6, 0); [2,4) -> (12, 6, 6); [3,6) -> (9, 6, 1).
+ * A wrong struct_size, min_sites == 0, an empty or out-of-matrix range, h1 == h2, an index >= n_hap, both pairs and mask_p,
+ * fewer than 2 members (or n_pairs == 0), a window not inside the range and a win_out / windows nullness mismatch return
+ * IMPOP_E_INVALID; |P| > IMPOP_IBS_MAX_N and n_pairs > IMPOP_IBS_MAX_PAIRS IMPOP_E_UNSUPPORTED; all before anything is uploaded
+ * or launched.  max_chunk_bytes (0 = 1 GiB) bounds the transposed words of one chunk of sites plus the segment staging of one
+ * range of pairs.  IMPOP_IBS_CHUNK_BLOCKS=n (1..4096) sets the site-chunk length in 64-site blocks and IMPOP_IBS_SEG_BLOCKS=n
+ * the length of the sub-segments of a chunk that run in parallel (test aids); records never change with either.
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_ibs_scan] route=<dense|compact> pairs= site_chunks= sub_segments= launches= tracts= bytes_streamed=
+ * (bytes_streamed: the site-major rows the transposes read plus the transposed words the walks read). */
+typedef struct impop_ibs_params {        /* 32 bytes */
+    uint32_t struct_size;
+    uint32_t min_sites;                  /* >= 1: a tract is reported when it is at least this many sites long */
+    uint64_t site_begin, site_end;       /* the range, ORIGINAL site coordinates; site_end == 0: the matrix's end */
+    uint64_t max_chunk_bytes;            /* 0 = 1 GiB: bounds the device memory of one chunk */
+} impop_ibs_params;
+typedef struct impop_ibs_pair {          /* 32 bytes, fixed layout, one per pair, in pair order */
+    uint32_t h1, h2;
+    uint32_t n_diff;                     /* sites of the range where the two rows differ */
+    uint32_t longest;                    /* longest tract of any length (0 when the rows differ at every site) */
+    uint32_t n_tracts;                   /* tracts >= min_sites */
+    uint32_t reserved;
+    uint64_t tract_sites;                /* sites inside those */
+} impop_ibs_pair;
+typedef struct impop_ibs_segment {       /* 32 bytes, fixed layout */
+    uint32_t h1, h2;
+    uint64_t begin, end;                 /* [begin, end), ORIGINAL coordinates */
+    uint32_t pair;                       /* index into the pair order */
+    uint32_t flags;                      /* IMPOP_IBS_OPEN_* */
+} impop_ibs_segment;
+typedef struct impop_ibs_window {        /* 32 bytes, fixed layout, one per window */
+    uint64_t pair_sites;                 /* sum over reported tracts of |tract intersected with the window| */
+    uint32_t tracts;                     /* reported tracts that meet the window */
+    uint32_t pairs_spanning;             /* reported tracts that contain the whole window (at most one per pair) */
+    uint32_t n_sites, reserved;          /* W as every other record reports it */
+    double share;                        /* host: (double)pair_sites / ((double)n_pairs * (double)(end - begin)); NaN for an empty window */
+} impop_ibs_window;
+int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m,
+                   const uint64_t *mask_p,            /* all-pairs form: pairs i < j of the members, i-major; NULL = all haplotypes */
+                   const uint32_t *pairs, uint64_t n_pairs,   /* list form: h1,h2 per pair; non-NULL excludes mask_p */
+                   const impop_window *windows, uint64_t n_windows,   /* nullable */
+                   const impop_ibs_params *params,
+                   impop_ibs_pair *pair_out,          /* nullable */
+                   impop_ibs_segment *seg_out, uint64_t seg_capacity, uint64_t *n_segments,
+                   impop_ibs_window *win_out);        /* n_windows records; NULL iff windows is NULL */
+/* With impop_ctx_gram_timing on, impop_ibs_scan brackets its kernels: kernel_ms[0] = transposes, [1] = the walks of both sweeps,
+ * [2] = combine / close kernels, summed since enable / reset; chunks = site chunks transposed (both sweeps counted). */
+int impop_ctx_ibs_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
 #define IMPOP_DSTAT_GROUP 3u   /* quartets whose sums one streaming launch of impop_dstat_scan keeps in registers */
 #define IMPOP_DSTAT_MAX_QUARTETS 64u
 /* Introgression statistics per window and quartet of populations (P1, P2, P3, O): Patterson's D (ABBA-BABA), f4 and Martin's f_d,

@@ -15,6 +15,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
     impop_scan.py --matrix chr2.npz --bed windows.bed --format diploid [-u subset.txt] [--roh-min-sites N] [--ind-table PATH]   # Ho, He, F_IS, ROH
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format ibs [-u subset.txt] [--ibs-min-sites N] [--ibs-pairs all|diploid] [--ibs-segments PATH] [--ibs-pair-table PATH]   # IBS tracts / ROH segments
     impop_scan.py --matrix chr2.npz --bed windows.bed --format sfs --panel A.txt [B.txt ...] [--sfs-outgroup i] [--sfs-pair i,j]...   # spectra, neutrality tests
     impop_scan.py --matrix chr2.npz --bed windows.bed --format dstat --panel P1.txt P2.txt P3.txt O.txt [more.txt] [--quartet 1,2,3,4]...   # ABBA-BABA D, f4, f_d
 
@@ -69,6 +70,18 @@ site, HE = 2 sum p q n / (n - 1) per site among the 2 N_IND copies, FIS = 1 - HO
 --roh-min-sites N sites (default 50) without a heterozygous site, F_ROH = the share of sites inside them; NA where undefined);
 --ind-table PATH adds one row per window and sample: CHROM START END SAMPLE HET HOM_ALT LONGEST_RUN ROH_RUNS ROH_SITES.  --compact
 allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
+
+--format ibs (impop_ibs_scan): pairwise identity-by-state tracts over the whole matrix of each BED row's contig, every pair of the
+sequences of -u (default: all; --ibs-pairs all) or the two haplotypes of every sample (--ibs-pairs diploid: the PanSN pairing of
+--format diploid, so the tracts are the runs of homozygosity as segments).  A tract is a maximal stretch of sites without a
+difference between the two rows; tracts of at least --ibs-min-sites N sites (default 50) are reported.  One table REGION LENGTH
+PAIRS TRACTS PAIRS_SPANNING PAIR_SITES SHARE, one row per BED row (TRACTS = reported tracts that meet the row's sites,
+PAIRS_SPANNING = those that contain all of them, PAIR_SITES = sites of the row inside reported tracts summed over the pairs, SHARE =
+PAIR_SITES / (PAIRS x the row's sites), "%.8f", NA for a row without sites); all BED rows of one matrix go into one call.
+--ibs-segments PATH writes the segment list as TSV `seq1 seq2 start end sites open` (start / end in bp, end exclusive; open = L, R,
+LR or . : the tract is cut by the matrix's first / last site, not by a difference), --ibs-pair-table PATH one row per pair: SEQ1
+SEQ2 N_DIFF LONGEST TRACTS TRACT_SITES.  --compact allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l,
+--devices N, -t / -r.
 
 --format dstat (impop_dstat_scan): introgression statistics per BED row and quartet (P1, P2, P3, O) of the --panel lists (4..8 of
 them).  --quartet i,j,k,o names a quartet by 1-based positions in --panel and may be repeated; with exactly four lists the default is
@@ -473,6 +486,60 @@ def diploid_refusal(args):
     if args.roh_min_sites is not None and args.roh_min_sites < 1:
         return "--roh-min-sites takes 1 or more"
     return None
+
+
+IBS_HEADER = "REGION\tLENGTH\tPAIRS\tTRACTS\tPAIRS_SPANNING\tPAIR_SITES\tSHARE"
+IBS_SEGMENT_HEADER = "seq1\tseq2\tstart\tend\tsites\topen"
+IBS_PAIR_HEADER = "SEQ1\tSEQ2\tN_DIFF\tLONGEST\tTRACTS\tTRACT_SITES"
+
+
+def ibs_refusal(args):
+    """what --format ibs does not combine with (one line each, exit 2, before any device is opened)"""
+    if args.format != "ibs":
+        if args.ibs_min_sites is not None or args.ibs_pairs is not None or args.ibs_segments is not None or args.ibs_pair_table is not None:
+            return "--ibs-min-sites / --ibs-pairs / --ibs-segments / --ibs-pair-table belong to --format ibs"
+        return None
+    if args.sim_list:
+        return "--format ibs scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format ibs is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format ibs runs on one GPU: not with --devices N"
+    if args.panel or args.pop_a or args.pop_b or args.sample_list:
+        return "--format ibs pairs the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+    if args.ibs_min_sites is not None and args.ibs_min_sites < 1:
+        return "--ibs-min-sites takes 1 or more"
+    return None
+
+
+def write_ibs_table(out, regions, L_col, n_pairs, recs):
+    """the table of --format ibs from impop_ibs_window records (one per region); n_pairs: the pairs of each region's matrix"""
+    print(IBS_HEADER, file=out)
+    for reg, L, npair, r in zip(regions, L_col, n_pairs, recs):
+        print(f"{reg}\t{L}\t{int(npair)}\t{int(r['tracts'])}\t{int(r['pairs_spanning'])}\t{int(r['pair_sites'])}\t{_na(r['share'])}", file=out)
+
+
+def write_ibs_segments(out, names, segs, site_bp, header=True):
+    """--ibs-segments: impop_ibs_segment records as TSV; site_bp(site) = the position of a site in bp"""
+    if header:
+        print(IBS_SEGMENT_HEADER, file=out)
+    for q in segs:
+        b, e, fl = int(q["begin"]), int(q["end"]), int(q["flags"])
+        print(f"{names[int(q['h1'])]}\t{names[int(q['h2'])]}\t{site_bp(b)}\t{site_bp(e - 1) + 1}\t{e - b}\t"
+              f"{('L' if fl & 1 else '') + ('R' if fl & 2 else '') or '.'}", file=out)
+
+
+def write_ibs_pairs(out, names, recs, header=True):
+    """--ibs-pair-table: impop_ibs_pair records, one row per pair"""
+    if header:
+        print(IBS_PAIR_HEADER, file=out)
+    for q in recs:
+        print(f"{names[int(q['h1'])]}\t{names[int(q['h2'])]}\t{int(q['n_diff'])}\t{int(q['longest'])}\t{int(q['n_tracts'])}\t"
+              f"{int(q['tract_sites'])}", file=out)
 
 
 DSTAT_HEADER = "CHROM\tSTART\tEND\tP1\tP2\tP3\tO\tN_SITES\tN_INFORMATIVE\tN_SKIPPED\tABBA\tBABA\tD\tF4\tF_D"
@@ -907,12 +974,13 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "dstat", "sfs", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
                          "ld = linkage disequilibrium per window (ZnS, mean |D'|, Kim-Nielsen omega; not part of `all`); "
                          "diploid = heterozygosity, F_IS and runs of homozygosity per window and individual (not part of `all`); "
+                         "ibs = pairwise identity-by-state tracts / ROH segments over each row's whole matrix (not part of `all`); "
                          "dstat = Patterson's D (ABBA-BABA), f4 and f_d per window and quartet of --panel populations (not part of `all`); "
                          "sfs = spectrum summaries and neutrality tests per window and --panel population, pair classes and spectra "
                          "(not part of `all`)")
@@ -931,6 +999,12 @@ def main():
     ap.add_argument("--roh-min-sites", type=int, default=None, metavar="N", help="diploid: a stretch without a heterozygous site counts as a "
                     "run of homozygosity when it is at least N sites long (default 50)")
     ap.add_argument("--ind-table", metavar="PATH", help="diploid: also write one row per window and sample to PATH")
+    ap.add_argument("--ibs-min-sites", type=int, default=None, metavar="N", help="ibs: a stretch without a difference between two "
+                    "sequences is reported when it is at least N sites long (default 50)")
+    ap.add_argument("--ibs-pairs", choices=["all", "diploid"], default=None, help="ibs: all = every pair of the sequences of -u (default); "
+                    "diploid = the two haplotypes of every sample, paired as --format diploid pairs them")
+    ap.add_argument("--ibs-segments", metavar="PATH", help="ibs: write the segment list to PATH (TSV seq1 seq2 start end sites open)")
+    ap.add_argument("--ibs-pair-table", metavar="PATH", help="ibs: write one row per pair to PATH (SEQ1 SEQ2 N_DIFF LONGEST TRACTS TRACT_SITES)")
     ap.add_argument("--quartet", action="append", default=None, metavar="i,j,k,o", help="dstat: the populations P1,P2,P3,O of a quartet as "
                     "1-based positions in --panel; repeatable (default with exactly four lists: 1,2,3,4)")
     ap.add_argument("--dstat-polarize", action="store_true", help="dstat: per site and quartet the outgroup's major allele is ancestral "
@@ -981,7 +1055,7 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or dstat_refusal(args)
+    refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or ibs_refusal(args) or dstat_refusal(args)
                or sfs_refusal(args))
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
@@ -1130,6 +1204,14 @@ def main():
     ld_pos = [None] * n_rows
     dip_recs = np.zeros(n_rows, dtype=impop_amd.DIPLOID_DTYPE)
     dip_ind = [None] * n_rows  # per row: (sample names, impop_diploid_ind rows)
+    ibs_recs = np.zeros(n_rows, dtype=impop_amd.IBS_WINDOW_DTYPE)
+    ibs_n_pairs = np.zeros(n_rows, dtype=np.int64)
+    ibs_seg_fh = open(args.ibs_segments, "w") if fmt == "ibs" and args.ibs_segments and rank == 0 else None
+    ibs_pair_fh = open(args.ibs_pair_table, "w") if fmt == "ibs" and args.ibs_pair_table and rank == 0 else None
+    if ibs_seg_fh:
+        print(IBS_SEGMENT_HEADER, file=ibs_seg_fh)
+    if ibs_pair_fh:
+        print(IBS_PAIR_HEADER, file=ibs_pair_fh)
     dstat_recs = np.zeros((n_rows, len(dstat_quartets or [])), dtype=impop_amd.DSTAT_DTYPE)
     dstat_sizes = [None] * n_rows  # per row: the populations' sizes in its matrix
     sfs_recs = np.zeros((n_rows, len(args.panel) if fmt == "sfs" else 0), dtype=impop_amd.SFS_DTYPE)
@@ -1347,6 +1429,38 @@ def main():
             dip_recs[idx] = recs
             run.close()
             continue
+        if fmt == "ibs":
+            ibs_kw = dict(min_sites=50 if args.ibs_min_sites is None else args.ibs_min_sites, windows=[(b, en) for b, en, _ in wins],
+                          want_segments=ibs_seg_fh is not None)
+            if (args.ibs_pairs or "all") == "diploid":
+                from impop_amd.popnames import pair_haplotypes
+                chosen = None if mask_p is None else [nm for nm, f in zip(names, mask_p) if f]
+                ibs_pairs, _, unpaired = pair_haplotypes(list(names), chosen)
+                if unpaired:
+                    print(f"Warning: --format ibs: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
+                          + " ".join(unpaired), file=sys.stderr)
+                if len(ibs_pairs) < 1:
+                    print("Error: --format ibs: no sample with both of its haplotypes (sample#1#..., sample#2#...) among the sequences",
+                          file=sys.stderr)
+                    run.close()
+                    sys.exit(2)
+                ibs_kw["pairs"] = ibs_pairs
+            else:
+                if n_matched < 2:
+                    print(f"Error: --format ibs: {n_matched} sequences make no pair", file=sys.stderr)
+                    run.close()
+                    sys.exit(2)
+                ibs_kw["mask_p"] = mask_p
+            prec, segs, wrec, _ = run.bm.ibs_scan(**ibs_kw)
+            ibs_recs[idx] = wrec
+            ibs_n_pairs[idx] = len(prec)
+            site_bp = (lambda c, mf=mf: int(mf.site_pos[c])) if mf.site_pos is not None else (lambda c, mf=mf: int(mf.origin + c))
+            if ibs_seg_fh:
+                write_ibs_segments(ibs_seg_fh, names, segs, site_bp, header=False)
+            if ibs_pair_fh:
+                write_ibs_pairs(ibs_pair_fh, names, prec, header=False)
+            run.close()
+            continue
         if fmt == "ehh":
             recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=mask_p, ref_hap=ref_hap, flanks=args.ehh_flanks or "reference")
             for i, c, r in zip(idx, cores, recs):
@@ -1424,6 +1538,11 @@ def main():
                 print(DIPLOID_IND_HEADER, file=fh)
                 for (reg, _, _, _), entry in zip(rows, dip_ind):
                     write_diploid_ind_table(fh, [reg], entry[0], [entry[1]], header=False)
+    elif fmt == "ibs":
+        write_ibs_table(out, [r[0] for r in rows], L_col, ibs_n_pairs, ibs_recs)
+        for fh in (ibs_seg_fh, ibs_pair_fh):
+            if fh:
+                fh.close()
     elif fmt == "dstat":
         write_dstat_table(out, [r[0] for r in rows], panel_labels or [], dstat_quartets, dstat_sizes, dstat_recs)
         if args.dstat_summary:
