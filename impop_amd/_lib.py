@@ -92,6 +92,23 @@ class ClusterStats(C.Structure):
                 ("sum_sq", C.c_uint64), ("n_sites", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PairdistParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("hist_bins", C.c_uint32), ("hist_width", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DistPanel(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("n_pairs", C.c_uint64), ("sum_h", C.c_uint64), ("sum_h2", C.c_uint64),
+                ("n_zero", C.c_uint64), ("min_h", C.c_uint32), ("max_h", C.c_uint32), ("min_i", C.c_uint32), ("min_j", C.c_uint32),
+                ("max_i", C.c_uint32), ("max_j", C.c_uint32)]
+
+
+class DistPair(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint64), ("sum_h", C.c_uint64), ("sum_h2", C.c_uint64), ("n_zero", C.c_uint64), ("min_h", C.c_uint32),
+                ("max_h", C.c_uint32), ("min_i", C.c_uint32), ("min_j", C.c_uint32), ("max_i", C.c_uint32), ("max_j", C.c_uint32),
+                ("nn_same_a", C.c_uint32), ("nn_same_b", C.c_uint32), ("nn_other_a", C.c_uint32), ("nn_other_b", C.c_uint32),
+                ("snn", C.c_double), ("gmin", C.c_double), ("reserved", C.c_uint64)]
+
+
 class EhhWindow(C.Structure):
     _fields_ = [("site_begin", C.c_uint64), ("site_end", C.c_uint64), ("core_site", C.c_uint64)]
 
@@ -215,6 +232,8 @@ assert C.sizeof(IdentityStats) == 144 and C.sizeof(IdentityProblem) == 64 and C.
 assert C.sizeof(WindowStats) == 128 and C.sizeof(Window) == 24 and C.sizeof(PairwiseStats) == 96
 assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
 assert C.sizeof(PanelStats) == 48 and C.sizeof(PanelWindow) == 8
+assert C.sizeof(DistPanel) == 64 and C.sizeof(DistPair) == 96 and C.sizeof(PairdistParams) == 16
+PAIRDIST_MAX_N, PAIRDIST_MAX_BINS = 4096, 1024  # IMPOP_PAIRDIST_MAX_N, IMPOP_PAIRDIST_MAX_BINS
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
 assert C.sizeof(HaplotypeStats) == 64 and C.sizeof(HaplotypeParams) == 16
 assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
@@ -251,6 +270,7 @@ SIGNATURES = {
     "impop_ctx_gram_timing": (C.c_int, [_vp, C.c_int]),
     "impop_ctx_gram_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_cluster_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "impop_ctx_pairdist_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_ehh_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_debug_timer_pool_sizes": (C.c_int, [_vp, _vp, _u64p]),
     "impop_matrix_synthetic_slab": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams), C.c_uint32, C.POINTER(_vp)]),
@@ -294,6 +314,8 @@ SIGNATURES = {
                                       C.POINTER(PairwiseParams), C.POINTER(PairwiseStats)]),
     "impop_pairwise_scan_panel": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairwiseParams),
                                             C.POINTER(PanelStats), C.POINTER(PairStats), C.POINTER(PanelWindow)]),
+    "impop_pairdist_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairdistParams),
+                                      C.POINTER(DistPanel), C.POINTER(DistPair), _u32p, _u32p]),
     "impop_cluster_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(ClusterParams),
                                      C.POINTER(ClusterStats), _u32p, _u32p]),
     "impop_pi_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, C.c_double, C.c_int, C.c_uint64, _u32p, _f64p, _f64p, _u32p, _u32p,

@@ -288,6 +288,11 @@ IMPOP_API int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64
     return ctx_timers_elapsed(ctx, impop_ctx::T_CLUSTER, 1, 0, total_ms, launches);
 }
 
+IMPOP_API int impop_ctx_pairdist_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
+    REQUIRE(ctx, "impop_ctx_pairdist_elapsed: ctx is NULL");
+    return ctx_timers_elapsed(ctx, impop_ctx::T_PAIRDIST, 1, 0, total_ms, launches);
+}
+
 IMPOP_API int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_ehh_elapsed: ctx is NULL");
     return ctx_timers_elapsed(ctx, impop_ctx::T_EHH, 1, 0, total_ms, launches);

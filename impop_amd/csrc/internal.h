@@ -168,7 +168,8 @@ struct impop_ctx {
         T_DSTAT = T_DIP + 2, // impop_dstat_scan: the streaming launches (impop_ctx_dstat_elapsed)
         T_SFS,               // impop_sfs_scan: summary / table launches (impop_ctx_sfs_elapsed)
         T_IBS = T_SFS + 2,   // impop_ibs_scan: transpose / walk / combine + close kernels (impop_ctx_ibs_elapsed)
-        T_COUNT = T_IBS + 3
+        T_PAIRDIST = T_IBS + 3,  // impop_pairdist_scan: the distribution kernel of every chunk (impop_ctx_pairdist_elapsed)
+        T_COUNT
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the

@@ -1,4 +1,5 @@
-// pairwise_scan.hip — the windowed all-pairs calls (impop_pairwise_scan, impop_pairwise_scan_panel, impop_cluster_scan): one shared
+// pairwise_scan.hip — the windowed all-pairs calls (impop_pairwise_scan, impop_pairwise_scan_panel, impop_cluster_scan,
+// impop_pairdist_scan): one shared
 // front end — windows -> Gram cells -> chunks (pair_plan.h), per chunk the Gram launch (pairwise.hip) and the filled SimBatch — and
 // what each call does with the identities: its PairEpilogue.
 #include <stdlib.h>
@@ -492,6 +493,67 @@ struct PanelEpilogue final : PairEpilogue {
     }
 };
 
+// impop_pairdist_scan's epilogue: one launch of the distribution kernel (pairdist.hip) per chunk — records, histograms and the
+// per-member nearest-neighbour tables it keeps in scratch
+struct PairdistEpilogue final : PairEpilogue {
+    uint32_t K, NP, M, B, width;            // B = 0: no histograms
+    bool hist_lds = false;
+    PairdistTables T{};
+    const std::vector<uint32_t> *hap_of, *merged, *moff;
+    impop_dist_panel *out_panels;
+    impop_dist_pair *out_pairs;             // nullable
+    uint32_t *hist_within, *hist_between;   // nullable
+    uint64_t chunks = 0, launches = 0;
+    uint32_t *d_hap = nullptr, *d_merged = nullptr, *d_moff = nullptr, *d_hw = nullptr, *d_hb = nullptr, *h_hw = nullptr, *h_hb = nullptr;
+    DistNN *d_nn = nullptr;
+    impop_dist_panel *d_pan = nullptr, *h_pan = nullptr;
+    impop_dist_pair *d_pair = nullptr, *h_pair = nullptr;
+    // the device bytes layout() takes per window of a chunk, histograms included (they bound a chunk: impop_pairdist_scan)
+    size_t per_window_bytes() const {
+        return (size_t)M * K * sizeof(DistNN) + K * sizeof(impop_dist_panel) + NP * sizeof(impop_dist_pair) + (size_t)(K + NP) * B * 4;
+    }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        D.sub(d_hap, M); D.sub(d_merged, merged->size() ? merged->size() : 1); D.sub(d_moff, NP + 1);
+        D.sub(d_nn, cap * M * K); D.sub(d_pan, cap * K); D.sub(d_pair, cap * NP);
+        D.sub(d_hw, cap * K * B); D.sub(d_hb, cap * NP * B);  // one region: zeroed by one memset where the kernel tallies into it
+        H.sub(h_pan, cap * K); H.sub(h_pair, out_pairs ? cap * NP : 0);
+        H.sub(h_hw, hist_within ? cap * K * B : 0); H.sub(h_hb, hist_between ? cap * NP * B : 0);
+    }
+    int upload(impop_ctx *ctx) override {
+        HIP_TRY(hipMemcpyAsync(d_hap, hap_of->data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!merged->empty()) HIP_TRY(hipMemcpyAsync(d_merged, merged->data(), merged->size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_moff, moff->data(), (size_t)(NP + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        T.hap_of = d_hap; T.merged = d_merged; T.moff = d_moff;
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const uint64_t cnt = c.cnt;
+        size_t slot = 0;  // the distribution kernel between two events of its own: impop_ctx_pairdist_elapsed
+        int rc = ctx->gram_timing ? ctx->timers[impop_ctx::T_PAIRDIST].begin(ctx->stream, &slot) : IMPOP_OK;
+        if (rc) return rc;
+        if (B && !hist_lds)
+            HIP_TRY(hipMemsetAsync(d_hw, 0, (size_t)((char *)(d_hb + cnt * NP * B) - (char *)d_hw), ctx->stream));
+        PairdistOut O{d_nn, d_pan, d_pair, d_hw, d_hb, B, width};
+        rc = launch_pairdist(ctx, c.b, cnt, c.d_s, T, O, hist_lds);
+        if (rc) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PAIRDIST].end(ctx->stream, slot))) return rc;
+        ++chunks; ++launches;
+        HIP_TRY(hipMemcpyAsync(h_pan, d_pan, cnt * K * sizeof(impop_dist_panel), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_pairs && NP) HIP_TRY(hipMemcpyAsync(h_pair, d_pair, cnt * NP * sizeof(impop_dist_pair), hipMemcpyDeviceToHost, ctx->stream));
+        if (hist_within && B) HIP_TRY(hipMemcpyAsync(h_hw, d_hw, cnt * K * B * 4, hipMemcpyDeviceToHost, ctx->stream));
+        if (hist_between && B && NP) HIP_TRY(hipMemcpyAsync(h_hb, d_hb, cnt * NP * B * 4, hipMemcpyDeviceToHost, ctx->stream));
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        for (uint64_t k = 0; k < c.cnt; ++k) {
+            memcpy(out_panels + c.ord[k] * K, h_pan + k * K, (size_t)K * sizeof(impop_dist_panel));
+            if (out_pairs && NP) memcpy(out_pairs + c.ord[k] * NP, h_pair + k * NP, (size_t)NP * sizeof(impop_dist_pair));
+            if (hist_within && B) memcpy(hist_within + c.ord[k] * K * B, h_hw + k * K * B, (size_t)K * B * 4);
+            if (hist_between && B && NP) memcpy(hist_between + c.ord[k] * NP * B, h_hb + k * NP * B, (size_t)NP * B * 4);
+        }
+    }
+};
+
 // ---- what the entry points share -------------------------------------------------------------------------------------------
 // the checks of impop_pairwise_params common to the calls that take one
 int check_pairwise_params(const impop_pairwise_params *params, const char *fn) {
@@ -513,6 +575,94 @@ std::vector<uint32_t> mask_members(const uint64_t *mask, uint32_t n) { return me
 
 }  // namespace
 static_assert(sizeof(impop_panel_stats) == 48 && sizeof(impop_panel_window) == 8 && sizeof(impop_pair_stats) == 48, "fixed record layouts");
+
+static_assert(sizeof(impop_dist_panel) == 64 && sizeof(impop_dist_pair) == 96 && sizeof(impop_pairdist_params) == 16, "fixed record layouts");
+static_assert(IMPOP_PAIRDIST_MAX_N == PAIRDIST_MAX_N, "positions are packed into 12 bits of a key");
+
+IMPOP_API int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                  const uint64_t *masks, uint32_t n_pop, const impop_pairdist_params *params,
+                                  impop_dist_panel *out_panels, impop_dist_pair *out_pairs, uint32_t *hist_within, uint32_t *hist_between) {
+    const char *fn = "impop_pairdist_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_pairdist_params), "impop_pairdist_params.struct_size mismatch");
+    REQUIRE(params->hist_bins <= IMPOP_PAIRDIST_MAX_BINS, "%s: hist_bins must be 0..%u", fn, (uint32_t)IMPOP_PAIRDIST_MAX_BINS);
+    REQUIRE(params->hist_width >= 1, "%s: hist_width must be at least 1", fn);
+    REQUIRE(n_pop >= 1 && n_pop <= 8, "%s: n_pop must be 1..8", fn);
+    REQUIRE(masks, "%s: masks is NULL", fn);
+    const uint32_t n = m->g.n_hap, K = n_pop, NP = K * (K - 1) / 2, mwords = (n + 63) / 64;
+    std::vector<uint8_t> cls(n, 0xFF);
+    std::vector<uint32_t> hap_of;  // the panels' members back to back, each ascending: position -> haplotype
+    PairdistEpilogue epi;
+    uint64_t p_max = 0;
+    for (uint32_t k = 0; k < K; ++k) {
+        epi.T.off[k] = (uint32_t)hap_of.size();
+        for (uint32_t i : mask_members(masks + (size_t)k * mwords, n)) {
+            REQUIRE(cls[i] == 0xFF, "%s: populations must be disjoint (population %u overlaps population %u)", fn, k, (uint32_t)cls[i]);
+            cls[i] = (uint8_t)k;
+            hap_of.push_back(i);
+        }
+        REQUIRE(hap_of.size() > epi.T.off[k], "%s: population %u is empty", fn, k);
+    }
+    for (uint32_t k = K; k < 9; ++k) epi.T.off[k] = (uint32_t)hap_of.size();
+    if (hap_of.size() > IMPOP_PAIRDIST_MAX_N) {  // refused before anything is uploaded or launched
+        set_error("%s: the panels hold %zu members, more than the limit of %u", fn, hap_of.size(), (uint32_t)IMPOP_PAIRDIST_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    const uint32_t M = (uint32_t)hap_of.size();
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_panels, "%s: NULL windows/out", fn);
+    int rc = check_windows(ctx, m, windows, n_windows, fn);
+    if (rc) return rc;
+    // per pair of panels: both panels' positions merged into ascending haplotype index (the order of the S_nn sum)
+    std::vector<uint32_t> merged, moff(1, 0u);
+    for (uint32_t a = 0; a < K; ++a) {
+        const uint64_t ma = epi.T.off[a + 1] - epi.T.off[a];
+        p_max = std::max(p_max, ma * (ma - 1) / 2);
+        for (uint32_t b = a + 1; b < K; ++b) {
+            p_max = std::max(p_max, ma * (epi.T.off[b + 1] - epi.T.off[b]));
+            uint32_t i = epi.T.off[a], j = epi.T.off[b];
+            while (i < epi.T.off[a + 1] || j < epi.T.off[b + 1])
+                merged.push_back(j >= epi.T.off[b + 1] || (i < epi.T.off[a + 1] && hap_of[i] < hap_of[j]) ? i++ : j++);
+            moff.push_back((uint32_t)merged.size());
+        }
+    }
+    const uint64_t max_W = widest_W(m, windows, n_windows);
+    if (!pd_sum_h2_admitted(max_W, p_max)) {  // before any launch
+        set_error("%s: sum_h2 may overflow 64 bits: the widest window has W = %llu and the largest record %llu pairs (W^2 x pairs must stay "
+                  "below 2^64)", fn, (unsigned long long)max_W, (unsigned long long)p_max);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    epi.K = K; epi.NP = NP; epi.M = M; epi.T.K = K; epi.T.M = M;
+    epi.B = (hist_within || (hist_between && NP)) ? params->hist_bins : 0u;
+    epi.width = params->hist_width;
+    epi.hap_of = &hap_of; epi.merged = &merged; epi.moff = &moff;
+    epi.out_panels = out_panels; epi.out_pairs = out_pairs; epi.hist_within = hist_within; epi.hist_between = hist_between;
+    // histograms in LDS where every counter fits next to the kernel's tables; IMPOP_PAIRDIST_LDS_BINS=n lowers what the LDS form
+    // takes, so that tests reach the global form at small sizes
+    if (epi.B) {
+        const size_t fixed = pairdist_lds_fixed(K, M);
+        size_t cap = fixed < PAIRDIST_LDS_BYTES ? (PAIRDIST_LDS_BYTES - fixed) / 4 : 0;
+        const char *e = getenv("IMPOP_PAIRDIST_LDS_BINS");
+        if (e && *e) {
+            const long v = strtol(e, nullptr, 10);
+            cap = std::min<size_t>(cap, v < 0 ? 0 : (size_t)v);
+        }
+        epi.hist_lds = (size_t)(K + NP) * epi.B <= cap;
+    }
+    PairFront in{};
+    in.fn = fn; in.identity_kind = IMPOP_IDENTITY_MATCH; in.round_digits = -1;
+    in.scan_host = nullptr; in.use_segmap = false; in.max_W = max_W;
+    // the per-member tables and the histograms of a chunk: at most 512 MiB of them
+    in.max_chunk_windows = std::min<uint64_t>(65535, std::max<uint64_t>(1, (512ull << 20) / epi.per_window_bytes()));
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (trace_on())
+        fprintf(stderr, "[impop_pairdist_scan] pops=%u pairs=%u members=%u windows=%llu chunks=%llu launches=%llu hist_bins=%u hist=%s\n", K, NP,
+                M, (unsigned long long)n_windows, (unsigned long long)epi.chunks, (unsigned long long)epi.launches, epi.B,
+                !epi.B ? "off" : epi.hist_lds ? "lds" : "global");
+    return IMPOP_OK;
+}
 
 IMPOP_API int impop_pairwise_scan_panel(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                                         const uint64_t *masks, uint32_t n_pop, const impop_pairwise_params *params,

@@ -5,6 +5,7 @@
 #pragma once
 #include "device_utils.h"
 #include "internal.h"
+#include "pairdist_math.h"
 
 namespace impop {
 
@@ -244,5 +245,26 @@ int launch_af_small(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, cons
 int launch_af_batch(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const uint32_t *d_idx, uint32_t m, double threshold,
                     uint32_t *d_adj, size_t adj_bytes_per_problem, impop_cluster_stats *d_rec, uint32_t *d_cluster_of, uint32_t *d_sizes,
                     bool want_members);
+
+// impop_pairdist_scan's distribution kernel (pairdist.hip): one workgroup per Gram problem.  The K panels' members are POSITIONS
+// 0 .. M - 1, panel k at off[k] .. off[k + 1), each panel ascending (pairdist_math.h).
+struct PairdistTables {
+    const uint32_t *hap_of;  // M: haplotype index of a position
+    const uint32_t *merged;  // per pair of panels p: the positions of both panels in ascending haplotype index, at moff[p]
+    const uint32_t *moff;    // K (K - 1) / 2 + 1
+    uint32_t off[9];
+    uint32_t K, M;
+};
+struct PairdistOut {
+    DistNN *nn;                              // scratch: n_problems x M x K
+    impop_dist_panel *panels;                // n_problems x K
+    impop_dist_pair *pairs;                  // n_problems x K (K - 1) / 2
+    uint32_t *hist_within, *hist_between;    // bins > 0: n_problems x K x bins | x K (K - 1) / 2 x bins; zeroed unless hist_lds
+    uint32_t bins, width;
+};
+constexpr size_t PAIRDIST_LDS_BYTES = 65536;     // what a workgroup takes at most: the fixed tables, and the histograms where they fit
+size_t pairdist_lds_fixed(uint32_t K, uint32_t M);  // bytes of the accumulators, the diagonal and the haplotype indexes
+int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PairdistTables &T,
+                    const PairdistOut &O, bool hist_lds);
 
 }  // namespace impop

@@ -72,6 +72,13 @@ PANEL_DTYPE = np.dtype([("pi", "<f8"), ("pi_site", "<f8"), ("tajima_d", "<f8"), 
 PANEL_WINDOW_DTYPE = np.dtype([("n_sites", "<u4"), ("s_all", "<u4")])
 assert PANEL_DTYPE.itemsize == 48 and PANEL_WINDOW_DTYPE.itemsize == 8
 
+DIST_PANEL_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_pairs", "<u8"), ("sum_h", "<u8"), ("sum_h2", "<u8"), ("n_zero", "<u8"),
+                             ("min_h", "<u4"), ("max_h", "<u4"), ("min_i", "<u4"), ("min_j", "<u4"), ("max_i", "<u4"), ("max_j", "<u4")])
+DIST_PAIR_DTYPE = np.dtype([("n_pairs", "<u8"), ("sum_h", "<u8"), ("sum_h2", "<u8"), ("n_zero", "<u8"), ("min_h", "<u4"), ("max_h", "<u4"),
+                            ("min_i", "<u4"), ("min_j", "<u4"), ("max_i", "<u4"), ("max_j", "<u4"), ("nn_same_a", "<u4"), ("nn_same_b", "<u4"),
+                            ("nn_other_a", "<u4"), ("nn_other_b", "<u4"), ("snn", "<f8"), ("gmin", "<f8"), ("reserved", "<u8")])
+assert DIST_PANEL_DTYPE.itemsize == 64 and DIST_PAIR_DTYPE.itemsize == 96
+
 IDENTITY_STATS_DTYPE = np.dtype([
     ("status", "<i4"), ("n_groups", "<u4"), ("pi", "<f8"), ("pi_site", "<f8"), ("sum_2pairs", "<f8"), ("n_pairs_with_data", "<u8"),
     ("fst", "<f8", (6,)), ("fst_counts", "<u8", (6,)), ("tajima_d", "<f8")])
@@ -204,6 +211,12 @@ class Context:
         """-> (summed clustering-kernel ms of cluster_scan — and Fst-kernel ms of pairwise_scan_panel —, chunks) since gram_timing(True)"""
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_cluster_elapsed(self.handle, C.byref(t), C.byref(k)))
+        return t.value, k.value
+
+    def pairdist_elapsed(self):
+        """-> (summed ms of pairdist_scan's distribution kernel, chunks) since gram_timing(True)"""
+        t, k = C.c_double(), C.c_uint64()
+        check(self._lib.impop_ctx_pairdist_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
 
     def ehh_elapsed(self):
@@ -661,6 +674,30 @@ class BitMatrix:
                                                       pairs.ctypes.data_as(C.POINTER(_lib.PairStats)) if want_pairs else None,
                                                       wins.ctypes.data_as(C.POINTER(_lib.PanelWindow))))
         return panels, pairs, wins
+
+    def pairdist_scan(self, windows, pops, hist_bins: int = 0, hist_width: int = 1):
+        """Pairwise-distance distributions of K (1..8) disjoint panels and all their pairs from ONE Gram pass per window
+        (impop_pairdist_scan): sums, extremes with the pairs that attain them, nearest-neighbour counts and S_nn, G_min.
+        -> (panels [n_windows, K] DIST_PANEL_DTYPE, pairs [n_windows, K(K-1)/2] DIST_PAIR_DTYPE in the pair order of scan_multi,
+            hist_within [n_windows, K, hist_bins] uint32, hist_between [n_windows, K(K-1)/2, hist_bins] uint32; both None when
+            hist_bins is 0).  A pair counts in bin min(H // hist_width, hist_bins - 1)."""
+        w = make_windows(windows)
+        K = len(pops)
+        NP = K * (K - 1) // 2
+        packed = np.concatenate([_mask_ptr(p, self.n_hap)[0] for p in pops]).astype(np.uint64) if K else np.zeros(1, np.uint64)
+        panels = np.zeros((len(w), K), dtype=DIST_PANEL_DTYPE)
+        pairs = np.zeros((len(w), NP), dtype=DIST_PAIR_DTYPE)
+        B = int(hist_bins)
+        hw = np.zeros((len(w), K, B), dtype=np.uint32) if B else None
+        hb = np.zeros((len(w), NP, B), dtype=np.uint32) if B else None
+        prm = _lib.PairdistParams(C.sizeof(_lib.PairdistParams), B, int(hist_width), 0)
+        u32p = C.POINTER(C.c_uint32)
+        check(self.ctx._lib.impop_pairdist_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
+                                                packed.ctypes.data_as(C.POINTER(C.c_uint64)), K, C.byref(prm),
+                                                panels.ctypes.data_as(C.POINTER(_lib.DistPanel)),
+                                                pairs.ctypes.data_as(C.POINTER(_lib.DistPair)) if NP else None,
+                                                hw.ctypes.data_as(u32p) if B else None, hb.ctypes.data_as(u32p) if B and NP else None))
+        return panels, pairs, hw, hb
 
     def cluster_scan(self, windows, mask_p=None, kind: str = "match", threshold: float = 1.0, round_digits: Optional[int] = None,
                      want_members: bool = True):

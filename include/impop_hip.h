@@ -484,6 +484,73 @@ typedef struct impop_cluster_stats { /* 32 bytes, fixed layout */
 int impop_cluster_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                        const uint64_t *mask_p, const impop_cluster_params *params, impop_cluster_stats *out_host,
                        uint32_t *cluster_of, uint32_t *sizes);
+#define IMPOP_PAIRDIST_MAX_N 4096u    /* members of the panels' union */
+#define IMPOP_PAIRDIST_MAX_BINS 1024u
+/* Pairwise-distance DISTRIBUTIONS per window, from the Gram pass of impop_pairwise_scan_panel: the mismatch distribution inside
+ * each panel, the extremes between panels (d_min, G_min of Geneva et al. 2015, RND_min) with the haplotype pair that attains
+ * them, and Hudson's nearest-neighbour statistic S_nn with its directional counts.  Exact integers throughout.
+ * The distance of haplotypes i and j in a window is H_ij = sum_s w_s [b_is != b_js] = a_i + a_j - 2 I_ij, the weighted Hamming
+ * distance (w_s = 1 on unweighted matrices); the per-window constant of a compacted matrix cancels.  No identity kind, no
+ * threshold, no rounding.
+ * masks: as impop_scan_multi — n_pop (1..8) bitsets of ceil(n_hap/64) uint64 words each, pairwise disjoint, none empty (anything
+ * else: IMPOP_E_INVALID); haplotypes in no panel contribute nothing.  The union may hold at most IMPOP_PAIRDIST_MAX_N members: a
+ * larger one returns IMPOP_E_UNSUPPORTED before anything is uploaded or launched.
+ * out_panels: n_windows x n_pop, over the pairs i < j of the panel.  out_pairs (nullable; NULL when n_pop == 1): n_windows x
+ * K(K-1)/2 in the pair order of impop_scan_multi, over i in panel k, j in panel l (k < l).  min_i .. max_j are haplotype indexes
+ * of the matrix; among pairs that tie, the pair with the smallest i wins, then the smallest j (i from panel k in a pair record).
+ * With n_pairs = 0: min_h = max_h = 0 and the four indexes are 0xFFFFFFFF.
+ * Nearest neighbours of a pair record, for every member i of k u l:  d_i = min over j in (k u l) \ {i} of H_ij,  tied_i =
+ * #{j : H_ij = d_i},  same_i = the number of those j in i's own panel.  nn_same_a / nn_same_b count the members of k / of l with
+ * same_i = tied_i, nn_other_a / nn_other_b those with same_i = 0, and
+ *     snn  = (sum_i (double)same_i / (double)tied_i) / (double)(m_k + m_l)
+ * the sum running sequentially, from 0.0, over i in ascending haplotype index (plain left-to-right double additions);
+ *     gmin = (double)min_h / ((double)sum_h / (double)n_pairs),   NaN when sum_h = 0.
+ * Histograms (hist_bins B = 0: none, else 1..IMPOP_PAIRDIST_MAX_BINS; hist_width >= 1; both tables nullable): hist_within is
+ * uint32 n_windows x n_pop x B, hist_between n_windows x K(K-1)/2 x B; a pair counts in bin min(H_ij / hist_width, B - 1), so
+ * the last bin collects the overflow.
+ * sum_h2 is exact when W_max^2 * P_max <= 2^64 - 1 (W_max: the largest W of the call's windows, P_max: the largest n_pairs of
+ * any record); otherwise the call returns IMPOP_E_UNSUPPORTED before any launch and the message names both numbers.  Every other
+ * sum fits whatever the input (H <= W <= 2^31, at most 2^23 pairs).
+ * A window without sites has H = 0 for every pair; n_windows == 0 returns IMPOP_OK; windows may overlap.  Chunking
+ * (IMPOP_PAIRWISE_CHUNK), uint16 or int32 Gram counts, the Gram chain length, compaction and weights never change a byte, and two
+ * calls return identical bytes (integer atomics only; the one double sum has a fixed order).  Checks the device error word like
+ * impop_pairwise_scan.  With impop_ctx_gram_timing on, impop_ctx_pairdist_elapsed returns the summed time of the chunks'
+ * distribution kernel next to the Gram time.  Histograms are tallied in LDS where all (K + pairs) x B counters fit next to the
+ * kernel's tables, else straight into the tables in global memory; IMPOP_PAIRDIST_LDS_BINS=n (0..36864, a test aid) lowers the
+ * number of counters the LDS form takes.  Under IMPOP_TRACE=1 one line per call on stderr, next to the [impop_gram] lines:
+ *   [impop_pairdist_scan] pops= pairs= members= windows= chunks= launches= hist_bins= hist=<off|lds|global>
+ * Known answer: haplotypes 0000, 0001, 0111, 0001 over one 4-site window, panels {0,1} and {2,3}: H01 = 1, H02 = 3, H03 = 1,
+ * H12 = 2, H13 = 0, H23 = 2.  Panel records: (n_pairs 1, sum_h 1, sum_h2 1, n_zero 0, min = max = 1 at (0,1)) and (1, 2, 4, 0,
+ * min = max = 2 at (2,3)).  Pair record: n_pairs 4, sum_h 6, sum_h2 14, n_zero 1, min_h 0 at (1,3), max_h 3 at (0,2); (same,
+ * tied) per member = (1,2), (0,1), (1,2), (0,1), so nn_same_a = nn_same_b = 0, nn_other_a = nn_other_b = 1, snn = 0.25,
+ * gmin = 0.0. */
+typedef struct impop_pairdist_params {
+    uint32_t struct_size;
+    uint32_t hist_bins;      /* 0 = no histograms */
+    uint32_t hist_width;     /* >= 1, also when hist_bins is 0 */
+    uint32_t reserved;
+} impop_pairdist_params;
+typedef struct impop_dist_panel {       /* 64 bytes, fixed layout: one per (window, panel) */
+    uint32_t n_members;                 /* size of the panel */
+    uint32_t n_sites;                   /* the window's W */
+    uint64_t n_pairs;                   /* m (m - 1) / 2 */
+    uint64_t sum_h, sum_h2, n_zero;     /* sum of H, of H^2, #{H = 0} */
+    uint32_t min_h, max_h;
+    uint32_t min_i, min_j, max_i, max_j;
+} impop_dist_panel;
+typedef struct impop_dist_pair {        /* 96 bytes, fixed layout: one per (window, pair k < l) */
+    uint64_t n_pairs;                   /* m_k m_l */
+    uint64_t sum_h, sum_h2, n_zero;
+    uint32_t min_h, max_h;
+    uint32_t min_i, min_j, max_i, max_j;
+    uint32_t nn_same_a, nn_same_b, nn_other_a, nn_other_b;
+    double snn, gmin;
+    uint64_t reserved;                  /* 0 */
+} impop_dist_pair;
+int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                        const uint64_t *masks, uint32_t n_pop, const impop_pairdist_params *params,
+                        impop_dist_panel *out_panels, impop_dist_pair *out_pairs /* nullable */,
+                        uint32_t *hist_within /* nullable */, uint32_t *hist_between /* nullable */);
 #define IMPOP_HAPLOTYPE_MAX_N 4096u
 /* Haplotype-frequency statistics per window from the stream impop_scan reads (no hap-major operand, no Gram; works on matrices
  * uploaded without IMPOP_KEEP_HAP_MAJOR, on compacted and on weighted ones).  Two members of P are the same haplotype in a window
@@ -876,6 +943,8 @@ int impop_ctx_gram_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches)
 /* With the same switch on, impop_cluster_scan also brackets its clustering kernel(s): their summed time and number of
  * chunks since enable / reset, next to the Gram time above. */
 int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
+/* ... and impop_pairdist_scan its distribution kernel: summed time and number of chunks since enable / reset. */
+int impop_ctx_pairdist_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
 /* Test aid: how many event pairs the four timers hold (created on first timed use, kept for reuse): sizes[0..2] = the
  * context's Gram / clustering / EHH timers, sizes[3] = the plan's (plan nullable: 0).  Nothing is created while timing is off. */
 int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]);

@@ -16,6 +16,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
     impop_scan.py --matrix chr2.npz --bed windows.bed --format diploid [-u subset.txt] [--roh-min-sites N] [--ind-table PATH]   # Ho, He, F_IS, ROH
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ibs [-u subset.txt] [--ibs-min-sites N] [--ibs-pairs all|diploid] [--ibs-segments PATH] [--ibs-pair-table PATH]   # IBS tracts / ROH segments
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format pairdist --panel a.txt b.txt [more.txt] [--pairdist-outgroup K] [--pairdist-panels panels.tsv] [--pairdist-hist hist.tsv --pairdist-bins B --pairdist-bin-width w] [--compact]   # d_min, G_min, S_nn, mismatch distributions
     impop_scan.py --matrix chr2.npz --bed windows.bed --format sfs --panel A.txt [B.txt ...] [--sfs-outgroup i] [--sfs-pair i,j]...   # spectra, neutrality tests
     impop_scan.py --matrix chr2.npz --bed windows.bed --format dstat --panel P1.txt P2.txt P3.txt O.txt [more.txt] [--quartet 1,2,3,4]...   # ABBA-BABA D, f4, f_d
 
@@ -92,6 +93,16 @@ doubles "%.8f", nan where undefined).  --dstat-polarize takes the outgroup's maj
 the outgroup is split evenly).  --dstat-blocks N with --dstat-summary PATH writes per quartet the value over all rows with its
 block-jackknife error: P1 P2 P3 O D D_SE D_Z F_D F_D_SE BLOCKS ABBA BABA.  Streams the scan index; --compact allowed.  One process, one
 GPU; not with --sim-list, -A / -B / -l / -u, --devices N, -t / -r.
+
+--format pairdist (impop_pairdist_scan): the distribution of the pairwise distances H per BED row, from one Gram pass for all --panel
+lists (1..8, disjoint).  Main table, one row per BED row and pair of lists: REGION LENGTH POP_A POP_B PAIRS DXY (mean H / LENGTH) DMIN
+DMIN_SEQ_A DMIN_SEQ_B (the closest pair of sequences) DMAX IDENTICAL (pairs with H = 0) GMIN SNN NN_SAME_A NN_SAME_B NN_OTHER_A
+NN_OTHER_B; --pairdist-outgroup K (1-based list) adds RNDMIN = DMIN / ((mean H(A,O) + mean H(B,O)) / 2), NA for the pairs that hold O.
+--pairdist-panels PATH writes per row and list REGION POP HAPLOTYPES PAIRS MEAN VARIANCE MIN MAX IDENTICAL RAGGEDNESS (Harpending's, of
+the histogram when one was asked for, else NA).  --pairdist-hist PATH with --pairdist-bins B (1..1024) and --pairdist-bin-width w
+writes the histograms in long form, non-zero bins only: REGION KIND (within | between) POP (list, or listA:listB) BIN COUNT; the last
+bin collects the overflow.  Doubles are printed with repr, NA where undefined.  --compact allowed.  One process, one GPU; not with
+--sim-list, -A / -B / -l / -u, --devices N, -t / -r.
 
 --format sfs (impop_sfs_scan): what is read from the site-frequency spectrum, per BED row and population of the --panel lists (1..8
 of them).  One table CHROM START END POP N N_SITES S ETA1 ETA_N1 N_SKIPPED THETA_W THETA_PI THETA_H THETA_L TAJIMA_D FAYWU_H
@@ -667,6 +678,100 @@ def sfs_refusal(args):
     return None
 
 
+def pairdist_refusal(args):
+    """what --format pairdist does not combine with (one line each, exit 2, before any device is opened)"""
+    own = (args.pairdist_outgroup is not None or args.pairdist_panels is not None or args.pairdist_hist is not None
+           or args.pairdist_bins is not None or args.pairdist_bin_width is not None)
+    if args.format != "pairdist":
+        return "--pairdist-outgroup / --pairdist-panels / --pairdist-hist / --pairdist-bins / --pairdist-bin-width belong to --format pairdist" if own else None
+    if args.sim_list:
+        return "--format pairdist scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format pairdist is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format pairdist runs on one GPU: not with --devices N"
+    if not args.panel or not 1 <= len(args.panel) <= 8:
+        return "--format pairdist takes --panel a.txt b.txt [more.txt]: 1 to 8 population lists"
+    if args.pop_a or args.pop_b or args.sample_list or args.subset:
+        return "--format pairdist reads the distances of the populations of --panel: not with -A / -B / -l / -u"
+    if args.threshold is not None or args.round_digits is not None or args.fst_round_digits is not None:
+        return "--format pairdist counts differing sites: it has no -t / -r"
+    if args.pairdist_outgroup is not None and not (len(args.panel) >= 3 and 1 <= args.pairdist_outgroup <= len(args.panel)):
+        return f"--pairdist-outgroup {args.pairdist_outgroup}: a 1-based position among at least three lists of --panel"
+    if (args.pairdist_bins is not None or args.pairdist_bin_width is not None) and args.pairdist_hist is None:
+        return "--pairdist-bins / --pairdist-bin-width belong to --pairdist-hist PATH"
+    if args.pairdist_hist is not None and args.pairdist_bins is None:
+        return "--pairdist-hist PATH needs --pairdist-bins B"
+    if args.pairdist_bins is not None and not 1 <= args.pairdist_bins <= 1024:
+        return "--pairdist-bins takes 1 to 1024"
+    if args.pairdist_bin_width is not None and args.pairdist_bin_width < 1:
+        return "--pairdist-bin-width takes 1 or more"
+    return None
+
+
+def scan_pairdist(args):
+    """--format pairdist: the main table to --output / stdout, the side tables to their paths"""
+    from impop_amd import pairdist as pd
+    if args.device is None:
+        args.device = 0
+    mats = {}
+    for p in args.matrix:
+        mf = load_matrix(p)
+        key = (mf.contig if mf.contig.startswith(args.region_prefix) else args.region_prefix + mf.contig) if mf.contig else ""
+        if key in mats:
+            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
+            sys.exit(2)
+        mats[key] = mf
+    if "" in mats and len(mats) > 1:
+        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
+        sys.exit(2)
+    per_mat = {}
+    for chrom, s, e in read_bed(args.bed, "pairdist"):
+        full = chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
+        key = "" if "" in mats else full
+        if key not in mats:
+            print(f"Warning: Skipping region {full}:{s}-{e}: no matrix holds chromosome {chrom}", file=sys.stderr)
+            continue
+        per_mat.setdefault(key, []).append((f"{full}:{s}-{e}", s, e))
+    labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
+    bins = args.pairdist_bins or 0
+    width = args.pairdist_bin_width or 1
+    og = None if args.pairdist_outgroup is None else args.pairdist_outgroup - 1
+    out = open(args.output, "w") if args.output else sys.stdout
+    pan_fh = open(args.pairdist_panels, "w") if args.pairdist_panels else None
+    hist_fh = open(args.pairdist_hist, "w") if args.pairdist_hist else None
+    print("\t".join(pd.MAIN_COLUMNS + (["RNDMIN"] if og is not None else [])), file=out)
+    if pan_fh:
+        print("\t".join(pd.PANEL_COLUMNS), file=pan_fh)
+    if hist_fh:
+        print("\t".join(pd.HIST_COLUMNS), file=hist_fh)
+    for key, rows in per_mat.items():
+        mf = mats[key]
+        pops = [flags_for(f, mf.names) for f in args.panel]
+        for k, f in enumerate(pops):  # what impop_pairdist_scan would refuse, with the lists' names
+            if not f.any():
+                print(f"Error: --format pairdist: {labels[k]} selects no sequence of the matrix", file=sys.stderr)
+                sys.exit(2)
+            for l in range(k):
+                if (pops[l] & f).any():
+                    print(f"Error: --format pairdist: {labels[l]} and {labels[k]} share a sequence; the lists must be disjoint", file=sys.stderr)
+                    sys.exit(2)
+        wins = [mf.site_range(s, e) + (e - s,) for _, s, e in rows]
+        run = Runner(args, mf, wins, True, 0, 1, 0)
+        try:
+            panels, pairs, hw, hb = run.bm.pairdist_scan(run.local_wins, pops, hist_bins=bins, hist_width=width)
+        finally:
+            run.close()
+        main, pan, hist = pd.tables([r[0] for r in rows], [e - s for _, s, e in rows], labels, list(mf.names), panels, pairs, hw, hb, outgroup=og)
+        for fh, table in ((out, main), (pan_fh, pan), (hist_fh, hist)):
+            if fh:
+                for row in table:
+                    print("\t".join(row), file=fh)
+    for fh in (pan_fh, hist_fh, out if args.output else None):
+        if fh:
+            fh.close()
+
+
 def sfs_row(region, label, n, r):
     """one row of the --format sfs table: region, the population's list name and size, the record"""
     chrom, start, end = split_region(region)
@@ -974,7 +1079,7 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "pairdist", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
@@ -1023,6 +1128,14 @@ def main():
     ap.add_argument("--sfs-blocks", type=int, default=None, metavar="N", help="sfs: with --sfs-spectra, the number of consecutive groups "
                     "of BED rows the spectra are summed over (default 1)")
     ap.add_argument("-A", "--pop-a"); ap.add_argument("-B", "--pop-b")
+    ap.add_argument("--pairdist-outgroup", type=int, default=None, metavar="K", help="pairdist: --panel list K (1-based) is the outgroup O: adds "
+                    "RNDMIN = DMIN / ((mean H(A,O) + mean H(B,O)) / 2) to the main table")
+    ap.add_argument("--pairdist-panels", metavar="PATH", help="pairdist: one row per window and --panel list to PATH: the mismatch "
+                    "distribution's mean, variance, extremes and raggedness")
+    ap.add_argument("--pairdist-hist", metavar="PATH", help="pairdist: the distance histograms within every list and between every pair to "
+                    "PATH, long form, non-zero bins only; needs --pairdist-bins")
+    ap.add_argument("--pairdist-bins", type=int, default=None, metavar="B", help="pairdist: bins per histogram (1..1024); the last collects the overflow")
+    ap.add_argument("--pairdist-bin-width", type=int, default=None, metavar="w", help="pairdist: distances per bin (default 1)")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
                     "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
                     "-r N or --identity dice from one Gram pass per window (impop_pairwise_scan_panel).  tajd: every panel (replaces "
@@ -1056,10 +1169,12 @@ def main():
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
     refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or ibs_refusal(args) or dstat_refusal(args)
-               or sfs_refusal(args))
+               or sfs_refusal(args) or pairdist_refusal(args))
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
+    if args.format == "pairdist":
+        return scan_pairdist(args)
     if args.sim_list:
         refusal = sim_list_refusal(args)
         if refusal:
