@@ -36,12 +36,15 @@ def doubles(abba, baba, f4_num, fd_den_p2, fd_den_p3, n):
     return d, f4, fd
 
 
-def reference(m01, pops, quartets, windows, polarize=False, weights=None):
+def reference(m01, pops, quartets, windows, polarize=False, weights=None, counts=None):
     """-> records [n_windows, n_quartets]; pops = lists of haplotype indices, quartets = rows (P1, P2, P3, O) of indices into pops,
-    windows = (site_begin, site_end) rows, weights = one integer per site or None"""
-    m = np.asarray(m01).astype(np.int64)
-    n_site = m.shape[1]
-    counts = [[int(x) for x in m[list(p)].sum(axis=0)] for p in pops]  # per population, per site
+    windows = (site_begin, site_end) rows, weights = one integer per site or None.  counts = the populations' column sums
+    [K][n_site] where the caller has them already (a wide matrix is then not cast to int64 as a whole; m01 is not read)"""
+    if counts is None:
+        m = np.asarray(m01).astype(np.int64)
+        counts = [m[list(p)].sum(axis=0) for p in pops]
+    counts = [[int(x) for x in c] for c in counts]  # per population, per site
+    n_site = len(counts[0])
     sizes = [len(p) for p in pops]
     wt = [1] * n_site if weights is None else [int(x) for x in weights]
     out = np.zeros((len(windows), len(quartets)), dtype=STATS_DTYPE)

@@ -69,11 +69,15 @@ def doubles(n, seg, sum_het, sum_c, sum_c2):
     return theta_w, theta_pi, theta_h, theta_l, tajima_d, faywu_h, faywu_h_norm, zeng_e
 
 
-def polarized_counts(m01, pops, outgroup):
-    """-> (counts [K][n_site] as the outgroup polarises them, tie [n_site], flipped [n_site])"""
-    m = np.asarray(m01).astype(np.int64)
-    n_site = m.shape[1]
-    counts = [[int(x) for x in m[list(p)].sum(axis=0)] for p in pops]
+def polarized_counts(m01, pops, outgroup, counts=None):
+    """-> (counts [K][n_site] as the outgroup polarises them, tie [n_site], flipped [n_site]).  counts = the populations' column
+    sums as stored, [K][n_site], where the caller has them already (a wide matrix is then not cast to int64 as a whole; m01 is
+    not read)"""
+    if counts is None:
+        m = np.asarray(m01).astype(np.int64)
+        counts = [m[list(p)].sum(axis=0) for p in pops]
+    counts = [[int(x) for x in c] for c in counts]
+    n_site = len(counts[0])
     sizes = [len(p) for p in pops]
     tie, flipped = [False] * n_site, [False] * n_site
     if outgroup is not None:
@@ -88,12 +92,13 @@ def polarized_counts(m01, pops, outgroup):
     return counts, tie, flipped
 
 
-def reference(m01, pops, pairs, windows, outgroup=None, weights=None):
+def reference(m01, pops, pairs, windows, outgroup=None, weights=None, counts=None):
     """-> (stats [n_windows, K], pair records [n_windows, P], sfs: K arrays [n_windows, n_k + 1], jsfs: P arrays
     [n_windows, n_a + 1, n_b + 1]); pops = lists of haplotype indices, pairs = rows (a, b) of indices into pops, windows =
-    (site_begin, site_end) rows, outgroup = an index into pops or None, weights = one integer per site or None"""
-    counts, tie, _ = polarized_counts(m01, pops, outgroup)
-    n_site = np.asarray(m01).shape[1]
+    (site_begin, site_end) rows, outgroup = an index into pops or None, weights = one integer per site or None, counts as
+    in polarized_counts"""
+    counts, tie, _ = polarized_counts(m01, pops, outgroup, counts)
+    n_site = len(counts[0])
     sizes = [len(p) for p in pops]
     K, P, W = len(pops), len(pairs), len(windows)
     wt = [1] * n_site if weights is None else [int(x) for x in weights]

@@ -11,6 +11,14 @@ one step beyond it where that step must be refused by an argument check (never b
   impop_pairwise_counts         n = 16384 / 16385, where the minor-allele polarity of the Gram operand switches off
   impop_pica2_pair_terms        directly, against pica2.py:125-145
 
+The calls added since then are in tests/test_gpu_upper_range_scans.py (the wide matrices both files use come from
+tests/wide_cases.py):
+
+  impop_dstat_scan / impop_sfs_scan  n_hap <= 65535: Gf > 4, 56 .. 64 KiB of mask LDS, products next to 2^30, sums next to 2^62
+  impop_sfs_scan's tables            a histogram that fills the 160 KiB of LDS exactly, one bin more, 65536 bins
+  impop_haplotype_scan / impop_ld_scan / impop_diploid_scan / impop_ibs_scan / impop_ehh_scan
+                                     their <= 4096 members (2048 individuals) scattered over a 65535-haplotype matrix
+
 The references are tests/plain_refs.py (pinned to the goldens and the C oracle by tests/test_plain_refs.py); the doubles of a
 scan record come from the oracle's site-count formulation under the tolerance policy of INTEGRATION.md 4 (conftest.stat_close).
 Everything else is exact."""
@@ -22,6 +30,7 @@ import pytest
 
 import plain_refs as pr
 from conftest import stat_close
+from wide_cases import SCAN_S, _crafted_wide, _scan_windows, _special  # noqa: F401 (moved there unchanged)
 
 pytestmark = pytest.mark.gpu
 
@@ -316,50 +325,6 @@ def test_ehh_curves_that_never_or_at_once_reach_zero(ctx):
 
 # ---- 4. scan and scan_multi above 4096 haplotypes ---------------------------------------------------------------------------------
 
-SCAN_S = 64 * 40 + 13
-
-
-def _special(n):
-    return [0, 31, 32, n - 2, n - 1]
-
-
-def _crafted_wide(n, seed):
-    """0/1 [n, SCAN_S] like _crafted of test_gpu_scan_rare.py: a rare-only, a common-only and a monomorphic stretch, then a mix.
-    Rare columns have 1 .. 4 carriers of either allele among haplotypes 0, 31, 32, n - 2, n - 1 (every subset, so n - 1 sits
-    in every slot of an entry and alone in one; 4 carriers is a common site); every such column appears at least once."""
-    rng = np.random.default_rng(seed)
-    S = SCAN_S
-    cols = []
-    for k in (1, 2, 3, 4):
-        for car in itertools.combinations(_special(n), k):
-            for pol in (0, 1):
-                c = np.zeros(n, np.uint8)
-                c[list(car)] = 1
-                cols.append(c ^ pol)
-    cols = np.array(cols).T  # [n, 60]
-    m = np.repeat((rng.random(S) < 0.5)[None, :].astype(np.uint8), n, axis=0)
-    m[:, :cols.shape[1]] = cols
-
-    def put_rare(lo, hi, p):
-        idx = np.nonzero(rng.random(hi - lo) < p)[0] + lo
-        m[:, idx] = cols[:, rng.integers(0, cols.shape[1], len(idx))]
-
-    def put_common(lo, hi, p):
-        idx = np.nonzero(rng.random(hi - lo) < p)[0] + lo
-        m[:, idx] = (rng.random((n, len(idx)), dtype=np.float32) < 0.3).astype(np.uint8)
-
-    put_rare(60, 400, 0.3)
-    put_common(400, 800, 0.1)
-    put_rare(1000, S, 0.08)
-    put_common(1000, S, 0.04)
-    for s in np.nonzero(rng.random(S - 1000) < 0.04)[0] + 1000:  # private sites of either polarity at random haplotypes
-        m[:, s] = 0
-        m[rng.integers(0, n), s] = 1
-        if rng.random() < 0.5:
-            m[:, s] ^= 1
-    return m
-
-
 def _masks_wide(n, seed, cfg):
     """P / A / B with the special haplotypes in P only, A only, B only, A and B (the overlap leaves both) or none; "last": A is
     exactly {n - 1}"""
@@ -376,13 +341,6 @@ def _masks_wide(n, seed, cfg):
         A[n - 1] = 1
         B[n - 1] = 0
     return P, A, B
-
-
-def _scan_windows(S):
-    w = [(0, 400, 0), (400, 800, 0), (800, 1000, 0), (0, S, S), (390, 410, 0), (999, 1001, 0), (5, 5, 0), (63, 65, 0), (S - 13, S, 0),
-         (1800, S, 12345), (0, 60, 0), (0, 1, 7)]
-    w += [(a, min(a + 150, S), 150) for a in range(1000, 1750, 150)]  # a tiling of the mixed stretch
-    return w
 
 
 def _check_records(oracle, recs, m, bits, wins, P, A, B, d_pi_mode, s_scope, where):
