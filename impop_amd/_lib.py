@@ -180,6 +180,16 @@ class IbsWindow(C.Structure):
                 ("reserved", C.c_uint32), ("share", C.c_double)]
 
 
+class IhsParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_mac", C.c_uint32), ("cutoff_milli", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_extend_bp", C.c_uint64), ("max_extend_sites", C.c_uint64)]
+
+
+class IhsCore(C.Structure):
+    _fields_ = [("site", C.c_uint64), ("n", C.c_uint32 * 2), ("c1", C.c_uint32 * 2), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("ihh2", (C.c_uint64 * 2) * 2), ("sl2", (C.c_uint64 * 2) * 2)]
+
+
 class DstatParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("polarize", C.c_int32), ("tile_blocks", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -242,6 +252,8 @@ assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(
 DIPLOID_MAX_N = 2048
 assert C.sizeof(IbsParams) == 32 and C.sizeof(IbsPair) == 32 and C.sizeof(IbsSegment) == 32 and C.sizeof(IbsWindow) == 32
 IBS_MAX_N, IBS_MAX_PAIRS, IBS_OPEN_LEFT, IBS_OPEN_RIGHT = 4096, 8388608, 1, 2
+assert C.sizeof(IhsParams) == 32 and C.sizeof(IhsCore) == 96
+IHS_SCAN_MAX_N = 4096
 assert C.sizeof(DstatStats) == 80 and C.sizeof(DstatParams) == 16
 DSTAT_GROUP, DSTAT_MAX_QUARTETS = 3, 64
 assert C.sizeof(SfsStats) == 112 and C.sizeof(SfsPair) == 32 and C.sizeof(SfsParams) == 24
@@ -338,6 +350,9 @@ SIGNATURES = {
     "impop_ibs_scan": (C.c_int, [_vp, _vp, _u64p, _u32p, C.c_uint64, C.POINTER(Window), C.c_uint64, C.POINTER(IbsParams),
                                  C.POINTER(IbsPair), C.POINTER(IbsSegment), C.c_uint64, _u64p, C.POINTER(IbsWindow)]),
     "impop_ctx_ibs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_ihs_scan": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _u64p, _u64p, C.POINTER(IhsParams),
+                                 C.POINTER(IhsCore), C.c_uint64, _u64p]),
+    "impop_ctx_ihs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_dstat_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, _u32p, C.c_uint32, C.POINTER(DstatParams),
                                    C.POINTER(DstatStats)]),
     "impop_ctx_dstat_elapsed": (C.c_int, [_vp, _f64p, _u64p]),

@@ -247,14 +247,15 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
     const uint32_t w = ctx->h_err;
     ctx->h_err = 0;
     HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s%s); the results of this call are invalid", fn, w,
+    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s%s%s); the results of this call are invalid", fn, w,
               (w & DEV_ERR_GROUPING) ? ": greedy grouping made no progress" : "",
               (w & DEV_ERR_CLUSTER) ? ": clustering ran out of rounds" : "",
               (w & DEV_ERR_EHH) ? ": EHH partition refinement is inconsistent" : "",
               (w & DEV_ERR_HAPSCAN) ? ": haplotype classes do not partition the members" : "",
               (w & DEV_ERR_LDSCAN) ? ": LD scan gathered a different number of sites than it selected" : "",
               (w & DEV_ERR_DIPLOID) ? ": diploid scan rows do not add up to their window" : "",
-              (w & DEV_ERR_IBS) ? ": IBS scan's two sweeps disagree on a pair's tracts" : "");
+              (w & DEV_ERR_IBS) ? ": IBS scan's two sweeps disagree on a pair's tracts" : "",
+              (w & DEV_ERR_IHS) ? ": iHS scan's break weights or reaches are inconsistent" : "");
     return IMPOP_E_INTERNAL;
 }
 }  // namespace impop

@@ -169,7 +169,8 @@ struct impop_ctx {
         T_SFS,               // impop_sfs_scan: summary / table launches (impop_ctx_sfs_elapsed)
         T_IBS = T_SFS + 2,   // impop_ibs_scan: transpose / walk / combine + close kernels (impop_ctx_ibs_elapsed)
         T_PAIRDIST = T_IBS + 3,  // impop_pairdist_scan: the distribution kernel of every chunk (impop_ctx_pairdist_elapsed)
-        T_COUNT
+        T_IHS,               // impop_ihs_scan: classify + tables / walk kernels (impop_ctx_ihs_elapsed)
+        T_COUNT = T_IHS + 2
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
@@ -292,6 +293,7 @@ constexpr uint32_t DEV_ERR_HAPSCAN = 8u;             // haplotype scan: the clas
 constexpr uint32_t DEV_ERR_LDSCAN = 16u;             // LD scan: the rows gathered for a window are not its n_used
 constexpr uint32_t DEV_ERR_DIPLOID = 32u;           // diploid scan: a window's rows do not add up to its het_total or its length
 constexpr uint32_t DEV_ERR_IBS = 64u;               // IBS scan: a pair's runs do not add up to the range, or the fill met a tract the count did not announce
+constexpr uint32_t DEV_ERR_IHS = 128u;              // iHS scan: a class's break weights do not add up to its pairs, or a reach lies in front of the warm-up start
 constexpr uint32_t DEV_ERR_EHH = 4u;                // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need

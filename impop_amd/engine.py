@@ -12,7 +12,9 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+
+from .ihs import IHS_DTYPE  # noqa: E402
 
 STATS_DTYPE = np.dtype([
     ("n_sites", "<u4"), ("s_all", "<u4"), ("s_p", "<u4"), ("s_a", "<u4"), ("s_b", "<u4"), ("flags", "<u4"),
@@ -247,6 +249,12 @@ class Context:
         """-> ([transpose, walk, combine + close] kernel ms of ibs_scan, site chunks transposed) since gram_timing(True)"""
         t, k = (C.c_double * 3)(), C.c_uint64()
         check(self._lib.impop_ctx_ibs_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def ihs_elapsed(self):
+        """-> ([classify + tables, walk] kernel ms of ihs_scan, walks timed) since gram_timing(True)"""
+        t, k = (C.c_double * 2)(), C.c_uint64()
+        check(self._lib.impop_ctx_ihs_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def dstat_elapsed(self):
@@ -830,6 +838,39 @@ class BitMatrix:
             if total.value:
                 call(seg, len(seg))
         return rec, seg, win, int(total.value)
+
+    def ihs_scan(self, mask_a=None, mask_b=None, site_begin: int = 0, site_end: Optional[int] = None, core_begin: Optional[int] = None,
+                 core_end: Optional[int] = None, min_mac: int = 1, cutoff_milli: int = 50, max_extend_bp: int = 0, max_extend_sites: int = 0,
+                 capacity: Optional[int] = None):
+        """Integrated haplotype homozygosity per core site (impop_ihs_scan): one population (mask_a, None = all haplotypes; classes
+        by allele: iHS, nSL) or two (mask_a, mask_b; classes by population: XP-EHH, XP-nSL).  Stepped sites are those of
+        [site_begin, site_end) that vary in the population(s); cores those inside [core_begin, core_end) (None = the site range)
+        with a minor-allele count of at least min_mac.  -> records (IHS_DTYPE, exact integers; impop_amd.ihs.ihs_values and
+        standardize make the scores).  One counting call, then one filling call; with capacity given, one call with room for that
+        many (-> None, and the count, when there are more cores: see n_cores of the returned tuple).
+        -> (records or None, number of cores)."""
+        ma, pa = _mask_ptr(mask_a, self.n_hap)
+        mb, pb = _mask_ptr(mask_b, self.n_hap)
+        se = 0 if site_end is None else int(site_end)
+        kb = int(site_begin) if core_begin is None else int(core_begin)
+        ke = 0 if core_end is None else int(core_end)  # 0: the site range's end, as in the ABI
+        prm = IhsParams(C.sizeof(IhsParams), int(min_mac), int(cutoff_milli), 0, int(max_extend_bp), int(max_extend_sites))
+        total = C.c_uint64(0)
+
+        def call(rec):
+            check(self.ctx._lib.impop_ihs_scan(self.ctx.handle, self.handle, int(site_begin), se, kb, ke, pa, pb, C.byref(prm),
+                                               None if rec is None else rec.ctypes.data_as(C.POINTER(IhsCore)),
+                                               0 if rec is None else len(rec), C.byref(total)))
+
+        if capacity is not None:
+            rec = np.zeros(int(capacity), dtype=IHS_DTYPE)
+            call(rec if len(rec) else None)
+            return (rec[:total.value] if total.value <= len(rec) else None), int(total.value)
+        call(None)
+        rec = np.zeros(total.value, dtype=IHS_DTYPE)
+        if total.value:
+            call(rec)
+        return rec, int(total.value)
 
     def dstat_scan(self, windows, pops, quartets, polarize: bool = False, tile_blocks: int = 0) -> np.ndarray:
         """Patterson's D (ABBA-BABA), f4 and Martin's f_d per window and quartet (impop_dstat_scan): pops = 4..8 masks, quartets =

@@ -1129,6 +1129,73 @@ int impop_paths_table_parse(const char *path, impop_gfa **out);
  * exposed so that the device implementation can be fuzzed against CPython. */
 int impop_py_round(impop_ctx *ctx, const double *x, uint64_t count, int ndigits, double *out);
 
+#define IMPOP_IHS_SCAN_MAX_N 4096u       /* |P| */
+#define IMPOP_IHS_EDGE_BITS  0x00FFu     /* flags: the integral ran into the end of the site range */
+#define IMPOP_IHS_LIMIT_BITS 0xFF00u     /* flags: the integral ran into max_extend_* */
+/* Per-site integrated haplotype homozygosity for a whole range of sites in one pass: the integers behind iHS and nSL (one
+ * population, classes by allele) and XP-EHH / XP-nSL (two populations, classes by population), with the EHH cutoff.  The device
+ * carries a positional Burrows-Wheeler transform over the sites that vary in P, so neighbouring cores share all their work and
+ * every number is an exact integer.  Works on full, weighted and compacted matrices (site weights play no part).
+ * Populations: mask_b NULL: K = 1, P = the members of mask_a (NULL = all haplotypes).  Else K = 2: A = mask_a, B = mask_b,
+ * disjoint, at least 2 members each, P = A u B.
+ * Stepped sites: the sites s of [site_begin, site_end) (site_end 0 = the matrix's end; ORIGINAL coordinates) with
+ * 0 < c_P(s) < |P|, numbered 0, 1, ... in order (ordinals); p(x) = the coordinate of ordinal x.  Sites monomorphic in P are
+ * never stepped on.  Cores: the stepped sites inside [core_begin, core_end) (core_end 0 = site_end) with
+ * min(c_P, |P| - c_P) >= min_mac, reported in site order.
+ * Classes at core k: K = 1: class a = the members of P whose bit at k is a; K = 2: class 0 = A, class 1 = B.  n_g = the size,
+ * C_g = n_g (n_g - 1) / 2.  Half 0 walks towards lower coordinates, half 1 towards higher; x_j = the ordinal j steps from k.
+ * surv(j) = the pairs of class g identical at every stepped site from x_j to k, k included (K = 1: surv(0) = C_g; K = 2: the
+ * pairs that agree at k).  Reach J: the largest j for which x_j exists and, for the base-pair measure, |p(x_j) - p(k)| <=
+ * max_extend_bp when that is non-zero, for the site measure, j <= max_extend_sites when that is non-zero.  Stop j*: the largest
+ * j <= J with 1000 surv(j) >= cutoff_milli C_g.  If that fails at j = 0, or n_g < 2, the integral is 0 and no flag is set.
+ *   ihh2[g][h] = sum over j < j* of (surv(j) + surv(j+1)) |p(x_j+1) - p(x_j)|      (twice the trapezoid, base pairs)
+ *   sl2[g][h]  = sum over j < j* of (surv(j) + surv(j+1))                           (the same in sites)
+ * Flags, bit 4 measure + 2 g + h (measure 0 = base pairs, 1 = sites): EDGE (bits 0..7) when j* = J and every existing x_j was
+ * within the limit, LIMIT (bits 8..15) when j* = J and the limit set J.  Either means the cutoff was not reached.
+ * Host doubles: iHH_g = (ihh2[g][0] + ihh2[g][1]) / (2 C_g), SL_g likewise; iHS = ln(iHH_1 / iHH_0), XP-EHH = ln(iHH_A / iHH_B).
+ * Capacity: *n_cores always receives the number of cores.  Records are written only when out_host is non-NULL and capacity is
+ * at least that number; else the call returns IMPOP_OK after the classification alone.
+ * Known answer: rows over 7 sites, site 0 first, h0 = 1011010, h1 = 1011000, h2 = 0011010, h3 = 0100110, h4 = 0101110,
+ * h5 = 1101100; all haplotypes, the whole matrix, min_mac 3, cutoff_milli 300, no limits.  Stepped: sites 0..5.  Four cores
+ * (site: n, c1, flags, ihh2 = sl2 as [[g0h0, g0h1], [g1h0, g1h1]]):
+ *   0: (3,3) (0,3)  85 [[0,6],[0,10]]     1: (3,3) (0,3) 119 [[4,22],[4,12]]
+ *   2: (3,3) (0,3) 221 [[10,6],[10,16]]   4: (3,3) (0,3) 187 [[22,4],[8,4]]
+ * With max_extend_bp 2 and max_extend_sites 1 the same cores give flags 43605, 43605, 64005, 21930,
+ * ihh2 [[0,6],[0,6]], [[4,12],[4,10]], [[10,6],[10,12]], [[12,4],[6,4]] and sl2 [[0,4],[0,4]], [[4,6],[4,6]], [[6,4],[6,6]],
+ * [[6,4],[4,4]].
+ * A wrong struct_size, min_mac == 0, cutoff_milli > 1000, a site range that is empty or outside the matrix (or 2^32 sites long),
+ * a core range outside the site range, overlapping populations, a population of fewer than 2 members and mask_b without mask_a
+ * return IMPOP_E_INVALID; |P| > IMPOP_IHS_SCAN_MAX_N IMPOP_E_UNSUPPORTED; all before anything is uploaded or launched.
+ * Chunks: the walk is cut into chunks of 64-site blocks, each warmed up from the farthest site its cores may reach under either
+ * limit.  The default length makes the warm-up a minor share of a chunk's steps.  A measure without a limit reaches the end of
+ * the range, so with either limit 0 there is one chunk per direction: exact, and slow on a long range.
+ * IMPOP_IHS_CHUNK_BLOCKS=n (1..4096) sets the chunk length (a test aid); records never change with it.
+ * Under IMPOP_TRACE=1 a call that gets past its refusals prints one line on stderr:
+ *   [impop_ihs_scan] route=<dense|compact> pops= members= stepped= cores= chunks= warmup_steps= launches= bytes_streamed=
+ * (chunks, warmup_steps: 0 when only the count was asked for; bytes_streamed: the rows the classification and the walks read). */
+typedef struct impop_ihs_params {        /* 32 bytes */
+    uint32_t struct_size;
+    uint32_t min_mac;                    /* >= 1 */
+    uint32_t cutoff_milli;               /* 0..1000: EHH cutoff in thousandths */
+    uint32_t reserved;
+    uint64_t max_extend_bp;              /* 0 = none */
+    uint64_t max_extend_sites;           /* 0 = none */
+} impop_ihs_params;
+typedef struct impop_ihs_core {          /* 96 bytes, fixed layout, all integers */
+    uint64_t site;
+    uint32_t n[2];                       /* class sizes */
+    uint32_t c1[2];                      /* carriers of allele 1 in each class */
+    uint32_t flags;
+    uint32_t reserved;
+    uint64_t ihh2[2][2];                 /* [class][half] */
+    uint64_t sl2[2][2];
+} impop_ihs_core;
+int impop_ihs_scan(impop_ctx *ctx, const impop_matrix *m, uint64_t site_begin, uint64_t site_end, uint64_t core_begin,
+                   uint64_t core_end, const uint64_t *mask_a, const uint64_t *mask_b, const impop_ihs_params *params,
+                   impop_ihs_core *out_host /* nullable */, uint64_t capacity, uint64_t *n_cores);
+/* With impop_ctx_gram_timing on, impop_ihs_scan brackets its kernels: kernel_ms[0] = classification, prefix and tables,
+ * [1] = the walk, summed since enable / reset; calls = walks timed. */
+int impop_ctx_ihs_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *calls);
 #ifdef __cplusplus
 }
 #endif

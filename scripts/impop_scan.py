@@ -15,6 +15,8 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed windows.bed --format hapstats [-u subset.txt] [--compact]   # K, H1, H12, H2/H1 per window
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ld [-u subset.txt] [--ld-min-maf F] [--ld-max-sites M]   # ZnS, |D'|, omega
     impop_scan.py --matrix chr2.npz --bed windows.bed --format diploid [-u subset.txt] [--roh-min-sites N] [--ind-table PATH]   # Ho, He, F_IS, ROH
+    impop_scan.py --matrix chr2.npz --bed cores.bed --format ihs [-u subset.txt] [--ihs-min-maf F] [--ihs-cutoff F] [--ihs-max-extend BP] [--ihs-max-extend-sites N] [--ihs-bins B] [--ihs-keep-edge] [--compact]   # iHS / nSL per site
+    impop_scan.py --matrix chr2.npz --bed cores.bed --format xpehh --panel a.txt b.txt [--ihs-...] [--compact]   # XP-EHH / XP-nSL per site
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ibs [-u subset.txt] [--ibs-min-sites N] [--ibs-pairs all|diploid] [--ibs-segments PATH] [--ibs-pair-table PATH]   # IBS tracts / ROH segments
     impop_scan.py --matrix chr2.npz --bed windows.bed --format pairdist --panel a.txt b.txt [more.txt] [--pairdist-outgroup K] [--pairdist-panels panels.tsv] [--pairdist-hist hist.tsv --pairdist-bins B --pairdist-bin-width w] [--compact]   # d_min, G_min, S_nn, mismatch distributions
     impop_scan.py --matrix chr2.npz --bed windows.bed --format sfs --panel A.txt [B.txt ...] [--sfs-outgroup i] [--sfs-pair i,j]...   # spectra, neutrality tests
@@ -71,6 +73,16 @@ site, HE = 2 sum p q n / (n - 1) per site among the 2 N_IND copies, FIS = 1 - HO
 --roh-min-sites N sites (default 50) without a heterozygous site, F_ROH = the share of sites inside them; NA where undefined);
 --ind-table PATH adds one row per window and sample: CHROM START END SAMPLE HET HOM_ALT LONGEST_RUN ROH_RUNS ROH_SITES.  --compact
 allowed.  One process, one GPU; not with --sim-list, -A / -B / --panel / -l, --devices N, -t / -r.
+
+--format ihs / xpehh (impop_ihs_scan): per-site integrated haplotype homozygosity from a device PBWT.  The site range is the whole
+matrix of each BED row's contig; the row selects the cores (the sites of the row that vary among the sequences and whose minor-allele
+frequency is at least --ihs-min-maf, default 0.05).  ihs: the sequences of -u (default: all), classes by allele, one row per core
+CHROM SITE N0 N1 FREQ1 IHH0 IHH1 IHS IHS_STD SL0 SL1 NSL NSL_STD FLAGS; xpehh: the two lists of --panel, classes by population,
+CHROM SITE NA NB FREQ1_A FREQ1_B IHH_A IHH_B XPEHH XPEHH_STD SL_A SL_B XPNSL XPNSL_STD FLAGS.  The EHH curve is integrated until it
+falls below --ihs-cutoff (default 0.05), at most --ihs-max-extend site coordinates (default 1000000; 0 = no limit) for IHH and
+--ihs-max-extend-sites varying sites (default 100; 0 = no limit) for SL.  The *_STD columns are standardised over all rows of the run:
+iHS and nSL within --ihs-bins (default 50) bins of FREQ1, the XP scores over all cores.  Cores whose integral ran into the end of the
+matrix (an EDGE bit in FLAGS) are left out unless --ihs-keep-edge is given.  Allele 1 against allele 0 is the caller's polarity.
 
 --format ibs (impop_ibs_scan): pairwise identity-by-state tracts over the whole matrix of each BED row's contig, every pair of the
 sequences of -u (default: all; --ibs-pairs all) or the two haplotypes of every sample (--ibs-pairs diploid: the PanSN pairing of
@@ -772,6 +784,133 @@ def scan_pairdist(args):
             fh.close()
 
 
+def ihs_refusal(args):
+    """what --format ihs / xpehh do not combine with (one line each, exit 2, before any device is opened)"""
+    own = (args.ihs_min_maf is not None or args.ihs_cutoff is not None or args.ihs_max_extend is not None
+           or args.ihs_max_extend_sites is not None or args.ihs_bins is not None or args.ihs_keep_edge)
+    if args.format not in ("ihs", "xpehh"):
+        return ("--ihs-min-maf / --ihs-cutoff / --ihs-max-extend / --ihs-max-extend-sites / --ihs-bins / --ihs-keep-edge belong to "
+                "--format ihs and --format xpehh") if own else None
+    f = f"--format {args.format}"
+    if args.sim_list:
+        return f"{f} scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return f"{f} is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return f"{f} runs on one GPU: not with --devices N"
+    if args.threshold is not None or args.round_digits is not None or args.fst_round_digits is not None:
+        return f"{f} integrates haplotype homozygosity: it has no -t / -r"
+    if args.format == "ihs" and (args.pop_a or args.pop_b or args.panel or args.sample_list):
+        return "--format ihs scans the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.format == "xpehh":
+        if not args.panel or len(args.panel) != 2:
+            return "--format xpehh takes --panel a.txt b.txt: two population lists"
+        if args.pop_a or args.pop_b or args.sample_list or args.subset:
+            return "--format xpehh compares the two populations of --panel: not with -A / -B / -l / -u"
+    if args.ihs_min_maf is not None and not 0.0 < args.ihs_min_maf <= 0.5:
+        return "--ihs-min-maf takes a frequency above 0, at most 0.5"
+    if args.ihs_cutoff is not None and not 0.0 <= args.ihs_cutoff <= 1.0:
+        return "--ihs-cutoff takes 0 to 1"
+    if (args.ihs_max_extend is not None and args.ihs_max_extend < 0) or (args.ihs_max_extend_sites is not None and args.ihs_max_extend_sites < 0):
+        return "--ihs-max-extend / --ihs-max-extend-sites take 0 (no limit) or more"
+    if args.ihs_bins is not None and args.ihs_bins < 1:
+        return "--ihs-bins takes 1 or more"
+    return None
+
+
+IHS_HEADER = "CHROM\tSITE\tN0\tN1\tFREQ1\tIHH0\tIHH1\tIHS\tIHS_STD\tSL0\tSL1\tNSL\tNSL_STD\tFLAGS"
+XPEHH_HEADER = "CHROM\tSITE\tNA\tNB\tFREQ1_A\tFREQ1_B\tIHH_A\tIHH_B\tXPEHH\tXPEHH_STD\tSL_A\tSL_B\tXPNSL\tXPNSL_STD\tFLAGS"
+
+
+def write_ihs_table(out, K, chroms, bps, rec, bins, keep_edge):
+    """the table of --format ihs (K = 1) / xpehh (K = 2) from impop_ihs_core records of all rows of the run: the doubles, the scores
+    standardised over all of them, one row per core; cores with an EDGE bit are left out unless keep_edge"""
+    from impop_amd import ihs as ih
+    v = ih.ihs_values(rec, K)
+    first, second = ("ihs", "nsl") if K == 1 else ("xpehh", "xpnsl")
+    freq = v["freq1"] if K == 1 else None
+    std = [ih.standardize(v[first], rec["flags"], 0, freq, bins), ih.standardize(v[second], rec["flags"], 1, freq, bins)]
+    num = lambda x: "NA" if x != x else f"{x:.8f}"  # noqa: E731
+    print(IHS_HEADER if K == 1 else XPEHH_HEADER, file=out)
+    for i, r in enumerate(rec):
+        if (int(r["flags"]) & ih.EDGE_BITS) and not keep_edge:
+            continue
+        n0, n1 = int(r["n"][0]), int(r["n"][1])
+        fr = num(v["freq1"][i]) if K == 1 else f"{int(r['c1'][0]) / n0:.8f}\t{int(r['c1'][1]) / n1:.8f}"
+        print(f"{chroms[i]}\t{bps[i]}\t{n0}\t{n1}\t{fr}\t{num(v['ihh'][i, 0])}\t{num(v['ihh'][i, 1])}\t{num(v[first][i])}\t{num(std[0][i])}\t"
+              f"{num(v['sl'][i, 0])}\t{num(v['sl'][i, 1])}\t{num(v[second][i])}\t{num(std[1][i])}\t{int(r['flags'])}", file=out)
+
+
+def scan_ihs(args):
+    """--format ihs / xpehh: one impop_ihs_scan per BED row over its contig's whole matrix, the row's sites as cores; the scores are
+    standardised over all rows of the run and the table goes to --output / stdout"""
+    import math
+    from impop_amd import ihs as ih
+    K = 2 if args.format == "xpehh" else 1
+    if args.device is None:
+        args.device = 0
+    mats = {}
+    for p in args.matrix:
+        mf = load_matrix(p)
+        key = (mf.contig if mf.contig.startswith(args.region_prefix) else args.region_prefix + mf.contig) if mf.contig else ""
+        if key in mats:
+            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
+            sys.exit(2)
+        mats[key] = mf
+    if "" in mats and len(mats) > 1:
+        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
+        sys.exit(2)
+    per_mat = {}
+    for chrom, s, e in read_bed(args.bed, args.format):
+        full = chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
+        key = "" if "" in mats else full
+        if key not in mats:
+            print(f"Warning: Skipping region {full}:{s}-{e}: no matrix holds chromosome {chrom}", file=sys.stderr)
+            continue
+        per_mat.setdefault(key, []).append((full, s, e))
+    maf = 0.05 if args.ihs_min_maf is None else args.ihs_min_maf
+    cutoff_milli = int(round(1000 * (0.05 if args.ihs_cutoff is None else args.ihs_cutoff)))
+    max_bp = 1000000 if args.ihs_max_extend is None else args.ihs_max_extend
+    max_sites = 100 if args.ihs_max_extend_sites is None else args.ihs_max_extend_sites
+    chroms, bps, recs = [], [], []
+    for key, rows in per_mat.items():
+        mf = mats[key]
+        if K == 2:
+            pops = [flags_for(f, mf.names) for f in args.panel]
+            if (pops[0] & pops[1]).any():
+                print("Error: --format xpehh: the two lists of --panel share a sequence; they must be disjoint", file=sys.stderr)
+                sys.exit(2)
+            if min(int(p.sum()) for p in pops) < 2:
+                print("Error: --format xpehh: each list of --panel needs at least two sequences of the matrix", file=sys.stderr)
+                sys.exit(2)
+            n_members = int(pops[0].sum() + pops[1].sum())
+        else:
+            pops = [flags_for(args.subset, mf.names) if args.subset else None, None]
+            n_members = mf.n_hap if pops[0] is None else int(pops[0].sum())
+            if n_members < 2:
+                print(f"Error: --format ihs: {n_members} sequences make no pair", file=sys.stderr)
+                sys.exit(2)
+        wins = [mf.site_range(s, e) + (e - s,) for _, s, e in rows]
+        run = Runner(args, mf, wins, False, 0, 1, 0)
+        site_bp = (lambda c, mf=mf: int(mf.site_pos[c])) if mf.site_pos is not None else (lambda c, mf=mf: int(mf.origin + c))
+        try:
+            for (full, _, _), (b, en, _) in zip(rows, wins):
+                if en <= b:
+                    continue
+                rec, _ = run.bm.ihs_scan(mask_a=pops[0], mask_b=pops[1], core_begin=b, core_end=en, min_mac=max(1, math.ceil(maf * n_members)),
+                                         cutoff_milli=cutoff_milli, max_extend_bp=max_bp, max_extend_sites=max_sites)
+                recs.append(rec)
+                chroms += [full] * len(rec)
+                bps += [site_bp(int(c)) for c in rec["site"]]
+        finally:
+            run.close()
+    out = open(args.output, "w") if args.output else sys.stdout
+    write_ihs_table(out, K, chroms, bps, np.concatenate(recs) if recs else np.zeros(0, dtype=ih.IHS_DTYPE),
+                    50 if args.ihs_bins is None else args.ihs_bins, args.ihs_keep_edge)
+    if args.output:
+        out.close()
+
+
 def sfs_row(region, label, n, r):
     """one row of the --format sfs table: region, the population's list name and size, the record"""
     chrom, start, end = split_region(region)
@@ -1079,7 +1218,7 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "pairdist", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "pairdist", "ihs", "xpehh", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
@@ -1088,7 +1227,8 @@ def main():
                          "ibs = pairwise identity-by-state tracts / ROH segments over each row's whole matrix (not part of `all`); "
                          "dstat = Patterson's D (ABBA-BABA), f4 and f_d per window and quartet of --panel populations (not part of `all`); "
                          "sfs = spectrum summaries and neutrality tests per window and --panel population, pair classes and spectra "
-                         "(not part of `all`)")
+                         "(not part of `all`); ihs = iHS and nSL per site from a device PBWT, xpehh = XP-EHH and XP-nSL per site between the "
+                         "two --panel populations, cores = the varying sites of each row (neither is part of `all`)")
     ap.add_argument("--af-clusters", metavar="FILE", help="af: long table REGION cluster_id count frequency (af.py's summary per window)")
     ap.add_argument("--af-details", metavar="FILE", help="af: long table REGION sample_id cluster_id threshold (af.py --details per window)")
     ap.add_argument("--ehh-core-offset", type=int, default=None, metavar="N", help="ehh: 0-based site offset of the core into each window "
@@ -1104,6 +1244,14 @@ def main():
     ap.add_argument("--roh-min-sites", type=int, default=None, metavar="N", help="diploid: a stretch without a heterozygous site counts as a "
                     "run of homozygosity when it is at least N sites long (default 50)")
     ap.add_argument("--ind-table", metavar="PATH", help="diploid: also write one row per window and sample to PATH")
+    ap.add_argument("--ihs-min-maf", type=float, default=None, metavar="F", help="ihs / xpehh: cores have a minor-allele frequency of at least F (default 0.05)")
+    ap.add_argument("--ihs-cutoff", type=float, default=None, metavar="F", help="ihs / xpehh: integrate until EHH falls below F (default 0.05)")
+    ap.add_argument("--ihs-max-extend", type=int, default=None, metavar="BP", help="ihs / xpehh: integrate IHH at most this far from the core, in site "
+                    "coordinates (default 1000000; 0 = no limit)")
+    ap.add_argument("--ihs-max-extend-sites", type=int, default=None, metavar="N", help="ihs / xpehh: integrate SL over at most N varying sites "
+                    "(default 100; 0 = no limit)")
+    ap.add_argument("--ihs-bins", type=int, default=None, metavar="B", help="ihs: frequency bins of the standardisation (default 50)")
+    ap.add_argument("--ihs-keep-edge", action="store_true", help="ihs / xpehh: keep the cores whose integral ran into the end of the matrix")
     ap.add_argument("--ibs-min-sites", type=int, default=None, metavar="N", help="ibs: a stretch without a difference between two "
                     "sequences is reported when it is at least N sites long (default 50)")
     ap.add_argument("--ibs-pairs", choices=["all", "diploid"], default=None, help="ibs: all = every pair of the sequences of -u (default); "
@@ -1169,12 +1317,14 @@ def main():
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
     refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or ibs_refusal(args) or dstat_refusal(args)
-               or sfs_refusal(args) or pairdist_refusal(args))
+               or sfs_refusal(args) or pairdist_refusal(args) or ihs_refusal(args))
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
     if args.format == "pairdist":
         return scan_pairdist(args)
+    if args.format in ("ihs", "xpehh"):
+        return scan_ihs(args)
     if args.sim_list:
         refusal = sim_list_refusal(args)
         if refusal:
