@@ -109,6 +109,23 @@ class DistPair(C.Structure):
                 ("snn", C.c_double), ("gmin", C.c_double), ("reserved", C.c_uint64)]
 
 
+class KinshipParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("kin_num", C.c_uint32), ("kin_den", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class KinWindow(C.Structure):
+    _fields_ = [("n_ind", C.c_uint32), ("n_sites", C.c_uint32), ("n_pairs", C.c_uint64), ("het_het", C.c_uint64), ("ibs0", C.c_uint64),
+                ("ibs2", C.c_uint64), ("n_related", C.c_uint32), ("n_undefined", C.c_uint32)]
+
+
+class KinPair(C.Structure):
+    _fields_ = [("t", C.c_uint64 * 9)]
+
+
+class KinWatch(C.Structure):
+    _fields_ = [("het_het", C.c_uint32), ("ibs0", C.c_uint32), ("het_i", C.c_uint32), ("het_j", C.c_uint32)]
+
+
 class EhhWindow(C.Structure):
     _fields_ = [("site_begin", C.c_uint64), ("site_end", C.c_uint64), ("core_site", C.c_uint64)]
 
@@ -244,6 +261,8 @@ assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
 assert C.sizeof(PanelStats) == 48 and C.sizeof(PanelWindow) == 8
 assert C.sizeof(DistPanel) == 64 and C.sizeof(DistPair) == 96 and C.sizeof(PairdistParams) == 16
 PAIRDIST_MAX_N, PAIRDIST_MAX_BINS = 4096, 1024  # IMPOP_PAIRDIST_MAX_N, IMPOP_PAIRDIST_MAX_BINS
+assert C.sizeof(KinWindow) == 48 and C.sizeof(KinPair) == 72 and C.sizeof(KinWatch) == 16 and C.sizeof(KinshipParams) == 16
+KINSHIP_MAX_N, KINSHIP_MAX_WATCH = 2048, 1024  # IMPOP_KINSHIP_MAX_N, IMPOP_KINSHIP_MAX_WATCH
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
 assert C.sizeof(HaplotypeStats) == 64 and C.sizeof(HaplotypeParams) == 16
 assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
@@ -328,6 +347,13 @@ SIGNATURES = {
                                             C.POINTER(PanelStats), C.POINTER(PairStats), C.POINTER(PanelWindow)]),
     "impop_pairdist_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairdistParams),
                                       C.POINTER(DistPanel), C.POINTER(DistPair), _u32p, _u32p]),
+    "impop_genotypes_create": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, C.POINTER(_vp)]),
+    "impop_genotypes_info": (C.c_int, [_vp, _u32p, _u64p, _u64p]),
+    "impop_genotypes_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),
+    "impop_genotypes_free": (C.c_int, [_vp, _vp]),
+    "impop_kinship_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, C.POINTER(KinshipParams), _u32p, C.c_uint32,
+                                     C.POINTER(KinWindow), C.POINTER(KinPair), C.POINTER(KinWatch)]),
+    "impop_ctx_kinship_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_cluster_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(ClusterParams),
                                      C.POINTER(ClusterStats), _u32p, _u32p]),
     "impop_pi_from_identity": (C.c_int, [_vp, _f64p, C.c_uint32, C.c_double, C.c_int, C.c_uint64, _u32p, _f64p, _f64p, _u32p, _u32p,

@@ -1,5 +1,5 @@
 // pairwise_scan.hip — the windowed all-pairs calls (impop_pairwise_scan, impop_pairwise_scan_panel, impop_cluster_scan,
-// impop_pairdist_scan): one shared
+// impop_pairdist_scan, impop_kinship_scan): one shared
 // front end — windows -> Gram cells -> chunks (pair_plan.h), per chunk the Gram launch (pairwise.hip) and the filled SimBatch — and
 // what each call does with the identities: its PairEpilogue.
 #include <stdlib.h>
@@ -554,6 +554,59 @@ struct PairdistEpilogue final : PairEpilogue {
     }
 };
 
+// impop_kinship_scan's epilogue (kinship.hip): per chunk the window kernel (records, watch rows, the diagonals) and, when the
+// per-pair totals are wanted, the totals kernel, which adds the chunk's tables into d_tot; d_tot lives across the chunks
+struct KinshipEpilogue final : PairEpilogue {
+    uint32_t N, n_watch;
+    int64_t num, den;
+    const uint32_t *watch;            // 2 x n_watch, host
+    impop_kin_window *out_windows;
+    impop_kin_watch *out_watch;       // nullable
+    bool want_totals;
+    uint64_t chunks = 0, launches = 0;
+    uint32_t *d_watch = nullptr, *d_diag = nullptr;
+    uint64_t *d_tot = nullptr, *d_part = nullptr;
+    impop_kin_window *d_win = nullptr, *h_win = nullptr;
+    impop_kin_watch *d_wat = nullptr, *h_wat = nullptr;
+    size_t n_totals() const { return want_totals ? (size_t)N * (N - 1) / 2 * 9 : 0; }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        D.sub(d_watch, 2 * (size_t)n_watch); D.sub(d_tot, n_totals());
+        const uint32_t Z = want_totals ? kinship_total_slices(N, cap) : 1u;  // the most slices a chunk of up to cap windows takes
+        D.sub(d_part, Z > 1 ? Z * n_totals() : 0);
+        D.sub(d_diag, cap * 2 * N); D.sub(d_win, cap); D.sub(d_wat, cap * n_watch);
+        H.sub(h_win, cap); H.sub(h_wat, cap * n_watch);
+    }
+    int upload(impop_ctx *ctx) override {
+        if (n_watch) HIP_TRY(hipMemcpyAsync(d_watch, watch, 2 * (size_t)n_watch * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (want_totals) HIP_TRY(hipMemsetAsync(d_tot, 0, n_totals() * 8, ctx->stream));
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const uint64_t cnt = c.cnt;
+        size_t slot = 0;  // the epilogue kernels between two events of their own: impop_ctx_kinship_elapsed
+        int rc = ctx->gram_timing ? ctx->timers[impop_ctx::T_KIN + 1].begin(ctx->stream, &slot) : IMPOP_OK;
+        if (rc) return rc;
+        const KinshipOut O{d_win, n_watch ? d_wat : nullptr, want_totals ? d_tot : nullptr, d_diag, d_part};
+        if ((rc = launch_kinship_windows(ctx, c.b, cnt, N, num, den, d_watch, n_watch, O))) return rc;
+        ++launches;
+        if (want_totals) {
+            if ((rc = launch_kinship_totals(ctx, c.b, cnt, N, O))) return rc;
+            launches += kinship_total_slices(N, cnt) > 1 ? 2 : 1;
+        }
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_KIN + 1].end(ctx->stream, slot))) return rc;
+        ++chunks;
+        HIP_TRY(hipMemcpyAsync(h_win, d_win, cnt * sizeof(impop_kin_window), hipMemcpyDeviceToHost, ctx->stream));
+        if (n_watch) HIP_TRY(hipMemcpyAsync(h_wat, d_wat, cnt * n_watch * sizeof(impop_kin_watch), hipMemcpyDeviceToHost, ctx->stream));
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        for (uint64_t k = 0; k < c.cnt; ++k) {
+            out_windows[c.ord[k]] = h_win[k];
+            if (n_watch) memcpy(out_watch + c.ord[k] * n_watch, h_wat + k * n_watch, (size_t)n_watch * sizeof(impop_kin_watch));
+        }
+    }
+};
+
 // ---- what the entry points share -------------------------------------------------------------------------------------------
 // the checks of impop_pairwise_params common to the calls that take one
 int check_pairwise_params(const impop_pairwise_params *params, const char *fn) {
@@ -661,6 +714,51 @@ IMPOP_API int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const i
         fprintf(stderr, "[impop_pairdist_scan] pops=%u pairs=%u members=%u windows=%llu chunks=%llu launches=%llu hist_bins=%u hist=%s\n", K, NP,
                 M, (unsigned long long)n_windows, (unsigned long long)epi.chunks, (unsigned long long)epi.launches, epi.B,
                 !epi.B ? "off" : epi.hist_lds ? "lds" : "global");
+    return IMPOP_OK;
+}
+
+static_assert(sizeof(impop_kin_window) == 48 && sizeof(impop_kin_pair) == 72 && sizeof(impop_kin_watch) == 16 &&
+                  sizeof(impop_kinship_params) == 16, "fixed record layouts");
+
+IMPOP_API int impop_kinship_scan(impop_ctx *ctx, const impop_genotypes *g, const impop_window *windows, uint64_t n_windows,
+                                 const impop_kinship_params *params, const uint32_t *watch, uint32_t n_watch,
+                                 impop_kin_window *out_windows, impop_kin_pair *out_pairs, impop_kin_watch *out_watch) {
+    const char *fn = "impop_kinship_scan";
+    REQUIRE(ctx && g && g->planes && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_kinship_params), "impop_kinship_params.struct_size mismatch");
+    REQUIRE(params->kin_den >= 1 && params->kin_den <= (1u << 20) && params->kin_num <= params->kin_den,
+            "%s: the threshold kin_num / kin_den needs 1 <= kin_den <= 2^20 and kin_num <= kin_den", fn);
+    const impop_matrix *m = g->planes;
+    const uint32_t N = g->n_ind;
+    REQUIRE(m->device == ctx->device, "%s: genotypes live on device %d, context on %d", fn, m->device, ctx->device);
+    REQUIRE(n_watch <= IMPOP_KINSHIP_MAX_WATCH, "%s: %u watched pairs exceed the limit (%u)", fn, n_watch, (uint32_t)IMPOP_KINSHIP_MAX_WATCH);
+    REQUIRE(!n_watch || (watch && out_watch), "%s: NULL watch / out_watch with n_watch = %u", fn, n_watch);
+    for (uint32_t q = 0; q < n_watch; ++q) {
+        const uint32_t a = watch[2 * q], b = watch[2 * q + 1];
+        REQUIRE(a < N && b < N, "%s: watched pair %u: individual %u outside the handle's %u", fn, q, a < N ? b : a, N);
+        REQUIRE(a != b, "%s: watched pair %u names individual %u twice", fn, q, a);
+    }
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_windows, "%s: NULL windows/out", fn);
+    int rc = check_windows(ctx, m, windows, n_windows, fn);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    KinshipEpilogue epi;
+    epi.N = N; epi.n_watch = n_watch; epi.num = params->kin_num; epi.den = params->kin_den;
+    epi.watch = watch; epi.out_windows = out_windows; epi.out_watch = out_watch; epi.want_totals = out_pairs != nullptr;
+    PairFront in{};
+    in.fn = fn; in.identity_kind = IMPOP_IDENTITY_MATCH; in.round_digits = -1;  // no polarity row: the counts are used as written
+    in.scan_host = nullptr; in.use_segmap = false; in.max_W = widest_W(m, windows, n_windows);
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (out_pairs) {  // the scratch the front end bound the totals into is still the context's
+        HIP_TRY(hipMemcpyAsync(out_pairs, epi.d_tot, epi.n_totals() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (trace_on())
+        fprintf(stderr, "[impop_kinship_scan] route=%s individuals=%u rows=%u windows=%llu chunks=%llu launches=%llu watch=%u plane_bytes=%llu\n",
+                m->compact ? "compact" : "dense", N, m->n_hap_pad, (unsigned long long)n_windows, (unsigned long long)epi.chunks,
+                (unsigned long long)epi.launches, n_watch, (unsigned long long)m->rb_bytes);
     return IMPOP_OK;
 }
 

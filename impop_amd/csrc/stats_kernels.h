@@ -267,4 +267,27 @@ size_t pairdist_lds_fixed(uint32_t K, uint32_t M);  // bytes of the accumulators
 int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PairdistTables &T,
                     const PairdistOut &O, bool hist_lds);
 
+// impop_kinship_scan's epilogue (kinship.hip) on a chunk's Gram problems of the 2N plane rows [H_0 .. H_{N-1}, A_0 .. A_{N-1}].
+struct KinshipOut {
+    impop_kin_window *windows;  // n_problems
+    impop_kin_watch *watch;     // n_problems x n_watch, or nullptr
+    uint64_t *totals;           // N (N - 1) / 2 x 9, ADDED to (one owner per entry), or nullptr
+    uint32_t *diag;             // scratch: n_problems x 2N, het then alt per problem (the windows kernel writes, the totals kernel reads)
+    uint64_t *part;             // scratch: kinship_total_slices x N (N - 1) / 2 x 9 when there is more than one slice, else unused
+};
+constexpr uint64_t KIN_TOTALS_THREADS = 1ull << 19;  // (pair, slice) threads the totals kernel aims at
+constexpr uint32_t KIN_TOTALS_MAX_SLICES = 64;
+uint32_t kinship_total_slices(uint32_t N, uint64_t n_problems);  // slices of the totals kernel for a chunk of n_problems windows
+// window records and watch rows: one workgroup per problem
+int launch_kinship_windows(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, int64_t num, int64_t den,
+                           const uint32_t *d_watch, uint32_t n_watch, const KinshipOut &O);
+// the per-pair tables of the chunk's problems added into O.totals: one thread per pair, the problems in turn
+int launch_kinship_totals(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, const KinshipOut &O);
+
 }  // namespace impop
+
+// the genotype planes of impop_genotypes_create: a matrix the Gram front end accepts (2N rows, RB32 operand alone), as its own type
+struct impop_genotypes {
+    impop_matrix *planes = nullptr;
+    uint32_t n_ind = 0;
+};

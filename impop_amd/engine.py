@@ -81,6 +81,12 @@ DIST_PAIR_DTYPE = np.dtype([("n_pairs", "<u8"), ("sum_h", "<u8"), ("sum_h2", "<u
                             ("nn_other_a", "<u4"), ("nn_other_b", "<u4"), ("snn", "<f8"), ("gmin", "<f8"), ("reserved", "<u8")])
 assert DIST_PANEL_DTYPE.itemsize == 64 and DIST_PAIR_DTYPE.itemsize == 96
 
+KIN_WINDOW_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("n_pairs", "<u8"), ("het_het", "<u8"), ("ibs0", "<u8"), ("ibs2", "<u8"),
+                             ("n_related", "<u4"), ("n_undefined", "<u4")])
+KIN_PAIR_DTYPE = np.dtype([("t", "<u8", (9,))])
+KIN_WATCH_DTYPE = np.dtype([("het_het", "<u4"), ("ibs0", "<u4"), ("het_i", "<u4"), ("het_j", "<u4")])
+assert KIN_WINDOW_DTYPE.itemsize == 48 and KIN_PAIR_DTYPE.itemsize == 72 and KIN_WATCH_DTYPE.itemsize == 16
+
 IDENTITY_STATS_DTYPE = np.dtype([
     ("status", "<i4"), ("n_groups", "<u4"), ("pi", "<f8"), ("pi_site", "<f8"), ("sum_2pairs", "<f8"), ("n_pairs_with_data", "<u8"),
     ("fst", "<f8", (6,)), ("fst_counts", "<u8", (6,)), ("tajima_d", "<f8")])
@@ -220,6 +226,12 @@ class Context:
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_pairdist_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
+
+    def kinship_elapsed(self):
+        """-> ([plane build, epilogue] kernel ms of genotypes() / kinship_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 2)(), C.c_uint64()
+        check(self._lib.impop_ctx_kinship_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
 
     def ehh_elapsed(self):
         """-> (summed kernel ms of ehh_scan, chunks) since gram_timing(True)"""
@@ -707,6 +719,20 @@ class BitMatrix:
                                                 hw.ctypes.data_as(u32p) if B else None, hb.ctypes.data_as(u32p) if B and NP else None))
         return panels, pairs, hw, hb
 
+    def genotypes(self, pairs) -> "Genotypes":
+        """The genotype planes of N >= 2 diploid individuals (impop_genotypes_create): pairs = [N, 2] haplotype indices as
+        diploid_scan takes them.  The handle owns its memory; this matrix may be freed afterwards."""
+        pr = np.asarray(pairs)
+        if pr.size and (pr.ndim != 2 or pr.shape[1] != 2):
+            raise ValueError("pairs must be [N, 2] haplotype indices")
+        if pr.size and (pr.min() < 0 or pr.max() > 0xFFFFFFFF):
+            raise ValueError("haplotype index outside 0 .. 2^32 - 1")
+        pr = np.ascontiguousarray(pr.reshape(-1, 2), dtype=np.uint32)
+        out = C.c_void_p()
+        check(self.ctx._lib.impop_genotypes_create(self.ctx.handle, self.handle, pr.ctypes.data_as(C.POINTER(C.c_uint32)), len(pr),
+                                                   C.byref(out)))
+        return Genotypes(self.ctx, out)
+
     def cluster_scan(self, windows, mask_p=None, kind: str = "match", threshold: float = 1.0, round_digits: Optional[int] = None,
                      want_members: bool = True):
         """af.cluster (af.py:35-54) per window from the bit matrix (impop_cluster_scan): components of
@@ -969,6 +995,69 @@ class BitMatrix:
         check(self.ctx._lib.impop_ehh_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(EhhWindow)), len(w), ptr,
                                            C.byref(prm), out.ctypes.data_as(C.POINTER(EhhStats))))
         return out
+
+
+class Genotypes:
+    """Per-individual genotype planes H = h1 ^ h2 and A = h1 & h2 resident in HBM (impop_genotypes)."""
+
+    def __init__(self, ctx: Context, handle):
+        self.ctx = ctx
+        self._h = handle
+        n, s, b = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        check(ctx._lib.impop_genotypes_info(handle, C.byref(n), C.byref(s), C.byref(b)))
+        self.n_ind, self.n_site, self.device_bytes = n.value, s.value, b.value
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise ImpopError(_lib.E_INVALID, "genotypes are freed")
+        return self._h
+
+    def free(self) -> None:
+        if self._h:
+            check(self.ctx._lib.impop_genotypes_free(self.ctx.handle if self.ctx._h else None, self._h))
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def download(self, site_begin: int = 0, site_end: Optional[int] = None) -> np.ndarray:
+        """-> [2N, words] uint64: rows H_0 .. H_{N-1}, A_0 .. A_{N-1} of the plane sites [site_begin, site_end), bit k of a row =
+        site site_begin + k."""
+        site_end = self.n_site if site_end is None else site_end
+        words = max((site_end - site_begin + 63) // 64, 1)
+        out = np.zeros((2 * self.n_ind, words), dtype=np.uint64)
+        check(self.ctx._lib.impop_genotypes_download(self.ctx.handle, self.handle, int(site_begin), int(site_end),
+                                                     out.ctypes.data_as(C.POINTER(C.c_uint64)), words))
+        return out
+
+    def kinship_scan(self, windows, kin=(884, 10000), watch=None, want_pairs: bool = True):
+        """Joint genotype tables and KING kinship of every pair of individuals per window (impop_kinship_scan).  kin = (num, den):
+        a pair is related in a window when its KING-robust kinship is at least num / den.  watch: [n_watch, 2] individual indices.
+        -> (windows KIN_WINDOW_DTYPE [n_windows], pairs KIN_PAIR_DTYPE [N(N-1)/2] summed over the windows, in the pair order of
+        scan_multi, or None, watch rows KIN_WATCH_DTYPE [n_windows, n_watch] or None)."""
+        w = make_windows(windows)
+        N = self.n_ind
+        wa = np.zeros((0, 2), np.uint32) if watch is None else np.asarray(watch)
+        if wa.size and (wa.ndim != 2 or wa.shape[1] != 2):
+            raise ValueError("watch must be [n_watch, 2] individual indices")
+        if wa.size and (wa.min() < 0 or wa.max() > 0xFFFFFFFF):
+            raise ValueError("individual index outside 0 .. 2^32 - 1")
+        wa = np.ascontiguousarray(wa.reshape(-1, 2), dtype=np.uint32)
+        nw = len(wa)
+        out = np.zeros(len(w), dtype=KIN_WINDOW_DTYPE)
+        pairs = np.zeros(N * (N - 1) // 2, dtype=KIN_PAIR_DTYPE) if want_pairs else None
+        rows = np.zeros((len(w), nw), dtype=KIN_WATCH_DTYPE) if nw else None
+        prm = _lib.KinshipParams(C.sizeof(_lib.KinshipParams), int(kin[0]), int(kin[1]), 0)
+        check(self.ctx._lib.impop_kinship_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), C.byref(prm),
+                                               wa.ctypes.data_as(C.POINTER(C.c_uint32)) if nw else None, nw,
+                                               out.ctypes.data_as(C.POINTER(_lib.KinWindow)),
+                                               pairs.ctypes.data_as(C.POINTER(_lib.KinPair)) if want_pairs else None,
+                                               rows.ctypes.data_as(C.POINTER(_lib.KinWatch)) if nw else None))
+        return out, pairs, rows
 
 
 class ScanPlan:

@@ -551,6 +551,74 @@ int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const impop_windo
                         const uint64_t *masks, uint32_t n_pop, const impop_pairdist_params *params,
                         impop_dist_panel *out_panels, impop_dist_pair *out_pairs /* nullable */,
                         uint32_t *hist_within /* nullable */, uint32_t *hist_between /* nullable */);
+#define IMPOP_KINSHIP_MAX_N 2048u        /* individuals of a genotype handle */
+#define IMPOP_KINSHIP_MAX_WATCH 1024u    /* watched pairs of a call */
+/* A PAIR OF INDIVIDUALS per window: the 3 x 3 joint genotype table and KING kinship of every pair of diploid individuals, from the
+ * Gram pass of impop_pairwise_scan.  Exact integers throughout.
+ * Genotype planes.  impop_genotypes_create pairs haplotypes into individuals as impop_diploid_scan does (pairs: h1, h2 per
+ * individual) and builds, on the device and from the source's site-major rows alone (the source need not have kept its hap-major
+ * copy), two bit planes per individual over the sites: H_i = h1 ^ h2 (heterozygous) and A_i = h1 & h2 (homozygous for the allele).
+ * The handle holds them as a 2N-row operand of the Gram kernel — rows H_0 .. H_{N-1}, A_0 .. A_{N-1}, stored as given (no polarity
+ * row), sites beyond n_site zero — and owns all its memory: the source may be freed afterwards.  Swapping h1 and h2 changes nothing.
+ * A compacted source gives compacted planes over the same kept sites (positions and the bitmap of the dropped all-ones sites are
+ * copied); a source with site weights returns IMPOP_E_UNSUPPORTED: a site is a column here.  An index >= n_hap, h1 == h2, a
+ * haplotype in two pairs and n_ind < 2 return IMPOP_E_INVALID, n_ind > IMPOP_KINSHIP_MAX_N IMPOP_E_UNSUPPORTED, all before anything
+ * is allocated.  impop_genotypes_info: n_site = the sites the planes hold (kept sites when compacted).  impop_genotypes_download:
+ * 2N rows (H then A) of the plane sites [site_begin, site_end), bit s - site_begin of a row = site s, like impop_matrix_download.
+ * The scan.  Per window and pair i < j, with g = 0 hom-ref, 1 het, 2 hom-alt, t[a][b] = the sites where g_i = a and g_j = b.  From
+ * the Gram entries HH = |H_i & H_j|, HA = |H_i & A_j|, AH = |A_i & H_j|, AA = |A_i & A_j| and the diagonals het = |H|, alt = |A|:
+ *     t11 = HH  t12 = HA  t21 = AH  t22 = AA  t10 = het_i - HH - HA  t01 = het_j - HH - AH  t20 = alt_i - AH - AA
+ *     t02 = alt_j - HA - AA  t00 = W - (the other eight)
+ * On compacted planes the window's dropped all-ones sites count in alt_i, alt_j and AA alone.  het_het = t11, ibs0 = t02 + t20,
+ * ibs1 = t01 + t10 + t12 + t21, ibs2 = t00 + t11 + t22.  A cell that would come out negative sets the device error word: the call
+ * returns IMPOP_E_INTERNAL with no partial results, like impop_pairwise_scan.
+ * out_windows: one impop_kin_window per window; its sums run over all N(N-1)/2 pairs.  With m = min(het_i, het_j), a pair is
+ * UNDEFINED in a window when m = 0 and RELATED when m > 0 and
+ *     kin_den * (2 (het_het - 2 ibs0) + 2 m - het_i - het_j) >= 4 m kin_num          (int64, exact)
+ * i.e. KING-robust kinship >= kin_num / kin_den (1 <= kin_den <= 2^20, 0 <= kin_num <= kin_den; else IMPOP_E_INVALID).
+ * out_pairs (nullable): N(N-1)/2 records in the pair order of impop_scan_multi — (0,1),(0,2),..,(1,2),.. — each the nine cells
+ * t[0][0], t[0][1], .., t[2][2] SUMMED OVER THE CALL'S WINDOWS; overlapping windows count as often as they occur.  One thread owns
+ * an entry across a chunk's windows and adds integers: identical bytes from call to call.
+ * out_watch (nullable with watch): n_windows x n_watch records, for the n_watch <= IMPOP_KINSHIP_MAX_WATCH listed pairs (i, j) of
+ * individuals, in any order of i and j (het_i belongs to the first): local relatedness along the chromosome.  i == j, an index >=
+ * N or n_watch above the limit return IMPOP_E_INVALID.
+ * n_windows == 0 returns IMPOP_OK; windows may overlap and may be empty (every cell 0).  Chunking (IMPOP_PAIRWISE_CHUNK), uint16 or
+ * int32 Gram counts, the Gram chain length, compaction of the source and the order of h1, h2 inside a pair never change a byte.
+ * With impop_ctx_gram_timing on, impop_ctx_kinship_elapsed returns kernel_ms[0] = the plane builds, [1] = the epilogue kernels,
+ * chunks = chunks timed, next to the Gram time.  Under IMPOP_TRACE=1 one line per call on stderr:
+ *   [impop_kinship_scan] route=<dense|compact> individuals= rows= windows= chunks= launches= watch= plane_bytes=
+ * Known answer (the rows of impop_diploid_scan's): h0 = 100010, h1 = 000010, h2 = 110000, h3 = 100001, pairs (0,1), (2,3), one
+ * window [0, 6): genotypes g_0 = 1,0,0,0,2,0 and g_1 = 2,1,0,0,0,1, so t00 = 2, t01 = 2, t12 = 1, t20 = 1, the rest 0; het =
+ * (1, 2), het_het = 0, ibs0 = 1, ibs2 = 2; KING within-family (het_het - 2 ibs0) / (het_i + het_j) = -2/3, KING-robust = -5/4. */
+typedef struct impop_genotypes impop_genotypes;
+int impop_genotypes_create(impop_ctx *ctx, const impop_matrix *m, const uint32_t *pairs /* h1,h2 per individual */, uint32_t n_ind,
+                           impop_genotypes **out);
+int impop_genotypes_info(const impop_genotypes *g, uint32_t *n_ind, uint64_t *n_site, uint64_t *device_bytes);
+int impop_genotypes_download(impop_ctx *ctx, const impop_genotypes *g, uint64_t site_begin, uint64_t site_end,
+                             uint64_t *bits_row_major /* 2N rows: H then A */, uint64_t row_stride_words);
+int impop_genotypes_free(impop_ctx *ctx, impop_genotypes *g);
+typedef struct impop_kinship_params {
+    uint32_t struct_size;
+    uint32_t kin_num, kin_den;          /* related: KING-robust kinship >= kin_num / kin_den */
+    uint32_t reserved;
+} impop_kinship_params;
+typedef struct impop_kin_window {       /* 48 bytes, fixed layout: one per window */
+    uint32_t n_ind;                     /* N */
+    uint32_t n_sites;                   /* the window's W */
+    uint64_t n_pairs;                   /* N (N - 1) / 2 */
+    uint64_t het_het, ibs0, ibs2;       /* sums over all pairs */
+    uint32_t n_related, n_undefined;    /* pairs at or above the threshold | with min(het_i, het_j) = 0 */
+} impop_kin_window;
+typedef struct impop_kin_pair {         /* 72 bytes, fixed layout: one per pair, summed over the call's windows */
+    uint64_t t[9];                      /* t[3 a + b] */
+} impop_kin_pair;
+typedef struct impop_kin_watch {        /* 16 bytes, fixed layout: one per (window, watched pair) */
+    uint32_t het_het, ibs0, het_i, het_j;
+} impop_kin_watch;
+int impop_kinship_scan(impop_ctx *ctx, const impop_genotypes *g, const impop_window *windows, uint64_t n_windows,
+                       const impop_kinship_params *params, const uint32_t *watch /* 2 x n_watch individuals, nullable */,
+                       uint32_t n_watch, impop_kin_window *out_windows, impop_kin_pair *out_pairs /* nullable */,
+                       impop_kin_watch *out_watch /* nullable */);
 #define IMPOP_HAPLOTYPE_MAX_N 4096u
 /* Haplotype-frequency statistics per window from the stream impop_scan reads (no hap-major operand, no Gram; works on matrices
  * uploaded without IMPOP_KEEP_HAP_MAJOR, on compacted and on weighted ones).  Two members of P are the same haplotype in a window
@@ -945,6 +1013,9 @@ int impop_ctx_gram_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches)
 int impop_ctx_cluster_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
 /* ... and impop_pairdist_scan its distribution kernel: summed time and number of chunks since enable / reset. */
 int impop_ctx_pairdist_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
+/* ... and impop_genotypes_create its plane-build kernel, impop_kinship_scan its epilogue kernels: kernel_ms[0] = plane builds,
+ * [1] = epilogue, summed since enable / reset; chunks = chunks of impop_kinship_scan timed. */
+int impop_ctx_kinship_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks);
 /* Test aid: how many event pairs the four timers hold (created on first timed use, kept for reuse): sizes[0..2] = the
  * context's Gram / clustering / EHH timers, sizes[3] = the plan's (plan nullable: 0).  Nothing is created while timing is off. */
 int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]);

@@ -18,6 +18,7 @@ run_h-fst.sh:148 / run_tajd.sh:101 / run_fst_impg.sh:158) so plot_*_trend.R work
     impop_scan.py --matrix chr2.npz --bed cores.bed --format ihs [-u subset.txt] [--ihs-min-maf F] [--ihs-cutoff F] [--ihs-max-extend BP] [--ihs-max-extend-sites N] [--ihs-bins B] [--ihs-keep-edge] [--compact]   # iHS / nSL per site
     impop_scan.py --matrix chr2.npz --bed cores.bed --format xpehh --panel a.txt b.txt [--ihs-...] [--compact]   # XP-EHH / XP-nSL per site
     impop_scan.py --matrix chr2.npz --bed windows.bed --format ibs [-u subset.txt] [--ibs-min-sites N] [--ibs-pairs all|diploid] [--ibs-segments PATH] [--ibs-pair-table PATH]   # IBS tracts / ROH segments
+    impop_scan.py --matrix chr2.npz --bed windows.bed --format kinship [-u subset.txt] [--kin-threshold 0.0884] [--kin-pairs pairs.tsv] [--kin-watch sampleA,sampleB ...] [--kin-watch-table watch.tsv] [--compact]   # joint genotype tables, KING kinship per pair of samples
     impop_scan.py --matrix chr2.npz --bed windows.bed --format pairdist --panel a.txt b.txt [more.txt] [--pairdist-outgroup K] [--pairdist-panels panels.tsv] [--pairdist-hist hist.tsv --pairdist-bins B --pairdist-bin-width w] [--compact]   # d_min, G_min, S_nn, mismatch distributions
     impop_scan.py --matrix chr2.npz --bed windows.bed --format sfs --panel A.txt [B.txt ...] [--sfs-outgroup i] [--sfs-pair i,j]...   # spectra, neutrality tests
     impop_scan.py --matrix chr2.npz --bed windows.bed --format dstat --panel P1.txt P2.txt P3.txt O.txt [more.txt] [--quartet 1,2,3,4]...   # ABBA-BABA D, f4, f_d
@@ -106,6 +107,12 @@ the outgroup is split evenly).  --dstat-blocks N with --dstat-summary PATH write
 block-jackknife error: P1 P2 P3 O D D_SE D_Z F_D F_D_SE BLOCKS ABBA BABA.  Streams the scan index; --compact allowed.  One process, one
 GPU; not with --sim-list, -A / -B / -l / -u, --devices N, -t / -r.
 
+--format kinship (impop_kinship_scan): a pair of individuals.  The sequences of -u (default: all) are paired into samples as --format
+diploid pairs them; per BED row REGION LENGTH INDIVIDUALS PAIRS HET_HET IBS0 IBS2 RELATED UNDEFINED, the sums over all pairs of samples and
+the pairs whose KING-robust kinship in the row is at least --kin-threshold (UNDEFINED: a sample without a heterozygous site).  --kin-pairs
+PATH writes, per pair, the joint genotype counts summed over all rows and all --matrix files (integer sums on the host) with KING_WITHIN,
+KING_ROBUST, IBS_DIST, IBS0_FRAC and the DEGREE label of the usual cut points 0.354 / 0.177 / 0.0884 / 0.0442.  --kin-watch A,B with
+--kin-watch-table PATH follows pairs row by row.
 --format pairdist (impop_pairdist_scan): the distribution of the pairwise distances H per BED row, from one Gram pass for all --panel
 lists (1..8, disjoint).  Main table, one row per BED row and pair of lists: REGION LENGTH POP_A POP_B PAIRS DXY (mean H / LENGTH) DMIN
 DMIN_SEQ_A DMIN_SEQ_B (the closest pair of sequences) DMAX IDENTICAL (pairs with H = 0) GMIN SNN NN_SAME_A NN_SAME_B NN_OTHER_A
@@ -784,6 +791,122 @@ def scan_pairdist(args):
             fh.close()
 
 
+def kinship_refusal(args):
+    """what --format kinship does not combine with (one line each, exit 2, before any device is opened)"""
+    own = args.kin_threshold is not None or args.kin_pairs is not None or bool(args.kin_watch) or args.kin_watch_table is not None
+    if args.format != "kinship":
+        return "--kin-threshold / --kin-pairs / --kin-watch / --kin-watch-table belong to --format kinship" if own else None
+    if args.sim_list:
+        return "--format kinship scans a presence matrix (--matrix / --bed): not with --sim-list"
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        return "--format kinship is a one-process, one-GPU scan: not under torch.distributed.run"
+    if args.devices > 1:
+        return "--format kinship runs on one GPU: not with --devices N"
+    if args.pop_a or args.pop_b or args.panel or args.sample_list:
+        return "--format kinship pairs the sequences of -u (default: all): not with -A / -B / --panel / -l"
+    if args.threshold is not None or args.round_digits is not None or args.fst_round_digits is not None:
+        return "--format kinship counts genotypes: it has no -t / -r (the kinship threshold is --kin-threshold)"
+    if args.kin_threshold is not None and not 0.0 <= args.kin_threshold <= 1.0:
+        return "--kin-threshold takes a kinship in 0 .. 1"
+    if bool(args.kin_watch) != (args.kin_watch_table is not None):
+        return "--kin-watch sampleA,sampleB and --kin-watch-table PATH go together"
+    for spec in args.kin_watch or []:
+        parts = spec.split(",")
+        if len(parts) != 2 or not all(parts) or parts[0] == parts[1]:
+            return f"--kin-watch {spec}: two different sample names, as in sampleA,sampleB"
+    if len(args.kin_watch or []) > 1024:
+        return "--kin-watch: at most 1024 pairs per run"
+    return None
+
+
+def scan_kinship(args):
+    """--format kinship: one row per BED row to --output / stdout, the per-pair totals and the watch rows to their paths"""
+    from impop_amd import kinship as kin
+    from impop_amd.popnames import pair_haplotypes
+    if args.device is None:
+        args.device = 0
+    mats = {}
+    for p in args.matrix:
+        mf = load_matrix(p)
+        key = (mf.contig if mf.contig.startswith(args.region_prefix) else args.region_prefix + mf.contig) if mf.contig else ""
+        if key in mats:
+            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
+            sys.exit(2)
+        mats[key] = mf
+    if "" in mats and len(mats) > 1:
+        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
+        sys.exit(2)
+    per_mat = {}
+    for chrom, s, e in read_bed(args.bed, "kinship"):
+        full = chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
+        key = "" if "" in mats else full
+        if key not in mats:
+            print(f"Warning: Skipping region {full}:{s}-{e}: no matrix holds chromosome {chrom}", file=sys.stderr)
+            continue
+        per_mat.setdefault(key, []).append((f"{full}:{s}-{e}", s, e))
+    frac = kin.threshold_fraction(0.0884 if args.kin_threshold is None else args.kin_threshold)
+    out = open(args.output, "w") if args.output else sys.stdout
+    watch_fh = open(args.kin_watch_table, "w") if args.kin_watch_table else None
+    print("\t".join(kin.WINDOW_COLUMNS), file=out)
+    if watch_fh:
+        print("\t".join(kin.WATCH_COLUMNS), file=watch_fh)
+    samples, totals = None, None
+    for key, rows in per_mat.items():
+        mf = mats[key]
+        if mf.site_weight is not None:
+            print("Error: --format kinship: the matrix has site weights; a genotype is read per column", file=sys.stderr)
+            sys.exit(2)
+        names = list(mf.names)
+        chosen = None if not args.subset else [nm for nm, f in zip(names, flags_for(args.subset, names)) if f]
+        pairs, smp, unpaired = pair_haplotypes(names, chosen)
+        if unpaired:
+            print(f"Warning: --format kinship: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
+                  + " ".join(unpaired), file=sys.stderr)
+        if len(pairs) < 2:
+            print("Error: --format kinship: fewer than two samples with both of their haplotypes (sample#1#..., sample#2#...) among the "
+                  "sequences", file=sys.stderr)
+            sys.exit(2)
+        if samples is not None and list(smp) != samples:
+            print(f"Error: --format kinship: the matrix of {key} pairs other samples than the one before it; the per-pair totals need one "
+                  "set of samples", file=sys.stderr)
+            sys.exit(2)
+        samples = list(smp)
+        watch = []
+        for spec in args.kin_watch or []:
+            a, b = spec.split(",")
+            if a not in samples or b not in samples:
+                print(f"Error: --kin-watch {spec}: {a if a not in samples else b} is not one of the paired samples", file=sys.stderr)
+                sys.exit(2)
+            watch.append((samples.index(a), samples.index(b)))
+        wins = [mf.site_range(s, e) + (e - s,) for _, s, e in rows]
+        run = Runner(args, mf, wins, False, 0, 1, 0)
+        try:
+            g = run.bm.genotypes(pairs)
+            try:
+                recs, ptot, wrows = g.kinship_scan(run.local_wins, kin=frac, watch=watch or None, want_pairs=args.kin_pairs is not None)
+            finally:
+                g.free()
+        finally:
+            run.close()
+        if ptot is not None:  # integer sums on the host, over all rows and all matrices
+            t = [[int(x) for x in rec] for rec in ptot["t"]]
+            totals = t if totals is None else [[a + b for a, b in zip(ra, rb)] for ra, rb in zip(totals, t)]
+        main, _, wat = kin.tables([r[0] for r in rows], [e - s for _, s, e in rows], samples, recs, None, watch, wrows)
+        for fh, table in ((out, main), (watch_fh, wat)):
+            if fh:
+                for row in table:
+                    print("\t".join(row), file=fh)
+    if args.kin_pairs:
+        with open(args.kin_pairs, "w") as fh:
+            print("\t".join(kin.PAIR_COLUMNS), file=fh)
+            if totals is not None:
+                for row in kin.tables([], [], samples, [], totals)[1]:
+                    print("\t".join(row), file=fh)
+    for fh in (watch_fh, out if args.output else None):
+        if fh:
+            fh.close()
+
+
 def ihs_refusal(args):
     """what --format ihs / xpehh do not combine with (one line each, exit 2, before any device is opened)"""
     own = (args.ihs_min_maf is not None or args.ihs_cutoff is not None or args.ihs_max_extend is not None
@@ -1218,7 +1341,7 @@ def main():
                     "identity table per window (formats pica2, hfst, tajd, all)")
     ap.add_argument("--sim-threads", type=int, default=0, metavar="N", help="--sim-list: host threads that parse tables "
                     "(default: OMP_NUM_THREADS, else 16)")
-    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "pairdist", "ihs", "xpehh", "all"], default="all",
+    ap.add_argument("--format", choices=["pica2", "hfst", "tajd", "fst3pi", "af", "ehh", "hapstats", "ld", "diploid", "ibs", "dstat", "sfs", "pairdist", "kinship", "ihs", "xpehh", "all"], default="all",
                     help="fst3pi = the 3 x pi table of run_fst_impg.sh (needs -A and -B, disjoint); af = haplotype clusters per window "
                          "(scripts/af.py; not part of `all`); ehh = integrated EHH per core site (ehhgfa.py; not part of `all`); "
                          "hapstats = haplotype-frequency statistics per window (K, H1, H12, H2/H1, diversity; not part of `all`); "
@@ -1283,6 +1406,13 @@ def main():
     ap.add_argument("--pairdist-hist", metavar="PATH", help="pairdist: the distance histograms within every list and between every pair to "
                     "PATH, long form, non-zero bins only; needs --pairdist-bins")
     ap.add_argument("--pairdist-bins", type=int, default=None, metavar="B", help="pairdist: bins per histogram (1..1024); the last collects the overflow")
+    ap.add_argument("--kin-threshold", type=float, default=None, metavar="PHI", help="kinship: a pair counts as RELATED in a window when its "
+                    "KING-robust kinship is at least PHI (default 0.0884, the 2nd / 3rd degree cut; compared exactly as round(PHI * 10000) / 10000)")
+    ap.add_argument("--kin-pairs", metavar="PATH", help="kinship: the joint genotype counts of every pair of samples summed over all BED rows "
+                    "and all --matrix files to PATH, with KING within-family and robust kinship, the IBS distance and the degree label")
+    ap.add_argument("--kin-watch", action="append", default=None, metavar="A,B", help="kinship: also follow the pair of samples A,B row by "
+                    "row (repeatable, at most 1024); needs --kin-watch-table")
+    ap.add_argument("--kin-watch-table", metavar="PATH", help="kinship: one row per BED row and --kin-watch pair to PATH")
     ap.add_argument("--pairdist-bin-width", type=int, default=None, metavar="w", help="pairdist: distances per bin (default 1)")
     ap.add_argument("--panel", nargs="+", metavar="POP.txt", help="K = 2..8 disjoint population lists.  hfst: every pair (replaces "
                     "run_h_fst_panels.sh), one table per pair headed `# POP_A-vs-POP_B` - unrounded `match` in ONE streaming pass, with "
@@ -1317,12 +1447,14 @@ def main():
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
     refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or ibs_refusal(args) or dstat_refusal(args)
-               or sfs_refusal(args) or pairdist_refusal(args) or ihs_refusal(args))
+               or sfs_refusal(args) or pairdist_refusal(args) or kinship_refusal(args) or ihs_refusal(args))
     if refusal:
         print(f"Error: {refusal}", file=sys.stderr)
         sys.exit(2)
     if args.format == "pairdist":
         return scan_pairdist(args)
+    if args.format == "kinship":
+        return scan_kinship(args)
     if args.format in ("ihs", "xpehh"):
         return scan_ihs(args)
     if args.sim_list:
