@@ -146,9 +146,11 @@ BED rows are matched to matrices by chromosome (run_pica2_impg.sh:139-151 builds
 a row whose chromosome no matrix holds is skipped with a warning.
 """
 import argparse
+import contextlib
 import math
 import os
 import sys
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -392,158 +394,16 @@ def write_tables(out, args, fmt, regions, L_col, col, s_all, samples_col, thr_tx
 
 
 AF_HEADER = "REGION\tLENGTH\tTHRESHOLD\tHAPLOTYPES\tCLUSTERS\tLARGEST\tSINGLETONS\tHOMOZYGOSITY"
-
-
-def af_refusal(args):
-    """what --format af does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "af":
-        if args.af_clusters or args.af_details:
-            return "--af-clusters / --af-details belong to --format af"
-        return None
-    if args.sim_list:
-        return "--format af scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format af is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format af runs on one GPU: not with --devices N"
-    if args.panel or args.pop_a or args.pop_b or args.sample_list:
-        return "--format af clusters the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    return None
-
-
 EHH_HEADER = "REGION\tLENGTH\tCORE\tALLELE\tREF_ALT\tN_HAPLOTYPES\tAREA\tIHH_LEFT\tIHH_RIGHT"
-
-
-def ehh_refusal(args):
-    """what --format ehh does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "ehh":
-        if args.ehh_core_offset is not None or args.ehh_cores or args.ehh_flanks is not None or args.ehh_ref is not None:
-            return "--ehh-core-offset / --ehh-cores / --ehh-flanks / --ehh-ref belong to --format ehh"
-        return None
-    if args.sim_list:
-        return "--format ehh scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format ehh is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format ehh runs on one GPU: not with --devices N"
-    if args.panel or args.pop_a or args.pop_b or args.sample_list or args.compact:
-        return "--format ehh scans the sequences of -u (default: all) on the full matrix: not with -A / -B / --panel / -l / --compact"
-    if args.ehh_core_offset is not None and args.ehh_cores:
-        return "give --ehh-core-offset or --ehh-cores, not both"
-    if args.ehh_core_offset is not None and args.ehh_core_offset < 0:
-        return "--ehh-core-offset is a 0-based offset into the window (>= 0)"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    return None
-
-
 HAP_HEADER = "REGION\tLENGTH\tSAMPLES\tSITES\tHAPLOTYPES\tH1\tH12\tH2_H1\tHAP_DIVERSITY"
-
-
-def hap_refusal(args):
-    """what --format hapstats does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "hapstats":
-        return None
-    if args.sim_list:
-        return "--format hapstats scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format hapstats is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format hapstats runs on one GPU: not with --devices N"
-    if args.panel or args.pop_a or args.pop_b or args.sample_list:
-        return "--format hapstats compares the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    return None
-
-
 LD_HEADER = "REGION\tLENGTH\tSAMPLES\tSITES\tQUALIFYING\tUSED\tZNS\tMEAN_DPRIME\tPERFECT\tCOMPLETE\tOMEGA_MAX\tOMEGA_POS"
-
-
-def ld_refusal(args):
-    """what --format ld does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "ld":
-        if args.ld_min_maf is not None or args.ld_max_sites is not None:
-            return "--ld-min-maf / --ld-max-sites belong to --format ld"
-        return None
-    if args.sim_list:
-        return "--format ld scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format ld is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format ld runs on one GPU: not with --devices N"
-    if args.panel or args.pop_a or args.pop_b or args.sample_list:
-        return "--format ld compares the sites among the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    if args.ld_min_maf is not None and not 0.0 <= args.ld_min_maf <= 0.5:
-        return "--ld-min-maf is a minor-allele frequency (0 .. 0.5)"
-    if args.ld_max_sites is not None and not 4 <= args.ld_max_sites <= 1024:
-        return "--ld-max-sites takes 4 .. 1024"
-    return None
-
-
 DIPLOID_HEADER = "CHROM\tSTART\tEND\tN_IND\tSITES\tHET_SITES\tHO\tHE\tFIS\tROH_RUNS\tF_ROH\tLONGEST_RUN"
 DIPLOID_IND_HEADER = "CHROM\tSTART\tEND\tSAMPLE\tHET\tHOM_ALT\tLONGEST_RUN\tROH_RUNS\tROH_SITES"
-
-
-def diploid_refusal(args):
-    """what --format diploid does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "diploid":
-        if args.roh_min_sites is not None or args.ind_table is not None:
-            return "--roh-min-sites / --ind-table belong to --format diploid"
-        return None
-    if args.sim_list:
-        return "--format diploid scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format diploid is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format diploid runs on one GPU: not with --devices N"
-    if args.panel or args.pop_a or args.pop_b or args.sample_list:
-        return "--format diploid pairs the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    if args.roh_min_sites is not None and args.roh_min_sites < 1:
-        return "--roh-min-sites takes 1 or more"
-    return None
 
 
 IBS_HEADER = "REGION\tLENGTH\tPAIRS\tTRACTS\tPAIRS_SPANNING\tPAIR_SITES\tSHARE"
 IBS_SEGMENT_HEADER = "seq1\tseq2\tstart\tend\tsites\topen"
 IBS_PAIR_HEADER = "SEQ1\tSEQ2\tN_DIFF\tLONGEST\tTRACTS\tTRACT_SITES"
-
-
-def ibs_refusal(args):
-    """what --format ibs does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "ibs":
-        if args.ibs_min_sites is not None or args.ibs_pairs is not None or args.ibs_segments is not None or args.ibs_pair_table is not None:
-            return "--ibs-min-sites / --ibs-pairs / --ibs-segments / --ibs-pair-table belong to --format ibs"
-        return None
-    if args.sim_list:
-        return "--format ibs scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format ibs is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format ibs runs on one GPU: not with --devices N"
-    if args.panel or args.pop_a or args.pop_b or args.sample_list:
-        return "--format ibs pairs the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    if args.ibs_min_sites is not None and args.ibs_min_sites < 1:
-        return "--ibs-min-sites takes 1 or more"
-    return None
 
 
 def write_ibs_table(out, regions, L_col, n_pairs, recs):
@@ -600,37 +460,6 @@ def parse_quartets(specs, n_panel):
     return out
 
 
-def dstat_refusal(args):
-    """what --format dstat does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "dstat":
-        if args.quartet or args.dstat_polarize or args.dstat_blocks is not None or args.dstat_summary is not None:
-            return "--quartet / --dstat-polarize / --dstat-blocks / --dstat-summary belong to --format dstat"
-        return None
-    if args.sim_list:
-        return "--format dstat scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format dstat is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format dstat runs on one GPU: not with --devices N"
-    if not args.panel or not 4 <= len(args.panel) <= 8:
-        return "--format dstat takes --panel P1.txt P2.txt P3.txt O.txt [more lists]: 4 to 8 population lists"
-    if args.pop_a or args.pop_b or args.sample_list or args.subset:
-        return "--format dstat compares the populations of --panel: not with -A / -B / -l / -u"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    if (args.dstat_blocks is None) != (args.dstat_summary is None):
-        return "--dstat-blocks N and --dstat-summary PATH go together"
-    if args.dstat_blocks is not None and args.dstat_blocks < 1:
-        return "--dstat-blocks takes 1 or more"
-    try:
-        parse_quartets(args.quartet, len(args.panel))
-    except ValueError as e:
-        return str(e)
-    return None
-
-
 SFS_HEADER = ("CHROM\tSTART\tEND\tPOP\tN\tN_SITES\tS\tETA1\tETA_N1\tN_SKIPPED\tTHETA_W\tTHETA_PI\tTHETA_H\tTHETA_L\tTAJIMA_D\tFAYWU_H\t"
               "FAYWU_H_NORM\tZENG_E")
 SFS_PAIRS_HEADER = "CHROM\tSTART\tEND\tPOP_A\tPOP_B\tPRIVATE_A\tPRIVATE_B\tSHARED\tFIXED_A\tFIXED_B\tN_UNION"
@@ -659,288 +488,6 @@ def parse_sfs_pairs(specs, n_panel):
     return out
 
 
-def sfs_refusal(args):
-    """what --format sfs does not combine with (one line each, exit 2, before any device is opened)"""
-    if args.format != "sfs":
-        if (args.sfs_outgroup is not None or args.sfs_pair or args.sfs_pairs_out is not None or args.sfs_spectra is not None
-                or args.sfs_blocks is not None):
-            return "--sfs-outgroup / --sfs-pair / --sfs-pairs-out / --sfs-spectra / --sfs-blocks belong to --format sfs"
-        return None
-    if args.sim_list:
-        return "--format sfs scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format sfs is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format sfs runs on one GPU: not with --devices N"
-    if not args.panel or not 1 <= len(args.panel) <= 8:
-        return "--format sfs takes --panel A.txt [B.txt ...]: 1 to 8 population lists"
-    if args.pop_a or args.pop_b or args.sample_list or args.subset:
-        return "--format sfs reads the spectra of the populations of --panel: not with -A / -B / -l / -u"
-    if args.threshold is not None or args.round_digits is not None or args.identity != "match":
-        return "-t / -r / --identity belong to other formats"
-    if args.fst_method != "direct" or args.fst_round_digits is not None or args.sequence_length is not None:
-        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
-    if args.sfs_outgroup is not None and not 1 <= args.sfs_outgroup <= len(args.panel):
-        return f"--sfs-outgroup {args.sfs_outgroup}: position is outside the {len(args.panel)} lists of --panel"
-    if args.sfs_blocks is not None and args.sfs_spectra is None:
-        return "--sfs-blocks N belongs to --sfs-spectra PATH.npz"
-    if args.sfs_blocks is not None and args.sfs_blocks < 1:
-        return "--sfs-blocks takes 1 or more"
-    try:
-        parse_sfs_pairs(args.sfs_pair, len(args.panel))
-    except ValueError as e:
-        return str(e)
-    if args.sfs_pairs_out is not None and not args.sfs_pair:
-        return "--sfs-pairs-out PATH needs at least one --sfs-pair i,j"
-    if args.sfs_pair and args.sfs_pairs_out is None and args.sfs_spectra is None:
-        return "--sfs-pair i,j goes with --sfs-pairs-out PATH or --sfs-spectra PATH.npz"
-    return None
-
-
-def pairdist_refusal(args):
-    """what --format pairdist does not combine with (one line each, exit 2, before any device is opened)"""
-    own = (args.pairdist_outgroup is not None or args.pairdist_panels is not None or args.pairdist_hist is not None
-           or args.pairdist_bins is not None or args.pairdist_bin_width is not None)
-    if args.format != "pairdist":
-        return "--pairdist-outgroup / --pairdist-panels / --pairdist-hist / --pairdist-bins / --pairdist-bin-width belong to --format pairdist" if own else None
-    if args.sim_list:
-        return "--format pairdist scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format pairdist is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format pairdist runs on one GPU: not with --devices N"
-    if not args.panel or not 1 <= len(args.panel) <= 8:
-        return "--format pairdist takes --panel a.txt b.txt [more.txt]: 1 to 8 population lists"
-    if args.pop_a or args.pop_b or args.sample_list or args.subset:
-        return "--format pairdist reads the distances of the populations of --panel: not with -A / -B / -l / -u"
-    if args.threshold is not None or args.round_digits is not None or args.fst_round_digits is not None:
-        return "--format pairdist counts differing sites: it has no -t / -r"
-    if args.pairdist_outgroup is not None and not (len(args.panel) >= 3 and 1 <= args.pairdist_outgroup <= len(args.panel)):
-        return f"--pairdist-outgroup {args.pairdist_outgroup}: a 1-based position among at least three lists of --panel"
-    if (args.pairdist_bins is not None or args.pairdist_bin_width is not None) and args.pairdist_hist is None:
-        return "--pairdist-bins / --pairdist-bin-width belong to --pairdist-hist PATH"
-    if args.pairdist_hist is not None and args.pairdist_bins is None:
-        return "--pairdist-hist PATH needs --pairdist-bins B"
-    if args.pairdist_bins is not None and not 1 <= args.pairdist_bins <= 1024:
-        return "--pairdist-bins takes 1 to 1024"
-    if args.pairdist_bin_width is not None and args.pairdist_bin_width < 1:
-        return "--pairdist-bin-width takes 1 or more"
-    return None
-
-
-def scan_pairdist(args):
-    """--format pairdist: the main table to --output / stdout, the side tables to their paths"""
-    from impop_amd import pairdist as pd
-    if args.device is None:
-        args.device = 0
-    mats = {}
-    for p in args.matrix:
-        mf = load_matrix(p)
-        key = (mf.contig if mf.contig.startswith(args.region_prefix) else args.region_prefix + mf.contig) if mf.contig else ""
-        if key in mats:
-            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
-            sys.exit(2)
-        mats[key] = mf
-    if "" in mats and len(mats) > 1:
-        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
-        sys.exit(2)
-    per_mat = {}
-    for chrom, s, e in read_bed(args.bed, "pairdist"):
-        full = chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
-        key = "" if "" in mats else full
-        if key not in mats:
-            print(f"Warning: Skipping region {full}:{s}-{e}: no matrix holds chromosome {chrom}", file=sys.stderr)
-            continue
-        per_mat.setdefault(key, []).append((f"{full}:{s}-{e}", s, e))
-    labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
-    bins = args.pairdist_bins or 0
-    width = args.pairdist_bin_width or 1
-    og = None if args.pairdist_outgroup is None else args.pairdist_outgroup - 1
-    out = open(args.output, "w") if args.output else sys.stdout
-    pan_fh = open(args.pairdist_panels, "w") if args.pairdist_panels else None
-    hist_fh = open(args.pairdist_hist, "w") if args.pairdist_hist else None
-    print("\t".join(pd.MAIN_COLUMNS + (["RNDMIN"] if og is not None else [])), file=out)
-    if pan_fh:
-        print("\t".join(pd.PANEL_COLUMNS), file=pan_fh)
-    if hist_fh:
-        print("\t".join(pd.HIST_COLUMNS), file=hist_fh)
-    for key, rows in per_mat.items():
-        mf = mats[key]
-        pops = [flags_for(f, mf.names) for f in args.panel]
-        for k, f in enumerate(pops):  # what impop_pairdist_scan would refuse, with the lists' names
-            if not f.any():
-                print(f"Error: --format pairdist: {labels[k]} selects no sequence of the matrix", file=sys.stderr)
-                sys.exit(2)
-            for l in range(k):
-                if (pops[l] & f).any():
-                    print(f"Error: --format pairdist: {labels[l]} and {labels[k]} share a sequence; the lists must be disjoint", file=sys.stderr)
-                    sys.exit(2)
-        wins = [mf.site_range(s, e) + (e - s,) for _, s, e in rows]
-        run = Runner(args, mf, wins, True, 0, 1, 0)
-        try:
-            panels, pairs, hw, hb = run.bm.pairdist_scan(run.local_wins, pops, hist_bins=bins, hist_width=width)
-        finally:
-            run.close()
-        main, pan, hist = pd.tables([r[0] for r in rows], [e - s for _, s, e in rows], labels, list(mf.names), panels, pairs, hw, hb, outgroup=og)
-        for fh, table in ((out, main), (pan_fh, pan), (hist_fh, hist)):
-            if fh:
-                for row in table:
-                    print("\t".join(row), file=fh)
-    for fh in (pan_fh, hist_fh, out if args.output else None):
-        if fh:
-            fh.close()
-
-
-def kinship_refusal(args):
-    """what --format kinship does not combine with (one line each, exit 2, before any device is opened)"""
-    own = args.kin_threshold is not None or args.kin_pairs is not None or bool(args.kin_watch) or args.kin_watch_table is not None
-    if args.format != "kinship":
-        return "--kin-threshold / --kin-pairs / --kin-watch / --kin-watch-table belong to --format kinship" if own else None
-    if args.sim_list:
-        return "--format kinship scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return "--format kinship is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return "--format kinship runs on one GPU: not with --devices N"
-    if args.pop_a or args.pop_b or args.panel or args.sample_list:
-        return "--format kinship pairs the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.threshold is not None or args.round_digits is not None or args.fst_round_digits is not None:
-        return "--format kinship counts genotypes: it has no -t / -r (the kinship threshold is --kin-threshold)"
-    if args.kin_threshold is not None and not 0.0 <= args.kin_threshold <= 1.0:
-        return "--kin-threshold takes a kinship in 0 .. 1"
-    if bool(args.kin_watch) != (args.kin_watch_table is not None):
-        return "--kin-watch sampleA,sampleB and --kin-watch-table PATH go together"
-    for spec in args.kin_watch or []:
-        parts = spec.split(",")
-        if len(parts) != 2 or not all(parts) or parts[0] == parts[1]:
-            return f"--kin-watch {spec}: two different sample names, as in sampleA,sampleB"
-    if len(args.kin_watch or []) > 1024:
-        return "--kin-watch: at most 1024 pairs per run"
-    return None
-
-
-def scan_kinship(args):
-    """--format kinship: one row per BED row to --output / stdout, the per-pair totals and the watch rows to their paths"""
-    from impop_amd import kinship as kin
-    from impop_amd.popnames import pair_haplotypes
-    if args.device is None:
-        args.device = 0
-    mats = {}
-    for p in args.matrix:
-        mf = load_matrix(p)
-        key = (mf.contig if mf.contig.startswith(args.region_prefix) else args.region_prefix + mf.contig) if mf.contig else ""
-        if key in mats:
-            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
-            sys.exit(2)
-        mats[key] = mf
-    if "" in mats and len(mats) > 1:
-        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
-        sys.exit(2)
-    per_mat = {}
-    for chrom, s, e in read_bed(args.bed, "kinship"):
-        full = chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
-        key = "" if "" in mats else full
-        if key not in mats:
-            print(f"Warning: Skipping region {full}:{s}-{e}: no matrix holds chromosome {chrom}", file=sys.stderr)
-            continue
-        per_mat.setdefault(key, []).append((f"{full}:{s}-{e}", s, e))
-    frac = kin.threshold_fraction(0.0884 if args.kin_threshold is None else args.kin_threshold)
-    out = open(args.output, "w") if args.output else sys.stdout
-    watch_fh = open(args.kin_watch_table, "w") if args.kin_watch_table else None
-    print("\t".join(kin.WINDOW_COLUMNS), file=out)
-    if watch_fh:
-        print("\t".join(kin.WATCH_COLUMNS), file=watch_fh)
-    samples, totals = None, None
-    for key, rows in per_mat.items():
-        mf = mats[key]
-        if mf.site_weight is not None:
-            print("Error: --format kinship: the matrix has site weights; a genotype is read per column", file=sys.stderr)
-            sys.exit(2)
-        names = list(mf.names)
-        chosen = None if not args.subset else [nm for nm, f in zip(names, flags_for(args.subset, names)) if f]
-        pairs, smp, unpaired = pair_haplotypes(names, chosen)
-        if unpaired:
-            print(f"Warning: --format kinship: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
-                  + " ".join(unpaired), file=sys.stderr)
-        if len(pairs) < 2:
-            print("Error: --format kinship: fewer than two samples with both of their haplotypes (sample#1#..., sample#2#...) among the "
-                  "sequences", file=sys.stderr)
-            sys.exit(2)
-        if samples is not None and list(smp) != samples:
-            print(f"Error: --format kinship: the matrix of {key} pairs other samples than the one before it; the per-pair totals need one "
-                  "set of samples", file=sys.stderr)
-            sys.exit(2)
-        samples = list(smp)
-        watch = []
-        for spec in args.kin_watch or []:
-            a, b = spec.split(",")
-            if a not in samples or b not in samples:
-                print(f"Error: --kin-watch {spec}: {a if a not in samples else b} is not one of the paired samples", file=sys.stderr)
-                sys.exit(2)
-            watch.append((samples.index(a), samples.index(b)))
-        wins = [mf.site_range(s, e) + (e - s,) for _, s, e in rows]
-        run = Runner(args, mf, wins, False, 0, 1, 0)
-        try:
-            g = run.bm.genotypes(pairs)
-            try:
-                recs, ptot, wrows = g.kinship_scan(run.local_wins, kin=frac, watch=watch or None, want_pairs=args.kin_pairs is not None)
-            finally:
-                g.free()
-        finally:
-            run.close()
-        if ptot is not None:  # integer sums on the host, over all rows and all matrices
-            t = [[int(x) for x in rec] for rec in ptot["t"]]
-            totals = t if totals is None else [[a + b for a, b in zip(ra, rb)] for ra, rb in zip(totals, t)]
-        main, _, wat = kin.tables([r[0] for r in rows], [e - s for _, s, e in rows], samples, recs, None, watch, wrows)
-        for fh, table in ((out, main), (watch_fh, wat)):
-            if fh:
-                for row in table:
-                    print("\t".join(row), file=fh)
-    if args.kin_pairs:
-        with open(args.kin_pairs, "w") as fh:
-            print("\t".join(kin.PAIR_COLUMNS), file=fh)
-            if totals is not None:
-                for row in kin.tables([], [], samples, [], totals)[1]:
-                    print("\t".join(row), file=fh)
-    for fh in (watch_fh, out if args.output else None):
-        if fh:
-            fh.close()
-
-
-def ihs_refusal(args):
-    """what --format ihs / xpehh do not combine with (one line each, exit 2, before any device is opened)"""
-    own = (args.ihs_min_maf is not None or args.ihs_cutoff is not None or args.ihs_max_extend is not None
-           or args.ihs_max_extend_sites is not None or args.ihs_bins is not None or args.ihs_keep_edge)
-    if args.format not in ("ihs", "xpehh"):
-        return ("--ihs-min-maf / --ihs-cutoff / --ihs-max-extend / --ihs-max-extend-sites / --ihs-bins / --ihs-keep-edge belong to "
-                "--format ihs and --format xpehh") if own else None
-    f = f"--format {args.format}"
-    if args.sim_list:
-        return f"{f} scans a presence matrix (--matrix / --bed): not with --sim-list"
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        return f"{f} is a one-process, one-GPU scan: not under torch.distributed.run"
-    if args.devices > 1:
-        return f"{f} runs on one GPU: not with --devices N"
-    if args.threshold is not None or args.round_digits is not None or args.fst_round_digits is not None:
-        return f"{f} integrates haplotype homozygosity: it has no -t / -r"
-    if args.format == "ihs" and (args.pop_a or args.pop_b or args.panel or args.sample_list):
-        return "--format ihs scans the sequences of -u (default: all): not with -A / -B / --panel / -l"
-    if args.format == "xpehh":
-        if not args.panel or len(args.panel) != 2:
-            return "--format xpehh takes --panel a.txt b.txt: two population lists"
-        if args.pop_a or args.pop_b or args.sample_list or args.subset:
-            return "--format xpehh compares the two populations of --panel: not with -A / -B / -l / -u"
-    if args.ihs_min_maf is not None and not 0.0 < args.ihs_min_maf <= 0.5:
-        return "--ihs-min-maf takes a frequency above 0, at most 0.5"
-    if args.ihs_cutoff is not None and not 0.0 <= args.ihs_cutoff <= 1.0:
-        return "--ihs-cutoff takes 0 to 1"
-    if (args.ihs_max_extend is not None and args.ihs_max_extend < 0) or (args.ihs_max_extend_sites is not None and args.ihs_max_extend_sites < 0):
-        return "--ihs-max-extend / --ihs-max-extend-sites take 0 (no limit) or more"
-    if args.ihs_bins is not None and args.ihs_bins < 1:
-        return "--ihs-bins takes 1 or more"
-    return None
-
-
 IHS_HEADER = "CHROM\tSITE\tN0\tN1\tFREQ1\tIHH0\tIHH1\tIHS\tIHS_STD\tSL0\tSL1\tNSL\tNSL_STD\tFLAGS"
 XPEHH_HEADER = "CHROM\tSITE\tNA\tNB\tFREQ1_A\tFREQ1_B\tIHH_A\tIHH_B\tXPEHH\tXPEHH_STD\tSL_A\tSL_B\tXPNSL\tXPNSL_STD\tFLAGS"
 
@@ -962,76 +509,6 @@ def write_ihs_table(out, K, chroms, bps, rec, bins, keep_edge):
         fr = num(v["freq1"][i]) if K == 1 else f"{int(r['c1'][0]) / n0:.8f}\t{int(r['c1'][1]) / n1:.8f}"
         print(f"{chroms[i]}\t{bps[i]}\t{n0}\t{n1}\t{fr}\t{num(v['ihh'][i, 0])}\t{num(v['ihh'][i, 1])}\t{num(v[first][i])}\t{num(std[0][i])}\t"
               f"{num(v['sl'][i, 0])}\t{num(v['sl'][i, 1])}\t{num(v[second][i])}\t{num(std[1][i])}\t{int(r['flags'])}", file=out)
-
-
-def scan_ihs(args):
-    """--format ihs / xpehh: one impop_ihs_scan per BED row over its contig's whole matrix, the row's sites as cores; the scores are
-    standardised over all rows of the run and the table goes to --output / stdout"""
-    import math
-    from impop_amd import ihs as ih
-    K = 2 if args.format == "xpehh" else 1
-    if args.device is None:
-        args.device = 0
-    mats = {}
-    for p in args.matrix:
-        mf = load_matrix(p)
-        key = (mf.contig if mf.contig.startswith(args.region_prefix) else args.region_prefix + mf.contig) if mf.contig else ""
-        if key in mats:
-            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
-            sys.exit(2)
-        mats[key] = mf
-    if "" in mats and len(mats) > 1:
-        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
-        sys.exit(2)
-    per_mat = {}
-    for chrom, s, e in read_bed(args.bed, args.format):
-        full = chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
-        key = "" if "" in mats else full
-        if key not in mats:
-            print(f"Warning: Skipping region {full}:{s}-{e}: no matrix holds chromosome {chrom}", file=sys.stderr)
-            continue
-        per_mat.setdefault(key, []).append((full, s, e))
-    maf = 0.05 if args.ihs_min_maf is None else args.ihs_min_maf
-    cutoff_milli = int(round(1000 * (0.05 if args.ihs_cutoff is None else args.ihs_cutoff)))
-    max_bp = 1000000 if args.ihs_max_extend is None else args.ihs_max_extend
-    max_sites = 100 if args.ihs_max_extend_sites is None else args.ihs_max_extend_sites
-    chroms, bps, recs = [], [], []
-    for key, rows in per_mat.items():
-        mf = mats[key]
-        if K == 2:
-            pops = [flags_for(f, mf.names) for f in args.panel]
-            if (pops[0] & pops[1]).any():
-                print("Error: --format xpehh: the two lists of --panel share a sequence; they must be disjoint", file=sys.stderr)
-                sys.exit(2)
-            if min(int(p.sum()) for p in pops) < 2:
-                print("Error: --format xpehh: each list of --panel needs at least two sequences of the matrix", file=sys.stderr)
-                sys.exit(2)
-            n_members = int(pops[0].sum() + pops[1].sum())
-        else:
-            pops = [flags_for(args.subset, mf.names) if args.subset else None, None]
-            n_members = mf.n_hap if pops[0] is None else int(pops[0].sum())
-            if n_members < 2:
-                print(f"Error: --format ihs: {n_members} sequences make no pair", file=sys.stderr)
-                sys.exit(2)
-        wins = [mf.site_range(s, e) + (e - s,) for _, s, e in rows]
-        run = Runner(args, mf, wins, False, 0, 1, 0)
-        site_bp = (lambda c, mf=mf: int(mf.site_pos[c])) if mf.site_pos is not None else (lambda c, mf=mf: int(mf.origin + c))
-        try:
-            for (full, _, _), (b, en, _) in zip(rows, wins):
-                if en <= b:
-                    continue
-                rec, _ = run.bm.ihs_scan(mask_a=pops[0], mask_b=pops[1], core_begin=b, core_end=en, min_mac=max(1, math.ceil(maf * n_members)),
-                                         cutoff_milli=cutoff_milli, max_extend_bp=max_bp, max_extend_sites=max_sites)
-                recs.append(rec)
-                chroms += [full] * len(rec)
-                bps += [site_bp(int(c)) for c in rec["site"]]
-        finally:
-            run.close()
-    out = open(args.output, "w") if args.output else sys.stdout
-    write_ihs_table(out, K, chroms, bps, np.concatenate(recs) if recs else np.zeros(0, dtype=ih.IHS_DTYPE),
-                    50 if args.ihs_bins is None else args.ihs_bins, args.ihs_keep_edge)
-    if args.output:
-        out.close()
 
 
 def sfs_row(region, label, n, r):
@@ -1249,15 +726,12 @@ def scan_sim_list(args, fmt, pica_t, pica_r, fst_r, thr_txt, r_txt):
             except ValueError:
                 ok = False
             if not ok:
-                print(f"Error: --format {fmt} with --sim-list needs a non-negative S column (row {row.chrom}:{row.start}-{row.end})",
-                      file=sys.stderr)
-                sys.exit(2)
+                fail(f"--format {fmt} with --sim-list needs a non-negative S column (row {row.chrom}:{row.start}-{row.end})")
     sample_count = None
     if args.sample_list:
         sample_count = awk_line_count(args.sample_list)  # run_tajd.sh:83
         if want_d and sample_count < 2:
-            print(f"Error: Need at least two samples to compute Tajima's D (found {sample_count})", file=sys.stderr)  # :84-87
-            sys.exit(1)
+            fail(f"Need at least two samples to compute Tajima's D (found {sample_count})", 1)  # :84-87
     pops, no_fst = None, set()
     NO_POP = "Error: No valid sequences found in one or both populations"
     if want_fst:
@@ -1331,6 +805,872 @@ def scan_sim_list(args, fmt, pica_t, pica_r, fst_r, thr_txt, r_txt):
                  fst_skip=fst_skip)
     if args.output:
         out.close()
+
+
+def fail(message, code=2):
+    print(f"Error: {message}", file=sys.stderr)
+    sys.exit(code)
+
+
+def panel_labels(args):
+    """the --panel lists' base names, as the tables print them"""
+    return [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
+
+
+def site_bp(mf):
+    """site index -> position in bp on the matrix's contig"""
+    return (lambda c: int(mf.site_pos[c])) if mf.site_pos is not None else (lambda c: int(mf.origin + c))
+
+
+def pair_samples(fmt, names, mask_p, min_samples):
+    """the sequences of mask_p (None: all) paired into samples by their PanSN fields -> (pairs, sample names); the sequences left
+    out are named in one warning, fewer than min_samples (1 or 2) paired samples end the run"""
+    from impop_amd.popnames import pair_haplotypes
+    chosen = None if mask_p is None else [nm for nm, f in zip(names, mask_p) if f]
+    pairs, samples, unpaired = pair_haplotypes(list(names), chosen)
+    if unpaired:
+        print(f"Warning: --format {fmt}: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
+              + " ".join(unpaired), file=sys.stderr)
+    if len(pairs) < min_samples:
+        few = "no sample with both of its haplotypes" if min_samples == 1 else "fewer than two samples with both of their haplotypes"
+        fail(f"--format {fmt}: {few} (sample#1#..., sample#2#...) among the sequences")
+    return pairs, samples
+
+
+def check_lists(fmt, labels, pops, groups, disjoint):
+    """what a --panel scan would refuse, with the lists' names.  groups: [(lists that must select a sequence, pairs of lists that
+    must not share one)], checked group by group; disjoint: the format's words behind `share a sequence; `"""
+    for need, pairs in groups:
+        for k in need:
+            if not pops[k].any():
+                fail(f"--format {fmt}: {labels[k]} selects no sequence of the matrix")
+        for a, b in pairs:
+            if (pops[a] & pops[b]).any():
+                fail(f"--format {fmt}: {labels[a]} and {labels[b]} share a sequence; {disjoint}")
+
+
+def pica_params(args):
+    """-> (threshold, round digits) behind the pica2-derived columns and the THRESHOLD / R_VALUE texts"""
+    if args.format in ("tajd", "all"):  # run_tajd.sh:9-10
+        pica_t = 0.999 if args.threshold is None else args.threshold
+        pica_r = 5 if args.round_digits is None else (None if args.round_digits == "none" else args.round_digits)
+    else:
+        pica_t = 1.0 if args.threshold is None else args.threshold
+        pica_r = None if args.round_digits in (None, "none") else args.round_digits
+    thr_txt = args.threshold_text if args.threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
+    return pica_t, pica_r, thr_txt, "" if pica_r is None else str(pica_r)
+
+
+class Job:
+    """The front end of every matrix-path format: the matrices keyed by contig, the usable BED rows with their region text and the
+    rows grouped per matrix (BED rows are matched to matrices by chromosome), and the one way through a matrix: windows -> Runner
+    -> scan -> close."""
+
+    def __init__(self, args, rank=0, world=1, local_rank=0):
+        self.args, self.rank, self.world, self.local_rank = args, rank, world, local_rank
+
+        def full_name(chrom):
+            return chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
+        self.mats = {}
+        for p in args.matrix:
+            mf = load_matrix(p)
+            key = full_name(mf.contig) if mf.contig else ""
+            if key in self.mats:
+                fail(f"two matrices for contig '{mf.contig}' ({p})")
+            self.mats[key] = mf
+        if "" in self.mats and len(self.mats) > 1:
+            fail("several --matrix files need a contig name each (matrixio `contig`)")
+        bed = read_bed(args.bed, args.format)
+        self.ehh_cores = read_core_positions(args.ehh_cores) if args.ehh_cores else None  # one per usable BED row: see row_bed
+        if self.ehh_cores is not None and len(self.ehh_cores) != len(bed):
+            fail(f"--ehh-cores holds {len(self.ehh_cores)} positions for {len(bed)} BED rows")
+        # rows[i] = (region, key of its matrix, start, end); row_bed[i] = index of row i among the usable BED rows
+        self.rows, self.per_mat, self.row_bed = [], {}, []
+        for bed_no, (chrom, s, e) in enumerate(bed):
+            region = f"{full_name(chrom)}:{s}-{e}"
+            key = "" if "" in self.mats else full_name(chrom)
+            if key not in self.mats:
+                print(f"Warning: Skipping region {region}: no matrix holds chromosome {chrom}", file=sys.stderr)
+                continue
+            self.per_mat.setdefault(key, []).append(len(self.rows))
+            self.rows.append((region, key, s, e))
+            self.row_bed.append(bed_no)
+        self.n_rows = len(self.rows)
+        self.regions = [r[0] for r in self.rows]
+        self.L_col = np.array([e - s for _, _, s, e in self.rows], dtype=np.int64)  # LENGTH = end - start (run_pica2_impg.sh:133)
+
+    def matrices(self):
+        """per matrix, in the order of each matrix's first BED row: (key, matrix, the indices of its rows, their windows)"""
+        for key, idx in self.per_mat.items():
+            mf = self.mats[key]
+            yield key, mf, np.array(idx), [mf.site_range(self.rows[i][2], self.rows[i][3]) + (int(self.L_col[i]),) for i in idx]
+
+    @contextlib.contextmanager
+    def upload(self, mf, wins, need_pairs):
+        """the matrix on the device(s) with its windows; closed on every way out"""
+        run = Runner(self.args, mf, wins, need_pairs, self.rank, self.world, self.local_rank)
+        try:
+            yield run
+        finally:
+            run.close()
+
+    def subset_mask(self, mf):
+        return flags_for(self.args.subset, mf.names) if self.args.subset else None
+
+    def open_output(self):
+        return (open(self.args.output, "w") if self.args.output else sys.stdout) if self.rank == 0 else open(os.devnull, "w")
+
+    def close_output(self, out):
+        if self.args.output or self.rank != 0:
+            out.close()
+
+
+def print_rows(handle, table):
+    if handle:
+        for row in table:
+            print("\t".join(row), file=handle)
+
+
+def scan_af(args, job):
+    """--format af: the main table to --output / stdout, --af-clusters / --af-details to their paths"""
+    from impop_amd.af import _sample_of, clusters_from_ranks
+    pica_t, pica_r, thr_txt, _ = pica_params(args)
+    want_members = bool(args.af_clusters or args.af_details)
+    out = job.open_output()
+    recs = np.zeros(job.n_rows, dtype=impop_amd.CLUSTER_DTYPE)
+    clusters = [None] * job.n_rows
+    for _, mf, idx, wins in job.matrices():
+        mask_p = job.subset_mask(mf)
+        members = [_sample_of(mf.names[i]) for i in (range(mf.n_hap) if mask_p is None else np.flatnonzero(mask_p))]
+        if len(set(members)) != len(members):
+            # af.py names its nodes by the cut name, so two sequences of one name would be ONE sample there, while the
+            # records count sequences: the main table and the side tables of one run would disagree
+            dup = sorted({m for m in members if members.count(m) > 1})[0]
+            fail(f"--format af needs distinct sequence names before the first ':' ('{dup}' names several rows of the matrix)")
+        with job.upload(mf, wins, True) as run:
+            res = run.bm.cluster_scan(run.local_wins, mask_p=mask_p, kind=args.identity, threshold=pica_t, round_digits=pica_r,
+                                      want_members=want_members)
+        if want_members:
+            recs[idx] = res[0]
+            for i, row in zip(idx, res[1]):
+                clusters[i] = clusters_from_ranks(row, members)
+        else:
+            recs[idx] = res
+    write_af_table(out, job.regions, job.L_col, thr_txt, recs)
+    if args.af_clusters:
+        with open(args.af_clusters, "w", newline="") as fh:
+            write_af_clusters(fh, job.regions, clusters)
+    if args.af_details:
+        with open(args.af_details, "w", newline="") as fh:
+            write_af_details(fh, job.regions, clusters, float(pica_t))
+    job.close_output(out)
+
+
+def scan_ehh(args, job):
+    """--format ehh: one core per BED row; cores and the reference sequence are checked before the matrix goes up"""
+    out = job.open_output()
+    lines = [None] * job.n_rows
+    for _, mf, idx, wins in job.matrices():
+        cores = []
+        for i, (b, en, _) in zip(idx, wins):
+            if job.ehh_cores is not None:
+                c = mf.site_range(job.ehh_cores[job.row_bed[i]], job.ehh_cores[job.row_bed[i]])[0]
+            else:
+                c = b + ((en - b) // 2 if args.ehh_core_offset is None else args.ehh_core_offset)
+            if not b <= c < en:
+                fail(f"--format ehh: the core of {job.regions[i]} (site {c}) is outside the window's sites [{b}, {en})")
+            cores.append(c)
+        ref_hap = 0
+        if args.ehh_ref is not None:
+            if args.ehh_ref not in mf.names:
+                fail(f"--ehh-ref {args.ehh_ref} is not a sequence of the matrix")
+            ref_hap = list(mf.names).index(args.ehh_ref)
+        with job.upload(mf, wins, False) as run:
+            recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=job.subset_mask(mf), ref_hap=ref_hap,
+                                   flanks=args.ehh_flanks or "reference")
+        bp = site_bp(mf)
+        for i, c, r in zip(idx, cores, recs):
+            lines[i] = ehh_rows(job.regions[i], int(job.L_col[i]), bp(c), r)
+    print(EHH_HEADER, file=out)
+    for rows in lines:
+        for line in rows:
+            print(line, file=out)
+    job.close_output(out)
+
+
+def scan_hapstats(args, job):
+    """--format hapstats: one row per BED row"""
+    out = job.open_output()
+    recs = np.zeros(job.n_rows, dtype=impop_amd.HAPLOTYPE_DTYPE)
+    for _, mf, idx, wins in job.matrices():
+        mask_p = job.subset_mask(mf)
+        if mask_p is not None and not mask_p.any():
+            fail("--format hapstats: -u selects no sequence of the matrix")
+        with job.upload(mf, wins, False) as run:
+            recs[idx] = run.hapstats(mask_p)
+    write_hap_table(out, job.regions, job.L_col, recs)
+    job.close_output(out)
+
+
+def scan_ld(args, job):
+    """--format ld: one row per BED row; OMEGA_POS is the position of the first used site right of the best split"""
+    out = job.open_output()
+    recs = np.zeros(job.n_rows, dtype=impop_amd.LD_DTYPE)
+    omega_pos = [None] * job.n_rows
+    for _, mf, idx, wins in job.matrices():
+        mask_p = job.subset_mask(mf)
+        if mask_p is not None and not mask_p.any():
+            fail("--format ld: -u selects no sequence of the matrix")
+        n_matched = mf.n_hap if mask_p is None else int(mask_p.sum())
+        with job.upload(mf, wins, False) as run:
+            got, used = run.ld(mask_p, ld_min_mac(0.05 if args.ld_min_maf is None else args.ld_min_maf, n_matched), args.ld_max_sites or 512)
+        recs[idx] = got
+        bp = site_bp(mf)
+        for i, r, u in zip(idx, got, used):
+            if r["omega_split"]:
+                omega_pos[i] = bp(int(u[int(r["omega_split"])]))
+    write_ld_table(out, job.regions, job.L_col, recs, omega_pos)
+    job.close_output(out)
+
+
+def scan_diploid(args, job):
+    """--format diploid: one row per BED row, --ind-table one per row and sample"""
+    out = job.open_output()
+    recs = np.zeros(job.n_rows, dtype=impop_amd.DIPLOID_DTYPE)
+    ind = [None] * job.n_rows  # per row: (sample names, impop_diploid_ind rows)
+    min_run = 50 if args.roh_min_sites is None else args.roh_min_sites
+    for _, mf, idx, wins in job.matrices():
+        pairs, samples = pair_samples("diploid", mf.names, job.subset_mask(mf), 1)
+        with job.upload(mf, wins, False) as run:
+            if args.ind_table:
+                recs[idx], ind_rows = run.diploid(pairs, min_run, True)
+                for i, q in zip(idx, ind_rows):
+                    ind[i] = (samples, q)
+            else:
+                recs[idx] = run.diploid(pairs, min_run, False)
+    write_diploid_table(out, job.regions, recs)
+    if args.ind_table:
+        with open(args.ind_table, "w") as fh:
+            print(DIPLOID_IND_HEADER, file=fh)
+            for reg, entry in zip(job.regions, ind):
+                write_diploid_ind_table(fh, [reg], entry[0], [entry[1]], header=False)
+    job.close_output(out)
+
+
+def scan_ibs(args, job):
+    """--format ibs: all BED rows of a matrix in one call over its whole site range; the segment list and the pair table are
+    written matrix by matrix"""
+    out = job.open_output()
+    seg_fh = open(args.ibs_segments, "w") if args.ibs_segments else None
+    pair_fh = open(args.ibs_pair_table, "w") if args.ibs_pair_table else None
+    if seg_fh:
+        print(IBS_SEGMENT_HEADER, file=seg_fh)
+    if pair_fh:
+        print(IBS_PAIR_HEADER, file=pair_fh)
+    recs = np.zeros(job.n_rows, dtype=impop_amd.IBS_WINDOW_DTYPE)
+    n_pairs = np.zeros(job.n_rows, dtype=np.int64)
+    for _, mf, idx, wins in job.matrices():
+        mask_p = job.subset_mask(mf)
+        kw = dict(min_sites=50 if args.ibs_min_sites is None else args.ibs_min_sites, windows=[(b, en) for b, en, _ in wins],
+                  want_segments=seg_fh is not None)
+        if (args.ibs_pairs or "all") == "diploid":
+            kw["pairs"], _ = pair_samples("ibs", mf.names, mask_p, 1)
+        else:
+            n_matched = mf.n_hap if mask_p is None else int(mask_p.sum())
+            if n_matched < 2:
+                fail(f"--format ibs: {n_matched} sequences make no pair")
+            kw["mask_p"] = mask_p
+        with job.upload(mf, wins, False) as run:
+            prec, segs, recs[idx], _ = run.bm.ibs_scan(**kw)
+        n_pairs[idx] = len(prec)
+        if seg_fh:
+            write_ibs_segments(seg_fh, mf.names, segs, site_bp(mf), header=False)
+        if pair_fh:
+            write_ibs_pairs(pair_fh, mf.names, prec, header=False)
+    write_ibs_table(out, job.regions, job.L_col, n_pairs, recs)
+    for fh in (seg_fh, pair_fh):
+        if fh:
+            fh.close()
+    job.close_output(out)
+
+
+def scan_dstat(args, job):
+    """--format dstat: one row per BED row and quartet, --dstat-summary the block jackknife over all rows"""
+    quartets = parse_quartets(args.quartet, len(args.panel))
+    labels = panel_labels(args)
+    out = job.open_output()
+    recs = np.zeros((job.n_rows, len(quartets)), dtype=impop_amd.DSTAT_DTYPE)
+    sizes_rows = [None] * job.n_rows  # per row: the populations' sizes in its matrix
+    for _, mf, idx, wins in job.matrices():
+        pops = [flags_for(f, mf.names) for f in args.panel]
+        check_lists("dstat", labels, pops, [(q, [(a, b) for i, a in enumerate(q) for b in q[i + 1:]]) for q in quartets],
+                    "the four populations of a quartet must be disjoint")
+        with job.upload(mf, wins, False) as run:
+            recs[idx] = run.dstat(pops, quartets, bool(args.dstat_polarize))
+        for i in idx:
+            sizes_rows[i] = [int(p.sum()) for p in pops]
+    write_dstat_table(out, job.regions, labels, quartets, sizes_rows, recs)
+    if args.dstat_summary:
+        with open(args.dstat_summary, "w") as fh:
+            write_dstat_summary(fh, labels, quartets, sizes_rows, recs, args.dstat_blocks)
+    job.close_output(out)
+
+
+def scan_sfs(args, job):
+    """--format sfs: one row per BED row and population, --sfs-pairs-out one per row and pair, --sfs-spectra the spectra summed
+    over --sfs-blocks consecutive groups of rows (scanned in batches of SFS_BATCH_ROWS rows)"""
+    from impop_amd.distributed import shard_range
+    pairs = parse_sfs_pairs(args.sfs_pair, len(args.panel))
+    labels = panel_labels(args)
+    out = job.open_output()
+    recs = np.zeros((job.n_rows, len(args.panel)), dtype=impop_amd.SFS_DTYPE)
+    pair_recs = np.zeros((job.n_rows, len(pairs)), dtype=impop_amd.SFS_PAIR_DTYPE)
+    sizes_rows = [None] * job.n_rows
+    n_blocks = args.sfs_blocks or 1
+    blocks, block_of = None, np.zeros(job.n_rows, dtype=np.int64)  # --sfs-spectra: name -> [blocks, bins...] sums; the block of every row
+    for j in range(n_blocks):
+        lo, hi = shard_range(job.n_rows, n_blocks, j)
+        block_of[lo:hi] = j
+    tables = (("sfs",) + (("jsfs",) if pairs else ())) if args.sfs_spectra else ()
+    for key, mf, idx, wins in job.matrices():
+        pops = [flags_for(f, mf.names) for f in args.panel]
+        check_lists("sfs", labels, pops, [(range(len(pops)), pairs)], "the two populations of a pair must be disjoint")
+        outgroup = None if args.sfs_outgroup is None else args.sfs_outgroup - 1
+        batch = SFS_BATCH_ROWS if tables else max(len(idx), 1)
+        with job.upload(mf, wins, False) as run:
+            for w0 in range(0, len(idx), batch):
+                part = idx[w0:w0 + batch]
+                recs[part], pr, sfs, jsfs = run.sfs(pops, pairs, outgroup, tables, w0, w0 + len(part))
+                if pairs:
+                    pair_recs[part] = pr
+                if tables:
+                    named = [(f"sfs_{labels[k]}", t) for k, t in enumerate(sfs)]
+                    named += [(f"jsfs_{labels[a]}_{labels[b]}", t) for (a, b), t in zip(pairs, jsfs or [])]
+                    if blocks is None:
+                        blocks = {nm: np.zeros((n_blocks,) + t.shape[1:], dtype=np.uint64) for nm, t in named}
+                    for nm, t in named:
+                        if blocks[nm].shape[1:] != t.shape[1:]:
+                            fail(f"--sfs-spectra: {nm} has another shape in the matrix of {key or 'the run'} (the lists select another "
+                                 "number of its sequences); write the spectra per matrix")
+                        np.add.at(blocks[nm], block_of[part], t.astype(np.uint64))
+        for i in idx:
+            sizes_rows[i] = [int(p.sum()) for p in pops]
+    write_sfs_table(out, job.regions, labels, sizes_rows, recs)
+    if args.sfs_pairs_out:
+        with open(args.sfs_pairs_out, "w") as fh:
+            write_sfs_pairs(fh, job.regions, labels, pairs, pair_recs)
+    if args.sfs_spectra:
+        np.savez(args.sfs_spectra, **(blocks or {}))
+    job.close_output(out)
+
+
+def scan_pairdist(args, job):
+    """--format pairdist: the main table to --output / stdout, the side tables to their paths; the rows are written matrix by matrix"""
+    from impop_amd import pairdist as pd
+    labels = panel_labels(args)
+    og = None if args.pairdist_outgroup is None else args.pairdist_outgroup - 1
+    out = job.open_output()
+    pan_fh = open(args.pairdist_panels, "w") if args.pairdist_panels else None
+    hist_fh = open(args.pairdist_hist, "w") if args.pairdist_hist else None
+    print("\t".join(pd.MAIN_COLUMNS + (["RNDMIN"] if og is not None else [])), file=out)
+    print_rows(pan_fh, [pd.PANEL_COLUMNS])
+    print_rows(hist_fh, [pd.HIST_COLUMNS])
+    for _, mf, idx, wins in job.matrices():
+        pops = [flags_for(f, mf.names) for f in args.panel]
+        check_lists("pairdist", labels, pops, [((k,), [(l, k) for l in range(k)]) for k in range(len(pops))], "the lists must be disjoint")
+        with job.upload(mf, wins, True) as run:
+            panels, pairs, hw, hb = run.bm.pairdist_scan(run.local_wins, pops, hist_bins=args.pairdist_bins or 0, hist_width=args.pairdist_bin_width or 1)
+        main, pan, hist = pd.tables([job.regions[i] for i in idx], [int(job.L_col[i]) for i in idx], labels, list(mf.names), panels, pairs,
+                                    hw, hb, outgroup=og)
+        for fh, table in ((out, main), (pan_fh, pan), (hist_fh, hist)):
+            print_rows(fh, table)
+    for fh in (pan_fh, hist_fh):
+        if fh:
+            fh.close()
+    job.close_output(out)
+
+
+def scan_kinship(args, job):
+    """--format kinship: one row per BED row to --output / stdout, the per-pair totals and the watch rows to their paths; the rows
+    are written matrix by matrix"""
+    from impop_amd import kinship as kin
+    frac = kin.threshold_fraction(0.0884 if args.kin_threshold is None else args.kin_threshold)
+    out = job.open_output()
+    watch_fh = open(args.kin_watch_table, "w") if args.kin_watch_table else None
+    print("\t".join(kin.WINDOW_COLUMNS), file=out)
+    print_rows(watch_fh, [kin.WATCH_COLUMNS])
+    samples, totals = None, None
+    for key, mf, idx, wins in job.matrices():
+        if mf.site_weight is not None:
+            fail("--format kinship: the matrix has site weights; a genotype is read per column")
+        pairs, smp = pair_samples("kinship", mf.names, job.subset_mask(mf), 2)
+        if samples is not None and list(smp) != samples:
+            fail(f"--format kinship: the matrix of {key} pairs other samples than the one before it; the per-pair totals need one set of samples")
+        samples = list(smp)
+        watch = []
+        for spec in args.kin_watch or []:
+            a, b = spec.split(",")
+            if a not in samples or b not in samples:
+                fail(f"--kin-watch {spec}: {a if a not in samples else b} is not one of the paired samples")
+            watch.append((samples.index(a), samples.index(b)))
+        with job.upload(mf, wins, False) as run:
+            g = run.bm.genotypes(pairs)
+            try:
+                recs, ptot, wrows = g.kinship_scan(run.local_wins, kin=frac, watch=watch or None, want_pairs=args.kin_pairs is not None)
+            finally:
+                g.free()
+        if ptot is not None:  # integer sums on the host, over all rows and all matrices
+            t = [[int(x) for x in rec] for rec in ptot["t"]]
+            totals = t if totals is None else [[a + b for a, b in zip(ra, rb)] for ra, rb in zip(totals, t)]
+        main, _, wat = kin.tables([job.regions[i] for i in idx], [int(job.L_col[i]) for i in idx], samples, recs, None, watch, wrows)
+        print_rows(out, main)
+        print_rows(watch_fh, wat)
+    if args.kin_pairs:
+        with open(args.kin_pairs, "w") as fh:
+            print_rows(fh, [kin.PAIR_COLUMNS])
+            if totals is not None:
+                print_rows(fh, kin.tables([], [], samples, [], totals)[1])
+    if watch_fh:
+        watch_fh.close()
+    job.close_output(out)
+
+
+def scan_ihs(args, job):
+    """--format ihs / xpehh: one impop_ihs_scan per BED row over its contig's whole matrix, the row's sites as cores; the scores are
+    standardised over all rows of the run (grouped by matrix) and the table goes to --output / stdout"""
+    from impop_amd import ihs as ih
+    K = 2 if args.format == "xpehh" else 1
+    maf = 0.05 if args.ihs_min_maf is None else args.ihs_min_maf
+    cutoff_milli = int(round(1000 * (0.05 if args.ihs_cutoff is None else args.ihs_cutoff)))
+    max_bp = 1000000 if args.ihs_max_extend is None else args.ihs_max_extend
+    max_sites = 100 if args.ihs_max_extend_sites is None else args.ihs_max_extend_sites
+    chroms, bps, recs = [], [], []
+    for _, mf, idx, wins in job.matrices():
+        if K == 2:
+            pops = [flags_for(f, mf.names) for f in args.panel]
+            if (pops[0] & pops[1]).any():
+                fail("--format xpehh: the two lists of --panel share a sequence; they must be disjoint")
+            if min(int(p.sum()) for p in pops) < 2:
+                fail("--format xpehh: each list of --panel needs at least two sequences of the matrix")
+            n_members = int(pops[0].sum() + pops[1].sum())
+        else:
+            pops = [job.subset_mask(mf), None]
+            n_members = mf.n_hap if pops[0] is None else int(pops[0].sum())
+            if n_members < 2:
+                fail(f"--format ihs: {n_members} sequences make no pair")
+        bp = site_bp(mf)
+        with job.upload(mf, wins, False) as run:
+            for i, (b, en, _) in zip(idx, wins):
+                if en <= b:
+                    continue
+                rec, _ = run.bm.ihs_scan(mask_a=pops[0], mask_b=pops[1], core_begin=b, core_end=en, min_mac=max(1, math.ceil(maf * n_members)),
+                                         cutoff_milli=cutoff_milli, max_extend_bp=max_bp, max_extend_sites=max_sites)
+                recs.append(rec)
+                chroms += [split_region(job.regions[i])[0]] * len(rec)
+                bps += [bp(int(c)) for c in rec["site"]]
+    out = job.open_output()
+    write_ihs_table(out, K, chroms, bps, np.concatenate(recs) if recs else np.zeros(0, dtype=ih.IHS_DTYPE),
+                    50 if args.ihs_bins is None else args.ihs_bins, args.ihs_keep_edge)
+    job.close_output(out)
+
+
+def classic_plan(args, rank, world, local_rank):
+    """pica2 / hfst / tajd / fst3pi / all: the checks between the refusals and the first file read, in their order, the process group
+    of a torch.distributed launch, and what is computed: (threshold, round digits) behind the pica2-derived columns, the round digits
+    of the h-fst table, which tables need the all-pairs path"""
+    fmt = args.format
+    # --panel on the all-pairs path (impop_pairwise_scan_panel) is the one-process form: refused before any rank waits for another
+    panel_allpairs = bool(args.panel) and (fmt in ("tajd", "all") or args.round_digits not in (None, "none") or args.identity != "match")
+    if panel_allpairs and world > 1:
+        fail("--panel with --format tajd / all, -r N or --identity dice runs on one GPU (impop_pairwise_scan_panel has no sharded "
+             "form): not under torch.distributed.run")
+    if args.panel and args.fst_method == "grouped":
+        fail("--panel has no --fst-method grouped (the panel calls are the direct method; use -A / -B per pair)")
+    if args.panel and fmt in ("tajd", "all") and args.sample_list:
+        fail("--panel with --format tajd / all takes every panel's list as its sample list: not with -l")
+    if args.panel and not 2 <= len(args.panel) <= 8:
+        fail("--panel takes 2 to 8 population lists")
+    if world > 1:
+        import torch
+        import torch.distributed as dist
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        if args.backend == "nccl":
+            torch.cuda.set_device(local_rank)
+            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
+        else:
+            dist.init_process_group(args.backend, rank=rank, world_size=world)
+    if args.devices > 1 and (world > 1 or args.panel or args.compact):
+        fail("--devices N is the one-process form: not under torch.distributed.run, not with --panel / --compact")
+    p = SimpleNamespace(grouped_fst=fmt == "hfst" and args.fst_method == "grouped")
+    p.pica_t, p.pica_r, p.thr_txt, p.r_txt = pica_params(args)
+    if fmt == "hfst":
+        p.fst_r = None if args.round_digits in (None, "none") else args.round_digits
+        if args.threshold is not None and not p.grouped_fst:
+            fail("--format hfst takes -t only with --fst-method grouped (h-fst.py has no threshold)")
+    else:
+        p.fst_r = None if args.fst_round_digits in (None, "none") else args.fst_round_digits
+    if args.fst_round_digits is not None and fmt != "all":
+        fail("--fst-round-digits belongs to --format all (use -r with --format hfst)")
+    p.grouped_t = 0.999 if args.threshold is None else args.threshold  # hud.py -t
+    p.pica_pairs = not (p.pica_t >= 1.0 and p.pica_r is None and args.identity == "match")
+    p.fst_pairs = p.grouped_fst or p.fst_r is not None or args.identity != "match"
+    p.want_pica = fmt in ("pica2", "tajd", "all", "fst3pi")
+    p.want_fst = fmt in ("hfst", "all") and not args.panel
+    if args.panel and fmt not in ("hfst", "tajd", "all"):
+        fail("--panel belongs to --format hfst (every pair), tajd (every panel), all (both) or dstat (quartets)")
+    # --panel: the pair tables come from the streaming K-population scan (impop_scan_multi) when h-fst is unrounded on `match`,
+    # else - like every per-panel tajd table - from impop_pairwise_scan_panel: one Gram pass per window for all panels and pairs
+    p.panel_fst = bool(args.panel) and fmt in ("hfst", "all")
+    p.panel_tajd = bool(args.panel) and fmt in ("tajd", "all")
+    p.need_pairs = (p.panel_tajd or (p.panel_fst and p.fst_pairs)) if args.panel else \
+        (p.want_pica and p.pica_pairs) or (p.want_fst and p.fst_pairs)
+    return p
+
+
+def classic_panel(args, job, run, idx, pops, t):
+    """--panel on hfst / tajd / all for the rows idx of one matrix: the pair records into t.panel_tables, the panel records into
+    t.panel_taj"""
+    p = job.plan
+    pr = pan = pw = None
+    if p.panel_fst and not p.fst_pairs:
+        pr = run.panel(pops)
+    one_call = p.panel_fst and p.fst_pairs and p.panel_tajd and p.pica_r == p.fst_r
+    if p.panel_tajd:
+        pan, pr2, pw = run.panel_allpairs(pops, p.pica_t, p.pica_r, True, one_call)
+        if one_call:
+            pr = pr2
+    if p.panel_fst and pr is None:  # (h-fst.py has no threshold: it only groups pica2)
+        _, pr, _ = run.panel_allpairs(pops, p.pica_t, p.fst_r, False, True)
+    if pr is not None:
+        if t.panel_tables is None:
+            t.panel_tables = np.zeros((job.n_rows, pr.shape[1]), dtype=pr.dtype)
+        t.panel_tables[idx] = pr
+    if pan is not None:
+        K = len(pops)
+        if t.panel_taj is None:
+            t.panel_taj = {"pi_site": np.full((job.n_rows, K), np.nan), "tajima_d": np.full((job.n_rows, K), np.nan),
+                           "s_all": np.zeros(job.n_rows, dtype=np.int64), "samples": [awk_line_count(f) for f in args.panel]}
+        t.panel_taj["pi_site"][idx] = pan["pi_site"]
+        t.panel_taj["s_all"][idx] = pw["s_all"]
+        D = pan["tajima_d"].copy()
+        for k in range(K):
+            cnt_k, matched = t.panel_taj["samples"][k], int(pops[k].sum())
+            if cnt_k < 2:
+                fail(f"Need at least two samples to compute Tajima's D (found {cnt_k})", 1)  # run_tajd.sh:84-87
+            if cnt_k != matched and len(idx):  # run_tajd.sh:180: n = the list's LINE count (see the -l case in classic_pair)
+                print(f"Warning: sample list {t.panel_labels[k]} has {cnt_k} lines but selects {matched} haplotypes; Tajima's D uses "
+                      f"n = {cnt_k} like run_tajd.sh", file=sys.stderr)
+                pi_txt = np.array([float(f"{float(x):.8f}") for x in pan["pi_site"][:, k]])
+                D[:, k] = run.ctx.tajimas_d(np.full(len(idx), cnt_k, dtype=np.int64), pw["s_all"].astype(np.float64), pi_txt)
+        t.panel_taj["tajima_d"][idx] = D
+
+
+def classic_fst3pi(job, run, idx, mask_a, mask_b, t):
+    """run_fst_impg.sh:73: pica2.py -t T -r R on the lists A, B and A u B, for the rows idx of one matrix"""
+    p = job.plan
+    if p.pica_pairs:
+        for name, sel in (("pi3_a", mask_a), ("pi3_b", mask_b), ("pi3_c", mask_a | mask_b)):
+            t.col[name][idx] = run.pairs(sel, None, None, p.pica_t, p.pica_r, False)["pi_site"]
+    else:
+        from impop_amd.drivers import pi_union_site
+        res = run.stream(None, mask_a, mask_b)
+        nA, nB = int(mask_a.sum()), int(mask_b.sum())
+        t.col["pi3_a"][idx], t.col["pi3_b"][idx] = res["pi_a"], res["pi_b"]
+        t.col["pi3_c"][idx] = [pi_union_site(r, nA, nB, int(L)) for r, L in zip(res, job.L_col[idx])]
+
+
+def classic_pair(args, job, run, idx, mask_p, mask_a, mask_b, n_hap, n_matched, t):
+    """the pica2 / h-fst / tajd columns of the rows idx of one matrix: one call where both tables round alike"""
+    p, fmt = job.plan, args.format
+    want_s = fmt in ("tajd", "all")
+    one_call = p.want_pica and p.want_fst and p.pica_pairs and p.fst_pairs and p.pica_r == p.fst_r and not p.grouped_fst
+    pica_rec = fst_rec = None
+    if p.want_pica:
+        pica_rec = run.pairs(mask_p, mask_a if one_call else None, mask_b if one_call else None, p.pica_t, p.pica_r, want_s) \
+            if p.pica_pairs else run.stream(mask_p, mask_a, mask_b)
+        if one_call or (p.want_fst and not p.pica_pairs and not p.fst_pairs):
+            fst_rec = pica_rec
+    if p.want_fst and fst_rec is None and mask_a is not None:
+        fst_rec = run.pairs(None, mask_a, mask_b, p.grouped_t, p.fst_r, False, args.fst_method if p.grouped_fst else "direct") \
+            if p.fst_pairs else run.stream(None, mask_a, mask_b)
+    if pica_rec is not None:
+        t.col["pi_site"][idx] = pica_rec["pi_site"]
+        if want_s:
+            t.s_all[idx] = pica_rec["s_all"]
+            D = pica_rec["tajima_d"]
+            t.samples_col = t.sample_count if t.sample_count is not None else n_hap
+            if t.sample_count is not None and t.sample_count != n_matched and len(idx):
+                # run_tajd.sh:180 hands tj_d.py `-n SAMPLE_COUNT`, the list's LINE count, whatever the number of
+                # haplotypes those lines select (a bare sample name selects two, an unknown name none, a repeated
+                # line counts twice).  The scan evaluated D with n = matched haplotypes: redo D (on the GPU,
+                # impop_tajimas_d) with the reference's n, pi through the same "%.8f" text (run_tajd.sh:174) and S.
+                print(f"Warning: sample list has {t.sample_count} lines but selects {n_matched} haplotypes; Tajima's D uses "
+                      f"n = {t.sample_count} like run_tajd.sh", file=sys.stderr)
+                pi_txt = np.array([float(f"{float(x):.8f}") for x in pica_rec["pi_site"]])
+                D = run.ctx.tajimas_d(np.full(len(idx), t.sample_count, dtype=np.int64), pica_rec["s_all"].astype(np.float64), pi_txt)
+            t.col["tajima_d"][idx] = D
+    if fst_rec is not None:
+        for k in ("fst", "pi_a", "pi_b", "pi_xy", "dxy", "da"):
+            t.col[k][idx] = fst_rec[k]
+
+
+def scan_classic(args, job):
+    """--format pica2 / hfst / tajd / fst3pi / all, with -A / -B, -l, -u or --panel, on one device, --devices N or one rank of a
+    torch.distributed job: the tables of the reference's drivers (write_tables)"""
+    p, fmt = job.plan, args.format
+    if args.sequence_length is not None:
+        if fmt != "pica2" or args.sequence_length <= 0:
+            fail("--sequence-length (a positive integer) belongs to --format pica2 (run_pica2_impg.sh -l)")
+        job.L_col[:] = args.sequence_length  # EFFECTIVE_LENGTH, run_pica2_impg.sh:153-157
+    out = job.open_output()
+    t = SimpleNamespace(s_all=np.zeros(job.n_rows, dtype=np.int64), panel_tables=None, panel_taj=None, samples_col=0, sample_count=None,
+                        panel_labels=panel_labels(args) if args.panel else None)
+    t.col = {k: np.full(job.n_rows, np.nan) for k in ("pi_site", "tajima_d", "fst", "pi_a", "pi_b", "pi_xy", "dxy", "da", "pi3_a", "pi3_b", "pi3_c")}
+    if args.sample_list:
+        t.sample_count = awk_line_count(args.sample_list)  # run_tajd.sh:83
+        if fmt in ("tajd", "all") and t.sample_count < 2:
+            fail(f"Need at least two samples to compute Tajima's D (found {t.sample_count})", 1)  # :84-87
+    for _, mf, idx, wins in job.matrices():
+        with job.upload(mf, wins, p.need_pairs) as run:
+            mask_p = mask_a = mask_b = None
+            if args.sample_list:
+                mask_p = flags_for(args.sample_list, mf.names)
+            if args.subset:
+                mask_p = flags_for(args.subset, mf.names)
+            n_matched = mf.n_hap if mask_p is None else int(mask_p.sum())
+            if args.pop_a and args.pop_b:
+                mask_a, mask_b = flags_for(args.pop_a, mf.names), flags_for(args.pop_b, mf.names)
+                if not mask_a.any() or not mask_b.any():
+                    fail("No valid sequences found in one or both populations", 1)  # h-fst.py:319-321
+            if args.panel:
+                classic_panel(args, job, run, idx, [flags_for(f, mf.names) for f in args.panel], t)
+            elif fmt == "fst3pi":
+                if mask_a is None:
+                    fail("--format fst3pi needs -A and -B")
+                if (mask_a & mask_b).any():
+                    fail("--format fst3pi needs disjoint populations")
+                classic_fst3pi(job, run, idx, mask_a, mask_b, t)
+            else:
+                classic_pair(args, job, run, idx, mask_p, mask_a, mask_b, mf.n_hap, n_matched, t)
+    write_tables(out, args, fmt, job.regions, job.L_col, t.col, t.s_all, t.samples_col, p.thr_txt, p.r_txt, t.panel_tables, t.panel_labels,
+                 panel_taj=t.panel_taj)
+    job.close_output(out)
+
+
+# ---- what each format does not combine with: one table, walked in its order by refusal() ------------------------------------------
+
+def _excludes(sentence, *options):
+    """the sentence saying whose sequences a format works on, and the options that sentence excludes"""
+    return lambda a: f"--format {a.format} {sentence}" if any(getattr(a, o) for o in options) else None
+
+
+def _takes_panel(lo, hi, lists):
+    return lambda a: None if a.panel and lo <= len(a.panel) <= hi else f"--format {a.format} takes --panel {lists}"
+
+
+def _has_no_threshold(why):
+    """the formats that count sites: -t / -r / --fst-round-digits mean nothing to them"""
+    return lambda a: f"--format {a.format} {why}" if (a.threshold is not None or a.round_digits is not None
+                                                       or a.fst_round_digits is not None) else None
+
+
+def _when(fmt, check):
+    return lambda a: check(a) if a.format == fmt else None
+
+
+def _no_identity(a):
+    if a.threshold is not None or a.round_digits is not None or a.identity != "match":
+        return "-t / -r / --identity belong to other formats"
+
+
+def _no_fst(a):
+    if a.fst_method != "direct" or a.fst_round_digits is not None or a.sequence_length is not None:
+        return "--fst-method / --fst-round-digits / --sequence-length belong to other formats"
+
+
+_OF_SUBSET = ("panel", "pop_a", "pop_b", "sample_list")   # what a format of the sequences of -u excludes: -A / -B / --panel / -l
+_OF_PANEL = ("pop_a", "pop_b", "sample_list", "subset")   # what a format of the --panel populations excludes: -A / -B / -l / -u
+
+
+def _ehh_values(a):
+    if a.ehh_core_offset is not None and a.ehh_cores:
+        return "give --ehh-core-offset or --ehh-cores, not both"
+    if a.ehh_core_offset is not None and a.ehh_core_offset < 0:
+        return "--ehh-core-offset is a 0-based offset into the window (>= 0)"
+
+
+def _ld_values(a):
+    if a.ld_min_maf is not None and not 0.0 <= a.ld_min_maf <= 0.5:
+        return "--ld-min-maf is a minor-allele frequency (0 .. 0.5)"
+    if a.ld_max_sites is not None and not 4 <= a.ld_max_sites <= 1024:
+        return "--ld-max-sites takes 4 .. 1024"
+
+
+def _diploid_values(a):
+    if a.roh_min_sites is not None and a.roh_min_sites < 1:
+        return "--roh-min-sites takes 1 or more"
+
+
+def _ibs_values(a):
+    if a.ibs_min_sites is not None and a.ibs_min_sites < 1:
+        return "--ibs-min-sites takes 1 or more"
+
+
+def _dstat_values(a):
+    if (a.dstat_blocks is None) != (a.dstat_summary is None):
+        return "--dstat-blocks N and --dstat-summary PATH go together"
+    if a.dstat_blocks is not None and a.dstat_blocks < 1:
+        return "--dstat-blocks takes 1 or more"
+    try:
+        parse_quartets(a.quartet, len(a.panel))
+    except ValueError as e:
+        return str(e)
+
+
+def _sfs_values(a):
+    if a.sfs_outgroup is not None and not 1 <= a.sfs_outgroup <= len(a.panel):
+        return f"--sfs-outgroup {a.sfs_outgroup}: position is outside the {len(a.panel)} lists of --panel"
+    if a.sfs_blocks is not None and a.sfs_spectra is None:
+        return "--sfs-blocks N belongs to --sfs-spectra PATH.npz"
+    if a.sfs_blocks is not None and a.sfs_blocks < 1:
+        return "--sfs-blocks takes 1 or more"
+    try:
+        parse_sfs_pairs(a.sfs_pair, len(a.panel))
+    except ValueError as e:
+        return str(e)
+    if a.sfs_pairs_out is not None and not a.sfs_pair:
+        return "--sfs-pairs-out PATH needs at least one --sfs-pair i,j"
+    if a.sfs_pair and a.sfs_pairs_out is None and a.sfs_spectra is None:
+        return "--sfs-pair i,j goes with --sfs-pairs-out PATH or --sfs-spectra PATH.npz"
+
+
+def _pairdist_values(a):
+    if a.pairdist_outgroup is not None and not (len(a.panel) >= 3 and 1 <= a.pairdist_outgroup <= len(a.panel)):
+        return f"--pairdist-outgroup {a.pairdist_outgroup}: a 1-based position among at least three lists of --panel"
+    if (a.pairdist_bins is not None or a.pairdist_bin_width is not None) and a.pairdist_hist is None:
+        return "--pairdist-bins / --pairdist-bin-width belong to --pairdist-hist PATH"
+    if a.pairdist_hist is not None and a.pairdist_bins is None:
+        return "--pairdist-hist PATH needs --pairdist-bins B"
+    if a.pairdist_bins is not None and not 1 <= a.pairdist_bins <= 1024:
+        return "--pairdist-bins takes 1 to 1024"
+    if a.pairdist_bin_width is not None and a.pairdist_bin_width < 1:
+        return "--pairdist-bin-width takes 1 or more"
+
+
+def _kinship_values(a):
+    if a.kin_threshold is not None and not 0.0 <= a.kin_threshold <= 1.0:
+        return "--kin-threshold takes a kinship in 0 .. 1"
+    if bool(a.kin_watch) != (a.kin_watch_table is not None):
+        return "--kin-watch sampleA,sampleB and --kin-watch-table PATH go together"
+    for spec in a.kin_watch or []:
+        parts = spec.split(",")
+        if len(parts) != 2 or not all(parts) or parts[0] == parts[1]:
+            return f"--kin-watch {spec}: two different sample names, as in sampleA,sampleB"
+    if len(a.kin_watch or []) > 1024:
+        return "--kin-watch: at most 1024 pairs per run"
+
+
+def _ihs_values(a):
+    if a.ihs_min_maf is not None and not 0.0 < a.ihs_min_maf <= 0.5:
+        return "--ihs-min-maf takes a frequency above 0, at most 0.5"
+    if a.ihs_cutoff is not None and not 0.0 <= a.ihs_cutoff <= 1.0:
+        return "--ihs-cutoff takes 0 to 1"
+    if (a.ihs_max_extend is not None and a.ihs_max_extend < 0) or (a.ihs_max_extend_sites is not None and a.ihs_max_extend_sites < 0):
+        return "--ihs-max-extend / --ihs-max-extend-sites take 0 (no limit) or more"
+    if a.ihs_bins is not None and a.ihs_bins < 1:
+        return "--ihs-bins takes 1 or more"
+
+
+class Format:
+    """One entry of FORMATS.  formats: the --format names it serves; scan(args, job): what runs them; own(args): whether one of its own
+    options was given, stray: the line that answers them under another format; checks: for a one-process, one-GPU format, what
+    follows the three sentences every such format shares (refusal()), in the order they are tried: each args -> a line or None."""
+
+    def __init__(self, formats, scan, own=None, stray=None, checks=None):
+        self.formats, self.scan, self.own, self.stray, self.checks = formats, scan, own, stray, checks
+        self.one_gpu = checks is not None
+
+
+FORMATS = (
+    Format(("af",), scan_af, lambda a: a.af_clusters or a.af_details, "--af-clusters / --af-details belong to --format af",
+           (_excludes("clusters the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET), _no_fst)),
+    Format(("ehh",), scan_ehh,
+           lambda a: a.ehh_core_offset is not None or a.ehh_cores or a.ehh_flanks is not None or a.ehh_ref is not None,
+           "--ehh-core-offset / --ehh-cores / --ehh-flanks / --ehh-ref belong to --format ehh",
+           (_excludes("scans the sequences of -u (default: all) on the full matrix: not with -A / -B / --panel / -l / --compact",
+                      *_OF_SUBSET, "compact"), _ehh_values, _no_identity, _no_fst)),
+    Format(("hapstats",), scan_hapstats, None, None,
+           (_excludes("compares the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET), _no_identity, _no_fst)),
+    Format(("ld",), scan_ld, lambda a: a.ld_min_maf is not None or a.ld_max_sites is not None,
+           "--ld-min-maf / --ld-max-sites belong to --format ld",
+           (_excludes("compares the sites among the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET),
+            _no_identity, _no_fst, _ld_values)),
+    Format(("diploid",), scan_diploid, lambda a: a.roh_min_sites is not None or a.ind_table is not None,
+           "--roh-min-sites / --ind-table belong to --format diploid",
+           (_excludes("pairs the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET), _no_identity, _no_fst,
+            _diploid_values)),
+    Format(("ibs",), scan_ibs,
+           lambda a: a.ibs_min_sites is not None or a.ibs_pairs is not None or a.ibs_segments is not None or a.ibs_pair_table is not None,
+           "--ibs-min-sites / --ibs-pairs / --ibs-segments / --ibs-pair-table belong to --format ibs",
+           (_excludes("pairs the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET), _no_identity, _no_fst,
+            _ibs_values)),
+    Format(("dstat",), scan_dstat,
+           lambda a: a.quartet or a.dstat_polarize or a.dstat_blocks is not None or a.dstat_summary is not None,
+           "--quartet / --dstat-polarize / --dstat-blocks / --dstat-summary belong to --format dstat",
+           (_takes_panel(4, 8, "P1.txt P2.txt P3.txt O.txt [more lists]: 4 to 8 population lists"),
+            _excludes("compares the populations of --panel: not with -A / -B / -l / -u", *_OF_PANEL), _no_identity, _no_fst, _dstat_values)),
+    Format(("sfs",), scan_sfs,
+           lambda a: (a.sfs_outgroup is not None or a.sfs_pair or a.sfs_pairs_out is not None or a.sfs_spectra is not None
+                      or a.sfs_blocks is not None),
+           "--sfs-outgroup / --sfs-pair / --sfs-pairs-out / --sfs-spectra / --sfs-blocks belong to --format sfs",
+           (_takes_panel(1, 8, "A.txt [B.txt ...]: 1 to 8 population lists"),
+            _excludes("reads the spectra of the populations of --panel: not with -A / -B / -l / -u", *_OF_PANEL), _no_identity, _no_fst,
+            _sfs_values)),
+    Format(("pairdist",), scan_pairdist,
+           lambda a: (a.pairdist_outgroup is not None or a.pairdist_panels is not None or a.pairdist_hist is not None
+                      or a.pairdist_bins is not None or a.pairdist_bin_width is not None),
+           "--pairdist-outgroup / --pairdist-panels / --pairdist-hist / --pairdist-bins / --pairdist-bin-width belong to --format pairdist",
+           (_takes_panel(1, 8, "a.txt b.txt [more.txt]: 1 to 8 population lists"),
+            _excludes("reads the distances of the populations of --panel: not with -A / -B / -l / -u", *_OF_PANEL),
+            _has_no_threshold("counts differing sites: it has no -t / -r"), _pairdist_values)),
+    Format(("kinship",), scan_kinship,
+           lambda a: a.kin_threshold is not None or a.kin_pairs is not None or bool(a.kin_watch) or a.kin_watch_table is not None,
+           "--kin-threshold / --kin-pairs / --kin-watch / --kin-watch-table belong to --format kinship",
+           (_excludes("pairs the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET),
+            _has_no_threshold("counts genotypes: it has no -t / -r (the kinship threshold is --kin-threshold)"), _kinship_values)),
+    Format(("ihs", "xpehh"), scan_ihs,
+           lambda a: (a.ihs_min_maf is not None or a.ihs_cutoff is not None or a.ihs_max_extend is not None
+                      or a.ihs_max_extend_sites is not None or a.ihs_bins is not None or a.ihs_keep_edge),
+           "--ihs-min-maf / --ihs-cutoff / --ihs-max-extend / --ihs-max-extend-sites / --ihs-bins / --ihs-keep-edge belong to "
+           "--format ihs and --format xpehh",
+           (_has_no_threshold("integrates haplotype homozygosity: it has no -t / -r"),
+            _when("ihs", _excludes("scans the sequences of -u (default: all): not with -A / -B / --panel / -l", *_OF_SUBSET)),
+            _when("xpehh", _takes_panel(2, 2, "a.txt b.txt: two population lists")),
+            _when("xpehh", _excludes("compares the two populations of --panel: not with -A / -B / -l / -u", *_OF_PANEL)), _ihs_values)),
+    Format(("pica2", "hfst", "tajd", "fst3pi", "all"), scan_classic),  # their checks: classic_plan(), sim_list_refusal()
+)
+
+
+def refusal(args):
+    """What the command line does not combine with: one line (exit 2, before any file is read or device opened), or None.  The table
+    is walked in its order: the entry of --format runs its checks, every entry before and after it answers for its own options."""
+    f = f"--format {args.format}"
+    for entry in FORMATS:
+        if args.format not in entry.formats:
+            if entry.own is not None and entry.own(args):
+                return entry.stray
+        elif entry.one_gpu:
+            if args.sim_list:
+                return f"{f} scans a presence matrix (--matrix / --bed): not with --sim-list"
+            if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+                return f"{f} is a one-process, one-GPU scan: not under torch.distributed.run"
+            if args.devices > 1:
+                return f"{f} runs on one GPU: not with --devices N"
+            for check in entry.checks:
+                message = check(args)
+                if message:
+                    return message
+    return None
 
 
 def main():
@@ -1446,522 +1786,33 @@ def main():
         ap.error("--sim-list replaces --matrix / --bed: give one or the other")
     if not args.sim_list and not (args.matrix and args.bed):
         ap.error("give --matrix and --bed, or --sim-list")
-    refusal = (af_refusal(args) or ehh_refusal(args) or hap_refusal(args) or ld_refusal(args) or diploid_refusal(args) or ibs_refusal(args) or dstat_refusal(args)
-               or sfs_refusal(args) or pairdist_refusal(args) or kinship_refusal(args) or ihs_refusal(args))
-    if refusal:
-        print(f"Error: {refusal}", file=sys.stderr)
-        sys.exit(2)
-    if args.format == "pairdist":
-        return scan_pairdist(args)
-    if args.format == "kinship":
-        return scan_kinship(args)
-    if args.format in ("ihs", "xpehh"):
-        return scan_ihs(args)
+    message = refusal(args)
+    if message:
+        fail(message)
+    fmt = args.format
+    entry = next(e for e in FORMATS if fmt in e.formats)
     if args.sim_list:
-        refusal = sim_list_refusal(args)
-        if refusal:
-            print(f"Error: {refusal}", file=sys.stderr)
-            sys.exit(2)
-    threshold_text = None
+        message = sim_list_refusal(args)
+        if message:
+            fail(message)
+    args.threshold_text = None
     if args.threshold is not None:
-        args.threshold, threshold_text = args.threshold
+        args.threshold, args.threshold_text = args.threshold
     # Multi-GPU: `python -m torch.distributed.run --nproc-per-node N scripts/impop_scan.py ...` — the BED rows
     # are sharded over ranks, each rank uploads only the slab its windows touch, scans it, and ONE
     # all-gather of the fixed-size records per scan brings everything to rank 0, which prints.
-    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    # --panel on the all-pairs path (impop_pairwise_scan_panel) is the one-process form: refused before any rank waits for another
-    panel_allpairs = bool(args.panel) and (args.format in ("tajd", "all") or args.round_digits not in (None, "none") or args.identity != "match")
-    if panel_allpairs and world > 1:
-        print("Error: --panel with --format tajd / all, -r N or --identity dice runs on one GPU (impop_pairwise_scan_panel has no sharded "
-              "form): not under torch.distributed.run", file=sys.stderr)
-        sys.exit(2)
-    if args.panel and args.fst_method == "grouped":
-        print("Error: --panel has no --fst-method grouped (the panel calls are the direct method; use -A / -B per pair)", file=sys.stderr)
-        sys.exit(2)
-    if args.panel and args.format in ("tajd", "all") and args.sample_list:
-        print("Error: --panel with --format tajd / all takes every panel's list as its sample list: not with -l", file=sys.stderr)
-        sys.exit(2)
-    if args.panel and args.format != "sfs" and not 2 <= len(args.panel) <= 8:
-        print("Error: --panel takes 2 to 8 population lists", file=sys.stderr)
-        sys.exit(2)
-    if world > 1:
-        import torch
-        import torch.distributed as dist
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        if args.backend == "nccl":
-            torch.cuda.set_device(local_rank)
-            dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
-        else:
-            dist.init_process_group(args.backend, rank=rank, world_size=world)
+    rank, world, local_rank = 0, 1, 0
+    if fmt not in ("pairdist", "kinship", "ihs", "xpehh"):  # these four never read the launcher's variables: device 0 unless --device
+        rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+        local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    plan = None if entry.one_gpu else classic_plan(args, rank, world, local_rank)
     if args.device is None:
         args.device = local_rank if (world == 1 or args.backend == "nccl") else 0
-    if args.devices > 1 and (world > 1 or args.panel or args.compact):
-        print("Error: --devices N is the one-process form: not under torch.distributed.run, not with --panel / --compact", file=sys.stderr)
-        sys.exit(2)
-    fmt = args.format
-    grouped_fst = fmt == "hfst" and args.fst_method == "grouped"
-
-    # ---- what is computed: (threshold, round digits) behind the pica2-derived columns, round digits of the h-fst table
-    given_r = args.round_digits
-    if fmt in ("tajd", "all"):  # run_tajd.sh:9-10
-        pica_t = 0.999 if args.threshold is None else args.threshold
-        pica_r = 5 if given_r is None else (None if given_r == "none" else given_r)
-    else:
-        pica_t = 1.0 if args.threshold is None else args.threshold
-        pica_r = None if given_r in (None, "none") else given_r
-    if fmt == "hfst":
-        fst_r = None if given_r in (None, "none") else given_r
-        if args.threshold is not None and not grouped_fst:
-            print("Error: --format hfst takes -t only with --fst-method grouped (h-fst.py has no threshold)", file=sys.stderr)
-            sys.exit(2)
-    else:
-        fst_r = None if args.fst_round_digits in (None, "none") else args.fst_round_digits
-    if args.fst_round_digits is not None and fmt not in ("all",):
-        print("Error: --fst-round-digits belongs to --format all (use -r with --format hfst)", file=sys.stderr)
-        sys.exit(2)
-    grouped_t = 0.999 if args.threshold is None else args.threshold  # hud.py -t
-    pica_pairs = not (pica_t >= 1.0 and pica_r is None and args.identity == "match")
-    fst_pairs = grouped_fst or fst_r is not None or args.identity != "match"
-    want_pica = fmt in ("pica2", "tajd", "all", "fst3pi")
-    want_fst = fmt in ("hfst", "all") and not args.panel
-    need_pairs = (want_pica and pica_pairs) or (want_fst and fst_pairs) or fmt == "af"
-    if args.panel and fmt not in ("hfst", "tajd", "all", "dstat", "sfs"):
-        print("Error: --panel belongs to --format hfst (every pair), tajd (every panel), all (both) or dstat (quartets)", file=sys.stderr)
-        sys.exit(2)
-    # --panel: the pair tables come from the streaming K-population scan (impop_scan_multi) when h-fst is unrounded on `match`,
-    # else - like every per-panel tajd table - from impop_pairwise_scan_panel: one Gram pass per window for all panels and pairs
-    panel_fst = bool(args.panel) and fmt in ("hfst", "all")
-    panel_tajd = bool(args.panel) and fmt in ("tajd", "all")
-    if args.panel:
-        need_pairs = panel_tajd or (panel_fst and fst_pairs)
-    dstat_quartets = parse_quartets(args.quartet, len(args.panel)) if fmt == "dstat" else None
-    sfs_pairs = parse_sfs_pairs(args.sfs_pair, len(args.panel)) if fmt == "sfs" else []
-
-    thr_txt = threshold_text if threshold_text is not None else repr(float(pica_t))  # as typed, like "${THRESHOLD}" in the drivers
-    r_txt = "" if pica_r is None else str(pica_r)
-    if args.sim_list:
-        return scan_sim_list(args, fmt, pica_t, pica_r, fst_r, thr_txt, r_txt)
-
-    # ---- matrices by chromosome, BED rows to their matrix
-    mats = [load_matrix(p) for p in args.matrix]
-    def full_name(chrom):
-        return chrom if chrom.startswith(args.region_prefix) else args.region_prefix + chrom
-    by_contig = {}
-    for p, mf in zip(args.matrix, mats):
-        key = full_name(mf.contig) if mf.contig else ""
-        if key in by_contig:
-            print(f"Error: two matrices for contig '{mf.contig}' ({p})", file=sys.stderr)
-            sys.exit(2)
-        by_contig[key] = mf
-    if "" in by_contig and len(mats) > 1:
-        print("Error: several --matrix files need a contig name each (matrixio `contig`)", file=sys.stderr)
-        sys.exit(2)
-    bed = read_bed(args.bed, fmt)
-    rows, per_mat, row_bed = [], {}, []  # row_bed[i] = index of row i among the usable BED rows (--ehh-cores is per BED row)
-    ehh_cores = read_core_positions(args.ehh_cores) if args.ehh_cores else None
-    if ehh_cores is not None and len(ehh_cores) != len(bed):
-        print(f"Error: --ehh-cores holds {len(ehh_cores)} positions for {len(bed)} BED rows", file=sys.stderr)
-        sys.exit(2)
-    for bed_no, (chrom, s, e) in enumerate(bed):
-        region = f"{full_name(chrom)}:{s}-{e}"
-        key = "" if "" in by_contig else full_name(chrom)
-        if key not in by_contig:
-            print(f"Warning: Skipping region {region}: no matrix holds chromosome {chrom}", file=sys.stderr)
-            continue
-        per_mat.setdefault(key, []).append(len(rows))
-        rows.append((region, key, s, e))
-        row_bed.append(bed_no)
-    n_rows = len(rows)
-    L_col = np.array([e - s for _, _, s, e in rows], dtype=np.int64)  # LENGTH = end - start (run_pica2_impg.sh:133)
-    if args.sequence_length is not None:
-        if fmt != "pica2" or args.sequence_length <= 0:
-            print("Error: --sequence-length (a positive integer) belongs to --format pica2 (run_pica2_impg.sh -l)", file=sys.stderr)
-            sys.exit(2)
-        L_col[:] = args.sequence_length  # EFFECTIVE_LENGTH, run_pica2_impg.sh:153-157
-    out = (open(args.output, "w") if args.output else sys.stdout) if rank == 0 else open(os.devnull, "w")
-
-    sample_count = None
-    if args.sample_list:
-        sample_count = awk_line_count(args.sample_list)  # run_tajd.sh:83
-        if fmt in ("tajd", "all") and sample_count < 2:
-            print(f"Error: Need at least two samples to compute Tajima's D (found {sample_count})", file=sys.stderr)  # :84-87
-            sys.exit(1)
-
-    f64 = lambda: np.full(n_rows, np.nan)  # noqa: E731
-    col = {k: f64() for k in ("pi_site", "tajima_d", "fst", "pi_a", "pi_b", "pi_xy", "dxy", "da", "pi3_a", "pi3_b", "pi3_c")}
-    s_all = np.zeros(n_rows, dtype=np.int64)
-    panel_tables, panel_labels, panel_taj = None, None, None
-    samples_col = 0
-    af_recs = np.zeros(n_rows, dtype=impop_amd.CLUSTER_DTYPE)
-    af_clusters = [None] * n_rows
-    ehh_lines = [None] * n_rows
-    hap_recs = np.zeros(n_rows, dtype=impop_amd.HAPLOTYPE_DTYPE)
-    ld_recs = np.zeros(n_rows, dtype=impop_amd.LD_DTYPE)
-    ld_pos = [None] * n_rows
-    dip_recs = np.zeros(n_rows, dtype=impop_amd.DIPLOID_DTYPE)
-    dip_ind = [None] * n_rows  # per row: (sample names, impop_diploid_ind rows)
-    ibs_recs = np.zeros(n_rows, dtype=impop_amd.IBS_WINDOW_DTYPE)
-    ibs_n_pairs = np.zeros(n_rows, dtype=np.int64)
-    ibs_seg_fh = open(args.ibs_segments, "w") if fmt == "ibs" and args.ibs_segments and rank == 0 else None
-    ibs_pair_fh = open(args.ibs_pair_table, "w") if fmt == "ibs" and args.ibs_pair_table and rank == 0 else None
-    if ibs_seg_fh:
-        print(IBS_SEGMENT_HEADER, file=ibs_seg_fh)
-    if ibs_pair_fh:
-        print(IBS_PAIR_HEADER, file=ibs_pair_fh)
-    dstat_recs = np.zeros((n_rows, len(dstat_quartets or [])), dtype=impop_amd.DSTAT_DTYPE)
-    dstat_sizes = [None] * n_rows  # per row: the populations' sizes in its matrix
-    sfs_recs = np.zeros((n_rows, len(args.panel) if fmt == "sfs" else 0), dtype=impop_amd.SFS_DTYPE)
-    sfs_pair_recs = np.zeros((n_rows, len(sfs_pairs)), dtype=impop_amd.SFS_PAIR_DTYPE)
-    sfs_sizes = [None] * n_rows
-    sfs_blocks, sfs_block_of = None, None  # --sfs-spectra: name -> [blocks, bins...] sums; the block of every row
-    if fmt == "sfs" and args.sfs_spectra:
-        from impop_amd.distributed import shard_range
-        n_blocks = args.sfs_blocks or 1
-        sfs_block_of = np.zeros(n_rows, dtype=np.int64)
-        for j in range(n_blocks):
-            lo, hi = shard_range(n_rows, n_blocks, j)
-            sfs_block_of[lo:hi] = j
-    for key, idx in per_mat.items():
-        mf = by_contig[key]
-        names = mf.names
-        idx = np.array(idx)
-        wins = []
-        for i in idx:
-            _, _, s, e = rows[i]
-            b, en = mf.site_range(s, e)
-            wins.append((b, en, int(L_col[i])))
-        if fmt == "ehh":  # cores and the reference sequence are checked before the matrix goes up
-            cores = []
-            for i, (b, en, _) in zip(idx, wins):
-                if ehh_cores is not None:
-                    c = mf.site_range(ehh_cores[row_bed[i]], ehh_cores[row_bed[i]])[0]
-                else:
-                    c = b + ((en - b) // 2 if args.ehh_core_offset is None else args.ehh_core_offset)
-                if not b <= c < en:
-                    print(f"Error: --format ehh: the core of {rows[i][0]} (site {c}) is outside the window's sites [{b}, {en})", file=sys.stderr)
-                    sys.exit(2)
-                cores.append(c)
-            ref_hap = 0
-            if args.ehh_ref is not None:
-                if args.ehh_ref not in names:
-                    print(f"Error: --ehh-ref {args.ehh_ref} is not a sequence of the matrix", file=sys.stderr)
-                    sys.exit(2)
-                ref_hap = list(names).index(args.ehh_ref)
-        run = Runner(args, mf, wins, need_pairs, rank, world, local_rank)
-        mask_p = mask_a = mask_b = None
-        n_matched = mf.n_hap
-        if args.sample_list:
-            mask_p = flags_for(args.sample_list, names)
-        if args.subset:
-            mask_p = flags_for(args.subset, names)
-        if mask_p is not None:
-            n_matched = int(mask_p.sum())
-        if args.pop_a and args.pop_b:
-            mask_a, mask_b = flags_for(args.pop_a, names), flags_for(args.pop_b, names)
-            if not mask_a.any() or not mask_b.any():
-                print("Error: No valid sequences found in one or both populations", file=sys.stderr)  # h-fst.py:319-321
-                sys.exit(1)
-        if fmt == "sfs":
-            panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
-            pops = [flags_for(f, names) for f in args.panel]
-            sizes = [int(p.sum()) for p in pops]
-            for k, n_k in enumerate(sizes):  # what impop_sfs_scan would refuse, with the lists' names
-                if n_k == 0:
-                    print(f"Error: --format sfs: {panel_labels[k]} selects no sequence of the matrix", file=sys.stderr)
-                    run.close()
-                    sys.exit(2)
-            for a, b in sfs_pairs:
-                if (pops[a] & pops[b]).any():
-                    print(f"Error: --format sfs: {panel_labels[a]} and {panel_labels[b]} share a sequence; the two populations of a pair "
-                          "must be disjoint", file=sys.stderr)
-                    run.close()
-                    sys.exit(2)
-            outgroup = None if args.sfs_outgroup is None else args.sfs_outgroup - 1
-            tables = (("sfs",) + (("jsfs",) if sfs_pairs else ())) if args.sfs_spectra else ()
-            batch = SFS_BATCH_ROWS if tables else max(len(idx), 1)
-            for w0 in range(0, len(idx), batch):
-                part = idx[w0:w0 + batch]
-                st, pr, sfs, jsfs = run.sfs(pops, sfs_pairs, outgroup, tables, w0, w0 + len(part))
-                sfs_recs[part] = st
-                if sfs_pairs:
-                    sfs_pair_recs[part] = pr
-                if tables:
-                    named = [(f"sfs_{panel_labels[k]}", t) for k, t in enumerate(sfs)]
-                    named += [(f"jsfs_{panel_labels[a]}_{panel_labels[b]}", t) for (a, b), t in zip(sfs_pairs, jsfs or [])]
-                    if sfs_blocks is None:
-                        sfs_blocks = {nm: np.zeros((args.sfs_blocks or 1,) + t.shape[1:], dtype=np.uint64) for nm, t in named}
-                    for nm, t in named:
-                        if sfs_blocks[nm].shape[1:] != t.shape[1:]:
-                            print(f"Error: --sfs-spectra: {nm} has another shape in the matrix of {key or 'the run'} (the lists select "
-                                  "another number of its sequences); write the spectra per matrix", file=sys.stderr)
-                            run.close()
-                            sys.exit(2)
-                        np.add.at(sfs_blocks[nm], sfs_block_of[part], t.astype(np.uint64))
-            for i in idx:
-                sfs_sizes[i] = sizes
-            run.close()
-            continue
-        if fmt == "dstat":
-            panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
-            pops = [flags_for(f, names) for f in args.panel]
-            sizes = [int(p.sum()) for p in pops]
-            for q in dstat_quartets:  # what impop_dstat_scan would refuse, with the lists' names
-                for a in q:
-                    if sizes[a] == 0:
-                        print(f"Error: --format dstat: {panel_labels[a]} selects no sequence of the matrix", file=sys.stderr)
-                        run.close()
-                        sys.exit(2)
-                for a, b in ((a, b) for i, a in enumerate(q) for b in q[i + 1:]):
-                    if (pops[a] & pops[b]).any():
-                        print(f"Error: --format dstat: {panel_labels[a]} and {panel_labels[b]} share a sequence; the four populations of a "
-                              "quartet must be disjoint", file=sys.stderr)
-                        run.close()
-                        sys.exit(2)
-            dstat_recs[idx] = run.dstat(pops, dstat_quartets, bool(args.dstat_polarize))
-            for i in idx:
-                dstat_sizes[i] = sizes
-            run.close()
-            continue
-        if args.panel:
-            panel_labels = [os.path.splitext(os.path.basename(f))[0] for f in args.panel]
-            pops = [flags_for(f, names) for f in args.panel]
-            pr = pan = pw = None
-            if panel_fst and not fst_pairs:
-                pr = run.panel(pops)
-            one_call = panel_fst and fst_pairs and panel_tajd and pica_r == fst_r
-            if panel_tajd:
-                pan, pr2, pw = run.panel_allpairs(pops, pica_t, pica_r, True, one_call)
-                if one_call:
-                    pr = pr2
-            if panel_fst and pr is None:  # (h-fst.py has no threshold: it only groups pica2)
-                _, pr, _ = run.panel_allpairs(pops, pica_t, fst_r, False, True)
-            if pr is not None:
-                if panel_tables is None:
-                    panel_tables = np.zeros((n_rows, pr.shape[1]), dtype=pr.dtype)
-                panel_tables[idx] = pr
-            if pan is not None:
-                K = len(pops)
-                if panel_taj is None:
-                    panel_taj = {"pi_site": np.full((n_rows, K), np.nan), "tajima_d": np.full((n_rows, K), np.nan),
-                                 "s_all": np.zeros(n_rows, dtype=np.int64), "samples": [awk_line_count(f) for f in args.panel]}
-                panel_taj["pi_site"][idx] = pan["pi_site"]
-                panel_taj["s_all"][idx] = pw["s_all"]
-                D = pan["tajima_d"].copy()
-                for k in range(K):
-                    cnt_k, matched = panel_taj["samples"][k], int(pops[k].sum())
-                    if cnt_k < 2:
-                        print(f"Error: Need at least two samples to compute Tajima's D (found {cnt_k})", file=sys.stderr)  # run_tajd.sh:84-87
-                        sys.exit(1)
-                    if cnt_k != matched and len(idx):  # run_tajd.sh:180: n = the list's LINE count (see the -l case below)
-                        print(f"Warning: sample list {panel_labels[k]} has {cnt_k} lines but selects {matched} haplotypes; Tajima's D uses "
-                              f"n = {cnt_k} like run_tajd.sh", file=sys.stderr)
-                        pi_txt = np.array([float(f"{float(x):.8f}") for x in pan["pi_site"][:, k]])
-                        D[:, k] = run.ctx.tajimas_d(np.full(len(idx), cnt_k, dtype=np.int64), pw["s_all"].astype(np.float64), pi_txt)
-                panel_taj["tajima_d"][idx] = D
-            run.close()
-            continue
-        if fmt == "af":
-            from impop_amd.af import _sample_of, clusters_from_ranks
-            want_members = bool(args.af_clusters or args.af_details)
-            members = [_sample_of(names[i]) for i in (range(mf.n_hap) if mask_p is None else np.flatnonzero(mask_p))]
-            if len(set(members)) != len(members):
-                # af.py names its nodes by the cut name, so two sequences of one name would be ONE sample there, while the
-                # records count sequences: the main table and the side tables of one run would disagree
-                dup = sorted({m for m in members if members.count(m) > 1})[0]
-                print(f"Error: --format af needs distinct sequence names before the first ':' ('{dup}' names several rows of the matrix)",
-                      file=sys.stderr)
-                run.close()
-                sys.exit(2)
-            res = run.bm.cluster_scan(run.local_wins, mask_p=mask_p, kind=args.identity, threshold=pica_t, round_digits=pica_r,
-                                      want_members=want_members)
-            if want_members:
-                af_recs[idx] = res[0]
-                for i, row in zip(idx, res[1]):
-                    af_clusters[i] = clusters_from_ranks(row, members)
-            else:
-                af_recs[idx] = res
-            run.close()
-            continue
-        if fmt == "hapstats":
-            if mask_p is not None and not mask_p.any():
-                print("Error: --format hapstats: -u selects no sequence of the matrix", file=sys.stderr)
-                run.close()
-                sys.exit(2)
-            hap_recs[idx] = run.hapstats(mask_p)
-            run.close()
-            continue
-        if fmt == "ld":
-            if mask_p is not None and not mask_p.any():
-                print("Error: --format ld: -u selects no sequence of the matrix", file=sys.stderr)
-                run.close()
-                sys.exit(2)
-            recs, used = run.ld(mask_p, ld_min_mac(0.05 if args.ld_min_maf is None else args.ld_min_maf, n_matched), args.ld_max_sites or 512)
-            ld_recs[idx] = recs
-            for i, r, u in zip(idx, recs, used):
-                if r["omega_split"]:
-                    c = int(u[int(r["omega_split"])])
-                    ld_pos[i] = int(mf.site_pos[c]) if mf.site_pos is not None else int(mf.origin + c)
-            run.close()
-            continue
-        if fmt == "diploid":
-            from impop_amd.popnames import pair_haplotypes
-            chosen = None if mask_p is None else [nm for nm, f in zip(names, mask_p) if f]
-            dip_pairs, dip_samples, unpaired = pair_haplotypes(list(names), chosen)
-            if unpaired:
-                print(f"Warning: --format diploid: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
-                      + " ".join(unpaired), file=sys.stderr)
-            if len(dip_pairs) < 1:
-                print("Error: --format diploid: no sample with both of its haplotypes (sample#1#..., sample#2#...) among the sequences",
-                      file=sys.stderr)
-                run.close()
-                sys.exit(2)
-            min_run = 50 if args.roh_min_sites is None else args.roh_min_sites
-            if args.ind_table:
-                recs, ind_rows = run.diploid(dip_pairs, min_run, True)
-                for i, q in zip(idx, ind_rows):
-                    dip_ind[i] = (dip_samples, q)
-            else:
-                recs = run.diploid(dip_pairs, min_run, False)
-            dip_recs[idx] = recs
-            run.close()
-            continue
-        if fmt == "ibs":
-            ibs_kw = dict(min_sites=50 if args.ibs_min_sites is None else args.ibs_min_sites, windows=[(b, en) for b, en, _ in wins],
-                          want_segments=ibs_seg_fh is not None)
-            if (args.ibs_pairs or "all") == "diploid":
-                from impop_amd.popnames import pair_haplotypes
-                chosen = None if mask_p is None else [nm for nm, f in zip(names, mask_p) if f]
-                ibs_pairs, _, unpaired = pair_haplotypes(list(names), chosen)
-                if unpaired:
-                    print(f"Warning: --format ibs: {len(unpaired)} sequences are not one of a sample's two haplotypes and are left out: "
-                          + " ".join(unpaired), file=sys.stderr)
-                if len(ibs_pairs) < 1:
-                    print("Error: --format ibs: no sample with both of its haplotypes (sample#1#..., sample#2#...) among the sequences",
-                          file=sys.stderr)
-                    run.close()
-                    sys.exit(2)
-                ibs_kw["pairs"] = ibs_pairs
-            else:
-                if n_matched < 2:
-                    print(f"Error: --format ibs: {n_matched} sequences make no pair", file=sys.stderr)
-                    run.close()
-                    sys.exit(2)
-                ibs_kw["mask_p"] = mask_p
-            prec, segs, wrec, _ = run.bm.ibs_scan(**ibs_kw)
-            ibs_recs[idx] = wrec
-            ibs_n_pairs[idx] = len(prec)
-            site_bp = (lambda c, mf=mf: int(mf.site_pos[c])) if mf.site_pos is not None else (lambda c, mf=mf: int(mf.origin + c))
-            if ibs_seg_fh:
-                write_ibs_segments(ibs_seg_fh, names, segs, site_bp, header=False)
-            if ibs_pair_fh:
-                write_ibs_pairs(ibs_pair_fh, names, prec, header=False)
-            run.close()
-            continue
-        if fmt == "ehh":
-            recs = run.bm.ehh_scan([(b, en) for b, en, _ in wins], cores, mask=mask_p, ref_hap=ref_hap, flanks=args.ehh_flanks or "reference")
-            for i, c, r in zip(idx, cores, recs):
-                core_bp = int(mf.site_pos[c]) if mf.site_pos is not None else int(mf.origin + c)
-                ehh_lines[i] = ehh_rows(rows[i][0], int(L_col[i]), core_bp, r)
-            run.close()
-            continue
-        if fmt == "fst3pi":
-            if mask_a is None:
-                print("Error: --format fst3pi needs -A and -B", file=sys.stderr)
-                sys.exit(2)
-            if (mask_a & mask_b).any():
-                print("Error: --format fst3pi needs disjoint populations", file=sys.stderr)
-                sys.exit(2)
-            if pica_pairs:  # run_fst_impg.sh:73: pica2.py -t T -r R on the lists A, B and A u B
-                for name, sel in (("pi3_a", mask_a), ("pi3_b", mask_b), ("pi3_c", mask_a | mask_b)):
-                    col[name][idx] = run.pairs(sel, None, None, pica_t, pica_r, False)["pi_site"]
-            else:
-                from impop_amd.drivers import pi_union_site
-                res = run.stream(None, mask_a, mask_b)
-                nA, nB = int(mask_a.sum()), int(mask_b.sum())
-                col["pi3_a"][idx], col["pi3_b"][idx] = res["pi_a"], res["pi_b"]
-                col["pi3_c"][idx] = [pi_union_site(r, nA, nB, int(L)) for r, L in zip(res, L_col[idx])]
-            run.close()
-            continue
-        want_s = fmt in ("tajd", "all")
-        one_call = want_pica and want_fst and pica_pairs and fst_pairs and pica_r == fst_r and not grouped_fst
-        pica_rec = fst_rec = None
-        if want_pica:
-            pica_rec = run.pairs(mask_p, mask_a if one_call else None, mask_b if one_call else None, pica_t, pica_r, want_s) \
-                if pica_pairs else run.stream(mask_p, mask_a, mask_b)
-            if one_call or (want_fst and not pica_pairs and not fst_pairs):
-                fst_rec = pica_rec
-        if want_fst and fst_rec is None and mask_a is not None:
-            fst_rec = run.pairs(None, mask_a, mask_b, grouped_t, fst_r, False, args.fst_method if grouped_fst else "direct") \
-                if fst_pairs else run.stream(None, mask_a, mask_b)
-        if pica_rec is not None:
-            col["pi_site"][idx] = pica_rec["pi_site"]
-            if want_s:
-                s_all[idx] = pica_rec["s_all"]
-                D = pica_rec["tajima_d"]
-                samples_col = sample_count if sample_count is not None else mf.n_hap
-                if sample_count is not None and sample_count != n_matched and len(idx):
-                    # run_tajd.sh:180 hands tj_d.py `-n SAMPLE_COUNT`, the list's LINE count, whatever the number of
-                    # haplotypes those lines select (a bare sample name selects two, an unknown name none, a repeated
-                    # line counts twice).  The scan evaluated D with n = matched haplotypes: redo D (on the GPU,
-                    # impop_tajimas_d) with the reference's n, pi through the same "%.8f" text (run_tajd.sh:174) and S.
-                    print(f"Warning: sample list has {sample_count} lines but selects {n_matched} haplotypes; Tajima's D uses "
-                          f"n = {sample_count} like run_tajd.sh", file=sys.stderr)
-                    pi_txt = np.array([float(f"{float(x):.8f}") for x in pica_rec["pi_site"]])
-                    D = run.ctx.tajimas_d(np.full(len(idx), sample_count, dtype=np.int64), pica_rec["s_all"].astype(np.float64), pi_txt)
-                col["tajima_d"][idx] = D
-        if fst_rec is not None:
-            for k in ("fst", "pi_a", "pi_b", "pi_xy", "dxy", "da"):
-                col[k][idx] = fst_rec[k]
-        run.close()
-
-    if fmt == "af":
-        regions = [r[0] for r in rows]
-        write_af_table(out, regions, L_col, thr_txt, af_recs)
-        if args.af_clusters:
-            with open(args.af_clusters, "w", newline="") as fh:
-                write_af_clusters(fh, regions, af_clusters)
-        if args.af_details:
-            with open(args.af_details, "w", newline="") as fh:
-                write_af_details(fh, regions, af_clusters, float(pica_t))
-    elif fmt == "hapstats":
-        write_hap_table(out, [r[0] for r in rows], L_col, hap_recs)
-    elif fmt == "ld":
-        write_ld_table(out, [r[0] for r in rows], L_col, ld_recs, ld_pos)
-    elif fmt == "diploid":
-        write_diploid_table(out, [r[0] for r in rows], dip_recs)
-        if args.ind_table:
-            with open(args.ind_table, "w") as fh:
-                print(DIPLOID_IND_HEADER, file=fh)
-                for (reg, _, _, _), entry in zip(rows, dip_ind):
-                    write_diploid_ind_table(fh, [reg], entry[0], [entry[1]], header=False)
-    elif fmt == "ibs":
-        write_ibs_table(out, [r[0] for r in rows], L_col, ibs_n_pairs, ibs_recs)
-        for fh in (ibs_seg_fh, ibs_pair_fh):
-            if fh:
-                fh.close()
-    elif fmt == "dstat":
-        write_dstat_table(out, [r[0] for r in rows], panel_labels or [], dstat_quartets, dstat_sizes, dstat_recs)
-        if args.dstat_summary:
-            with open(args.dstat_summary, "w") as fh:
-                write_dstat_summary(fh, panel_labels or [], dstat_quartets, dstat_sizes, dstat_recs, args.dstat_blocks)
-    elif fmt == "sfs":
-        write_sfs_table(out, [r[0] for r in rows], panel_labels or [], sfs_sizes, sfs_recs)
-        if args.sfs_pairs_out:
-            with open(args.sfs_pairs_out, "w") as fh:
-                write_sfs_pairs(fh, [r[0] for r in rows], panel_labels or [], sfs_pairs, sfs_pair_recs)
-        if args.sfs_spectra:
-            np.savez(args.sfs_spectra, **(sfs_blocks or {}))
-    elif fmt == "ehh":
-        print(EHH_HEADER, file=out)
-        for lines in ehh_lines:
-            for line in lines:
-                print(line, file=out)
-    else:
-        write_tables(out, args, fmt, [r[0] for r in rows], L_col, col, s_all, samples_col, thr_txt, r_txt, panel_tables, panel_labels,
-                     panel_taj=panel_taj)
-    if args.output or rank != 0:
-        out.close()
+    if plan is not None and args.sim_list:
+        return scan_sim_list(args, fmt, plan.pica_t, plan.pica_r, plan.fst_r, plan.thr_txt, plan.r_txt)
+    job = Job(args, rank, world, local_rank)
+    job.plan = plan
+    entry.scan(args, job)
     if world > 1:
         import torch.distributed as dist
         dist.barrier()
