@@ -116,6 +116,23 @@ __device__ inline uint64_t wave_sum_u64(uint64_t v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// wave64 sum in the VALU alone (DPP: no LDS instruction, where every __shfl_xor is a ds_bpermute): lanes 48..63 get the total.
+// Within a row of 16 lanes a butterfly (lane ^ 1, lane ^ 2, 7 - lane within 8, 15 - lane within 16), then the last lane of row 0
+// into row 1 and of row 2 into row 3 (row_bcast:15, rows 1 and 3 written), then the last lane of row 1 into rows 2 and 3
+// (row_bcast:31).  A lane of a row that is not written adds the 0 given as the old value.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_add_u32(uint32_t v) {
+    return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xF, false);
+}
+__device__ __forceinline__ uint32_t wave_sum_u32_dpp(uint32_t v) {
+    v = dpp_add_u32<0xB1, 0xF>(v);   // quad_perm:[1,0,3,2]
+    v = dpp_add_u32<0x4E, 0xF>(v);   // quad_perm:[2,3,0,1]
+    v = dpp_add_u32<0x141, 0xF>(v);  // row_half_mirror
+    v = dpp_add_u32<0x140, 0xF>(v);  // row_mirror
+    v = dpp_add_u32<0x142, 0xA>(v);  // row_bcast:15
+    v = dpp_add_u32<0x143, 0xC>(v);  // row_bcast:31
+    return v;
+}
 __device__ inline double wave_sum_f64(double v) {  // fixed butterfly order: deterministic
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

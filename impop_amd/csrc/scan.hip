@@ -198,6 +198,9 @@ __device__ __forceinline__ void rare_range_coded(const uint64_t *__restrict__ ra
 // Exact integers, the same totals as the 8-byte entries give.  The 32-bit lane accumulators still hold: the tile budget counts 8
 // bytes per rare site whichever stream it sits in, so a tile has at most tile_blocks x 64 x 4 WPS / 8 <= 2^21 rare sites at
 // tile_blocks = 4096, 2^13 per lane, each adding at most 2 x 511 to a sum — below 2^24 next to the rows' 2^27.
+// SKIP (the instantiations with the distinct-row stream): a word past the range in every lane of the wave is not decoded (a
+// ballot): four table reads that add nothing — a bench tile holds 2.2 words per thread where a batch decodes SU = 4
+template <bool SKIP = false>
 __device__ __forceinline__ void single_range(const uint16_t *__restrict__ single, uint64_t s0, uint64_t s1, const uint16_t *hcode,
                                              const PopSizes &ps, LaneAcc32 &acc) {
     constexpr int SU = 4;
@@ -216,6 +219,9 @@ __device__ __forceinline__ void single_range(const uint16_t *__restrict__ single
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
             const uint64_t i = w + 256 * u;
+            if constexpr (SKIP) {
+                if (__builtin_amdgcn_ballot_w64(i < w1) == 0) continue;
+            }
             uint64_t x = i < w1 ? v[u] : ~0ull;
             uint32_t in = i < w1 ? 4u : 0u;
             if (i == w0 && head) { x |= (1ull << (16 * head)) - 1ull; in -= head; }
@@ -269,6 +275,38 @@ __device__ __forceinline__ void tile_reduce_store(LaneAcc &acc, TilePartial *out
     const uint64_t q0 = wave_sum_u64(acc.q_p), q1 = wave_sum_u64(acc.q_a), q2 = wave_sum_u64(acc.q_b),
                    q3 = wave_sum_u64(acc.q_ab);
     if (lane == 0) {
+        red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; red[wave][3] = s3;
+        red[wave][4] = q0; red[wave][5] = q1; red[wave][6] = q2; red[wave][7] = q3;
+    }
+    __syncthreads();
+    if (threadIdx.x < 8) {
+        const uint64_t v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        TilePartial *o = out + blockIdx.x;
+        switch (threadIdx.x) {
+            case 0: o->s_all = (uint32_t)v; break;
+            case 1: o->s_p = (uint32_t)v; break;
+            case 2: o->s_a = (uint32_t)v; break;
+            case 3: o->s_b = (uint32_t)v; break;
+            case 4: o->sum_p = v; break;
+            case 5: o->sum_a = v; break;
+            case 6: o->sum_b = v; break;
+            default: o->sum_ab = v; break;
+        }
+    }
+}
+
+// The same store from 32-bit lane sums, the wave sums taken in the VALU (wave_sum_u32_dpp): the 72 ds_bpermute of a wave in
+// tile_reduce_store are LDS instructions, and a workgroup that moves 20 KB is short of LDS issue slots before it is short of
+// anything else.  A lane sum is below 2^32 and 64 of them are not: each is summed as its low and its
+// high 16 bits, two wave sums below 2^22.
+__device__ __forceinline__ void tile_reduce_store32(const LaneAcc32 &acc, TilePartial *out) {
+    __shared__ uint64_t red[4][8];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    auto wide = [](uint32_t q) { return (uint64_t)wave_sum_u32_dpp(q & 0xFFFFu) + ((uint64_t)wave_sum_u32_dpp(q >> 16) << 16); };
+    const uint32_t s0 = wave_sum_u32_dpp(acc.s_all), s1 = wave_sum_u32_dpp(acc.s_p), s2 = wave_sum_u32_dpp(acc.s_a),
+                   s3 = wave_sum_u32_dpp(acc.s_b);
+    const uint64_t q0 = wide(acc.q_p), q1 = wide(acc.q_a), q2 = wide(acc.q_b), q3 = wide(acc.q_ab);
+    if (lane == 63) {
         red[wave][0] = s0; red[wave][1] = s1; red[wave][2] = s2; red[wave][3] = s3;
         red[wave][4] = q0; red[wave][5] = q1; red[wave][6] = q2; red[wave][7] = q3;
     }
@@ -429,12 +467,16 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
         __syncthreads();
         rare_range_coded(rare, t.rare_begin, t.rare_end, hcode, ps, acc);
-        if (has_single) single_range(single, sr.begin, sr.end, hcode, ps, acc);
+        if (has_single) single_range<UNIQ>(single, sr.begin, sr.end, hcode, ps, acc);
     }
-    LaneAcc wide;
-    wide.s_all = acc.s_all; wide.s_p = acc.s_p; wide.s_a = acc.s_a; wide.s_b = acc.s_b;
-    wide.q_p = acc.q_p; wide.q_a = acc.q_a; wide.q_b = acc.q_b; wide.q_ab = acc.q_ab;
-    tile_reduce_store(wide, out);
+    if constexpr (UNIQ) {
+        tile_reduce_store32(acc, out);
+    } else {
+        LaneAcc wide;
+        wide.s_all = acc.s_all; wide.s_p = acc.s_p; wide.s_a = acc.s_a; wide.s_b = acc.s_b;
+        wide.q_p = acc.q_p; wide.q_a = acc.q_a; wide.q_b = acc.q_b; wide.q_ab = acc.q_ab;
+        tile_reduce_store(wide, out);
+    }
 }
 
 // Any wps (n > 512 haplotypes, and every weighted matrix): the three masks of the WHOLE haplotype axis sit in
