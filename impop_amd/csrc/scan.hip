@@ -8,7 +8,8 @@
 // wps dwords with ceil(wps/4) fully coalesced 1 KiB wave loads (layout: internal.h).  The
 // three population masks are wave-uniform and live in SGPRs.  Integer partials per tile are
 // written once (no atomics => deterministic); a second tiny kernel sums each window's tiles
-// and evaluates the fp64 statistics in the reference's operation order.
+// and evaluates the fp64 statistics in the reference's operation order.  Plans of many small tiles on a unique-row route run
+// the second body instead, one WAVE per tile and four tiles per workgroup (scan_tiles_kernel_wave).
 #include <algorithm>
 #include <map>
 #include <vector>
@@ -170,19 +171,21 @@ struct RareMoments {
         acc.q_ab += ps.nB * a1 + ps.nA * b1 - 2u * ab;
     }
 };
+// NT threads share the entries [e0, e1), tid = this thread's index among them: the workgroup's 256, or the 64 of a one-wave tile
+template <int NT = 256>
 __device__ __forceinline__ void rare_range_coded(const uint64_t *__restrict__ rare, uint64_t e0, uint64_t e1, const uint16_t *hcode,
-                                                 const PopSizes &ps, LaneAcc32 &acc) {
+                                                 const PopSizes &ps, LaneAcc32 &acc, uint32_t tid) {
     constexpr int RU = 4;
     RareMoments mo;
-    uint64_t e = e0 + threadIdx.x;
-    for (; e + 256 * (RU - 1) < e1; e += 256 * RU) {
+    uint64_t e = e0 + tid;
+    for (; e + NT * (RU - 1) < e1; e += NT * RU) {
         uint64_t v[RU];
 #pragma unroll
-        for (int u = 0; u < RU; ++u) v[u] = stream_load(rare + e + 256 * u);
+        for (int u = 0; u < RU; ++u) v[u] = stream_load(rare + e + NT * u);
 #pragma unroll
         for (int u = 0; u < RU; ++u) mo.add(v[u], hcode, ps, acc);
     }
-    for (; e < e1; e += 256) mo.add(stream_load(rare + e), hcode, ps, acc);
+    for (; e < e1; e += NT) mo.add(stream_load(rare + e), hcode, ps, acc);
     mo.fold(ps, acc);
 }
 
@@ -200,25 +203,27 @@ __device__ __forceinline__ void rare_range_coded(const uint64_t *__restrict__ ra
 // tile_blocks = 4096, 2^13 per lane, each adding at most 2 x 511 to a sum — below 2^24 next to the rows' 2^27.
 // SKIP (the instantiations with the distinct-row stream): a word past the range in every lane of the wave is not decoded (a
 // ballot): four table reads that add nothing — a bench tile holds 2.2 words per thread where a batch decodes SU = 4
-template <bool SKIP = false>
+// NT, tid as in rare_range_coded; SU words in flight per thread, 4 SU <= 31 for the 5-bit fields.  A one-wave tile (NT = 64)
+// takes SU = 5: the 550 words of a bench tile are two batches, 9 words decoded per lane and one skipped
+template <bool SKIP = false, int NT = 256, int SU = 4>
 __device__ __forceinline__ void single_range(const uint16_t *__restrict__ single, uint64_t s0, uint64_t s1, const uint16_t *hcode,
-                                             const PopSizes &ps, LaneAcc32 &acc) {
-    constexpr int SU = 4;
+                                             const PopSizes &ps, LaneAcc32 &acc, uint32_t tid) {
+    static_assert(4 * SU <= 31, "a batch overflows a 5-bit field of the table's sums");
     const uint64_t *words = reinterpret_cast<const uint64_t *>(single);
     const uint64_t w0 = s0 >> 2, w1 = (s1 + 3) >> 2;
     const uint32_t head = (uint32_t)(s0 & 3), tail = (uint32_t)(s1 & 3);  // slots cut off the first word, slots kept of the last (0: all)
     uint32_t k = 0, kA = 0, kB = 0, kP = 0, kAB = 0;
-    for (uint64_t w = w0 + threadIdx.x; w < w1; w += 256 * SU) {
+    for (uint64_t w = w0 + tid; w < w1; w += NT * SU) {
         uint64_t v[SU];
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
-            const uint64_t i = w + 256 * u;
+            const uint64_t i = w + NT * u;
             v[u] = stream_load(words + (i < w1 ? i : w1 - 1));  // past the range: a word of it again, dropped below
         }
         uint32_t code = 0;
 #pragma unroll
         for (int u = 0; u < SU; ++u) {
-            const uint64_t i = w + 256 * u;
+            const uint64_t i = w + NT * u;
             if constexpr (SKIP) {
                 if (__builtin_amdgcn_ballot_w64(i < w1) == 0) continue;
             }
@@ -335,10 +340,11 @@ __device__ __forceinline__ void tile_reduce_store32(const LaneAcc32 &acc, TilePa
 // turn: the tile's ranges hand their blocks to the four waves from ONE running block index (a bench tile is a head block, one or
 // two blocks of representatives and a tail block: three loops that each start at wave 0 would give all of them to one wave and
 // serialise the loads).  In: how many blocks of this range go by before this wave's first; out: the same for the next range.
-template <int WPS, bool SUBSET_P, bool FOLDED, int U>
+// NW: the waves that share the range, 4 or the 1 of a one-wave tile (turn stays 0).
+template <int WPS, bool SUBSET_P, bool FOLDED, int U, int NW = 4>
 __device__ __forceinline__ void row_range(const uint32_t *__restrict__ sb, const uint8_t *__restrict__ wts, uint64_t s0, uint64_t s1,
                                           uint32_t &turn, uint32_t lane, const MaskArgs<WPS> &mk, const PopSizes &ps, LaneAcc32 &acc) {
-    if (s1 <= s0) return;  // workgroup-uniform
+    if (s1 <= s0) return;  // uniform over the NW waves
     const uint64_t b0 = s0 >> 6, b1 = (s1 + 63) >> 6;
     const uint32_t lo = (uint32_t)(s0 - (b0 << 6));
     const uint32_t hi = (uint32_t)(s1 - ((b1 - 1) << 6));  // 1..64
@@ -350,22 +356,22 @@ __device__ __forceinline__ void row_range(const uint32_t *__restrict__ sb, const
         }
     };
     uint64_t b = b0 + turn;
-    turn = (turn + 4u - (uint32_t)((b1 - b0) & 3u)) & 3u;
-    for (; b + 4 * (U - 1) < b1; b += 4 * U) {
+    turn = (turn + (uint32_t)NW - (uint32_t)((b1 - b0) & (NW - 1))) & (uint32_t)(NW - 1);
+    for (; b + NW * (U - 1) < b1; b += NW * U) {
         uint32_t w[U][WPS], wt[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            load_site<WPS>(sb + (b + 4 * u) * (64ull * WPS), lane, w[u]);
-            wt[u] = FOLDED ? (uint32_t)stream_load(wts + (b + 4 * u) * 64 + lane) : 1u;
+            load_site<WPS>(sb + (b + NW * u) * (64ull * WPS), lane, w[u]);
+            wt[u] = FOLDED ? (uint32_t)stream_load(wts + (b + NW * u) * 64 + lane) : 1u;
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-            trim(w[u], b + 4 * u);
+            trim(w[u], b + NW * u);
             site_accumulate<WPS, SUBSET_P, FOLDED>(w[u], mk, ps, acc, wt[u]);
         }
     }
     if constexpr (U > 1) {
-        for (; b < b1; b += 4) {
+        for (; b < b1; b += NW) {
             uint32_t w0[WPS];
             load_site<WPS>(sb + b * (64ull * WPS), lane, w0);
             const uint32_t wt0 = FOLDED ? (uint32_t)stream_load(wts + b * 64 + lane) : 1u;
@@ -466,8 +472,8 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         }
         if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
         __syncthreads();
-        rare_range_coded(rare, t.rare_begin, t.rare_end, hcode, ps, acc);
-        if (has_single) single_range<UNIQ>(single, sr.begin, sr.end, hcode, ps, acc);
+        rare_range_coded(rare, t.rare_begin, t.rare_end, hcode, ps, acc, threadIdx.x);
+        if (has_single) single_range<UNIQ>(single, sr.begin, sr.end, hcode, ps, acc, threadIdx.x);
     }
     if constexpr (UNIQ) {
         tile_reduce_store32(acc, out);
@@ -477,6 +483,74 @@ __global__ __launch_bounds__(256, IMPOP_SCAN_MIN_WAVES) void scan_tiles_kernel(c
         wide.q_p = acc.q_p; wide.q_a = acc.q_a; wide.q_b = acc.q_b; wide.q_ab = acc.q_ab;
         tile_reduce_store(wide, out);
     }
+}
+
+// The 48-byte partial of a one-wave tile: no LDS and no barrier, the wave sums in the VALU (lanes 48..63 hold them) and lane 63
+// writes the record itself.  A lane sum is below 2^32 by the plan's cap (tile_cut.h, wave_tile_fits), summed as two halves as above.
+__device__ __forceinline__ void wave_reduce_store32(const LaneAcc32 &acc, uint32_t lane, TilePartial *o) {
+    auto wide = [](uint32_t q) { return (uint64_t)wave_sum_u32_dpp(q & 0xFFFFu) + ((uint64_t)wave_sum_u32_dpp(q >> 16) << 16); };
+    TilePartial r;
+    r.s_all = wave_sum_u32_dpp(acc.s_all); r.s_p = wave_sum_u32_dpp(acc.s_p); r.s_a = wave_sum_u32_dpp(acc.s_a);
+    r.s_b = wave_sum_u32_dpp(acc.s_b);
+    r.sum_p = wide(acc.q_p); r.sum_a = wide(acc.q_a); r.sum_b = wide(acc.q_b); r.sum_ab = wide(acc.q_ab);
+    if (lane == 63) *o = r;
+}
+
+// The second body of the fixed-WPS kernel on a unique-row route: ONE WAVE PER TILE, wave w of workgroup g owns tile 4 g + w.
+// A bench tile is about 20 KB — a head block, one or two blocks of representatives, a tail block, some 46 entries and 2 200
+// singletons — so in scan_tiles_kernel each of the four waves owns at most one block, and everything else a wave executes (tile
+// decode, the dispatch around three row ranges, the table share, entries, singletons, 72 DPP adds, the store) is per-wave fixed
+// cost that all four pay for the same tile: the kernel is bound by VALU issue of that replicated overhead (DESIGN.md 4.1, round
+// 25).  Here a tile pays it once.  The wave index is scalar, so the tile, its SingleRange and its UniqRange come through scalar
+// loads and every per-tile branch is a scalar branch; the ranges are the same row_range, rare_range_coded and single_range at
+// stride 1 block / 64 threads.  The code table is filled once per workgroup by all 256 threads — the four tiles share the plan's
+// masks — whatever the tiles hold (whether a tile has rare sites is not workgroup-uniform here), and that barrier is the only
+// one: after it the four waves never meet again, and a wave past the last tile leaves.  Which plans run this body: tile_cut.h,
+// wave_tile_choice — the 32-bit lane sums hold four times as much of a tile as in the four-wave body.
+template <int WPS, bool SUBSET_P>
+__global__ __launch_bounds__(256, 5) void scan_tiles_kernel_wave(const uint32_t *__restrict__ sb, const uint64_t *__restrict__ rare,
+                                                                 const ScanTile *__restrict__ tiles, const MaskArgs<WPS> mk,
+                                                                 const PopSizes ps, TilePartial *__restrict__ out,
+                                                                 const uint16_t *__restrict__ single,
+                                                                 const SingleRange *__restrict__ singles,
+                                                                 const uint32_t *__restrict__ uniq, const uint8_t *__restrict__ uniq_wt,
+                                                                 const UniqRange *__restrict__ uniqs, uint32_t n_tiles) {
+    __shared__ uint16_t hcode[RARE_CODE_SIZE];
+    {
+        constexpr int CODE_PER_THREAD = (32 * WPS + 255) / 256;
+        const uint32_t *mkw = reinterpret_cast<const uint32_t *>(&mk);  // p | a | b
+#pragma unroll
+        for (int j = 0; j < CODE_PER_THREAD; ++j) {
+            const uint32_t h = threadIdx.x + 256u * j, bit = h & 31u;
+            if (h < 32u * WPS) {
+                const uint32_t mp = mkw[h >> 5], ma = mkw[WPS + (h >> 5)], mb = mkw[2 * WPS + (h >> 5)];
+                hcode[h] = (uint16_t)(((ma >> bit) & 1u) | (((mb >> bit) & 1u) << 5) | (((mp >> bit) & 1u) << 10) |
+                                      (((ma & mb) >> bit & 1u) << 15));
+            }
+        }
+        if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
+    }
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t k = 4u * blockIdx.x + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar
+    if (k >= n_tiles) return;
+    const ScanTile t = tiles[k];
+    SingleRange sr = {0, 0};
+    if (singles) sr = singles[k];
+    const UniqRange ur = uniqs[k];
+    LaneAcc32 acc;
+    constexpr int G = (WPS + 3) / 4;
+    constexpr int U = IMPOP_SCAN_UNROLL > 0 ? IMPOP_SCAN_UNROLL : (G >= 3 ? 2 : G == 2 ? 4 : 8);
+    uint32_t turn = 0;
+    const bool folded = ur.end > ur.begin;
+    const MidBlocks mid = mid_blocks(t.site_begin, t.site_end);
+    const uint64_t head_end = folded ? mid.g0 << 6 : t.site_end, tail_begin = folded ? mid.g1 << 6 : t.site_end;
+    row_range<WPS, SUBSET_P, false, U, 1>(sb, nullptr, t.site_begin, head_end, turn, lane, mk, ps, acc);
+    row_range<WPS, SUBSET_P, true, U, 1>(uniq, uniq_wt, ur.begin, ur.end, turn, lane, mk, ps, acc);
+    row_range<WPS, SUBSET_P, false, 1, 1>(sb, nullptr, tail_begin, t.site_end, turn, lane, mk, ps, acc);  // one block at most
+    if (t.rare_end > t.rare_begin) rare_range_coded<64>(rare, t.rare_begin, t.rare_end, hcode, ps, acc, lane);
+    if (sr.end > sr.begin) single_range<true, 64, 5>(single, sr.begin, sr.end, hcode, ps, acc, lane);
+    wave_reduce_store32(acc, lane, out + k);
 }
 
 // Any wps (n > 512 haplotypes, and every weighted matrix): the three masks of the WHOLE haplotype axis sit in
@@ -838,6 +912,7 @@ struct impop_scan_plan {
     const uint32_t *uniq = nullptr;  // unique-row route: m->d_vuniq, m->d_vuniq_wt and every tile's range of them, else null
     const uint8_t *uniq_wt = nullptr;
     UniqRange *d_uniqs = nullptr;
+    bool wave_tiles = false;  // unique-row route: launches run scan_tiles_kernel_wave, one wave per tile (tile_cut.h, wave_tile_choice)
     uint64_t n_windows = 0, n_tiles = 0, bytes_streamed = 0;
     PopSizes ps{};
     bool subset_p = false;
@@ -912,7 +987,8 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
 // split = on, or off:<the reason there is none, blanks as _>; single_sites = the singleton stream of a packed route (all of the
 // matrix), rare_streamed = the bytes of rare sites the plan really reads (rare_bytes keeps counting 8 per rare site);
 // unique_rows = the representatives of the distinct-row stream of a unique-row route (all of the matrix), rows_streamed = the
-// bytes of rows the plan really reads (bytes_streamed = rows_streamed + rare_streamed)
+// bytes of rows the plan really reads (bytes_streamed = rows_streamed + rare_streamed); wave_tiles = 1 where the fixed-WPS kernel
+// will run one wave per tile (the last key; the free-text why= stays behind it, where the parsers that cut the line there expect it)
 static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
     if (!trace_on()) return;
     const char *why = rt.indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
@@ -923,12 +999,12 @@ static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_w
     const uint64_t rows_streamed = rt.bytes_streamed - rare_streamed;
     std::string off = "off:" + (!m->wt_prefix.empty() && m->d_vrare ? std::string("site weights") : m->rskip);
     for (char &ch : off) ch = ch == ' ' ? '_' : ch;
-    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu unique_rows=%llu rows_streamed=%llu%s%s\n",
+    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu unique_rows=%llu rows_streamed=%llu wave_tiles=%d%s%s\n",
             rt.indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(rt.indexed ? m->n_vkept : m->g.n_site),
             (unsigned long long)rt.tiles.size(), (unsigned long long)rt.bytes_streamed, (unsigned long long)n_windows,
             (unsigned long long)(rt.split ? m->n_vrare : 0), (unsigned long long)rare_bytes, rt.split ? "on" : off.c_str(), (unsigned long long)(rt.packed ? m->n_vsingle : 0),
             (unsigned long long)rare_streamed, (unsigned long long)(rt.uniq ? m->n_vuniq : 0), (unsigned long long)rows_streamed,
-            *why ? " why=" : "", why);
+            rt.wave_tiles ? 1 : 0, *why ? " why=" : "", why);
     fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
 }
 
@@ -1012,6 +1088,14 @@ int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, con
         rt.uniq_wt = m->d_vuniq_wt;
         if ((rc = tile_uniq_ranges(ctx, m, rt))) return rc;
         rt.apply_uniq_ranges(m->g.wps);
+        // ... and which body of the kernel reads them: by the plan's largest tile, IMPOP_SCAN_WAVE_TILES=0|1 overriding the rule
+        uint64_t max_blocks = 0, max_rare = 0;
+        for (size_t k = 0; k < rt.tiles.size(); ++k) {
+            max_blocks = std::max(max_blocks, tile_blocks_read(rt.tiles[k], rt.uniqs[k]));
+            max_rare = std::max(max_rare, tile_rare_words(rt.tiles[k], rt.packed ? rt.singles[k] : SingleRange{0, 0}));
+        }
+        const int force = env_is("IMPOP_SCAN_WAVE_TILES", '0') ? 0 : env_is("IMPOP_SCAN_WAVE_TILES", '1') ? 1 : -1;
+        rt.wave_tiles = wave_tile_choice(force, rt.tiles.size(), max_blocks, max_rare, ctx->n_cu);
     }
     rc = window_weights(m, windows, n_windows, rt);
     if (rc) return rc;
@@ -1072,8 +1156,14 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
     hipLaunchKernelGGL((scan_tiles_kernel<WPS, SP, UQ>), dim3((uint32_t)p->n_tiles), dim3(256), 0, st, p->sb, p->rare, p->d_tiles, \
                        mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles, p->uniq, p->uniq_wt,                \
                        (const UniqRange *)p->d_uniqs)
-    if (p->d_uniqs) { if (p->subset_p) LAUNCH(true, true); else LAUNCH(false, true); }
-    else            { if (p->subset_p) LAUNCH(true, false); else LAUNCH(false, false); }
+#define LAUNCH_WAVE(SP)                                                                                                        \
+    hipLaunchKernelGGL((scan_tiles_kernel_wave<WPS, SP>), dim3((uint32_t)((p->n_tiles + 3) / 4)), dim3(256), 0, st, p->sb, p->rare, \
+                       p->d_tiles, mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles, p->uniq, p->uniq_wt,    \
+                       (const UniqRange *)p->d_uniqs, (uint32_t)p->n_tiles)
+    if (p->wave_tiles)   { if (p->subset_p) LAUNCH_WAVE(true); else LAUNCH_WAVE(false); }
+    else if (p->d_uniqs) { if (p->subset_p) LAUNCH(true, true); else LAUNCH(false, true); }
+    else                 { if (p->subset_p) LAUNCH(true, false); else LAUNCH(false, false); }
+#undef LAUNCH_WAVE
 #undef LAUNCH
 }
 
@@ -1107,7 +1197,7 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
     p->sb = rt.sb; p->rare = rt.rare; p->single = rt.single;
-    p->uniq = rt.uniq; p->uniq_wt = rt.uniq_wt;
+    p->uniq = rt.uniq; p->uniq_wt = rt.uniq_wt; p->wave_tiles = rt.wave_tiles;
     p->n_tiles = rt.tiles.size(); p->bytes_streamed = rt.bytes_streamed;
     m->users++;
     p->d_pi_mode = prm.d_pi_mode; p->s_scope = prm.s_scope;

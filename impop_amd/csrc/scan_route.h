@@ -29,6 +29,7 @@ struct ScanRoute : TileCut {  // ... and how cut_tiles cut it: tiles, singles, w
     // same caller, whether or not the route is packed.
     const uint32_t *uniq = nullptr;
     const uint8_t *uniq_wt = nullptr;
+    bool wave_tiles = false;  // ... and the kernel will run one wave per tile (tile_cut.h, wave_tile_choice)
     std::vector<LayoutWindow> lw;  // the windows as ranges of sb's sites, of rare's entries (split) and of single's (packed)
     uint32_t tile_blocks = 0;
 };

@@ -55,6 +55,45 @@ constexpr uint64_t UNIQ_ROW_SUM_MAX = 1ull << 16, UNIQ_WEIGHT_MAX = 64, UNIQ_RAR
 inline uint64_t uniq_lane_sum_bound(uint64_t mid) {
     return ((mid + 1 + 3) / 4) * UNIQ_WEIGHT_MAX * UNIQ_ROW_SUM_MAX + UNIQ_ROW_SUM_MAX + UNIQ_RARE_SUM_MAX;
 }
+// One wave per tile (scan.hip, scan_tiles_kernel_wave): the tile's sums sit in 64 lanes, not 256.  A lane then takes one row of
+// EVERY block the tile reads — a representative adds at most UNIQ_WEIGHT_MAX x UNIQ_ROW_SUM_MAX = 2^22, a row of a head, of a tail
+// or of a tile without the stream 2^16, counted here as a representative all the same — and one in 64 of the tile's rare words:
+// 8-byte entries of the rare stream (one site of minor count m <= 3) and 8-byte words of the singleton stream (four sites of
+// m = 1).  A rare site adds m (n - m) <= 3 x 511 or mA (nB - mB) + mB (nA - mA) <= 3 x 512 to a sum, below WAVE_RARE_SITE_SUM_MAX,
+// so a word at most four times that.  The entries and the singleton words are two loops of stride 64, each rounded up.
+constexpr uint64_t WAVE_RARE_SITE_SUM_MAX = 1ull << 11, WAVE_RARE_WORD_SUM_MAX = 4 * WAVE_RARE_SITE_SUM_MAX;
+// the largest sum one lane of a one-wave tile can reach: `blocks` blocks read (rows and representatives), `rare_words` rare words
+inline uint64_t wave_lane_sum_bound(uint64_t blocks, uint64_t rare_words) {
+    return blocks * UNIQ_WEIGHT_MAX * UNIQ_ROW_SUM_MAX + (rare_words / 64 + 2) * WAVE_RARE_WORD_SUM_MAX;
+}
+// What a one-wave tile may hold: round figures under wave_lane_sum_bound(...) < 2^32 — 512 x 2^22 = 2^31 for the rows and
+// (2^12 + 2) x 2^13 < 2^26 for the rare words.  Far above what one wave is good for (wave_tile_rule): the cap is what makes the
+// 32-bit lane sums right, the rule what makes the kernel worth taking.
+constexpr uint64_t WAVE_BLOCKS_MAX = 512, WAVE_RARE_WORDS_MAX = 1ull << 18;
+static_assert(WAVE_BLOCKS_MAX * UNIQ_WEIGHT_MAX * UNIQ_ROW_SUM_MAX + (WAVE_RARE_WORDS_MAX / 64 + 2) * WAVE_RARE_WORD_SUM_MAX < (1ull << 32),
+              "a one-wave tile at the cap overflows a 32-bit lane sum");
+inline bool wave_tile_fits(uint64_t blocks, uint64_t rare_words) { return blocks <= WAVE_BLOCKS_MAX && rare_words <= WAVE_RARE_WORDS_MAX; }
+// The default choice between the two bodies of the fixed-WPS kernel on a unique-row route, from the plan's number of tiles and
+// its largest tile (blocks read; rare words).  One wave per tile pays the per-tile fixed cost — decode, range dispatch, table
+// share, reduction, store — once where four waves pay it four times, and takes a quarter of the workgroups; it is the better
+// body where tiles are small and many.  False: above the cap (then whatever the override says, the caller runs four waves);
+// with fewer than WAVE_RULE_TILES_PER_CU n_cu tiles, where four-wave workgroups reach more CUs and SIMDs than n_tiles / 4 one-wave
+// ones do; and with a tile beyond WAVE_RULE_BLOCKS blocks or WAVE_RULE_RARE_WORDS rare words, which one wave walks four times as
+// serially as four.  The thresholds are measured on an MI355X at 465 haplotypes (tools/sweep_wave_tiles.py; DESIGN.md 4.1, round
+// 25): from 2 048 tiles of 7 to 20 KB one wave wins by more than the four-wave arm's spread and at 1 536 it does not; at 3 072
+// and 4 854 tiles it wins up to 100 kb windows as one tile (29 KB: at most 6 blocks read and about 1 200 rare words) and is level
+// from 150 kb (38 KB: 7 blocks, 1 800 rare words).  n_cu <= 0 counts as 256, as in default_tile_rule.
+constexpr uint64_t WAVE_RULE_TILES_PER_CU = 8, WAVE_RULE_BLOCKS = 6, WAVE_RULE_RARE_WORDS = 1536;
+inline bool wave_tile_rule(uint64_t n_tiles, uint64_t max_blocks, uint64_t max_rare_words, int n_cu) {
+    if (!wave_tile_fits(max_blocks, max_rare_words)) return false;
+    if (n_tiles < WAVE_RULE_TILES_PER_CU * (uint64_t)(n_cu > 0 ? n_cu : 256)) return false;
+    return max_blocks <= WAVE_RULE_BLOCKS && max_rare_words <= WAVE_RULE_RARE_WORDS;
+}
+// override: -1 none (the rule), 0 never, 1 whenever the cap allows (IMPOP_SCAN_WAVE_TILES, read where a plan is made)
+inline bool wave_tile_choice(int override_, uint64_t n_tiles, uint64_t max_blocks, uint64_t max_rare_words, int n_cu) {
+    if (override_ == 0 || !wave_tile_fits(max_blocks, max_rare_words)) return false;
+    return override_ == 1 ? true : wave_tile_rule(n_tiles, max_blocks, max_rare_words, n_cu);
+}
 // bytes of the blocks of the stream the rows [begin, end) of it touch, whole, each with its 64 weight bytes
 IMPOP_TILE_HD inline uint64_t uniq_bytes_streamed(uint64_t begin, uint64_t end, uint32_t wps) {
     return end > begin ? ((end + 63) / 64 - begin / 64) * (256ull * wps + 64ull) : 0;
@@ -74,6 +113,16 @@ inline uint64_t tile_row_bytes_streamed(const ScanTile &t, const UniqRange &u, u
     if (u.end <= u.begin) return ((t.site_end + 63) / 64 - t.site_begin / 64) * 256ull * wps;
     const uint64_t edge = (t.site_begin % 64 != 0) + (t.site_end % 64 != 0);
     return edge * 256ull * wps + uniq_bytes_streamed(u.begin, u.end, wps);
+}
+// the same in blocks, of rows and of the stream alike, and the tile's rare words (entries and singleton words): what
+// wave_tile_fits and wave_tile_rule ask of a plan's largest tile
+inline uint64_t tile_blocks_read(const ScanTile &t, const UniqRange &u) {
+    if (t.site_end <= t.site_begin) return 0;
+    if (u.end <= u.begin) return (t.site_end + 63) / 64 - t.site_begin / 64;
+    return (t.site_begin % 64 != 0) + (t.site_end % 64 != 0) + ((u.end + 63) / 64 - u.begin / 64);
+}
+inline uint64_t tile_rare_words(const ScanTile &t, const SingleRange &s) {
+    return (t.rare_end - t.rare_begin) + single_bytes_streamed(s) / 8;
 }
 struct WinDesc {
     uint64_t t0, t1;  // tile range

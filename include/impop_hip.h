@@ -255,9 +255,10 @@ int impop_scan_plan_fetch(impop_scan_plan *plan, impop_window_stats *out_host);
  * of the tile's whole blocks of rows).
  * Under IMPOP_TRACE=1 impop_scan_plan_create prints one line per plan on stderr:
  *   [impop_scan] route=<indexed|dense|compact> kept_sites=<n> tiles=<n> bytes_streamed=<n> windows=<n> rare_sites=<n>
- *                rare_bytes=<n> split=<on|off:reason> single_sites=<n> rare_streamed=<n> unique_rows=<n> rows_streamed=<n> [why=<reason>]
+ *                rare_bytes=<n> split=<on|off:reason> single_sites=<n> rare_streamed=<n> unique_rows=<n> rows_streamed=<n> wave_tiles=<0|1> [why=<reason>]
  * unique_rows: the representatives of the matrix's distinct-row stream when the plan reads it, else 0; rows_streamed: the bytes
- * of rows (and representatives) among bytes_streamed, rare_streamed the rest. */
+ * of rows (and representatives) among bytes_streamed, rare_streamed the rest; wave_tiles: the plan's launches run one wave per
+ * tile (small tiles in number; IMPOP_SCAN_WAVE_TILES=0|1 where the plan is made: never / whenever the 32-bit lane sums allow). */
 int impop_scan_plan_info(const impop_scan_plan *plan, uint64_t *n_tiles, uint64_t *bytes_streamed);
 /* Measurement aid: with timing enabled every launch brackets the streaming kernel
  * (not the tiny epilogue) with hipEvents on the context's stream; elapsed() synchronises
