@@ -96,6 +96,15 @@ class PairdistParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("hist_bins", C.c_uint32), ("hist_width", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PcaParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("tol", C.c_double), ("max_iter", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PcaWindow(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("rank", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32), ("sum_h", C.c_uint64), ("lambda", C.c_double * 8), ("resid", C.c_double * 8)]
+
+
 class DistPanel(C.Structure):
     _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("n_pairs", C.c_uint64), ("sum_h", C.c_uint64), ("sum_h2", C.c_uint64),
                 ("n_zero", C.c_uint64), ("min_h", C.c_uint32), ("max_h", C.c_uint32), ("min_i", C.c_uint32), ("min_j", C.c_uint32),
@@ -261,6 +270,8 @@ assert C.sizeof(ClusterStats) == 32 and C.sizeof(ClusterParams) == 24
 assert C.sizeof(PanelStats) == 48 and C.sizeof(PanelWindow) == 8
 assert C.sizeof(DistPanel) == 64 and C.sizeof(DistPair) == 96 and C.sizeof(PairdistParams) == 16
 PAIRDIST_MAX_N, PAIRDIST_MAX_BINS = 4096, 1024  # IMPOP_PAIRDIST_MAX_N, IMPOP_PAIRDIST_MAX_BINS
+assert C.sizeof(PcaParams) == 24 and C.sizeof(PcaWindow) == 160
+PCA_MAX_N, PCA_MAX_K, PCA_MAX_DIST_WINDOWS = 1024, 8, 16384  # IMPOP_PCA_MAX_N, IMPOP_PCA_MAX_K, the most windows out_dist2 takes
 assert C.sizeof(KinWindow) == 48 and C.sizeof(KinPair) == 72 and C.sizeof(KinWatch) == 16 and C.sizeof(KinshipParams) == 16
 KINSHIP_MAX_N, KINSHIP_MAX_WATCH = 2048, 1024  # IMPOP_KINSHIP_MAX_N, IMPOP_KINSHIP_MAX_WATCH
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
@@ -303,6 +314,7 @@ SIGNATURES = {
     "impop_ctx_cluster_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_pairdist_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_ctx_ehh_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+    "impop_ctx_pca_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_debug_timer_pool_sizes": (C.c_int, [_vp, _vp, _u64p]),
     "impop_matrix_synthetic_slab": (C.c_int, [_vp, C.c_uint32, C.c_uint64, C.c_uint64, C.POINTER(SynthParams), C.c_uint32, C.POINTER(_vp)]),
     "impop_matrix_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),
@@ -347,6 +359,7 @@ SIGNATURES = {
                                             C.POINTER(PanelStats), C.POINTER(PairStats), C.POINTER(PanelWindow)]),
     "impop_pairdist_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairdistParams),
                                       C.POINTER(DistPanel), C.POINTER(DistPair), _u32p, _u32p]),
+    "impop_pca_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(PcaParams), C.POINTER(PcaWindow), _f64p, _f64p]),
     "impop_genotypes_create": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, C.POINTER(_vp)]),
     "impop_genotypes_info": (C.c_int, [_vp, _u32p, _u64p, _u64p]),
     "impop_genotypes_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),

@@ -300,6 +300,11 @@ IMPOP_API int impop_ctx_kinship_elapsed(impop_ctx *ctx, double kernel_ms[2], uin
     return ctx_timers_elapsed(ctx, impop_ctx::T_KIN, 2, 1, kernel_ms, chunks);
 }
 
+IMPOP_API int impop_ctx_pca_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks) {
+    REQUIRE(ctx && kernel_ms, "impop_ctx_pca_elapsed: NULL argument");
+    return ctx_timers_elapsed(ctx, impop_ctx::T_PCA, 2, 0, kernel_ms, chunks);
+}
+
 IMPOP_API int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
     REQUIRE(ctx, "impop_ctx_ehh_elapsed: ctx is NULL");
     return ctx_timers_elapsed(ctx, impop_ctx::T_EHH, 1, 0, total_ms, launches);

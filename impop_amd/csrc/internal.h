@@ -171,7 +171,8 @@ struct impop_ctx {
         T_PAIRDIST = T_IBS + 3,  // impop_pairdist_scan: the distribution kernel of every chunk (impop_ctx_pairdist_elapsed)
         T_IHS,               // impop_ihs_scan: classify + tables / walk kernels (impop_ctx_ihs_elapsed)
         T_KIN = T_IHS + 2,   // impop_genotypes_create's plane build / impop_kinship_scan's epilogue kernels (impop_ctx_kinship_elapsed)
-        T_COUNT = T_KIN + 2
+        T_PCA = T_KIN + 2,   // impop_pca_scan: the eigen kernel of every chunk / the distance kernel (impop_ctx_pca_elapsed)
+        T_COUNT = T_PCA + 2
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "pair_plan.h"
+#include "pca_math.h"
 #include "stats_kernels.h"
 #include "win_chunks.h"
 
@@ -554,6 +555,62 @@ struct PairdistEpilogue final : PairEpilogue {
     }
 };
 
+// impop_pca_scan's epilogue (pca.hip): one launch of the eigen kernel per chunk — records and vectors; the symmetric distance
+// matrices the kernel gathers live in scratch, one per window of a chunk.  With the window distances wanted, every window's
+// vectors, eigenvalues and usability also go to tables that live across the chunks, in the caller's window order.
+struct PcaEpilogue final : PairEpilogue {
+    uint32_t M, k, max_iter;
+    double tol;
+    bool h16, want_dist;
+    uint64_t n_windows;
+    const std::vector<uint32_t> *hap_of;
+    impop_pca_window *out_windows;
+    double *out_vectors;  // nullable
+    uint64_t chunks = 0, launches = 0;
+    uint32_t *d_hap = nullptr, *d_ok = nullptr;
+    char *d_hs = nullptr;
+    uint64_t *d_ord = nullptr;
+    impop_pca_window *d_rec = nullptr, *h_rec = nullptr;
+    double *d_vec = nullptr, *h_vec = nullptr, *d_allvec = nullptr, *d_lam = nullptr, *d_dist = nullptr;
+    size_t hs_bytes() const { return (size_t)M * M * (h16 ? 2 : 4); }
+    // the device bytes layout() takes per window of a chunk (they bound a chunk: impop_pca_scan)
+    size_t per_window_bytes() const { return hs_bytes() + sizeof(impop_pca_window) + (size_t)k * M * 8 + 8; }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        D.sub(d_hap, M); D.sub(d_ord, cap); D.sub(d_rec, cap); D.sub(d_vec, out_vectors ? cap * k * M : 0);
+        D.sub(d_allvec, want_dist ? n_windows * k * M : 0); D.sub(d_lam, want_dist ? n_windows * 8 : 0);
+        D.sub(d_ok, want_dist ? n_windows : 0); D.sub(d_dist, want_dist ? n_windows * n_windows : 0);
+        D.sub(d_hs, cap * hs_bytes());
+        H.sub(h_rec, cap); H.sub(h_vec, out_vectors ? cap * k * M : 0);
+    }
+    int upload(impop_ctx *ctx) override {
+        HIP_TRY(hipMemcpyAsync(d_hap, hap_of->data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const uint64_t cnt = c.cnt;
+        if (want_dist) HIP_TRY(hipMemcpyAsync(d_ord, c.ord, cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+        size_t slot = 0;  // the eigen kernel between two events of its own: impop_ctx_pca_elapsed
+        int rc = ctx->gram_timing ? ctx->timers[impop_ctx::T_PCA].begin(ctx->stream, &slot) : IMPOP_OK;
+        if (rc) return rc;
+        const PcaIn in{d_hap, d_hs, want_dist ? d_ord : nullptr, M, k, max_iter, h16 ? 1u : 0u, tol};
+        const PcaOut O{d_rec, out_vectors ? d_vec : nullptr, want_dist ? d_allvec : nullptr, want_dist ? d_lam : nullptr,
+                       want_dist ? d_ok : nullptr};  // (a table of zero bytes shares its offset with what follows it)
+        rc = launch_pca_eigen(ctx, c.b, cnt, c.d_s, in, O);
+        if (rc) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PCA].end(ctx->stream, slot))) return rc;
+        ++chunks; ++launches;
+        HIP_TRY(hipMemcpyAsync(h_rec, d_rec, cnt * sizeof(impop_pca_window), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_vectors) HIP_TRY(hipMemcpyAsync(h_vec, d_vec, cnt * k * M * 8, hipMemcpyDeviceToHost, ctx->stream));
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        for (uint64_t i = 0; i < c.cnt; ++i) {
+            out_windows[c.ord[i]] = h_rec[i];
+            if (out_vectors) memcpy(out_vectors + c.ord[i] * k * M, h_vec + i * k * M, (size_t)k * M * 8);
+        }
+    }
+};
+
 // impop_kinship_scan's epilogue (kinship.hip): per chunk the window kernel (records, watch rows, the diagonals) and, when the
 // per-pair totals are wanted, the totals kernel, which adds the chunk's tables into d_tot; d_tot lives across the chunks
 struct KinshipEpilogue final : PairEpilogue {
@@ -714,6 +771,71 @@ IMPOP_API int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const i
         fprintf(stderr, "[impop_pairdist_scan] pops=%u pairs=%u members=%u windows=%llu chunks=%llu launches=%llu hist_bins=%u hist=%s\n", K, NP,
                 M, (unsigned long long)n_windows, (unsigned long long)epi.chunks, (unsigned long long)epi.launches, epi.B,
                 !epi.B ? "off" : epi.hist_lds ? "lds" : "global");
+    return IMPOP_OK;
+}
+
+static_assert(sizeof(impop_pca_params) == 24 && sizeof(impop_pca_window) == 160, "fixed record layouts");
+static_assert(IMPOP_PCA_MAX_N == PCA_MAX_N && IMPOP_PCA_MAX_K == PCA_MAX_K && PCA_MAX_K + 8 <= PCA_B, "the block holds k + 8 columns");
+
+IMPOP_API int impop_pca_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                             const uint64_t *mask_p, const impop_pca_params *params, impop_pca_window *out_windows, double *out_vectors,
+                             double *out_dist2) {
+    const char *fn = "impop_pca_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_pca_params), "impop_pca_params.struct_size mismatch");
+    REQUIRE(params->k >= 1 && params->k <= IMPOP_PCA_MAX_K, "%s: k must be 1..%u", fn, (uint32_t)IMPOP_PCA_MAX_K);
+    REQUIRE(params->tol >= 1e-13 && params->tol <= 1e-2, "%s: tol must be in [1e-13, 1e-2]", fn);
+    REQUIRE(params->max_iter >= 1 && params->max_iter <= 100000, "%s: max_iter must be 1..100000", fn);
+    const std::vector<uint32_t> hap_of = mask_members(mask_p, m->g.n_hap);
+    REQUIRE(hap_of.size() >= 2, "%s: the mask holds %zu members, fewer than 2", fn, hap_of.size());
+    if (hap_of.size() > IMPOP_PCA_MAX_N) {  // refused before anything is uploaded or launched
+        set_error("%s: the mask holds %zu members, more than the limit of %u", fn, hap_of.size(), (uint32_t)IMPOP_PCA_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    if (out_dist2 && n_windows > 16384) {
+        set_error("%s: window distances of %llu windows, more than the limit of 16384", fn, (unsigned long long)n_windows);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    REQUIRE(!out_dist2 || out_vectors, "%s: out_dist2 needs out_vectors", fn);
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_windows, "%s: NULL windows/out", fn);
+    int rc = check_windows(ctx, m, windows, n_windows, fn);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const uint64_t max_W = widest_W(m, windows, n_windows);
+    PcaEpilogue epi;
+    epi.M = (uint32_t)hap_of.size(); epi.k = params->k; epi.max_iter = params->max_iter; epi.tol = params->tol;
+    epi.h16 = max_W < 65536;  // a distance is at most its window's W
+    epi.want_dist = out_dist2 != nullptr; epi.n_windows = n_windows;
+    epi.hap_of = &hap_of; epi.out_windows = out_windows; epi.out_vectors = out_vectors;
+    PairFront in{};
+    in.fn = fn; in.identity_kind = IMPOP_IDENTITY_MATCH; in.round_digits = -1;  // Hamming distances: no unflip pass
+    in.scan_host = nullptr; in.use_segmap = false; in.max_W = max_W;
+    // the gathered distance matrices and the vectors of a chunk: at most 1 GiB of them
+    in.max_chunk_windows = std::min<uint64_t>(65535, std::max<uint64_t>(1, (1ull << 30) / epi.per_window_bytes()));
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (out_dist2) {  // the scratch the front end bound the all-window tables into is still the context's
+        size_t slot = 0;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PCA + 1].begin(ctx->stream, &slot))) return rc;
+        rc = launch_pca_dist(ctx, epi.d_allvec, epi.d_lam, epi.d_ok, epi.M, epi.k, n_windows, epi.d_dist);
+        if (rc) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PCA + 1].end(ctx->stream, slot))) return rc;
+        ++epi.launches;
+        HIP_TRY(hipMemcpyAsync(out_dist2, epi.d_dist, n_windows * n_windows * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (trace_on()) {
+        uint32_t it_max = 0;
+        uint64_t bad = 0;
+        for (uint64_t i = 0; i < n_windows; ++i) {
+            it_max = std::max(it_max, out_windows[i].iterations);
+            bad += out_windows[i].flags & 1u;
+        }
+        fprintf(stderr, "[impop_pca_scan] route=%s members=%u k=%u windows=%llu chunks=%llu launches=%llu iterations_max=%u unconverged=%llu "
+                "dist=%s\n", m->compact ? "compact" : "dense", epi.M, epi.k, (unsigned long long)n_windows, (unsigned long long)epi.chunks,
+                (unsigned long long)epi.launches, it_max, (unsigned long long)bad, out_dist2 ? "on" : "off");
+    }
     return IMPOP_OK;
 }
 

@@ -267,6 +267,28 @@ size_t pairdist_lds_fixed(uint32_t K, uint32_t M);  // bytes of the accumulators
 int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PairdistTables &T,
                     const PairdistOut &O, bool hist_lds);
 
+// impop_pca_scan's kernels (pca.hip).  The eigen kernel: one workgroup per Gram problem; the members are positions 0 .. m - 1 in
+// ascending haplotype index.  The distance kernel: once per call, over the vectors of all windows in the caller's window order.
+struct PcaIn {
+    const uint32_t *hap_of;  // m: haplotype index of a position
+    void *hs;                // scratch: n_problems x m x m distances, symmetric, uint16 where h16 else uint32
+    const uint64_t *ord;     // problem p is window ord[p] of the call (the slot of the all-window tables), or nullptr
+    uint32_t m, k, max_iter, h16;
+    double tol;
+};
+struct PcaOut {
+    impop_pca_window *rec;   // n_problems
+    double *vec;             // n_problems x k x m, or nullptr
+    double *all_vec;         // per WINDOW of the call: k x m | 8 eigenvalues | usable by the distance kernel; or nullptr
+    double *all_lam;
+    uint32_t *all_ok;
+};
+size_t pca_eigen_lds_bytes(uint32_t m);
+int launch_pca_eigen(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PcaIn &in,
+                     const PcaOut &out);
+int launch_pca_dist(impop_ctx *ctx, const double *d_vec, const double *d_lam, const uint32_t *d_ok, uint32_t m, uint32_t k,
+                    uint64_t n_windows, double *d_out);
+
 // impop_kinship_scan's epilogue (kinship.hip) on a chunk's Gram problems of the 2N plane rows [H_0 .. H_{N-1}, A_0 .. A_{N-1}].
 struct KinshipOut {
     impop_kin_window *windows;  // n_problems

@@ -80,6 +80,9 @@ DIST_PAIR_DTYPE = np.dtype([("n_pairs", "<u8"), ("sum_h", "<u8"), ("sum_h2", "<u
                             ("min_i", "<u4"), ("min_j", "<u4"), ("max_i", "<u4"), ("max_j", "<u4"), ("nn_same_a", "<u4"), ("nn_same_b", "<u4"),
                             ("nn_other_a", "<u4"), ("nn_other_b", "<u4"), ("snn", "<f8"), ("gmin", "<f8"), ("reserved", "<u8")])
 assert DIST_PANEL_DTYPE.itemsize == 64 and DIST_PAIR_DTYPE.itemsize == 96
+PCA_WINDOW_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("rank", "<u4"), ("iterations", "<u4"), ("flags", "<u4"),
+                             ("reserved", "<u4"), ("sum_h", "<u8"), ("lambda", "<f8", (8,)), ("resid", "<f8", (8,))])
+assert PCA_WINDOW_DTYPE.itemsize == 160
 
 KIN_WINDOW_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("n_pairs", "<u8"), ("het_het", "<u8"), ("ibs0", "<u8"), ("ibs2", "<u8"),
                              ("n_related", "<u4"), ("n_undefined", "<u4")])
@@ -226,6 +229,12 @@ class Context:
         t, k = C.c_double(), C.c_uint64()
         check(self._lib.impop_ctx_pairdist_elapsed(self.handle, C.byref(t), C.byref(k)))
         return t.value, k.value
+
+    def pca_elapsed(self):
+        """-> ([eigen kernel, distance kernel] ms of pca_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 2)(), C.c_uint64()
+        check(self._lib.impop_ctx_pca_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
 
     def kinship_elapsed(self):
         """-> ([plane build, epilogue] kernel ms of genotypes() / kinship_scan, chunks) since gram_timing(True)"""
@@ -718,6 +727,31 @@ class BitMatrix:
                                                 pairs.ctypes.data_as(C.POINTER(_lib.DistPair)) if NP else None,
                                                 hw.ctypes.data_as(u32p) if B else None, hb.ctypes.data_as(u32p) if B and NP else None))
         return panels, pairs, hw, hb
+
+    def pca_scan(self, windows, mask_p=None, k: int = 2, tol: float = 1e-10, max_iter: int = 500, want_vectors: bool = True,
+                 want_dist: bool = False):
+        """Principal components per window (impop_pca_scan): the k (1..8) largest eigenpairs of the double-centred Hamming
+        distance matrix of the members of mask_p, from ONE Gram pass per window.
+        -> (records [n_windows] PCA_WINDOW_DTYPE, vectors [n_windows, k, |P|] float64 or None, dist2 [n_windows, n_windows]
+            float64 or None).  Vector j of a window is unit length, orthogonal to the ones vector, its largest component positive;
+        all zeros for j >= rank.  dist2 is lostruct's distance between windows (NaN rows for windows of rank 0 or unconverged);
+        it needs the vectors."""
+        w = make_windows(windows)
+        if want_dist and not want_vectors:
+            raise ValueError("want_dist needs want_vectors")
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        n_p = self.n_hap if mask_p is None else int(np.unpackbits(kp.view(np.uint8), bitorder="little")[: self.n_hap].sum())
+        out = np.zeros(len(w), dtype=PCA_WINDOW_DTYPE)
+        k = int(k)
+        vec = np.zeros((len(w), max(k, 0), n_p), dtype=np.float64) if want_vectors else None
+        d2 = np.zeros((len(w), len(w)), dtype=np.float64) if want_dist else None
+        prm = _lib.PcaParams(C.sizeof(_lib.PcaParams), k, float(tol), int(max_iter), 0)
+        f64p = C.POINTER(C.c_double)
+        check(self.ctx._lib.impop_pca_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, C.byref(prm),
+                                           out.ctypes.data_as(C.POINTER(_lib.PcaWindow)),
+                                           vec.ctypes.data_as(f64p) if want_vectors else None,
+                                           d2.ctypes.data_as(f64p) if want_dist else None))
+        return out, vec, d2
 
     def genotypes(self, pairs) -> "Genotypes":
         """The genotype planes of N >= 2 diploid individuals (impop_genotypes_create): pairs = [N, 2] haplotype indices as

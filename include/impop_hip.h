@@ -552,6 +552,70 @@ int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const impop_windo
                         const uint64_t *masks, uint32_t n_pop, const impop_pairdist_params *params,
                         impop_dist_panel *out_panels, impop_dist_pair *out_pairs /* nullable */,
                         uint32_t *hist_within /* nullable */, uint32_t *hist_between /* nullable */);
+#define IMPOP_PCA_MAX_N 1024u   /* members of the mask */
+#define IMPOP_PCA_MAX_K 8u
+/* PRINCIPAL COMPONENTS per window ("local PCA", Li & Ralph 2019): the k largest eigenpairs of the double-centred distance matrix
+ * of the members of one mask, from the Gram pass of impop_pairwise_scan.  For 0/1 haplotypes the Hamming distance is the squared
+ * Euclidean distance, so B below is X X^T with X the haplotype matrix centred per site: its eigenvectors are the principal
+ * component scores of the haplotypes.
+ * Per window, over the members P of mask_p (m = |P|, ascending haplotype index; NULL = all haplotypes):
+ *   H_ij  = the weighted Hamming distance of impop_pairdist_scan, a_i + a_j - 2 I_ij (polarity-invariant; the constant of a
+ *           compacted matrix cancels),
+ *   r_i   = sum_{j in P} H_ij,   t = sum_i r_i,   sum_h = sum_{i<j} H_ij = t / 2,
+ *   B_ij  = -1/2 (H_ij - r_i/m - r_j/m + t/m^2);   as exact integers  2 m^2 B_ij = m (r_i + r_j) - m^2 H_ij - t.
+ * trace(B) = sum_h / m,  B 1 = 0,  B is positive semidefinite with rank <= min(m - 1, number of sites).
+ * Output: the k (1 .. IMPOP_PCA_MAX_K) largest eigenpairs (lambda_j, v_j) of B.  lambda is descending; each v_j is a unit 2-norm
+ * vector of m doubles, orthogonal to the ones vector; sign: the component of largest magnitude is positive, the lowest index on
+ * exact ties.  The proportion of variance explained by pair j is lambda_j m / sum_h.
+ * Zero eigenvalues: a Ritz value theta_j <= tol trace(B) is reported as lambda_j = 0.0 with an all-zero vector; `rank` counts the
+ * others (a prefix of the k).  A window with sum_h = 0 (no sites, or all members identical) has rank 0 and iterations 0.
+ * Method and convergence: block subspace iteration with Rayleigh-Ritz on a block of 16 vectors (>= k + 8 for every k), in fp64.
+ * It iterates until every j < rank has || B v_j - theta_j v_j ||_2 <= tol theta_1; if max_iter steps do not get there, flag bit 0
+ * is set and the last iterate and its residuals are returned (the call still returns IMPOP_OK).  Guaranteed regime: with the
+ * default max_iter = 500 a window converges whenever lambda_{k+9} <= 0.9 lambda_j for every non-zero lambda_j, j <= k, of the
+ * exact spectrum (a block of at least k + 8 vectors contracts the error of pair j by at most lambda_{k+9} / lambda_j per step, and
+ * 0.9^500 ~ 1e-23).  Outside it, raise max_iter or read the flag.
+ * Determinism: the start block is a fixed function of (member position, column); every reduction has one fixed order and there
+ * are no floating-point atomics; everything the solver reads is an exact integer.  Two calls return identical bytes, and none of
+ * chunking (IMPOP_PAIRWISE_CHUNK), uint16 or int32 Gram counts (IMPOP_GRAM_U16=0), the Gram chain length (IMPOP_GRAM_CHAIN),
+ * compaction, weights against the bp-expanded matrix, or the order of the windows in the list changes a byte of a window's result.
+ * out_windows: n_windows records.  out_vectors (nullable): n_windows x k x |P| doubles, vector j of window w at (w k + j) |P|.
+ * out_dist2 (nullable): n_windows x n_windows, lostruct's distance between windows: with a_j = lambda_j / sum_{i<k} lambda_i,
+ *   d2(w, w') = sum_j a_j^2 + sum_l a'_l^2 - 2 sum_{j,l} a_j a'_l (v_j . v'_l)^2,
+ * clamped at 0 from below; exactly symmetric, the diagonal exactly 0; rows and columns of windows with rank 0 or flag bit 0 are
+ * NaN, the diagonal included.  d2 does not depend on the vectors' signs nor on rotations inside an eigenspace.  It is one launch
+ * after the last chunk, over the vectors of all windows, which stay on the device for it.
+ * Refusals, all before anything is uploaded or launched: struct_size mismatch, k = 0 or k > IMPOP_PCA_MAX_K, tol outside
+ * [1e-13, 1e-2], max_iter outside 1 .. 100000, |P| < 2, out_dist2 without out_vectors: IMPOP_E_INVALID; |P| > IMPOP_PCA_MAX_N,
+ * out_dist2 with more than 16384 windows: IMPOP_E_UNSUPPORTED.  n_windows == 0 returns IMPOP_OK.  Windows may overlap; a
+ * weighted matrix gives what its bp-expanded matrix gives.  Checks the device error word like impop_pairwise_scan.  With
+ * impop_ctx_gram_timing on, impop_ctx_pca_elapsed returns kernel_ms[0] = the eigen kernel of every chunk, [1] = the distance
+ * kernel, summed since enable / reset, next to the Gram time; chunks = eigen launches timed.
+ * Under IMPOP_TRACE=1 one line per call on stderr, next to the [impop_gram] lines:
+ *   [impop_pca_scan] route=<dense|compact> members= k= windows= chunks= launches= iterations_max= unconverged= dist=<off|on>
+ * Known answer: haplotypes 0000, 0001, 0111, 0001 over one 4-site window, all members: H01 = 1, H02 = 3, H03 = 1, H12 = 2,
+ * H13 = 0, H23 = 2; r = (5, 3, 7, 3), t = 18, sum_h = 9, trace = 2.25;
+ * 32 B = [[22, -2, -18, -2], [-2, 6, -10, 6], [-18, -10, 38, -10], [-2, 6, -10, 6]];
+ * lambda = (9 +- sqrt(17)) / 8 = 1.6403882032022..., 0.6096117967977..., the rest 0;
+ * v_1 = (-0.472668, -0.184524, 0.841716, -0.184524). */
+typedef struct impop_pca_params {   /* 24 bytes */
+    uint32_t struct_size, k;
+    double tol;                     /* relative residual bound, 1e-13 <= tol <= 1e-2; the Python and CLI default is 1e-10 */
+    uint32_t max_iter, reserved;    /* 1 .. 100000; default 500 */
+} impop_pca_params;
+typedef struct impop_pca_window {   /* 160 bytes, fixed layout: one per window */
+    uint32_t n_members, n_sites;
+    uint32_t rank;                  /* eigenvalues reported non-zero, <= k */
+    uint32_t iterations;
+    uint32_t flags;                 /* bit 0: not converged within max_iter */
+    uint32_t reserved;
+    uint64_t sum_h;                 /* exact; trace(B) = sum_h / n_members */
+    double lambda[8];               /* descending; 0.0 for rank <= j < k; NaN for j >= k */
+    double resid[8];                /* ||B v_j - lambda_j v_j||_2 as last evaluated; NaN for j >= rank */
+} impop_pca_window;
+int impop_pca_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                   const uint64_t *mask_p /* nullable */, const impop_pca_params *params, impop_pca_window *out_windows,
+                   double *out_vectors /* nullable: n_windows x k x |P| */, double *out_dist2 /* nullable: n_windows x n_windows */);
 #define IMPOP_KINSHIP_MAX_N 2048u        /* individuals of a genotype handle */
 #define IMPOP_KINSHIP_MAX_WATCH 1024u    /* watched pairs of a call */
 /* A PAIR OF INDIVIDUALS per window: the 3 x 3 joint genotype table and KING kinship of every pair of diploid individuals, from the
@@ -1017,6 +1081,9 @@ int impop_ctx_pairdist_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launc
 /* ... and impop_genotypes_create its plane-build kernel, impop_kinship_scan its epilogue kernels: kernel_ms[0] = plane builds,
  * [1] = epilogue, summed since enable / reset; chunks = chunks of impop_kinship_scan timed. */
 int impop_ctx_kinship_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks);
+/* ... and impop_pca_scan its two kernels: kernel_ms[0] = the eigen kernel of every chunk, [1] = the distance kernel, summed since
+ * enable / reset; chunks = eigen launches timed. */
+int impop_ctx_pca_elapsed(impop_ctx *ctx, double kernel_ms[2] /* eigen kernel, distance kernel */, uint64_t *chunks);
 /* Test aid: how many event pairs the four timers hold (created on first timed use, kept for reuse): sizes[0..2] = the
  * context's Gram / clustering / EHH timers, sizes[3] = the plan's (plan nullable: 0).  Nothing is created while timing is off. */
 int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]);
