@@ -100,6 +100,21 @@ class PcaParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("tol", C.c_double), ("max_iter", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class PermtestParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("n_perm", C.c_uint32), ("seed", C.c_uint64)]
+
+
+class PermPair(C.Structure):
+    _fields_ = [("n_a", C.c_uint32), ("n_b", C.c_uint32), ("n_sites", C.c_uint32), ("n_perm", C.c_uint32), ("wa", C.c_uint64),
+                ("wb", C.c_uint64), ("ab", C.c_uint64), ("nn", C.c_uint64), ("ge_fst", C.c_uint32), ("ge_phi", C.c_uint32),
+                ("ge_dxy", C.c_uint32), ("ge_snn", C.c_uint32), ("fst", C.c_double), ("phi_st", C.c_double), ("dxy", C.c_double),
+                ("snn", C.c_double), ("p_fst", C.c_double), ("p_phi", C.c_double), ("p_dxy", C.c_double), ("p_snn", C.c_double)]
+
+
+class PermNull(C.Structure):
+    _fields_ = [("wa", C.c_uint64), ("wb", C.c_uint64), ("nn", C.c_uint64)]
+
+
 class PcaWindow(C.Structure):
     _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("rank", C.c_uint32), ("iterations", C.c_uint32), ("flags", C.c_uint32),
                 ("reserved", C.c_uint32), ("sum_h", C.c_uint64), ("lambda", C.c_double * 8), ("resid", C.c_double * 8)]
@@ -272,6 +287,9 @@ assert C.sizeof(DistPanel) == 64 and C.sizeof(DistPair) == 96 and C.sizeof(Paird
 PAIRDIST_MAX_N, PAIRDIST_MAX_BINS = 4096, 1024  # IMPOP_PAIRDIST_MAX_N, IMPOP_PAIRDIST_MAX_BINS
 assert C.sizeof(PcaParams) == 24 and C.sizeof(PcaWindow) == 160
 PCA_MAX_N, PCA_MAX_K, PCA_MAX_DIST_WINDOWS = 1024, 8, 16384  # IMPOP_PCA_MAX_N, IMPOP_PCA_MAX_K, the most windows out_dist2 takes
+assert C.sizeof(PermtestParams) == 16 and C.sizeof(PermPair) == 128 and C.sizeof(PermNull) == 24
+# IMPOP_PERMTEST_MAX_N, IMPOP_PERMTEST_MAX_PERM, the most entries out_null takes, SCALE of the nn sums
+PERMTEST_MAX_N, PERMTEST_MAX_PERM, PERMTEST_MAX_NULL, PERMTEST_SCALE = 1024, 16384, 1 << 22, 2952069120
 assert C.sizeof(KinWindow) == 48 and C.sizeof(KinPair) == 72 and C.sizeof(KinWatch) == 16 and C.sizeof(KinshipParams) == 16
 KINSHIP_MAX_N, KINSHIP_MAX_WATCH = 2048, 1024  # IMPOP_KINSHIP_MAX_N, IMPOP_KINSHIP_MAX_WATCH
 assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWindow) == 24
@@ -360,6 +378,10 @@ SIGNATURES = {
     "impop_pairdist_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairdistParams),
                                       C.POINTER(DistPanel), C.POINTER(DistPair), _u32p, _u32p]),
     "impop_pca_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(PcaParams), C.POINTER(PcaWindow), _f64p, _f64p]),
+    "impop_permtest_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PermtestParams),
+                                      C.POINTER(PermPair), C.POINTER(PermNull)]),
+    "impop_permtest_labels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),
+    "impop_ctx_permtest_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_genotypes_create": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, C.POINTER(_vp)]),
     "impop_genotypes_info": (C.c_int, [_vp, _u32p, _u64p, _u64p]),
     "impop_genotypes_download": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, _u64p, C.c_uint64]),

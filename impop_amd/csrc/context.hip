@@ -247,7 +247,7 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
     const uint32_t w = ctx->h_err;
     ctx->h_err = 0;
     HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s%s%s%s); the results of this call are invalid", fn, w,
+    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s%s%s%s%s); the results of this call are invalid", fn, w,
               (w & DEV_ERR_GROUPING) ? ": greedy grouping made no progress" : "",
               (w & DEV_ERR_CLUSTER) ? ": clustering ran out of rounds" : "",
               (w & DEV_ERR_EHH) ? ": EHH partition refinement is inconsistent" : "",
@@ -256,7 +256,8 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
               (w & DEV_ERR_DIPLOID) ? ": diploid scan rows do not add up to their window" : "",
               (w & DEV_ERR_IBS) ? ": IBS scan's two sweeps disagree on a pair's tracts" : "",
               (w & DEV_ERR_IHS) ? ": iHS scan's break weights or reaches are inconsistent" : "",
-              (w & DEV_ERR_KINSHIP) ? ": kinship scan met a negative cell in a joint genotype table" : "");
+              (w & DEV_ERR_KINSHIP) ? ": kinship scan met a negative cell in a joint genotype table" : "",
+              (w & DEV_ERR_PERMTEST) ? ": permutation test's matrix-core sums of the observed labelling differ from the direct ones" : "");
     return IMPOP_E_INTERNAL;
 }
 }  // namespace impop
@@ -303,6 +304,11 @@ IMPOP_API int impop_ctx_kinship_elapsed(impop_ctx *ctx, double kernel_ms[2], uin
 IMPOP_API int impop_ctx_pca_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks) {
     REQUIRE(ctx && kernel_ms, "impop_ctx_pca_elapsed: NULL argument");
     return ctx_timers_elapsed(ctx, impop_ctx::T_PCA, 2, 0, kernel_ms, chunks);
+}
+
+IMPOP_API int impop_ctx_permtest_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks) {
+    REQUIRE(ctx && kernel_ms, "impop_ctx_permtest_elapsed: NULL argument");
+    return ctx_timers_elapsed(ctx, impop_ctx::T_PERM, 2, 1, kernel_ms, chunks);
 }
 
 IMPOP_API int impop_ctx_ehh_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {

@@ -1,5 +1,5 @@
 // pairwise_scan.hip — the windowed all-pairs calls (impop_pairwise_scan, impop_pairwise_scan_panel, impop_cluster_scan,
-// impop_pairdist_scan, impop_kinship_scan): one shared
+// impop_pairdist_scan, impop_kinship_scan, impop_pca_scan, impop_permtest_scan): one shared
 // front end — windows -> Gram cells -> chunks (pair_plan.h), per chunk the Gram launch (pairwise.hip) and the filled SimBatch — and
 // what each call does with the identities: its PairEpilogue.
 #include <stdlib.h>
@@ -11,6 +11,7 @@
 
 #include "pair_plan.h"
 #include "pca_math.h"
+#include "perm_math.h"
 #include "stats_kernels.h"
 #include "win_chunks.h"
 
@@ -664,6 +665,91 @@ struct KinshipEpilogue final : PairEpilogue {
     }
 };
 
+// impop_permtest_scan's epilogue (permtest.hip): per chunk the preparation kernel (byte planes of every pair's distance matrix,
+// row sums, tie masks, the observed integers) and the labelling kernel (the null integers on the matrix cores, compared and counted on
+// the device); the doubles of a record are finalised here, on the host, from the integers (perm_math.h)
+struct PermtestEpilogue final : PairEpilogue {
+    PermtestTables T{};
+    uint32_t n_perm;
+    const std::vector<uint32_t> *hap_of, *merged, *moff;
+    const std::vector<uint64_t> *z0, *labels, *loff;
+    impop_perm_pair *out_pairs;
+    impop_perm_null *out_null;  // nullable
+    uint64_t chunks = 0, launches = 0;
+    uint32_t *d_hap = nullptr, *d_merged = nullptr, *d_moff = nullptr;
+    uint64_t *d_z0 = nullptr, *d_labels = nullptr, *d_loff = nullptr;
+    PermtestScratch X{};
+    PermObs *h_obs = nullptr;
+    uint32_t *h_ge = nullptr, *h_st = nullptr;
+    uint64_t *h_null = nullptr;
+    impop_window_stats *h_ws = nullptr;
+    const impop_window_stats *d_ws = nullptr;
+    // the device bytes layout() takes per window of a chunk (they bound a chunk: impop_permtest_scan)
+    size_t per_window_bytes() const {
+        const size_t mp = T.m_pad_max;
+        return (size_t)T.NP * (mp * mp * T.planes + mp * T.mw_max * 8 + mp * 16 + sizeof(PermObs) + 16 + (out_null ? (size_t)n_perm * 24 : 0));
+    }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        const size_t slots = cap * T.NP, mp = T.m_pad_max;
+        D.sub(d_hap, T.M); D.sub(d_merged, merged->size()); D.sub(d_moff, T.NP + 1);
+        D.sub(d_z0, z0->size()); D.sub(d_labels, labels->size()); D.sub(d_loff, T.NP);
+        D.sub(X.planes, slots * mp * mp * T.planes); D.sub(X.ties, slots * mp * T.mw_max); D.sub(X.rows, slots * mp);
+        D.sub(X.term, slots * mp); D.sub(X.st, slots * mp); D.sub(X.obs, slots); D.sub(X.ge, slots * 4);
+        D.sub(X.null, out_null ? slots * n_perm * 3 : 0);
+        H.sub(h_obs, slots); H.sub(h_ge, slots * 4); H.sub(h_st, slots * mp); H.sub(h_null, out_null ? slots * n_perm * 3 : 0);
+        H.sub(h_ws, cap);
+    }
+    int upload(impop_ctx *ctx) override {
+        HIP_TRY(hipMemcpyAsync(d_hap, hap_of->data(), (size_t)T.M * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_merged, merged->data(), merged->size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_moff, moff->data(), moff->size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_z0, z0->data(), z0->size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_labels, labels->data(), labels->size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d_loff, loff->data(), loff->size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        T.hap_of = d_hap; T.merged = d_merged; T.moff = d_moff; T.z0 = d_z0; T.labels = d_labels; T.loff = d_loff;
+        if (!out_null) X.null = nullptr;  // (a table of zero bytes shares its offset with what follows it)
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        const uint64_t cnt = c.cnt, slots = cnt * T.NP;
+        HIP_TRY(hipMemsetAsync(X.ge, 0, slots * 16, ctx->stream));
+        size_t s0 = 0, s1 = 0;  // the two kernels between events of their own: impop_ctx_permtest_elapsed
+        int rc = ctx->gram_timing ? ctx->timers[impop_ctx::T_PERM].begin(ctx->stream, &s0) : IMPOP_OK;
+        if (rc) return rc;
+        if ((rc = launch_permtest_prep(ctx, c.b, cnt, T, X))) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PERM].end(ctx->stream, s0))) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PERM + 1].begin(ctx->stream, &s1))) return rc;
+        if ((rc = launch_permtest_labels(ctx, cnt, T, X))) return rc;
+        if (ctx->gram_timing && (rc = ctx->timers[impop_ctx::T_PERM + 1].end(ctx->stream, s1))) return rc;
+        ++chunks; launches += 2;
+        HIP_TRY(hipMemcpyAsync(h_obs, X.obs, slots * sizeof(PermObs), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_ge, X.ge, slots * 16, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_st, X.st, slots * T.m_pad_max * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(h_ws, c.d_s, cnt * sizeof(impop_window_stats), hipMemcpyDeviceToHost, ctx->stream));
+        if (out_null) HIP_TRY(hipMemcpyAsync(h_null, X.null, slots * n_perm * 24, hipMemcpyDeviceToHost, ctx->stream));
+        return IMPOP_OK;
+    }
+    void collect(const PairChunk &c) override {
+        for (uint64_t k = 0; k < c.cnt; ++k)
+            for (uint32_t p = 0, a = 0; a < T.K; ++a)
+                for (uint32_t b = a + 1; b < T.K; ++b, ++p) {
+                    const uint64_t slot = k * T.NP + p;
+                    const PermObs &o = h_obs[slot];
+                    const uint32_t m_k = T.off[a + 1] - T.off[a], m_l = T.off[b + 1] - T.off[b], *ge = h_ge + slot * 4;
+                    const PermDoubles d = perm_doubles(o, m_k, m_l);
+                    impop_perm_pair r;
+                    r.n_a = m_k; r.n_b = m_l; r.n_sites = h_ws[k].n_sites; r.n_perm = n_perm;
+                    r.wa = o.wa; r.wb = o.wb; r.ab = o.tot - o.wa - o.wb; r.nn = o.nn;
+                    r.ge_fst = ge[0]; r.ge_phi = ge[1]; r.ge_dxy = ge[2]; r.ge_snn = ge[3];
+                    r.fst = d.fst; r.phi_st = d.phi_st; r.dxy = d.dxy; r.snn = perm_snn(h_st + slot * T.m_pad_max, m_k + m_l);
+                    r.p_fst = perm_p(ge[0], n_perm); r.p_phi = perm_p(ge[1], n_perm); r.p_dxy = perm_p(ge[2], n_perm);
+                    r.p_snn = perm_p(ge[3], n_perm);
+                    out_pairs[c.ord[k] * T.NP + p] = r;
+                    if (out_null) memcpy(out_null + (c.ord[k] * T.NP + p) * n_perm, h_null + slot * n_perm * 3, (size_t)n_perm * 24);
+                }
+    }
+};
+
 // ---- what the entry points share -------------------------------------------------------------------------------------------
 // the checks of impop_pairwise_params common to the calls that take one
 int check_pairwise_params(const impop_pairwise_params *params, const char *fn) {
@@ -771,6 +857,119 @@ IMPOP_API int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const i
         fprintf(stderr, "[impop_pairdist_scan] pops=%u pairs=%u members=%u windows=%llu chunks=%llu launches=%llu hist_bins=%u hist=%s\n", K, NP,
                 M, (unsigned long long)n_windows, (unsigned long long)epi.chunks, (unsigned long long)epi.launches, epi.B,
                 !epi.B ? "off" : epi.hist_lds ? "lds" : "global");
+    return IMPOP_OK;
+}
+
+static_assert(sizeof(impop_permtest_params) == 16 && sizeof(impop_perm_pair) == 128 && sizeof(impop_perm_null) == 24, "fixed record layouts");
+static_assert(IMPOP_PERMTEST_MAX_N == PERMTEST_MAX_N && IMPOP_PERMTEST_MAX_PERM == PERMTEST_MAX_PERM, "the kernels' tables are sized for these");
+
+IMPOP_API int impop_permtest_labels(uint64_t seed, uint32_t pair_index, uint32_t m, uint32_t m_a, uint32_t n_perm, uint64_t *out) {
+    const char *fn = "impop_permtest_labels";
+    REQUIRE(out || !n_perm, "%s: out is NULL", fn);
+    REQUIRE(m >= 2 && m <= IMPOP_PERMTEST_MAX_N && m_a >= 1 && m_a < m, "%s: needs 1 <= m_a < m <= %u", fn, (uint32_t)IMPOP_PERMTEST_MAX_N);
+    REQUIRE(n_perm <= IMPOP_PERMTEST_MAX_PERM, "%s: n_perm must be at most %u", fn, (uint32_t)IMPOP_PERMTEST_MAX_PERM);
+    std::vector<uint32_t> a(m);
+    const uint32_t mw = (m + 63) / 64;
+    for (uint32_t r = 0; r < n_perm; ++r) perm_labelling(seed, pair_index, r, m, m_a, a.data(), out + (size_t)r * mw);
+    return IMPOP_OK;
+}
+
+IMPOP_API int impop_permtest_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                  const uint64_t *masks, uint32_t n_pop, const impop_permtest_params *params, impop_perm_pair *out_pairs,
+                                  impop_perm_null *out_null) {
+    const char *fn = "impop_permtest_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_permtest_params), "impop_permtest_params.struct_size mismatch");
+    REQUIRE(n_pop >= 2 && n_pop <= 8, "%s: n_pop must be 2..8", fn);
+    REQUIRE(params->n_perm >= 1 && params->n_perm <= IMPOP_PERMTEST_MAX_PERM, "%s: n_perm must be 1..%u", fn, (uint32_t)IMPOP_PERMTEST_MAX_PERM);
+    REQUIRE(masks, "%s: masks is NULL", fn);
+    const uint32_t n = m->g.n_hap, K = n_pop, NP = K * (K - 1) / 2, mwords = (n + 63) / 64, n_perm = params->n_perm;
+    std::vector<uint8_t> cls(n, 0xFF);
+    std::vector<uint32_t> hap_of;  // the panels' members back to back, each ascending: position -> haplotype
+    PermtestEpilogue epi;
+    for (uint32_t k = 0; k < K; ++k) {
+        epi.T.off[k] = (uint32_t)hap_of.size();
+        for (uint32_t i : mask_members(masks + (size_t)k * mwords, n)) {
+            REQUIRE(cls[i] == 0xFF, "%s: populations must be disjoint (population %u overlaps population %u)", fn, k, (uint32_t)cls[i]);
+            cls[i] = (uint8_t)k;
+            hap_of.push_back(i);
+        }
+        REQUIRE(hap_of.size() > epi.T.off[k], "%s: population %u is empty", fn, k);
+    }
+    for (uint32_t k = K; k < 9; ++k) epi.T.off[k] = (uint32_t)hap_of.size();
+    if (hap_of.size() > IMPOP_PERMTEST_MAX_N) {  // refused before anything is uploaded or launched
+        set_error("%s: the panels hold %zu members, more than the limit of %u", fn, hap_of.size(), (uint32_t)IMPOP_PERMTEST_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    if (out_null && (n_windows > (1ull << 22) || n_windows * NP * n_perm > (1ull << 22))) {
+        set_error("%s: a null table of %llu windows x %u pairs x %u labellings exceeds 2^22 entries", fn, (unsigned long long)n_windows, NP, n_perm);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    if (!n_windows) return IMPOP_OK;
+    REQUIRE(windows && out_pairs, "%s: NULL windows/out", fn);
+    int rc = check_windows(ctx, m, windows, n_windows, fn);
+    if (rc) return rc;
+    uint64_t p_max = 0;
+    for (uint32_t k = 0; k < K; ++k) p_max = std::max<uint64_t>(p_max, perm_q(epi.T.off[k + 1] - epi.T.off[k]));
+    const uint64_t max_W = widest_W(m, windows, n_windows);
+    if (!perm_fst_admitted(max_W, p_max)) {  // before any launch
+        set_error("%s: the Fst comparison may overflow: the widest window has W = %llu and the largest panel %llu pairs (W x pairs^2 must "
+                  "stay at or below 2^62)", fn, (unsigned long long)max_W, (unsigned long long)p_max);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    // per pair of panels: both panels' positions merged into ascending haplotype index, the observed labelling over that order, and
+    // the labellings themselves (the one generator: perm_math.h perm_labelling)
+    std::vector<uint32_t> merged, moff(1, 0u), fy(IMPOP_PERMTEST_MAX_N);
+    std::vector<uint64_t> z0, labels, loff;
+    uint32_t m_max = 0;
+    for (uint32_t a = 0; a < K; ++a)
+        for (uint32_t b = a + 1; b < K; ++b) m_max = std::max(m_max, epi.T.off[a + 1] - epi.T.off[a] + epi.T.off[b + 1] - epi.T.off[b]);
+    const uint32_t mw_max = (m_max + 63) / 64;
+    for (uint32_t a = 0, p = 0; a < K; ++a)
+        for (uint32_t b = a + 1; b < K; ++b, ++p) {
+            uint32_t i = epi.T.off[a], j = epi.T.off[b];
+            z0.resize((size_t)(p + 1) * mw_max, 0ull);
+            for (uint32_t at = 0; i < epi.T.off[a + 1] || j < epi.T.off[b + 1]; ++at) {
+                const bool from_a = j >= epi.T.off[b + 1] || (i < epi.T.off[a + 1] && hap_of[i] < hap_of[j]);
+                if (from_a) z0[(size_t)p * mw_max + (at >> 6)] |= 1ull << (at & 63u);
+                merged.push_back(from_a ? i++ : j++);
+            }
+            moff.push_back((uint32_t)merged.size());
+            const uint32_t mp = moff[p + 1] - moff[p], mw = (mp + 63) / 64;
+            loff.push_back(labels.size());
+            labels.resize(labels.size() + (size_t)n_perm * mw);
+            for (uint32_t r = 0; r < n_perm; ++r)
+                perm_labelling(params->seed, p, r, mp, epi.T.off[a + 1] - epi.T.off[a], fy.data(), labels.data() + loff[p] + (size_t)r * mw);
+        }
+    HIP_TRY(hipSetDevice(ctx->device));
+    epi.T.K = K; epi.T.M = (uint32_t)hap_of.size(); epi.T.NP = NP; epi.T.n_perm = n_perm;
+    uint64_t h_max = max_W;  // a distance is at most its window's W; on a compacted matrix at most what the window KEEPS
+    if (compact_weighted(m)) {
+        h_max = 0;
+        for (uint64_t i = 0; i < n_windows; ++i)
+            h_max = std::max(h_max, window_W(m, windows[i].site_begin, windows[i].site_end) - ones_weight(m, windows[i].site_begin, windows[i].site_end));
+    } else if (m->compact) {
+        std::vector<impop_window> kept;
+        if ((rc = map_windows_device(ctx, m, windows, n_windows, kept))) return rc;
+        h_max = 0;
+        for (uint64_t i = 0; i < n_windows; ++i) h_max = std::max(h_max, kept[i].site_end - kept[i].site_begin);
+    }
+    epi.T.planes = h_max < 256 ? 1u : h_max < 65536 ? 2u : h_max < (1ull << 24) ? 3u : 4u;
+    epi.T.mw_max = mw_max; epi.T.m_pad_max = 64 * mw_max;
+    epi.n_perm = n_perm;
+    epi.hap_of = &hap_of; epi.merged = &merged; epi.moff = &moff; epi.z0 = &z0; epi.labels = &labels; epi.loff = &loff;
+    epi.out_pairs = out_pairs; epi.out_null = out_null;
+    PairFront in{};
+    in.fn = fn; in.identity_kind = IMPOP_IDENTITY_MATCH; in.round_digits = -1;  // Hamming distances: no unflip pass
+    in.scan_host = nullptr; in.use_segmap = false; in.max_W = max_W;
+    // the byte planes, tie masks and null rows of a chunk: at most 1 GiB of them
+    in.max_chunk_windows = std::min<uint64_t>(65535, std::max<uint64_t>(1, (1ull << 30) / epi.per_window_bytes()));
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (trace_on())
+        fprintf(stderr, "[impop_permtest_scan] route=%s pops=%u pairs=%u members=%u perms=%u planes=%u windows=%llu chunks=%llu launches=%llu "
+                "null=%s\n", m->compact ? "compact" : "dense", K, NP, epi.T.M, n_perm, epi.T.planes, (unsigned long long)n_windows,
+                (unsigned long long)epi.chunks, (unsigned long long)epi.launches, out_null ? "on" : "off");
     return IMPOP_OK;
 }
 

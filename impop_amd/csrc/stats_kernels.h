@@ -306,6 +306,34 @@ int launch_kinship_windows(impop_ctx *ctx, const SimBatch &b, uint64_t n_problem
 // the per-pair tables of the chunk's problems added into O.totals: one thread per pair, the problems in turn
 int launch_kinship_totals(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, const KinshipOut &O);
 
+// impop_permtest_scan's kernels (permtest.hip).  A SLOT is a (problem, pair of panels): slot = problem x NP + pair.  The members
+// of a pair are positions 0 .. m - 1 in ascending haplotype index (the merged lists of impop_pairdist_scan); m_pad = 64 ceil(m / 64).
+struct PermObs;
+constexpr uint32_t PERM_TASK_COLS = 64;  // columns of a labelling task: z0 and 63 labellings
+struct PermtestTables {
+    const uint32_t *hap_of;   // M: haplotype index of a panel-major position
+    const uint32_t *merged;   // per pair p: the positions of both panels in ascending haplotype index, at moff[p]
+    const uint32_t *moff;     // NP + 1
+    const uint64_t *z0;       // per pair p: the observed labelling, mw_max words at p x mw_max
+    const uint64_t *labels;   // per pair p: n_perm x ceil(m_p / 64) words at loff[p]
+    const uint64_t *loff;     // NP
+    uint32_t off[9];
+    uint32_t K, M, NP, n_perm, planes, m_pad_max, mw_max;  // planes: bytes of a distance, 1..4; the largest m_pad / its words
+};
+struct PermtestScratch {
+    int8_t *planes;    // slot x planes x m_pad_max^2: plane q of H as (byte - 128), row stride the PAIR's m_pad
+    uint64_t *ties;    // slot x m_pad_max x mw_max: row i's nearest-neighbour tie mask at i x ceil(m / 64)
+    uint64_t *rows;    // slot x m_pad_max: r_i
+    uint32_t *term;    // slot x m_pad_max: SCALE / tied_i
+    uint32_t *st;      // slot x m_pad_max: same_i(z0) << 16 | tied_i (the host's snn)
+    PermObs *obs;      // slot: the observed wa, wb, nn and tot
+    uint32_t *ge;      // slot x 4: fst, phi, dxy, snn; zeroed by the caller, added to with integer atomics
+    uint64_t *null;    // slot x n_perm x {wa, wb, nn}, or nullptr
+};
+uint32_t permtest_blocks(uint32_t n_perm);  // labelling tasks per slot
+int launch_permtest_prep(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const PermtestTables &T, const PermtestScratch &X);
+int launch_permtest_labels(impop_ctx *ctx, uint64_t n_problems, const PermtestTables &T, const PermtestScratch &X);
+
 }  // namespace impop
 
 // the genotype planes of impop_genotypes_create: a matrix the Gram front end accepts (2N rows, RB32 operand alone), as its own type

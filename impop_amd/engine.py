@@ -83,6 +83,12 @@ assert DIST_PANEL_DTYPE.itemsize == 64 and DIST_PAIR_DTYPE.itemsize == 96
 PCA_WINDOW_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("rank", "<u4"), ("iterations", "<u4"), ("flags", "<u4"),
                              ("reserved", "<u4"), ("sum_h", "<u8"), ("lambda", "<f8", (8,)), ("resid", "<f8", (8,))])
 assert PCA_WINDOW_DTYPE.itemsize == 160
+PERM_PAIR_DTYPE = np.dtype([("n_a", "<u4"), ("n_b", "<u4"), ("n_sites", "<u4"), ("n_perm", "<u4"), ("wa", "<u8"), ("wb", "<u8"), ("ab", "<u8"),
+                            ("nn", "<u8"), ("ge_fst", "<u4"), ("ge_phi", "<u4"), ("ge_dxy", "<u4"), ("ge_snn", "<u4"), ("fst", "<f8"),
+                            ("phi_st", "<f8"), ("dxy", "<f8"), ("snn", "<f8"), ("p_fst", "<f8"), ("p_phi", "<f8"), ("p_dxy", "<f8"),
+                            ("p_snn", "<f8")])
+PERM_NULL_DTYPE = np.dtype([("wa", "<u8"), ("wb", "<u8"), ("nn", "<u8")])
+assert PERM_PAIR_DTYPE.itemsize == 128 and PERM_NULL_DTYPE.itemsize == 24
 
 KIN_WINDOW_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("n_pairs", "<u8"), ("het_het", "<u8"), ("ibs0", "<u8"), ("ibs2", "<u8"),
                              ("n_related", "<u4"), ("n_undefined", "<u4")])
@@ -144,6 +150,15 @@ def _mask_ptr(mask, n):
         raise ValueError("bitset mask has the wrong number of words")
     a = np.ascontiguousarray(a, dtype=np.uint64)
     return a, a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def permtest_labels(seed: int, pair_index: int, m: int, m_a: int, n_perm: int) -> np.ndarray:
+    """The labellings impop_permtest_scan uses (impop_permtest_labels; host only): [n_perm, ceil(m / 64)] uint64 masks over the
+    m positions of a pair's members in ascending haplotype index, each with exactly m_a ones."""
+    out = np.zeros((int(n_perm), (int(m) + 63) // 64), dtype=np.uint64)
+    check(_lib.load().impop_permtest_labels(int(seed) & 0xFFFFFFFFFFFFFFFF, int(pair_index), int(m), int(m_a), int(n_perm),
+                                            out.ctypes.data_as(C.POINTER(C.c_uint64))))
+    return out
 
 
 def make_windows(windows) -> np.ndarray:
@@ -234,6 +249,12 @@ class Context:
         """-> ([eigen kernel, distance kernel] ms of pca_scan, chunks) since gram_timing(True)"""
         t, k = (C.c_double * 2)(), C.c_uint64()
         check(self._lib.impop_ctx_pca_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def permtest_elapsed(self):
+        """-> ([preparation kernel, labelling kernel] ms of permtest_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 2)(), C.c_uint64()
+        check(self._lib.impop_ctx_permtest_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def kinship_elapsed(self):
@@ -752,6 +773,29 @@ class BitMatrix:
                                            vec.ctypes.data_as(f64p) if want_vectors else None,
                                            d2.ctypes.data_as(f64p) if want_dist else None))
         return out, vec, d2
+
+    def permtest_scan(self, windows, pops, n_perm: int = 1000, seed: int = 1, null: bool = False):
+        """Permutation p-values for Hudson's Fst, AMOVA Phi_ST, Dxy and S_nn of every pair of K (2..8) disjoint panels, from ONE Gram
+        pass per window (impop_permtest_scan).  The same n_perm labellings (permtest_labels) serve every window of the call.
+        -> (pairs [n_windows, K(K-1)/2] PERM_PAIR_DTYPE in the pair order of scan_multi,
+            null [n_windows, K(K-1)/2, n_perm] PERM_NULL_DTYPE or None): the observed integers and doubles, how many labellings were
+        at least as extreme per test, p = (1 + ge) / (n_perm + 1); null holds every labelling's (wa, wb, nn)."""
+        w = make_windows(windows)
+        K = len(pops)
+        NP = K * (K - 1) // 2
+        packed = np.concatenate([_mask_ptr(p, self.n_hap)[0] for p in pops]).astype(np.uint64) if K else np.zeros(1, np.uint64)
+        n_perm = int(n_perm)
+        pairs = np.zeros((len(w), NP), dtype=PERM_PAIR_DTYPE)
+        nul = None
+        if null:  # a shape the call refuses (n_perm, the 2^22 entries of a null table) gets no table allocated for it first
+            ok = 0 < n_perm <= _lib.PERMTEST_MAX_PERM and len(w) * NP * n_perm <= _lib.PERMTEST_MAX_NULL
+            nul = np.zeros((len(w), NP, n_perm) if ok else (1, 1, 1), dtype=PERM_NULL_DTYPE)
+        prm = _lib.PermtestParams(C.sizeof(_lib.PermtestParams), max(n_perm, 0), int(seed) & 0xFFFFFFFFFFFFFFFF)
+        check(self.ctx._lib.impop_permtest_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w),
+                                                packed.ctypes.data_as(C.POINTER(C.c_uint64)), K, C.byref(prm),
+                                                pairs.ctypes.data_as(C.POINTER(_lib.PermPair)),
+                                                nul.ctypes.data_as(C.POINTER(_lib.PermNull)) if null else None))
+        return pairs, nul
 
     def genotypes(self, pairs) -> "Genotypes":
         """The genotype planes of N >= 2 diploid individuals (impop_genotypes_create): pairs = [N, 2] haplotype indices as

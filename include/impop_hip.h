@@ -616,6 +616,87 @@ typedef struct impop_pca_window {   /* 160 bytes, fixed layout: one per window *
 int impop_pca_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                    const uint64_t *mask_p /* nullable */, const impop_pca_params *params, impop_pca_window *out_windows,
                    double *out_vectors /* nullable: n_windows x k x |P| */, double *out_dist2 /* nullable: n_windows x n_windows */);
+#define IMPOP_PERMTEST_MAX_N 1024u      /* members of the panels' union */
+#define IMPOP_PERMTEST_MAX_PERM 16384u  /* labellings of a call */
+/* PERMUTATION P-VALUES for Hudson's Fst, AMOVA Phi_ST, Dxy and Hudson's S_nn (Hudson 2000) per window and pair of panels, from
+ * the Gram pass of impop_pairdist_scan.  The device adds integers only.
+ * masks, n_pop: as impop_pairdist_scan — disjoint, non-empty bitsets — with n_pop 2..8 and at most IMPOP_PERMTEST_MAX_N members in
+ * the union of all panels.  out_pairs: n_windows x K(K-1)/2 records in the pair order of impop_scan_multi.
+ * For a pair k < l: U = the members of k u l in ascending haplotype index, positions 0 .. m - 1 (m = m_k + m_l).  A LABELLING z is
+ * an m-bit mask (bit i of word i / 64) with exactly m_k ones; z0, the observed labelling, marks the members of k.
+ * Integers of a labelling, with H_ij the weighted Hamming distance of impop_pairdist_scan (polarity, compaction and weights cancel
+ * as they do there):
+ *   wa(z) = sum_{i<j, z_i=z_j=1} H_ij,   wb(z) = sum_{i<j, z_i=z_j=0} H_ij,   tot = sum_{i<j in U} H_ij,   ab(z) = tot - wa - wb.
+ * Nearest neighbours do not depend on the labelling: d_i = min_{j != i in U} H_ij, T_i = {j : H_ij = d_i}, tied_i = |T_i|; then
+ *   same_i(z) = #{j in T_i : z_j = z_i},   nn(z) = sum_i same_i(z) * floor(SCALE / tied_i),   SCALE = 2952069120 (= 720720 * 4096).
+ * SCALE makes equal multisets of terms sum to equal integers in any order; the sum is exact whenever tied_i <= 16 or tied_i divides
+ * SCALE.
+ * "At least as extreme": all four tests are one-sided, towards more differentiation, and compared in integers:
+ *   dxy:  ab(z) >= ab(z0)
+ *   phi:  wa(z) m_l + wb(z) m_k <= wa(z0) m_l + wb(z0) m_k   (AMOVA Phi_ST of two groups, Excoffier et al. 1992: Phi_ST falls
+ *         strictly as the within-group SSD rises, because the total SSD is fixed)
+ *   fst:  x(z) ab(z0) <= x(z0) ab(z) as 128-bit products, x(z) = wa q_l + wb q_k, q = max(m (m - 1) / 2, 1) of the panel (Hudson,
+ *         the estimator of h-fst.py).  The inequality is the definition in the degenerate cases too: ab(z) = 0 with x(z) > 0 is
+ *         not counted against a z0 with ab(z0) > 0; tot = 0 counts every labelling.
+ *   snn:  nn(z) >= nn(z0)
+ * Labellings.  impop_permtest_labels is the one definition: labelling r of pair index p is a uniform random m_k-subset of the m
+ * positions, a function of (seed, p, m, m_k, r) only — not of n_perm, the windows, the chunking or the device — so a call with fewer
+ * permutations sees a prefix.  Generator: sm(x) = splitmix64's output for state x, that is z = x + 0x9E3779B97F4A7C15;
+ * z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31).  k1 = sm(seed),
+ * k2 = sm(k1 ^ p), k3 = sm(k2 ^ r), u_t = sm(k3 + t * 0x9E3779B97F4A7C15) (all mod 2^64).  A partial Fisher-Yates over
+ * a[0 .. m) = 0 .. m - 1: step t = 0 .. m_k - 1 swaps a[t] with a[t + hi], hi = the high 64 bits of the 128-bit product
+ * u_t * (m - t); the labelling's ones are a[0 .. m_k).  The same labellings serve every window of a call (the tables are built once,
+ * on the host, and uploaded): THE P-VALUES OF NEIGHBOURING WINDOWS THEREFORE SHARE THEIR NULL DRAWS.
+ * Record: n_a = m_k, n_b = m_l, n_sites = the window's W; wa, wb, ab, nn of z0; ge_* = how many of the n_perm labellings are counted
+ * above (z0 itself is not among them); p_* = (1.0 + (double)ge) / ((double)n_perm + 1.0).  The observed doubles are in raw distance
+ * units, not divided by W (fst and phi_st are scale-free), finalised on the host from the integers in this order:
+ *   dxy    = (double)ab / ((double)m_k * (double)m_l)
+ *   pi_a   = (double)wa / (double)q_k when m_k >= 2, else 0.0; pi_b likewise from wb, q_l, m_l;  pi_xy = (pi_a + pi_b) / 2.0
+ *   fst    = (dxy - pi_xy) / dxy when dxy > 0.0, else 0.0                                              
+ *   phi_st = NaN when m <= 2; else ssd_w = (double)wa / (double)m_k + (double)wb / (double)m_l;  ssd_a = (double)tot / (double)m - ssd_w;
+ *            ms_w = ssd_w / (double)(m - 2);  n0 = 2.0 * (double)m_k * (double)m_l / (double)m;  s2a = (ssd_a - ms_w) / n0;
+ *            den = s2a + ms_w;  phi_st = s2a / den, NaN when den == 0.0
+ *   snn    = the snn of impop_pairdist_scan for the same pair (same bytes): the left-to-right sum of (double)same_i(z0) /
+ *            (double)tied_i over i ascending, divided by (double)m
+ * out_null (nullable): n_windows x pairs x n_perm entries {wa, wb, nn}, the null distribution; allowed when n_windows * pairs *
+ * n_perm <= 2^22, otherwise IMPOP_E_UNSUPPORTED.
+ * Refusals, all before anything is uploaded or launched.  IMPOP_E_INVALID: struct_size mismatch, n_pop < 2 or > 8, n_perm = 0 or >
+ * IMPOP_PERMTEST_MAX_PERM, overlapping or empty masks.  IMPOP_E_UNSUPPORTED: union > IMPOP_PERMTEST_MAX_N; the null-table bound;
+ * W_max * P_max^2 > 2^62 (W_max the widest window weight, P_max the largest q of any panel), so that x fits 63 bits and the 128-bit
+ * products cannot overflow — the message names both numbers.  n_windows == 0 returns IMPOP_OK.
+ * Two calls return identical bytes, and none of chunking (IMPOP_PAIRWISE_CHUNK), uint16 or int32 Gram counts (IMPOP_GRAM_U16=0),
+ * the Gram chain length (IMPOP_GRAM_CHAIN), compaction, weights against the bp-expanded matrix, or the order of the windows changes a
+ * byte.  Checks the device error word like impop_pairwise_scan; in particular every labelling task recomputes z0 on the matrix
+ * cores and the call fails (IMPOP_E_INTERNAL) if that differs from the direct sums.  With impop_ctx_gram_timing on,
+ * impop_ctx_permtest_elapsed returns kernel_ms[0] = the preparation kernel, [1] = the labelling kernel, summed since enable / reset.
+ * Under IMPOP_TRACE=1 one line per call on stderr, next to the [impop_gram] lines:
+ *   [impop_permtest_scan] route=<dense|compact> pops= pairs= members= perms= planes= windows= chunks= launches= null=<off|on>
+ * (planes = the bytes a distance of the call takes, 1..4).
+ * Known answer: haplotypes 0000, 0001, 0111, 0001 over one 4-site window, panels {0,1} and {2,3}: H01 = 1, H02 = 3, H03 = 1,
+ * H12 = 2, H13 = 0, H23 = 2, tot = 9.  Observed: wa 1, wb 2, ab 6; T = ({1,3}, {3}, {1,3}, {1}), same(z0) = (1, 0, 1, 0),
+ * nn = SCALE, snn = 0.25.  The six possible labellings by their A positions give (wa, wb) = {0,1}: (1,2), {0,2}: (3,0),
+ * {0,3}: (1,2), {1,2}: (2,1), {1,3}: (0,3), {2,3}: (2,1); ab = 6 for all of them. */
+typedef struct impop_permtest_params {  /* 16 bytes */
+    uint32_t struct_size;
+    uint32_t n_perm;                    /* 1 .. IMPOP_PERMTEST_MAX_PERM */
+    uint64_t seed;
+} impop_permtest_params;
+typedef struct impop_perm_pair {        /* 128 bytes, fixed layout: one per (window, pair k < l) */
+    uint32_t n_a, n_b, n_sites, n_perm;
+    uint64_t wa, wb, ab, nn;            /* observed */
+    uint32_t ge_fst, ge_phi, ge_dxy, ge_snn;
+    double fst, phi_st, dxy, snn;       /* observed */
+    double p_fst, p_phi, p_dxy, p_snn;
+} impop_perm_pair;
+typedef struct impop_perm_null {        /* 24 bytes */
+    uint64_t wa, wb, nn;
+} impop_perm_null;
+int impop_permtest_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                        const uint64_t *masks, uint32_t n_pop, const impop_permtest_params *params, impop_perm_pair *out_pairs,
+                        impop_perm_null *out_null /* nullable */);
+/* Host only, no context: labellings 0 .. n_perm - 1 of pair index pair_index over m positions with m_a ones (1 <= m_a < m <=
+ * IMPOP_PERMTEST_MAX_N, n_perm <= IMPOP_PERMTEST_MAX_PERM; else IMPOP_E_INVALID).  out: n_perm x ceil(m / 64) words. */
+int impop_permtest_labels(uint64_t seed, uint32_t pair_index, uint32_t m, uint32_t m_a, uint32_t n_perm, uint64_t *out);
 #define IMPOP_KINSHIP_MAX_N 2048u        /* individuals of a genotype handle */
 #define IMPOP_KINSHIP_MAX_WATCH 1024u    /* watched pairs of a call */
 /* A PAIR OF INDIVIDUALS per window: the 3 x 3 joint genotype table and KING kinship of every pair of diploid individuals, from the
@@ -1084,6 +1165,9 @@ int impop_ctx_kinship_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chu
 /* ... and impop_pca_scan its two kernels: kernel_ms[0] = the eigen kernel of every chunk, [1] = the distance kernel, summed since
  * enable / reset; chunks = eigen launches timed. */
 int impop_ctx_pca_elapsed(impop_ctx *ctx, double kernel_ms[2] /* eigen kernel, distance kernel */, uint64_t *chunks);
+/* ... and impop_permtest_scan its two kernels: kernel_ms[0] = the preparation kernel, [1] = the labelling kernel of every chunk,
+ * summed since enable / reset; chunks = chunks timed. */
+int impop_ctx_permtest_elapsed(impop_ctx *ctx, double kernel_ms[2] /* preparation, labelling */, uint64_t *chunks);
 /* Test aid: how many event pairs the four timers hold (created on first timed use, kept for reuse): sizes[0..2] = the
  * context's Gram / clustering / EHH timers, sizes[3] = the plan's (plan nullable: 0).  Nothing is created while timing is off. */
 int impop_debug_timer_pool_sizes(const impop_ctx *ctx, const impop_scan_plan *plan, uint64_t sizes[4]);
