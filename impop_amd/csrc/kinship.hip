@@ -1,15 +1,15 @@
 // kinship.hip — impop_genotypes_* (the per-individual genotype planes H = h1 ^ h2, A = h1 & h2, built on the device straight into
-// the Gram kernel's RB32 operand layout) and the kernels of impop_kinship_scan's epilogue (pairwise_scan.hip KinshipEpilogue): per
-// window and pair of individuals the 3 x 3 joint genotype table from four Gram entries and the diagonals (kin_math.h).
-#include <string.h>
-
-#include <algorithm>
-#include <vector>
-
-#include "chunk_run.h"
+// the Gram kernel's RB32 operand layout) and impop_kinship_scan: its kernels, its PairEpilogue (pair_front.h) and the entry point.
+// Per window and pair of individuals the 3 x 3 joint genotype table from four Gram entries and the diagonals (kin_math.h).
 #include "hap_words.h"
 #include "kin_math.h"
-#include "stats_kernels.h"
+#include "pair_front.h"
+
+// the genotype planes of impop_genotypes_create: a matrix the Gram front end accepts (2N rows, RB32 operand alone), as its own type
+struct impop_genotypes {
+    impop_matrix *planes = nullptr;
+    uint32_t n_ind = 0;
+};
 
 namespace impop {
 
@@ -65,7 +65,17 @@ __global__ void geno_download_kernel(const uint32_t *__restrict__ rb, uint64_t r
     out[t] = v;
 }
 
-// ---- the epilogue --------------------------------------------------------------------------------------------------------------
+// ---- the epilogue, on a chunk's Gram problems of the 2N plane rows [H_0 .. H_{N-1}, A_0 .. A_{N-1}] -------------------------------
+struct KinshipOut {
+    impop_kin_window *windows;  // n_problems
+    impop_kin_watch *watch;     // n_problems x n_watch, or nullptr
+    uint64_t *totals;           // N (N - 1) / 2 x 9, ADDED to (one owner per entry), or nullptr
+    uint32_t *diag;             // scratch: n_problems x 2N, het then alt per problem (the windows kernel writes, the totals kernel reads)
+    uint64_t *part;             // scratch: kinship_total_slices x N (N - 1) / 2 x 9 when there is more than one slice, else unused
+};
+constexpr uint64_t KIN_TOTALS_THREADS = 1ull << 19;  // (pair, slice) threads the totals kernel aims at
+constexpr uint32_t KIN_TOTALS_MAX_SLICES = 64;
+
 // the table of the pair i < j of problem S.  gram_at adds a compacted problem's constant (its dropped all-ones sites) to every entry:
 // it belongs to alt and AA alone, so the H entries give it back
 __device__ __forceinline__ bool kin_pair_table(const SimView &S, uint32_t N, uint32_t i, uint32_t j, uint32_t het_i, uint32_t alt_i,
@@ -162,13 +172,14 @@ __global__ __launch_bounds__(KIN_T) void kinship_totals_reduce_kernel(const uint
 }
 
 // slices of the totals kernel: enough (pair, slice) threads to fill the device, never more slices than windows
-uint32_t kinship_total_slices(uint32_t N, uint64_t n_problems) {
+static uint32_t kinship_total_slices(uint32_t N, uint64_t n_problems) {
     const uint64_t pairs = (uint64_t)N * (N - 1) / 2;
     const uint64_t want = (KIN_TOTALS_THREADS + pairs - 1) / pairs;
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, KIN_TOTALS_MAX_SLICES), n_problems));
 }
 
-int launch_kinship_windows(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, int64_t num, int64_t den,
+// window records and watch rows: one workgroup per problem
+static int launch_kinship_windows(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, int64_t num, int64_t den,
                            const uint32_t *d_watch, uint32_t n_watch, const KinshipOut &O) {
     if (!n_problems) return IMPOP_OK;
     REQUIRE(N >= 2 && N <= IMPOP_KINSHIP_MAX_N && 2 * N <= b.n && n_problems < 0x7FFFFFFFull && O.diag && (!n_watch || (d_watch && O.watch)),
@@ -179,7 +190,8 @@ int launch_kinship_windows(impop_ctx *ctx, const SimBatch &b, uint64_t n_problem
     return IMPOP_OK;
 }
 
-int launch_kinship_totals(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, const KinshipOut &O) {
+// the per-pair tables of the chunk's problems added into O.totals: one thread per pair, the problems in turn
+static int launch_kinship_totals(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, const KinshipOut &O) {
     if (!n_problems) return IMPOP_OK;
     const uint32_t Z = kinship_total_slices(N, n_problems);
     REQUIRE(N >= 2 && N <= IMPOP_KINSHIP_MAX_N && 2 * N <= b.n && O.diag && O.totals && (Z == 1 || O.part), "launch_kinship_totals: bad shape");
@@ -194,6 +206,45 @@ int launch_kinship_totals(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems
     }
     return IMPOP_OK;
 }
+
+// impop_kinship_scan's epilogue: per chunk the window kernel (records, watch rows, the diagonals) and, when the per-pair totals are
+// wanted, the totals kernel, which adds the chunk's tables into d_tot; d_tot lives across the chunks
+struct KinshipEpilogue final : PairEpilogue {
+    uint32_t N, n_watch;
+    int64_t num, den;
+    const uint32_t *watch;            // 2 x n_watch, host
+    Result<impop_kin_window> win;
+    Result<impop_kin_watch> wat;
+    bool want_totals;
+    uint64_t launches = 0;
+    uint32_t *d_watch = nullptr, *d_diag = nullptr;
+    uint64_t *d_tot = nullptr, *d_part = nullptr;
+    size_t n_totals() const { return want_totals ? (size_t)N * (N - 1) / 2 * 9 : 0; }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        D.sub(d_watch, 2 * (size_t)n_watch); D.sub(d_tot, n_totals());
+        const uint32_t Z = want_totals ? kinship_total_slices(N, cap) : 1u;  // the most slices a chunk of up to cap windows takes
+        D.sub(d_part, Z > 1 ? Z * n_totals() : 0);
+        D.sub(d_diag, cap * 2 * N); win.layout(D, H, cap); wat.layout(D, H, cap);
+    }
+    int upload(impop_ctx *ctx) override {
+        if (n_watch) HIP_TRY(hipMemcpyAsync(d_watch, watch, 2 * (size_t)n_watch * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (want_totals) HIP_TRY(hipMemsetAsync(d_tot, 0, n_totals() * 8, ctx->stream));
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        // the epilogue kernels between two events of their own: impop_ctx_kinship_elapsed
+        int rc = timed(ctx, ctx->timers[impop_ctx::T_KIN + 1], [&] {
+            const KinshipOut O{win.d, n_watch ? wat.d : nullptr, want_totals ? d_tot : nullptr, d_diag, d_part};
+            const int r = launch_kinship_windows(ctx, c.b, c.cnt, N, num, den, d_watch, n_watch, O);
+            return r || !want_totals ? r : launch_kinship_totals(ctx, c.b, c.cnt, N, O);
+        });
+        if (rc) return rc;
+        launches += !want_totals ? 1 : kinship_total_slices(N, c.cnt) > 1 ? 3 : 2;
+        if ((rc = win.down(ctx, c.cnt))) return rc;
+        return wat.down(ctx, c.cnt);
+    }
+    void collect(const PairChunk &c) override { win.scatter(c); wat.scatter(c); }
+};
 
 }  // namespace impop
 
@@ -336,5 +387,47 @@ IMPOP_API int impop_genotypes_free(impop_ctx *ctx, impop_genotypes *g) {
     const int rc = impop_matrix_free(ctx, g->planes);
     if (rc) return rc;
     delete g;
+    return IMPOP_OK;
+}
+
+static_assert(sizeof(impop_kin_window) == 48 && sizeof(impop_kin_pair) == 72 && sizeof(impop_kin_watch) == 16 &&
+                  sizeof(impop_kinship_params) == 16, "fixed record layouts");
+
+IMPOP_API int impop_kinship_scan(impop_ctx *ctx, const impop_genotypes *g, const impop_window *windows, uint64_t n_windows,
+                                 const impop_kinship_params *params, const uint32_t *watch, uint32_t n_watch,
+                                 impop_kin_window *out_windows, impop_kin_pair *out_pairs, impop_kin_watch *out_watch) {
+    const char *fn = "impop_kinship_scan";
+    REQUIRE(ctx && g && g->planes && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_kinship_params), "impop_kinship_params.struct_size mismatch");
+    REQUIRE(params->kin_den >= 1 && params->kin_den <= (1u << 20) && params->kin_num <= params->kin_den,
+            "%s: the threshold kin_num / kin_den needs 1 <= kin_den <= 2^20 and kin_num <= kin_den", fn);
+    const impop_matrix *m = g->planes;
+    const uint32_t N = g->n_ind;
+    REQUIRE(m->device == ctx->device, "%s: genotypes live on device %d, context on %d", fn, m->device, ctx->device);
+    REQUIRE(n_watch <= IMPOP_KINSHIP_MAX_WATCH, "%s: %u watched pairs exceed the limit (%u)", fn, n_watch, (uint32_t)IMPOP_KINSHIP_MAX_WATCH);
+    REQUIRE(!n_watch || (watch && out_watch), "%s: NULL watch / out_watch with n_watch = %u", fn, n_watch);
+    for (uint32_t q = 0; q < n_watch; ++q) {
+        const uint32_t a = watch[2 * q], b = watch[2 * q + 1];
+        REQUIRE(a < N && b < N, "%s: watched pair %u: individual %u outside the handle's %u", fn, q, a < N ? b : a, N);
+        REQUIRE(a != b, "%s: watched pair %u names individual %u twice", fn, q, a);
+    }
+    bool go;
+    int rc = windows_ready(ctx, m, windows, n_windows, out_windows, fn, &go);
+    if (rc || !go) return rc;
+    KinshipEpilogue epi;
+    epi.N = N; epi.n_watch = n_watch; epi.num = params->kin_num; epi.den = params->kin_den;
+    epi.watch = watch; epi.want_totals = out_pairs != nullptr;
+    epi.win.want(out_windows, 1); epi.wat.want(out_watch, n_watch);
+    PairFront in = hamming_front(fn, widest_W(m, windows, n_windows));  // no polarity row: the counts are used as written
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (out_pairs) {  // the scratch the front end bound the totals into is still the context's
+        HIP_TRY(hipMemcpyAsync(out_pairs, epi.d_tot, epi.n_totals() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (trace_on())
+        fprintf(stderr, "[impop_kinship_scan] route=%s individuals=%u rows=%u windows=%llu chunks=%llu launches=%llu watch=%u plane_bytes=%llu\n",
+                m->compact ? "compact" : "dense", N, m->n_hap_pad, (unsigned long long)n_windows, (unsigned long long)in.chunks,
+                (unsigned long long)epi.launches, n_watch, (unsigned long long)m->rb_bytes);
     return IMPOP_OK;
 }

@@ -1,6 +1,6 @@
-// pairdist.hip — the distribution kernel of impop_pairdist_scan (pairwise_scan.hip PairdistEpilogue): per window, from the chunk's
-// Gram counts, the sums, extremes and histograms of the pairwise distances inside K panels and between their pairs, and every
-// member's nearest neighbours against each panel, then the records.  All combines and the finalisation are pairdist_math.h.
+// pairdist.hip — impop_pairdist_scan: its distribution kernel, its PairEpilogue (pair_front.h) and the entry point.  Per window,
+// from the chunk's Gram counts, the sums, extremes and histograms of the pairwise distances inside K panels and between their pairs,
+// and every member's nearest neighbours against each panel, then the records.  All combines and the finalisation are pairdist_math.h.
 //
 // One workgroup per window; the panels' haplotype indexes and the Gram diagonal sit in LDS.  A wave owns a ROW: member p against
 // every other member q, panel by panel (the members are laid out panel-major, so a panel is a range of positions).  The Gram
@@ -11,11 +11,21 @@
 // The pairs a record counts are the q > p of a row; a wave keeps them in its lanes across its rows of one panel, reduces them once
 // per pair of panels and adds the result to the record's accumulator in LDS with integer atomics.  The (min, ties) tables, M x K
 // entries per window, live in global scratch.
-#include "stats_kernels.h"
+#include "pair_front.h"
 
 namespace impop {
 
 constexpr int PD_T = 256;
+
+struct PairdistTables : PanelTables {};  // a PanelTables under the name pairdist_kernel's exported symbol carries; adds nothing
+struct PairdistOut {
+    DistNN *nn;                              // scratch: n_problems x M x K
+    impop_dist_panel *panels;                // n_problems x K
+    impop_dist_pair *pairs;                  // n_problems x K (K - 1) / 2
+    uint32_t *hist_within, *hist_between;    // bins > 0: n_problems x K x bins | x K (K - 1) / 2 x bins; zeroed unless hist_lds
+    uint32_t bins, width;
+};
+constexpr size_t PAIRDIST_LDS_BYTES = 65536;     // what a workgroup takes at most: the fixed tables, and the histograms where they fit
 
 __device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
 #pragma unroll
@@ -124,11 +134,8 @@ __global__ __launch_bounds__(PD_T) void pairdist_kernel(SimBatch batch, const im
         O.panels[w * K + tid] = r;
     }
     for (uint32_t pr = wave; pr < NP; pr += n_waves) {
-        uint32_t ka = 0, rest = pr;  // pair pr = panels (ka, kb)
-        while (rest >= K - 1 - ka) { rest -= K - 1 - ka; ++ka; }
-        const uint32_t kb = ka + 1 + rest;
-        const uint32_t *list = T.merged + T.moff[pr];  // the positions of ka u kb in ascending haplotype index
-        const uint32_t len = T.moff[pr + 1] - T.moff[pr];
+        const PanelPair P = panel_pair(K, T.merged, T.moff, pr);
+        const uint32_t ka = P.ka, kb = P.kb, len = P.len, *list = P.list;  // the positions of ka u kb in ascending haplotype index
         double sum = 0.0;
         uint32_t same_a = 0, same_b = 0, other_a = 0, other_b = 0;
         for (uint32_t base = 0; base < len; base += 64) {
@@ -169,10 +176,11 @@ __global__ __launch_bounds__(PD_T) void pairdist_kernel(SimBatch batch, const im
         }
 }
 
-size_t pairdist_lds_fixed(uint32_t K, uint32_t M) { return (size_t)(K + K * (K - 1) / 2) * sizeof(DistAcc) + (size_t)M * 8; }
+// bytes of the accumulators, the diagonal and the haplotype indexes
+static size_t pairdist_lds_fixed(uint32_t K, uint32_t M) { return (size_t)(K + K * (K - 1) / 2) * sizeof(DistAcc) + (size_t)M * 8; }
 
-int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PairdistTables &T,
-                    const PairdistOut &O, bool hist_lds) {
+static int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PairdistTables &T,
+                           const PairdistOut &O, bool hist_lds) {
     if (!n_problems) return IMPOP_OK;
     const uint32_t R = T.K + T.K * (T.K - 1) / 2;
     const size_t lds = pairdist_lds_fixed(T.K, T.M) + (hist_lds ? (size_t)R * O.bins * 4 : 0);
@@ -185,4 +193,109 @@ int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, cons
     return IMPOP_OK;
 }
 
+// impop_pairdist_scan's epilogue: one launch of the distribution kernel per chunk — records, histograms and the per-member
+// nearest-neighbour tables it keeps in scratch
+struct PairdistEpilogue final : PairEpilogue {
+    uint32_t K, NP, M, B, width;            // B = 0: no histograms
+    bool hist_lds = false;
+    PairdistTables T{};
+    PanelUpload tables;
+    Result<impop_dist_panel> pan;
+    Result<impop_dist_pair> pair;
+    Result<uint32_t> hw, hb;                // hist_within, hist_between
+    uint64_t launches = 0;
+    DistNN *d_nn = nullptr;
+    // the device bytes layout() takes per window of a chunk, histograms included (they bound a chunk: impop_pairdist_scan)
+    size_t per_window_bytes() const {
+        return (size_t)M * K * sizeof(DistNN) + K * sizeof(impop_dist_panel) + NP * sizeof(impop_dist_pair) + (size_t)(K + NP) * B * 4;
+    }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        tables.layout(D);
+        D.sub(d_nn, cap * M * K); pan.layout(D, H, cap); pair.layout(D, H, cap, NP);
+        hw.layout(D, H, cap, (size_t)K * B); hb.layout(D, H, cap, (size_t)NP * B);  // one region: zeroed by one memset where the kernel tallies into it
+    }
+    int upload(impop_ctx *ctx) override { return tables.upload(ctx, T); }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        // the distribution kernel between two events of its own: impop_ctx_pairdist_elapsed
+        int rc = timed(ctx, ctx->timers[impop_ctx::T_PAIRDIST], [&] {
+            if (B && !hist_lds) HIP_TRY(hipMemsetAsync(hw.d, 0, (size_t)((char *)(hb.d + c.cnt * NP * B) - (char *)hw.d), ctx->stream));
+            const PairdistOut O{d_nn, pan.d, pair.d, hw.d, hb.d, B, width};
+            return launch_pairdist(ctx, c.b, c.cnt, c.d_s, T, O, hist_lds);
+        });
+        if (rc) return rc;
+        ++launches;
+        if ((rc = pan.down(ctx, c.cnt)) || (rc = pair.down(ctx, c.cnt)) || (rc = hw.down(ctx, c.cnt))) return rc;
+        return hb.down(ctx, c.cnt);
+    }
+    void collect(const PairChunk &c) override { pan.scatter(c); pair.scatter(c); hw.scatter(c); hb.scatter(c); }
+};
+
 }  // namespace impop
+
+using namespace impop;
+
+static_assert(sizeof(impop_dist_panel) == 64 && sizeof(impop_dist_pair) == 96 && sizeof(impop_pairdist_params) == 16, "fixed record layouts");
+static_assert(IMPOP_PAIRDIST_MAX_N == PAIRDIST_MAX_N, "positions are packed into 12 bits of a key");
+
+IMPOP_API int impop_pairdist_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                                  const uint64_t *masks, uint32_t n_pop, const impop_pairdist_params *params,
+                                  impop_dist_panel *out_panels, impop_dist_pair *out_pairs, uint32_t *hist_within, uint32_t *hist_between) {
+    const char *fn = "impop_pairdist_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_pairdist_params), "impop_pairdist_params.struct_size mismatch");
+    REQUIRE(params->hist_bins <= IMPOP_PAIRDIST_MAX_BINS, "%s: hist_bins must be 0..%u", fn, (uint32_t)IMPOP_PAIRDIST_MAX_BINS);
+    REQUIRE(params->hist_width >= 1, "%s: hist_width must be at least 1", fn);
+    REQUIRE(n_pop >= 1 && n_pop <= 8, "%s: n_pop must be 1..8", fn);
+    REQUIRE(masks, "%s: masks is NULL", fn);
+    const uint32_t K = n_pop, NP = K * (K - 1) / 2;
+    PanelSet panels;
+    int rc = panel_refused(panel_set(masks, K, m->g.n_hap, panels), fn);
+    if (rc) return rc;
+    if (panels.M > IMPOP_PAIRDIST_MAX_N) {  // refused before anything is uploaded or launched
+        set_error("%s: the panels hold %zu members, more than the limit of %u", fn, (size_t)panels.M, (uint32_t)IMPOP_PAIRDIST_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    bool go;
+    if ((rc = windows_ready(ctx, m, windows, n_windows, out_panels, fn, &go)) || !go) return rc;
+    const MergedPairs pairs = merged_pairs(panels, false);
+    uint64_t p_max = 0;  // the pairs of the largest record
+    for (uint32_t a = 0; a < K; ++a) {
+        const uint64_t ma = panels.size(a);
+        p_max = std::max(p_max, ma * (ma - 1) / 2);
+        for (uint32_t b = a + 1; b < K; ++b) p_max = std::max(p_max, ma * panels.size(b));
+    }
+    const uint64_t max_W = widest_W(m, windows, n_windows);
+    if (!pd_sum_h2_admitted(max_W, p_max)) {  // before any launch
+        set_error("%s: sum_h2 may overflow 64 bits: the widest window has W = %llu and the largest record %llu pairs (W^2 x pairs must stay "
+                  "below 2^64)", fn, (unsigned long long)max_W, (unsigned long long)p_max);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    PairdistEpilogue epi;
+    epi.K = K; epi.NP = NP; epi.M = panels.M;
+    epi.B = (hist_within || (hist_between && NP)) ? params->hist_bins : 0u;
+    epi.width = params->hist_width;
+    epi.tables.set = &panels; epi.tables.pairs = &pairs;
+    epi.pan.want(out_panels, K); epi.pair.want(out_pairs, NP);
+    epi.hw.want(hist_within, (size_t)K * epi.B); epi.hb.want(hist_between, (size_t)NP * epi.B);
+    // histograms in LDS where every counter fits next to the kernel's tables; IMPOP_PAIRDIST_LDS_BINS=n lowers what the LDS form
+    // takes, so that tests reach the global form at small sizes
+    if (epi.B) {
+        const size_t fixed = pairdist_lds_fixed(K, epi.M);
+        size_t cap = fixed < PAIRDIST_LDS_BYTES ? (PAIRDIST_LDS_BYTES - fixed) / 4 : 0;
+        const char *e = getenv("IMPOP_PAIRDIST_LDS_BINS");
+        if (e && *e) {
+            const long v = strtol(e, nullptr, 10);
+            cap = std::min<size_t>(cap, v < 0 ? 0 : (size_t)v);
+        }
+        epi.hist_lds = (size_t)(K + NP) * epi.B <= cap;
+    }
+    // the per-member tables and the histograms of a chunk: at most 512 MiB of them
+    PairFront in = hamming_front(fn, max_W, chunk_windows(512ull << 20, epi.per_window_bytes()));
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (trace_on())
+        fprintf(stderr, "[impop_pairdist_scan] pops=%u pairs=%u members=%u windows=%llu chunks=%llu launches=%llu hist_bins=%u hist=%s\n", K, NP,
+                epi.M, (unsigned long long)n_windows, (unsigned long long)in.chunks, (unsigned long long)epi.launches, epi.B,
+                !epi.B ? "off" : epi.hist_lds ? "lds" : "global");
+    return IMPOP_OK;
+}

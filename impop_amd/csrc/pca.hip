@@ -1,6 +1,6 @@
-// pca.hip — the kernels of impop_pca_scan (pairwise_scan.hip PcaEpilogue): per window the k largest eigenpairs of the double-centred
-// distance matrix B = -1/2 J H J of the members, by block subspace iteration with Rayleigh-Ritz (all arithmetic: pca_math.h), and
-// once per call the window-to-window distances from the vectors of all windows.
+// pca.hip — impop_pca_scan: its kernels, its PairEpilogue (pair_front.h) and the entry point.  Per window the k largest eigenpairs
+// of the double-centred distance matrix B = -1/2 J H J of the members, by block subspace iteration with Rayleigh-Ritz (all
+// arithmetic: pca_math.h), and once per call the window-to-window distances from the vectors of all windows.
 //
 // Eigen kernel: one workgroup per window, of 256 threads up to 256 members, 512 up to 512, 1024 beyond, so that a thread owns
 // one row of the block (the template keeps R rows per thread; only R = 1 is built: two rows spilt far more registers than the
@@ -11,13 +11,29 @@
 // -1/2 J (H V) = B V because V is kept orthogonal to the ones vector.  Everything else an iteration does is local to a row except
 // the sums over rows, which all go through one reduction: a transposing fold of 16 values per lane inside a wave, the waves
 // added in order (fixed order, no atomics).  The 16 x 16 Jacobi runs on 256 threads, one matrix element each.
-#include "chunk_run.h"
+#include "pair_front.h"
 #include "pca_math.h"
-#include "stats_kernels.h"
 
 namespace impop {
 
 constexpr int PCA_T = 256;  // threads of the distance kernel
+
+// The eigen kernel: one workgroup per Gram problem; the members are positions 0 .. m - 1 in ascending haplotype index.  The distance
+// kernel: once per call, over the vectors of all windows in the caller's window order.
+struct PcaIn {
+    const uint32_t *hap_of;  // m: haplotype index of a position
+    void *hs;                // scratch: n_problems x m x m distances, symmetric, uint16 where h16 else uint32
+    const uint64_t *ord;     // problem p is window ord[p] of the call (the slot of the all-window tables), or nullptr
+    uint32_t m, k, max_iter, h16;
+    double tol;
+};
+struct PcaOut {
+    impop_pca_window *rec;   // n_problems
+    double *vec;             // n_problems x k x m, or nullptr
+    double *all_vec;         // per WINDOW of the call: k x m | 8 eigenvalues | usable by the distance kernel; or nullptr
+    double *all_lam;
+    uint32_t *all_ok;
+};
 
 // ---- the one reduction: every thread brings 16 partial sums; afterwards the workgroup's 16 totals are pca_tot(red, buf, q)
 template <int HALF, int BIT>
@@ -71,7 +87,7 @@ __device__ __forceinline__ PcaLds pca_carve(double *base, uint32_t m) {
     L.ctl = L.order + PCA_B;
     return L;
 }
-size_t pca_eigen_lds_bytes(uint32_t m) { return pca_lds_doubles(m) * 8 + (size_t)m * 8 + (PCA_B + 8) * 4; }
+static size_t pca_eigen_lds_bytes(uint32_t m) { return pca_lds_doubles(m) * 8 + (size_t)m * 8 + (PCA_B + 8) * 4; }
 
 // orthonormalise the block held in the threads' rows (inactive rows are zero) and leave it in LDS
 template <int NT, int R>
@@ -412,7 +428,7 @@ static int launch_eigen_as(impop_ctx *ctx, const SimBatch &b, uint64_t n, const 
     return IMPOP_OK;
 }
 
-int launch_pca_eigen(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PcaIn &in,
+static int launch_pca_eigen(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PcaIn &in,
                      const PcaOut &out) {
     if (!n_problems) return IMPOP_OK;
     REQUIRE(in.m >= 2 && in.m <= PCA_MAX_N && in.k >= 1 && in.k <= PCA_MAX_K && in.max_iter >= 1, "launch_pca_eigen: bad shape");
@@ -439,7 +455,7 @@ static int launch_dist_as(impop_ctx *ctx, const double *d_vec, const double *d_l
     return IMPOP_OK;
 }
 
-int launch_pca_dist(impop_ctx *ctx, const double *d_vec, const double *d_lam, const uint32_t *d_ok, uint32_t m, uint32_t k,
+static int launch_pca_dist(impop_ctx *ctx, const double *d_vec, const double *d_lam, const uint32_t *d_ok, uint32_t m, uint32_t k,
                     uint64_t n_windows, double *d_out) {
     if (!n_windows) return IMPOP_OK;
     REQUIRE(m >= 2 && m <= PCA_MAX_N && k >= 1 && k <= PCA_MAX_K, "launch_pca_dist: bad shape");
@@ -459,4 +475,109 @@ int launch_pca_dist(impop_ctx *ctx, const double *d_vec, const double *d_lam, co
     return IMPOP_OK;
 }
 
+// impop_pca_scan's epilogue: one launch of the eigen kernel per chunk — records and vectors; the symmetric distance matrices the
+// kernel gathers live in scratch, one per window of a chunk.  With the window distances wanted, every window's vectors, eigenvalues
+// and usability also go to tables that live across the chunks, in the caller's window order.
+struct PcaEpilogue final : PairEpilogue {
+    uint32_t M, k, max_iter;
+    double tol;
+    bool h16, want_dist;
+    uint64_t n_windows;
+    const std::vector<uint32_t> *hap_of;
+    Result<impop_pca_window> rec;
+    Result<double> vec;
+    uint64_t launches = 0;
+    uint32_t *d_hap = nullptr, *d_ok = nullptr;
+    char *d_hs = nullptr;
+    uint64_t *d_ord = nullptr;
+    double *d_allvec = nullptr, *d_lam = nullptr, *d_dist = nullptr;
+    size_t hs_bytes() const { return (size_t)M * M * (h16 ? 2 : 4); }
+    // the device bytes layout() takes per window of a chunk (they bound a chunk: impop_pca_scan)
+    size_t per_window_bytes() const { return hs_bytes() + sizeof(impop_pca_window) + (size_t)k * M * 8 + 8; }
+    void layout(Layout &D, Layout &H, uint64_t cap) override {
+        D.sub(d_hap, M); D.sub(d_ord, cap); rec.layout(D, H, cap); vec.layout(D, H, cap);
+        D.sub(d_allvec, want_dist ? n_windows * k * M : 0); D.sub(d_lam, want_dist ? n_windows * 8 : 0);
+        D.sub(d_ok, want_dist ? n_windows : 0); D.sub(d_dist, want_dist ? n_windows * n_windows : 0);
+        D.sub(d_hs, cap * hs_bytes());
+    }
+    int upload(impop_ctx *ctx) override {
+        HIP_TRY(hipMemcpyAsync(d_hap, hap_of->data(), (size_t)M * 4, hipMemcpyHostToDevice, ctx->stream));
+        return IMPOP_OK;
+    }
+    int launch(impop_ctx *ctx, const PairChunk &c) override {
+        if (want_dist) HIP_TRY(hipMemcpyAsync(d_ord, c.ord, c.cnt * 8, hipMemcpyHostToDevice, ctx->stream));
+        const PcaIn in{d_hap, d_hs, want_dist ? d_ord : nullptr, M, k, max_iter, h16 ? 1u : 0u, tol};
+        const PcaOut O{rec.d, vec.n ? vec.d : nullptr, want_dist ? d_allvec : nullptr, want_dist ? d_lam : nullptr,
+                       want_dist ? d_ok : nullptr};  // (a table of zero bytes shares its offset with what follows it)
+        // the eigen kernel between two events of its own: impop_ctx_pca_elapsed
+        int rc = timed(ctx, ctx->timers[impop_ctx::T_PCA], [&] { return launch_pca_eigen(ctx, c.b, c.cnt, c.d_s, in, O); });
+        if (rc) return rc;
+        ++launches;
+        if ((rc = rec.down(ctx, c.cnt))) return rc;
+        return vec.down(ctx, c.cnt);
+    }
+    void collect(const PairChunk &c) override { rec.scatter(c); vec.scatter(c); }
+};
+
 }  // namespace impop
+
+using namespace impop;
+
+static_assert(sizeof(impop_pca_params) == 24 && sizeof(impop_pca_window) == 160, "fixed record layouts");
+static_assert(IMPOP_PCA_MAX_N == PCA_MAX_N && IMPOP_PCA_MAX_K == PCA_MAX_K && PCA_MAX_K + 8 <= PCA_B, "the block holds k + 8 columns");
+
+IMPOP_API int impop_pca_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                             const uint64_t *mask_p, const impop_pca_params *params, impop_pca_window *out_windows, double *out_vectors,
+                             double *out_dist2) {
+    const char *fn = "impop_pca_scan";
+    REQUIRE(ctx && m && params, "%s: NULL argument", fn);
+    REQUIRE(params->struct_size == sizeof(impop_pca_params), "impop_pca_params.struct_size mismatch");
+    REQUIRE(params->k >= 1 && params->k <= IMPOP_PCA_MAX_K, "%s: k must be 1..%u", fn, (uint32_t)IMPOP_PCA_MAX_K);
+    REQUIRE(params->tol >= 1e-13 && params->tol <= 1e-2, "%s: tol must be in [1e-13, 1e-2]", fn);
+    REQUIRE(params->max_iter >= 1 && params->max_iter <= 100000, "%s: max_iter must be 1..100000", fn);
+    const std::vector<uint32_t> hap_of = mask_members(mask_p, m->g.n_hap);
+    REQUIRE(hap_of.size() >= 2, "%s: the mask holds %zu members, fewer than 2", fn, hap_of.size());
+    if (hap_of.size() > IMPOP_PCA_MAX_N) {  // refused before anything is uploaded or launched
+        set_error("%s: the mask holds %zu members, more than the limit of %u", fn, hap_of.size(), (uint32_t)IMPOP_PCA_MAX_N);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    if (out_dist2 && n_windows > 16384) {
+        set_error("%s: window distances of %llu windows, more than the limit of 16384", fn, (unsigned long long)n_windows);
+        return IMPOP_E_UNSUPPORTED;
+    }
+    REQUIRE(!out_dist2 || out_vectors, "%s: out_dist2 needs out_vectors", fn);
+    bool go;
+    int rc = windows_ready(ctx, m, windows, n_windows, out_windows, fn, &go);
+    if (rc || !go) return rc;
+    const uint64_t max_W = widest_W(m, windows, n_windows);
+    PcaEpilogue epi;
+    epi.M = (uint32_t)hap_of.size(); epi.k = params->k; epi.max_iter = params->max_iter; epi.tol = params->tol;
+    epi.h16 = max_W < 65536;  // a distance is at most its window's W
+    epi.want_dist = out_dist2 != nullptr; epi.n_windows = n_windows;
+    epi.hap_of = &hap_of;
+    epi.rec.want(out_windows, 1); epi.vec.want(out_vectors, (size_t)epi.k * epi.M);
+    // the gathered distance matrices and the vectors of a chunk: at most 1 GiB of them
+    PairFront in = hamming_front(fn, max_W, chunk_windows(1ull << 30, epi.per_window_bytes()));
+    rc = pairwise_front(ctx, m, windows, n_windows, in, epi);
+    if (rc) return rc;
+    if (out_dist2) {  // the scratch the front end bound the all-window tables into is still the context's
+        rc = timed(ctx, ctx->timers[impop_ctx::T_PCA + 1],
+                   [&] { return launch_pca_dist(ctx, epi.d_allvec, epi.d_lam, epi.d_ok, epi.M, epi.k, n_windows, epi.d_dist); });
+        if (rc) return rc;
+        ++epi.launches;
+        HIP_TRY(hipMemcpyAsync(out_dist2, epi.d_dist, n_windows * n_windows * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (trace_on()) {
+        uint32_t it_max = 0;
+        uint64_t bad = 0;
+        for (uint64_t i = 0; i < n_windows; ++i) {
+            it_max = std::max(it_max, out_windows[i].iterations);
+            bad += out_windows[i].flags & 1u;
+        }
+        fprintf(stderr, "[impop_pca_scan] route=%s members=%u k=%u windows=%llu chunks=%llu launches=%llu iterations_max=%u unconverged=%llu "
+                "dist=%s\n", m->compact ? "compact" : "dense", epi.M, epi.k, (unsigned long long)n_windows, (unsigned long long)in.chunks,
+                (unsigned long long)epi.launches, it_max, (unsigned long long)bad, out_dist2 ? "on" : "off");
+    }
+    return IMPOP_OK;
+}

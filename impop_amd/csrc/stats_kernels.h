@@ -246,98 +246,4 @@ int launch_af_batch(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, cons
                     uint32_t *d_adj, size_t adj_bytes_per_problem, impop_cluster_stats *d_rec, uint32_t *d_cluster_of, uint32_t *d_sizes,
                     bool want_members);
 
-// impop_pairdist_scan's distribution kernel (pairdist.hip): one workgroup per Gram problem.  The K panels' members are POSITIONS
-// 0 .. M - 1, panel k at off[k] .. off[k + 1), each panel ascending (pairdist_math.h).
-struct PairdistTables {
-    const uint32_t *hap_of;  // M: haplotype index of a position
-    const uint32_t *merged;  // per pair of panels p: the positions of both panels in ascending haplotype index, at moff[p]
-    const uint32_t *moff;    // K (K - 1) / 2 + 1
-    uint32_t off[9];
-    uint32_t K, M;
-};
-struct PairdistOut {
-    DistNN *nn;                              // scratch: n_problems x M x K
-    impop_dist_panel *panels;                // n_problems x K
-    impop_dist_pair *pairs;                  // n_problems x K (K - 1) / 2
-    uint32_t *hist_within, *hist_between;    // bins > 0: n_problems x K x bins | x K (K - 1) / 2 x bins; zeroed unless hist_lds
-    uint32_t bins, width;
-};
-constexpr size_t PAIRDIST_LDS_BYTES = 65536;     // what a workgroup takes at most: the fixed tables, and the histograms where they fit
-size_t pairdist_lds_fixed(uint32_t K, uint32_t M);  // bytes of the accumulators, the diagonal and the haplotype indexes
-int launch_pairdist(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PairdistTables &T,
-                    const PairdistOut &O, bool hist_lds);
-
-// impop_pca_scan's kernels (pca.hip).  The eigen kernel: one workgroup per Gram problem; the members are positions 0 .. m - 1 in
-// ascending haplotype index.  The distance kernel: once per call, over the vectors of all windows in the caller's window order.
-struct PcaIn {
-    const uint32_t *hap_of;  // m: haplotype index of a position
-    void *hs;                // scratch: n_problems x m x m distances, symmetric, uint16 where h16 else uint32
-    const uint64_t *ord;     // problem p is window ord[p] of the call (the slot of the all-window tables), or nullptr
-    uint32_t m, k, max_iter, h16;
-    double tol;
-};
-struct PcaOut {
-    impop_pca_window *rec;   // n_problems
-    double *vec;             // n_problems x k x m, or nullptr
-    double *all_vec;         // per WINDOW of the call: k x m | 8 eigenvalues | usable by the distance kernel; or nullptr
-    double *all_lam;
-    uint32_t *all_ok;
-};
-size_t pca_eigen_lds_bytes(uint32_t m);
-int launch_pca_eigen(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const impop_window_stats *d_stats, const PcaIn &in,
-                     const PcaOut &out);
-int launch_pca_dist(impop_ctx *ctx, const double *d_vec, const double *d_lam, const uint32_t *d_ok, uint32_t m, uint32_t k,
-                    uint64_t n_windows, double *d_out);
-
-// impop_kinship_scan's epilogue (kinship.hip) on a chunk's Gram problems of the 2N plane rows [H_0 .. H_{N-1}, A_0 .. A_{N-1}].
-struct KinshipOut {
-    impop_kin_window *windows;  // n_problems
-    impop_kin_watch *watch;     // n_problems x n_watch, or nullptr
-    uint64_t *totals;           // N (N - 1) / 2 x 9, ADDED to (one owner per entry), or nullptr
-    uint32_t *diag;             // scratch: n_problems x 2N, het then alt per problem (the windows kernel writes, the totals kernel reads)
-    uint64_t *part;             // scratch: kinship_total_slices x N (N - 1) / 2 x 9 when there is more than one slice, else unused
-};
-constexpr uint64_t KIN_TOTALS_THREADS = 1ull << 19;  // (pair, slice) threads the totals kernel aims at
-constexpr uint32_t KIN_TOTALS_MAX_SLICES = 64;
-uint32_t kinship_total_slices(uint32_t N, uint64_t n_problems);  // slices of the totals kernel for a chunk of n_problems windows
-// window records and watch rows: one workgroup per problem
-int launch_kinship_windows(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, int64_t num, int64_t den,
-                           const uint32_t *d_watch, uint32_t n_watch, const KinshipOut &O);
-// the per-pair tables of the chunk's problems added into O.totals: one thread per pair, the problems in turn
-int launch_kinship_totals(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, uint32_t N, const KinshipOut &O);
-
-// impop_permtest_scan's kernels (permtest.hip).  A SLOT is a (problem, pair of panels): slot = problem x NP + pair.  The members
-// of a pair are positions 0 .. m - 1 in ascending haplotype index (the merged lists of impop_pairdist_scan); m_pad = 64 ceil(m / 64).
-struct PermObs;
-constexpr uint32_t PERM_TASK_COLS = 64;  // columns of a labelling task: z0 and 63 labellings
-struct PermtestTables {
-    const uint32_t *hap_of;   // M: haplotype index of a panel-major position
-    const uint32_t *merged;   // per pair p: the positions of both panels in ascending haplotype index, at moff[p]
-    const uint32_t *moff;     // NP + 1
-    const uint64_t *z0;       // per pair p: the observed labelling, mw_max words at p x mw_max
-    const uint64_t *labels;   // per pair p: n_perm x ceil(m_p / 64) words at loff[p]
-    const uint64_t *loff;     // NP
-    uint32_t off[9];
-    uint32_t K, M, NP, n_perm, planes, m_pad_max, mw_max;  // planes: bytes of a distance, 1..4; the largest m_pad / its words
-};
-struct PermtestScratch {
-    int8_t *planes;    // slot x planes x m_pad_max^2: plane q of H as (byte - 128), row stride the PAIR's m_pad
-    uint64_t *ties;    // slot x m_pad_max x mw_max: row i's nearest-neighbour tie mask at i x ceil(m / 64)
-    uint64_t *rows;    // slot x m_pad_max: r_i
-    uint32_t *term;    // slot x m_pad_max: SCALE / tied_i
-    uint32_t *st;      // slot x m_pad_max: same_i(z0) << 16 | tied_i (the host's snn)
-    PermObs *obs;      // slot: the observed wa, wb, nn and tot
-    uint32_t *ge;      // slot x 4: fst, phi, dxy, snn; zeroed by the caller, added to with integer atomics
-    uint64_t *null;    // slot x n_perm x {wa, wb, nn}, or nullptr
-};
-uint32_t permtest_blocks(uint32_t n_perm);  // labelling tasks per slot
-int launch_permtest_prep(impop_ctx *ctx, const SimBatch &b, uint64_t n_problems, const PermtestTables &T, const PermtestScratch &X);
-int launch_permtest_labels(impop_ctx *ctx, uint64_t n_problems, const PermtestTables &T, const PermtestScratch &X);
-
 }  // namespace impop
-
-// the genotype planes of impop_genotypes_create: a matrix the Gram front end accepts (2N rows, RB32 operand alone), as its own type
-struct impop_genotypes {
-    impop_matrix *planes = nullptr;
-    uint32_t n_ind = 0;
-};

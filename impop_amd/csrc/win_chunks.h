@@ -10,6 +10,7 @@
 namespace impop {
 
 // The haplotypes a mask selects (bitset of ceil(n_hap / 64) words; null: everyone; bits at or above n_hap are ignored).
+// (K disjoint masks as panels — classes, positions, merged pairs — are panel_set.h, built on this.)
 struct MemberSet {
     std::vector<uint32_t> idx;   // the members, ascending
     std::vector<int32_t> ppos;   // wps * 32 entries: a member's position in idx, -1 for everyone else (padding rows included)
