@@ -221,6 +221,23 @@ class IbsWindow(C.Structure):
                 ("reserved", C.c_uint32), ("share", C.c_double)]
 
 
+class IbdParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_sites", C.c_uint32), ("site_begin", C.c_uint64), ("site_end", C.c_uint64),
+                ("min_seed", C.c_uint64), ("min_extend", C.c_uint64), ("min_output", C.c_uint64), ("max_gap", C.c_uint64),
+                ("map_pos", C.POINTER(C.c_uint64)), ("map_g", C.POINTER(C.c_uint64)), ("n_map", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class IbdPair(C.Structure):
+    _fields_ = [("h1", C.c_uint32), ("h2", C.c_uint32), ("n_segments", C.c_uint32), ("n_candidates", C.c_uint32),
+                ("total_len", C.c_uint64), ("total_extent", C.c_uint64), ("longest_len", C.c_uint64), ("ibs_sites", C.c_uint64)]
+
+
+class IbdSegment(C.Structure):
+    _fields_ = [("h1", C.c_uint32), ("h2", C.c_uint32), ("begin", C.c_uint64), ("end", C.c_uint64), ("len", C.c_uint64),
+                ("ibs_sites", C.c_uint32), ("n_tracts", C.c_uint32), ("pair", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class IhsParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_mac", C.c_uint32), ("cutoff_milli", C.c_uint32), ("reserved", C.c_uint32),
                 ("max_extend_bp", C.c_uint64), ("max_extend_sites", C.c_uint64)]
@@ -300,6 +317,8 @@ assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(
 DIPLOID_MAX_N = 2048
 assert C.sizeof(IbsParams) == 32 and C.sizeof(IbsPair) == 32 and C.sizeof(IbsSegment) == 32 and C.sizeof(IbsWindow) == 32
 IBS_MAX_N, IBS_MAX_PAIRS, IBS_OPEN_LEFT, IBS_OPEN_RIGHT = 4096, 8388608, 1, 2
+assert C.sizeof(IbdParams) == 88 and C.sizeof(IbdPair) == 48 and C.sizeof(IbdSegment) == 48
+IBD_MAX_MAP = 1 << 22  # IMPOP_IBD_MAX_MAP
 assert C.sizeof(IhsParams) == 32 and C.sizeof(IhsCore) == 96
 IHS_SCAN_MAX_N = 4096
 assert C.sizeof(DstatStats) == 80 and C.sizeof(DstatParams) == 16
@@ -411,6 +430,9 @@ SIGNATURES = {
     "impop_ibs_scan": (C.c_int, [_vp, _vp, _u64p, _u32p, C.c_uint64, C.POINTER(Window), C.c_uint64, C.POINTER(IbsParams),
                                  C.POINTER(IbsPair), C.POINTER(IbsSegment), C.c_uint64, _u64p, C.POINTER(IbsWindow)]),
     "impop_ctx_ibs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_ibd_scan": (C.c_int, [_vp, _vp, _u64p, _u32p, C.c_uint64, C.POINTER(Window), C.c_uint64, C.POINTER(IbdParams),
+                                 C.POINTER(IbdPair), C.POINTER(IbdSegment), C.c_uint64, _u64p, C.POINTER(IbsWindow)]),
+    "impop_ctx_ibd_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_ihs_scan": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _u64p, _u64p, C.POINTER(IhsParams),
                                  C.POINTER(IhsCore), C.c_uint64, _u64p]),
     "impop_ctx_ihs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),

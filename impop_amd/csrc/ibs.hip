@@ -29,6 +29,7 @@
 #include "device_utils.h"
 #include "dip_runs.h"
 #include "ibs_plan.h"
+#include "ibs_sweeps.h"
 #include "internal.h"
 #include "scan_route.h"
 #include "win_chunks.h"
@@ -252,24 +253,22 @@ static void ibs_launch_walk(impop_ctx *ctx, const IbsArgs &A, uint32_t n_tiles, 
 
 using namespace impop;
 
-IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64_t *mask_p, const uint32_t *pairs, uint64_t n_pairs,
-                             const impop_window *windows, uint64_t n_windows, const impop_ibs_params *params, impop_ibs_pair *pair_out,
-                             impop_ibs_segment *seg_out, uint64_t seg_capacity, uint64_t *n_segments, impop_ibs_window *win_out) {
-    static_assert(sizeof(impop_ibs_params) == 32 && sizeof(impop_ibs_pair) == 32 && sizeof(impop_ibs_segment) == 32 &&
-                      sizeof(impop_ibs_window) == 32,
-                  "ABI layout");
-    const char *fn = "impop_ibs_scan";
-    REQUIRE(ctx && m && params && n_segments, "%s: NULL argument", fn);
-    REQUIRE(params->struct_size == sizeof(impop_ibs_params), "impop_ibs_params.struct_size mismatch");
+// The two sweeps of impop_ibs_scan for the range [b, e) (e == 0: the matrix's end).  client null: the call itself.  Else
+// (impop_ibd_scan, ibs_sweeps.h) the tracts stay on the device: every pair range is filled into the staging and handed to the client.
+int impop::ibs_scan_run(const char *fn, impop_ctx *ctx, const impop_matrix *m, const uint64_t *mask_p, const uint32_t *pairs, uint64_t n_pairs,
+                        const impop_window *windows, uint64_t n_windows, uint64_t b, uint64_t e, uint32_t min_sites,
+                        uint64_t max_chunk_bytes, impop_ibs_pair *pair_out, impop_ibs_segment *seg_out, uint64_t seg_capacity,
+                        uint64_t *n_segments, impop_ibs_window *win_out, IbsClient *client) {
     REQUIRE(m->device == ctx->device, "%s: matrix lives on device %d, context on %d", fn, m->device, ctx->device);
-    REQUIRE(params->min_sites >= 1, "%s: min_sites must be at least 1", fn);
-    const uint64_t span = matrix_span(m), b = params->site_begin, e = params->site_end ? params->site_end : span;
+    REQUIRE(min_sites >= 1, "%s: min_sites must be at least 1", fn);
+    const uint64_t span = matrix_span(m);
+    if (!e) e = span;
     REQUIRE(b < e && e <= span, "%s: bad range [%llu,%llu) for %llu sites", fn, (unsigned long long)b, (unsigned long long)e,
             (unsigned long long)span);
     REQUIRE(e - b < (1ull << 32), "%s: a range of %llu sites does not fit the records' 32-bit lengths", fn, (unsigned long long)(e - b));
     REQUIRE(!(pairs && mask_p), "%s: give either a pair list or a member mask", fn);
     REQUIRE((windows == nullptr) == (win_out == nullptr), "%s: windows and win_out must both be given or both be NULL", fn);
-    const uint32_t nh = m->g.n_hap, wps = m->g.wps, n_pad = wps * 32, min_sites = params->min_sites;
+    const uint32_t nh = m->g.n_hap, wps = m->g.wps, n_pad = wps * 32;
     const bool all = pairs == nullptr;
 
     // the rows: the members, or the haplotypes of the list; the list's pairs as rows
@@ -313,7 +312,7 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
     // the range's columns of d_sb and their blocks
     const uint64_t cb = m->compact ? pos_lower_bound(m, b) : b, ce = m->compact ? pos_lower_bound(m, e) : e;
     const uint64_t blk0 = cb >> 6, n_blk = ce > cb ? ((ce + 63) >> 6) - blk0 : 0;
-    const uint64_t budget = chunk_budget(params->max_chunk_bytes);
+    const uint64_t budget = chunk_budget(max_chunk_bytes);
     const std::vector<IbsTile> tiles_all = all ? ibs_tiles_all(n, 0, n_pairs) : ibs_tiles_list(0, n_pairs);
     const IbsCut cut = ibs_cut(n_blk, stride, n_pairs, tiles_all.size(), (uint32_t)ctx->n_cu, budget / 2,
                                env_tile_blocks("IMPOP_IBS_CHUNK_BLOCKS"), env_tile_blocks("IMPOP_IBS_SEG_BLOCKS"));
@@ -337,7 +336,8 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
                  o_edge = L.take<uint64_t>(wp.edge.size()), o_sbeg = L.take<uint64_t>(wp.sbeg.size()),
                  o_send = L.take<uint64_t>(wp.send.size()), o_acc = L.take<unsigned long long>(want_win ? wp.acc_words() : 0),
                  o_wm = L.take<uint64_t>(cut.chunk_blocks * stride), o_sum = L.take<DipSummary>((uint64_t)cut.n_sub * n_pairs),
-                 o_carry = L.take<DipSummary>(n_pairs), o_rec = L.take<impop_ibs_pair>(n_pairs), fixed = L.total();
+                 o_carry = L.take<DipSummary>(n_pairs), o_rec = L.take<impop_ibs_pair>(n_pairs),
+                 o_extra = L.take_bytes(client ? client->extra_bytes : 0), fixed = L.total();
     HIP_TRY(hipSetDevice(ctx->device));
     void *d = nullptr;
     int rc = ctx_scratch(ctx, fixed, &d);
@@ -374,7 +374,8 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
     A.n = n;
     A.min_sites = min_sites;
 
-    EventPairs *timer = ctx->timers + impop_ctx::T_IBS;
+    if (client && client->prepare && (rc = client->prepare(L.at<char>(d, o_extra), n_pairs))) return rc;
+    EventPairs *timer = ctx->timers + (client ? client->timer : (int)impop_ctx::T_IBS);
     uint64_t launches = 0, bytes_streamed = 0, chunks_run = 0, subs_run = 0;
     std::vector<IbsTile> tiles;  // of the sweep in flight: alive until its synchronisation
     // one sweep over the range's chunks for the pairs [p0, p1); A.seg / A.off / A.win say what a fill leaves behind
@@ -437,7 +438,9 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
     *n_segments = total;
 
     // sweep 2: the segment list, where it fits, and the window tables
-    const bool want_seg = seg_out && seg_capacity >= total && total > 0;
+    // a client's tracts always go through the staging, and it sees every pair range, tracts or none
+    const bool want_seg = client || (seg_out && seg_capacity >= total && total > 0);
+    uint64_t ranges_run = 0;
     if (want_seg || (want_win && total > 0)) {
         const std::vector<uint64_t> ranges = want_seg ? ibs_pair_ranges(off, seg_cap) : std::vector<uint64_t>{0, n_pairs};
         uint64_t max_seg = 0;
@@ -461,9 +464,15 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
         }
         for (size_t k = 0; k + 1 < ranges.size(); ++k) {
             const uint64_t p0 = ranges[k], p1 = ranges[k + 1], cnt = off[p1] - off[p0];
-            if (cnt == 0 && !want_win) continue;
+            if (cnt == 0 && !want_win && !client) continue;
             A.seg = want_seg ? L2.at<impop_ibs_segment>(d2, o_seg) : nullptr;
             A.off0 = off[p0];
+            ++ranges_run;
+            if (client) {
+                if (cnt && (rc = sweep(true, p0, p1))) return rc;
+                if ((rc = client->range(IbsStage{p0, p1, n_pairs, A.rec, A.off, A.seg, off[p0], cnt}))) return rc;  // synchronises
+                continue;
+            }
             if ((rc = sweep(true, p0, p1))) return rc;
             if (want_seg && cnt)
                 HIP_TRY(hipMemcpyAsync(seg_out + off[p0], A.seg, cnt * sizeof(impop_ibs_segment), hipMemcpyDeviceToHost, st));
@@ -489,6 +498,14 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
             win_out[i] = o;
         }
     }
+    if (client) {
+        client->n_pairs = n_pairs;
+        client->tracts = total;
+        client->pair_ranges = ranges_run;
+        client->launches = launches;
+        client->bytes_streamed = bytes_streamed;
+        return IMPOP_OK;
+    }
     if (trace_on()) {
         fprintf(stderr, "[impop_ibs_scan] route=%s pairs=%llu site_chunks=%llu sub_segments=%llu launches=%llu tracts=%llu bytes_streamed=%llu\n",
                 m->compact ? "compact" : "dense", (unsigned long long)n_pairs, (unsigned long long)chunks_run, (unsigned long long)subs_run,
@@ -496,6 +513,18 @@ IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64
         fflush(stderr);
     }
     return IMPOP_OK;
+}
+
+IMPOP_API int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m, const uint64_t *mask_p, const uint32_t *pairs, uint64_t n_pairs,
+                             const impop_window *windows, uint64_t n_windows, const impop_ibs_params *params, impop_ibs_pair *pair_out,
+                             impop_ibs_segment *seg_out, uint64_t seg_capacity, uint64_t *n_segments, impop_ibs_window *win_out) {
+    static_assert(sizeof(impop_ibs_params) == 32 && sizeof(impop_ibs_pair) == 32 && sizeof(impop_ibs_segment) == 32 &&
+                      sizeof(impop_ibs_window) == 32,
+                  "ABI layout");
+    REQUIRE(ctx && m && params && n_segments, "%s: NULL argument", "impop_ibs_scan");
+    REQUIRE(params->struct_size == sizeof(impop_ibs_params), "impop_ibs_params.struct_size mismatch");
+    return ibs_scan_run("impop_ibs_scan", ctx, m, mask_p, pairs, n_pairs, windows, n_windows, params->site_begin, params->site_end,
+                        params->min_sites, params->max_chunk_bytes, pair_out, seg_out, seg_capacity, n_segments, win_out, nullptr);
 }
 
 IMPOP_API int impop_ctx_ibs_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks) {

@@ -173,7 +173,8 @@ struct impop_ctx {
         T_KIN = T_IHS + 2,   // impop_genotypes_create's plane build / impop_kinship_scan's epilogue kernels (impop_ctx_kinship_elapsed)
         T_PCA = T_KIN + 2,   // impop_pca_scan: the eigen kernel of every chunk / the distance kernel (impop_ctx_pca_elapsed)
         T_PERM = T_PCA + 2,  // impop_permtest_scan: the preparation / labelling kernel of every chunk (impop_ctx_permtest_elapsed)
-        T_COUNT = T_PERM + 2
+        T_IBD = T_PERM + 2,  // impop_ibd_scan: transpose / walk / combine + close / chain kernels (impop_ctx_ibd_elapsed)
+        T_COUNT = T_IBD + 4
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
@@ -299,6 +300,7 @@ constexpr uint32_t DEV_ERR_IBS = 64u;               // IBS scan: a pair's runs d
 constexpr uint32_t DEV_ERR_IHS = 128u;              // iHS scan: a class's break weights do not add up to its pairs, or a reach lies in front of the warm-up start
 constexpr uint32_t DEV_ERR_KINSHIP = 256u;          // kinship scan: a cell of a pair's joint genotype table came out negative
 constexpr uint32_t DEV_ERR_PERMTEST = 512u;         // permutation test: the matrix-core path's values of the observed labelling are not the direct ones
+constexpr uint32_t DEV_ERR_IBD = 1024u;             // IBD scan: the fill met a segment the count did not announce, or fewer than it announced
 constexpr uint32_t DEV_ERR_EHH = 4u;                // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 from .ihs import IHS_DTYPE  # noqa: E402
 
@@ -58,6 +58,11 @@ IBS_SEGMENT_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("begin", "<u8"), ("
 IBS_WINDOW_DTYPE = np.dtype([("pair_sites", "<u8"), ("tracts", "<u4"), ("pairs_spanning", "<u4"), ("n_sites", "<u4"), ("reserved", "<u4"),
                              ("share", "<f8")])
 assert IBS_PAIR_DTYPE.itemsize == 32 and IBS_SEGMENT_DTYPE.itemsize == 32 and IBS_WINDOW_DTYPE.itemsize == 32
+IBD_PAIR_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("n_segments", "<u4"), ("n_candidates", "<u4"), ("total_len", "<u8"),
+                           ("total_extent", "<u8"), ("longest_len", "<u8"), ("ibs_sites", "<u8")])
+IBD_SEGMENT_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("begin", "<u8"), ("end", "<u8"), ("len", "<u8"), ("ibs_sites", "<u4"),
+                              ("n_tracts", "<u4"), ("pair", "<u4"), ("flags", "<u4")])
+assert IBD_PAIR_DTYPE.itemsize == 48 and IBD_SEGMENT_DTYPE.itemsize == 48
 DSTAT_DTYPE = np.dtype([("n_sites", "<u4"), ("n_informative", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4"), ("abba", "<i8"), ("baba", "<i8"),
                         ("f4_num", "<i8"), ("fd_den_p2", "<i8"), ("fd_den_p3", "<i8"), ("d", "<f8"), ("f4", "<f8"), ("fd", "<f8")])
 assert DSTAT_DTYPE.itemsize == 80
@@ -286,6 +291,12 @@ class Context:
         t, k = (C.c_double * 2)(), C.c_uint64()
         check(self._lib.impop_ctx_diploid_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
+
+    def ibd_elapsed(self):
+        """-> ([transpose, walk, combine + close, chain] kernel ms of ibd_scan, site chunks transposed) since gram_timing(True)"""
+        t, k = (C.c_double * 4)(), C.c_uint64(0)
+        check(self._lib.impop_ctx_ibd_elapsed(self.handle, t, C.byref(k)))
+        return [t[0], t[1], t[2], t[3]], int(k.value)
 
     def ibs_elapsed(self):
         """-> ([transpose, walk, combine + close] kernel ms of ibs_scan, site chunks transposed) since gram_timing(True)"""
@@ -888,13 +899,8 @@ class BitMatrix:
                                                ind.ctypes.data_as(C.POINTER(DiploidInd)) if want_individuals else None))
         return (out, ind) if want_individuals else out
 
-    def ibs_scan(self, pairs=None, mask_p=None, min_sites: int = 1, site_begin: int = 0, site_end: Optional[int] = None, windows=None,
-                 want_segments: bool = True, max_chunk_bytes: int = 0, seg_capacity: Optional[int] = None):
-        """Pairwise identity-by-state tracts over [site_begin, site_end) (impop_ibs_scan; site_end None = the matrix's end): every
-        pair of the members of mask_p (None = all haplotypes), or pairs = [n, 2] haplotype indices.  -> (pair records
-        (IBS_PAIR_DTYPE), segments (IBS_SEGMENT_DTYPE: the tracts of at least min_sites sites, pair-major) or None, window records
-        (IBS_WINDOW_DTYPE) or None, the total number of segments).  Segments: one counting call, then one filling call; or, with
-        seg_capacity given, one call with room for that many (None when the list is longer)."""
+    def _pair_list_args(self, pairs, mask_p):
+        """the pair arguments of ibs_scan / ibd_scan -> (pointer or None, n_pairs, the array it points into, records to expect)"""
         pp, n_pairs, pr = None, 0, None
         if pairs is not None:
             pr = np.asarray(pairs)
@@ -915,6 +921,16 @@ class BitMatrix:
             else:
                 k = int(np.count_nonzero(flags))
             n_rec = k * (k - 1) // 2
+        return pp, n_pairs, pr, n_rec
+
+    def ibs_scan(self, pairs=None, mask_p=None, min_sites: int = 1, site_begin: int = 0, site_end: Optional[int] = None, windows=None,
+                 want_segments: bool = True, max_chunk_bytes: int = 0, seg_capacity: Optional[int] = None):
+        """Pairwise identity-by-state tracts over [site_begin, site_end) (impop_ibs_scan; site_end None = the matrix's end): every
+        pair of the members of mask_p (None = all haplotypes), or pairs = [n, 2] haplotype indices.  -> (pair records
+        (IBS_PAIR_DTYPE), segments (IBS_SEGMENT_DTYPE: the tracts of at least min_sites sites, pair-major) or None, window records
+        (IBS_WINDOW_DTYPE) or None, the total number of segments).  Segments: one counting call, then one filling call; or, with
+        seg_capacity given, one call with room for that many (None when the list is longer)."""
+        pp, n_pairs, pr, n_rec = self._pair_list_args(pairs, mask_p)
         mk, mp = _mask_ptr(mask_p, self.n_hap)
         w = None if windows is None else make_windows(windows)
         prm = IbsParams(C.sizeof(IbsParams), int(min_sites), int(site_begin), 0 if site_end is None else int(site_end), int(max_chunk_bytes))
@@ -939,6 +955,55 @@ class BitMatrix:
         else:
             call(None, 0)
             seg = np.zeros(total.value, dtype=IBS_SEGMENT_DTYPE)
+            if total.value:
+                call(seg, len(seg))
+        return rec, seg, win, int(total.value)
+
+    def ibd_scan(self, min_seed: int, min_extend: int, min_output: int, max_gap: int = 0, min_sites: int = 1, map_pos=None, map_g=None,
+                 pairs=None, mask_p=None, site_begin: int = 0, site_end: Optional[int] = None, windows=None, want_segments: bool = True,
+                 max_chunk_bytes: int = 0, seg_capacity: Optional[int] = None):
+        """IBD segments over [site_begin, site_end) (impop_ibd_scan): a pair's exact IBS tracts of at least min_sites sites and
+        min_extend length, joined across gaps of at most max_gap coordinates; a chain is reported when it holds a tract of at least
+        min_seed and is min_output long.  Lengths are in the units of the map (map_pos, map_g: breakpoints in original site
+        coordinates and their uint64 map values), or sites without one.  Pairs as ibs_scan.  -> (pair records (IBD_PAIR_DTYPE),
+        segments (IBD_SEGMENT_DTYPE, pair-major) or None, window records (IBS_WINDOW_DTYPE, over the segments) or None, the total
+        number of segments).  Segments: one counting call, then one filling call; or, with seg_capacity given, one call with room
+        for that many (None when the list is longer)."""
+        pp, n_pairs, pr, n_rec = self._pair_list_args(pairs, mask_p)
+        mk, mp = _mask_ptr(mask_p, self.n_hap)
+        w = None if windows is None else make_windows(windows)
+        if (map_pos is None) != (map_g is None):
+            raise ValueError("map_pos and map_g go together")
+        mpos = mg = None
+        if map_pos is not None:
+            mpos, mg = np.ascontiguousarray(map_pos, dtype=np.uint64).reshape(-1), np.ascontiguousarray(map_g, dtype=np.uint64).reshape(-1)
+            if len(mpos) != len(mg):
+                raise ValueError("map_pos and map_g differ in length")
+        n_map = 0 if mpos is None else len(mpos)
+        prm = IbdParams(C.sizeof(IbdParams), int(min_sites), int(site_begin), 0 if site_end is None else int(site_end), int(min_seed),
+                        int(min_extend), int(min_output), int(max_gap), mpos.ctypes.data_as(C.POINTER(C.c_uint64)) if n_map else None,
+                        mg.ctypes.data_as(C.POINTER(C.c_uint64)) if n_map else None, n_map, 0, int(max_chunk_bytes))
+        rec = np.zeros(max(n_rec, 0), dtype=IBD_PAIR_DTYPE)
+        win = None if w is None else np.zeros(len(w), dtype=IBS_WINDOW_DTYPE)
+        total = C.c_uint64(0)
+
+        def call(seg, cap):
+            check(self.ctx._lib.impop_ibd_scan(self.ctx.handle, self.handle, mp, pp, n_pairs,
+                                               None if w is None else w.ctypes.data_as(C.POINTER(Window)), 0 if w is None else len(w),
+                                               C.byref(prm), rec.ctypes.data_as(C.POINTER(IbdPair)),
+                                               None if seg is None else seg.ctypes.data_as(C.POINTER(IbdSegment)), cap, C.byref(total),
+                                               None if win is None else win.ctypes.data_as(C.POINTER(IbsWindow))))
+
+        seg = None
+        if not want_segments:
+            call(None, 0)
+        elif seg_capacity is not None:
+            seg = np.zeros(int(seg_capacity), dtype=IBD_SEGMENT_DTYPE)
+            call(seg, len(seg))
+            seg = seg[:total.value] if total.value <= len(seg) else None
+        else:
+            call(None, 0)
+            seg = np.zeros(total.value, dtype=IBD_SEGMENT_DTYPE)
             if total.value:
                 call(seg, len(seg))
         return rec, seg, win, int(total.value)

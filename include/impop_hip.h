@@ -983,6 +983,79 @@ int impop_ibs_scan(impop_ctx *ctx, const impop_matrix *m,
 /* With impop_ctx_gram_timing on, impop_ibs_scan brackets its kernels: kernel_ms[0] = transposes, [1] = the walks of both sweeps,
  * [2] = combine / close kernels, summed since enable / reset; chunks = site chunks transposed (both sweeps counted). */
 int impop_ctx_ibs_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
+#define IMPOP_IBD_MAX_MAP 4194304u       /* breakpoints of a genetic map (2^22) */
+/* Identity-by-descent segments of pairs of haplotypes: impop_ibs_scan's exact tracts joined across short gaps, with lengths
+ * measured on a genetic map.  The rule is the seed-and-extend rule of hap-IBD (Zhou, Browning & Browning 2020) written as a pure
+ * function of a pair's exact tracts; it is integer-exact.  No parity with that program's output is claimed: this definition is
+ * the contract.  Matrix, range [b, e) = [site_begin, site_end), pairs (member mask or list) and windows are impop_ibs_scan's.
+ * Map (optional): n_map breakpoints (pos_k, g_k), pos strictly ascending in ORIGINAL site coordinates, g non-decreasing uint64 in
+ * the caller's length unit (the command line uses micro-centimorgans).  G(x) = g_0 for x <= pos_0, g_last for x >= pos_last, else
+ * with pos_k <= x < pos_{k+1}: G(x) = g_k + floor((x - pos_k) (g_{k+1} - g_k) / (pos_{k+1} - pos_k)) in uint64.  A map with a pos
+ * or g step >= 2^32 is refused (the product cannot overflow), as are n_map == 1 and n_map > IMPOP_IBD_MAX_MAP.  Without a map
+ * (both pointers NULL, n_map 0) G(x) = x.
+ * Tracts of a pair: exactly impop_ibs_scan's tracts of [b, e) before any length filter.  The LENGTH of [s, t) is G(t) - G(s), its
+ * EXTENT t - s.
+ * Candidate: a tract with extent >= min_sites (>= 1) and length >= min_extend.  Seed: a candidate with length >= min_seed;
+ * min_seed < min_extend is refused.
+ * Chain: a maximal run of consecutive candidates of the pair in which each next candidate begins at most max_gap coordinates
+ * after the previous one ends (gap = next.begin - prev.end >= 1, so max_gap = 0 never joins).  Non-candidate tracts and
+ * discordant sites between two candidates lie inside the gap.
+ * IBD segment: a chain that holds at least one seed and has G(end) - G(begin) >= min_output, begin = the first candidate's
+ * begin, end = the last candidate's end; len = G(end) - G(begin), n_tracts = its candidates, ibs_sites = the sum of their
+ * extents, flags = IMPOP_IBS_OPEN_LEFT / _RIGHT when begin == b / end == e.  Site weights play no part; on a compacted matrix
+ * the coordinates are the kept sites' original positions.  The list is pair-major, ascending inside a pair.
+ * Known answers: two rows over 40 sites, h0 all 0, h1 with 1 at sites 10, 12 and 30; pair (0,1), range [0,40): the tracts are
+ * [0,10), [11,12), [13,30), [31,40).
+ *   (a) no map, min_sites 2, min_extend 5, min_seed 12, min_output 20: max_gap 3 gives one segment [0,40), len 40, n_tracts 3,
+ *       ibs_sites 36, open on both sides; max_gap 2 gives one segment [13,40), len 27, n_tracts 2, ibs_sites 26, OPEN_RIGHT (the
+ *       chain {[0,10)} has no seed); max_gap 2 with min_output 30 gives nothing.
+ *   (b) map (0,0),(20,100),(40,120), so G(13) = 65, G(30) = 110, G(31) = 111; min_sites 2, min_extend 10, min_seed 40,
+ *       min_output 50, max_gap 3: [31,40) has length 9 and is no candidate; one segment [0,30), len 110, n_tracts 2,
+ *       ibs_sites 27, OPEN_LEFT.
+ * Cost: the tracts of extent >= min_sites are staged on the device (impop_ibs_scan's two sweeps, a range of pairs at a time) and
+ * one wave per pair chains them; min_sites is the cost lever: with min_sites = 1 every tract is staged.
+ * Capacity: as impop_ibs_scan.  *n_segments always receives the total; seg_out is written only when seg_capacity >= total;
+ * pair_out and win_out are filled either way.  Window records are impop_ibs_window with "reported tract" read as "IBD segment".
+ * Everything impop_ibs_scan refuses, a bad map and min_seed < min_extend return IMPOP_E_INVALID; |P| > IMPOP_IBS_MAX_N, n_pairs >
+ * IMPOP_IBS_MAX_PAIRS and n_map > IMPOP_IBD_MAX_MAP IMPOP_E_UNSUPPORTED; all before anything is uploaded or launched.  A segment
+ * the counting pass did not announce is never written: the device error word is set and the call returns IMPOP_E_INTERNAL.
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_ibd_scan] route=<dense|compact> pairs= pair_ranges= candidates= segments= map_points= launches= bytes_streamed=
+ * (candidates: the tracts that passed extent and min_extend; map_points: the breakpoints uploaded, those that bracket the range). */
+typedef struct impop_ibd_params {        /* 88 bytes */
+    uint32_t struct_size;
+    uint32_t min_sites;                  /* >= 1: extent a candidate needs; the tracts staged */
+    uint64_t site_begin, site_end;       /* as impop_ibs_params */
+    uint64_t min_seed, min_extend, min_output;   /* units of G */
+    uint64_t max_gap;                    /* coordinates */
+    const uint64_t *map_pos, *map_g;     /* n_map each, or both NULL */
+    uint32_t n_map, reserved;
+    uint64_t max_chunk_bytes;            /* as impop_ibs_params */
+} impop_ibd_params;
+typedef struct impop_ibd_pair {          /* 48 bytes, fixed layout, one per pair, in pair order */
+    uint32_t h1, h2;
+    uint32_t n_segments;                 /* IBD segments of the pair */
+    uint32_t n_candidates;               /* its candidate tracts, in a reported chain or not */
+    uint64_t total_len, total_extent, longest_len, ibs_sites;   /* over the reported segments: sums of len, end - begin, the largest len, sum of ibs_sites */
+} impop_ibd_pair;
+typedef struct impop_ibd_segment {       /* 48 bytes, fixed layout */
+    uint32_t h1, h2;
+    uint64_t begin, end;                 /* [begin, end), ORIGINAL coordinates */
+    uint64_t len;                        /* G(end) - G(begin) */
+    uint32_t ibs_sites, n_tracts;        /* over the chain's candidates */
+    uint32_t pair;                       /* index into the pair order */
+    uint32_t flags;                      /* IMPOP_IBS_OPEN_* */
+} impop_ibd_segment;
+int impop_ibd_scan(impop_ctx *ctx, const impop_matrix *m,
+                   const uint64_t *mask_p, const uint32_t *pairs, uint64_t n_pairs,   /* as impop_ibs_scan */
+                   const impop_window *windows, uint64_t n_windows,   /* nullable */
+                   const impop_ibd_params *params,
+                   impop_ibd_pair *pair_out,          /* nullable */
+                   impop_ibd_segment *seg_out, uint64_t seg_capacity, uint64_t *n_segments,
+                   impop_ibs_window *win_out);        /* n_windows records; NULL iff windows is NULL */
+/* With impop_ctx_gram_timing on: kernel_ms[0] = transposes, [1] = walks, [2] = combine / close, [3] = the chain kernel (both
+ * forms), summed since enable / reset; chunks = site chunks transposed. */
+int impop_ctx_ibd_elapsed(impop_ctx *ctx, double kernel_ms[4], uint64_t *chunks);
 #define IMPOP_DSTAT_GROUP 3u   /* quartets whose sums one streaming launch of impop_dstat_scan keeps in registers */
 #define IMPOP_DSTAT_MAX_QUARTETS 64u
 /* Introgression statistics per window and quartet of populations (P1, P2, P3, O): Patterson's D (ABBA-BABA), f4 and Martin's f_d,
