@@ -100,6 +100,24 @@ class PcaParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("k", C.c_uint32), ("tol", C.c_double), ("max_iter", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class TreeParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("linkage", C.c_uint32)]
+
+
+class TreeWindow(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("n_zero_merges", C.c_uint32), ("n_tied_merges", C.c_uint32),
+                ("sum_h", C.c_uint64), ("root_num", C.c_uint64), ("root_size_a", C.c_uint32), ("root_size_b", C.c_uint32),
+                ("reserved", C.c_uint64)]
+
+
+class TreeMerge(C.Structure):
+    _fields_ = [("a", C.c_uint32), ("b", C.c_uint32), ("size_a", C.c_uint32), ("size_b", C.c_uint32), ("num", C.c_uint64)]
+
+
+class TreePanel(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("largest_clade", C.c_uint32), ("mrca_size", C.c_uint32), ("mrca_merge", C.c_uint32)]
+
+
 class PermtestParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("n_perm", C.c_uint32), ("seed", C.c_uint64)]
 
@@ -304,6 +322,8 @@ assert C.sizeof(DistPanel) == 64 and C.sizeof(DistPair) == 96 and C.sizeof(Paird
 PAIRDIST_MAX_N, PAIRDIST_MAX_BINS = 4096, 1024  # IMPOP_PAIRDIST_MAX_N, IMPOP_PAIRDIST_MAX_BINS
 assert C.sizeof(PcaParams) == 24 and C.sizeof(PcaWindow) == 160
 PCA_MAX_N, PCA_MAX_K, PCA_MAX_DIST_WINDOWS = 1024, 8, 16384  # IMPOP_PCA_MAX_N, IMPOP_PCA_MAX_K, the most windows out_dist2 takes
+assert C.sizeof(TreeParams) == 8 and C.sizeof(TreeWindow) == 48 and C.sizeof(TreeMerge) == 24 and C.sizeof(TreePanel) == 16
+TREE_MAX_N, TREE_LINKAGES = 1024, {"single": 0, "complete": 1, "average": 2}  # IMPOP_TREE_MAX_N, IMPOP_LINKAGE_*
 assert C.sizeof(PermtestParams) == 16 and C.sizeof(PermPair) == 128 and C.sizeof(PermNull) == 24
 # IMPOP_PERMTEST_MAX_N, IMPOP_PERMTEST_MAX_PERM, the most entries out_null takes, SCALE of the nn sums
 PERMTEST_MAX_N, PERMTEST_MAX_PERM, PERMTEST_MAX_NULL, PERMTEST_SCALE = 1024, 16384, 1 << 22, 2952069120
@@ -397,6 +417,9 @@ SIGNATURES = {
     "impop_pairdist_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PairdistParams),
                                       C.POINTER(DistPanel), C.POINTER(DistPair), _u32p, _u32p]),
     "impop_pca_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(PcaParams), C.POINTER(PcaWindow), _f64p, _f64p]),
+    "impop_tree_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, _u64p, C.c_uint32, C.POINTER(TreeParams),
+                                  C.POINTER(TreeWindow), C.POINTER(TreeMerge), C.POINTER(TreePanel)]),
+    "impop_ctx_tree_elapsed": (C.c_int, [_vp, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
     "impop_permtest_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.c_uint32, C.POINTER(PermtestParams),
                                       C.POINTER(PermPair), C.POINTER(PermNull)]),
     "impop_permtest_labels": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _u64p]),

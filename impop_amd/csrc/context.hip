@@ -307,6 +307,11 @@ IMPOP_API int impop_ctx_pca_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_
     return ctx_timers_elapsed(ctx, impop_ctx::T_PCA, 2, 0, kernel_ms, chunks);
 }
 
+IMPOP_API int impop_ctx_tree_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches) {
+    REQUIRE(ctx, "impop_ctx_tree_elapsed: ctx is NULL");
+    return ctx_timers_elapsed(ctx, impop_ctx::T_TREE, 1, 0, total_ms, launches);
+}
+
 IMPOP_API int impop_ctx_permtest_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chunks) {
     REQUIRE(ctx && kernel_ms, "impop_ctx_permtest_elapsed: NULL argument");
     return ctx_timers_elapsed(ctx, impop_ctx::T_PERM, 2, 1, kernel_ms, chunks);

@@ -174,7 +174,8 @@ struct impop_ctx {
         T_PCA = T_KIN + 2,   // impop_pca_scan: the eigen kernel of every chunk / the distance kernel (impop_ctx_pca_elapsed)
         T_PERM = T_PCA + 2,  // impop_permtest_scan: the preparation / labelling kernel of every chunk (impop_ctx_permtest_elapsed)
         T_IBD = T_PERM + 2,  // impop_ibd_scan: transpose / walk / combine + close / chain kernels (impop_ctx_ibd_elapsed)
-        T_COUNT = T_IBD + 4
+        T_TREE = T_IBD + 4,  // impop_tree_scan: the tree kernel of every chunk (impop_ctx_tree_elapsed)
+        T_COUNT
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the

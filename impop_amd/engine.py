@@ -88,6 +88,11 @@ assert DIST_PANEL_DTYPE.itemsize == 64 and DIST_PAIR_DTYPE.itemsize == 96
 PCA_WINDOW_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("rank", "<u4"), ("iterations", "<u4"), ("flags", "<u4"),
                              ("reserved", "<u4"), ("sum_h", "<u8"), ("lambda", "<f8", (8,)), ("resid", "<f8", (8,))])
 assert PCA_WINDOW_DTYPE.itemsize == 160
+TREE_WINDOW_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_zero_merges", "<u4"), ("n_tied_merges", "<u4"), ("sum_h", "<u8"),
+                              ("root_num", "<u8"), ("root_size_a", "<u4"), ("root_size_b", "<u4"), ("reserved", "<u8")])
+TREE_MERGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("size_a", "<u4"), ("size_b", "<u4"), ("num", "<u8")])
+TREE_PANEL_DTYPE = np.dtype([("n_members", "<u4"), ("largest_clade", "<u4"), ("mrca_size", "<u4"), ("mrca_merge", "<u4")])
+assert TREE_WINDOW_DTYPE.itemsize == 48 and TREE_MERGE_DTYPE.itemsize == 24 and TREE_PANEL_DTYPE.itemsize == 16
 PERM_PAIR_DTYPE = np.dtype([("n_a", "<u4"), ("n_b", "<u4"), ("n_sites", "<u4"), ("n_perm", "<u4"), ("wa", "<u8"), ("wb", "<u8"), ("ab", "<u8"),
                             ("nn", "<u8"), ("ge_fst", "<u4"), ("ge_phi", "<u4"), ("ge_dxy", "<u4"), ("ge_snn", "<u4"), ("fst", "<f8"),
                             ("phi_st", "<f8"), ("dxy", "<f8"), ("snn", "<f8"), ("p_fst", "<f8"), ("p_phi", "<f8"), ("p_dxy", "<f8"),
@@ -255,6 +260,12 @@ class Context:
         t, k = (C.c_double * 2)(), C.c_uint64()
         check(self._lib.impop_ctx_pca_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
+
+    def tree_elapsed(self):
+        """-> (tree kernel ms of tree_scan, chunks) since gram_timing(True)"""
+        t, k = C.c_double(), C.c_uint64()
+        check(self._lib.impop_ctx_tree_elapsed(self.handle, C.byref(t), C.byref(k)))
+        return t.value, k.value
 
     def permtest_elapsed(self):
         """-> ([preparation kernel, labelling kernel] ms of permtest_scan, chunks) since gram_timing(True)"""
@@ -784,6 +795,31 @@ class BitMatrix:
                                            vec.ctypes.data_as(f64p) if want_vectors else None,
                                            d2.ctypes.data_as(f64p) if want_dist else None))
         return out, vec, d2
+
+    def tree_scan(self, windows, mask_p=None, pops=None, linkage: str = "average", want_merges: bool = True):
+        """Exact linkage trees per window (impop_tree_scan): the single / complete / average (UPGMA) tree of the members of mask_p
+        over their Hamming distances, in integers with a fixed tie rule, from ONE Gram pass per window.  pops: up to 8 disjoint
+        0/1 flag arrays inside mask_p.
+        -> (windows [n_windows] TREE_WINDOW_DTYPE, merges [n_windows, |P| - 1] TREE_MERGE_DTYPE or None, panels [n_windows, K]
+            TREE_PANEL_DTYPE or None when there are no pops).  A merge names its two clusters by their lowest member POSITION in
+        mask_p; num is the numerator of its value (impop_amd.tree.heights)."""
+        w = make_windows(windows)
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        n_p = self.n_hap if mask_p is None else int(np.unpackbits(kp.view(np.uint8), bitorder="little")[: self.n_hap].sum())
+        K = len(pops) if pops else 0
+        packed = np.concatenate([_mask_ptr(p, self.n_hap)[0] for p in pops]).astype(np.uint64) if K else None
+        out = np.zeros(len(w), dtype=TREE_WINDOW_DTYPE)
+        merges = np.zeros((len(w), max(n_p - 1, 0)), dtype=TREE_MERGE_DTYPE) if want_merges else None
+        panels = np.zeros((len(w), K), dtype=TREE_PANEL_DTYPE) if K else None
+        if linkage not in _lib.TREE_LINKAGES:
+            raise ValueError("linkage must be one of %s" % ", ".join(_lib.TREE_LINKAGES))
+        prm = _lib.TreeParams(C.sizeof(_lib.TreeParams), _lib.TREE_LINKAGES[linkage])
+        check(self.ctx._lib.impop_tree_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp,
+                                            packed.ctypes.data_as(C.POINTER(C.c_uint64)) if K else None, K, C.byref(prm),
+                                            out.ctypes.data_as(C.POINTER(_lib.TreeWindow)),
+                                            merges.ctypes.data_as(C.POINTER(_lib.TreeMerge)) if want_merges else None,
+                                            panels.ctypes.data_as(C.POINTER(_lib.TreePanel)) if K else None))
+        return out, merges, panels
 
     def permtest_scan(self, windows, pops, n_perm: int = 1000, seed: int = 1, null: bool = False):
         """Permutation p-values for Hudson's Fst, AMOVA Phi_ST, Dxy and S_nn of every pair of K (2..8) disjoint panels, from ONE Gram

@@ -616,6 +616,77 @@ typedef struct impop_pca_window {   /* 160 bytes, fixed layout: one per window *
 int impop_pca_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
                    const uint64_t *mask_p /* nullable */, const impop_pca_params *params, impop_pca_window *out_windows,
                    double *out_vectors /* nullable: n_windows x k x |P| */, double *out_dist2 /* nullable: n_windows x n_windows */);
+#define IMPOP_TREE_MAX_N 1024u   /* members of the mask */
+enum { IMPOP_LINKAGE_SINGLE = 0, IMPOP_LINKAGE_COMPLETE = 1, IMPOP_LINKAGE_AVERAGE = 2 };
+/* LINKAGE TREES per window ("local trees"): the single-, complete- or average-linkage (UPGMA) tree of the members of one mask over
+ * their Hamming distances, from the Gram pass of impop_pairwise_scan, and per panel where it forms a clade.  Exact integers
+ * throughout, with one fixed tie rule: the output is a function of the distances alone.
+ * Members and distances: the members P of mask_p (NULL = all haplotypes) are positions 0 .. m - 1 in ascending haplotype index,
+ * m = |P| >= 2.  H_ij is the weighted Hamming distance of impop_pairdist_scan, a_i + a_j - 2 I_ij (polarity-invariant; the constant
+ * of a compacted matrix cancels).
+ * Clusters and values: every member starts as a cluster NAMED by its position.  The value of a pair of live clusters (A, B) is
+ *   single: min H_ij,   complete: max H_ij,   average: S_AB / (|A| |B|) with S_AB = sum H_ij,   over i in A, j in B.
+ * Merge rule: each of the m - 1 steps merges the live pair with the smallest (value, a, b), lexicographic, a < b the clusters'
+ * names (a cluster's name is its lowest member position).  Average linkage compares values EXACTLY, S_1 D_2 against S_2 D_1 as full
+ * 128-bit products: S <= W D with W < 2^31 and D = |A| |B| <= 2^18, and two pairs live at once have D_1 D_2 <= m^4 / 64 = 2^34
+ * (|A|^2 |B| |C| with |A| + |B| + |C| <= m = 1024, largest at |A| = m / 2), so a product reaches 2^65: 64 bits do not hold it.
+ * The merged cluster keeps the name a; its distances follow Lance-Williams in integers: the min, the max, or the sum of the two sums.
+ * out_merges (nullable): n_windows x (m - 1) records in merge order.  num is the value's numerator; the denominator is
+ * size_a size_b for average linkage and 1 otherwise.  All three linkages are reducible (d(K, A u B) >= min(d(K, A), d(K, B))), so
+ * the values are non-decreasing in merge order.  n_zero_merges counts the merges at value 0 (m minus the distinct haplotypes of the
+ * window); n_tied_merges counts the steps at which at least two live pairs attain the minimum: there the topology is the tie
+ * rule's.  root_num, root_size_a, root_size_b repeat the last merge.
+ * Panels (n_pop 0..8; out_panels n_windows x n_pop, required exactly when n_pop > 0): panel_masks are n_pop bitsets as in
+ * impop_pairdist_scan, disjoint and non-empty, and subsets of P (a panel member outside mask_p: IMPOP_E_INVALID).  largest_clade is
+ * the size of the largest cluster ever formed, singletons included, whose members all lie in the panel.  mrca_size is the size of
+ * the first cluster that holds the whole panel, mrca_merge the index of that merge (0xFFFFFFFF for a one-member panel, whose
+ * mrca_size is 1): the panel is monophyletic IN THE TREE AS OUTPUT iff mrca_size == n_members.  Members in no panel count towards
+ * sizes only.
+ * Refusals, all before anything is uploaded or launched: struct_size mismatch, linkage > 2, |P| < 2, n_pop > 8, out_panels given
+ * without n_pop or n_pop without out_panels, panels that overlap, are empty or leave P: IMPOP_E_INVALID; |P| > IMPOP_TREE_MAX_N:
+ * IMPOP_E_UNSUPPORTED.  n_windows == 0 returns IMPOP_OK.
+ * A window without sites has every value 0: m - 1 zero merges (0, 1), (0, 2), ..., all tied except the last, when only one pair is
+ * left.  Windows may overlap.  None of chunking (IMPOP_PAIRWISE_CHUNK), uint16 or int32 Gram counts (IMPOP_GRAM_U16=0), the Gram
+ * chain length (IMPOP_GRAM_CHAIN), compaction, weights against the bp-expanded matrix, the order of the windows in the list, or the
+ * width in which the kernel stores its sums (uint32 where W floor(m^2 / 4) < 2^32 proves they fit, else uint64; IMPOP_TREE_WIDE=1,
+ * a test aid, forces uint64) ever changes a byte, and two calls return identical bytes.  Checks the device error word like
+ * impop_pairwise_scan.  With impop_ctx_gram_timing on, impop_ctx_tree_elapsed returns the summed time of the chunks' tree kernel
+ * next to the Gram time.
+ * The kernel never rescans the matrix per step: every live row caches its nearest neighbour, and a merge rescans only row a and
+ * the rows whose cached neighbour was a or b.  Under IMPOP_TRACE=1 one line per call on stderr, next to the [impop_gram] lines:
+ *   [impop_tree_scan] route=<dense|compact> linkage=<single|complete|average> members= pops= windows= chunks= launches=
+ *                     rows_recomputed= tied_windows=
+ * rows_recomputed sums, over all merges of the call, the live rows whose cached neighbour was a or b — a and b themselves among
+ * them, so it is at least 2 (m - 1) per window; b retires, the others are rescanned.  tied_windows: windows with n_tied_merges > 0.
+ * Known answer: haplotypes 0000, 0001, 0111, 0001 over one 4-site window, all members: H01 = 1, H02 = 3, H03 = 1, H12 = 2,
+ * H13 = 0, H23 = 2.  Average linkage, merges (a, b, size_a, size_b, num): (1, 3, 1, 1, 0); then S_01 = H01 + H03 = 2 over 2 pairs
+ * = 1 against S_12 = 4 over 2 = 2 and H02 = 3: (0, 1, 1, 2, 2); then (0, 2, 3, 1, 7), value 7/3.  n_zero_merges 1, n_tied_merges 0,
+ * sum_h 9, root (7, 3, 1).  Panels {0, 1} and {2, 3}: largest_clade 1 / 1, mrca_size 3 / 4, mrca_merge 1 / 2.  Single linkage:
+ * (1, 3, 1, 1, 0), (0, 1, 1, 2, 1), (0, 2, 3, 1, 2).  Complete linkage: (1, 3, 1, 1, 0), (0, 1, 1, 2, 1), (0, 2, 3, 1, 3). */
+typedef struct impop_tree_params {   /* 8 bytes */
+    uint32_t struct_size, linkage;   /* IMPOP_LINKAGE_* */
+} impop_tree_params;
+typedef struct impop_tree_window {   /* 48 bytes, fixed layout: one per window */
+    uint32_t n_members, n_sites;
+    uint32_t n_zero_merges;          /* merges at value 0: n_members - (distinct haplotypes of the window) */
+    uint32_t n_tied_merges;          /* merges whose value another live pair equalled: the topology there is the tie rule's */
+    uint64_t sum_h;                  /* as impop_pca_window.sum_h */
+    uint64_t root_num;               /* the last merge */
+    uint32_t root_size_a, root_size_b;
+    uint64_t reserved;               /* 0 */
+} impop_tree_window;
+typedef struct impop_tree_merge {    /* 24 bytes: n_members - 1 per window, in merge order */
+    uint32_t a, b;                   /* a < b: member POSITIONS naming the two clusters */
+    uint32_t size_a, size_b;
+    uint64_t num;                    /* single: min, complete: max, average: SUM of H_ij over i in A, j in B */
+} impop_tree_merge;
+typedef struct impop_tree_panel {    /* 16 bytes: one per (window, panel) */
+    uint32_t n_members, largest_clade, mrca_size, mrca_merge;
+} impop_tree_panel;
+int impop_tree_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                    const uint64_t *mask_p /* nullable = all */, const uint64_t *panel_masks /* nullable */, uint32_t n_pop /* 0..8 */,
+                    const impop_tree_params *params, impop_tree_window *out_windows, impop_tree_merge *out_merges /* nullable */,
+                    impop_tree_panel *out_panels /* nullable; required non-NULL iff n_pop > 0 */);
 #define IMPOP_PERMTEST_MAX_N 1024u      /* members of the panels' union */
 #define IMPOP_PERMTEST_MAX_PERM 16384u  /* labellings of a call */
 /* PERMUTATION P-VALUES for Hudson's Fst, AMOVA Phi_ST, Dxy and Hudson's S_nn (Hudson 2000) per window and pair of panels, from
@@ -1238,6 +1309,8 @@ int impop_ctx_kinship_elapsed(impop_ctx *ctx, double kernel_ms[2], uint64_t *chu
 /* ... and impop_pca_scan its two kernels: kernel_ms[0] = the eigen kernel of every chunk, [1] = the distance kernel, summed since
  * enable / reset; chunks = eigen launches timed. */
 int impop_ctx_pca_elapsed(impop_ctx *ctx, double kernel_ms[2] /* eigen kernel, distance kernel */, uint64_t *chunks);
+/* ... and impop_tree_scan its tree kernel: summed time and number of chunks since enable / reset. */
+int impop_ctx_tree_elapsed(impop_ctx *ctx, double *total_ms, uint64_t *launches);
 /* ... and impop_permtest_scan its two kernels: kernel_ms[0] = the preparation kernel, [1] = the labelling kernel of every chunk,
  * summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_permtest_elapsed(impop_ctx *ctx, double kernel_ms[2] /* preparation, labelling */, uint64_t *chunks);
