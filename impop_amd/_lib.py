@@ -387,6 +387,7 @@ SIGNATURES = {
     "impop_scan_plan_launch": (C.c_int, [_vp, _vp]),
     "impop_scan_plan_fetch": (C.c_int, [_vp, C.POINTER(WindowStats)]),
     "impop_scan_plan_info": (C.c_int, [_vp, _u64p, _u64p]),
+    "impop_scan_plan_digest_info": (C.c_int, [_vp, C.POINTER(C.c_int), _u64p, _u64p, _u64p, C.c_char_p, C.c_size_t]),
     "impop_scan_plan_device_records": (C.c_int, [_vp, C.POINTER(_vp)]),
     "impop_shard_range": (C.c_int, [C.c_uint64, C.c_int, C.c_int, _u64p, _u64p]),
     "impop_shard_windows": (C.c_int, [C.POINTER(Window), C.c_uint64, C.c_int, C.c_int, _u64p, _u64p, _u64p, _u64p]),

@@ -336,6 +336,10 @@ inline uint32_t ones_weight(const impop_matrix *m, uint64_t s0, uint64_t s1) {
 }
 inline bool compact_weighted(const impop_matrix *m) { return m->compact && !m->ones_wt_prefix.empty(); }
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n);  // fills ctx->d_taj for n (device kernel)
+// scan.hip: impop_scan_plan_create for the library's own calls.  reusable = false: the plan is launched once, and the default
+// rule leaves it without a tile digest (tile_digest.h: a plan launched once must not pay for the build)
+int scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,
+                     const uint64_t *mask_a, const uint64_t *mask_b, const impop_scan_params *params, bool reusable, impop_scan_plan **out);
 
 // windows are given in ORIGINAL site coordinates; for a compacted matrix map them to kept-site index
 // ranges (`mapped`), else `mapped` is a plain copy.  span() = the coordinate range windows must lie in.

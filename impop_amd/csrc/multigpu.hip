@@ -89,7 +89,7 @@ IMPOP_API int impop_scan_sharded(impop_ctx *const *ctxs, const impop_matrix *con
         }
         std::vector<impop_window> loc(windows + first[k], windows + first[k] + count[k]);
         for (impop_window &w : loc) { w.site_begin -= slab_site_begin[k]; w.site_end -= slab_site_begin[k]; }
-        rc = impop_scan_plan_create(ctxs[k], slabs[k], loc.data(), count[k], mask_p, mask_a, mask_b, params, &plans[k]);
+        rc = scan_plan_create(ctxs[k], slabs[k], loc.data(), count[k], mask_p, mask_a, mask_b, params, false, &plans[k]);
         if (rc) { cleanup(); return rc; }
     }
     // 2. every device starts its pass before any result is waited for

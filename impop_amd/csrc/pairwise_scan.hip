@@ -502,7 +502,7 @@ IMPOP_API int impop_pairwise_scan_panel(impop_ctx *ctx, const impop_matrix *m, c
         impop_scan_params sp;
         sp.struct_size = sizeof sp; sp.d_pi_mode = params->d_pi_mode; sp.s_scope = 1; sp.tile_blocks = 0;
         impop_scan_plan *plan = nullptr;
-        rc = impop_scan_plan_create(ctx, m, windows, n_windows, masks, nullptr, nullptr, &sp, &plan);
+        rc = scan_plan_create(ctx, m, windows, n_windows, masks, nullptr, nullptr, &sp, false, &plan);
         if (rc) return rc;
         std::vector<impop_window_stats> rec(n_windows);
         sp_host.resize((size_t)K * n_windows);
@@ -548,7 +548,7 @@ IMPOP_API int impop_pairwise_scan(impop_ctx *ctx, const impop_matrix *m, const i
     // subset's own counts: the streaming scan of the same windows
     const bool use_segmap = want_s && !mask_p;
     impop_scan_plan *plan = nullptr;
-    rc = (want_s && !use_segmap) ? impop_scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, &sp, &plan) : IMPOP_OK;
+    rc = (want_s && !use_segmap) ? scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, &sp, false, &plan) : IMPOP_OK;
     if (rc) return rc;
     auto fail = [&](int code) {
         if (plan) impop_scan_plan_destroy(plan);

@@ -95,31 +95,38 @@ __device__ __forceinline__ void sb_for_each_dword(const uint32_t *blk, uint32_t 
     sb_use_tail(G, r, tl, f);
 }
 
-// compile-time shape (the fixed-WPS scan kernel): all WPS dwords of site `lane`
-template <int WPS>
-__device__ __forceinline__ void load_site(const uint32_t *__restrict__ blk, uint32_t lane, uint32_t (&w)[WPS]) {
+// compile-time shape (the fixed-WPS scan kernel): all WPS dwords of row i of a block of `rows` rows at blk, interleaved by
+// granule as an SB64 block is (rows = 64) — granule g of row i at dword (g rows + i) 4, the last granule's R dwords at
+// (G - 1) rows 4 + i R.  rows a multiple of 4 keeps every granule section 64-byte aligned to blk (the tile digest, tile_digest.h)
+template <int WPS, bool STREAM>
+__device__ __forceinline__ void load_row(const uint32_t *__restrict__ blk, uint32_t rows, uint32_t i, uint32_t (&w)[WPS]) {
     constexpr int G = (WPS + 3) / 4;
     constexpr int R = WPS - 4 * (G - 1);
 #pragma unroll
     for (int g = 0; g < G - 1; ++g) {
-        const u32v4 v = stream_load(sb_granule(blk, g, lane));
+        const u32v4 v = sb_load<STREAM>(reinterpret_cast<const u32v4 *>(blk + (uint64_t)g * (rows * 4) + i * 4));
         w[4 * g + 0] = v.x; w[4 * g + 1] = v.y; w[4 * g + 2] = v.z; w[4 * g + 3] = v.w;
     }
-    const uint32_t *last = blk + (G - 1) * 256 + lane * R;
+    const uint32_t *last = blk + (G - 1) * (rows * 4) + i * R;
     if constexpr (R == 4) {
-        const u32v4 v = stream_load(reinterpret_cast<const u32v4 *>(last));
+        const u32v4 v = sb_load<STREAM>(reinterpret_cast<const u32v4 *>(last));
         w[4 * (G - 1) + 0] = v.x; w[4 * (G - 1) + 1] = v.y; w[4 * (G - 1) + 2] = v.z; w[4 * (G - 1) + 3] = v.w;
     } else if constexpr (R == 3) {
         // 12-byte, 4-byte-aligned: three dwords (the backend merges them into one dwordx3)
-        w[4 * (G - 1) + 0] = stream_load(last);
-        w[4 * (G - 1) + 1] = stream_load(last + 1);
-        w[4 * (G - 1) + 2] = stream_load(last + 2);
+        w[4 * (G - 1) + 0] = sb_load<STREAM>(last);
+        w[4 * (G - 1) + 1] = sb_load<STREAM>(last + 1);
+        w[4 * (G - 1) + 2] = sb_load<STREAM>(last + 2);
     } else if constexpr (R == 2) {
-        const u32v2 v = stream_load(reinterpret_cast<const u32v2 *>(last));
+        const u32v2 v = sb_load<STREAM>(reinterpret_cast<const u32v2 *>(last));
         w[4 * (G - 1) + 0] = v.x; w[4 * (G - 1) + 1] = v.y;
     } else {
-        w[4 * (G - 1)] = stream_load(last);
+        w[4 * (G - 1)] = sb_load<STREAM>(last);
     }
+}
+// all WPS dwords of site `lane` of an SB64 block
+template <int WPS>
+__device__ __forceinline__ void load_site(const uint32_t *__restrict__ blk, uint32_t lane, uint32_t (&w)[WPS]) {
+    load_row<WPS, true>(blk, 64u, lane, w);
 }
 
 }  // namespace impop

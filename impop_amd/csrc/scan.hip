@@ -9,7 +9,8 @@
 // three population masks are wave-uniform and live in SGPRs.  Integer partials per tile are
 // written once (no atomics => deterministic); a second tiny kernel sums each window's tiles
 // and evaluates the fp64 statistics in the reference's operation order.  Plans of many small tiles on a unique-row route run
-// the second body instead, one WAVE per tile and four tiles per workgroup (scan_tiles_kernel_wave).
+// the second body instead, one WAVE per tile and four tiles per workgroup (scan_tiles_kernel_wave) — and, where the plan is kept
+// for more launches, read a per-tile digest of everything no mask enters, built where the plan is made (scan_tiles_kernel_digest).
 #include <algorithm>
 #include <map>
 #include <vector>
@@ -20,6 +21,7 @@
 #include "pop_stream.h"
 #include "sb64.h"
 #include "scan_route.h"
+#include "tile_digest.h"
 
 namespace impop {
 
@@ -189,6 +191,20 @@ __device__ __forceinline__ void rare_range_coded(const uint64_t *__restrict__ ra
     mo.fold(ps, acc);
 }
 
+// What a lane's singletons add to its sums, from how many there are (k) and how many of their carriers lie in A, in B, in P and in
+// both A and B: RareMoments::fold at m = 1.  single_range and the tile digest's histogram (scan_tiles_kernel_digest) close with it.
+__device__ __forceinline__ void singles_fold(uint32_t k, uint32_t kA, uint32_t kB, uint32_t kP, uint32_t kAB, const PopSizes &ps,
+                                             LaneAcc32 &acc) {
+    acc.s_all += k;
+    acc.s_p += ps.nP > 1u ? kP : 0u;
+    acc.s_a += ps.nA > 1u ? kA : 0u;
+    acc.s_b += ps.nB > 1u ? kB : 0u;
+    acc.q_p += kP * (ps.nP - 1u);
+    acc.q_a += kA * (ps.nA - 1u);
+    acc.q_b += kB * (ps.nB - 1u);
+    acc.q_ab += ps.nB * kA + ps.nA * kB - 2u * kAB;
+}
+
 // The packed route's singleton stream (internal.h, d_vsingle): singletons [s0, s1) of a tile, 2 bytes each, read as the aligned
 // 8-byte words [s0 / 4, ceil(s1 / 4)) — thread t takes word w0 + t, w0 + t + 256, ..., SU of them in flight (non-temporal,
 // 512 bytes per wave load; the stream's 0xFFFF padding keeps the last word inside the allocation).  Slots outside [s0, s1) —
@@ -238,14 +254,7 @@ __device__ __forceinline__ void single_range(const uint16_t *__restrict__ single
         }
         kA += code & 31u; kB += (code >> 5) & 31u; kP += (code >> 10) & 31u; kAB += code >> 15;
     }
-    acc.s_all += k;
-    acc.s_p += ps.nP > 1u ? kP : 0u;
-    acc.s_a += ps.nA > 1u ? kA : 0u;
-    acc.s_b += ps.nB > 1u ? kB : 0u;
-    acc.q_p += kP * (ps.nP - 1u);
-    acc.q_a += kA * (ps.nA - 1u);
-    acc.q_b += kB * (ps.nB - 1u);
-    acc.q_ab += ps.nB * kA + ps.nA * kB - 2u * kAB;
+    singles_fold(k, kA, kB, kP, kAB, ps, acc);
 }
 
 // entries [e0, e1) of a tile, thread t takes e0 + t, e0 + t + 256, ...: RU coalesced 512-byte wave loads in flight per wave
@@ -496,6 +505,24 @@ __device__ __forceinline__ void wave_reduce_store32(const LaneAcc32 &acc, uint32
     if (lane == 63) *o = r;
 }
 
+// The code table of a workgroup whose waves own a tile each, filled by all 256 threads from the masks in the kernel arguments
+// (the caller's barrier follows): set_masks acts at the next launch.
+template <int WPS>
+__device__ __forceinline__ void code_table_fill(uint16_t *hcode, const MaskArgs<WPS> &mk) {
+    constexpr int CODE_PER_THREAD = (32 * WPS + 255) / 256;
+    const uint32_t *mkw = reinterpret_cast<const uint32_t *>(&mk);  // p | a | b
+#pragma unroll
+    for (int j = 0; j < CODE_PER_THREAD; ++j) {
+        const uint32_t h = threadIdx.x + 256u * j, bit = h & 31u;
+        if (h < 32u * WPS) {
+            const uint32_t mp = mkw[h >> 5], ma = mkw[WPS + (h >> 5)], mb = mkw[2 * WPS + (h >> 5)];
+            hcode[h] = (uint16_t)(((ma >> bit) & 1u) | (((mb >> bit) & 1u) << 5) | (((mp >> bit) & 1u) << 10) |
+                                  (((ma & mb) >> bit & 1u) << 15));
+        }
+    }
+    if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
+}
+
 // The second body of the fixed-WPS kernel on a unique-row route: ONE WAVE PER TILE, wave w of workgroup g owns tile 4 g + w.
 // A bench tile is about 20 KB — a head block, one or two blocks of representatives, a tail block, some 46 entries and 2 200
 // singletons — so in scan_tiles_kernel each of the four waves owns at most one block, and everything else a wave executes (tile
@@ -516,20 +543,7 @@ __global__ __launch_bounds__(256, 5) void scan_tiles_kernel_wave(const uint32_t 
                                                                  const uint32_t *__restrict__ uniq, const uint8_t *__restrict__ uniq_wt,
                                                                  const UniqRange *__restrict__ uniqs, uint32_t n_tiles) {
     __shared__ uint16_t hcode[RARE_CODE_SIZE];
-    {
-        constexpr int CODE_PER_THREAD = (32 * WPS + 255) / 256;
-        const uint32_t *mkw = reinterpret_cast<const uint32_t *>(&mk);  // p | a | b
-#pragma unroll
-        for (int j = 0; j < CODE_PER_THREAD; ++j) {
-            const uint32_t h = threadIdx.x + 256u * j, bit = h & 31u;
-            if (h < 32u * WPS) {
-                const uint32_t mp = mkw[h >> 5], ma = mkw[WPS + (h >> 5)], mb = mkw[2 * WPS + (h >> 5)];
-                hcode[h] = (uint16_t)(((ma >> bit) & 1u) | (((mb >> bit) & 1u) << 5) | (((mp >> bit) & 1u) << 10) |
-                                      (((ma & mb) >> bit & 1u) << 15));
-            }
-        }
-        if (threadIdx.x == 0) hcode[RARE_CODE_NONE] = 0;
-    }
+    code_table_fill<WPS>(hcode, mk);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t k = 4u * blockIdx.x + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar
@@ -550,6 +564,67 @@ __global__ __launch_bounds__(256, 5) void scan_tiles_kernel_wave(const uint32_t 
     row_range<WPS, SUBSET_P, false, 1, 1>(sb, nullptr, tail_begin, t.site_end, turn, lane, mk, ps, acc);  // one block at most
     if (t.rare_end > t.rare_begin) rare_range_coded<64>(rare, t.rare_begin, t.rare_end, hcode, ps, acc, lane);
     if (sr.end > sr.begin) single_range<true, 64, 5>(single, sr.begin, sr.end, hcode, ps, acc, lane);
+    wave_reduce_store32(acc, lane, out + k);
+}
+
+// The one-wave body on a plan with a tile digest (tile_digest.h; built where the plan is made, digest_build_kernel below): the
+// same workgroup — wave w of workgroup g owns tile 4 g + w, one table, one barrier — and the same TilePartial, from what the
+// plan worked out once because no mask enters it.  A tile's common rows are ONE run of weighted representatives (a bench tile:
+// about 29 of them, one block, where the body above walks a head, one or two blocks of the stream and a tail through three
+// dispatches), with neither trim nor range arithmetic: a lane at or past the count loads nothing and accumulates zero words at
+// weight 0.  Its singletons are 32 WPS uint16 counts: lane l reads those of haplotypes 8 l .. 8 l + 7 in one 16-byte load and
+// their table values in one LDS read, eight multiplies by table bits in place of nine decoded words.  A tile whose range of the
+// singleton stream is shorter than a histogram kept it (a scalar branch).  The entries are the rare stream's, as above.
+// The digest is read again at every launch and is a fraction of the plan's streams, so its loads are plain ones (the
+// streams' are non-temporal: read once).
+template <int WPS, bool SUBSET_P>
+__global__ __launch_bounds__(256, 5) void scan_tiles_kernel_digest(const uint32_t *__restrict__ rows, const uint16_t *__restrict__ wts,
+                                                                   const uint16_t *__restrict__ hists,
+                                                                   const DigestDesc *__restrict__ descs,
+                                                                   const uint64_t *__restrict__ rare,
+                                                                   const uint16_t *__restrict__ single, const MaskArgs<WPS> mk,
+                                                                   const PopSizes ps, TilePartial *__restrict__ out, uint32_t n_tiles) {
+    __shared__ __attribute__((aligned(16))) uint16_t hcode[RARE_CODE_SIZE];
+    code_table_fill<WPS>(hcode, mk);
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t k = 4u * blockIdx.x + (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // scalar
+    if (k >= n_tiles) return;
+    const DigestDesc d = descs[k];
+    // the histogram's 16 bytes go out first and arrive behind the rows; lanes past the 32 WPS haplotypes hold no count
+    u32v4 cnt = {0u, 0u, 0u, 0u};
+    if (d.hist != 0 && lane < 4u * WPS) cnt = *reinterpret_cast<const u32v4 *>(hists + ((uint64_t)(d.hist - 1) * (32u * WPS) + 8u * lane));
+    LaneAcc32 acc;
+    const uint32_t padded = (uint32_t)digest_rows_padded(d.n_rows);
+    const uint32_t *base = rows + d.row_off * WPS;
+    for (uint32_t b = 0; b < d.n_rows; b += 64) {
+        const uint32_t i = b + lane;
+        uint32_t w[WPS] = {}, wt = 0;
+        if (i < d.n_rows) {
+            load_row<WPS, false>(base, padded, i, w);
+            wt = wts[d.row_off + i];
+        }
+        site_accumulate<WPS, SUBSET_P, true>(w, mk, ps, acc, wt);
+    }
+    if (d.rare_end > d.rare_begin) rare_range_coded<64>(rare, d.rare_begin, d.rare_end, hcode, ps, acc, lane);
+    if (d.hist != 0) {
+        // table values past 32 WPS are unset and meet a count of 0
+        const u32v4 code = *reinterpret_cast<const u32v4 *>(hcode + 8u * lane);
+        uint32_t n1 = 0, kA = 0, kB = 0, kP = 0, kAB = 0;
+        auto add = [&](uint32_t c, uint32_t v) {
+            n1 += c;
+            kA += __umul24(c, v & 1u); kB += __umul24(c, (v >> 5) & 1u); kP += __umul24(c, (v >> 10) & 1u); kAB += __umul24(c, (v >> 15) & 1u);
+        };
+        const uint32_t cw[4] = {cnt.x, cnt.y, cnt.z, cnt.w}, vw[4] = {code.x, code.y, code.z, code.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            add(cw[j] & 0xFFFFu, vw[j] & 0xFFFFu);
+            add(cw[j] >> 16, vw[j] >> 16);
+        }
+        singles_fold(n1, kA, kB, kP, kAB, ps, acc);
+    } else if (d.single_end > d.single_begin) {
+        single_range<true, 64, 5>(single, d.single_begin, d.single_end, hcode, ps, acc, lane);
+    }
     wave_reduce_store32(acc, lane, out + k);
 }
 
@@ -913,6 +988,13 @@ struct impop_scan_plan {
     const uint8_t *uniq_wt = nullptr;
     UniqRange *d_uniqs = nullptr;
     bool wave_tiles = false;  // unique-row route: launches run scan_tiles_kernel_wave, one wave per tile (tile_cut.h, wave_tile_choice)
+    // tile digest (tile_digest.h): one allocation of rows | weights | histograms and every tile's descriptor; launches then run
+    // scan_tiles_kernel_digest.  d_digest null: none, digest_why says why
+    void *d_digest = nullptr;
+    DigestDesc *d_descs = nullptr;
+    uint64_t digest_weight_off = 0, digest_hist_off = 0;
+    uint64_t digest_rows = 0, digest_hist_tiles = 0, digest_bytes = 0;
+    std::string digest_why = "not a scan plan of the one-wave body";
     uint64_t n_windows = 0, n_tiles = 0, bytes_streamed = 0;
     PopSizes ps{};
     bool subset_p = false;
@@ -988,23 +1070,25 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
 // matrix), rare_streamed = the bytes of rare sites the plan really reads (rare_bytes keeps counting 8 per rare site);
 // unique_rows = the representatives of the distinct-row stream of a unique-row route (all of the matrix), rows_streamed = the
 // bytes of rows the plan really reads (bytes_streamed = rows_streamed + rare_streamed); wave_tiles = 1 where the fixed-WPS kernel
-// will run one wave per tile (the last key; the free-text why= stays behind it, where the parsers that cut the line there expect it)
-static void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
+// will run one wave per tile; digest = 1 where it will run from the plan's tile digest, and the three byte counts are then what
+// such a launch reads (the last key; the free-text why= stays behind it, where the parsers that cut the line there expect it)
+void impop::trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows) {
     if (!trace_on()) return;
     const char *why = rt.indexed || m->compact ? "" : !m->wt_prefix.empty() && m->d_vsb ? "site weights" : m->vskip.c_str();
     uint64_t rare_bytes = 0, rare_streamed = 0;
     for (const ScanTile &t : rt.tiles) rare_bytes += (t.rare_end - t.rare_begin) * 8ull;
     rare_streamed = rare_bytes;
     for (const SingleRange &r : rt.singles) { rare_bytes += (r.end - r.begin) * 8ull; rare_streamed += single_bytes_streamed(r); }
+    if (rt.digest) rare_streamed = rt.digest_rare_streamed;
     const uint64_t rows_streamed = rt.bytes_streamed - rare_streamed;
     std::string off = "off:" + (!m->wt_prefix.empty() && m->d_vrare ? std::string("site weights") : m->rskip);
     for (char &ch : off) ch = ch == ' ' ? '_' : ch;
-    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu unique_rows=%llu rows_streamed=%llu wave_tiles=%d%s%s\n",
+    fprintf(stderr, "[impop_scan] route=%s kept_sites=%llu tiles=%llu bytes_streamed=%llu windows=%llu rare_sites=%llu rare_bytes=%llu split=%s single_sites=%llu rare_streamed=%llu unique_rows=%llu rows_streamed=%llu wave_tiles=%d digest=%d%s%s\n",
             rt.indexed ? "indexed" : m->compact ? "compact" : "dense", (unsigned long long)(rt.indexed ? m->n_vkept : m->g.n_site),
             (unsigned long long)rt.tiles.size(), (unsigned long long)rt.bytes_streamed, (unsigned long long)n_windows,
             (unsigned long long)(rt.split ? m->n_vrare : 0), (unsigned long long)rare_bytes, rt.split ? "on" : off.c_str(), (unsigned long long)(rt.packed ? m->n_vsingle : 0),
             (unsigned long long)rare_streamed, (unsigned long long)(rt.uniq ? m->n_vuniq : 0), (unsigned long long)rows_streamed,
-            rt.wave_tiles ? 1 : 0, *why ? " why=" : "", why);
+            rt.wave_tiles ? 1 : 0, rt.digest ? 1 : 0, *why ? " why=" : "", why);
     fflush(stderr);  // in order with the caller's own stderr lines even where stderr is buffered
 }
 
@@ -1031,6 +1115,159 @@ static int tile_uniq_ranges(impop_ctx *ctx, const impop_matrix *m, ScanRoute &rt
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(rt.uniqs.data(), L.at<UniqRange>(d, o_out), nt * sizeof(UniqRange), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return IMPOP_OK;
+}
+
+// ---- the tile digest of a plan (tile_digest.h), built on the device where the plan is made ----
+// One workgroup per tile.  The tile's candidate rows — head rows, representatives of the distinct-row stream with their weights,
+// tail rows; every row where the tile has no range of the stream — are brought to canonical form in LDS (a row whose haplotype 0
+// carries 1 is complemented within the n_hap real haplotypes: a row and its complement then are the same words, padding bits
+// zero), and candidate i is a representative unless an earlier candidate has its hash and its words: first occurrence, so the
+// order is the rows' own and the same at every build.  The weights of a class add up in LDS (integers: any order).
+// Count pass (n_reps not null): the tile's number of representatives.  Write pass (descs not null): its rows and weights at the
+// place digest_layout gave it, rank = the representatives before it, and its singleton histogram where it has one.
+// A tile above DIGEST_ROWS_MAX candidates is refused by the host before any launch; the kernel leaves it alone all the same.
+__global__ __launch_bounds__(256) void digest_build_kernel(const uint32_t *__restrict__ sb, const uint32_t *__restrict__ uniq,
+                                                           const uint8_t *__restrict__ uniq_wt, const ScanTile *__restrict__ tiles,
+                                                           const UniqRange *__restrict__ uniqs, uint32_t n_hap, uint32_t wps,
+                                                           uint32_t G, uint32_t r, uint32_t *__restrict__ n_reps,
+                                                           const DigestDesc *__restrict__ descs, uint32_t *__restrict__ rows,
+                                                           uint16_t *__restrict__ wts, const uint16_t *__restrict__ single,
+                                                           const SingleRange *__restrict__ singles, uint16_t *__restrict__ hists) {
+    constexpr uint32_t MAXC = (uint32_t)DIGEST_ROWS_MAX;
+    __shared__ uint32_t cand[MAXC * 16];  // wps <= 16 dwords per candidate
+    __shared__ uint32_t hash[MAXC], wsum[MAXC], hist[MAXC];
+    __shared__ uint16_t cwt[MAXC], first[MAXC];
+    __shared__ uint32_t n_rep;
+    const uint32_t k = blockIdx.x, tid = threadIdx.x;
+    const ScanTile t = tiles[k];
+    const UniqRange ur = uniqs[k];
+    const bool folded = ur.end > ur.begin, any = t.site_end > t.site_begin;
+    const MidBlocks mid = mid_blocks(t.site_begin, t.site_end);
+    const uint64_t head_end = folded ? mid.g0 << 6 : t.site_end, tail_begin = folded ? mid.g1 << 6 : t.site_end;
+    const uint64_t nh64 = any ? head_end - t.site_begin : 0, nu64 = folded ? ur.end - ur.begin : 0, nt64 = any ? t.site_end - tail_begin : 0;
+    if (nh64 + nu64 + nt64 > MAXC || wps > 16) {  // uniform
+        if (n_reps && tid == 0) n_reps[k] = 0xFFFFFFFFu;
+        return;
+    }
+    const uint32_t nh = (uint32_t)nh64, nu = (uint32_t)nu64, nc = nh + nu + (uint32_t)nt64;
+    const uint32_t last_mask = (n_hap & 31u) ? (1u << (n_hap & 31u)) - 1u : 0xFFFFFFFFu;
+    if (tid == 0) n_rep = 0;
+    for (uint32_t i = tid; i < nc; i += 256) {
+        const bool rep = i >= nh && i < nh + nu;
+        const uint64_t s = i < nh ? t.site_begin + i : rep ? ur.begin + (i - nh) : tail_begin + (i - nh - nu);
+        const uint32_t *src = rep ? uniq : sb;
+        const uint64_t blk = s >> 6;
+        const uint32_t l = (uint32_t)(s & 63);
+        const bool flip = (src[sb_index(wps, G, r, blk, l, 0)] & 1u) != 0;
+        uint32_t h = 2166136261u;
+        for (uint32_t q = 0; q < wps; ++q) {
+            uint32_t v = src[sb_index(wps, G, r, blk, l, q)];
+            if (flip) v ^= q + 1 == wps ? last_mask : 0xFFFFFFFFu;
+            cand[i * wps + q] = v;
+            h = (h ^ v) * 16777619u;
+        }
+        hash[i] = h;
+        wsum[i] = 0;
+        cwt[i] = rep ? (uint16_t)uniq_wt[s] : (uint16_t)1;
+    }
+    __syncthreads();
+    for (uint32_t i = tid; i < nc; i += 256) {
+        uint32_t f = i;
+        for (uint32_t j = 0; j < i; ++j) {
+            if (hash[j] != hash[i]) continue;
+            bool same = true;
+            for (uint32_t q = 0; q < wps; ++q) same = same && cand[j * wps + q] == cand[i * wps + q];
+            if (same) { f = j; break; }
+        }
+        first[i] = (uint16_t)f;
+        atomicAdd(&wsum[f], (uint32_t)cwt[i]);
+        if (f == i) atomicAdd(&n_rep, 1u);
+    }
+    __syncthreads();
+    if (n_reps && tid == 0) n_reps[k] = n_rep;
+    if (!descs) return;
+    const DigestDesc d = descs[k];
+    const uint32_t padded = (uint32_t)digest_rows_padded(d.n_rows);
+    uint32_t *base = rows + d.row_off * wps;
+    for (uint32_t i = tid; i < nc; i += 256) {
+        if (first[i] != i) continue;
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < i; ++j) rank += first[j] == j;
+        if (rank >= d.n_rows) continue;  // never: the count pass saw the same rows
+        for (uint32_t q = 0; q < wps; ++q) {
+            const uint32_t g = q >> 2;
+            const uint64_t at = g + 1 < G ? ((uint64_t)g * padded + rank) * 4 + (q & 3u) : (uint64_t)(G - 1) * padded * 4 + (uint64_t)rank * r + (q - 4 * (G - 1));
+            base[at] = cand[i * wps + q];
+        }
+        wts[d.row_off + rank] = (uint16_t)wsum[i];
+    }
+    if (d.hist == 0) return;  // uniform
+    const uint32_t nh16 = 32u * wps;
+    const SingleRange sr = singles[k];
+    for (uint32_t h = tid; h < nh16; h += 256) hist[h] = 0;
+    __syncthreads();
+    for (uint64_t s = sr.begin + tid; s < sr.end; s += 256) {
+        const uint32_t h = single[s] & 0x7FFFu;  // bit 15: which allele the carrier holds, nothing to a singleton's sums
+        if (h < nh16) atomicAdd(&hist[h], 1u);
+    }
+    __syncthreads();
+    uint16_t *dst = hists + (uint64_t)(d.hist - 1) * nh16;
+    for (uint32_t h = tid; h < nh16; h += 256) dst[h] = (uint16_t)hist[h];
+}
+
+// Decides whether plan p, whose tables are queued for upload on the context's stream, takes a digest, and builds it: the caps
+// and the rule of tile_digest.h, IMPOP_SCAN_DIGEST=0|1 overriding the rule.  The count pass and one small download give the host
+// every tile's place; one allocation; the write pass.  On return rt counts what a launch of the plan reads.  reusable: the
+// plan's maker may launch it again (impop_scan_plan_create), else a one-shot call made it, which the rule leaves without.
+static int plan_build_digest(impop_scan_plan *p, ScanRoute &rt, bool reusable) {
+    const impop_matrix *m = p->m;
+    impop_ctx *ctx = p->ctx;
+    const size_t nt = rt.tiles.size();
+    const uint32_t wps = m->g.wps;
+    if (!rt.wave_tiles || !nt) return IMPOP_OK;
+    const int force = env_is("IMPOP_SCAN_DIGEST", '0') ? 0 : env_is("IMPOP_SCAN_DIGEST", '1') ? 1 : -1;
+    bool all_fit = true;
+    for (size_t k = 0; k < nt && all_fit; ++k) all_fit = digest_tile_fits(rt.tiles[k], rt.uniqs[k], rt.packed ? rt.singles[k] : SingleRange{0, 0});
+    if (!digest_wanted(force, reusable, true, all_fit)) {
+        p->digest_why = force == 0 ? "IMPOP_SCAN_DIGEST=0" : !all_fit ? "a tile holds more than the digest's caps" : "a one-shot scan does not pay for the build";
+        return IMPOP_OK;
+    }
+    uint32_t *d_reps = nullptr;
+    std::vector<uint32_t> reps(nt);
+    auto launch = [&](uint32_t *n_reps, const DigestDesc *descs) {
+        hipLaunchKernelGGL(digest_build_kernel, dim3((uint32_t)nt), dim3(256), 0, ctx->stream, m->d_vsb, m->d_vuniq, m->d_vuniq_wt,
+                           (const ScanTile *)p->d_tiles, (const UniqRange *)p->d_uniqs, m->g.n_hap, wps, m->g.G, m->g.r, n_reps, descs,
+                           (uint32_t *)p->d_digest, (uint16_t *)((char *)p->d_digest + p->digest_weight_off), p->single,
+                           (const SingleRange *)p->d_singles, (uint16_t *)((char *)p->d_digest + p->digest_hist_off));
+        return hipGetLastError();
+    };
+    HIP_TRY(hipMalloc((void **)&d_reps, nt * sizeof(uint32_t)));
+    hipError_t e = launch(d_reps, nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(reps.data(), d_reps, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipFree(d_reps);
+    HIP_TRY(e);
+    for (size_t k = 0; k < nt; ++k)
+        REQUIRE(reps[k] <= DIGEST_ROWS_MAX, "impop_scan: tile %zu: the digest's count pass refused it", k);
+    DigestLayout L;
+    digest_layout(rt.tiles, rt.singles, reps.data(), wps, L);
+    if (!digest_choice(force, reusable, true, all_fit, L.bytes_streamed(), rt.bytes_streamed)) {
+        p->digest_why = "a launch would read more bytes with the digest than without";
+        return IMPOP_OK;
+    }
+    HIP_TRY(hipMalloc(&p->d_digest, std::max<size_t>(L.alloc_bytes(), 16)));
+    HIP_TRY(hipMalloc((void **)&p->d_descs, nt * sizeof(DigestDesc)));
+    p->digest_weight_off = L.weight_offset(); p->digest_hist_off = L.hist_offset();
+    HIP_TRY(hipMemsetAsync(p->d_digest, 0, std::max<size_t>(L.alloc_bytes(), 16), ctx->stream));  // the padding rows: zero words, weight 0
+    HIP_TRY(hipMemcpyAsync(p->d_descs, L.descs.data(), nt * sizeof(DigestDesc), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(launch(nullptr, p->d_descs));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // L dies at return
+    p->digest_rows = L.n_rows; p->digest_hist_tiles = L.n_hist_tiles; p->digest_bytes = L.digest_bytes();
+    p->digest_why.clear();
+    rt.digest = true;
+    rt.digest_rare_streamed = L.rare_streamed();
+    rt.bytes_streamed = L.bytes_streamed();
     return IMPOP_OK;
 }
 
@@ -1066,7 +1303,7 @@ int impop::check_window_weights(const char *fn, const impop_matrix *m, const imp
 // index when the matrix has one and no site weights (d_wt is indexed by matrix site), with the rare-entry stream of a split
 // index; else the matrix itself (compacted: original coordinates -> kept-site index ranges).  tile_blocks 0: the default.
 int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-                      uint32_t tile_blocks, ScanRoute &rt, bool want_packed) {
+                      uint32_t tile_blocks, ScanRoute &rt, bool want_packed, bool trace) {
     rt.indexed = m->d_vsb != nullptr && m->wt_prefix.empty();
     rt.split = rt.indexed && m->d_vrare != nullptr;
     rt.packed = want_packed && rt.split && m->d_vsingle != nullptr;
@@ -1101,7 +1338,7 @@ int impop::scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, con
     if (rc) return rc;
     REQUIRE(rt.tiles.size() < 0x7FFFFFFFull, "%s: %llu tiles exceed one launch; raise tile_blocks", fn,
             (unsigned long long)rt.tiles.size());
-    trace_route(m, rt, n_windows);
+    if (trace) trace_route(m, rt, n_windows);
     return IMPOP_OK;
 }
 
@@ -1160,9 +1397,16 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
     hipLaunchKernelGGL((scan_tiles_kernel_wave<WPS, SP>), dim3((uint32_t)((p->n_tiles + 3) / 4)), dim3(256), 0, st, p->sb, p->rare, \
                        p->d_tiles, mk, p->ps, p->d_parts, p->single, (const SingleRange *)p->d_singles, p->uniq, p->uniq_wt,    \
                        (const UniqRange *)p->d_uniqs, (uint32_t)p->n_tiles)
-    if (p->wave_tiles)   { if (p->subset_p) LAUNCH_WAVE(true); else LAUNCH_WAVE(false); }
+#define LAUNCH_DIGEST(SP)                                                                                                          \
+    hipLaunchKernelGGL((scan_tiles_kernel_digest<WPS, SP>), dim3((uint32_t)((p->n_tiles + 3) / 4)), dim3(256), 0, st,                  \
+                       (const uint32_t *)p->d_digest, (const uint16_t *)((const char *)p->d_digest + p->digest_weight_off),           \
+                       (const uint16_t *)((const char *)p->d_digest + p->digest_hist_off), (const DigestDesc *)p->d_descs, p->rare, \
+                       p->single, mk, p->ps, p->d_parts, (uint32_t)p->n_tiles)
+    if (p->d_digest)     { if (p->subset_p) LAUNCH_DIGEST(true); else LAUNCH_DIGEST(false); }
+    else if (p->wave_tiles) { if (p->subset_p) LAUNCH_WAVE(true); else LAUNCH_WAVE(false); }
     else if (p->d_uniqs) { if (p->subset_p) LAUNCH(true, true); else LAUNCH(false, true); }
     else                 { if (p->subset_p) LAUNCH(true, false); else LAUNCH(false, false); }
+#undef LAUNCH_DIGEST
 #undef LAUNCH_WAVE
 #undef LAUNCH
 }
@@ -1170,6 +1414,12 @@ static void launch_scan_fixed(impop_scan_plan *p, hipStream_t st) {
 IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows,
                                      uint64_t n_windows, const uint64_t *mask_p, const uint64_t *mask_a,
                                      const uint64_t *mask_b, const impop_scan_params *params, impop_scan_plan **out) {
+    return scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, params, true, out);
+}
+
+int impop::scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
+                            const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b, const impop_scan_params *params,
+                            bool reusable, impop_scan_plan **out) {
     REQUIRE(ctx && m && out, "impop_scan_plan_create: NULL argument");
     *out = nullptr;
     REQUIRE(n_windows == 0 || windows, "impop_scan_plan_create: windows is NULL");
@@ -1192,7 +1442,7 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     ScanRoute rt;
     // the plan will launch the fixed-WPS kernel (impop_scan_plan_launch), the one reader of the singleton and distinct-row streams
     const bool fixed_wps = m->wt_prefix.empty() && m->g.wps <= 16;
-    rc = scan_route("impop_scan", ctx, m, windows, n_windows, prm.tile_blocks, rt, fixed_wps);
+    rc = scan_route("impop_scan", ctx, m, windows, n_windows, prm.tile_blocks, rt, fixed_wps, false);  // the trace line: below
     if (rc) return rc;
     impop_scan_plan *p = new impop_scan_plan();
     p->ctx = ctx; p->m = m; p->n_windows = n_windows;
@@ -1229,6 +1479,10 @@ IMPOP_API int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, cons
     if (!rt.tiles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_tiles, rt.tiles.data(), rt.tiles.size() * sizeof(ScanTile), hipMemcpyHostToDevice, ctx->stream));
     if (n_windows) PLAN_TRY(hipMemcpyAsync(p->d_wins, rt.wins.data(), n_windows * sizeof(WinDesc), hipMemcpyHostToDevice, ctx->stream));
     PLAN_TRY(hipMemcpyAsync(p->d_masks, p->masks.data(), (size_t)3 * wps * 4, hipMemcpyHostToDevice, ctx->stream));
+    // the tile digest, where the plan takes one: built behind the uploads it reads, and the plan then reports what its launches read
+    if ((rc = plan_build_digest(p, rt, reusable))) return fail(rc);
+    p->bytes_streamed = rt.bytes_streamed;
+    trace_route(m, rt, n_windows);
     PLAN_TRY(hipStreamSynchronize(ctx->stream));  // host vectors die at return
 #undef PLAN_TRY
     rc = ensure_tajima_consts(ctx, p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2);
@@ -1320,6 +1574,17 @@ IMPOP_API int impop_scan_plan_info(const impop_scan_plan *p, uint64_t *n_tiles, 
     return IMPOP_OK;
 }
 
+IMPOP_API int impop_scan_plan_digest_info(const impop_scan_plan *p, int *on, uint64_t *n_rows, uint64_t *n_hist_tiles,
+                                          uint64_t *digest_bytes, char *why, size_t why_len) {
+    REQUIRE(p, "impop_scan_plan_digest_info: plan is NULL");
+    if (on) *on = p->d_digest != nullptr;
+    if (n_rows) *n_rows = p->digest_rows;
+    if (n_hist_tiles) *n_hist_tiles = p->digest_hist_tiles;
+    if (digest_bytes) *digest_bytes = p->digest_bytes;
+    if (why && why_len) snprintf(why, why_len, "%s", p->digest_why.c_str());
+    return IMPOP_OK;
+}
+
 IMPOP_API int impop_scan_plan_timing(impop_scan_plan *p, int enable) {
     REQUIRE(p, "impop_scan_plan_timing: plan is NULL");
     HIP_TRY(hipSetDevice(p->ctx->device));
@@ -1357,6 +1622,8 @@ IMPOP_API int impop_scan_plan_destroy(impop_scan_plan *p) {
     if (p->d_masks) hipFree(p->d_masks);
     if (p->d_singles) hipFree(p->d_singles);
     if (p->d_uniqs) hipFree(p->d_uniqs);
+    if (p->d_digest) hipFree(p->d_digest);
+    if (p->d_descs) hipFree(p->d_descs);
     if (p->m) p->m->users--;
     delete p;
     return IMPOP_OK;
@@ -1366,7 +1633,7 @@ IMPOP_API int impop_scan(impop_ctx *ctx, const impop_matrix *m, const impop_wind
                          const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
                          const impop_scan_params *params, impop_window_stats *out_host) {
     impop_scan_plan *p = nullptr;
-    int rc = impop_scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, params, &p);
+    int rc = scan_plan_create(ctx, m, windows, n_windows, mask_p, mask_a, mask_b, params, false, &p);
     if (rc) return rc;
     rc = impop_scan_plan_launch(p, nullptr);
     if (!rc) rc = impop_scan_plan_fetch(p, out_host);

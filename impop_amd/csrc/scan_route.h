@@ -30,6 +30,10 @@ struct ScanRoute : TileCut {  // ... and how cut_tiles cut it: tiles, singles, w
     const uint32_t *uniq = nullptr;
     const uint8_t *uniq_wt = nullptr;
     bool wave_tiles = false;  // ... and the kernel will run one wave per tile (tile_cut.h, wave_tile_choice)
+    // ... from the plan's tile digest (tile_digest.h; only impop_scan_plan_create's plans): bytes_streamed then counts what such a
+    // launch reads, digest_rare_streamed of it for histograms, kept singleton ranges and entries
+    bool digest = false;
+    uint64_t digest_rare_streamed = 0;
     std::vector<LayoutWindow> lw;  // the windows as ranges of sb's sites, of rare's entries (split) and of single's (packed)
     uint32_t tile_blocks = 0;
 };
@@ -42,9 +46,11 @@ int check_windows(const char *fn, const impop_matrix *m, const impop_window *win
 int check_window_weights(const char *fn, const impop_matrix *m, const impop_window *windows, uint64_t n_windows);
 // windows (validated, matrix coordinates) -> the route of a scan of m and what a launch on it streams.  tile_blocks 0: the default.
 // want_packed: the caller's kernel reads the singleton stream and the distinct-row stream; the route is packed when the matrix
-// has the one and a unique-row route when it has the other (else as without)
+// has the one and a unique-row route when it has the other (else as without).  trace: print the route's trace line (a caller
+// that goes on deciding what the line reports passes false and calls trace_route itself, once)
 int scan_route(const char *fn, impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows,
-               uint32_t tile_blocks, ScanRoute &rt, bool want_packed = false);
+               uint32_t tile_blocks, ScanRoute &rt, bool want_packed = false, bool trace = true);
+void trace_route(const impop_matrix *m, const ScanRoute &rt, uint64_t n_windows);
 // a tile-size override for tests, <name>=n in the environment: n clamped to 1..4096, 0 where the variable is unset or empty
 uint32_t env_tile_blocks(const char *name);
 

@@ -651,13 +651,17 @@ class BitMatrix:
 
     def scan(self, windows, mask_p=None, mask_a=None, mask_b=None, d_pi_mode: int = 0, s_scope: int = 0,
              tile_blocks: int = 0) -> np.ndarray:
-        """pi + Hudson Fst + Tajima's D + S for every window in one streaming pass."""
-        p = self.plan(windows, mask_p, mask_a, mask_b, d_pi_mode, s_scope, tile_blocks)
-        try:
-            p.launch()
-            return p.fetch()
-        finally:
-            p.destroy()
+        """pi + Hudson Fst + Tajima's D + S for every window in one streaming pass (impop_scan: a plan made, launched once and
+        destroyed, which therefore builds no tile digest; plan() is for launching again)."""
+        w = make_windows(windows)
+        prm = ScanParams(C.sizeof(ScanParams), int(d_pi_mode), int(s_scope), int(tile_blocks))
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        ka, pa = _mask_ptr(mask_a, self.n_hap)
+        kb, pb = _mask_ptr(mask_b, self.n_hap)
+        out = np.zeros(len(w), dtype=STATS_DTYPE)
+        check(self.ctx._lib.impop_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, pa, pb,
+                                       C.byref(prm), out.ctypes.data_as(C.POINTER(WindowStats))))
+        return out
 
     def scan_multi(self, windows, pops) -> np.ndarray:
         """All-pairs Hudson Fst of K disjoint populations in one pass -> array [n_windows, K(K-1)/2] of
@@ -1258,6 +1262,14 @@ class ScanPlan:
         check(lib.impop_scan_plan_info(self._h, C.byref(t), C.byref(b)))
         self.n_tiles, self.bytes_streamed = t.value, b.value
         self.n_windows = len(windows)
+
+    def digest_info(self) -> dict:
+        """The plan's tile digest: {"on", "n_rows" (representatives over all tiles), "n_hist_tiles", "digest_bytes"} and "why"
+        (the reason there is none, else "")."""
+        on, r, h, b = C.c_int(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        why = C.create_string_buffer(256)
+        check(self.matrix.ctx._lib.impop_scan_plan_digest_info(self._h, C.byref(on), C.byref(r), C.byref(h), C.byref(b), why, len(why)))
+        return {"on": bool(on.value), "n_rows": r.value, "n_hist_tiles": h.value, "digest_bytes": b.value, "why": why.value.decode()}
 
     def set_masks(self, mask_p=None, mask_a=None, mask_b=None) -> None:
         """Swap the subset / population masks; the tile tables (windows) are kept."""

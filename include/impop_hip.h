@@ -255,11 +255,22 @@ int impop_scan_plan_fetch(impop_scan_plan *plan, impop_window_stats *out_host);
  * of the tile's whole blocks of rows).
  * Under IMPOP_TRACE=1 impop_scan_plan_create prints one line per plan on stderr:
  *   [impop_scan] route=<indexed|dense|compact> kept_sites=<n> tiles=<n> bytes_streamed=<n> windows=<n> rare_sites=<n>
- *                rare_bytes=<n> split=<on|off:reason> single_sites=<n> rare_streamed=<n> unique_rows=<n> rows_streamed=<n> wave_tiles=<0|1> [why=<reason>]
+ *                rare_bytes=<n> split=<on|off:reason> single_sites=<n> rare_streamed=<n> unique_rows=<n> rows_streamed=<n> wave_tiles=<0|1>
+ *                digest=<0|1> [why=<reason>]
  * unique_rows: the representatives of the matrix's distinct-row stream when the plan reads it, else 0; rows_streamed: the bytes
  * of rows (and representatives) among bytes_streamed, rare_streamed the rest; wave_tiles: the plan's launches run one wave per
  * tile (small tiles in number; IMPOP_SCAN_WAVE_TILES=0|1 where the plan is made: never / whenever the 32-bit lane sums allow). */
 int impop_scan_plan_info(const impop_scan_plan *plan, uint64_t *n_tiles, uint64_t *bytes_streamed);
+/* The plan's tile digest (digest=1 of the trace line).  A plan and its matrix do not change, only the masks do, so a plan of
+ * many small tiles that its maker will launch again works out once, per tile, what no mask enters: the tile's distinct common
+ * rows under complement with a weight each, and how many of its singleton sites every haplotype carries.  Launches then read
+ * the digest in place of the rows and the singleton stream, and bytes_streamed counts that.  Taken by default where the plan
+ * runs one wave per tile, every tile fits the digest's caps and a launch reads no more bytes than without; never for the
+ * one-shot impop_scan.  IMPOP_SCAN_DIGEST=0|1 where the plan is made: never / whenever the caps allow.  Records are the same
+ * bytes either way.  on: 0|1; n_rows: representatives over all tiles; n_hist_tiles: tiles with a histogram; digest_bytes: device
+ * memory the digest holds; why: the reason there is none, else "".  Every pointer may be NULL. */
+int impop_scan_plan_digest_info(const impop_scan_plan *plan, int *on, uint64_t *n_rows, uint64_t *n_hist_tiles, uint64_t *digest_bytes,
+                                char *why, size_t why_len);
 /* Measurement aid: with timing enabled every launch brackets the streaming kernel
  * (not the tiny epilogue) with hipEvents on the context's stream; elapsed() synchronises
  * and returns the summed kernel time and the number of launches since enable/reset. */

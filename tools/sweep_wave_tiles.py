@@ -34,6 +34,7 @@ def main():
     ap.add_argument("--tile-blocks", type=int, default=0, help="0: the default tile; else the plans' tile_blocks (larger tiles)")
     a = ap.parse_args()
     import impop_amd
+    os.environ["IMPOP_SCAN_DIGEST"] = "0"  # the two bodies on the streams: a kept plan on one wave would otherwise take a tile digest
     ctx = impop_amd.Context(0)
     n = a.n_hap
     bm = ctx.synthetic(n, a.sites, seed=20251031)
