@@ -132,11 +132,17 @@ int on_side_stream(impop_ctx *ctx, const std::function<int()> &body) {
     return IMPOP_OK;
 }
 
+int fill_tajima_consts(impop_ctx *ctx, int64_t n, double *d_out) {
+    hipLaunchKernelGGL(tajima_consts_kernel, dim3(1), dim3(64), 0, ctx->stream, n, d_out);
+    HIP_TRY(hipGetLastError());
+    return IMPOP_OK;
+}
+
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n) {
     if (!ctx->d_taj) HIP_TRY(hipMalloc(&ctx->d_taj, 8 * sizeof(double)));
     if (ctx->taj_n != n) {
-        hipLaunchKernelGGL(tajima_consts_kernel, dim3(1), dim3(64), 0, ctx->stream, n, ctx->d_taj);
-        HIP_TRY(hipGetLastError());
+        const int rc = fill_tajima_consts(ctx, n, ctx->d_taj);
+        if (rc) return rc;
         ctx->taj_n = n;
     }
     return IMPOP_OK;

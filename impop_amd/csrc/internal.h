@@ -148,7 +148,8 @@ struct impop_ctx {
     bool own_stream = false;
     char arch[128] = {0};
     int n_cu = 0;
-    // cached Tajima constants on the device, keyed by n (8 doubles: a1,a2,b1,b2,c1,c2,e1,e2)
+    // cached Tajima constants on the device, keyed by n (8 doubles: a1,a2,b1,b2,c1,c2,e1,e2): for the all-pairs calls, which
+    // synchronise before they return.  Scan plans own their constants (impop_scan_plan::d_taj)
     double *d_taj = nullptr;
     int64_t taj_n = -1;
     uint32_t *d_queue = nullptr;  // 8 task-queue heads of the persistent Gram kernel
@@ -336,6 +337,9 @@ inline uint32_t ones_weight(const impop_matrix *m, uint64_t s0, uint64_t s1) {
 }
 inline bool compact_weighted(const impop_matrix *m) { return m->compact && !m->ones_wt_prefix.empty(); }
 int ensure_tajima_consts(impop_ctx *ctx, int64_t n);  // fills ctx->d_taj for n (device kernel)
+// the same kernel into a slot of the caller's (8 doubles), on the context's stream: a scan plan's own constants, which no other
+// plan or call on the context retargets (a captured launch reads its slot at replay time)
+int fill_tajima_consts(impop_ctx *ctx, int64_t n, double *d_out);
 // scan.hip: impop_scan_plan_create for the library's own calls.  reusable = false: the plan is launched once, and the default
 // rule leaves it without a tile digest (tile_digest.h: a plan launched once must not pay for the build)
 int scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,

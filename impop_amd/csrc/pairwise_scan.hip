@@ -330,7 +330,7 @@ struct PairwiseStatsEpilogue final : PairEpilogue {
         if (rc) return rc;
         HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
         PairFinalIn in{d_p, d_h, c.d_s};
-        rc = ensure_tajima_consts(ctx, nP >= 2 ? (int64_t)nP : 2);  // the cache may have been retargeted by another plan
+        rc = ensure_tajima_consts(ctx, nP >= 2 ? (int64_t)nP : 2);  // the cache may have been retargeted by another call
         if (rc) return rc;
         hipLaunchKernelGGL(pairwise_finalize_kernel, dim3((uint32_t)((cnt + 63) / 64)), dim3(64), 0, ctx->stream, in, cnt,
                            want_s ? nP : 0u, params->d_pi_mode, want_s ? params->s_scope : 0, ctx->d_taj, rec.d);

@@ -1005,6 +1005,11 @@ struct impop_scan_plan {
     WinDesc *d_wins = nullptr;
     TilePartial *d_parts = nullptr;
     uint32_t *d_masks = nullptr;
+    // Tajima's constants for the plan's nP (8 doubles, tajima_consts_kernel), the plan's own: written at creation and by a
+    // set_masks that changes nP, read by every finalize launch.  A launch touches no state of the context, so one captured
+    // at any moment replays right whatever other plans and calls of the context did in between
+    double *d_taj = nullptr;
+    int64_t taj_n = -1;  // the n d_taj holds, or was last queued to hold
     impop_window_stats *d_out = nullptr;
     bool timing = false;
     EventPairs timer;  // one pair per timed launch of the streaming kernel
@@ -1062,6 +1067,16 @@ static void plan_set_masks(impop_scan_plan *p, const uint64_t *mask_p, const uin
     p->masks.insert(p->masks.end(), mp.begin(), mp.end());
     p->masks.insert(p->masks.end(), ma.begin(), ma.end());
     p->masks.insert(p->masks.end(), mb.begin(), mb.end());
+}
+
+// queues the constants of the plan's nP into its own slot on the context's stream, where the slot holds another n's
+static int plan_fill_tajima(impop_scan_plan *p) {
+    const int64_t n = p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2;
+    if (p->taj_n == n) return IMPOP_OK;
+    const int rc = fill_tajima_consts(p->ctx, n, p->d_taj);
+    if (rc) return rc;
+    p->taj_n = n;
+    return IMPOP_OK;
 }
 
 // IMPOP_TRACE=1: one line per plan (and per impop_scan_multi) with the route it streams; tests read it.  kept_sites = every
@@ -1468,6 +1483,8 @@ int impop::scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_w
     PLAN_TRY(hipMalloc((void **)&p->d_wins, std::max<size_t>(n_windows, 1) * sizeof(WinDesc)));
     PLAN_TRY(hipMalloc((void **)&p->d_out, std::max<size_t>(n_windows, 1) * sizeof(impop_window_stats)));
     PLAN_TRY(hipMalloc((void **)&p->d_masks, (size_t)3 * wps * 4));
+    PLAN_TRY(hipMalloc((void **)&p->d_taj, 8 * sizeof(double)));
+    if ((rc = plan_fill_tajima(p))) return fail(rc);
     if (rt.packed) {
         PLAN_TRY(hipMalloc((void **)&p->d_singles, std::max<size_t>(rt.singles.size(), 1) * sizeof(SingleRange)));
         if (!rt.singles.empty()) PLAN_TRY(hipMemcpyAsync(p->d_singles, rt.singles.data(), rt.singles.size() * sizeof(SingleRange), hipMemcpyHostToDevice, ctx->stream));
@@ -1485,8 +1502,6 @@ int impop::scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_w
     trace_route(m, rt, n_windows);
     PLAN_TRY(hipStreamSynchronize(ctx->stream));  // host vectors die at return
 #undef PLAN_TRY
-    rc = ensure_tajima_consts(ctx, p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2);
-    if (rc) return fail(rc);
     *out = p;
     return IMPOP_OK;
 }
@@ -1499,7 +1514,9 @@ IMPOP_API int impop_scan_plan_set_masks(impop_scan_plan *p, const uint64_t *mask
     // the device copy is only rewritten behind them in stream order
     plan_set_masks(p, mask_p, mask_a, mask_b);
     HIP_TRY(hipMemcpyAsync(p->d_masks, p->masks.data(), p->masks.size() * 4, hipMemcpyHostToDevice, p->ctx->stream));
-    return IMPOP_OK;
+    // ... and so are the plan's Tajima constants where nP changed.  A graph captured before holds the previous subset sizes
+    // and kernel choice as arguments of its launches: capture again after this call
+    return plan_fill_tajima(p);
 }
 
 IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
@@ -1508,9 +1525,9 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
     hipStream_t st = ctx->stream;
     // one process may drive several devices (impop_scan_sharded): kernels go to the device the plan's stream lives on
     HIP_TRY(hipSetDevice(ctx->device));
-    // the cached Tajima constants belong to the context; another plan may have changed n since
-    int rc = ensure_tajima_consts(ctx, p->ps.nP >= 2 ? (int64_t)p->ps.nP : 2);
-    if (rc) return rc;
+    // exactly the two kernels below, on the plan's own buffers (its Tajima constants too: p->d_taj): nothing of the context
+    // is read or written, so what a capture records and what its replay runs cannot disagree
+    int rc = IMPOP_OK;
     const bool timed = p->timing && p->n_tiles;
     size_t slot = 0;
     if (timed && (rc = p->timer.begin(st, &slot))) return rc;
@@ -1539,13 +1556,13 @@ IMPOP_API int impop_scan_plan_launch(impop_scan_plan *p, void *d_out) {
         impop_window_stats *dst = d_out ? (impop_window_stats *)d_out : p->d_out;
         if (p->finalize_tpw == 1)
             hipLaunchKernelGGL(scan_finalize_kernel<1>, dim3((uint32_t)((p->n_windows + 127) / 128)), dim3(128), 0, st, p->d_parts,
-                               p->d_wins, p->n_windows, p->ps, ctx->d_taj, p->d_pi_mode, p->s_scope, dst);
+                               p->d_wins, p->n_windows, p->ps, p->d_taj, p->d_pi_mode, p->s_scope, dst);
         else if (p->finalize_tpw == 64)
             hipLaunchKernelGGL(scan_finalize_kernel<64>, dim3((uint32_t)((p->n_windows + 3) / 4)), dim3(256), 0, st, p->d_parts,
-                               p->d_wins, p->n_windows, p->ps, ctx->d_taj, p->d_pi_mode, p->s_scope, dst);
+                               p->d_wins, p->n_windows, p->ps, p->d_taj, p->d_pi_mode, p->s_scope, dst);
         else
             hipLaunchKernelGGL(scan_finalize_kernel<256>, dim3((uint32_t)p->n_windows), dim3(256), 0, st, p->d_parts,
-                               p->d_wins, p->n_windows, p->ps, ctx->d_taj, p->d_pi_mode, p->s_scope, dst);
+                               p->d_wins, p->n_windows, p->ps, p->d_taj, p->d_pi_mode, p->s_scope, dst);
         HIP_TRY(hipGetLastError());
     }
     return IMPOP_OK;
@@ -1620,6 +1637,7 @@ IMPOP_API int impop_scan_plan_destroy(impop_scan_plan *p) {
     if (p->d_wins) hipFree(p->d_wins);
     if (p->d_out) hipFree(p->d_out);
     if (p->d_masks) hipFree(p->d_masks);
+    if (p->d_taj) hipFree(p->d_taj);
     if (p->d_singles) hipFree(p->d_singles);
     if (p->d_uniqs) hipFree(p->d_uniqs);
     if (p->d_digest) hipFree(p->d_digest);

@@ -241,12 +241,18 @@ int impop_scan_plan_create(impop_ctx *ctx, const impop_matrix *m, const impop_wi
                            const uint64_t *mask_p, const uint64_t *mask_a, const uint64_t *mask_b,
                            const impop_scan_params *params, impop_scan_plan **out);
 /* Replace the three subset masks of an existing plan (the tile tables depend on the windows only), e.g.
- * to scan the same windows for many population pairs; takes effect for launches issued afterwards. */
+ * to scan the same windows for many population pairs; takes effect for launches issued afterwards.
+ * A launch captured into a graph BEFORE this call keeps the subset sizes and kernel choice it was
+ * captured with: after impop_scan_plan_set_masks, capture again. */
 int impop_scan_plan_set_masks(impop_scan_plan *plan, const uint64_t *mask_p, const uint64_t *mask_a,
                               const uint64_t *mask_b);
 /* Enqueue one pass over all windows on the context's stream (no host sync, no
  * allocation: graph-capturable).  d_out: device buffer of n_windows records, or
- * NULL to use the plan's internal buffer. */
+ * NULL to use the plan's internal buffer.
+ * A launch is two kernels on buffers the plan owns (its Tajima constants among them) and touches no
+ * state of the context.  A captured launch is a snapshot of the plan's kernel choice and subset sizes;
+ * any number of plans, and of graphs captured from them, may share a context and be launched, replayed
+ * and mixed with every other call on it in any order. */
 int impop_scan_plan_launch(impop_scan_plan *plan, void *d_out);
 /* Synchronise and copy the plan's internal result buffer to the host. */
 int impop_scan_plan_fetch(impop_scan_plan *plan, impop_window_stats *out_host);

@@ -177,7 +177,7 @@ def test_graph_replay():
     assert pl.digest_info()["on"]
     pl.launch()
     assert pl.fetch().tobytes() == want1.tobytes()
-    pl.set_masks(P, A2, B2)  # same P: the context's Tajima constants stay as they are, the capture holds the two kernels only
+    pl.set_masks(P, A2, B2)  # a plan owns its Tajima constants: a capture holds the two kernels only, whatever P (test_gpu_scan_shared_context.py)
     c.synchronize()
     assert hip.hipStreamBeginCapture(stream, 0) == 0  # hipStreamCaptureModeGlobal
     pl.launch()

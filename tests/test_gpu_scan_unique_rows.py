@@ -347,7 +347,7 @@ def test_graph_replay():
     pl = bm.plan(LISTS["nested"], P, A, B, tile_blocks=2)  # tiles that read the stream
     pl.launch()
     direct1 = pl.fetch()
-    pl.set_masks(P, A2, B2)  # same P: the context's Tajima constants stay as they are, the capture holds the two kernels only
+    pl.set_masks(P, A2, B2)  # a plan owns its Tajima constants: a capture holds the two kernels only, whatever P (test_gpu_scan_shared_context.py)
     pl.launch()
     direct2 = pl.fetch()
     assert direct1.tobytes() != direct2.tobytes()
