@@ -204,6 +204,24 @@ class LdStats(C.Structure):
                 ("omega_max", C.c_double)]
 
 
+class RecombParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_mac", C.c_uint32), ("max_sites", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class RecombStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("n_qualifying", C.c_uint32), ("n_used", C.c_uint32),
+                ("rmin", C.c_uint32), ("n_incompatible_adjacent", C.c_uint32), ("n_blocks", C.c_uint32),
+                ("longest_block_sites", C.c_uint32), ("n_congruent_adjacent", C.c_uint32), ("n_congruent_partitions", C.c_uint32),
+                ("n_partitions", C.c_uint32), ("reserved", C.c_uint32), ("n_incompatible", C.c_uint64),
+                ("longest_block_begin", C.c_uint64), ("longest_block_end", C.c_uint64), ("four_gamete_fraction", C.c_double),
+                ("wall_b", C.c_double), ("wall_q", C.c_double)]
+
+
+class RecombSite(C.Structure):
+    _fields_ = [("left1", C.c_uint32), ("n_left", C.c_uint32), ("rep", C.c_uint32), ("carriers", C.c_uint32)]
+
+
 class DiploidParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_run", C.c_uint32), ("max_chunk_bytes", C.c_uint64)]
 
@@ -333,6 +351,8 @@ assert C.sizeof(EhhStats) == 64 and C.sizeof(EhhParams) == 24 and C.sizeof(EhhWi
 assert C.sizeof(HaplotypeStats) == 64 and C.sizeof(HaplotypeParams) == 16
 assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
 LD_MAX_N, LD_MAX_SITES = 4096, 1024
+assert C.sizeof(RecombStats) == 96 and C.sizeof(RecombParams) == 24 and C.sizeof(RecombSite) == 16
+RECOMB_MAX_N, RECOMB_MAX_SITES = 4096, 16384  # IMPOP_RECOMB_MAX_N, IMPOP_RECOMB_MAX_SITES
 assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(DiploidParams) == 16
 DIPLOID_MAX_N = 2048
 assert C.sizeof(IbsParams) == 32 and C.sizeof(IbsPair) == 32 and C.sizeof(IbsSegment) == 32 and C.sizeof(IbsWindow) == 32
@@ -448,6 +468,9 @@ SIGNATURES = {
     "impop_ctx_haplotype_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_ld_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(LdParams), C.POINTER(LdStats), _u64p]),
     "impop_ctx_ld_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_recomb_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(RecombParams), C.POINTER(RecombStats), _u64p,
+                                    C.POINTER(RecombSite)]),
+    "impop_ctx_recomb_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_diploid_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u32p, C.c_uint32, C.POINTER(DiploidParams),
                                      C.POINTER(DiploidStats), C.POINTER(DiploidInd)]),
     "impop_ctx_diploid_elapsed": (C.c_int, [_vp, _f64p, _u64p]),

@@ -4,11 +4,9 @@
 // Windows are mapped straight onto d_sb, which holds every row of the matrix whatever index was built beside it (a compacted
 // matrix: onto its kept sites; the dropped ones are monomorphic and never qualify), so a record cannot depend on the upload's
 // keep flags.  Per chunk of windows, three launches:
-//   1. ld_select_kernel  one wave per 64-site block of a window: c = carriers among P of the lane's site, the ballot of
-//                        min(c, |P| - c) >= min_mac over the window's sites -> one 64-bit qualifying mask per block.
-//   2. ld_gather_kernel  one workgroup per window: q = the masks' popcount, a running prefix over the blocks ranks every
-//                        qualifying site, the sites of rank floor(k q / m) are kept; their rows ANDed with P, their c and their
-//                        original coordinate go to the chunk's scratch at [window][k].
+//   1. ld_select_kernel  the qualifying mask of every 64-site block of a window            (ld_select.h, shared with recomb.hip)
+//   2. ld_gather_kernel  the used sites' rows ANDed with P, their c and their original coordinate go to the chunk's scratch at
+//                        [window][k]                                                            (ld_select.h)
 //   3. ld_pairs_kernel   one workgroup per window: the lane that owns site t runs k = 0..m-1 over broadcast rows and adds r2 into
 //                        a_t while k < t and into b_t while k > t, |D'| into dp_t while k < t — every pair is evaluated twice and
 //                        nothing is accumulated across lanes, so the doubles do not depend on scheduling.  One lane then runs the
@@ -21,116 +19,17 @@
 
 #include "device_utils.h"
 #include "internal.h"
+#include "ld_select.h"
 #include "sb64.h"
 #include "scan_route.h"
 #include "win_chunks.h"
 
 namespace impop {
 
-constexpr int LD_T = 256;  // threads of every workgroup here
 // the used rows of a window are staged in LDS up to this many bytes (465 haplotypes x 512 sites: 32 KB); else read from scratch
 constexpr size_t LD_LDS_ROW_BYTES = 64 * 1024;
 static_assert(IMPOP_LD_MAX_N <= 4096u, "num^2 and den stay below 2^53 only for n <= 4096");
-
-struct LdWin {          // a window of a chunk
-    uint64_t s0, s1;    // its sites in d_sb
-    uint64_t blk_off;   // its first qualifying mask in the chunk's mask array
-    uint32_t n_sites, pad;  // W
-};
-
-// grid = (windows of the chunk, slices of a window's blocks)
-__global__ __launch_bounds__(LD_T) void ld_select_kernel(const uint32_t *__restrict__ sb, const LdWin *__restrict__ wins, uint32_t wps,
-                                                         uint32_t G, uint32_t r, const uint32_t *__restrict__ pbits, uint32_t nP,
-                                                         uint32_t min_mac, uint64_t *__restrict__ qmask) {
-    const uint32_t lane = threadIdx.x & 63, wave = (uint32_t)__builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const LdWin w = wins[blockIdx.x];
-    if (w.s1 <= w.s0) return;
-    const uint64_t b0 = w.s0 >> 6, b1 = (w.s1 + 63) >> 6;
-    for (uint64_t b = b0 + (uint64_t)blockIdx.y * 4 + wave; b < b1; b += 4ull * gridDim.y) {
-        uint32_t c = 0;
-        sb_for_each_dword<true>(sb + b * 64ull * wps, G, r, lane, [&](uint32_t k, uint32_t d) { c += __popc(d & pbits[k]); });
-        const uint64_t site = b * 64 + lane;
-        const uint32_t mac = c < nP - c ? c : nP - c;
-        const uint64_t mask = __ballot(site >= w.s0 && site < w.s1 && mac >= min_mac);
-        if (lane == 0) qmask[w.blk_off + (b - b0)] = mask;
-    }
-}
-
-// grid = windows of the chunk.  qm[2 w] = q, qm[2 w + 1] = m.
-__global__ __launch_bounds__(LD_T) void ld_gather_kernel(const uint32_t *__restrict__ sb, const LdWin *__restrict__ wins, uint32_t wps,
-                                                         uint32_t G, uint32_t r, const uint32_t *__restrict__ pbits,
-                                                         const uint64_t *__restrict__ pos, uint32_t max_sites,
-                                                         const uint64_t *__restrict__ qmask, uint32_t *__restrict__ rows,
-                                                         uint32_t *__restrict__ cs, uint64_t *__restrict__ coords, uint32_t *__restrict__ qm,
-                                                         uint32_t *__restrict__ err) {
-    __shared__ uint64_t s_site[IMPOP_LD_MAX_SITES];
-    __shared__ uint32_t s_scan[LD_T];
-    __shared__ uint32_t s_q, s_base, s_placed;
-    const uint32_t tid = threadIdx.x;
-    const LdWin w = wins[blockIdx.x];
-    const uint64_t b0 = w.s0 >> 6, nb = w.s1 > w.s0 ? ((w.s1 + 63) >> 6) - b0 : 0;
-    const uint64_t *qw = qmask + w.blk_off;
-    if (tid == 0) {
-        s_q = 0;
-        s_base = 0;
-        s_placed = 0;
-    }
-    for (uint32_t k = tid; k < max_sites; k += LD_T) s_site[k] = w.s0;  // a site that can be read, whatever goes wrong below
-    __syncthreads();
-    uint32_t mine = 0;
-    for (uint64_t i = tid; i < nb; i += LD_T) mine += (uint32_t)__popcll(qw[i]);
-    if (mine) atomicAdd(&s_q, mine);
-    __syncthreads();
-    const uint64_t q = s_q, m = q < max_sites ? q : max_sites;
-    // ranks: blocks LD_T at a time, an exclusive scan of their counts on top of the running base
-    for (uint64_t i0 = 0; i0 < nb && m; i0 += LD_T) {
-        const uint64_t i = i0 + tid;
-        uint64_t mask = i < nb ? qw[i] : 0ull;
-        const uint32_t c = (uint32_t)__popcll(mask);
-        s_scan[tid] = c;
-        __syncthreads();
-        for (uint32_t off = 1; off < LD_T; off <<= 1) {
-            const uint32_t v = tid >= off ? s_scan[tid - off] : 0u;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        uint64_t rank = (uint64_t)s_base + s_scan[tid] - c;
-        uint32_t placed = 0;
-        for (; mask; mask &= mask - 1, ++rank) {
-            // rank is used iff some k < m has floor(k q / m) == rank; q >= m: at most one, the smallest k >= rank m / q
-            const uint64_t k = (rank * m + q - 1) / q;
-            if (k < m && k * q / m == rank) {
-                s_site[k] = (b0 + i) * 64 + (uint64_t)__builtin_ctzll(mask);
-                ++placed;
-            }
-        }
-        if (placed) atomicAdd(&s_placed, placed);
-        __syncthreads();
-        if (tid == LD_T - 1) s_base += s_scan[tid];
-        __syncthreads();
-    }
-    __syncthreads();
-    const uint64_t o = (uint64_t)blockIdx.x * max_sites;
-    for (uint32_t k = tid; k < max_sites; k += LD_T) coords[o + k] = k < m ? (pos ? pos[s_site[k]] : s_site[k]) : 0ull;
-    uint32_t *dst = rows + o * wps;
-    for (uint64_t idx = tid; idx < m * wps; idx += LD_T) {
-        const uint32_t k = (uint32_t)(idx / wps), j = (uint32_t)(idx % wps);
-        const uint64_t s = s_site[k];
-        dst[idx] = sb[sb_index(wps, G, r, s >> 6, (uint32_t)(s & 63), j)] & pbits[j];
-    }
-    __syncthreads();  // the rows this workgroup wrote are read back below
-    for (uint32_t k = tid; k < m; k += LD_T) {
-        uint32_t c = 0;
-        for (uint32_t j = 0; j < wps; ++j) c += __popc(dst[(uint64_t)k * wps + j]);
-        cs[o + k] = c;
-    }
-    if (tid == 0) {
-        qm[2 * blockIdx.x] = (uint32_t)q;
-        qm[2 * blockIdx.x + 1] = (uint32_t)m;
-        if (s_placed != m) atomicOr(err, DEV_ERR_LDSCAN);
-    }
-}
+static_assert(IMPOP_LD_MAX_SITES <= LD_GATHER_LDS_SITES, "the gather keeps this call's site list in LDS");
 
 // grid = windows of the chunk.  Dynamic LDS: a, b, dp (8 max_sites each) | c (4 max_sites) | 4 counters | LDS_ROWS: the rows,
 // one every wps | 1 dwords (an odd stride: the lanes' own rows fall on different banks).
@@ -241,7 +140,7 @@ using namespace impop;
 
 IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,
                             const impop_ld_params *params, impop_ld_stats *out_host, uint64_t *used_sites) {
-    static_assert(sizeof(impop_ld_stats) == 72 && sizeof(impop_ld_params) == 24 && sizeof(LdWin) == 32, "ABI layout");
+    static_assert(sizeof(impop_ld_stats) == 72 && sizeof(impop_ld_params) == 24 && sizeof(LdWin) == 40, "ABI layout");
     const char *fn = "impop_ld_scan";
     REQUIRE(ctx && m && params, "%s: NULL argument", fn);
     REQUIRE(params->struct_size == sizeof(impop_ld_params), "impop_ld_params.struct_size mismatch");
@@ -271,7 +170,7 @@ IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_w
     uint64_t bytes_streamed = 0;
     for (uint64_t i = 0; i < n_windows; ++i) {
         const uint64_t s0 = mapped[i].site_begin, s1 = mapped[i].site_end;
-        nb[i] = s1 > s0 ? ((s1 + 63) >> 6) - (s0 >> 6) : 0;
+        nb[i] = ld_blocks(s0, s1);
         bytes_streamed += nb[i] * 256ull * wps;
     }
     const std::vector<WinChunk> chunks =
@@ -320,19 +219,21 @@ IMPOP_API int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_w
         uint64_t n_blocks = 0, longest = 0;  // blocks of all the chunk's windows / of its longest one
         for (size_t k = 0; k < cnt; ++k) {
             const uint64_t i = c.w_begin + k;
-            h_wins[k] = LdWin{mapped[i].site_begin, mapped[i].site_end, n_blocks, (uint32_t)window_W(m, windows[i].site_begin, windows[i].site_end), 0u};
+            h_wins[k] = LdWin{mapped[i].site_begin, mapped[i].site_end, n_blocks, (uint64_t)k * max_sites,
+                              (uint32_t)window_W(m, windows[i].site_begin, windows[i].site_end), max_sites};
             n_blocks += nb[i];
             longest = std::max(longest, nb[i]);
         }
         if ((rc = run.up(o_wins, o_wins + cnt * sizeof(LdWin)))) return rc;
-        const uint32_t slices = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((longest + 63) / 64, 1), 1024);
+        const uint32_t slices = ld_select_slices(longest);
         if ((rc = run.timed(timer[0], [&] {
             hipLaunchKernelGGL(ld_select_kernel, dim3((uint32_t)cnt, slices), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r,
                                d_pbits, nP, params->min_mac, d_qmask);
         }))) return rc;
         if ((rc = run.timed(timer[1], [&] {
             hipLaunchKernelGGL(ld_gather_kernel, dim3((uint32_t)cnt), dim3(LD_T), 0, ctx->stream, m->d_sb, d_wins, wps, m->g.G, m->g.r, d_pbits,
-                               m->compact ? m->d_pos : nullptr, max_sites, d_qmask, d_rows, d_cs, d_coords, d_qm, ctx->d_err);
+                               m->compact ? m->d_pos : nullptr, max_sites, d_qmask, d_rows, d_cs, d_coords, d_qm, nullptr, ctx->d_err,
+                               DEV_ERR_LDSCAN);
         }))) return rc;
         if ((rc = run.timed(timer[2], [&] {
             if (rows_in_lds)

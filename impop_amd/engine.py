@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, RecombParams, RecombStats, RecombSite, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 from .ihs import IHS_DTYPE  # noqa: E402
 
@@ -46,6 +46,13 @@ LD_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_qualifying", 
                      ("n_complete", "<u4"), ("omega_split", "<u4"), ("reserved", "<u4"), ("sum_r2", "<f8"), ("sum_dprime", "<f8"),
                      ("zns", "<f8"), ("mean_dprime", "<f8"), ("omega_max", "<f8")])
 assert LD_DTYPE.itemsize == 72
+RECOMB_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_qualifying", "<u4"), ("n_used", "<u4"), ("rmin", "<u4"),
+                         ("n_incompatible_adjacent", "<u4"), ("n_blocks", "<u4"), ("longest_block_sites", "<u4"),
+                         ("n_congruent_adjacent", "<u4"), ("n_congruent_partitions", "<u4"), ("n_partitions", "<u4"), ("reserved", "<u4"),
+                         ("n_incompatible", "<u8"), ("longest_block_begin", "<u8"), ("longest_block_end", "<u8"),
+                         ("four_gamete_fraction", "<f8"), ("wall_b", "<f8"), ("wall_q", "<f8")])
+RECOMB_SITE_DTYPE = np.dtype([("left1", "<u4"), ("n_left", "<u4"), ("rep", "<u4"), ("carriers", "<u4")])
+assert RECOMB_DTYPE.itemsize == 96 and RECOMB_SITE_DTYPE.itemsize == 16
 DIPLOID_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("s_p", "<u4"), ("het_sites", "<u4"), ("het_total", "<u8"), ("sum_p", "<u8"),
                           ("roh_sites_total", "<u8"), ("roh_runs_total", "<u4"), ("longest_run", "<u4"), ("ho", "<f8"), ("he", "<f8"),
                           ("f_is", "<f8"), ("f_roh", "<f8")])
@@ -295,6 +302,12 @@ class Context:
         """-> ([select, gather, pairs] kernel ms of ld_scan, chunks) since gram_timing(True)"""
         t, k = (C.c_double * 3)(), C.c_uint64()
         check(self._lib.impop_ctx_ld_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def recomb_elapsed(self):
+        """-> ([select, gather, pairs, finish] kernel ms of recomb_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 4)(), C.c_uint64()
+        check(self._lib.impop_ctx_recomb_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def diploid_elapsed(self):
@@ -916,6 +929,27 @@ class BitMatrix:
                                           out.ctypes.data_as(C.POINTER(LdStats)),
                                           sites.ctypes.data_as(C.POINTER(C.c_uint64)) if want_sites else None))
         return (out, sites) if want_sites else out
+
+    def recomb_scan(self, windows, mask_p=None, min_mac: int = 2, max_sites: int = 4096, want_sites: bool = False,
+                    want_site_table: bool = False, max_chunk_bytes: int = 0):
+        """Recombination per window (impop_recomb_scan): among the members of mask_p, the sites with minor-allele count >= min_mac,
+        thinned evenly to at most max_sites, the four-gamete test over all their pairs.  -> records (RECOMB_DTYPE: Hudson-Kaplan
+        R_min, incompatible pairs, four-gamete blocks, Wall's B and Q), then with want_sites used_sites [n_windows, max_sites]
+        uint64 (original coordinates), then with want_site_table the per-site rows [n_windows, max_sites] (RECOMB_SITE_DTYPE:
+        left1, n_left, rep, carriers); the first n_used entries of a row are valid, the rest 0."""
+        w = make_windows(windows)
+        out = np.zeros(len(w), dtype=RECOMB_DTYPE)
+        prm = RecombParams(C.sizeof(RecombParams), int(min_mac), int(max_sites), 0, int(max_chunk_bytes))
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        cols = int(max_sites) if max_sites else 4096
+        sites = np.zeros((len(w), cols), dtype=np.uint64) if want_sites else None
+        table = np.zeros((len(w), cols), dtype=RECOMB_SITE_DTYPE) if want_site_table else None
+        check(self.ctx._lib.impop_recomb_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, C.byref(prm),
+                                              out.ctypes.data_as(C.POINTER(RecombStats)),
+                                              sites.ctypes.data_as(C.POINTER(C.c_uint64)) if want_sites else None,
+                                              table.ctypes.data_as(C.POINTER(RecombSite)) if want_site_table else None))
+        res = (out,) + ((sites,) if want_sites else ()) + ((table,) if want_site_table else ())
+        return res if len(res) > 1 else out
 
     def diploid_scan(self, windows, pairs, min_run: int, want_individuals: bool = False, max_chunk_bytes: int = 0):
         """The individual level of a windowed scan (impop_diploid_scan): pairs = [N, 2] haplotype indices, the two copies of each

@@ -933,6 +933,72 @@ int impop_ld_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *win
 /* With impop_ctx_gram_timing on, impop_ld_scan brackets its kernels per chunk: kernel_ms[0] = select, [1] = gather, [2] = pairs,
  * summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_ld_elapsed(impop_ctx *ctx, double kernel_ms[3], uint64_t *chunks);
+#define IMPOP_RECOMB_MAX_N     4096u
+#define IMPOP_RECOMB_MAX_SITES 16384u
+/* Recombination per window under the infinite-sites model: the four-gamete test over all site pairs, Hudson & Kaplan's (1985)
+ * lower bound R_min with its breakpoint intervals, four-gamete haplotype blocks (Wang et al. 2002) and Wall's (1999) B and Q, from
+ * the site-major rows alone (works on full, weighted and compacted matrices; site weights change n_sites only).  Every device
+ * output is an integer; the three doubles are one host operation each on those integers.
+ * Members: P (mask_p; NULL = all), n = |P|.  Site selection is impop_ld_scan's rule: a site qualifies iff min(c, n - c) >= min_mac;
+ * the qualifying sites are ranked by position 0..q-1 and with m = min(q, max_sites) the site of rank floor(k q / m) is used,
+ * k = 0..m-1.  max_sites 0 means 4096; 2 .. IMPOP_RECOMB_MAX_SITES.  n_qualifying = q, n_used = m.  Thinning drops sites, never
+ * adds an incompatible pair, so the R_min of a thinned window is still a valid lower bound on its recombination events.
+ * Pair relations, used sites indexed 0..m-1 in position order, rows masked by P, for sites s and t:
+ *     n11 = popcount(row_s & row_t)   n10 = c_s - n11   n01 = c_t - n11   n00 = n - c_s - c_t + n11
+ *     incompatible(s,t) iff all four are > 0
+ *     congruent(s,t)    iff (n10 == 0 && n01 == 0) || (n11 == 0 && n00 == 0): the same bipartition of P, so stored polarity is
+ *                       irrelevant
+ * Per site j (site_table, nullable, n_windows x max_sites):
+ *     left1_j = 1 + max{ i < j : incompatible(i,j) }, 0 if there is none       n_left_j = #{ i < j : incompatible(i,j) }
+ *     rep_j = min{ i <= j : congruent(i,j) }                                   carriers = c_j
+ * Per window:
+ *     n_incompatible = sum_j n_left_j        n_incompatible_adjacent = #{ j >= 1 : left1_j == j }
+ *     rmin: cut = 0, r = 0; for j ascending: if left1_j >= 1 && left1_j - 1 >= cut then ++r, cut = j.  The chosen open intervals
+ *       are (left1_j - 1, j); intervals that share an end point are disjoint, as in Hudson & Kaplan 1985.  The greedy equals the
+ *       paper's deletion procedure and the maximum number of disjoint intervals among all incompatible pairs.
+ *     blocks (pairwise compatible runs): M_j = max_{k<=j} left1_k; the longest compatible run ending at j is M_j..j.
+ *       n_blocks = #{ j : j == m-1 or M_{j+1} > M_j } (the maximal runs); longest_block_sites = max_j (j - M_j + 1), ties to the
+ *       smallest j; longest_block_begin / _end = the ORIGINAL coordinates of its first and last site.  All 0 when m = 0.
+ *     Wall 1999: n_congruent_adjacent (B') = #{ j >= 1 : rep_j == rep_{j-1} }; n_partitions = #{ j : rep_j == j };
+ *       n_congruent_partitions (A) = the distinct rep values among the sites of at least one congruent adjacent pair.
+ *     four_gamete_fraction = n_incompatible / (m (m-1) / 2)   wall_b = B' / (m - 1)   wall_q = (B' + A) / m, each one IEEE
+ *       division of exact values on the host, NaN where the denominator is 0.
+ * Known answer: haplotypes h0..h3, five sites as rows over (h0,h1,h2,h3) 1100, 1010, 1100, 0011, 1000, min_mac 1, one window:
+ *     left1 0,1,2,2,0   n_left 0,1,1,1,0   rep 0,1,0,0,4   n_incompatible 3   n_incompatible_adjacent 2   rmin 2 with the
+ *     intervals (0,1) and (1,2)   n_blocks 3   longest block sites 2..4 (3)   B' 1   A 1   n_partitions 3   wall_b 0.25   wall_q 0.4
+ * used_sites (nullable, n_windows x max_sites with max_sites as resolved) receives the ORIGINAL coordinates of the used sites;
+ * entries of used_sites and site_table beyond n_used are 0.
+ * |P| = 0, min_mac = 0, max_sites outside 2..IMPOP_RECOMB_MAX_SITES or a window outside the matrix return IMPOP_E_INVALID,
+ * |P| > IMPOP_RECOMB_MAX_N IMPOP_E_UNSUPPORTED, all before anything is uploaded or launched; n_windows == 0 returns IMPOP_OK.
+ * Windows may overlap.  max_chunk_bytes (0 = 1 GiB) bounds the device memory of one chunk of windows; chunking, the upload's keep
+ * flags and compaction never change a record.  Checks the device error word like impop_ld_scan (set when a window's gathered rows
+ * are not its n_used, or when rmin exceeds the number of sites with left1 > 0).
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_recomb_scan] route=<dense|compact> windows= chunks= launches= qualifying= used= pair_tiles= bytes_streamed=
+ * pair_tiles = sum over the windows of ceil(n_used / 256), the tiles of sites the pair kernel worked on. */
+typedef struct impop_recomb_params {
+    uint32_t struct_size;
+    uint32_t min_mac;         /* >= 1 */
+    uint32_t max_sites;       /* 0 = 4096; 2 .. IMPOP_RECOMB_MAX_SITES */
+    uint32_t reserved;
+    uint64_t max_chunk_bytes; /* 0 = 1 GiB */
+} impop_recomb_params;
+typedef struct impop_recomb_stats { /* 96 bytes, fixed layout */
+    uint32_t n_members, n_sites, n_qualifying, n_used, rmin, n_incompatible_adjacent, n_blocks, longest_block_sites,
+        n_congruent_adjacent, n_congruent_partitions, n_partitions, reserved;
+    uint64_t n_incompatible, longest_block_begin, longest_block_end;
+    double four_gamete_fraction, wall_b, wall_q;
+} impop_recomb_stats;
+typedef struct impop_recomb_site { /* 16 bytes */
+    uint32_t left1, n_left, rep, carriers;
+} impop_recomb_site;
+int impop_recomb_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,
+                      const impop_recomb_params *params, impop_recomb_stats *out_host,
+                      uint64_t *used_sites /* nullable, n_windows x max_sites */,
+                      impop_recomb_site *site_table /* nullable, n_windows x max_sites */);
+/* With impop_ctx_gram_timing on, impop_recomb_scan brackets its kernels per chunk: kernel_ms[0] = select, [1] = gather, [2] = pairs,
+ * [3] = finish, summed since enable / reset; chunks = chunks timed. */
+int impop_ctx_recomb_elapsed(impop_ctx *ctx, double kernel_ms[4], uint64_t *chunks);
 #define IMPOP_DIPLOID_MAX_N 2048u
 /* The individual level of a windowed scan: observed heterozygosity, Wright's F_IS and runs of homozygosity per window and per
  * diploid individual, from the site-major rows alone (no hap-major operand, no Gram; works on full, weighted and compacted
