@@ -222,6 +222,27 @@ class RecombSite(C.Structure):
     _fields_ = [("left1", C.c_uint32), ("n_left", C.c_uint32), ("rep", C.c_uint32), ("carriers", C.c_uint32)]
 
 
+class LdbandParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("min_mac", C.c_uint32), ("band_sites", C.c_uint32), ("n_bins", C.c_uint32),
+                ("thr_num", C.c_uint32), ("thr_den", C.c_uint32), ("bin_width", C.c_uint64), ("max_dist", C.c_uint64),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class LdbandStats(C.Structure):
+    _fields_ = [("n_members", C.c_uint32), ("n_sites", C.c_uint32), ("n_qualifying", C.c_uint32), ("n_kept", C.c_uint32),
+                ("n_pairs", C.c_uint64), ("sum_r2_fx", C.c_uint64), ("n_strong", C.c_uint64), ("n_perfect", C.c_uint64),
+                ("site_off", C.c_uint64), ("mean_r2", C.c_double)]
+
+
+class LdbandBin(C.Structure):
+    _fields_ = [("pairs", C.c_uint64), ("sum_r2_fx", C.c_uint64), ("n_strong", C.c_uint64)]
+
+
+class LdbandSite(C.Structure):
+    _fields_ = [("coord", C.c_uint64), ("ld_score_fx", C.c_uint64), ("carriers", C.c_uint32), ("n_partners", C.c_uint32),
+                ("n_strong", C.c_uint32), ("kept", C.c_uint32)]
+
+
 class DiploidParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_run", C.c_uint32), ("max_chunk_bytes", C.c_uint64)]
 
@@ -353,6 +374,9 @@ assert C.sizeof(LdStats) == 72 and C.sizeof(LdParams) == 24
 LD_MAX_N, LD_MAX_SITES = 4096, 1024
 assert C.sizeof(RecombStats) == 96 and C.sizeof(RecombParams) == 24 and C.sizeof(RecombSite) == 16
 RECOMB_MAX_N, RECOMB_MAX_SITES = 4096, 16384  # IMPOP_RECOMB_MAX_N, IMPOP_RECOMB_MAX_SITES
+assert C.sizeof(LdbandStats) == 64 and C.sizeof(LdbandParams) == 48 and C.sizeof(LdbandBin) == 24 and C.sizeof(LdbandSite) == 32
+# IMPOP_LDBAND_MAX_N, IMPOP_LDBAND_MAX_BAND, IMPOP_LDBAND_MAX_BINS, IMPOP_LDBAND_FX_ONE
+LDBAND_MAX_N, LDBAND_MAX_BAND, LDBAND_MAX_BINS, LDBAND_FX_ONE = 4096, 1024, 4096, 1 << 30
 assert C.sizeof(DiploidStats) == 80 and C.sizeof(DiploidInd) == 24 and C.sizeof(DiploidParams) == 16
 DIPLOID_MAX_N = 2048
 assert C.sizeof(IbsParams) == 32 and C.sizeof(IbsPair) == 32 and C.sizeof(IbsSegment) == 32 and C.sizeof(IbsWindow) == 32
@@ -471,6 +495,9 @@ SIGNATURES = {
     "impop_recomb_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(RecombParams), C.POINTER(RecombStats), _u64p,
                                     C.POINTER(RecombSite)]),
     "impop_ctx_recomb_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_ldband_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u64p, C.POINTER(LdbandParams), C.POINTER(LdbandStats),
+                                    C.POINTER(LdbandBin), C.POINTER(LdbandSite), C.c_uint64, _u64p]),
+    "impop_ctx_ldband_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_diploid_scan": (C.c_int, [_vp, _vp, C.POINTER(Window), C.c_uint64, _u32p, C.c_uint32, C.POINTER(DiploidParams),
                                      C.POINTER(DiploidStats), C.POINTER(DiploidInd)]),
     "impop_ctx_diploid_elapsed": (C.c_int, [_vp, _f64p, _u64p]),

@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, RecombParams, RecombStats, RecombSite, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, RecombParams, RecombStats, RecombSite, LdbandParams, LdbandStats, LdbandBin, LdbandSite, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 from .ihs import IHS_DTYPE  # noqa: E402
 
@@ -53,6 +53,12 @@ RECOMB_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_qualifyin
                          ("four_gamete_fraction", "<f8"), ("wall_b", "<f8"), ("wall_q", "<f8")])
 RECOMB_SITE_DTYPE = np.dtype([("left1", "<u4"), ("n_left", "<u4"), ("rep", "<u4"), ("carriers", "<u4")])
 assert RECOMB_DTYPE.itemsize == 96 and RECOMB_SITE_DTYPE.itemsize == 16
+LDBAND_DTYPE = np.dtype([("n_members", "<u4"), ("n_sites", "<u4"), ("n_qualifying", "<u4"), ("n_kept", "<u4"), ("n_pairs", "<u8"),
+                         ("sum_r2_fx", "<u8"), ("n_strong", "<u8"), ("n_perfect", "<u8"), ("site_off", "<u8"), ("mean_r2", "<f8")])
+LDBAND_BIN_DTYPE = np.dtype([("pairs", "<u8"), ("sum_r2_fx", "<u8"), ("n_strong", "<u8")])
+LDBAND_SITE_DTYPE = np.dtype([("coord", "<u8"), ("ld_score_fx", "<u8"), ("carriers", "<u4"), ("n_partners", "<u4"), ("n_strong", "<u4"),
+                              ("kept", "<u4")])
+assert LDBAND_DTYPE.itemsize == 64 and LDBAND_BIN_DTYPE.itemsize == 24 and LDBAND_SITE_DTYPE.itemsize == 32
 DIPLOID_DTYPE = np.dtype([("n_ind", "<u4"), ("n_sites", "<u4"), ("s_p", "<u4"), ("het_sites", "<u4"), ("het_total", "<u8"), ("sum_p", "<u8"),
                           ("roh_sites_total", "<u8"), ("roh_runs_total", "<u4"), ("longest_run", "<u4"), ("ho", "<f8"), ("he", "<f8"),
                           ("f_is", "<f8"), ("f_roh", "<f8")])
@@ -302,6 +308,12 @@ class Context:
         """-> ([select, gather, pairs] kernel ms of ld_scan, chunks) since gram_timing(True)"""
         t, k = (C.c_double * 3)(), C.c_uint64()
         check(self._lib.impop_ctx_ld_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
+
+    def ldband_elapsed(self):
+        """-> ([select, rank + gather, pairs, prune, reduce] kernel ms of ldband_scan, chunks) since gram_timing(True)"""
+        t, k = (C.c_double * 5)(), C.c_uint64()
+        check(self._lib.impop_ctx_ldband_elapsed(self.handle, t, C.byref(k)))
         return list(t), k.value
 
     def recomb_elapsed(self):
@@ -949,6 +961,41 @@ class BitMatrix:
                                               sites.ctypes.data_as(C.POINTER(C.c_uint64)) if want_sites else None,
                                               table.ctypes.data_as(C.POINTER(RecombSite)) if want_site_table else None))
         res = (out,) + ((sites,) if want_sites else ()) + ((table,) if want_site_table else ())
+        return res if len(res) > 1 else out
+
+    def ldband_scan(self, windows, mask_p=None, min_mac: int = 2, band_sites: int = 256, max_dist: int = 0, bin_width: int = 1000,
+                    n_bins: int = 100, threshold=(1, 5), want_bins: bool = False, want_sites: bool = False, max_chunk_bytes: int = 0):
+        """Banded LD per window (impop_ldband_scan): among the members of mask_p, every site with minor-allele count >= min_mac (no
+        thinning) against its next band_sites such sites, no further than max_dist apart (0: no limit).  -> records (LDBAND_DTYPE:
+        pairs, the fixed-point sum of r2, strong and perfect pairs, sites a greedy pruning at r2 > threshold[0] / threshold[1]
+        keeps, site_off, mean_r2), then with want_bins the decay counters [n_windows, n_bins] (LDBAND_BIN_DTYPE), then with
+        want_sites the site table as ONE flat array (LDBAND_SITE_DTYPE: coord, ld_score_fx, carriers, n_partners, n_strong, kept):
+        window w's rows are [site_off[w], site_off[w] + n_qualifying[w]).  The table is sized by a first call without one."""
+        w = make_windows(windows)
+        out = np.zeros(len(w), dtype=LDBAND_DTYPE)
+        prm = LdbandParams(C.sizeof(LdbandParams), int(min_mac), int(band_sites), int(n_bins), int(threshold[0]), int(threshold[1]),
+                           int(bin_width), int(max_dist), int(max_chunk_bytes))
+        kp, pp = _mask_ptr(mask_p, self.n_hap)
+        bins = np.zeros((len(w), max(int(n_bins), 0)), dtype=LDBAND_BIN_DTYPE) if want_bins else None
+
+        def call(table, capacity):
+            rows = C.c_uint64(0)
+            check(self.ctx._lib.impop_ldband_scan(self.ctx.handle, self.handle, w.ctypes.data_as(C.POINTER(Window)), len(w), pp, C.byref(prm),
+                                                  out.ctypes.data_as(C.POINTER(LdbandStats)),
+                                                  bins.ctypes.data_as(C.POINTER(LdbandBin)) if want_bins else None,
+                                                  table.ctypes.data_as(C.POINTER(LdbandSite)) if table is not None else None, capacity,
+                                                  C.byref(rows)))
+            return rows.value
+
+        table = None
+        if want_sites:
+            total = call(None, 0)
+            table = np.zeros(total, dtype=LDBAND_SITE_DTYPE)
+            if total and call(table, total) != total:
+                raise ImpopError("impop_ldband_scan: the site table's size changed between two calls")
+        else:
+            call(None, 0)
+        res = (out,) + ((bins,) if want_bins else ()) + ((table,) if want_sites else ())
         return res if len(res) > 1 else out
 
     def diploid_scan(self, windows, pairs, min_run: int, want_individuals: bool = False, max_chunk_bytes: int = 0):

@@ -999,6 +999,85 @@ int impop_recomb_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window 
 /* With impop_ctx_gram_timing on, impop_recomb_scan brackets its kernels per chunk: kernel_ms[0] = select, [1] = gather, [2] = pairs,
  * [3] = finish, summed since enable / reset; chunks = chunks timed. */
 int impop_ctx_recomb_elapsed(impop_ctx *ctx, double kernel_ms[4], uint64_t *chunks);
+#define IMPOP_LDBAND_MAX_N     4096u
+#define IMPOP_LDBAND_MAX_BAND  1024u
+#define IMPOP_LDBAND_MAX_BINS  4096u
+#define IMPOP_LDBAND_FX_ONE    1073741824u   /* 2^30 */
+/* Banded LD per window: r2 between every qualifying site and its next band_sites qualifying neighbours, with NO thinning, and from
+ * that one object the LD decay curve (mean r2 by distance bin), per-site LD scores (Bulik-Sullivan et al. 2015) and a greedy LD
+ * pruning of the sites.  Works on full, weighted and compacted matrices; site weights change n_sites only.  r2 is turned into a
+ * fixed-point integer, so every device output is an integer and a plain restatement agrees bit for bit.
+ * Members: P (mask_p; NULL = all), n = |P|.  A site of a window qualifies iff min(c, n - c) >= min_mac (impop_ld_scan's rule).
+ * All q qualifying sites of the window are used, indexed 0..q-1 in position order; coord_j is the ORIGINAL coordinate of site j.
+ * Band: the pair (j, k), j < k, is in the band iff k - j <= band_sites and (max_dist == 0 or coord_k - coord_j <= max_dist).
+ * Pairs never cross windows; windows may overlap and are independent.
+ * Pair arithmetic, rows masked by P: n11 = popcount(row_j & row_k)
+ *     num = n n11 - c_j c_k      den = c_j (n - c_j) c_k (n - c_k)                     (impop_ld_scan's, in int64)
+ *     r2 = (double)(num num) / (double)den      fx = (uint64_t)(r2 * 1073741824.0)     (0 <= fx <= IMPOP_LDBAND_FX_ONE)
+ *     perfect iff num num == den       strong iff num num thr_den > thr_num den        (uint64; both products < 2^60)
+ * Every quantity is invariant under flipping a site's alleles.
+ * Decay bin of a pair: d = coord_k - coord_j, bin = min(d / bin_width, n_bins - 1) by integer division.
+ * Pruning, greedy in position order (a fixed tie rule: the earlier site stays; no parity with PLINK's --indep-pairwise, which
+ * removes by allele frequency inside sliding windows, is claimed): kept_0 = 1; kept_j = 1 iff there is no i < j with (i, j) in the
+ * band, strong(i, j) and kept_i.  As a sliding window: K is a band_sites-bit register whose bit o-1 holds kept_{j-o}, strongmask_j
+ * has bit o-1 set iff (j-o, j) is in the band and strong; kept_j = ((strongmask_j & K) == 0), then K = (K << 1) | kept_j.
+ * Outputs: out_host[w] (n_pairs, sum_r2_fx, n_strong, n_perfect over the band pairs of the window; n_kept; site_off = the window's
+ * first row in the site table = the sum of n_qualifying of the windows before it; mean_r2 = (double)sum_r2_fx / ((double)n_pairs *
+ * 1073741824.0) on the host, NaN when n_pairs == 0).  bins (nullable, n_windows x n_bins): pairs, sum_r2_fx, n_strong of the band
+ * pairs per decay bin.  site_table (nullable): one row per qualifying site of every window, windows in order, sites in position
+ * order; ld_score_fx = the sum of fx over the site's band partners on BOTH sides, n_partners and n_strong count them likewise.
+ * Capacity: *n_site_rows (nullable) always receives the sum of q; with site_table NULL or site_capacity below that sum nothing is
+ * written to the table, the records and bins are filled all the same.
+ * IMPOP_E_INVALID before anything is launched: a wrong struct_size, |P| = 0, min_mac = 0, band_sites outside
+ * 1..IMPOP_LDBAND_MAX_BAND, n_bins outside 1..IMPOP_LDBAND_MAX_BINS, bin_width = 0, thr_den = 0, thr_den > 65535, thr_num > thr_den,
+ * a window outside the matrix.  IMPOP_E_UNSUPPORTED before anything is launched: |P| > IMPOP_LDBAND_MAX_N.  n_windows == 0 returns
+ * IMPOP_OK.  One refusal can only come AFTER the select pass, because q is not known before it: a single window whose q rows,
+ * strong masks and site rows, q (4 ceil(n_hap / 32) + 8 ceil(band_sites / 64) + 32) bytes, exceed max_chunk_bytes (0 = 1 GiB),
+ * or whose q band_sites >= 2^34, returns IMPOP_E_UNSUPPORTED with the numbers in the message.  The call counts q for every window
+ * first and refuses before the first record, bin or table row is written: nothing is partially written.
+ * Chunking, the LDS or global form of the decay counters (IMPOP_LDBAND_LDS_BINS=n lowers the bins the LDS form takes: a test aid),
+ * the upload's keep flags and compaction never change a byte.  Checks the device error word (set when the rows gathered for a
+ * window are not its q, when a window keeps more sites than it has, or when the site rows do not add up to twice the record).
+ * Known answer: haplotypes h0..h3, five sites as rows over (h0,h1,h2,h3) 1100, 1010, 1100, 0011, 1000, one window, min_mac 1,
+ * band_sites 4, max_dist 0, bin_width 2, n_bins 3, threshold 1/2.  r2: (0,2), (0,3), (2,3) give 1; (0,4), (1,4), (2,4), (3,4) give
+ * 4/12, fx 357913941; the other three 0.  n_pairs 10, sum_r2_fx 4652881236, n_perfect 3, n_strong 3; kept 1,1,0,0,1, n_kept 3;
+ * ld_score_fx 2505397589, 357913941, 2505397589, 2505397589, 1431655764; n_partners 4 each; bins (pairs, fx, strong)
+ * (4, 1431655765, 1), (5, 2863311530, 2), (1, 357913941, 0).
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_ldband_scan] route=<dense|compact> windows= chunks= launches= qualifying= pairs= band= bins=<lds|global|off> bytes_streamed=
+ * pairs = the sum of n_pairs; bins=off when bins is NULL; bytes_streamed = what the counting pass, the select and the gather
+ * kernels read of the matrix plus the gathered rows. */
+typedef struct impop_ldband_params {
+    uint32_t struct_size;
+    uint32_t min_mac;         /* >= 1 */
+    uint32_t band_sites;      /* 1 .. IMPOP_LDBAND_MAX_BAND */
+    uint32_t n_bins;          /* 1 .. IMPOP_LDBAND_MAX_BINS */
+    uint32_t thr_num;         /* strong iff r2 > thr_num / thr_den; thr_num <= thr_den */
+    uint32_t thr_den;         /* 1 .. 65535 */
+    uint64_t bin_width;       /* >= 1, in coordinate units */
+    uint64_t max_dist;        /* 0 = no distance limit */
+    uint64_t max_chunk_bytes; /* 0 = 1 GiB */
+} impop_ldband_params;
+typedef struct impop_ldband_stats { /* 64 bytes, fixed layout */
+    uint32_t n_members, n_sites, n_qualifying, n_kept;
+    uint64_t n_pairs, sum_r2_fx, n_strong, n_perfect, site_off;
+    double mean_r2;
+} impop_ldband_stats;
+typedef struct impop_ldband_bin { /* 24 bytes */
+    uint64_t pairs, sum_r2_fx, n_strong;
+} impop_ldband_bin;
+typedef struct impop_ldband_site { /* 32 bytes */
+    uint64_t coord, ld_score_fx;
+    uint32_t carriers, n_partners, n_strong, kept;
+} impop_ldband_site;
+int impop_ldband_scan(impop_ctx *ctx, const impop_matrix *m, const impop_window *windows, uint64_t n_windows, const uint64_t *mask_p,
+                      const impop_ldband_params *params, impop_ldband_stats *out_host,
+                      impop_ldband_bin *bins /* nullable, n_windows x n_bins */,
+                      impop_ldband_site *site_table /* nullable, site_capacity rows */, uint64_t site_capacity,
+                      uint64_t *n_site_rows /* nullable */);
+/* With impop_ctx_gram_timing on, impop_ldband_scan brackets its kernels per chunk: kernel_ms[0] = select (the counting pass
+ * included), [1] = rank + gather, [2] = pairs, [3] = prune, [4] = reduce, summed since enable / reset; chunks = chunks timed. */
+int impop_ctx_ldband_elapsed(impop_ctx *ctx, double kernel_ms[5], uint64_t *chunks);
 #define IMPOP_DIPLOID_MAX_N 2048u
 /* The individual level of a windowed scan: observed heterozygosity, Wright's F_IS and runs of homozygosity per window and per
  * diploid individual, from the site-major rows alone (no hap-major operand, no Gram; works on full, weighted and compacted
