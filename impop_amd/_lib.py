@@ -278,6 +278,28 @@ class IbsWindow(C.Structure):
                 ("reserved", C.c_uint32), ("share", C.c_double)]
 
 
+class PaintParams(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mismatch_cost", C.c_uint32), ("switch_cost", C.c_uint32), ("n_panels", C.c_uint32),
+                ("site_begin", C.c_uint64), ("site_end", C.c_uint64), ("site_switch_cost", C.POINTER(C.c_uint32)),
+                ("n_site_switch_cost", C.c_uint64), ("group", C.POINTER(C.c_uint32)), ("panel", C.POINTER(C.c_uint8)),
+                ("max_chunk_bytes", C.c_uint64)]
+
+
+class PaintRecipient(C.Structure):
+    _fields_ = [("h", C.c_uint32), ("n_donors", C.c_uint32), ("n_segments", C.c_uint32), ("n_mismatch", C.c_uint32),
+                ("distinct_donors", C.c_uint32), ("longest_sites", C.c_uint32), ("longest_donor", C.c_uint32), ("reserved", C.c_uint32),
+                ("cost", C.c_uint64)]
+
+
+class PaintSegment(C.Structure):
+    _fields_ = [("h", C.c_uint32), ("donor", C.c_uint32), ("begin", C.c_uint64), ("end", C.c_uint64), ("n_sites", C.c_uint32),
+                ("n_mismatch", C.c_uint32), ("recipient", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PaintWindow(C.Structure):
+    _fields_ = [("n_switches", C.c_uint64), ("n_mismatch", C.c_uint64), ("cells", C.c_uint64), ("copied", C.c_uint64 * 9)]
+
+
 class IbdParams(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("min_sites", C.c_uint32), ("site_begin", C.c_uint64), ("site_end", C.c_uint64),
                 ("min_seed", C.c_uint64), ("min_extend", C.c_uint64), ("min_output", C.c_uint64), ("max_gap", C.c_uint64),
@@ -383,6 +405,9 @@ assert C.sizeof(IbsParams) == 32 and C.sizeof(IbsPair) == 32 and C.sizeof(IbsSeg
 IBS_MAX_N, IBS_MAX_PAIRS, IBS_OPEN_LEFT, IBS_OPEN_RIGHT = 4096, 8388608, 1, 2
 assert C.sizeof(IbdParams) == 88 and C.sizeof(IbdPair) == 48 and C.sizeof(IbdSegment) == 48
 IBD_MAX_MAP = 1 << 22  # IMPOP_IBD_MAX_MAP
+assert C.sizeof(PaintParams) == 72 and C.sizeof(PaintRecipient) == 40 and C.sizeof(PaintSegment) == 40 and C.sizeof(PaintWindow) == 96
+# IMPOP_PAINT_MAX_DONORS, IMPOP_PAINT_MAX_RECIPIENTS, IMPOP_PAINT_MAX_PANELS, IMPOP_PAINT_MAX_COST, IMPOP_PAINT_NO_PANEL
+PAINT_MAX_DONORS, PAINT_MAX_RECIPIENTS, PAINT_MAX_PANELS, PAINT_MAX_COST, PAINT_NO_PANEL = 1024, 4096, 8, 1 << 20, 255
 assert C.sizeof(IhsParams) == 32 and C.sizeof(IhsCore) == 96
 IHS_SCAN_MAX_N = 4096
 assert C.sizeof(DstatStats) == 80 and C.sizeof(DstatParams) == 16
@@ -507,6 +532,10 @@ SIGNATURES = {
     "impop_ibd_scan": (C.c_int, [_vp, _vp, _u64p, _u32p, C.c_uint64, C.POINTER(Window), C.c_uint64, C.POINTER(IbdParams),
                                  C.POINTER(IbdPair), C.POINTER(IbdSegment), C.c_uint64, _u64p, C.POINTER(IbsWindow)]),
     "impop_ctx_ibd_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
+    "impop_paint_scan": (C.c_int, [_vp, _vp, _u64p, _u32p, C.c_uint32, C.POINTER(Window), C.c_uint64, C.POINTER(PaintParams),
+                                   C.POINTER(PaintRecipient), C.POINTER(PaintSegment), C.c_uint64, _u64p, _u32p, _u64p,
+                                   C.POINTER(PaintWindow), _u32p]),
+    "impop_ctx_paint_elapsed": (C.c_int, [_vp, _f64p, _u64p]),
     "impop_ihs_scan": (C.c_int, [_vp, _vp, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, _u64p, _u64p, C.POINTER(IhsParams),
                                  C.POINTER(IhsCore), C.c_uint64, _u64p]),
     "impop_ctx_ihs_elapsed": (C.c_int, [_vp, _f64p, _u64p]),

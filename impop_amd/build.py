@@ -14,7 +14,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libimpop_hip.so")
-SOURCES = ["context.hip", "layout.hip", "scan.hip", "stats.hip", "stats_small.hip", "pairdist.hip", "pca.hip", "tree.hip", "permtest.hip", "kinship.hip", "stats_batch.hip", "pairwise.hip", "pairwise_scan.hip", "simparse.hip", "ehh.hip", "hapscan.hip", "ldscan.hip", "recomb.hip", "ldband.hip", "diploid.hip", "ibs.hip", "ibd.hip", "ihs.hip", "dstat.hip", "sfs.hip", "multigpu.hip", "gfaparse.hip"]
+SOURCES = ["context.hip", "layout.hip", "scan.hip", "stats.hip", "stats_small.hip", "pairdist.hip", "pca.hip", "tree.hip", "permtest.hip", "kinship.hip", "stats_batch.hip", "pairwise.hip", "pairwise_scan.hip", "simparse.hip", "ehh.hip", "hapscan.hip", "ldscan.hip", "recomb.hip", "ldband.hip", "diploid.hip", "ibs.hip", "paint.hip", "ibd.hip", "ihs.hip", "dstat.hip", "sfs.hip", "multigpu.hip", "gfaparse.hip"]
 FLAGS = [
     "-O3", "-std=c++17", "-fPIC", "-shared", "--offload-arch=gfx950",
     "-ffp-contract=off",          # fp64 epilogues follow the reference's operation order exactly

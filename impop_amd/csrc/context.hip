@@ -253,7 +253,7 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
     const uint32_t w = ctx->h_err;
     ctx->h_err = 0;
     HIP_TRY(hipMemsetAsync(ctx->d_err, 0, sizeof(uint32_t), ctx->stream));
-    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s%s%s%s%s%s%s%s); the results of this call are invalid", fn, w,
+    set_error("%s: internal device check failed (code 0x%x%s%s%s%s%s%s%s%s%s%s%s%s%s%s); the results of this call are invalid", fn, w,
               (w & DEV_ERR_GROUPING) ? ": greedy grouping made no progress" : "",
               (w & DEV_ERR_CLUSTER) ? ": clustering ran out of rounds" : "",
               (w & DEV_ERR_EHH) ? ": EHH partition refinement is inconsistent" : "",
@@ -266,7 +266,8 @@ int ctx_err_result(impop_ctx *ctx, const char *fn) {
               (w & DEV_ERR_PERMTEST) ? ": permutation test's matrix-core sums of the observed labelling differ from the direct ones" : "",
               (w & DEV_ERR_IBD) ? ": IBD scan's count and fill passes disagree on a pair's segments" : "",
               (w & DEV_ERR_RECOMB) ? ": recombination scan gathered a different number of sites than it selected, or R_min is out of range" : "",
-              (w & DEV_ERR_LDBAND) ? ": banded LD scan gathered a different number of sites than it selected, or its site rows do not add up to its record" : "");
+              (w & DEV_ERR_LDBAND) ? ": banded LD scan gathered a different number of sites than it selected, or its site rows do not add up to its record" : "",
+              (w & DEV_ERR_PAINT) ? ": painting's path does not reproduce the forward pass's cost, or its count and emit passes disagree" : "");
     return IMPOP_E_INTERNAL;
 }
 }  // namespace impop

@@ -133,6 +133,22 @@ __device__ __forceinline__ uint32_t wave_sum_u32_dpp(uint32_t v) {
     v = dpp_add_u32<0x143, 0xC>(v);  // row_bcast:31
     return v;
 }
+// wave64 minimum in the VALU alone, the same six DPP steps: lanes 48..63 get the minimum.  A lane of a row that is not written
+// takes the identity 0xFFFFFFFF given as the old value.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t dpp_min_u32(uint32_t v) {
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)0xFFFFFFFFu, (int)v, CTRL, ROW_MASK, 0xF, false);
+    return o < v ? o : v;
+}
+__device__ __forceinline__ uint32_t wave_min_u32_dpp(uint32_t v) {
+    v = dpp_min_u32<0xB1, 0xF>(v);   // quad_perm:[1,0,3,2]
+    v = dpp_min_u32<0x4E, 0xF>(v);   // quad_perm:[2,3,0,1]
+    v = dpp_min_u32<0x141, 0xF>(v);  // row_half_mirror
+    v = dpp_min_u32<0x140, 0xF>(v);  // row_mirror
+    v = dpp_min_u32<0x142, 0xA>(v);  // row_bcast:15
+    v = dpp_min_u32<0x143, 0xC>(v);  // row_bcast:31
+    return v;
+}
 __device__ inline double wave_sum_f64(double v) {  // fixed butterfly order: deterministic
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);

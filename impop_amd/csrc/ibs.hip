@@ -30,6 +30,7 @@
 #include "dip_runs.h"
 #include "ibs_plan.h"
 #include "ibs_sweeps.h"
+#include "ibs_transpose.h"
 #include "internal.h"
 #include "scan_route.h"
 #include "win_chunks.h"
@@ -40,29 +41,7 @@ static_assert(sizeof(DipSummary) == 40, "summaries are stored as 40-byte records
 constexpr int IBS_T = 256;
 static_assert(IBS_T == (int)IBS_PAIRS, "one pair per lane");
 
-// grid = ceil(len / 4): wave = one 64-site block of the chunk.  ppos[h] = row of haplotype h or -1 (padding rows included),
-// pmask[k] = the rows of dword column k.  [cb, ce) = the range's columns: everything outside is written as 0.
-__global__ __launch_bounds__(256) void ibs_transpose_kernel(const uint32_t *__restrict__ sb, uint32_t wps, uint32_t G, uint32_t r,
-                                                            const int32_t *__restrict__ ppos, const uint32_t *__restrict__ pmask,
-                                                            uint64_t blk_abs0, uint64_t len, uint64_t cb, uint64_t ce, uint32_t stride,
-                                                            uint64_t *__restrict__ wm) {
-    const uint32_t lane = threadIdx.x & 63;
-    const uint64_t bi = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (bi >= len) return;  // wave-uniform
-    const uint64_t B = blk_abs0 + bi;
-    uint64_t edge = ~0ull;
-    if (B * 64 < cb) edge &= ~0ull << (cb - B * 64);
-    if (ce - B * 64 < 64) edge &= (1ull << (ce - B * 64)) - 1ull;
-    for (uint32_t k = 0; k < wps; ++k) {
-        const uint32_t pm = (uint32_t)__builtin_amdgcn_readfirstlane(pmask[k]);
-        if (pm == 0u) continue;
-        const uint64_t keep = ballot_transpose32(sb[sb_index(wps, G, r, B, lane, k)], lane) & edge;
-        if (lane < 32) {
-            const int32_t pp = ppos[32 * k + lane];
-            if (pp >= 0) wm[bi * stride + (uint32_t)pp] = keep;
-        }
-    }
-}
+// ibs_transpose_kernel: ibs_transpose.h
 
 struct IbsArgs {
     const uint64_t *wm;    // the chunk's words

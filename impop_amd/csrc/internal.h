@@ -178,7 +178,8 @@ struct impop_ctx {
         T_TREE = T_IBD + 4,  // impop_tree_scan: the tree kernel of every chunk (impop_ctx_tree_elapsed)
         T_RECOMB,            // impop_recomb_scan: select / gather / pairs / finish kernels (impop_ctx_recomb_elapsed)
         T_LDBAND = T_RECOMB + 4,  // impop_ldband_scan: select / rank + gather / pairs / prune / reduce kernels (impop_ctx_ldband_elapsed)
-        T_COUNT = T_LDBAND + 5
+        T_PAINT = T_LDBAND + 5,   // impop_paint_scan: transpose / forward / backtrack + emit / window kernels (impop_ctx_paint_elapsed)
+        T_COUNT = T_PAINT + 4
     };
     impop::EventPairs timers[T_COUNT];
     // side stream + fork/join events (created on first use): independent latency-bound epilogue kernels of the
@@ -307,6 +308,7 @@ constexpr uint32_t DEV_ERR_PERMTEST = 512u;         // permutation test: the mat
 constexpr uint32_t DEV_ERR_IBD = 1024u;             // IBD scan: the fill met a segment the count did not announce, or fewer than it announced
 constexpr uint32_t DEV_ERR_RECOMB = 2048u;         // recombination scan: a window's gathered rows are not its n_used, or rmin exceeds the sites that have an incompatible left neighbour
 constexpr uint32_t DEV_ERR_LDBAND = 4096u;         // banded LD scan: a window's gathered rows are not its q, it keeps more sites than it has, or its site rows do not add up to twice its record
+constexpr uint32_t DEV_ERR_PAINT = 8192u;          // painting: a path's recomputed cost is not the forward pass's, its segments do not tile the range, or the emit met a segment the count did not announce
 constexpr uint32_t DEV_ERR_EHH = 4u;                // ehh partition refinement ended with classes that do not account for the unbroken pairs
 int ctx_aux(impop_ctx *ctx, int slot, size_t bytes, void **out);
 // stats.hip: seed_rank -> order (inverse permutation) restricted to `members` (positions 0..m of the member list); ranks only need

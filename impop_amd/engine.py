@@ -12,7 +12,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (IDENTITY_DICE, IDENTITY_MATCH, KEEP_DENSE_SCAN, KEEP_HAP_MAJOR, KEEP_NO_RARE_SPLIT, KEEP_NO_SINGLE_STREAM, KEEP_NO_UNIQUE_ROWS, KEEP_SITE_BLOCKED, ImpopError, PairwiseParams,
-                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, RecombParams, RecombStats, RecombSite, LdbandParams, LdbandStats, LdbandBin, LdbandSite, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
+                   ClusterParams, ClusterStats, HaplotypeParams, HaplotypeStats, LdParams, LdStats, RecombParams, RecombStats, RecombSite, LdbandParams, LdbandStats, LdbandBin, LdbandSite, DiploidParams, DiploidStats, DiploidInd, IbsParams, IbsPair, IbsSegment, IbsWindow, IbdParams, IbdPair, IbdSegment, PaintParams, PaintRecipient, PaintSegment, PaintWindow, IhsParams, IhsCore, DstatParams, DstatStats, SfsParams, SfsStats, SfsPair, EhhParams, EhhStats, EhhWindow, PairwiseStats, ScanParams, SynthParams, Window, WindowStats, check)
 
 from .ihs import IHS_DTYPE  # noqa: E402
 
@@ -76,6 +76,12 @@ IBD_PAIR_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("n_segments", "<u4"), 
 IBD_SEGMENT_DTYPE = np.dtype([("h1", "<u4"), ("h2", "<u4"), ("begin", "<u8"), ("end", "<u8"), ("len", "<u8"), ("ibs_sites", "<u4"),
                               ("n_tracts", "<u4"), ("pair", "<u4"), ("flags", "<u4")])
 assert IBD_PAIR_DTYPE.itemsize == 48 and IBD_SEGMENT_DTYPE.itemsize == 48
+PAINT_RECIPIENT_DTYPE = np.dtype([("h", "<u4"), ("n_donors", "<u4"), ("n_segments", "<u4"), ("n_mismatch", "<u4"), ("distinct_donors", "<u4"),
+                                  ("longest_sites", "<u4"), ("longest_donor", "<u4"), ("reserved", "<u4"), ("cost", "<u8")])
+PAINT_SEGMENT_DTYPE = np.dtype([("h", "<u4"), ("donor", "<u4"), ("begin", "<u8"), ("end", "<u8"), ("n_sites", "<u4"), ("n_mismatch", "<u4"),
+                                ("recipient", "<u4"), ("reserved", "<u4")])
+PAINT_WINDOW_DTYPE = np.dtype([("n_switches", "<u8"), ("n_mismatch", "<u8"), ("cells", "<u8"), ("copied", "<u8", (9,))])
+assert PAINT_RECIPIENT_DTYPE.itemsize == 40 and PAINT_SEGMENT_DTYPE.itemsize == 40 and PAINT_WINDOW_DTYPE.itemsize == 96
 DSTAT_DTYPE = np.dtype([("n_sites", "<u4"), ("n_informative", "<u4"), ("n_skipped", "<u4"), ("flags", "<u4"), ("abba", "<i8"), ("baba", "<i8"),
                         ("f4_num", "<i8"), ("fd_den_p2", "<i8"), ("fd_den_p3", "<i8"), ("d", "<f8"), ("f4", "<f8"), ("fd", "<f8")])
 assert DSTAT_DTYPE.itemsize == 80
@@ -333,6 +339,13 @@ class Context:
         t, k = (C.c_double * 4)(), C.c_uint64(0)
         check(self._lib.impop_ctx_ibd_elapsed(self.handle, t, C.byref(k)))
         return [t[0], t[1], t[2], t[3]], int(k.value)
+
+    def paint_elapsed(self):
+        """-> ([transpose, forward, backtrack + emit, windows] kernel ms of paint_scan, site chunks the forward kernel ran) since
+        gram_timing(True)"""
+        t, k = (C.c_double * 4)(), C.c_uint64()
+        check(self._lib.impop_ctx_paint_elapsed(self.handle, t, C.byref(k)))
+        return list(t), k.value
 
     def ibs_elapsed(self):
         """-> ([transpose, walk, combine + close] kernel ms of ibs_scan, site chunks transposed) since gram_timing(True)"""
@@ -1128,6 +1141,65 @@ class BitMatrix:
             if total.value:
                 call(seg, len(seg))
         return rec, seg, win, int(total.value)
+
+    def paint_scan(self, recipients, donors=None, mismatch_cost: int = 1, switch_cost: int = 1, site_switch_cost=None, group=None,
+                   panel=None, n_panels: int = 0, site_begin: int = 0, site_end: Optional[int] = None, windows=None,
+                   want_segments: bool = True, want_chunks: bool = True, want_ancestry: bool = True, max_chunk_bytes: int = 0,
+                   seg_capacity: Optional[int] = None):
+        """Li-Stephens Viterbi mosaics (impop_paint_scan): every haplotype of `recipients` painted from the donors (a 0/1 or packed
+        mask over the haplotypes, None = all) other than those of its own group (group: uint32 per haplotype, None = every
+        haplotype its own group), with integer costs: mismatch_cost per differing site, switch_cost (or site_switch_cost[s], one
+        per stored site of the range) per change of donor.  panel: uint8 per haplotype (0 .. n_panels - 1, 255 = none).
+        -> dict(recipients=PAINT_RECIPIENT_DTYPE, segments=PAINT_SEGMENT_DTYPE or None, n_segments, chunk_counts / chunk_sites =
+        [n_rec, n_hap] or None, windows=PAINT_WINDOW_DTYPE or None, anc=[n_windows, n_rec, n_panels + 1] or None).  Segments: one
+        call without the list, then one with room; or, with seg_capacity given, one call (None when the list is longer)."""
+        rcp = np.ascontiguousarray(recipients, dtype=np.uint32).reshape(-1)
+        mk, mp = _mask_ptr(donors, self.n_hap)
+        w = None if windows is None else make_windows(windows)
+        csw = None if site_switch_cost is None else np.ascontiguousarray(site_switch_cost, dtype=np.uint32).reshape(-1)
+        grp = None if group is None else np.ascontiguousarray(group, dtype=np.uint32).reshape(-1)
+        pan = None if panel is None else np.ascontiguousarray(panel, dtype=np.uint8).reshape(-1)
+        for name, a in (("group", grp), ("panel", pan)):
+            if a is not None and len(a) != self.n_hap:
+                raise ValueError(f"{name} needs one entry per haplotype ({self.n_hap}), got {len(a)}")
+        prm = PaintParams(C.sizeof(PaintParams), int(mismatch_cost), int(switch_cost), int(n_panels), int(site_begin),
+                          0 if site_end is None else int(site_end), None if csw is None else csw.ctypes.data_as(C.POINTER(C.c_uint32)),
+                          0 if csw is None else len(csw), None if grp is None else grp.ctypes.data_as(C.POINTER(C.c_uint32)),
+                          None if pan is None else pan.ctypes.data_as(C.POINTER(C.c_uint8)), int(max_chunk_bytes))
+        n_rec = len(rcp)
+        rec = np.zeros(n_rec, dtype=PAINT_RECIPIENT_DTYPE)
+        cc = np.zeros((n_rec, self.n_hap), dtype=np.uint32) if want_chunks else None
+        cs = np.zeros((n_rec, self.n_hap), dtype=np.uint64) if want_chunks else None
+        win = None if w is None else np.zeros(len(w), dtype=PAINT_WINDOW_DTYPE)
+        anc = np.zeros((len(w), n_rec, int(n_panels) + 1), dtype=np.uint32) if w is not None and want_ancestry else None
+        total = C.c_uint64(0)
+
+        def call(seg, cap):
+            check(self.ctx._lib.impop_paint_scan(self.ctx.handle, self.handle, mp, rcp.ctypes.data_as(C.POINTER(C.c_uint32)), n_rec,
+                                                 None if w is None else w.ctypes.data_as(C.POINTER(Window)), 0 if w is None else len(w),
+                                                 C.byref(prm), rec.ctypes.data_as(C.POINTER(PaintRecipient)),
+                                                 None if seg is None else seg.ctypes.data_as(C.POINTER(PaintSegment)), cap, C.byref(total),
+                                                 None if cc is None else cc.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                 None if cs is None else cs.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                 None if win is None else win.ctypes.data_as(C.POINTER(PaintWindow)),
+                                                 None if anc is None else anc.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+        seg = None
+        if not want_segments:
+            call(None, 0)
+        elif seg_capacity is not None:
+            seg = np.zeros(int(seg_capacity), dtype=PAINT_SEGMENT_DTYPE)
+            call(seg, len(seg))
+            seg = seg[:total.value] if total.value <= len(seg) else None
+        else:
+            # every path has at most one segment per stored site; a first guess of 64 per recipient usually holds
+            seg = np.zeros(max(64 * n_rec, 1), dtype=PAINT_SEGMENT_DTYPE)
+            call(seg, len(seg))
+            if total.value > len(seg):
+                seg = np.zeros(total.value, dtype=PAINT_SEGMENT_DTYPE)
+                call(seg, len(seg))
+            seg = seg[:total.value]
+        return dict(recipients=rec, segments=seg, n_segments=int(total.value), chunk_counts=cc, chunk_sites=cs, windows=win, anc=anc)
 
     def ihs_scan(self, mask_a=None, mask_b=None, site_begin: int = 0, site_end: Optional[int] = None, core_begin: Optional[int] = None,
                  core_end: Optional[int] = None, min_mac: int = 1, cutoff_milli: int = 50, max_extend_bp: int = 0, max_extend_sites: int = 0,

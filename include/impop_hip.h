@@ -1289,6 +1289,112 @@ int impop_ibd_scan(impop_ctx *ctx, const impop_matrix *m,
 /* With impop_ctx_gram_timing on: kernel_ms[0] = transposes, [1] = walks, [2] = combine / close, [3] = the chain kernel (both
  * forms), summed since enable / reset; chunks = site chunks transposed. */
 int impop_ctx_ibd_elapsed(impop_ctx *ctx, double kernel_ms[4], uint64_t *chunks);
+#define IMPOP_PAINT_MAX_DONORS     1024u     /* admissible donors per recipient */
+#define IMPOP_PAINT_MAX_RECIPIENTS 4096u
+#define IMPOP_PAINT_MAX_PANELS     8u
+#define IMPOP_PAINT_MAX_COST       1048576u  /* 2^20: the largest switch cost */
+#define IMPOP_PAINT_NO_PANEL       255u
+/* Chromosome painting: every recipient haplotype as a mosaic of donor haplotypes, the Li & Stephens (2003) copying model read as
+ * a Viterbi path with integer costs (a min-plus recursion).  Every output is an integer; ties fall by the rules below.
+ * Inputs: the matrix m and the range [b, e) = [site_begin, site_end) as impop_ibs_scan; a donor mask mask_d over the haplotypes
+ * (NULL = all); n_rec recipient haplotypes, which may also be donors; optionally group[h] (uint32 per haplotype, NULL means
+ * group[h] = h) and panel[h] (uint8 per haplotype, 0 .. n_panels - 1, IMPOP_PAINT_NO_PANEL = no panel; n_panels <= 8).
+ * Admissible donors: donor j is admissible for recipient i iff j is in mask_d and group[j] != group[i].  So a haplotype never
+ * copies from itself, and with sample groups never from the other haplotype of its own individual.  Admissible donors are ordered
+ * by haplotype index.  Each recipient needs at least 1.
+ * Sites and coordinates: the sites s = 0 .. L-1 are the stored sites of the range; on a compacted matrix they are the kept sites
+ * and coord(s) is their original coordinate, as in impop_ibs_scan.  Site weights play no part.
+ * Costs: mu = mismatch_cost, 1 <= mu <= 65535.  c_s, the cost of changing donor between site s-1 and s (s >= 1), is the constant
+ * switch_cost or, with site_switch_cost non-NULL, site_switch_cost[s]: one uint32 per stored site of the range (n_site_switch_cost
+ * must be L), entry 0 ignored.  Every c_s lies in 0 .. IMPOP_PAINT_MAX_COST.
+ * Recursion, for recipient i over its admissible donors j:
+ *     V_j(0) = mu * [x_i(0) != x_j(0)]
+ *     M(s)   = min_j V_j(s)            A(s) = the LOWEST admissible j with V_j(s) = M(s)
+ *     stay_j(s) = ( V_j(s-1) <= M(s-1) + c_s )                    (a tie stays)
+ *     V_j(s) = mu * [x_i(s) != x_j(s)] + min( V_j(s-1), M(s-1) + c_s )
+ *     path:  d(L-1) = A(L-1);   d(s-1) = d(s) if stay_{d(s)}(s) else A(s-1)
+ *     cost = M(L-1)   (uint64)
+ * Segments: a segment is a maximal run [s0, s1) of constant d; adjacent segments always differ in donor.  begin = coord(s0), or b
+ * for the first segment; end = coord(s1), or e for the last, so a recipient's segments tile [b, e); n_sites = s1 - s0; n_mismatch
+ * = the sites of the run where recipient and donor differ.  The segment list is recipient-major, ascending.
+ * Segment capacity: as impop_ibs_scan.  *n_segments always receives the total; seg_out is written only when seg_capacity >= the
+ * total; every other output is filled either way.
+ * chunk_counts[n_rec][n_hap] (uint32) = the segments recipient r copies from haplotype h; chunk_sites[n_rec][n_hap] (uint64) = the
+ * sites of those segments (ChromoPainter's chunk-count and chunk-length matrices, with lengths in sites).
+ * Windows [wb, we), original coordinates, any list (overlapping, irregular, empty, outside the range): a site belongs to a window
+ * iff its coordinate lies in it.  A window record sums over all recipients: n_switches = the sites s >= 1 with d(s) != d(s-1),
+ * n_mismatch, cells = recipients x sites, copied[p] = the cells whose donor has panel p (slot 8: no panel).
+ * anc[n_windows][n_rec][n_panels + 1] (uint32) = the same split per recipient, slot n_panels = no panel: the local-ancestry table.
+ * Known answers: h0 = 000000000100, h1 = 000000111111, h2 = 111111000000, h3 = 111111111011 (site 0 first), recipient h0, donors
+ * {1, 2, 3}, dense, range [0, 12).  mu 1, c 2: cost 3, n_mismatch 1, segments h1 [0,6), h2 [6,12).  mu 3, c 1: cost 3, n_mismatch
+ * 0, h1 [0,6), h2 [6,9), h1 [9,10), h2 [10,12).  mu 1, c 5: cost 5, n_mismatch 5, h1 [0,12).  With every donor identical to the
+ * recipient: one segment from the lowest admissible donor, cost 0.
+ * What it is not: it is not the posterior (forward-backward) painting; it has no stay-probability term beyond what the caller
+ * folds into c_s; no parity with ChromoPainter's output is claimed: this definition is the contract.
+ * IMPOP_E_INVALID: a wrong struct_size, an empty or out-of-matrix range (or one of 2^32 sites or more, or, on a compacted matrix,
+ * one without a kept site), n_rec == 0, a recipient index out of range or repeated, a recipient without an admissible donor, mu
+ * or a switch cost outside its range, n_site_switch_cost != L, n_panels > 0 without panel or a panel value that is neither
+ * < n_panels nor 255, windows / win_out / anc_out nullness that does not go together.  IMPOP_E_UNSUPPORTED: more than
+ * IMPOP_PAINT_MAX_DONORS admissible donors of a recipient, n_rec > IMPOP_PAINT_MAX_RECIPIENTS, n_panels > IMPOP_PAINT_MAX_PANELS.
+ * All before anything is uploaded or launched.
+ * Cost: O(recipients x donors x sites), serial along the sites.  One wave holds a recipient's states in registers; per site it
+ * writes 8 bytes (A(s) and the site where that state's segment began), from which the path falls out in one jump per segment.
+ * Recipients run in ranges whose per-site records fit half of max_chunk_bytes (0 = 1 GiB), the sites in chunks of 64-site blocks
+ * whose transposed words fit the other half; IMPOP_PAINT_CHUNK_BLOCKS=n (1..4096) sets the chunk length (test aid).  Records never
+ * change with either.  The emit pass recomputes mu * n_mismatch + the switch costs of every path from the words; where that is not
+ * the forward pass's cost, a recipient's n_sites do not sum to L or a segment was not announced by the count, the device error
+ * word is set, nothing unannounced is written and the call returns IMPOP_E_INTERNAL.
+ * Under IMPOP_TRACE=1 the call prints one line on stderr:
+ *   [impop_paint_scan] route=<dense|compact> recipients= donors= sites= site_chunks= recipient_ranges= segments= launches= bytes_streamed=
+ * (donors: the members of mask_d; site_chunks: chunks transposed, all passes; bytes_streamed: rows read by the transposes plus
+ * words read by the forward kernel). */
+typedef struct impop_paint_params {      /* 72 bytes */
+    uint32_t struct_size;
+    uint32_t mismatch_cost;              /* mu, 1 .. 65535 */
+    uint32_t switch_cost;                /* c, 0 .. IMPOP_PAINT_MAX_COST; ignored when site_switch_cost is given */
+    uint32_t n_panels;                   /* 0 .. IMPOP_PAINT_MAX_PANELS */
+    uint64_t site_begin, site_end;       /* the range, ORIGINAL site coordinates; site_end == 0: the matrix's end */
+    const uint32_t *site_switch_cost;    /* nullable: c_s per stored site of the range */
+    uint64_t n_site_switch_cost;         /* its stated length: must be L */
+    const uint32_t *group;               /* nullable: n_hap entries */
+    const uint8_t *panel;                /* nullable: n_hap entries */
+    uint64_t max_chunk_bytes;            /* 0 = 1 GiB */
+} impop_paint_params;
+typedef struct impop_paint_recipient {   /* 40 bytes, fixed layout, one per recipient, in the caller's order */
+    uint32_t h;
+    uint32_t n_donors;                   /* admissible donors */
+    uint32_t n_segments;
+    uint32_t n_mismatch;
+    uint32_t distinct_donors;
+    uint32_t longest_sites;              /* the longest segment's n_sites (the first of equals) */
+    uint32_t longest_donor;              /* and its donor */
+    uint32_t reserved;
+    uint64_t cost;                       /* M(L-1) */
+} impop_paint_recipient;
+typedef struct impop_paint_segment {     /* 40 bytes, fixed layout */
+    uint32_t h, donor;                   /* recipient and donor haplotype */
+    uint64_t begin, end;                 /* [begin, end), ORIGINAL coordinates */
+    uint32_t n_sites, n_mismatch;
+    uint32_t recipient;                  /* index into the recipient list */
+    uint32_t reserved;
+} impop_paint_segment;
+typedef struct impop_paint_window {      /* 96 bytes, fixed layout, one per window */
+    uint64_t n_switches, n_mismatch, cells;
+    uint64_t copied[9];                  /* cells by the donor's panel; slot 8 = no panel */
+} impop_paint_window;
+int impop_paint_scan(impop_ctx *ctx, const impop_matrix *m,
+                     const uint64_t *mask_d,                       /* donors; NULL = all haplotypes */
+                     const uint32_t *recipients, uint32_t n_rec,
+                     const impop_window *windows, uint64_t n_windows,   /* nullable */
+                     const impop_paint_params *params,
+                     impop_paint_recipient *rec_out,               /* nullable */
+                     impop_paint_segment *seg_out, uint64_t seg_capacity, uint64_t *n_segments,
+                     uint32_t *chunk_counts, uint64_t *chunk_sites,   /* nullable, n_rec x n_hap each */
+                     impop_paint_window *win_out,                  /* nullable; needs windows */
+                     uint32_t *anc_out);                           /* nullable; needs windows */
+/* With impop_ctx_gram_timing on: kernel_ms[0] = transposes, [1] = the forward kernel, [2] = backtrack (count + emit), mismatch and
+ * record kernels, [3] = the window kernel, summed since enable / reset; chunks = site chunks the forward kernel ran. */
+int impop_ctx_paint_elapsed(impop_ctx *ctx, double kernel_ms[4], uint64_t *chunks);
 #define IMPOP_DSTAT_GROUP 3u   /* quartets whose sums one streaming launch of impop_dstat_scan keeps in registers */
 #define IMPOP_DSTAT_MAX_QUARTETS 64u
 /* Introgression statistics per window and quartet of populations (P1, P2, P3, O): Patterson's D (ABBA-BABA), f4 and Martin's f_d,
